@@ -27,6 +27,9 @@ Device clocks: the device ramps its clocks over the first ~20 ms of load, so a 2
 step) and not the sweep (80 us).  The W + K region is therefore run twice: from cold clocks first (`cold_clocks` in the JSON
 line), then again after `--device-warmup-ms` (default 30) of untimed sweeps -- `value` is the second run.
 
+Outputs: `--dump-outputs DIR` writes what the last timed step computed (DIR/<name>.npy, float64, at most DUMP_LIMIT bytes) so that
+two builds can be compared output for output; the inputs are seeded, so the same arguments give the same inputs on every run.
+
 Other workloads (`--workload c3|c4|c5|hbm`) are measurement aids for DESIGN.md, not the contract line.
 """
 import argparse
@@ -233,7 +236,13 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--device-warmup-ms", type=float, default=30.0,
                     help="untimed sweeps before the W + K region so that it runs at ramped device clocks (0: off; the cold run is reported either way)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (defect, Phi, ... as [row][segment] float64) to DIR/<name>.npy; above "
+                         "DUMP_LIMIT bytes a fixed, seeded sample of the segments (DIR/segments.npy holds their indices)")
+    a = ap.parse_args()
+    if a.dump_outputs and a.workload == "newton":
+        ap.error("--dump-outputs: the newton workload times whole iterations and has no sweep outputs to write")
+    return a
 
 
 def cpu_baseline(workload, seconds, threads=1, ndim=12, reference_algorithm=False):
@@ -1197,6 +1206,50 @@ def emit(out, a):
     return 1 if (bad and a.strict) else 0
 
 
+DUMP_LIMIT = 64 * 10**6    # --dump-outputs: bytes written at most (64 MB), .npy headers included
+DUMP_SEED = 20260901       # the segment sample of outputs larger than that: the same on every run and every build
+
+
+def dump_columns(S, rows):
+    """Segments --dump-outputs writes when each of S segments has `rows` float64 outputs: None = all of them if they fit DUMP_LIMIT,
+    else a fixed, seeded sample in increasing order (its index array, one float64 per segment, and the headers counted)."""
+    room = DUMP_LIMIT - 4096           # .npy headers: 128 bytes per file
+    if 8 * rows * S <= room:
+        return None
+    m = room // (8 * (rows + 1))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(S, m, replace=False))
+
+
+def snapshot_outputs(w, torch, dbuf, gathered=None):
+    """--dump-outputs: device copies of the arrays the last timed step handed its caller -- the defect buffer it wrote, the
+    workload's other outputs (rewritten by every step), the gathered defect vector at N > 1 -- as [row][segment], reduced to
+    dump_columns()' sample of the segments when they are larger than DUMP_LIMIT."""
+    S = w.S
+    outs = {"defect": dbuf}
+    if w.wl in ("c2", "hbm", "c4", "c5_stm"):
+        outs["Phi"] = w.Phi
+    for k in ("Jac", "dtf", "errs"):
+        if k in w.extra:
+            outs[k] = w.extra[k]
+    if gathered is not None:
+        outs["defect_gathered"] = gathered
+    if w.blocks:             # one record per segment, [segment][row]
+        outs["defect"], outs["Phi"] = (outs[k].reshape(S, -1).T for k in ("defect", "Phi"))
+    cols = dump_columns(S, sum(v.numel() // S for v in outs.values()))
+    if cols is None:
+        return {k: v.clone(memory_format=torch.contiguous_format) for k, v in outs.items()}
+    idx = torch.from_numpy(cols).to(dbuf.device)
+    snap = {k: v.index_select(-1, idx) for k, v in outs.items()}
+    snap["segments"] = torch.from_numpy(cols.astype(np.float64))
+    return snap
+
+
+def write_outputs(d, snap):
+    os.makedirs(d, exist_ok=True)
+    for k, v in snap.items():
+        np.save(os.path.join(d, k + ".npy"), v.cpu().numpy().astype(np.float64, copy=False))
+
+
 def self_launch(a):
     """`bench.py --gpus N` without a launcher: start the contract's launcher as a CHILD process -- before anything in this process
     has touched the GPU (replacing a process that has initialised HIP takes the node down) -- and leave with its exit code.  Its
@@ -1553,6 +1606,10 @@ def main():
         plan.rebalance(stream=st)                      # lanes ordered by the warm-up sweep's step counts (on device)
         rebalanced = True
     elapsed = timed_leg()
+    dumped = None
+    if a.dump_outputs and rank == 0:     # before anything below launches the sweep again
+        last = (a.steps - 1) % len(dbufs)
+        dumped = snapshot_outputs(w, torch, dbufs[last], gathered[last] if use_coll else None)
     kern_ms, burst_n, samples = sample_launches(torch, lambda: sweep(dbufs[0]))   # separate pass: the dominant kernel alone
 
     if use_coll:
@@ -1704,6 +1761,8 @@ def main():
                     optional(name + "_parity", leg[1])
         if leg_errors:
             out["leg_errors"] = leg_errors
+        if dumped is not None:
+            write_outputs(a.dump_outputs, dumped)
         exit_code = emit(out, a)
     if use_coll:
         dist.barrier()              # nobody unmaps a window a peer may still be pushing into

@@ -1,6 +1,6 @@
 """bench.py's bookkeeping, checked without a GPU: which stored counter profile a roofline object quotes (an
 8 192-segment line quoted the 4 096-segment profile), the BASELINE sizes of the workloads, the work model's consistency with
-SURVEY 8d, and that every compact config leg names a workload bench.py knows."""
+SURVEY 8d, that every compact config leg names a workload bench.py knows, and what --dump-outputs writes."""
 import importlib.util
 import json
 import os
@@ -190,3 +190,45 @@ def test_optional_legs_that_raise_or_run_out_of_time_do_not_cost_the_headline():
     long_form["configs"]["hbm"] = {"error": "skipped: --time-budget 240 s used up"}
     line = bench.compact_line(long_form)
     assert line["ok"] is True and "failed" not in line and line["skipped"] == ["hbm"]
+
+
+def test_dump_outputs_writes_every_segment_or_one_fixed_sample_within_the_limit():
+    """--dump-outputs: the contract size (14-dim defect + 14x14 STM, 4 096 segments) is written whole; the HBM point's outputs
+    (12 + 144 rows x 1 048 576 segments, 1.3 GB) shrink to a seeded sample of segments, the same on every call, inside DUMP_LIMIT."""
+    import numpy as np
+    assert bench.DUMP_LIMIT == 64 * 10**6
+    assert bench.dump_columns(4096, 14 + 196) is None
+    cols = bench.dump_columns(bench.HBM_SEGMENTS, 12 + 144)
+    assert np.array_equal(cols, bench.dump_columns(bench.HBM_SEGMENTS, 12 + 144))
+    assert np.all(np.diff(cols) > 0) and 0 <= cols[0] and cols[-1] < bench.HBM_SEGMENTS
+    assert len(cols) > 50000 and 8 * (12 + 144 + 1) * len(cols) + 3 * 128 <= bench.DUMP_LIMIT
+
+
+def test_dump_outputs_are_row_by_segment_in_every_layout(tmp_path, monkeypatch):
+    """What --dump-outputs writes, on host tensors: [row][segment] float64 for the plain and the per-segment (blocks) layout, and the
+    sampled columns with their indices once the outputs exceed DUMP_LIMIT."""
+    import types
+    import numpy as np
+    import torch
+    S, nd = 6, 3
+    defect = torch.arange(nd * S, dtype=torch.float64).reshape(nd, S)
+    Phi = 1000.0 + torch.arange(nd * nd * S, dtype=torch.float64).reshape(nd * nd, S)
+    w = types.SimpleNamespace(S=S, wl="c2", Phi=Phi, extra={}, blocks=False)
+    bench.write_outputs(str(tmp_path / "plain"), bench.snapshot_outputs(w, torch, defect))
+    assert sorted(os.listdir(tmp_path / "plain")) == ["Phi.npy", "defect.npy"]
+    for name, want in (("defect", defect), ("Phi", Phi)):
+        got = np.load(tmp_path / "plain" / (name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, want.numpy())
+    # blocks layout: the same buffers hold one record per segment
+    w.blocks, w.wl = True, "c5_stm"
+    snap = bench.snapshot_outputs(w, torch, defect)
+    assert np.array_equal(snap["defect"].numpy(), defect.reshape(S, nd).T.numpy())
+    assert np.array_equal(snap["Phi"].numpy(), Phi.reshape(S, nd * nd).T.numpy())
+    # over the limit: room for exactly two segments of (3 + 9) rows and their index
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096 + 2 * 8 * (nd + nd * nd + 1))
+    w.blocks, w.wl = False, "c2"
+    bench.write_outputs(str(tmp_path / "sample"), bench.snapshot_outputs(w, torch, defect))
+    seg = np.load(tmp_path / "sample" / "segments.npy")
+    assert seg.dtype == np.float64 and len(seg) == 2 and np.all(np.diff(seg) > 0)
+    assert np.array_equal(np.load(tmp_path / "sample" / "Phi.npy"), Phi.numpy()[:, seg.astype(int)])
+    assert np.array_equal(np.load(tmp_path / "sample" / "defect.npy"), defect.numpy()[:, seg.astype(int)])

@@ -111,3 +111,32 @@ def test_bench_headline_survives_a_spent_time_budget():
     assert out["ok"] is True and out["value"] > 1e7 and out["roofline"]["frac"] > 0.2 and out["cpu_baseline"]["value"] > 0 and out["parity"]["ok"] is True
     assert set(out["skipped"]) >= {"ref12", "refint", "host_api", "newton", "c1", "c3", "c4", "c5", "c5_stm", "hbm"}
     assert all(leg["ok"] is None for leg in out["configs"].values()) and "ref12" not in out and "newton_us" not in out
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_steps_results(oracle, tmp_path):
+    """`--dump-outputs DIR`: after exactly --steps timed steps the contract sweep's defect [14 x 4 096] and STM [196 x 4 096] land in
+    DIR as float64, and they are the sweep of bench.py's seeded inputs -- equal to the oracle on its 256-segment sample."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import torch
+    from lowthrustopt_amd import synth
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    d = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                        "--time-budget", "0", "--live-traffic", "off", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert sorted(os.listdir(d)) == ["Phi.npy", "defect.npy"]
+    defect, Phi = np.load(d / "defect.npy"), np.load(d / "Phi.npy")
+    assert defect.shape == (14, 4096) and Phi.shape == (196, 4096) and defect.dtype == Phi.dtype == np.float64
+    assert np.all(np.isfinite(defect)) and np.all(np.isfinite(Phi))
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    XC, T = synth.indirect_problem(4097, seed=0)
+    par = bench.parity_vs_oracle(14, bench.to14(XC), T, torch.from_numpy(defect), torch.from_numpy(Phi), 4096)
+    assert par["oracle_rc"] == 0 and par["defect_rel_l2"] < 1e-10 and par["stm_rel_max"] < 1e-10, par
