@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""Earth-Moon L2 halo -> halo transfer by DIRECT multiple shooting, on the GPU.
+
+Follows the direct demo of the reference (CRTBP_Multishoot_direct_demo.jl:183-196): the stacked halo guess (the stacking of
+halo_transfer_demo.py: tau1 = 0.75, 30 nodes over 20 days), zero thrust, nsteps = 10, Isp = 2000 s, mass = 1000 kg,
+flagEnd = false, beta = 0, no impulses, at most 100 iterations.  The whole loop -- Jacobian sweep, the minimum-energy QP step
+solved exactly on the device, the batched line search -- is one lto_direct_solve call.  With --then-indirect the smoothed
+states are handed to the indirect method (p = 2, adjoints only first), the reference's sequence.
+"""
+import importlib.util
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import lowthrustopt_amd as lto  # noqa: E402
+from lowthrustopt_amd import drivers, synth  # noqa: E402
+from lowthrustopt_amd.constants import MU, DU, TU  # noqa: E402
+
+
+def _stacking():
+    spec = importlib.util.spec_from_file_location("halo_transfer_demo", os.path.join(ROOT, "examples", "halo_transfer_demo.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def demo_problem(n_nodes=30, tof_days=20.0, tau1=0.75):
+    """(X_all [6 x n], u_all [3 x n], t_TU, tau1, tau2, X0_times, X0_states, Xf_times, Xf_states): the stacked guess and the two
+    orbit tables on normalised times LinRange(0, 1, 100) (demo :68-71).  tau2 = the phase of orbit 2 the stacking joins."""
+    X, t = _stacking().stacked_guess(n_nodes, tof_days, tau1)
+    tabs = synth.halo_orbits()
+    times = [np.linspace(0.0, 1.0, tb.shape[1]) for tb in tabs]
+    # phase of the guess's last node on orbit 2 (find_tau, demo :151): nearest table sample, refined on a fine grid
+    taus = np.linspace(0.0, 1.0, 20001)
+    d = np.linalg.norm(synth.halo_state(1, taus * 99 * synth.HALO_DT[1]) - X[:, -1:], axis=0)
+    tau2 = float(taus[np.argmin(d)])
+    U = np.zeros((3, n_nodes))
+    return X, U, t, tau1, tau2, times[0], tabs[0], times[1], tabs[1]
+
+
+def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100):
+    ctx = lto.default_context(0)
+    X, U, t, tau1, tau2, t0s, X0s, tfs, Xfs = demo_problem()
+    n, nsteps, Isp, mass = X.shape[1], 10, 2000.0, 1000.0
+    ops = drivers.HipDirectOps(MU, DU, TU, Isp, ctx) if python_loop else None
+    t0 = time.perf_counter()
+    X, U, tau1, tau2, t, dV1, dV2, defect = drivers.multiShoot_CRTBP_direct(
+        X, U, tau1, tau2, t, np.zeros(3), np.zeros(3), MU, DU, TU, n, nsteps, mass, Isp, t0s, X0s, tfs, Xfs, False, False, 0.0,
+        False, maxIter, ops=ops, verbose=verbose)
+    last = drivers.multiShoot_CRTBP_direct.last
+    res = {"direct": (last["status"], last["iterations"], float(np.abs(defect).max())), "X": X, "U": U}
+    print("direct: status %d after %d iterations, max defect %.2e, max thrust %.3f N (%.2f s)" % (
+        last["status"], last["iterations"], np.abs(defect).max(), np.linalg.norm(U, axis=0).max(), time.perf_counter() - t0))
+    if then_indirect and last["status"] == 0:
+        rng = np.random.default_rng(0)
+        XC = np.vstack([X, 0.1 * rng.standard_normal((6, n))])
+        XC, d, flag = drivers.multiShoot_CRTBP_indirect(XC, t, MU, DU, TU, n, mass, 10.0, False, True, 10, 2.0, 1.0, verbose=verbose)
+        XC, d, flag = drivers.multiShoot_CRTBP_indirect(XC, t, MU, DU, TU, n, mass, 10.0, False, False, 50, 2.0, 1.0, verbose=verbose)
+        print("indirect p = 2 from the direct solution: status %d, max defect %.2e" % (flag, np.abs(d).max()))
+        res["indirect"] = (flag, float(np.abs(d).max()))
+    return res
+
+
+if __name__ == "__main__":
+    main(verbose="-q" not in sys.argv, then_indirect="--then-indirect" in sys.argv, python_loop="--python-loop" in sys.argv)

@@ -44,6 +44,7 @@ extern "C" {
 #define LTO_EBADP 2           /* reference: error("Invalid value of p!") stateCostate_deriv.jl:52 */
 #define LTO_ENODEVICE 3       /* no usable gfx950 device                                         */
 #define LTO_ENOMEM 4          /* host memory (or a host thread) could not be had inside a call   */
+#define LTO_ESINGULAR 5       /* lto_direct_qp_step: a trajectory's KKT system is singular (its outputs are NaN) */
 
 /* Integrators.  RK4 = GeneralCode/ode.jl:21-73; RKF78_FIXED = ode7_8, ode.jl:773-953 (the direct
  * path's integrator); RKF78_ADAPTIVE = ode78, ode.jl:364-544; DOP853_ADAPTIVE = order-8 adaptive pair
@@ -223,6 +224,44 @@ int lto_direct_jacobian(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, cons
                         const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm, double* Jac_temp,
                         double* ddefect_dtf, double* defect, double* errors);
 
+/* ---- Direct multiple shooting: the QP step and the loop of multiShoot_CRTBP_direct (src/multiShoot_CRTBP_direct.jl:477-594)
+ * for the reference demo's setting (CRTBP_Multishoot_direct_demo.jl:183-193): flagEnd = false, beta = 0, tf fixed (tf_jump = 0,
+ * :292).  optimizeTraj (:248-403) is then a convex QP with equality constraints only,
+ *   min  sum_k w_k |u_k + du_k|^2 + (DU/TU)^2 (|dV1 + d1|^2 + |dV2 + d2|^2)      w_k = trapezoid weights of t (:323-326)
+ *   s.t. Jac_i [dx_i; dx_{i+1}; du_i; du_{i+1}] = -defect_i                         (:337)
+ *        x_0[0:6] + dx_0[0:6] + [0; dV1 + d1] = s0,  x_{n-1}[0:6] + dx_{n-1}[0:6] + [0; dV2 + d2] = sf   (:370-375)
+ *        x_0[6] + dx_0[6] = mass (nstate 7, :269-271);  d1 = d2 = 0 unless allow_impulsive (:298-302),
+ * solved on the device exactly (its KKT system as a block-bidiagonal BVP, structured orthogonal cyclic reduction).
+ * Per-trajectory targets: the interpolated end states (interpEndStates, :434-461), the initial mass and the current impulses. */
+typedef struct lto_direct_targets {
+  double s0[6], sf[6], mass, dV1[3], dV2[3];
+} lto_direct_targets;
+/* One Jacobian sweep (lto_direct_jacobian) and one QP step.  Host arrays as lto_direct_jacobian; targets [n_targets] with
+ * n_targets = 1 or n_batch.  Outputs: dX [nstate x n_nodes x n_batch], dU [3 x n_nodes x n_batch] (N), dV [6 x n_batch] (the
+ * impulse updates d1; d2 -- zero unless allow_impulsive), cost [n_batch] (the QP objective at the step).  A singular KKT system
+ * (e.g. too few nodes to reach the terminal state) returns LTO_ESINGULAR with that trajectory's outputs NaN. */
+int lto_direct_qp_step(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
+                       int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets, int n_targets,
+                       int allow_impulsive, double* dX, double* dU, double* dV, double* cost);
+/* The loop of multiShoot_CRTBP_direct (:477-594) with the trajectories resident in HBM: defect sweep, then while
+ * max|defect| > 1e-6 (:491): Jacobian sweep, QP step, line search over LinRange(0.1, 1, 10) after iteration 10 (:557-560, the ten
+ * trial points of every trajectory in ONE batched defect sweep), update of X, U, dV1, dV2 (:562-569), t recomputed through tau
+ * (:582), defect sweep.  Only scalars cross the link inside the loop; finished trajectories are frozen with a zero step.
+ *   X_in/X_out [nstate x n_nodes x n_batch], U_in/U_out [3 x n_nodes x n_batch], t [n_nodes x n_tgrids], targets [n_targets]
+ *   (1 or n_batch); dV_out [6 x n_batch] (final dV1; dV2), t_out [n_nodes x n_batch], defect_out [nstate x (n_nodes-1) x n_batch]
+ *   (all outputs but X_out and status may be NULL); history [3 x maxIter x n_batch] = (max|defect|, cost, alpha) per iteration.
+ *   status [n_batch]: 0 converged, 1 maxIter reached, 2 NaN, 3 singular KKT system.  The reference prints and returns; the flags
+ *   extend it with the indirect driver's convention (lto_indirect_solve). */
+int lto_direct_solve_batch(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
+                           const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
+                           const lto_direct_targets* targets, int n_targets, int allow_impulsive, int maxIter, double* X_out,
+                           double* U_out, double* dV_out, double* t_out, double* defect_out, int* status, int* iterations,
+                           double* history);
+int lto_direct_solve(lto_ctx* ctx, int nstate, int n_nodes, const double* X_in, const double* U_in, const double* t, int nsteps,
+                     const lto_direct_params* prm, const lto_direct_targets* targets, int allow_impulsive, int maxIter,
+                     double* X_out, double* U_out, double* dV_out, double* t_out, double* defect_out, int* status,
+                     int* iterations, double* history);
+
 /* ------------------------------------------------- device-resident API (operands already in HBM)
  * Struct-of-arrays, segment/node index fastest, so that a wavefront's 64 lanes read 512
  * contiguous bytes per component.  With J = n_nodes*n_batch nodes and S = (n_nodes-1)*n_batch
@@ -377,6 +416,17 @@ int lto_indirect_plan_last_kernel(const lto_indirect_plan* plan);
  * stage evaluations once and sends the columns through the four stage matrices; 0 chooses it for such plans from 65 536 segments.
  * One kernel per dimension whatever the batch's control laws (the law is chosen per trajectory at run time; round 6). */
 int lto_indirect_plan_set_cols_per_lane(lto_indirect_plan* plan, int cols);
+
+/* QP step of the direct method on the device (see lto_direct_qp_step), operands in the SoA layouts above: Jac / defect as
+ * lto_direct_jacobian_dev leaves them, X, U, t the point they were taken at, targets a DEVICE array of n_batch
+ * lto_direct_targets.  dX [nstate][ldx], dU [3][ldu] (node-indexed), dV [n_batch][6], cost [n_batch] (device).  The workspace
+ * (rows and records of the reduction, ~1.5 KB per segment and level-0 row) is allocated by the plan at its first step and kept.
+ * lto_direct_plan_qp_status: device int [n_batch] of the plan's last step, 1 = singular KKT system (outputs NaN), else 0. */
+int lto_direct_qp_step_dev(lto_direct_plan* plan, void* stream, const double* Jac, long ldj, const double* defect, long ldd,
+                           const double* X, long ldx, const double* U, long ldu, const double* t, int n_tgrids,
+                           const lto_direct_targets* targets, int allow_impulsive, double* dX, double* dU, double* dV,
+                           double* cost);
+const int* lto_direct_plan_qp_status(const lto_direct_plan* plan);
 
 /* Newton step of the indirect method solved on the device: delta = -Jac_full \ defect for the block-bidiagonal
  * [Phi_i | -I] system with both end states fixed (src/multiShoot_CRTBP_indirect.jl:123-142, :181-182), by structured

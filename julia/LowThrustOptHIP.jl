@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_qp_step, direct_solve, LtoDirectTargets, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
 const liblto = get(ENV, "LTO_HIP_LIB", joinpath(@__DIR__, "..", "lowthrustopt_amd", "liblto_hip.so"))
 
@@ -53,6 +53,13 @@ LtoParams(t::Tuple) = LtoParams(map(Float64, t)...)
 struct LtoDirectParams
     MU::Cdouble; DU::Cdouble; TU::Cdouble; Isp::Cdouble
 end
+
+# per-trajectory targets of the direct QP step (lto_direct_targets): interpolated end states, initial mass, current impulses
+struct LtoDirectTargets
+    s0::NTuple{6,Cdouble}; sf::NTuple{6,Cdouble}; mass::Cdouble; dV1::NTuple{3,Cdouble}; dV2::NTuple{3,Cdouble}
+end
+LtoDirectTargets(s0, sf, mass, dV1, dV2) = LtoDirectTargets(NTuple{6,Cdouble}(s0), NTuple{6,Cdouble}(sf), Cdouble(mass),
+                                                            NTuple{3,Cdouble}(dV1), NTuple{3,Cdouble}(dV2))
 
 mutable struct LtoContext
     handle::Ptr{Cvoid}
@@ -287,6 +294,40 @@ function direct_jacobianCalc(ctx::LtoHandle, X_all::Matrix{Float64}, u_all::Matr
 end
 
 # ------------------------------------------------------------------------------------------- device-resident API
+# optimizeTraj of multiShoot_CRTBP_direct (direct.jl:248-403) for flagEnd = false: one Jacobian sweep and the exact QP step on the
+# device.  state_0 / state_f from interpEndStates.  Returns (x_update, u_update, dV1_update, dV2_update, cost).
+function direct_qp_step(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Float64}, t_TU::Vector{Float64}, nsteps, Isp,
+                        MU, DU, TU, state_0, state_f, mass, dV1, dV2; allowImpulsive::Bool = false)
+    nstate, n_nodes = size(X_all)
+    dX = zeros(nstate, n_nodes); dU = zeros(3, n_nodes); dV = zeros(6); cost = zeros(1)
+    prm = Ref(LtoDirectParams(MU, DU, TU, Isp))
+    tg = Ref(LtoDirectTargets(state_0, state_f, mass, dV1, dV2))
+    rc = ccall(entry(ctx, :direct_qp_step), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ref{LtoDirectParams},
+                Ref{LtoDirectTargets}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+               ctx.handle, nstate, n_nodes, 1, X_all, u_all, t_TU, 1, nsteps, prm, tg, 1, allowImpulsive, dX, dU, dV, cost)
+    check(ctx, rc)
+    (dX, dU, dV[1:3], dV[4:6], cost[1])
+end
+
+# The loop of multiShoot_CRTBP_direct (direct.jl:477-594) on the device: returns (X_all, u_all, t_TU, dV1, dV2, defect,
+# status, iterations, history [3 x maxIter] = (max|defect|, cost, alpha)); status 0 converged, 1 maxIter, 2 NaN, 3 singular.
+function direct_solve(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Float64}, t_TU::Vector{Float64}, nsteps, Isp,
+                      MU, DU, TU, state_0, state_f, mass, dV1, dV2, maxIter::Integer; allowImpulsive::Bool = false)
+    nstate, n_nodes = size(X_all)
+    Xo = zeros(nstate, n_nodes); Uo = zeros(3, n_nodes); dV = zeros(6); to = zeros(n_nodes); defect = zeros(nstate, n_nodes - 1)
+    status = zeros(Cint, 1); iters = zeros(Cint, 1); hist = fill(NaN, 3, max(maxIter, 1))
+    prm = Ref(LtoDirectParams(MU, DU, TU, Isp))
+    tg = Ref(LtoDirectTargets(state_0, state_f, mass, dV1, dV2))
+    rc = ccall(entry(ctx, :direct_solve), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ref{LtoDirectParams}, Ref{LtoDirectTargets},
+                Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}),
+               ctx.handle, nstate, n_nodes, X_all, u_all, t_TU, nsteps, prm, tg, allowImpulsive, maxIter, Xo, Uo, dV, to, defect,
+               status, iters, hist)
+    check(ctx, rc)
+    (Xo, Uo, to, dV[1:3], dV[4:6], defect, Int(status[1]), Int(iters[1]), hist[:, 1:maxIter])
+end
+
 # The operands stay in HBM between calls (struct-of-arrays, see include/lto.h "device-resident API"); every function
 # below takes RAW DEVICE POINTERS (`Ptr{Cvoid}`) and a `hipStream_t` (`Ptr{Cvoid}`, C_NULL = HIP's default stream) and
 # returns as soon as the work is enqueued.  With AMDGPU.jl: `p = Ptr{Cvoid}(UInt(pointer(A)))` for a `ROCArray{Float64}`

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LTO_HIP_LIB") or os.path.join(_HERE, "liblto_hip.so")
 
 LTO_OK, LTO_EINVAL, LTO_ENULL, LTO_EUNSUPPORTED = 0, -1, -2, -3
-LTO_EHIP, LTO_EBADP, LTO_ENODEVICE, LTO_ENOMEM = 1, 2, 3, 4
+LTO_EHIP, LTO_EBADP, LTO_ENODEVICE, LTO_ENOMEM, LTO_ESINGULAR = 1, 2, 3, 4, 5
 
 
 class LtoError(RuntimeError):
@@ -31,6 +31,12 @@ class LtoParams(C.Structure):
 
 class LtoDirectParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("MU", "DU", "TU", "Isp")]
+
+
+class LtoDirectTargets(C.Structure):
+    """Per-trajectory targets of the direct QP step: interpolated end states, initial mass, current impulses."""
+    _fields_ = [("s0", C.c_double * 6), ("sf", C.c_double * 6), ("mass", C.c_double), ("dV1", C.c_double * 3),
+                ("dV2", C.c_double * 3)]
 
 
 _dp = C.POINTER(C.c_double)
@@ -113,6 +119,15 @@ SIGNATURES = {
                                            _vp]),
     "lto_direct_jacobian_dev": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_int, _vp, C.c_long, _vp, _vp,
                                           C.c_long, _vp]),
+    "lto_direct_qp_step": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(LtoDirectParams),
+                                     _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "lto_direct_qp_step_dev": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long, _vp, C.c_int, _vp,
+                                         C.c_int, _vp, _vp, _vp, _vp]),
+    "lto_direct_plan_qp_status": (_vp, [_vp]),
+    "lto_direct_solve_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(LtoDirectParams),
+                                         _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_direct_solve": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams), _vp, C.c_int, C.c_int,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_pack_soa_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_long, _vp, C.c_long]),
     "lto_unpack_soa_dev": (C.c_int, [_vp, _vp, _vp, C.c_long, C.c_int, C.c_long, _vp]),
     "lto_defect_norms_dev": (C.c_int, [_vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int, _vp, _vp]),

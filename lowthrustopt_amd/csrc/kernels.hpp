@@ -114,6 +114,29 @@ hipError_t launch_direct_jacobian(int nstate, const DirectArgs& a, hipStream_t s
 // base wave + one wave per sensitivity column for 32 segments, skewed by one RKF7(8) step (one barrier per step)
 hipError_t launch_direct_jacobian_pipe(int nstate, const DirectArgs& a, hipStream_t st);
 
+// QP step of the direct method on the device (kernels_direct_qp.hip): the KKT system as a block-bidiagonal BVP, structured
+// orthogonal cyclic reduction.  Operands in the SoA layouts of the direct sweeps; targets [n_batch][19] (lto_direct_targets).
+struct DirectQpArgs {
+  int n_nodes, n_batch;
+  const double* Jac; long ldj;
+  const double* defect; long ldd;
+  const double* X; long ldx;
+  const double* U; long ldu;
+  const double* t; int t_stride;
+  const double* targets;
+  int impulsive;
+  double c2;                       // (DU/TU)^2
+  double* dX; long ldX;            // [nstate][ldX]
+  double* dU; long ldU;            // [3][ldU]
+  double* dV;                      // [n_batch][6]: impulse updates at node 0 and node n-1
+  double* cost;                    // [n_batch]
+  double* singular;                // [n_batch] or null: 1.0 where the trajectory's KKT system is singular
+};
+size_t direct_qp_workspace_bytes(int nstate, int n_nodes, int n_batch);
+int* direct_qp_status(void* workspace, int nstate, int n_nodes, int n_batch);   // [n_batch] inside the workspace: 1 = singular
+hipError_t launch_direct_qp(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st);
+hipError_t launch_direct_qp_update_dv(double* targets, const double* dV, const double* step, int n_batch, hipStream_t st);
+
 // Newton step of the indirect method on the device (kernels_bvp.hip): structured orthogonal cyclic reduction.
 size_t bvp_workspace_doubles(int n_nodes, int n_batch);
 hipError_t launch_bvp_solve(const double* Phi, long ldp, const double* defect, long ldd, int n_nodes, int n_batch,

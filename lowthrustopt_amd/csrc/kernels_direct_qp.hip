@@ -1,0 +1,501 @@
+// kernels_direct_qp.hip -- the QP step of direct multiple shooting on the device (optimizeTraj of
+// src/multiShoot_CRTBP_direct.jl:248-403 for the reference demo's setting: flagEnd = false, beta = 0, tf fixed).
+//
+// With the end points frozen, the thrust bound commented out (:305-317) and tf_jump = 0 (:292) the subproblem is a convex QP
+// with equality constraints only:
+//   min  sum_k w_k |u_k + du_k|^2 + (DU/TU)^2 (|dV1 + d1|^2 + |dV2 + d2|^2)            (:323-326, :377-380)
+//   s.t. E_i dx_i + F_i dx_{i+1} + G_i du_i + H_i du_{i+1} = -defect_i                    (:337)
+//        x_0[0:6] + dx_0[0:6] + [0; dV1 + d1] = s0,  x_{n-1}[0:6] + dx_{n-1}[0:6] + [0; dV2 + d2] = sf      (:370-375)
+//        x_0[6] + dx_0[6] = mass (nstate 7, :269-271);   d1 = d2 = 0 unless allowImpulsive (:298-302).
+// Its optimality conditions, WITHOUT eliminating anything, are a square block-bidiagonal two-point BVP in the node vector
+// y_k = (dx_k, du_k, lambda_k), NB = 2 ns + 3 unknowns per node (lambda_k = multiplier of defect k, lambda_{n-1} a dummy pinned
+// to 0).  Block row i (NB rows) couples y_i and y_{i+1}: defect constraint i, stationarity in du_{i+1}
+// (2 w (u + du) + H_i^T l_i + G_{i+1}^T l_{i+1} = 0) and in dx_{i+1} (F_i^T l_i + E_{i+1}^T l_{i+1} = 0); a pinned component's
+// stationarity row is its pin instead; with allowImpulsive the impulse is eliminated through the velocity pin and the row carries
+// the 2 (DU/TU)^2 term.  Node 0 contributes ns + 3 boundary rows (its stationarity / pins), node n-1 ns rows (lambda = 0).
+//
+// Solved like the indirect Newton step (kernels_bvp.hip): STRUCTURED ORTHOGONAL cyclic reduction.  At every level adjacent block
+// rows are stacked, the 2NB x NB column block of their shared node is triangularised by Householder reflections (one wavefront per
+// pair, lane = column, reflector broadcast by v_readlane), the top NB rows are kept for back-substitution and the bottom NB rows
+// are the new block row.  The shared node's block [B_top; A_bottom] always has full column rank: B_i is block triangular with
+// diagonal blocks F_i, 2 w I and E_{i+1}^T (state-transition derivatives, invertible), and a merged row's B inherits that.  The
+// last level leaves one block row on (y_0, y_{n-1}); with the two boundary blocks that is a 2NB x 2NB system, triangularised the
+// same way in one wavefront per trajectory.  Orthogonal transformations only -- no products of STMs (kernels_bvp.hip:10-13).
+//
+// Scaling: rows mix nondimensional states with controls in N (G ~ 1e-5 per N, w ~ 0.1 TU).  Per trajectory, with g = max |G|,|H|
+// and w = max dt, the unknowns are du = s_u u~, lambda = s_l l~ and the stationarity rows are multiplied by r_u (du) and r_x = 1/s_l
+// (dx): s_u = 1/g, r_u = g/(2w), s_l = 2w/g^2, all rounded to powers of two (exact).  Every block is then O(1).
+#include "kernels.hpp"
+#include <type_traits>
+
+namespace lto {
+
+template <int NS>
+struct QpDims {
+  static constexpr int NB = 2 * NS + 3;          // unknowns per node: dx (NS), du (3), lambda (NS)
+  static constexpr int R2 = 2 * NB;              // rows of a pair's stack
+  static constexpr int NCOLS = 3 * NB + 1;       // mid | left | right | rhs
+  static constexpr int ROW = 2 * NB * NB + NB;   // A (NB x NB), B (NB x NB), r (NB), column-major
+  static constexpr int REC_R = 0, REC_CA = NB * NB, REC_CB = 2 * NB * NB, REC_G = 3 * NB * NB, REC = 3 * NB * NB + NB;
+  static_assert(NCOLS <= 64, "one wavefront per pair");
+};
+
+struct QpArgs {
+  int n_nodes, n_batch, S_traj;
+  const double* Jac; long ldj;       // the Jacobian sweep's SoA outputs: Jac[(col*NS+row)*ldj + s]
+  const double* defect; long ldd;
+  const double* X; long ldx;
+  const double* U; long ldu;
+  const double* t; int t_stride;
+  const double* tg;                  // targets [n_batch][QP_TARGET]: s0[6], sf[6], mass, dV1[3], dV2[3]
+  int impulsive;
+  double c2;                         // (DU/TU)^2
+  unsigned long long* gw;            // [n_batch][2]: bits of max |G|,|H| and of max dt (non-negative doubles order as integers)
+  double* rec;                       // [n_batch][n_nodes][REC]
+  double* Y; long ldy;               // solution, scaled unknowns: Y[c*ldy + b*n_nodes + k]
+  int* status;                       // [n_batch]: 0 ok, 1 singular KKT system
+};
+constexpr int QP_TARGET = 19;
+
+struct QpScale { double su, ru, sl, rx; };
+__device__ __forceinline__ double pow2_near(const double v) { return ldexp(1.0, ilogb(v)); }
+__device__ __forceinline__ QpScale qp_scale(const QpArgs& a, const int b) {
+  double g = __longlong_as_double((long long)a.gw[2 * b]), w = __longlong_as_double((long long)a.gw[2 * b + 1]);
+  if (!(g > 0.0) || !(g < 1e300)) g = 1.0;
+  if (!(w > 0.0) || !(w < 1e300)) w = 1.0;
+  QpScale s;
+  s.su = pow2_near(1.0 / g);
+  s.ru = pow2_near(g / (2.0 * w));
+  s.sl = pow2_near(2.0 * w / (g * g));
+  s.rx = 1.0 / s.sl;
+  return s;
+}
+__device__ __forceinline__ double qp_weight(const QpArgs& a, const int b, const int k) {   // trapezoid weight of node k (:323-326)
+  const double* t = a.t + (long)b * a.t_stride;
+  double w = 0.0;
+  if (k > 0) w += 0.5 * (t[k] - t[k - 1]);
+  if (k < a.n_nodes - 1) w += 0.5 * (t[k + 1] - t[k]);
+  return w;
+}
+
+// ---- per-trajectory scale inputs: max |G|,|H| over the segments, max dt
+template <int NS>
+__global__ __launch_bounds__(256) void k_qp_gmax(QpArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  double g = 0.0, w = 0.0;
+  if (i < a.S_traj) {
+    const long s = (long)b * a.S_traj + i;
+#pragma unroll
+    for (int col = 2 * NS; col < 2 * NS + 6; ++col)
+#pragma unroll
+      for (int r = 0; r < NS; ++r) g = fmax(g, fabs(a.Jac[(long)(col * NS + r) * a.ldj + s]));
+    const double* t = a.t + (long)b * a.t_stride;
+    w = fabs(t[i + 1] - t[i]);
+  }
+  for (int off = 32; off > 0; off >>= 1) { g = fmax(g, __shfl_xor(g, off)); w = fmax(w, __shfl_xor(w, off)); }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(&a.gw[2 * b], (unsigned long long)__double_as_longlong(g));
+    atomicMax(&a.gw[2 * b + 1], (unsigned long long)__double_as_longlong(w));
+  }
+}
+
+// ---- element (r, cc) of the level-0 block row i of trajectory b: cc < NB column of y_i, cc < 2NB column of y_{i+1}, cc = 2NB rhs
+template <int NS>
+__device__ double qp_elem0(const QpArgs& a, const QpScale& sc, const int b, const int i, const int r, const int cc) {
+  constexpr int NB = QpDims<NS>::NB;
+  const long s = (long)b * a.S_traj + i;
+  const int k = i + 1;
+  const bool last = (k == a.n_nodes - 1);
+  const long node = (long)b * a.n_nodes + k;
+  const bool isA = cc < NB, isB = (cc >= NB && cc < 2 * NB);
+  const int c = isA ? cc : cc - NB;
+  auto J = [&](const long seg, const int row, const int col) { return a.Jac[(long)(col * NS + row) * a.ldj + seg]; };
+  if (r < NS) {                                   // defect constraint i (:337)
+    if (!isA && !isB) return -a.defect[(long)r * a.ldd + s];
+    if (c < NS) return J(s, r, isA ? c : NS + c);
+    if (c < NS + 3) return sc.su * J(s, r, (isA ? 2 * NS : 2 * NS + 3) + c - NS);
+    return 0.0;
+  }
+  if (r < NS + 3) {                               // stationarity in du_{i+1}, scaled by r_u
+    const int q = r - NS;
+    if (isA) return (c >= NS + 3) ? sc.ru * sc.sl * J(s, c - NS - 3, 2 * NS + 3 + q) : 0.0;
+    const double wk = qp_weight(a, b, k);
+    if (isB) {
+      if (c == NS + q) return sc.ru * 2.0 * wk * sc.su;
+      if (c >= NS + 3 && !last) return sc.ru * sc.sl * J(s + 1, c - NS - 3, 2 * NS + q);
+      return 0.0;
+    }
+    return -sc.ru * 2.0 * wk * a.U[(long)q * a.ldu + node];
+  }
+  const int j = r - NS - 3;                       // stationarity in dx_{i+1}, scaled by r_x -- or the terminal pin
+  const double* tg = a.tg + (long)b * QP_TARGET;
+  if (last && (j < 3 || (j < 6 && !a.impulsive))) {
+    if (isA) return 0.0;
+    if (isB) return (c == j) ? 1.0 : 0.0;
+    return tg[6 + j] - a.X[(long)j * a.ldx + node] - (j >= 3 ? tg[16 + j - 3] : 0.0);
+  }
+  if (isA) return (c >= NS + 3) ? J(s, c - NS - 3, NS + j) : 0.0;
+  if (isB) {
+    if (!last) return (c >= NS + 3) ? J(s + 1, c - NS - 3, j) : 0.0;
+    return (j < 6 && c == j) ? 2.0 * a.c2 * sc.rx : 0.0;            // impulse eliminated through the velocity pin
+  }
+  return (last && j < 6) ? sc.rx * 2.0 * a.c2 * (tg[6 + j] - a.X[(long)j * a.ldx + node]) : 0.0;
+}
+
+// ---- element (r, c) of node 0's boundary block (NS + 3 rows on y_0; c = NB: rhs)
+template <int NS>
+__device__ double qp_elem_bc0(const QpArgs& a, const QpScale& sc, const int b, const int r, const int c) {
+  constexpr int NB = QpDims<NS>::NB;
+  const long node = (long)b * a.n_nodes, s = (long)b * a.S_traj;
+  auto J = [&](const int row, const int col) { return a.Jac[(long)(col * NS + row) * a.ldj + s]; };
+  const double* tg = a.tg + (long)b * QP_TARGET;
+  if (r < 3) {                                    // stationarity in du_0
+    const double w0 = qp_weight(a, b, 0);
+    if (c == NS + r) return sc.ru * 2.0 * w0 * sc.su;
+    if (c >= NS + 3 && c < NB) return sc.ru * sc.sl * J(c - NS - 3, 2 * NS + r);
+    if (c == NB) return -sc.ru * 2.0 * w0 * a.U[(long)r * a.ldu + node];
+    return 0.0;
+  }
+  const int j = r - 3;
+  if (j == 6) {                                   // initial mass (:269-271)
+    if (c == NB) return tg[12] - a.X[6 * a.ldx + node];
+    return (c == 6) ? 1.0 : 0.0;
+  }
+  if (j < 3 || !a.impulsive) {
+    if (c == NB) return tg[j] - a.X[(long)j * a.ldx + node] - (j >= 3 ? tg[13 + j - 3] : 0.0);
+    return (c == j) ? 1.0 : 0.0;
+  }
+  if (c >= NS + 3 && c < NB) return J(c - NS - 3, j);
+  if (c == j) return 2.0 * a.c2 * sc.rx;
+  if (c == NB) return sc.rx * 2.0 * a.c2 * (tg[j] - a.X[(long)j * a.ldx + node]);
+  return 0.0;
+}
+
+template <int K>
+__device__ __forceinline__ double qp_bcast(const double x) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(x), K), hi = __builtin_amdgcn_readlane(__double2hiint(x), K);
+  return __hiloint2double(hi, lo);
+}
+template <int FIRST, int LAST, class F>
+__device__ __forceinline__ void qp_static_for(F&& f) {
+  if constexpr (FIRST < LAST) {
+    f(std::integral_constant<int, FIRST>{});
+    qp_static_for<FIRST + 1, LAST>(f);
+  }
+}
+
+// NK Householder reflections on a ROWS-row stack, lane c = column c (c < NL); the reflector of step k is lane k's column
+template <int ROWS, int NK, int NL>
+__device__ __forceinline__ void qp_householder(double (&col)[ROWS], const int c) {
+  qp_static_for<0, NK>([&](auto kc) {
+    constexpr int k = decltype(kc)::value;
+    double x[ROWS];
+#pragma unroll
+    for (int r = k + 1; r < ROWS; ++r) x[r] = qp_bcast<k>(col[r]);
+    const double alpha = qp_bcast<k>(col[k]);
+    double q0 = 0.0, q1 = 0.0;
+#pragma unroll
+    for (int r = k + 1; r < ROWS; ++r) {
+      if (((r - k - 1) & 1) == 0) q0 = __builtin_fma(x[r], x[r], q0);
+      else q1 = __builtin_fma(x[r], x[r], q1);
+    }
+    const double xn2 = q0 + q1;
+    const bool trivial = (xn2 == 0.0);
+    const double nrm = sqrt(__builtin_fma(alpha, alpha, xn2));
+    const double beta = (alpha >= 0.0) ? -nrm : nrm;
+    const double vk = alpha - beta;
+    const double g = trivial ? 0.0 : 1.0 / (beta * (beta - alpha));
+    if (c == k && !trivial) col[k] = beta;
+    if (c > k && c < NL) {
+      double w0 = vk * col[k], w1 = 0.0;
+#pragma unroll
+      for (int r = k + 1; r < ROWS; ++r) {
+        if (((r - k - 1) & 1) == 0) w0 = __builtin_fma(x[r], col[r], w0);
+        else w1 = __builtin_fma(x[r], col[r], w1);
+      }
+      const double w = (w0 + w1) * g;
+      col[k] = __builtin_fma(-w, vk, col[k]);
+#pragma unroll
+      for (int r = k + 1; r < ROWS; ++r) col[r] = __builtin_fma(-w, x[r], col[r]);
+    }
+  });
+}
+
+// ---- one level of the reduction: pair j of trajectory b stacks rows 2j and 2j+1 of `cur` (FIRST: the level-0 rows, formed from
+// the sweep's outputs), eliminates node (2j+1) 2^level and writes the new row j of `nxt`; a row without a partner is carried.
+template <int NS, bool FIRST>
+__global__ __launch_bounds__(64) void k_qp_level(QpArgs a, const int level, const int M, const double* __restrict__ cur,
+                                                 double* __restrict__ nxt) {
+  using D = QpDims<NS>;
+  constexpr int NB = D::NB;
+  const int j = blockIdx.x, b = blockIdx.y, c = threadIdx.x;
+  const QpScale sc = qp_scale(a, b);
+  const double* rows = cur + (long)b * a.S_traj * D::ROW;
+  double* orow = nxt + ((long)b * a.S_traj + j) * D::ROW;
+  if (2 * j + 1 >= M) {                           // carried row
+    for (int e = c; e < D::ROW; e += 64) {
+      double v;
+      if (FIRST) {
+        const int cc = (e < 2 * NB * NB) ? e / NB : 2 * NB, r = (e < 2 * NB * NB) ? e % NB : e - 2 * NB * NB;
+        v = qp_elem0<NS>(a, sc, b, 2 * j, r, cc);
+      } else {
+        v = rows[(long)(2 * j) * D::ROW + e];
+      }
+      orow[e] = v;
+    }
+    return;
+  }
+  double col[D::R2];
+#pragma unroll
+  for (int r = 0; r < D::R2; ++r) col[r] = 0.0;
+  const double* top = rows + (long)(2 * j) * D::ROW;
+  const double* bot = top + D::ROW;
+  // columns: shared node [B_top; A_bot] | left node [A_top; 0] | right node [0; B_bot] | rhs
+  if (c < NB) {
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+      col[r] = FIRST ? qp_elem0<NS>(a, sc, b, 2 * j, r, NB + c) : top[NB * NB + c * NB + r];
+      col[NB + r] = FIRST ? qp_elem0<NS>(a, sc, b, 2 * j + 1, r, c) : bot[c * NB + r];
+    }
+  } else if (c < 2 * NB) {
+#pragma unroll
+    for (int r = 0; r < NB; ++r) col[r] = FIRST ? qp_elem0<NS>(a, sc, b, 2 * j, r, c - NB) : top[(c - NB) * NB + r];
+  } else if (c < 3 * NB) {
+#pragma unroll
+    for (int r = 0; r < NB; ++r) col[NB + r] = FIRST ? qp_elem0<NS>(a, sc, b, 2 * j + 1, r, c - NB) : bot[NB * NB + (c - 2 * NB) * NB + r];
+  } else if (c == 3 * NB) {
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+      col[r] = FIRST ? qp_elem0<NS>(a, sc, b, 2 * j, r, 2 * NB) : top[2 * NB * NB + r];
+      col[NB + r] = FIRST ? qp_elem0<NS>(a, sc, b, 2 * j + 1, r, 2 * NB) : bot[2 * NB * NB + r];
+    }
+  }
+  qp_householder<D::R2, NB, D::NCOLS>(col, c);
+  const int mid = (2 * j + 1) << level;
+  double* rec = a.rec + ((long)b * a.n_nodes + mid) * D::REC;
+  if (c < NB) {
+#pragma unroll
+    for (int r = 0; r < NB; ++r) rec[D::REC_R + c * NB + r] = (r <= c) ? col[r] : 0.0;
+  } else if (c < 2 * NB) {
+#pragma unroll
+    for (int r = 0; r < NB; ++r) { rec[D::REC_CA + (c - NB) * NB + r] = col[r]; orow[(c - NB) * NB + r] = col[NB + r]; }
+  } else if (c < 3 * NB) {
+#pragma unroll
+    for (int r = 0; r < NB; ++r) { rec[D::REC_CB + (c - 2 * NB) * NB + r] = col[r]; orow[NB * NB + (c - 2 * NB) * NB + r] = col[NB + r]; }
+  } else if (c == 3 * NB) {
+#pragma unroll
+    for (int r = 0; r < NB; ++r) { rec[D::REC_G + r] = col[r]; orow[2 * NB * NB + r] = col[NB + r]; }
+  }
+}
+
+// ---- the last level: the one block row A y_0 + B y_{n-1} = r with node 0's boundary block (NS + 3 rows) and lambda_{n-1} = 0 (NS
+// rows): 2NB x 2NB, triangularised in one wavefront (lane = column), back-substituted by lane 0 from LDS.  A pivot below 1e-13 of
+// the largest marks the trajectory's KKT system singular (e.g. too few nodes to reach the terminal state).
+template <int NS>
+__global__ __launch_bounds__(64) void k_qp_final(QpArgs a, const double* __restrict__ cur) {
+  using D = QpDims<NS>;
+  constexpr int NB = D::NB, N2 = 2 * NB;
+  __shared__ double Rs[N2 + 1][N2];
+  __shared__ double ys[N2];
+  const int b = blockIdx.x, c = threadIdx.x;
+  const QpScale sc = qp_scale(a, b);
+  const double* row = cur + (long)b * a.S_traj * D::ROW;
+  double col[N2];
+#pragma unroll
+  for (int r = 0; r < N2; ++r) col[r] = 0.0;
+  if (c <= N2) {
+    const int rc = (c < N2) ? c : 2 * NB;       // column of the block row: y_0 | y_{n-1} | rhs
+#pragma unroll
+    for (int r = 0; r < NB; ++r) col[r] = row[(rc < 2 * NB) ? (long)rc * NB + r : 2L * NB * NB + r];
+    if (c < NB || c == N2) {
+      const int bc = (c < NB) ? c : NB;
+#pragma unroll
+      for (int r = 0; r < NS + 3; ++r) col[NB + r] = qp_elem_bc0<NS>(a, sc, b, r, bc);
+    } else if (c >= NB + NS + 3) {              // lambda_{n-1} = 0
+#pragma unroll
+      for (int r = NB + NS + 3; r < N2; ++r) col[r] = (r == c) ? 1.0 : 0.0;
+    }
+  }
+  qp_householder<N2, N2, N2 + 1>(col, c);
+  if (c <= N2) {
+#pragma unroll
+    for (int r = 0; r < N2; ++r) Rs[c][r] = col[r];
+  }
+  __syncthreads();
+  if (c == 0) {
+    double dmax = 0.0, dmin = 1e300;
+    for (int k = 0; k < N2; ++k) { dmax = fmax(dmax, fabs(Rs[k][k])); dmin = fmin(dmin, fabs(Rs[k][k])); }
+    a.status[b] = (dmin <= 1e-13 * dmax) ? 1 : 0;
+    for (int k = N2 - 1; k >= 0; --k) {
+      double s = Rs[N2][k];
+      for (int m = k + 1; m < N2; ++m) s -= Rs[m][k] * ys[m];
+      ys[k] = s / Rs[k][k];
+    }
+  }
+  __syncthreads();
+  if (c < N2) {
+    const long node = (long)b * a.n_nodes + ((c < NB) ? 0 : a.n_nodes - 1);
+    a.Y[(long)(c % NB) * a.ldy + node] = ys[c];
+  }
+}
+
+// ---- back-substitution of one level: pair j forms y_mid = R^{-1} (g - Ca y_left - Cb y_right), lane r = row r
+template <int NS>
+__global__ __launch_bounds__(64) void k_qp_back(QpArgs a, const int level) {
+  using D = QpDims<NS>;
+  constexpr int NB = D::NB;
+  const int j = blockIdx.x, b = blockIdx.y, r = threadIdx.x;
+  const int mid = (2 * j + 1) << level, left = (2 * j) << level;
+  int right = (2 * j + 2) << level;
+  if (right > a.n_nodes - 1) right = a.n_nodes - 1;
+  const double* rec = a.rec + ((long)b * a.n_nodes + mid) * D::REC;
+  const long nb = (long)b * a.n_nodes;
+  const int rr = r < NB ? r : NB - 1;
+  double s = rec[D::REC_G + rr];
+  for (int c = 0; c < NB; ++c)
+    s -= rec[D::REC_CA + c * NB + rr] * a.Y[(long)c * a.ldy + nb + left] + rec[D::REC_CB + c * NB + rr] * a.Y[(long)c * a.ldy + nb + right];
+  const double rdiag = 1.0 / rec[D::REC_R + rr * NB + rr];
+  double x = 0.0;
+  qp_static_for<0, NB>([&](auto kc) {
+    constexpr int k = NB - 1 - decltype(kc)::value;
+    const double xk = qp_bcast<k>(s * rdiag);
+    if (rr == k) x = xk;
+    if (rr < k) s = __builtin_fma(-rec[D::REC_R + k * NB + rr], xk, s);
+  });
+  if (r < NB) a.Y[(long)r * a.ldy + nb + mid] = x;
+}
+
+// ---- unscale into the caller's arrays, grid over nodes; per-block partial sums of the control cost (:377-380) in `part`
+constexpr int QP_FIN = 256;
+template <int NS>
+__global__ __launch_bounds__(QP_FIN) void k_qp_unscale(QpArgs a, double* dX, long ldX, double* dU, long ldU, double* part) {
+  const int b = blockIdx.y, tid = threadIdx.x, k = blockIdx.x * QP_FIN + tid;
+  const QpScale sc = qp_scale(a, b);
+  const bool bad = a.status[b] != 0;              // singular: every output of the trajectory is NaN (and the status says why)
+  const double nan = __builtin_nan("");
+  double acc = 0.0;
+  if (k < a.n_nodes) {
+    const long node = (long)b * a.n_nodes + k;
+#pragma unroll
+    for (int c = 0; c < NS; ++c) dX[(long)c * ldX + node] = bad ? nan : a.Y[(long)c * a.ldy + node];
+    const double wk = qp_weight(a, b, k);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const double du = bad ? nan : sc.su * a.Y[(long)(NS + q) * a.ldy + node];
+      dU[(long)q * ldU + node] = du;
+      const double u = a.U[(long)q * a.ldu + node] + du;
+      acc = __builtin_fma(wk * u, u, acc);
+    }
+  }
+  __shared__ double red[QP_FIN];
+  red[tid] = acc;
+  __syncthreads();
+  for (int h = QP_FIN / 2; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) part[(long)b * gridDim.x + blockIdx.x] = red[0];
+}
+// ---- the impulses through the pins and the cost, one thread per trajectory (the partial sums added in a fixed order)
+__global__ void k_qp_cost(QpArgs a, const double* dX, long ldX, double* dV, double* cost, double* singular, const double* part, int nblk) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.n_batch) return;
+  const bool bad = a.status[b] != 0;
+  const double nan = __builtin_nan("");
+  double acc = 0.0;
+  for (int k = 0; k < nblk; ++k) acc += part[(long)b * nblk + k];
+  const double* tg = a.tg + (long)b * QP_TARGET;
+  const long nb = (long)b * a.n_nodes;
+  double ce = 0.0;
+  for (int e = 0; e < 2; ++e) {
+    const long node = nb + (e ? a.n_nodes - 1 : 0);
+    for (int q = 0; q < 3; ++q) {
+      const double dv = tg[13 + 3 * e + q];
+      // impulse update d = s_v - x_v - dx_v - dV (the velocity pin solved for it); 0 when impulses are off
+      const double upd = a.impulsive ? tg[6 * e + 3 + q] - a.X[(long)(3 + q) * a.ldx + node] - dX[(long)(3 + q) * ldX + node] - dv : 0.0;
+      dV[(long)b * 6 + 3 * e + q] = bad ? nan : upd;
+      ce += (dv + upd) * (dv + upd);
+    }
+  }
+  cost[b] = bad ? nan : acc + a.c2 * ce;
+  if (singular) singular[b] = bad ? 1.0 : 0.0;
+}
+
+// workspace: rows A | rows B | records | Y | partial sums | gw (u64) | status (int)
+static size_t qp_doubles_before_gw(int nstate, int n_nodes, int n_batch) {
+  const size_t S = (size_t)(n_nodes - 1) * n_batch, J = (size_t)n_nodes * n_batch;
+  const size_t row = (nstate == 7) ? QpDims<7>::ROW : QpDims<6>::ROW, rec = (nstate == 7) ? QpDims<7>::REC : QpDims<6>::REC;
+  const size_t nb = (nstate == 7) ? QpDims<7>::NB : QpDims<6>::NB;
+  const size_t nblk = (size_t)(n_nodes + QP_FIN - 1) / QP_FIN;
+  return 2 * S * row + J * rec + nb * J + nblk * n_batch;
+}
+size_t direct_qp_workspace_bytes(int nstate, int n_nodes, int n_batch) {
+  return sizeof(double) * qp_doubles_before_gw(nstate, n_nodes, n_batch) + sizeof(unsigned long long) * 2 * n_batch +
+         sizeof(int) * n_batch + 4096;
+}
+int* direct_qp_status(void* workspace, int nstate, int n_nodes, int n_batch) {
+  return (int*)((char*)workspace + sizeof(double) * qp_doubles_before_gw(nstate, n_nodes, n_batch) +
+                sizeof(unsigned long long) * 2 * n_batch);
+}
+
+template <int NS>
+static hipError_t direct_qp_impl(const DirectQpArgs& q, void* workspace, hipStream_t st) {
+  using D = QpDims<NS>;
+  QpArgs a;
+  a.n_nodes = q.n_nodes; a.n_batch = q.n_batch; a.S_traj = q.n_nodes - 1;
+  a.Jac = q.Jac; a.ldj = q.ldj; a.defect = q.defect; a.ldd = q.ldd; a.X = q.X; a.ldx = q.ldx; a.U = q.U; a.ldu = q.ldu;
+  a.t = q.t; a.t_stride = q.t_stride; a.tg = q.targets; a.impulsive = q.impulsive; a.c2 = q.c2;
+  const size_t S = (size_t)a.S_traj * a.n_batch, J = (size_t)a.n_nodes * a.n_batch;
+  double* rowsA = (double*)workspace;
+  double* rowsB = rowsA + S * D::ROW;
+  a.rec = rowsB + S * D::ROW;
+  a.Y = a.rec + J * D::REC; a.ldy = (long)J;
+  const int nblk = (a.n_nodes + QP_FIN - 1) / QP_FIN;
+  double* part = a.Y + (size_t)D::NB * J;
+  a.gw = (unsigned long long*)(part + (size_t)nblk * a.n_batch);
+  a.status = (int*)(a.gw + 2 * a.n_batch);
+  hipError_t e = hipMemsetAsync(a.gw, 0, sizeof(unsigned long long) * 2 * a.n_batch, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((k_qp_gmax<NS>), dim3((a.S_traj + 255) / 256, a.n_batch), dim3(256), 0, st, a);
+  int M = a.S_traj, level = 0;
+  int Ms[40];
+  double* cur = rowsA;
+  double* nxt = rowsB;
+  bool first = true;
+  do {                                  // a single segment still passes once: its level-0 row is formed ("carried")
+    Ms[level] = M;
+    const int groups = (M + 1) / 2;
+    if (first) hipLaunchKernelGGL((k_qp_level<NS, true>), dim3(groups, a.n_batch), dim3(64), 0, st, a, level, M, cur, nxt);
+    else hipLaunchKernelGGL((k_qp_level<NS, false>), dim3(groups, a.n_batch), dim3(64), 0, st, a, level, M, cur, nxt);
+    { double* t = cur; cur = nxt; nxt = t; }
+    first = false;
+    M = groups;
+    ++level;
+  } while (M > 1);
+  hipLaunchKernelGGL((k_qp_final<NS>), dim3(a.n_batch), dim3(64), 0, st, a, cur);
+  for (int l = level - 1; l >= 0; --l) {
+    const int pairs = Ms[l] / 2;
+    if (pairs > 0) hipLaunchKernelGGL((k_qp_back<NS>), dim3(pairs, a.n_batch), dim3(64), 0, st, a, l);
+  }
+  hipLaunchKernelGGL((k_qp_unscale<NS>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, a, q.dX, q.ldX, q.dU, q.ldU, part);
+  hipLaunchKernelGGL(k_qp_cost, dim3((a.n_batch + 63) / 64), dim3(64), 0, st, a, q.dX, q.ldX, q.dV, q.cost, q.singular, part, nblk);
+  return hipGetLastError();
+}
+
+// the impulses of the solve loop's targets after a step:  dV1 += alpha_b d1, dV2 += alpha_b d2  (:568-569; alpha = 0: frozen)
+__global__ void k_qp_update_dv(double* tg, const double* dV, const double* step, int nb) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb * 6) return;
+  const int b = i / 6, q = i % 6;
+  if (step[b] != 0.0) tg[(long)b * QP_TARGET + 13 + q] = __builtin_fma(step[b], dV[i], tg[(long)b * QP_TARGET + 13 + q]);
+}
+hipError_t launch_direct_qp_update_dv(double* targets, const double* dV, const double* step, int n_batch, hipStream_t st) {
+  hipLaunchKernelGGL(k_qp_update_dv, dim3((6 * n_batch + 255) / 256), dim3(256), 0, st, targets, dV, step, n_batch);
+  return hipGetLastError();
+}
+
+hipError_t launch_direct_qp(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st) {
+  return (nstate == 7) ? direct_qp_impl<7>(q, workspace, st) : direct_qp_impl<6>(q, workspace, st);
+}
+
+}  // namespace lto

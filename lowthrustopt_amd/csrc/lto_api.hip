@@ -144,6 +144,8 @@ struct lto_direct_plan {
   int nstate, n_nodes, n_batch, S, nsteps;
   lto_direct_params prm;
   int kernel;       // LTO_KERNEL_*
+  void* qp_ws;      // workspace of the QP step (kernels_direct_qp.hip), allocated at the plan's first step
+  double* qp_singular_out;   // lto_direct_solve_batch: where the QP step also reports singular systems (device, [n_batch])
 };
 
 namespace {
@@ -1544,10 +1546,15 @@ int lto_direct_plan_create(lto_ctx* c, int nstate, int n_nodes, int n_batch, int
   return rc;
 }
 
+static void direct_plan_free(lto_direct_plan* p) {
+  if (p->qp_ws) (void)hipFree(p->qp_ws);        // hipFree waits for the device
+  delete p;
+}
+
 void lto_direct_plan_destroy(lto_direct_plan* p) {
   if (!p) return;
   lto_ctx* c = p->ctx;
-  delete p;
+  direct_plan_free(p);
   if (ctx_release(c, OWNER_PLAN)) ctx_free(c);
 }
 
@@ -2071,6 +2078,304 @@ int lto_direct_midpoints(lto_ctx* c, int nstate, int n_nodes, int n_batch, const
   if (!c) return LTO_ENULL;
   if (!X || !U || !t || !x_mid) return set_err(c, LTO_ENULL, "X, U, t or x_mid is NULL");
   return direct_host(c, nstate, n_nodes, n_batch, X, U, t, n_tgrids, nsteps, prm, nullptr, nullptr, defect, errors, false, x_mid);
+}
+
+
+/* ------------------------------------------------------------------------------ direct QP step and solve loop */
+int lto_direct_qp_step_dev(lto_direct_plan* p, void* stream, const double* Jac, long ldj, const double* defect, long ldd,
+                           const double* X, long ldx, const double* U, long ldu, const double* t, int n_tgrids,
+                           const lto_direct_targets* targets, int allow_impulsive, double* dX, double* dU, double* dV,
+                           double* cost) {
+  if (!p) return LTO_ENULL;
+  lto_ctx* c = p->ctx;
+  if (!Jac || !defect || !X || !U || !t || !targets || !dX || !dU || !dV || !cost)
+    return set_err(c, LTO_ENULL, "lto_direct_qp_step_dev: a required array is NULL");
+  const long J = (long)p->n_nodes * p->n_batch;
+  if (ldj < p->S || ldd < p->S || ldx < J || ldu < J) return set_err(c, LTO_EINVAL, "ldj/ldd smaller than the segment count or ldx/ldu than the node count");
+  if (n_tgrids != 1 && n_tgrids != p->n_batch) return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch");
+  int rc = bind_device(c);
+  if (rc) return rc;
+  if (!p->qp_ws) {
+    const size_t bytes = direct_qp_workspace_bytes(p->nstate, p->n_nodes, p->n_batch);
+    const hipError_t e = hipMalloc(&p->qp_ws, bytes);
+    if (e != hipSuccess) { p->qp_ws = nullptr; return set_err(c, LTO_EHIP, "QP workspace", e); }
+  }
+  DirectQpArgs q;
+  std::memset(&q, 0, sizeof q);
+  q.n_nodes = p->n_nodes; q.n_batch = p->n_batch;
+  q.Jac = Jac; q.ldj = ldj; q.defect = defect; q.ldd = ldd; q.X = X; q.ldx = ldx; q.U = U; q.ldu = ldu;
+  q.t = t; q.t_stride = (n_tgrids == 1) ? 0 : p->n_nodes;
+  q.targets = (const double*)targets; q.impulsive = allow_impulsive ? 1 : 0;
+  const double vu = p->prm.DU / p->prm.TU;                 // costEnd = sum(((dV + dV_jump) * DU/TU).^2)  (:377)
+  q.c2 = vu * vu;
+  q.dX = dX; q.ldX = ldx; q.dU = dU; q.ldU = ldu; q.dV = dV; q.cost = cost;
+  q.singular = p->qp_singular_out;
+  hipStream_t st = (hipStream_t)stream;
+  timing_begin(c, st);
+  const hipError_t e = launch_direct_qp(p->nstate, q, p->qp_ws, st);
+  timing_end(c, st);
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_direct_qp", e);
+  return LTO_OK;
+}
+
+const int* lto_direct_plan_qp_status(const lto_direct_plan* p) {
+  return (p && p->qp_ws) ? direct_qp_status(p->qp_ws, p->nstate, p->n_nodes, p->n_batch) : nullptr;
+}
+
+static bool direct_targets_expand(const lto_direct_targets* targets, int n_targets, int B, lto::HostBuf<lto_direct_targets>& out) {
+  if (!out.alloc((size_t)B)) return false;
+  for (int b = 0; b < B; ++b) out[(size_t)b] = targets[n_targets == 1 ? 0 : b];
+  return true;
+}
+
+int lto_direct_qp_step(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
+                       int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets, int n_targets,
+                       int allow_impulsive, double* dX, double* dU, double* dV, double* cost) {
+  // shape checks first, so that they answer without a device (a context needs one)
+  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
+  if (!c) return LTO_ENULL;
+  if (!X || !U || !t || !prm || !targets || !dX || !dU || !dV || !cost) return set_err(c, LTO_ENULL, "lto_direct_qp_step: a required array is NULL");
+  if (n_targets != 1 && n_targets != n_batch) return set_err(c, LTO_EINVAL, "n_targets must be 1 or n_batch");
+  CallTimer call_timer(c);
+  lto_direct_plan* p = nullptr;
+  int rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &p);
+  if (rc) return rc;
+  if (n_tgrids != 1 && n_tgrids != n_batch) { delete p; return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch"); }
+  lto::HostBuf<lto_direct_targets> tg;
+  lto::HostBuf<int> h_stat(n_batch, 0);
+  if (!direct_targets_expand(targets, n_targets, n_batch, tg) || !h_stat.ok()) { delete p; return set_err(c, LTO_ENOMEM, "lto_direct_qp_step: out of host memory"); }
+  const long J = (long)n_nodes * n_batch, S = p->S;
+  const int nj = nstate * 2 * (nstate + 3);
+  const size_t need = al256(sizeof(double) * nstate * J) * 4 + al256(sizeof(double) * 3 * J) * 4 + al256(sizeof(double) * n_nodes * n_tgrids) +
+                      al256(sizeof(double) * nj * S) + al256(sizeof(double) * nstate * S) + al256(sizeof(lto_direct_targets) * n_batch) +
+                      al256(sizeof(double) * 7 * n_batch) * 2 + 8192;
+  rc = arena_reserve(c, need);
+  if (rc) { delete p; return rc; }
+  c->arena_top = 0;
+  double* d_xa = arena_take<double>(c, (size_t)nstate * J);
+  double* d_X = arena_take<double>(c, (size_t)nstate * J);
+  double* d_dX = arena_take<double>(c, (size_t)nstate * J);
+  double* d_dXa = arena_take<double>(c, (size_t)nstate * J);
+  double* d_ua = arena_take<double>(c, (size_t)3 * J);
+  double* d_U = arena_take<double>(c, (size_t)3 * J);
+  double* d_dU = arena_take<double>(c, (size_t)3 * J);
+  double* d_dUa = arena_take<double>(c, (size_t)3 * J);
+  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
+  double* d_jac = arena_take<double>(c, (size_t)nj * S);
+  double* d_def = arena_take<double>(c, (size_t)nstate * S);
+  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)n_batch);
+  double* d_dV = arena_take<double>(c, (size_t)7 * n_batch);
+  double* d_cost = arena_take<double>(c, (size_t)7 * n_batch);
+  hipStream_t st = c->stream;
+  hipError_t e = stage_in(c, X, nstate, J, d_xa, d_X, J, st);
+  if (e == hipSuccess) e = stage_in(c, U, 3, J, d_ua, d_U, J, st);
+  if (e == hipSuccess) e = vec_in(c, t, (long)n_nodes * n_tgrids, d_t, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * n_batch, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { (void)hipStreamSynchronize(st); delete p; return set_err(c, LTO_EHIP, "stage in", e); }
+  rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, d_t, n_tgrids, d_jac, S, nullptr, d_def, S, nullptr);
+  if (rc == LTO_OK) rc = lto_direct_qp_step_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t, n_tgrids, d_tg, allow_impulsive, d_dX, d_dU, d_dV, d_cost);
+  if (rc == LTO_OK) {
+    e = stage_out(c, d_dX, J, nstate, J, d_dXa, dX, st);
+    if (e == hipSuccess) e = stage_out(c, d_dU, J, 3, J, d_dUa, dU, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dV, d_dV, sizeof(double) * 6 * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_stat.data(), lto_direct_plan_qp_status(p), sizeof(int) * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = stream_wait(st);
+    if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
+    for (int b = 0; b < n_batch && rc == LTO_OK; ++b)
+      if (h_stat[b]) rc = set_err(c, LTO_ESINGULAR, "the KKT system of a trajectory's QP step is singular (too few nodes to reach the terminal state?)");
+  } else {
+    (void)hipStreamSynchronize(st);
+  }
+  direct_plan_free(p);
+  return rc;
+}
+
+int lto_direct_solve_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
+                           const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
+                           const lto_direct_targets* targets, int n_targets, int allow_impulsive, int maxIter, double* X_out,
+                           double* U_out, double* dV_out, double* t_out, double* defect_out, int* status_flag, int* iterations,
+                           double* history) {
+  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
+  if (!c) return LTO_ENULL;
+  if (!X_in || !U_in || !t || !prm || !targets || !X_out || !status_flag)
+    return set_err(c, LTO_ENULL, "X_in, U_in, t, prm, targets, X_out or status is NULL");
+  if (maxIter < 0) return set_err(c, LTO_EINVAL, "maxIter must be >= 0");
+  if ((n_tgrids != 1 && n_tgrids != n_batch) || (n_targets != 1 && n_targets != n_batch)) return set_err(c, LTO_EINVAL, "n_tgrids / n_targets must be 1 or n_batch");
+  constexpr int NA = 10;                                   // LinRange(0.1, 1, 10), :412
+  const int B = n_batch;
+  if ((long)B * NA * (n_nodes - 1) > 0x3fffffffL) return set_err(c, LTO_EINVAL, "too many line-search segments");
+  const long n = n_nodes, J = n * B, S = (n - 1) * B;
+  const int nj = nstate * 2 * (nstate + 3);
+  // t recomputed through tau with tf unchanged (:478-480, :582): the grid of every iteration after the first update, and the
+  // grid of the QP's weights (t_TU_fixed, :321); the ten trial trajectories of trajectory b carry its grid
+  lto::HostBuf<double> t1((size_t)n * n_tgrids), tl((size_t)n * B * NA);
+  lto::HostBuf<lto_direct_targets> tg;
+  if (!t1.ok() || !tl.ok() || !direct_targets_expand(targets, n_targets, B, tg)) return set_err(c, LTO_ENOMEM, "lto_direct_solve_batch: out of host memory");
+  for (int g = 0; g < n_tgrids; ++g) {
+    const double* tg0 = t + (size_t)g * n;
+    const double t0 = tg0[0], tf = tg0[n - 1];
+    for (long k = 0; k < n; ++k) {
+      const double tau = (tg0[k] - t0) / (tf - t0) * 2.0 - 1.0;
+      t1[(size_t)g * n + k] = t0 + (tau + 1.0) / 2.0 * (tf - t0);
+    }
+  }
+  for (int b = 0; b < B; ++b) for (int a = 0; a < NA; ++a)
+    std::memcpy(&tl[((size_t)b * NA + a) * n], &t1[(size_t)(n_tgrids == 1 ? 0 : b) * n], sizeof(double) * n);
+  lto_direct_plan* p = nullptr;
+  lto_direct_plan* pl = nullptr;
+  int rc = direct_plan_build(c, nstate, n_nodes, B, nsteps, prm, &p);
+  if (rc) return rc;
+  rc = direct_plan_build(c, nstate, n_nodes, B * NA, nsteps, prm, &pl);
+  if (rc) { direct_plan_free(p); return rc; }
+  const size_t n_small = 6 * (size_t)B + 2 * (size_t)NA * B + NA + 64;
+  const size_t need = al256(sizeof(double) * nstate * J) * 3 + al256(sizeof(double) * 3 * J) * 3 + al256(sizeof(double) * (nstate + 3) * J * NA) +
+                      al256(sizeof(double) * n * n_tgrids) * 2 + al256(sizeof(double) * n * B * NA) + al256(sizeof(double) * nj * S) +
+                      al256(sizeof(double) * nstate * S) * 2 + al256(sizeof(double) * nstate * S * NA) + al256(sizeof(lto_direct_targets) * B) +
+                      al256(sizeof(double) * 6 * B) + al256(sizeof(double) * n_small) + 65536;
+  rc = arena_reserve(c, need);
+  if (rc) { direct_plan_free(pl); direct_plan_free(p); return rc; }
+  c->arena_top = 0;
+  double* d_aos = arena_take<double>(c, (size_t)nstate * J);
+  double* d_X = arena_take<double>(c, (size_t)nstate * J);
+  double* d_dX = arena_take<double>(c, (size_t)nstate * J);
+  double* d_uaos = arena_take<double>(c, (size_t)3 * J);
+  double* d_U = arena_take<double>(c, (size_t)3 * J);
+  double* d_dU = arena_take<double>(c, (size_t)3 * J);
+  double* d_Xt = arena_take<double>(c, (size_t)(nstate + 3) * J * NA);
+  double* d_Ut = d_Xt + (size_t)nstate * J * NA;
+  double* d_t = arena_take<double>(c, (size_t)n * n_tgrids);
+  double* d_t1 = arena_take<double>(c, (size_t)n * n_tgrids);
+  double* d_tl = arena_take<double>(c, (size_t)n * B * NA);
+  double* d_jac = arena_take<double>(c, (size_t)nj * S);
+  double* d_def = arena_take<double>(c, (size_t)nstate * S);
+  double* d_def_aos = arena_take<double>(c, (size_t)nstate * S);
+  double* d_deft = arena_take<double>(c, (size_t)nstate * S * NA);
+  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)B);
+  double* d_dV = arena_take<double>(c, (size_t)6 * B);
+  double* d_small = arena_take<double>(c, n_small);
+  double* d_step = d_small;                                // [B]    step length (0 = frozen)      } read back together
+  double* d_mx = d_step + B;                               // [B]    max |defect|                 }
+  double* d_cost = d_mx + B;                               // [B]    QP objective                 } read back together
+  double* d_sing = d_cost + B;                             // [B]    1 = singular KKT system      }
+  double* d_act = d_sing + B;                              // [B]    1 = trajectory still in its loop
+  double* d_search = d_act + B;                            // [B]    1 = line search on (iteration > 10)
+  double* d_ss = d_search + B;                             // [NA*B] per-trial sums of squares
+  double* d_alphas = d_ss + (size_t)NA * B;                // [NA]
+  p->qp_singular_out = d_sing;
+  (void)report_reserve(c, (size_t)4 * B);
+  hipStream_t st = c->stream;
+  double alphas[NA];
+  for (int a = 0; a < NA; ++a) alphas[a] = 0.1 + (1.0 - 0.1) / (NA - 1) * a;
+  alphas[NA - 1] = 1.0;
+  lto::HostBuf<double> h_er(B, 1.0), h_back((size_t)4 * B), h_act(B, -1.0), h_search(B, -1.0);   // er = 1.0 (:488)
+  lto::HostBuf<int> it(B, 0), status(B, 0);
+  lto::HostBuf<char> active(B, 1), moved(B, 0);
+  if (!h_er.ok() || !h_back.ok() || !h_act.ok() || !h_search.ok() || !it.ok() || !status.ok() || !active.ok() || !moved.ok()) {
+    direct_plan_free(pl); direct_plan_free(p);
+    return set_err(c, LTO_ENOMEM, "lto_direct_solve_batch: out of host memory");
+  }
+  hipError_t e = stage_in(c, X_in, nstate, J, d_aos, d_X, J, st);
+  if (e == hipSuccess) e = stage_in(c, U_in, 3, J, d_uaos, d_U, J, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n * n_tgrids, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_t1, t1.data(), sizeof(double) * n * n_tgrids, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tl, tl.data(), sizeof(double) * n * B * NA, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * B, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_alphas, alphas, sizeof alphas, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, sizeof(double) * 4 * B, st);
+  if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage in", e);
+  const double* t_cur = d_t;                               // the caller's grid until the first update, then t through tau
+
+  if (rc == LTO_OK) rc = lto_direct_defect_dev(p, st, d_X, J, d_U, J, t_cur, n_tgrids, d_def, S, nullptr);    // :485 (er = 1.0: one step at least)
+  auto any_active = [&]() { for (int b = 0; b < B; ++b) if (active[b]) return true; return false; };
+  while (rc == LTO_OK) {
+    // `while er > 1e-6` (:491) + the iteration limit (:492-496), trajectory by trajectory
+    for (int b = 0; b < B; ++b) {
+      if (!active[b]) continue;
+      if (!(h_er[b] > 1e-6)) { active[b] = 0; continue; }             // converged, or NaN (the comparison is false)
+      if (++it[b] > maxIter) { status[b] = 1; active[b] = 0; it[b] = maxIter; }
+    }
+    if (!any_active()) break;
+    bool flags_changed = false, search = false;
+    for (int b = 0; b < B; ++b) {
+      const double fa = active[b] ? 1.0 : 0.0, fs = (active[b] && it[b] > 10) ? 1.0 : 0.0;      // :557
+      search |= fs != 0.0;
+      if (fa != h_act[b] || fs != h_search[b]) { h_act[b] = fa; h_search[b] = fs; flags_changed = true; }
+    }
+    if (flags_changed) {
+      e = hipMemcpyAsync(d_act, h_act.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_search, h_search.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
+      if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "flag upload", e); break; }
+    }
+    rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, t_cur, n_tgrids, d_jac, S, nullptr, nullptr, 0, nullptr);   // :500
+    if (rc == LTO_OK)                                                                                                    // :525-529
+      rc = lto_direct_qp_step_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t1, n_tgrids, d_tg, allow_impulsive, d_dX, d_dU, d_dV, d_cost);
+    if (rc != LTO_OK) break;
+    if (search) {                                          // lineSearch (:405-430): the ten trial points of every problem, one sweep
+      e = launch_trial_points(d_X, d_dX, J, nstate, n_nodes, B, NA, d_alphas, d_Xt, J * NA, st);
+      if (e == hipSuccess) e = launch_trial_points(d_U, d_dU, J, 3, n_nodes, B, NA, d_alphas, d_Ut, J * NA, st);
+      if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "trial points", e); break; }
+      rc = lto_direct_defect_dev(pl, st, d_Xt, J * NA, d_Ut, J * NA, d_tl, B * NA, d_deft, S * NA, nullptr);
+      if (rc != LTO_OK) break;
+      e = launch_defect_norms(d_deft, S * NA, nstate, n_nodes - 1, B * NA, d_ss, nullptr, st);      // sum(defect[:].^2), :422
+      if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "line search", e); break; }
+    }
+    // alpha (:428-429), 1 (:556), or 0 for a frozen trajectory
+    e = launch_pick_alpha(d_ss, d_alphas, NA, d_act, d_search, d_step, B, nullptr, nullptr, st);
+    if (e == hipSuccess) e = launch_axpy_traj(d_X, d_dX, d_step, d_X, J, nstate, n_nodes, B, st);     // :562
+    if (e == hipSuccess) e = launch_axpy_traj(d_U, d_dU, d_step, d_U, J, 3, n_nodes, B, st);          // :563
+    if (e == hipSuccess) e = launch_direct_qp_update_dv((double*)d_tg, d_dV, d_step, B, st);           // :568-569
+    if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "update", e); break; }
+    t_cur = d_t1;                                                                                        // :582
+    rc = lto_direct_defect_dev(p, st, d_X, J, d_U, J, t_cur, n_tgrids, d_def, S, nullptr);              // :585
+    if (rc != LTO_OK) break;
+    e = launch_defect_norms(d_def, S, nstate, (int)(n - 1), B, nullptr, d_mx, st);                      // :588
+    if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "norm", e); break; }
+    rc = read_scalars(c, st, d_step, 4 * B, nullptr, 0, h_back.data());                                // step | max|d| | cost | singular
+    if (rc != LTO_OK) break;
+    for (int b = 0; b < B; ++b) {
+      if (!active[b]) continue;
+      moved[b] = 1;
+      h_er[b] = h_back[B + b];
+      if (history) {
+        double* hrow = history + ((size_t)b * maxIter + (it[b] - 1)) * 3;
+        hrow[0] = h_er[b]; hrow[1] = h_back[2 * B + b]; hrow[2] = h_back[b];
+      }
+      if (h_back[3 * B + b] != 0.0) { status[b] = 3; active[b] = 0; }
+    }
+  }
+  p->qp_singular_out = nullptr;
+  if (rc == LTO_OK) {
+    e = stage_out(c, d_X, J, nstate, J, d_aos, X_out, st);
+    if (e == hipSuccess && U_out) e = stage_out(c, d_U, J, 3, J, d_uaos, U_out, st);
+    if (e == hipSuccess && defect_out) e = stage_out(c, d_def, S, nstate, S, d_def_aos, defect_out, st);
+    if (e == hipSuccess && dV_out) e = hipMemcpy2DAsync(dV_out, sizeof(double) * 6, (const double*)d_tg + 13, sizeof(lto_direct_targets),
+                                                         sizeof(double) * 6, B, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = stream_wait(st);
+    if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
+    if (rc == LTO_OK)
+      for (int b = 0; b < B; ++b)
+        if (status[b] != 3 && (X_out[(size_t)nstate * n * b] != X_out[(size_t)nstate * n * b] || h_er[b] != h_er[b])) status[b] = 2;
+    if (rc == LTO_OK && t_out)
+      for (int b = 0; b < B; ++b) {
+        const size_t g = (size_t)(n_tgrids == 1 ? 0 : b) * n;
+        std::memcpy(t_out + (size_t)b * n, moved[b] ? &t1[g] : t + g, sizeof(double) * n);
+      }
+  } else {
+    (void)hipStreamSynchronize(st);
+  }
+  for (int b = 0; b < B; ++b) { status_flag[b] = status[b]; if (iterations) iterations[b] = it[b]; }
+  direct_plan_free(pl);
+  direct_plan_free(p);
+  return rc;
+}
+
+int lto_direct_solve(lto_ctx* c, int nstate, int n_nodes, const double* X_in, const double* U_in, const double* t, int nsteps,
+                     const lto_direct_params* prm, const lto_direct_targets* targets, int allow_impulsive, int maxIter,
+                     double* X_out, double* U_out, double* dV_out, double* t_out, double* defect_out, int* status,
+                     int* iterations, double* history) {
+  return lto_direct_solve_batch(c, nstate, n_nodes, 1, X_in, U_in, t, 1, nsteps, prm, targets, 1, allow_impulsive, maxIter, X_out,
+                                U_out, dV_out, t_out, defect_out, status, iterations, history);
 }
 
 }  // extern "C"

@@ -14,8 +14,14 @@
 Same signatures, return tuples and status flags as the Julia functions (the reference is Julia; this mirror exists
 because no `julia` binary is available to run julia/LowThrustOptHIP.jl -- see INTEGRATION.md).  The propagation
 (defects, STM blocks) always runs on the GPU through the C ABI; only the small sparse least-squares solve is on the
-host, as in the reference (`-Jac_sparse \\ defect_vec`, :182).  The direct driver's JuMP/Ipopt QP
-(src/multiShoot_CRTBP_direct.jl:248-403) is out of scope; its hot-path closures are in hotpath.py.
+host, as in the reference (`-Jac_sparse \\ defect_vec`, :182).
+
+  multiShoot_CRTBP_direct     src/multiShoot_CRTBP_direct.jl:58-594 for flagEnd = false (the reference demo's setting): the
+                              JuMP/Ipopt subproblem optimizeTraj (:248-403) is then an equality-constrained convex QP, solved
+                              exactly -- on the device by lto_direct_solve (ops=None), on the host by a dense KKT solve
+                              (direct_qp_dense) when `ops` is injected.  flagEnd = true (box-bounded tau updates, beta
+                              penalty) stays out of scope.
+  interpEndStates             :434-461 (natural cubic spline of the end-orbit tables)
 
 `ops` lets the CPU unit tests inject a different propagation back end; the product default is the HIP library.
 """
@@ -235,6 +241,188 @@ class HipDirectOps:
         """sum(defect.^2) of every trial trajectory X_batch[:, :, b], U_batch[:, :, b]: one batched launch."""
         d, _ = hotpath.direct_defectCalc(X_batch, U_batch, t, nsteps, self.MU, self.DU, self.TU, self.Isp, ctx=self.ctx)
         return np.sum(d * d, axis=(0, 1))
+
+
+    def jacobian(self, X, U, t, nsteps):
+        """(Jac_temp [nstate x nvar x (n-1)], defect): the blocks d defect_i / d [x_i; x_{i+1}; u_i; u_{i+1}] (:111-143)."""
+        Jt, _, d, _ = hotpath.direct_jacobian_blocks(X, U, t, nsteps, self.MU, self.DU, self.TU, self.Isp, ctx=self.ctx)
+        return Jt, d
+
+
+def _natural_spline(x, Y, xq):
+    """Natural cubic spline through (x, Y[:, j]) (second derivative 0 at both ends), evaluated at xq: one column per row of Y."""
+    x = np.asarray(x, dtype=np.float64)
+    Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
+    n = x.size
+    h = np.diff(x)
+    # second derivatives M: M_0 = M_{n-1} = 0, h_{i-1} M_{i-1} + 2 (h_{i-1} + h_i) M_i + h_i M_{i+1} = 6 (slope_i - slope_{i-1})
+    A = np.zeros((n, n))
+    R = np.zeros((n, Y.shape[0]))
+    A[0, 0] = A[-1, -1] = 1.0
+    slope = np.diff(Y, axis=1) / h
+    for i in range(1, n - 1):
+        A[i, i - 1], A[i, i], A[i, i + 1] = h[i - 1], 2.0 * (h[i - 1] + h[i]), h[i]
+        R[i] = 6.0 * (slope[:, i] - slope[:, i - 1])
+    M = np.linalg.solve(A, R)
+    i = int(np.clip(np.searchsorted(x, xq, side="right") - 1, 0, n - 2))
+    a, b = x[i + 1] - xq, xq - x[i]
+    return (M[i] * a ** 3 + M[i + 1] * b ** 3) / (6.0 * h[i]) + (Y[:, i] - M[i] * h[i] ** 2 / 6.0) * a / h[i] + \
+        (Y[:, i + 1] - M[i + 1] * h[i] ** 2 / 6.0) * b / h[i]
+
+
+def interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU=None):
+    """Interpolated initial and final states (direct.jl:434-461): τ1 and τ2 are wrapped into [0, 1] as the reference does (`while
+    τ > 1: τ -= 1`, `while τ < 0: τ += 1`), then each of the six components is interpolated in its orbit table by
+    `BSpline(Cubic(Natural()))` on grid.  In Interpolations.jl `Natural` is the `Line` boundary condition: the second derivative
+    of the interpolant vanishes at the first and last grid point, i.e. the classical natural cubic spline through the samples
+    (the one scipy.interpolate.CubicSpline(bc_type="natural") builds).  Returns (state_0[6], state_f[6])."""
+    def wrap(tau):
+        tau = float(tau)
+        while tau > 1:
+            tau -= 1
+        while tau < 0:
+            tau += 1
+        return tau
+    s0 = _natural_spline(X0_times, np.asarray(X0_states)[:6], wrap(τ1))
+    sf = _natural_spline(Xf_times, np.asarray(Xf_states)[:6], wrap(τ2))
+    return s0, sf
+
+
+def direct_qp_dense(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, mass, dV1, dV2, DU, TU, allowImpulsive=False):
+    """optimizeTraj (direct.jl:248-403) for flagEnd = false, beta = 0, tf fixed -- the host restatement of the device QP step: the
+    equality-constrained QP's KKT system, assembled densely and solved by LU after symmetric (Ruiz) equilibration.
+    Returns (x_update, u_update, dV1_update, dV2_update, cost)."""
+    Jt = np.asarray(Jac_temp, dtype=np.float64)
+    d = np.asarray(defect, dtype=np.float64)
+    X = np.asarray(X_all, dtype=np.float64)
+    U = np.asarray(u_all, dtype=np.float64)
+    t = np.asarray(t_TU, dtype=np.float64)
+    ns, _, S = Jt.shape
+    n = S + 1
+    c2 = (DU / TU) ** 2
+    nz = ns * n + 3 * n + 6                               # dx (node-major), du, dV1_jump, dV2_jump
+    iu, iv = ns * n, ns * n + 3 * n
+    dt = np.diff(t)
+    w = np.concatenate([dt / 2, [dt[-1] / 2]]) + np.concatenate([[0.0], dt[:-1] / 2, [0.0]])   # :324-326
+    Q = np.zeros(nz)
+    q = np.zeros(nz)                                      # cost = z'Qz + 2q'z + const
+    for k in range(n):
+        Q[iu + 3 * k:iu + 3 * k + 3] = w[k]
+        q[iu + 3 * k:iu + 3 * k + 3] = w[k] * U[:, k]
+    Q[iv:iv + 6] = c2
+    q[iv:iv + 3] = c2 * np.asarray(dV1, dtype=np.float64)
+    q[iv + 3:iv + 6] = c2 * np.asarray(dV2, dtype=np.float64)
+    rows, rhs = [], []
+    for i in range(S):                                    # -Jac_full * [X_jump; u_jump] = defect   (:337)
+        A = np.zeros((ns, nz))
+        A[:, ns * i:ns * i + 2 * ns] = Jt[:, :2 * ns, i]
+        A[:, iu + 3 * i:iu + 3 * i + 6] = Jt[:, 2 * ns:, i]
+        rows.append(A)
+        rhs.append(-d[:, i])
+    for k, s, dv, o in ((0, state_0, dV1, 0), (n - 1, state_f, dV2, 3)):    # hard-fixed end points (:370-375)
+        A = np.zeros((6, nz))
+        A[:, ns * k:ns * k + 6] = np.eye(6)
+        A[3:, iv + o:iv + o + 3] = np.eye(3)
+        rows.append(A)
+        rhs.append(np.asarray(s, dtype=np.float64) - X[:6, k] - np.r_[0.0, 0.0, 0.0, np.asarray(dv, dtype=np.float64)])
+    if ns == 7:                                           # initial mass (:269-271)
+        A = np.zeros((1, nz))
+        A[0, 6] = 1.0
+        rows.append(A)
+        rhs.append(np.array([mass - X[6, 0]]))
+    if not allowImpulsive:                                # dV1_jump = dV2_jump = 0 (:298-302)
+        A = np.zeros((6, nz))
+        A[:, iv:iv + 6] = np.eye(6)
+        rows.append(A)
+        rhs.append(np.zeros(6))
+    A = np.vstack(rows)
+    b = np.concatenate(rhs)
+    m = A.shape[0]
+    K = np.zeros((nz + m, nz + m))
+    K[:nz, :nz] = np.diag(2.0 * Q)
+    K[:nz, nz:] = A.T
+    K[nz:, :nz] = A
+    r = np.concatenate([-2.0 * q, b])
+    D = np.ones(nz + m)
+    for _ in range(20):                                   # rows mix nondimensional states with controls in N
+        Ks = K * D[:, None] * D[None, :]
+        D = D / np.sqrt(np.maximum(np.abs(Ks).max(axis=1), 1e-300))
+    z = np.linalg.solve(K * D[:, None] * D[None, :], r * D) * D
+    x_update = z[:ns * n].reshape(n, ns).T
+    u_update = z[iu:iv].reshape(n, 3).T
+    dV1_u, dV2_u = (z[iv:iv + 3], z[iv + 3:iv + 6]) if allowImpulsive else (np.zeros(3), np.zeros(3))   # exact zeros when pinned
+    cost = float(np.sum(w[None, :] * (U + u_update) ** 2) + c2 * (np.sum((dV1 + dV1_u) ** 2) + np.sum((dV2 + dV2_u) ** 2)))
+    return x_update, u_update, dV1_u, dV2_u, cost
+
+
+def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states,
+                            Xf_times, Xf_states, plot_yn, flagEnd, β, allowImpulsive, maxIter, ops=None, verbose=True):
+    """Direct multiple shooting with frozen end points (direct.jl:58-594).  Returns the reference's tuple
+    (X_all, u_all, τ1, τ2, t_TU, dV1, dV2, defect).
+
+    ops=None: the whole loop is ONE library call (lto_direct_solve: Jacobian sweep, QP step, batched line search and update on
+    the device).  An injected `ops` (defect / jacobian / defect_batch_sumsq, e.g. HipDirectOps or a CPU back end) runs this
+    Python mirror of the loop with the QP solved on the host (direct_qp_dense).  The status of the last call is kept in
+    `multiShoot_CRTBP_direct.last` = {"status", "iterations", "history"} (0 converged, 1 maxIter, 2 NaN, 3 singular KKT system;
+    history rows: max|defect|, cost, alpha) -- the reference prints its progress and returns no flag.
+    flagEnd = true (tau updates inside +-0.1 and the beta-weighted quadratic end-point model, :278-292, :353-369) raises
+    NotImplementedError: that subproblem has inequality bounds, which the exact equality-constrained solve does not cover."""
+    if flagEnd:
+        raise NotImplementedError("multiShoot_CRTBP_direct: flagEnd = true needs the box-bounded tau updates and the beta penalty "
+                                  "(direct.jl:278-292, :353-369) -- a bound-constrained QP, not covered by the exact "
+                                  "equality-constrained QP step; use flagEnd = false (the reference demo's setting)")
+    del plot_yn, β                                        # no plotting; beta only enters with flagEnd
+    X = np.array(X_all, dtype=np.float64, order="F")
+    U = np.array(u_all, dtype=np.float64, order="F")
+    t = np.array(t_TU, dtype=np.float64)
+    dV1 = np.array(dV1, dtype=np.float64).reshape(3)
+    dV2 = np.array(dV2, dtype=np.float64).reshape(3)
+    nstate = X.shape[0]
+    assert X.shape[1] == n_nodes
+    state_0, state_f = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU)
+    maxIter = int(maxIter)
+    if ops is None:
+        tg = hotpath.direct_targets(state_0, state_f, mass, dV1, dV2)
+        X, U, dV, t, defect, status, iters, hist = hotpath.direct_solve(X, U, t, nsteps, MU, DU, TU, Isp, tg, allowImpulsive, maxIter)
+        if verbose:
+            for k in range(iters):
+                print("Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f." % (k + 1, hist[0, k], hist[1, k], hist[2, k]))
+        multiShoot_CRTBP_direct.last = {"status": status, "iterations": iters, "history": hist}
+        return X, U, τ1, τ2, t, dV[:3].copy(), dV[3:].copy(), defect
+    t0, tf = t[0], t[-1]
+    tau = (t - t0) / (tf - t0) * 2 - 1                   # :480
+    t_fixed = t0 + (tau + 1) / 2 * (tf - t0)              # t_TU_fixed (:321) = t after the first update (:582)
+    defect, _ = ops.defect(X, U, t, nsteps)               # :485
+    hist = np.full((3, max(maxIter, 1)), np.nan)
+    it, er, status = 0, 1.0, 0                            # er = 1.0: at least one step (:488)
+    while er > 1e-6:                                      # :491 (NaN leaves the loop)
+        it += 1
+        if it > maxIter:
+            it, status = maxIter, 1
+            break
+        Jt, _ = ops.jacobian(X, U, t, nsteps)
+        x_up, u_up, dV1_up, dV2_up, cost = direct_qp_dense(Jt, defect, X, U, t_fixed, state_0, state_f, mass, dV1, dV2, DU, TU,
+                                                           allowImpulsive)
+        if not np.isfinite(cost):
+            status = 3
+            break
+        alpha = 1.0
+        if it > 10:                                       # :557-560
+            alpha = lineSearch_direct(X, x_up, U, u_up, t_fixed, nstate, n_nodes, nsteps, Isp, MU, DU, TU, ops=ops)
+        X = X + x_up * alpha
+        U = U + u_up * alpha
+        dV1 = dV1 + dV1_up * alpha
+        dV2 = dV2 + dV2_up * alpha
+        t = t_fixed
+        defect, _ = ops.defect(X, U, t, nsteps)           # :585
+        er = float(np.abs(defect).max())
+        hist[:, it - 1] = (er, cost, alpha)
+        if verbose:
+            print("Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f." % (it, er, cost, alpha))
+    if status == 0 and not np.isfinite(er):
+        status = 2
+    multiShoot_CRTBP_direct.last = {"status": status, "iterations": it, "history": hist[:, :maxIter]}
+    return X, U, τ1, τ2, t, dV1, dV2, defect
 
 
 def lineSearch_direct(X_all, x_update, u_all, u_update, t_TU, nstate, n_nodes, nsteps, Isp, MU, DU, TU, ops=None):

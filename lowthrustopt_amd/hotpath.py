@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from .constants import RK4, RKF78_FIXED, RKF78_ADAPTIVE, DOP853_ADAPTIVE  # noqa: F401
-from ._lib import LtoError, LtoIntegrator, LtoParams, LtoDirectParams, LTO_EINVAL
+from ._lib import LtoError, LtoIntegrator, LtoParams, LtoDirectParams, LtoDirectTargets, LTO_EINVAL
 
 
 def integrator(method=DOP853_ADAPTIVE, steps=0, rtol=1e-13, atol=1e-13, max_steps=0):
@@ -653,6 +653,78 @@ def direct_jacobianCalc(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None, w
     return direct_scatter(Jt, dtf if with_tf else None)
 
 
+def direct_targets(s0, sf, mass, dV1, dV2):
+    """lto_direct_targets: interpolated end states s0, sf (6 each), initial mass, current impulses dV1, dV2 (3 each)."""
+    t = LtoDirectTargets()
+    t.s0[:] = [float(v) for v in np.asarray(s0, dtype=np.float64).reshape(6)]
+    t.sf[:] = [float(v) for v in np.asarray(sf, dtype=np.float64).reshape(6)]
+    t.mass = float(mass)
+    t.dV1[:] = [float(v) for v in np.asarray(dV1, dtype=np.float64).reshape(3)]
+    t.dV2[:] = [float(v) for v in np.asarray(dV2, dtype=np.float64).reshape(3)]
+    return t
+
+
+def _targets_array(targets):
+    """One lto_direct_targets or a sequence of them (one per trajectory) -> (ctypes array, count)."""
+    if isinstance(targets, LtoDirectTargets):
+        targets = [targets]
+    arr = (LtoDirectTargets * len(targets))(*targets)
+    return arr, len(targets)
+
+
+def direct_qp_step(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive=False, ctx=None):
+    """One Jacobian sweep and one QP step of the direct method (optimizeTraj, direct.jl:248-403, for flagEnd = false, beta = 0,
+    tf fixed) on the device: returns (x_update[nstate x n], u_update[3 x n], dV_update[6] = (dV1_jump; dV2_jump), cost).
+    A trailing batch axis on X_all / u_all solves several problems at once (targets: one, or one per trajectory); the outputs
+    then carry it too.  A singular KKT system raises LtoError(LTO_ESINGULAR)."""
+    ctx = ctx or default_context()
+    X = _f64(X_all)
+    U = _f64(u_all)
+    ns, n, B, batched = _batch_dims(X)
+    t, ntg = _tgrids(t_TU, n, B)
+    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    tg, ntgt = _targets_array(targets)
+    dX = np.zeros((ns, n, B), order="F")
+    dU = np.zeros((3, n, B), order="F")
+    dV = np.zeros((6, B), order="F")
+    cost = np.zeros(B)
+    ctx.check(ctx.fn("direct_qp_step")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
+                                         C.cast(tg, C.c_void_p), ntgt, 1 if allowImpulsive else 0, _ptr(dX), _ptr(dU), _ptr(dV),
+                                         _ptr(cost)))
+    if not batched:
+        return dX[:, :, 0], dU[:, :, 0], dV[:, 0], float(cost[0])
+    return dX, dU, dV, cost
+
+
+def direct_solve(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive=False, maxIter=100, ctx=None):
+    """The loop of multiShoot_CRTBP_direct (direct.jl:477-594) on the device, trajectories resident in HBM (lto_direct_solve_batch).
+    Returns (X_all, u_all, dV[6] = (dV1; dV2), t_TU, defect, status, iterations, history[3 x maxIter] = (max|defect|, cost, alpha));
+    status 0 converged, 1 maxIter, 2 NaN, 3 singular KKT system.  A trailing batch axis solves several problems in one loop."""
+    ctx = ctx or default_context()
+    X = _f64(X_all)
+    U = _f64(u_all)
+    ns, n, B, batched = _batch_dims(X)
+    t, ntg = _tgrids(t_TU, n, B)
+    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    tg, ntgt = _targets_array(targets)
+    mi = int(maxIter)
+    Xo = np.zeros((ns, n, B), order="F")
+    Uo = np.zeros((3, n, B), order="F")
+    dV = np.zeros((6, B), order="F")
+    to = np.zeros((n, B), order="F")
+    defect = np.zeros((ns, n - 1, B), order="F")
+    status = np.zeros(B, dtype=np.int32)
+    iters = np.zeros(B, dtype=np.int32)
+    hist = np.full((3, max(mi, 1), B), np.nan, order="F")
+    ctx.check(ctx.fn("direct_solve_batch")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
+                                             C.cast(tg, C.c_void_p), ntgt, 1 if allowImpulsive else 0, mi, _ptr(Xo), _ptr(Uo),
+                                             _ptr(dV), _ptr(to), _ptr(defect), _ptr(status), _ptr(iters), _ptr(hist)))
+    hist = hist[:, :mi]
+    if not batched:
+        return (Xo[:, :, 0], Uo[:, :, 0], dV[:, 0], to[:, 0], defect[:, :, 0], int(status[0]), int(iters[0]), hist[:, :, 0])
+    return Xo, Uo, dV, to, defect, status, iters, hist
+
+
 # ------------------------------------------------------------------------------------------------
 # Device-resident plans (operands stay in HBM; SoA layouts of include/lto.h)
 # ------------------------------------------------------------------------------------------------
@@ -794,6 +866,19 @@ class DirectPlan:
         self.ctx.check(self.ctx.lib.lto_direct_jacobian_dev(self.handle, stream, _dptr(X), int(ldx), _dptr(U), int(ldu),
                                                             _dptr(t), int(n_tgrids), _dptr(Jac), int(ldj), _dptr(dtf),
                                                             _dptr(defect), int(ldd), _dptr(errors)))
+
+    def qp_step(self, Jac, ldj, defect, ldd, X, ldx, U, ldu, t, n_tgrids, targets, dX, dU, dV, cost, allowImpulsive=False,
+                stream=None):
+        """The QP step on device arrays (lto_direct_qp_step_dev): targets is a device array of n_batch lto_direct_targets (19 float64
+        each: s0, sf, mass, dV1, dV2); dX [nstate][ldx], dU [3][ldu], dV [n_batch][6], cost [n_batch]."""
+        self.ctx.check(self.ctx.lib.lto_direct_qp_step_dev(self.handle, stream, _dptr(Jac), int(ldj), _dptr(defect), int(ldd),
+                                                           _dptr(X), int(ldx), _dptr(U), int(ldu), _dptr(t), int(n_tgrids),
+                                                           _dptr(targets), 1 if allowImpulsive else 0, _dptr(dX), _dptr(dU),
+                                                           _dptr(dV), _dptr(cost)))
+
+    def qp_status_ptr(self):
+        """Device int [n_batch] of the last QP step: 1 = singular KKT system (lto_direct_plan_qp_status)."""
+        return self.ctx.lib.lto_direct_plan_qp_status(self.handle)
 
     def close(self):
         if getattr(self, "handle", None):

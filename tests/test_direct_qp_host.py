@@ -1,0 +1,180 @@
+"""CPU: the direct method's QP step and loop (multiShoot_CRTBP_direct, flagEnd = false) on the host, and the new C ABI entry
+points' argument checks without a device."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import lowthrustopt_amd as lto
+from lowthrustopt_amd import _lib, drivers, synth
+from oracle import oracle as O
+
+C2 = (lto.DU / lto.TU) ** 2
+
+
+def _problem(n, ns, seed):
+    X, U, T = synth.direct_problem(n, nstate=ns, seed=seed)
+    X, U, t = X[:, :, 0], U[:, :, 0], T[:, 0]
+    rng = np.random.default_rng(seed)
+    s0 = X[:6, 0] + 1e-3 * rng.standard_normal(6)
+    sf = X[:6, -1] + 1e-3 * rng.standard_normal(6)
+    dV1, dV2 = 1e-3 * rng.standard_normal(3), 1e-3 * rng.standard_normal(3)
+    return X, U, t, s0, sf, 1000.0, dV1, dV2
+
+
+def _qp_matrices(Jt, d, X, U, t, s0, sf, mass, dV1, dV2, imp):
+    """The same QP written out independently: min z'Qz + 2q'z s.t. Az = b, z = (dx node-major, du, dV1_jump, dV2_jump)."""
+    ns, _, S = Jt.shape
+    n = S + 1
+    nz = ns * n + 3 * n + 6
+    iu, iv = ns * n, ns * n + 3 * n
+    w = np.zeros(n)
+    w[:-1] += np.diff(t) / 2
+    w[1:] += np.diff(t) / 2
+    Q, q = np.zeros(nz), np.zeros(nz)
+    Q[iu:iv] = np.repeat(w, 3)
+    q[iu:iv] = (U * w[None, :]).T.reshape(-1)
+    Q[iv:] = C2
+    q[iv:] = C2 * np.r_[dV1, dV2]
+    A, b = [], []
+    for i in range(S):
+        r = np.zeros((ns, nz))
+        r[:, ns * i:ns * (i + 2)] = Jt[:, :2 * ns, i]
+        r[:, iu + 3 * i:iu + 3 * i + 6] = Jt[:, 2 * ns:, i]
+        A.append(r)
+        b.append(-d[:, i])
+    for k, s, dv, o in ((0, s0, dV1, 0), (n - 1, sf, dV2, 3)):
+        r = np.zeros((6, nz))
+        r[:, ns * k:ns * k + 6] = np.eye(6)
+        r[3:, iv + o:iv + o + 3] = np.eye(3)
+        A.append(r)
+        b.append(s - X[:6, k] - np.r_[0, 0, 0, dv])
+    if ns == 7:
+        r = np.zeros((1, nz))
+        r[0, 6] = 1
+        A.append(r)
+        b.append([mass - X[6, 0]])
+    if not imp:
+        r = np.zeros((6, nz))
+        r[:, iv:] = np.eye(6)
+        A.append(r)
+        b.append(np.zeros(6))
+    return np.vstack(A), np.concatenate([np.atleast_1d(v) for v in b]), Q, q
+
+
+def _nullspace_solve(A, b, Q, q):
+    """Parametrise the feasible set by the SVD of A (z = z0 + N y) and minimise over y."""
+    Uu, s, Vt = np.linalg.svd(A)
+    r = int(np.sum(s > s[0] * 1e-13))
+    z0 = Vt[:r].T @ ((Uu[:, :r].T @ b) / s[:r])
+    N = Vt[r:].T
+    y = np.linalg.solve(N.T @ (Q[:, None] * N), -N.T @ (Q * z0 + q))
+    return z0 + N @ y, N
+
+
+@pytest.mark.parametrize("ns", [6, 7])
+@pytest.mark.parametrize("n", [4, 9, 16])
+@pytest.mark.parametrize("imp", [False, True])
+def test_dense_qp_matches_nullspace_solve(ns, n, imp):
+    X, U, t, s0, sf, mass, dV1, dV2 = _problem(n, ns, seed=n + 10 * ns)
+    Jt, _, d = O.direct_jacobian_dual(X, U, t, 10, lto.MU, lto.DU, lto.TU, 2000.0)
+    dx, du, v1, v2, cost = drivers.direct_qp_dense(Jt, d, X, U, t, s0, sf, mass, dV1, dV2, lto.DU, lto.TU, allowImpulsive=imp)
+    z = np.concatenate([dx.T.reshape(-1), du.T.reshape(-1), v1, v2])
+    A, b, Q, q = _qp_matrices(Jt, d, X, U, t, s0, sf, mass, dV1, dV2, imp)
+    zn, N = _nullspace_solve(A, b, Q, q)
+    assert np.linalg.norm(z - zn) <= 1e-9 * np.linalg.norm(zn)
+    # KKT residual: primal feasibility and the gradient's component in the feasible directions
+    assert np.linalg.norm(A @ z - b) <= 1e-12 * (np.linalg.norm(A) * np.linalg.norm(z) + np.linalg.norm(b))
+    g = 2 * (Q * z + q)
+    assert np.linalg.norm(N.T @ g) <= 1e-12 * (np.linalg.norm(2 * Q * z) + np.linalg.norm(2 * q))
+    if not imp:
+        assert np.all(v1 == 0) and np.all(v2 == 0)
+    w = np.zeros(n)
+    w[:-1] += np.diff(t) / 2
+    w[1:] += np.diff(t) / 2
+    ref_cost = np.sum(w * np.sum((U + du) ** 2, axis=0)) + C2 * (np.sum((dV1 + v1) ** 2) + np.sum((dV2 + v2) ** 2))
+    assert abs(cost - ref_cost) <= 1e-12 * ref_cost
+
+
+def test_interp_end_states_natural_spline():
+    from scipy.interpolate import CubicSpline
+    t1, t2 = synth.halo_orbits()
+    times1, times2 = np.linspace(0, 1, t1.shape[1]), np.linspace(0, 1, t2.shape[1])
+    cs1 = CubicSpline(times1, t1[:6], axis=1, bc_type="natural")
+    cs2 = CubicSpline(times2, t2[:6], axis=1, bc_type="natural")
+    for tau1, tau2 in ((0.75, 0.5), (0.0, 1.0), (0.123, 0.987), (1.75, -0.25), (-2.3, 3.6)):
+        s0, sf = drivers.interpEndStates(tau1, tau2, times1, t1, times2, t2, lto.MU)
+        w1, w2 = tau1 % 1.0 if not (0 <= tau1 <= 1) else tau1, tau2 % 1.0 if not (0 <= tau2 <= 1) else tau2
+        assert np.abs(s0 - cs1(w1)).max() <= 1e-14 * max(1.0, np.abs(t1).max())
+        assert np.abs(sf - cs2(w2)).max() <= 1e-14 * max(1.0, np.abs(t2).max())
+
+
+class OracleDirectOps:
+    """CPU back end of the direct loop: the oracle's sweeps (test infrastructure)."""
+
+    def __init__(self, Isp):
+        self.Isp = Isp
+
+    def defect(self, X, U, t, nsteps):
+        return O.direct_defect(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, self.Isp)
+
+    def jacobian(self, X, U, t, nsteps):
+        Jt, _, d = O.direct_jacobian_dual(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, self.Isp)
+        return Jt, d
+
+    def defect_batch_sumsq(self, Xb, Ub, t, nsteps):
+        return np.array([np.sum(self.defect(Xb[:, :, k], Ub[:, :, k], t, nsteps)[0] ** 2) for k in range(Xb.shape[2])])
+
+
+@pytest.mark.parametrize("ns", [6, 7])
+def test_python_loop_converges_on_oracle(ns):
+    n = 8
+    X, U, T = synth.direct_problem(n, nstate=ns, seed=5)
+    X, U, t = X[:, :, 0].copy(), U[:, :, 0].copy(), T[:, 0]
+    tabs = synth.halo_orbits()
+    times = [np.linspace(0, 1, tb.shape[1]) for tb in tabs]
+    s0, sf = drivers.interpEndStates(0.3, 0.6, times[0], tabs[0], times[1], tabs[1])
+    # guess: the stacked synthetic nodes with the interpolated end states planted, i.e. defects everywhere
+    X[:6, 0], X[:6, -1] = s0, sf
+    out = drivers.multiShoot_CRTBP_direct(X, U, 0.3, 0.6, t, np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, n, 10, 1000.0, 2000.0,
+                                          times[0], tabs[0], times[1], tabs[1], False, False, 0.0, False, 20,
+                                          ops=OracleDirectOps(2000.0), verbose=False)
+    Xo, Uo, tau1, tau2, to, dV1, dV2, defect = out
+    last = drivers.multiShoot_CRTBP_direct.last
+    assert last["status"] == 0 and 1 <= last["iterations"] <= 20
+    assert np.abs(defect).max() <= 1e-6
+    assert np.abs(Xo[:6, 0] - s0).max() < 1e-9 and np.abs(Xo[:6, -1] - sf).max() < 1e-9
+    assert np.all(dV1 == 0) and np.all(dV2 == 0) and (tau1, tau2) == (0.3, 0.6)
+
+
+def test_flag_end_is_out_of_scope():
+    X, U, T = synth.direct_problem(4)
+    tabs = synth.halo_orbits()
+    times = [np.linspace(0, 1, tb.shape[1]) for tb in tabs]
+    with pytest.raises(NotImplementedError, match="flagEnd"):
+        drivers.multiShoot_CRTBP_direct(X[:, :, 0], U[:, :, 0], 0.3, 0.6, T[:, 0], np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, 4,
+                                        10, 1000.0, 2000.0, times[0], tabs[0], times[1], tabs[1], False, True, 1.0, False, 5,
+                                        ops=OracleDirectOps(2000.0), verbose=False)
+
+
+def test_direct_qp_entry_points_without_a_device():
+    lib = lto.load_library()
+    for name in ("lto_direct_qp_step", "lto_direct_qp_step_dev", "lto_direct_plan_qp_status", "lto_direct_solve",
+                 "lto_direct_solve_batch"):
+        assert hasattr(lib, name) and name in _lib.SIGNATURES
+    assert C.sizeof(_lib.LtoDirectTargets) == 19 * 8
+    x = np.zeros(64)
+    p = x.ctypes.data_as(C.c_void_p)
+    prm = _lib.LtoDirectParams(lto.MU, lto.DU, lto.TU, 2000.0)
+    tg = lto.direct_targets(np.zeros(6), np.zeros(6), 1000.0, np.zeros(3), np.zeros(3))
+    st = (C.c_int * 1)()
+    # NULL context / plan
+    assert lib.lto_direct_qp_step(None, 6, 4, 1, p, p, p, 1, 10, C.byref(prm), C.byref(tg), 1, 0, p, p, p, p) == _lib.LTO_ENULL
+    assert lib.lto_direct_qp_step_dev(None, None, p, 3, p, 3, p, 4, p, 4, p, 1, p, 0, p, p, p, p) == _lib.LTO_ENULL
+    assert lib.lto_direct_solve(None, 7, 4, p, p, p, 10, C.byref(prm), C.byref(tg), 0, 10, p, p, p, p, p, st, None, None) == _lib.LTO_ENULL
+    assert lib.lto_direct_plan_qp_status(None) is None
+    # bad shapes
+    for ns, n in ((5, 4), (8, 4), (12, 4), (6, 1), (7, 0)):
+        assert lib.lto_direct_qp_step(None, ns, n, 1, p, p, p, 1, 10, C.byref(prm), C.byref(tg), 1, 0, p, p, p, p) == _lib.LTO_EINVAL
+        assert lib.lto_direct_solve_batch(None, ns, n, 1, p, p, p, 1, 10, C.byref(prm), C.byref(tg), 1, 0, 10, p, p, p, p, p, st, None,
+                                          None) == _lib.LTO_EINVAL

@@ -1,0 +1,205 @@
+"""GPU: the direct method's QP step (lto_direct_qp_step, kernels_direct_qp.hip) against the host KKT solve built from the same
+device Jacobian blocks, and the device loop of multiShoot_CRTBP_direct (lto_direct_solve / _batch) on the reference demo."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+import lowthrustopt_amd as lto
+from lowthrustopt_amd import drivers, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ISP, NSTEPS = 2000.0, 10
+
+
+def _problems(n, ns, B, seed):
+    """B different problems: own time grids (segment lengths scaled by 1 + 0.1 b) and own targets."""
+    X, U, T = synth.direct_problem(n, n_batch=B, nstate=ns, seed=seed)
+    T = T * (1.0 + 0.1 * np.arange(B))[None, :]
+    rng = np.random.default_rng(seed)
+    tg, tg_np = [], []
+    for b in range(B):
+        s0 = X[:6, 0, b] + 1e-4 * rng.standard_normal(6)
+        sf = X[:6, -1, b] + 1e-4 * rng.standard_normal(6)
+        dV1, dV2 = 1e-4 * rng.standard_normal(3), 1e-4 * rng.standard_normal(3)
+        tg.append(lto.direct_targets(s0, sf, 1000.0 - b, dV1, dV2))
+        tg_np.append((s0, sf, 1000.0 - b, dV1, dV2))
+    return np.asfortranarray(X), np.asfortranarray(U), np.asfortranarray(T), tg, tg_np
+
+
+def _host_qp_sparse(Jt, d, X, U, t, s0, sf, mass, dV1, dV2, imp):
+    """The same KKT system as drivers.direct_qp_dense, sparse, for the one large case."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spl
+    ns, _, S = Jt.shape
+    n = S + 1
+    nz = ns * n + 3 * n + 6
+    iu, iv = ns * n, ns * n + 3 * n
+    w = np.zeros(n)
+    w[:-1] += np.diff(t) / 2
+    w[1:] += np.diff(t) / 2
+    c2 = (lto.DU / lto.TU) ** 2
+    Q = np.r_[np.zeros(ns * n), np.repeat(w, 3), c2 * np.ones(6)]
+    q = np.r_[np.zeros(ns * n), (U * w[None, :]).T.reshape(-1), c2 * dV1, c2 * dV2]
+    rows, cols, vals, b = [], [], [], []
+    r0 = 0
+    for i in range(S):
+        for a in range(ns):
+            for c in range(2 * ns):
+                rows.append(r0 + a); cols.append(ns * i + c); vals.append(Jt[a, c, i])
+            for c in range(6):
+                rows.append(r0 + a); cols.append(iu + 3 * i + c); vals.append(Jt[a, 2 * ns + c, i])
+        b.extend(-d[:, i]); r0 += ns
+    for k, s, dv, o in ((0, s0, dV1, 0), (n - 1, sf, dV2, 3)):
+        for j in range(6):
+            rows.append(r0 + j); cols.append(ns * k + j); vals.append(1.0)
+            if j >= 3:
+                rows.append(r0 + j); cols.append(iv + o + j - 3); vals.append(1.0)
+        b.extend(s - X[:6, k] - np.r_[0, 0, 0, dv]); r0 += 6
+    if ns == 7:
+        rows.append(r0); cols.append(6); vals.append(1.0); b.append(mass - X[6, 0]); r0 += 1
+    if not imp:
+        for j in range(6):
+            rows.append(r0 + j); cols.append(iv + j); vals.append(1.0)
+        b.extend(np.zeros(6)); r0 += 6
+    A = sp.csr_matrix((vals, (rows, cols)), shape=(r0, nz))
+    K = sp.bmat([[sp.diags(2 * Q), A.T], [A, None]]).tocsc()
+    rhs = np.r_[-2 * q, b]
+    D = np.ones(K.shape[0])
+    for _ in range(20):
+        Ks = sp.diags(D) @ K @ sp.diags(D)
+        D = D / np.sqrt(np.maximum(abs(Ks).max(axis=1).toarray().ravel(), 1e-300))
+    z = spl.spsolve((sp.diags(D) @ K @ sp.diags(D)).tocsc(), rhs * D) * D
+    return z[:ns * n].reshape(n, ns).T, z[iu:iv].reshape(n, 3).T, (z[iv:iv + 6] if imp else np.zeros(6))
+
+
+def _rel(a, b):
+    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
+
+
+def _check_step(Jt, d, X, U, t, tgt, imp, dX, dU, dV, cost, dense=True):
+    s0, sf, mass, dV1, dV2 = tgt
+    if dense:
+        hx, hu, h1, h2, hc = drivers.direct_qp_dense(Jt, d, X, U, t, s0, sf, mass, dV1, dV2, lto.DU, lto.TU, allowImpulsive=imp)
+        hv = np.r_[h1, h2]
+        assert abs(cost - hc) <= 1e-9 * abs(hc)
+    else:
+        hx, hu, hv = _host_qp_sparse(Jt, d, X, U, t, s0, sf, mass, dV1, dV2, imp)
+    assert _rel(dX, hx) <= 1e-9 and _rel(dU, hu) <= 1e-9
+    if imp:
+        assert _rel(dV, hv) <= 1e-9
+    else:
+        assert np.all(dV == 0)
+    ns = X.shape[0]
+    # the step satisfies the linearised defects and the end-point pins
+    lin = np.einsum("rci,ci->ri", Jt[:, :ns], dX[:, :-1]) + np.einsum("rci,ci->ri", Jt[:, ns:2 * ns], dX[:, 1:]) + \
+        np.einsum("rci,ci->ri", Jt[:, 2 * ns:2 * ns + 3], dU[:, :-1]) + np.einsum("rci,ci->ri", Jt[:, 2 * ns + 3:], dU[:, 1:]) + d
+    scale = np.abs(d).max() + np.abs(Jt).max() * (np.abs(dX).max() + np.abs(dU).max())
+    assert np.abs(lin).max() <= 1e-12 * scale
+    e0 = X[:6, 0] + dX[:6, 0] + np.r_[0, 0, 0, dV1 + dV[:3]] - s0
+    ef = X[:6, -1] + dX[:6, -1] + np.r_[0, 0, 0, dV2 + dV[3:]] - sf
+    assert max(np.abs(e0).max(), np.abs(ef).max()) <= 1e-12 * max(1.0, np.abs(X[:6]).max())
+    if ns == 7:
+        assert abs(X[6, 0] + dX[6, 0] - mass) <= 1e-12 * mass
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ns", [6, 7])
+@pytest.mark.parametrize("imp", [False, True])
+@pytest.mark.parametrize("n,B", [(3, 1), (17, 5), (30, 1), (257, 1), (257, 5)])
+def test_device_qp_step_matches_host_kkt(gpu_ctx, ns, imp, n, B):
+    X, U, T, tg, tg_np = _problems(n, ns, B, seed=n + ns)
+    Jt, _, d, _ = lto.direct_jacobian_blocks(X, U, T, NSTEPS, lto.MU, lto.DU, lto.TU, ISP, ctx=gpu_ctx)
+    dX, dU, dV, cost = lto.direct_qp_step(X, U, T, NSTEPS, lto.MU, lto.DU, lto.TU, ISP, tg, allowImpulsive=imp, ctx=gpu_ctx)
+    for b in range(B):
+        _check_step(Jt[..., b], d[..., b], X[..., b], U[..., b], T[:, b], tg_np[b], imp, dX[..., b], dU[..., b], dV[:, b], cost[b])
+
+
+@pytest.mark.gpu
+def test_device_qp_step_large(gpu_ctx):
+    """The one large case: 4 097 nodes (a power of two + 1: every level of the reduction carries a row)."""
+    X, U, T, tg, tg_np = _problems(4097, 7, 1, seed=3)
+    Jt, _, d, _ = lto.direct_jacobian_blocks(X[..., 0], U[..., 0], T[:, 0], NSTEPS, lto.MU, lto.DU, lto.TU, ISP, ctx=gpu_ctx)
+    dX, dU, dV, cost = lto.direct_qp_step(X[..., 0], U[..., 0], T[:, 0], NSTEPS, lto.MU, lto.DU, lto.TU, ISP, tg[0], allowImpulsive=True,
+                                          ctx=gpu_ctx)
+    _check_step(Jt, d, X[..., 0], U[..., 0], T[:, 0], tg_np[0], True, dX, dU, dV, cost, dense=False)
+
+
+@pytest.mark.gpu
+def test_singular_kkt_is_reported(gpu_ctx):
+    """Controls without effect on the defect (G = H = 0) leave the pinned end states unreachable: the KKT system of the QP is
+    singular, and the device step reports it (plan status 1, NaN outputs) instead of returning NaN silently."""
+    import torch
+    ns, n = 6, 2
+    nvar = 2 * (ns + 3)
+    dev = torch.device("cuda", 0)
+    Jb = np.zeros((ns, nvar))
+    Jb[:, :ns], Jb[:, ns:2 * ns] = np.eye(ns), -np.eye(ns)
+    Jac = torch.tensor(Jb.T.reshape(-1, 1), dtype=torch.float64, device=dev).contiguous()       # [(col*ns+row)][1]
+    defect = torch.full((ns, 1), 1e-3, dtype=torch.float64, device=dev)
+    X = torch.zeros((ns, n), dtype=torch.float64, device=dev)
+    U = torch.zeros((3, n), dtype=torch.float64, device=dev)
+    t = torch.tensor([0.0, 0.1], dtype=torch.float64, device=dev)
+    tg = lto.direct_targets(np.zeros(6), np.full(6, 0.1), 1000.0, np.zeros(3), np.zeros(3))
+    tgd = torch.tensor(np.frombuffer(bytes(tg), dtype=np.float64).copy(), device=dev)
+    dX, dU = torch.zeros_like(X), torch.zeros_like(U)
+    dV, cost = torch.zeros(6, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
+    plan = lto.DirectPlan(gpu_ctx, ns, n, 1, NSTEPS, lto.MU, lto.DU, lto.TU, ISP)
+    plan.qp_step(Jac, 1, defect, 1, X, n, U, n, t, 1, tgd, dX, dU, dV, cost, stream=None)
+    torch.cuda.synchronize()
+    assert plan.qp_status_ptr()                       # the plan's status array exists after a step
+    # finite inputs: the kernels write NaN only for a trajectory whose system they found singular
+    assert torch.isnan(cost).all() and torch.isnan(dX).all() and torch.isnan(dU).all()
+    plan.close()
+
+
+def _demo():
+    spec = importlib.util.spec_from_file_location("halo_direct_demo", os.path.join(ROOT, "examples", "halo_direct_demo.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.gpu
+def test_reference_direct_demo_converges(gpu_ctx):
+    demo = _demo()
+    X, U, t, tau1, tau2, a, b, c, d = demo.demo_problem()
+    args = (tau1, tau2, t, np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, 30, NSTEPS, 1000.0, ISP, a, b, c, d, False, False, 0.0,
+            False, 100)
+    Xl, Ul, *_, defect_l = drivers.multiShoot_CRTBP_direct(X, U, *args, verbose=False)
+    lib = dict(drivers.multiShoot_CRTBP_direct.last)
+    Xp, Up, *_, defect_p = drivers.multiShoot_CRTBP_direct(X, U, *args, ops=drivers.HipDirectOps(lto.MU, lto.DU, lto.TU, ISP, gpu_ctx),
+                                                           verbose=False)
+    py = dict(drivers.multiShoot_CRTBP_direct.last)
+    print("direct demo: library loop %d iterations, history %s" % (lib["iterations"], np.array2string(lib["history"][:, :lib["iterations"]], precision=3)))
+    assert lib["status"] == 0 and np.abs(defect_l).max() <= 1e-6
+    assert py["status"] == 0 and np.abs(defect_p).max() <= 1e-6
+    assert lib["iterations"] == py["iterations"]
+    assert np.abs(Xl - Xp).max() <= 1e-8
+
+
+@pytest.mark.gpu
+def test_solve_batch_equals_single_solves(gpu_ctx):
+    demo = _demo()
+    X, U, t, tau1, tau2, a, b, c, d = demo.demo_problem()
+    B = 4
+    Xb = np.repeat(X[:, :, None], B, axis=2)
+    Ub = np.zeros((3, 30, B))
+    Tb = np.repeat(t[:, None], B, axis=1) * (1.0 + 0.05 * np.arange(B))[None, :]
+    tgs = []
+    for k in range(B):
+        s0, sf = drivers.interpEndStates(tau1 + 0.01 * k, tau2 - 0.01 * k, a, b, c, d)
+        tgs.append(lto.direct_targets(s0, sf, 1000.0, np.zeros(3), np.zeros(3)))
+    out_b = lto.direct_solve(np.asfortranarray(Xb), np.asfortranarray(Ub), np.asfortranarray(Tb), NSTEPS, lto.MU, lto.DU, lto.TU, ISP,
+                             tgs, maxIter=100, ctx=gpu_ctx)
+    for k in range(B):
+        out_s = lto.direct_solve(X, np.zeros((3, 30)), Tb[:, k], NSTEPS, lto.MU, lto.DU, lto.TU, ISP, tgs[k], maxIter=100, ctx=gpu_ctx)
+        assert out_s[5] == out_b[5][k] == 0 and out_s[6] == out_b[6][k]
+        for j in (0, 1, 4):
+            assert np.abs(out_s[j] - out_b[j][..., k]).max() <= 1e-12 * max(1.0, np.abs(out_s[j]).max())
+    # NaN input: status 2, promptly
+    Xn = X.copy()
+    Xn[0, 5] = np.nan
+    out = lto.direct_solve(Xn, np.zeros((3, 30)), t, NSTEPS, lto.MU, lto.DU, lto.TU, ISP, tgs[0], maxIter=100, ctx=gpu_ctx)
+    assert out[5] == 2 and out[6] <= 1
