@@ -6,6 +6,10 @@ halo_transfer_demo.py: tau1 = 0.75, 30 nodes over 20 days), zero thrust, nsteps 
 flagEnd = false, beta = 0, no impulses, at most 100 iterations.  The whole loop -- Jacobian sweep, the minimum-energy QP step
 solved exactly on the device, the batched line search -- is one lto_direct_solve call.  With --then-indirect the smoothed
 states are handed to the indirect method (p = 2, adjoints only first), the reference's sequence.
+
+--free-ends [beta] runs the reference's other mode, flagEnd = true (default beta = 0): odd iterations also move the departure and
+arrival phases tau1, tau2 (by at most 0.1 per step), so the transfer finds where on the two orbits it starts and ends.  The run
+starts from tau2 offset by --tau2-offset (default 0.02) from the stacked value and prints the final phases.
 """
 import importlib.util
 import os
@@ -42,19 +46,22 @@ def demo_problem(n_nodes=30, tof_days=20.0, tau1=0.75):
     return X, U, t, tau1, tau2, times[0], tabs[0], times[1], tabs[1]
 
 
-def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100):
+def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100, free_ends=None, tau2_offset=0.0):
     ctx = lto.default_context(0)
     X, U, t, tau1, tau2, t0s, X0s, tfs, Xfs = demo_problem()
+    tau2 += tau2_offset
     n, nsteps, Isp, mass = X.shape[1], 10, 2000.0, 1000.0
     ops = drivers.HipDirectOps(MU, DU, TU, Isp, ctx) if python_loop else None
     t0 = time.perf_counter()
+    flag_end = free_ends is not None
     X, U, tau1, tau2, t, dV1, dV2, defect = drivers.multiShoot_CRTBP_direct(
-        X, U, tau1, tau2, t, np.zeros(3), np.zeros(3), MU, DU, TU, n, nsteps, mass, Isp, t0s, X0s, tfs, Xfs, False, False, 0.0,
-        False, maxIter, ops=ops, verbose=verbose)
+        X, U, tau1, tau2, t, np.zeros(3), np.zeros(3), MU, DU, TU, n, nsteps, mass, Isp, t0s, X0s, tfs, Xfs, False, flag_end,
+        float(free_ends or 0.0), False, maxIter, ops=None if flag_end else ops, verbose=verbose)
     last = drivers.multiShoot_CRTBP_direct.last
-    res = {"direct": (last["status"], last["iterations"], float(np.abs(defect).max())), "X": X, "U": U}
-    print("direct: status %d after %d iterations, max defect %.2e, max thrust %.3f N (%.2f s)" % (
-        last["status"], last["iterations"], np.abs(defect).max(), np.linalg.norm(U, axis=0).max(), time.perf_counter() - t0))
+    res = {"direct": (last["status"], last["iterations"], float(np.abs(defect).max())), "X": X, "U": U, "tau": (tau1, tau2)}
+    print("direct%s: status %d after %d iterations, max defect %.2e, cost %.6f, tau = (%.9f, %.9f), max thrust %.3f N (%.2f s)" % (
+        " (free ends, beta = %g)" % free_ends if flag_end else "", last["status"], last["iterations"], np.abs(defect).max(),
+        last["history"][1, last["iterations"] - 1], tau1, tau2, np.linalg.norm(U, axis=0).max(), time.perf_counter() - t0))
     if then_indirect and last["status"] == 0:
         rng = np.random.default_rng(0)
         XC = np.vstack([X, 0.1 * rng.standard_normal((6, n))])
@@ -65,5 +72,21 @@ def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100):
     return res
 
 
+def _arg(flag, default):
+    """Value after `flag` (a number), the default if absent or not followed by a number, None if the flag is absent."""
+    if flag not in sys.argv:
+        return None
+    k = sys.argv.index(flag)
+    try:
+        return float(sys.argv[k + 1])
+    except (IndexError, ValueError):
+        return default
+
+
 if __name__ == "__main__":
-    main(verbose="-q" not in sys.argv, then_indirect="--then-indirect" in sys.argv, python_loop="--python-loop" in sys.argv)
+    free = _arg("--free-ends", 0.0)
+    off = _arg("--tau2-offset", 0.02)
+    if off is None:
+        off = 0.02 if free is not None else 0.0
+    main(verbose="-q" not in sys.argv, then_indirect="--then-indirect" in sys.argv, python_loop="--python-loop" in sys.argv,
+         free_ends=free, tau2_offset=off)

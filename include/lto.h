@@ -262,6 +262,52 @@ int lto_direct_solve(lto_ctx* ctx, int nstate, int n_nodes, const double* X_in, 
                      double* X_out, double* U_out, double* dV_out, double* t_out, double* defect_out, int* status,
                      int* iterations, double* history);
 
+/* ---- Free end points (flagEnd = true, src/multiShoot_CRTBP_direct.jl:278-292, :353-369, :521-569): the optimiser also moves the
+ * departure phase tau1 on orbit 1 and the arrival phase tau2 on orbit 2.  With s(.) = interpEndStates (each argument wrapped into
+ * [0, 1] on its own) and h = 0.05, the end model at (tau1, tau2) is s0 = s(tau1), g0 = (s(tau1+h) - s(tau1-h)) / 2h,
+ * c0 = (s(tau1+h) - 2 s(tau1) + s(tau1-h)) / h^2, and sf, gf, cf the same at tau2 on orbit 2.  A free step solves the frozen step's
+ * QP with the end constraints x_0[0:6] + dx_0[0:6] + [0; dV1 + d1] = s0 + g0 p1, x_{n-1}[0:6] + dx_{n-1}[0:6] + [0; dV2 + d2] =
+ * sf + gf p2, the bounds |p1|, |p2| <= 0.1 and the cost term beta (|c0|/2 p1^2 + |cf|/2 p2^2); tf stays fixed (:292). */
+typedef struct lto_direct_orbits {
+  int n0, nf;                        /* samples of the departure and arrival orbit tables (>= 2 each) */
+  const double* t0;                  /* [n0] strictly increasing normalised times (host) */
+  const double* X0;                  /* [6 x n0] column-major: the state of sample i at X0[6 i .. 6 i + 5] (host) */
+  const double* tf;                  /* [nf] */
+  const double* Xf;                  /* [6 x nf] */
+} lto_direct_orbits;
+typedef struct lto_direct_end_model {
+  double g0[6], gf[6], c0_norm, cf_norm;     /* g0, gf and the 2-norms of c0, cf */
+} lto_direct_end_model;
+/* End targets and end model of n_batch trajectories on the device: tau [2 x n_batch] = (tau1; tau2) per trajectory, s_out
+ * [12 x n_batch] = (s0; sf), model [n_batch].  The natural-spline moments of the tables are solved on the host once per call. */
+int lto_direct_end_states(lto_ctx* ctx, const lto_direct_orbits* orbits, int n_batch, const double* tau, double* s_out,
+                          lto_direct_end_model* model);
+/* One Jacobian sweep and one free-end QP step (arguments as lto_direct_qp_step); targets, model and beta [n_targets] (1 or
+ * n_batch).  p_out [2 x n_batch] = (p1; p2); cost includes the beta term.  The 2 x 2 bound-constrained problem in p is solved
+ * exactly on the device: smallest reduced cost over the interior point, the clamped edge minimisers and the corners;
+ * exact ties go to the smaller max|p|, then to that order. */
+int lto_direct_qp_step_free(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
+                            int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets,
+                            const lto_direct_end_model* model, const double* beta, int n_targets, int allow_impulsive, double* dX,
+                            double* dU, double* dV, double* p_out, double* cost);
+/* The loop of lto_direct_solve_batch with the end points taken from the orbit tables at tau: tau_in [2 x n_batch], beta
+ * [n_targets].  The mass and the impulses dV1, dV2 come from targets; its s0 and sf are ignored and recomputed from tau at the
+ * start and after every tau update.  flag_end = 1: odd iterations are free-end steps and tau += alpha p afterwards (not wrapped);
+ * even iterations are frozen-end steps at the current tau (:521-526).  flag_end = 0: every step is frozen.  tau_out [2 x n_batch]
+ * (may be NULL); history [5 x maxIter x n_batch] = (max|defect|, cost, alpha, tau1, tau2) after each iteration.  Other arguments and
+ * status codes as lto_direct_solve_batch. */
+int lto_direct_solve_free_batch(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
+                                const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
+                                const lto_direct_orbits* orbits, const lto_direct_targets* targets, int n_targets,
+                                const double* tau_in, const double* beta, int flag_end, int allow_impulsive, int maxIter,
+                                double* X_out, double* U_out, double* dV_out, double* t_out, double* defect_out, double* tau_out,
+                                int* status, int* iterations, double* history);
+int lto_direct_solve_free(lto_ctx* ctx, int nstate, int n_nodes, const double* X_in, const double* U_in, const double* t, int nsteps,
+                          const lto_direct_params* prm, const lto_direct_orbits* orbits, const lto_direct_targets* targets,
+                          const double* tau_in, double beta, int flag_end, int allow_impulsive, int maxIter, double* X_out,
+                          double* U_out, double* dV_out, double* t_out, double* defect_out, double* tau_out, int* status,
+                          int* iterations, double* history);
+
 /* ------------------------------------------------- device-resident API (operands already in HBM)
  * Struct-of-arrays, segment/node index fastest, so that a wavefront's 64 lanes read 512
  * contiguous bytes per component.  With J = n_nodes*n_batch nodes and S = (n_nodes-1)*n_batch

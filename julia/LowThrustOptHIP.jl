@@ -17,7 +17,8 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_qp_step, direct_solve, LtoDirectTargets, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_qp_step, direct_solve, direct_end_states, direct_qp_step_free, direct_solve_free,
+       LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
 const liblto = get(ENV, "LTO_HIP_LIB", joinpath(@__DIR__, "..", "lowthrustopt_amd", "liblto_hip.so"))
 
@@ -60,6 +61,16 @@ struct LtoDirectTargets
 end
 LtoDirectTargets(s0, sf, mass, dV1, dV2) = LtoDirectTargets(NTuple{6,Cdouble}(s0), NTuple{6,Cdouble}(sf), Cdouble(mass),
                                                             NTuple{3,Cdouble}(dV1), NTuple{3,Cdouble}(dV2))
+
+# the two orbit tables of the free-end model (lto_direct_orbits): the arrays must stay alive across the call (GC.@preserve)
+struct LtoDirectOrbits
+    n0::Cint; nf::Cint; t0::Ptr{Cdouble}; X0::Ptr{Cdouble}; tf::Ptr{Cdouble}; Xf::Ptr{Cdouble}
+end
+# per-trajectory end model of a free-end step (lto_direct_end_model)
+struct LtoDirectEndModel
+    g0::NTuple{6,Cdouble}; gf::NTuple{6,Cdouble}; c0_norm::Cdouble; cf_norm::Cdouble
+end
+LtoDirectEndModel(g0, gf, c0, cf) = LtoDirectEndModel(NTuple{6,Cdouble}(g0), NTuple{6,Cdouble}(gf), Cdouble(c0), Cdouble(cf))
 
 mutable struct LtoContext
     handle::Ptr{Cvoid}
@@ -326,6 +337,65 @@ function direct_solve(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Flo
                status, iters, hist)
     check(ctx, rc)
     (Xo, Uo, to, dV[1:3], dV[4:6], defect, Int(status[1]), Int(iters[1]), hist[:, 1:maxIter])
+end
+
+# Free end points (flagEnd = true, direct.jl:278-292, :353-369, :521-569).  X0_states / Xf_states are [6 x n] (rows = state).
+_orbits(X0_times, X0_states, Xf_times, Xf_states) =
+    LtoDirectOrbits(length(X0_times), length(Xf_times), pointer(X0_times), pointer(X0_states), pointer(Xf_times), pointer(Xf_states))
+
+# End targets and end model at (tau1, tau2) on the device: returns (state_0, state_f, LtoDirectEndModel).
+function direct_end_states(ctx::LtoContext, τ1, τ2, X0_times::Vector{Float64}, X0_states::Matrix{Float64}, Xf_times::Vector{Float64},
+                           Xf_states::Matrix{Float64})
+    tau = [Float64(τ1), Float64(τ2)]; s = zeros(12); model = Ref(LtoDirectEndModel(zeros(6), zeros(6), 0.0, 0.0))
+    rc = GC.@preserve X0_times X0_states Xf_times Xf_states begin
+        ob = Ref(_orbits(X0_times, X0_states, Xf_times, Xf_states))
+        ccall(entry(ctx, :direct_end_states), Cint,
+              (Ptr{Cvoid}, Ref{LtoDirectOrbits}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoDirectEndModel}), ctx.handle, ob, 1, tau, s, model)
+    end
+    check(ctx, rc)
+    (s[1:6], s[7:12], model[])
+end
+
+# optimizeTraj with flagEnd = true: one Jacobian sweep and the exact free-end QP step.  Returns (x_update, u_update, p1_update,
+# p2_update, dV1_update, dV2_update, cost).
+function direct_qp_step_free(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Float64}, t_TU::Vector{Float64}, nsteps, Isp,
+                             MU, DU, TU, state_0, state_f, model::LtoDirectEndModel, β, mass, dV1, dV2; allowImpulsive::Bool = false)
+    nstate, n_nodes = size(X_all)
+    dX = zeros(nstate, n_nodes); dU = zeros(3, n_nodes); dV = zeros(6); p = zeros(2); cost = zeros(1)
+    prm = Ref(LtoDirectParams(MU, DU, TU, Isp))
+    tg = Ref(LtoDirectTargets(state_0, state_f, mass, dV1, dV2))
+    rc = ccall(entry(ctx, :direct_qp_step_free), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ref{LtoDirectParams},
+                Ref{LtoDirectTargets}, Ref{LtoDirectEndModel}, Ref{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}),
+               ctx.handle, nstate, n_nodes, 1, X_all, u_all, t_TU, 1, nsteps, prm, tg, Ref(model), Ref(Cdouble(β)), 1, allowImpulsive,
+               dX, dU, dV, p, cost)
+    check(ctx, rc)
+    (dX, dU, p[1], p[2], dV[1:3], dV[4:6], cost[1])
+end
+
+# The loop of multiShoot_CRTBP_direct with flagEnd on the device: returns (X_all, u_all, τ1, τ2, t_TU, dV1, dV2, defect, status,
+# iterations, history [5 x maxIter] = (max|defect|, cost, alpha, τ1, τ2)).
+function direct_solve_free(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Float64}, τ1, τ2, t_TU::Vector{Float64}, nsteps,
+                           Isp, MU, DU, TU, X0_times::Vector{Float64}, X0_states::Matrix{Float64}, Xf_times::Vector{Float64},
+                           Xf_states::Matrix{Float64}, flagEnd::Bool, β, mass, dV1, dV2, maxIter::Integer; allowImpulsive::Bool = false)
+    nstate, n_nodes = size(X_all)
+    Xo = zeros(nstate, n_nodes); Uo = zeros(3, n_nodes); dV = zeros(6); to = zeros(n_nodes); defect = zeros(nstate, n_nodes - 1)
+    tau = [Float64(τ1), Float64(τ2)]; tau_o = zeros(2)
+    status = zeros(Cint, 1); iters = zeros(Cint, 1); hist = fill(NaN, 5, max(maxIter, 1))
+    prm = Ref(LtoDirectParams(MU, DU, TU, Isp))
+    tg = Ref(LtoDirectTargets(zeros(6), zeros(6), mass, dV1, dV2))
+    rc = GC.@preserve X0_times X0_states Xf_times Xf_states begin
+        ob = Ref(_orbits(X0_times, X0_states, Xf_times, Xf_states))
+        ccall(entry(ctx, :direct_solve_free), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ref{LtoDirectParams}, Ref{LtoDirectOrbits},
+               Ref{LtoDirectTargets}, Ptr{Cdouble}, Cdouble, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+               Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}),
+              ctx.handle, nstate, n_nodes, X_all, u_all, t_TU, nsteps, prm, ob, tg, tau, β, flagEnd, allowImpulsive, maxIter, Xo, Uo,
+              dV, to, defect, tau_o, status, iters, hist)
+    end
+    check(ctx, rc)
+    (Xo, Uo, tau_o[1], tau_o[2], to, dV[1:3], dV[4:6], defect, Int(status[1]), Int(iters[1]), hist[:, 1:maxIter])
 end
 
 # The operands stay in HBM between calls (struct-of-arrays, see include/lto.h "device-resident API"); every function

@@ -39,6 +39,16 @@ class LtoDirectTargets(C.Structure):
                 ("dV2", C.c_double * 3)]
 
 
+class LtoDirectOrbits(C.Structure):
+    """The two orbit tables of the free-end model: sample counts, times, 6 x n states (column-major)."""
+    _fields_ = [("n0", C.c_int), ("nf", C.c_int), ("t0", C.c_void_p), ("X0", C.c_void_p), ("tf", C.c_void_p), ("Xf", C.c_void_p)]
+
+
+class LtoDirectEndModel(C.Structure):
+    """Per-trajectory end model of a free-end step: g0, gf (first differences) and the 2-norms of c0, cf (second differences)."""
+    _fields_ = [("g0", C.c_double * 6), ("gf", C.c_double * 6), ("c0_norm", C.c_double), ("cf_norm", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 
@@ -126,6 +136,15 @@ SIGNATURES = {
     "lto_direct_plan_qp_status": (_vp, [_vp]),
     "lto_direct_solve_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(LtoDirectParams),
                                          _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_direct_end_states": (C.c_int, [_vp, C.POINTER(LtoDirectOrbits), C.c_int, _vp, _vp, _vp]),
+    "lto_direct_qp_step_free": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(LtoDirectParams),
+                                          _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lto_direct_solve_free_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int,
+                                              C.POINTER(LtoDirectParams), C.POINTER(LtoDirectOrbits), _vp, C.c_int, _vp, _vp, C.c_int,
+                                              C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_direct_solve_free": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams),
+                                        C.POINTER(LtoDirectOrbits), _vp, _vp, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp]),
     "lto_direct_solve": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams), _vp, C.c_int, C.c_int,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_pack_soa_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_long, _vp, C.c_long]),

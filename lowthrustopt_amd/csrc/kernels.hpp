@@ -131,11 +131,24 @@ struct DirectQpArgs {
   double* dV;                      // [n_batch][6]: impulse updates at node 0 and node n-1
   double* cost;                    // [n_batch]
   double* singular;                // [n_batch] or null: 1.0 where the trajectory's KKT system is singular
+  // free ends only (launch_direct_qp_free)
+  const double* model;             // [n_batch][14] (lto_direct_end_model): g0[6], gf[6], |c0|, |cf|
+  const double* beta;              // [n_batch]
+  double* p;                       // [n_batch][2]: the phase updates p1, p2
 };
-size_t direct_qp_workspace_bytes(int nstate, int n_nodes, int n_batch);
-int* direct_qp_status(void* workspace, int nstate, int n_nodes, int n_batch);   // [n_batch] inside the workspace: 1 = singular
+// workspace of either step: nr = 1 (frozen ends) or 3 (free ends: three right-hand sides)
+size_t direct_qp_workspace_bytes(int nstate, int n_nodes, int n_batch, int nr);
+int* direct_qp_status(void* workspace, int n_batch);   // [n_batch] inside the workspace: 1 = singular
 hipError_t launch_direct_qp(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st);
+// free ends (flagEnd = true): the same reduction with the right-hand sides z0 | dz/dp1 | dz/dp2, then the 2 x 2 box QP in p
+hipError_t launch_direct_qp_free(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st);
 hipError_t launch_direct_qp_update_dv(double* targets, const double* dV, const double* step, int n_batch, hipStream_t st);
+// the two orbit tables of the free-end model on the device: times [n], states and natural-spline second derivatives [n][6]
+struct EndOrbitsDev { int n[2]; const double* t[2]; const double* Y[2]; const double* M[2]; };
+// per trajectory b: s[b * s_stride + 0..11] = (s0; sf) at tau[2b], tau[2b+1], model[b][14] = (g0; gf; |c0|; |cf|)
+hipError_t launch_end_states(const EndOrbitsDev& o, const double* tau, int n_batch, double* s, int s_stride, double* model,
+                             hipStream_t st);
+hipError_t launch_tau_update(double* tau, const double* p, const double* step, int n_batch, hipStream_t st);
 
 // Newton step of the indirect method on the device (kernels_bvp.hip): structured orthogonal cyclic reduction.
 size_t bvp_workspace_doubles(int n_nodes, int n_batch);

@@ -30,13 +30,14 @@
 
 namespace lto {
 
-template <int NS>
+// NR right-hand sides: 1 for the frozen-end step, 3 for the free-end step (z0 | dz/dp1 | dz/dp2, kernels below and DESIGN 4.8c)
+template <int NS, int NR = 1>
 struct QpDims {
   static constexpr int NB = 2 * NS + 3;          // unknowns per node: dx (NS), du (3), lambda (NS)
   static constexpr int R2 = 2 * NB;              // rows of a pair's stack
-  static constexpr int NCOLS = 3 * NB + 1;       // mid | left | right | rhs
-  static constexpr int ROW = 2 * NB * NB + NB;   // A (NB x NB), B (NB x NB), r (NB), column-major
-  static constexpr int REC_R = 0, REC_CA = NB * NB, REC_CB = 2 * NB * NB, REC_G = 3 * NB * NB, REC = 3 * NB * NB + NB;
+  static constexpr int NCOLS = 3 * NB + NR;      // mid | left | right | rhs (NR)
+  static constexpr int ROW = 2 * NB * NB + NR * NB;   // A (NB x NB), B (NB x NB), r (NB x NR), column-major
+  static constexpr int REC_R = 0, REC_CA = NB * NB, REC_CB = 2 * NB * NB, REC_G = 3 * NB * NB, REC = 3 * NB * NB + NR * NB;
   static_assert(NCOLS <= 64, "one wavefront per pair");
 };
 
@@ -52,10 +53,14 @@ struct QpArgs {
   double c2;                         // (DU/TU)^2
   unsigned long long* gw;            // [n_batch][2]: bits of max |G|,|H| and of max dt (non-negative doubles order as integers)
   double* rec;                       // [n_batch][n_nodes][REC]
-  double* Y; long ldy;               // solution, scaled unknowns: Y[c*ldy + b*n_nodes + k]
+  double* Y; long ldy;               // solution, scaled unknowns: Y[(m*NB + c)*ldy + b*n_nodes + k], m = right-hand side
   int* status;                       // [n_batch]: 0 ok, 1 singular KKT system
+  const double* em;                  // free ends only: end model [n_batch][QP_MODEL]: g0[6], gf[6], |c0|, |cf| (lto_direct_end_model)
+  const double* beta;                // free ends only: [n_batch]
 };
 constexpr int QP_TARGET = 19;
+constexpr int QP_MODEL = 14;
+constexpr double QP_PBOUND = 0.1;    // |p1|, |p2| <= 0.1 (:280-284)
 
 struct QpScale { double su, ru, sl, rx; };
 __device__ __forceinline__ double pow2_near(const double v) { return ldexp(1.0, ilogb(v)); }
@@ -171,6 +176,23 @@ __device__ double qp_elem_bc0(const QpArgs& a, const QpScale& sc, const int b, c
   return 0.0;
 }
 
+// ---- free ends: the extra right-hand sides m = 1 (d/dp1) and m = 2 (d/dp2).  The end targets s0 + g0 p1 and sf + gf p2 enter
+// only the pins of node 0 and node n-1 and, with impulses, the velocity rows through which the impulse is eliminated.
+template <int NS>
+__device__ double qp_elem0_free(const QpArgs& a, const QpScale& sc, const int b, const int i, const int r, const int m) {
+  const int j = r - NS - 3;
+  if (m != 2 || i + 2 != a.n_nodes || j < 0 || j >= 6) return 0.0;
+  const double gf = a.em[(long)b * QP_MODEL + 6 + j];
+  return (j < 3 || !a.impulsive) ? gf : sc.rx * 2.0 * a.c2 * gf;
+}
+template <int NS>
+__device__ double qp_elem_bc0_free(const QpArgs& a, const QpScale& sc, const int b, const int r, const int m) {
+  const int j = r - 3;
+  if (m != 1 || j < 0 || j >= 6) return 0.0;
+  const double g0 = a.em[(long)b * QP_MODEL + j];
+  return (j < 3 || !a.impulsive) ? g0 : sc.rx * 2.0 * a.c2 * g0;
+}
+
 template <int K>
 __device__ __forceinline__ double qp_bcast(const double x) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(x), K), hi = __builtin_amdgcn_readlane(__double2hiint(x), K);
@@ -223,10 +245,10 @@ __device__ __forceinline__ void qp_householder(double (&col)[ROWS], const int c)
 
 // ---- one level of the reduction: pair j of trajectory b stacks rows 2j and 2j+1 of `cur` (FIRST: the level-0 rows, formed from
 // the sweep's outputs), eliminates node (2j+1) 2^level and writes the new row j of `nxt`; a row without a partner is carried.
-template <int NS, bool FIRST>
+template <int NS, bool FIRST, int NR>
 __global__ __launch_bounds__(64) void k_qp_level(QpArgs a, const int level, const int M, const double* __restrict__ cur,
                                                  double* __restrict__ nxt) {
-  using D = QpDims<NS>;
+  using D = QpDims<NS, NR>;
   constexpr int NB = D::NB;
   const int j = blockIdx.x, b = blockIdx.y, c = threadIdx.x;
   const QpScale sc = qp_scale(a, b);
@@ -236,8 +258,10 @@ __global__ __launch_bounds__(64) void k_qp_level(QpArgs a, const int level, cons
     for (int e = c; e < D::ROW; e += 64) {
       double v;
       if (FIRST) {
-        const int cc = (e < 2 * NB * NB) ? e / NB : 2 * NB, r = (e < 2 * NB * NB) ? e % NB : e - 2 * NB * NB;
-        v = qp_elem0<NS>(a, sc, b, 2 * j, r, cc);
+        const int cc = (e < 2 * NB * NB) ? e / NB : 2 * NB, r = (e < 2 * NB * NB) ? e % NB : (e - 2 * NB * NB) % NB;
+        const int m = (e < 2 * NB * NB) ? 0 : (e - 2 * NB * NB) / NB;
+        if constexpr (NR == 1) v = qp_elem0<NS>(a, sc, b, 2 * j, r, cc);
+        else v = (m == 0) ? qp_elem0<NS>(a, sc, b, 2 * j, r, cc) : qp_elem0_free<NS>(a, sc, b, 2 * j, r, m);
       } else {
         v = rows[(long)(2 * j) * D::ROW + e];
       }
@@ -269,6 +293,13 @@ __global__ __launch_bounds__(64) void k_qp_level(QpArgs a, const int level, cons
       col[r] = FIRST ? qp_elem0<NS>(a, sc, b, 2 * j, r, 2 * NB) : top[2 * NB * NB + r];
       col[NB + r] = FIRST ? qp_elem0<NS>(a, sc, b, 2 * j + 1, r, 2 * NB) : bot[2 * NB * NB + r];
     }
+  } else if (NR > 1 && c < D::NCOLS) {            // the free-end right-hand sides
+    const int m = c - 3 * NB;
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+      col[r] = FIRST ? qp_elem0_free<NS>(a, sc, b, 2 * j, r, m) : top[2 * NB * NB + m * NB + r];
+      col[NB + r] = FIRST ? qp_elem0_free<NS>(a, sc, b, 2 * j + 1, r, m) : bot[2 * NB * NB + m * NB + r];
+    }
   }
   qp_householder<D::R2, NB, D::NCOLS>(col, c);
   const int mid = (2 * j + 1) << level;
@@ -282,21 +313,22 @@ __global__ __launch_bounds__(64) void k_qp_level(QpArgs a, const int level, cons
   } else if (c < 3 * NB) {
 #pragma unroll
     for (int r = 0; r < NB; ++r) { rec[D::REC_CB + (c - 2 * NB) * NB + r] = col[r]; orow[NB * NB + (c - 2 * NB) * NB + r] = col[NB + r]; }
-  } else if (c == 3 * NB) {
+  } else if (c >= 3 * NB && c < D::NCOLS) {
+    const int m = c - 3 * NB;
 #pragma unroll
-    for (int r = 0; r < NB; ++r) { rec[D::REC_G + r] = col[r]; orow[2 * NB * NB + r] = col[NB + r]; }
+    for (int r = 0; r < NB; ++r) { rec[D::REC_G + m * NB + r] = col[r]; orow[2 * NB * NB + m * NB + r] = col[NB + r]; }
   }
 }
 
 // ---- the last level: the one block row A y_0 + B y_{n-1} = r with node 0's boundary block (NS + 3 rows) and lambda_{n-1} = 0 (NS
 // rows): 2NB x 2NB, triangularised in one wavefront (lane = column), back-substituted by lane 0 from LDS.  A pivot below 1e-13 of
 // the largest marks the trajectory's KKT system singular (e.g. too few nodes to reach the terminal state).
-template <int NS>
+template <int NS, int NR>
 __global__ __launch_bounds__(64) void k_qp_final(QpArgs a, const double* __restrict__ cur) {
-  using D = QpDims<NS>;
+  using D = QpDims<NS, NR>;
   constexpr int NB = D::NB, N2 = 2 * NB;
-  __shared__ double Rs[N2 + 1][N2];
-  __shared__ double ys[N2];
+  __shared__ double Rs[N2 + NR][N2];
+  __shared__ double ys[NR][N2];
   const int b = blockIdx.x, c = threadIdx.x;
   const QpScale sc = qp_scale(a, b);
   const double* row = cur + (long)b * a.S_traj * D::ROW;
@@ -315,9 +347,15 @@ __global__ __launch_bounds__(64) void k_qp_final(QpArgs a, const double* __restr
 #pragma unroll
       for (int r = NB + NS + 3; r < N2; ++r) col[r] = (r == c) ? 1.0 : 0.0;
     }
+  } else if (NR > 1 && c < N2 + NR) {           // the free-end right-hand sides (zero in the lambda_{n-1} rows)
+    const int m = c - N2;
+#pragma unroll
+    for (int r = 0; r < NB; ++r) col[r] = row[2L * NB * NB + m * NB + r];
+#pragma unroll
+    for (int r = 0; r < NS + 3; ++r) col[NB + r] = qp_elem_bc0_free<NS>(a, sc, b, r, m);
   }
-  qp_householder<N2, N2, N2 + 1>(col, c);
-  if (c <= N2) {
+  qp_householder<N2, N2, N2 + NR>(col, c);
+  if (c < N2 + NR) {
 #pragma unroll
     for (int r = 0; r < N2; ++r) Rs[c][r] = col[r];
   }
@@ -326,23 +364,26 @@ __global__ __launch_bounds__(64) void k_qp_final(QpArgs a, const double* __restr
     double dmax = 0.0, dmin = 1e300;
     for (int k = 0; k < N2; ++k) { dmax = fmax(dmax, fabs(Rs[k][k])); dmin = fmin(dmin, fabs(Rs[k][k])); }
     a.status[b] = (dmin <= 1e-13 * dmax) ? 1 : 0;
+  }
+  if (c < NR) {                                 // lane m back-substitutes right-hand side m
     for (int k = N2 - 1; k >= 0; --k) {
-      double s = Rs[N2][k];
-      for (int m = k + 1; m < N2; ++m) s -= Rs[m][k] * ys[m];
-      ys[k] = s / Rs[k][k];
+      double s = Rs[N2 + c][k];
+      for (int m = k + 1; m < N2; ++m) s -= Rs[m][k] * ys[c][m];
+      ys[c][k] = s / Rs[k][k];
     }
   }
   __syncthreads();
   if (c < N2) {
     const long node = (long)b * a.n_nodes + ((c < NB) ? 0 : a.n_nodes - 1);
-    a.Y[(long)(c % NB) * a.ldy + node] = ys[c];
+#pragma unroll
+    for (int m = 0; m < NR; ++m) a.Y[(long)(m * NB + c % NB) * a.ldy + node] = ys[m][c];
   }
 }
 
 // ---- back-substitution of one level: pair j forms y_mid = R^{-1} (g - Ca y_left - Cb y_right), lane r = row r
-template <int NS>
+template <int NS, int NR>
 __global__ __launch_bounds__(64) void k_qp_back(QpArgs a, const int level) {
-  using D = QpDims<NS>;
+  using D = QpDims<NS, NR>;
   constexpr int NB = D::NB;
   const int j = blockIdx.x, b = blockIdx.y, r = threadIdx.x;
   const int mid = (2 * j + 1) << level, left = (2 * j) << level;
@@ -351,18 +392,29 @@ __global__ __launch_bounds__(64) void k_qp_back(QpArgs a, const int level) {
   const double* rec = a.rec + ((long)b * a.n_nodes + mid) * D::REC;
   const long nb = (long)b * a.n_nodes;
   const int rr = r < NB ? r : NB - 1;
-  double s = rec[D::REC_G + rr];
-  for (int c = 0; c < NB; ++c)
-    s -= rec[D::REC_CA + c * NB + rr] * a.Y[(long)c * a.ldy + nb + left] + rec[D::REC_CB + c * NB + rr] * a.Y[(long)c * a.ldy + nb + right];
+  double s[NR], x[NR];
+#pragma unroll
+  for (int m = 0; m < NR; ++m) {
+    const double* Ym = a.Y + (long)m * NB * a.ldy;
+    s[m] = rec[D::REC_G + m * NB + rr];
+    for (int c = 0; c < NB; ++c)
+      s[m] -= rec[D::REC_CA + c * NB + rr] * Ym[(long)c * a.ldy + nb + left] + rec[D::REC_CB + c * NB + rr] * Ym[(long)c * a.ldy + nb + right];
+    x[m] = 0.0;
+  }
   const double rdiag = 1.0 / rec[D::REC_R + rr * NB + rr];
-  double x = 0.0;
   qp_static_for<0, NB>([&](auto kc) {
     constexpr int k = NB - 1 - decltype(kc)::value;
-    const double xk = qp_bcast<k>(s * rdiag);
-    if (rr == k) x = xk;
-    if (rr < k) s = __builtin_fma(-rec[D::REC_R + k * NB + rr], xk, s);
+#pragma unroll
+    for (int m = 0; m < NR; ++m) {
+      const double xk = qp_bcast<k>(s[m] * rdiag);
+      if (rr == k) x[m] = xk;
+      if (rr < k) s[m] = __builtin_fma(-rec[D::REC_R + k * NB + rr], xk, s[m]);
+    }
   });
-  if (r < NB) a.Y[(long)r * a.ldy + nb + mid] = x;
+  if (r < NB) {
+#pragma unroll
+    for (int m = 0; m < NR; ++m) a.Y[(long)(m * NB + r) * a.ldy + nb + mid] = x[m];
+  }
 }
 
 // ---- unscale into the caller's arrays, grid over nodes; per-block partial sums of the control cost (:377-380) in `part`
@@ -421,39 +473,180 @@ __global__ void k_qp_cost(QpArgs a, const double* dX, long ldX, double* dV, doub
   if (singular) singular[b] = bad ? 1.0 : 0.0;
 }
 
-// workspace: rows A | rows B | records | Y | partial sums | gw (u64) | status (int)
-static size_t qp_doubles_before_gw(int nstate, int n_nodes, int n_batch) {
-  const size_t S = (size_t)(n_nodes - 1) * n_batch, J = (size_t)n_nodes * n_batch;
-  const size_t row = (nstate == 7) ? QpDims<7>::ROW : QpDims<6>::ROW, rec = (nstate == 7) ? QpDims<7>::REC : QpDims<6>::REC;
-  const size_t nb = (nstate == 7) ? QpDims<7>::NB : QpDims<6>::NB;
-  const size_t nblk = (size_t)(n_nodes + QP_FIN - 1) / QP_FIN;
-  return 2 * S * row + J * rec + nb * J + nblk * n_batch;
-}
-size_t direct_qp_workspace_bytes(int nstate, int n_nodes, int n_batch) {
-  return sizeof(double) * qp_doubles_before_gw(nstate, n_nodes, n_batch) + sizeof(unsigned long long) * 2 * n_batch +
-         sizeof(int) * n_batch + 4096;
-}
-int* direct_qp_status(void* workspace, int nstate, int n_nodes, int n_batch) {
-  return (int*)((char*)workspace + sizeof(double) * qp_doubles_before_gw(nstate, n_nodes, n_batch) +
-                sizeof(unsigned long long) * 2 * n_batch);
+// ---- free ends: the solution is z(p) = z0 + z1 p1 + z2 p2 and the reduced cost
+//   phi(p) = phi0 + G.p + p'Hp/2,  phi0 = the frozen cost of z0,
+//   G_i = 2 (sum_k w_k (u_k + du0_k).du_ik + c2 sum_e a_e.b_ei),  H_ij = 2 (sum_k w_k du_ik.du_jk + c2 sum_e b_ei.b_ej) + beta |c|_i delta_ij
+// with a_e, b_ei the end-point impulse terms dV + d and their p-derivatives.  Per-block partial sums of the six node sums
+// (u.u, u.du1, u.du2, du1.du1, du1.du2, du2.du2, all weighted) in `part` [n_batch][nblk][6].
+constexpr int QP_NSUM = 6;
+template <int NS>
+__global__ __launch_bounds__(QP_FIN) void k_qp_free_sums(QpArgs a, double* part) {
+  constexpr int NB = QpDims<NS, 3>::NB;
+  const int b = blockIdx.y, tid = threadIdx.x, k = blockIdx.x * QP_FIN + tid;
+  const QpScale sc = qp_scale(a, b);
+  double acc[QP_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (k < a.n_nodes) {
+    const long node = (long)b * a.n_nodes + k;
+    const double wk = qp_weight(a, b, k);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const double u = a.U[(long)q * a.ldu + node] + sc.su * a.Y[(long)(NS + q) * a.ldy + node];
+      const double d1 = sc.su * a.Y[(long)(NB + NS + q) * a.ldy + node], d2 = sc.su * a.Y[(long)(2 * NB + NS + q) * a.ldy + node];
+      acc[0] = __builtin_fma(wk * u, u, acc[0]);
+      acc[1] = __builtin_fma(wk * u, d1, acc[1]);
+      acc[2] = __builtin_fma(wk * u, d2, acc[2]);
+      acc[3] = __builtin_fma(wk * d1, d1, acc[3]);
+      acc[4] = __builtin_fma(wk * d1, d2, acc[4]);
+      acc[5] = __builtin_fma(wk * d2, d2, acc[5]);
+    }
+  }
+  __shared__ double red[QP_NSUM][QP_FIN];
+#pragma unroll
+  for (int m = 0; m < QP_NSUM; ++m) red[m][tid] = acc[m];
+  __syncthreads();
+  for (int h = QP_FIN / 2; h > 0; h >>= 1) {
+    if (tid < h)
+#pragma unroll
+      for (int m = 0; m < QP_NSUM; ++m) red[m][tid] += red[m][tid + h];
+    __syncthreads();
+  }
+  if (tid < QP_NSUM) part[((long)b * gridDim.x + blockIdx.x) * QP_NSUM + tid] = red[tid][0];
 }
 
+__device__ __forceinline__ double qp_phi(const double* G, const double* H, const double phi0, const double p1, const double p2) {
+  return phi0 + G[0] * p1 + G[1] * p2 + 0.5 * (H[0] * p1 * p1 + 2.0 * H[1] * p1 * p2 + H[2] * p2 * p2);
+}
+__device__ __forceinline__ double qp_clamp(const double v) { return fmin(fmax(v, -QP_PBOUND), QP_PBOUND); }
+
+// ---- the 2 x 2 box QP of every trajectory, one thread each: min phi(p) over |p1|, |p2| <= 0.1.  Candidates, in this order:
+// the interior stationary point (H positive definite and the point inside the box), the clamped 1-D minimisers on the edges
+// p1 = -d, +d, p2 = -d, +d, and the four corners.  phi is convex, so the smallest phi among them is the minimum; exact ties go to
+// the smaller max|p|, then to the earlier candidate.  Then the impulses, p and the cost (with the beta term).
 template <int NS>
+__global__ void k_qp_free_box(QpArgs a, double* dV, double* pout, double* cost, double* singular, const double* part, int nblk) {
+  constexpr int NB = QpDims<NS, 3>::NB;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.n_batch) return;
+  const bool bad = a.status[b] != 0;
+  const double nan = __builtin_nan("");
+  double sum[QP_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < nblk; ++k)
+#pragma unroll
+    for (int m = 0; m < QP_NSUM; ++m) sum[m] += part[((long)b * nblk + k) * QP_NSUM + m];
+  const double* tg = a.tg + (long)b * QP_TARGET;
+  const double* em = a.em + (long)b * QP_MODEL;
+  const long nb = (long)b * a.n_nodes;
+  // end-point impulse terms dV_e + d_e = a_e + b_e1 p1 + b_e2 p2 (d_e = s_v + g_v p_e - x_v - dx_v - dV_e, or 0 without impulses)
+  double ae[6], be1[6], be2[6];
+  for (int e = 0; e < 2; ++e) {
+    const long node = nb + (e ? a.n_nodes - 1 : 0);
+    for (int q = 0; q < 3; ++q) {
+      const int v = 3 + q, i = 3 * e + q;
+      if (a.impulsive) {
+        ae[i] = tg[6 * e + v] - a.X[(long)v * a.ldx + node] - a.Y[(long)v * a.ldy + node];
+        be1[i] = (e == 0 ? em[v] : 0.0) - a.Y[(long)(NB + v) * a.ldy + node];
+        be2[i] = (e == 1 ? em[6 + v] : 0.0) - a.Y[(long)(2 * NB + v) * a.ldy + node];
+      } else {
+        ae[i] = tg[13 + i];
+        be1[i] = be2[i] = 0.0;
+      }
+    }
+  }
+  double caa = 0.0, ca1 = 0.0, ca2 = 0.0, c11 = 0.0, c12 = 0.0, c22 = 0.0;
+  for (int i = 0; i < 6; ++i) {
+    caa += ae[i] * ae[i]; ca1 += ae[i] * be1[i]; ca2 += ae[i] * be2[i];
+    c11 += be1[i] * be1[i]; c12 += be1[i] * be2[i]; c22 += be2[i] * be2[i];
+  }
+  const double beta = a.beta[b];
+  const double phi0 = sum[0] + a.c2 * caa;
+  const double G[2] = {2.0 * (sum[1] + a.c2 * ca1), 2.0 * (sum[2] + a.c2 * ca2)};
+  const double H[3] = {2.0 * (sum[3] + a.c2 * c11) + beta * em[12], 2.0 * (sum[4] + a.c2 * c12), 2.0 * (sum[5] + a.c2 * c22) + beta * em[13]};
+  double best = 0.0, bp1 = 0.0, bp2 = 0.0, bm = 0.0;
+  bool have = false;
+  auto consider = [&](const double p1, const double p2) {
+    const double f = qp_phi(G, H, phi0, p1, p2), m = fmax(fabs(p1), fabs(p2));
+    if (!have || f < best || (f == best && m < bm)) { best = f; bp1 = p1; bp2 = p2; bm = m; have = true; }
+  };
+  const double d = QP_PBOUND, det = H[0] * H[2] - H[1] * H[1];
+  if (H[0] > 0.0 && det > 0.0) {
+    const double p1 = (-G[0] * H[2] + G[1] * H[1]) / det, p2 = (-G[1] * H[0] + G[0] * H[1]) / det;
+    if (fabs(p1) <= d && fabs(p2) <= d) consider(p1, p2);
+  }
+  for (int s = -1; s <= 1; s += 2) {               // edges p1 = s d: min over p2
+    const double p1 = s * d;
+    if (H[2] > 0.0) consider(p1, qp_clamp(-(G[1] + H[1] * p1) / H[2]));
+  }
+  for (int s = -1; s <= 1; s += 2) {               // edges p2 = s d: min over p1
+    const double p2 = s * d;
+    if (H[0] > 0.0) consider(qp_clamp(-(G[0] + H[1] * p2) / H[0]), p2);
+  }
+  consider(-d, -d); consider(d, -d); consider(-d, d); consider(d, d);
+  for (int e = 0; e < 2; ++e)
+    for (int q = 0; q < 3; ++q) {
+      const int i = 3 * e + q;
+      dV[(long)b * 6 + i] = bad ? nan : (a.impulsive ? ae[i] + be1[i] * bp1 + be2[i] * bp2 - tg[13 + i] : 0.0);
+    }
+  pout[2 * b] = bad ? nan : bp1;
+  pout[2 * b + 1] = bad ? nan : bp2;
+  cost[b] = bad ? nan : best;
+  if (singular) singular[b] = bad ? 1.0 : 0.0;
+}
+
+// ---- dX = z0 + z1 p1 + z2 p2 (dx part), dU = s_u (du part), grid over nodes
+template <int NS>
+__global__ __launch_bounds__(QP_FIN) void k_qp_free_combine(QpArgs a, const double* pout, double* dX, long ldX, double* dU, long ldU) {
+  constexpr int NB = QpDims<NS, 3>::NB;
+  const int b = blockIdx.y, k = blockIdx.x * QP_FIN + threadIdx.x;
+  if (k >= a.n_nodes) return;
+  const QpScale sc = qp_scale(a, b);
+  const double p1 = pout[2 * b], p2 = pout[2 * b + 1];      // NaN for a singular system
+  const long node = (long)b * a.n_nodes + k;
+  auto z = [&](const int c) {
+    return __builtin_fma(a.Y[(long)(2 * NB + c) * a.ldy + node], p2, __builtin_fma(a.Y[(long)(NB + c) * a.ldy + node], p1, a.Y[(long)c * a.ldy + node]));
+  };
+#pragma unroll
+  for (int c = 0; c < NS; ++c) dX[(long)c * ldX + node] = z(c);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) dU[(long)q * ldU + node] = sc.su * z(NS + q);
+}
+
+// workspace: gw (u64 [2 n_batch]) | status (int [n_batch]) | rows A | rows B | records | Y | partial sums; NR = 1 or 3
+static size_t qp_header_bytes(int n_batch) {
+  return ((sizeof(unsigned long long) * 2 * n_batch + sizeof(int) * n_batch + 255) / 256) * 256;
+}
+template <int NS, int NR>
+static size_t qp_doubles(int n_nodes, int n_batch) {
+  using D = QpDims<NS, NR>;
+  const size_t S = (size_t)(n_nodes - 1) * n_batch, J = (size_t)n_nodes * n_batch;
+  const size_t nblk = (size_t)(n_nodes + QP_FIN - 1) / QP_FIN;
+  return 2 * S * D::ROW + J * D::REC + (size_t)NR * D::NB * J + nblk * n_batch * (NR == 1 ? 1 : QP_NSUM);
+}
+size_t direct_qp_workspace_bytes(int nstate, int n_nodes, int n_batch, int nr) {
+  const size_t nd = (nstate == 7) ? (nr == 3 ? qp_doubles<7, 3>(n_nodes, n_batch) : qp_doubles<7, 1>(n_nodes, n_batch))
+                                  : (nr == 3 ? qp_doubles<6, 3>(n_nodes, n_batch) : qp_doubles<6, 1>(n_nodes, n_batch));
+  return qp_header_bytes(n_batch) + sizeof(double) * nd + 4096;
+}
+int* direct_qp_status(void* workspace, int n_batch) {
+  return (int*)((char*)workspace + sizeof(unsigned long long) * 2 * n_batch);
+}
+
+template <int NS, int NR>
 static hipError_t direct_qp_impl(const DirectQpArgs& q, void* workspace, hipStream_t st) {
-  using D = QpDims<NS>;
+  using D = QpDims<NS, NR>;
   QpArgs a;
   a.n_nodes = q.n_nodes; a.n_batch = q.n_batch; a.S_traj = q.n_nodes - 1;
   a.Jac = q.Jac; a.ldj = q.ldj; a.defect = q.defect; a.ldd = q.ldd; a.X = q.X; a.ldx = q.ldx; a.U = q.U; a.ldu = q.ldu;
   a.t = q.t; a.t_stride = q.t_stride; a.tg = q.targets; a.impulsive = q.impulsive; a.c2 = q.c2;
+  a.em = q.model; a.beta = q.beta;
   const size_t S = (size_t)a.S_traj * a.n_batch, J = (size_t)a.n_nodes * a.n_batch;
-  double* rowsA = (double*)workspace;
+  a.gw = (unsigned long long*)workspace;
+  a.status = direct_qp_status(workspace, a.n_batch);
+  double* rowsA = (double*)((char*)workspace + qp_header_bytes(a.n_batch));
   double* rowsB = rowsA + S * D::ROW;
   a.rec = rowsB + S * D::ROW;
   a.Y = a.rec + J * D::REC; a.ldy = (long)J;
   const int nblk = (a.n_nodes + QP_FIN - 1) / QP_FIN;
-  double* part = a.Y + (size_t)D::NB * J;
-  a.gw = (unsigned long long*)(part + (size_t)nblk * a.n_batch);
-  a.status = (int*)(a.gw + 2 * a.n_batch);
+  double* part = a.Y + (size_t)NR * D::NB * J;
   hipError_t e = hipMemsetAsync(a.gw, 0, sizeof(unsigned long long) * 2 * a.n_batch, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_qp_gmax<NS>), dim3((a.S_traj + 255) / 256, a.n_batch), dim3(256), 0, st, a);
@@ -465,17 +658,23 @@ static hipError_t direct_qp_impl(const DirectQpArgs& q, void* workspace, hipStre
   do {                                  // a single segment still passes once: its level-0 row is formed ("carried")
     Ms[level] = M;
     const int groups = (M + 1) / 2;
-    if (first) hipLaunchKernelGGL((k_qp_level<NS, true>), dim3(groups, a.n_batch), dim3(64), 0, st, a, level, M, cur, nxt);
-    else hipLaunchKernelGGL((k_qp_level<NS, false>), dim3(groups, a.n_batch), dim3(64), 0, st, a, level, M, cur, nxt);
+    if (first) hipLaunchKernelGGL((k_qp_level<NS, true, NR>), dim3(groups, a.n_batch), dim3(64), 0, st, a, level, M, cur, nxt);
+    else hipLaunchKernelGGL((k_qp_level<NS, false, NR>), dim3(groups, a.n_batch), dim3(64), 0, st, a, level, M, cur, nxt);
     { double* t = cur; cur = nxt; nxt = t; }
     first = false;
     M = groups;
     ++level;
   } while (M > 1);
-  hipLaunchKernelGGL((k_qp_final<NS>), dim3(a.n_batch), dim3(64), 0, st, a, cur);
+  hipLaunchKernelGGL((k_qp_final<NS, NR>), dim3(a.n_batch), dim3(64), 0, st, a, cur);
   for (int l = level - 1; l >= 0; --l) {
     const int pairs = Ms[l] / 2;
-    if (pairs > 0) hipLaunchKernelGGL((k_qp_back<NS>), dim3(pairs, a.n_batch), dim3(64), 0, st, a, l);
+    if (pairs > 0) hipLaunchKernelGGL((k_qp_back<NS, NR>), dim3(pairs, a.n_batch), dim3(64), 0, st, a, l);
+  }
+  if constexpr (NR == 3) {
+    hipLaunchKernelGGL((k_qp_free_sums<NS>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, a, part);
+    hipLaunchKernelGGL((k_qp_free_box<NS>), dim3((a.n_batch + 63) / 64), dim3(64), 0, st, a, q.dV, q.p, q.cost, q.singular, part, nblk);
+    hipLaunchKernelGGL((k_qp_free_combine<NS>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, a, q.p, q.dX, q.ldX, q.dU, q.ldU);
+    return hipGetLastError();
   }
   hipLaunchKernelGGL((k_qp_unscale<NS>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, a, q.dX, q.ldX, q.dU, q.ldU, part);
   hipLaunchKernelGGL(k_qp_cost, dim3((a.n_batch + 63) / 64), dim3(64), 0, st, a, q.dX, q.ldX, q.dV, q.cost, q.singular, part, nblk);
@@ -495,7 +694,71 @@ hipError_t launch_direct_qp_update_dv(double* targets, const double* dV, const d
 }
 
 hipError_t launch_direct_qp(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st) {
-  return (nstate == 7) ? direct_qp_impl<7>(q, workspace, st) : direct_qp_impl<6>(q, workspace, st);
+  return (nstate == 7) ? direct_qp_impl<7, 1>(q, workspace, st) : direct_qp_impl<6, 1>(q, workspace, st);
+}
+hipError_t launch_direct_qp_free(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st) {
+  return (nstate == 7) ? direct_qp_impl<7, 3>(q, workspace, st) : direct_qp_impl<6, 3>(q, workspace, st);
+}
+
+}  // namespace lto
+
+namespace lto {
+
+// ---- free ends: the end states and the end model of every trajectory at its current (tau1, tau2) -- interpEndStates (:434-461)
+// at tau and tau +- h, each argument wrapped into [0, 1] on its own, and the finite differences of :339-349.  One thread per
+// trajectory and end point; the natural-spline second derivatives of the two tables come from the host (fixed for a call).
+__device__ double end_spline(const EndOrbitsDev& o, const int e, const int j, double x) {
+  int guard = 0;                                   // the reference's wrap (:438-449); a non-finite or absurd tau gives NaN
+  if (!(fabs(x) < 1e6)) return __builtin_nan("");
+  while (x > 1.0 && guard++ < 2000000) x -= 1.0;
+  while (x < 0.0 && guard++ < 2000000) x += 1.0;
+  const int n = o.n[e];
+  const double* t = o.t[e];
+  const double* Y = o.Y[e];
+  const double* M = o.M[e];
+  int lo = 0, hi = n - 1;                          // the last i with t[i] <= x, clipped to [0, n-2]
+  if (x < t[0]) hi = 0;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) / 2;
+    if (t[mid] <= x) lo = mid; else hi = mid;
+  }
+  const int i = lo < n - 2 ? lo : n - 2;
+  const double h = t[i + 1] - t[i], a = t[i + 1] - x, b = x - t[i];
+  const double Mi = M[j + 6 * i], Mj = M[j + 6 * (i + 1)];
+  return (Mi * a * a * a + Mj * b * b * b) / (6.0 * h) + (Y[j + 6 * i] - Mi * h * h / 6.0) * a / h +
+         (Y[j + 6 * (i + 1)] - Mj * h * h / 6.0) * b / h;
+}
+__global__ void k_end_states(EndOrbitsDev o, const double* tau, int n_batch, double* s, int s_stride, double* model) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= 2 * n_batch) return;
+  const int b = g / 2, e = g % 2;
+  const double x = tau[g], h = 0.05;               // pert (:340)
+  double c2 = 0.0;
+  for (int j = 0; j < 6; ++j) {
+    const double s0 = end_spline(o, e, j, x), sp = end_spline(o, e, j, x + h), sm = end_spline(o, e, j, x - h);
+    s[(long)b * s_stride + 6 * e + j] = s0;
+    const double gj = (sp - sm) / (2.0 * h), cj = (sp - 2.0 * s0 + sm) / (h * h);
+    model[(long)b * QP_MODEL + 6 * e + j] = gj;
+    c2 += cj * cj;
+  }
+  model[(long)b * QP_MODEL + 12 + e] = sqrt(c2);
+}
+hipError_t launch_end_states(const EndOrbitsDev& o, const double* tau, int n_batch, double* s, int s_stride, double* model,
+                             hipStream_t st) {
+  hipLaunchKernelGGL(k_end_states, dim3((2 * n_batch + 63) / 64), dim3(64), 0, st, o, tau, n_batch, s, s_stride, model);
+  return hipGetLastError();
+}
+
+// tau1 += alpha p1, tau2 += alpha p2 (:564-565), not wrapped; alpha = 0: frozen
+__global__ void k_tau_update(double* tau, const double* p, const double* step, int n_batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 2 * n_batch) return;
+  const double a = step[i / 2];
+  if (a != 0.0) tau[i] = tau[i] + p[i] * a;
+}
+hipError_t launch_tau_update(double* tau, const double* p, const double* step, int n_batch, hipStream_t st) {
+  hipLaunchKernelGGL(k_tau_update, dim3((2 * n_batch + 63) / 64), dim3(64), 0, st, tau, p, step, n_batch);
+  return hipGetLastError();
 }
 
 }  // namespace lto

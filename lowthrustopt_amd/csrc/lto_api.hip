@@ -145,6 +145,7 @@ struct lto_direct_plan {
   lto_direct_params prm;
   int kernel;       // LTO_KERNEL_*
   void* qp_ws;      // workspace of the QP step (kernels_direct_qp.hip), allocated at the plan's first step
+  int qp_ws_nr;     // right-hand sides the workspace is sized for: 1 (frozen ends) or 3 (free ends, grown at the first free step)
   double* qp_singular_out;   // lto_direct_solve_batch: where the QP step also reports singular systems (device, [n_batch])
 };
 
@@ -1551,6 +1552,17 @@ static void direct_plan_free(lto_direct_plan* p) {
   delete p;
 }
 
+// the QP workspace for nr right-hand sides (1: frozen ends, 3: free ends); a frozen-end workspace grows at the first free step
+static int direct_qp_workspace(lto_direct_plan* p, int nr) {
+  if (p->qp_ws && p->qp_ws_nr >= nr) return LTO_OK;
+  if (p->qp_ws) { (void)hipFree(p->qp_ws); p->qp_ws = nullptr; }
+  const size_t bytes = direct_qp_workspace_bytes(p->nstate, p->n_nodes, p->n_batch, nr);
+  const hipError_t e = hipMalloc(&p->qp_ws, bytes);
+  if (e != hipSuccess) { p->qp_ws = nullptr; return set_err(p->ctx, LTO_EHIP, "QP workspace", e); }
+  p->qp_ws_nr = nr;
+  return LTO_OK;
+}
+
 void lto_direct_plan_destroy(lto_direct_plan* p) {
   if (!p) return;
   lto_ctx* c = p->ctx;
@@ -2095,11 +2107,8 @@ int lto_direct_qp_step_dev(lto_direct_plan* p, void* stream, const double* Jac, 
   if (n_tgrids != 1 && n_tgrids != p->n_batch) return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch");
   int rc = bind_device(c);
   if (rc) return rc;
-  if (!p->qp_ws) {
-    const size_t bytes = direct_qp_workspace_bytes(p->nstate, p->n_nodes, p->n_batch);
-    const hipError_t e = hipMalloc(&p->qp_ws, bytes);
-    if (e != hipSuccess) { p->qp_ws = nullptr; return set_err(c, LTO_EHIP, "QP workspace", e); }
-  }
+  rc = direct_qp_workspace(p, 1);
+  if (rc) return rc;
   DirectQpArgs q;
   std::memset(&q, 0, sizeof q);
   q.n_nodes = p->n_nodes; q.n_batch = p->n_batch;
@@ -2119,7 +2128,123 @@ int lto_direct_qp_step_dev(lto_direct_plan* p, void* stream, const double* Jac, 
 }
 
 const int* lto_direct_plan_qp_status(const lto_direct_plan* p) {
-  return (p && p->qp_ws) ? direct_qp_status(p->qp_ws, p->nstate, p->n_nodes, p->n_batch) : nullptr;
+  return (p && p->qp_ws) ? direct_qp_status(p->qp_ws, p->n_batch) : nullptr;
+}
+
+// free ends (flagEnd = true): the QP step with the phase updates p1, p2 in +-0.1 (kernels_direct_qp.hip).  model and
+// beta are device arrays of n_batch lto_direct_end_model / doubles; p [n_batch][2] (device).
+static int direct_qp_step_free_dev(lto_direct_plan* p, hipStream_t st, const double* Jac, long ldj, const double* defect, long ldd,
+                                   const double* X, long ldx, const double* U, long ldu, const double* t, int n_tgrids,
+                                   const lto_direct_targets* targets, const lto_direct_end_model* model, const double* beta,
+                                   int allow_impulsive, double* dX, double* dU, double* dV, double* pout, double* cost) {
+  lto_ctx* c = p->ctx;
+  int rc = direct_qp_workspace(p, 3);
+  if (rc) return rc;
+  DirectQpArgs q;
+  std::memset(&q, 0, sizeof q);
+  q.n_nodes = p->n_nodes; q.n_batch = p->n_batch;
+  q.Jac = Jac; q.ldj = ldj; q.defect = defect; q.ldd = ldd; q.X = X; q.ldx = ldx; q.U = U; q.ldu = ldu;
+  q.t = t; q.t_stride = (n_tgrids == 1) ? 0 : p->n_nodes;
+  q.targets = (const double*)targets; q.impulsive = allow_impulsive ? 1 : 0;
+  const double vu = p->prm.DU / p->prm.TU;
+  q.c2 = vu * vu;
+  q.dX = dX; q.ldX = ldx; q.dU = dU; q.ldU = ldu; q.dV = dV; q.cost = cost;
+  q.singular = p->qp_singular_out;
+  q.model = (const double*)model; q.beta = beta; q.p = pout;
+  timing_begin(c, st);
+  const hipError_t e = launch_direct_qp_free(p->nstate, q, p->qp_ws, st);
+  timing_end(c, st);
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_direct_qp_free", e);
+  return LTO_OK;
+}
+
+// the two orbit tables on the device with the natural-spline second derivatives (a tridiagonal solve on the host, once per call)
+struct DevOrbits {
+  EndOrbitsDev o;
+  double* buf = nullptr;
+  ~DevOrbits() { if (buf) (void)hipFree(buf); }
+};
+static bool orbits_ok(const lto_direct_orbits* ob) {
+  return ob && ob->n0 >= 2 && ob->nf >= 2 && ob->t0 && ob->X0 && ob->tf && ob->Xf;
+}
+static int orbits_upload(lto_ctx* c, const lto_direct_orbits* ob, DevOrbits& d, hipStream_t st) {
+  const int n[2] = {ob->n0, ob->nf};
+  const double* T[2] = {ob->t0, ob->tf};
+  const double* Y[2] = {ob->X0, ob->Xf};
+  for (int e = 0; e < 2; ++e)
+    for (int i = 0; i + 1 < n[e]; ++i)
+      if (!(T[e][i + 1] > T[e][i])) return set_err(c, LTO_EINVAL, "orbit table times must increase strictly");
+  const size_t tot = (size_t)13 * (n[0] + n[1]);
+  lto::HostBuf<double> h(tot, 0.0), cp, dp;
+  if (!h.ok() || !cp.alloc((size_t)std::max(n[0], n[1])) || !dp.alloc((size_t)6 * std::max(n[0], n[1])))
+    return set_err(c, LTO_ENOMEM, "orbit tables: out of host memory");
+  size_t off = 0;
+  size_t offs[2][3];
+  for (int e = 0; e < 2; ++e) {
+    const int m = n[e];
+    const double* t = T[e];
+    double* ht = &h[off];
+    double* hY = ht + m;
+    double* hM = hY + 6 * (size_t)m;
+    offs[e][0] = off; offs[e][1] = off + m; offs[e][2] = off + 7 * (size_t)m;
+    off += 13 * (size_t)m;
+    for (int i = 0; i < m; ++i) { ht[i] = t[i]; for (int j = 0; j < 6; ++j) hY[j + 6 * i] = Y[e][j + 6 * (size_t)i]; }
+    // natural spline (M_0 = M_{m-1} = 0): h_{i-1} M_{i-1} + 2 (h_{i-1} + h_i) M_i + h_i M_{i+1} = 6 (slope_i - slope_{i-1}), Thomas
+    for (int j = 0; j < 6; ++j) { hM[j] = 0.0; hM[j + 6 * (size_t)(m - 1)] = 0.0; }
+    if (m > 2) {
+      for (int i = 1; i < m - 1; ++i) {
+        const double h0 = t[i] - t[i - 1], h1 = t[i + 1] - t[i];
+        const double diag = 2.0 * (h0 + h1) - (i > 1 ? h0 * cp[i - 1] : 0.0);
+        cp[i] = h1 / diag;
+        for (int j = 0; j < 6; ++j) {
+          const double r = 6.0 * ((hY[j + 6 * (i + 1)] - hY[j + 6 * i]) / h1 - (hY[j + 6 * i] - hY[j + 6 * (i - 1)]) / h0);
+          dp[j + 6 * (size_t)i] = (r - (i > 1 ? h0 * dp[j + 6 * (size_t)(i - 1)] : 0.0)) / diag;
+        }
+      }
+      for (int i = m - 2; i >= 1; --i)
+        for (int j = 0; j < 6; ++j) hM[j + 6 * (size_t)i] = dp[j + 6 * (size_t)i] - cp[i] * hM[j + 6 * (size_t)(i + 1)];
+    }
+  }
+  hipError_t e = hipMalloc(&d.buf, sizeof(double) * tot);
+  if (e != hipSuccess) { d.buf = nullptr; return set_err(c, LTO_EHIP, "orbit tables", e); }
+  e = hipMemcpyAsync(d.buf, h.data(), sizeof(double) * tot, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = stream_wait(st);                // h is released on return
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "orbit tables", e);
+  for (int k = 0; k < 2; ++k) {
+    d.o.n[k] = n[k];
+    d.o.t[k] = d.buf + offs[k][0]; d.o.Y[k] = d.buf + offs[k][1]; d.o.M[k] = d.buf + offs[k][2];
+  }
+  return LTO_OK;
+}
+
+int lto_direct_end_states(lto_ctx* c, const lto_direct_orbits* orbits, int n_batch, const double* tau, double* s_out,
+                          lto_direct_end_model* model) {
+  if (n_batch < 1) return c ? set_err(c, LTO_EINVAL, "n_batch must be >= 1") : LTO_EINVAL;
+  if (!c) return LTO_ENULL;
+  if (!orbits || !tau || !s_out || !model) return set_err(c, LTO_ENULL, "lto_direct_end_states: a required argument is NULL");
+  if (!orbits_ok(orbits)) return set_err(c, LTO_EINVAL, "orbit tables need >= 2 samples each and non-NULL arrays");
+  int rc = bind_device(c);
+  if (rc) return rc;
+  CallTimer call_timer(c);
+  hipStream_t st = c->stream;
+  DevOrbits dob;
+  rc = orbits_upload(c, orbits, dob, st);
+  if (rc) return rc;
+  double* d = nullptr;
+  const size_t nd = (size_t)n_batch * (2 + 12 + 14);
+  hipError_t e = hipMalloc(&d, sizeof(double) * nd);
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_direct_end_states", e);
+  double* d_tau = d;
+  double* d_s = d + 2 * (size_t)n_batch;
+  double* d_m = d_s + 12 * (size_t)n_batch;
+  e = hipMemcpyAsync(d_tau, tau, sizeof(double) * 2 * n_batch, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = launch_end_states(dob.o, d_tau, n_batch, d_s, 12, d_m, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(s_out, d_s, sizeof(double) * 12 * n_batch, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(model, d_m, sizeof(double) * 14 * n_batch, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = stream_wait(st);
+  (void)hipFree(d);
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_direct_end_states", e);
+  return LTO_OK;
 }
 
 static bool direct_targets_expand(const lto_direct_targets* targets, int n_targets, int B, lto::HostBuf<lto_direct_targets>& out) {
@@ -2191,15 +2316,105 @@ int lto_direct_qp_step(lto_ctx* c, int nstate, int n_nodes, int n_batch, const d
   return rc;
 }
 
-int lto_direct_solve_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
-                           const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
-                           const lto_direct_targets* targets, int n_targets, int allow_impulsive, int maxIter, double* X_out,
-                           double* U_out, double* dV_out, double* t_out, double* defect_out, int* status_flag, int* iterations,
-                           double* history) {
+int lto_direct_qp_step_free(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
+                            int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets,
+                            const lto_direct_end_model* model, const double* beta, int n_targets, int allow_impulsive, double* dX,
+                            double* dU, double* dV, double* p_out, double* cost) {
+  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
+  if (!c) return LTO_ENULL;
+  if (!X || !U || !t || !prm || !targets || !model || !beta || !dX || !dU || !dV || !p_out || !cost)
+    return set_err(c, LTO_ENULL, "lto_direct_qp_step_free: a required array is NULL");
+  if (n_targets != 1 && n_targets != n_batch) return set_err(c, LTO_EINVAL, "n_targets must be 1 or n_batch");
+  if (n_tgrids != 1 && n_tgrids != n_batch) return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch");
+  CallTimer call_timer(c);
+  lto_direct_plan* p = nullptr;
+  int rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &p);
+  if (rc) return rc;
+  lto::HostBuf<lto_direct_targets> tg;
+  lto::HostBuf<lto_direct_end_model> em(n_batch);
+  lto::HostBuf<double> hb(n_batch);
+  lto::HostBuf<int> h_stat(n_batch, 0);
+  if (!direct_targets_expand(targets, n_targets, n_batch, tg) || !em.ok() || !hb.ok() || !h_stat.ok()) {
+    delete p;
+    return set_err(c, LTO_ENOMEM, "lto_direct_qp_step_free: out of host memory");
+  }
+  for (int b = 0; b < n_batch; ++b) { em[b] = model[n_targets == 1 ? 0 : b]; hb[b] = beta[n_targets == 1 ? 0 : b]; }
+  const long J = (long)n_nodes * n_batch, S = p->S;
+  const int nj = nstate * 2 * (nstate + 3);
+  const size_t need = al256(sizeof(double) * nstate * J) * 4 + al256(sizeof(double) * 3 * J) * 4 + al256(sizeof(double) * n_nodes * n_tgrids) +
+                      al256(sizeof(double) * nj * S) + al256(sizeof(double) * nstate * S) + al256(sizeof(lto_direct_targets) * n_batch) +
+                      al256(sizeof(lto_direct_end_model) * n_batch) + al256(sizeof(double) * 7 * n_batch) * 4 + 8192;
+  rc = arena_reserve(c, need);
+  if (rc) { delete p; return rc; }
+  c->arena_top = 0;
+  double* d_xa = arena_take<double>(c, (size_t)nstate * J);
+  double* d_X = arena_take<double>(c, (size_t)nstate * J);
+  double* d_dX = arena_take<double>(c, (size_t)nstate * J);
+  double* d_dXa = arena_take<double>(c, (size_t)nstate * J);
+  double* d_ua = arena_take<double>(c, (size_t)3 * J);
+  double* d_U = arena_take<double>(c, (size_t)3 * J);
+  double* d_dU = arena_take<double>(c, (size_t)3 * J);
+  double* d_dUa = arena_take<double>(c, (size_t)3 * J);
+  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
+  double* d_jac = arena_take<double>(c, (size_t)nj * S);
+  double* d_def = arena_take<double>(c, (size_t)nstate * S);
+  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)n_batch);
+  lto_direct_end_model* d_em = arena_take<lto_direct_end_model>(c, (size_t)n_batch);
+  double* d_dV = arena_take<double>(c, (size_t)7 * n_batch);
+  double* d_cost = arena_take<double>(c, (size_t)7 * n_batch);
+  double* d_beta = arena_take<double>(c, (size_t)7 * n_batch);
+  double* d_p = arena_take<double>(c, (size_t)7 * n_batch);
+  hipStream_t st = c->stream;
+  hipError_t e = stage_in(c, X, nstate, J, d_xa, d_X, J, st);
+  if (e == hipSuccess) e = stage_in(c, U, 3, J, d_ua, d_U, J, st);
+  if (e == hipSuccess) e = vec_in(c, t, (long)n_nodes * n_tgrids, d_t, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * n_batch, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_em, em.data(), sizeof(lto_direct_end_model) * n_batch, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_beta, hb.data(), sizeof(double) * n_batch, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { (void)hipStreamSynchronize(st); delete p; return set_err(c, LTO_EHIP, "stage in", e); }
+  rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, d_t, n_tgrids, d_jac, S, nullptr, d_def, S, nullptr);
+  if (rc == LTO_OK)
+    rc = direct_qp_step_free_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t, n_tgrids, d_tg, d_em, d_beta, allow_impulsive, d_dX, d_dU,
+                                 d_dV, d_p, d_cost);
+  if (rc == LTO_OK) {
+    e = stage_out(c, d_dX, J, nstate, J, d_dXa, dX, st);
+    if (e == hipSuccess) e = stage_out(c, d_dU, J, 3, J, d_dUa, dU, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dV, d_dV, sizeof(double) * 6 * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(p_out, d_p, sizeof(double) * 2 * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_stat.data(), lto_direct_plan_qp_status(p), sizeof(int) * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = stream_wait(st);
+    if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
+    for (int b = 0; b < n_batch && rc == LTO_OK; ++b)
+      if (h_stat[b]) rc = set_err(c, LTO_ESINGULAR, "the KKT system of a trajectory's QP step is singular (too few nodes to reach the terminal state?)");
+  } else {
+    (void)hipStreamSynchronize(st);
+  }
+  direct_plan_free(p);
+  return rc;
+}
+
+// free ends of lto_direct_solve_free_batch (null for lto_direct_solve_batch)
+struct DirectFreeEnds {
+  const lto_direct_orbits* orbits;
+  const double* tau_in;       // [2 x n_batch]
+  const double* beta;        // [n_targets]
+  int flag_end;
+  double* tau_out;            // [2 x n_batch] or null
+};
+
+static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
+                             const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
+                             const lto_direct_targets* targets, int n_targets, int allow_impulsive, int maxIter, double* X_out,
+                             double* U_out, double* dV_out, double* t_out, double* defect_out, int* status_flag, int* iterations,
+                             double* history, const DirectFreeEnds* fe) {
   if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
   if (!c) return LTO_ENULL;
   if (!X_in || !U_in || !t || !prm || !targets || !X_out || !status_flag)
     return set_err(c, LTO_ENULL, "X_in, U_in, t, prm, targets, X_out or status is NULL");
+  if (fe && (!fe->orbits || !fe->tau_in || !fe->beta)) return set_err(c, LTO_ENULL, "orbits, tau_in or beta is NULL");
+  if (fe && !orbits_ok(fe->orbits)) return set_err(c, LTO_EINVAL, "orbit tables need >= 2 samples each and non-NULL arrays");
+  const int hw = fe ? 5 : 3;                               // history row: max|defect|, cost, alpha (, tau1, tau2)
   if (maxIter < 0) return set_err(c, LTO_EINVAL, "maxIter must be >= 0");
   if ((n_tgrids != 1 && n_tgrids != n_batch) || (n_targets != 1 && n_targets != n_batch)) return set_err(c, LTO_EINVAL, "n_tgrids / n_targets must be 1 or n_batch");
   constexpr int NA = 10;                                   // LinRange(0.1, 1, 10), :412
@@ -2263,12 +2478,36 @@ int lto_direct_solve_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, con
   double* d_ss = d_search + B;                             // [NA*B] per-trial sums of squares
   double* d_alphas = d_ss + (size_t)NA * B;                // [NA]
   p->qp_singular_out = d_sing;
-  (void)report_reserve(c, (size_t)4 * B);
+  (void)report_reserve(c, (size_t)(fe ? 6 : 4) * B);
   hipStream_t st = c->stream;
+  // free ends: tau [2B] | p [2B] | end model [14B] | beta [B] on the device, the orbit tables with their spline moments
+  DevOrbits dob;
+  double* d_fe = nullptr;
+  double *d_tau = nullptr, *d_p = nullptr, *d_em = nullptr, *d_beta = nullptr;
+  if (fe) {
+    rc = orbits_upload(c, fe->orbits, dob, st);
+    lto::HostBuf<double> hb(B);
+    if (rc == LTO_OK && !hb.ok()) rc = set_err(c, LTO_ENOMEM, "lto_direct_solve_free_batch: out of host memory");
+    if (rc == LTO_OK) {
+      for (int b = 0; b < B; ++b) hb[b] = fe->beta[n_targets == 1 ? 0 : b];
+      hipError_t e0 = hipMalloc(&d_fe, sizeof(double) * 19 * B);
+      if (e0 != hipSuccess) { d_fe = nullptr; rc = set_err(c, LTO_EHIP, "free-end buffers", e0); }
+      else {
+        d_tau = d_fe; d_p = d_tau + 2 * (size_t)B; d_em = d_p + 2 * (size_t)B; d_beta = d_em + 14 * (size_t)B;
+        e0 = hipMemcpyAsync(d_tau, fe->tau_in, sizeof(double) * 2 * B, hipMemcpyHostToDevice, st);
+        if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_beta, hb.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
+        if (e0 == hipSuccess) e0 = hipMemsetAsync(d_p, 0, sizeof(double) * 2 * B, st);
+        if (e0 == hipSuccess) e0 = stream_wait(st);        // hb is released at the end of this block
+        if (e0 != hipSuccess) rc = set_err(c, LTO_EHIP, "free-end buffers", e0);
+      }
+    }
+    if (rc == LTO_OK && fe->flag_end) rc = direct_qp_workspace(p, 3);
+    if (rc) { if (d_fe) (void)hipFree(d_fe); p->qp_singular_out = nullptr; direct_plan_free(pl); direct_plan_free(p); return rc; }
+  }
   double alphas[NA];
   for (int a = 0; a < NA; ++a) alphas[a] = 0.1 + (1.0 - 0.1) / (NA - 1) * a;
   alphas[NA - 1] = 1.0;
-  lto::HostBuf<double> h_er(B, 1.0), h_back((size_t)4 * B), h_act(B, -1.0), h_search(B, -1.0);   // er = 1.0 (:488)
+  lto::HostBuf<double> h_er(B, 1.0), h_back((size_t)(fe ? 6 : 4) * B), h_act(B, -1.0), h_search(B, -1.0);   // er = 1.0 (:488)
   lto::HostBuf<int> it(B, 0), status(B, 0);
   lto::HostBuf<char> active(B, 1), moved(B, 0);
   if (!h_er.ok() || !h_back.ok() || !h_act.ok() || !h_search.ok() || !it.ok() || !status.ok() || !active.ok() || !moved.ok()) {
@@ -2283,6 +2522,8 @@ int lto_direct_solve_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, con
   if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * B, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_alphas, alphas, sizeof alphas, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, sizeof(double) * 4 * B, st);
+  // free ends: s0 and sf of the targets from tau (interpEndStates at the current tau, :339-349)
+  if (e == hipSuccess && fe) e = launch_end_states(dob.o, d_tau, B, (double*)d_tg, 19, d_em, st);
   if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage in", e);
   const double* t_cur = d_t;                               // the caller's grid until the first update, then t through tau
 
@@ -2307,8 +2548,15 @@ int lto_direct_solve_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, con
       if (e == hipSuccess) e = hipMemcpyAsync(d_search, h_search.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
       if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "flag upload", e); break; }
     }
+    // flagEnd: free ends on odd iterations, frozen on even ones (:521-526).  The active trajectories share the iteration count.
+    bool free_it = false;
+    if (fe && fe->flag_end)
+      for (int b = 0; b < B; ++b) if (active[b] && (it[b] & 1)) free_it = true;
     rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, t_cur, n_tgrids, d_jac, S, nullptr, nullptr, 0, nullptr);   // :500
-    if (rc == LTO_OK)                                                                                                    // :525-529
+    if (rc == LTO_OK && free_it)
+      rc = direct_qp_step_free_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t1, n_tgrids, d_tg, (const lto_direct_end_model*)d_em,
+                                   d_beta, allow_impulsive, d_dX, d_dU, d_dV, d_p, d_cost);
+    else if (rc == LTO_OK)                                                                                               // :525-529
       rc = lto_direct_qp_step_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t1, n_tgrids, d_tg, allow_impulsive, d_dX, d_dU, d_dV, d_cost);
     if (rc != LTO_OK) break;
     if (search) {                                          // lineSearch (:405-430): the ten trial points of every problem, one sweep
@@ -2325,21 +2573,24 @@ int lto_direct_solve_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, con
     if (e == hipSuccess) e = launch_axpy_traj(d_X, d_dX, d_step, d_X, J, nstate, n_nodes, B, st);     // :562
     if (e == hipSuccess) e = launch_axpy_traj(d_U, d_dU, d_step, d_U, J, 3, n_nodes, B, st);          // :563
     if (e == hipSuccess) e = launch_direct_qp_update_dv((double*)d_tg, d_dV, d_step, B, st);           // :568-569
+    if (e == hipSuccess && free_it) e = launch_tau_update(d_tau, d_p, d_step, B, st);                   // :564-565
+    if (e == hipSuccess && free_it) e = launch_end_states(dob.o, d_tau, B, (double*)d_tg, 19, d_em, st);  // targets at the new tau
     if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "update", e); break; }
     t_cur = d_t1;                                                                                        // :582
     rc = lto_direct_defect_dev(p, st, d_X, J, d_U, J, t_cur, n_tgrids, d_def, S, nullptr);              // :585
     if (rc != LTO_OK) break;
     e = launch_defect_norms(d_def, S, nstate, (int)(n - 1), B, nullptr, d_mx, st);                      // :588
     if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "norm", e); break; }
-    rc = read_scalars(c, st, d_step, 4 * B, nullptr, 0, h_back.data());                                // step | max|d| | cost | singular
+    rc = read_scalars(c, st, d_step, 4 * B, d_tau, fe ? 2 * B : 0, h_back.data());                    // step | max|d| | cost | singular (| tau)
     if (rc != LTO_OK) break;
     for (int b = 0; b < B; ++b) {
       if (!active[b]) continue;
       moved[b] = 1;
       h_er[b] = h_back[B + b];
       if (history) {
-        double* hrow = history + ((size_t)b * maxIter + (it[b] - 1)) * 3;
+        double* hrow = history + ((size_t)b * maxIter + (it[b] - 1)) * hw;
         hrow[0] = h_er[b]; hrow[1] = h_back[2 * B + b]; hrow[2] = h_back[b];
+        if (fe) { hrow[3] = h_back[4 * B + 2 * b]; hrow[4] = h_back[4 * B + 2 * b + 1]; }
       }
       if (h_back[3 * B + b] != 0.0) { status[b] = 3; active[b] = 0; }
     }
@@ -2351,6 +2602,7 @@ int lto_direct_solve_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, con
     if (e == hipSuccess && defect_out) e = stage_out(c, d_def, S, nstate, S, d_def_aos, defect_out, st);
     if (e == hipSuccess && dV_out) e = hipMemcpy2DAsync(dV_out, sizeof(double) * 6, (const double*)d_tg + 13, sizeof(lto_direct_targets),
                                                          sizeof(double) * 6, B, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && fe && fe->tau_out) e = hipMemcpyAsync(fe->tau_out, d_tau, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = stream_wait(st);
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
     if (rc == LTO_OK)
@@ -2365,9 +2617,40 @@ int lto_direct_solve_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, con
     (void)hipStreamSynchronize(st);
   }
   for (int b = 0; b < B; ++b) { status_flag[b] = status[b]; if (iterations) iterations[b] = it[b]; }
+  if (d_fe) (void)hipFree(d_fe);
   direct_plan_free(pl);
   direct_plan_free(p);
   return rc;
+}
+
+int lto_direct_solve_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
+                           const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
+                           const lto_direct_targets* targets, int n_targets, int allow_impulsive, int maxIter, double* X_out,
+                           double* U_out, double* dV_out, double* t_out, double* defect_out, int* status_flag, int* iterations,
+                           double* history) {
+  return direct_solve_impl(c, nstate, n_nodes, n_batch, X_in, U_in, t, n_tgrids, nsteps, prm, targets, n_targets, allow_impulsive,
+                           maxIter, X_out, U_out, dV_out, t_out, defect_out, status_flag, iterations, history, nullptr);
+}
+
+int lto_direct_solve_free_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
+                                const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
+                                const lto_direct_orbits* orbits, const lto_direct_targets* targets, int n_targets,
+                                const double* tau_in, const double* beta, int flag_end, int allow_impulsive, int maxIter,
+                                double* X_out, double* U_out, double* dV_out, double* t_out, double* defect_out, double* tau_out,
+                                int* status_flag, int* iterations, double* history) {
+  const DirectFreeEnds fe = {orbits, tau_in, beta, flag_end ? 1 : 0, tau_out};
+  return direct_solve_impl(c, nstate, n_nodes, n_batch, X_in, U_in, t, n_tgrids, nsteps, prm, targets, n_targets, allow_impulsive,
+                           maxIter, X_out, U_out, dV_out, t_out, defect_out, status_flag, iterations, history, &fe);
+}
+
+int lto_direct_solve_free(lto_ctx* c, int nstate, int n_nodes, const double* X_in, const double* U_in, const double* t, int nsteps,
+                          const lto_direct_params* prm, const lto_direct_orbits* orbits, const lto_direct_targets* targets,
+                          const double* tau_in, double beta, int flag_end, int allow_impulsive, int maxIter, double* X_out,
+                          double* U_out, double* dV_out, double* t_out, double* defect_out, double* tau_out, int* status,
+                          int* iterations, double* history) {
+  return lto_direct_solve_free_batch(c, nstate, n_nodes, 1, X_in, U_in, t, 1, nsteps, prm, orbits, targets, 1, tau_in, &beta, flag_end,
+                                     allow_impulsive, maxIter, X_out, U_out, dV_out, t_out, defect_out, tau_out, status, iterations,
+                                     history);
 }
 
 int lto_direct_solve(lto_ctx* c, int nstate, int n_nodes, const double* X_in, const double* U_in, const double* t, int nsteps,

@@ -355,23 +355,159 @@ def direct_qp_dense(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, mass
     return x_update, u_update, dV1_u, dV2_u, cost
 
 
+END_PERT = 0.05          # pert of the end model's finite differences (direct.jl:340)
+P_BOUND = 0.1            # |p1|, |p2| <= 0.1 with flagEnd (direct.jl:280-284)
+
+
+def end_model(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states):
+    """The free-end model of optimizeTraj (direct.jl:339-349) at (τ1, τ2): interpEndStates at τ and τ ± 0.05 (each argument
+    wrapped on its own), g = central first difference, c = second difference.  Returns (s0, sf, g0, gf, |c0|, |cf|)."""
+    h = END_PERT
+    s0, sf = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states)
+    s0p, sfp = interpEndStates(τ1 + h, τ2 + h, X0_times, X0_states, Xf_times, Xf_states)
+    s0m, sfm = interpEndStates(τ1 - h, τ2 - h, X0_times, X0_states, Xf_times, Xf_states)
+    g0, gf = (s0p - s0m) / (2 * h), (sfp - sfm) / (2 * h)
+    c0, cf = (s0p - 2 * s0 + s0m) / h ** 2, (sfp - 2 * sf + sfm) / h ** 2
+    return s0, sf, g0, gf, float(np.linalg.norm(c0)), float(np.linalg.norm(cf))
+
+
+def direct_qp_dense_free(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, g0, gf, c0_norm, cf_norm, β, mass, dV1, dV2, DU, TU,
+                         allowImpulsive=False):
+    """optimizeTraj with flagEnd = true (direct.jl:278-292, :353-369): the host reference of the device's free-end step, by a
+    different route.  The phase updates p1, p2 are two more variables of one dense KKT system, the end constraints are
+    x_0 + dx_0 + [0; dV1 + d1] = s0 + g0 p1 and x_{n-1} + dx_{n-1} + [0; dV2 + d2] = sf + gf p2, the cost gains
+    β (|c0|/2 p1² + |cf|/2 p2²), and the bounds |p| <= 0.1 are handled by enumerating the nine active sets (each p free, at -0.1
+    or at +0.1).  An active set is accepted when its free p lie in the box and the multipliers of its active bounds have the right
+    sign; the accepted point of smallest cost is returned (ties: smaller max|p|).  Returns (x_update, u_update, dV1_update,
+    dV2_update, p1, p2, cost)."""
+    Jt = np.asarray(Jac_temp, dtype=np.float64)
+    d = np.asarray(defect, dtype=np.float64)
+    X = np.asarray(X_all, dtype=np.float64)
+    U = np.asarray(u_all, dtype=np.float64)
+    t = np.asarray(t_TU, dtype=np.float64)
+    dV1 = np.asarray(dV1, dtype=np.float64)
+    dV2 = np.asarray(dV2, dtype=np.float64)
+    ns, _, S = Jt.shape
+    n = S + 1
+    c2 = (DU / TU) ** 2
+    nz = ns * n + 3 * n + 6 + 2                           # dx (node-major), du, dV1_jump, dV2_jump, p1, p2
+    iu, iv, ip = ns * n, ns * n + 3 * n, ns * n + 3 * n + 6
+    dt = np.diff(t)
+    w = np.concatenate([dt / 2, [dt[-1] / 2]]) + np.concatenate([[0.0], dt[:-1] / 2, [0.0]])
+    Q = np.zeros(nz)
+    q = np.zeros(nz)                                      # cost = z'Qz + 2q'z + const
+    for k in range(n):
+        Q[iu + 3 * k:iu + 3 * k + 3] = w[k]
+        q[iu + 3 * k:iu + 3 * k + 3] = w[k] * U[:, k]
+    Q[iv:iv + 6] = c2
+    q[iv:iv + 3] = c2 * dV1
+    q[iv + 3:iv + 6] = c2 * dV2
+    Q[ip], Q[ip + 1] = β * c0_norm / 2, β * cf_norm / 2
+    rows, rhs = [], []
+    for i in range(S):
+        A = np.zeros((ns, nz))
+        A[:, ns * i:ns * i + 2 * ns] = Jt[:, :2 * ns, i]
+        A[:, iu + 3 * i:iu + 3 * i + 6] = Jt[:, 2 * ns:, i]
+        rows.append(A)
+        rhs.append(-d[:, i])
+    for k, s, g, dv, o in ((0, state_0, g0, dV1, 0), (n - 1, state_f, gf, dV2, 1)):   # linear end model (:356-357)
+        A = np.zeros((6, nz))
+        A[:, ns * k:ns * k + 6] = np.eye(6)
+        A[3:, iv + 3 * o:iv + 3 * o + 3] = np.eye(3)
+        A[:, ip + o] = -np.asarray(g, dtype=np.float64)
+        rows.append(A)
+        rhs.append(np.asarray(s, dtype=np.float64) - X[:6, k] - np.r_[0.0, 0.0, 0.0, dv])
+    if ns == 7:
+        A = np.zeros((1, nz))
+        A[0, 6] = 1.0
+        rows.append(A)
+        rhs.append(np.array([mass - X[6, 0]]))
+    if not allowImpulsive:
+        A = np.zeros((6, nz))
+        A[:, iv:iv + 6] = np.eye(6)
+        rows.append(A)
+        rhs.append(np.zeros(6))
+    A0 = np.vstack(rows)
+    b0 = np.concatenate(rhs)
+    best = None
+    for pat in [(a1, a2) for a1 in (0, -1, 1) for a2 in (0, -1, 1)]:      # 0 free, -1 at -0.1, +1 at +0.1
+        act = [(j, sgn) for j, sgn in enumerate(pat) if sgn]
+        A = A0
+        b = b0
+        if act:
+            Ab = np.zeros((len(act), nz))
+            for r, (j, sgn) in enumerate(act):
+                Ab[r, ip + j] = 1.0
+            A = np.vstack([A0, Ab])
+            b = np.concatenate([b0, [sgn * P_BOUND for _, sgn in act]])
+        m = A.shape[0]
+        K = np.zeros((nz + m, nz + m))
+        K[:nz, :nz] = np.diag(2.0 * Q)
+        K[:nz, nz:] = A.T
+        K[nz:, :nz] = A
+        r = np.concatenate([-2.0 * q, b])
+        D = np.ones(nz + m)
+        with np.errstate(all="ignore"):
+            for _ in range(20):
+                Ks = K * D[:, None] * D[None, :]
+                D = D / np.sqrt(np.maximum(np.abs(Ks).max(axis=1), 1e-300))
+        try:
+            sol = np.linalg.solve(K * D[:, None] * D[None, :], r * D) * D
+        except np.linalg.LinAlgError:
+            continue
+        if not np.all(np.isfinite(sol)):                  # singular for this active set (e.g. beta = 0 and g = 0: p undetermined)
+            continue
+        z, lam = sol[:nz], sol[nz:]
+        p = z[ip:ip + 2]
+        if any(sgn == 0 and abs(p[j]) > P_BOUND * (1 + 1e-12) for j, sgn in enumerate(pat)):
+            continue                                      # a free p outside the box
+        lam_b = lam[A0.shape[0]:]                         # row p_j = ±0.1: grad f + lam e_j = 0, lam >= 0 at +0.1, <= 0 at -0.1
+        scale = 1e-9 * max(1.0, float(np.abs(2.0 * Q * z + 2.0 * q).max()))
+        if any(sgn * lb < -scale for (j, sgn), lb in zip(act, lam_b)):
+            continue
+        p = np.array([sgn * P_BOUND if sgn else p[j] for j, sgn in enumerate(pat)])   # exact bounds
+        dx = z[:ns * n].reshape(n, ns).T
+        du = z[iu:iv].reshape(n, 3).T
+        d1, d2 = (z[iv:iv + 3], z[iv + 3:iv + 6]) if allowImpulsive else (np.zeros(3), np.zeros(3))
+        cost = float(np.sum(w[None, :] * (U + du) ** 2) + c2 * (np.sum((dV1 + d1) ** 2) + np.sum((dV2 + d2) ** 2)) +
+                     β * (c0_norm / 2 * p[0] ** 2 + cf_norm / 2 * p[1] ** 2))
+        key = (cost, float(np.abs(p).max()))
+        if best is None or key < best[0]:
+            best = (key, (dx, du, d1, d2, float(p[0]), float(p[1]), cost))
+    if best is None:
+        raise np.linalg.LinAlgError("direct_qp_dense_free: no active set satisfies the optimality conditions")
+    return best[1]
+
+
 def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states,
                             Xf_times, Xf_states, plot_yn, flagEnd, β, allowImpulsive, maxIter, ops=None, verbose=True):
     """Direct multiple shooting with frozen end points (direct.jl:58-594).  Returns the reference's tuple
     (X_all, u_all, τ1, τ2, t_TU, dV1, dV2, defect).
 
     ops=None: the whole loop is ONE library call (lto_direct_solve: Jacobian sweep, QP step, batched line search and update on
-    the device).  An injected `ops` (defect / jacobian / defect_batch_sumsq, e.g. HipDirectOps or a CPU back end) runs this
-    Python mirror of the loop with the QP solved on the host (direct_qp_dense).  The status of the last call is kept in
-    `multiShoot_CRTBP_direct.last` = {"status", "iterations", "history"} (0 converged, 1 maxIter, 2 NaN, 3 singular KKT system;
-    history rows: max|defect|, cost, alpha) -- the reference prints its progress and returns no flag.
-    flagEnd = true (tau updates inside +-0.1 and the beta-weighted quadratic end-point model, :278-292, :353-369) raises
-    NotImplementedError: that subproblem has inequality bounds, which the exact equality-constrained solve does not cover."""
+    the device); with flagEnd = true it is lto_direct_solve_free (free end points on odd iterations, τ1 and τ2 updated and
+    returned).  An injected `ops` (defect / jacobian / defect_batch_sumsq, e.g. HipDirectOps or a CPU back end) runs this
+    Python mirror of the loop (direct_loop_host) with the QP solved on the host (direct_qp_dense).  The status of the last call
+    is kept in `multiShoot_CRTBP_direct.last` = {"status", "iterations", "history"} (0 converged, 1 maxIter, 2 NaN, 3 singular
+    KKT system; history rows: max|defect|, cost, alpha (, τ1, τ2 with flagEnd)) -- the reference prints its progress and returns
+    no flag.  flagEnd = true with an injected `ops` raises NotImplementedError: only the device path covers it (the mirror loop
+    with free ends is direct_loop_host)."""
+    if flagEnd and ops is not None:
+        raise NotImplementedError("multiShoot_CRTBP_direct: flagEnd = true runs on the device only (ops=None); the host mirror of "
+                                  "the free-end loop is drivers.direct_loop_host")
+    del plot_yn                                           # no plotting
     if flagEnd:
-        raise NotImplementedError("multiShoot_CRTBP_direct: flagEnd = true needs the box-bounded tau updates and the beta penalty "
-                                  "(direct.jl:278-292, :353-369) -- a bound-constrained QP, not covered by the exact "
-                                  "equality-constrained QP step; use flagEnd = false (the reference demo's setting)")
-    del plot_yn, β                                        # no plotting; beta only enters with flagEnd
+        X = np.array(X_all, dtype=np.float64, order="F")
+        state_0, state_f = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU)
+        tg = hotpath.direct_targets(state_0, state_f, mass, dV1, dV2)
+        orbits = hotpath.DirectOrbits(X0_times, X0_states, Xf_times, Xf_states)
+        X, U, dV, t, defect, tau, status, iters, hist = hotpath.direct_solve_free(
+            X, u_all, t_TU, nsteps, MU, DU, TU, Isp, orbits, tg, [τ1, τ2], β, True, allowImpulsive, int(maxIter))
+        if verbose:
+            for k in range(iters):
+                print("Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f. tau1 = %.6f, tau2 = %.6f." % (k + 1, *hist[:, k]))
+        multiShoot_CRTBP_direct.last = {"status": status, "iterations": iters, "history": hist}
+        return X, U, float(tau[0]), float(tau[1]), t, dV[:3].copy(), dV[3:].copy(), defect
     X = np.array(X_all, dtype=np.float64, order="F")
     U = np.array(u_all, dtype=np.float64, order="F")
     t = np.array(t_TU, dtype=np.float64)
@@ -389,11 +525,32 @@ def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, 
                 print("Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f." % (k + 1, hist[0, k], hist[1, k], hist[2, k]))
         multiShoot_CRTBP_direct.last = {"status": status, "iterations": iters, "history": hist}
         return X, U, τ1, τ2, t, dV[:3].copy(), dV[3:].copy(), defect
+    out, last = direct_loop_host(X, U, τ1, τ2, t, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times,
+                                 Xf_states, False, β, allowImpulsive, maxIter, ops, verbose)
+    last["history"] = last["history"][:3]
+    multiShoot_CRTBP_direct.last = last
+    return out
+
+
+def direct_loop_host(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times,
+                     Xf_states, flagEnd, β, allowImpulsive, maxIter, ops, verbose=True):
+    """The Python mirror of the multiShoot_CRTBP_direct loop (direct.jl:477-594) on an injected `ops` back end, the QP solved on
+    the host: direct_qp_dense, or with flagEnd on odd iterations direct_qp_dense_free at the end model of the current τ
+    (:521-526), followed by τ += alpha p (:564-565).  Returns ((X_all, u_all, τ1, τ2, t_TU, dV1, dV2, defect),
+    {"status", "iterations", "history"}) with history rows max|defect|, cost, alpha, τ1, τ2."""
+    X = np.array(X_all, dtype=np.float64, order="F")
+    U = np.array(u_all, dtype=np.float64, order="F")
+    t = np.array(t_TU, dtype=np.float64)
+    dV1 = np.array(dV1, dtype=np.float64).reshape(3)
+    dV2 = np.array(dV2, dtype=np.float64).reshape(3)
+    nstate = X.shape[0]
+    assert X.shape[1] == n_nodes
+    maxIter = int(maxIter)
     t0, tf = t[0], t[-1]
     tau = (t - t0) / (tf - t0) * 2 - 1                   # :480
     t_fixed = t0 + (tau + 1) / 2 * (tf - t0)              # t_TU_fixed (:321) = t after the first update (:582)
     defect, _ = ops.defect(X, U, t, nsteps)               # :485
-    hist = np.full((3, max(maxIter, 1)), np.nan)
+    hist = np.full((5, max(maxIter, 1)), np.nan)
     it, er, status = 0, 1.0, 0                            # er = 1.0: at least one step (:488)
     while er > 1e-6:                                      # :491 (NaN leaves the loop)
         it += 1
@@ -401,8 +558,15 @@ def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, 
             it, status = maxIter, 1
             break
         Jt, _ = ops.jacobian(X, U, t, nsteps)
-        x_up, u_up, dV1_up, dV2_up, cost = direct_qp_dense(Jt, defect, X, U, t_fixed, state_0, state_f, mass, dV1, dV2, DU, TU,
-                                                           allowImpulsive)
+        p1 = p2 = 0.0
+        if flagEnd and it % 2 == 1:                       # free ends on odd iterations (:523-526)
+            s0, sf, g0, gf, c0n, cfn = end_model(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states)
+            x_up, u_up, dV1_up, dV2_up, p1, p2, cost = direct_qp_dense_free(Jt, defect, X, U, t_fixed, s0, sf, g0, gf, c0n, cfn, β,
+                                                                            mass, dV1, dV2, DU, TU, allowImpulsive)
+        else:
+            state_0, state_f = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU)
+            x_up, u_up, dV1_up, dV2_up, cost = direct_qp_dense(Jt, defect, X, U, t_fixed, state_0, state_f, mass, dV1, dV2, DU, TU,
+                                                               allowImpulsive)
         if not np.isfinite(cost):
             status = 3
             break
@@ -413,16 +577,18 @@ def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, 
         U = U + u_up * alpha
         dV1 = dV1 + dV1_up * alpha
         dV2 = dV2 + dV2_up * alpha
+        if flagEnd and it % 2 == 1:
+            τ1 = τ1 + p1 * alpha                          # :564-565, not wrapped
+            τ2 = τ2 + p2 * alpha
         t = t_fixed
         defect, _ = ops.defect(X, U, t, nsteps)           # :585
         er = float(np.abs(defect).max())
-        hist[:, it - 1] = (er, cost, alpha)
+        hist[:, it - 1] = (er, cost, alpha, τ1, τ2)
         if verbose:
             print("Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f." % (it, er, cost, alpha))
     if status == 0 and not np.isfinite(er):
         status = 2
-    multiShoot_CRTBP_direct.last = {"status": status, "iterations": it, "history": hist[:, :maxIter]}
-    return X, U, τ1, τ2, t, dV1, dV2, defect
+    return (X, U, τ1, τ2, t, dV1, dV2, defect), {"status": status, "iterations": it, "history": hist[:, :maxIter]}
 
 
 def lineSearch_direct(X_all, x_update, u_all, u_update, t_TU, nstate, n_nodes, nsteps, Isp, MU, DU, TU, ops=None):

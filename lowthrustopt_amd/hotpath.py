@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from .constants import RK4, RKF78_FIXED, RKF78_ADAPTIVE, DOP853_ADAPTIVE  # noqa: F401
-from ._lib import LtoError, LtoIntegrator, LtoParams, LtoDirectParams, LtoDirectTargets, LTO_EINVAL
+from ._lib import LtoError, LtoIntegrator, LtoParams, LtoDirectParams, LtoDirectTargets, LtoDirectOrbits, LtoDirectEndModel, LTO_EINVAL
 
 
 def integrator(method=DOP853_ADAPTIVE, steps=0, rtol=1e-13, atol=1e-13, max_steps=0):
@@ -723,6 +723,122 @@ def direct_solve(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpu
     if not batched:
         return (Xo[:, :, 0], Uo[:, :, 0], dV[:, 0], to[:, 0], defect[:, :, 0], int(status[0]), int(iters[0]), hist[:, :, 0])
     return Xo, Uo, dV, to, defect, status, iters, hist
+
+
+class DirectOrbits:
+    """lto_direct_orbits over the two orbit tables of the free-end model (times [n], states [>= 6 x n]); keeps the arrays alive."""
+
+    def __init__(self, X0_times, X0_states, Xf_times, Xf_states):
+        self._keep = [np.ascontiguousarray(X0_times, dtype=np.float64).reshape(-1),
+                      np.asfortranarray(np.asarray(X0_states, dtype=np.float64)[:6]),
+                      np.ascontiguousarray(Xf_times, dtype=np.float64).reshape(-1),
+                      np.asfortranarray(np.asarray(Xf_states, dtype=np.float64)[:6])]
+        t0, X0, tf, Xf = self._keep
+        if X0.shape != (6, t0.size) or Xf.shape != (6, tf.size):
+            raise ValueError("orbit tables: states must be [6 x n] with n the number of times")
+        self.struct = LtoDirectOrbits(int(t0.size), int(tf.size), _ptr(t0), _ptr(X0), _ptr(tf), _ptr(Xf))
+
+
+def direct_end_model(g0, gf, c0_norm, cf_norm):
+    """lto_direct_end_model: g0, gf (6 each) and the 2-norms of c0, cf."""
+    m = LtoDirectEndModel()
+    m.g0[:] = [float(v) for v in np.asarray(g0, dtype=np.float64).reshape(6)]
+    m.gf[:] = [float(v) for v in np.asarray(gf, dtype=np.float64).reshape(6)]
+    m.c0_norm, m.cf_norm = float(c0_norm), float(cf_norm)
+    return m
+
+
+def _orbits(orbits):
+    return orbits if isinstance(orbits, DirectOrbits) else DirectOrbits(*orbits)
+
+
+def direct_end_states(tau, orbits, ctx=None):
+    """End targets and end model of the free-end step on the device (lto_direct_end_states).  tau [2] or [2 x B] = (tau1; tau2);
+    orbits = DirectOrbits or (X0_times, X0_states, Xf_times, Xf_states).  Returns (s0, sf, g0, gf, c0_norm, cf_norm) with a
+    trailing batch axis when tau has one."""
+    ctx = ctx or default_context()
+    ob = _orbits(orbits)
+    tau = np.asarray(tau, dtype=np.float64)
+    batched = tau.ndim == 2
+    tau = np.asfortranarray(tau.reshape(2, -1))
+    B = tau.shape[1]
+    s = np.zeros((12, B), order="F")
+    model = (LtoDirectEndModel * B)()
+    ctx.check(ctx.fn("direct_end_states")(ctx.handle, C.byref(ob.struct), B, _ptr(tau), _ptr(s), C.cast(model, C.c_void_p)))
+    g0 = np.array([list(m.g0) for m in model]).T
+    gf = np.array([list(m.gf) for m in model]).T
+    c0 = np.array([m.c0_norm for m in model])
+    cf = np.array([m.cf_norm for m in model])
+    if not batched:
+        return s[:6, 0], s[6:, 0], g0[:, 0], gf[:, 0], float(c0[0]), float(cf[0])
+    return s[:6], s[6:], g0, gf, c0, cf
+
+
+def direct_qp_step_free(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, models, beta, allowImpulsive=False, ctx=None):
+    """One Jacobian sweep and one FREE-END QP step (flagEnd = true, lto_direct_qp_step_free): targets (lto_direct_targets, s0 and
+    sf the end states at the current tau), models (lto_direct_end_model) and beta: one, or one per trajectory.  Returns
+    (x_update, u_update, dV_update[6], p[2] = (p1_update; p2_update), cost) -- with a trailing batch axis on a batched call."""
+    ctx = ctx or default_context()
+    X = _f64(X_all)
+    U = _f64(u_all)
+    ns, n, B, batched = _batch_dims(X)
+    t, ntg = _tgrids(t_TU, n, B)
+    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    tg, ntgt = _targets_array(targets)
+    if isinstance(models, LtoDirectEndModel):
+        models = [models]
+    em = (LtoDirectEndModel * len(models))(*models)
+    bt = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64).reshape(-1), (ntgt,)))
+    if len(models) != ntgt:
+        raise ValueError("need as many end models as targets")
+    dX = np.zeros((ns, n, B), order="F")
+    dU = np.zeros((3, n, B), order="F")
+    dV = np.zeros((6, B), order="F")
+    p = np.zeros((2, B), order="F")
+    cost = np.zeros(B)
+    ctx.check(ctx.fn("direct_qp_step_free")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
+                                              C.cast(tg, C.c_void_p), C.cast(em, C.c_void_p), _ptr(bt), ntgt,
+                                              1 if allowImpulsive else 0, _ptr(dX), _ptr(dU), _ptr(dV), _ptr(p), _ptr(cost)))
+    if not batched:
+        return dX[:, :, 0], dU[:, :, 0], dV[:, 0], p[:, 0], float(cost[0])
+    return dX, dU, dV, p, cost
+
+
+def direct_solve_free(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, orbits, targets, tau, beta, flagEnd=True, allowImpulsive=False,
+                      maxIter=100, ctx=None):
+    """The loop of multiShoot_CRTBP_direct with end points on the orbit tables (lto_direct_solve_free_batch): tau [2] or [2 x B] =
+    (tau1; tau2) per trajectory, beta one or one per target.  The mass and impulses come from targets; s0 and sf are recomputed
+    from tau.  flagEnd: free ends on odd iterations.  Returns (X_all, u_all, dV[6], t_TU, defect, tau[2], status, iterations,
+    history[5 x maxIter] = (max|defect|, cost, alpha, tau1, tau2)); a trailing batch axis on X_all solves a multi-start batch."""
+    ctx = ctx or default_context()
+    X = _f64(X_all)
+    U = _f64(u_all)
+    ns, n, B, batched = _batch_dims(X)
+    t, ntg = _tgrids(t_TU, n, B)
+    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    ob = _orbits(orbits)
+    tg, ntgt = _targets_array(targets)
+    ti = np.asfortranarray(np.broadcast_to(np.asarray(tau, dtype=np.float64).reshape(2, -1), (2, B)))
+    bt = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64).reshape(-1), (ntgt,)))
+    mi = int(maxIter)
+    Xo = np.zeros((ns, n, B), order="F")
+    Uo = np.zeros((3, n, B), order="F")
+    dV = np.zeros((6, B), order="F")
+    to = np.zeros((n, B), order="F")
+    defect = np.zeros((ns, n - 1, B), order="F")
+    tau_o = np.zeros((2, B), order="F")
+    status = np.zeros(B, dtype=np.int32)
+    iters = np.zeros(B, dtype=np.int32)
+    hist = np.full((5, max(mi, 1), B), np.nan, order="F")
+    ctx.check(ctx.fn("direct_solve_free_batch")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
+                                                  C.byref(ob.struct), C.cast(tg, C.c_void_p), ntgt, _ptr(ti), _ptr(bt),
+                                                  1 if flagEnd else 0, 1 if allowImpulsive else 0, mi, _ptr(Xo), _ptr(Uo), _ptr(dV),
+                                                  _ptr(to), _ptr(defect), _ptr(tau_o), _ptr(status), _ptr(iters), _ptr(hist)))
+    hist = hist[:, :mi]
+    if not batched:
+        return (Xo[:, :, 0], Uo[:, :, 0], dV[:, 0], to[:, 0], defect[:, :, 0], tau_o[:, 0], int(status[0]), int(iters[0]),
+                hist[:, :, 0])
+    return Xo, Uo, dV, to, defect, tau_o, status, iters, hist
 
 
 # ------------------------------------------------------------------------------------------------

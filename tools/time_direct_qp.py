@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Time the direct QP step (lto_direct_qp_step_dev) beside the Jacobian sweep it follows, on device-resident operands.
 
-usage: python tools/time_direct_qp.py [segments ...]   (default 30 4096 16384; nstate 6, nsteps 10, one trajectory)
+usage: python tools/time_direct_qp.py [--free] [segments ...]   (default 30 4096 16384; nstate 6, nsteps 10, one trajectory)
 Prints one line per size: mean wall time of the Jacobian sweep and of the QP step over 20 repetitions (HIP events).  For
 per-kernel times run it under `rocprofv3 --kernel-trace --stats -- python tools/time_direct_qp.py` (a run of its own).
+--free: the free-end step (flagEnd = true, lto_direct_qp_step_free) beside the frozen-end step, both through the host-pointer
+entries with the library's kernel timing (HIP events around the QP launches only): median over the repetitions.
 """
 import json
 import os
@@ -58,7 +60,30 @@ def run(S, reps=20, ns=6, nsteps=10):
     return out
 
 
+def run_free(S, reps=20, ns=6, nsteps=10):
+    n = S + 1
+    X, U, T = synth.direct_problem(n, nstate=ns)
+    X, U, t = X[:, :, 0], U[:, :, 0], T[:, 0]
+    tg = lto.direct_targets(X[:6, 0], X[:6, -1], 1000.0, np.zeros(3), np.zeros(3))
+    em = lto.direct_end_model(np.full(6, 0.1), np.full(6, -0.1), 1.0, 1.0)
+    ctx = lto.default_context(0)
+    ctx.set_timing(True)
+    out = {"segments": S}
+    steps = (("frozen_qp_ms", lambda: lto.direct_qp_step(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, 2000.0, tg, ctx=ctx)),
+             ("free_qp_ms", lambda: lto.direct_qp_step_free(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, 2000.0, tg, em, 1.0, ctx=ctx)))
+    for name, f in steps:
+        ms = []
+        for k in range(reps + 3):
+            f()
+            if k >= 3:
+                ms.append(ctx.last_kernel_ms())
+        out[name] = float(np.median(ms))
+    ctx.set_timing(False)
+    return out
+
+
 if __name__ == "__main__":
-    sizes = [int(a) for a in sys.argv[1:]] or [30, 4096, 16384]
+    free = "--free" in sys.argv
+    sizes = [int(a) for a in sys.argv[1:] if a != "--free"] or [30, 4096, 16384]
     for S in sizes:
-        print(json.dumps(run(S)), flush=True)
+        print(json.dumps(run_free(S) if free else run(S)), flush=True)
