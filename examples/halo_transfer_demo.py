@@ -7,6 +7,9 @@ variables (:188-192), then p = 1 at 0.05 N (:240-247) and the rho continuation (
 its direct method (JuMP/Ipopt QP, out of scope here) to smooth the stacked guess; this script goes straight to the
 indirect method, so it needs a few more Newton iterations.  Every defect / Jacobian / Newton solve runs in
 liblto_hip.so; random costates are seeded (the reference's are not).
+
+--mass [Isp] (default 2000 s) continues with the variable-mass system: the p = 2 solution lifted to 14 rows, m0 = 1000 kg,
+free final mass, then p = 1 and the rho continuation; m_f and the fuel used are printed per level.
 """
 import os
 import sys
@@ -39,22 +42,66 @@ def stacked_guess(n_nodes=30, tof_days=20.0, tau1=0.75):
     return X, t
 
 
-def main(seed=0, verbose=True, rho_target=1e-2, python_loop=False):
+def solve_p2(seed=0, verbose=True, ops=None, n=30, mass=1e3):
+    """The demo's p = 2 (minimum energy) solve, thrust unconstrained (10 N): adjoints only, then everything.
+    Returns (XC [12 x n], t, defect, status)."""
+    X, t = stacked_guess(n)
+    rng = np.random.default_rng(seed)
+    XC = np.vstack([X, 0.1 * rng.standard_normal((6, n))])
+    XC[:, 1:-1] += 1e-10 * rng.standard_normal((12, n - 2))
+    XC, defect, flag = drivers.multiShoot_CRTBP_indirect(XC, t, MU, DU, TU, n, mass, 10.0, False, True, 10, 2.0, 1.0, ops=ops, verbose=verbose)
+    XC, defect, flag = drivers.multiShoot_CRTBP_indirect(XC, t, MU, DU, TU, n, mass, 10.0, False, False, 50, 2.0, 1.0, ops=ops, verbose=verbose)
+    return XC, t, defect, flag
+
+
+def mass_run(XC, t, Isp, rho_target, ctx, verbose=True, n=30, mass0=1e3):
+    """Variable-mass extension: the p = 2 solution lifted to 14 rows (m0 = mass0, lambda_m = 0) and solved with the free final
+    mass at the given Isp, then p = 1 at 0.05 N and the rho continuation 1/2, 1/4, ... down to rho_target.
+    Returns {level: (status, max defect, m_f)}."""
+    X14 = drivers.lift_to_mass(XC, mass0)
+    X14, defect, flag = drivers.multiShoot_CRTBP_indirect_mass(X14, t, MU, DU, TU, n, Isp, 10.0, False, False, 50, 2.0, 1.0, verbose=verbose)
+    out = {"p2": (flag, float(np.abs(defect).max()), float(X14[6, -1]))}
+    print("mass, p = 2, Isp %g s: status %d, max defect %.2e, m_f %.3f kg, fuel %.3f kg" % (Isp, flag, np.abs(defect).max(), X14[6, -1], mass0 - X14[6, -1]))
+    if flag != 0:
+        return out
+    X1, defect, flag1 = drivers.multiShoot_CRTBP_indirect_mass(X14, t, MU, DU, TU, n, Isp, 0.05, False, False, 30, 1.0, 1.0, verbose=verbose)
+    out["p1"] = (flag1, float(np.abs(defect).max()), float(X1[6, -1]))
+    print("mass, p = 1, rho = 1: status %d, max defect %.2e, m_f %.3f kg, fuel %.3f kg" % (flag1, np.abs(defect).max(), X1[6, -1], mass0 - X1[6, -1]))
+    if flag1 != 0:
+        return out
+    # rho continuation 1/2, 1/4, ... down to rho_target, each level started from the one before (one device solve per level;
+    # a level that does not converge in 30 iterations falls back to reduceFuel_indirect_mass's back-off from the last good level)
+    rhos = []
+    while (rhos[-1] if rhos else 1.0) / 2 > rho_target:
+        rhos.append((rhos[-1] if rhos else 1.0) / 2)
+    rhos.append(rho_target)
+    X, rho_prev = X1, 1.0
+    for r in rhos:
+        prm = lto.make_params(MU, DU, TU, 0.05, Isp, 1.0, 1.0, r)
+        Xn, Dn, st, its, _ = lto.indirect_solve(X, t, prm, None, False, 30, ctx=ctx)
+        how = "%2d iterations" % its
+        if st != 0:
+            Xn, Dn, st = drivers.reduceFuel_indirect_mass(X, t, MU, DU, TU, n, Isp, 0.05, rho_prev, r, verbose=False)
+            how = "continuation"
+        out["rho=%g" % r] = (int(st), float(np.abs(Dn).max()), float(Xn[6, -1]))
+        print("mass, p = 1, rho = %-9g status %d, %s, max defect %.2e, m_f %.3f kg, fuel %.3f kg"
+              % (r, st, how, np.abs(Dn).max(), Xn[6, -1], mass0 - Xn[6, -1]))
+        if st != 0:
+            break
+        X, rho_prev = Xn, r
+    return out
+
+
+def main(seed=0, verbose=True, rho_target=1e-2, python_loop=False, mass_isp=None):
     ctx = lto.default_context(0)
     # default: every multiShoot_CRTBP_indirect call is ONE library call (lto_indirect_solve: Newton loop, line search
     # and end-state pinning on the device); --python-loop drives the same device operators from the Python mirror of
     # the reference loop.  Integrator: adaptive order-8 pair @1e-13 (the reference's setting).
     ops = drivers.HipOps(ctx) if python_loop else None
     n = 30
-    X, t = stacked_guess(n)
-    rng = np.random.default_rng(seed)
-    XC = np.vstack([X, 0.1 * rng.standard_normal((6, n))])
-    XC[:, 1:-1] += 1e-10 * rng.standard_normal((12, n - 2))
     mass = 1e3
     t0 = time.perf_counter()
-    # p = 2 (minimum energy), thrust unconstrained: adjoints only, then everything
-    XC, defect, flag = drivers.multiShoot_CRTBP_indirect(XC, t, MU, DU, TU, n, mass, 10.0, False, True, 10, 2.0, 1.0, ops=ops, verbose=verbose)
-    XC, defect, flag = drivers.multiShoot_CRTBP_indirect(XC, t, MU, DU, TU, n, mass, 10.0, False, False, 50, 2.0, 1.0, ops=ops, verbose=verbose)
+    XC, t, defect, flag = solve_p2(seed, verbose, ops, n, mass)
     print("p = 2: status %d, max defect %.2e" % (flag, np.abs(defect).max()))
     res = {"p2": (flag, float(np.abs(defect).max()))}
     if flag == 0:
@@ -71,10 +118,22 @@ def main(seed=0, verbose=True, rho_target=1e-2, python_loop=False):
                 lam = np.linalg.norm(XD[9:12], axis=0)
                 thr = 0.5 * (1 + np.tanh((lam - 1) / (2 * rho_target))) * 0.05
                 print("thrust profile: on %.0f %% of the flight, max %.3f N" % (100 * np.mean(thr > 0.025), thr.max()))
+    if mass_isp is not None and flag == 0:
+        res["mass"] = mass_run(XC, t, mass_isp, rho_target, ctx, verbose, n, mass)
     print("wall time %.2f s" % (time.perf_counter() - t0))
     return res
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if not a.startswith("-")]
-    main(rho_target=float(args[0]) if args else 1e-2, verbose="-q" not in sys.argv, python_loop="--python-loop" in sys.argv)
+    # usage: halo_transfer_demo.py [rho_target] [-q] [--python-loop] [--mass [Isp]]
+    argv = sys.argv[1:]
+    mass_isp = None
+    if "--mass" in argv:
+        i = argv.index("--mass")
+        mass_isp = 2000.0
+        if i + 1 < len(argv) and not argv[i + 1].startswith("-"):
+            mass_isp = float(argv[i + 1])
+            del argv[i + 1]
+        del argv[i]
+    args = [a for a in argv if not a.startswith("-")]
+    main(rho_target=float(args[0]) if args else 1e-2, verbose="-q" not in argv, python_loop="--python-loop" in argv, mass_isp=mass_isp)

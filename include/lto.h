@@ -164,7 +164,8 @@ int lto_indirect_jacobian(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, cons
  * least-squares step of optimizeTraj_OLS (:149-218) incl. the flag_adjointsOnly column mask (:169-178) and the
  * second-order correction (:190-214, applied when norm(xc_update, Inf) < soc_threshold; the reference uses 1e-1).
  * Only XC and t are uploaded and xc_update [ndim x n_nodes x n_batch] and (optionally) the nominal defect are
- * downloaded; Phi stays in HBM. */
+ * downloaded; Phi stays in HBM.  ndim = 12 or 14 (pinned entries: see lto_indirect_solve); the step reads XC as given (it does
+ * not reset lambda_m(tf)) and leaves exact zeros in the pinned entries of xc_update. */
 int lto_indirect_newton_step(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, const double* XC, const double* t,
                              int n_tgrids, const lto_params* prm, int n_prm, const lto_integrator* integ,
                              int flag_adjointsOnly, double soc_threshold, double* xc_update, double* defect);
@@ -173,7 +174,12 @@ int lto_indirect_newton_step(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, c
  * resident in HBM: while max|defect| > 1e-10 { jacobianCalc; optimizeTraj_OLS incl. adjoints-only mask and second-order
  * correction (:149-218); after iteration 3 the 20-point lineSearch (:221-246) as ONE batched sweep; XC += alpha *
  * xc_update; end states re-pinned (:324-325); defectCalc }.  Only scalars cross PCIe inside the loop.
- *   XC_in, XC_out [12 x n_nodes] (may alias), defect [12 x (n_nodes-1)] or NULL,
+ *   ndim = 12: the reference's system; pinned XC[0:6, 0] and XC[0:6, n-1] (the end states).
+ *   ndim = 14: the variable-mass system (r, v, m, lambda_r, lambda_v, lambda_m), Isp in prm->mass; pinned XC[0:7, 0] (r0, v0 and
+ *              the initial mass m0) and XC[0:6, n-1] (rf, vf) and XC[13, n-1] = lambda_m(tf) = 0, the transversality condition of
+ *              the FREE final mass XC[6, n-1].  The loop sets XC[13, n-1] to 0 on entry.  Unknowns 7 + 14(n-2) + 7 = 14(n-1):
+ *              the regular step is square; adjoints-only masks the 7 state columns of every node (least squares).
+ *   XC_in, XC_out [ndim x n_nodes] (may alias), defect [ndim x (n_nodes-1)] or NULL,
  *   *status_flag: 0 converged, 1 maxIter reached (also after "Not likely to converge", :333-336), 2 NaN (:339-341),
  *   *iterations (or NULL): the reference's iterCount on exit,
  *   history (or NULL): [2 x maxIter] column k = (max|defect|, alpha) after iteration k+1 -- the progress line of :332. */
@@ -184,8 +190,8 @@ int lto_indirect_solve(lto_ctx* ctx, int ndim, int n_nodes, const double* XC_in,
 /* n_batch independent problems through the same loop, side by side (homotopy / thrust levels, several initial guesses:
  * the concurrent form of the continuation of src/HelperFunctions.jl:105-193).  Every device operation covers the
  * whole batch; a trajectory that has left the reference loop (converged, NaN, iteration limit) is frozen by a zero
- * step length.  Arrays carry a trailing batch dimension: XC [12 x n_nodes x n_batch], t [n_nodes x n_tgrids],
- * prm [n_prm] (n_tgrids, n_prm = 1 or n_batch), defect [12 x (n_nodes-1) x n_batch], status_flag / iterations
+ * step length.  Arrays carry a trailing batch dimension: XC [ndim x n_nodes x n_batch], t [n_nodes x n_tgrids],
+ * prm [n_prm] (n_tgrids, n_prm = 1 or n_batch), defect [ndim x (n_nodes-1) x n_batch], status_flag / iterations
  * [n_batch], history [2 x maxIter x n_batch]. */
 int lto_indirect_solve_batch(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, const double* XC_in, const double* t,
                              int n_tgrids, const lto_params* prm, int n_prm, const lto_integrator* integ,
@@ -480,7 +486,8 @@ const int* lto_direct_plan_qp_status(const lto_direct_plan* plan);
  * the state columns of every node are masked out (:169-178) and the over-determined system is solved in the
  * least-squares sense, as `\` does.  Phi != NULL factors and solves; Phi == NULL re-uses the stored factorisation
  * of the same variant for a new right-hand side (the second-order-correction re-solve, :190-214).
- * delta is SoA [12][ldx], node-indexed. */
+ * delta is SoA [ndim][ldx], node-indexed.  ndim = 14 plans: the pinned columns are those of lto_indirect_solve (first node
+ * 0-6, last node 0-5 and 13), and delta is exactly 0 there; LTO_LAYOUT_BLOCKS plans are refused for either ndim. */
 int lto_indirect_newton_solve_dev(lto_indirect_plan* plan, void* stream, const double* Phi, long ldp,
                                   const double* defect, long ldd, int adjoints_only, double* delta, long ldx);
 /* y[i] = x[i] + alpha d[i], i < count (trial points X + alpha dX, update accumulation) */

@@ -169,7 +169,8 @@ function indirect_jacobianCalc(ctx::LtoHandle, XC_all, t_TU, nstate, n_nodes, pa
 end
 
 """One Newton iteration on the device (indirect.jl:290-296): jacobianCalc, the least-squares step of
-optimizeTraj_OLS (incl. the flag_adjointsOnly column mask) and its second-order correction; returns (xc_update, defect)."""
+optimizeTraj_OLS (incl. the flag_adjointsOnly column mask) and its second-order correction; returns (xc_update, defect).
+12 or 14 rows; for 14 the pinned entries are those of `indirect_solve`."""
 function indirect_newton_step(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}, params;
                               integ::LtoIntegrator = LtoIntegrator(), flag_adjointsOnly::Bool = false,
                               soc_threshold::Float64 = 1e-1)
@@ -203,7 +204,8 @@ end
 the GPU: returns (XC_all, defect, status_flag) exactly as the reference driver does, so
 `multiShoot_CRTBP_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass0, thrustLimit, plot_yn, flag_adjointsOnly, maxIter, p, rho)`
 can forward to `indirect_solve(LTO, XC_all, t_TU, (MU, DU, TU, thrustLimit, mass0, 1.0, p, rho), flag_adjointsOnly, maxIter)`
-when `plot_yn` is false."""
+when `plot_yn` is false.  14 rows (r, v, m, λ_r, λ_v, λ_m; Isp in the tuple's mass slot) solve the variable-mass system with a
+free final mass: XC_all[1:7, 1], XC_all[1:6, end] and XC_all[14, end] = λ_m(tf) = 0 are pinned (the last is set on entry)."""
 function indirect_solve(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}, params, flag_adjointsOnly::Bool,
                         maxIter::Integer; integ::LtoIntegrator = LtoIntegrator(), verbose::Bool = true)
     ndim, n_nodes = size(XC_all)
@@ -227,7 +229,7 @@ function indirect_solve(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{F
     (XC_new, defect1, Int(status[]))
 end
 
-"""n_batch independent Newton loops side by side (`lto_indirect_solve_batch`): `XC_all` [12 x n_nodes x n_batch], `t_TU`
+"""n_batch independent Newton loops side by side (`lto_indirect_solve_batch`): `XC_all` [12 or 14 x n_nodes x n_batch], `t_TU`
 [n_nodes] (shared grid), `params` a vector of n_batch parameter tuples (e.g. one rho per level of a continuation ladder).
 Returns (XC_all, defect, status_flags, iterCounts)."""
 function indirect_solve_batch(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::Vector{Float64}, params::Vector,

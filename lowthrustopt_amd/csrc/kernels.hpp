@@ -150,9 +150,9 @@ hipError_t launch_end_states(const EndOrbitsDev& o, const double* tau, int n_bat
                              hipStream_t st);
 hipError_t launch_tau_update(double* tau, const double* p, const double* step, int n_batch, hipStream_t st);
 
-// Newton step of the indirect method on the device (kernels_bvp.hip): structured orthogonal cyclic reduction.
-size_t bvp_workspace_doubles(int n_nodes, int n_batch);
-hipError_t launch_bvp_solve(const double* Phi, long ldp, const double* defect, long ldd, int n_nodes, int n_batch,
+// Newton step of the indirect method on the device (kernels_bvp.hip): structured orthogonal cyclic reduction, ndim = 12 or 14.
+size_t bvp_workspace_doubles(int ndim, int n_nodes, int n_batch);
+hipError_t launch_bvp_solve(int ndim, const double* Phi, long ldp, const double* defect, long ldd, int n_nodes, int n_batch,
                             int adjoints_only, double* workspace, double* delta, long ldx, hipStream_t st);
 hipError_t launch_axpy(const double* x, const double* d, double alpha, double* y, long count, hipStream_t st);
 
@@ -212,6 +212,9 @@ hipError_t launch_take_trial(const double* trial, long ldt, const double* ss, co
                              hipStream_t st);   // step != nullptr: also k_pick_alpha's outputs (one launch for both)
 hipError_t launch_iter_report(const double* a, int na, const double* b, int nb, double* host_dev, long long* seq_dev, long long seq, hipStream_t st);
 hipError_t launch_end_states(double* X, long ld, int n, int nb, int nrow, double* saved, int restore, hipStream_t st);
+// 14-dim pins: saved[b][14] = first node rows 0-6, last node rows 0-5 and 13.  restore = 0 also sets the last node's row 13
+// (lambda_m(tf)) to 0 before saving it; restore = 1 writes the saved values back.
+hipError_t launch_end_pins14(double* X, long ld, int n, int nb, double* saved, int restore, hipStream_t st);
 hipError_t launch_defect_norms(const double* defect, long ldd, int ndim, int seg_per_traj, int n_batch, double* sumsq,
                                double* maxabs, hipStream_t st);
 

@@ -27,104 +27,119 @@
 
 namespace lto {
 
-// Two variants (template parameter NU = free unknowns per node):
-//   NU = 12  the square system of the regular iterations (all 12 components of the interior nodes free, the two end
+// Four variants (template parameters NX = rows of a block row = the state + costate dimension, NU = free unknowns per node):
+//   NX = 12, NU = 12  the square system of the regular iterations (all 12 components of the interior nodes free, the two end
 //            states fixed): 24 x 36 stacks, 12 reflections eliminate the shared unknown, the other 12 rows ARE the new
 //            block row.
-//   NU = 6   flag_adjointsOnly (indirect.jl:169-178): only the costates are free, A_i = Phi_i[:, 7:12], B_i = -I[:, 7:12];
+//   NX = 12, NU = 6   flag_adjointsOnly (indirect.jl:169-178): only the costates are free, A_i = Phi_i[:, 7:12], B_i = -I[:, 7:12];
 //            the system is over-determined (12(n-1) equations, 6n unknowns) and is solved in the least-squares sense,
 //            as `\` does: the 24 x 18 stack is triangularised completely (18 reflections); rows 0-5 define the shared
 //            unknown, rows 6-17 are the new (upper-trapezoidal) block row, rows 18-23 carry only residual and drop out.
-template <int NU> struct BvpDims {
-  static constexpr int NK = (NU == 12) ? 12 : 18;            // Householder reflections per pair
+//   NX = 14, NU = 14  the variable-mass system y = (r, v, m, lambda_r, lambda_v, lambda_m), square: 28 x 43 stacks, 14 reflections.
+//            43 + 28 identity columns do not fit one wavefront, so Q^T is formed in a SECOND pass (see bvp_reflect_store).
+//   NX = 14, NU = 7   its adjoints-only variant (the 7 costates free): 28 x 22 stacks, 21 reflections; rows 0-6 the eliminated
+//            unknown, rows 7-20 the new block row, rows 21-27 residual only; 22 + 28 = 50 lanes, Q^T in the idle lanes as for 12.
+// Pinned end-state columns (zero columns of Jac_full, :141-142): 12-dim first node 0-5, last node 0-5; 14-dim first node 0-6
+// (r0, v0, m0), last node 0-5 and 13 (rf, vf, lambda_m(tf) = 0: the final mass is free).
+template <int NX, int NU> struct BvpDims {
+  static_assert(NU == NX || 2 * NU == NX, "square or costates-only");
+  static constexpr int R2 = 2 * NX;                          // rows of a pair's stack
+  static constexpr int NK = (NU == NX) ? NX : 3 * NU;        // Householder reflections per pair
   static constexpr int NCOLS = 3 * NU + 1;                   // mid | left | right | rhs
-  static constexpr int NLANES = NCOLS + 24;                  // ... | the 24 columns of the identity, which end up as Q^T
-  static constexpr int ROW = 24 * NU + 12;                   // A (12 x NU), B (12 x NU), r (12)
+  static constexpr bool QT_PASS = NCOLS + R2 > 64;           // the identity does not fit the idle lanes: Q^T by a second pass
+  static constexpr int NLANES = QT_PASS ? NCOLS : NCOLS + R2; // ... | the R2 columns of the identity, which end up as Q^T
+  static constexpr int ROW = 2 * NX * NU + NX;               // A (NX x NU), B (NX x NU), r (NX)
   static constexpr int REC_R = 0, REC_CA = NU * NU, REC_CB = 2 * NU * NU, REC_G = 3 * NU * NU;
-  static constexpr int REC_QT = 3 * NU * NU + NU, REC = REC_QT + 24 * 24;    // QT[c][r] = (Q^T)_{r c}: lane r reads consecutive doubles
+  static constexpr int REC_QT = 3 * NU * NU + NU, REC = REC_QT + R2 * R2;    // QT[c][r] = (Q^T)_{r c}: lane r reads consecutive doubles
   static_assert(NLANES <= 64, "one wavefront per pair");
+  static_assert(!QT_PASS || (NU == NX && NU + R2 <= NCOLS - 1), "the second pass runs in the left / right lanes");
 };
+// Pinned columns of the end nodes, as column indices of Phi (0 .. NX-1)
+template <int NX> __device__ __forceinline__ constexpr bool bvp_pinned_first(const int pc) { return pc < NX / 2; }
+template <int NX> __device__ __forceinline__ constexpr bool bvp_pinned_last(const int pc) { return pc < 6 || (NX == 14 && pc == 13); }
 constexpr int BVP_CHUNK = 16;      // block rows per workgroup of a chunk launch (four levels)
 constexpr int BVP_CHUNK_LEVELS = 4;
 
 struct BvpArgs {
   int n_nodes, n_batch, S_traj;       // S_traj = n_nodes - 1
   double* rec;                        // [n_batch][n_nodes][REC]  (entries 1 .. n_nodes-2 used)
-  double* delta; long ldx;            // SoA [12][ldx], node j = b*n_nodes + k
+  double* delta; long ldx;            // SoA [NX][ldx], node j = b*n_nodes + k
   const double* Phi; long ldp;        // the sweep's outputs: level-0 rows are read from them directly
   const double* defect; long ldd;
 };
 
 // ---- the stack of a pair, lane c = column c: [mid | left | right | rhs | identity]
 // from two block rows in memory (global or LDS)
-template <int NU>
-__device__ __forceinline__ void bvp_stack_rows(const double* top, const double* bot, const int c, double (&col)[24]) {
-  using D = BvpDims<NU>;
+template <int NX, int NU>
+__device__ __forceinline__ void bvp_stack_rows(const double* top, const double* bot, const int c, double (&col)[2 * NX]) {
+  using D = BvpDims<NX, NU>;
 #pragma unroll
-  for (int r = 0; r < 24; ++r) col[r] = 0.0;
+  for (int r = 0; r < D::R2; ++r) col[r] = 0.0;
   if (c < NU) {                        // shared unknown: [B_top; A_bot]
 #pragma unroll
-    for (int r = 0; r < 12; ++r) { col[r] = top[12 * NU + c * 12 + r]; col[12 + r] = bot[c * 12 + r]; }
+    for (int r = 0; r < NX; ++r) { col[r] = top[NX * NU + c * NX + r]; col[NX + r] = bot[c * NX + r]; }
   } else if (c < 2 * NU) {             // left unknown: [A_top; 0]
 #pragma unroll
-    for (int r = 0; r < 12; ++r) col[r] = top[(c - NU) * 12 + r];
+    for (int r = 0; r < NX; ++r) col[r] = top[(c - NU) * NX + r];
   } else if (c < 3 * NU) {             // right unknown: [0; B_bot]
 #pragma unroll
-    for (int r = 0; r < 12; ++r) col[12 + r] = bot[12 * NU + (c - 2 * NU) * 12 + r];
+    for (int r = 0; r < NX; ++r) col[NX + r] = bot[NX * NU + (c - 2 * NU) * NX + r];
   } else if (c == 3 * NU) {
 #pragma unroll
-    for (int r = 0; r < 12; ++r) { col[r] = top[24 * NU + r]; col[12 + r] = bot[24 * NU + r]; }
+    for (int r = 0; r < NX; ++r) { col[r] = top[2 * NX * NU + r]; col[NX + r] = bot[2 * NX * NU + r]; }
   } else if (c < D::NLANES) {
 #pragma unroll
-    for (int r = 0; r < 24; ++r) col[r] = (r == c - D::NCOLS) ? 1.0 : 0.0;
+    for (int r = 0; r < D::R2; ++r) col[r] = (r == c - D::NCOLS) ? 1.0 : 0.0;
   }
 }
 // element e of the level-0 block row of segment i of trajectory b (s = b S_traj + i): [A | B | r] from the sweep's outputs
-template <int NU>
+template <int NX, int NU>
 __device__ __forceinline__ double bvp_row0_A(const BvpArgs& a, const long s, const int i, const int c, const int r) {
-  const int pc = (NU == 12) ? c : 6 + c;                                            // columns of Phi_i that belong to free unknowns
-  return (NU == 12 && i == 0 && c < 6) ? 0.0 : a.Phi[(long)(pc * 12 + r) * a.ldp + s];   // fixed initial state (:141)
+  const int pc = (NU == NX) ? c : NX - NU + c;                                      // columns of Phi_i that belong to free unknowns
+  if constexpr (NX == 12) return (NU == 12 && i == 0 && c < 6) ? 0.0 : a.Phi[(long)(pc * 12 + r) * a.ldp + s];   // fixed initial state (:141)
+  else return (NU == NX && i == 0 && bvp_pinned_first<NX>(pc)) ? 0.0 : a.Phi[(long)(pc * NX + r) * a.ldp + s];
 }
-template <int NU>
+template <int NX, int NU>
 __device__ __forceinline__ double bvp_row0_B(const BvpArgs& a, const int i, const int c, const int r) {
-  const int pc = (NU == 12) ? c : 6 + c;                                            // -I restricted to the free unknowns
-  return (r == pc && !(NU == 12 && i == a.S_traj - 1 && c < 6)) ? -1.0 : 0.0;       // fixed final state (:142)
+  const int pc = (NU == NX) ? c : NX - NU + c;                                      // -I restricted to the free unknowns
+  if constexpr (NX == 12) return (r == pc && !(NU == 12 && i == a.S_traj - 1 && c < 6)) ? -1.0 : 0.0;   // fixed final state (:142)
+  else return (r == pc && !(i == a.S_traj - 1 && bvp_pinned_last<NX>(pc))) ? -1.0 : 0.0;
 }
 // ... the stack of the level-0 pair (2j, 2j + 1) without materialising the rows
-template <int NU>
-__device__ __forceinline__ void bvp_stack_sweep(const BvpArgs& a, const int b, const int j, const int c, double (&col)[24]) {
-  using D = BvpDims<NU>;
+template <int NX, int NU>
+__device__ __forceinline__ void bvp_stack_sweep(const BvpArgs& a, const int b, const int j, const int c, double (&col)[2 * NX]) {
+  using D = BvpDims<NX, NU>;
   const int it = 2 * j, ib = 2 * j + 1;
   const long st = (long)b * a.S_traj + it, sb = st + 1;
 #pragma unroll
-  for (int r = 0; r < 24; ++r) col[r] = 0.0;
+  for (int r = 0; r < D::R2; ++r) col[r] = 0.0;
   if (c < NU) {
 #pragma unroll
-    for (int r = 0; r < 12; ++r) { col[r] = bvp_row0_B<NU>(a, it, c, r); col[12 + r] = bvp_row0_A<NU>(a, sb, ib, c, r); }
+    for (int r = 0; r < NX; ++r) { col[r] = bvp_row0_B<NX, NU>(a, it, c, r); col[NX + r] = bvp_row0_A<NX, NU>(a, sb, ib, c, r); }
   } else if (c < 2 * NU) {
 #pragma unroll
-    for (int r = 0; r < 12; ++r) col[r] = bvp_row0_A<NU>(a, st, it, c - NU, r);
+    for (int r = 0; r < NX; ++r) col[r] = bvp_row0_A<NX, NU>(a, st, it, c - NU, r);
   } else if (c < 3 * NU) {
 #pragma unroll
-    for (int r = 0; r < 12; ++r) col[12 + r] = bvp_row0_B<NU>(a, ib, c - 2 * NU, r);
+    for (int r = 0; r < NX; ++r) col[NX + r] = bvp_row0_B<NX, NU>(a, ib, c - 2 * NU, r);
   } else if (c == 3 * NU) {
 #pragma unroll
-    for (int r = 0; r < 12; ++r) { col[r] = -a.defect[(long)r * a.ldd + st]; col[12 + r] = -a.defect[(long)r * a.ldd + sb]; }
+    for (int r = 0; r < NX; ++r) { col[r] = -a.defect[(long)r * a.ldd + st]; col[NX + r] = -a.defect[(long)r * a.ldd + sb]; }
   } else if (c < D::NLANES) {
 #pragma unroll
-    for (int r = 0; r < 24; ++r) col[r] = (r == c - D::NCOLS) ? 1.0 : 0.0;
+    for (int r = 0; r < D::R2; ++r) col[r] = (r == c - D::NCOLS) ? 1.0 : 0.0;
   }
 }
 // a level-0 row that has no partner (odd count): materialised as it is carried up
-template <int NU>
+template <int NX, int NU>
 __device__ __forceinline__ void bvp_row_from_sweep(const BvpArgs& a, const int b, const int i, double* dst, const int lane) {
-  using D = BvpDims<NU>;
+  using D = BvpDims<NX, NU>;
   const long s = (long)b * a.S_traj + i;
   for (int e = lane; e < D::ROW; e += 64) {
     double v;
-    if (e < 12 * NU) v = bvp_row0_A<NU>(a, s, i, e / 12, e % 12);
-    else if (e < 24 * NU) v = bvp_row0_B<NU>(a, i, (e - 12 * NU) / 12, (e - 12 * NU) % 12);
-    else v = -a.defect[(long)(e - 24 * NU) * a.ldd + s];
+    if (e < NX * NU) v = bvp_row0_A<NX, NU>(a, s, i, e / NX, e % NX);
+    else if (e < 2 * NX * NU) v = bvp_row0_B<NX, NU>(a, i, (e - NX * NU) / NX, (e - NX * NU) % NX);
+    else v = -a.defect[(long)(e - 2 * NX * NU) * a.ldd + s];
     dst[e] = v;
   }
 }
@@ -151,26 +166,65 @@ __device__ __forceinline__ void bvp_static_for(F&& f) {
   }
 }
 
+// Reflection k of a column stack of R rows held one column per lane, applied to the lanes c in (k, LANES): the reflection of
+// bvp_reflect_store below (see there), for the 14-dim final solve.  Lane k keeps beta on its diagonal and the reflector's tail
+// below it; vk_out / g_out return the reflector's head and scale.
+template <int R, int K, int LANES>
+__device__ __forceinline__ void bvp_reflect(double (&col)[R], const int c, double& vk_out, double& g_out) {
+  constexpr int k = K;
+  double x[R];
+#pragma unroll
+  for (int r = k + 1; r < R; ++r) x[r] = lane_bcast<k>(col[r]);
+  const double alpha = lane_bcast<k>(col[k]);
+  double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+#pragma unroll
+  for (int r = k + 1; r < R; ++r) {
+    if (((r - k - 1) & 3) == 0) q0 = __builtin_fma(x[r], x[r], q0);
+    else if (((r - k - 1) & 3) == 1) q1 = __builtin_fma(x[r], x[r], q1);
+    else if (((r - k - 1) & 3) == 2) q2 = __builtin_fma(x[r], x[r], q2);
+    else q3 = __builtin_fma(x[r], x[r], q3);
+  }
+  const double xn2 = (q0 + q1) + (q2 + q3);
+  const bool trivial = (xn2 == 0.0);                 // nothing below the diagonal: H = I
+  const double n2 = __builtin_fma(alpha, alpha, xn2);
+  const double nrm = n2 * rsqrt_nr(n2);
+  const double beta = (alpha >= 0.0) ? -nrm : nrm;
+  const double vk = alpha - beta;
+  const double g = trivial ? 0.0 : rcp_nr(beta * (beta - alpha));
+  vk_out = vk; g_out = g;
+  if (c == k && !trivial) col[k] = beta;
+  if (c > k && c < LANES) {
+    double w0 = vk * col[k], w1 = 0.0, w2 = 0.0, w3 = 0.0;
+#pragma unroll
+    for (int r = k + 1; r < R; ++r) {
+      if (((r - k - 1) & 3) == 0) w0 = __builtin_fma(x[r], col[r], w0);
+      else if (((r - k - 1) & 3) == 1) w1 = __builtin_fma(x[r], col[r], w1);
+      else if (((r - k - 1) & 3) == 2) w2 = __builtin_fma(x[r], col[r], w2);
+      else w3 = __builtin_fma(x[r], col[r], w3);
+    }
+    const double w = ((w0 + w1) + (w2 + w3)) * g;
+    col[k] = __builtin_fma(-w, vk, col[k]);
+#pragma unroll
+    for (int r = k + 1; r < R; ++r) col[r] = __builtin_fma(-w, x[r], col[r]);
+  }
+}
+
 // ---- NK Householder reflections on the stack (one wavefront, lane = column; the reflector of step k is lane k's column,
 // broadcast by v_readlane), then the record of the eliminated node `rec` and the new block row `nr`
-template <int NU>
-__device__ __forceinline__ void bvp_reflect_store(double (&col)[24], const int c, double* rec, double* nr) {
-  using D = BvpDims<NU>;
+template <int NX, int NU>
+__device__ __forceinline__ void bvp_reflect_store(double (&col)[2 * NX], const int c, double* rec, double* nr) {
+  using D = BvpDims<NX, NU>;
+  constexpr int R2 = D::R2;
+  double my_v = 0.0, my_g = 0.0;        // QT_PASS: lane k keeps the head and scale of reflector k
   bvp_static_for<0, D::NK>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
-    // Reflection k: H = I - g v v^T with v = (alpha - beta, x_{k+1}, ..., x_23) taken from lane k's column AS IT IS, beta =
-    // -sign(alpha) |(alpha, x)|, g = 1 / (beta (beta - alpha)).  Round 4: the reflector is not normalised (nobody stores it any
-    // more -- the record keeps R and the explicit Q^T), so lane k's column is broadcast first (v_readlane, overlapping the norm's
-    // chain), every lane forms the same norm and g from the broadcast values (one reciprocal square root and ONE reciprocal by
-    // Newton refinement of the hardware seeds, ~1 ulp), and the 23 scaling multiplications and the broadcast of tau are gone:
-    // ~130 instead of ~165 instructions per reflection, twelve (eighteen) reflections per pair.
-    double x[24];
+    double x[R2];
 #pragma unroll
-    for (int r = k + 1; r < 24; ++r) x[r] = lane_bcast<k>(col[r]);
+    for (int r = k + 1; r < R2; ++r) x[r] = lane_bcast<k>(col[r]);
     const double alpha = lane_bcast<k>(col[k]);
     double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
 #pragma unroll
-    for (int r = k + 1; r < 24; ++r) {
+    for (int r = k + 1; r < R2; ++r) {
       if (((r - k - 1) & 3) == 0) q0 = __builtin_fma(x[r], x[r], q0);
       else if (((r - k - 1) & 3) == 1) q1 = __builtin_fma(x[r], x[r], q1);
       else if (((r - k - 1) & 3) == 2) q2 = __builtin_fma(x[r], x[r], q2);
@@ -183,11 +237,15 @@ __device__ __forceinline__ void bvp_reflect_store(double (&col)[24], const int c
     const double beta = (alpha >= 0.0) ? -nrm : nrm;
     const double vk = alpha - beta;
     const double g = trivial ? 0.0 : rcp_nr(beta * (beta - alpha));
+    if constexpr (D::QT_PASS) { if (c == k) { my_v = vk; my_g = g; } }
     if (c == k && !trivial) col[k] = beta;
-    if (c > k && c < D::NLANES) {
+    // The 14-dim adjoints-only stack triangularises an all-zero column (the pinned lambda_m(tf) column of the last node); then
+    // beta = 0 * rsqrt(0) is NaN and H = I must not be applied as 0 * NaN.  (The other stacks triangularise only columns that
+    // are nonzero in a regular system: code unchanged.)
+    if (c > k && c < D::NLANES && !(NX == 14 && NU < NX && trivial)) {
       double w0 = vk * col[k], w1 = 0.0, w2 = 0.0, w3 = 0.0;
 #pragma unroll
-      for (int r = k + 1; r < 24; ++r) {
+      for (int r = k + 1; r < R2; ++r) {
         if (((r - k - 1) & 3) == 0) w0 = __builtin_fma(x[r], col[r], w0);
         else if (((r - k - 1) & 3) == 1) w1 = __builtin_fma(x[r], col[r], w1);
         else if (((r - k - 1) & 3) == 2) w2 = __builtin_fma(x[r], col[r], w2);
@@ -196,10 +254,10 @@ __device__ __forceinline__ void bvp_reflect_store(double (&col)[24], const int c
       const double w = ((w0 + w1) + (w2 + w3)) * g;
       col[k] = __builtin_fma(-w, vk, col[k]);
 #pragma unroll
-      for (int r = k + 1; r < 24; ++r) col[r] = __builtin_fma(-w, x[r], col[r]);
+      for (int r = k + 1; r < R2; ++r) col[r] = __builtin_fma(-w, x[r], col[r]);
     }
   });
-  // rows 0 .. NU-1: the eliminated unknown; rows NU .. NU+11: the new block row (entries below the diagonal of a
+  // rows 0 .. NU-1: the eliminated unknown; rows NU .. NU+NX-1: the new block row (entries below the diagonal of a
   // triangularised column are reflector storage, i.e. structural zeros of the matrix)
   if (c < NU) {
 #pragma unroll
@@ -208,20 +266,54 @@ __device__ __forceinline__ void bvp_reflect_store(double (&col)[24], const int c
 #pragma unroll
     for (int r = 0; r < NU; ++r) rec[D::REC_CA + (c - NU) * NU + r] = col[r];
 #pragma unroll
-    for (int r = 0; r < 12; ++r) nr[(c - NU) * 12 + r] = (c < D::NK && NU + r > c) ? 0.0 : col[NU + r];
+    for (int r = 0; r < NX; ++r) nr[(c - NU) * NX + r] = (c < D::NK && NU + r > c) ? 0.0 : col[NU + r];
   } else if (c < 3 * NU) {
 #pragma unroll
     for (int r = 0; r < NU; ++r) rec[D::REC_CB + (c - 2 * NU) * NU + r] = col[r];
 #pragma unroll
-    for (int r = 0; r < 12; ++r) nr[12 * NU + (c - 2 * NU) * 12 + r] = (c < D::NK && NU + r > c) ? 0.0 : col[NU + r];
+    for (int r = 0; r < NX; ++r) nr[NX * NU + (c - 2 * NU) * NX + r] = (c < D::NK && NU + r > c) ? 0.0 : col[NU + r];
   } else if (c == 3 * NU) {
 #pragma unroll
     for (int r = 0; r < NU; ++r) rec[D::REC_G + r] = col[r];
 #pragma unroll
-    for (int r = 0; r < 12; ++r) nr[24 * NU + r] = col[NU + r];
-  } else if (c < D::NLANES) {          // column c' of the identity has become Q^T e_c'
+    for (int r = 0; r < NX; ++r) nr[2 * NX * NU + r] = col[NU + r];
+  } else if (!D::QT_PASS && c < D::NLANES) {   // column c' of the identity has become Q^T e_c'
 #pragma unroll
-    for (int r = 0; r < 24; ++r) rec[D::REC_QT + (c - D::NCOLS) * 24 + r] = col[r];
+    for (int r = 0; r < R2; ++r) rec[D::REC_QT + (c - D::NCOLS) * R2 + r] = col[r];
+  }
+  if constexpr (D::QT_PASS) {
+    // 14-dim square: 43 columns + 28 of the identity > 64 lanes.  The left / right lanes NU .. NU+R2-1 are free once their
+    // columns are stored above; they take the identity and the NK reflectors are applied again, each broadcast from the lane that
+    // formed it (its tail is still below its diagonal, its head and scale in my_v / my_g).  Same operations as the one-pass form
+    // applies to its identity lanes: Q^T costs a second NK-reflection pass, and the re-solve stays one matrix-vector product.
+    const bool q = (c >= NU && c < NU + R2);
+#pragma unroll
+    for (int r = 0; r < R2; ++r) if (q) col[r] = (r == c - NU) ? 1.0 : 0.0;
+    bvp_static_for<0, D::NK>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      double x[R2];
+#pragma unroll
+      for (int r = k + 1; r < R2; ++r) x[r] = lane_bcast<k>(col[r]);
+      const double vk = lane_bcast<k>(my_v), g = lane_bcast<k>(my_g);
+      if (q) {
+        double w0 = vk * col[k], w1 = 0.0, w2 = 0.0, w3 = 0.0;
+#pragma unroll
+        for (int r = k + 1; r < R2; ++r) {
+          if (((r - k - 1) & 3) == 0) w0 = __builtin_fma(x[r], col[r], w0);
+          else if (((r - k - 1) & 3) == 1) w1 = __builtin_fma(x[r], col[r], w1);
+          else if (((r - k - 1) & 3) == 2) w2 = __builtin_fma(x[r], col[r], w2);
+          else w3 = __builtin_fma(x[r], col[r], w3);
+        }
+        const double w = ((w0 + w1) + (w2 + w3)) * g;
+        col[k] = __builtin_fma(-w, vk, col[k]);
+#pragma unroll
+        for (int r = k + 1; r < R2; ++r) col[r] = __builtin_fma(-w, x[r], col[r]);
+      }
+    });
+    if (q) {
+#pragma unroll
+      for (int r = 0; r < R2; ++r) rec[D::REC_QT + (c - NU) * R2 + r] = col[r];
+    }
   }
 }
 
@@ -229,19 +321,19 @@ __device__ __forceinline__ void bvp_reflect_store(double (&col)[24], const int c
 __device__ __forceinline__ int bvp_mid(const int j, const int level) { return (2 * j + 1) << level; }
 
 // ---- level-0 rows into a buffer (only when the whole problem fits the tail launch: at most 16 segments)
-template <int NU>
+template <int NX, int NU>
 __global__ __launch_bounds__(64) void k_bvp_rows0(BvpArgs a, double* rows) {
-  using D = BvpDims<NU>;
+  using D = BvpDims<NX, NU>;
   const int i = blockIdx.x, b = blockIdx.y;
-  bvp_row_from_sweep<NU>(a, b, i, rows + ((long)b * a.S_traj + i) * D::ROW, threadIdx.x);
+  bvp_row_from_sweep<NX, NU>(a, b, i, rows + ((long)b * a.S_traj + i) * D::ROW, threadIdx.x);
 }
-template <int NU>
+template <int NX, int NU>
 __global__ __launch_bounds__(256) void k_bvp_rhs0(BvpArgs a, double* rhs) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;       // over S_total * 12
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;       // over S_total * NX
   const long S_total = (long)a.S_traj * a.n_batch;
-  if (idx >= S_total * 12) return;
-  const long s = idx / 12;
-  const int c = (int)(idx - s * 12);
+  if (idx >= S_total * NX) return;
+  const long s = idx / NX;
+  const int c = (int)(idx - s * NX);
   rhs[idx] = -a.defect[(long)c * a.ldd + s];
 }
 
@@ -249,9 +341,9 @@ __global__ __launch_bounds__(256) void k_bvp_rhs0(BvpArgs a, double* rhs) {
 // `level0` (M0 rows; FIRST: level 0, read from the sweep's outputs) and everything that grows out of them: 8, 4, 2, 1 pairs in
 // as many wavefronts, the rows in between in LDS, its one row of level level0 + 4 to out[g].  A row without a partner (odd
 // count) is carried up unchanged.
-template <int NU, bool FIRST>
+template <int NX, int NU, bool FIRST>
 __global__ __launch_bounds__(512) void k_bvp_chunk(BvpArgs a, const int level0, const int M0, const double* __restrict__ cur, double* __restrict__ out) {
-  using D = BvpDims<NU>;
+  using D = BvpDims<NX, NU>;
   __shared__ double bufA[8][D::ROW];
   __shared__ double bufB[4][D::ROW];
   const int g = blockIdx.x, b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -267,12 +359,12 @@ __global__ __launch_bounds__(512) void k_bvp_chunk(BvpArgs a, const int level0, 
       const double* top = (l == 0) ? rows + (long)(2 * j) * D::ROW : (l == 1) ? bufA[2 * wave] : (l == 2) ? bufB[2 * wave] : bufA[0];
       const double* bot = (l == 0) ? top + D::ROW : (l == 1) ? bufA[2 * wave + 1] : (l == 2) ? bufB[2 * wave + 1] : bufA[1];
       if (2 * j + 1 < M) {
-        double col[24];
-        if (FIRST && l == 0) bvp_stack_sweep<NU>(a, b, j, lane, col);
-        else bvp_stack_rows<NU>(top, bot, lane, col);
-        bvp_reflect_store<NU>(col, lane, a.rec + ((long)b * a.n_nodes + bvp_mid(j, level0 + l)) * D::REC, dst);
+        double col[D::R2];
+        if (FIRST && l == 0) bvp_stack_sweep<NX, NU>(a, b, j, lane, col);
+        else bvp_stack_rows<NX, NU>(top, bot, lane, col);
+        bvp_reflect_store<NX, NU>(col, lane, a.rec + ((long)b * a.n_nodes + bvp_mid(j, level0 + l)) * D::REC, dst);
       } else if (FIRST && l == 0) {
-        bvp_row_from_sweep<NU>(a, b, 2 * j, dst, lane);
+        bvp_row_from_sweep<NX, NU>(a, b, 2 * j, dst, lane);
       } else {
         for (int e = lane; e < D::ROW; e += 64) dst[e] = top[e];
       }
@@ -283,40 +375,41 @@ __global__ __launch_bounds__(512) void k_bvp_chunk(BvpArgs a, const int level0, 
 }
 
 // ---- a new right-hand side through the stored orthogonal factors (the second-order-correction re-solve): per pair
-// x' = Q^T [r_top; r_bot], 32 lanes (lane r = row r), the first NU entries are the eliminated node's g, the next 12 the new
-// row's right-hand side.  Right-hand sides travel in their own small buffers [n_batch][S_traj][12].
-template <int NU>
+// x' = Q^T [r_top; r_bot], 32 lanes (lane r = row r), the first NU entries are the eliminated node's g, the next NX the new
+// row's right-hand side.  Right-hand sides travel in their own small buffers [n_batch][S_traj][NX].
+template <int NX, int NU>
 __device__ __forceinline__ void bvp_rhs_pair(const double* xt, const double* xb, const double* rec_c, double* rec_g, double* nr, const int r) {
-  using D = BvpDims<NU>;
-  const int rr = r < 24 ? r : 23;
+  using D = BvpDims<NX, NU>;
+  constexpr int R2 = D::R2;
+  const int rr = r < R2 ? r : R2 - 1;
   double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
-  for (int c = 0; c < 12; c += 2) {
-    acc0 = __builtin_fma(rec_c[D::REC_QT + c * 24 + rr], xt[c], acc0);
-    acc1 = __builtin_fma(rec_c[D::REC_QT + (c + 1) * 24 + rr], xt[c + 1], acc1);
+  for (int c = 0; c < NX; c += 2) {
+    acc0 = __builtin_fma(rec_c[D::REC_QT + c * R2 + rr], xt[c], acc0);
+    acc1 = __builtin_fma(rec_c[D::REC_QT + (c + 1) * R2 + rr], xt[c + 1], acc1);
   }
 #pragma unroll
-  for (int c = 0; c < 12; c += 2) {
-    acc0 = __builtin_fma(rec_c[D::REC_QT + (12 + c) * 24 + rr], xb[c], acc0);
-    acc1 = __builtin_fma(rec_c[D::REC_QT + (13 + c) * 24 + rr], xb[c + 1], acc1);
+  for (int c = 0; c < NX; c += 2) {
+    acc0 = __builtin_fma(rec_c[D::REC_QT + (NX + c) * R2 + rr], xb[c], acc0);
+    acc1 = __builtin_fma(rec_c[D::REC_QT + (NX + 1 + c) * R2 + rr], xb[c + 1], acc1);
   }
   const double x = acc0 + acc1;
   if (r < NU) rec_g[D::REC_G + r] = x;
-  else if (r < NU + 12) nr[r - NU] = x;
+  else if (r < NU + NX) nr[r - NU] = x;
 }
-template <int NU, bool FIRST>
+template <int NX, int NU, bool FIRST>
 __global__ __launch_bounds__(256) void k_bvp_chunk_rhs(BvpArgs a, const int level0, const int M0, const double* __restrict__ cur, double* __restrict__ out) {
-  using D = BvpDims<NU>;
-  __shared__ double x0[16][12];      // FIRST: this workgroup's level-0 right-hand sides
-  __shared__ double xA[8][12];
-  __shared__ double xB[4][12];
+  using D = BvpDims<NX, NU>;
+  __shared__ double x0[16][NX];      // FIRST: this workgroup's level-0 right-hand sides
+  __shared__ double xA[8][NX];
+  __shared__ double xB[4][NX];
   const int g = blockIdx.x, b = blockIdx.y, grp = threadIdx.x >> 5, r = threadIdx.x & 31;
-  const double* rows = cur + (long)b * a.S_traj * 12;
-  double* orow = out + ((long)b * a.S_traj + g) * 12;
+  const double* rows = cur + (long)b * a.S_traj * NX;
+  double* orow = out + ((long)b * a.S_traj + g) * NX;
   int M = M0;
   if (FIRST) {
-    if (threadIdx.x < 16 * 12) {
-      const int i = threadIdx.x / 12, c = threadIdx.x % 12;
+    if (threadIdx.x < 16 * NX) {
+      const int i = threadIdx.x / NX, c = threadIdx.x % NX;
       const int ig = g * BVP_CHUNK + i;
       x0[i][c] = (ig < M0) ? -a.defect[(long)c * a.ldd + (long)b * a.S_traj + ig] : 0.0;
     }
@@ -328,12 +421,12 @@ __global__ __launch_bounds__(256) void k_bvp_chunk_rhs(BvpArgs a, const int leve
     const int j = g * width + grp;
     if (grp < width && 2 * j < M) {
       double* dst = (l == 0) ? xA[grp] : (l == 1) ? xB[grp] : (l == 2) ? xA[grp] : orow;
-      const double* top = (l == 0) ? (FIRST ? x0[2 * grp] : rows + (long)(2 * j) * 12) : (l == 1) ? xA[2 * grp] : (l == 2) ? xB[2 * grp] : xA[0];
-      const double* bot = (l == 0) ? (FIRST ? x0[2 * grp + 1] : top + 12) : (l == 1) ? xA[2 * grp + 1] : (l == 2) ? xB[2 * grp + 1] : xA[1];
+      const double* top = (l == 0) ? (FIRST ? x0[2 * grp] : rows + (long)(2 * j) * NX) : (l == 1) ? xA[2 * grp] : (l == 2) ? xB[2 * grp] : xA[0];
+      const double* bot = (l == 0) ? (FIRST ? x0[2 * grp + 1] : top + NX) : (l == 1) ? xA[2 * grp + 1] : (l == 2) ? xB[2 * grp + 1] : xA[1];
       if (2 * j + 1 < M) {
         double* rec = a.rec + ((long)b * a.n_nodes + bvp_mid(j, level0 + l)) * D::REC;
-        bvp_rhs_pair<NU>(top, bot, rec, rec, dst, r);
-      } else if (r < 12) {
+        bvp_rhs_pair<NX, NU>(top, bot, rec, rec, dst, r);
+      } else if (r < NX) {
         dst[r] = top[r];
       }
     }
@@ -407,20 +500,65 @@ __device__ __forceinline__ void bvp_final_one(const BvpArgs& a, const double* ro
   }
 }
 
+// 14-dim last level: the free unknowns of the two end nodes are the 7 costates of the first node and, of the last node, m and
+// lambda_r, lambda_v (square: 14 x 14) or lambda_r, lambda_v only (adjoints-only: 14 x 13, least squares).  Householder QR with
+// lane = column (the pair reduction's reflection, 14 rows), then back-substitution on broadcast values.  The re-solve forms it
+// again from the kept matrix and the new right-hand side (one small problem per trajectory).
+template <int NU>
+__device__ __forceinline__ void bvp_final_qr14(const BvpArgs& a, const double* row, const double* rhs, const int b, const int lane) {
+  constexpr int NX = 14;
+  constexpr bool SQ = (NU == NX);
+  constexpr int oA = SQ ? 7 : 0, oB = SQ ? 6 : 0;      // first free column of A / B (in the row's column numbering)
+  constexpr int nA = 7, nB = SQ ? 7 : 6, NC = nA + nB;  // free columns; lane NC carries the right-hand side
+  double col[NX];
+#pragma unroll
+  for (int r = 0; r < NX; ++r) {
+    double v = 0.0;
+    if (lane < nA) v = row[(oA + lane) * NX + r];
+    else if (lane < NC) v = row[NX * NU + (oB + lane - nA) * NX + r];
+    else if (lane == NC) v = rhs ? rhs[r] : row[2 * NX * NU + r];
+    col[r] = v;
+  }
+  bvp_static_for<0, NC>([&](auto kc) {
+    double vk, g;
+    bvp_reflect<NX, decltype(kc)::value, NC + 1>(col, lane, vk, g);
+  });
+  double y[NC], x[NC];
+#pragma unroll
+  for (int r = 0; r < NC; ++r) y[r] = lane_bcast<NC>(col[r]);      // Q^T r, the rows that meet R
+  bvp_static_for<0, NC>([&](auto kc) {
+    constexpr int k = NC - 1 - decltype(kc)::value;
+    x[k] = y[k] / lane_bcast<k>(col[k]);
+#pragma unroll
+    for (int r = 0; r < k; ++r) y[r] = __builtin_fma(-lane_bcast<k>(col[r]), x[k], y[r]);
+  });
+  if (lane == 0) {
+    const long n0 = (long)b * a.n_nodes, n1 = n0 + a.n_nodes - 1;
+    constexpr int off = NX - NU;
+#pragma unroll
+    for (int r = 0; r < NX; ++r) { a.delta[(long)r * a.ldx + n0] = 0.0; a.delta[(long)r * a.ldx + n1] = 0.0; }
+#pragma unroll
+    for (int c = 0; c < nA; ++c) a.delta[(long)(off + oA + c) * a.ldx + n0] = x[c];
+#pragma unroll
+    for (int c = 0; c < nB; ++c) a.delta[(long)(off + oB + c) * a.ldx + n1] = x[nA + c];
+  }
+}
+
 // Back-substitution of one pair: d_mid = R^{-1} (g - Ca d_left - Cb d_right), SIXTEEN lanes per pair (lane r = row r of the
 // unknown): the record's matrices are read as rows of NU consecutive doubles.  Lane r forms s_r = g_r - (Ca d_left + Cb
 // d_right)_r, then the triangular solve runs column by column: lane k divides, broadcasts x_k inside the 16-lane group, the
 // lanes above it update their s.
-template <int NU>
+template <int NX, int NU>
 __device__ __forceinline__ void bvp_backsub_pair16(const BvpArgs& a, int level, int M, const int j, const int b, const int r) {
-  using D = BvpDims<NU>;
+  using D = BvpDims<NX, NU>;
+  static_assert(NU <= 16, "one 16-lane group per pair");
   if (j >= M / 2) return;               // uniform for the 16 lanes of a pair
   const int mid = (2 * j + 1) << level, left = (2 * j) << level;
   int right = (2 * j + 2) << level;
   if (right > a.n_nodes - 1) right = a.n_nodes - 1;
   const double* rec = a.rec + ((long)b * a.n_nodes + mid) * D::REC;
   const long nb = (long)b * a.n_nodes;
-  constexpr int off = 12 - NU;
+  constexpr int off = NX - NU;
   const int rr = r < NU ? r : NU - 1;   // lanes NU..15 shadow the last row (no stores)
   double s = rec[D::REC_G + rr];
 #pragma unroll
@@ -439,13 +577,13 @@ __device__ __forceinline__ void bvp_backsub_pair16(const BvpArgs& a, int level, 
     s = __builtin_fma(-rec[D::REC_R + k * NU + (rr < k ? rr : 0)], (rr < k) ? xk : 0.0, s);
   });
   if (r < NU) a.delta[(long)(off + r) * a.ldx + nb + mid] = x;
-  if (NU == 6 && r < 6) a.delta[(long)r * a.ldx + nb + mid] = 0.0;       // states are not updated
+  if (NU < NX && r < NX - NU) a.delta[(long)r * a.ldx + nb + mid] = 0.0;   // states are not updated
 }
 
 // ---- FOUR levels of the back-substitution in one launch, the mirror image of k_bvp_chunk: workgroup g forms the unknowns its
 // chunk eliminated at levels level0 + 3 .. level0 (1, 2, 4, 8 pairs, sixteen lanes each); their outer unknowns are its own of
 // the level before or those of earlier launches.  (Workgroup-scope ordering of the unknowns through global memory.)
-template <int NU>
+template <int NX, int NU>
 __global__ __launch_bounds__(128) void k_bvp_backchunk(BvpArgs a, const int level0, const int M0) {
   const int g = blockIdx.x, b = blockIdx.y, grp = threadIdx.x >> 4, r = threadIdx.x & 15;
   int Ms[BVP_CHUNK_LEVELS];
@@ -455,20 +593,20 @@ __global__ __launch_bounds__(128) void k_bvp_backchunk(BvpArgs a, const int leve
 #pragma unroll
   for (int l = BVP_CHUNK_LEVELS - 1; l >= 0; --l) {
     const int width = 8 >> l;
-    if (grp < width) bvp_backsub_pair16<NU>(a, level0 + l, Ms[l], g * width + grp, b, r);
+    if (grp < width) bvp_backsub_pair16<NX, NU>(a, level0 + l, Ms[l], g * width + grp, b, r);
     __syncthreads();
   }
 }
 
 // ---- the top of the tree in ONE launch: at most 16 block rows -- the remaining levels (8 pairs = 8 wavefronts, 2 per SIMD: the
-// full register budget), the final 12 x 12 solve and the matching back-substitution levels inside one 512-thread workgroup per
+// full register budget), the final NX x NX solve and the matching back-substitution levels inside one 512-thread workgroup per
 // trajectory, separated by __syncthreads() (workgroup-scope ordering of the global-memory block rows).  A 30-node problem
 // (the reference demo) is a chunk launch, this one and a back-substitution launch.
 // factor = 0: the re-solve; `rows` then only supplies the last level's matrix (kept from the factorisation), the right-hand
 // sides travel through rhs_cur / rhs_nxt.
-template <int NU>
+template <int NX, int NU>
 __global__ __launch_bounds__(512) void k_bvp_tail(BvpArgs a, int level0, int M0, double* cur, double* nxt, double* rhs_cur, double* rhs_nxt, int factor) {
-  using D = BvpDims<NU>;
+  using D = BvpDims<NX, NU>;
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   int M = M0, level = level0;
   int Ms[8];
@@ -479,21 +617,21 @@ __global__ __launch_bounds__(512) void k_bvp_tail(BvpArgs a, int level0, int M0,
       const double* rows = cur + (long)b * a.S_traj * D::ROW;
       double* orows = nxt + (long)b * a.S_traj * D::ROW;
       if (wave < npairs) {
-        double col[24];
-        bvp_stack_rows<NU>(rows + (long)(2 * wave) * D::ROW, rows + (long)(2 * wave + 1) * D::ROW, lane, col);
-        bvp_reflect_store<NU>(col, lane, a.rec + ((long)b * a.n_nodes + bvp_mid(wave, level)) * D::REC, orows + (long)wave * D::ROW);
+        double col[D::R2];
+        bvp_stack_rows<NX, NU>(rows + (long)(2 * wave) * D::ROW, rows + (long)(2 * wave + 1) * D::ROW, lane, col);
+        bvp_reflect_store<NX, NU>(col, lane, a.rec + ((long)b * a.n_nodes + bvp_mid(wave, level)) * D::REC, orows + (long)wave * D::ROW);
       } else if (wave == npairs && carry) {
         for (int e = lane; e < D::ROW; e += 64) orows[(long)npairs * D::ROW + e] = rows[(long)(M - 1) * D::ROW + e];
       }
     } else {
-      const double* rows = rhs_cur + (long)b * a.S_traj * 12;
-      double* orows = rhs_nxt + (long)b * a.S_traj * 12;
+      const double* rows = rhs_cur + (long)b * a.S_traj * NX;
+      double* orows = rhs_nxt + (long)b * a.S_traj * NX;
       const int grp = tid >> 5, r = tid & 31;
       if (grp < npairs) {
         double* rec = a.rec + ((long)b * a.n_nodes + bvp_mid(grp, level)) * D::REC;
-        bvp_rhs_pair<NU>(rows + (long)(2 * grp) * 12, rows + (long)(2 * grp + 1) * 12, rec, rec, orows + (long)grp * 12, r);
-      } else if (grp == npairs && carry && r < 12) {
-        orows[(long)npairs * 12 + r] = rows[(long)(M - 1) * 12 + r];
+        bvp_rhs_pair<NX, NU>(rows + (long)(2 * grp) * NX, rows + (long)(2 * grp + 1) * NX, rec, rec, orows + (long)grp * NX, r);
+      } else if (grp == npairs && carry && r < NX) {
+        orows[(long)npairs * NX + r] = rows[(long)(M - 1) * NX + r];
       }
     }
     __syncthreads();
@@ -502,10 +640,15 @@ __global__ __launch_bounds__(512) void k_bvp_tail(BvpArgs a, int level0, int M0,
     M = npairs + carry;
     ++level;
   }
-  if (wave == 0) bvp_final_one<NU>(a, cur + (long)b * a.S_traj * D::ROW, factor ? nullptr : rhs_cur + (long)b * a.S_traj * 12, b, lane);
+  if (wave == 0) {
+    const double* frow = cur + (long)b * a.S_traj * D::ROW;
+    const double* frhs = factor ? nullptr : rhs_cur + (long)b * a.S_traj * NX;
+    if constexpr (NX == 12) bvp_final_one<NU>(a, frow, frhs, b, lane);
+    else bvp_final_qr14<NU>(a, frow, frhs, b, lane);
+  }
   __syncthreads();
   for (int l = level - 1; l >= level0; --l) {
-    bvp_backsub_pair16<NU>(a, l, Ms[l - level0], tid >> 4, b, tid & 15);     // at most 8 pairs: 32 groups of 16 lanes
+    bvp_backsub_pair16<NX, NU>(a, l, Ms[l - level0], tid >> 4, b, tid & 15);     // at most 8 pairs: 32 groups of 16 lanes
     __syncthreads();
   }
 }
@@ -519,20 +662,23 @@ __global__ __launch_bounds__(256) void k_axpy(const double* __restrict__ x, cons
 
 // Workspace: the rows of the levels that cross launches (level 4: a sixteenth of the segments, level 8: ...; the level-0 rows
 // of a problem of at most 16 segments), two of them; two right-hand-side buffers; the records; the last level's row kept
-// for the re-solve.  Sized for the larger (NU = 12) variant; the adjoints-only variant uses a prefix of every part.
-static size_t bvp_rows_doubles(int n_nodes, int n_batch) { return (size_t)(n_nodes - 1) * n_batch * BvpDims<12>::ROW; }
-size_t bvp_workspace_doubles(int n_nodes, int n_batch) {
+// for the re-solve.  Sized for the larger (square) variant of the dimension; the adjoints-only variant uses a prefix of every part.
+static size_t bvp_rows_doubles(int ndim, int n_nodes, int n_batch) {
+  return (size_t)(n_nodes - 1) * n_batch * (ndim == 14 ? BvpDims<14, 14>::ROW : BvpDims<12, 12>::ROW);
+}
+size_t bvp_workspace_doubles(int ndim, int n_nodes, int n_batch) {
   // (the level-4 buffer needs a sixteenth of this, but a trajectory's rows keep the pitch S_traj * ROW in every buffer: simple
   // indexing for 4 096 segments x 2.4 KB x 2 = 20 MB)
-  return 2 * bvp_rows_doubles(n_nodes, n_batch) + 2 * (size_t)(n_nodes - 1) * n_batch * 12 + (size_t)n_nodes * n_batch * BvpDims<12>::REC;
+  const size_t rec = (ndim == 14) ? BvpDims<14, 14>::REC : BvpDims<12, 12>::REC;
+  return 2 * bvp_rows_doubles(ndim, n_nodes, n_batch) + 2 * (size_t)(n_nodes - 1) * n_batch * ndim + (size_t)n_nodes * n_batch * rec;
 }
 
-template <int NU>
+template <int NX, int NU>
 static hipError_t bvp_solve_impl(const double* Phi, long ldp, const double* defect, long ldd, int n_nodes, int n_batch,
                                  double* workspace, double* delta, long ldx, hipStream_t st) {
   BvpArgs a;
   a.n_nodes = n_nodes; a.n_batch = n_batch; a.S_traj = n_nodes - 1;
-  const size_t rows_sz = bvp_rows_doubles(n_nodes, n_batch), rhs_sz = (size_t)a.S_traj * n_batch * 12;
+  const size_t rows_sz = bvp_rows_doubles(NX, n_nodes, n_batch), rhs_sz = (size_t)a.S_traj * n_batch * NX;
   double* rowsA = workspace;
   double* rowsB = workspace + rows_sz;
   double* rhsA = workspace + 2 * rows_sz;
@@ -542,7 +688,7 @@ static hipError_t bvp_solve_impl(const double* Phi, long ldp, const double* defe
   a.Phi = Phi; a.ldp = ldp; a.defect = defect; a.ldd = ldd;
   const bool factor = (Phi != nullptr);
   // The re-solve walks the same sequence of buffer swaps as the factorisation, so its tail finds the last level's row -- the
-  // matrix of the final 12 x 12 system, which only the factorisation forms -- where that pass left it.
+  // matrix of the final NX x NX system, which only the factorisation forms -- where that pass left it.
   int M = a.S_traj, level = 0;
   int Ms[48];
   double* cur = rowsA;
@@ -550,20 +696,31 @@ static hipError_t bvp_solve_impl(const double* Phi, long ldp, const double* defe
   double* rcur = rhsA;
   double* rnxt = rhsB;
   bool first = true;
+  // 14-dim square: the chunk kernel that reads the level-0 stacks straight from the sweep's outputs needs more than the 256
+  // registers two waves per SIMD leave (its second Q^T pass keeps the reflectors live), so its level-0 rows are materialised
+  // first (3.2 KB per segment written and read once) and the chunk kernel of the higher levels takes them.
+  constexpr bool rows_first = BvpDims<NX, NU>::QT_PASS;
+  if (rows_first && factor && M > BVP_CHUNK) {
+    hipLaunchKernelGGL((k_bvp_rows0<NX, NU>), dim3(M, n_batch), dim3(64), 0, st, a, cur);
+  }
   if (M <= BVP_CHUNK) {                // the whole problem fits the tail: materialise its level-0 rows
-    if (factor) hipLaunchKernelGGL((k_bvp_rows0<NU>), dim3(M, n_batch), dim3(64), 0, st, a, cur);
-    else hipLaunchKernelGGL((k_bvp_rhs0<NU>), dim3((unsigned)(((long)M * n_batch * 12 + 255) / 256)), dim3(256), 0, st, a, rcur);
+    if (factor) hipLaunchKernelGGL((k_bvp_rows0<NX, NU>), dim3(M, n_batch), dim3(64), 0, st, a, cur);
+    else hipLaunchKernelGGL((k_bvp_rhs0<NX, NU>), dim3((unsigned)(((long)M * n_batch * NX + 255) / 256)), dim3(256), 0, st, a, rcur);
   }
   while (M > BVP_CHUNK) {
     const int Mn = (M + BVP_CHUNK - 1) / BVP_CHUNK;
     int m = M;
     for (int l = 0; l < BVP_CHUNK_LEVELS; ++l) { Ms[level + l] = m; m = (m + 1) / 2; }
     if (factor) {
-      if (first) hipLaunchKernelGGL((k_bvp_chunk<NU, true>), dim3(Mn, n_batch), dim3(512), 0, st, a, level, M, cur, nxt);
-      else hipLaunchKernelGGL((k_bvp_chunk<NU, false>), dim3(Mn, n_batch), dim3(512), 0, st, a, level, M, cur, nxt);
+      if constexpr (!rows_first) {
+        if (first) hipLaunchKernelGGL((k_bvp_chunk<NX, NU, true>), dim3(Mn, n_batch), dim3(512), 0, st, a, level, M, cur, nxt);
+        else hipLaunchKernelGGL((k_bvp_chunk<NX, NU, false>), dim3(Mn, n_batch), dim3(512), 0, st, a, level, M, cur, nxt);
+      } else {
+        hipLaunchKernelGGL((k_bvp_chunk<NX, NU, false>), dim3(Mn, n_batch), dim3(512), 0, st, a, level, M, cur, nxt);
+      }
     } else {
-      if (first) hipLaunchKernelGGL((k_bvp_chunk_rhs<NU, true>), dim3(Mn, n_batch), dim3(256), 0, st, a, level, M, rcur, rnxt);
-      else hipLaunchKernelGGL((k_bvp_chunk_rhs<NU, false>), dim3(Mn, n_batch), dim3(256), 0, st, a, level, M, rcur, rnxt);
+      if (first) hipLaunchKernelGGL((k_bvp_chunk_rhs<NX, NU, true>), dim3(Mn, n_batch), dim3(256), 0, st, a, level, M, rcur, rnxt);
+      else hipLaunchKernelGGL((k_bvp_chunk_rhs<NX, NU, false>), dim3(Mn, n_batch), dim3(256), 0, st, a, level, M, rcur, rnxt);
     }
     { double* t = cur; cur = nxt; nxt = t; }
     { double* t = rcur; rcur = rnxt; rnxt = t; }
@@ -572,19 +729,23 @@ static hipError_t bvp_solve_impl(const double* Phi, long ldp, const double* defe
     level += BVP_CHUNK_LEVELS;
   }
   // remaining levels, final solve and their back-substitution in one launch per trajectory
-  hipLaunchKernelGGL((k_bvp_tail<NU>), dim3(n_batch), dim3(512), 0, st, a, level, M, cur, nxt, rcur, rnxt, factor ? 1 : 0);
+  hipLaunchKernelGGL((k_bvp_tail<NX, NU>), dim3(n_batch), dim3(512), 0, st, a, level, M, cur, nxt, rcur, rnxt, factor ? 1 : 0);
   for (int l = level - BVP_CHUNK_LEVELS; l >= 0; l -= BVP_CHUNK_LEVELS) {
     const int groups = (Ms[l] + BVP_CHUNK - 1) / BVP_CHUNK;
-    hipLaunchKernelGGL((k_bvp_backchunk<NU>), dim3(groups, n_batch), dim3(128), 0, st, a, l, Ms[l]);
+    hipLaunchKernelGGL((k_bvp_backchunk<NX, NU>), dim3(groups, n_batch), dim3(128), 0, st, a, l, Ms[l]);
   }
   return hipGetLastError();
 }
 
-// Factor (if Phi != null) or re-apply to a new rhs (Phi == null), then solve: delta[12][ldx] (SoA, node-indexed).
-hipError_t launch_bvp_solve(const double* Phi, long ldp, const double* defect, long ldd, int n_nodes, int n_batch,
+// Factor (if Phi != null) or re-apply to a new rhs (Phi == null), then solve: delta[ndim][ldx] (SoA, node-indexed).
+hipError_t launch_bvp_solve(int ndim, const double* Phi, long ldp, const double* defect, long ldd, int n_nodes, int n_batch,
                             int adjoints_only, double* workspace, double* delta, long ldx, hipStream_t st) {
-  return adjoints_only ? bvp_solve_impl<6>(Phi, ldp, defect, ldd, n_nodes, n_batch, workspace, delta, ldx, st)
-                       : bvp_solve_impl<12>(Phi, ldp, defect, ldd, n_nodes, n_batch, workspace, delta, ldx, st);
+  if (ndim == 14)
+    return adjoints_only ? bvp_solve_impl<14, 7>(Phi, ldp, defect, ldd, n_nodes, n_batch, workspace, delta, ldx, st)
+                         : bvp_solve_impl<14, 14>(Phi, ldp, defect, ldd, n_nodes, n_batch, workspace, delta, ldx, st);
+  if (ndim != 12) return hipErrorInvalidValue;
+  return adjoints_only ? bvp_solve_impl<12, 6>(Phi, ldp, defect, ldd, n_nodes, n_batch, workspace, delta, ldx, st)
+                       : bvp_solve_impl<12, 12>(Phi, ldp, defect, ldd, n_nodes, n_batch, workspace, delta, ldx, st);
 }
 
 hipError_t launch_axpy(const double* x, const double* d, double alpha, double* y, long count, hipStream_t st) {

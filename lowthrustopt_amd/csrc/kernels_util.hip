@@ -451,6 +451,22 @@ __global__ void k_end_states(double* X, long ld, int n, int nrow, double* saved,
   if (dir) X[idx] = sv[r]; else sv[r] = X[idx];
 }
 
+// the 14-dim counterpart (the 7 + 7 pinned entries of the variable-mass system): saved [nb][14] = node 0 rows 0-6, node n-1
+// rows 0-5 and 13
+__global__ void k_end_pins14(double* X, long ld, int n, double* saved, int dir) {
+  const int b = blockIdx.x;
+  const int r = threadIdx.x;
+  if (r >= 14) return;
+  const int row = (r < 7) ? r : (r < 13) ? r - 7 : 13;
+  const long idx = (long)row * ld + (long)b * n + (r < 7 ? 0 : n - 1);
+  double* sv = saved + (long)b * 14;
+  if (dir) X[idx] = sv[r];
+  else {
+    if (r == 13) X[idx] = 0.0;               // lambda_m(tf) = 0: transversality of the free final mass
+    sv[r] = X[idx];
+  }
+}
+
 hipError_t launch_trial_points(const double* X, const double* d, long ld, int ndim, int n, int nb, int na, const double* alphas,
                                double* Xt, long ldt, hipStream_t st) {
   const long total = (long)ndim * nb * na * n;
@@ -474,6 +490,12 @@ hipError_t launch_axpy_traj(const double* x, const double* d, const double* alph
 hipError_t launch_end_states(double* X, long ld, int n, int nb, int nrow, double* saved, int restore, hipStream_t st) {
   if (nb <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_end_states, dim3(nb), dim3(64), 0, st, X, ld, n, nrow, saved, restore);
+  return hipGetLastError();
+}
+
+hipError_t launch_end_pins14(double* X, long ld, int n, int nb, double* saved, int restore, hipStream_t st) {
+  if (nb <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_end_pins14, dim3(nb), dim3(64), 0, st, X, ld, n, saved, restore);
   return hipGetLastError();
 }
 

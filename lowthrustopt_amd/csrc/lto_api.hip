@@ -917,7 +917,6 @@ int lto_indirect_newton_solve_dev(lto_indirect_plan* p, void* stream, const doub
                                   long ldd, int adjoints_only, double* delta, long ldx) {
   if (!p) return LTO_ENULL;
   lto_ctx* c = p->ctx;
-  if (p->ndim != 12) return set_err(c, LTO_EUNSUPPORTED, "device Newton solve is built for ndim = 12");
   if (p->out_blocks) return set_err(c, LTO_EUNSUPPORTED, "device Newton solve reads struct-of-arrays Phi / defect: use a plan with LTO_LAYOUT_SOA");
   if (!defect || !delta) return set_err(c, LTO_ENULL, "defect or delta is NULL");
   if (ldd < p->S || (Phi && ldp < p->S) || ldx < (long)p->n_nodes * p->n_batch) return set_err(c, LTO_EINVAL, "leading dimension too small");
@@ -925,13 +924,13 @@ int lto_indirect_newton_solve_dev(lto_indirect_plan* p, void* stream, const doub
   if (rc) return rc;
   if (!p->d_bvp) {
     if (!Phi) return set_err(c, LTO_EINVAL, "no factorisation yet: the first solve needs Phi");
-    p->bvp_bytes = sizeof(double) * bvp_workspace_doubles(p->n_nodes, p->n_batch);
+    p->bvp_bytes = sizeof(double) * bvp_workspace_doubles(p->ndim, p->n_nodes, p->n_batch);
     hipError_t e = pool_alloc(c, (void**)&p->d_bvp, p->bvp_bytes);
     if (e != hipSuccess) { p->d_bvp = nullptr; return set_err(c, LTO_EHIP, "newton workspace", e); }
   }
   const int variant = adjoints_only ? 1 : 0;
   if (!Phi && p->bvp_variant != variant) return set_err(c, LTO_EINVAL, "re-solve requested for a variant that was not factored");
-  hipError_t e = launch_bvp_solve(Phi, ldp, defect, ldd, p->n_nodes, p->n_batch, variant, p->d_bvp, delta, ldx, (hipStream_t)stream);
+  hipError_t e = launch_bvp_solve(p->ndim, Phi, ldp, defect, ldd, p->n_nodes, p->n_batch, variant, p->d_bvp, delta, ldx, (hipStream_t)stream);
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_bvp_solve", e);
   if (Phi) p->bvp_variant = variant;
   return LTO_OK;
@@ -1197,31 +1196,32 @@ int lto_indirect_newton_step(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
                              double soc_threshold, double* xc_update, double* defect) {
   if (!c) return LTO_ENULL;
   if (!XC || !t || !xc_update) return set_err(c, LTO_ENULL, "XC, t or xc_update is NULL");
-  if (ndim != 12) return set_err(c, LTO_EUNSUPPORTED, "device Newton step is built for ndim = 12");
+  if (ndim != 12 && ndim != 14) return set_err(c, LTO_EUNSUPPORTED, "device Newton step is built for ndim = 12 and 14");
   if (n_tgrids != 1 && n_tgrids != n_batch) return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch");
   lto_indirect_plan* p = nullptr;
   int rc = host_plan_acquire(c, ndim, n_nodes, n_batch, prm, n_prm, integ, &p);   // cached between calls, owned by the context
   if (rc) return rc;
+  const int nd = ndim;
   const long J = (long)n_nodes * n_batch, S = p->S;
-  const size_t need = al256(sizeof(double) * 12 * J) * 5 + al256(sizeof(double) * n_nodes * n_tgrids) +
-                      al256(sizeof(double) * 12 * S) * 3 + al256(sizeof(double) * 144 * S) + 16384;
+  const size_t need = al256(sizeof(double) * nd * J) * 5 + al256(sizeof(double) * n_nodes * n_tgrids) +
+                      al256(sizeof(double) * nd * S) * 3 + al256(sizeof(double) * nd * nd * S) + 16384;
   rc = arena_reserve(c, need);
   if (rc) return rc;
   c->arena_top = 0;
-  double* d_aos = arena_take<double>(c, (size_t)12 * J);
-  double* d_X = arena_take<double>(c, (size_t)12 * J);
-  double* d_X2 = arena_take<double>(c, (size_t)12 * J);
-  double* d_del = arena_take<double>(c, (size_t)12 * J);
-  double* d_del2 = arena_take<double>(c, (size_t)12 * J);
+  double* d_aos = arena_take<double>(c, (size_t)nd * J);
+  double* d_X = arena_take<double>(c, (size_t)nd * J);
+  double* d_X2 = arena_take<double>(c, (size_t)nd * J);
+  double* d_del = arena_take<double>(c, (size_t)nd * J);
+  double* d_del2 = arena_take<double>(c, (size_t)nd * J);
   double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
-  double* d_def = arena_take<double>(c, (size_t)12 * S);
-  double* d_def2 = arena_take<double>(c, (size_t)12 * S);
-  double* d_def_aos = arena_take<double>(c, (size_t)12 * S);
-  double* d_phi = arena_take<double>(c, (size_t)144 * S);
+  double* d_def = arena_take<double>(c, (size_t)nd * S);
+  double* d_def2 = arena_take<double>(c, (size_t)nd * S);
+  double* d_def_aos = arena_take<double>(c, (size_t)nd * S);
+  double* d_phi = arena_take<double>(c, (size_t)nd * nd * S);
   hipStream_t st = c->stream;
-  hipError_t e = hipMemcpyAsync(d_aos, XC, sizeof(double) * 12 * J, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(d_aos, XC, sizeof(double) * nd * J, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n_nodes * n_tgrids, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_pack_soa(d_aos, 12, J, d_X, J, st);
+  if (e == hipSuccess) e = launch_pack_soa(d_aos, nd, J, d_X, J, st);
   if (e != hipSuccess) { (void)hipStreamSynchronize(st); return set_err(c, LTO_EHIP, "stage in", e); }
   host_order_adopt(c, p, true);
   rc = lto_indirect_jacobian_dev(p, st, d_X, J, d_t, n_tgrids, d_phi, S, d_def, S);
@@ -1229,35 +1229,35 @@ int lto_indirect_newton_step(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
   if (rc == LTO_OK) rc = lto_indirect_newton_solve_dev(p, st, d_phi, S, d_def, S, flag_adjointsOnly, d_del, J);
   double* h_del = nullptr;
   if (rc == LTO_OK) {
-    h_del = (double*)std::malloc(sizeof(double) * 12 * (size_t)J);
+    h_del = (double*)std::malloc(sizeof(double) * nd * (size_t)J);
     if (!h_del) rc = set_err(c, LTO_EHIP, "host allocation failed");
   }
   if (rc == LTO_OK) {
-    e = hipMemcpyAsync(h_del, d_del, sizeof(double) * 12 * J, hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(h_del, d_del, sizeof(double) * nd * J, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "newton step", e);
   }
   if (rc == LTO_OK) {
     double mx = 0.0;
     bool finite = true;
-    for (long k = 0; k < 12 * J; ++k) { const double v = std::fabs(h_del[k]); if (!(v == v)) finite = false; if (v > mx) mx = v; }
+    for (long k = 0; k < nd * J; ++k) { const double v = std::fabs(h_del[k]); if (!(v == v)) finite = false; if (v > mx) mx = v; }
     if (finite && mx < soc_threshold) {   // :190  norm(xc_update, Inf) < 1e-1
-      e = launch_axpy(d_X, d_del, 1.0, d_X2, 12 * J, st);
+      e = launch_axpy(d_X, d_del, 1.0, d_X2, nd * J, st);
       if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "axpy", e);
       if (rc == LTO_OK) rc = lto_indirect_defect_dev(p, st, d_X2, J, d_t, n_tgrids, d_def2, S, nullptr);
       if (rc == LTO_OK) rc = lto_indirect_newton_solve_dev(p, st, nullptr, 0, d_def2, S, flag_adjointsOnly, d_del2, J);
       if (rc == LTO_OK) {
-        e = launch_axpy(d_del, d_del2, 1.0, d_del, 12 * J, st);
+        e = launch_axpy(d_del, d_del2, 1.0, d_del, nd * J, st);
         if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "axpy", e);
       }
     }
   }
   if (rc == LTO_OK) {
-    e = launch_unpack_soa(d_del, J, 12, J, d_aos, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(xc_update, d_aos, sizeof(double) * 12 * J, hipMemcpyDeviceToHost, st);
+    e = launch_unpack_soa(d_del, J, nd, J, d_aos, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(xc_update, d_aos, sizeof(double) * nd * J, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && defect) {
-      e = launch_unpack_soa(d_def, S, 12, S, d_def_aos, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(defect, d_def_aos, sizeof(double) * 12 * S, hipMemcpyDeviceToHost, st);
+      e = launch_unpack_soa(d_def, S, nd, S, d_def_aos, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(defect, d_def_aos, sizeof(double) * nd * S, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
@@ -1280,7 +1280,7 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
                              double* XC_out, double* defect, int* status_flag, int* iterations, double* history) {
   if (!c) return LTO_ENULL;
   if (!XC_in || !t || !prm || !integ || !XC_out || !status_flag) return set_err(c, LTO_ENULL, "XC_in, t, prm, integ, XC_out or status_flag is NULL");
-  if (ndim != 12) return set_err(c, LTO_EUNSUPPORTED, "the device Newton loop is built for ndim = 12");
+  if (ndim != 12 && ndim != 14) return set_err(c, LTO_EUNSUPPORTED, "the device Newton loop is built for ndim = 12 and 14");
   if (maxIter < 0) return set_err(c, LTO_EINVAL, "maxIter must be >= 0");
   if (n_batch < 1 || n_nodes < 2) return set_err(c, LTO_EINVAL, "need n_nodes >= 2 and n_batch >= 1");
   if ((n_tgrids != 1 && n_tgrids != n_batch) || (n_prm != 1 && n_prm != n_batch)) return set_err(c, LTO_EINVAL, "n_tgrids / n_prm must be 1 or n_batch");
@@ -1301,36 +1301,37 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
   }
   lto_indirect_plan* p = nullptr;
   lto_indirect_plan* pl = nullptr;
-  int rc = plan_build(c, 12, n_nodes, B, prm, n_prm, integ, &p);
+  const int nd = ndim;                                     // 12: state + costate; 14: + mass and mass costate
+  int rc = plan_build(c, nd, n_nodes, B, prm, n_prm, integ, &p);
   if (rc) return rc;
-  rc = plan_build(c, 12, n_nodes, B * NA, n_prm == 1 ? prm : prm_l.data(), n_prm == 1 ? 1 : B * NA, integ, &pl);
+  rc = plan_build(c, nd, n_nodes, B * NA, n_prm == 1 ? prm : prm_l.data(), n_prm == 1 ? 1 : B * NA, integ, &pl);
   if (rc) { plan_free(p); return rc; }
   const long n = n_nodes, J = n * B, S = (n - 1) * B;
   const int ntl = (n_tgrids == 1) ? 1 : B * NA;
-  const size_t n_small = (size_t)12 * B + NA + 6 * (size_t)B + 2 * (size_t)NA * B + 64;
-  const size_t need = al256(sizeof(double) * 12 * J) * 5 + al256(sizeof(double) * 12 * J * NA) + al256(sizeof(double) * n * n_tgrids) +
-                      al256(sizeof(double) * n * ntl) + al256(sizeof(double) * 12 * S) * 4 + al256(sizeof(double) * 12 * S * NA) +
-                      al256(sizeof(double) * 144 * S) + al256(sizeof(double) * n_small) + 65536;
+  const size_t n_small = (size_t)nd * B + NA + 6 * (size_t)B + 2 * (size_t)NA * B + 64;
+  const size_t need = al256(sizeof(double) * nd * J) * 5 + al256(sizeof(double) * nd * J * NA) + al256(sizeof(double) * n * n_tgrids) +
+                      al256(sizeof(double) * n * ntl) + al256(sizeof(double) * nd * S) * 4 + al256(sizeof(double) * nd * S * NA) +
+                      al256(sizeof(double) * nd * nd * S) + al256(sizeof(double) * n_small) + 65536;
   rc = arena_reserve(c, need);
   if (rc) { plan_free(pl); plan_free(p); return rc; }
   c->arena_top = 0;
-  double* d_aos = arena_take<double>(c, (size_t)12 * J);
-  double* d_X = arena_take<double>(c, (size_t)12 * J);
-  double* d_X2 = arena_take<double>(c, (size_t)12 * J);
-  double* d_del = arena_take<double>(c, (size_t)12 * J);
-  double* d_del2 = arena_take<double>(c, (size_t)12 * J);
-  double* d_Xt = arena_take<double>(c, (size_t)12 * J * NA);
+  double* d_aos = arena_take<double>(c, (size_t)nd * J);
+  double* d_X = arena_take<double>(c, (size_t)nd * J);
+  double* d_X2 = arena_take<double>(c, (size_t)nd * J);
+  double* d_del = arena_take<double>(c, (size_t)nd * J);
+  double* d_del2 = arena_take<double>(c, (size_t)nd * J);
+  double* d_Xt = arena_take<double>(c, (size_t)nd * J * NA);
   double* d_t = arena_take<double>(c, (size_t)n * n_tgrids);
   double* d_tl = (n_tgrids == 1) ? d_t : arena_take<double>(c, (size_t)n * ntl);
-  double* d_def = arena_take<double>(c, (size_t)12 * S);
-  double* d_def2 = arena_take<double>(c, (size_t)12 * S);
-  double* d_defj = arena_take<double>(c, (size_t)12 * S);   // the STM sweep's own defect (right-hand side of the step); d_def stays defectCalc's
-  double* d_def_aos = arena_take<double>(c, (size_t)12 * S);
-  double* d_deft = arena_take<double>(c, (size_t)12 * S * NA);
-  double* d_phi = arena_take<double>(c, (size_t)144 * S);
+  double* d_def = arena_take<double>(c, (size_t)nd * S);
+  double* d_def2 = arena_take<double>(c, (size_t)nd * S);
+  double* d_defj = arena_take<double>(c, (size_t)nd * S);   // the STM sweep's own defect (right-hand side of the step); d_def stays defectCalc's
+  double* d_def_aos = arena_take<double>(c, (size_t)nd * S);
+  double* d_deft = arena_take<double>(c, (size_t)nd * S * NA);
+  double* d_phi = arena_take<double>(c, (size_t)nd * nd * S);
   double* d_small = arena_take<double>(c, n_small);
-  double* d_saved = d_small;                               // [B][12] pinned end states
-  double* d_alphas = d_saved + (size_t)12 * B;             // [NA]   trial step lengths
+  double* d_saved = d_small;                               // [B][nd] pinned end states (12: 6 + 6, 14: 7 + 7)
+  double* d_alphas = d_saved + (size_t)nd * B;             // [NA]   trial step lengths
   double* d_step = d_alphas + NA;                          // [B]    step length / SOC mask per trajectory
   double* d_mx = d_step + B;                               // [B]    per-trajectory max norms
   double* d_ss = d_mx + B;                                 // [NA*B] per-trial sums of squares
@@ -1353,17 +1354,18 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
     return set_err(c, LTO_ENOMEM, "lto_indirect_solve_batch: out of host memory");
   }
 
-  hipError_t e = hipMemcpyAsync(d_aos, XC_in, sizeof(double) * 12 * J, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(d_aos, XC_in, sizeof(double) * nd * J, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n * n_tgrids, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && n_tgrids != 1) e = hipMemcpyAsync(d_tl, t_l.data(), sizeof(double) * n * ntl, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_alphas, alphas, sizeof alphas, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_pack_soa(d_aos, 12, J, d_X, J, st);
-  if (e == hipSuccess) e = launch_end_states(d_X, J, n_nodes, B, 6, d_saved, 0, st);           // state_0, state_f  (:270-271)
+  if (e == hipSuccess) e = launch_pack_soa(d_aos, nd, J, d_X, J, st);
+  // state_0, state_f  (:270-271); 14-dim: also m0, and lambda_m(tf) set to 0 (free final mass)
+  if (e == hipSuccess) e = (nd == 12) ? launch_end_states(d_X, J, n_nodes, B, 6, d_saved, 0, st) : launch_end_pins14(d_X, J, n_nodes, B, d_saved, 0, st);
   if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage in", e);
 
   // per-trajectory max |v| of an SoA block [rows][ld], `per` columns per trajectory -> host (NaN-propagating)
   auto max_abs = [&](const double* v, long ld, long per, double* out) -> int {
-    hipError_t q = launch_defect_norms(v, ld, 12, (int)per, B, nullptr, d_mx, st);
+    hipError_t q = launch_defect_norms(v, ld, nd, (int)per, B, nullptr, d_mx, st);
     if (q == hipSuccess) q = hipMemcpyAsync(out, d_mx, sizeof(double) * B, hipMemcpyDeviceToHost, st);
     if (q == hipSuccess) q = hipStreamSynchronize(st);
     return q == hipSuccess ? LTO_OK : set_err(c, LTO_EHIP, "norm", q);
@@ -1399,7 +1401,7 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
     if (rc == LTO_OK && host_order_wanted(p, true)) rc = lto_indirect_plan_rebalance(p, st);
     if (rc == LTO_OK) rc = lto_indirect_newton_solve_dev(p, st, d_phi, S, d_defj, S, flag_adjointsOnly, d_del, J);  // :182
     if (rc != LTO_OK) break;
-    e = launch_defect_norms(d_del, J, 12, (int)n, B, nullptr, d_mxdel, st);                          // max |xc_update| per trajectory
+    e = launch_defect_norms(d_del, J, nd, (int)n, B, nullptr, d_mxdel, st);                          // max |xc_update| per trajectory
     if (e == hipSuccess) e = launch_soc_mask(d_mxdel, d_act, 1e-1, d_step, B, st);                   // second-order correction, :190-214
     if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "soc mask", e); break; }
     bool soc = true;
@@ -1410,40 +1412,41 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
       for (int b = 0; b < B; ++b) soc |= (active[b] && h_mx[b] == h_mx[b] && h_mx[b] < 1e-1);
     }
     if (soc) {
-      e = launch_axpy(d_X, d_del, 1.0, d_X2, 12 * J, st);
+      e = launch_axpy(d_X, d_del, 1.0, d_X2, nd * J, st);
       if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "axpy", e); break; }
       rc = lto_indirect_defect_dev(p, st, d_X2, J, d_t, n_tgrids, d_def2, S, nullptr);
       if (rc == LTO_OK) rc = lto_indirect_newton_solve_dev(p, st, nullptr, 0, d_def2, S, flag_adjointsOnly, d_del2, J);
       if (rc != LTO_OK) break;
-      e = launch_axpy_traj(d_del, d_del2, d_step, d_del, J, 12, n_nodes, B, st);                      // masked: step = 0 keeps d_del
+      e = launch_axpy_traj(d_del, d_del2, d_step, d_del, J, nd, n_nodes, B, st);                      // masked: step = 0 keeps d_del
       if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "axpy", e); break; }
     }
     bool search = false, all_search = true;
     for (int b = 0; b < B; ++b) if (active[b]) { search |= it[b] > 3; all_search &= it[b] > 3; }
     if (search) {                                          // :300-302: the 20 trial trajectories of every problem, one sweep
-      e = launch_trial_points(d_X, d_del, J, 12, n_nodes, B, NA, d_alphas, d_Xt, J * NA, st);
+      e = launch_trial_points(d_X, d_del, J, nd, n_nodes, B, NA, d_alphas, d_Xt, J * NA, st);
       if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "trial points", e); break; }
       rc = lto_indirect_defect_dev(pl, st, d_Xt, J * NA, d_tl, ntl, d_deft, S * NA, nullptr);
       // the next trial sweeps run with the lanes ordered by this one's step counts; near convergence the counts hardly move, so the
       // order (always a valid permutation, whatever its age) is renewed every fourth sweep only
       if (rc == LTO_OK && host_order_wanted(pl, false) && (trial_sweeps++ & 3) == 0) rc = lto_indirect_plan_rebalance(pl, st);
       if (rc != LTO_OK) break;
-      e = launch_defect_norms(d_deft, S * NA, 12, n_nodes - 1, B * NA, d_ss, d_mxt, st);           // sum(defect.^2), :240 (+ max |defect|)
+      e = launch_defect_norms(d_deft, S * NA, nd, n_nodes - 1, B * NA, d_ss, d_mxt, st);           // sum(defect.^2), :240 (+ max |defect|)
       if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "line search", e); break; }
     }
     // alpha (:244-245), 1, or 0 (frozen).  When every active trajectory searched, the same launch takes the chosen trial's max
     // |defect| and defect block: CHECK UPDATE (:328-331) without a sweep -- the new XC_all is the chosen trial point bit for bit
     // (same fma, the update's end-state rows are zero), so defectCalc there is the lanes of the line search's sweep that integrated it.
     const bool reuse = search && all_search;
-    e = reuse ? launch_take_trial(d_deft, S * NA, d_ss, d_act, d_search, NA, n_nodes - 1, 12, B, d_def, S, d_alphas, d_step, d_mxt, d_mx, st)
+    e = reuse ? launch_take_trial(d_deft, S * NA, d_ss, d_act, d_search, NA, n_nodes - 1, nd, B, d_def, S, d_alphas, d_step, d_mxt, d_mx, st)
               : launch_pick_alpha(d_ss, d_alphas, NA, d_act, d_search, d_step, B, nullptr, nullptr, st);
-    if (e == hipSuccess) e = launch_axpy_traj(d_X, d_del, d_step, d_X, J, 12, n_nodes, B, st);      // :304
-    if (e == hipSuccess) e = launch_end_states(d_X, J, n_nodes, B, 6, d_saved, 1, st);             // :324-325
+    if (e == hipSuccess) e = launch_axpy_traj(d_X, d_del, d_step, d_X, J, nd, n_nodes, B, st);      // :304
+    if (e == hipSuccess) e = (nd == 12) ? launch_end_states(d_X, J, n_nodes, B, 6, d_saved, 1, st)     // :324-325
+                                        : launch_end_pins14(d_X, J, n_nodes, B, d_saved, 1, st);
     if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "update", e); break; }
     if (!reuse) {
       rc = lto_indirect_defect_dev(p, st, d_X, J, d_t, n_tgrids, d_def, S, nullptr);               // :328
       if (rc != LTO_OK) break;
-      e = launch_defect_norms(d_def, S, 12, (int)(n - 1), B, nullptr, d_mx, st);                     // :331
+      e = launch_defect_norms(d_def, S, nd, (int)(n - 1), B, nullptr, d_mx, st);                     // :331
       if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "norm", e); break; }
     }
     // one read-back: [step | max |defect|] are adjacent in the small block, max |xc_update| follows the flags
@@ -1466,11 +1469,11 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
     }
   }
   if (rc == LTO_OK) {
-    e = launch_unpack_soa(d_X, J, 12, J, d_aos, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(XC_out, d_aos, sizeof(double) * 12 * J, hipMemcpyDeviceToHost, st);
+    e = launch_unpack_soa(d_X, J, nd, J, d_aos, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(XC_out, d_aos, sizeof(double) * nd * J, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && defect) {
-      e = launch_unpack_soa(d_def, S, 12, S, d_def_aos, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(defect, d_def_aos, sizeof(double) * 12 * S, hipMemcpyDeviceToHost, st);
+      e = launch_unpack_soa(d_def, S, nd, S, d_def_aos, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(defect, d_def_aos, sizeof(double) * nd * S, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess) e = max_abs(d_def, S, n - 1, h_mx.data()) == LTO_OK ? hipSuccess : hipErrorUnknown;
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
@@ -1478,7 +1481,7 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
     // report status 2 here, as drivers.multiShoot_CRTBP_indirect does
     if (rc == LTO_OK)
       for (int b = 0; b < B; ++b)
-        if (XC_out[(size_t)12 * n * b] != XC_out[(size_t)12 * n * b] || h_mx[b] != h_mx[b]) status[b] = 2;
+        if (XC_out[(size_t)nd * n * b] != XC_out[(size_t)nd * n * b] || h_mx[b] != h_mx[b]) status[b] = 2;
   } else {
     (void)hipStreamSynchronize(st);
   }

@@ -8,6 +8,9 @@
   lineSearch_direct           src/multiShoot_CRTBP_direct.jl:405-430   (10 alphas in ONE batched launch -- SURVEY N2)
   homotopy_solve              concurrent form of the rho continuation (HelperFunctions.jl:105-193): every level of the
                               ladder is a trajectory of ONE batched device Newton loop (lto_indirect_solve_batch)
+  multiShoot_CRTBP_indirect_mass / optimizeTraj_OLS_mass / reduceFuel_indirect_mass / lift_to_mass
+                              the same loop on the 14-dim variable-mass system (free final mass, lambda_m(tf) = 0):
+                              what the reference's `nstate == 7` branches (:158-161, :195-199) were meant to solve
   controlLaw_cart             src/multiShoot_CRTBP_indirect.jl:389-440 (costates -> thrust vectors in N: the u_all format
                                                                         of the direct transcription; host post-processing)
 
@@ -113,11 +116,11 @@ def multiShoot_CRTBP_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass0, thrustLi
     """Indirect multiple shooting with fixed end states (indirect.jl:58-61, :254-345).
     Returns (XC_all, defect, status_flag): 0 converged, 1 maxIter reached, 2 NaN.
     The driver is the reference's: 12 rows (state + costate, constant mass `mass0`).  The 14-dim extension (mass and mass
-    costate as states, Isp in the parameter tuple's mass slot) exists for the sweeps only (indirect_defectCalc /
-    indirect_stm with ndim = 14) -- the reference's loop pins XC_all[1:6] and solves 12x12 blocks (indirect.jl:324-325)."""
+    costate as states, Isp in the parameter tuple's mass slot) is solved by multiShoot_CRTBP_indirect_mass -- the reference's
+    loop pins XC_all[1:6] and solves 12x12 blocks (indirect.jl:324-325)."""
     if np.asarray(XC_all).shape[0] != 12:
         raise ValueError("multiShoot_CRTBP_indirect drives the reference's 12-row state+costate system; got %d rows "
-                         "(the 14-dim extension is available through indirect_defectCalc / indirect_stm only)" % np.asarray(XC_all).shape[0])
+                         "(the 14-row variable-mass system is solved by multiShoot_CRTBP_indirect_mass)" % np.asarray(XC_all).shape[0])
     if ops is None:
         # product default: the whole loop below is one library call with the trajectory resident on the device
         # (lto_indirect_solve); the Python loop remains for injected back ends
@@ -179,16 +182,18 @@ def reduceFuel_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass, thrustLimit, rh
                         verbose=True, rng=None):
     """rho continuation (HelperFunctions.jl:105-193): halve rho on success, back off on failure.
     status_flag 3 = continuation exhausted (:161)."""
+    def run(X, rho):
+        return multiShoot_CRTBP_indirect(X, t_TU, MU, DU, TU, n_nodes, mass, thrustLimit, False, False, 10, 1.0, rho,
+                                         ops=ops, verbose=verbose)
+    return _rho_continuation(run, XC_all, rho_current, rho_target, rng)
+
+
+def _rho_continuation(run, XC_all, rho_current, rho_target, rng=None):
+    """The continuation loop of reduceFuel_indirect (HelperFunctions.jl:105-193); run(X, rho) -> (XC, defect, status)."""
     rng = rng or np.random.default_rng(0)
     if rho_target > rho_current:
         rho_target = rho_current
-    p = 1.0
     rho_temp = rho_current
-    maxIter = 10
-
-    def run(X, rho):
-        return multiShoot_CRTBP_indirect(X, t_TU, MU, DU, TU, n_nodes, mass, thrustLimit, False, False, maxIter, p, rho,
-                                         ops=ops, verbose=verbose)
 
     XC_new, defect, status = run(XC_all, rho_temp)
     if status == 0 and rho_current == rho_target:
@@ -212,6 +217,132 @@ def reduceFuel_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass, thrustLimit, rh
             rho_temp *= 3 * (1 + rng.random())
         XC_new, defect, status = run(XC_all, rho_temp)
     return XC_new, defect, status
+
+
+def lift_to_mass(XC12, mass0):
+    """12 rows (r, v, lambda_r, lambda_v) -> the 14 rows of the variable-mass system (r, v, m, lambda_r, lambda_v, lambda_m)
+    with m = mass0 and lambda_m = 0 at every node.  [12 x n] or [12 x n x B]."""
+    X = np.asarray(XC12, dtype=np.float64)
+    if X.shape[0] != 12:
+        raise ValueError("lift_to_mass takes 12 rows; got %d" % X.shape[0])
+    out = np.zeros((14,) + X.shape[1:], order="F")
+    out[0:6] = X[0:6]
+    out[6] = mass0
+    out[7:13] = X[6:12]
+    return out
+
+
+def _mass_free_columns(n_nodes, flag_adjointsOnly):
+    """Unknowns of the 14-dim step: every column of Jac_full except the pinned ones (first node 0:7, last node 0:6 and 13);
+    adjoints-only also drops the 7 state columns (r, v, m) of every node."""
+    nd = 14
+    free = np.ones(nd * n_nodes, dtype=bool)
+    free[0:7] = False
+    last = nd * (n_nodes - 1)
+    free[last:last + 6] = False
+    free[last + 13] = False
+    if flag_adjointsOnly:
+        for k in range(n_nodes):
+            free[k * nd:k * nd + 7] = False
+    return free
+
+
+def optimizeTraj_OLS_mass(XC_all, t_TU, defect, Phi, n_nodes, params, flag_adjointsOnly, ops):
+    """The least-squares Newton step of the 14-dim variable-mass system, with the second-order correction of
+    optimizeTraj_OLS (indirect.jl:149-218): Jac_full from indirect_scatter_mass, the pinned columns (and, adjoints-only, the
+    state columns of every node) removed, x = -J \\ defect.  Square for the regular step, least squares for adjoints-only.
+    The pinned entries of the update are exactly 0."""
+    nd = 14
+    defect_vec = np.asarray(defect).reshape(-1, order="F")
+    J = hotpath.indirect_scatter_mass(np.asarray(Phi), sparse=True)
+    free = _mass_free_columns(n_nodes, flag_adjointsOnly)
+    Jm = J[:, np.flatnonzero(free)]
+    upd = np.zeros(nd * n_nodes)
+    upd[free] = _solve_ls(Jm, defect_vec)
+    xc_update = upd.reshape(nd, n_nodes, order="F")
+    if np.abs(xc_update).max() < 1e-1:                      # :190  SOC: same Jacobian, defect at the trial point
+        d_soc = ops.defect(XC_all + xc_update, t_TU, params)
+        upd2 = np.zeros(nd * n_nodes)
+        upd2[free] = _solve_ls(Jm, np.asarray(d_soc).reshape(-1, order="F"))
+        xc_update = xc_update + upd2.reshape(nd, n_nodes, order="F")
+    return xc_update
+
+
+def multiShoot_CRTBP_indirect_mass(XC_all, t_TU, MU, DU, TU, n_nodes, Isp, thrustLimit, plot_yn, flag_adjointsOnly,
+                                   maxIter, p, rho, ops=None, verbose=True):
+    """Indirect multiple shooting of the 14-dim variable-mass system y = (r, v, m, lambda_r, lambda_v, lambda_m), free final
+    mass.  Pinned in every iteration: XC_all[0:7, 0] (r0, v0, m0 = XC_all[6, 0]) and XC_all[0:6, -1] (rf, vf); on entry
+    XC_all[13, -1] = lambda_m(tf) is set to 0, the transversality condition of the free final mass.  Otherwise the reference
+    loop of multiShoot_CRTBP_indirect: stop at max|defect| <= 1e-10, second-order correction, the 20-point line search from
+    iteration 4, status flags 0 / 1 / 2.  ops=None: one lto_indirect_solve call (ndim = 14, Isp in the parameter tuple's mass
+    slot); an injected `ops` runs the Python mirror with the host step optimizeTraj_OLS_mass.
+    Returns (XC_all, defect, status_flag)."""
+    XC_all = np.array(XC_all, dtype=np.float64, order="F")
+    if XC_all.ndim != 2 or XC_all.shape[0] != 14:
+        raise ValueError("multiShoot_CRTBP_indirect_mass takes the 14-row variable-mass system; got shape %s "
+                         "(lift_to_mass(XC12, mass0) builds it from 12 rows)" % (XC_all.shape,))
+    if not (Isp > 0):
+        raise ValueError("Isp must be positive; got %r" % (Isp,))
+    if not (XC_all[6, 0] > 0):
+        raise ValueError("the initial mass XC_all[6, 0] must be positive; got %r" % (XC_all[6, 0],))
+    params = hotpath.make_params(MU, DU, TU, thrustLimit, Isp, 1.0, p, rho)   # mass slot = Isp for 14 rows
+    if ops is None:
+        XC_out, defect, status_flag, iterCount, hist = hotpath.indirect_solve(XC_all, t_TU, params, None, flag_adjointsOnly, maxIter)
+        if verbose:
+            for k, (er, alpha) in enumerate(hist):
+                print("Iter %d. Max defect = %.2e. alpha = %.3f." % (k + 1, er, alpha))
+                if not (er <= 1e3):
+                    print("Not likely to converge. Aborting.")
+            if status_flag == 1:
+                print("Reached max iteration count at %d iterations" % iterCount)
+        return XC_out, defect, status_flag
+    t_TU = np.array(t_TU, dtype=np.float64)
+    XC_all[13, -1] = 0.0
+    state_0 = XC_all[:7, 0].copy()
+    state_f = XC_all[:6, -1].copy()
+    status_flag = 0
+    defect = ops.defect(XC_all, t_TU, params)
+    iterCount = 0
+    er = 1.0
+    while er > 1e-10:
+        iterCount += 1
+        if iterCount > maxIter:
+            if verbose:
+                print("Reached max iteration count at %d iterations" % iterCount)
+            status_flag = 1
+            break
+        Phi, _ = ops.stm(XC_all, t_TU, params)
+        xc_update = optimizeTraj_OLS_mass(XC_all, t_TU, defect, Phi, n_nodes, params, flag_adjointsOnly, ops)
+        alpha = 1.0
+        if iterCount > 3:
+            alpha = lineSearch(XC_all, xc_update, t_TU, params, ops)
+        XC_all = XC_all + xc_update * alpha
+        XC_all[:7, 0] = state_0
+        XC_all[:6, -1] = state_f
+        XC_all[13, -1] = 0.0
+        defect = ops.defect(XC_all, t_TU, params)
+        er = float(np.max(np.abs(defect))) if np.all(np.isfinite(defect)) else float("nan")
+        if verbose:
+            print("Iter %d. Max defect = %.2e. alpha = %.3f." % (iterCount, er, alpha))
+        if not (er <= 1e3):
+            if verbose:
+                print("Not likely to converge. Aborting.")
+            iterCount += 100
+            if er != er:
+                break
+    if np.isnan(XC_all[0, 0]) or not np.all(np.isfinite(defect)):
+        status_flag = 2
+    return XC_all, defect, status_flag
+
+
+def reduceFuel_indirect_mass(XC_all, t_TU, MU, DU, TU, n_nodes, Isp, thrustLimit, rho_current, rho_target, ops=None,
+                             verbose=True, rng=None):
+    """The rho continuation of reduceFuel_indirect (HelperFunctions.jl:105-193) on the 14-dim variable-mass system: p = 1,
+    10 iterations per level, halve rho on success, back off on failure; status_flag 3 = continuation exhausted."""
+    def run(X, rho):
+        return multiShoot_CRTBP_indirect_mass(X, t_TU, MU, DU, TU, n_nodes, Isp, thrustLimit, False, False, 10, 1.0, rho,
+                                              ops=ops, verbose=verbose)
+    return _rho_continuation(run, XC_all, rho_current, rho_target, rng)
 
 
 def homotopy_defect_sweep(XC_levels, t_TU, MU, DU, TU, mass, thrustLimit, rhos, ops=None):

@@ -472,6 +472,36 @@ def indirect_scatter(Phi, sparse=False):
     return J
 
 
+def indirect_scatter_mass(Phi, sparse=False):
+    """Jac_full of the 14-dim variable-mass system: row block i = [Phi_i | -I] at columns 14 i + (0:28) (0-based), as for
+    12 rows, with the pinned columns zeroed -- the first node's r0, v0, m0 (columns 0:7) and the last node's rf, vf and
+    lambda_m(tf) (columns 14(n-1) + 0:6 and 14(n-1) + 13).  The final mass, column 14(n-1) + 6, is free."""
+    nd, _, S = Phi.shape
+    if nd != 14:
+        raise ValueError("indirect_scatter_mass takes 14 x 14 blocks; got %d rows" % nd)
+    n = S + 1
+    last = nd * (n - 1)
+    pinned = np.r_[np.arange(7), last + np.arange(6), last + 13]
+    if sparse:
+        import scipy.sparse as sp
+        rows = (np.arange(S)[:, None, None] * nd + np.arange(nd)[None, :, None] + np.zeros((1, 1, nd), int)).ravel()
+        cols = (np.arange(S)[:, None, None] * nd + np.zeros((1, nd, 1), int) + np.arange(nd)[None, None, :]).ravel()
+        vals = np.transpose(Phi, (2, 0, 1)).ravel()
+        ir = (np.arange(S)[:, None] * nd + np.arange(nd)[None, :]).ravel()
+        ic = ir + nd
+        J = sp.coo_matrix((np.concatenate([vals, -np.ones(S * nd)]),
+                           (np.concatenate([rows, ir]), np.concatenate([cols, ic]))), shape=(nd * S, nd * n)).tocsc()
+        keep = np.ones(nd * n)
+        keep[pinned] = 0.0
+        return (J @ sp.diags(keep)).tocsc()
+    J = np.zeros((nd * S, nd * n))
+    for i in range(S):
+        J[nd * i:nd * (i + 1), nd * i:nd * (i + 1)] = Phi[:, :, i]
+        J[nd * i:nd * (i + 1), nd * (i + 1):nd * (i + 2)] = -np.eye(nd)
+    J[:, pinned] = 0.0
+    return J
+
+
 def indirect_jacobianCalc(XC_all, t_TU, params, integ=None, ctx=None, sparse=False):
     """jacobianCalc of multiShoot_CRTBP_indirect (:93-146): Jac_full [12(n-1) x 12n]."""
     Phi, _ = indirect_stm(XC_all, t_TU, params, integ, ctx)
@@ -517,7 +547,7 @@ def indirect_solve(XC_all, t_TU, params, integ=None, flag_adjointsOnly=False, ma
 
 
 def indirect_solve_batch(XC_all, t_TU, params, integ=None, flag_adjointsOnly=False, maxIter=10, ctx=None):
-    """n_batch independent Newton loops side by side (lto_indirect_solve_batch): XC_all [12 x n x B], t_TU [n] or
+    """n_batch independent Newton loops side by side (lto_indirect_solve_batch): XC_all [ndim x n x B] (12 or 14 rows), t_TU [n] or
     [n x B], params one tuple or B.  Returns (XC_all, defect, status_flag[B], iterCount[B], history) with
     history[b] = array of (max|defect|, alpha) per completed iteration of trajectory b."""
     ctx = ctx or default_context()

@@ -1,0 +1,180 @@
+"""The 14-dim variable-mass indirect solve on the host: the least-squares step optimizeTraj_OLS_mass against dense linear
+algebra on the CPU oracle's STMs, the Python mirror loop of multiShoot_CRTBP_indirect_mass on an exactly consistent problem,
+and the argument checks of the new entry points.  Rows: (r, v, m, lambda_r, lambda_v, lambda_m); pinned every iteration:
+XC[0:7, 0], XC[0:6, -1] and XC[13, -1] = 0 (free final mass)."""
+import numpy as np
+import pytest
+
+from lowthrustopt_amd import drivers, hotpath, synth
+from lowthrustopt_amd.constants import MU, DU, TU
+
+STEPS = 24
+THR, ISP = 0.05, 2000.0
+
+
+def prm_list(params):
+    return [params.MU, params.DU, params.TU, params.thrustLimit, params.mass, params.time_direction, params.p, params.rho]
+
+
+class OracleOps14:
+    """The 14-dim sweeps of the CPU oracle (fixed-step RK4) behind the `ops` interface of the drivers."""
+
+    def __init__(self, O):
+        self.O = O
+
+    def defect(self, XC, t, params):
+        _, d, rc = self.O.indirect14(XC, t, prm_list(params), self.O.RK4, STEPS, want_stm=False)
+        assert rc == 0
+        return d
+
+    def stm(self, XC, t, params):
+        Phi, d, rc = self.O.indirect14(XC, t, prm_list(params), self.O.RK4, STEPS)
+        assert rc == 0
+        return Phi, d
+
+    def defect_batch_sumsq(self, XC_batch, t, params):
+        return np.array([np.sum(self.defect(np.asfortranarray(XC_batch[:, :, b]), t, params) ** 2) for b in range(XC_batch.shape[2])])
+
+
+def guess14(n, seed=1, lam=0.1):
+    XC, T = synth.indirect_problem(n, seed=seed, lam_sigma=lam)
+    X14 = drivers.lift_to_mass(XC[:, :, 0], 1000.0)
+    X14[6] = 1000.0 - 0.01 * np.arange(n)
+    X14[13] = 0.2
+    X14[13, -1] = 0.0
+    return X14, T[:, 0]
+
+
+def pinned_mask(n):
+    m = np.zeros((14, n), dtype=bool)
+    m[0:7, 0] = True
+    m[0:6, -1] = True
+    m[13, -1] = True
+    return m
+
+
+def dense_step(Phi, defect, adjoints_only):
+    n = Phi.shape[2] + 1
+    J = hotpath.indirect_scatter_mass(Phi)
+    free = ~pinned_mask(n).reshape(-1, order="F")
+    if adjoints_only:
+        st = np.zeros((14, n), dtype=bool)
+        st[0:7] = True
+        free &= ~st.reshape(-1, order="F")
+    Jf = J[:, free]
+    rhs = -defect.reshape(-1, order="F")
+    x = np.zeros(14 * n)
+    if Jf.shape[0] == Jf.shape[1]:
+        assert np.linalg.matrix_rank(Jf) == Jf.shape[1]
+        x[free] = np.linalg.solve(Jf, rhs)
+    else:
+        x[free] = np.linalg.lstsq(Jf, rhs, rcond=None)[0]
+    return x.reshape(14, n, order="F")
+
+
+def with_soc(X, t, params, ops, Phi, defect, adjoints_only):
+    upd = dense_step(Phi, defect, adjoints_only)
+    if np.abs(upd).max() < 1e-1:
+        upd = upd + dense_step(Phi, ops.defect(X + upd, t, params), adjoints_only)
+    return upd
+
+
+def test_scatter_mass_pins_and_blocks():
+    rng = np.random.default_rng(0)
+    Phi = rng.standard_normal((14, 14, 3))
+    J = hotpath.indirect_scatter_mass(Phi)
+    Js = hotpath.indirect_scatter_mass(Phi, sparse=True).toarray()
+    assert J.shape == (42, 56) and np.array_equal(J, Js)
+    zero = np.flatnonzero(~J.any(axis=0))
+    assert list(zero) == [0, 1, 2, 3, 4, 5, 6, 42, 43, 44, 45, 46, 47, 55]
+    assert np.array_equal(J[14:28, 28:42], -np.eye(14)) and np.array_equal(J[14:28, 14:28], Phi[:, :, 1])
+    # the 12-row scatter is unchanged
+    P12 = rng.standard_normal((12, 12, 3))
+    J12 = hotpath.indirect_scatter(P12)
+    assert list(np.flatnonzero(~J12.any(axis=0))) == [0, 1, 2, 3, 4, 5, 36, 37, 38, 39, 40, 41]
+
+
+@pytest.mark.parametrize("n", [2, 3, 9])
+@pytest.mark.parametrize("adjoints_only", [False, True])
+def test_host_step_equals_dense_solve(oracle, n, adjoints_only):
+    ops = OracleOps14(oracle)
+    X, t = guess14(n)
+    params = hotpath.make_params(MU, DU, TU, THR, ISP, 1.0, 1.0, 1.0)
+    Phi, d = ops.stm(X, t, params)
+    upd = drivers.optimizeTraj_OLS_mass(X, t, d, Phi, n, params, adjoints_only, ops)
+    ref = with_soc(X, t, params, ops, Phi, d, adjoints_only)
+    assert np.abs(upd - ref).max() <= 1e-9 * max(1.0, np.abs(ref).max())
+    assert np.all(upd[pinned_mask(n)] == 0.0)
+    if adjoints_only:
+        assert np.all(upd[0:7] == 0.0)
+    else:
+        assert np.any(upd[6, -1] != 0.0)           # the final mass is free
+
+
+def consistent_problem(oracle, n=12):
+    """Nodes sampled from ONE trajectory of the oracle's discrete map at p = 1, rho = 1, lambda_m shifted so that
+    lambda_m(tf) = 0 (lambda_m does not feed back into the p = 1 dynamics)."""
+    XC, T = synth.indirect_problem(n, seed=4, lam_sigma=0.1)
+    t = T[:, 0]
+    params = hotpath.make_params(MU, DU, TU, THR, ISP, 1.0, 1.0, 1.0)
+    X = np.zeros((14, n), order="F")
+    X[:, 0] = drivers.lift_to_mass(XC[:, :1, 0], 1000.0)[:, 0]
+    X[13, 0] = 0.4
+    for k in range(n - 1):
+        pair = np.asfortranarray(np.stack([X[:, k], np.zeros(14)], axis=1))
+        _, d, rc = oracle.indirect14(pair, t[k:k + 2], prm_list(params), oracle.RK4, STEPS, want_stm=False)
+        assert rc == 0
+        X[:, k + 1] = d[:, 0]
+    X[13] -= X[13, -1]
+    return X, t, params
+
+
+def test_lambda_m_shift_keeps_the_trajectory(oracle):
+    X, t, params = consistent_problem(oracle)
+    d = OracleOps14(oracle).defect(X, t, params)
+    assert np.abs(d).max() < 1e-12 * np.abs(X).max()
+    assert X[13, -1] == 0.0 and np.all(np.diff(X[6]) <= 0.0)
+
+
+def test_mirror_loop_recovers_consistent_problem(oracle):
+    X, t, params = consistent_problem(oracle)
+    n = X.shape[1]
+    rng = np.random.default_rng(5)
+    X0 = X.copy()
+    X0[:, 1:-1] += 1e-3 * rng.standard_normal((14, n - 2)) * np.maximum(1e-3, np.abs(X[:, 1:-1]))
+    X0[6, -1] += 1e-3
+    Xs, defect, status = drivers.multiShoot_CRTBP_indirect_mass(X0, t, MU, DU, TU, n, ISP, THR, False, False, 20, 1.0, 1.0,
+                                                                ops=OracleOps14(oracle), verbose=False)
+    assert status == 0 and np.abs(defect).max() <= 1e-10
+    assert np.array_equal(Xs[0:7, 0], X0[0:7, 0]) and np.array_equal(Xs[0:6, -1], X0[0:6, -1]) and Xs[13, -1] == 0.0
+    scale = np.maximum(1.0, np.abs(X).max(axis=1, keepdims=True))
+    assert np.abs((Xs - X) / scale).max() < 1e-8
+
+
+def test_lift_to_mass():
+    XC, _ = synth.indirect_problem(5, n_batch=2)
+    X14 = drivers.lift_to_mass(XC, 750.0)
+    assert X14.shape == (14, 5, 2)
+    assert np.array_equal(X14[[0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12]], XC)
+    assert np.all(X14[6] == 750.0) and np.all(X14[13] == 0.0)
+    with pytest.raises(ValueError):
+        drivers.lift_to_mass(X14, 1.0)
+
+
+def test_argument_checks(oracle):
+    XC, T = synth.indirect_problem(6)
+    X14 = drivers.lift_to_mass(XC[:, :, 0], 1000.0)
+    t = T[:, 0]
+    ops = OracleOps14(oracle)
+    with pytest.raises(ValueError):         # 12 rows go to multiShoot_CRTBP_indirect
+        drivers.multiShoot_CRTBP_indirect_mass(XC[:, :, 0], t, MU, DU, TU, 6, ISP, THR, False, False, 5, 1.0, 1.0, ops=ops, verbose=False)
+    for isp in (0.0, -2000.0):
+        with pytest.raises(ValueError):
+            drivers.multiShoot_CRTBP_indirect_mass(X14, t, MU, DU, TU, 6, isp, THR, False, False, 5, 1.0, 1.0, ops=ops, verbose=False)
+    bad = X14.copy()
+    bad[6, 0] = 0.0
+    with pytest.raises(ValueError):
+        drivers.multiShoot_CRTBP_indirect_mass(bad, t, MU, DU, TU, 6, ISP, THR, False, False, 5, 1.0, 1.0, ops=ops, verbose=False)
+    # the 12-row driver still refuses 14 rows
+    with pytest.raises(ValueError):
+        drivers.multiShoot_CRTBP_indirect(X14, t, MU, DU, TU, 6, 1000.0, THR, False, False, 5, 1.0, 1.0, ops=ops, verbose=False)
