@@ -239,10 +239,13 @@ __device__ __forceinline__ void bvp_reflect_store(double (&col)[2 * NX], const i
     const double g = trivial ? 0.0 : rcp_nr(beta * (beta - alpha));
     if constexpr (D::QT_PASS) { if (c == k) { my_v = vk; my_g = g; } }
     if (c == k && !trivial) col[k] = beta;
-    // The 14-dim adjoints-only stack triangularises an all-zero column (the pinned lambda_m(tf) column of the last node); then
-    // beta = 0 * rsqrt(0) is NaN and H = I must not be applied as 0 * NaN.  (The other stacks triangularise only columns that
-    // are nonzero in a regular system: code unchanged.)
-    if (c > k && c < D::NLANES && !(NX == 14 && NU < NX && trivial)) {
+    // An adjoints-only stack can triangularise a column that is zero from its diagonal down: the 14-dim one always does at the
+    // pinned lambda_m(tf) column of the last node, and either does whenever the left / right columns of a pair are linearly
+    // dependent (a pair's 2NX x 3NU stack need not have full rank when the whole least-squares system has; e.g. signed-permutation
+    // STMs).  Then beta = 0 * rsqrt(0) is NaN and H = I must not be applied as 0 * NaN.  The rows below NU + NX still carry only
+    // residual, so the new block row stays exact.  (The square stacks triangularise only their shared unknown's columns, which
+    // hold -I: never zero, code unchanged.)
+    if (c > k && c < D::NLANES && !(NU < NX && trivial)) {
       double w0 = vk * col[k], w1 = 0.0, w2 = 0.0, w3 = 0.0;
 #pragma unroll
       for (int r = k + 1; r < R2; ++r) {
