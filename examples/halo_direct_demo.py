@@ -10,6 +10,8 @@ states are handed to the indirect method (p = 2, adjoints only first), the refer
 --free-ends [beta] runs the reference's other mode, flagEnd = true (default beta = 0): odd iterations also move the departure and
 arrival phases tau1, tau2 (by at most 0.1 per step), so the transfer finds where on the two orbits it starts and ends.  The run
 starts from tau2 offset by --tau2-offset (default 0.02) from the stacked value and prints the final phases.
+--free-tf [days] also makes the time of flight a variable of the free iterations, at most `days` per step (default 1, the
+reference's bound; implies --free-ends 0 unless given): tf in [1 day, 40 days].
 """
 import importlib.util
 import os
@@ -46,7 +48,7 @@ def demo_problem(n_nodes=30, tof_days=20.0, tau1=0.75):
     return X, U, t, tau1, tau2, times[0], tabs[0], times[1], tabs[1]
 
 
-def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100, free_ends=None, tau2_offset=0.0):
+def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100, free_ends=None, tau2_offset=0.0, free_tf=None):
     ctx = lto.default_context(0)
     X, U, t, tau1, tau2, t0s, X0s, tfs, Xfs = demo_problem()
     tau2 += tau2_offset
@@ -56,12 +58,16 @@ def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100, free
     flag_end = free_ends is not None
     X, U, tau1, tau2, t, dV1, dV2, defect = drivers.multiShoot_CRTBP_direct(
         X, U, tau1, tau2, t, np.zeros(3), np.zeros(3), MU, DU, TU, n, nsteps, mass, Isp, t0s, X0s, tfs, Xfs, False, flag_end,
-        float(free_ends or 0.0), False, maxIter, ops=None if flag_end else ops, verbose=verbose)
+        float(free_ends or 0.0), False, maxIter, ops=None if flag_end else ops, verbose=verbose,
+        tf_step=float(free_tf or 0.0) * lto.day / TU if flag_end else 0.0)
     last = drivers.multiShoot_CRTBP_direct.last
-    res = {"direct": (last["status"], last["iterations"], float(np.abs(defect).max())), "X": X, "U": U, "tau": (tau1, tau2)}
+    res = {"direct": (last["status"], last["iterations"], float(np.abs(defect).max())), "X": X, "U": U, "tau": (tau1, tau2),
+           "tf_days": float(t[-1] * TU / lto.day)}
     print("direct%s: status %d after %d iterations, max defect %.2e, cost %.6f, tau = (%.9f, %.9f), max thrust %.3f N (%.2f s)" % (
         " (free ends, beta = %g)" % free_ends if flag_end else "", last["status"], last["iterations"], np.abs(defect).max(),
         last["history"][1, last["iterations"] - 1], tau1, tau2, np.linalg.norm(U, axis=0).max(), time.perf_counter() - t0))
+    if free_tf and flag_end:
+        print("free tf (step %g days): tf = %.6f days" % (free_tf, res["tf_days"]))
     if then_indirect and last["status"] == 0:
         rng = np.random.default_rng(0)
         XC = np.vstack([X, 0.1 * rng.standard_normal((6, n))])
@@ -88,5 +94,8 @@ if __name__ == "__main__":
     off = _arg("--tau2-offset", 0.02)
     if off is None:
         off = 0.02 if free is not None else 0.0
+    free_tf = _arg("--free-tf", 1.0)
+    if free_tf is not None and free is None:
+        free = 0.0                                        # a free tf moves on the free-end iterations
     main(verbose="-q" not in sys.argv, then_indirect="--then-indirect" in sys.argv, python_loop="--python-loop" in sys.argv,
-         free_ends=free, tau2_offset=off)
+         free_ends=free, tau2_offset=off, free_tf=free_tf)

@@ -314,6 +314,42 @@ int lto_direct_solve_free(lto_ctx* ctx, int nstate, int n_nodes, const double* X
                           double* U_out, double* dV_out, double* t_out, double* defect_out, double* tau_out, int* status,
                           int* iterations, double* history);
 
+/* ---- Free time of flight with free end points (src/multiShoot_CRTBP_direct.jl:286-295, :503-516, :567, :582): on a
+ * free iteration the subproblem gains p3 = tf_jump, the defect constraints read Jac_i [dx_i; dx_{i+1}; du_i; du_{i+1}] + dtf_i p3 =
+ * -defect_i with dtf_i = d defect_i / d tf (the Jacobian sweep's tf column), and p3 is bounded by lo = max(-step, tf_min - tf),
+ * hi = min(step, tf_max - tf).  The 3 x 3 box QP in (p1, p2, p3) is solved exactly on the device.  Times in TU. */
+typedef struct lto_direct_tf_bounds {
+  double step;                       /* bound of |tf_jump| per free iteration (the reference: 1 day) */
+  double tf_min, tf_max;             /* absolute bounds of tf; tf_min > t0 keeps the grid from collapsing */
+} lto_direct_tf_bounds;
+/* One Jacobian sweep (with the tf column) and one free-end, free-tf QP step: arguments as lto_direct_qp_step_free, tfb [n_targets];
+ * tf = the last entry of each trajectory's grid.  p_out [3 x n_batch] = (p1; p2; p3).  Ties of the box QP go to the smaller
+ * max(|p1|/0.1, |p2|/0.1, |p3|/step), then to the earlier candidate (interior point, then the faces p1 = lo, hi, p2 = lo, hi,
+ * p3 = lo, hi); a coordinate on a bound is the bound value itself.  LTO_EINVAL for step < 0, tf outside [tf_min, tf_max] or
+ * tf_min <= t0. */
+int lto_direct_qp_step_free_tf(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
+                               int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets,
+                               const lto_direct_end_model* model, const double* beta, const lto_direct_tf_bounds* tfb, int n_targets,
+                               int allow_impulsive, double* dX, double* dU, double* dV, double* p_out, double* cost);
+/* The loop of lto_direct_solve_free_batch with tf a variable of the free iterations (flag_end = 1, odd iterations): after the line
+ * search tau += alpha (p1, p2), tf += alpha p3 (kept in [tf_min, tf_max]), and every trajectory's grid is rebuilt from the entry
+ * grid, t = t0 + (tau_grid + 1) / 2 (tf - t0).  As in the reference (:560) the line search evaluates its trial points on the
+ * current grid, not at tf + alpha p3.  tfb [n_targets]; t_out [n_nodes x n_batch] is each trajectory's final grid; history
+ * [6 x maxIter x n_batch] = (max|defect|, cost, alpha, tau1, tau2, tf).  flag_end = 0, or step = 0 for every trajectory, runs
+ * lto_direct_solve_free_batch (same outputs byte for byte, history row 5 the constant tf).  Argument codes as
+ * lto_direct_qp_step_free_tf. */
+int lto_direct_solve_free_tf_batch(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
+                                   const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
+                                   const lto_direct_orbits* orbits, const lto_direct_targets* targets, int n_targets,
+                                   const double* tau_in, const double* beta, const lto_direct_tf_bounds* tfb, int flag_end,
+                                   int allow_impulsive, int maxIter, double* X_out, double* U_out, double* dV_out, double* t_out,
+                                   double* defect_out, double* tau_out, int* status, int* iterations, double* history);
+int lto_direct_solve_free_tf(lto_ctx* ctx, int nstate, int n_nodes, const double* X_in, const double* U_in, const double* t,
+                             int nsteps, const lto_direct_params* prm, const lto_direct_orbits* orbits,
+                             const lto_direct_targets* targets, const double* tau_in, double beta, const lto_direct_tf_bounds* tfb,
+                             int flag_end, int allow_impulsive, int maxIter, double* X_out, double* U_out, double* dV_out,
+                             double* t_out, double* defect_out, double* tau_out, int* status, int* iterations, double* history);
+
 /* ------------------------------------------------- device-resident API (operands already in HBM)
  * Struct-of-arrays, segment/node index fastest, so that a wavefront's 64 lanes read 512
  * contiguous bytes per component.  With J = n_nodes*n_batch nodes and S = (n_nodes-1)*n_batch

@@ -18,6 +18,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify,
        direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_qp_step, direct_solve, direct_end_states, direct_qp_step_free, direct_solve_free,
+       LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
 const liblto = get(ENV, "LTO_HIP_LIB", joinpath(@__DIR__, "..", "lowthrustopt_amd", "liblto_hip.so"))
@@ -395,6 +396,58 @@ function direct_solve_free(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matri
                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}),
               ctx.handle, nstate, n_nodes, X_all, u_all, t_TU, nsteps, prm, ob, tg, tau, β, flagEnd, allowImpulsive, maxIter, Xo, Uo,
               dV, to, defect, tau_o, status, iters, hist)
+    end
+    check(ctx, rc)
+    (Xo, Uo, tau_o[1], tau_o[2], to, dV[1:3], dV[4:6], defect, Int(status[1]), Int(iters[1]), hist[:, 1:maxIter])
+end
+
+# Free time of flight (direct.jl:286-295, :503-516, :567, :582): tf_jump bounded by `step` per free iteration and tf by [tf_min,
+# tf_max] (TU; tf_min past t0).  A Julia twin of lto_direct_tf_bounds.
+struct LtoDirectTfBounds
+    step::Cdouble
+    tf_min::Cdouble
+    tf_max::Cdouble
+end
+
+# optimizeTraj with flagEnd = true and a free tf: one Jacobian sweep with the tf column and the exact free-end, free-tf QP step
+# (tf = t_TU[end]).  Returns (x_update, u_update, p1_update, p2_update, tf_update, dV1_update, dV2_update, cost).
+function direct_qp_step_free_tf(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Float64}, t_TU::Vector{Float64}, nsteps, Isp,
+                                MU, DU, TU, state_0, state_f, model::LtoDirectEndModel, β, tfb::LtoDirectTfBounds, mass, dV1, dV2;
+                                allowImpulsive::Bool = false)
+    nstate, n_nodes = size(X_all)
+    dX = zeros(nstate, n_nodes); dU = zeros(3, n_nodes); dV = zeros(6); p = zeros(3); cost = zeros(1)
+    prm = Ref(LtoDirectParams(MU, DU, TU, Isp))
+    tg = Ref(LtoDirectTargets(state_0, state_f, mass, dV1, dV2))
+    rc = ccall(entry(ctx, :direct_qp_step_free_tf), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ref{LtoDirectParams},
+                Ref{LtoDirectTargets}, Ref{LtoDirectEndModel}, Ref{Cdouble}, Ref{LtoDirectTfBounds}, Cint, Cint, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+               ctx.handle, nstate, n_nodes, 1, X_all, u_all, t_TU, 1, nsteps, prm, tg, Ref(model), Ref(Cdouble(β)), Ref(tfb), 1,
+               allowImpulsive, dX, dU, dV, p, cost)
+    check(ctx, rc)
+    (dX, dU, p[1], p[2], p[3], dV[1:3], dV[4:6], cost[1])
+end
+
+# The loop of multiShoot_CRTBP_direct with flagEnd and a free tf on the device: returns (X_all, u_all, τ1, τ2, t_TU (the final
+# grid), dV1, dV2, defect, status, iterations, history [6 x maxIter] = (max|defect|, cost, alpha, τ1, τ2, tf)).
+function direct_solve_free_tf(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Float64}, τ1, τ2, t_TU::Vector{Float64}, nsteps,
+                              Isp, MU, DU, TU, X0_times::Vector{Float64}, X0_states::Matrix{Float64}, Xf_times::Vector{Float64},
+                              Xf_states::Matrix{Float64}, flagEnd::Bool, β, tfb::LtoDirectTfBounds, mass, dV1, dV2, maxIter::Integer;
+                              allowImpulsive::Bool = false)
+    nstate, n_nodes = size(X_all)
+    Xo = zeros(nstate, n_nodes); Uo = zeros(3, n_nodes); dV = zeros(6); to = zeros(n_nodes); defect = zeros(nstate, n_nodes - 1)
+    tau = [Float64(τ1), Float64(τ2)]; tau_o = zeros(2)
+    status = zeros(Cint, 1); iters = zeros(Cint, 1); hist = fill(NaN, 6, max(maxIter, 1))
+    prm = Ref(LtoDirectParams(MU, DU, TU, Isp))
+    tg = Ref(LtoDirectTargets(zeros(6), zeros(6), mass, dV1, dV2))
+    rc = GC.@preserve X0_times X0_states Xf_times Xf_states begin
+        ob = Ref(_orbits(X0_times, X0_states, Xf_times, Xf_states))
+        ccall(entry(ctx, :direct_solve_free_tf), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ref{LtoDirectParams}, Ref{LtoDirectOrbits},
+               Ref{LtoDirectTargets}, Ptr{Cdouble}, Cdouble, Ref{LtoDirectTfBounds}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+               Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}),
+              ctx.handle, nstate, n_nodes, X_all, u_all, t_TU, nsteps, prm, ob, tg, tau, β, Ref(tfb), flagEnd, allowImpulsive, maxIter,
+              Xo, Uo, dV, to, defect, tau_o, status, iters, hist)
     end
     check(ctx, rc)
     (Xo, Uo, tau_o[1], tau_o[2], to, dV[1:3], dV[4:6], defect, Int(status[1]), Int(iters[1]), hist[:, 1:maxIter])

@@ -49,6 +49,11 @@ class LtoDirectEndModel(C.Structure):
     _fields_ = [("g0", C.c_double * 6), ("gf", C.c_double * 6), ("c0_norm", C.c_double), ("cf_norm", C.c_double)]
 
 
+class LtoDirectTfBounds(C.Structure):
+    """Bounds of a free time of flight (TU): |tf_jump| <= step per free iteration, tf_min <= tf <= tf_max."""
+    _fields_ = [("step", C.c_double), ("tf_min", C.c_double), ("tf_max", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 
@@ -145,6 +150,14 @@ SIGNATURES = {
     "lto_direct_solve_free": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams),
                                         C.POINTER(LtoDirectOrbits), _vp, _vp, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _vp]),
+    "lto_direct_qp_step_free_tf": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(LtoDirectParams),
+                                             _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lto_direct_solve_free_tf_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int,
+                                                 C.POINTER(LtoDirectParams), C.POINTER(LtoDirectOrbits), _vp, C.c_int, _vp, _vp, _vp,
+                                                 C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_direct_solve_free_tf": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams),
+                                           C.POINTER(LtoDirectOrbits), _vp, _vp, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_direct_solve": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams), _vp, C.c_int, C.c_int,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_pack_soa_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_long, _vp, C.c_long]),

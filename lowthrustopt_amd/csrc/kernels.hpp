@@ -134,7 +134,11 @@ struct DirectQpArgs {
   // free ends only (launch_direct_qp_free)
   const double* model;             // [n_batch][14] (lto_direct_end_model): g0[6], gf[6], |c0|, |cf|
   const double* beta;              // [n_batch]
-  double* p;                       // [n_batch][2]: the phase updates p1, p2
+  double* p;                       // [n_batch][2]: the phase updates p1, p2 ([n_batch][3] with p3 = tf_jump: launch_direct_qp_free_tf)
+  // free time of flight only (launch_direct_qp_free_tf)
+  const double* dtf;               // [nstate][ldd]: d defect / d tf
+  const double* tfb;               // [n_batch][3]: step, tf_min, tf_max
+  const double* tf;                // [n_batch]: current tf
 };
 // workspace of either step: nr = 1 (frozen ends) or 3 (free ends: three right-hand sides)
 size_t direct_qp_workspace_bytes(int nstate, int n_nodes, int n_batch, int nr);
@@ -142,6 +146,8 @@ int* direct_qp_status(void* workspace, int n_batch);   // [n_batch] inside the w
 hipError_t launch_direct_qp(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st);
 // free ends (flagEnd = true): the same reduction with the right-hand sides z0 | dz/dp1 | dz/dp2, then the 2 x 2 box QP in p
 hipError_t launch_direct_qp_free(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st);
+// free ends and free tf: right-hand sides z0 | dz/dp1 | dz/dp2 | dz/dp3, then the 3 x 3 box QP in p
+hipError_t launch_direct_qp_free_tf(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st);
 hipError_t launch_direct_qp_update_dv(double* targets, const double* dV, const double* step, int n_batch, hipStream_t st);
 // the two orbit tables of the free-end model on the device: times [n], states and natural-spline second derivatives [n][6]
 struct EndOrbitsDev { int n[2]; const double* t[2]; const double* Y[2]; const double* M[2]; };
@@ -149,6 +155,12 @@ struct EndOrbitsDev { int n[2]; const double* t[2]; const double* Y[2]; const do
 hipError_t launch_end_states(const EndOrbitsDev& o, const double* tau, int n_batch, double* s, int s_stride, double* model,
                              hipStream_t st);
 hipError_t launch_tau_update(double* tau, const double* p, const double* step, int n_batch, hipStream_t st);
+// free tf: tau and tf updates from p [n_batch][3]; the grids t [n_batch][n] from tau_grid, t0 [n_batch], tf [n_batch] and their na
+// copies per trajectory for the line search, tl [n_batch * na][n]
+hipError_t launch_tf_update(double* tau, double* tf, const double* p, const double* step, const double* tfb, int n_batch,
+                            hipStream_t st);
+hipError_t launch_tf_grid(const double* taug, const double* t0, const double* tf, int n, int n_batch, double* t, double* tl, int na,
+                          hipStream_t st);
 
 // Newton step of the indirect method on the device (kernels_bvp.hip): structured orthogonal cyclic reduction, ndim = 12 or 14.
 size_t bvp_workspace_doubles(int ndim, int n_nodes, int n_batch);

@@ -30,7 +30,8 @@
 
 namespace lto {
 
-// NR right-hand sides: 1 for the frozen-end step, 3 for the free-end step (z0 | dz/dp1 | dz/dp2, kernels below and DESIGN 4.8c)
+// NR right-hand sides: 1 for the frozen-end step, 3 for the free-end step (z0 | dz/dp1 | dz/dp2, kernels below and DESIGN 4.8c),
+// 4 for the free-end step with a free time of flight (... | dz/dp3, p3 = tf_jump)
 template <int NS, int NR = 1>
 struct QpDims {
   static constexpr int NB = 2 * NS + 3;          // unknowns per node: dx (NS), du (3), lambda (NS)
@@ -58,6 +59,15 @@ struct QpArgs {
   const double* em;                  // free ends only: end model [n_batch][QP_MODEL]: g0[6], gf[6], |c0|, |cf| (lto_direct_end_model)
   const double* beta;                // free ends only: [n_batch]
 };
+// free time of flight (NR = 4): the tf column of the sweep and the per-trajectory bounds.  A separate type, so that the kernels of
+// NR = 1 and 3 keep their argument layout.
+struct QpArgsTf : QpArgs {
+  const double* dtf;                 // d defect / d tf [NS][ldd] (the Jacobian sweep's tf column)
+  const double* tfb;                 // [n_batch][3]: step, tf_min, tf_max (lto_direct_tf_bounds, TU)
+  const double* tf;                  // [n_batch]: the current tf of every trajectory
+};
+template <int NR>
+using QpA = std::conditional_t<NR == 4, QpArgsTf, QpArgs>;
 constexpr int QP_TARGET = 19;
 constexpr int QP_MODEL = 14;
 constexpr double QP_PBOUND = 0.1;    // |p1|, |p2| <= 0.1 (:280-284)
@@ -177,9 +187,14 @@ __device__ double qp_elem_bc0(const QpArgs& a, const QpScale& sc, const int b, c
 }
 
 // ---- free ends: the extra right-hand sides m = 1 (d/dp1) and m = 2 (d/dp2).  The end targets s0 + g0 p1 and sf + gf p2 enter
-// only the pins of node 0 and node n-1 and, with impulses, the velocity rows through which the impulse is eliminated.
-template <int NS>
-__device__ double qp_elem0_free(const QpArgs& a, const QpScale& sc, const int b, const int i, const int r, const int m) {
+// only the pins of node 0 and node n-1 and, with impulses, the velocity rows through which the impulse is eliminated.  With a free
+// tf (NR = 4), m = 3 (d/dp3): the defect rows of segment i read J z + dtf_i p3 = -defect_i, so the column is -dtf_i there (unscaled,
+// like the defect column) and zero elsewhere -- the end targets do not depend on tf.
+template <int NS, int NR>
+__device__ double qp_elem0_free(const QpA<NR>& a, const QpScale& sc, const int b, const int i, const int r, const int m) {
+  if constexpr (NR == 4) {
+    if (m == 3) return (r < NS) ? -a.dtf[(long)r * a.ldd + (long)b * a.S_traj + i] : 0.0;
+  }
   const int j = r - NS - 3;
   if (m != 2 || i + 2 != a.n_nodes || j < 0 || j >= 6) return 0.0;
   const double gf = a.em[(long)b * QP_MODEL + 6 + j];
@@ -246,7 +261,7 @@ __device__ __forceinline__ void qp_householder(double (&col)[ROWS], const int c)
 // ---- one level of the reduction: pair j of trajectory b stacks rows 2j and 2j+1 of `cur` (FIRST: the level-0 rows, formed from
 // the sweep's outputs), eliminates node (2j+1) 2^level and writes the new row j of `nxt`; a row without a partner is carried.
 template <int NS, bool FIRST, int NR>
-__global__ __launch_bounds__(64) void k_qp_level(QpArgs a, const int level, const int M, const double* __restrict__ cur,
+__global__ __launch_bounds__(64) void k_qp_level(QpA<NR> a, const int level, const int M, const double* __restrict__ cur,
                                                  double* __restrict__ nxt) {
   using D = QpDims<NS, NR>;
   constexpr int NB = D::NB;
@@ -261,7 +276,7 @@ __global__ __launch_bounds__(64) void k_qp_level(QpArgs a, const int level, cons
         const int cc = (e < 2 * NB * NB) ? e / NB : 2 * NB, r = (e < 2 * NB * NB) ? e % NB : (e - 2 * NB * NB) % NB;
         const int m = (e < 2 * NB * NB) ? 0 : (e - 2 * NB * NB) / NB;
         if constexpr (NR == 1) v = qp_elem0<NS>(a, sc, b, 2 * j, r, cc);
-        else v = (m == 0) ? qp_elem0<NS>(a, sc, b, 2 * j, r, cc) : qp_elem0_free<NS>(a, sc, b, 2 * j, r, m);
+        else v = (m == 0) ? qp_elem0<NS>(a, sc, b, 2 * j, r, cc) : qp_elem0_free<NS, NR>(a, sc, b, 2 * j, r, m);
       } else {
         v = rows[(long)(2 * j) * D::ROW + e];
       }
@@ -297,8 +312,8 @@ __global__ __launch_bounds__(64) void k_qp_level(QpArgs a, const int level, cons
     const int m = c - 3 * NB;
 #pragma unroll
     for (int r = 0; r < NB; ++r) {
-      col[r] = FIRST ? qp_elem0_free<NS>(a, sc, b, 2 * j, r, m) : top[2 * NB * NB + m * NB + r];
-      col[NB + r] = FIRST ? qp_elem0_free<NS>(a, sc, b, 2 * j + 1, r, m) : bot[2 * NB * NB + m * NB + r];
+      col[r] = FIRST ? qp_elem0_free<NS, NR>(a, sc, b, 2 * j, r, m) : top[2 * NB * NB + m * NB + r];
+      col[NB + r] = FIRST ? qp_elem0_free<NS, NR>(a, sc, b, 2 * j + 1, r, m) : bot[2 * NB * NB + m * NB + r];
     }
   }
   qp_householder<D::R2, NB, D::NCOLS>(col, c);
@@ -476,41 +491,46 @@ __global__ void k_qp_cost(QpArgs a, const double* dX, long ldX, double* dV, doub
 // ---- free ends: the solution is z(p) = z0 + z1 p1 + z2 p2 and the reduced cost
 //   phi(p) = phi0 + G.p + p'Hp/2,  phi0 = the frozen cost of z0,
 //   G_i = 2 (sum_k w_k (u_k + du0_k).du_ik + c2 sum_e a_e.b_ei),  H_ij = 2 (sum_k w_k du_ik.du_jk + c2 sum_e b_ei.b_ej) + beta |c|_i delta_ij
-// with a_e, b_ei the end-point impulse terms dV + d and their p-derivatives.  Per-block partial sums of the six node sums
-// (u.u, u.du1, u.du2, du1.du1, du1.du2, du2.du2, all weighted) in `part` [n_batch][nblk][6].
+// with a_e, b_ei the end-point impulse terms dV + d and their p-derivatives.  Per-block partial sums of the node sums in `part`
+// [n_batch][nblk][qp_nsum(NR)], in this order: u.u, u.du_m (m = 1 .. NR-1), du_i.du_j (i <= j, row by row), all weighted -- six for
+// NR = 3, ten for NR = 4 (p3 = tf_jump adds z3, with no beta term).
 constexpr int QP_NSUM = 6;
-template <int NS>
+__host__ __device__ constexpr int qp_nsum(const int nr) { return 1 + (nr - 1) + (nr - 1) * nr / 2; }
+template <int NS, int NR>
 __global__ __launch_bounds__(QP_FIN) void k_qp_free_sums(QpArgs a, double* part) {
-  constexpr int NB = QpDims<NS, 3>::NB;
+  constexpr int NB = QpDims<NS, NR>::NB, NP = NR - 1, NSUM = qp_nsum(NR);
   const int b = blockIdx.y, tid = threadIdx.x, k = blockIdx.x * QP_FIN + tid;
   const QpScale sc = qp_scale(a, b);
-  double acc[QP_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double acc[NSUM] = {};
   if (k < a.n_nodes) {
     const long node = (long)b * a.n_nodes + k;
     const double wk = qp_weight(a, b, k);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
+    for (int q = 0; q < 3; ++q) {             // straight-line code per q (qp_static_for): the NR = 3 kernel as before this form
       const double u = a.U[(long)q * a.ldu + node] + sc.su * a.Y[(long)(NS + q) * a.ldy + node];
-      const double d1 = sc.su * a.Y[(long)(NB + NS + q) * a.ldy + node], d2 = sc.su * a.Y[(long)(2 * NB + NS + q) * a.ldy + node];
+      double d[NP];
+      qp_static_for<0, NP>([&](auto m) { d[m] = sc.su * a.Y[(long)((m + 1) * NB + NS + q) * a.ldy + node]; });
       acc[0] = __builtin_fma(wk * u, u, acc[0]);
-      acc[1] = __builtin_fma(wk * u, d1, acc[1]);
-      acc[2] = __builtin_fma(wk * u, d2, acc[2]);
-      acc[3] = __builtin_fma(wk * d1, d1, acc[3]);
-      acc[4] = __builtin_fma(wk * d1, d2, acc[4]);
-      acc[5] = __builtin_fma(wk * d2, d2, acc[5]);
+      qp_static_for<0, NP>([&](auto m) { acc[1 + m] = __builtin_fma(wk * u, d[m], acc[1 + m]); });
+      qp_static_for<0, NP>([&](auto i) {
+        qp_static_for<i, NP>([&](auto j) {
+          constexpr int s = 1 + NP + i * NP - i * (i - 1) / 2 + (j - i);   // row i of the upper triangle starts after rows 0 .. i-1
+          acc[s] = __builtin_fma(wk * d[i], d[j], acc[s]);
+        });
+      });
     }
   }
-  __shared__ double red[QP_NSUM][QP_FIN];
+  __shared__ double red[NSUM][QP_FIN];
 #pragma unroll
-  for (int m = 0; m < QP_NSUM; ++m) red[m][tid] = acc[m];
+  for (int m = 0; m < NSUM; ++m) red[m][tid] = acc[m];
   __syncthreads();
   for (int h = QP_FIN / 2; h > 0; h >>= 1) {
     if (tid < h)
 #pragma unroll
-      for (int m = 0; m < QP_NSUM; ++m) red[m][tid] += red[m][tid + h];
+      for (int m = 0; m < NSUM; ++m) red[m][tid] += red[m][tid + h];
     __syncthreads();
   }
-  if (tid < QP_NSUM) part[((long)b * gridDim.x + blockIdx.x) * QP_NSUM + tid] = red[tid][0];
+  if (tid < NSUM) part[((long)b * gridDim.x + blockIdx.x) * NSUM + tid] = red[tid][0];
 }
 
 __device__ __forceinline__ double qp_phi(const double* G, const double* H, const double phi0, const double p1, const double p2) {
@@ -518,10 +538,32 @@ __device__ __forceinline__ double qp_phi(const double* G, const double* H, const
 }
 __device__ __forceinline__ double qp_clamp(const double v) { return fmin(fmax(v, -QP_PBOUND), QP_PBOUND); }
 
-// ---- the 2 x 2 box QP of every trajectory, one thread each: min phi(p) over |p1|, |p2| <= 0.1.  Candidates, in this order:
-// the interior stationary point (H positive definite and the point inside the box), the clamped 1-D minimisers on the edges
-// p1 = -d, +d, p2 = -d, +d, and the four corners.  phi is convex, so the smallest phi among them is the minimum; exact ties go to
-// the smaller max|p|, then to the earlier candidate.  Then the impulses, p and the cost (with the beta term).
+// ---- the exact minimum of a convex 2-D quadratic G.p + p'Hp/2 (H = [H0 H1; H1 H2]) over the box [lo1, hi1] x [lo2, hi2]: every
+// candidate is handed to `consider`, in this order: the interior stationary point (H positive definite and the point inside the
+// box), the clamped 1-D minimisers on the edges p1 = lo1, hi1, p2 = lo2, hi2, and the four corners.  A coordinate on a bound is the
+// bound value itself.
+template <class F>
+__device__ __forceinline__ void qp_box2(const double* G, const double* H, const double lo1, const double hi1, const double lo2,
+                                        const double hi2, F&& consider) {
+  const double det = H[0] * H[2] - H[1] * H[1];
+  if (H[0] > 0.0 && det > 0.0) {
+    const double p1 = (-G[0] * H[2] + G[1] * H[1]) / det, p2 = (-G[1] * H[0] + G[0] * H[1]) / det;
+    if (p1 >= lo1 && p1 <= hi1 && p2 >= lo2 && p2 <= hi2) consider(p1, p2);
+  }
+  for (int s = 0; s < 2; ++s) {                    // edges p1 = lo1, hi1: min over p2
+    const double p1 = s ? hi1 : lo1;
+    if (H[2] > 0.0) consider(p1, fmin(fmax(-(G[1] + H[1] * p1) / H[2], lo2), hi2));
+  }
+  for (int s = 0; s < 2; ++s) {                    // edges p2 = lo2, hi2: min over p1
+    const double p2 = s ? hi2 : lo2;
+    if (H[0] > 0.0) consider(fmin(fmax(-(G[0] + H[1] * p2) / H[0], lo1), hi1), p2);
+  }
+  consider(lo1, lo2); consider(hi1, lo2); consider(lo1, hi2); consider(hi1, hi2);
+}
+
+// ---- the 2 x 2 box QP of every trajectory, one thread each: min phi(p) over |p1|, |p2| <= 0.1 over the candidates of qp_box2.  phi
+// is convex, so the smallest phi among them is the minimum; exact ties go to the smaller max|p|, then to the earlier candidate.  Then
+// the impulses, p and the cost (with the beta term).
 template <int NS>
 __global__ void k_qp_free_box(QpArgs a, double* dV, double* pout, double* cost, double* singular, const double* part, int nblk) {
   constexpr int NB = QpDims<NS, 3>::NB;
@@ -567,6 +609,7 @@ __global__ void k_qp_free_box(QpArgs a, double* dV, double* pout, double* cost, 
     const double f = qp_phi(G, H, phi0, p1, p2), m = fmax(fabs(p1), fabs(p2));
     if (!have || f < best || (f == best && m < bm)) { best = f; bp1 = p1; bp2 = p2; bm = m; have = true; }
   };
+  // the candidates of qp_box2 at +-d, written out: this kernel's code stays as it was before qp_box2
   const double d = QP_PBOUND, det = H[0] * H[2] - H[1] * H[1];
   if (H[0] > 0.0 && det > 0.0) {
     const double p1 = (-G[0] * H[2] + G[1] * H[1]) / det, p2 = (-G[1] * H[0] + G[0] * H[1]) / det;
@@ -592,17 +635,135 @@ __global__ void k_qp_free_box(QpArgs a, double* dV, double* pout, double* cost, 
   if (singular) singular[b] = bad ? 1.0 : 0.0;
 }
 
-// ---- dX = z0 + z1 p1 + z2 p2 (dx part), dU = s_u (du part), grid over nodes
+// ---- free tf: the 3 x 3 box QP in p = (p1, p2, p3 = tf_jump), one thread per trajectory.  Bounds |p1|, |p2| <= 0.1
+// and p3 in [lo, hi], lo = max(-step, tf_min - tf), hi = min(step, tf_max - tf) (:286-295).  Candidates, in this order: the interior
+// stationary point (H positive definite by its leading minors and the point inside the box), then the exact 2-D box minimum of each
+// face p1 = lo, p1 = hi, p2 = lo, p2 = hi, p3 = lo, p3 = hi (qp_box2 on the other two coordinates, in increasing order).  phi is
+// convex, so the smallest phi among them is the minimum, also when H is singular.  Ties: the smaller max(|p1|/0.1, |p2|/0.1,
+// |p3|/step) (the last term 0 when step = 0), then the earlier candidate.  p [n_batch][3].
+__device__ __forceinline__ double qp_phi3(const double (&G)[3], const double (&H)[3][3], const double phi0, const double (&p)[3]) {
+  double q = 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    q += H[i][i] * p[i] * p[i];
+#pragma unroll
+    for (int j = i + 1; j < 3; ++j) q += 2.0 * H[i][j] * p[i] * p[j];
+  }
+  return phi0 + G[0] * p[0] + G[1] * p[1] + G[2] * p[2] + 0.5 * q;
+}
 template <int NS>
+__global__ __launch_bounds__(64) void k_qp_free_box3(QpArgsTf a, double* dV, double* pout, double* cost, double* singular, const double* part, int nblk) {
+  constexpr int NB = QpDims<NS, 4>::NB, NSUM = qp_nsum(4);
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.n_batch) return;
+  const bool bad = a.status[b] != 0;
+  const double nan = __builtin_nan("");
+  double sum[NSUM];
+#pragma unroll
+  for (int m = 0; m < NSUM; ++m) sum[m] = 0.0;
+  for (int k = 0; k < nblk; ++k)
+#pragma unroll
+    for (int m = 0; m < NSUM; ++m) sum[m] += part[((long)b * nblk + k) * NSUM + m];
+  const double* tg = a.tg + (long)b * QP_TARGET;
+  const double* em = a.em + (long)b * QP_MODEL;
+  const long nb = (long)b * a.n_nodes;
+  // end-point impulse terms dV_e + d_e = a_e + sum_m b_em p_m; tf enters them only through dx at the end nodes
+  double ae[6], be[3][6];
+  for (int e = 0; e < 2; ++e) {
+    const long node = nb + (e ? a.n_nodes - 1 : 0);
+    for (int q = 0; q < 3; ++q) {
+      const int v = 3 + q, i = 3 * e + q;
+      if (a.impulsive) {
+        ae[i] = tg[6 * e + v] - a.X[(long)v * a.ldx + node] - a.Y[(long)v * a.ldy + node];
+        be[0][i] = (e == 0 ? em[v] : 0.0) - a.Y[(long)(NB + v) * a.ldy + node];
+        be[1][i] = (e == 1 ? em[6 + v] : 0.0) - a.Y[(long)(2 * NB + v) * a.ldy + node];
+        be[2][i] = -a.Y[(long)(3 * NB + v) * a.ldy + node];
+      } else {
+        ae[i] = tg[13 + i];
+        be[0][i] = be[1][i] = be[2][i] = 0.0;
+      }
+    }
+  }
+  double caa = 0.0, ca[3] = {0.0, 0.0, 0.0}, cb[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  for (int i = 0; i < 6; ++i) {
+    caa += ae[i] * ae[i];
+    for (int m = 0; m < 3; ++m) {
+      ca[m] += ae[i] * be[m][i];
+      for (int l = m; l < 3; ++l) cb[m][l] += be[m][i] * be[l][i];
+    }
+  }
+  const double beta = a.beta[b];
+  const double phi0 = sum[0] + a.c2 * caa;
+  double G[3], H[3][3];
+  for (int m = 0, s = 4; m < 3; ++m) {
+    G[m] = 2.0 * (sum[1 + m] + a.c2 * ca[m]);
+    for (int l = m; l < 3; ++l, ++s) H[m][l] = H[l][m] = 2.0 * (sum[s] + a.c2 * cb[m][l]);
+  }
+  H[0][0] += beta * em[12];
+  H[1][1] += beta * em[13];
+  const double* tb = a.tfb + (long)b * 3;
+  const double step = tb[0], tf = a.tf[b];
+  const double lo[3] = {-QP_PBOUND, -QP_PBOUND, fmax(-step, tb[1] - tf)};
+  const double hi[3] = {QP_PBOUND, QP_PBOUND, fmin(step, tb[2] - tf)};
+  const double inv3 = step > 0.0 ? 1.0 / step : 0.0;
+  double best = 0.0, bp[3] = {0.0, 0.0, 0.0}, bm = 0.0;
+  bool have = false;
+  auto consider = [&](const double (&p)[3]) {
+    const double f = qp_phi3(G, H, phi0, p);
+    const double m = fmax(fmax(fabs(p[0]), fabs(p[1])) / QP_PBOUND, fabs(p[2]) * inv3);
+    if (!have || f < best || (f == best && m < bm)) { best = f; bp[0] = p[0]; bp[1] = p[1]; bp[2] = p[2]; bm = m; have = true; }
+  };
+  // interior: H p = -G by the adjugate, H positive definite by Sylvester's criterion
+  const double A00 = H[1][1] * H[2][2] - H[1][2] * H[1][2], A01 = H[0][2] * H[1][2] - H[0][1] * H[2][2],
+               A02 = H[0][1] * H[1][2] - H[0][2] * H[1][1], A11 = H[0][0] * H[2][2] - H[0][2] * H[0][2],
+               A12 = H[0][1] * H[0][2] - H[0][0] * H[1][2], A22 = H[0][0] * H[1][1] - H[0][1] * H[0][1];
+  const double det = H[0][0] * A00 + H[0][1] * A01 + H[0][2] * A02;
+  if (H[0][0] > 0.0 && A22 > 0.0 && det > 0.0) {
+    const double p[3] = {-(A00 * G[0] + A01 * G[1] + A02 * G[2]) / det, -(A01 * G[0] + A11 * G[1] + A12 * G[2]) / det,
+                         -(A02 * G[0] + A12 * G[1] + A22 * G[2]) / det};
+    if (p[0] >= lo[0] && p[0] <= hi[0] && p[1] >= lo[1] && p[1] <= hi[1] && p[2] >= lo[2] && p[2] <= hi[2]) consider(p);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {                   // faces p_k = lo_k, hi_k: the exact 2-D minimum over the other two
+    const int i = (k == 0) ? 1 : 0, j = (k == 2) ? 1 : 2;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const double v = s ? hi[k] : lo[k];
+      const double Gf[2] = {G[i] + H[i][k] * v, G[j] + H[j][k] * v};
+      const double Hf[3] = {H[i][i], H[i][j], H[j][j]};
+      qp_box2(Gf, Hf, lo[i], hi[i], lo[j], hi[j], [&](const double x, const double y) {
+        double p[3];
+        p[k] = v; p[i] = x; p[j] = y;
+        consider(p);
+      });
+    }
+  }
+  for (int e = 0; e < 2; ++e)
+    for (int q = 0; q < 3; ++q) {
+      const int i = 3 * e + q;
+      dV[(long)b * 6 + i] = bad ? nan : (a.impulsive ? ae[i] + be[0][i] * bp[0] + be[1][i] * bp[1] + be[2][i] * bp[2] - tg[13 + i] : 0.0);
+    }
+  for (int m = 0; m < 3; ++m) pout[3 * b + m] = bad ? nan : bp[m];
+  cost[b] = bad ? nan : best;
+  if (singular) singular[b] = bad ? 1.0 : 0.0;
+}
+
+// ---- dX = z0 + sum_m z_m p_m (dx part), dU = s_u (du part), grid over nodes; p [n_batch][NR - 1]
+template <int NS, int NR>
 __global__ __launch_bounds__(QP_FIN) void k_qp_free_combine(QpArgs a, const double* pout, double* dX, long ldX, double* dU, long ldU) {
-  constexpr int NB = QpDims<NS, 3>::NB;
+  constexpr int NB = QpDims<NS, NR>::NB, NP = NR - 1;
   const int b = blockIdx.y, k = blockIdx.x * QP_FIN + threadIdx.x;
   if (k >= a.n_nodes) return;
   const QpScale sc = qp_scale(a, b);
-  const double p1 = pout[2 * b], p2 = pout[2 * b + 1];      // NaN for a singular system
+  double p[NP];
+  qp_static_for<0, NP>([&](auto m) { p[m] = pout[NP * b + m]; });    // NaN for a singular system
   const long node = (long)b * a.n_nodes + k;
-  auto z = [&](const int c) {
-    return __builtin_fma(a.Y[(long)(2 * NB + c) * a.ldy + node], p2, __builtin_fma(a.Y[(long)(NB + c) * a.ldy + node], p1, a.Y[(long)c * a.ldy + node]));
+  auto z = [&](const int c) {          // fma(z_NP, p_NP, ... fma(z_1, p_1, z_0)), loaded outermost term first
+    double y[NR];
+    qp_static_for<0, NR>([&](auto mm) { y[NP - mm] = a.Y[(long)((NP - mm) * NB + c) * a.ldy + node]; });
+    double v = y[0];
+    qp_static_for<1, NR>([&](auto m) { v = __builtin_fma(y[m], p[m - 1], v); });
+    return v;
   };
 #pragma unroll
   for (int c = 0; c < NS; ++c) dX[(long)c * ldX + node] = z(c);
@@ -610,7 +771,7 @@ __global__ __launch_bounds__(QP_FIN) void k_qp_free_combine(QpArgs a, const doub
   for (int q = 0; q < 3; ++q) dU[(long)q * ldU + node] = sc.su * z(NS + q);
 }
 
-// workspace: gw (u64 [2 n_batch]) | status (int [n_batch]) | rows A | rows B | records | Y | partial sums; NR = 1 or 3
+// workspace: gw (u64 [2 n_batch]) | status (int [n_batch]) | rows A | rows B | records | Y | partial sums; NR = 1, 3 or 4
 static size_t qp_header_bytes(int n_batch) {
   return ((sizeof(unsigned long long) * 2 * n_batch + sizeof(int) * n_batch + 255) / 256) * 256;
 }
@@ -619,11 +780,11 @@ static size_t qp_doubles(int n_nodes, int n_batch) {
   using D = QpDims<NS, NR>;
   const size_t S = (size_t)(n_nodes - 1) * n_batch, J = (size_t)n_nodes * n_batch;
   const size_t nblk = (size_t)(n_nodes + QP_FIN - 1) / QP_FIN;
-  return 2 * S * D::ROW + J * D::REC + (size_t)NR * D::NB * J + nblk * n_batch * (NR == 1 ? 1 : QP_NSUM);
+  return 2 * S * D::ROW + J * D::REC + (size_t)NR * D::NB * J + nblk * n_batch * qp_nsum(NR);
 }
 size_t direct_qp_workspace_bytes(int nstate, int n_nodes, int n_batch, int nr) {
-  const size_t nd = (nstate == 7) ? (nr == 3 ? qp_doubles<7, 3>(n_nodes, n_batch) : qp_doubles<7, 1>(n_nodes, n_batch))
-                                  : (nr == 3 ? qp_doubles<6, 3>(n_nodes, n_batch) : qp_doubles<6, 1>(n_nodes, n_batch));
+  const size_t nd = (nstate == 7) ? (nr == 4 ? qp_doubles<7, 4>(n_nodes, n_batch) : nr == 3 ? qp_doubles<7, 3>(n_nodes, n_batch) : qp_doubles<7, 1>(n_nodes, n_batch))
+                                  : (nr == 4 ? qp_doubles<6, 4>(n_nodes, n_batch) : nr == 3 ? qp_doubles<6, 3>(n_nodes, n_batch) : qp_doubles<6, 1>(n_nodes, n_batch));
   return qp_header_bytes(n_batch) + sizeof(double) * nd + 4096;
 }
 int* direct_qp_status(void* workspace, int n_batch) {
@@ -633,11 +794,12 @@ int* direct_qp_status(void* workspace, int n_batch) {
 template <int NS, int NR>
 static hipError_t direct_qp_impl(const DirectQpArgs& q, void* workspace, hipStream_t st) {
   using D = QpDims<NS, NR>;
-  QpArgs a;
+  QpA<NR> a;
   a.n_nodes = q.n_nodes; a.n_batch = q.n_batch; a.S_traj = q.n_nodes - 1;
   a.Jac = q.Jac; a.ldj = q.ldj; a.defect = q.defect; a.ldd = q.ldd; a.X = q.X; a.ldx = q.ldx; a.U = q.U; a.ldu = q.ldu;
   a.t = q.t; a.t_stride = q.t_stride; a.tg = q.targets; a.impulsive = q.impulsive; a.c2 = q.c2;
   a.em = q.model; a.beta = q.beta;
+  if constexpr (NR == 4) { a.dtf = q.dtf; a.tfb = q.tfb; a.tf = q.tf; }
   const size_t S = (size_t)a.S_traj * a.n_batch, J = (size_t)a.n_nodes * a.n_batch;
   a.gw = (unsigned long long*)workspace;
   a.status = direct_qp_status(workspace, a.n_batch);
@@ -649,7 +811,7 @@ static hipError_t direct_qp_impl(const DirectQpArgs& q, void* workspace, hipStre
   double* part = a.Y + (size_t)NR * D::NB * J;
   hipError_t e = hipMemsetAsync(a.gw, 0, sizeof(unsigned long long) * 2 * a.n_batch, st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_qp_gmax<NS>), dim3((a.S_traj + 255) / 256, a.n_batch), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((k_qp_gmax<NS>), dim3((a.S_traj + 255) / 256, a.n_batch), dim3(256), 0, st, (const QpArgs&)a);
   int M = a.S_traj, level = 0;
   int Ms[40];
   double* cur = rowsA;
@@ -665,15 +827,19 @@ static hipError_t direct_qp_impl(const DirectQpArgs& q, void* workspace, hipStre
     M = groups;
     ++level;
   } while (M > 1);
-  hipLaunchKernelGGL((k_qp_final<NS, NR>), dim3(a.n_batch), dim3(64), 0, st, a, cur);
+  const QpArgs& ab = a;                 // the kernels past the first level read the common arguments only
+  hipLaunchKernelGGL((k_qp_final<NS, NR>), dim3(a.n_batch), dim3(64), 0, st, ab, cur);
   for (int l = level - 1; l >= 0; --l) {
     const int pairs = Ms[l] / 2;
-    if (pairs > 0) hipLaunchKernelGGL((k_qp_back<NS, NR>), dim3(pairs, a.n_batch), dim3(64), 0, st, a, l);
+    if (pairs > 0) hipLaunchKernelGGL((k_qp_back<NS, NR>), dim3(pairs, a.n_batch), dim3(64), 0, st, ab, l);
   }
-  if constexpr (NR == 3) {
-    hipLaunchKernelGGL((k_qp_free_sums<NS>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, a, part);
-    hipLaunchKernelGGL((k_qp_free_box<NS>), dim3((a.n_batch + 63) / 64), dim3(64), 0, st, a, q.dV, q.p, q.cost, q.singular, part, nblk);
-    hipLaunchKernelGGL((k_qp_free_combine<NS>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, a, q.p, q.dX, q.ldX, q.dU, q.ldU);
+  if constexpr (NR >= 3) {
+    hipLaunchKernelGGL((k_qp_free_sums<NS, NR>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, ab, part);
+    if constexpr (NR == 4)
+      hipLaunchKernelGGL((k_qp_free_box3<NS>), dim3((a.n_batch + 63) / 64), dim3(64), 0, st, a, q.dV, q.p, q.cost, q.singular, part, nblk);
+    else
+      hipLaunchKernelGGL((k_qp_free_box<NS>), dim3((a.n_batch + 63) / 64), dim3(64), 0, st, a, q.dV, q.p, q.cost, q.singular, part, nblk);
+    hipLaunchKernelGGL((k_qp_free_combine<NS, NR>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, ab, q.p, q.dX, q.ldX, q.dU, q.ldU);
     return hipGetLastError();
   }
   hipLaunchKernelGGL((k_qp_unscale<NS>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, a, q.dX, q.ldX, q.dU, q.ldU, part);
@@ -698,6 +864,9 @@ hipError_t launch_direct_qp(int nstate, const DirectQpArgs& q, void* workspace, 
 }
 hipError_t launch_direct_qp_free(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st) {
   return (nstate == 7) ? direct_qp_impl<7, 3>(q, workspace, st) : direct_qp_impl<6, 3>(q, workspace, st);
+}
+hipError_t launch_direct_qp_free_tf(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st) {
+  return (nstate == 7) ? direct_qp_impl<7, 4>(q, workspace, st) : direct_qp_impl<6, 4>(q, workspace, st);
 }
 
 }  // namespace lto
@@ -758,6 +927,40 @@ __global__ void k_tau_update(double* tau, const double* p, const double* step, i
 }
 hipError_t launch_tau_update(double* tau, const double* p, const double* step, int n_batch, hipStream_t st) {
   hipLaunchKernelGGL(k_tau_update, dim3((2 * n_batch + 63) / 64), dim3(64), 0, st, tau, p, step, n_batch);
+  return hipGetLastError();
+}
+
+// free tf: tau1 += alpha p1, tau2 += alpha p2, then tf += alpha p3 (:564-567), p [n_batch][3]; alpha = 0: frozen.  tf is kept in
+// [tf_min, tf_max] (tfb [n_batch][3]) against the rounding of tf + alpha (bound - tf).
+__global__ void k_tf_update(double* tau, double* tf, const double* p, const double* step, const double* tfb, int n_batch) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n_batch) return;
+  const double a = step[b];
+  if (a == 0.0) return;
+  tau[2 * b] = tau[2 * b] + p[3 * b] * a;
+  tau[2 * b + 1] = tau[2 * b + 1] + p[3 * b + 1] * a;
+  tf[b] = fmin(fmax(tf[b] + p[3 * b + 2] * a, tfb[3 * b + 1]), tfb[3 * b + 2]);
+}
+// the grid of every trajectory from its tf: t = t0 + (tau_grid + 1) / 2 (tf - t0) (:582), evaluated as written (no contraction, so
+// that it equals the host's formula bit for bit), and the copies of the line search's na trial trajectories per trajectory
+__global__ void k_tf_grid(const double* taug, const double* t0, const double* tf, int n, int n_batch, double* t, double* tl, int na) {
+#pragma clang fp contract(off)
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)n * n_batch) return;
+  const int b = (int)(i / n), k = (int)(i % n);
+  const double v = t0[b] + (taug[i] + 1.0) / 2.0 * (tf[b] - t0[b]);
+  t[i] = v;
+  for (int a = 0; a < na; ++a) tl[((long)b * na + a) * n + k] = v;
+}
+hipError_t launch_tf_update(double* tau, double* tf, const double* p, const double* step, const double* tfb, int n_batch,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(k_tf_update, dim3((n_batch + 63) / 64), dim3(64), 0, st, tau, tf, p, step, tfb, n_batch);
+  return hipGetLastError();
+}
+hipError_t launch_tf_grid(const double* taug, const double* t0, const double* tf, int n, int n_batch, double* t, double* tl, int na,
+                          hipStream_t st) {
+  const long tot = (long)n * n_batch;
+  hipLaunchKernelGGL(k_tf_grid, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, taug, t0, tf, n, n_batch, t, tl, na);
   return hipGetLastError();
 }
 

@@ -2161,6 +2161,52 @@ static int direct_qp_step_free_dev(lto_direct_plan* p, hipStream_t st, const dou
   return LTO_OK;
 }
 
+// free ends and free tf: the free-end step with p3 = tf_jump; dtf the sweep's tf column [nstate][ldd], tfb [n_batch][3]
+// and tf [n_batch] device arrays; p [n_batch][3] (device).
+static int direct_qp_step_free_tf_dev(lto_direct_plan* p, hipStream_t st, const double* Jac, long ldj, const double* dtf,
+                                      const double* defect, long ldd, const double* X, long ldx, const double* U, long ldu,
+                                      const double* t, int n_tgrids, const lto_direct_targets* targets, const lto_direct_end_model* model,
+                                      const double* beta, const double* tfb, const double* tf, int allow_impulsive, double* dX,
+                                      double* dU, double* dV, double* pout, double* cost) {
+  lto_ctx* c = p->ctx;
+  int rc = direct_qp_workspace(p, 4);
+  if (rc) return rc;
+  DirectQpArgs q;
+  std::memset(&q, 0, sizeof q);
+  q.n_nodes = p->n_nodes; q.n_batch = p->n_batch;
+  q.Jac = Jac; q.ldj = ldj; q.defect = defect; q.ldd = ldd; q.X = X; q.ldx = ldx; q.U = U; q.ldu = ldu;
+  q.t = t; q.t_stride = (n_tgrids == 1) ? 0 : p->n_nodes;
+  q.targets = (const double*)targets; q.impulsive = allow_impulsive ? 1 : 0;
+  const double vu = p->prm.DU / p->prm.TU;
+  q.c2 = vu * vu;
+  q.dX = dX; q.ldX = ldx; q.dU = dU; q.ldU = ldu; q.dV = dV; q.cost = cost;
+  q.singular = p->qp_singular_out;
+  q.model = (const double*)model; q.beta = beta; q.p = pout;
+  q.dtf = dtf; q.tfb = tfb; q.tf = tf;
+  timing_begin(c, st);
+  const hipError_t e = launch_direct_qp_free_tf(p->nstate, q, p->qp_ws, st);
+  timing_end(c, st);
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_direct_qp_free_tf", e);
+  return LTO_OK;
+}
+
+// the argument rules of a free tf, per trajectory b (bounds tfb[n_targets == 1 ? 0 : b], grid n_tgrids == 1 ? 0 : b): step >= 0,
+// tf_min <= tf <= tf_max with tf the grid's last entry, and tf_min > t0 (the reference's tf >= 0 with t0 = 0 allows an empty grid)
+static int tf_bounds_check(lto_ctx* c, const lto_direct_tf_bounds* tfb, int n_targets, const double* t, int n_tgrids, int n_nodes,
+                           int n_batch) {
+  for (int b = 0; b < n_batch; ++b) {
+    const lto_direct_tf_bounds& q = tfb[n_targets == 1 ? 0 : b];
+    const double* g = t + (size_t)(n_tgrids == 1 ? 0 : b) * n_nodes;
+    const double t0 = g[0], tf = g[n_nodes - 1];
+    const char* why = !(q.step >= 0.0) ? "tf bounds: step must be >= 0"
+                      : !(tf >= q.tf_min && tf <= q.tf_max) ? "tf bounds: tf (the grid's last entry) outside [tf_min, tf_max]"
+                      : !(q.tf_min > t0) ? "tf bounds: tf_min must lie past t0"
+                                         : nullptr;
+    if (why) return c ? set_err(c, LTO_EINVAL, why) : LTO_EINVAL;
+  }
+  return LTO_OK;
+}
+
 // the two orbit tables on the device with the natural-spline second derivatives (a tridiagonal solve on the host, once per call)
 struct DevOrbits {
   EndOrbitsDev o;
@@ -2397,13 +2443,103 @@ int lto_direct_qp_step_free(lto_ctx* c, int nstate, int n_nodes, int n_batch, co
   return rc;
 }
 
-// free ends of lto_direct_solve_free_batch (null for lto_direct_solve_batch)
+int lto_direct_qp_step_free_tf(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
+                               int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets,
+                               const lto_direct_end_model* model, const double* beta, const lto_direct_tf_bounds* tfb, int n_targets,
+                               int allow_impulsive, double* dX, double* dU, double* dV, double* p_out, double* cost) {
+  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
+  if ((n_targets != 1 && n_targets != n_batch) || (n_tgrids != 1 && n_tgrids != n_batch))
+    return c ? set_err(c, LTO_EINVAL, "n_targets / n_tgrids must be 1 or n_batch") : LTO_EINVAL;
+  if (t && tfb) {
+    const int rc0 = tf_bounds_check(c, tfb, n_targets, t, n_tgrids, n_nodes, n_batch);
+    if (rc0) return rc0;
+  }
+  if (!c) return LTO_ENULL;
+  if (!X || !U || !t || !prm || !targets || !model || !beta || !tfb || !dX || !dU || !dV || !p_out || !cost)
+    return set_err(c, LTO_ENULL, "lto_direct_qp_step_free_tf: a required array is NULL");
+  CallTimer call_timer(c);
+  lto_direct_plan* p = nullptr;
+  int rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &p);
+  if (rc) return rc;
+  lto::HostBuf<lto_direct_targets> tg;
+  lto::HostBuf<lto_direct_end_model> em(n_batch);
+  lto::HostBuf<double> hb((size_t)5 * n_batch);           // beta [B] | tf bounds [B][3] | tf [B]
+  lto::HostBuf<int> h_stat(n_batch, 0);
+  if (!direct_targets_expand(targets, n_targets, n_batch, tg) || !em.ok() || !hb.ok() || !h_stat.ok()) {
+    delete p;
+    return set_err(c, LTO_ENOMEM, "lto_direct_qp_step_free_tf: out of host memory");
+  }
+  for (int b = 0; b < n_batch; ++b) {
+    const int k = n_targets == 1 ? 0 : b;
+    em[b] = model[k]; hb[b] = beta[k];
+    hb[n_batch + 3 * b] = tfb[k].step; hb[n_batch + 3 * b + 1] = tfb[k].tf_min; hb[n_batch + 3 * b + 2] = tfb[k].tf_max;
+    hb[4 * (size_t)n_batch + b] = t[(size_t)(n_tgrids == 1 ? 0 : b) * n_nodes + n_nodes - 1];
+  }
+  const long J = (long)n_nodes * n_batch, S = p->S;
+  const int nj = nstate * 2 * (nstate + 3);
+  const size_t need = al256(sizeof(double) * nstate * J) * 4 + al256(sizeof(double) * 3 * J) * 4 + al256(sizeof(double) * n_nodes * n_tgrids) +
+                      al256(sizeof(double) * nj * S) + al256(sizeof(double) * nstate * S) * 2 + al256(sizeof(lto_direct_targets) * n_batch) +
+                      al256(sizeof(lto_direct_end_model) * n_batch) + al256(sizeof(double) * 7 * n_batch) * 3 +
+                      al256(sizeof(double) * 5 * n_batch) + 8192;
+  rc = arena_reserve(c, need);
+  if (rc) { delete p; return rc; }
+  c->arena_top = 0;
+  double* d_xa = arena_take<double>(c, (size_t)nstate * J);
+  double* d_X = arena_take<double>(c, (size_t)nstate * J);
+  double* d_dX = arena_take<double>(c, (size_t)nstate * J);
+  double* d_dXa = arena_take<double>(c, (size_t)nstate * J);
+  double* d_ua = arena_take<double>(c, (size_t)3 * J);
+  double* d_U = arena_take<double>(c, (size_t)3 * J);
+  double* d_dU = arena_take<double>(c, (size_t)3 * J);
+  double* d_dUa = arena_take<double>(c, (size_t)3 * J);
+  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
+  double* d_jac = arena_take<double>(c, (size_t)nj * S);
+  double* d_def = arena_take<double>(c, (size_t)nstate * S);
+  double* d_dtf = arena_take<double>(c, (size_t)nstate * S);
+  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)n_batch);
+  lto_direct_end_model* d_em = arena_take<lto_direct_end_model>(c, (size_t)n_batch);
+  double* d_dV = arena_take<double>(c, (size_t)7 * n_batch);
+  double* d_cost = arena_take<double>(c, (size_t)7 * n_batch);
+  double* d_p = arena_take<double>(c, (size_t)7 * n_batch);
+  double* d_hb = arena_take<double>(c, (size_t)5 * n_batch);
+  hipStream_t st = c->stream;
+  hipError_t e = stage_in(c, X, nstate, J, d_xa, d_X, J, st);
+  if (e == hipSuccess) e = stage_in(c, U, 3, J, d_ua, d_U, J, st);
+  if (e == hipSuccess) e = vec_in(c, t, (long)n_nodes * n_tgrids, d_t, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * n_batch, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_em, em.data(), sizeof(lto_direct_end_model) * n_batch, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_hb, hb.data(), sizeof(double) * 5 * n_batch, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { (void)hipStreamSynchronize(st); delete p; return set_err(c, LTO_EHIP, "stage in", e); }
+  rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, d_t, n_tgrids, d_jac, S, d_dtf, d_def, S, nullptr);
+  if (rc == LTO_OK)
+    rc = direct_qp_step_free_tf_dev(p, st, d_jac, S, d_dtf, d_def, S, d_X, J, d_U, J, d_t, n_tgrids, d_tg, d_em, d_hb, d_hb + n_batch,
+                                    d_hb + 4 * (size_t)n_batch, allow_impulsive, d_dX, d_dU, d_dV, d_p, d_cost);
+  if (rc == LTO_OK) {
+    e = stage_out(c, d_dX, J, nstate, J, d_dXa, dX, st);
+    if (e == hipSuccess) e = stage_out(c, d_dU, J, 3, J, d_dUa, dU, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dV, d_dV, sizeof(double) * 6 * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(p_out, d_p, sizeof(double) * 3 * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_stat.data(), lto_direct_plan_qp_status(p), sizeof(int) * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = stream_wait(st);
+    if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
+    for (int b = 0; b < n_batch && rc == LTO_OK; ++b)
+      if (h_stat[b]) rc = set_err(c, LTO_ESINGULAR, "the KKT system of a trajectory's QP step is singular (too few nodes to reach the terminal state?)");
+  } else {
+    (void)hipStreamSynchronize(st);
+  }
+  direct_plan_free(p);
+  return rc;
+}
+
+// free ends of lto_direct_solve_free_batch (null for lto_direct_solve_batch); tfb non-null: lto_direct_solve_free_tf_batch
 struct DirectFreeEnds {
   const lto_direct_orbits* orbits;
   const double* tau_in;       // [2 x n_batch]
   const double* beta;        // [n_targets]
   int flag_end;
   double* tau_out;            // [2 x n_batch] or null
+  const lto_direct_tf_bounds* tfb;   // [n_targets] or null
 };
 
 static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
@@ -2417,11 +2553,16 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     return set_err(c, LTO_ENULL, "X_in, U_in, t, prm, targets, X_out or status is NULL");
   if (fe && (!fe->orbits || !fe->tau_in || !fe->beta)) return set_err(c, LTO_ENULL, "orbits, tau_in or beta is NULL");
   if (fe && !orbits_ok(fe->orbits)) return set_err(c, LTO_EINVAL, "orbit tables need >= 2 samples each and non-NULL arrays");
-  const int hw = fe ? 5 : 3;                               // history row: max|defect|, cost, alpha (, tau1, tau2)
+  const int hw = fe ? (fe->tfb ? 6 : 5) : 3;               // history row: max|defect|, cost, alpha (, tau1, tau2 (, tf))
   if (maxIter < 0) return set_err(c, LTO_EINVAL, "maxIter must be >= 0");
   if ((n_tgrids != 1 && n_tgrids != n_batch) || (n_targets != 1 && n_targets != n_batch)) return set_err(c, LTO_EINVAL, "n_tgrids / n_targets must be 1 or n_batch");
   constexpr int NA = 10;                                   // LinRange(0.1, 1, 10), :412
   const int B = n_batch;
+  // free tf: with flag_end and a positive step for some trajectory.  Otherwise a free-tf call is the free-end loop
+  // with history row 5 the constant tf.
+  bool tfm = false;
+  if (fe && fe->tfb && fe->flag_end)
+    for (int b = 0; b < B; ++b) if (fe->tfb[n_targets == 1 ? 0 : b].step > 0.0) tfm = true;
   if ((long)B * NA * (n_nodes - 1) > 0x3fffffffL) return set_err(c, LTO_EINVAL, "too many line-search segments");
   const long n = n_nodes, J = n * B, S = (n - 1) * B;
   const int nj = nstate * 2 * (nstate + 3);
@@ -2481,40 +2622,73 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
   double* d_ss = d_search + B;                             // [NA*B] per-trial sums of squares
   double* d_alphas = d_ss + (size_t)NA * B;                // [NA]
   p->qp_singular_out = d_sing;
-  (void)report_reserve(c, (size_t)(fe ? 6 : 4) * B);
+  (void)report_reserve(c, (size_t)(fe ? 7 : 4) * B);
   hipStream_t st = c->stream;
-  // free ends: tau [2B] | p [2B] | end model [14B] | beta [B] on the device, the orbit tables with their spline moments
+  // free ends: tau [2B] | tf [B] | p [3B] | end model [14B] | beta [B] | tf bounds [3B] | t0 [B] on the device, the orbit tables with
+  // their spline moments; free tf also: the grids [B][n] | tau_grid [B][n] | the tf column [nstate][S]
   DevOrbits dob;
   double* d_fe = nullptr;
-  double *d_tau = nullptr, *d_p = nullptr, *d_em = nullptr, *d_beta = nullptr;
+  double* d_tfx = nullptr;
+  double *d_tau = nullptr, *d_tf = nullptr, *d_p = nullptr, *d_em = nullptr, *d_beta = nullptr, *d_tfb = nullptr, *d_t0 = nullptr;
+  double *d_tb = nullptr, *d_taug = nullptr, *d_dtf = nullptr;
   if (fe) {
     rc = orbits_upload(c, fe->orbits, dob, st);
-    lto::HostBuf<double> hb(B);
-    if (rc == LTO_OK && !hb.ok()) rc = set_err(c, LTO_ENOMEM, "lto_direct_solve_free_batch: out of host memory");
+    lto::HostBuf<double> hb((size_t)6 * B), hg(tfm ? (size_t)2 * n * B : 1);   // beta [B] | tf [B] | t0 [B] | tf bounds [3B]
+    if (rc == LTO_OK && (!hb.ok() || !hg.ok())) rc = set_err(c, LTO_ENOMEM, "lto_direct_solve_free_batch: out of host memory");
     if (rc == LTO_OK) {
       for (int b = 0; b < B; ++b) hb[b] = fe->beta[n_targets == 1 ? 0 : b];
-      hipError_t e0 = hipMalloc(&d_fe, sizeof(double) * 19 * B);
+      hipError_t e0 = hipMalloc(&d_fe, sizeof(double) * 25 * B);
       if (e0 != hipSuccess) { d_fe = nullptr; rc = set_err(c, LTO_EHIP, "free-end buffers", e0); }
       else {
-        d_tau = d_fe; d_p = d_tau + 2 * (size_t)B; d_em = d_p + 2 * (size_t)B; d_beta = d_em + 14 * (size_t)B;
+        d_tau = d_fe; d_tf = d_tau + 2 * (size_t)B; d_p = d_tf + B; d_em = d_p + 3 * (size_t)B; d_beta = d_em + 14 * (size_t)B;
+        d_tfb = d_beta + B; d_t0 = d_tfb + 3 * (size_t)B;
         e0 = hipMemcpyAsync(d_tau, fe->tau_in, sizeof(double) * 2 * B, hipMemcpyHostToDevice, st);
         if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_beta, hb.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
-        if (e0 == hipSuccess) e0 = hipMemsetAsync(d_p, 0, sizeof(double) * 2 * B, st);
-        if (e0 == hipSuccess) e0 = stream_wait(st);        // hb is released at the end of this block
+        if (e0 == hipSuccess) e0 = hipMemsetAsync(d_p, 0, sizeof(double) * 3 * B, st);
+        if (e0 == hipSuccess && tfm) {
+          // tf, t0, the bounds and tau_grid of every trajectory from its entry grid (:478-480); the grids start as t1
+          for (int b = 0; b < B; ++b) {
+            const lto_direct_tf_bounds& q = fe->tfb[n_targets == 1 ? 0 : b];
+            const double* g = t + (size_t)(n_tgrids == 1 ? 0 : b) * n;
+            hb[B + b] = g[n - 1]; hb[2 * (size_t)B + b] = g[0];
+            hb[3 * (size_t)B + 3 * b] = q.step; hb[3 * (size_t)B + 3 * b + 1] = q.tf_min; hb[3 * (size_t)B + 3 * b + 2] = q.tf_max;
+            for (long k = 0; k < n; ++k) {
+              hg[(size_t)b * n + k] = t1[(size_t)(n_tgrids == 1 ? 0 : b) * n + k];
+              hg[(size_t)(B + b) * n + k] = (g[k] - g[0]) / (g[n - 1] - g[0]) * 2.0 - 1.0;
+            }
+          }
+          e0 = hipMalloc(&d_tfx, sizeof(double) * (2 * (size_t)n * B + (size_t)nstate * S));
+          if (e0 != hipSuccess) d_tfx = nullptr;
+          else {
+            d_tb = d_tfx; d_taug = d_tb + (size_t)n * B; d_dtf = d_taug + (size_t)n * B;
+            e0 = hipMemcpyAsync(d_tf, &hb[B], sizeof(double) * B, hipMemcpyHostToDevice, st);
+            if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_t0, &hb[2 * (size_t)B], sizeof(double) * B, hipMemcpyHostToDevice, st);
+            if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_tfb, &hb[3 * (size_t)B], sizeof(double) * 3 * B, hipMemcpyHostToDevice, st);
+            if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_tb, hg.data(), sizeof(double) * 2 * n * B, hipMemcpyHostToDevice, st);
+          }
+        }
+        if (e0 == hipSuccess) e0 = stream_wait(st);        // hb and hg are released at the end of this block
         if (e0 != hipSuccess) rc = set_err(c, LTO_EHIP, "free-end buffers", e0);
       }
     }
-    if (rc == LTO_OK && fe->flag_end) rc = direct_qp_workspace(p, 3);
-    if (rc) { if (d_fe) (void)hipFree(d_fe); p->qp_singular_out = nullptr; direct_plan_free(pl); direct_plan_free(p); return rc; }
+    if (rc == LTO_OK && fe->flag_end) rc = direct_qp_workspace(p, tfm ? 4 : 3);
+    if (rc) {
+      if (d_fe) (void)hipFree(d_fe);
+      if (d_tfx) (void)hipFree(d_tfx);
+      p->qp_singular_out = nullptr; direct_plan_free(pl); direct_plan_free(p);
+      return rc;
+    }
   }
   double alphas[NA];
   for (int a = 0; a < NA; ++a) alphas[a] = 0.1 + (1.0 - 0.1) / (NA - 1) * a;
   alphas[NA - 1] = 1.0;
-  lto::HostBuf<double> h_er(B, 1.0), h_back((size_t)(fe ? 6 : 4) * B), h_act(B, -1.0), h_search(B, -1.0);   // er = 1.0 (:488)
+  lto::HostBuf<double> h_er(B, 1.0), h_back((size_t)(fe ? 7 : 4) * B), h_act(B, -1.0), h_search(B, -1.0);   // er = 1.0 (:488)
   lto::HostBuf<int> it(B, 0), status(B, 0);
   lto::HostBuf<char> active(B, 1), moved(B, 0);
   if (!h_er.ok() || !h_back.ok() || !h_act.ok() || !h_search.ok() || !it.ok() || !status.ok() || !active.ok() || !moved.ok()) {
-    direct_plan_free(pl); direct_plan_free(p);
+    if (d_fe) (void)hipFree(d_fe);
+    if (d_tfx) (void)hipFree(d_tfx);
+    p->qp_singular_out = nullptr; direct_plan_free(pl); direct_plan_free(p);
     return set_err(c, LTO_ENOMEM, "lto_direct_solve_batch: out of host memory");
   }
   hipError_t e = stage_in(c, X_in, nstate, J, d_aos, d_X, J, st);
@@ -2529,8 +2703,11 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
   if (e == hipSuccess && fe) e = launch_end_states(dob.o, d_tau, B, (double*)d_tg, 19, d_em, st);
   if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage in", e);
   const double* t_cur = d_t;                               // the caller's grid until the first update, then t through tau
+  int ntg_cur = n_tgrids;
+  const double* t_qp = tfm ? d_tb : d_t1;                  // the grid of the QP's weights: with free tf every trajectory has its own
+  const int ntg_qp = tfm ? B : n_tgrids;
 
-  if (rc == LTO_OK) rc = lto_direct_defect_dev(p, st, d_X, J, d_U, J, t_cur, n_tgrids, d_def, S, nullptr);    // :485 (er = 1.0: one step at least)
+  if (rc == LTO_OK) rc = lto_direct_defect_dev(p, st, d_X, J, d_U, J, t_cur, ntg_cur, d_def, S, nullptr);    // :485 (er = 1.0: one step at least)
   auto any_active = [&]() { for (int b = 0; b < B; ++b) if (active[b]) return true; return false; };
   while (rc == LTO_OK) {
     // `while er > 1e-6` (:491) + the iteration limit (:492-496), trajectory by trajectory
@@ -2555,14 +2732,22 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     bool free_it = false;
     if (fe && fe->flag_end)
       for (int b = 0; b < B; ++b) if (active[b] && (it[b] & 1)) free_it = true;
-    rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, t_cur, n_tgrids, d_jac, S, nullptr, nullptr, 0, nullptr);   // :500
-    if (rc == LTO_OK && free_it)
+    if (tfm && free_it)                                    // :500 with the tf column (:503-516)
+      rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, t_cur, ntg_cur, d_jac, S, d_dtf, nullptr, S, nullptr);
+    else
+      rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, t_cur, ntg_cur, d_jac, S, nullptr, nullptr, 0, nullptr);   // :500
+    if (rc == LTO_OK && free_it && tfm)
+      rc = direct_qp_step_free_tf_dev(p, st, d_jac, S, d_dtf, d_def, S, d_X, J, d_U, J, t_qp, ntg_qp, d_tg,
+                                      (const lto_direct_end_model*)d_em, d_beta, d_tfb, d_tf, allow_impulsive, d_dX, d_dU, d_dV, d_p, d_cost);
+    else if (rc == LTO_OK && free_it)
       rc = direct_qp_step_free_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t1, n_tgrids, d_tg, (const lto_direct_end_model*)d_em,
                                    d_beta, allow_impulsive, d_dX, d_dU, d_dV, d_p, d_cost);
     else if (rc == LTO_OK)                                                                                               // :525-529
-      rc = lto_direct_qp_step_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t1, n_tgrids, d_tg, allow_impulsive, d_dX, d_dU, d_dV, d_cost);
+      rc = lto_direct_qp_step_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, t_qp, ntg_qp, d_tg, allow_impulsive, d_dX, d_dU, d_dV, d_cost);
     if (rc != LTO_OK) break;
-    if (search) {                                          // lineSearch (:405-430): the ten trial points of every problem, one sweep
+    // lineSearch (:405-430): the ten trial points of every problem, one sweep.  With free tf they are evaluated on the current grid
+    // (`lineSearch(..., t_TU, ...)`, :560), not at tf + alpha p3: d_tl holds each trajectory's current grid (k_tf_grid)
+    if (search) {
       e = launch_trial_points(d_X, d_dX, J, nstate, n_nodes, B, NA, d_alphas, d_Xt, J * NA, st);
       if (e == hipSuccess) e = launch_trial_points(d_U, d_dU, J, 3, n_nodes, B, NA, d_alphas, d_Ut, J * NA, st);
       if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "trial points", e); break; }
@@ -2576,15 +2761,18 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     if (e == hipSuccess) e = launch_axpy_traj(d_X, d_dX, d_step, d_X, J, nstate, n_nodes, B, st);     // :562
     if (e == hipSuccess) e = launch_axpy_traj(d_U, d_dU, d_step, d_U, J, 3, n_nodes, B, st);          // :563
     if (e == hipSuccess) e = launch_direct_qp_update_dv((double*)d_tg, d_dV, d_step, B, st);           // :568-569
-    if (e == hipSuccess && free_it) e = launch_tau_update(d_tau, d_p, d_step, B, st);                   // :564-565
+    if (e == hipSuccess && free_it && !tfm) e = launch_tau_update(d_tau, d_p, d_step, B, st);           // :564-565
+    if (e == hipSuccess && free_it && tfm) e = launch_tf_update(d_tau, d_tf, d_p, d_step, d_tfb, B, st);  // :564-567
     if (e == hipSuccess && free_it) e = launch_end_states(dob.o, d_tau, B, (double*)d_tg, 19, d_em, st);  // targets at the new tau
+    if (e == hipSuccess && free_it && tfm) e = launch_tf_grid(d_taug, d_t0, d_tf, (int)n, B, d_tb, d_tl, NA, st);   // :582
     if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "update", e); break; }
-    t_cur = d_t1;                                                                                        // :582
-    rc = lto_direct_defect_dev(p, st, d_X, J, d_U, J, t_cur, n_tgrids, d_def, S, nullptr);              // :585
+    t_cur = tfm ? d_tb : d_t1;                                                                           // :582
+    ntg_cur = tfm ? B : n_tgrids;
+    rc = lto_direct_defect_dev(p, st, d_X, J, d_U, J, t_cur, ntg_cur, d_def, S, nullptr);               // :585
     if (rc != LTO_OK) break;
     e = launch_defect_norms(d_def, S, nstate, (int)(n - 1), B, nullptr, d_mx, st);                      // :588
     if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "norm", e); break; }
-    rc = read_scalars(c, st, d_step, 4 * B, d_tau, fe ? 2 * B : 0, h_back.data());                    // step | max|d| | cost | singular (| tau)
+    rc = read_scalars(c, st, d_step, 4 * B, d_tau, fe ? (tfm ? 3 : 2) * B : 0, h_back.data());         // step | max|d| | cost | singular (| tau (| tf))
     if (rc != LTO_OK) break;
     for (int b = 0; b < B; ++b) {
       if (!active[b]) continue;
@@ -2594,6 +2782,7 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
         double* hrow = history + ((size_t)b * maxIter + (it[b] - 1)) * hw;
         hrow[0] = h_er[b]; hrow[1] = h_back[2 * B + b]; hrow[2] = h_back[b];
         if (fe) { hrow[3] = h_back[4 * B + 2 * b]; hrow[4] = h_back[4 * B + 2 * b + 1]; }
+        if (fe && fe->tfb) hrow[5] = tfm ? h_back[6 * B + b] : t[(size_t)(n_tgrids == 1 ? 0 : b) * n + n - 1];
       }
       if (h_back[3 * B + b] != 0.0) { status[b] = 3; active[b] = 0; }
     }
@@ -2606,6 +2795,9 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     if (e == hipSuccess && dV_out) e = hipMemcpy2DAsync(dV_out, sizeof(double) * 6, (const double*)d_tg + 13, sizeof(lto_direct_targets),
                                                          sizeof(double) * 6, B, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && fe && fe->tau_out) e = hipMemcpyAsync(fe->tau_out, d_tau, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, st);
+    lto::HostBuf<double> h_tb(tfm && t_out ? (size_t)n * B : 1);
+    if (e == hipSuccess && tfm && t_out) e = h_tb.ok() ? hipMemcpyAsync(h_tb.data(), d_tb, sizeof(double) * n * B, hipMemcpyDeviceToHost, st)
+                                                       : hipErrorOutOfMemory;
     if (e == hipSuccess) e = stream_wait(st);
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
     if (rc == LTO_OK)
@@ -2614,13 +2806,14 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     if (rc == LTO_OK && t_out)
       for (int b = 0; b < B; ++b) {
         const size_t g = (size_t)(n_tgrids == 1 ? 0 : b) * n;
-        std::memcpy(t_out + (size_t)b * n, moved[b] ? &t1[g] : t + g, sizeof(double) * n);
+        std::memcpy(t_out + (size_t)b * n, !moved[b] ? t + g : tfm ? &h_tb[(size_t)b * n] : &t1[g], sizeof(double) * n);
       }
   } else {
     (void)hipStreamSynchronize(st);
   }
   for (int b = 0; b < B; ++b) { status_flag[b] = status[b]; if (iterations) iterations[b] = it[b]; }
   if (d_fe) (void)hipFree(d_fe);
+  if (d_tfx) (void)hipFree(d_tfx);
   direct_plan_free(pl);
   direct_plan_free(p);
   return rc;
@@ -2641,7 +2834,7 @@ int lto_direct_solve_free_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch
                                 const double* tau_in, const double* beta, int flag_end, int allow_impulsive, int maxIter,
                                 double* X_out, double* U_out, double* dV_out, double* t_out, double* defect_out, double* tau_out,
                                 int* status_flag, int* iterations, double* history) {
-  const DirectFreeEnds fe = {orbits, tau_in, beta, flag_end ? 1 : 0, tau_out};
+  const DirectFreeEnds fe = {orbits, tau_in, beta, flag_end ? 1 : 0, tau_out, nullptr};
   return direct_solve_impl(c, nstate, n_nodes, n_batch, X_in, U_in, t, n_tgrids, nsteps, prm, targets, n_targets, allow_impulsive,
                            maxIter, X_out, U_out, dV_out, t_out, defect_out, status_flag, iterations, history, &fe);
 }
@@ -2654,6 +2847,37 @@ int lto_direct_solve_free(lto_ctx* c, int nstate, int n_nodes, const double* X_i
   return lto_direct_solve_free_batch(c, nstate, n_nodes, 1, X_in, U_in, t, 1, nsteps, prm, orbits, targets, 1, tau_in, &beta, flag_end,
                                      allow_impulsive, maxIter, X_out, U_out, dV_out, t_out, defect_out, tau_out, status, iterations,
                                      history);
+}
+
+int lto_direct_solve_free_tf_batch(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X_in, const double* U_in,
+                                   const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
+                                   const lto_direct_orbits* orbits, const lto_direct_targets* targets, int n_targets,
+                                   const double* tau_in, const double* beta, const lto_direct_tf_bounds* tfb, int flag_end,
+                                   int allow_impulsive, int maxIter, double* X_out, double* U_out, double* dV_out, double* t_out,
+                                   double* defect_out, double* tau_out, int* status_flag, int* iterations, double* history) {
+  // the argument rules of a free tf answer without a device, like the shape checks
+  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
+  if ((n_tgrids != 1 && n_tgrids != n_batch) || (n_targets != 1 && n_targets != n_batch))
+    return c ? set_err(c, LTO_EINVAL, "n_tgrids / n_targets must be 1 or n_batch") : LTO_EINVAL;
+  if (t && tfb) {
+    const int rc = tf_bounds_check(c, tfb, n_targets, t, n_tgrids, n_nodes, n_batch);
+    if (rc) return rc;
+  }
+  if (!c) return LTO_ENULL;
+  if (!tfb) return set_err(c, LTO_ENULL, "tfb is NULL");
+  const DirectFreeEnds fe = {orbits, tau_in, beta, flag_end ? 1 : 0, tau_out, tfb};
+  return direct_solve_impl(c, nstate, n_nodes, n_batch, X_in, U_in, t, n_tgrids, nsteps, prm, targets, n_targets, allow_impulsive,
+                           maxIter, X_out, U_out, dV_out, t_out, defect_out, status_flag, iterations, history, &fe);
+}
+
+int lto_direct_solve_free_tf(lto_ctx* c, int nstate, int n_nodes, const double* X_in, const double* U_in, const double* t, int nsteps,
+                             const lto_direct_params* prm, const lto_direct_orbits* orbits, const lto_direct_targets* targets,
+                             const double* tau_in, double beta, const lto_direct_tf_bounds* tfb, int flag_end, int allow_impulsive,
+                             int maxIter, double* X_out, double* U_out, double* dV_out, double* t_out, double* defect_out,
+                             double* tau_out, int* status, int* iterations, double* history) {
+  return lto_direct_solve_free_tf_batch(c, nstate, n_nodes, 1, X_in, U_in, t, 1, nsteps, prm, orbits, targets, 1, tau_in, &beta, tfb,
+                                        flag_end, allow_impulsive, maxIter, X_out, U_out, dV_out, t_out, defect_out, tau_out, status,
+                                        iterations, history);
 }
 
 int lto_direct_solve(lto_ctx* c, int nstate, int n_nodes, const double* X_in, const double* U_in, const double* t, int nsteps,

@@ -31,6 +31,7 @@ host, as in the reference (`-Jac_sparse \\ defect_vec`, :182).
 import numpy as np
 
 from . import hotpath
+from .constants import day
 
 
 class HipOps:
@@ -379,6 +380,11 @@ class HipDirectOps:
         Jt, _, d, _ = hotpath.direct_jacobian_blocks(X, U, t, nsteps, self.MU, self.DU, self.TU, self.Isp, ctx=self.ctx)
         return Jt, d
 
+    def jacobian_tf(self, X, U, t, nsteps):
+        """(Jac_temp, dtf, defect): the blocks and the tf column d defect_i / d tf (:503-516, exact on the device)."""
+        Jt, dtf, d, _ = hotpath.direct_jacobian_blocks(X, U, t, nsteps, self.MU, self.DU, self.TU, self.Isp, ctx=self.ctx)
+        return Jt, dtf, d
+
 
 def _natural_spline(x, Y, xq):
     """Natural cubic spline through (x, Y[:, j]) (second derivative 0 at both ends), evaluated at xq: one column per row of Y."""
@@ -610,8 +616,133 @@ def direct_qp_dense_free(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f,
     return best[1]
 
 
+TF_STEP_DAYS = 1.0       # |tf_jump| <= 1 day per free iteration (direct.jl:288)
+TF_MAX_DAYS = 40.0       # tf <= 40 days (direct.jl:294)
+
+
+def tf_bounds_default(t0, TU, step_days=TF_STEP_DAYS):
+    """(step, tf_min, tf_max) in TU: the reference's 1-day step and 40-day ceiling (direct.jl:288-295); its floor tf >= 0 would let
+    the grid collapse onto t0, so tf_min is one day past t0."""
+    return (step_days * day / TU, t0 + day / TU, TF_MAX_DAYS * day / TU)
+
+
+def direct_qp_dense_free_tf(Jac_temp, dtf, defect, X_all, u_all, t_TU, state_0, state_f, g0, gf, c0_norm, cf_norm, β, mass, dV1, dV2,
+                            DU, TU, tf, tf_bounds, allowImpulsive=False):
+    """optimizeTraj with flagEnd = true and a free time of flight (direct.jl:278-295, :337, :353-369): the host reference of the
+    device's free-tf step, by a different route.  p1, p2 and p3 = tf_jump are three more variables of one dense KKT system; the
+    defect rows read Jac_i [dx_i; dx_{i+1}; du_i; du_{i+1}] + dtf_i p3 = -defect_i; tf_bounds = (step, tf_min, tf_max) bound p3 to
+    [max(-step, tf_min - tf), min(step, tf_max - tf)] and |p1|, |p2| <= 0.1.  The 27 active sets (each p free, at its lower or at
+    its upper bound) are enumerated; a set is accepted when its free p lie in their bounds and the multipliers of its active bounds
+    have the right sign, and the accepted point of smallest cost is returned (ties: the smaller max(|p1|/0.1, |p2|/0.1, |p3|/step)).
+    Returns (x_update, u_update, dV1_update, dV2_update, p1, p2, p3, cost)."""
+    Jt = np.asarray(Jac_temp, dtype=np.float64)
+    dtf = np.asarray(dtf, dtype=np.float64)
+    d = np.asarray(defect, dtype=np.float64)
+    X = np.asarray(X_all, dtype=np.float64)
+    U = np.asarray(u_all, dtype=np.float64)
+    t = np.asarray(t_TU, dtype=np.float64)
+    dV1 = np.asarray(dV1, dtype=np.float64)
+    dV2 = np.asarray(dV2, dtype=np.float64)
+    step, tf_min, tf_max = (float(v) for v in tf_bounds)
+    lo = np.array([-P_BOUND, -P_BOUND, max(-step, tf_min - tf)])
+    hi = np.array([P_BOUND, P_BOUND, min(step, tf_max - tf)])
+    ns, _, S = Jt.shape
+    n = S + 1
+    c2 = (DU / TU) ** 2
+    nz = ns * n + 3 * n + 6 + 3                           # dx (node-major), du, dV1_jump, dV2_jump, p1, p2, p3
+    iu, iv, ip = ns * n, ns * n + 3 * n, ns * n + 3 * n + 6
+    dt = np.diff(t)
+    w = np.concatenate([dt / 2, [dt[-1] / 2]]) + np.concatenate([[0.0], dt[:-1] / 2, [0.0]])
+    Q = np.zeros(nz)
+    q = np.zeros(nz)                                      # cost = z'Qz + 2q'z + const
+    for k in range(n):
+        Q[iu + 3 * k:iu + 3 * k + 3] = w[k]
+        q[iu + 3 * k:iu + 3 * k + 3] = w[k] * U[:, k]
+    Q[iv:iv + 6] = c2
+    q[iv:iv + 3] = c2 * dV1
+    q[iv + 3:iv + 6] = c2 * dV2
+    Q[ip], Q[ip + 1] = β * c0_norm / 2, β * cf_norm / 2
+    rows, rhs = [], []
+    for i in range(S):                                    # -Jac_full * [X_jump; u_jump; tf_jump] = defect (:337, :516)
+        A = np.zeros((ns, nz))
+        A[:, ns * i:ns * i + 2 * ns] = Jt[:, :2 * ns, i]
+        A[:, iu + 3 * i:iu + 3 * i + 6] = Jt[:, 2 * ns:, i]
+        A[:, ip + 2] = dtf[:, i]
+        rows.append(A)
+        rhs.append(-d[:, i])
+    for k, s, g, dv, o in ((0, state_0, g0, dV1, 0), (n - 1, state_f, gf, dV2, 1)):
+        A = np.zeros((6, nz))
+        A[:, ns * k:ns * k + 6] = np.eye(6)
+        A[3:, iv + 3 * o:iv + 3 * o + 3] = np.eye(3)
+        A[:, ip + o] = -np.asarray(g, dtype=np.float64)
+        rows.append(A)
+        rhs.append(np.asarray(s, dtype=np.float64) - X[:6, k] - np.r_[0.0, 0.0, 0.0, dv])
+    if ns == 7:
+        A = np.zeros((1, nz))
+        A[0, 6] = 1.0
+        rows.append(A)
+        rhs.append(np.array([mass - X[6, 0]]))
+    if not allowImpulsive:
+        A = np.zeros((6, nz))
+        A[:, iv:iv + 6] = np.eye(6)
+        rows.append(A)
+        rhs.append(np.zeros(6))
+    A0 = np.vstack(rows)
+    b0 = np.concatenate(rhs)
+    scale_p = np.array([1 / P_BOUND, 1 / P_BOUND, 1 / step if step > 0 else 0.0])
+    best = None
+    for pat in [(a1, a2, a3) for a1 in (0, -1, 1) for a2 in (0, -1, 1) for a3 in (0, -1, 1)]:   # 0 free, -1 at lo, +1 at hi
+        act = [(j, sgn) for j, sgn in enumerate(pat) if sgn]
+        A, b = A0, b0
+        if act:
+            Ab = np.zeros((len(act), nz))
+            for r, (j, sgn) in enumerate(act):
+                Ab[r, ip + j] = 1.0
+            A = np.vstack([A0, Ab])
+            b = np.concatenate([b0, [lo[j] if sgn < 0 else hi[j] for j, sgn in act]])
+        m = A.shape[0]
+        K = np.zeros((nz + m, nz + m))
+        K[:nz, :nz] = np.diag(2.0 * Q)
+        K[:nz, nz:] = A.T
+        K[nz:, :nz] = A
+        r = np.concatenate([-2.0 * q, b])
+        D = np.ones(nz + m)
+        with np.errstate(all="ignore"):
+            for _ in range(20):
+                Ks = K * D[:, None] * D[None, :]
+                D = D / np.sqrt(np.maximum(np.abs(Ks).max(axis=1), 1e-300))
+        try:
+            sol = np.linalg.solve(K * D[:, None] * D[None, :], r * D) * D
+        except np.linalg.LinAlgError:
+            continue
+        if not np.all(np.isfinite(sol)):                  # singular for this active set (p undetermined)
+            continue
+        z, lam = sol[:nz], sol[nz:]
+        p = z[ip:ip + 3]
+        tol = 1e-12 * np.maximum(hi - lo, 1e-300)
+        if any(sgn == 0 and (p[j] < lo[j] - tol[j] or p[j] > hi[j] + tol[j]) for j, sgn in enumerate(pat)):
+            continue                                      # a free p outside its bounds
+        lam_b = lam[A0.shape[0]:]                         # row p_j = bound: lam >= 0 at the upper bound, <= 0 at the lower one
+        scale = 1e-9 * max(1.0, float(np.abs(2.0 * Q * z + 2.0 * q).max()))
+        if any(sgn * lb < -scale for (j, sgn), lb in zip(act, lam_b)):
+            continue
+        p = np.array([(lo[j] if sgn < 0 else hi[j]) if sgn else min(max(p[j], lo[j]), hi[j]) for j, sgn in enumerate(pat)])
+        dx = z[:ns * n].reshape(n, ns).T
+        du = z[iu:iv].reshape(n, 3).T
+        d1, d2 = (z[iv:iv + 3], z[iv + 3:iv + 6]) if allowImpulsive else (np.zeros(3), np.zeros(3))
+        cost = float(np.sum(w[None, :] * (U + du) ** 2) + c2 * (np.sum((dV1 + d1) ** 2) + np.sum((dV2 + d2) ** 2)) +
+                     β * (c0_norm / 2 * p[0] ** 2 + cf_norm / 2 * p[1] ** 2))
+        key = (cost, float(np.max(np.abs(p) * scale_p)))
+        if best is None or key < best[0]:
+            best = (key, (dx, du, d1, d2, float(p[0]), float(p[1]), float(p[2]), cost))
+    if best is None:
+        raise np.linalg.LinAlgError("direct_qp_dense_free_tf: no active set satisfies the optimality conditions")
+    return best[1]
+
+
 def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states,
-                            Xf_times, Xf_states, plot_yn, flagEnd, β, allowImpulsive, maxIter, ops=None, verbose=True):
+                            Xf_times, Xf_states, plot_yn, flagEnd, β, allowImpulsive, maxIter, ops=None, verbose=True, *, tf_step=0.0,
+                            tf_bounds=None):
     """Direct multiple shooting with frozen end points (direct.jl:58-594).  Returns the reference's tuple
     (X_all, u_all, τ1, τ2, t_TU, dV1, dV2, defect).
 
@@ -622,11 +753,33 @@ def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, 
     is kept in `multiShoot_CRTBP_direct.last` = {"status", "iterations", "history"} (0 converged, 1 maxIter, 2 NaN, 3 singular
     KKT system; history rows: max|defect|, cost, alpha (, τ1, τ2 with flagEnd)) -- the reference prints its progress and returns
     no flag.  flagEnd = true with an injected `ops` raises NotImplementedError: only the device path covers it (the mirror loop
-    with free ends is direct_loop_host)."""
+    with free ends is direct_loop_host).
+
+    tf_step (TU, keyword): 0 pins tf, as the reference does (`d = 0.`, :292).  With flagEnd and tf_step > 0 the time of flight is a
+    variable of the free iterations too (lto_direct_solve_free_tf): |tf_jump| <= tf_step per iteration, tf in tf_bounds = (tf_min,
+    tf_max) (default: one day past t0, 40 days), and the returned t_TU is the final grid; the history gains the row tf."""
     if flagEnd and ops is not None:
         raise NotImplementedError("multiShoot_CRTBP_direct: flagEnd = true runs on the device only (ops=None); the host mirror of "
                                   "the free-end loop is drivers.direct_loop_host")
     del plot_yn                                           # no plotting
+    if flagEnd and tf_step > 0:
+        X = np.array(X_all, dtype=np.float64, order="F")
+        t = np.array(t_TU, dtype=np.float64)
+        state_0, state_f = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU)
+        tg = hotpath.direct_targets(state_0, state_f, mass, dV1, dV2)
+        orbits = hotpath.DirectOrbits(X0_times, X0_states, Xf_times, Xf_states)
+        _, tf_min, tf_max = tf_bounds_default(t[0], TU)
+        if tf_bounds is not None:
+            tf_min, tf_max = tf_bounds
+        tb = hotpath.direct_tf_bounds(tf_step, tf_min, tf_max)
+        X, U, dV, t, defect, tau, status, iters, hist = hotpath.direct_solve_free_tf(
+            X, u_all, t, nsteps, MU, DU, TU, Isp, orbits, tg, [τ1, τ2], β, tb, True, allowImpulsive, int(maxIter))
+        if verbose:
+            for k in range(iters):
+                print("Iter %d. Max defect = %.2e. Cost = %.5f. tf = %.2f days. alpha = %.3f." % (
+                    k + 1, hist[0, k], hist[1, k], hist[5, k] * TU / day, hist[2, k]))
+        multiShoot_CRTBP_direct.last = {"status": status, "iterations": iters, "history": hist}
+        return X, U, float(tau[0]), float(tau[1]), t, dV[:3].copy(), dV[3:].copy(), defect
     if flagEnd:
         X = np.array(X_all, dtype=np.float64, order="F")
         state_0, state_f = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU)
@@ -664,11 +817,16 @@ def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, 
 
 
 def direct_loop_host(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times,
-                     Xf_states, flagEnd, β, allowImpulsive, maxIter, ops, verbose=True):
+                     Xf_states, flagEnd, β, allowImpulsive, maxIter, ops, verbose=True, *, tf_bounds=None):
     """The Python mirror of the multiShoot_CRTBP_direct loop (direct.jl:477-594) on an injected `ops` back end, the QP solved on
     the host: direct_qp_dense, or with flagEnd on odd iterations direct_qp_dense_free at the end model of the current τ
     (:521-526), followed by τ += alpha p (:564-565).  Returns ((X_all, u_all, τ1, τ2, t_TU, dV1, dV2, defect),
-    {"status", "iterations", "history"}) with history rows max|defect|, cost, alpha, τ1, τ2."""
+    {"status", "iterations", "history"}) with history rows max|defect|, cost, alpha, τ1, τ2.
+
+    tf_bounds = (step, tf_min, tf_max) (TU, keyword): None keeps tf pinned, as above.  Otherwise the history gains the row tf, and
+    with flagEnd and step > 0 the odd iterations also move tf: `ops.jacobian_tf(X, U, t, nsteps) -> (Jac_temp, dtf, defect)` gives
+    the tf column, direct_qp_dense_free_tf the step, and after the line search (on the current grid, :560) τ += alpha (p1, p2),
+    tf += alpha p3 (kept in [tf_min, tf_max]) and t = t0 + (τ_grid + 1) / 2 (tf - t0) (:567, :582)."""
     X = np.array(X_all, dtype=np.float64, order="F")
     U = np.array(u_all, dtype=np.float64, order="F")
     t = np.array(t_TU, dtype=np.float64)
@@ -680,21 +838,28 @@ def direct_loop_host(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes
     t0, tf = t[0], t[-1]
     tau = (t - t0) / (tf - t0) * 2 - 1                   # :480
     t_fixed = t0 + (tau + 1) / 2 * (tf - t0)              # t_TU_fixed (:321) = t after the first update (:582)
+    move_tf = tf_bounds is not None and flagEnd and float(tf_bounds[0]) > 0
     defect, _ = ops.defect(X, U, t, nsteps)               # :485
-    hist = np.full((5, max(maxIter, 1)), np.nan)
+    hist = np.full((5 if tf_bounds is None else 6, max(maxIter, 1)), np.nan)
     it, er, status = 0, 1.0, 0                            # er = 1.0: at least one step (:488)
     while er > 1e-6:                                      # :491 (NaN leaves the loop)
         it += 1
         if it > maxIter:
             it, status = maxIter, 1
             break
-        Jt, _ = ops.jacobian(X, U, t, nsteps)
-        p1 = p2 = 0.0
-        if flagEnd and it % 2 == 1:                       # free ends on odd iterations (:523-526)
+        p1 = p2 = p3 = 0.0
+        if move_tf and it % 2 == 1:                       # free ends and free tf (:503-516, :523-526)
+            Jt, dtf, _ = ops.jacobian_tf(X, U, t, nsteps)
+            s0, sf, g0, gf, c0n, cfn = end_model(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states)
+            x_up, u_up, dV1_up, dV2_up, p1, p2, p3, cost = direct_qp_dense_free_tf(
+                Jt, dtf, defect, X, U, t_fixed, s0, sf, g0, gf, c0n, cfn, β, mass, dV1, dV2, DU, TU, tf, tf_bounds, allowImpulsive)
+        elif flagEnd and it % 2 == 1:                     # free ends on odd iterations (:523-526)
+            Jt, _ = ops.jacobian(X, U, t, nsteps)
             s0, sf, g0, gf, c0n, cfn = end_model(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states)
             x_up, u_up, dV1_up, dV2_up, p1, p2, cost = direct_qp_dense_free(Jt, defect, X, U, t_fixed, s0, sf, g0, gf, c0n, cfn, β,
                                                                             mass, dV1, dV2, DU, TU, allowImpulsive)
         else:
+            Jt, _ = ops.jacobian(X, U, t, nsteps)
             state_0, state_f = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU)
             x_up, u_up, dV1_up, dV2_up, cost = direct_qp_dense(Jt, defect, X, U, t_fixed, state_0, state_f, mass, dV1, dV2, DU, TU,
                                                                allowImpulsive)
@@ -711,10 +876,13 @@ def direct_loop_host(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes
         if flagEnd and it % 2 == 1:
             τ1 = τ1 + p1 * alpha                          # :564-565, not wrapped
             τ2 = τ2 + p2 * alpha
+        if move_tf and it % 2 == 1:                       # :567, :582
+            tf = min(max(tf + p3 * alpha, float(tf_bounds[1])), float(tf_bounds[2]))
+            t_fixed = t0 + (tau + 1) / 2 * (tf - t0)
         t = t_fixed
         defect, _ = ops.defect(X, U, t, nsteps)           # :585
         er = float(np.abs(defect).max())
-        hist[:, it - 1] = (er, cost, alpha, τ1, τ2)
+        hist[:, it - 1] = (er, cost, alpha, τ1, τ2) if tf_bounds is None else (er, cost, alpha, τ1, τ2, tf)
         if verbose:
             print("Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f." % (it, er, cost, alpha))
     if status == 0 and not np.isfinite(er):

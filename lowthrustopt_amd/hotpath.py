@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from .constants import RK4, RKF78_FIXED, RKF78_ADAPTIVE, DOP853_ADAPTIVE  # noqa: F401
-from ._lib import LtoError, LtoIntegrator, LtoParams, LtoDirectParams, LtoDirectTargets, LtoDirectOrbits, LtoDirectEndModel, LTO_EINVAL
+from ._lib import LtoError, LtoIntegrator, LtoParams, LtoDirectParams, LtoDirectTargets, LtoDirectOrbits, LtoDirectEndModel, LtoDirectTfBounds, LTO_EINVAL
 
 
 def integrator(method=DOP853_ADAPTIVE, steps=0, rtol=1e-13, atol=1e-13, max_steps=0):
@@ -864,6 +864,89 @@ def direct_solve_free(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, orbits, targe
                                                   C.byref(ob.struct), C.cast(tg, C.c_void_p), ntgt, _ptr(ti), _ptr(bt),
                                                   1 if flagEnd else 0, 1 if allowImpulsive else 0, mi, _ptr(Xo), _ptr(Uo), _ptr(dV),
                                                   _ptr(to), _ptr(defect), _ptr(tau_o), _ptr(status), _ptr(iters), _ptr(hist)))
+    hist = hist[:, :mi]
+    if not batched:
+        return (Xo[:, :, 0], Uo[:, :, 0], dV[:, 0], to[:, 0], defect[:, :, 0], tau_o[:, 0], int(status[0]), int(iters[0]),
+                hist[:, :, 0])
+    return Xo, Uo, dV, to, defect, tau_o, status, iters, hist
+
+
+def direct_tf_bounds(step, tf_min, tf_max):
+    """lto_direct_tf_bounds (TU): |tf_jump| <= step per free iteration, tf_min <= tf <= tf_max (tf_min past t0)."""
+    return LtoDirectTfBounds(float(step), float(tf_min), float(tf_max))
+
+
+def _tf_bounds_array(tf_bounds, ntgt):
+    if isinstance(tf_bounds, LtoDirectTfBounds):
+        tf_bounds = [tf_bounds]
+    if len(tf_bounds) != ntgt:
+        raise ValueError("need as many tf bounds as targets")
+    return (LtoDirectTfBounds * ntgt)(*tf_bounds)
+
+
+def direct_qp_step_free_tf(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, models, beta, tf_bounds, allowImpulsive=False,
+                           ctx=None):
+    """One Jacobian sweep (with the tf column) and one free-end, FREE-TF QP step (lto_direct_qp_step_free_tf): as
+    direct_qp_step_free, with tf_bounds (lto_direct_tf_bounds, one or one per target); tf is the last entry of each grid.  Returns
+    (x_update, u_update, dV_update[6], p[3] = (p1; p2; tf_update), cost) -- with a trailing batch axis on a batched call."""
+    ctx = ctx or default_context()
+    X = _f64(X_all)
+    U = _f64(u_all)
+    ns, n, B, batched = _batch_dims(X)
+    t, ntg = _tgrids(t_TU, n, B)
+    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    tg, ntgt = _targets_array(targets)
+    if isinstance(models, LtoDirectEndModel):
+        models = [models]
+    if len(models) != ntgt:
+        raise ValueError("need as many end models as targets")
+    em = (LtoDirectEndModel * ntgt)(*models)
+    tb = _tf_bounds_array(tf_bounds, ntgt)
+    bt = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64).reshape(-1), (ntgt,)))
+    dX = np.zeros((ns, n, B), order="F")
+    dU = np.zeros((3, n, B), order="F")
+    dV = np.zeros((6, B), order="F")
+    p = np.zeros((3, B), order="F")
+    cost = np.zeros(B)
+    ctx.check(ctx.fn("direct_qp_step_free_tf")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
+                                                 C.cast(tg, C.c_void_p), C.cast(em, C.c_void_p), _ptr(bt), C.cast(tb, C.c_void_p), ntgt,
+                                                 1 if allowImpulsive else 0, _ptr(dX), _ptr(dU), _ptr(dV), _ptr(p), _ptr(cost)))
+    if not batched:
+        return dX[:, :, 0], dU[:, :, 0], dV[:, 0], p[:, 0], float(cost[0])
+    return dX, dU, dV, p, cost
+
+
+def direct_solve_free_tf(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, orbits, targets, tau, beta, tf_bounds, flagEnd=True,
+                         allowImpulsive=False, maxIter=100, ctx=None):
+    """The loop of multiShoot_CRTBP_direct with free end points AND a free time of flight (lto_direct_solve_free_tf_batch): as
+    direct_solve_free, with tf_bounds (one or one per target).  Returns (X_all, u_all, dV[6], t_TU (each trajectory's final grid),
+    defect, tau[2], status, iterations, history[6 x maxIter] = (max|defect|, cost, alpha, tau1, tau2, tf))."""
+    ctx = ctx or default_context()
+    X = _f64(X_all)
+    U = _f64(u_all)
+    ns, n, B, batched = _batch_dims(X)
+    t, ntg = _tgrids(t_TU, n, B)
+    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    ob = _orbits(orbits)
+    tg, ntgt = _targets_array(targets)
+    tb = _tf_bounds_array(tf_bounds, ntgt)
+    ti = np.asfortranarray(np.broadcast_to(np.asarray(tau, dtype=np.float64).reshape(2, -1), (2, B)))
+    bt = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64).reshape(-1), (ntgt,)))
+    mi = int(maxIter)
+    Xo = np.zeros((ns, n, B), order="F")
+    Uo = np.zeros((3, n, B), order="F")
+    dV = np.zeros((6, B), order="F")
+    to = np.zeros((n, B), order="F")
+    defect = np.zeros((ns, n - 1, B), order="F")
+    tau_o = np.zeros((2, B), order="F")
+    status = np.zeros(B, dtype=np.int32)
+    iters = np.zeros(B, dtype=np.int32)
+    hist = np.full((6, max(mi, 1), B), np.nan, order="F")
+    ctx.check(ctx.fn("direct_solve_free_tf_batch")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
+                                                     C.byref(ob.struct), C.cast(tg, C.c_void_p), ntgt, _ptr(ti), _ptr(bt),
+                                                     C.cast(tb, C.c_void_p), 1 if flagEnd else 0, 1 if allowImpulsive else 0, mi,
+                                                     _ptr(Xo), _ptr(Uo), _ptr(dV), _ptr(to), _ptr(defect), _ptr(tau_o), _ptr(status),
+                                                     _ptr(iters), _ptr(hist)))
     hist = hist[:, :mi]
     if not batched:
         return (Xo[:, :, 0], Uo[:, :, 0], dV[:, 0], to[:, 0], defect[:, :, 0], tau_o[:, 0], int(status[0]), int(iters[0]),

@@ -6,6 +6,7 @@ Prints one line per size: mean wall time of the Jacobian sweep and of the QP ste
 per-kernel times run it under `rocprofv3 --kernel-trace --stats -- python tools/time_direct_qp.py` (a run of its own).
 --free: the free-end step (flagEnd = true, lto_direct_qp_step_free) beside the frozen-end step, both through the host-pointer
 entries with the library's kernel timing (HIP events around the QP launches only): median over the repetitions.
+--free-tf: the same, with the free-end, free-tf step (lto_direct_qp_step_free_tf, 1-day step) timed beside the two.
 """
 import json
 import os
@@ -60,7 +61,7 @@ def run(S, reps=20, ns=6, nsteps=10):
     return out
 
 
-def run_free(S, reps=20, ns=6, nsteps=10):
+def run_free(S, reps=20, ns=6, nsteps=10, free_tf=False):
     n = S + 1
     X, U, T = synth.direct_problem(n, nstate=ns)
     X, U, t = X[:, :, 0], U[:, :, 0], T[:, 0]
@@ -71,6 +72,11 @@ def run_free(S, reps=20, ns=6, nsteps=10):
     out = {"segments": S}
     steps = (("frozen_qp_ms", lambda: lto.direct_qp_step(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, 2000.0, tg, ctx=ctx)),
              ("free_qp_ms", lambda: lto.direct_qp_step_free(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, 2000.0, tg, em, 1.0, ctx=ctx)))
+    if free_tf:
+        day = lto.day / lto.TU
+        tb = lto.direct_tf_bounds(day, t[0] + day, t[-1] + 10 * day)       # the synthetic grids run past 40 days
+        steps += (("free_tf_qp_ms", lambda: lto.direct_qp_step_free_tf(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, 2000.0, tg, em, 1.0, tb,
+                                                                       ctx=ctx)),)
     for name, f in steps:
         ms = []
         for k in range(reps + 3):
@@ -83,7 +89,8 @@ def run_free(S, reps=20, ns=6, nsteps=10):
 
 
 if __name__ == "__main__":
-    free = "--free" in sys.argv
-    sizes = [int(a) for a in sys.argv[1:] if a != "--free"] or [30, 4096, 16384]
+    free_tf = "--free-tf" in sys.argv
+    free = "--free" in sys.argv or free_tf
+    sizes = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or [30, 4096, 16384]
     for S in sizes:
-        print(json.dumps(run_free(S) if free else run(S)), flush=True)
+        print(json.dumps(run_free(S, free_tf=free_tf) if free else run(S)), flush=True)
