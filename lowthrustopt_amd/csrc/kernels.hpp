@@ -131,23 +131,21 @@ struct DirectQpArgs {
   double* dV;                      // [n_batch][6]: impulse updates at node 0 and node n-1
   double* cost;                    // [n_batch]
   double* singular;                // [n_batch] or null: 1.0 where the trajectory's KKT system is singular
-  // free ends only (launch_direct_qp_free)
+  // free ends only (nr = 3 or 4)
   const double* model;             // [n_batch][14] (lto_direct_end_model): g0[6], gf[6], |c0|, |cf|
   const double* beta;              // [n_batch]
-  double* p;                       // [n_batch][2]: the phase updates p1, p2 ([n_batch][3] with p3 = tf_jump: launch_direct_qp_free_tf)
-  // free time of flight only (launch_direct_qp_free_tf)
+  double* p;                       // [n_batch][2]: the phase updates p1, p2 ([n_batch][3] with p3 = tf_jump: nr = 4)
+  // free time of flight only (nr = 4)
   const double* dtf;               // [nstate][ldd]: d defect / d tf
   const double* tfb;               // [n_batch][3]: step, tf_min, tf_max
   const double* tf;                // [n_batch]: current tf
 };
-// workspace of either step: nr = 1 (frozen ends) or 3 (free ends: three right-hand sides)
+// workspace of the step with nr right-hand sides (1, 3 or 4)
 size_t direct_qp_workspace_bytes(int nstate, int n_nodes, int n_batch, int nr);
 int* direct_qp_status(void* workspace, int n_batch);   // [n_batch] inside the workspace: 1 = singular
-hipError_t launch_direct_qp(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st);
-// free ends (flagEnd = true): the same reduction with the right-hand sides z0 | dz/dp1 | dz/dp2, then the 2 x 2 box QP in p
-hipError_t launch_direct_qp_free(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st);
-// free ends and free tf: right-hand sides z0 | dz/dp1 | dz/dp2 | dz/dp3, then the 3 x 3 box QP in p
-hipError_t launch_direct_qp_free_tf(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st);
+// nr right-hand sides: 1 frozen ends; 3 free ends (flagEnd = true): z0 | dz/dp1 | dz/dp2, then the 2 x 2 box QP in p; 4 free ends
+// and free tf: z0 | dz/dp1 | dz/dp2 | dz/dp3, then the 3 x 3 box QP in p.  Any other nr: hipErrorInvalidValue.
+hipError_t launch_direct_qp(int nstate, int nr, const DirectQpArgs& q, void* workspace, hipStream_t st);
 hipError_t launch_direct_qp_update_dv(double* targets, const double* dV, const double* step, int n_batch, hipStream_t st);
 // the two orbit tables of the free-end model on the device: times [n], states and natural-spline second derivatives [n][6]
 struct EndOrbitsDev { int n[2]; const double* t[2]; const double* Y[2]; const double* M[2]; };

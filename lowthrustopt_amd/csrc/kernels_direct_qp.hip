@@ -859,14 +859,13 @@ hipError_t launch_direct_qp_update_dv(double* targets, const double* dV, const d
   return hipGetLastError();
 }
 
-hipError_t launch_direct_qp(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st) {
-  return (nstate == 7) ? direct_qp_impl<7, 1>(q, workspace, st) : direct_qp_impl<6, 1>(q, workspace, st);
-}
-hipError_t launch_direct_qp_free(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st) {
-  return (nstate == 7) ? direct_qp_impl<7, 3>(q, workspace, st) : direct_qp_impl<6, 3>(q, workspace, st);
-}
-hipError_t launch_direct_qp_free_tf(int nstate, const DirectQpArgs& q, void* workspace, hipStream_t st) {
-  return (nstate == 7) ? direct_qp_impl<7, 4>(q, workspace, st) : direct_qp_impl<6, 4>(q, workspace, st);
+hipError_t launch_direct_qp(int nstate, int nr, const DirectQpArgs& q, void* workspace, hipStream_t st) {
+  switch (nr) {
+    case 1: return (nstate == 7) ? direct_qp_impl<7, 1>(q, workspace, st) : direct_qp_impl<6, 1>(q, workspace, st);
+    case 3: return (nstate == 7) ? direct_qp_impl<7, 3>(q, workspace, st) : direct_qp_impl<6, 3>(q, workspace, st);
+    case 4: return (nstate == 7) ? direct_qp_impl<7, 4>(q, workspace, st) : direct_qp_impl<6, 4>(q, workspace, st);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace lto

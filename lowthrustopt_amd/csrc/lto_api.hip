@@ -1555,7 +1555,8 @@ static void direct_plan_free(lto_direct_plan* p) {
   delete p;
 }
 
-// the QP workspace for nr right-hand sides (1: frozen ends, 3: free ends); a frozen-end workspace grows at the first free step
+// the QP workspace for nr right-hand sides (1: frozen ends, 3: free ends, 4: free ends and free tf); a smaller workspace grows at
+// the first step that needs more
 static int direct_qp_workspace(lto_direct_plan* p, int nr) {
   if (p->qp_ws && p->qp_ws_nr >= nr) return LTO_OK;
   if (p->qp_ws) { (void)hipFree(p->qp_ws); p->qp_ws = nullptr; }
@@ -2097,20 +2098,17 @@ int lto_direct_midpoints(lto_ctx* c, int nstate, int n_nodes, int n_batch, const
 
 
 /* ------------------------------------------------------------------------------ direct QP step and solve loop */
-int lto_direct_qp_step_dev(lto_direct_plan* p, void* stream, const double* Jac, long ldj, const double* defect, long ldd,
-                           const double* X, long ldx, const double* U, long ldu, const double* t, int n_tgrids,
-                           const lto_direct_targets* targets, int allow_impulsive, double* dX, double* dU, double* dV,
-                           double* cost) {
-  if (!p) return LTO_ENULL;
+// the QP step on device operands (kernels_direct_qp.hip) with nr right-hand sides: 1 frozen ends; 3 free ends (flagEnd = true,
+// DESIGN 4.8c) with the end models and beta of every trajectory and the phase updates p [n_batch][2]; 4 free ends and free tf
+// (DESIGN 4.8e), also with the sweep's tf column dtf [nstate][ldd], tfb [n_batch][3], tf [n_batch], and p [n_batch][3].  The
+// operands of a variant other than nr's are not passed on.
+static int direct_qp_launch(lto_direct_plan* p, hipStream_t st, int nr, const double* Jac, long ldj, const double* defect, long ldd,
+                            const double* X, long ldx, const double* U, long ldu, const double* t, int n_tgrids,
+                            const lto_direct_targets* targets, int allow_impulsive, double* dX, double* dU, double* dV, double* cost,
+                            const lto_direct_end_model* model = nullptr, const double* beta = nullptr, double* pout = nullptr,
+                            const double* dtf = nullptr, const double* tfb = nullptr, const double* tf = nullptr) {
   lto_ctx* c = p->ctx;
-  if (!Jac || !defect || !X || !U || !t || !targets || !dX || !dU || !dV || !cost)
-    return set_err(c, LTO_ENULL, "lto_direct_qp_step_dev: a required array is NULL");
-  const long J = (long)p->n_nodes * p->n_batch;
-  if (ldj < p->S || ldd < p->S || ldx < J || ldu < J) return set_err(c, LTO_EINVAL, "ldj/ldd smaller than the segment count or ldx/ldu than the node count");
-  if (n_tgrids != 1 && n_tgrids != p->n_batch) return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch");
-  int rc = bind_device(c);
-  if (rc) return rc;
-  rc = direct_qp_workspace(p, 1);
+  const int rc = direct_qp_workspace(p, nr);
   if (rc) return rc;
   DirectQpArgs q;
   std::memset(&q, 0, sizeof q);
@@ -2122,72 +2120,34 @@ int lto_direct_qp_step_dev(lto_direct_plan* p, void* stream, const double* Jac, 
   q.c2 = vu * vu;
   q.dX = dX; q.ldX = ldx; q.dU = dU; q.ldU = ldu; q.dV = dV; q.cost = cost;
   q.singular = p->qp_singular_out;
-  hipStream_t st = (hipStream_t)stream;
+  if (nr > 1) { q.model = (const double*)model; q.beta = beta; q.p = pout; }
+  if (nr == 4) { q.dtf = dtf; q.tfb = tfb; q.tf = tf; }
   timing_begin(c, st);
-  const hipError_t e = launch_direct_qp(p->nstate, q, p->qp_ws, st);
+  const hipError_t e = launch_direct_qp(p->nstate, nr, q, p->qp_ws, st);
   timing_end(c, st);
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_direct_qp", e);
   return LTO_OK;
 }
 
+int lto_direct_qp_step_dev(lto_direct_plan* p, void* stream, const double* Jac, long ldj, const double* defect, long ldd,
+                           const double* X, long ldx, const double* U, long ldu, const double* t, int n_tgrids,
+                           const lto_direct_targets* targets, int allow_impulsive, double* dX, double* dU, double* dV,
+                           double* cost) {
+  if (!p) return LTO_ENULL;
+  lto_ctx* c = p->ctx;
+  if (!Jac || !defect || !X || !U || !t || !targets || !dX || !dU || !dV || !cost)
+    return set_err(c, LTO_ENULL, "lto_direct_qp_step_dev: a required array is NULL");
+  const long J = (long)p->n_nodes * p->n_batch;
+  if (ldj < p->S || ldd < p->S || ldx < J || ldu < J) return set_err(c, LTO_EINVAL, "ldj/ldd smaller than the segment count or ldx/ldu than the node count");
+  if (n_tgrids != 1 && n_tgrids != p->n_batch) return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch");
+  const int rc = bind_device(c);
+  if (rc) return rc;
+  return direct_qp_launch(p, (hipStream_t)stream, 1, Jac, ldj, defect, ldd, X, ldx, U, ldu, t, n_tgrids, targets, allow_impulsive, dX,
+                          dU, dV, cost);
+}
+
 const int* lto_direct_plan_qp_status(const lto_direct_plan* p) {
   return (p && p->qp_ws) ? direct_qp_status(p->qp_ws, p->n_batch) : nullptr;
-}
-
-// free ends (flagEnd = true): the QP step with the phase updates p1, p2 in +-0.1 (kernels_direct_qp.hip).  model and
-// beta are device arrays of n_batch lto_direct_end_model / doubles; p [n_batch][2] (device).
-static int direct_qp_step_free_dev(lto_direct_plan* p, hipStream_t st, const double* Jac, long ldj, const double* defect, long ldd,
-                                   const double* X, long ldx, const double* U, long ldu, const double* t, int n_tgrids,
-                                   const lto_direct_targets* targets, const lto_direct_end_model* model, const double* beta,
-                                   int allow_impulsive, double* dX, double* dU, double* dV, double* pout, double* cost) {
-  lto_ctx* c = p->ctx;
-  int rc = direct_qp_workspace(p, 3);
-  if (rc) return rc;
-  DirectQpArgs q;
-  std::memset(&q, 0, sizeof q);
-  q.n_nodes = p->n_nodes; q.n_batch = p->n_batch;
-  q.Jac = Jac; q.ldj = ldj; q.defect = defect; q.ldd = ldd; q.X = X; q.ldx = ldx; q.U = U; q.ldu = ldu;
-  q.t = t; q.t_stride = (n_tgrids == 1) ? 0 : p->n_nodes;
-  q.targets = (const double*)targets; q.impulsive = allow_impulsive ? 1 : 0;
-  const double vu = p->prm.DU / p->prm.TU;
-  q.c2 = vu * vu;
-  q.dX = dX; q.ldX = ldx; q.dU = dU; q.ldU = ldu; q.dV = dV; q.cost = cost;
-  q.singular = p->qp_singular_out;
-  q.model = (const double*)model; q.beta = beta; q.p = pout;
-  timing_begin(c, st);
-  const hipError_t e = launch_direct_qp_free(p->nstate, q, p->qp_ws, st);
-  timing_end(c, st);
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_direct_qp_free", e);
-  return LTO_OK;
-}
-
-// free ends and free tf: the free-end step with p3 = tf_jump; dtf the sweep's tf column [nstate][ldd], tfb [n_batch][3]
-// and tf [n_batch] device arrays; p [n_batch][3] (device).
-static int direct_qp_step_free_tf_dev(lto_direct_plan* p, hipStream_t st, const double* Jac, long ldj, const double* dtf,
-                                      const double* defect, long ldd, const double* X, long ldx, const double* U, long ldu,
-                                      const double* t, int n_tgrids, const lto_direct_targets* targets, const lto_direct_end_model* model,
-                                      const double* beta, const double* tfb, const double* tf, int allow_impulsive, double* dX,
-                                      double* dU, double* dV, double* pout, double* cost) {
-  lto_ctx* c = p->ctx;
-  int rc = direct_qp_workspace(p, 4);
-  if (rc) return rc;
-  DirectQpArgs q;
-  std::memset(&q, 0, sizeof q);
-  q.n_nodes = p->n_nodes; q.n_batch = p->n_batch;
-  q.Jac = Jac; q.ldj = ldj; q.defect = defect; q.ldd = ldd; q.X = X; q.ldx = ldx; q.U = U; q.ldu = ldu;
-  q.t = t; q.t_stride = (n_tgrids == 1) ? 0 : p->n_nodes;
-  q.targets = (const double*)targets; q.impulsive = allow_impulsive ? 1 : 0;
-  const double vu = p->prm.DU / p->prm.TU;
-  q.c2 = vu * vu;
-  q.dX = dX; q.ldX = ldx; q.dU = dU; q.ldU = ldu; q.dV = dV; q.cost = cost;
-  q.singular = p->qp_singular_out;
-  q.model = (const double*)model; q.beta = beta; q.p = pout;
-  q.dtf = dtf; q.tfb = tfb; q.tf = tf;
-  timing_begin(c, st);
-  const hipError_t e = launch_direct_qp_free_tf(p->nstate, q, p->qp_ws, st);
-  timing_end(c, st);
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_direct_qp_free_tf", e);
-  return LTO_OK;
 }
 
 // the argument rules of a free tf, per trajectory b (bounds tfb[n_targets == 1 ? 0 : b], grid n_tgrids == 1 ? 0 : b): step >= 0,
@@ -2205,6 +2165,22 @@ static int tf_bounds_check(lto_ctx* c, const lto_direct_tf_bounds* tfb, int n_ta
     if (why) return c ? set_err(c, LTO_EINVAL, why) : LTO_EINVAL;
   }
   return LTO_OK;
+}
+
+// the checks the direct QP-step and solve entries share, in their order: the shape, and for a free tf (free_tf) the counts and the tf
+// bounds (given t and tfb), answer without a context, so without a device; then the context.  The entry checks its arrays next.
+static int direct_entry_check(lto_ctx* c, int nstate, int n_nodes, int n_batch, int n_tgrids, int n_targets, bool free_tf,
+                              const double* t, const lto_direct_tf_bounds* tfb) {
+  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
+  if (free_tf) {
+    if ((n_targets != 1 && n_targets != n_batch) || (n_tgrids != 1 && n_tgrids != n_batch))
+      return c ? set_err(c, LTO_EINVAL, "n_targets / n_tgrids must be 1 or n_batch") : LTO_EINVAL;
+    if (t && tfb) {
+      const int rc = tf_bounds_check(c, tfb, n_targets, t, n_tgrids, n_nodes, n_batch);
+      if (rc) return rc;
+    }
+  }
+  return c ? LTO_OK : LTO_ENULL;
 }
 
 // the two orbit tables on the device with the natural-spline second derivatives (a tridiagonal solve on the host, once per call)
@@ -2302,29 +2278,53 @@ static bool direct_targets_expand(const lto_direct_targets* targets, int n_targe
   return true;
 }
 
-int lto_direct_qp_step(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
-                       int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets, int n_targets,
-                       int allow_impulsive, double* dX, double* dU, double* dV, double* cost) {
-  // shape checks first, so that they answer without a device (a context needs one)
-  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
-  if (!c) return LTO_ENULL;
-  if (!X || !U || !t || !prm || !targets || !dX || !dU || !dV || !cost) return set_err(c, LTO_ENULL, "lto_direct_qp_step: a required array is NULL");
-  if (n_targets != 1 && n_targets != n_batch) return set_err(c, LTO_EINVAL, "n_targets must be 1 or n_batch");
+// one Jacobian sweep and one QP step on host arrays with nr right-hand sides (direct_qp_launch): model and beta for nr > 1, tfb for
+// nr = 4, one or one per target; p_out [n_batch][nr - 1] for nr > 1.  tf is each grid's last entry.
+static int direct_qp_step_host(lto_ctx* c, const char* who, int nr, int nstate, int n_nodes, int n_batch, const double* X,
+                               const double* U, const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm,
+                               const lto_direct_targets* targets, const lto_direct_end_model* model, const double* beta,
+                               const lto_direct_tf_bounds* tfb, int n_targets, int allow_impulsive, double* dX, double* dU, double* dV,
+                               double* p_out, double* cost) {
+  int rc = direct_entry_check(c, nstate, n_nodes, n_batch, n_tgrids, n_targets, nr == 4, t, tfb);
+  if (rc) return rc;
+  char msg[96];
+  if (!X || !U || !t || !prm || !targets || !dX || !dU || !dV || !cost || (nr > 1 && (!model || !beta || !p_out)) || (nr == 4 && !tfb)) {
+    std::snprintf(msg, sizeof msg, "%s: a required array is NULL", who);
+    return set_err(c, LTO_ENULL, msg);
+  }
+  if ((n_targets != 1 && n_targets != n_batch) || (n_tgrids != 1 && n_tgrids != n_batch))
+    return set_err(c, LTO_EINVAL, "n_targets / n_tgrids must be 1 or n_batch");
   CallTimer call_timer(c);
   lto_direct_plan* p = nullptr;
-  int rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &p);
+  rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &p);
   if (rc) return rc;
-  if (n_tgrids != 1 && n_tgrids != n_batch) { delete p; return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch"); }
+  const int B = n_batch;
+  const size_t nh = nr == 4 ? 5 * (size_t)B : nr == 3 ? (size_t)B : 0;   // beta [B] (| tf bounds [B][3] | tf [B])
   lto::HostBuf<lto_direct_targets> tg;
-  lto::HostBuf<int> h_stat(n_batch, 0);
-  if (!direct_targets_expand(targets, n_targets, n_batch, tg) || !h_stat.ok()) { delete p; return set_err(c, LTO_ENOMEM, "lto_direct_qp_step: out of host memory"); }
-  const long J = (long)n_nodes * n_batch, S = p->S;
+  lto::HostBuf<lto_direct_end_model> em(nr > 1 ? (size_t)B : 0);
+  lto::HostBuf<double> hb(nh);
+  lto::HostBuf<int> h_stat(B, 0);
+  if (!direct_targets_expand(targets, n_targets, B, tg) || !em.ok() || !hb.ok() || !h_stat.ok()) {
+    direct_plan_free(p);
+    std::snprintf(msg, sizeof msg, "%s: out of host memory", who);
+    return set_err(c, LTO_ENOMEM, msg);
+  }
+  for (int b = 0; b < B && nr > 1; ++b) {
+    const int k = n_targets == 1 ? 0 : b;
+    em[b] = model[k]; hb[b] = beta[k];
+    if (nr == 4) {
+      hb[B + 3 * b] = tfb[k].step; hb[B + 3 * b + 1] = tfb[k].tf_min; hb[B + 3 * b + 2] = tfb[k].tf_max;
+      hb[4 * (size_t)B + b] = t[(size_t)(n_tgrids == 1 ? 0 : b) * n_nodes + n_nodes - 1];
+    }
+  }
+  const long J = (long)n_nodes * B, S = p->S;
   const int nj = nstate * 2 * (nstate + 3);
   const size_t need = al256(sizeof(double) * nstate * J) * 4 + al256(sizeof(double) * 3 * J) * 4 + al256(sizeof(double) * n_nodes * n_tgrids) +
-                      al256(sizeof(double) * nj * S) + al256(sizeof(double) * nstate * S) + al256(sizeof(lto_direct_targets) * n_batch) +
-                      al256(sizeof(double) * 7 * n_batch) * 2 + 8192;
+                      al256(sizeof(double) * nj * S) + al256(sizeof(double) * nstate * S) * (nr == 4 ? 2 : 1) +
+                      al256(sizeof(lto_direct_targets) * B) + al256(sizeof(lto_direct_end_model) * em.size()) +
+                      al256(sizeof(double) * 7 * B) * 3 + al256(sizeof(double) * nh) + 8192;
   rc = arena_reserve(c, need);
-  if (rc) { delete p; return rc; }
+  if (rc) { direct_plan_free(p); return rc; }
   c->arena_top = 0;
   double* d_xa = arena_take<double>(c, (size_t)nstate * J);
   double* d_X = arena_take<double>(c, (size_t)nstate * J);
@@ -2337,199 +2337,64 @@ int lto_direct_qp_step(lto_ctx* c, int nstate, int n_nodes, int n_batch, const d
   double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
   double* d_jac = arena_take<double>(c, (size_t)nj * S);
   double* d_def = arena_take<double>(c, (size_t)nstate * S);
-  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)n_batch);
-  double* d_dV = arena_take<double>(c, (size_t)7 * n_batch);
-  double* d_cost = arena_take<double>(c, (size_t)7 * n_batch);
+  double* d_dtf = nr == 4 ? arena_take<double>(c, (size_t)nstate * S) : nullptr;
+  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)B);
+  lto_direct_end_model* d_em = arena_take<lto_direct_end_model>(c, em.size());
+  double* d_dV = arena_take<double>(c, (size_t)7 * B);
+  double* d_cost = arena_take<double>(c, (size_t)7 * B);
+  double* d_p = arena_take<double>(c, (size_t)7 * B);
+  double* d_hb = arena_take<double>(c, nh);
   hipStream_t st = c->stream;
   hipError_t e = stage_in(c, X, nstate, J, d_xa, d_X, J, st);
   if (e == hipSuccess) e = stage_in(c, U, 3, J, d_ua, d_U, J, st);
   if (e == hipSuccess) e = vec_in(c, t, (long)n_nodes * n_tgrids, d_t, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * n_batch, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) { (void)hipStreamSynchronize(st); delete p; return set_err(c, LTO_EHIP, "stage in", e); }
-  rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, d_t, n_tgrids, d_jac, S, nullptr, d_def, S, nullptr);
-  if (rc == LTO_OK) rc = lto_direct_qp_step_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t, n_tgrids, d_tg, allow_impulsive, d_dX, d_dU, d_dV, d_cost);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * B, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && nr > 1) e = hipMemcpyAsync(d_em, em.data(), sizeof(lto_direct_end_model) * B, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && nr > 1) e = hipMemcpyAsync(d_hb, hb.data(), sizeof(double) * nh, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { (void)hipStreamSynchronize(st); direct_plan_free(p); return set_err(c, LTO_EHIP, "stage in", e); }
+  rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, d_t, n_tgrids, d_jac, S, d_dtf, d_def, S, nullptr);
+  if (rc == LTO_OK)
+    rc = direct_qp_launch(p, st, nr, d_jac, S, d_def, S, d_X, J, d_U, J, d_t, n_tgrids, d_tg, allow_impulsive, d_dX, d_dU, d_dV, d_cost,
+                          d_em, d_hb, d_p, d_dtf, d_hb + B, d_hb + 4 * (size_t)B);
   if (rc == LTO_OK) {
     e = stage_out(c, d_dX, J, nstate, J, d_dXa, dX, st);
     if (e == hipSuccess) e = stage_out(c, d_dU, J, 3, J, d_dUa, dU, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dV, d_dV, sizeof(double) * 6 * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_stat.data(), lto_direct_plan_qp_status(p), sizeof(int) * n_batch, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dV, d_dV, sizeof(double) * 6 * B, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && nr > 1) e = hipMemcpyAsync(p_out, d_p, sizeof(double) * (nr - 1) * B, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * B, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_stat.data(), lto_direct_plan_qp_status(p), sizeof(int) * B, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = stream_wait(st);
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
-    for (int b = 0; b < n_batch && rc == LTO_OK; ++b)
+    for (int b = 0; b < B && rc == LTO_OK; ++b)
       if (h_stat[b]) rc = set_err(c, LTO_ESINGULAR, "the KKT system of a trajectory's QP step is singular (too few nodes to reach the terminal state?)");
   } else {
     (void)hipStreamSynchronize(st);
   }
   direct_plan_free(p);
   return rc;
+}
+
+int lto_direct_qp_step(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
+                       int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets, int n_targets,
+                       int allow_impulsive, double* dX, double* dU, double* dV, double* cost) {
+  return direct_qp_step_host(c, "lto_direct_qp_step", 1, nstate, n_nodes, n_batch, X, U, t, n_tgrids, nsteps, prm, targets, nullptr,
+                             nullptr, nullptr, n_targets, allow_impulsive, dX, dU, dV, nullptr, cost);
 }
 
 int lto_direct_qp_step_free(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
                             int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets,
                             const lto_direct_end_model* model, const double* beta, int n_targets, int allow_impulsive, double* dX,
                             double* dU, double* dV, double* p_out, double* cost) {
-  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
-  if (!c) return LTO_ENULL;
-  if (!X || !U || !t || !prm || !targets || !model || !beta || !dX || !dU || !dV || !p_out || !cost)
-    return set_err(c, LTO_ENULL, "lto_direct_qp_step_free: a required array is NULL");
-  if (n_targets != 1 && n_targets != n_batch) return set_err(c, LTO_EINVAL, "n_targets must be 1 or n_batch");
-  if (n_tgrids != 1 && n_tgrids != n_batch) return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch");
-  CallTimer call_timer(c);
-  lto_direct_plan* p = nullptr;
-  int rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &p);
-  if (rc) return rc;
-  lto::HostBuf<lto_direct_targets> tg;
-  lto::HostBuf<lto_direct_end_model> em(n_batch);
-  lto::HostBuf<double> hb(n_batch);
-  lto::HostBuf<int> h_stat(n_batch, 0);
-  if (!direct_targets_expand(targets, n_targets, n_batch, tg) || !em.ok() || !hb.ok() || !h_stat.ok()) {
-    delete p;
-    return set_err(c, LTO_ENOMEM, "lto_direct_qp_step_free: out of host memory");
-  }
-  for (int b = 0; b < n_batch; ++b) { em[b] = model[n_targets == 1 ? 0 : b]; hb[b] = beta[n_targets == 1 ? 0 : b]; }
-  const long J = (long)n_nodes * n_batch, S = p->S;
-  const int nj = nstate * 2 * (nstate + 3);
-  const size_t need = al256(sizeof(double) * nstate * J) * 4 + al256(sizeof(double) * 3 * J) * 4 + al256(sizeof(double) * n_nodes * n_tgrids) +
-                      al256(sizeof(double) * nj * S) + al256(sizeof(double) * nstate * S) + al256(sizeof(lto_direct_targets) * n_batch) +
-                      al256(sizeof(lto_direct_end_model) * n_batch) + al256(sizeof(double) * 7 * n_batch) * 4 + 8192;
-  rc = arena_reserve(c, need);
-  if (rc) { delete p; return rc; }
-  c->arena_top = 0;
-  double* d_xa = arena_take<double>(c, (size_t)nstate * J);
-  double* d_X = arena_take<double>(c, (size_t)nstate * J);
-  double* d_dX = arena_take<double>(c, (size_t)nstate * J);
-  double* d_dXa = arena_take<double>(c, (size_t)nstate * J);
-  double* d_ua = arena_take<double>(c, (size_t)3 * J);
-  double* d_U = arena_take<double>(c, (size_t)3 * J);
-  double* d_dU = arena_take<double>(c, (size_t)3 * J);
-  double* d_dUa = arena_take<double>(c, (size_t)3 * J);
-  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
-  double* d_jac = arena_take<double>(c, (size_t)nj * S);
-  double* d_def = arena_take<double>(c, (size_t)nstate * S);
-  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)n_batch);
-  lto_direct_end_model* d_em = arena_take<lto_direct_end_model>(c, (size_t)n_batch);
-  double* d_dV = arena_take<double>(c, (size_t)7 * n_batch);
-  double* d_cost = arena_take<double>(c, (size_t)7 * n_batch);
-  double* d_beta = arena_take<double>(c, (size_t)7 * n_batch);
-  double* d_p = arena_take<double>(c, (size_t)7 * n_batch);
-  hipStream_t st = c->stream;
-  hipError_t e = stage_in(c, X, nstate, J, d_xa, d_X, J, st);
-  if (e == hipSuccess) e = stage_in(c, U, 3, J, d_ua, d_U, J, st);
-  if (e == hipSuccess) e = vec_in(c, t, (long)n_nodes * n_tgrids, d_t, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * n_batch, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_em, em.data(), sizeof(lto_direct_end_model) * n_batch, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_beta, hb.data(), sizeof(double) * n_batch, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) { (void)hipStreamSynchronize(st); delete p; return set_err(c, LTO_EHIP, "stage in", e); }
-  rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, d_t, n_tgrids, d_jac, S, nullptr, d_def, S, nullptr);
-  if (rc == LTO_OK)
-    rc = direct_qp_step_free_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t, n_tgrids, d_tg, d_em, d_beta, allow_impulsive, d_dX, d_dU,
-                                 d_dV, d_p, d_cost);
-  if (rc == LTO_OK) {
-    e = stage_out(c, d_dX, J, nstate, J, d_dXa, dX, st);
-    if (e == hipSuccess) e = stage_out(c, d_dU, J, 3, J, d_dUa, dU, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dV, d_dV, sizeof(double) * 6 * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(p_out, d_p, sizeof(double) * 2 * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_stat.data(), lto_direct_plan_qp_status(p), sizeof(int) * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = stream_wait(st);
-    if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
-    for (int b = 0; b < n_batch && rc == LTO_OK; ++b)
-      if (h_stat[b]) rc = set_err(c, LTO_ESINGULAR, "the KKT system of a trajectory's QP step is singular (too few nodes to reach the terminal state?)");
-  } else {
-    (void)hipStreamSynchronize(st);
-  }
-  direct_plan_free(p);
-  return rc;
+  return direct_qp_step_host(c, "lto_direct_qp_step_free", 3, nstate, n_nodes, n_batch, X, U, t, n_tgrids, nsteps, prm, targets, model,
+                             beta, nullptr, n_targets, allow_impulsive, dX, dU, dV, p_out, cost);
 }
 
 int lto_direct_qp_step_free_tf(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
                                int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets,
                                const lto_direct_end_model* model, const double* beta, const lto_direct_tf_bounds* tfb, int n_targets,
                                int allow_impulsive, double* dX, double* dU, double* dV, double* p_out, double* cost) {
-  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
-  if ((n_targets != 1 && n_targets != n_batch) || (n_tgrids != 1 && n_tgrids != n_batch))
-    return c ? set_err(c, LTO_EINVAL, "n_targets / n_tgrids must be 1 or n_batch") : LTO_EINVAL;
-  if (t && tfb) {
-    const int rc0 = tf_bounds_check(c, tfb, n_targets, t, n_tgrids, n_nodes, n_batch);
-    if (rc0) return rc0;
-  }
-  if (!c) return LTO_ENULL;
-  if (!X || !U || !t || !prm || !targets || !model || !beta || !tfb || !dX || !dU || !dV || !p_out || !cost)
-    return set_err(c, LTO_ENULL, "lto_direct_qp_step_free_tf: a required array is NULL");
-  CallTimer call_timer(c);
-  lto_direct_plan* p = nullptr;
-  int rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &p);
-  if (rc) return rc;
-  lto::HostBuf<lto_direct_targets> tg;
-  lto::HostBuf<lto_direct_end_model> em(n_batch);
-  lto::HostBuf<double> hb((size_t)5 * n_batch);           // beta [B] | tf bounds [B][3] | tf [B]
-  lto::HostBuf<int> h_stat(n_batch, 0);
-  if (!direct_targets_expand(targets, n_targets, n_batch, tg) || !em.ok() || !hb.ok() || !h_stat.ok()) {
-    delete p;
-    return set_err(c, LTO_ENOMEM, "lto_direct_qp_step_free_tf: out of host memory");
-  }
-  for (int b = 0; b < n_batch; ++b) {
-    const int k = n_targets == 1 ? 0 : b;
-    em[b] = model[k]; hb[b] = beta[k];
-    hb[n_batch + 3 * b] = tfb[k].step; hb[n_batch + 3 * b + 1] = tfb[k].tf_min; hb[n_batch + 3 * b + 2] = tfb[k].tf_max;
-    hb[4 * (size_t)n_batch + b] = t[(size_t)(n_tgrids == 1 ? 0 : b) * n_nodes + n_nodes - 1];
-  }
-  const long J = (long)n_nodes * n_batch, S = p->S;
-  const int nj = nstate * 2 * (nstate + 3);
-  const size_t need = al256(sizeof(double) * nstate * J) * 4 + al256(sizeof(double) * 3 * J) * 4 + al256(sizeof(double) * n_nodes * n_tgrids) +
-                      al256(sizeof(double) * nj * S) + al256(sizeof(double) * nstate * S) * 2 + al256(sizeof(lto_direct_targets) * n_batch) +
-                      al256(sizeof(lto_direct_end_model) * n_batch) + al256(sizeof(double) * 7 * n_batch) * 3 +
-                      al256(sizeof(double) * 5 * n_batch) + 8192;
-  rc = arena_reserve(c, need);
-  if (rc) { delete p; return rc; }
-  c->arena_top = 0;
-  double* d_xa = arena_take<double>(c, (size_t)nstate * J);
-  double* d_X = arena_take<double>(c, (size_t)nstate * J);
-  double* d_dX = arena_take<double>(c, (size_t)nstate * J);
-  double* d_dXa = arena_take<double>(c, (size_t)nstate * J);
-  double* d_ua = arena_take<double>(c, (size_t)3 * J);
-  double* d_U = arena_take<double>(c, (size_t)3 * J);
-  double* d_dU = arena_take<double>(c, (size_t)3 * J);
-  double* d_dUa = arena_take<double>(c, (size_t)3 * J);
-  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
-  double* d_jac = arena_take<double>(c, (size_t)nj * S);
-  double* d_def = arena_take<double>(c, (size_t)nstate * S);
-  double* d_dtf = arena_take<double>(c, (size_t)nstate * S);
-  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)n_batch);
-  lto_direct_end_model* d_em = arena_take<lto_direct_end_model>(c, (size_t)n_batch);
-  double* d_dV = arena_take<double>(c, (size_t)7 * n_batch);
-  double* d_cost = arena_take<double>(c, (size_t)7 * n_batch);
-  double* d_p = arena_take<double>(c, (size_t)7 * n_batch);
-  double* d_hb = arena_take<double>(c, (size_t)5 * n_batch);
-  hipStream_t st = c->stream;
-  hipError_t e = stage_in(c, X, nstate, J, d_xa, d_X, J, st);
-  if (e == hipSuccess) e = stage_in(c, U, 3, J, d_ua, d_U, J, st);
-  if (e == hipSuccess) e = vec_in(c, t, (long)n_nodes * n_tgrids, d_t, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * n_batch, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_em, em.data(), sizeof(lto_direct_end_model) * n_batch, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_hb, hb.data(), sizeof(double) * 5 * n_batch, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) { (void)hipStreamSynchronize(st); delete p; return set_err(c, LTO_EHIP, "stage in", e); }
-  rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, d_t, n_tgrids, d_jac, S, d_dtf, d_def, S, nullptr);
-  if (rc == LTO_OK)
-    rc = direct_qp_step_free_tf_dev(p, st, d_jac, S, d_dtf, d_def, S, d_X, J, d_U, J, d_t, n_tgrids, d_tg, d_em, d_hb, d_hb + n_batch,
-                                    d_hb + 4 * (size_t)n_batch, allow_impulsive, d_dX, d_dU, d_dV, d_p, d_cost);
-  if (rc == LTO_OK) {
-    e = stage_out(c, d_dX, J, nstate, J, d_dXa, dX, st);
-    if (e == hipSuccess) e = stage_out(c, d_dU, J, 3, J, d_dUa, dU, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dV, d_dV, sizeof(double) * 6 * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(p_out, d_p, sizeof(double) * 3 * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_stat.data(), lto_direct_plan_qp_status(p), sizeof(int) * n_batch, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = stream_wait(st);
-    if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
-    for (int b = 0; b < n_batch && rc == LTO_OK; ++b)
-      if (h_stat[b]) rc = set_err(c, LTO_ESINGULAR, "the KKT system of a trajectory's QP step is singular (too few nodes to reach the terminal state?)");
-  } else {
-    (void)hipStreamSynchronize(st);
-  }
-  direct_plan_free(p);
-  return rc;
+  return direct_qp_step_host(c, "lto_direct_qp_step_free_tf", 4, nstate, n_nodes, n_batch, X, U, t, n_tgrids, nsteps, prm, targets,
+                             model, beta, tfb, n_targets, allow_impulsive, dX, dU, dV, p_out, cost);
 }
 
 // free ends of lto_direct_solve_free_batch (null for lto_direct_solve_batch); tfb non-null: lto_direct_solve_free_tf_batch
@@ -2547,8 +2412,8 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
                              const lto_direct_targets* targets, int n_targets, int allow_impulsive, int maxIter, double* X_out,
                              double* U_out, double* dV_out, double* t_out, double* defect_out, int* status_flag, int* iterations,
                              double* history, const DirectFreeEnds* fe) {
-  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
-  if (!c) return LTO_ENULL;
+  int rc = direct_entry_check(c, nstate, n_nodes, n_batch, n_tgrids, n_targets, false, nullptr, nullptr);
+  if (rc) return rc;
   if (!X_in || !U_in || !t || !prm || !targets || !X_out || !status_flag)
     return set_err(c, LTO_ENULL, "X_in, U_in, t, prm, targets, X_out or status is NULL");
   if (fe && (!fe->orbits || !fe->tau_in || !fe->beta)) return set_err(c, LTO_ENULL, "orbits, tau_in or beta is NULL");
@@ -2583,7 +2448,7 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     std::memcpy(&tl[((size_t)b * NA + a) * n], &t1[(size_t)(n_tgrids == 1 ? 0 : b) * n], sizeof(double) * n);
   lto_direct_plan* p = nullptr;
   lto_direct_plan* pl = nullptr;
-  int rc = direct_plan_build(c, nstate, n_nodes, B, nsteps, prm, &p);
+  rc = direct_plan_build(c, nstate, n_nodes, B, nsteps, prm, &p);
   if (rc) return rc;
   rc = direct_plan_build(c, nstate, n_nodes, B * NA, nsteps, prm, &pl);
   if (rc) { direct_plan_free(p); return rc; }
@@ -2736,14 +2601,9 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
       rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, t_cur, ntg_cur, d_jac, S, d_dtf, nullptr, S, nullptr);
     else
       rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, t_cur, ntg_cur, d_jac, S, nullptr, nullptr, 0, nullptr);   // :500
-    if (rc == LTO_OK && free_it && tfm)
-      rc = direct_qp_step_free_tf_dev(p, st, d_jac, S, d_dtf, d_def, S, d_X, J, d_U, J, t_qp, ntg_qp, d_tg,
-                                      (const lto_direct_end_model*)d_em, d_beta, d_tfb, d_tf, allow_impulsive, d_dX, d_dU, d_dV, d_p, d_cost);
-    else if (rc == LTO_OK && free_it)
-      rc = direct_qp_step_free_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, d_t1, n_tgrids, d_tg, (const lto_direct_end_model*)d_em,
-                                   d_beta, allow_impulsive, d_dX, d_dU, d_dV, d_p, d_cost);
-    else if (rc == LTO_OK)                                                                                               // :525-529
-      rc = lto_direct_qp_step_dev(p, st, d_jac, S, d_def, S, d_X, J, d_U, J, t_qp, ntg_qp, d_tg, allow_impulsive, d_dX, d_dU, d_dV, d_cost);
+    if (rc == LTO_OK)                                      // :525-529
+      rc = direct_qp_launch(p, st, free_it ? (tfm ? 4 : 3) : 1, d_jac, S, d_def, S, d_X, J, d_U, J, t_qp, ntg_qp, d_tg, allow_impulsive,
+                            d_dX, d_dU, d_dV, d_cost, (const lto_direct_end_model*)d_em, d_beta, d_p, d_dtf, d_tfb, d_tf);
     if (rc != LTO_OK) break;
     // lineSearch (:405-430): the ten trial points of every problem, one sweep.  With free tf they are evaluated on the current grid
     // (`lineSearch(..., t_TU, ...)`, :560), not at tf + alpha p3: d_tl holds each trajectory's current grid (k_tf_grid)
@@ -2855,15 +2715,8 @@ int lto_direct_solve_free_tf_batch(lto_ctx* c, int nstate, int n_nodes, int n_ba
                                    const double* tau_in, const double* beta, const lto_direct_tf_bounds* tfb, int flag_end,
                                    int allow_impulsive, int maxIter, double* X_out, double* U_out, double* dV_out, double* t_out,
                                    double* defect_out, double* tau_out, int* status_flag, int* iterations, double* history) {
-  // the argument rules of a free tf answer without a device, like the shape checks
-  if ((nstate != 6 && nstate != 7) || n_nodes < 2 || n_batch < 1) return c ? set_err(c, LTO_EINVAL, "need nstate 6 or 7, n_nodes >= 2, n_batch >= 1") : LTO_EINVAL;
-  if ((n_tgrids != 1 && n_tgrids != n_batch) || (n_targets != 1 && n_targets != n_batch))
-    return c ? set_err(c, LTO_EINVAL, "n_tgrids / n_targets must be 1 or n_batch") : LTO_EINVAL;
-  if (t && tfb) {
-    const int rc = tf_bounds_check(c, tfb, n_targets, t, n_tgrids, n_nodes, n_batch);
-    if (rc) return rc;
-  }
-  if (!c) return LTO_ENULL;
+  const int rc = direct_entry_check(c, nstate, n_nodes, n_batch, n_tgrids, n_targets, true, t, tfb);
+  if (rc) return rc;
   if (!tfb) return set_err(c, LTO_ENULL, "tfb is NULL");
   const DirectFreeEnds fe = {orbits, tau_in, beta, flag_end ? 1 : 0, tau_out, tfb};
   return direct_solve_impl(c, nstate, n_nodes, n_batch, X_in, U_in, t, n_tgrids, nsteps, prm, targets, n_targets, allow_impulsive,

@@ -762,52 +762,38 @@ def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, 
         raise NotImplementedError("multiShoot_CRTBP_direct: flagEnd = true runs on the device only (ops=None); the host mirror of "
                                   "the free-end loop is drivers.direct_loop_host")
     del plot_yn                                           # no plotting
-    if flagEnd and tf_step > 0:
-        X = np.array(X_all, dtype=np.float64, order="F")
-        t = np.array(t_TU, dtype=np.float64)
-        state_0, state_f = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU)
-        tg = hotpath.direct_targets(state_0, state_f, mass, dV1, dV2)
-        orbits = hotpath.DirectOrbits(X0_times, X0_states, Xf_times, Xf_states)
-        _, tf_min, tf_max = tf_bounds_default(t[0], TU)
-        if tf_bounds is not None:
-            tf_min, tf_max = tf_bounds
-        tb = hotpath.direct_tf_bounds(tf_step, tf_min, tf_max)
-        X, U, dV, t, defect, tau, status, iters, hist = hotpath.direct_solve_free_tf(
-            X, u_all, t, nsteps, MU, DU, TU, Isp, orbits, tg, [τ1, τ2], β, tb, True, allowImpulsive, int(maxIter))
-        if verbose:
-            for k in range(iters):
-                print("Iter %d. Max defect = %.2e. Cost = %.5f. tf = %.2f days. alpha = %.3f." % (
-                    k + 1, hist[0, k], hist[1, k], hist[5, k] * TU / day, hist[2, k]))
-        multiShoot_CRTBP_direct.last = {"status": status, "iterations": iters, "history": hist}
-        return X, U, float(tau[0]), float(tau[1]), t, dV[:3].copy(), dV[3:].copy(), defect
-    if flagEnd:
-        X = np.array(X_all, dtype=np.float64, order="F")
-        state_0, state_f = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU)
-        tg = hotpath.direct_targets(state_0, state_f, mass, dV1, dV2)
-        orbits = hotpath.DirectOrbits(X0_times, X0_states, Xf_times, Xf_states)
-        X, U, dV, t, defect, tau, status, iters, hist = hotpath.direct_solve_free(
-            X, u_all, t_TU, nsteps, MU, DU, TU, Isp, orbits, tg, [τ1, τ2], β, True, allowImpulsive, int(maxIter))
-        if verbose:
-            for k in range(iters):
-                print("Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f. tau1 = %.6f, tau2 = %.6f." % (k + 1, *hist[:, k]))
-        multiShoot_CRTBP_direct.last = {"status": status, "iterations": iters, "history": hist}
-        return X, U, float(tau[0]), float(tau[1]), t, dV[:3].copy(), dV[3:].copy(), defect
     X = np.array(X_all, dtype=np.float64, order="F")
     U = np.array(u_all, dtype=np.float64, order="F")
     t = np.array(t_TU, dtype=np.float64)
     dV1 = np.array(dV1, dtype=np.float64).reshape(3)
     dV2 = np.array(dV2, dtype=np.float64).reshape(3)
-    nstate = X.shape[0]
     assert X.shape[1] == n_nodes
     state_0, state_f = interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU)
     maxIter = int(maxIter)
     if ops is None:
         tg = hotpath.direct_targets(state_0, state_f, mass, dV1, dV2)
-        X, U, dV, t, defect, status, iters, hist = hotpath.direct_solve(X, U, t, nsteps, MU, DU, TU, Isp, tg, allowImpulsive, maxIter)
+        orbits = hotpath.DirectOrbits(X0_times, X0_states, Xf_times, Xf_states)
+        if flagEnd and tf_step > 0:
+            _, tf_min, tf_max = tf_bounds_default(t[0], TU)
+            if tf_bounds is not None:
+                tf_min, tf_max = tf_bounds
+            tb = hotpath.direct_tf_bounds(tf_step, tf_min, tf_max)
+            X, U, dV, t, defect, tau, status, iters, hist = hotpath.direct_solve_free_tf(
+                X, U, t, nsteps, MU, DU, TU, Isp, orbits, tg, [τ1, τ2], β, tb, True, allowImpulsive, maxIter)
+            line = lambda k: "Iter %d. Max defect = %.2e. Cost = %.5f. tf = %.2f days. alpha = %.3f." % (
+                k + 1, hist[0, k], hist[1, k], hist[5, k] * TU / day, hist[2, k])
+        elif flagEnd:
+            X, U, dV, t, defect, tau, status, iters, hist = hotpath.direct_solve_free(
+                X, U, t, nsteps, MU, DU, TU, Isp, orbits, tg, [τ1, τ2], β, True, allowImpulsive, maxIter)
+            line = lambda k: "Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f. tau1 = %.6f, tau2 = %.6f." % (k + 1, *hist[:, k])
+        else:
+            X, U, dV, t, defect, status, iters, hist = hotpath.direct_solve(X, U, t, nsteps, MU, DU, TU, Isp, tg, allowImpulsive, maxIter)
+            line = lambda k: "Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f." % (k + 1, hist[0, k], hist[1, k], hist[2, k])
         if verbose:
             for k in range(iters):
-                print("Iter %d. Max defect = %.2e. Cost = %.5f. alpha = %.3f." % (k + 1, hist[0, k], hist[1, k], hist[2, k]))
+                print(line(k))
         multiShoot_CRTBP_direct.last = {"status": status, "iterations": iters, "history": hist}
+        τ1, τ2 = (float(tau[0]), float(tau[1])) if flagEnd else (τ1, τ2)
         return X, U, τ1, τ2, t, dV[:3].copy(), dV[3:].copy(), defect
     out, last = direct_loop_host(X, U, τ1, τ2, t, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times,
                                  Xf_states, False, β, allowImpulsive, maxIter, ops, verbose)

@@ -702,11 +702,9 @@ def _targets_array(targets):
     return arr, len(targets)
 
 
-def direct_qp_step(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive=False, ctx=None):
-    """One Jacobian sweep and one QP step of the direct method (optimizeTraj, direct.jl:248-403, for flagEnd = false, beta = 0,
-    tf fixed) on the device: returns (x_update[nstate x n], u_update[3 x n], dV_update[6] = (dV1_jump; dV2_jump), cost).
-    A trailing batch axis on X_all / u_all solves several problems at once (targets: one, or one per trajectory); the outputs
-    then carry it too.  A singular KKT system raises LtoError(LTO_ESINGULAR)."""
+def _direct_qp_call(name, n_p, X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive, ctx, extra=lambda ntgt: ()):
+    """The marshalling the lto_direct_qp_step* entries share: extra(ntgt) gives the ctypes arguments between the targets and their
+    count, n_p the number of p values per trajectory (0: the entry returns none)."""
     ctx = ctx or default_context()
     X = _f64(X_all)
     U = _f64(u_all)
@@ -714,45 +712,87 @@ def direct_qp_step(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowIm
     t, ntg = _tgrids(t_TU, n, B)
     prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
     tg, ntgt = _targets_array(targets)
+    args = extra(ntgt)
     dX = np.zeros((ns, n, B), order="F")
     dU = np.zeros((3, n, B), order="F")
     dV = np.zeros((6, B), order="F")
+    p = np.zeros((n_p, B), order="F")
     cost = np.zeros(B)
-    ctx.check(ctx.fn("direct_qp_step")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
-                                         C.cast(tg, C.c_void_p), ntgt, 1 if allowImpulsive else 0, _ptr(dX), _ptr(dU), _ptr(dV),
-                                         _ptr(cost)))
+    ctx.check(ctx.fn(name)(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm), C.cast(tg, C.c_void_p),
+                           *args, ntgt, 1 if allowImpulsive else 0, _ptr(dX), _ptr(dU), _ptr(dV), *((_ptr(p),) if n_p else ()),
+                           _ptr(cost)))
+    out = (dX, dU, dV) + ((p,) if n_p else ())
     if not batched:
-        return dX[:, :, 0], dU[:, :, 0], dV[:, 0], float(cost[0])
-    return dX, dU, dV, cost
+        return tuple(a[..., 0] for a in out) + (float(cost[0]),)
+    return out + (cost,)
 
 
-def direct_solve(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive=False, maxIter=100, ctx=None):
-    """The loop of multiShoot_CRTBP_direct (direct.jl:477-594) on the device, trajectories resident in HBM (lto_direct_solve_batch).
-    Returns (X_all, u_all, dV[6] = (dV1; dV2), t_TU, defect, status, iterations, history[3 x maxIter] = (max|defect|, cost, alpha));
-    status 0 converged, 1 maxIter, 2 NaN, 3 singular KKT system.  A trailing batch axis solves several problems in one loop."""
+def _direct_solve_call(name, n_hist, X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive, maxIter, ctx, orbits=None,
+                       extra=lambda ntgt, B: ()):
+    """The marshalling the lto_direct_solve*_batch entries share: the orbit tables of free ends go in front of the targets and make
+    the entry return tau, extra(ntgt, B) gives the ctypes arguments between the targets' count and allowImpulsive, and the history
+    has n_hist rows."""
     ctx = ctx or default_context()
     X = _f64(X_all)
     U = _f64(u_all)
     ns, n, B, batched = _batch_dims(X)
     t, ntg = _tgrids(t_TU, n, B)
     prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    ob = None if orbits is None else _orbits(orbits)
     tg, ntgt = _targets_array(targets)
+    args = extra(ntgt, B)
     mi = int(maxIter)
     Xo = np.zeros((ns, n, B), order="F")
     Uo = np.zeros((3, n, B), order="F")
     dV = np.zeros((6, B), order="F")
     to = np.zeros((n, B), order="F")
     defect = np.zeros((ns, n - 1, B), order="F")
+    tau_o = np.zeros((2, B), order="F")
     status = np.zeros(B, dtype=np.int32)
     iters = np.zeros(B, dtype=np.int32)
-    hist = np.full((3, max(mi, 1), B), np.nan, order="F")
-    ctx.check(ctx.fn("direct_solve_batch")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
-                                             C.cast(tg, C.c_void_p), ntgt, 1 if allowImpulsive else 0, mi, _ptr(Xo), _ptr(Uo),
-                                             _ptr(dV), _ptr(to), _ptr(defect), _ptr(status), _ptr(iters), _ptr(hist)))
+    hist = np.full((n_hist, max(mi, 1), B), np.nan, order="F")
+    free = ob is not None
+    ctx.check(ctx.fn(name)(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
+                           *((C.byref(ob.struct),) if free else ()), C.cast(tg, C.c_void_p), ntgt, *args, 1 if allowImpulsive else 0, mi,
+                           _ptr(Xo), _ptr(Uo), _ptr(dV), _ptr(to), _ptr(defect), *((_ptr(tau_o),) if free else ()), _ptr(status),
+                           _ptr(iters), _ptr(hist)))
     hist = hist[:, :mi]
+    out = (Xo, Uo, dV, to, defect) + ((tau_o,) if free else ())
     if not batched:
-        return (Xo[:, :, 0], Uo[:, :, 0], dV[:, 0], to[:, 0], defect[:, :, 0], int(status[0]), int(iters[0]), hist[:, :, 0])
-    return Xo, Uo, dV, to, defect, status, iters, hist
+        return tuple(a[..., 0] for a in out) + (int(status[0]), int(iters[0]), hist[:, :, 0])
+    return out + (status, iters, hist)
+
+
+def _end_models_array(models, ntgt):
+    if isinstance(models, LtoDirectEndModel):
+        models = [models]
+    if len(models) != ntgt:
+        raise ValueError("need as many end models as targets")
+    return (LtoDirectEndModel * ntgt)(*models)
+
+
+def _betas(beta, ntgt):
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64).reshape(-1), (ntgt,)))
+
+
+def _taus(tau, B):
+    return np.asfortranarray(np.broadcast_to(np.asarray(tau, dtype=np.float64).reshape(2, -1), (2, B)))
+
+
+def direct_qp_step(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive=False, ctx=None):
+    """One Jacobian sweep and one QP step of the direct method (optimizeTraj, direct.jl:248-403, for flagEnd = false, beta = 0,
+    tf fixed) on the device: returns (x_update[nstate x n], u_update[3 x n], dV_update[6] = (dV1_jump; dV2_jump), cost).
+    A trailing batch axis on X_all / u_all solves several problems at once (targets: one, or one per trajectory); the outputs
+    then carry it too.  A singular KKT system raises LtoError(LTO_ESINGULAR)."""
+    return _direct_qp_call("direct_qp_step", 0, X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive, ctx)
+
+
+def direct_solve(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive=False, maxIter=100, ctx=None):
+    """The loop of multiShoot_CRTBP_direct (direct.jl:477-594) on the device, trajectories resident in HBM (lto_direct_solve_batch).
+    Returns (X_all, u_all, dV[6] = (dV1; dV2), t_TU, defect, status, iterations, history[3 x maxIter] = (max|defect|, cost, alpha));
+    status 0 converged, 1 maxIter, 2 NaN, 3 singular KKT system.  A trailing batch axis solves several problems in one loop."""
+    return _direct_solve_call("direct_solve_batch", 3, X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive, maxIter,
+                              ctx)
 
 
 class DirectOrbits:
@@ -808,30 +848,9 @@ def direct_qp_step_free(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, mo
     """One Jacobian sweep and one FREE-END QP step (flagEnd = true, lto_direct_qp_step_free): targets (lto_direct_targets, s0 and
     sf the end states at the current tau), models (lto_direct_end_model) and beta: one, or one per trajectory.  Returns
     (x_update, u_update, dV_update[6], p[2] = (p1_update; p2_update), cost) -- with a trailing batch axis on a batched call."""
-    ctx = ctx or default_context()
-    X = _f64(X_all)
-    U = _f64(u_all)
-    ns, n, B, batched = _batch_dims(X)
-    t, ntg = _tgrids(t_TU, n, B)
-    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
-    tg, ntgt = _targets_array(targets)
-    if isinstance(models, LtoDirectEndModel):
-        models = [models]
-    em = (LtoDirectEndModel * len(models))(*models)
-    bt = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64).reshape(-1), (ntgt,)))
-    if len(models) != ntgt:
-        raise ValueError("need as many end models as targets")
-    dX = np.zeros((ns, n, B), order="F")
-    dU = np.zeros((3, n, B), order="F")
-    dV = np.zeros((6, B), order="F")
-    p = np.zeros((2, B), order="F")
-    cost = np.zeros(B)
-    ctx.check(ctx.fn("direct_qp_step_free")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
-                                              C.cast(tg, C.c_void_p), C.cast(em, C.c_void_p), _ptr(bt), ntgt,
-                                              1 if allowImpulsive else 0, _ptr(dX), _ptr(dU), _ptr(dV), _ptr(p), _ptr(cost)))
-    if not batched:
-        return dX[:, :, 0], dU[:, :, 0], dV[:, 0], p[:, 0], float(cost[0])
-    return dX, dU, dV, p, cost
+    def extra(ntgt):
+        return C.cast(_end_models_array(models, ntgt), C.c_void_p), _ptr(_betas(beta, ntgt))
+    return _direct_qp_call("direct_qp_step_free", 2, X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive, ctx, extra)
 
 
 def direct_solve_free(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, orbits, targets, tau, beta, flagEnd=True, allowImpulsive=False,
@@ -840,35 +859,10 @@ def direct_solve_free(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, orbits, targe
     (tau1; tau2) per trajectory, beta one or one per target.  The mass and impulses come from targets; s0 and sf are recomputed
     from tau.  flagEnd: free ends on odd iterations.  Returns (X_all, u_all, dV[6], t_TU, defect, tau[2], status, iterations,
     history[5 x maxIter] = (max|defect|, cost, alpha, tau1, tau2)); a trailing batch axis on X_all solves a multi-start batch."""
-    ctx = ctx or default_context()
-    X = _f64(X_all)
-    U = _f64(u_all)
-    ns, n, B, batched = _batch_dims(X)
-    t, ntg = _tgrids(t_TU, n, B)
-    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
-    ob = _orbits(orbits)
-    tg, ntgt = _targets_array(targets)
-    ti = np.asfortranarray(np.broadcast_to(np.asarray(tau, dtype=np.float64).reshape(2, -1), (2, B)))
-    bt = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64).reshape(-1), (ntgt,)))
-    mi = int(maxIter)
-    Xo = np.zeros((ns, n, B), order="F")
-    Uo = np.zeros((3, n, B), order="F")
-    dV = np.zeros((6, B), order="F")
-    to = np.zeros((n, B), order="F")
-    defect = np.zeros((ns, n - 1, B), order="F")
-    tau_o = np.zeros((2, B), order="F")
-    status = np.zeros(B, dtype=np.int32)
-    iters = np.zeros(B, dtype=np.int32)
-    hist = np.full((5, max(mi, 1), B), np.nan, order="F")
-    ctx.check(ctx.fn("direct_solve_free_batch")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
-                                                  C.byref(ob.struct), C.cast(tg, C.c_void_p), ntgt, _ptr(ti), _ptr(bt),
-                                                  1 if flagEnd else 0, 1 if allowImpulsive else 0, mi, _ptr(Xo), _ptr(Uo), _ptr(dV),
-                                                  _ptr(to), _ptr(defect), _ptr(tau_o), _ptr(status), _ptr(iters), _ptr(hist)))
-    hist = hist[:, :mi]
-    if not batched:
-        return (Xo[:, :, 0], Uo[:, :, 0], dV[:, 0], to[:, 0], defect[:, :, 0], tau_o[:, 0], int(status[0]), int(iters[0]),
-                hist[:, :, 0])
-    return Xo, Uo, dV, to, defect, tau_o, status, iters, hist
+    def extra(ntgt, B):
+        return _ptr(_taus(tau, B)), _ptr(_betas(beta, ntgt)), 1 if flagEnd else 0
+    return _direct_solve_call("direct_solve_free_batch", 5, X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive,
+                              maxIter, ctx, orbits, extra)
 
 
 def direct_tf_bounds(step, tf_min, tf_max):
@@ -889,31 +883,11 @@ def direct_qp_step_free_tf(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets,
     """One Jacobian sweep (with the tf column) and one free-end, FREE-TF QP step (lto_direct_qp_step_free_tf): as
     direct_qp_step_free, with tf_bounds (lto_direct_tf_bounds, one or one per target); tf is the last entry of each grid.  Returns
     (x_update, u_update, dV_update[6], p[3] = (p1; p2; tf_update), cost) -- with a trailing batch axis on a batched call."""
-    ctx = ctx or default_context()
-    X = _f64(X_all)
-    U = _f64(u_all)
-    ns, n, B, batched = _batch_dims(X)
-    t, ntg = _tgrids(t_TU, n, B)
-    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
-    tg, ntgt = _targets_array(targets)
-    if isinstance(models, LtoDirectEndModel):
-        models = [models]
-    if len(models) != ntgt:
-        raise ValueError("need as many end models as targets")
-    em = (LtoDirectEndModel * ntgt)(*models)
-    tb = _tf_bounds_array(tf_bounds, ntgt)
-    bt = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64).reshape(-1), (ntgt,)))
-    dX = np.zeros((ns, n, B), order="F")
-    dU = np.zeros((3, n, B), order="F")
-    dV = np.zeros((6, B), order="F")
-    p = np.zeros((3, B), order="F")
-    cost = np.zeros(B)
-    ctx.check(ctx.fn("direct_qp_step_free_tf")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
-                                                 C.cast(tg, C.c_void_p), C.cast(em, C.c_void_p), _ptr(bt), C.cast(tb, C.c_void_p), ntgt,
-                                                 1 if allowImpulsive else 0, _ptr(dX), _ptr(dU), _ptr(dV), _ptr(p), _ptr(cost)))
-    if not batched:
-        return dX[:, :, 0], dU[:, :, 0], dV[:, 0], p[:, 0], float(cost[0])
-    return dX, dU, dV, p, cost
+    def extra(ntgt):
+        em = _end_models_array(models, ntgt)
+        tb = _tf_bounds_array(tf_bounds, ntgt)
+        return C.cast(em, C.c_void_p), _ptr(_betas(beta, ntgt)), C.cast(tb, C.c_void_p)
+    return _direct_qp_call("direct_qp_step_free_tf", 3, X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive, ctx, extra)
 
 
 def direct_solve_free_tf(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, orbits, targets, tau, beta, tf_bounds, flagEnd=True,
@@ -921,37 +895,11 @@ def direct_solve_free_tf(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, orbits, ta
     """The loop of multiShoot_CRTBP_direct with free end points AND a free time of flight (lto_direct_solve_free_tf_batch): as
     direct_solve_free, with tf_bounds (one or one per target).  Returns (X_all, u_all, dV[6], t_TU (each trajectory's final grid),
     defect, tau[2], status, iterations, history[6 x maxIter] = (max|defect|, cost, alpha, tau1, tau2, tf))."""
-    ctx = ctx or default_context()
-    X = _f64(X_all)
-    U = _f64(u_all)
-    ns, n, B, batched = _batch_dims(X)
-    t, ntg = _tgrids(t_TU, n, B)
-    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
-    ob = _orbits(orbits)
-    tg, ntgt = _targets_array(targets)
-    tb = _tf_bounds_array(tf_bounds, ntgt)
-    ti = np.asfortranarray(np.broadcast_to(np.asarray(tau, dtype=np.float64).reshape(2, -1), (2, B)))
-    bt = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64).reshape(-1), (ntgt,)))
-    mi = int(maxIter)
-    Xo = np.zeros((ns, n, B), order="F")
-    Uo = np.zeros((3, n, B), order="F")
-    dV = np.zeros((6, B), order="F")
-    to = np.zeros((n, B), order="F")
-    defect = np.zeros((ns, n - 1, B), order="F")
-    tau_o = np.zeros((2, B), order="F")
-    status = np.zeros(B, dtype=np.int32)
-    iters = np.zeros(B, dtype=np.int32)
-    hist = np.full((6, max(mi, 1), B), np.nan, order="F")
-    ctx.check(ctx.fn("direct_solve_free_tf_batch")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
-                                                     C.byref(ob.struct), C.cast(tg, C.c_void_p), ntgt, _ptr(ti), _ptr(bt),
-                                                     C.cast(tb, C.c_void_p), 1 if flagEnd else 0, 1 if allowImpulsive else 0, mi,
-                                                     _ptr(Xo), _ptr(Uo), _ptr(dV), _ptr(to), _ptr(defect), _ptr(tau_o), _ptr(status),
-                                                     _ptr(iters), _ptr(hist)))
-    hist = hist[:, :mi]
-    if not batched:
-        return (Xo[:, :, 0], Uo[:, :, 0], dV[:, 0], to[:, 0], defect[:, :, 0], tau_o[:, 0], int(status[0]), int(iters[0]),
-                hist[:, :, 0])
-    return Xo, Uo, dV, to, defect, tau_o, status, iters, hist
+    def extra(ntgt, B):
+        tb = _tf_bounds_array(tf_bounds, ntgt)
+        return _ptr(_taus(tau, B)), _ptr(_betas(beta, ntgt)), C.cast(tb, C.c_void_p), 1 if flagEnd else 0
+    return _direct_solve_call("direct_solve_free_tf_batch", 6, X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive,
+                              maxIter, ctx, orbits, extra)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,7 +1,5 @@
 """GPU: free end points of the direct method (flagEnd = true) -- the device end model, the free-end QP step against the host
 reference built from the same device Jacobian blocks, and the free-end loop (lto_direct_solve_free / _batch) on the halo demo."""
-import importlib.util
-import os
 
 import numpy as np
 import pytest
@@ -9,23 +7,15 @@ import pytest
 import lowthrustopt_amd as lto
 from lowthrustopt_amd import drivers, synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import direct_helpers as DH
+
 ISP, NSTEPS = 2000.0, 10
 DEMO_TAU2_OFFSET = 0.02
 
 
-def _tables():
-    tabs = synth.halo_orbits()
-    return np.linspace(0, 1, tabs[0].shape[1]), tabs[0], np.linspace(0, 1, tabs[1].shape[1]), tabs[1]
-
-
-def _rel(a, b):
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
-
-
 @pytest.mark.gpu
 def test_device_end_states_match_host(gpu_ctx):
-    tabs = _tables()
+    tabs = DH.tables()
     taus = np.array([[0.3, 0.6], [0.02, 0.99], [0.999, 0.001], [1.03, -0.04], [0.0, 1.0], [0.75, 0.5]]).T
     s0, sf, g0, gf, c0, cf = lto.direct_end_states(np.asfortranarray(taus), tabs, ctx=gpu_ctx)
     for b in range(taus.shape[1]):
@@ -39,7 +29,7 @@ def _free_problems(n, ns, B, seed):
     """B problems with their own grids, phases and beta; the end nodes sit on the orbits a little away from the phases."""
     X, U, T = synth.direct_problem(n, n_batch=B, nstate=ns, seed=seed)
     T = T * (1.0 + 0.1 * np.arange(B))[None, :]
-    tabs = _tables()
+    tabs = DH.tables()
     rng = np.random.default_rng(seed)
     betas = np.array([0.0, 1.0, 100.0, 0.5, 10.0])[:B]
     tg, em, host = [], [], []
@@ -69,10 +59,10 @@ def test_device_free_step_matches_host(gpu_ctx, ns, imp, n):
         model, mass, dV1, dV2 = host[b]
         hx, hu, h1, h2, p1, p2, hc = drivers.direct_qp_dense_free(Jt[..., b], d[..., b], X[..., b], U[..., b], T[:, b], *model, betas[b],
                                                                   mass, dV1, dV2, lto.DU, lto.TU, allowImpulsive=imp)
-        assert _rel(dX[..., b], hx) <= 1e-9 and _rel(dU[..., b], hu) <= 1e-9
+        assert DH.rel(dX[..., b], hx) <= 1e-9 and DH.rel(dU[..., b], hu) <= 1e-9
         assert np.abs(p[:, b] - [p1, p2]).max() <= 1e-9 * 0.1
         if imp:
-            assert _rel(dV[:, b], np.r_[h1, h2]) <= 1e-9
+            assert DH.rel(dV[:, b], np.r_[h1, h2]) <= 1e-9
         else:
             assert np.all(dV[:, b] == 0)
         assert abs(cost[b] - hc) <= 1e-9 * abs(hc)
@@ -95,20 +85,13 @@ def test_device_free_step_large(gpu_ctx):
     tgp = lto.direct_targets(s0 + g0 * p[0], sf + gf * p[1], mass, dV1, dV2)
     fx, fu, fv, fc = lto.direct_qp_step(X, U, T, NSTEPS, lto.MU, lto.DU, lto.TU, ISP, tgp, allowImpulsive=True, ctx=gpu_ctx)
     assert np.all(np.abs(p) <= 0.1)
-    assert _rel(dX, fx) <= 1e-9 and _rel(dU, fu) <= 1e-9 and _rel(dV, fv) <= 1e-9
+    assert DH.rel(dX, fx) <= 1e-9 and DH.rel(dU, fu) <= 1e-9 and DH.rel(dV, fv) <= 1e-9
     assert abs(cost - (fc + 1.0 * (c0 / 2 * p[0] ** 2 + cf / 2 * p[1] ** 2))) <= 1e-9 * abs(cost)
-
-
-def _demo():
-    spec = importlib.util.spec_from_file_location("halo_direct_demo", os.path.join(ROOT, "examples", "halo_direct_demo.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @pytest.mark.gpu
 def test_flag_end_off_is_the_frozen_solve(gpu_ctx):
-    X, U, t, tau1, tau2, *tabs = _demo().demo_problem()
+    X, U, t, tau1, tau2, *tabs = DH.demo().demo_problem()
     tau = np.array([tau1, tau2 + DEMO_TAU2_OFFSET])
     s0, sf, *_ = lto.direct_end_states(tau, tabs, ctx=gpu_ctx)
     tg = lto.direct_targets(s0, sf, 1000.0, np.zeros(3), np.zeros(3))
@@ -123,7 +106,7 @@ def test_flag_end_off_is_the_frozen_solve(gpu_ctx):
 
 @pytest.mark.gpu
 def test_demo_free_ends_converges_and_matches_the_mirror_loop(gpu_ctx):
-    X, U, t, tau1, tau2, *tabs = _demo().demo_problem()
+    X, U, t, tau1, tau2, *tabs = DH.demo().demo_problem()
     tau_0 = (tau1, tau2 + DEMO_TAU2_OFFSET)
     args = (t, np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, 30, NSTEPS, 1000.0, ISP, *tabs, False, True, 0.0, False, 100)
     Xl, Ul, t1, t2, tl, dV1, dV2, defect = drivers.multiShoot_CRTBP_direct(X, U, *tau_0, *args, verbose=False)
@@ -154,7 +137,7 @@ def test_demo_free_ends_converges_and_matches_the_mirror_loop(gpu_ctx):
 
 @pytest.mark.gpu
 def test_multistart_batch_equals_single_solves(gpu_ctx):
-    X, U, t, tau1, tau2, *tabs = _demo().demo_problem()
+    X, U, t, tau1, tau2, *tabs = DH.demo().demo_problem()
     B = 4
     taus = np.array([[tau1, tau2 + o] for o in (0.0, 0.01, 0.02, -0.01)]).T
     tg = lto.direct_targets(np.zeros(6), np.zeros(6), 1000.0, np.zeros(3), np.zeros(3))

@@ -2,8 +2,6 @@
 optimality conditions, the host end model, the mirror loop with free ends on the CPU oracle, and the new C entry points'
 argument checks."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
@@ -12,21 +10,17 @@ import lowthrustopt_amd as lto
 from lowthrustopt_amd import _lib, drivers, synth
 from oracle import oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import direct_helpers as DH
+
 C2 = (lto.DU / lto.TU) ** 2
 ISP = 2000.0
-
-
-def _tables():
-    tabs = synth.halo_orbits()
-    return np.linspace(0, 1, tabs[0].shape[1]), tabs[0], np.linspace(0, 1, tabs[1].shape[1]), tabs[1]
 
 
 def _free_problem(n, ns, seed, tau, shift):
     """A synthetic problem whose end nodes sit on the orbits at tau + shift: the free step wants to move the phases by ~shift."""
     X, U, T = synth.direct_problem(n, nstate=ns, seed=seed)
     X, U, t = X[:, :, 0].copy(), U[:, :, 0].copy(), T[:, 0]
-    tabs = _tables()
+    tabs = DH.tables()
     a0, af = drivers.interpEndStates(tau[0] + shift[0], tau[1] + shift[1], *tabs)
     X[:6, 0], X[:6, -1] = a0, af
     rng = np.random.default_rng(seed)
@@ -137,7 +131,7 @@ def test_dense_free_step_with_flat_ends_is_the_frozen_step(ns, imp):
 
 @pytest.mark.parametrize("tau1,tau2", [(0.3, 0.6), (0.02, 0.99), (0.999, 0.001), (1.03, -0.04)])
 def test_host_end_model_is_the_finite_differences(tau1, tau2):
-    tabs = _tables()
+    tabs = DH.tables()
     s0, sf, g0, gf, c0, cf = drivers.end_model(tau1, tau2, *tabs)
     h = 0.05
 
@@ -148,23 +142,6 @@ def test_host_end_model_is_the_finite_differences(tau1, tau2):
     np.testing.assert_allclose(gf, (s(tau2 + h, 1) - s(tau2 - h, 1)) / (2 * h), rtol=0, atol=1e-13)
     assert abs(c0 - np.linalg.norm((s(tau1 + h, 0) - 2 * s(tau1, 0) + s(tau1 - h, 0)) / h ** 2)) <= 1e-12 * max(1.0, c0)
     assert abs(cf - np.linalg.norm((s(tau2 + h, 1) - 2 * s(tau2, 1) + s(tau2 - h, 1)) / h ** 2)) <= 1e-12 * max(1.0, cf)
-
-
-class OracleDirectOps:
-    """CPU back end of the direct loop: the oracle's sweeps."""
-
-    def __init__(self, Isp):
-        self.Isp = Isp
-
-    def defect(self, X, U, t, nsteps):
-        return O.direct_defect(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, self.Isp)
-
-    def jacobian(self, X, U, t, nsteps):
-        Jt, _, d = O.direct_jacobian_dual(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, self.Isp)
-        return Jt, d
-
-    def defect_batch_sumsq(self, Xb, Ub, t, nsteps):
-        return np.array([np.sum(self.defect(Xb[:, :, k], Ub[:, :, k], t, nsteps)[0] ** 2) for k in range(Xb.shape[2])])
 
 
 def _loop(X, U, tau1, tau2, t, tabs, beta, maxIter, ops, n):
@@ -187,10 +164,10 @@ def test_mirror_loop_with_free_ends_converges_on_oracle():
     n = 8
     X, U, T = synth.direct_problem(n, seed=5)
     X, U, t = X[:, :, 0].copy(), U[:, :, 0].copy(), T[:, 0]
-    tabs = _tables()
+    tabs = DH.tables()
     s0, sf = drivers.interpEndStates(0.32, 0.58, *tabs)
     X[:6, 0], X[:6, -1] = s0, sf                          # end nodes on the orbits, away from the starting phases 0.3, 0.6
-    out, last = _loop(X, U, 0.3, 0.6, t, tabs, 0.0, 30, OracleDirectOps(ISP), n)
+    out, last = _loop(X, U, 0.3, 0.6, t, tabs, 0.0, 30, DH.OracleDirectOps(ISP), n)
     Xo, Uo, tau1, tau2, to, dV1, dV2, defect = out
     assert last["status"] == 0 and np.abs(defect).max() <= 1e-6
     assert (tau1, tau2) != (0.3, 0.6)
@@ -200,20 +177,13 @@ def test_mirror_loop_with_free_ends_converges_on_oracle():
     assert np.abs(Xo[:6, 0] - s0n).max() < 1e-3 and np.abs(Xo[:6, -1] - sfn).max() < 1e-3
 
 
-def _demo():
-    spec = importlib.util.spec_from_file_location("halo_direct_demo", os.path.join(ROOT, "examples", "halo_direct_demo.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 DEMO_TAU2_OFFSET = 0.02
 
 
 def test_mirror_loop_free_ends_halo_demo_preview():
     """CPU preview of the GPU demo case: the 30-node halo demo, flagEnd = true, beta = 0, tau2 offset from its stacked value."""
-    X, U, t, tau1, tau2, *tabs = _demo().demo_problem()
-    out, last = _loop(X, U, tau1, tau2 + DEMO_TAU2_OFFSET, t, tabs, 0.0, 100, OracleDirectOps(ISP), 30)
+    X, U, t, tau1, tau2, *tabs = DH.demo().demo_problem()
+    out, last = _loop(X, U, tau1, tau2 + DEMO_TAU2_OFFSET, t, tabs, 0.0, 100, DH.OracleDirectOps(ISP), 30)
     defect = out[7]
     print("free-end demo preview (oracle): status %d, %d iterations, tau = (%.9f, %.9f), cost %.6f" % (
         last["status"], last["iterations"], out[2], out[3], last["history"][1, last["iterations"] - 1]))
@@ -233,7 +203,7 @@ def test_free_entry_points_without_a_device():
     prm = _lib.LtoDirectParams(lto.MU, lto.DU, lto.TU, ISP)
     tg = lto.direct_targets(np.zeros(6), np.zeros(6), 1000.0, np.zeros(3), np.zeros(3))
     em = lto.direct_end_model(np.zeros(6), np.zeros(6), 0.0, 0.0)
-    ob = lto.DirectOrbits(*_tables())
+    ob = lto.DirectOrbits(*DH.tables())
     st = (C.c_int * 1)()
     assert lib.lto_direct_end_states(None, C.byref(ob.struct), 1, p, p, C.byref(em)) == _lib.LTO_ENULL
     assert lib.lto_direct_end_states(None, C.byref(ob.struct), 0, p, p, C.byref(em)) == _lib.LTO_EINVAL

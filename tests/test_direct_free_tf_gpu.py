@@ -1,8 +1,6 @@
 """GPU: a free time of flight in the direct method's free-end step -- the device step against the dense host reference built from
 the same device Jacobian blocks and tf column, a 4 097-node step against a sparse host solve, the delegation of a pinned tf, and the
 free-tf loop (lto_direct_solve_free_tf / _batch) on the halo demo."""
-import importlib.util
-import os
 
 import numpy as np
 import pytest
@@ -13,26 +11,18 @@ import lowthrustopt_amd as lto
 from lowthrustopt_amd import drivers, synth
 from oracle import oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import direct_helpers as DH
+
 ISP, NSTEPS = 2000.0, 10
 DAY = lto.day / lto.TU
 DEMO_TAU2_OFFSET = 0.02
-
-
-def _tables():
-    tabs = synth.halo_orbits()
-    return np.linspace(0, 1, tabs[0].shape[1]), tabs[0], np.linspace(0, 1, tabs[1].shape[1]), tabs[1]
-
-
-def _rel(a, b):
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
 
 
 def _tf_problems(n, ns, B, seed):
     """B problems with their own grids, phases, beta and tf bounds: wide, tight (p3 at +-step) and absolute bounds around tf."""
     X, U, T = synth.direct_problem(n, n_batch=B, nstate=ns, seed=seed)
     T = T * (1.0 + 0.1 * np.arange(B))[None, :]
-    tabs = _tables()
+    tabs = DH.tables()
     rng = np.random.default_rng(seed)
     betas = np.array([0.0, 1.0, 100.0, 0.5, 10.0])[:B]
     tg, em, tb, host = [], [], [], []
@@ -68,11 +58,11 @@ def test_device_free_tf_step_matches_host(gpu_ctx, ns, imp, n):
         hx, hu, h1, h2, p1, p2, p3, hc = drivers.direct_qp_dense_free_tf(Jt[..., b], dtf[..., b], d[..., b], X[..., b], U[..., b], T[:, b],
                                                                          *model, betas[b], mass, dV1, dV2, lto.DU, lto.TU, tf, tfb,
                                                                          allowImpulsive=imp)
-        assert _rel(dX[..., b], hx) <= 1e-9 and _rel(dU[..., b], hu) <= 1e-9
+        assert DH.rel(dX[..., b], hx) <= 1e-9 and DH.rel(dU[..., b], hu) <= 1e-9
         assert np.abs(p[:2, b] - [p1, p2]).max() <= 1e-9 * 0.1
         assert abs(p[2, b] - p3) <= 1e-9 * max(tfb[0], 1e-300) or abs(p[2, b] - p3) <= 1e-9 * abs(p3)
         if imp:
-            assert _rel(dV[:, b], np.r_[h1, h2]) <= 1e-9
+            assert DH.rel(dV[:, b], np.r_[h1, h2]) <= 1e-9
         else:
             assert np.all(dV[:, b] == 0)
         assert abs(cost[b] - hc) <= 1e-9 * abs(hc)
@@ -149,22 +139,15 @@ def test_device_free_tf_step_large_matches_sparse_solve(gpu_ctx):
                                                      allowImpulsive=False, ctx=gpu_ctx)
     Jt, dtf, d, _ = lto.direct_jacobian_blocks(X, U, T, NSTEPS, lto.MU, lto.DU, lto.TU, ISP, ctx=gpu_ctx)
     hx, hu = _sparse_fixed_p(Jt, dtf, d, X, U, T, s0 + g0 * p[0], sf + gf * p[1], mass, dV1, dV2, False, p[2], lto.DU, lto.TU)
-    print("4 097 nodes: p = (%.6e, %.6e, %.6e), |dX - sparse| rel %.2e, |dU - sparse| rel %.2e" % (*p, _rel(dX, hx), _rel(dU, hu)))
+    print("4 097 nodes: p = (%.6e, %.6e, %.6e), |dX - sparse| rel %.2e, |dU - sparse| rel %.2e" % (*p, DH.rel(dX, hx), DH.rel(dU, hu)))
     assert np.all(np.abs(p[:2]) <= 0.1) and abs(p[2]) <= tfb[0]
-    assert _rel(dX, hx) <= 1e-9 and _rel(dU, hu) <= 1e-9
-
-
-def _demo():
-    spec = importlib.util.spec_from_file_location("halo_direct_demo", os.path.join(ROOT, "examples", "halo_direct_demo.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    assert DH.rel(dX, hx) <= 1e-9 and DH.rel(dU, hu) <= 1e-9
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["step0", "flag_end0"])
 def test_pinned_tf_delegates_to_the_free_end_solve(gpu_ctx, case):
-    X, U, t, tau1, tau2, *tabs = _demo().demo_problem()
+    X, U, t, tau1, tau2, *tabs = DH.demo().demo_problem()
     tau = np.array([tau1, tau2 + DEMO_TAU2_OFFSET])
     tg = lto.direct_targets(np.zeros(6), np.zeros(6), 1000.0, np.zeros(3), np.zeros(3))
     flag = case != "flag_end0"
@@ -182,7 +165,7 @@ def test_pinned_tf_delegates_to_the_free_end_solve(gpu_ctx, case):
 @pytest.mark.gpu
 def test_demo_free_tf_converges_and_matches_the_mirror_loop(gpu_ctx):
     """30 nodes, tau2 offset 0.02, beta = 0, step 1 day: library loop against the HipDirectOps mirror loop; report the run."""
-    X, U, t, tau1, tau2, *tabs = _demo().demo_problem()
+    X, U, t, tau1, tau2, *tabs = DH.demo().demo_problem()
     tau_0 = (tau1, tau2 + DEMO_TAU2_OFFSET)
     tfb = drivers.tf_bounds_default(t[0], lto.TU)
     args = (np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, 30, NSTEPS, 1000.0, ISP, *tabs, False, True, 0.0, False, 100)
@@ -218,7 +201,7 @@ def test_demo_free_tf_converges_and_matches_the_mirror_loop(gpu_ctx):
 
 @pytest.mark.gpu
 def test_multistart_over_tf_equals_single_solves(gpu_ctx):
-    X, U, t, tau1, tau2, *tabs = _demo().demo_problem()
+    X, U, t, tau1, tau2, *tabs = DH.demo().demo_problem()
     tofs = (18.0, 20.0, 22.0)
     B = len(tofs)
     T = np.asfortranarray(np.stack([t[0] + (t - t[0]) * (tof * DAY) / (t[-1] - t[0]) for tof in tofs], axis=1))

@@ -10,31 +10,22 @@ import lowthrustopt_amd as lto
 from lowthrustopt_amd import _lib, drivers, synth
 from oracle import oracle as O
 
+import direct_helpers as DH
+
 C2 = (lto.DU / lto.TU) ** 2
 ISP = 2000.0
 DAY = lto.day / lto.TU
 
 
-def _tables():
-    tabs = synth.halo_orbits()
-    return np.linspace(0, 1, tabs[0].shape[1]), tabs[0], np.linspace(0, 1, tabs[1].shape[1]), tabs[1]
-
-
-def _dtf(X, U, t):
-    """The tf column from the oracle: d defect_i / d h_i times h_i / (tf - t0) (every segment length scales with tf - t0)."""
-    Jt, dh, d = O.direct_jacobian_dual(X, U, t, 10, lto.MU, lto.DU, lto.TU, ISP)
-    return Jt, dh * (np.diff(t) / (t[-1] - t[0]))[None, :], d
-
-
 def _tf_problem(n, ns, seed, tau, shift):
     X, U, T = synth.direct_problem(n, nstate=ns, seed=seed)
     X, U, t = X[:, :, 0].copy(), U[:, :, 0].copy(), T[:, 0]
-    tabs = _tables()
+    tabs = DH.tables()
     a0, af = drivers.interpEndStates(tau[0] + shift[0], tau[1] + shift[1], *tabs)
     X[:6, 0], X[:6, -1] = a0, af
     rng = np.random.default_rng(seed)
     dV1, dV2 = 1e-4 * rng.standard_normal(3), 1e-4 * rng.standard_normal(3)
-    Jt, dtf, d = _dtf(X, U, t)
+    Jt, dtf, d = DH.dtf(X, U, t)
     model = drivers.end_model(tau[0], tau[1], *tabs)
     return Jt, dtf, d, X, U, t, model, 1000.0, dV1, dV2
 
@@ -162,26 +153,9 @@ def test_dense_free_tf_step_with_pinned_tf_is_the_free_step(ns, imp):
 def test_oracle_tf_column_matches_the_central_difference():
     X, U, T = synth.direct_problem(8, seed=5)
     X, U, t = X[:, :, 0], U[:, :, 0], T[:, 0]
-    _, dtf, _ = _dtf(X, U, t)
+    _, dtf, _ = DH.dtf(X, U, t)
     fd = O.direct_dtf_fd(X, U, t, 10, lto.MU, lto.DU, lto.TU, ISP)
     assert np.abs(dtf - fd).max() <= 1e-6 * max(1.0, np.abs(fd).max())
-
-
-class OracleDirectOps:
-    """CPU back end of the direct loop with the tf column: the oracle's sweeps."""
-
-    def defect(self, X, U, t, nsteps):
-        return O.direct_defect(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, ISP)
-
-    def jacobian(self, X, U, t, nsteps):
-        Jt, _, d = O.direct_jacobian_dual(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, ISP)
-        return Jt, d
-
-    def jacobian_tf(self, X, U, t, nsteps):
-        return _dtf(X, U, t)
-
-    def defect_batch_sumsq(self, Xb, Ub, t, nsteps):
-        return np.array([np.sum(self.defect(Xb[:, :, k], Ub[:, :, k], t, nsteps)[0] ** 2) for k in range(Xb.shape[2])])
 
 
 def check_tf_history(hist, iters, tf0, tfb):
@@ -203,12 +177,12 @@ def test_mirror_loop_with_free_tf_converges_on_oracle():
     n = 8
     X, U, T = synth.direct_problem(n, seed=5)
     X, U, t = X[:, :, 0].copy(), U[:, :, 0].copy(), T[:, 0]
-    tabs = _tables()
+    tabs = DH.tables()
     s0, sf = drivers.interpEndStates(0.32, 0.58, *tabs)
     X[:6, 0], X[:6, -1] = s0, sf
     tfb = drivers.tf_bounds_default(t[0], lto.TU)
     out, last = drivers.direct_loop_host(X, U, 0.3, 0.6, t, np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, n, 10, 1000.0, ISP, *tabs,
-                                         True, 0.0, False, 30, OracleDirectOps(), verbose=False, tf_bounds=tfb)
+                                         True, 0.0, False, 30, DH.OracleDirectOps(), verbose=False, tf_bounds=tfb)
     Xo, Uo, tau1, tau2, to, dV1, dV2, defect = out
     hist, iters = last["history"], last["iterations"]
     print("free-tf mirror (oracle, 8 nodes): status %d, %d iterations, tf %.9f -> %.9f TU" % (last["status"], iters, t[-1],
@@ -227,9 +201,9 @@ def test_mirror_loop_tf_bounds_none_and_zero_step_keep_the_pinned_loop():
     n = 8
     X, U, T = synth.direct_problem(n, seed=5)
     X, U, t = X[:, :, 0].copy(), U[:, :, 0].copy(), T[:, 0]
-    tabs = _tables()
+    tabs = DH.tables()
     args = (X, U, 0.3, 0.6, t, np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, n, 10, 1000.0, ISP, *tabs, True, 0.0, False, 6,
-            OracleDirectOps())
+            DH.OracleDirectOps())
     a, la = drivers.direct_loop_host(*args, verbose=False)
     b, lb = drivers.direct_loop_host(*args, verbose=False, tf_bounds=(0.0, t[0] + DAY, 40 * DAY))
     for u, v in zip(a, b):
@@ -250,7 +224,7 @@ def test_free_tf_entry_points_without_a_device():
     prm = _lib.LtoDirectParams(lto.MU, lto.DU, lto.TU, ISP)
     tg = lto.direct_targets(np.zeros(6), np.zeros(6), 1000.0, np.zeros(3), np.zeros(3))
     em = lto.direct_end_model(np.zeros(6), np.zeros(6), 0.0, 0.0)
-    ob = lto.DirectOrbits(*_tables())
+    ob = lto.DirectOrbits(*DH.tables())
     st = (C.c_int * 1)()
     good = lto.direct_tf_bounds(0.2, 1.0, 9.0)
 

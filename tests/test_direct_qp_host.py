@@ -9,6 +9,8 @@ import lowthrustopt_amd as lto
 from lowthrustopt_amd import _lib, drivers, synth
 from oracle import oracle as O
 
+import direct_helpers as DH
+
 C2 = (lto.DU / lto.TU) ** 2
 
 
@@ -109,23 +111,6 @@ def test_interp_end_states_natural_spline():
         assert np.abs(sf - cs2(w2)).max() <= 1e-14 * max(1.0, np.abs(t2).max())
 
 
-class OracleDirectOps:
-    """CPU back end of the direct loop: the oracle's sweeps (test infrastructure)."""
-
-    def __init__(self, Isp):
-        self.Isp = Isp
-
-    def defect(self, X, U, t, nsteps):
-        return O.direct_defect(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, self.Isp)
-
-    def jacobian(self, X, U, t, nsteps):
-        Jt, _, d = O.direct_jacobian_dual(X, U, t, nsteps, lto.MU, lto.DU, lto.TU, self.Isp)
-        return Jt, d
-
-    def defect_batch_sumsq(self, Xb, Ub, t, nsteps):
-        return np.array([np.sum(self.defect(Xb[:, :, k], Ub[:, :, k], t, nsteps)[0] ** 2) for k in range(Xb.shape[2])])
-
-
 @pytest.mark.parametrize("ns", [6, 7])
 def test_python_loop_converges_on_oracle(ns):
     n = 8
@@ -138,7 +123,7 @@ def test_python_loop_converges_on_oracle(ns):
     X[:6, 0], X[:6, -1] = s0, sf
     out = drivers.multiShoot_CRTBP_direct(X, U, 0.3, 0.6, t, np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, n, 10, 1000.0, 2000.0,
                                           times[0], tabs[0], times[1], tabs[1], False, False, 0.0, False, 20,
-                                          ops=OracleDirectOps(2000.0), verbose=False)
+                                          ops=DH.OracleDirectOps(2000.0), verbose=False)
     Xo, Uo, tau1, tau2, to, dV1, dV2, defect = out
     last = drivers.multiShoot_CRTBP_direct.last
     assert last["status"] == 0 and 1 <= last["iterations"] <= 20
@@ -154,7 +139,7 @@ def test_flag_end_is_out_of_scope():
     with pytest.raises(NotImplementedError, match="flagEnd"):
         drivers.multiShoot_CRTBP_direct(X[:, :, 0], U[:, :, 0], 0.3, 0.6, T[:, 0], np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, 4,
                                         10, 1000.0, 2000.0, times[0], tabs[0], times[1], tabs[1], False, True, 1.0, False, 5,
-                                        ops=OracleDirectOps(2000.0), verbose=False)
+                                        ops=DH.OracleDirectOps(2000.0), verbose=False)
 
 
 def test_direct_qp_entry_points_without_a_device():

@@ -1,7 +1,5 @@
 """GPU: the direct method's QP step (lto_direct_qp_step, kernels_direct_qp.hip) against the host KKT solve built from the same
 device Jacobian blocks, and the device loop of multiShoot_CRTBP_direct (lto_direct_solve / _batch) on the reference demo."""
-import importlib.util
-import os
 
 import numpy as np
 import pytest
@@ -9,7 +7,8 @@ import pytest
 import lowthrustopt_amd as lto
 from lowthrustopt_amd import drivers, synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import direct_helpers as DH
+
 ISP, NSTEPS = 2000.0, 10
 
 
@@ -74,10 +73,6 @@ def _host_qp_sparse(Jt, d, X, U, t, s0, sf, mass, dV1, dV2, imp):
     return z[:ns * n].reshape(n, ns).T, z[iu:iv].reshape(n, 3).T, (z[iv:iv + 6] if imp else np.zeros(6))
 
 
-def _rel(a, b):
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
-
-
 def _check_step(Jt, d, X, U, t, tgt, imp, dX, dU, dV, cost, dense=True):
     s0, sf, mass, dV1, dV2 = tgt
     if dense:
@@ -86,9 +81,9 @@ def _check_step(Jt, d, X, U, t, tgt, imp, dX, dU, dV, cost, dense=True):
         assert abs(cost - hc) <= 1e-9 * abs(hc)
     else:
         hx, hu, hv = _host_qp_sparse(Jt, d, X, U, t, s0, sf, mass, dV1, dV2, imp)
-    assert _rel(dX, hx) <= 1e-9 and _rel(dU, hu) <= 1e-9
+    assert DH.rel(dX, hx) <= 1e-9 and DH.rel(dU, hu) <= 1e-9
     if imp:
-        assert _rel(dV, hv) <= 1e-9
+        assert DH.rel(dV, hv) <= 1e-9
     else:
         assert np.all(dV == 0)
     ns = X.shape[0]
@@ -154,16 +149,9 @@ def test_singular_kkt_is_reported(gpu_ctx):
     plan.close()
 
 
-def _demo():
-    spec = importlib.util.spec_from_file_location("halo_direct_demo", os.path.join(ROOT, "examples", "halo_direct_demo.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 @pytest.mark.gpu
 def test_reference_direct_demo_converges(gpu_ctx):
-    demo = _demo()
+    demo = DH.demo()
     X, U, t, tau1, tau2, a, b, c, d = demo.demo_problem()
     args = (tau1, tau2, t, np.zeros(3), np.zeros(3), lto.MU, lto.DU, lto.TU, 30, NSTEPS, 1000.0, ISP, a, b, c, d, False, False, 0.0,
             False, 100)
@@ -181,7 +169,7 @@ def test_reference_direct_demo_converges(gpu_ctx):
 
 @pytest.mark.gpu
 def test_solve_batch_equals_single_solves(gpu_ctx):
-    demo = _demo()
+    demo = DH.demo()
     X, U, t, tau1, tau2, a, b, c, d = demo.demo_problem()
     B = 4
     Xb = np.repeat(X[:, :, None], B, axis=2)
