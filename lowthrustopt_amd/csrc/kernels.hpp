@@ -221,10 +221,9 @@ hipError_t launch_take_trial(const double* trial, long ldt, const double* ss, co
                              int ndim, int nb, double* defect, long ldd, const double* alphas, double* step, const double* mxt, double* mx,
                              hipStream_t st);   // step != nullptr: also k_pick_alpha's outputs (one launch for both)
 hipError_t launch_iter_report(const double* a, int na, const double* b, int nb, double* host_dev, long long* seq_dev, long long seq, hipStream_t st);
-hipError_t launch_end_states(double* X, long ld, int n, int nb, int nrow, double* saved, int restore, hipStream_t st);
-// 14-dim pins: saved[b][14] = first node rows 0-6, last node rows 0-5 and 13.  restore = 0 also sets the last node's row 13
-// (lambda_m(tf)) to 0 before saving it; restore = 1 writes the saved values back.
-hipError_t launch_end_pins14(double* X, long ld, int n, int nb, double* saved, int restore, hipStream_t st);
+// pinned end entries (12 or 14 rows): saved[b][nd] = first node rows 0 .. nd/2-1, last node rows 0-5 (and 13 for nd = 14).
+// restore = 0 saves them, for nd = 14 after setting the last node's row 13 (lambda_m(tf)) to 0; restore = 1 writes them back.
+hipError_t launch_end_pins(double* X, long ld, int n, int nb, int nd, double* saved, int restore, hipStream_t st);
 hipError_t launch_defect_norms(const double* defect, long ldd, int ndim, int seg_per_traj, int n_batch, double* sumsq,
                                double* maxabs, hipStream_t st);
 

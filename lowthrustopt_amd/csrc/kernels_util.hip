@@ -440,29 +440,20 @@ hipError_t launch_iter_report(const double* a, int na, const double* b, int nb, 
   return hipGetLastError();
 }
 
-// save (dir = 0) or restore (dir = 1) the first `nrow` rows of node 0 and node n-1 of every trajectory
-// (indirect.jl:270-271, :324-325); saved [nb][2 nrow]
-__global__ void k_end_states(double* X, long ld, int n, int nrow, double* saved, int dir) {
+// save (dir = 0) or restore (dir = 1) the pinned entries of node 0 and node n-1 of every trajectory (indirect.jl:270-271,
+// :324-325): saved [nb][nd] = node 0 rows 0 .. nd/2-1, node n-1 rows 0-5, and for nd = 14 node n-1 row 13 (lambda_m(tf)), which
+// saving first sets to 0 -- the transversality condition of the free final mass
+__global__ void k_end_pins(double* X, long ld, int n, int nd, double* saved, int dir) {
   const int b = blockIdx.x;
   const int r = threadIdx.x;
-  if (r >= 2 * nrow) return;
-  const long idx = (long)(r % nrow) * ld + (long)b * n + (r < nrow ? 0 : n - 1);
-  double* sv = saved + (long)b * 2 * nrow;
-  if (dir) X[idx] = sv[r]; else sv[r] = X[idx];
-}
-
-// the 14-dim counterpart (the 7 + 7 pinned entries of the variable-mass system): saved [nb][14] = node 0 rows 0-6, node n-1
-// rows 0-5 and 13
-__global__ void k_end_pins14(double* X, long ld, int n, double* saved, int dir) {
-  const int b = blockIdx.x;
-  const int r = threadIdx.x;
-  if (r >= 14) return;
-  const int row = (r < 7) ? r : (r < 13) ? r - 7 : 13;
-  const long idx = (long)row * ld + (long)b * n + (r < 7 ? 0 : n - 1);
-  double* sv = saved + (long)b * 14;
+  if (r >= nd) return;
+  const int h = nd / 2;
+  const int row = (r < h) ? r : (r < h + 6) ? r - h : nd - 1;
+  const long idx = (long)row * ld + (long)b * n + (r < h ? 0 : n - 1);
+  double* sv = saved + (long)b * nd;
   if (dir) X[idx] = sv[r];
   else {
-    if (r == 13) X[idx] = 0.0;               // lambda_m(tf) = 0: transversality of the free final mass
+    if (r >= h + 6) X[idx] = 0.0;
     sv[r] = X[idx];
   }
 }
@@ -487,15 +478,9 @@ hipError_t launch_axpy_traj(const double* x, const double* d, const double* alph
   return hipGetLastError();
 }
 
-hipError_t launch_end_states(double* X, long ld, int n, int nb, int nrow, double* saved, int restore, hipStream_t st) {
+hipError_t launch_end_pins(double* X, long ld, int n, int nb, int nd, double* saved, int restore, hipStream_t st) {
   if (nb <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_end_states, dim3(nb), dim3(64), 0, st, X, ld, n, nrow, saved, restore);
-  return hipGetLastError();
-}
-
-hipError_t launch_end_pins14(double* X, long ld, int n, int nb, double* saved, int restore, hipStream_t st) {
-  if (nb <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_end_pins14, dim3(nb), dim3(64), 0, st, X, ld, n, saved, restore);
+  hipLaunchKernelGGL(k_end_pins, dim3(nb), dim3(64), 0, st, X, ld, n, nd, saved, restore);
   return hipGetLastError();
 }
 

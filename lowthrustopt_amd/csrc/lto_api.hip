@@ -1360,7 +1360,7 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
   if (e == hipSuccess) e = hipMemcpyAsync(d_alphas, alphas, sizeof alphas, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = launch_pack_soa(d_aos, nd, J, d_X, J, st);
   // state_0, state_f  (:270-271); 14-dim: also m0, and lambda_m(tf) set to 0 (free final mass)
-  if (e == hipSuccess) e = (nd == 12) ? launch_end_states(d_X, J, n_nodes, B, 6, d_saved, 0, st) : launch_end_pins14(d_X, J, n_nodes, B, d_saved, 0, st);
+  if (e == hipSuccess) e = launch_end_pins(d_X, J, n_nodes, B, nd, d_saved, 0, st);
   if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage in", e);
 
   // per-trajectory max |v| of an SoA block [rows][ld], `per` columns per trajectory -> host (NaN-propagating)
@@ -1440,8 +1440,7 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
     e = reuse ? launch_take_trial(d_deft, S * NA, d_ss, d_act, d_search, NA, n_nodes - 1, nd, B, d_def, S, d_alphas, d_step, d_mxt, d_mx, st)
               : launch_pick_alpha(d_ss, d_alphas, NA, d_act, d_search, d_step, B, nullptr, nullptr, st);
     if (e == hipSuccess) e = launch_axpy_traj(d_X, d_del, d_step, d_X, J, nd, n_nodes, B, st);      // :304
-    if (e == hipSuccess) e = (nd == 12) ? launch_end_states(d_X, J, n_nodes, B, 6, d_saved, 1, st)     // :324-325
-                                        : launch_end_pins14(d_X, J, n_nodes, B, d_saved, 1, st);
+    if (e == hipSuccess) e = launch_end_pins(d_X, J, n_nodes, B, nd, d_saved, 1, st);                // :324-325
     if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "update", e); break; }
     if (!reuse) {
       rc = lto_indirect_defect_dev(p, st, d_X, J, d_t, n_tgrids, d_def, S, nullptr);               // :328

@@ -10,7 +10,9 @@
                               ladder is a trajectory of ONE batched device Newton loop (lto_indirect_solve_batch)
   multiShoot_CRTBP_indirect_mass / optimizeTraj_OLS_mass / reduceFuel_indirect_mass / lift_to_mass
                               the same loop on the 14-dim variable-mass system (free final mass, lambda_m(tf) = 0):
-                              what the reference's `nstate == 7` branches (:158-161, :195-199) were meant to solve
+                              what the reference's `nstate == 7` branches (:158-161, :195-199) were meant to solve.
+                              Both systems run one loop (_solve_indirect) and one least-squares step (_ols_step); they
+                              differ only in which entries of XC_all[:, node] are pinned (_PINS, keyed by the row count)
   controlLaw_cart             src/multiShoot_CRTBP_indirect.jl:389-440 (costates -> thrust vectors in N: the u_all format
                                                                         of the direct transcription; host post-processing)
 
@@ -82,25 +84,48 @@ def _solve_ls(J, rhs):
     return np.linalg.lstsq(J, -rhs, rcond=None)[0]
 
 
-def optimizeTraj_OLS(XC_all, t_TU, defect, Phi, nstate, n_nodes, params, flag_adjointsOnly, ops):
-    """Least-squares Newton step with second-order correction (indirect.jl:149-218)."""
-    nd = 2 * nstate
-    defect_vec = defect.reshape(-1, order="F")
-    J = hotpath.indirect_scatter(Phi, sparse=True)
-    temp = np.ones(J.shape[1], dtype=bool)
-    if flag_adjointsOnly:                                   # :169-178: drop the state columns of nodes 1..n-1
-        for ind in range(n_nodes - 1):
-            temp[ind * nd: ind * nd + nstate] = False
-    Jm = J[:, np.flatnonzero(temp)]
-    upd = np.zeros(J.shape[1])
-    upd[temp] = _solve_ls(Jm, defect_vec)                   # :182
+# Entries of XC_all[:, node] pinned in every Newton iteration, by row count: (rows at the first node, rows at the last node, rows
+# of the last node held at 0).  12 rows: r, v at both ends (indirect.jl:270-271, :324-325).  14 rows: also m0 at the first node,
+# and lambda_m(tf) = 0 at the last -- the transversality condition of the free final mass.
+_PINS = {12: ([0, 1, 2, 3, 4, 5], [0, 1, 2, 3, 4, 5], []),
+         14: ([0, 1, 2, 3, 4, 5, 6], [0, 1, 2, 3, 4, 5, 13], [13])}
+
+
+def _pinned(nd, n_nodes):
+    """[nd x n_nodes] mask of the pinned entries."""
+    first, last, _ = _PINS[nd]
+    m = np.zeros((nd, n_nodes), dtype=bool)
+    m[first, 0] = True
+    m[last, -1] = True
+    return m
+
+
+def _ols_step(XC_all, t_TU, defect, Phi, n_nodes, params, flag_adjointsOnly, ops):
+    """optimizeTraj_OLS of 12 or 14 rows (indirect.jl:149-218): x = -J \\ defect over the free columns of Jac_full -- all but the
+    pinned ones, adjoints-only also without every node's state columns (:169-178) -- then the second-order correction with the
+    same Jacobian.  The pinned entries of the update are exactly 0."""
+    Phi = np.asarray(Phi)
+    nd = Phi.shape[0]
+    J = hotpath.indirect_scatter(Phi, sparse=True) if nd == 12 else hotpath.indirect_scatter_mass(Phi, sparse=True)
+    free = ~_pinned(nd, n_nodes)
+    if flag_adjointsOnly:
+        free[:nd // 2] = False
+    free = free.reshape(-1, order="F")
+    Jm = J[:, np.flatnonzero(free)]
+    upd = np.zeros(nd * n_nodes)
+    upd[free] = _solve_ls(Jm, np.asarray(defect).reshape(-1, order="F"))     # :182
     xc_update = upd.reshape(nd, n_nodes, order="F")
     if np.abs(xc_update).max() < 1e-1:                      # :190  SOC: same Jacobian, defect at the trial point
         d_soc = ops.defect(XC_all + xc_update, t_TU, params)
-        upd2 = np.zeros(J.shape[1])
-        upd2[temp] = _solve_ls(Jm, d_soc.reshape(-1, order="F"))
+        upd2 = np.zeros(nd * n_nodes)
+        upd2[free] = _solve_ls(Jm, np.asarray(d_soc).reshape(-1, order="F"))
         xc_update = xc_update + upd2.reshape(nd, n_nodes, order="F")
     return xc_update
+
+
+def optimizeTraj_OLS(XC_all, t_TU, defect, Phi, nstate, n_nodes, params, flag_adjointsOnly, ops):
+    """Least-squares Newton step with second-order correction (indirect.jl:149-218), 12 rows."""
+    return _ols_step(XC_all, t_TU, defect, Phi, n_nodes, params, flag_adjointsOnly, ops)
 
 
 def lineSearch(XC_all, xc_update, t_TU, params, ops):
@@ -112,20 +137,11 @@ def lineSearch(XC_all, xc_update, t_TU, params, ops):
     return float(alpha_all[int(np.argmin(er))])             # first minimiser, as `alpha[er .== minimum(er)][1]`
 
 
-def multiShoot_CRTBP_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass0, thrustLimit, plot_yn, flag_adjointsOnly,
-                              maxIter, p, rho, ops=None, verbose=True):
-    """Indirect multiple shooting with fixed end states (indirect.jl:58-61, :254-345).
-    Returns (XC_all, defect, status_flag): 0 converged, 1 maxIter reached, 2 NaN.
-    The driver is the reference's: 12 rows (state + costate, constant mass `mass0`).  The 14-dim extension (mass and mass
-    costate as states, Isp in the parameter tuple's mass slot) is solved by multiShoot_CRTBP_indirect_mass -- the reference's
-    loop pins XC_all[1:6] and solves 12x12 blocks (indirect.jl:324-325)."""
-    if np.asarray(XC_all).shape[0] != 12:
-        raise ValueError("multiShoot_CRTBP_indirect drives the reference's 12-row state+costate system; got %d rows "
-                         "(the 14-row variable-mass system is solved by multiShoot_CRTBP_indirect_mass)" % np.asarray(XC_all).shape[0])
+def _solve_indirect(XC_all, t_TU, n_nodes, params, flag_adjointsOnly, maxIter, ops, verbose):
+    """The Newton loop of multiShoot_CRTBP_indirect (indirect.jl:254-345) for 12 or 14 rows: with ops=None one lto_indirect_solve
+    call, the trajectory resident on the device; with an injected `ops` the Python mirror below.  Returns (XC_all, defect,
+    status_flag)."""
     if ops is None:
-        # product default: the whole loop below is one library call with the trajectory resident on the device
-        # (lto_indirect_solve); the Python loop remains for injected back ends
-        params = hotpath.make_params(MU, DU, TU, thrustLimit, mass0, 1.0, p, rho)
         XC_out, defect, status_flag, iterCount, hist = hotpath.indirect_solve(XC_all, t_TU, params, None, flag_adjointsOnly, maxIter)
         if verbose:
             for k, (er, alpha) in enumerate(hist):
@@ -135,14 +151,14 @@ def multiShoot_CRTBP_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass0, thrustLi
             if status_flag == 1:
                 print("Reached max iteration count at %d iterations" % iterCount)
         return XC_out, defect, status_flag
-    ops = ops or HipOps()
-    XC_all = np.array(XC_all, dtype=np.float64, order="F")
+    nd = XC_all.shape[0]
     t_TU = np.array(t_TU, dtype=np.float64)
-    nstate = XC_all.shape[0] // 2                            # :255
-    params = hotpath.make_params(MU, DU, TU, thrustLimit, mass0, 1.0, p, rho)   # :258-260
+    XC_all[_PINS[nd][2], -1] = 0.0                           # 14 rows: lambda_m(tf) = 0 on entry
+    pinned = _pinned(nd, XC_all.shape[1])
+    pins = XC_all[pinned]                                    # :270-271
+    # the 12-row mirror takes an injected device step where there is one; the 14-row mirror always takes the host step
+    device_step = nd == 12 and hasattr(ops, "newton_step") and getattr(ops, "device_newton", True)
     status_flag = 0
-    state_0 = XC_all[:nstate, 0].copy()
-    state_f = XC_all[:nstate, -1].copy()
     defect = ops.defect(XC_all, t_TU, params)                # :274
     iterCount = 0
     er = 1.0
@@ -153,17 +169,16 @@ def multiShoot_CRTBP_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass0, thrustLi
                 print("Reached max iteration count at %d iterations" % iterCount)
             status_flag = 1
             break
-        if hasattr(ops, "newton_step") and getattr(ops, "device_newton", True):
+        if device_step:
             xc_update = ops.newton_step(XC_all, t_TU, params, flag_adjointsOnly)   # :290-296 on the device
         else:
-            Phi, _ = ops.stm(XC_all, t_TU, params)               # jacobianCalc, :290
-            xc_update = optimizeTraj_OLS(XC_all, t_TU, defect, Phi, nstate, n_nodes, params, flag_adjointsOnly, ops)
+            Phi, _ = ops.stm(XC_all, t_TU, params)           # jacobianCalc, :290
+            xc_update = _ols_step(XC_all, t_TU, defect, Phi, n_nodes, params, flag_adjointsOnly, ops)
         alpha = 1.0
         if iterCount > 3:                                    # :300
             alpha = lineSearch(XC_all, xc_update, t_TU, params, ops)
         XC_all = XC_all + xc_update * alpha
-        XC_all[:nstate, 0] = state_0                         # :324-325
-        XC_all[:nstate, -1] = state_f
+        XC_all[pinned] = pins                                # :324-325
         defect = ops.defect(XC_all, t_TU, params)            # :328
         er = float(np.max(np.abs(defect))) if np.all(np.isfinite(defect)) else float("nan")
         if verbose:
@@ -177,6 +192,23 @@ def multiShoot_CRTBP_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass0, thrustLi
     if np.isnan(XC_all[0, 0]) or not np.all(np.isfinite(defect)):
         status_flag = 2                                      # :339-341
     return XC_all, defect, status_flag
+
+
+def multiShoot_CRTBP_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass0, thrustLimit, plot_yn, flag_adjointsOnly,
+                              maxIter, p, rho, ops=None, verbose=True):
+    """Indirect multiple shooting with fixed end states (indirect.jl:58-61, :254-345).
+    Returns (XC_all, defect, status_flag): 0 converged, 1 maxIter reached, 2 NaN.
+    The driver is the reference's: 12 rows (state + costate, constant mass `mass0`).  The 14-dim extension (mass and mass
+    costate as states, Isp in the parameter tuple's mass slot) is solved by multiShoot_CRTBP_indirect_mass -- the reference's
+    loop pins XC_all[1:6] and solves 12x12 blocks (indirect.jl:324-325).  ops=None: one lto_indirect_solve call; an injected
+    `ops` runs the Python mirror of the loop, with `ops.newton_step` when it has one (and `device_newton` is not False), else
+    `ops.stm` and the host step optimizeTraj_OLS."""
+    if np.asarray(XC_all).shape[0] != 12:
+        raise ValueError("multiShoot_CRTBP_indirect drives the reference's 12-row state+costate system; got %d rows "
+                         "(the 14-row variable-mass system is solved by multiShoot_CRTBP_indirect_mass)" % np.asarray(XC_all).shape[0])
+    params = hotpath.make_params(MU, DU, TU, thrustLimit, mass0, 1.0, p, rho)   # :258-260
+    XC_all = np.array(XC_all, dtype=np.float64, order="F")
+    return _solve_indirect(XC_all, t_TU, n_nodes, params, flag_adjointsOnly, maxIter, ops, verbose)
 
 
 def reduceFuel_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass, thrustLimit, rho_current, rho_target, ops=None,
@@ -233,40 +265,10 @@ def lift_to_mass(XC12, mass0):
     return out
 
 
-def _mass_free_columns(n_nodes, flag_adjointsOnly):
-    """Unknowns of the 14-dim step: every column of Jac_full except the pinned ones (first node 0:7, last node 0:6 and 13);
-    adjoints-only also drops the 7 state columns (r, v, m) of every node."""
-    nd = 14
-    free = np.ones(nd * n_nodes, dtype=bool)
-    free[0:7] = False
-    last = nd * (n_nodes - 1)
-    free[last:last + 6] = False
-    free[last + 13] = False
-    if flag_adjointsOnly:
-        for k in range(n_nodes):
-            free[k * nd:k * nd + 7] = False
-    return free
-
-
 def optimizeTraj_OLS_mass(XC_all, t_TU, defect, Phi, n_nodes, params, flag_adjointsOnly, ops):
-    """The least-squares Newton step of the 14-dim variable-mass system, with the second-order correction of
-    optimizeTraj_OLS (indirect.jl:149-218): Jac_full from indirect_scatter_mass, the pinned columns (and, adjoints-only, the
-    state columns of every node) removed, x = -J \\ defect.  Square for the regular step, least squares for adjoints-only.
-    The pinned entries of the update are exactly 0."""
-    nd = 14
-    defect_vec = np.asarray(defect).reshape(-1, order="F")
-    J = hotpath.indirect_scatter_mass(np.asarray(Phi), sparse=True)
-    free = _mass_free_columns(n_nodes, flag_adjointsOnly)
-    Jm = J[:, np.flatnonzero(free)]
-    upd = np.zeros(nd * n_nodes)
-    upd[free] = _solve_ls(Jm, defect_vec)
-    xc_update = upd.reshape(nd, n_nodes, order="F")
-    if np.abs(xc_update).max() < 1e-1:                      # :190  SOC: same Jacobian, defect at the trial point
-        d_soc = ops.defect(XC_all + xc_update, t_TU, params)
-        upd2 = np.zeros(nd * n_nodes)
-        upd2[free] = _solve_ls(Jm, np.asarray(d_soc).reshape(-1, order="F"))
-        xc_update = xc_update + upd2.reshape(nd, n_nodes, order="F")
-    return xc_update
+    """The least-squares Newton step of the 14-dim variable-mass system: optimizeTraj_OLS on Jac_full from indirect_scatter_mass.
+    Square for the regular step, least squares for adjoints-only."""
+    return _ols_step(XC_all, t_TU, defect, Phi, n_nodes, params, flag_adjointsOnly, ops)
 
 
 def multiShoot_CRTBP_indirect_mass(XC_all, t_TU, MU, DU, TU, n_nodes, Isp, thrustLimit, plot_yn, flag_adjointsOnly,
@@ -276,7 +278,7 @@ def multiShoot_CRTBP_indirect_mass(XC_all, t_TU, MU, DU, TU, n_nodes, Isp, thrus
     XC_all[13, -1] = lambda_m(tf) is set to 0, the transversality condition of the free final mass.  Otherwise the reference
     loop of multiShoot_CRTBP_indirect: stop at max|defect| <= 1e-10, second-order correction, the 20-point line search from
     iteration 4, status flags 0 / 1 / 2.  ops=None: one lto_indirect_solve call (ndim = 14, Isp in the parameter tuple's mass
-    slot); an injected `ops` runs the Python mirror with the host step optimizeTraj_OLS_mass.
+    slot); an injected `ops` runs the Python mirror with `ops.stm` and the host step optimizeTraj_OLS_mass.
     Returns (XC_all, defect, status_flag)."""
     XC_all = np.array(XC_all, dtype=np.float64, order="F")
     if XC_all.ndim != 2 or XC_all.shape[0] != 14:
@@ -287,53 +289,7 @@ def multiShoot_CRTBP_indirect_mass(XC_all, t_TU, MU, DU, TU, n_nodes, Isp, thrus
     if not (XC_all[6, 0] > 0):
         raise ValueError("the initial mass XC_all[6, 0] must be positive; got %r" % (XC_all[6, 0],))
     params = hotpath.make_params(MU, DU, TU, thrustLimit, Isp, 1.0, p, rho)   # mass slot = Isp for 14 rows
-    if ops is None:
-        XC_out, defect, status_flag, iterCount, hist = hotpath.indirect_solve(XC_all, t_TU, params, None, flag_adjointsOnly, maxIter)
-        if verbose:
-            for k, (er, alpha) in enumerate(hist):
-                print("Iter %d. Max defect = %.2e. alpha = %.3f." % (k + 1, er, alpha))
-                if not (er <= 1e3):
-                    print("Not likely to converge. Aborting.")
-            if status_flag == 1:
-                print("Reached max iteration count at %d iterations" % iterCount)
-        return XC_out, defect, status_flag
-    t_TU = np.array(t_TU, dtype=np.float64)
-    XC_all[13, -1] = 0.0
-    state_0 = XC_all[:7, 0].copy()
-    state_f = XC_all[:6, -1].copy()
-    status_flag = 0
-    defect = ops.defect(XC_all, t_TU, params)
-    iterCount = 0
-    er = 1.0
-    while er > 1e-10:
-        iterCount += 1
-        if iterCount > maxIter:
-            if verbose:
-                print("Reached max iteration count at %d iterations" % iterCount)
-            status_flag = 1
-            break
-        Phi, _ = ops.stm(XC_all, t_TU, params)
-        xc_update = optimizeTraj_OLS_mass(XC_all, t_TU, defect, Phi, n_nodes, params, flag_adjointsOnly, ops)
-        alpha = 1.0
-        if iterCount > 3:
-            alpha = lineSearch(XC_all, xc_update, t_TU, params, ops)
-        XC_all = XC_all + xc_update * alpha
-        XC_all[:7, 0] = state_0
-        XC_all[:6, -1] = state_f
-        XC_all[13, -1] = 0.0
-        defect = ops.defect(XC_all, t_TU, params)
-        er = float(np.max(np.abs(defect))) if np.all(np.isfinite(defect)) else float("nan")
-        if verbose:
-            print("Iter %d. Max defect = %.2e. alpha = %.3f." % (iterCount, er, alpha))
-        if not (er <= 1e3):
-            if verbose:
-                print("Not likely to converge. Aborting.")
-            iterCount += 100
-            if er != er:
-                break
-    if np.isnan(XC_all[0, 0]) or not np.all(np.isfinite(defect)):
-        status_flag = 2
-    return XC_all, defect, status_flag
+    return _solve_indirect(XC_all, t_TU, n_nodes, params, flag_adjointsOnly, maxIter, ops, verbose)
 
 
 def reduceFuel_indirect_mass(XC_all, t_TU, MU, DU, TU, n_nodes, Isp, thrustLimit, rho_current, rho_target, ops=None,

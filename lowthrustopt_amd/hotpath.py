@@ -398,25 +398,31 @@ def _tgrids(t, n_nodes, n_batch):
     return t, n_batch
 
 
-def indirect_defectCalc(XC_all, t_TU, params, integ=None, ctx=None, out=None):
-    """defectCalc of multiShoot_CRTBP_indirect (:63-90): returns (defect[12 x (n-1)], errors[n-1]).
-    A trailing batch axis on XC_all sweeps several trajectories (line-search trial points, homotopy levels)
-    in one launch; params may then be one tuple or one per trajectory.  out = (defect, errors): Fortran-ordered float64
-    arrays of shapes (ndim, n-1, B) and (n-1, B) written in place."""
+def _indirect_args(XC_all, t_TU, params, integ, ctx):
+    """The prologue of the indirect wrappers: (ctx, (ndim, n_nodes, n_batch, batched), the library call's leading arguments
+    (handle, ndim, n_nodes, n_batch, XC, t, n_tgrids, params, n_params, integrator)).  The pointers keep their arrays alive."""
     ctx = ctx or default_context()
     integ = integ or integrator()
     XC = _f64(XC_all)
     ndim, n, B, batched = _batch_dims(XC)
     t, ntg = _tgrids(t_TU, n, B)
     prm, nprm = _params_array(params)
+    return ctx, (ndim, n, B, batched), (ctx.handle, ndim, n, B, _ptr(XC), _ptr(t), ntg, prm, nprm, C.byref(integ))
+
+
+def indirect_defectCalc(XC_all, t_TU, params, integ=None, ctx=None, out=None):
+    """defectCalc of multiShoot_CRTBP_indirect (:63-90): returns (defect[12 x (n-1)], errors[n-1]).
+    A trailing batch axis on XC_all sweeps several trajectories (line-search trial points, homotopy levels)
+    in one launch; params may then be one tuple or one per trajectory.  out = (defect, errors): Fortran-ordered float64
+    arrays of shapes (ndim, n-1, B) and (n-1, B) written in place."""
+    ctx, (ndim, n, B, batched), args = _indirect_args(XC_all, t_TU, params, integ, ctx)
     if out is not None:
         defect, errors = out
         _check_out((defect, errors), ((ndim, n - 1, B), (n - 1, B)), "(ndim, n-1, B) and (n-1, B)")
     else:
         defect = np.zeros((ndim, n - 1, B), order="F")
         errors = np.zeros((n - 1, B), order="F")
-    ctx.check(ctx.fn("indirect_defect")(ctx.handle, ndim, n, B, _ptr(XC), _ptr(t), ntg, prm, nprm, C.byref(integ),
-                                          _ptr(defect), _ptr(errors)))
+    ctx.check(ctx.fn("indirect_defect")(*args, _ptr(defect), _ptr(errors)))
     if not batched:
         return defect[:, :, 0], errors[:, 0]
     return defect, errors
@@ -426,30 +432,23 @@ def indirect_stm(XC_all, t_TU, params, integ=None, ctx=None, out=None):
     """Compact Jacobian blocks: Phi[12 x 12 x (n-1)] with Phi[:,:,i] = d x(t_{i+1}) / d XC_all[:,i]
     (the ForwardDiff.jacobian(f, x0) of :121), plus the defect.  out = (Phi, defect): Fortran-ordered float64 arrays of
     shapes (ndim, ndim, n-1, B) and (ndim, n-1, B) written in place (e.g. from Context.pinned_empty)."""
-    ctx = ctx or default_context()
-    integ = integ or integrator()
-    XC = _f64(XC_all)
-    ndim, n, B, batched = _batch_dims(XC)
-    t, ntg = _tgrids(t_TU, n, B)
-    prm, nprm = _params_array(params)
+    ctx, (ndim, n, B, batched), args = _indirect_args(XC_all, t_TU, params, integ, ctx)
     if out is not None:
         Phi, defect = out
         _check_out((Phi, defect), ((ndim, ndim, n - 1, B), (ndim, n - 1, B)), "(ndim, ndim, n-1, B) and (ndim, n-1, B)")
     else:
         Phi = np.empty((ndim, ndim, n - 1, B), order="F")
         defect = np.empty((ndim, n - 1, B), order="F")
-    ctx.check(ctx.fn("indirect_jacobian")(ctx.handle, ndim, n, B, _ptr(XC), _ptr(t), ntg, prm, nprm, C.byref(integ),
-                                            _ptr(Phi), _ptr(defect)))
+    ctx.check(ctx.fn("indirect_jacobian")(*args, _ptr(Phi), _ptr(defect)))
     if not batched:
         return Phi[:, :, :, 0], defect[:, :, 0]
     return Phi, defect
 
 
-def indirect_scatter(Phi, sparse=False):
-    """Band scatter of jacobianCalc (:123-142): row block i = [Phi_i | -I] at columns 12(i-1)+(1:24)
-    (1-based), then columns 1:6 and (end-11):(end-6) zeroed (fixed end states)."""
+def _band(Phi, sparse):
+    """Row block i = [Phi_i | -I] at the columns of nodes i and i+1 (jacobianCalc, :123-142), nothing pinned yet: a dense
+    array, or a COO matrix that keeps Phi's zeros as stored entries."""
     nd, _, S = Phi.shape
-    ns = nd // 2
     n = S + 1
     if sparse:
         import scipy.sparse as sp
@@ -458,46 +457,44 @@ def indirect_scatter(Phi, sparse=False):
         vals = np.transpose(Phi, (2, 0, 1)).ravel()
         ir = (np.arange(S)[:, None] * nd + np.arange(nd)[None, :]).ravel()
         ic = ir + nd
-        J = sp.coo_matrix((np.concatenate([vals, -np.ones(S * nd)]),
-                           (np.concatenate([rows, ir]), np.concatenate([cols, ic]))), shape=(nd * S, nd * n)).tolil()
-        J[:, 0:ns] = 0.0
-        J[:, nd * n - nd:nd * n - ns] = 0.0
-        return J.tocsc()
+        return sp.coo_matrix((np.concatenate([vals, -np.ones(S * nd)]),
+                              (np.concatenate([rows, ir]), np.concatenate([cols, ic]))), shape=(nd * S, nd * n))
     J = np.zeros((nd * S, nd * n))
     for i in range(S):
         J[nd * i:nd * (i + 1), nd * i:nd * (i + 1)] = Phi[:, :, i]
         J[nd * i:nd * (i + 1), nd * (i + 1):nd * (i + 2)] = -np.eye(nd)
-    J[:, 0:ns] = 0.0
-    J[:, nd * n - nd:nd * n - ns] = 0.0
     return J
+
+
+def indirect_scatter(Phi, sparse=False):
+    """Band scatter of jacobianCalc (:123-142): row block i = [Phi_i | -I] at columns 12(i-1)+(1:24)
+    (1-based), then columns 1:6 and (end-11):(end-6) zeroed (fixed end states)."""
+    nd = Phi.shape[0]
+    ns = nd // 2
+    J = _band(Phi, sparse)
+    if sparse:
+        J = J.tolil()
+    ncol = J.shape[1]
+    J[:, 0:ns] = 0.0
+    J[:, ncol - nd:ncol - ns] = 0.0
+    return J.tocsc() if sparse else J
 
 
 def indirect_scatter_mass(Phi, sparse=False):
     """Jac_full of the 14-dim variable-mass system: row block i = [Phi_i | -I] at columns 14 i + (0:28) (0-based), as for
     12 rows, with the pinned columns zeroed -- the first node's r0, v0, m0 (columns 0:7) and the last node's rf, vf and
     lambda_m(tf) (columns 14(n-1) + 0:6 and 14(n-1) + 13).  The final mass, column 14(n-1) + 6, is free."""
-    nd, _, S = Phi.shape
+    nd = Phi.shape[0]
     if nd != 14:
         raise ValueError("indirect_scatter_mass takes 14 x 14 blocks; got %d rows" % nd)
-    n = S + 1
-    last = nd * (n - 1)
+    J = _band(Phi, sparse)
+    last = J.shape[1] - nd
     pinned = np.r_[np.arange(7), last + np.arange(6), last + 13]
     if sparse:
         import scipy.sparse as sp
-        rows = (np.arange(S)[:, None, None] * nd + np.arange(nd)[None, :, None] + np.zeros((1, 1, nd), int)).ravel()
-        cols = (np.arange(S)[:, None, None] * nd + np.zeros((1, nd, 1), int) + np.arange(nd)[None, None, :]).ravel()
-        vals = np.transpose(Phi, (2, 0, 1)).ravel()
-        ir = (np.arange(S)[:, None] * nd + np.arange(nd)[None, :]).ravel()
-        ic = ir + nd
-        J = sp.coo_matrix((np.concatenate([vals, -np.ones(S * nd)]),
-                           (np.concatenate([rows, ir]), np.concatenate([cols, ic]))), shape=(nd * S, nd * n)).tocsc()
-        keep = np.ones(nd * n)
+        keep = np.ones(J.shape[1])
         keep[pinned] = 0.0
-        return (J @ sp.diags(keep)).tocsc()
-    J = np.zeros((nd * S, nd * n))
-    for i in range(S):
-        J[nd * i:nd * (i + 1), nd * i:nd * (i + 1)] = Phi[:, :, i]
-        J[nd * i:nd * (i + 1), nd * (i + 1):nd * (i + 2)] = -np.eye(nd)
+        return (J.tocsc() @ sp.diags(keep)).tocsc()
     J[:, pinned] = 0.0
     return J
 
@@ -511,16 +508,10 @@ def indirect_jacobianCalc(XC_all, t_TU, params, integ=None, ctx=None, sparse=Fal
 def indirect_newton_step(XC_all, t_TU, params, integ=None, ctx=None, soc_threshold=1e-1, flag_adjointsOnly=False):
     """One Newton iteration on the device (jacobianCalc + least-squares step of optimizeTraj_OLS incl. the
     adjoints-only column mask + second-order correction, indirect.jl:290-296): returns (xc_update, defect)."""
-    ctx = ctx or default_context()
-    integ = integ or integrator()
-    XC = _f64(XC_all)
-    ndim, n, B, batched = _batch_dims(XC)
-    t, ntg = _tgrids(t_TU, n, B)
-    prm, nprm = _params_array(params)
+    ctx, (ndim, n, B, batched), args = _indirect_args(XC_all, t_TU, params, integ, ctx)
     upd = np.zeros((ndim, n, B), order="F")
     defect = np.zeros((ndim, n - 1, B), order="F")
-    ctx.check(ctx.fn("indirect_newton_step")(ctx.handle, ndim, n, B, _ptr(XC), _ptr(t), ntg, prm, nprm, C.byref(integ),
-                                               1 if flag_adjointsOnly else 0, float(soc_threshold), _ptr(upd), _ptr(defect)))
+    ctx.check(ctx.fn("indirect_newton_step")(*args, 1 if flag_adjointsOnly else 0, float(soc_threshold), _ptr(upd), _ptr(defect)))
     if not batched:
         return upd[:, :, 0], defect[:, :, 0]
     return upd, defect
@@ -528,42 +519,26 @@ def indirect_newton_step(XC_all, t_TU, params, integ=None, ctx=None, soc_thresho
 
 def indirect_solve(XC_all, t_TU, params, integ=None, flag_adjointsOnly=False, maxIter=10, ctx=None):
     """The Newton loop of multiShoot_CRTBP_indirect (indirect.jl:254-345) as ONE library call, trajectory resident on
-    the device: returns (XC_all, defect, status_flag, iterCount, history[k] = (max|defect|, alpha) of iteration k+1)."""
-    ctx = ctx or default_context()
-    integ = integ or integrator()
-    XC = _f64(XC_all)
-    ndim, n = XC.shape
-    t = np.ascontiguousarray(t_TU, dtype=np.float64)
-    prm, _ = _params_array(params)
-    XC_out = np.zeros((ndim, n), order="F")
-    defect = np.zeros((ndim, n - 1), order="F")
-    hist = np.full((2, max(int(maxIter), 1)), np.nan, order="F")
-    status = C.c_int(0)
-    iters = C.c_int(0)
-    ctx.check(ctx.fn("indirect_solve")(ctx.handle, ndim, n, _ptr(XC), _ptr(t), prm, C.byref(integ), 1 if flag_adjointsOnly else 0,
-                                       int(maxIter), _ptr(XC_out), _ptr(defect), C.byref(status), C.byref(iters), _ptr(hist)))
-    done = int(np.count_nonzero(~np.isnan(hist[1])))          # alpha is written for every completed iteration
-    return XC_out, defect, status.value, iters.value, hist[:, :done].T.copy()
+    the device: returns (XC_all, defect, status_flag, iterCount, history[k] = (max|defect|, alpha) of iteration k+1).
+    indirect_solve_batch with one trajectory."""
+    if np.ndim(XC_all) != 2:
+        raise ValueError("indirect_solve takes one trajectory [ndim x n_nodes]; indirect_solve_batch takes a batch")
+    XC_out, defect, status, iters, history = indirect_solve_batch(XC_all, t_TU, params, integ, flag_adjointsOnly, maxIter, ctx)
+    return XC_out[:, :, 0], defect[:, :, 0], int(status[0]), int(iters[0]), history[0]
 
 
 def indirect_solve_batch(XC_all, t_TU, params, integ=None, flag_adjointsOnly=False, maxIter=10, ctx=None):
     """n_batch independent Newton loops side by side (lto_indirect_solve_batch): XC_all [ndim x n x B] (12 or 14 rows), t_TU [n] or
     [n x B], params one tuple or B.  Returns (XC_all, defect, status_flag[B], iterCount[B], history) with
     history[b] = array of (max|defect|, alpha) per completed iteration of trajectory b."""
-    ctx = ctx or default_context()
-    integ = integ or integrator()
-    XC = _f64(XC_all)
-    ndim, n, B, batched = _batch_dims(XC)
-    t, ntg = _tgrids(t_TU, n, B)
-    prm, nprm = _params_array(params)
+    ctx, (ndim, n, B, _), args = _indirect_args(XC_all, t_TU, params, integ, ctx)
     XC_out = np.zeros((ndim, n, B), order="F")
     defect = np.zeros((ndim, n - 1, B), order="F")
     mi = max(int(maxIter), 1)
     hist = np.full((2, mi, B), np.nan, order="F")
     status = np.zeros(B, dtype=np.int32)
     iters = np.zeros(B, dtype=np.int32)
-    ctx.check(ctx.fn("indirect_solve_batch")(ctx.handle, ndim, n, B, _ptr(XC), _ptr(t), ntg, prm, nprm, C.byref(integ),
-                                             1 if flag_adjointsOnly else 0, int(maxIter), _ptr(XC_out), _ptr(defect),
+    ctx.check(ctx.fn("indirect_solve_batch")(*args, 1 if flag_adjointsOnly else 0, int(maxIter), _ptr(XC_out), _ptr(defect),
                                              _ptr(status), _ptr(iters), _ptr(hist) if maxIter > 0 else None))
     history = [hist[:, ~np.isnan(hist[1, :, b]), b].T.copy() for b in range(B)]
     return XC_out, defect, status, iters, history

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import bvp_reference as R
 import lowthrustopt_amd as lto
 from lowthrustopt_amd import drivers, synth
 from lowthrustopt_amd.constants import MU, DU, TU
@@ -15,21 +16,6 @@ from lowthrustopt_amd.constants import MU, DU, TU
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G0 = 9.81
 pytestmark = pytest.mark.gpu
-
-
-def pinned_mask(n):
-    m = np.zeros((14, n), dtype=bool)
-    m[0:7, 0] = True
-    m[0:6, -1] = True
-    m[13, -1] = True
-    return m
-
-
-def dense_free(n, adjoints_only):
-    free = ~pinned_mask(n)
-    if adjoints_only:
-        free[0:7] = False
-    return free.reshape(-1, order="F")
 
 
 def guess14(n, n_batch, seed):
@@ -63,14 +49,14 @@ def test_device_step_vs_dense(gpu_ctx, n_nodes, n_batch, adjoints_only):
         plan.newton_solve(None, 0, d2, S, delta2, J, adjoints_only=not adjoints_only)
     torch.cuda.synchronize()
     Pn = Phi.cpu().numpy().reshape(14, 14, n_batch, n_nodes - 1).transpose(1, 0, 3, 2)
-    free = dense_free(n_nodes, adjoints_only)
+    free = R.free_mask(14, n_nodes, adjoints_only).reshape(-1, order="F")
     for dd, de in ((d, delta), (d2, delta2)):
         dn = dd.cpu().numpy().reshape(14, n_batch, n_nodes - 1).transpose(0, 2, 1)
         den = de.cpu().numpy().reshape(14, n_batch, n_nodes).transpose(0, 2, 1)
         assert np.all(np.isfinite(den))
         for b in range(n_batch):
             x = den[:, :, b]
-            assert np.all(x[pinned_mask(n_nodes)] == 0.0)
+            assert np.all(x[R.pinned_mask(14, n_nodes)] == 0.0)
             if adjoints_only:
                 assert np.all(x[0:7] == 0.0)
             Jd = lto.indirect_scatter_mass(np.asfortranarray(Pn[:, :, :, b]))
@@ -102,7 +88,7 @@ def test_newton_step_vs_host_step(gpu_ctx):
         assert np.array_equal(d, defect)
         ref = drivers.optimizeTraj_OLS_mass(X14, t, d, Phi, n, prm, adj, ops)
         assert np.abs(upd - ref).max() <= 1e-9 * max(1.0, np.abs(ref).max())
-        assert np.all(upd[pinned_mask(n)] == 0.0)
+        assert np.all(upd[R.pinned_mask(14, n)] == 0.0)
 
 
 def consistent_problem(ctx, n=12):

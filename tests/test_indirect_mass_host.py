@@ -5,6 +5,7 @@ XC[0:7, 0], XC[0:6, -1] and XC[13, -1] = 0 (free final mass)."""
 import numpy as np
 import pytest
 
+import bvp_reference as R
 from lowthrustopt_amd import drivers, hotpath, synth
 from lowthrustopt_amd.constants import MU, DU, TU
 
@@ -45,22 +46,10 @@ def guess14(n, seed=1, lam=0.1):
     return X14, T[:, 0]
 
 
-def pinned_mask(n):
-    m = np.zeros((14, n), dtype=bool)
-    m[0:7, 0] = True
-    m[0:6, -1] = True
-    m[13, -1] = True
-    return m
-
-
 def dense_step(Phi, defect, adjoints_only):
     n = Phi.shape[2] + 1
     J = hotpath.indirect_scatter_mass(Phi)
-    free = ~pinned_mask(n).reshape(-1, order="F")
-    if adjoints_only:
-        st = np.zeros((14, n), dtype=bool)
-        st[0:7] = True
-        free &= ~st.reshape(-1, order="F")
+    free = R.free_mask(14, n, adjoints_only).reshape(-1, order="F")
     Jf = J[:, free]
     rhs = -defect.reshape(-1, order="F")
     x = np.zeros(14 * n)
@@ -104,7 +93,7 @@ def test_host_step_equals_dense_solve(oracle, n, adjoints_only):
     upd = drivers.optimizeTraj_OLS_mass(X, t, d, Phi, n, params, adjoints_only, ops)
     ref = with_soc(X, t, params, ops, Phi, d, adjoints_only)
     assert np.abs(upd - ref).max() <= 1e-9 * max(1.0, np.abs(ref).max())
-    assert np.all(upd[pinned_mask(n)] == 0.0)
+    assert np.all(upd[R.pinned_mask(14, n)] == 0.0)
     if adjoints_only:
         assert np.all(upd[0:7] == 0.0)
     else:
