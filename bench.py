@@ -11,21 +11,29 @@ fp64"): indirect method, 14-dim state + mass + costates PLUS the 14x14 STM (the 
 `jacobianCalc` sweep (which also emits the defect) of src/multiShoot_CRTBP_indirect.jl:93-146 per step.  Inputs are
 synthetic halo->halo stacked trajectories (lowthrustopt_amd/synth.py) resident in HBM (struct-of-arrays) before the
 timed region starts.  The reference's own CRTBP system is 12-dim (constant mass): the same sweep on that
-system -- the one reference parity is claimed for -- is timed in the same run and reported as `reference_system_12dim`
-(`--ndim 12` makes it the main line).
+system -- the one reference parity is claimed for -- is timed in the same `--full` run and reported as
+`reference_system_12dim` (`--ndim 12` makes it the main line).
 N > 1: weak scaling -- every rank sweeps its own 4 096 segments, then one RCCL all-gather of the per-rank
 defect slabs (ndim x 4096 doubles) gives every rank the full defect vector.
 
+Plain run and `--full`: without `--full` the run does only what its headline needs -- set-up, the device warm-up, W warm-up
+and K timed steps, `--dump-outputs`, the line (`value`, `ms_per_step` and the run's configuration; the checks that the timed
+steps' outputs are finite and, at N > 1, that the gathered slabs are right, stay).  `--full` adds everything else the line
+can carry: the cold-clocks run, the 12-dim and reference-integrator legs, the roofline object with its launch-period pass and
+counter passes, the CPU baselines and oracle parity, the host-API, Newton-iteration and BASELINE config legs, C5's step-count
+study.  The cold-clocks run and the 12-dim legs come before the device warm-up, everything else after the timed steps.
+
 Timing: the K steps of the timed region are enqueued back to back with NO event in between (an event pair per launch
 serialises the queue and costs ~12 us per step at the contract size); `value` = segments x K / that wall time, so it does
-not depend on K.  The dominant kernel's launch duration (`roofline.kernel_ms`) comes from a separate pass right after the
-timed region, at the same ramped clocks: one HIP event pair on the launch stream around a burst of back-to-back launches,
+not depend on K.  The dominant kernel's launch duration (`roofline.kernel_ms`, `--full`) comes from a separate pass right after
+the timed region, at the same ramped clocks: one HIP event pair on the launch stream around a burst of back-to-back launches,
 divided by their number (so the ~1.5 us between consecutive launches is counted against the kernel).  N_SAMPLE isolated
 launches with an event pair each are reported beside it (`kernel_ms_isolated`): the device drops its clocks between them.
 
 Device clocks: the device ramps its clocks over the first ~20 ms of load, so a 25-launch run measures the ramp (91 us per
-step) and not the sweep (80 us).  The W + K region is therefore run twice: from cold clocks first (`cold_clocks` in the JSON
-line), then again after `--device-warmup-ms` (default 30) of untimed sweeps -- `value` is the second run.
+step) and not the sweep (80 us).  The W + K region therefore follows `--device-warmup-ms` (default 30) of untimed sweeps,
+counted from the return of a first sweep (whose launch may also load the code object).  `--full` also runs the W + K region
+once from cold clocks before everything else (`cold_clocks` in the JSON line).
 
 Outputs: `--dump-outputs DIR` writes what the last timed step computed (DIR/<name>.npy, float64, at most DUMP_LIMIT bytes) so that
 two builds can be compared output for output; the inputs are seeded, so the same arguments give the same inputs on every run.
@@ -218,18 +226,21 @@ def parse():
                     help="14 = state + mass + costates (BASELINE configs[1]; default of c2 / c2_defect / hbm); 12 = the "
                          "reference's own constant-mass system (parity path; default of the other workloads)")
     ap.add_argument("--method", default="", choices=["", "rk4", "rkf78", "dop853"], help="override the workload's integrator")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the line can carry besides the headline (cold clocks, 12-dim legs, roofline, CPU baselines, parity, host "
+                         "API, Newton iteration, config legs); default: set-up, warm-up, the timed steps, --dump-outputs and the line only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="default line without the compact legs of the other BASELINE configs (`configs`)")
+    ap.add_argument("--no-configs", action="store_true", help="--full line without the compact legs of the other BASELINE configs (`configs`)")
     ap.add_argument("--verbose", action="store_true",
                     help="print the long form of the line (every leg's full roofline object, the prose notes on how each figure was obtained); "
                          "default: the compact line of compact_line() -- numbers and short tokens only, under LINE_BUDGET bytes")
     ap.add_argument("--detail", default="", help="also write the long form to this file (the compact line's `detail` then names it)")
     ap.add_argument("--time-budget", type=float, default=240.0,
-                    help="seconds after which the OPTIONAL legs of the line (12-dim legs, host API, Newton iteration, config legs, counter passes) "
-                         "are skipped instead of started: the contract leg and its roofline / cpu_baseline / parity always run")
+                    help="--full: seconds after which the OPTIONAL legs of the line (12-dim legs, host API, Newton iteration, config legs, counter "
+                         "passes) are skipped instead of started: the contract leg and its roofline / cpu_baseline / parity always run")
     ap.add_argument("--strict", action="store_true", help="exit 1 when a leg failed or a parity figure exceeds its tolerance (the line's `ok` says so either way)")
     ap.add_argument("--live-traffic", default="auto", choices=["auto", "on", "off"],
-                    help="roofline.traffic from counter passes of THIS run: rank 0 at N = 1 starts `rocprofv3 --pmc FETCH_SIZE` and "
+                    help="--full: roofline.traffic from counter passes of THIS run: rank 0 at N = 1 starts `rocprofv3 --pmc FETCH_SIZE` and "
                          "`--pmc WRITE_SIZE` (separate passes) on a child that runs the workload's sweep only; auto = when rocprofv3 is on "
                          "PATH and the baseline legs run too (not with --no-cpu-baseline); on failure the stored profile's figure stays")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # the child of --live-traffic: W + K sweeps, no output
@@ -701,7 +712,8 @@ class NewtonIteration:
             if sync and name == "update":          # the library's loop reads back once per iteration (step length, max |defect|, max |dx|)
                 self.lto.read_scalars(self.ctx, self.scal, 3, None, 0, self.host, stream=self.st)
 
-    def measure(self, reps=40, split_reps=20):
+    def measure(self, reps=40, split_reps=20, full=True):
+        """Time per iteration; full: also without host reads, every operation alone and the sweeps' step counts."""
         torch = self.torch
         for _ in range(5):
             self.iteration()
@@ -711,6 +723,9 @@ class NewtonIteration:
             self.iteration()
         torch.cuda.synchronize()
         us = (time.perf_counter() - t0) / reps * 1e6
+        if not full:
+            finite = bool(torch.isfinite(self.d3).all() and torch.isfinite(self.dt).all() and torch.isfinite(self.delta).all())
+            return {"segments": self.S, "us_per_iteration": us, "finite": finite, "problem": self.problem}
         t0 = time.perf_counter()
         for _ in range(reps):
             self.iteration(sync=False)
@@ -799,11 +814,11 @@ def cpu_newton_baseline(S, seconds, problem=None):
                       "scipy sparse solves + 20 line-search sweeps, as indirect.jl:280-337 does them" % (calls, S, el)}
 
 
-def leg_newton(lto, synth, ctx, st, torch, sizes, cpu_seconds):
+def leg_newton(lto, synth, ctx, st, torch, sizes, cpu_seconds, full=True):
     out = []
     for S in sizes:
         it = NewtonIteration(lto, synth, ctx, st, torch, S)
-        r = it.measure()
+        r = it.measure(full=full)
         problem = (np.asfortranarray(it.X.cpu().numpy()), it.t.cpu().numpy(), it.prm)
         it.close()
         if cpu_seconds > 0:
@@ -1168,7 +1183,7 @@ def compact_line(out, detail=None):
                                "in_lib": [_num(ha["ms_in_library_pageable"], 4), _num(ha["ms_in_library_page_locked"], 4)]}
     nw = out.get("newton_iteration")
     if nw:
-        line["newton_us"] = {str(it["segments"]): [_num(it["us_per_iteration"], 4), _num(it["us_per_iteration_without_host_reads"], 4), _num(it["split_sum_us"], 4),
+        line["newton_us"] = {str(it["segments"]): [_num(it["us_per_iteration"], 4), _num(it.get("us_per_iteration_without_host_reads"), 4), _num(it.get("split_sum_us"), 4),
                                                      _num((it.get("cpu_baseline") or {}).get("value"), 4)] for it in nw["sizes"]}
     if out.get("configs"):
         line["configs"] = {k: _leg_compact(v) for k, v in out["configs"].items()}
@@ -1326,7 +1341,7 @@ def main():
     if wl == "newton":
         # measurement aid: the Newton iteration alone -- also what `rocprofv3 --kernel-trace --stats` / `--pmc` runs of
         # tools/gpu_round.sh profile (`--pmc-child`: iterations only, no output)
-        sizes = [a.segments] if a.segments else [29, 4096]
+        sizes = [a.segments] if a.segments else ([29, 4096] if a.full else [4096])
         if a.pmc_child:
             it = NewtonIteration(lto, synth, ctx, st, torch, sizes[-1])
             for _ in range(a.warmup + a.steps):
@@ -1334,7 +1349,7 @@ def main():
             torch.cuda.synchronize()
             it.close(); ctx.close()
             return
-        res = leg_newton(lto, synth, ctx, st, torch, sizes, 0.0 if a.no_cpu_baseline else a.cpu_seconds / 3)
+        res = leg_newton(lto, synth, ctx, st, torch, sizes, a.cpu_seconds / 3 if (a.full and not a.no_cpu_baseline) else 0.0, full=a.full)
         big = res["sizes"][-1]
         code = emit({"metric": "time per iteration of multiShoot_CRTBP_indirect's Newton loop (device-resident)", "value": big["us_per_iteration"],
                      "unit": "us", "n_gpus": 1, "steps": 40, "warmup": 5, "ms_per_step": big["us_per_iteration"] * 1e-3,
@@ -1573,19 +1588,19 @@ def main():
         return time.perf_counter() - t0
 
     # The device raises its clocks over the first ~20 ms of load (measured: --steps 20 --warmup 5 -> 91 us per step,
-    # --warmup 200 -> 81 us, 2 000 timed steps -> 80 us): a 25-launch run sits entirely inside that ramp.  So the contract
-    # leg is run TWICE -- once from cold clocks (reported as `cold_clocks`), then, after the 12-dim legs and `device_warmup_ms` of
-    # untimed sweeps of the contract workload, again with W warm-up + K timed steps: that second run is `value`.  --device-warmup-ms 0 reports
-    # the cold run as `value`.
+    # --warmup 200 -> 81 us, 2 000 timed steps -> 80 us): a 25-launch run sits entirely inside that ramp.  So W warm-up + K timed
+    # steps follow `device_warmup_ms` of untimed sweeps of the contract workload: that run is `value`.  --full runs the contract
+    # leg once more before everything else, from cold clocks (reported as `cold_clocks`).  --device-warmup-ms 0 reports the cold
+    # run as `value`.
     cold = None
     rebalanced = False
-    if a.device_warmup_ms > 0 and not c5:
+    if a.full and a.device_warmup_ms > 0 and not c5:
         cold_elapsed = timed_leg()
         cold = {"ms_per_step": cold_elapsed / a.steps * 1e3, "value": world * S * a.steps / cold_elapsed,
                 "note": "the same W + K region run first, from idle clocks (max over ranks not taken)"}
 
     ref12 = refint = None
-    if rank == 0 and world == 1 and wl == "c2" and a.ndim == 14 and not a.method and not a.segments:
+    if a.full and rank == 0 and world == 1 and wl == "c2" and a.ndim == 14 and not a.method and not a.segments:
         # the reference's own system (12-dim, constant mass): the sweep reference parity is claimed for, and the reference's own
         # integrator setting on it -- same run, timed the same way (W warm-up + K timed steps), BEFORE the contract leg's warm-up
         ref12 = optional("ref12", lambda: leg_12dim(lto, synth, ctx, st, torch, a))
@@ -1593,7 +1608,10 @@ def main():
 
     if a.device_warmup_ms > 0 and not c5:
         # untimed sweeps of THIS workload straight before its timed region (the other legs leave the clocks wherever their own
-        # kernels and host-side pauses put them)
+        # kernels and host-side pauses put them), counted from the return of a first one: in a run without the legs before this
+        # point, that first launch also loads the code object
+        sweep(dbufs[0])
+        torch.cuda.synchronize()
         tw = time.perf_counter()
         while (time.perf_counter() - tw) * 1e3 < a.device_warmup_ms:
             for _ in range(20):
@@ -1610,7 +1628,8 @@ def main():
     if a.dump_outputs and rank == 0:     # before anything below launches the sweep again
         last = (a.steps - 1) % len(dbufs)
         dumped = snapshot_outputs(w, torch, dbufs[last], gathered[last] if use_coll else None)
-    kern_ms, burst_n, samples = sample_launches(torch, lambda: sweep(dbufs[0]))   # separate pass: the dominant kernel alone
+    if a.full:
+        kern_ms, burst_n, samples = sample_launches(torch, lambda: sweep(dbufs[0]))   # separate pass: the dominant kernel alone
 
     if use_coll:
         for b in range(len(dbufs)):
@@ -1620,9 +1639,10 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=ctl)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-        kt = torch.tensor([kern_ms], dtype=torch.float64, device=ctl)
-        dist.all_reduce(kt, op=dist.ReduceOp.MAX)
-        kern_ms = float(kt.item())
+        if a.full:
+            kt = torch.tensor([kern_ms], dtype=torch.float64, device=ctl)
+            dist.all_reduce(kt, op=dist.ReduceOp.MAX)
+            kern_ms = float(kt.item())
 
     # sanity: the sweep produced finite numbers (a failed launch would leave zeros / raise earlier)
     assert bool(torch.isfinite(defect).all()), "non-finite defect in benchmark sweep"
@@ -1662,9 +1682,9 @@ def main():
             out["device_warmup_ms"] = a.device_warmup_ms
         if wl in ("c2", "hbm", "c4", "c5_stm"):
             out["config"]["stm_kernel"] = plan.last_kernel()
-        if (wl, a.ndim) in WORK and not a.method:
+        if a.full and (wl, a.ndim) in WORK and not a.method:
             out["roofline"] = roofline(wl, a.ndim, S, kern_ms, samples=samples, burst_n=burst_n)
-        elif wl == "c2" and a.method == "dop853":
+        elif a.full and wl == "c2" and a.method == "dop853":
             # the reference's own integrator setting (adaptive order 8 @ 1e-13 + STM): flops from the step counts of this sweep
             acc, rej = plan.step_counts(stream=st)
             trial = float((acc + rej).sum())
@@ -1672,7 +1692,7 @@ def main():
             out["roofline"] = roofline(wl, a.ndim, S, kern_ms, work=(dop853_flops(trial, f_rhs, dim) / S, nbytes), samples=samples, burst_n=burst_n, method="dop853")
             out["roofline"]["flops_from"] = ("measured step counts of this sweep: %.2f accepted + %.2f rejected trial steps per segment (max %d) x "
                                              "(12 x %d + 148 x %d)" % (acc.mean(), rej.mean(), int((acc + rej).max()), f_rhs, dim))
-        if c5:
+        if a.full and c5:
             # wavefront-divergence / load-balance study: a wave runs until its slowest lane has finished
             acc, rej = plan.step_counts(stream=st)
             tot = (acc + rej).astype(np.float64)
@@ -1695,7 +1715,7 @@ def main():
                                "group": grp,
                                "note": "efficiency = segment-steps executed / (group x slowest segment per wavefront / workgroup); rebalanced = "
                                        "lto_indirect_plan_rebalance ordered the lanes by the warm-up sweep's step counts"}
-        if world == 1 and not a.no_cpu_baseline and wl in ("c2", "c3", "c2_defect") and not a.method:
+        if a.full and world == 1 and not a.no_cpu_baseline and wl in ("c2", "c3", "c2_defect") and not a.method:
             out["cpu_baseline"] = cpu_baseline("c3" if wl == "c3" else "c2", a.cpu_seconds, ndim=a.ndim)
             if wl == "c2":
                 # the metric's second half: defect L2 error of this very run against the oracle (checker), 256-segment sample
@@ -1710,7 +1730,7 @@ def main():
                 r = optional("cpu_all_cores", lambda: cpu_baseline("c3" if wl == "c3" else "c2", max(min(3.0, a.cpu_seconds), a.cpu_seconds / 3), threads=ncpu, ndim=a.ndim))
                 if r:
                     out["cpu_baseline_all_cores"] = r
-        if world == 1 and not a.no_cpu_baseline and not a.method and (wl in ("c3", "c4", "c5", "c5_stm") or (wl == "hbm" and a.ndim == 12)):
+        if a.full and world == 1 and not a.no_cpu_baseline and not a.method and (wl in ("c3", "c4", "c5", "c5_stm") or (wl == "hbm" and a.ndim == 12)):
             # the single-workload lines carry what their `configs` legs carry: an oracle sample of this run's own last sweep and the
             # oracle timed on one core on that sample
             par, cpu = config_parity_and_cpu(w, lto, max(min(1.0, a.cpu_seconds), a.cpu_seconds / 4))
@@ -1719,11 +1739,11 @@ def main():
                 out.setdefault("cpu_baseline", cpu)         # (the leg above timed the same thing on a larger sample)
             else:
                 out["cpu_baseline"] = cpu
-        if world == 1 and wl == "c2" and not a.method and not a.segments:
+        if a.full and world == 1 and wl == "c2" and not a.method and not a.segments:
             r = optional("host_api", lambda: leg_host_api(lto, ctx, XC, T, prm, integ, a.ndim, S))
             if r:
                 out["host_api"] = r
-        want_live = a.live_traffic == "on" or (a.live_traffic == "auto" and not a.no_cpu_baseline)
+        want_live = a.full and (a.live_traffic == "on" or (a.live_traffic == "auto" and not a.no_cpu_baseline))
         if world == 1 and want_live and "roofline" in out and wl in ("c2", "c2_defect", "c3", "c4", "hbm"):   # (the C5 sweeps order their lanes first)
             argv_wl = ["--workload", wl, "--ndim", str(a.ndim)]
             if a.segments: argv_wl += ["--segments", str(a.segments)]
@@ -1738,12 +1758,12 @@ def main():
                 rf["traffic"], rf["traffic_from"] = live, how
             else:
                 rf["traffic_live"] = "not measured in this run (%s): the stored profile's figure stands" % how
-        if world == 1 and wl == "c2" and a.ndim == 14 and not a.method and not a.segments:
+        if a.full and world == 1 and wl == "c2" and a.ndim == 14 and not a.method and not a.segments:
             # what a user of the reference's driver waits for per iteration
             r = optional("newton", lambda: leg_newton(lto, synth, ctx, st, torch, [29, 4096], 0.0 if a.no_cpu_baseline else max(min(2.0, a.cpu_seconds), a.cpu_seconds / 4)))
             if r:
                 out["newton_iteration"] = r
-        if world == 1 and wl == "c2" and a.ndim == 14 and not a.method and not a.segments and not a.no_configs:
+        if a.full and world == 1 and wl == "c2" and a.ndim == 14 and not a.method and not a.segments and not a.no_configs:
             # BASELINE configs[2..4] and the HBM evidence point, each at its full single-GPU size, in this same line
             plan.close(); plan = None
             cfgs = {}

@@ -232,3 +232,25 @@ def test_dump_outputs_are_row_by_segment_in_every_layout(tmp_path, monkeypatch):
     assert seg.dtype == np.float64 and len(seg) == 2 and np.all(np.diff(seg) > 0)
     assert np.array_equal(np.load(tmp_path / "sample" / "Phi.npy"), Phi.numpy()[:, seg.astype(int)])
     assert np.array_equal(np.load(tmp_path / "sample" / "defect.npy"), defect.numpy()[:, seg.astype(int)])
+
+
+def test_plain_run_is_the_default_and_its_line_carries_the_headline_alone(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` is a plain run (`--full` off): its long form holds the contract keys and the run's
+    configuration only, and compact_line() reduces it without any of the legs --full adds (roofline null, no cold clocks, baselines,
+    parity or config legs); likewise a plain `--workload newton` line, which times the iteration alone."""
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert a.full is False and a.steps == 20 and a.warmup == 5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert bench.parse().full is True
+    long_form = _canned_long_form()
+    plain = {k: v for k, v in long_form.items() if k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                                                            "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")}
+    line = bench.compact_line(plain)
+    assert line["ok"] is True and line["roofline"] is None and line["value"] == bench._num(long_form["value"], 6)
+    for k in ("cold_ms_per_step", "cpu_baseline", "parity", "ref12", "refint", "host_api_ms", "newton_us", "configs", "failed", "skipped"):
+        assert k not in line, k
+    it = {k: long_form["newton_iteration"]["sizes"][1][k] for k in ("segments", "us_per_iteration", "finite", "problem")}
+    plain["newton_iteration"] = {"sizes": [it]}
+    assert bench.compact_line(plain)["newton_us"] == {"4096": [bench._num(it["us_per_iteration"], 4), None, None, None]}

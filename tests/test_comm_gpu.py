@@ -344,7 +344,7 @@ def test_bench_sharded_configs_with_ranks_sharing_the_device(wl, world, per_rank
     followed by the all-gather of the defect slabs (12 x segments-per-rank doubles per rank) and the slab check.  Ranks share device
     0 here; on the driver's node every rank has its own."""
     rc, out, err = _run_bench({"LTO_BENCH_SHARE_DEVICE": "1"}, ["--workload", wl, "--gpus", str(world), "--steps", "3", "--warmup", "2",
-                                                                "--no-cpu-baseline"])
+                                                                "--full", "--no-cpu-baseline"])
     assert rc == 0 and out is not None, err
     assert out["n_gpus"] == world and out["scaling"] == "strong"
     assert out["config"]["segments_per_gpu"] == per_rank and out["config"]["global_segments"] == world * per_rank

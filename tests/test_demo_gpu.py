@@ -65,8 +65,8 @@ def test_halo_transfer_demo_continuation_to_the_reference_target():
 
 @pytest.mark.gpu
 def test_default_bench_line_is_compact_complete_and_every_leg_within_tolerance():
-    """The line the driver parses (advisor finding on bench.py:1371): `bench.py` with the driver's flags prints
-    ONE line last on stdout, under 6 000 bytes, with roofline / cpu_baseline / parity at the top level and the five BASELINE config
+    """The line the driver parses (advisor finding on bench.py:1371): `bench.py --full` with the driver's flags
+    prints ONE line last on stdout, under 6 000 bytes, with roofline / cpu_baseline / parity at the top level and the five BASELINE config
     legs; every leg's oracle sample is COMPARED with its tolerance (`ok`), and `--strict` turns a failed leg into a non-zero exit."""
     import json
     import os
@@ -74,7 +74,7 @@ def test_default_bench_line_is_compact_complete_and_every_leg_within_tolerance()
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0.4",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "0.4",
                         "--live-traffic", "off", "--strict"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = p.stdout.strip().splitlines()
@@ -96,7 +96,7 @@ def test_default_bench_line_is_compact_complete_and_every_leg_within_tolerance()
 
 @pytest.mark.gpu
 def test_bench_headline_survives_a_spent_time_budget():
-    """`--time-budget 0`: every optional leg is skipped (named in `skipped`), the contract leg with its roofline, cpu_baseline and
+    """`--full --time-budget 0`: every optional leg is skipped (named in `skipped`), the contract leg with its roofline, cpu_baseline and
     parity still runs and the line is printed -- what protects the headline on a slow box."""
     import json
     import os
@@ -104,13 +104,35 @@ def test_bench_headline_survives_a_spent_time_budget():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0.3",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "0.3",
                         "--time-budget", "0", "--strict"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads(p.stdout.strip().splitlines()[-1])
     assert out["ok"] is True and out["value"] > 1e7 and out["roofline"]["frac"] > 0.2 and out["cpu_baseline"]["value"] > 0 and out["parity"]["ok"] is True
     assert set(out["skipped"]) >= {"ref12", "refint", "host_api", "newton", "c1", "c3", "c4", "c5", "c5_stm", "hbm"}
     assert all(leg["ok"] is None for leg in out["configs"].values()) and "ref12" not in out and "newton_us" not in out
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` without `--full`: the contract keys and the run's configuration, and none of the legs
+    `--full` adds (cold clocks, roofline, CPU baselines, parity, 12-dim, host-API, Newton and config legs)."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = p.stdout.strip().splitlines()
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["metric"] == "segment-integrations/sec (state+costate+STM)" and out["unit"] == "segment-integrations/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f64" and out["steps"] == 20 and out["warmup"] == 5 and out["n_gpus"] == 1
+    assert out["value"] > 1e7 and abs(out["value"] * out["ms_per_step"] * 1e-3 / 4096 - 1) < 1e-4
+    assert out["config"]["segments_per_gpu"] == 4096 and out["ok"] is True and out["roofline"] is None
+    for k in ("cold_ms_per_step", "cpu_baseline", "parity", "ref12", "refint", "host_api_ms", "newton_us", "configs", "failed", "skipped"):
+        assert k not in out, k
 
 
 @pytest.mark.gpu
