@@ -41,7 +41,6 @@ struct lto_ctx {
   // grow-only device arena for the host-pointer API
   char* arena;
   size_t arena_bytes;
-  size_t arena_top;
   // small cache of device blocks for plan-owned buffers: the host-pointer API builds a plan per call, and a
   // hipMalloc/hipFree pair costs more than a 29-segment sweep
   struct { void* ptr; size_t bytes; } pool[8];
@@ -170,7 +169,7 @@ int bind_device(lto_ctx* c) {
   return LTO_OK;
 }
 
-// ---- arena: reset at the start of each host-pointer call, bump-allocated, 256-B aligned
+// ---- arena: laid out afresh by each host-pointer call, 256-B aligned
 int arena_reserve(lto_ctx* c, size_t bytes) {
   if (bytes <= c->arena_bytes) return LTO_OK;
   if (c->arena) { LTO_HIP(c, hipStreamSynchronize(c->stream)); LTO_HIP(c, hipFree(c->arena)); c->arena = nullptr; c->arena_bytes = 0; }
@@ -180,12 +179,31 @@ int arena_reserve(lto_ctx* c, size_t bytes) {
   return LTO_OK;
 }
 inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-template <class T>
-T* arena_take(lto_ctx* c, size_t count) {
-  T* p = (T*)(c->arena + c->arena_top);
-  c->arena_top += al256(count * sizeof(T));
-  return p;
-}
+
+// The scratch of one host-pointer call: every buffer is declared once with its element count (add), then reserve() grows the
+// arena to the exact sum of the 256-B-aligned sizes and fills in the pointers, in the order of declaration.
+class ArenaLayout {
+  static constexpr int kMax = 24;
+  struct Slot { void* ptr; void (*set)(void*, char*); size_t bytes; };
+  Slot slot_[kMax];
+  int n_ = 0;
+  template <class T> void add1(T*& p, size_t count) {
+    if (n_ < kMax) slot_[n_] = {&p, [](void* q, char* at) { *(T**)q = (T*)at; }, al256(sizeof(T) * count)};
+    ++n_;
+  }
+ public:
+  template <class... T> void add(size_t count, T*&... p) { (add1(p, count), ...); }   // buffers of `count` elements each
+  int reserve(lto_ctx* c) {
+    if (n_ > kMax) return set_err(c, LTO_EINVAL, "internal: too many scratch buffers");
+    size_t total = 0;
+    for (int k = 0; k < n_; ++k) total += slot_[k].bytes;
+    const int rc = arena_reserve(c, total);
+    if (rc) return rc;
+    size_t off = 0;
+    for (int k = 0; k < n_; ++k) { slot_[k].set(slot_[k].ptr, c->arena + off); off += slot_[k].bytes; }
+    return LTO_OK;
+  }
+};
 
 // ---- device block cache (see lto_ctx::pool)
 hipError_t pool_alloc(lto_ctx* c, void** out, size_t bytes) {
@@ -269,6 +287,7 @@ void timing_end(lto_ctx* c, hipStream_t st) {
 extern "C" {
 
 static void plan_free(lto_indirect_plan* p);
+static void direct_plan_free(lto_direct_plan* p);
 static void ctx_free(lto_ctx* c);
 static int host_plan_acquire(lto_ctx* c, int ndim, int n_nodes, int n_batch, const lto_params* prm, int n_prm,
                              const lto_integrator* integ, lto_indirect_plan** out);
@@ -382,6 +401,44 @@ struct CallTimer {
   ~CallTimer() { if (c) c->last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
+// End of a host-pointer call: poll the stream for up to ~1 ms before blocking in the runtime.  A 4 096-segment sweep is
+// over in 0.2 ms, and the wake-up of a blocked hipStreamSynchronize is a visible part of that.
+static hipError_t stream_wait(hipStream_t st) {
+  const auto give_up = std::chrono::steady_clock::now() + std::chrono::milliseconds(1);
+  do {
+    for (int k = 0; k < 16; ++k) {
+      const hipError_t q = hipStreamQuery(st);
+      if (q != hipErrorNotReady) return q;
+    }
+  } while (std::chrono::steady_clock::now() < give_up);
+  return hipStreamSynchronize(st);
+}
+
+// What a host-pointer call owns on the context's stream: the short-lived plans it builds ([0] the trajectories', [1] the line
+// search's) and the device blocks it allocates.  At scope exit the stream is drained first -- unless the call has waited for it
+// since its last launch (`idle`, set by wait()) -- and only then is anything freed: a plan's blocks go back to the context's block
+// cache (pool_free) and may be handed to the next plan at once.  Host buffers the stream copies from or into are declared ahead of
+// it, so that they outlive the drain.  Plans of the context (host_plan_acquire, lto_*_plan_create) are never given to it.
+struct HostCall {
+  hipStream_t st;
+  bool idle = false;
+  lto_indirect_plan* plan[2] = {};
+  lto_direct_plan* dplan[2] = {};
+  void* block[2] = {};
+  explicit HostCall(lto_ctx* c) : st(c->stream) {}
+  HostCall(const HostCall&) = delete;
+  HostCall& operator=(const HostCall&) = delete;
+  hipError_t wait() { const hipError_t e = stream_wait(st); idle = e == hipSuccess; return e; }
+  ~HostCall() {
+    if (!idle) (void)hipStreamSynchronize(st);
+    for (int k = 1; k >= 0; --k) {
+      if (plan[k]) plan_free(plan[k]);
+      if (dplan[k]) direct_plan_free(dplan[k]);
+      if (block[k]) (void)hipFree(block[k]);
+    }
+  }
+};
+
 /* ------------------------------------------------------------------------------ indirect plans */
 
 // plan construction without lifetime bookkeeping (the library's own short-lived and cached plans)
@@ -398,20 +455,19 @@ static int plan_build(lto_ctx* c, int ndim, int n_nodes, int n_batch, const lto_
   if (rc) return rc;
   rc = bind_device(c);
   if (rc) return rc;
-  TrajParams* h = (TrajParams*)std::malloc(sizeof(TrajParams) * (size_t)n_prm);
-  if (!h) return set_err(c, LTO_EHIP, "host allocation failed");
+  lto::HostBuf<TrajParams> h((size_t)n_prm);
+  if (!h.ok()) return set_err(c, LTO_EHIP, "host allocation failed");
   int pm = 0;
-  rc = make_traj_params(c, ndim, prm, n_prm, h, &pm);
-  if (rc) { std::free(h); return rc; }
+  rc = make_traj_params(c, ndim, prm, n_prm, h.data(), &pm);
+  if (rc) return rc;
   lto_indirect_plan* p = new (std::nothrow) lto_indirect_plan();
-  if (!p) { std::free(h); return set_err(c, LTO_EHIP, "host allocation failed"); }
+  if (!p) return set_err(c, LTO_EHIP, "host allocation failed");
   std::memset(p, 0, sizeof *p);
   p->ctx = c; p->ndim = ndim; p->n_nodes = n_nodes; p->n_batch = n_batch; p->S = (n_nodes - 1) * n_batch;
   p->pm = pm; p->n_prm = n_prm; p->integ = *integ; p->bvp_variant = -1;
   if (p->integ.max_steps <= 0) p->integ.max_steps = 100000;
   hipError_t e = pool_alloc(c, (void**)&p->d_tp, sizeof(TrajParams) * (size_t)n_prm);
-  if (e == hipSuccess) e = hipMemcpy(p->d_tp, h, sizeof(TrajParams) * (size_t)n_prm, hipMemcpyHostToDevice);
-  std::free(h);
+  if (e == hipSuccess) e = hipMemcpy(p->d_tp, h.data(), sizeof(TrajParams) * (size_t)n_prm, hipMemcpyHostToDevice);
   const bool adaptive = integ->method == LTO_RKF78_ADAPTIVE || integ->method == LTO_DOP853_ADAPTIVE;
   if (e == hipSuccess && adaptive) {
     e = pool_alloc(c, (void**)&p->d_nacc, sizeof(int) * (size_t)p->S);
@@ -453,8 +509,8 @@ int lto_indirect_plan_create(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
 
 // The caller may have launched sweeps of this plan on its own streams: the plan's device blocks go back to the
 // context's block cache (pool_free) and may be handed to the next plan at once, so everything in flight on the device
-// has to finish first.  Destroying a plan is rare; the library's own short-lived plans use plan_free after
-// synchronising the one stream they used.
+// has to finish first.  Destroying a plan is rare; the library's own short-lived plans are freed by HostCall, behind a
+// drain of the one stream they used.
 void lto_indirect_plan_destroy(lto_indirect_plan* p) {
   if (!p) return;
   lto_ctx* c = p->ctx;
@@ -1055,13 +1111,14 @@ int lto_calibrate_kernels(lto_ctx* c) {
   const long Smax = lane_round, nmax = Smax + 1;
   hipStream_t st = c->stream;
   LTO_HIP(c, hipStreamSynchronize(st));
-  rc = arena_reserve(c, al256(sizeof(double) * 14 * nmax) + al256(sizeof(double) * nmax) + al256(sizeof(double) * 196 * Smax) + al256(sizeof(double) * 14 * Smax) + 4096);
+  double *d_X, *d_t, *d_phi, *d_def;
+  ArenaLayout scratch;
+  scratch.add((size_t)14 * nmax, d_X);
+  scratch.add((size_t)nmax, d_t);
+  scratch.add((size_t)196 * Smax, d_phi);
+  scratch.add((size_t)14 * Smax, d_def);
+  rc = scratch.reserve(c);
   if (rc) return rc;
-  c->arena_top = 0;
-  double* d_X = arena_take<double>(c, (size_t)14 * nmax);
-  double* d_t = arena_take<double>(c, (size_t)nmax);
-  double* d_phi = arena_take<double>(c, (size_t)196 * Smax);
-  double* d_def = arena_take<double>(c, (size_t)14 * Smax);
   // a state near the Earth-Moon L2 halo family (0.17 DU from the Moon), small costates; 1 000 kg / lambda_m = 0.1 for the 14-row layout
   const double x12[12] = {1.1599795702248494, 0.0097200000000000, -0.1240184140575570, 0.0087153964800000, -0.2085329310256100, 0.0105833000000000,
                           0.01, -0.02, 0.015, 0.02, 0.01, -0.01};
@@ -1093,9 +1150,10 @@ int lto_calibrate_kernels(lto_ctx* c) {
     for (int f = 0; f < 6 && rc == LTO_OK; ++f) {     // f = 5: the whole-segment lanes (12-dim only)
       if (nd == 14 && (f == 2 || f == 3 || f == 5)) continue;
       const long S = (f == 5) ? lane_round : per_round[f];      // one full round: with 44 x CUs segments the 44-form is the cheaper one, with 48 x CUs the 48-form
-      lto_indirect_plan* p = nullptr;
-      rc = plan_build(c, nd, (int)(S + 1), 1, &prm, 1, &integ, &p);
+      HostCall call(c);                             // owns the family's plan
+      rc = plan_build(c, nd, (int)(S + 1), 1, &prm, 1, &integ, &call.plan[0]);
       if (rc) break;
+      lto_indirect_plan* p = call.plan[0];
       p->kernel = (f == 5) ? LTO_KERNEL_LANE : family_kernel[f];
       p->p48_form = (f == 3) ? 44 : 48;
       if (f == 2) p->cols_per_lane = 3;
@@ -1117,7 +1175,7 @@ int lto_calibrate_kernels(lto_ctx* c) {
           rc = set_err(c, LTO_EHIP, "calibration timing");
         ms[q] = m;
       }
-      plan_free(p);
+      call.idle = rc == LTO_OK;                     // e1 was waited for behind the last sweep
       if (rc == LTO_OK) {
         std::sort(ms, ms + 5);
         if (f == 5) measured_lane = ms[2] * 1e3 * (64.0 / integ.steps);
@@ -1203,37 +1261,28 @@ int lto_indirect_newton_step(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
   if (rc) return rc;
   const int nd = ndim;
   const long J = (long)n_nodes * n_batch, S = p->S;
-  const size_t need = al256(sizeof(double) * nd * J) * 5 + al256(sizeof(double) * n_nodes * n_tgrids) +
-                      al256(sizeof(double) * nd * S) * 3 + al256(sizeof(double) * nd * nd * S) + 16384;
-  rc = arena_reserve(c, need);
+  double *d_aos, *d_X, *d_X2, *d_del, *d_del2, *d_t, *d_def, *d_def2, *d_def_aos, *d_phi;
+  ArenaLayout scratch;
+  scratch.add((size_t)nd * J, d_aos, d_X, d_X2, d_del, d_del2);
+  scratch.add((size_t)n_nodes * n_tgrids, d_t);
+  scratch.add((size_t)nd * S, d_def, d_def2, d_def_aos);
+  scratch.add((size_t)nd * nd * S, d_phi);
+  rc = scratch.reserve(c);
   if (rc) return rc;
-  c->arena_top = 0;
-  double* d_aos = arena_take<double>(c, (size_t)nd * J);
-  double* d_X = arena_take<double>(c, (size_t)nd * J);
-  double* d_X2 = arena_take<double>(c, (size_t)nd * J);
-  double* d_del = arena_take<double>(c, (size_t)nd * J);
-  double* d_del2 = arena_take<double>(c, (size_t)nd * J);
-  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
-  double* d_def = arena_take<double>(c, (size_t)nd * S);
-  double* d_def2 = arena_take<double>(c, (size_t)nd * S);
-  double* d_def_aos = arena_take<double>(c, (size_t)nd * S);
-  double* d_phi = arena_take<double>(c, (size_t)nd * nd * S);
+  lto::HostBuf<double> h_del;
+  HostCall call(c);
   hipStream_t st = c->stream;
   hipError_t e = hipMemcpyAsync(d_aos, XC, sizeof(double) * nd * J, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n_nodes * n_tgrids, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = launch_pack_soa(d_aos, nd, J, d_X, J, st);
-  if (e != hipSuccess) { (void)hipStreamSynchronize(st); return set_err(c, LTO_EHIP, "stage in", e); }
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "stage in", e);
   host_order_adopt(c, p, true);
   rc = lto_indirect_jacobian_dev(p, st, d_X, J, d_t, n_tgrids, d_phi, S, d_def, S);
   if (rc == LTO_OK) host_order_refresh(c, p, true, st);
   if (rc == LTO_OK) rc = lto_indirect_newton_solve_dev(p, st, d_phi, S, d_def, S, flag_adjointsOnly, d_del, J);
-  double* h_del = nullptr;
+  if (rc == LTO_OK && !h_del.alloc((size_t)nd * J)) rc = set_err(c, LTO_EHIP, "host allocation failed");
   if (rc == LTO_OK) {
-    h_del = (double*)std::malloc(sizeof(double) * nd * (size_t)J);
-    if (!h_del) rc = set_err(c, LTO_EHIP, "host allocation failed");
-  }
-  if (rc == LTO_OK) {
-    e = hipMemcpyAsync(h_del, d_del, sizeof(double) * nd * J, hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(h_del.data(), d_del, sizeof(double) * nd * J, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "newton step", e);
   }
@@ -1260,13 +1309,54 @@ int lto_indirect_newton_step(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
       if (e == hipSuccess) e = hipMemcpyAsync(defect, d_def_aos, sizeof(double) * nd * S, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
+    call.idle = e == hipSuccess;
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
-  } else {
-    (void)hipStreamSynchronize(st);
   }
-  std::free(h_del);
   return rc;
 }
+
+/* The per-trajectory bookkeeping of the two batched device Newton loops (lto_indirect_solve_batch, direct_solve_impl): who is still
+ * in its loop, the iteration counts, the status flags and the last max |defect| on the host; the trial step lengths
+ * LinRange(0.1, 1, n_alpha); and the flags the device reads per trajectory (1 = still in the loop, 1 = line search on), uploaded
+ * when they change.  The tolerance, the first line-search iteration and what the counts report stay with each loop. */
+struct NewtonBatch {
+  const int B;
+  lto::HostBuf<char> active;
+  lto::HostBuf<int> it, status;
+  lto::HostBuf<double> h_er, h_act, h_search, alphas;     // h_act / h_search: the flags last uploaded (-1: none yet)
+  NewtonBatch(int n_batch, int n_alpha)
+      : B(n_batch), active(B, 1), it(B, 0), status(B, 0), h_er(B, 1.0), h_act(B, -1.0), h_search(B, -1.0), alphas(n_alpha) {
+    if (!alphas.ok()) return;
+    for (int a = 0; a < n_alpha; ++a) alphas[a] = 0.1 + (1.0 - 0.1) / (n_alpha - 1) * a;
+    alphas[n_alpha - 1] = 1.0;
+  }
+  bool ok() const { return active.ok() && it.ok() && status.ok() && h_er.ok() && h_act.ok() && h_search.ok() && alphas.ok(); }
+  bool any_active() const { for (int b = 0; b < B; ++b) if (active[b]) return true; return false; }
+  // `while er > tol` and the iteration limit, trajectory by trajectory; false once none is left in its loop.  A trajectory that
+  // reaches the limit leaves with status 1 and its count past maxIter.
+  bool next(double tol, int maxIter) {
+    for (int b = 0; b < B; ++b) {
+      if (!active[b]) continue;
+      if (!(h_er[b] > tol)) { active[b] = 0; continue; }            // converged, or NaN (the comparison is false)
+      if (++it[b] > maxIter) { status[b] = 1; active[b] = 0; }
+    }
+    return any_active();
+  }
+  // the device's flags of this iteration, the line search on past iteration `search_after`
+  hipError_t upload_flags(int search_after, double* d_act, double* d_search, hipStream_t st) {
+    bool changed = false;
+    for (int b = 0; b < B; ++b) {
+      const double fa = active[b] ? 1.0 : 0.0, fs = (active[b] && it[b] > search_after) ? 1.0 : 0.0;
+      if (fa != h_act[b] || fs != h_search[b]) { h_act[b] = fa; h_search[b] = fs; changed = true; }
+    }
+    if (!changed) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(d_act, h_act.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
+    return e == hipSuccess ? hipMemcpyAsync(d_search, h_search.data(), sizeof(double) * B, hipMemcpyHostToDevice, st) : e;
+  }
+  void copy_out(int* status_flag, int* iterations) const {
+    for (int b = 0; b < B; ++b) { status_flag[b] = status[b]; if (iterations) iterations[b] = it[b]; }
+  }
+};
 
 /* Whole Newton loop of multiShoot_CRTBP_indirect (src/multiShoot_CRTBP_indirect.jl:254-345) with the trajectories
  * resident in HBM: per iteration one STM sweep, the structured least-squares step (+ second-order correction), the
@@ -1299,37 +1389,32 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
     for (int b = 0; b < B; ++b) for (int a = 0; a < NA; ++a)
       std::memcpy(&t_l[((size_t)b * NA + a) * n_nodes], t + (size_t)b * n_nodes, sizeof(double) * n_nodes);
   }
-  lto_indirect_plan* p = nullptr;
-  lto_indirect_plan* pl = nullptr;
   const int nd = ndim;                                     // 12: state + costate; 14: + mass and mass costate
-  int rc = plan_build(c, nd, n_nodes, B, prm, n_prm, integ, &p);
+  NewtonBatch nb(B, NA);                                   // er = 1.0: :279
+  lto::HostBuf<double> h_mx(B), h_step(B), h_back((size_t)3 * B);
+  HostCall call(c);
+  int rc = plan_build(c, nd, n_nodes, B, prm, n_prm, integ, &call.plan[0]);
+  if (rc == LTO_OK) rc = plan_build(c, nd, n_nodes, B * NA, n_prm == 1 ? prm : prm_l.data(), n_prm == 1 ? 1 : B * NA, integ, &call.plan[1]);
   if (rc) return rc;
-  rc = plan_build(c, nd, n_nodes, B * NA, n_prm == 1 ? prm : prm_l.data(), n_prm == 1 ? 1 : B * NA, integ, &pl);
-  if (rc) { plan_free(p); return rc; }
+  lto_indirect_plan* p = call.plan[0];
+  lto_indirect_plan* pl = call.plan[1];                    // the line search's trial trajectories
   const long n = n_nodes, J = n * B, S = (n - 1) * B;
   const int ntl = (n_tgrids == 1) ? 1 : B * NA;
   const size_t n_small = (size_t)nd * B + NA + 6 * (size_t)B + 2 * (size_t)NA * B + 64;
-  const size_t need = al256(sizeof(double) * nd * J) * 5 + al256(sizeof(double) * nd * J * NA) + al256(sizeof(double) * n * n_tgrids) +
-                      al256(sizeof(double) * n * ntl) + al256(sizeof(double) * nd * S) * 4 + al256(sizeof(double) * nd * S * NA) +
-                      al256(sizeof(double) * nd * nd * S) + al256(sizeof(double) * n_small) + 65536;
-  rc = arena_reserve(c, need);
-  if (rc) { plan_free(pl); plan_free(p); return rc; }
-  c->arena_top = 0;
-  double* d_aos = arena_take<double>(c, (size_t)nd * J);
-  double* d_X = arena_take<double>(c, (size_t)nd * J);
-  double* d_X2 = arena_take<double>(c, (size_t)nd * J);
-  double* d_del = arena_take<double>(c, (size_t)nd * J);
-  double* d_del2 = arena_take<double>(c, (size_t)nd * J);
-  double* d_Xt = arena_take<double>(c, (size_t)nd * J * NA);
-  double* d_t = arena_take<double>(c, (size_t)n * n_tgrids);
-  double* d_tl = (n_tgrids == 1) ? d_t : arena_take<double>(c, (size_t)n * ntl);
-  double* d_def = arena_take<double>(c, (size_t)nd * S);
-  double* d_def2 = arena_take<double>(c, (size_t)nd * S);
-  double* d_defj = arena_take<double>(c, (size_t)nd * S);   // the STM sweep's own defect (right-hand side of the step); d_def stays defectCalc's
-  double* d_def_aos = arena_take<double>(c, (size_t)nd * S);
-  double* d_deft = arena_take<double>(c, (size_t)nd * S * NA);
-  double* d_phi = arena_take<double>(c, (size_t)nd * nd * S);
-  double* d_small = arena_take<double>(c, n_small);
+  double *d_aos, *d_X, *d_X2, *d_del, *d_del2, *d_Xt, *d_t, *d_tl, *d_def, *d_def2, *d_defj, *d_def_aos, *d_deft, *d_phi, *d_small;
+  ArenaLayout scratch;
+  scratch.add((size_t)nd * J, d_aos, d_X, d_X2, d_del, d_del2);
+  scratch.add((size_t)nd * J * NA, d_Xt);
+  scratch.add((size_t)n * n_tgrids, d_t);
+  if (n_tgrids != 1) scratch.add((size_t)n * ntl, d_tl);
+  // d_defj: the STM sweep's own defect (right-hand side of the step); d_def stays defectCalc's
+  scratch.add((size_t)nd * S, d_def, d_def2, d_defj, d_def_aos);
+  scratch.add((size_t)nd * S * NA, d_deft);
+  scratch.add((size_t)nd * nd * S, d_phi);
+  scratch.add(n_small, d_small);
+  rc = scratch.reserve(c);
+  if (rc) return rc;
+  if (n_tgrids == 1) d_tl = d_t;
   double* d_saved = d_small;                               // [B][nd] pinned end states (12: 6 + 6, 14: 7 + 7)
   double* d_alphas = d_saved + (size_t)nd * B;             // [NA]   trial step lengths
   double* d_step = d_alphas + NA;                          // [B]    step length / SOC mask per trajectory
@@ -1341,23 +1426,14 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
   double* d_mxt = d_mxdel + B;                             // [NA*B] per-trial max |defect|
   (void)report_reserve(c, (size_t)3 * B);
   hipStream_t st = c->stream;
-  double alphas[NA];
-  for (int a = 0; a < NA; ++a) alphas[a] = 0.1 + (1.0 - 0.1) / (NA - 1) * a;
-  alphas[NA - 1] = 1.0;
-  lto::HostBuf<double> h_mx(B), h_er(B, 1.0), h_step(B), h_back((size_t)3 * B), h_act(B, -1.0), h_search(B, -1.0);   // er = 1.0: :279
   bool soc_speculative = false;
   unsigned trial_sweeps = 0;
-  lto::HostBuf<int> it(B, 0), status(B, 0);
-  lto::HostBuf<char> active(B, 1);
-  if (!h_mx.ok() || !h_er.ok() || !h_step.ok() || !h_back.ok() || !h_act.ok() || !h_search.ok() || !it.ok() || !status.ok() || !active.ok()) {
-    plan_free(pl); plan_free(p);
-    return set_err(c, LTO_ENOMEM, "lto_indirect_solve_batch: out of host memory");
-  }
+  if (!nb.ok() || !h_mx.ok() || !h_step.ok() || !h_back.ok()) return set_err(c, LTO_ENOMEM, "lto_indirect_solve_batch: out of host memory");
 
   hipError_t e = hipMemcpyAsync(d_aos, XC_in, sizeof(double) * nd * J, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n * n_tgrids, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && n_tgrids != 1) e = hipMemcpyAsync(d_tl, t_l.data(), sizeof(double) * n * ntl, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_alphas, alphas, sizeof alphas, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_alphas, nb.alphas.data(), sizeof(double) * NA, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = launch_pack_soa(d_aos, nd, J, d_X, J, st);
   // state_0, state_f  (:270-271); 14-dim: also m0, and lambda_m(tf) set to 0 (free final mass)
   if (e == hipSuccess) e = launch_end_pins(d_X, J, n_nodes, B, nd, d_saved, 0, st);
@@ -1370,32 +1446,17 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
     if (q == hipSuccess) q = hipStreamSynchronize(st);
     return q == hipSuccess ? LTO_OK : set_err(c, LTO_EHIP, "norm", q);
   };
-  auto any_active = [&]() { for (int b = 0; b < B; ++b) if (active[b]) return true; return false; };
 
   if (rc == LTO_OK) rc = lto_indirect_defect_dev(p, st, d_X, J, d_t, n_tgrids, d_def, S, nullptr);      // :274
-  while (rc == LTO_OK && any_active()) {
-    // `while er > 1e-10` (:280) + the iteration limit (:281-286), trajectory by trajectory
-    for (int b = 0; b < B; ++b) {
-      if (!active[b]) continue;
-      if (!(h_er[b] > 1e-10)) { active[b] = 0; continue; }            // converged, or NaN (the comparison is false)
-      if (++it[b] > maxIter) { status[b] = 1; active[b] = 0; }
-    }
-    if (!any_active()) break;
+  // `while er > 1e-10` (:280) + the iteration limit (:281-286), trajectory by trajectory
+  while (rc == LTO_OK && nb.next(1e-10, maxIter)) {
     // Round 4: the loop's decisions are taken on the device -- the second-order-correction mask from max |xc_update| (:190) and the
     // line search's first minimiser (:244-245) -- so the host reads back ONCE per iteration (max |defect|, the step lengths and
     // max |xc_update| together) instead of three times.  While the last known max |xc_update| of some active trajectory is
     // >= 0.1 the correction is still decided on the host (one more read-back, but a defect sweep and a re-solve whose result would
     // be discarded are not launched); once every active trajectory has been below, it is computed for all and applied by mask.
-    bool flags_changed = false;
-    for (int b = 0; b < B; ++b) {
-      const double fa = active[b] ? 1.0 : 0.0, fs = (active[b] && it[b] > 3) ? 1.0 : 0.0;
-      if (fa != h_act[b] || fs != h_search[b]) { h_act[b] = fa; h_search[b] = fs; flags_changed = true; }
-    }
-    if (flags_changed) {
-      e = hipMemcpyAsync(d_act, h_act.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_search, h_search.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "flag upload", e); break; }
-    }
+    e = nb.upload_flags(3, d_act, d_search, st);                                                      // line search from iteration 4
+    if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "flag upload", e); break; }
     rc = lto_indirect_jacobian_dev(p, st, d_X, J, d_t, n_tgrids, d_phi, S, d_defj, S);             // :290
     // large adaptive problems: the next sweeps of this plan run with the lanes ordered by this sweep's step counts
     if (rc == LTO_OK && host_order_wanted(p, true)) rc = lto_indirect_plan_rebalance(p, st);
@@ -1409,7 +1470,7 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
       rc = read_scalars(c, st, d_mxdel, B, nullptr, 0, h_mx.data());
       if (rc != LTO_OK) break;
       soc = false;
-      for (int b = 0; b < B; ++b) soc |= (active[b] && h_mx[b] == h_mx[b] && h_mx[b] < 1e-1);
+      for (int b = 0; b < B; ++b) soc |= (nb.active[b] && h_mx[b] == h_mx[b] && h_mx[b] < 1e-1);
     }
     if (soc) {
       e = launch_axpy(d_X, d_del, 1.0, d_X2, nd * J, st);
@@ -1421,7 +1482,7 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
       if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "axpy", e); break; }
     }
     bool search = false, all_search = true;
-    for (int b = 0; b < B; ++b) if (active[b]) { search |= it[b] > 3; all_search &= it[b] > 3; }
+    for (int b = 0; b < B; ++b) if (nb.active[b]) { search |= nb.it[b] > 3; all_search &= nb.it[b] > 3; }
     if (search) {                                          // :300-302: the 20 trial trajectories of every problem, one sweep
       e = launch_trial_points(d_X, d_del, J, nd, n_nodes, B, NA, d_alphas, d_Xt, J * NA, st);
       if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "trial points", e); break; }
@@ -1455,16 +1516,16 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
     for (int b = 0; b < B; ++b) {
       h_step[b] = h_back[b]; h_mx[b] = h_back[B + b];
       const double md = h_back[2 * B + b];
-      if (active[b] && !(md < 1e-1)) soc_speculative = false;        // somebody is still taking big steps (or NaN): decide on the host next time
+      if (nb.active[b] && !(md < 1e-1)) soc_speculative = false;     // somebody is still taking big steps (or NaN): decide on the host next time
     }
     for (int b = 0; b < B; ++b) {
-      if (!active[b]) continue;
-      h_er[b] = h_mx[b];
-      if (history && it[b] <= maxIter) {
-        history[((size_t)b * maxIter + (it[b] - 1)) * 2] = h_er[b];
-        history[((size_t)b * maxIter + (it[b] - 1)) * 2 + 1] = h_step[b];
+      if (!nb.active[b]) continue;
+      nb.h_er[b] = h_mx[b];
+      if (history && nb.it[b] <= maxIter) {
+        history[((size_t)b * maxIter + (nb.it[b] - 1)) * 2] = nb.h_er[b];
+        history[((size_t)b * maxIter + (nb.it[b] - 1)) * 2 + 1] = h_step[b];
       }
-      if (h_er[b] > 1e3) it[b] += 100;                     // "Not likely to converge. Aborting." (:333-336)
+      if (nb.h_er[b] > 1e3) nb.it[b] += 100;               // "Not likely to converge. Aborting." (:333-336)
     }
   }
   if (rc == LTO_OK) {
@@ -1474,19 +1535,16 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
       e = launch_unpack_soa(d_def, S, nd, S, d_def_aos, st);
       if (e == hipSuccess) e = hipMemcpyAsync(defect, d_def_aos, sizeof(double) * nd * S, hipMemcpyDeviceToHost, st);
     }
-    if (e == hipSuccess) e = max_abs(d_def, S, n - 1, h_mx.data()) == LTO_OK ? hipSuccess : hipErrorUnknown;
+    if (e == hipSuccess) e = max_abs(d_def, S, n - 1, h_mx.data()) == LTO_OK ? hipSuccess : hipErrorUnknown;   // (ends in a stream synchronise)
+    call.idle = e == hipSuccess;
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
     // :339-341 flags a NaN trajectory; a NaN defect leaves the loop the same way (NaN > 1e-10 is false), so both
     // report status 2 here, as drivers.multiShoot_CRTBP_indirect does
     if (rc == LTO_OK)
       for (int b = 0; b < B; ++b)
-        if (XC_out[(size_t)nd * n * b] != XC_out[(size_t)nd * n * b] || h_mx[b] != h_mx[b]) status[b] = 2;
-  } else {
-    (void)hipStreamSynchronize(st);
+        if (XC_out[(size_t)nd * n * b] != XC_out[(size_t)nd * n * b] || h_mx[b] != h_mx[b]) nb.status[b] = 2;
   }
-  for (int b = 0; b < B; ++b) { status_flag[b] = status[b]; if (iterations) iterations[b] = it[b]; }
-  plan_free(pl);
-  plan_free(p);
+  nb.copy_out(status_flag, iterations);
   return rc;
 }
 
@@ -1711,19 +1769,6 @@ int lto_defect_norms_dev(lto_ctx* c, void* stream, const double* defect, long ld
  * stream synchronise.  The caller's buffers are only touched inside the call.  Pass buffers from lto_host_alloc
  * (page-locked) and the copies are plain DMA at link speed; pageable buffers are staged by the HIP runtime. */
 
-// End of a host-pointer call: poll the stream for up to ~1 ms before blocking in the runtime.  A 4 096-segment sweep is
-// over in 0.2 ms, and the wake-up of a blocked hipStreamSynchronize is a visible part of that.
-static hipError_t stream_wait(hipStream_t st) {
-  const auto give_up = std::chrono::steady_clock::now() + std::chrono::milliseconds(1);
-  do {
-    for (int k = 0; k < 16; ++k) {
-      const hipError_t q = hipStreamQuery(st);
-      if (q != hipErrorNotReady) return q;
-    }
-  } while (std::chrono::steady_clock::now() < give_up);
-  return hipStreamSynchronize(st);
-}
-
 // Device view of a caller's buffer that lies wholly inside a block from lto_host_alloc; nullptr for any other memory.
 static double* pinned_view(lto_ctx* c, const double* host, size_t bytes) {
   const char* h = (const char*)host;
@@ -1867,31 +1912,27 @@ int lto_indirect_defect(lto_ctx* c, int ndim, int n_nodes, int n_batch, const do
   int rc = host_plan_acquire(c, ndim, n_nodes, n_batch, prm, n_prm, integ, &p);   // cached between calls, owned by the context
   if (rc) return rc;
   const long J = (long)n_nodes * n_batch, S = p->S;
-  const size_t need = al256(sizeof(double) * ndim * J) * 2 + al256(sizeof(double) * n_nodes * n_tgrids) +
-                      al256(sizeof(double) * ndim * S) * 2 + al256(sizeof(double) * S) + 4096;
-  rc = arena_reserve(c, need);
+  double *d_aos, *d_X, *d_t, *d_def, *d_def_aos, *d_err;
+  ArenaLayout scratch;
+  scratch.add((size_t)ndim * J, d_aos, d_X);
+  scratch.add((size_t)n_nodes * n_tgrids, d_t);
+  scratch.add((size_t)ndim * S, d_def, d_def_aos);
+  scratch.add((size_t)S, d_err);
+  rc = scratch.reserve(c);
   if (rc) return rc;
-  c->arena_top = 0;
-  double* d_aos = arena_take<double>(c, (size_t)ndim * J);
-  double* d_X = arena_take<double>(c, (size_t)ndim * J);
-  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
-  double* d_def = arena_take<double>(c, (size_t)ndim * S);
-  double* d_def_aos = arena_take<double>(c, (size_t)ndim * S);
-  double* d_err = arena_take<double>(c, (size_t)S);
+  HostCall call(c);
   hipStream_t st = c->stream;
   hipError_t e = stage_in(c, XC, ndim, J, d_aos, d_X, J, st);
   if (e == hipSuccess) e = vec_in(c, t, (long)n_nodes * n_tgrids, d_t, st);
-  if (e != hipSuccess) { (void)hipStreamSynchronize(st); return set_err(c, LTO_EHIP, "stage in", e); }
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "stage in", e);
   host_order_adopt(c, p, false);
   rc = lto_indirect_defect_dev(p, st, d_X, J, d_t, n_tgrids, d_def, S, errors ? d_err : nullptr);
   if (rc == LTO_OK) host_order_refresh(c, p, false, st);
   if (rc == LTO_OK) {
     e = stage_out(c, d_def, S, ndim, S, d_def_aos, defect, st);
     if (e == hipSuccess && errors) e = vec_out(c, d_err, S, errors, st);
-    if (e == hipSuccess) e = stream_wait(st);
+    if (e == hipSuccess) e = call.wait();
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
-  } else {
-    (void)hipStreamSynchronize(st);
   }
   return rc;
 }
@@ -1907,18 +1948,15 @@ int lto_indirect_jacobian(lto_ctx* c, int ndim, int n_nodes, int n_batch, const 
   if (rc) return rc;
   const long J = (long)n_nodes * n_batch, S = p->S;
   const int nn = ndim * ndim;
-  const size_t need = al256(sizeof(double) * ndim * J) * 2 + al256(sizeof(double) * n_nodes * n_tgrids) +
-                      al256(sizeof(double) * ndim * S) * 2 + al256(sizeof(double) * nn * S) * 2 + 4096;
-  rc = arena_reserve(c, need);
+  double *d_aos, *d_X, *d_t, *d_def, *d_def_aos, *d_phi, *d_phi_aos;
+  ArenaLayout scratch;
+  scratch.add((size_t)ndim * J, d_aos, d_X);
+  scratch.add((size_t)n_nodes * n_tgrids, d_t);
+  scratch.add((size_t)ndim * S, d_def, d_def_aos);
+  scratch.add((size_t)nn * S, d_phi, d_phi_aos);
+  rc = scratch.reserve(c);
   if (rc) return rc;
-  c->arena_top = 0;
-  double* d_aos = arena_take<double>(c, (size_t)ndim * J);
-  double* d_X = arena_take<double>(c, (size_t)ndim * J);
-  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
-  double* d_def = arena_take<double>(c, (size_t)ndim * S);
-  double* d_def_aos = arena_take<double>(c, (size_t)ndim * S);
-  double* d_phi = arena_take<double>(c, (size_t)nn * S);
-  double* d_phi_aos = arena_take<double>(c, (size_t)nn * S);
+  HostCall call(c);
   hipStream_t st = c->stream;
   // all operands page-locked: node array and time grid come in with one launch, STM and defect leave with one
   const long nt = (long)n_nodes * n_tgrids;
@@ -1933,7 +1971,7 @@ int lto_indirect_jacobian(lto_ctx* c, int ndim, int n_nodes, int n_batch, const 
     e = stage_in(c, XC, ndim, J, d_aos, d_X, J, st);
     if (e == hipSuccess) e = vec_in(c, t, nt, d_t, st);
   }
-  if (e != hipSuccess) { (void)hipStreamSynchronize(st); return set_err(c, LTO_EHIP, "stage in", e); }
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "stage in", e);
   host_order_adopt(c, p, true);
   rc = lto_indirect_jacobian_dev(p, st, d_X, J, d_t, n_tgrids, d_phi, S, d_def, S);
   if (rc == LTO_OK) host_order_refresh(c, p, true, st);
@@ -1944,10 +1982,8 @@ int lto_indirect_jacobian(lto_ctx* c, int ndim, int n_nodes, int n_batch, const 
       e = stage_out(c, d_phi, S, nn, S, d_phi_aos, Phi, st);
       if (e == hipSuccess && defect) e = stage_out(c, d_def, S, ndim, S, d_def_aos, defect, st);
     }
-    if (e == hipSuccess) e = stream_wait(st);
+    if (e == hipSuccess) e = call.wait();
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
-  } else {
-    (void)hipStreamSynchronize(st);
   }
   return rc;
 }
@@ -1960,12 +1996,13 @@ int lto_indirect_densify(lto_ctx* c, int ndim, int n_nodes, const double* XC, co
   if (!c) return LTO_ENULL;
   if (!XC || !t || !XC_dense || !t_dense) return set_err(c, LTO_ENULL, "XC, t, XC_dense or t_dense is NULL");
   if (n_desired < 2) return set_err(c, LTO_EINVAL, "n_desired must be >= 2");
-  lto_indirect_plan* p = nullptr;
-  int rc = plan_build(c, ndim, n_nodes, 1, prm, 1, integ, &p);
+  lto::HostBuf<int> h_first;
+  HostCall call(c);
+  int rc = plan_build(c, ndim, n_nodes, 1, prm, 1, integ, &call.plan[0]);
   if (rc) return rc;
+  lto_indirect_plan* p = call.plan[0];
   const int S = p->S;
-  int* h_first = (int*)std::malloc(sizeof(int) * (size_t)(S + 1));
-  if (!h_first) { plan_free(p); return set_err(c, LTO_EHIP, "host allocation failed"); }
+  if (!h_first.alloc((size_t)S + 1)) return set_err(c, LTO_EHIP, "host allocation failed");
   const double t0 = t[0], tn = t[n_nodes - 1];
   for (int k = 0; k < n_desired; ++k) {
     const double tau = (double)k / (double)(n_desired - 1);
@@ -1979,25 +2016,23 @@ int lto_indirect_densify(lto_ctx* c, int ndim, int n_nodes, const double* XC, co
   }
   h_first[S] = n_desired - 1;
   const long J = n_nodes;
-  const size_t need = al256(sizeof(double) * ndim * J) * 2 + al256(sizeof(double) * n_nodes) + al256(sizeof(int) * (S + 1)) +
-                      al256(sizeof(double) * n_desired) * 2 + al256(sizeof(double) * ndim * n_desired) * 2 + 8192;
-  rc = arena_reserve(c, need);
-  if (rc) { std::free(h_first); plan_free(p); return rc; }
-  c->arena_top = 0;
-  double* d_aos = arena_take<double>(c, (size_t)ndim * J);
-  double* d_X = arena_take<double>(c, (size_t)ndim * J);
-  double* d_t = arena_take<double>(c, (size_t)n_nodes);
-  int* d_first = arena_take<int>(c, (size_t)S + 1);
-  double* d_td = arena_take<double>(c, (size_t)n_desired);
-  double* d_Y = arena_take<double>(c, (size_t)ndim * n_desired);
-  double* d_Yaos = arena_take<double>(c, (size_t)ndim * n_desired);
+  double *d_aos, *d_X, *d_t, *d_td, *d_Y, *d_Yaos;
+  int* d_first;
+  ArenaLayout scratch;
+  scratch.add((size_t)ndim * J, d_aos, d_X);
+  scratch.add((size_t)n_nodes, d_t);
+  scratch.add((size_t)S + 1, d_first);
+  scratch.add((size_t)n_desired, d_td);
+  scratch.add((size_t)ndim * n_desired, d_Y, d_Yaos);
+  rc = scratch.reserve(c);
+  if (rc) return rc;
   hipStream_t st = c->stream;
   hipError_t e = hipMemcpyAsync(d_aos, XC, sizeof(double) * ndim * J, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n_nodes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_first, h_first, sizeof(int) * (S + 1), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_first, h_first.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_td, t_dense, sizeof(double) * n_desired, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = launch_pack_soa(d_aos, ndim, J, d_X, J, st);
-  if (e != hipSuccess) { (void)hipStreamSynchronize(st); std::free(h_first); plan_free(p); return set_err(c, LTO_EHIP, "stage in", e); }
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "stage in", e);
   // the final state lands in the last column of Y: final_state[c * n_batch + traj] with ld = n_desired, offset n_desired-1
   // is not expressible through the [ND][n_batch] layout, so take it into the tail of d_Yaos and splice on the host side
   double* d_final = d_Yaos;   // [ndim] (n_batch = 1); overwritten by the unpack afterwards, so copy it out first
@@ -2008,13 +2043,9 @@ int lto_indirect_densify(lto_ctx* c, int ndim, int n_nodes, const double* XC, co
       e = hipMemcpyAsync(d_Y + (size_t)cc * n_desired + (n_desired - 1), d_final + cc, sizeof(double), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = launch_unpack_soa(d_Y, n_desired, ndim, n_desired, d_Yaos, st);
     if (e == hipSuccess) e = hipMemcpyAsync(XC_dense, d_Yaos, sizeof(double) * ndim * n_desired, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = stream_wait(st);
+    if (e == hipSuccess) e = call.wait();
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
-  } else {
-    (void)hipStreamSynchronize(st);
   }
-  std::free(h_first);
-  plan_free(p);
   return rc;
 }
 
@@ -2022,36 +2053,28 @@ static int direct_host(lto_ctx* c, int nstate, int n_nodes, int n_batch, const d
                        int n_tgrids, int nsteps, const lto_direct_params* prm, double* Jac_temp, double* ddefect_dtf,
                        double* defect, double* errors, bool want_jac, double* x_mid = nullptr) {
   CallTimer call_timer(c);
-  lto_direct_plan* p = nullptr;
-  int rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &p);
+  HostCall call(c);
+  int rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &call.dplan[0]);
   if (rc) return rc;
-  if (n_tgrids != 1 && n_tgrids != n_batch) { delete p; return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch"); }
+  lto_direct_plan* p = call.dplan[0];
+  if (n_tgrids != 1 && n_tgrids != n_batch) return set_err(c, LTO_EINVAL, "n_tgrids must be 1 or n_batch");
   const long J = (long)n_nodes * n_batch, S = p->S;
   const int nvar = 2 * (nstate + 3), nj = nstate * nvar;
-  size_t need = al256(sizeof(double) * nstate * J) * 2 + al256(sizeof(double) * 3 * J) * 2 +
-                al256(sizeof(double) * n_nodes * n_tgrids) + al256(sizeof(double) * nstate * S) * 4 +
-                al256(sizeof(double) * S) + 8192;
-  if (want_jac) need += al256(sizeof(double) * nj * S) * 2;
-  rc = arena_reserve(c, need);
-  if (rc) { delete p; return rc; }
-  c->arena_top = 0;
-  double* d_xa = arena_take<double>(c, (size_t)nstate * J);
-  double* d_X = arena_take<double>(c, (size_t)nstate * J);
-  double* d_ua = arena_take<double>(c, (size_t)3 * J);
-  double* d_U = arena_take<double>(c, (size_t)3 * J);
-  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
-  double* d_def = arena_take<double>(c, (size_t)nstate * S);
-  double* d_def_aos = arena_take<double>(c, (size_t)nstate * S);
-  double* d_dtf = arena_take<double>(c, (size_t)nstate * S);
-  double* d_dtf_aos = arena_take<double>(c, (size_t)nstate * S);
-  double* d_err = arena_take<double>(c, (size_t)S);
-  double* d_jac = want_jac ? arena_take<double>(c, (size_t)nj * S) : nullptr;
-  double* d_jac_aos = want_jac ? arena_take<double>(c, (size_t)nj * S) : nullptr;
+  double *d_xa, *d_X, *d_ua, *d_U, *d_t, *d_def, *d_def_aos, *d_dtf, *d_dtf_aos, *d_err, *d_jac = nullptr, *d_jac_aos = nullptr;
+  ArenaLayout scratch;
+  scratch.add((size_t)nstate * J, d_xa, d_X);
+  scratch.add((size_t)3 * J, d_ua, d_U);
+  scratch.add((size_t)n_nodes * n_tgrids, d_t);
+  scratch.add((size_t)nstate * S, d_def, d_def_aos, d_dtf, d_dtf_aos);
+  scratch.add((size_t)S, d_err);
+  if (want_jac) scratch.add((size_t)nj * S, d_jac, d_jac_aos);
+  rc = scratch.reserve(c);
+  if (rc) return rc;
   hipStream_t st = c->stream;
   hipError_t e = stage_in(c, X, nstate, J, d_xa, d_X, J, st);
   if (e == hipSuccess) e = stage_in(c, U, 3, J, d_ua, d_U, J, st);
   if (e == hipSuccess) e = vec_in(c, t, (long)n_nodes * n_tgrids, d_t, st);
-  if (e != hipSuccess) { delete p; return set_err(c, LTO_EHIP, "stage in", e); }
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "stage in", e);
   if (want_jac)
     rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, d_t, n_tgrids, d_jac, S, d_dtf, d_def, S, d_err);
   else   // the dtf staging buffers are free on this path: they carry the mid-point states
@@ -2064,12 +2087,9 @@ static int direct_host(lto_ctx* c, int nstate, int n_nodes, int n_batch, const d
       e = stage_out(c, d_jac, S, nj, S, d_jac_aos, Jac_temp, st);
       if (e == hipSuccess && ddefect_dtf) e = stage_out(c, d_dtf, S, nstate, S, d_dtf_aos, ddefect_dtf, st);
     }
-    if (e == hipSuccess) e = stream_wait(st);
+    if (e == hipSuccess) e = call.wait();
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
-  } else {
-    (void)hipStreamSynchronize(st);
   }
-  delete p;
   return rc;
 }
 
@@ -2250,23 +2270,22 @@ int lto_direct_end_states(lto_ctx* c, const lto_direct_orbits* orbits, int n_bat
   int rc = bind_device(c);
   if (rc) return rc;
   CallTimer call_timer(c);
-  hipStream_t st = c->stream;
   DevOrbits dob;
+  HostCall call(c);
+  hipStream_t st = c->stream;
   rc = orbits_upload(c, orbits, dob, st);
   if (rc) return rc;
-  double* d = nullptr;
   const size_t nd = (size_t)n_batch * (2 + 12 + 14);
-  hipError_t e = hipMalloc(&d, sizeof(double) * nd);
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_direct_end_states", e);
-  double* d_tau = d;
-  double* d_s = d + 2 * (size_t)n_batch;
+  hipError_t e = hipMalloc(&call.block[0], sizeof(double) * nd);
+  if (e != hipSuccess) { call.block[0] = nullptr; return set_err(c, LTO_EHIP, "lto_direct_end_states", e); }
+  double* d_tau = (double*)call.block[0];
+  double* d_s = d_tau + 2 * (size_t)n_batch;
   double* d_m = d_s + 12 * (size_t)n_batch;
   e = hipMemcpyAsync(d_tau, tau, sizeof(double) * 2 * n_batch, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = launch_end_states(dob.o, d_tau, n_batch, d_s, 12, d_m, st);
   if (e == hipSuccess) e = hipMemcpyAsync(s_out, d_s, sizeof(double) * 12 * n_batch, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(model, d_m, sizeof(double) * 14 * n_batch, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = stream_wait(st);
-  (void)hipFree(d);
+  if (e == hipSuccess) e = call.wait();
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_direct_end_states", e);
   return LTO_OK;
 }
@@ -2294,17 +2313,17 @@ static int direct_qp_step_host(lto_ctx* c, const char* who, int nr, int nstate, 
   if ((n_targets != 1 && n_targets != n_batch) || (n_tgrids != 1 && n_tgrids != n_batch))
     return set_err(c, LTO_EINVAL, "n_targets / n_tgrids must be 1 or n_batch");
   CallTimer call_timer(c);
-  lto_direct_plan* p = nullptr;
-  rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &p);
-  if (rc) return rc;
   const int B = n_batch;
   const size_t nh = nr == 4 ? 5 * (size_t)B : nr == 3 ? (size_t)B : 0;   // beta [B] (| tf bounds [B][3] | tf [B])
   lto::HostBuf<lto_direct_targets> tg;
   lto::HostBuf<lto_direct_end_model> em(nr > 1 ? (size_t)B : 0);
   lto::HostBuf<double> hb(nh);
   lto::HostBuf<int> h_stat(B, 0);
+  HostCall call(c);
+  rc = direct_plan_build(c, nstate, n_nodes, n_batch, nsteps, prm, &call.dplan[0]);
+  if (rc) return rc;
+  lto_direct_plan* p = call.dplan[0];
   if (!direct_targets_expand(targets, n_targets, B, tg) || !em.ok() || !hb.ok() || !h_stat.ok()) {
-    direct_plan_free(p);
     std::snprintf(msg, sizeof msg, "%s: out of host memory", who);
     return set_err(c, LTO_ENOMEM, msg);
   }
@@ -2318,31 +2337,22 @@ static int direct_qp_step_host(lto_ctx* c, const char* who, int nr, int nstate, 
   }
   const long J = (long)n_nodes * B, S = p->S;
   const int nj = nstate * 2 * (nstate + 3);
-  const size_t need = al256(sizeof(double) * nstate * J) * 4 + al256(sizeof(double) * 3 * J) * 4 + al256(sizeof(double) * n_nodes * n_tgrids) +
-                      al256(sizeof(double) * nj * S) + al256(sizeof(double) * nstate * S) * (nr == 4 ? 2 : 1) +
-                      al256(sizeof(lto_direct_targets) * B) + al256(sizeof(lto_direct_end_model) * em.size()) +
-                      al256(sizeof(double) * 7 * B) * 3 + al256(sizeof(double) * nh) + 8192;
-  rc = arena_reserve(c, need);
-  if (rc) { direct_plan_free(p); return rc; }
-  c->arena_top = 0;
-  double* d_xa = arena_take<double>(c, (size_t)nstate * J);
-  double* d_X = arena_take<double>(c, (size_t)nstate * J);
-  double* d_dX = arena_take<double>(c, (size_t)nstate * J);
-  double* d_dXa = arena_take<double>(c, (size_t)nstate * J);
-  double* d_ua = arena_take<double>(c, (size_t)3 * J);
-  double* d_U = arena_take<double>(c, (size_t)3 * J);
-  double* d_dU = arena_take<double>(c, (size_t)3 * J);
-  double* d_dUa = arena_take<double>(c, (size_t)3 * J);
-  double* d_t = arena_take<double>(c, (size_t)n_nodes * n_tgrids);
-  double* d_jac = arena_take<double>(c, (size_t)nj * S);
-  double* d_def = arena_take<double>(c, (size_t)nstate * S);
-  double* d_dtf = nr == 4 ? arena_take<double>(c, (size_t)nstate * S) : nullptr;
-  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)B);
-  lto_direct_end_model* d_em = arena_take<lto_direct_end_model>(c, em.size());
-  double* d_dV = arena_take<double>(c, (size_t)7 * B);
-  double* d_cost = arena_take<double>(c, (size_t)7 * B);
-  double* d_p = arena_take<double>(c, (size_t)7 * B);
-  double* d_hb = arena_take<double>(c, nh);
+  double *d_xa, *d_X, *d_dX, *d_dXa, *d_ua, *d_U, *d_dU, *d_dUa, *d_t, *d_jac, *d_def, *d_dtf = nullptr, *d_dV, *d_cost, *d_p, *d_hb;
+  lto_direct_targets* d_tg;
+  lto_direct_end_model* d_em;
+  ArenaLayout scratch;
+  scratch.add((size_t)nstate * J, d_xa, d_X, d_dX, d_dXa);
+  scratch.add((size_t)3 * J, d_ua, d_U, d_dU, d_dUa);
+  scratch.add((size_t)n_nodes * n_tgrids, d_t);
+  scratch.add((size_t)nj * S, d_jac);
+  scratch.add((size_t)nstate * S, d_def);
+  if (nr == 4) scratch.add((size_t)nstate * S, d_dtf);
+  scratch.add((size_t)B, d_tg);
+  scratch.add(em.size(), d_em);
+  scratch.add((size_t)7 * B, d_dV, d_cost, d_p);
+  scratch.add(nh, d_hb);
+  rc = scratch.reserve(c);
+  if (rc) return rc;
   hipStream_t st = c->stream;
   hipError_t e = stage_in(c, X, nstate, J, d_xa, d_X, J, st);
   if (e == hipSuccess) e = stage_in(c, U, 3, J, d_ua, d_U, J, st);
@@ -2350,7 +2360,7 @@ static int direct_qp_step_host(lto_ctx* c, const char* who, int nr, int nstate, 
   if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * B, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && nr > 1) e = hipMemcpyAsync(d_em, em.data(), sizeof(lto_direct_end_model) * B, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && nr > 1) e = hipMemcpyAsync(d_hb, hb.data(), sizeof(double) * nh, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) { (void)hipStreamSynchronize(st); direct_plan_free(p); return set_err(c, LTO_EHIP, "stage in", e); }
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "stage in", e);
   rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, d_t, n_tgrids, d_jac, S, d_dtf, d_def, S, nullptr);
   if (rc == LTO_OK)
     rc = direct_qp_launch(p, st, nr, d_jac, S, d_def, S, d_X, J, d_U, J, d_t, n_tgrids, d_tg, allow_impulsive, d_dX, d_dU, d_dV, d_cost,
@@ -2362,14 +2372,11 @@ static int direct_qp_step_host(lto_ctx* c, const char* who, int nr, int nstate, 
     if (e == hipSuccess && nr > 1) e = hipMemcpyAsync(p_out, d_p, sizeof(double) * (nr - 1) * B, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * B, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(h_stat.data(), lto_direct_plan_qp_status(p), sizeof(int) * B, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = stream_wait(st);
+    if (e == hipSuccess) e = call.wait();
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
     for (int b = 0; b < B && rc == LTO_OK; ++b)
       if (h_stat[b]) rc = set_err(c, LTO_ESINGULAR, "the KKT system of a trajectory's QP step is singular (too few nodes to reach the terminal state?)");
-  } else {
-    (void)hipStreamSynchronize(st);
   }
-  direct_plan_free(p);
   return rc;
 }
 
@@ -2445,38 +2452,34 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
   }
   for (int b = 0; b < B; ++b) for (int a = 0; a < NA; ++a)
     std::memcpy(&tl[((size_t)b * NA + a) * n], &t1[(size_t)(n_tgrids == 1 ? 0 : b) * n], sizeof(double) * n);
-  lto_direct_plan* p = nullptr;
-  lto_direct_plan* pl = nullptr;
-  rc = direct_plan_build(c, nstate, n_nodes, B, nsteps, prm, &p);
+  DevOrbits dob;
+  NewtonBatch nb(B, NA);                                   // er = 1.0 (:488)
+  lto::HostBuf<double> h_back((size_t)(fe ? 7 : 4) * B);
+  lto::HostBuf<char> moved(B, 0);
+  HostCall call(c);
+  rc = direct_plan_build(c, nstate, n_nodes, B, nsteps, prm, &call.dplan[0]);
+  if (rc == LTO_OK) rc = direct_plan_build(c, nstate, n_nodes, B * NA, nsteps, prm, &call.dplan[1]);
   if (rc) return rc;
-  rc = direct_plan_build(c, nstate, n_nodes, B * NA, nsteps, prm, &pl);
-  if (rc) { direct_plan_free(p); return rc; }
+  lto_direct_plan* p = call.dplan[0];
+  lto_direct_plan* pl = call.dplan[1];                     // the line search's trial trajectories
   const size_t n_small = 6 * (size_t)B + 2 * (size_t)NA * B + NA + 64;
-  const size_t need = al256(sizeof(double) * nstate * J) * 3 + al256(sizeof(double) * 3 * J) * 3 + al256(sizeof(double) * (nstate + 3) * J * NA) +
-                      al256(sizeof(double) * n * n_tgrids) * 2 + al256(sizeof(double) * n * B * NA) + al256(sizeof(double) * nj * S) +
-                      al256(sizeof(double) * nstate * S) * 2 + al256(sizeof(double) * nstate * S * NA) + al256(sizeof(lto_direct_targets) * B) +
-                      al256(sizeof(double) * 6 * B) + al256(sizeof(double) * n_small) + 65536;
-  rc = arena_reserve(c, need);
-  if (rc) { direct_plan_free(pl); direct_plan_free(p); return rc; }
-  c->arena_top = 0;
-  double* d_aos = arena_take<double>(c, (size_t)nstate * J);
-  double* d_X = arena_take<double>(c, (size_t)nstate * J);
-  double* d_dX = arena_take<double>(c, (size_t)nstate * J);
-  double* d_uaos = arena_take<double>(c, (size_t)3 * J);
-  double* d_U = arena_take<double>(c, (size_t)3 * J);
-  double* d_dU = arena_take<double>(c, (size_t)3 * J);
-  double* d_Xt = arena_take<double>(c, (size_t)(nstate + 3) * J * NA);
+  double *d_aos, *d_X, *d_dX, *d_uaos, *d_U, *d_dU, *d_Xt, *d_t, *d_t1, *d_tl, *d_jac, *d_def, *d_def_aos, *d_deft, *d_dV, *d_small;
+  lto_direct_targets* d_tg;
+  ArenaLayout scratch;
+  scratch.add((size_t)nstate * J, d_aos, d_X, d_dX);
+  scratch.add((size_t)3 * J, d_uaos, d_U, d_dU);
+  scratch.add((size_t)(nstate + 3) * J * NA, d_Xt);
+  scratch.add((size_t)n * n_tgrids, d_t, d_t1);
+  scratch.add((size_t)n * B * NA, d_tl);
+  scratch.add((size_t)nj * S, d_jac);
+  scratch.add((size_t)nstate * S, d_def, d_def_aos);
+  scratch.add((size_t)nstate * S * NA, d_deft);
+  scratch.add((size_t)B, d_tg);
+  scratch.add((size_t)6 * B, d_dV);
+  scratch.add(n_small, d_small);
+  rc = scratch.reserve(c);
+  if (rc) return rc;
   double* d_Ut = d_Xt + (size_t)nstate * J * NA;
-  double* d_t = arena_take<double>(c, (size_t)n * n_tgrids);
-  double* d_t1 = arena_take<double>(c, (size_t)n * n_tgrids);
-  double* d_tl = arena_take<double>(c, (size_t)n * B * NA);
-  double* d_jac = arena_take<double>(c, (size_t)nj * S);
-  double* d_def = arena_take<double>(c, (size_t)nstate * S);
-  double* d_def_aos = arena_take<double>(c, (size_t)nstate * S);
-  double* d_deft = arena_take<double>(c, (size_t)nstate * S * NA);
-  lto_direct_targets* d_tg = arena_take<lto_direct_targets>(c, (size_t)B);
-  double* d_dV = arena_take<double>(c, (size_t)6 * B);
-  double* d_small = arena_take<double>(c, n_small);
   double* d_step = d_small;                                // [B]    step length (0 = frozen)      } read back together
   double* d_mx = d_step + B;                               // [B]    max |defect|                 }
   double* d_cost = d_mx + B;                               // [B]    QP objective                 } read back together
@@ -2490,9 +2493,6 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
   hipStream_t st = c->stream;
   // free ends: tau [2B] | tf [B] | p [3B] | end model [14B] | beta [B] | tf bounds [3B] | t0 [B] on the device, the orbit tables with
   // their spline moments; free tf also: the grids [B][n] | tau_grid [B][n] | the tf column [nstate][S]
-  DevOrbits dob;
-  double* d_fe = nullptr;
-  double* d_tfx = nullptr;
   double *d_tau = nullptr, *d_tf = nullptr, *d_p = nullptr, *d_em = nullptr, *d_beta = nullptr, *d_tfb = nullptr, *d_t0 = nullptr;
   double *d_tb = nullptr, *d_taug = nullptr, *d_dtf = nullptr;
   if (fe) {
@@ -2501,10 +2501,10 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     if (rc == LTO_OK && (!hb.ok() || !hg.ok())) rc = set_err(c, LTO_ENOMEM, "lto_direct_solve_free_batch: out of host memory");
     if (rc == LTO_OK) {
       for (int b = 0; b < B; ++b) hb[b] = fe->beta[n_targets == 1 ? 0 : b];
-      hipError_t e0 = hipMalloc(&d_fe, sizeof(double) * 25 * B);
-      if (e0 != hipSuccess) { d_fe = nullptr; rc = set_err(c, LTO_EHIP, "free-end buffers", e0); }
+      hipError_t e0 = hipMalloc(&call.block[0], sizeof(double) * 25 * B);
+      if (e0 != hipSuccess) { call.block[0] = nullptr; rc = set_err(c, LTO_EHIP, "free-end buffers", e0); }
       else {
-        d_tau = d_fe; d_tf = d_tau + 2 * (size_t)B; d_p = d_tf + B; d_em = d_p + 3 * (size_t)B; d_beta = d_em + 14 * (size_t)B;
+        d_tau = (double*)call.block[0]; d_tf = d_tau + 2 * (size_t)B; d_p = d_tf + B; d_em = d_p + 3 * (size_t)B; d_beta = d_em + 14 * (size_t)B;
         d_tfb = d_beta + B; d_t0 = d_tfb + 3 * (size_t)B;
         e0 = hipMemcpyAsync(d_tau, fe->tau_in, sizeof(double) * 2 * B, hipMemcpyHostToDevice, st);
         if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_beta, hb.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
@@ -2521,10 +2521,10 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
               hg[(size_t)(B + b) * n + k] = (g[k] - g[0]) / (g[n - 1] - g[0]) * 2.0 - 1.0;
             }
           }
-          e0 = hipMalloc(&d_tfx, sizeof(double) * (2 * (size_t)n * B + (size_t)nstate * S));
-          if (e0 != hipSuccess) d_tfx = nullptr;
+          e0 = hipMalloc(&call.block[1], sizeof(double) * (2 * (size_t)n * B + (size_t)nstate * S));
+          if (e0 != hipSuccess) call.block[1] = nullptr;
           else {
-            d_tb = d_tfx; d_taug = d_tb + (size_t)n * B; d_dtf = d_taug + (size_t)n * B;
+            d_tb = (double*)call.block[1]; d_taug = d_tb + (size_t)n * B; d_dtf = d_taug + (size_t)n * B;
             e0 = hipMemcpyAsync(d_tf, &hb[B], sizeof(double) * B, hipMemcpyHostToDevice, st);
             if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_t0, &hb[2 * (size_t)B], sizeof(double) * B, hipMemcpyHostToDevice, st);
             if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_tfb, &hb[3 * (size_t)B], sizeof(double) * 3 * B, hipMemcpyHostToDevice, st);
@@ -2536,32 +2536,16 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
       }
     }
     if (rc == LTO_OK && fe->flag_end) rc = direct_qp_workspace(p, tfm ? 4 : 3);
-    if (rc) {
-      if (d_fe) (void)hipFree(d_fe);
-      if (d_tfx) (void)hipFree(d_tfx);
-      p->qp_singular_out = nullptr; direct_plan_free(pl); direct_plan_free(p);
-      return rc;
-    }
+    if (rc) return rc;
   }
-  double alphas[NA];
-  for (int a = 0; a < NA; ++a) alphas[a] = 0.1 + (1.0 - 0.1) / (NA - 1) * a;
-  alphas[NA - 1] = 1.0;
-  lto::HostBuf<double> h_er(B, 1.0), h_back((size_t)(fe ? 7 : 4) * B), h_act(B, -1.0), h_search(B, -1.0);   // er = 1.0 (:488)
-  lto::HostBuf<int> it(B, 0), status(B, 0);
-  lto::HostBuf<char> active(B, 1), moved(B, 0);
-  if (!h_er.ok() || !h_back.ok() || !h_act.ok() || !h_search.ok() || !it.ok() || !status.ok() || !active.ok() || !moved.ok()) {
-    if (d_fe) (void)hipFree(d_fe);
-    if (d_tfx) (void)hipFree(d_tfx);
-    p->qp_singular_out = nullptr; direct_plan_free(pl); direct_plan_free(p);
-    return set_err(c, LTO_ENOMEM, "lto_direct_solve_batch: out of host memory");
-  }
+  if (!nb.ok() || !h_back.ok() || !moved.ok()) return set_err(c, LTO_ENOMEM, "lto_direct_solve_batch: out of host memory");
   hipError_t e = stage_in(c, X_in, nstate, J, d_aos, d_X, J, st);
   if (e == hipSuccess) e = stage_in(c, U_in, 3, J, d_uaos, d_U, J, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n * n_tgrids, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t1, t1.data(), sizeof(double) * n * n_tgrids, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_tl, tl.data(), sizeof(double) * n * B * NA, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_tg, tg.data(), sizeof(lto_direct_targets) * B, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_alphas, alphas, sizeof alphas, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_alphas, nb.alphas.data(), sizeof(double) * NA, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, sizeof(double) * 4 * B, st);
   // free ends: s0 and sf of the targets from tau (interpEndStates at the current tau, :339-349)
   if (e == hipSuccess && fe) e = launch_end_states(dob.o, d_tau, B, (double*)d_tg, 19, d_em, st);
@@ -2572,30 +2556,16 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
   const int ntg_qp = tfm ? B : n_tgrids;
 
   if (rc == LTO_OK) rc = lto_direct_defect_dev(p, st, d_X, J, d_U, J, t_cur, ntg_cur, d_def, S, nullptr);    // :485 (er = 1.0: one step at least)
-  auto any_active = [&]() { for (int b = 0; b < B; ++b) if (active[b]) return true; return false; };
-  while (rc == LTO_OK) {
-    // `while er > 1e-6` (:491) + the iteration limit (:492-496), trajectory by trajectory
-    for (int b = 0; b < B; ++b) {
-      if (!active[b]) continue;
-      if (!(h_er[b] > 1e-6)) { active[b] = 0; continue; }             // converged, or NaN (the comparison is false)
-      if (++it[b] > maxIter) { status[b] = 1; active[b] = 0; it[b] = maxIter; }
-    }
-    if (!any_active()) break;
-    bool flags_changed = false, search = false;
-    for (int b = 0; b < B; ++b) {
-      const double fa = active[b] ? 1.0 : 0.0, fs = (active[b] && it[b] > 10) ? 1.0 : 0.0;      // :557
-      search |= fs != 0.0;
-      if (fa != h_act[b] || fs != h_search[b]) { h_act[b] = fa; h_search[b] = fs; flags_changed = true; }
-    }
-    if (flags_changed) {
-      e = hipMemcpyAsync(d_act, h_act.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_search, h_search.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "flag upload", e); break; }
-    }
+  // `while er > 1e-6` (:491) + the iteration limit (:492-496), trajectory by trajectory
+  while (rc == LTO_OK && nb.next(1e-6, maxIter)) {
+    e = nb.upload_flags(10, d_act, d_search, st);                                                       // line search from iteration 11 (:557)
+    if (e != hipSuccess) { rc = set_err(c, LTO_EHIP, "flag upload", e); break; }
+    bool search = false;
+    for (int b = 0; b < B; ++b) search |= nb.h_search[b] != 0.0;
     // flagEnd: free ends on odd iterations, frozen on even ones (:521-526).  The active trajectories share the iteration count.
     bool free_it = false;
     if (fe && fe->flag_end)
-      for (int b = 0; b < B; ++b) if (active[b] && (it[b] & 1)) free_it = true;
+      for (int b = 0; b < B; ++b) if (nb.active[b] && (nb.it[b] & 1)) free_it = true;
     if (tfm && free_it)                                    // :500 with the tf column (:503-516)
       rc = lto_direct_jacobian_dev(p, st, d_X, J, d_U, J, t_cur, ntg_cur, d_jac, S, d_dtf, nullptr, S, nullptr);
     else
@@ -2634,19 +2604,18 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     rc = read_scalars(c, st, d_step, 4 * B, d_tau, fe ? (tfm ? 3 : 2) * B : 0, h_back.data());         // step | max|d| | cost | singular (| tau (| tf))
     if (rc != LTO_OK) break;
     for (int b = 0; b < B; ++b) {
-      if (!active[b]) continue;
+      if (!nb.active[b]) continue;
       moved[b] = 1;
-      h_er[b] = h_back[B + b];
+      nb.h_er[b] = h_back[B + b];
       if (history) {
-        double* hrow = history + ((size_t)b * maxIter + (it[b] - 1)) * hw;
-        hrow[0] = h_er[b]; hrow[1] = h_back[2 * B + b]; hrow[2] = h_back[b];
+        double* hrow = history + ((size_t)b * maxIter + (nb.it[b] - 1)) * hw;
+        hrow[0] = nb.h_er[b]; hrow[1] = h_back[2 * B + b]; hrow[2] = h_back[b];
         if (fe) { hrow[3] = h_back[4 * B + 2 * b]; hrow[4] = h_back[4 * B + 2 * b + 1]; }
         if (fe && fe->tfb) hrow[5] = tfm ? h_back[6 * B + b] : t[(size_t)(n_tgrids == 1 ? 0 : b) * n + n - 1];
       }
-      if (h_back[3 * B + b] != 0.0) { status[b] = 3; active[b] = 0; }
+      if (h_back[3 * B + b] != 0.0) { nb.status[b] = 3; nb.active[b] = 0; }
     }
   }
-  p->qp_singular_out = nullptr;
   if (rc == LTO_OK) {
     e = stage_out(c, d_X, J, nstate, J, d_aos, X_out, st);
     if (e == hipSuccess && U_out) e = stage_out(c, d_U, J, 3, J, d_uaos, U_out, st);
@@ -2657,24 +2626,19 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     lto::HostBuf<double> h_tb(tfm && t_out ? (size_t)n * B : 1);
     if (e == hipSuccess && tfm && t_out) e = h_tb.ok() ? hipMemcpyAsync(h_tb.data(), d_tb, sizeof(double) * n * B, hipMemcpyDeviceToHost, st)
                                                        : hipErrorOutOfMemory;
-    if (e == hipSuccess) e = stream_wait(st);
+    if (e == hipSuccess) e = call.wait();
     if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
     if (rc == LTO_OK)
       for (int b = 0; b < B; ++b)
-        if (status[b] != 3 && (X_out[(size_t)nstate * n * b] != X_out[(size_t)nstate * n * b] || h_er[b] != h_er[b])) status[b] = 2;
+        if (nb.status[b] != 3 && (X_out[(size_t)nstate * n * b] != X_out[(size_t)nstate * n * b] || nb.h_er[b] != nb.h_er[b])) nb.status[b] = 2;
     if (rc == LTO_OK && t_out)
       for (int b = 0; b < B; ++b) {
         const size_t g = (size_t)(n_tgrids == 1 ? 0 : b) * n;
         std::memcpy(t_out + (size_t)b * n, !moved[b] ? t + g : tfm ? &h_tb[(size_t)b * n] : &t1[g], sizeof(double) * n);
       }
-  } else {
-    (void)hipStreamSynchronize(st);
   }
-  for (int b = 0; b < B; ++b) { status_flag[b] = status[b]; if (iterations) iterations[b] = it[b]; }
-  if (d_fe) (void)hipFree(d_fe);
-  if (d_tfx) (void)hipFree(d_tfx);
-  direct_plan_free(pl);
-  direct_plan_free(p);
+  for (int b = 0; b < B; ++b) nb.it[b] = std::min(nb.it[b], maxIter);   // a trajectory that reached the limit reports maxIter (:492-496)
+  nb.copy_out(status_flag, iterations);
   return rc;
 }
 
