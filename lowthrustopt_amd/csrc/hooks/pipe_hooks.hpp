@@ -17,6 +17,7 @@ struct BarrierWait {
   __device__ __forceinline__ void sync() { __syncthreads(); }
   __device__ __forceinline__ int sync_or(const int pred) { return __syncthreads_or(pred); }
   __device__ __forceinline__ void report(double*, long, int, long) const {}          // (rows, ld, row, column)
+  __device__ __forceinline__ void report_edges(double*, long, int, long) const {}    // (rows, ld, first of four rows, column)
 };
 // ticks (s_memtime) and 100 MHz ticks of a region
 struct RegionClock {

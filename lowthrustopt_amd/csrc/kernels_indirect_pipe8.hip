@@ -40,6 +40,11 @@
 // columns: coefficients' first pass; w5: w4 -- so every wave reaches every barrier.  A poll that runs out (it cannot
 // while the producer runs) raises a workgroup flag that turns the workgroup's outputs into NaN instead of hanging.
 //
+// Edges (probe build, tools/probe_pipe8_edges.py; ticks at the contract size, 14-dim): the fill phase is ~5 000 (base steps 0, 1;
+// the column waves wait), the drain phase ~4 500 (the column waves' last two steps; base and coefficient waves wait), and after
+// the last barrier each wave stores its outputs.  The base wave loads the end node its defect needs (X at node + 1) during the drain
+// phase, before the last barrier: loaded after it, that load made the base wave's epilogue (~7 800 ticks) the workgroup's longest.
+//
 // For the always-thrust-limited control laws (p = 0, p = 1) of the 14-dim system nothing depends on lambda_m: the base
 // wave integrates 13 components, the coefficient wave -- which evaluates lambda_m_dot at every stage argument anyway --
 // accumulates lambda_m off the critical stream, and the STM column d/d lambda_m(t0) is the unit vector, so its lane stays
@@ -55,6 +60,8 @@ constexpr int P8_SPIN_LIMIT = 1 << 22;   // polls before a waiting wave gives up
 #define P8_SYNC() p8_wait.sync()
 #define P8_WAIT_DECL hook::BarrierWait p8_wait
 #define P8_WAIT_REPORT(a) do { if ((threadIdx.x & 63) == 0) p8_wait.report((a).defect, (a).ldd, 16, blockIdx.x * PIPE_SEG + (threadIdx.x >> 6)); } while (0)
+// ... and, at the end of a role, the ticks of its edges (fill, drain, epilogue; rows 20..23: tools/probe_pipe8_edges.py)
+#define P8_EDGES_REPORT(a) do { if ((threadIdx.x & 63) == 0) p8_wait.report_edges((a).defect, (a).ldd, 20, blockIdx.x * PIPE_SEG + (threadIdx.x >> 6)); } while (0)
 
 template <int ND, int PM> struct Pipe8 {
   using Arg = PipeArg<ND, PM>;
@@ -128,8 +135,8 @@ __device__ __forceinline__ void pipe8_role_base(const IndirectArgs& a, const Pip
   hook::RegionClock loop_clock;
   loop_clock.start();
   P8_WAIT_DECL;
-  for (int p = 0; p < npairs + 1; ++p) {
-    if (p < npairs && PIPE_ROLE_ON(a, 1) && (PIPE_ROLE_ON(a, 16) || slot == 0)) {
+  for (int p = 0; p < npairs; ++p) {
+    if (PIPE_ROLE_ON(a, 1) && (PIPE_ROLE_ON(a, 16) || slot == 0)) {
       for (int j = 0; j < 2; ++j) {
         const int step = 2 * p + j;
         if (step >= steps) break;
@@ -166,18 +173,24 @@ __device__ __forceinline__ void pipe8_role_base(const IndirectArgs& a, const Pip
     }
     P8_SYNC();
   }
+  // the drain phase: nothing to integrate, so the end node the defect needs is loaded while the column waves finish
+  double x1[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) x1[c] = a.X[c * a.ldx + L.node + 1];
+  P8_SYNC();
   P8_WAIT_REPORT(a);
   if (L.in_range && slot == 0) {
     const bool fail = fl->fail != 0;
     if (a.defect) {
 #pragma unroll
-      for (int c = 0; c < NB; ++c) a.defect[c * a.ldd + L.s] = fail ? __builtin_nan("") : y[c] - a.X[c * a.ldx + L.node + 1];
+      for (int c = 0; c < NB; ++c) a.defect[c * a.ldd + L.s] = fail ? __builtin_nan("") : y[c] - x1[c];
     }
     if (a.errors) a.errors[L.s] = 0.0;
     if (a.nacc) a.nacc[L.s] = steps;
     if (a.nrej) a.nrej[L.s] = 0;
     if (seg == 0) loop_clock.report(a.defect, a.ldd, 17, 18, L.s);     // probe build: ticks of the phase loop, per workgroup
   }
+  P8_EDGES_REPORT(a);
 }
 
 // ------------------------------------------------------------------------------------- base role, paired stages (round 3)
@@ -355,19 +368,25 @@ __device__ __forceinline__ void pipe8_role_base_paired(const IndirectArgs& a, co
     }
     if ((step & 1) || step == steps - 1) P8_SYNC();
   }
+  // the drain phase: the end node the defect needs is loaded while the column waves finish (after the barrier it cost the
+  // workgroup's longest epilogue)
+  double x1[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) x1[c] = a.X[c * a.ldx + L.node + 1];
   P8_SYNC();
   P8_WAIT_REPORT(a);
   if (L.in_range && q == 0) {
     const bool fail = fl->fail != 0;
     if (a.defect) {
 #pragma unroll
-      for (int c = 0; c < NB; ++c) a.defect[c * a.ldd + L.s] = fail ? __builtin_nan("") : y[c] - a.X[c * a.ldx + L.node + 1];
+      for (int c = 0; c < NB; ++c) a.defect[c * a.ldd + L.s] = fail ? __builtin_nan("") : y[c] - x1[c];
     }
     if (a.errors) a.errors[L.s] = 0.0;
     if (a.nacc) a.nacc[L.s] = steps;
     if (a.nrej) a.nrej[L.s] = 0;
     if (seg == 0) loop_clock.report(a.defect, a.ldd, 17, 18, L.s);     // probe build: ticks of the step loop, per workgroup
   }
+  P8_EDGES_REPORT(a);
 }
 
 // --------------------------------------------------------------------------------------------------- coefficient role
@@ -431,6 +450,7 @@ __device__ __forceinline__ void pipe8_role_coef(const IndirectArgs& a, const Pip
       a.defect[(ND - 1) * a.ldd + L.s] = fl->fail ? __builtin_nan("") : (a.X[r] + sum) - a.X[r + 1];
     }
   }
+  P8_EDGES_REPORT(a);
 }
 
 // STM column `col` of the lane's segment to global memory: y carries 3^k Phi (stm_scale undoes it); columns the row does
@@ -472,6 +492,7 @@ __device__ __forceinline__ void pipe8_role_columns(const IndirectArgs& a, const 
   }
   P8_WAIT_REPORT(a);
   pipe8_store_column<ND, P::NA>(a, L, col, y, fl->fail != 0);
+  P8_EDGES_REPORT(a);
 }
 
 // --------------------------------------------------------------- column role of the alternating job (segments 12..15)
@@ -533,6 +554,7 @@ __device__ __forceinline__ void pipe8_role_columns_alt(const IndirectArgs& a, co
     load();
     pipe8_store_column<ND, P::NA>(a, L, col, y, fl->fail != 0);
   }
+  P8_EDGES_REPORT(a);
 }
 
 // ------------------------------------------------------------------------------------------------------------- kernel

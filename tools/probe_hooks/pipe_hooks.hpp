@@ -11,9 +11,25 @@ constexpr bool kProbeBuild = true;
 
 struct BarrierWait {
   long long waited = 0;
-  __device__ __forceinline__ void sync() { const long long t = clock64(); __syncthreads(); waited += clock64() - t; }
+  // edges of a phase loop (report_edges): ticks from the wave's first hook to leaving the first barrier (fill), from leaving the
+  // second-to-last barrier to arriving at the last (drain), and from leaving the last barrier to the report (epilogue)
+  long long born = clock64(), first_leave = 0, prev_leave = 0, last_arrive = 0, last_leave = 0;
+  int nsync = 0;
+  __device__ __forceinline__ void sync() {
+    const long long t = clock64(); __syncthreads(); const long long t2 = clock64();
+    waited += t2 - t;
+    if (nsync++ == 0) first_leave = t2;
+    prev_leave = last_leave; last_arrive = t; last_leave = t2;
+  }
   __device__ __forceinline__ int sync_or(const int pred) { const long long t = clock64(); const int r = __syncthreads_or(pred); waited += clock64() - t; return r; }
   __device__ __forceinline__ void report(double* rows, long ld, int row, long col) const { if (rows) rows[row * ld + col] = (double)waited; }
+  __device__ __forceinline__ void report_edges(double* rows, long ld, int row0, long col) const {
+    if (!rows) return;
+    rows[row0 * ld + col] = (double)(first_leave - born);
+    rows[(row0 + 1) * ld + col] = (double)(nsync > 1 ? last_arrive - prev_leave : 0);
+    rows[(row0 + 2) * ld + col] = (double)(clock64() - last_leave);
+    rows[(row0 + 3) * ld + col] = (double)nsync;
+  }
 };
 struct RegionClock {
   long long c0 = 0, w0 = 0;

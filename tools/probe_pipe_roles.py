@@ -26,7 +26,7 @@ for ndim in (14, 12):
     prm = lto.make_params(lto.MU, lto.DU, lto.TU, 0.05, slot, 1.0, 1.0, 1.0)
     X = torch.from_numpy(synth.to_soa_nodes(Xh)).cuda()
     t = torch.from_numpy(np.ascontiguousarray(T[:, 0])).cuda()
-    d = torch.zeros(20, S, dtype=torch.float64, device="cuda")   # rows 16..18: probe build diagnostics
+    d = torch.zeros(24, S, dtype=torch.float64, device="cuda")   # rows 16..23: probe build diagnostics (pipe8: 20..23 its edges)
     Phi = torch.zeros(ndim * ndim, S, dtype=torch.float64, device="cuda")
     for mask, name in [(int(m), "mask %s" % m) for m in os.environ.get("MASKS", "0,6,5,3,7,4,1").split(",")]:
         plan = lto.IndirectPlan(ctx, n, 1, prm, lto.integrator(lto.RK4, steps=64, max_steps=(1 << 20) | mask), ndim=ndim)
