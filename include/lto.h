@@ -288,6 +288,27 @@ typedef struct lto_direct_end_model {
  * [12 x n_batch] = (s0; sf), model [n_batch].  The natural-spline moments of the tables are solved on the host once per call. */
 int lto_direct_end_states(lto_ctx* ctx, const lto_direct_orbits* orbits, int n_batch, const double* tau, double* s_out,
                           lto_direct_end_model* model);
+/* addTimeFinal (src/HelperFunctions.jl:196-250, re-specified): a new time of flight for a converged 12-dim solution XC
+ * [12 x n_nodes] on t [n_nodes], for each of n_dt changes dt[k] > 0 (TU) side by side.  Per k: the end costates are zeroed (on a
+ * copy) and a ballistic tail node is appended at t_end = t[n-1] + dt[k]; the extended trajectory is densified at
+ * LinRange(t[0], t_end, n_desired) (the final propagated state last, as lto_indirect_densify); each component's natural cubic
+ * spline through the samples is evaluated at t_out = LinRange(t[0], t_end, n_nodes) (the samples themselves at both ends); the
+ * last node's position and velocity are replaced by s(tau*) of the arrival table, tau* the first minimiser of |s(j / 1000) - x|_2
+ * over j = 0..1000 (find_tau); then, when XC_out is not NULL, the fixed-end Newton loop of lto_indirect_solve_batch runs on t_out.
+ * Only orbits->nf, tf and Xf are read.  Outputs: t_out [n_nodes x n_dt], tau_out [n_dt], XC_guess [12 x n_nodes x n_dt] (the
+ * re-meshed guesses; may be NULL), XC_out, defect, status_flag, iterations, history as lto_indirect_solve_batch with n_batch = n_dt
+ * (XC_out NULL: guesses only), cost [n_dt] (may be NULL): trapezoid over the n_desired-point dense output of XC_out of the thrust
+ * acceleration magnitude umag(|lambda_v|), in DU/TU.  ndim != 12 or an integrator other than LTO_RK4 / LTO_DOP853_ADAPTIVE:
+ * LTO_EUNSUPPORTED; a dt <= 0 or not finite, n_desired < 4: LTO_EINVAL. */
+int lto_indirect_add_time_batch(lto_ctx* ctx, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                                const lto_integrator* integ, const lto_direct_orbits* orbits, int n_dt, const double* dt,
+                                int n_desired, int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out,
+                                double* tau_out, double* defect, int* status_flag, int* iterations, double* history, double* cost);
+int lto_indirect_add_time(lto_ctx* ctx, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                          const lto_integrator* integ, const lto_direct_orbits* orbits, double dt, int n_desired,
+                          int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
+                          double* defect, int* status_flag, int* iterations, double* history, double* cost);
+
 /* One Jacobian sweep and one free-end QP step (arguments as lto_direct_qp_step); targets, model and beta [n_targets] (1 or
  * n_batch).  p_out [2 x n_batch] = (p1; p2); cost includes the beta term.  The 2 x 2 bound-constrained problem in p is solved
  * exactly on the device: smallest reduced cost over the interior point, the clamped edge minimisers and the corners;

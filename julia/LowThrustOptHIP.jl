@@ -16,7 +16,7 @@ using SparseArrays, LinearAlgebra, Libdl
 export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pack_soa!, unpack_soa!, defect_norms!, indirect_defect_dev!,
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
-export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify,
+export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, addTimeFinal, tf_sweep,
        direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_qp_step, direct_solve, direct_end_states, direct_qp_step_free, direct_solve_free,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
@@ -247,6 +247,53 @@ function indirect_solve_batch(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::V
                XC_new, defect1, status, iters, C_NULL)
     check(ctx, rc)
     (XC_new, defect1, Int.(status), Int.(iters))
+end
+
+"""addTimeFinal (src/HelperFunctions.jl:196-250, re-specified: DESIGN 4.12) in one library call (`lto_indirect_add_time`): the
+converged 12-row solution with a ballistic tail of Δt TU, densified at `n_desired` points, re-meshed onto LinRange(t[1], t[end] + Δt,
+n_nodes), its end snapped onto the arrival table (`Xf_times` in [0, 1], `Xf_states` [6 x nf]) and re-solved with fixed ends.
+Returns (XC_new, t_new) on status 0, otherwise the original (XC_all, t_TU) -- the reference's convention (:239-249)."""
+function addTimeFinal(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}, Δt, MU, DU, TU, n_nodes, mass, thrustLimit,
+                      p, rho, Xf_times::Vector{Float64}, Xf_states::Matrix{Float64}; maxIter::Integer = 10, n_desired::Integer = 200,
+                      flag_adjointsOnly::Bool = false, integ::LtoIntegrator = LtoIntegrator())
+    ndim = size(XC_all, 1)
+    XC_new = zeros(ndim, n_nodes); t_new = zeros(n_nodes); tau = zeros(1); defect1 = zeros(ndim, n_nodes - 1)
+    status = Ref{Cint}(0); iters = Ref{Cint}(0)
+    prm = Ref(LtoParams((MU, DU, TU, thrustLimit, mass, 1.0, p, rho)))
+    rc = GC.@preserve Xf_times Xf_states begin
+        ob = Ref(LtoDirectOrbits(0, length(Xf_times), C_NULL, C_NULL, pointer(Xf_times), pointer(Xf_states)))
+        ccall((:lto_indirect_add_time, liblto), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoParams}, Ref{LtoIntegrator}, Ref{LtoDirectOrbits}, Cdouble,
+               Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint},
+               Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx.handle, ndim, n_nodes, XC_all, t_TU, prm, Ref(integ), ob, Float64(Δt), n_desired, flag_adjointsOnly ? 1 : 0,
+              maxIter, C_NULL, XC_new, t_new, tau, defect1, status, iters, C_NULL, C_NULL)
+    end
+    check(ctx, rc)
+    status[] == 0 ? (XC_new, t_new) : (XC_all, t_TU)
+end
+
+"""addTimeFinal for many Δt side by side (`lto_indirect_add_time_batch`): the cost-versus-time-of-flight curve of a converged
+transfer.  Returns (XC [12 x n x K], t [n x K], tau [K], status [K], iterations [K], cost [K] in DU/TU)."""
+function tf_sweep(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}, Δts::Vector{Float64}, MU, DU, TU, mass,
+                  thrustLimit, p, rho, Xf_times::Vector{Float64}, Xf_states::Matrix{Float64}; maxIter::Integer = 10,
+                  n_desired::Integer = 200, flag_adjointsOnly::Bool = false, integ::LtoIntegrator = LtoIntegrator())
+    ndim, n_nodes = size(XC_all)
+    K = length(Δts)
+    XC = zeros(ndim, n_nodes, K); t = zeros(n_nodes, K); tau = zeros(K); defect1 = zeros(ndim, n_nodes - 1, K)
+    status = zeros(Cint, K); iters = zeros(Cint, K); cost = zeros(K)
+    prm = Ref(LtoParams((MU, DU, TU, thrustLimit, mass, 1.0, p, rho)))
+    rc = GC.@preserve Xf_times Xf_states begin
+        ob = Ref(LtoDirectOrbits(0, length(Xf_times), C_NULL, C_NULL, pointer(Xf_times), pointer(Xf_states)))
+        ccall((:lto_indirect_add_time_batch, liblto), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoParams}, Ref{LtoIntegrator}, Ref{LtoDirectOrbits}, Cint,
+               Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint},
+               Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx.handle, ndim, n_nodes, XC_all, t_TU, prm, Ref(integ), ob, K, Δts, n_desired, flag_adjointsOnly ? 1 : 0, maxIter,
+              C_NULL, XC, t, tau, defect1, status, iters, C_NULL, cost)
+    end
+    check(ctx, rc)
+    (XC, t, tau, Int.(status), Int.(iters), cost)
 end
 
 # ---------------------------------------------------------------------------------------------- direct

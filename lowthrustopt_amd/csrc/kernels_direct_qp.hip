@@ -26,6 +26,7 @@
 // and w = max dt, the unknowns are du = s_u u~, lambda = s_l l~ and the stationarity rows are multiplied by r_u (du) and r_x = 1/s_l
 // (dx): s_u = 1/g, r_u = g/(2w), s_l = 2w/g^2, all rounded to powers of two (exact).  Every block is then O(1).
 #include "kernels.hpp"
+#include "orbit_spline.hpp"
 #include <type_traits>
 
 namespace lto {
@@ -875,27 +876,6 @@ namespace lto {
 // ---- free ends: the end states and the end model of every trajectory at its current (tau1, tau2) -- interpEndStates (:434-461)
 // at tau and tau +- h, each argument wrapped into [0, 1] on its own, and the finite differences of :339-349.  One thread per
 // trajectory and end point; the natural-spline second derivatives of the two tables come from the host (fixed for a call).
-__device__ double end_spline(const EndOrbitsDev& o, const int e, const int j, double x) {
-  int guard = 0;                                   // the reference's wrap (:438-449); a non-finite or absurd tau gives NaN
-  if (!(fabs(x) < 1e6)) return __builtin_nan("");
-  while (x > 1.0 && guard++ < 2000000) x -= 1.0;
-  while (x < 0.0 && guard++ < 2000000) x += 1.0;
-  const int n = o.n[e];
-  const double* t = o.t[e];
-  const double* Y = o.Y[e];
-  const double* M = o.M[e];
-  int lo = 0, hi = n - 1;                          // the last i with t[i] <= x, clipped to [0, n-2]
-  if (x < t[0]) hi = 0;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) / 2;
-    if (t[mid] <= x) lo = mid; else hi = mid;
-  }
-  const int i = lo < n - 2 ? lo : n - 2;
-  const double h = t[i + 1] - t[i], a = t[i + 1] - x, b = x - t[i];
-  const double Mi = M[j + 6 * i], Mj = M[j + 6 * (i + 1)];
-  return (Mi * a * a * a + Mj * b * b * b) / (6.0 * h) + (Y[j + 6 * i] - Mi * h * h / 6.0) * a / h +
-         (Y[j + 6 * (i + 1)] - Mj * h * h / 6.0) * b / h;
-}
 __global__ void k_end_states(EndOrbitsDev o, const double* tau, int n_batch, double* s, int s_stride, double* model) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= 2 * n_batch) return;

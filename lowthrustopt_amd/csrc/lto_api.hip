@@ -1365,11 +1365,15 @@ struct NewtonBatch {
  * n_batch independent problems (homotopy levels, thrust levels, different guesses) run the loop side by side: every
  * device operation covers the whole batch; a trajectory that has left the reference loop (converged, NaN, iteration
  * limit) is frozen by a zero step length and its results are kept. */
-int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC_in, const double* t, int n_tgrids,
-                             const lto_params* prm, int n_prm, const lto_integrator* integ, int flag_adjointsOnly, int maxIter,
-                             double* XC_out, double* defect, int* status_flag, int* iterations, double* history) {
+// d_Xin: the starting trajectories already on the device ([ndim][n_nodes n_batch] struct-of-arrays, the loop's own layout) instead
+// of XC_in; d_Xout: if set, the final trajectories are also copied there (same layout).  lto_indirect_add_time_batch starts the loop
+// from its re-meshed guesses this way.
+static int indirect_solve_impl(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC_in, const double* d_Xin, const double* t,
+                               int n_tgrids, const lto_params* prm, int n_prm, const lto_integrator* integ, int flag_adjointsOnly,
+                               int maxIter, double* XC_out, double* d_Xout, double* defect, int* status_flag, int* iterations,
+                               double* history) {
   if (!c) return LTO_ENULL;
-  if (!XC_in || !t || !prm || !integ || !XC_out || !status_flag) return set_err(c, LTO_ENULL, "XC_in, t, prm, integ, XC_out or status_flag is NULL");
+  if ((!XC_in && !d_Xin) || !t || !prm || !integ || !XC_out || !status_flag) return set_err(c, LTO_ENULL, "XC_in, t, prm, integ, XC_out or status_flag is NULL");
   if (ndim != 12 && ndim != 14) return set_err(c, LTO_EUNSUPPORTED, "the device Newton loop is built for ndim = 12 and 14");
   if (maxIter < 0) return set_err(c, LTO_EINVAL, "maxIter must be >= 0");
   if (n_batch < 1 || n_nodes < 2) return set_err(c, LTO_EINVAL, "need n_nodes >= 2 and n_batch >= 1");
@@ -1430,11 +1434,12 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
   unsigned trial_sweeps = 0;
   if (!nb.ok() || !h_mx.ok() || !h_step.ok() || !h_back.ok()) return set_err(c, LTO_ENOMEM, "lto_indirect_solve_batch: out of host memory");
 
-  hipError_t e = hipMemcpyAsync(d_aos, XC_in, sizeof(double) * nd * J, hipMemcpyHostToDevice, st);
+  hipError_t e = d_Xin ? hipMemcpyAsync(d_X, d_Xin, sizeof(double) * nd * J, hipMemcpyDeviceToDevice, st)
+                       : hipMemcpyAsync(d_aos, XC_in, sizeof(double) * nd * J, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n * n_tgrids, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && n_tgrids != 1) e = hipMemcpyAsync(d_tl, t_l.data(), sizeof(double) * n * ntl, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_alphas, nb.alphas.data(), sizeof(double) * NA, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_pack_soa(d_aos, nd, J, d_X, J, st);
+  if (e == hipSuccess && !d_Xin) e = launch_pack_soa(d_aos, nd, J, d_X, J, st);
   // state_0, state_f  (:270-271); 14-dim: also m0, and lambda_m(tf) set to 0 (free final mass)
   if (e == hipSuccess) e = launch_end_pins(d_X, J, n_nodes, B, nd, d_saved, 0, st);
   if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage in", e);
@@ -1531,6 +1536,7 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
   if (rc == LTO_OK) {
     e = launch_unpack_soa(d_X, J, nd, J, d_aos, st);
     if (e == hipSuccess) e = hipMemcpyAsync(XC_out, d_aos, sizeof(double) * nd * J, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && d_Xout) e = hipMemcpyAsync(d_Xout, d_X, sizeof(double) * nd * J, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && defect) {
       e = launch_unpack_soa(d_def, S, nd, S, d_def_aos, st);
       if (e == hipSuccess) e = hipMemcpyAsync(defect, d_def_aos, sizeof(double) * nd * S, hipMemcpyDeviceToHost, st);
@@ -1546,6 +1552,14 @@ int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, con
   }
   nb.copy_out(status_flag, iterations);
   return rc;
+}
+
+int lto_indirect_solve_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC_in, const double* t, int n_tgrids,
+                             const lto_params* prm, int n_prm, const lto_integrator* integ, int flag_adjointsOnly, int maxIter,
+                             double* XC_out, double* defect, int* status_flag, int* iterations, double* history) {
+  if (c && !XC_in) return set_err(c, LTO_ENULL, "XC_in, t, prm, integ, XC_out or status_flag is NULL");
+  return indirect_solve_impl(c, ndim, n_nodes, n_batch, XC_in, nullptr, t, n_tgrids, prm, n_prm, integ, flag_adjointsOnly, maxIter,
+                             XC_out, nullptr, defect, status_flag, iterations, history);
 }
 
 int lto_indirect_solve(lto_ctx* c, int ndim, int n_nodes, const double* XC_in, const double* t, const lto_params* prm,
@@ -2288,6 +2302,142 @@ int lto_direct_end_states(lto_ctx* c, const lto_direct_orbits* orbits, int n_bat
   if (e == hipSuccess) e = call.wait();
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_direct_end_states", e);
   return LTO_OK;
+}
+
+/* addTimeFinal (src/HelperFunctions.jl:196-250, re-specified in DESIGN 4.12) for K time-of-flight changes dt[K] of one converged
+ * 12-dim solution, every phase on the device: the K extended trajectories (end costates zeroed, a ballistic tail node at
+ * t[n-1] + dt) through the dense-output sweep at LinRange(t[0], t_end, n_desired); the natural-spline re-mesh onto LinRange(t[0],
+ * t_end, n) (k_remesh_spline); the snap of the last node onto the arrival orbit (k_find_tau); then, if XC_out is set, the fixed-end
+ * Newton loop of lto_indirect_solve_batch started from the guesses in HBM, and the cost of its results (k_dense_cost). */
+int lto_indirect_add_time_batch(lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                                const lto_integrator* integ, const lto_direct_orbits* orbits, int n_dt, const double* dt, int n_desired,
+                                int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
+                                double* defect, int* status_flag, int* iterations, double* history, double* cost) {
+  if (!c) return LTO_ENULL;
+  if (!XC || !t || !prm || !integ || !orbits || !dt || !t_out || !tau_out || (XC_out && !status_flag))
+    return set_err(c, LTO_ENULL, "lto_indirect_add_time_batch: a required argument is NULL");
+  if (ndim != 12) return set_err(c, LTO_EUNSUPPORTED, "lto_indirect_add_time_batch: ndim must be 12 (dense output)");
+  if (integ->method != LTO_RK4 && integ->method != LTO_DOP853_ADAPTIVE)
+    return set_err(c, LTO_EUNSUPPORTED, "lto_indirect_add_time_batch: dense output is built for LTO_RK4 and LTO_DOP853_ADAPTIVE");
+  if (n_dt < 1 || n_nodes < 2 || n_desired < 4 || maxIter < 0)
+    return set_err(c, LTO_EINVAL, "lto_indirect_add_time_batch: need n_dt >= 1, n_nodes >= 2, n_desired >= 4, maxIter >= 0");
+  for (int b = 0; b < n_dt; ++b)
+    if (!(dt[b] > 0.0) || !std::isfinite(dt[b])) return set_err(c, LTO_EINVAL, "lto_indirect_add_time_batch: every dt must be finite and > 0");
+  if (orbits->nf < 2 || !orbits->tf || !orbits->Xf) return set_err(c, LTO_EINVAL, "lto_indirect_add_time_batch: the arrival table needs >= 2 samples");
+  const int K = n_dt, n = n_nodes, m = n_desired, ne = n + 1;
+  if ((long)K * m * 12 > 0x7fffffffL || (long)K * ne * 12 > 0x7fffffffL) return set_err(c, LTO_EINVAL, "lto_indirect_add_time_batch: batch too large");
+  int rc = bind_device(c);
+  if (rc) return rc;
+  CallTimer call_timer(c);
+  // host side: the grids, the sample ranges of every segment, the extended trajectories and the Thomas factors
+  lto::HostBuf<double> h_te((size_t)K * ne), h_td((size_t)K * m), h_cp((size_t)m, 0.0), h_xe((size_t)12 * K * ne);
+  lto::HostBuf<int> h_fe((size_t)K * n + 1), h_fc((size_t)K * (n - 1) + 1);
+  if (!h_te.ok() || !h_td.ok() || !h_cp.ok() || !h_xe.ok() || !h_fe.ok() || !h_fc.ok())
+    return set_err(c, LTO_ENOMEM, "lto_indirect_add_time_batch: out of host memory");
+  const double t0 = t[0];
+  // samples of segment i of a grid g[0..nn-1]: td in [g_i, g_{i+1}); the last segment also takes the last sample (t_end itself: the
+  // lane steps onto it exactly as the final-state store of lto_indirect_densify does)
+  auto ranges = [&](const double* g, int nn, const double* tdb, int* f, int base) {
+    int j = 0;
+    for (int i = 0; i < nn - 1; ++i) {
+      f[i] = base + j;
+      while (j < m - 1 && tdb[j] < g[i + 1]) ++j;
+    }
+  };
+  for (int b = 0; b < K; ++b) {
+    const double te = t[n - 1] + dt[b];
+    double* tb = &h_te[(size_t)b * ne];
+    std::memcpy(tb, t, sizeof(double) * n);
+    tb[n] = te;
+    double* tdb = &h_td[(size_t)b * m];
+    for (int k = 0; k < m; ++k) { const double tau = (double)k / (double)(m - 1); tdb[k] = (1.0 - tau) * t0 + tau * te; }
+    double* tnb = t_out + (size_t)b * n;
+    for (int k = 0; k < n; ++k) { const double tau = (double)k / (double)(n - 1); tnb[k] = (1.0 - tau) * t0 + tau * te; }
+    ranges(tb, ne, tdb, &h_fe[(size_t)b * n], b * m);
+    ranges(tnb, n, tdb, &h_fc[(size_t)b * (n - 1)], b * m);
+    double* xb = &h_xe[(size_t)12 * ne * b];
+    std::memcpy(xb, XC, sizeof(double) * 12 * n);
+    for (int q = 6; q < 12; ++q) xb[12 * (n - 1) + q] = 0.0;         // :199 (on a copy)
+    std::memcpy(xb + 12 * n, xb + 12 * (n - 1), sizeof(double) * 12);  // the tail's end node: never read by the sweep
+  }
+  h_fe[(size_t)K * n] = K * m;
+  h_fc[(size_t)K * (n - 1)] = K * m;
+  for (int i = 1; i < m - 1; ++i) h_cp[i] = 1.0 / (4.0 - h_cp[i - 1]);
+  // device side: one block, carved 256-B aligned
+  const long Je = (long)K * ne, Jn = (long)K * n, Jm = (long)K * m;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off += al256(bytes); return at; };
+  const size_t o_xa = take(sizeof(double) * 12 * Je), o_xe = take(sizeof(double) * 12 * Je), o_te = take(sizeof(double) * Je),
+               o_tn = take(sizeof(double) * Jn), o_td = take(sizeof(double) * Jm), o_cp = take(sizeof(double) * m),
+               o_fe = take(sizeof(int) * (Jn + 1)), o_fc = take(sizeof(int) * (Jn - K + 1)), o_y = take(sizeof(double) * 12 * Jm),
+               o_mom = take(sizeof(double) * 12 * Jm), o_g = take(sizeof(double) * 12 * Jn), o_ga = take(sizeof(double) * 12 * Jn),
+               o_xc = take(sizeof(double) * 12 * Jn), o_tau = take(sizeof(double) * K), o_cost = take(sizeof(double) * K);
+  lto_direct_orbits arr = *orbits;                 // the upload builds both tables: the departure side gets the arrival's
+  arr.n0 = arr.nf; arr.t0 = arr.tf; arr.X0 = arr.Xf;
+  DevOrbits dob;
+  HostCall call(c);
+  hipStream_t st = c->stream;
+  rc = orbits_upload(c, &arr, dob, st);
+  if (rc) return rc;
+  hipError_t e = hipMalloc(&call.block[0], off);
+  if (e != hipSuccess) { call.block[0] = nullptr; return set_err(c, LTO_EHIP, "lto_indirect_add_time_batch", e); }
+  char* base = (char*)call.block[0];
+  double *d_xa = (double*)(base + o_xa), *d_xe = (double*)(base + o_xe), *d_te = (double*)(base + o_te), *d_tn = (double*)(base + o_tn),
+         *d_td = (double*)(base + o_td), *d_cp = (double*)(base + o_cp), *d_y = (double*)(base + o_y), *d_mom = (double*)(base + o_mom),
+         *d_g = (double*)(base + o_g), *d_ga = (double*)(base + o_ga), *d_xc = (double*)(base + o_xc), *d_tau = (double*)(base + o_tau),
+         *d_cost = (double*)(base + o_cost);
+  int *d_fe = (int*)(base + o_fe), *d_fc = (int*)(base + o_fc);
+  rc = plan_build(c, 12, ne, K, prm, 1, integ, &call.plan[0]);
+  if (rc) return rc;
+  e = hipMemcpyAsync(d_xa, h_xe.data(), sizeof(double) * 12 * Je, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_te, h_te.data(), sizeof(double) * Je, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tn, t_out, sizeof(double) * Jn, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_td, h_td.data(), sizeof(double) * Jm, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_cp, h_cp.data(), sizeof(double) * m, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_fe, h_fe.data(), sizeof(int) * (Jn + 1), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_fc, h_fc.data(), sizeof(int) * (Jn - K + 1), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = launch_pack_soa(d_xa, 12, Je, d_xe, Je, st);
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_add_time_batch: stage in", e);
+  // 1-2: the extended trajectories' dense output, Y [12][K m]
+  rc = lto_indirect_dense_dev(call.plan[0], st, d_xe, Je, d_te, K, d_fe, d_td, d_y, Jm, nullptr);
+  if (rc) return rc;
+  // 3-4: re-mesh, then the end snapped onto the arrival orbit; the guesses G [12][K n] in the solve's layout
+  RemeshArgs ra;
+  ra.Y = d_y; ra.ldy = Jm; ra.td = d_td; ra.tn = d_tn; ra.cp = d_cp; ra.mom = d_mom; ra.G = d_g; ra.ldg = Jn;
+  ra.m = m; ra.n = n; ra.K = K;
+  e = launch_remesh_spline(ra, st);
+  if (e == hipSuccess) e = launch_find_tau(dob.o, d_g, Jn, n, K, d_tau, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(tau_out, d_tau, sizeof(double) * K, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && XC_guess) {
+    e = launch_unpack_soa(d_g, Jn, 12, Jn, d_ga, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(XC_guess, d_ga, sizeof(double) * 12 * Jn, hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess) e = call.wait();
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_add_time_batch: re-mesh", e);
+  if (!XC_out) return LTO_OK;
+  // 5: the fixed-end Newton loop on the new grids (:236-237), started from G
+  rc = indirect_solve_impl(c, 12, n, K, nullptr, d_g, t_out, K, prm, 1, integ, flag_adjointsOnly, maxIter, XC_out, cost ? d_xc : nullptr,
+                           defect, status_flag, iterations, history);
+  if (rc || !cost) return rc;
+  // the cost of every result: its dense output at the same LinRange(t[0], t_end, n_desired), trapezoid of umag
+  call.idle = false;
+  rc = plan_build(c, 12, n, K, prm, 1, integ, &call.plan[1]);
+  if (rc == LTO_OK) rc = lto_indirect_dense_dev(call.plan[1], st, d_xc, Jn, d_tn, K, d_fc, d_td, d_y, Jm, nullptr);
+  if (rc) return rc;
+  const double aL = prm->thrustLimit / prm->mass / 1e3 * (prm->TU * prm->TU) / prm->DU;   // stateCostate_deriv.jl:33
+  e = launch_dense_cost(d_y, Jm, d_td, m, K, aL, prm->p, prm->rho, d_cost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * K, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = call.wait();
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_add_time_batch: cost", e);
+  return LTO_OK;
+}
+
+int lto_indirect_add_time(lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                          const lto_integrator* integ, const lto_direct_orbits* orbits, double dt, int n_desired, int flag_adjointsOnly,
+                          int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out, double* defect, int* status_flag,
+                          int* iterations, double* history, double* cost) {
+  return lto_indirect_add_time_batch(c, ndim, n_nodes, XC, t, prm, integ, orbits, 1, &dt, n_desired, flag_adjointsOnly, maxIter,
+                                     XC_guess, XC_out, t_out, tau_out, defect, status_flag, iterations, history, cost);
 }
 
 static bool direct_targets_expand(const lto_direct_targets* targets, int n_targets, int B, lto::HostBuf<lto_direct_targets>& out) {

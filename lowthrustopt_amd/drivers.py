@@ -845,6 +845,41 @@ def lineSearch_direct(X_all, x_update, u_all, u_update, t_TU, nstate, n_nodes, n
     return float(alpha_all[int(np.argmin(er))])             # first minimiser, as `alpha[1]` (:428-429)
 
 
+def addTimeFinal(XC_all, t_TU, Δt, MU, DU, TU, n_nodes, mass, thrustLimit, p, rho, Xf_times, Xf_states, maxIter=10,
+                 n_desired=200, flag_adjointsOnly=False, integ=None, ctx=None, verbose=True):
+    """addTimeFinal (HelperFunctions.jl:196-250), re-specified where the reference cannot run: a converged 12-row
+    solution on t_TU gets a ballistic tail of Δt TU (end costates zeroed -- on a copy, the caller's array is not changed), is
+    densified at n_desired points (the reference's 200, :208), re-meshed onto LinRange(t[0], t[end] + Δt, n_nodes), its end
+    snapped onto the arrival orbit table (find_τ, :38-48) and re-solved by the fixed-end indirect loop.  Every phase runs in one
+    library call (lto_indirect_add_time_batch).  Returns (XC_new, t_new) on status 0, otherwise the original (XC_all, t_TU)
+    unchanged (:239-249)."""
+    XC_all = np.array(XC_all, dtype=np.float64, order="F")
+    t_TU = np.array(t_TU, dtype=np.float64)
+    if XC_all.shape != (12, int(n_nodes)):
+        raise ValueError("addTimeFinal takes the 12-row solution [12 x n_nodes]; got shape %s" % (XC_all.shape,))
+    params = hotpath.make_params(MU, DU, TU, thrustLimit, mass, 1.0, p, rho)
+    r = hotpath.indirect_add_time(XC_all, t_TU, params, Xf_times, Xf_states, [float(Δt)], n_desired=n_desired, integ=integ,
+                                  flag_adjointsOnly=flag_adjointsOnly, maxIter=maxIter, ctx=ctx)
+    if verbose:
+        print("addTimeFinal: Δt = %.6g TU, τ* = %.3f, status %d after %d iterations" % (Δt, r.tau[0], r.status[0], r.iterations[0]))
+    if r.status[0] == 0:
+        return r.XC_out[:, :, 0].copy(), r.t_out[:, 0].copy()
+    return XC_all, t_TU
+
+
+def tf_sweep(XC_all, t_TU, Δts, MU, DU, TU, mass, thrustLimit, p, rho, Xf_times, Xf_states, maxIter=10, n_desired=200,
+             flag_adjointsOnly=False, integ=None, ctx=None):
+    """addTimeFinal for many Δt at once: the cost-versus-time-of-flight curve of a converged transfer in one library call.
+    Returns a dict of per-Δt arrays: dt [K], tof [K] (TU), XC [12 x n x K], t [n x K], tau [K], status [K], iterations [K],
+    max_defect [K] and cost [K] (Δv of the control law, DU/TU)."""
+    params = hotpath.make_params(MU, DU, TU, thrustLimit, mass, 1.0, p, rho)
+    dts = np.asarray(Δts, dtype=np.float64).reshape(-1)
+    r = hotpath.indirect_add_time(XC_all, t_TU, params, Xf_times, Xf_states, dts, n_desired=n_desired, integ=integ,
+                                  flag_adjointsOnly=flag_adjointsOnly, maxIter=maxIter, ctx=ctx)
+    return {"dt": dts, "tof": r.t_out[-1] - r.t_out[0], "XC": r.XC_out, "t": r.t_out, "tau": r.tau, "status": r.status,
+            "iterations": r.iterations, "max_defect": np.abs(r.defect).max(axis=(0, 1)), "cost": r.cost}
+
+
 def meshRefine_direct(X_all, u_all, t_TU, nstate, n_nodes, nsteps, Isp, MU, DU, TU, tol_min=1e-20, tol_max=1e-18,
                       max_nodes=1 << 20, batched=True, ops=None, verbose=True):
     """Errors-driven mesh refinement of the direct transcription (direct.jl:597-680): nodes are removed while the

@@ -11,6 +11,7 @@ Names, argument meaning and return shapes follow the Julia closures; arrays are 
 julia/LowThrustOptHIP.jl.  Nothing here computes on the CPU: without the HIP
 library and a GPU every call raises.
 """
+import collections
 import ctypes as C
 
 import weakref
@@ -817,6 +818,55 @@ def direct_end_states(tau, orbits, ctx=None):
     if not batched:
         return s[:6, 0], s[6:, 0], g0[:, 0], gf[:, 0], float(c0[0]), float(cf[0])
     return s[:6], s[6:], g0, gf, c0, cf
+
+
+AddTime = collections.namedtuple("AddTime", "XC_guess XC_out t_out tau defect status iterations history cost")
+
+
+def indirect_add_time(XC, t, params, Xf_times, Xf_states, dts, n_desired=200, integ=None, flag_adjointsOnly=False, maxIter=10,
+                      solve=True, ctx=None):
+    """addTimeFinal (src/HelperFunctions.jl:196-250, re-specified: DESIGN 4.12) for K time-of-flight changes at once
+    (lto_indirect_add_time_batch): the converged 12-dim solution XC [12 x n] on t [n] with a ballistic tail of dts[k] TU,
+    densified at n_desired points, re-meshed onto LinRange(t[0], t[n-1] + dts[k], n) and its end snapped onto the arrival orbit
+    table (Xf_times [nf] in [0, 1], Xf_states [6 x nf]); then, with solve = True, the fixed-end Newton loop on the new grids.
+    Returns AddTime(XC_guess [12 x n x K], XC_out [12 x n x K], t_out [n x K], tau [K], defect [12 x (n-1) x K], status [K],
+    iterations [K], history (one array of (max|defect|, alpha) per trajectory), cost [K] in DU/TU); the solve's fields are None
+    when solve = False."""
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    X = _f64(XC)
+    if X.ndim != 2:
+        raise ValueError("indirect_add_time takes one trajectory [ndim x n_nodes]")
+    ndim, n = X.shape
+    tt = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+    if tt.size != n:
+        raise ValueError("t must have one time per node")
+    dts = np.ascontiguousarray(dts, dtype=np.float64).reshape(-1)
+    K = dts.size
+    prm, _ = _params_array(params)
+    tf = np.ascontiguousarray(Xf_times, dtype=np.float64).reshape(-1)
+    ob = DirectOrbits(tf, Xf_states, tf, Xf_states)
+    ob.struct.n0, ob.struct.t0, ob.struct.X0 = 0, None, None       # only the arrival side is read
+    guess = np.zeros((ndim, n, K), order="F")
+    t_out = np.zeros((n, K), order="F")
+    tau = np.zeros(K)
+    XC_out = defect = status = iters = hist = cost = None
+    if solve:
+        XC_out = np.zeros((ndim, n, K), order="F")
+        defect = np.zeros((ndim, n - 1, K), order="F")
+        status = np.zeros(K, dtype=np.int32)
+        iters = np.zeros(K, dtype=np.int32)
+        hist = np.full((2, max(int(maxIter), 1), K), np.nan, order="F")
+        cost = np.zeros(K)
+    ctx.check(ctx.fn("indirect_add_time_batch")(
+        ctx.handle, ndim, n, _ptr(X), _ptr(tt), prm, C.byref(integ), C.byref(ob.struct), K, _ptr(dts), int(n_desired),
+        1 if flag_adjointsOnly else 0, int(maxIter), _ptr(guess), _ptr(XC_out) if solve else None, _ptr(t_out), _ptr(tau),
+        _ptr(defect) if solve else None, _ptr(status) if solve else None, _ptr(iters) if solve else None,
+        _ptr(hist) if solve and maxIter > 0 else None, _ptr(cost) if solve else None))
+    history = None
+    if solve:
+        history = [hist[:, ~np.isnan(hist[1, :, b]), b].T.copy() for b in range(K)]
+    return AddTime(guess, XC_out, t_out, tau, defect, status, iters, history, cost)
 
 
 def direct_qp_step_free(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, models, beta, allowImpulsive=False, ctx=None):
