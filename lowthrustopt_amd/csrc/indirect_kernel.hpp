@@ -314,31 +314,31 @@ static hipError_t launch_one(const IndirectArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// `pm` = bit mask of the control-law classes present in the batch.  One launch per class; with more than one class
-// each launch filters its own trajectories (class_filter), so no kernel ever branches on p.
+// One launch per control-law class present in `pm` (kernels.hpp for_classes).
 
 template <int ND, int METHOD>
 static hipError_t launch_dense_pm(int pm, const IndirectArgs& a0, const DenseArgs& d, hipStream_t st) {
   dim3 grid((a0.S + 63) / 64);
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  if (pm & (1 << PM_P0)) hipLaunchKernelGGL((k_indirect_dense<ND, PM_P0, METHOD>), grid, dim3(64), 0, st, a, d);
-  if (pm & (1 << PM_P1)) hipLaunchKernelGGL((k_indirect_dense<ND, PM_P1, METHOD>), grid, dim3(64), 0, st, a, d);
-  if (pm & (1 << PM_P2)) hipLaunchKernelGGL((k_indirect_dense<ND, PM_P2, METHOD>), grid, dim3(64), 0, st, a, d);
-  if (pm & (1 << PM_PGEN)) hipLaunchKernelGGL((k_indirect_dense<ND, PM_PGEN, METHOD>), grid, dim3(64), 0, st, a, d);
+  // every class is launched and the error state read once, behind the last launch
+  (void)for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) {
+    hipLaunchKernelGGL((k_indirect_dense<ND, decltype(cls)::value, METHOD>), grid, dim3(64), 0, st, a, d);
+    return hipSuccess;
+  });
   return hipGetLastError();
 }
 
 template <int ND, int METHOD, int COLS>
 static hipError_t launch_pm(int pm, const IndirectArgs& a0, hipStream_t st) {
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_one<ND, PM_P0, METHOD, COLS>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_one<ND, PM_P1, METHOD, COLS>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P2))) e = launch_one<ND, PM_P2, METHOD, COLS>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_PGEN))) e = launch_one<ND, PM_PGEN, METHOD, COLS>(a, st);
-  return e;
+  return for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_one<ND, decltype(cls)::value, METHOD, COLS>(a, st); });
 }
+
+// The per-lane family of one dimension: <12> is defined in kernels_indirect.hip, <14> in kernels_indirect14.hip (two translation
+// units for compile time); launch_indirect_defect / launch_indirect_stm (kernels_indirect.hip) switch on ndim.
+template <int ND> hipError_t launch_defect_nd(int pm, int method, const IndirectArgs& a, hipStream_t st);
+template <int ND> hipError_t launch_stm_nd(int pm, int method, int cols, const IndirectArgs& a, hipStream_t st);
+template <> hipError_t launch_defect_nd<12>(int pm, int method, const IndirectArgs& a, hipStream_t st);
+template <> hipError_t launch_defect_nd<14>(int pm, int method, const IndirectArgs& a, hipStream_t st);
+template <> hipError_t launch_stm_nd<12>(int pm, int method, int cols, const IndirectArgs& a, hipStream_t st);
+template <> hipError_t launch_stm_nd<14>(int pm, int method, int cols, const IndirectArgs& a, hipStream_t st);
 
 }  // namespace lto

@@ -1,7 +1,9 @@
 // kernels.hpp -- argument blocks and launch entry points shared by the .hip translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "dynamics.hpp"
+#include "sweep_policy.hpp"        // what every indirect form is built for (the indirect_*_available predicates) and which one runs
 
 namespace lto {
 
@@ -67,11 +69,36 @@ struct DirectArgs {
 };
 
 static inline bool single_class(int pm) { return (pm & (pm - 1)) == 0; }   // pm: bit mask of p-classes
+static_assert(kThrustLimitedClasses == ((1 << PM_P0) | (1 << PM_P1)) && kOtherClasses == ((1 << PM_P2) | (1 << PM_PGEN)), "sweep_policy.hpp numbers the classes as PMode does");
+static_assert(M_RK4 == LTO_RK4 && M_DOP853_ADAPTIVE == LTO_DOP853_ADAPTIVE, "sweep_policy.hpp reads Method ids as LTO_*");
+
+// `pm` = bit mask of the control-law classes present in the batch.  One launch per class of CLASSES that is present: the args are
+// copied once and, with more than one class in the batch, every launch filters its own trajectories (class_filter), so no kernel
+// ever branches on p.  one(std::integral_constant<int, PM>, args) launches the class's kernel; the first error ends the sequence.
+// Forms built for the always-thrust-limited laws only pass <PM_P0, PM_P1>.
+// (A recursion, not a fold over the pack: the compiler emits a unit's kernels in the order these calls are instantiated, and a fold
+// instantiates the last class first -- same kernels, but every local label of the device assembly renumbered.)
+template <int CLASS, int... REST, class One>
+static inline hipError_t for_classes_from(int pm, const IndirectArgs& a, One& one) {
+  if (pm & (1 << CLASS)) {
+    const hipError_t e = one(std::integral_constant<int, CLASS>{}, a);
+    if (e != hipSuccess) return e;
+  }
+  if constexpr (sizeof...(REST) > 0) return for_classes_from<REST...>(pm, a, one);
+  else return hipSuccess;
+}
+template <int... CLASSES, class One>
+static inline hipError_t for_classes(int pm, const IndirectArgs& a0, One&& one) {
+  IndirectArgs a = a0;
+  a.class_filter = single_class(pm) ? 0 : 1;
+  return for_classes_from<CLASSES...>(pm, a, one);
+}
 
 // Launchers return hipSuccess or the launch error.  `pm` is a bit mask of the PMode classes present in the batch (bit c = class c), `method` a Method.
-hipError_t launch_indirect_defect(int pm, int method, const IndirectArgs& a, hipStream_t st);
+// One launcher per family; ndim = 12 or 14 (where a family's two dimensions are separate translation units, the switch is in the 12-dim one).
+hipError_t launch_indirect_defect(int ndim, int pm, int method, const IndirectArgs& a, hipStream_t st);
 // cols_per_lane in {1,2,3}; 0 = choose from S.
-hipError_t launch_indirect_stm(int pm, int method, int cols_per_lane, const IndirectArgs& a, hipStream_t st);
+hipError_t launch_indirect_stm(int ndim, int pm, int method, int cols_per_lane, const IndirectArgs& a, hipStream_t st);
 // dense output: segment s is sampled at td[first[s] .. first[s+1]); Y is SoA [ndim][ldy]
 struct DenseArgs {
   const int* first;        // [S+1] prefix offsets into td / columns of Y
@@ -80,21 +107,16 @@ struct DenseArgs {
   double* final_state;     // [ND][n_batch] or null: x(t_n) of every trajectory
 };
 hipError_t launch_indirect_dense(int ndim, int pm, int method, const IndirectArgs& a, const DenseArgs& d, hipStream_t st);
-hipError_t launch_indirect14_defect(int pm, int method, const IndirectArgs& a, hipStream_t st);
-hipError_t launch_indirect14_stm(int pm, int method, int cols_per_lane, const IndirectArgs& a, hipStream_t st);
 // wave-specialised STM kernel (kernels_indirect_coop.hip): base wave + column waves per 16 segments
 hipError_t launch_indirect_stm_coop(int ndim, int pm, int method, const IndirectArgs& a, hipStream_t st);
-// the same with every 12-component state split over two lanes (kernels_indirect_coop2.hip): 12-dim, DOP853 adaptive only
-hipError_t launch_indirect_stm_coop2(int pm, const IndirectArgs& a, hipStream_t st);
-// ... and its 14-dim form (kernels_indirect_coop2_14.hip): states split 7 + 7, thirteen columns; the always-thrust-limited laws (p = 0, 1) only
-hipError_t launch_indirect_stm_coop2_14(int pm, const IndirectArgs& a, hipStream_t st);
-bool indirect_stm_coop2_14_available(int pm);
+// the same with every 12-component state split over two lanes (kernels_indirect_coop2.hip), DOP853 adaptive only; the 14-dim form
+// (kernels_indirect_coop2_14.hip) splits the states 7 + 7, thirteen columns: the always-thrust-limited laws (p = 0, 1) only
+hipError_t launch_indirect_stm_coop2(int ndim, int pm, const IndirectArgs& a, hipStream_t st);
 // defect-only sweep with two lanes per segment (kernels_indirect_defect2.hip): 12-dim, DOP853 adaptive only
 hipError_t launch_indirect_defect2(int pm, const IndirectArgs& a, hipStream_t st);
-// ... with four lanes per segment (same file): while the chip has a SIMD per 16 segments to spare
-hipError_t launch_indirect_defect4(int pm, const IndirectArgs& a, hipStream_t st);
-// ... on the 14-dim system (same file; p = 0 / 1 batches, see indirect_stm_coop2_14_available)
-hipError_t launch_indirect14_defect4(int pm, const IndirectArgs& a, hipStream_t st);
+// ... with four lanes per segment (same file): while the chip has a SIMD per 16 segments to spare; 14-dim for p = 0 / 1 batches
+// (indirect_defect4_available)
+hipError_t launch_indirect_defect4(int ndim, int pm, const IndirectArgs& a, hipStream_t st);
 // three-role pipeline, fixed-step RK4 only: base wave, coefficient wave and column waves per 16 segments, skewed by one RK4 step.
 // Eight-wave form (kernels_indirect_pipe8.hip): one STM column per lane with the coefficients broadcast inside the FMA (v_fmac_f64_dpp
 // row_newbcast), two RK4 steps per phase, a fourth of the column work alternates between two SIMDs, base role with paired stages
@@ -104,11 +126,8 @@ hipError_t launch_indirect_stm_pipe48(int ndim, int pm, const IndirectArgs& a, b
 hipError_t launch_indirect_stm_pipe32(int ndim, int pm, const IndirectArgs& a, hipStream_t st);   // kernels_indirect_pipe32.hip
 // one RK4 step, lane = whole segment with all twelve STM columns (kernels_indirect_stream.hip): the HBM-bound corner of the sweep
 hipError_t launch_indirect_stm_stream(int ndim, int pm, const IndirectArgs& a, hipStream_t st);
-bool indirect_stm_stream_available(int ndim, int method, int steps, long S);
 // RK4, any number of steps, lane = whole segment with the full STM (kernels_indirect_lane.hip): batches that fill the chip many times over
 hipError_t launch_indirect_stm_lane(int pm, const IndirectArgs& a, hipStream_t st);
-bool indirect_stm_lane_available(int ndim, int method, long S);
-bool indirect_stm_pipe32_available(int ndim, int pm);
 hipError_t launch_direct_defect(int nstate, const DirectArgs& a, hipStream_t st);
 hipError_t launch_direct_jacobian(int nstate, const DirectArgs& a, hipStream_t st);
 // base wave + one wave per sensitivity column for 32 segments, skewed by one RKF7(8) step (one barrier per step)

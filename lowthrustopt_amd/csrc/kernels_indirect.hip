@@ -3,7 +3,7 @@
 
 namespace lto {
 
-hipError_t launch_indirect_defect(int pm, int method, const IndirectArgs& a, hipStream_t st) {
+template <> hipError_t launch_defect_nd<12>(int pm, int method, const IndirectArgs& a, hipStream_t st) {
   if (a.S <= 0) return hipSuccess;
   switch (method) {
     case M_RK4: return launch_pm<12, M_RK4, 0>(pm, a, st);
@@ -14,7 +14,7 @@ hipError_t launch_indirect_defect(int pm, int method, const IndirectArgs& a, hip
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_indirect_stm(int pm, int method, int cols, const IndirectArgs& a, hipStream_t st) {
+template <> hipError_t launch_stm_nd<12>(int pm, int method, int cols, const IndirectArgs& a, hipStream_t st) {
   if (a.S <= 0) return hipSuccess;
   if (method == M_RK4) {
     if (cols == 0) {
@@ -34,6 +34,14 @@ hipError_t launch_indirect_stm(int pm, int method, int cols, const IndirectArgs&
   // 13-stage methods: no per-lane STM form (round 6: the memory-resident one-column-per-lane kernels, never AUTO's choice, are gone --
   // lto_api.hip sends such sweeps to the cooperative kernels)
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_indirect_defect(int ndim, int pm, int method, const IndirectArgs& a, hipStream_t st) {
+  return ndim == 12 ? launch_defect_nd<12>(pm, method, a, st) : launch_defect_nd<14>(pm, method, a, st);
+}
+
+hipError_t launch_indirect_stm(int ndim, int pm, int method, int cols, const IndirectArgs& a, hipStream_t st) {
+  return ndim == 12 ? launch_stm_nd<12>(pm, method, cols, a, st) : launch_stm_nd<14>(pm, method, cols, a, st);
 }
 
 hipError_t launch_indirect_dense(int ndim, int pm, int method, const IndirectArgs& a, const DenseArgs& d, hipStream_t st) {

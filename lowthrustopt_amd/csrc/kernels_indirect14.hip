@@ -4,7 +4,7 @@
 
 namespace lto {
 
-hipError_t launch_indirect14_defect(int pm, int method, const IndirectArgs& a, hipStream_t st) {
+template <> hipError_t launch_defect_nd<14>(int pm, int method, const IndirectArgs& a, hipStream_t st) {
   if (a.S <= 0) return hipSuccess;
   switch (method) {
     case M_RK4: return launch_pm<14, M_RK4, 0>(pm, a, st);
@@ -15,7 +15,7 @@ hipError_t launch_indirect14_defect(int pm, int method, const IndirectArgs& a, h
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_indirect14_stm(int pm, int method, int cols, const IndirectArgs& a, hipStream_t st) {
+template <> hipError_t launch_stm_nd<14>(int pm, int method, int cols, const IndirectArgs& a, hipStream_t st) {
   if (a.S <= 0) return hipSuccess;
   if (method == M_RK4) {
     if (cols == 0) cols = (((long)a.S + 63) / 64 * 14 <= 4096) ? 1 : 2;

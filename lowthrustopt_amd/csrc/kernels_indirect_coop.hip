@@ -389,14 +389,7 @@ static hipError_t launch_coop_one(const IndirectArgs& a, hipStream_t st) {
 
 template <int ND, int METHOD>
 static hipError_t launch_coop_pm(int pm, const IndirectArgs& a0, hipStream_t st) {
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_coop_one<ND, PM_P0, METHOD>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_coop_one<ND, PM_P1, METHOD>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P2))) e = launch_coop_one<ND, PM_P2, METHOD>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_PGEN))) e = launch_coop_one<ND, PM_PGEN, METHOD>(a, st);
-  return e;
+  return for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_coop_one<ND, decltype(cls)::value, METHOD>(a, st); });
 }
 
 hipError_t launch_indirect_stm_coop(int ndim, int pm, int method, const IndirectArgs& a, hipStream_t st) {

@@ -489,17 +489,13 @@ static hipError_t launch_coop2_one(const IndirectArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// 12-dim system, DOP853 adaptive only.
-hipError_t launch_indirect_stm_coop2(int pm, const IndirectArgs& a0, hipStream_t st) {
+hipError_t launch_indirect_stm_coop2_14(int pm, const IndirectArgs& a, hipStream_t st);   // kernels_indirect_coop2_14.hip
+
+// DOP853 adaptive only; the 12-dim system here, the 14-dim one in its own translation unit.
+hipError_t launch_indirect_stm_coop2(int ndim, int pm, const IndirectArgs& a0, hipStream_t st) {
+  if (ndim != 12) return launch_indirect_stm_coop2_14(pm, a0, st);
   if (a0.S <= 0) return hipSuccess;
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_coop2_one<PM_P0>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_coop2_one<PM_P1>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P2))) e = launch_coop2_one<PM_P2>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_PGEN))) e = launch_coop2_one<PM_PGEN>(a, st);
-  return e;
+  return for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_coop2_one<decltype(cls)::value>(a, st); });
 }
 
 }  // namespace lto

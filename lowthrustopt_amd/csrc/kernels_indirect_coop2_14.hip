@@ -423,18 +423,11 @@ static hipError_t launch_coop14_one(const IndirectArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-bool indirect_stm_coop2_14_available(int pm) { return (pm & ~((1 << PM_P0) | (1 << PM_P1))) == 0; }
-
 // 14-dim system, DOP853 adaptive, batches of the always-thrust-limited laws only (p = 0, p = 1).
 hipError_t launch_indirect_stm_coop2_14(int pm, const IndirectArgs& a0, hipStream_t st) {
   if (a0.S <= 0) return hipSuccess;
   if (!indirect_stm_coop2_14_available(pm) || !a0.Phi) return hipErrorInvalidValue;
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_coop14_one<PM_P0>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_coop14_one<PM_P1>(a, st);
-  return e;
+  return for_classes<PM_P0, PM_P1>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_coop14_one<decltype(cls)::value>(a, st); });
 }
 
 }  // namespace lto

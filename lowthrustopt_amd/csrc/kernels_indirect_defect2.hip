@@ -391,42 +391,21 @@ static hipError_t launch_defect4_one(const IndirectArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// 14-dim system, DOP853 adaptive, defect only, four lanes per segment: batches of the always-thrust-limited laws (p = 0, p = 1)
-hipError_t launch_indirect14_defect4(int pm, const IndirectArgs& a0, hipStream_t st) {
+// DOP853 adaptive, defect only, four lanes per segment: the 12-dim system, and the 14-dim one for batches of the
+// always-thrust-limited laws (p = 0, p = 1)
+hipError_t launch_indirect_defect4(int ndim, int pm, const IndirectArgs& a0, hipStream_t st) {
   if (a0.S <= 0) return hipSuccess;
-  if ((pm & ~((1 << PM_P0) | (1 << PM_P1))) != 0 || !a0.defect) return hipErrorInvalidValue;
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_defect4_one<PM_P0, 14>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_defect4_one<PM_P1, 14>(a, st);
-  return e;
-}
-
-// 12-dim system, DOP853 adaptive, defect only, four lanes per segment.
-hipError_t launch_indirect_defect4(int pm, const IndirectArgs& a0, hipStream_t st) {
-  if (a0.S <= 0) return hipSuccess;
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_defect4_one<PM_P0>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_defect4_one<PM_P1>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P2))) e = launch_defect4_one<PM_P2>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_PGEN))) e = launch_defect4_one<PM_PGEN>(a, st);
-  return e;
+  if (ndim == 14) {
+    if (!indirect_stm_coop2_14_available(pm) || !a0.defect) return hipErrorInvalidValue;
+    return for_classes<PM_P0, PM_P1>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_defect4_one<decltype(cls)::value, 14>(a, st); });
+  }
+  return for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_defect4_one<decltype(cls)::value>(a, st); });
 }
 
 // 12-dim system, DOP853 adaptive, defect only.
 hipError_t launch_indirect_defect2(int pm, const IndirectArgs& a0, hipStream_t st) {
   if (a0.S <= 0) return hipSuccess;
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_defect2_one<PM_P0>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_defect2_one<PM_P1>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P2))) e = launch_defect2_one<PM_P2>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_PGEN))) e = launch_defect2_one<PM_PGEN>(a, st);
-  return e;
+  return for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_defect2_one<decltype(cls)::value>(a, st); });
 }
 
 }  // namespace lto

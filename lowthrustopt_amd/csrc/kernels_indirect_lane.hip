@@ -305,19 +305,10 @@ static hipError_t launch_lane_one(const IndirectArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-bool indirect_stm_lane_available(int ndim, int method, long S) { return ndim == 12 && method == M_RK4 && S < (1L << 29); }
-
 hipError_t launch_indirect_stm_lane(int pm, const IndirectArgs& a0, hipStream_t st) {
   if (a0.S <= 0) return hipSuccess;
   if (a0.steps < 1 || !a0.Phi || a0.order) return hipErrorInvalidValue;
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_lane_one<PM_P0>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_lane_one<PM_P1>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P2))) e = launch_lane_one<PM_P2>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_PGEN))) e = launch_lane_one<PM_PGEN>(a, st);
-  return e;
+  return for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_lane_one<decltype(cls)::value>(a, st); });
 }
 
 }  // namespace lto

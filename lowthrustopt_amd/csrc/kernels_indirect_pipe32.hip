@@ -301,29 +301,13 @@ static hipError_t launch_pipe32_one(const IndirectArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// Which (dimension, control-law classes) this form is built for.
-bool indirect_stm_pipe32_available(int ndim, int pm) {
-  if (ndim == 12) return true;
-  return ndim == 14 && !(pm & ((1 << PM_P2) | (1 << PM_PGEN)));
-}
-
 // RK4 only; steps >= 1.
 hipError_t launch_indirect_stm_pipe32(int ndim, int pm, const IndirectArgs& a0, hipStream_t st) {
   if (a0.S <= 0) return hipSuccess;
   if (a0.steps < 1 || !indirect_stm_pipe32_available(ndim, pm)) return hipErrorInvalidValue;
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (ndim == 12) {
-    if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_pipe32_one<12, PM_P0>(a, st);
-    if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_pipe32_one<12, PM_P1>(a, st);
-    if (e == hipSuccess && (pm & (1 << PM_P2))) e = launch_pipe32_one<12, PM_P2>(a, st);
-    if (e == hipSuccess && (pm & (1 << PM_PGEN))) e = launch_pipe32_one<12, PM_PGEN>(a, st);
-  } else {
-    if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_pipe32_one<14, PM_P0>(a, st);
-    if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_pipe32_one<14, PM_P1>(a, st);
-  }
-  return e;
+  if (ndim == 12)
+    return for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_pipe32_one<12, decltype(cls)::value>(a, st); });
+  return for_classes<PM_P0, PM_P1>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_pipe32_one<14, decltype(cls)::value>(a, st); });
 }
 
 }  // namespace lto

@@ -264,14 +264,7 @@ static hipError_t launch_pipe48_one(const IndirectArgs& a, hipStream_t st) {
 
 template <int ND, int SEG>
 static hipError_t launch_pipe48_pm(int pm, const IndirectArgs& a0, hipStream_t st) {
-  IndirectArgs a = a0;
-  a.class_filter = single_class(pm) ? 0 : 1;
-  hipError_t e = hipSuccess;
-  if (e == hipSuccess && (pm & (1 << PM_P0))) e = launch_pipe48_one<ND, PM_P0, SEG>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P1))) e = launch_pipe48_one<ND, PM_P1, SEG>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_P2))) e = launch_pipe48_one<ND, PM_P2, SEG>(a, st);
-  if (e == hipSuccess && (pm & (1 << PM_PGEN))) e = launch_pipe48_one<ND, PM_PGEN, SEG>(a, st);
-  return e;
+  return for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) { return launch_pipe48_one<ND, decltype(cls)::value, SEG>(a, st); });
 }
 
 // RK4 only; steps >= 1.  seg44: the 44-segment form (12-dim only; ignored for 14).

@@ -148,10 +148,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   }
 }
 
-bool indirect_stm_stream_available(int ndim, int method, int steps, long S) {
-  return (ndim == 12 || ndim == 14) && method == M_RK4 && steps == 1 && S < (1L << 29);
-}
-
 // One launch whatever the batch's control laws (PM_ANY): mixed-class batches used to be one launch per class.
 hipError_t launch_indirect_stm_stream(int ndim, int pm, const IndirectArgs& a, hipStream_t st) {
   (void)pm;

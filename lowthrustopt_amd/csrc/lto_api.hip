@@ -23,14 +23,6 @@
 
 using namespace lto;
 
-// RK4 STM sweeps with >= 6 steps, 12-dim: microseconds per round of the form whose lane is a whole segment (kernels_indirect_lane.hip;
-// a round = 256 segments per CU) at 64 steps on MI355X, for AUTO's comparison with the pipelines' round costs (default of
-// lto_ctx::lane_round_us; lto_calibrate_kernels measures it on the context's own device).
-static const double kLaneRoundUs = 505.0;      // round 6 (explicit register parking, matrices from the base evaluations' by-products): was 590
-// us per round at 64 steps, MI355X: [12-dim | 14-dim][eight-wave (16 x CUs) | 48-segment (48 x CUs) | per-lane with 3 columns (64 x CUs) |
-// 44-segment (44 x CUs) | 32-segment (32 x CUs)]; lto_calibrate_kernels replaces them with the context's own device's
-static const double kRoundCostDefault[2][5] = {{63.0, 165.0, 246.0, 139.0, 111.0}, {72.0, 191.0, 1e300, 1e300, 128.0}};
-
 struct lto_ctx {
   int device;
   int cu_count;    // compute units of the device: the kernel choice works in rounds of workgroups per CU
@@ -479,7 +471,7 @@ static int plan_build(lto_ctx* c, int ndim, int n_nodes, int n_batch, const lto_
   }
   // Page-locked landing place of the trial-step statistics that steer AUTO's lanes per segment (lto_indirect_defect_dev): here, not
   // in the first sweep that wants it -- a sweep may be inside a caller's graph capture, where nothing may be allocated.
-  if (ndim == 12 && integ->method == LTO_DOP853_ADAPTIVE && p->S >= 64L * c->cu_count) {
+  if (defect_stats_wanted(ndim, integ->method, LTO_KERNEL_AUTO, 0, p->S, c->cu_count)) {
     void* hp = nullptr; void* dp = nullptr;
     if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess &&
         pool_alloc(c, (void**)&p->d_stats_acc, sizeof(unsigned long long) * 4) == hipSuccess &&
@@ -581,7 +573,7 @@ static hipError_t segment_order(int kind, const int* nacc, const int* nrej, long
 }
 
 // Record staging (12-dim plans with the reference's integrator setting): the buffers come with the lane order, outside any sweep.
-static bool stage_capable(const lto_indirect_plan* p) { return p->ndim == 12 && p->integ.method == LTO_DOP853_ADAPTIVE; }
+static bool stage_capable(const lto_indirect_plan* p) { return indirect_records_available(p->ndim, p->integ.method); }
 // need_phi: the plan runs STM sweeps, so the [S][144] Phi records are wanted too.  A defect-only plan (the line search's S x 20
 // trial plan) never gets them: at 256 x 1 024 x 20 segments they would pin 6 GB nothing reads (advisor finding, round 4).  An
 // allocation that fails switches staging off for what it was for -- the sweeps then gather from the caller's arrays as before --
@@ -654,9 +646,9 @@ int lto_indirect_plan_set_kernel(lto_indirect_plan* p, int kernel) {
     return set_err(p->ctx, LTO_EINVAL, "kernel must be LTO_KERNEL_AUTO, _PER_LANE, _COOP, _PIPE8, _COOP2, _PIPE48, _PIPE32 or _LANE");
   if (kernel == LTO_KERNEL_LANE && !indirect_stm_lane_available(p->ndim, p->integ.method, p->S))
     return set_err(p->ctx, LTO_EINVAL, "LTO_KERNEL_LANE is built for 12-dim RK4 plans");
-  if (kernel == LTO_KERNEL_COOP2 && (p->integ.method != LTO_DOP853_ADAPTIVE || (p->ndim != 12 && !indirect_stm_coop2_14_available(p->pm))))
+  if (kernel == LTO_KERNEL_COOP2 && !indirect_stm_coop2_available(p->ndim, p->integ.method, p->pm))
     return set_err(p->ctx, LTO_EINVAL, "LTO_KERNEL_COOP2 is built for DOP853_ADAPTIVE plans: 12-dim, and 14-dim with p = 0 or p = 1");
-  if ((kernel == LTO_KERNEL_PIPE8 || kernel == LTO_KERNEL_PIPE48 || kernel == LTO_KERNEL_PIPE32) && p->integ.method != LTO_RK4)
+  if ((kernel == LTO_KERNEL_PIPE8 || kernel == LTO_KERNEL_PIPE48 || kernel == LTO_KERNEL_PIPE32) && !indirect_stm_pipeline_available(p->integ.method))
     return set_err(p->ctx, LTO_EINVAL, "the pipeline kernels are built for fixed-step RK4 plans");
   if (kernel == LTO_KERNEL_PIPE32 && !indirect_stm_pipe32_available(p->ndim, p->pm))
     return set_err(p->ctx, LTO_EINVAL, "LTO_KERNEL_PIPE32 is built for 12-dim plans and for 14-dim plans with p = 0 or p = 1");
@@ -669,8 +661,7 @@ int lto_indirect_plan_last_kernel(const lto_indirect_plan* p) { return p ? p->la
 int lto_indirect_plan_set_defect_lanes(lto_indirect_plan* p, int lanes) {
   if (!p) return LTO_ENULL;
   if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4) return set_err(p->ctx, LTO_EINVAL, "defect lanes must be 0 (choose), 1, 2 or 4");
-  const bool quad14 = p->ndim == 14 && p->integ.method == LTO_DOP853_ADAPTIVE && indirect_stm_coop2_14_available(p->pm);
-  if (lanes > 1 && !(p->ndim == 12 && p->integ.method == LTO_DOP853_ADAPTIVE) && !(lanes == 4 && quad14))
+  if ((lanes == 2 && !indirect_defect2_available(p->ndim, p->integ.method)) || (lanes == 4 && !indirect_defect4_available(p->ndim, p->integ.method, p->pm)))
     return set_err(p->ctx, LTO_EINVAL, "two and four lanes per segment are built for 12-dim DOP853_ADAPTIVE plans (the reference's integrator setting); "
                                        "four also for 14-dim DOP853_ADAPTIVE plans with p = 0 or p = 1");
   p->defect_lanes = lanes;
@@ -679,7 +670,7 @@ int lto_indirect_plan_set_defect_lanes(lto_indirect_plan* p, int lanes) {
 
 int lto_indirect_plan_set_warm_start(lto_indirect_plan* p, int on) {
   if (!p) return LTO_ENULL;
-  if (on && !(p->ndim == 12 && p->integ.method == LTO_DOP853_ADAPTIVE))
+  if (on && !indirect_warm_start_available(p->ndim, p->integ.method))
     return set_err(p->ctx, LTO_EINVAL, "warm start is built for 12-dim DOP853_ADAPTIVE plans (the reference's integrator setting)");
   if (on) {
     // Both arrays are allocated and zeroed HERE, not inside the first warm sweep (advisor finding, round 3): a sweep may be part
@@ -745,6 +736,38 @@ static int fill_indirect_args(lto_indirect_plan* p, const double* X, long ldx, c
   return LTO_OK;
 }
 
+// Record staging of a sweep, for both entries below.  kernel_records: the form that runs reads node records and writes per-segment
+// records.  Balanced lane order (the global kind): nodes in, Phi / defects out as records (IndirectArgs::Xa / Pa / Da), coalesced
+// transposes either side of the sweep (records_out).  LTO_LAYOUT_BLOCKS: the caller's Phi / defect arrays ARE the records the kernel
+// writes -- no record arrays of the plan's own and no transposes behind the sweep, with or without a lane order.
+static int records_in(lto_indirect_plan* p, bool kernel_records, IndirectArgs* a, hipStream_t st, bool* staged) {
+  const bool blocks = p->out_blocks != 0;
+  *staged = a->order && p->order_kind == 1 && kernel_records && p->d_xa && (blocks || (p->d_da && (!a->Phi || p->d_pa)));
+  if (*staged) {
+    hipError_t q = launch_node_records(a->X, a->ldx, a->t, a->t_stride, p->n_nodes, (long)p->n_nodes * p->n_batch, p->d_xa, st);
+    if (q != hipSuccess) return set_err(p->ctx, LTO_EHIP, "launch_node_records", q);
+    a->Xa = p->d_xa;
+    if (a->Phi) a->Pa = p->d_pa;
+    if (a->defect) a->Da = p->d_da;
+  }
+  if (blocks && a->Phi) a->Pa = a->Phi;
+  if (blocks && a->defect) a->Da = a->defect;
+  return LTO_OK;
+}
+static hipError_t records_out(const lto_indirect_plan* p, bool staged, const IndirectArgs& a, hipStream_t st) {
+  if (!staged || p->out_blocks) return hipSuccess;
+  hipError_t e = a.Phi ? launch_pack_soa(p->d_pa, 144, p->S, a.Phi, a.ldp, st) : hipSuccess;
+  if (e == hipSuccess && a.Da) e = launch_pack_soa(p->d_da, 12, p->S, a.defect, a.ldd, st);
+  return e;
+}
+
+static hipError_t launch_defect(int lanes, const lto_indirect_plan* p, const IndirectArgs& a, hipStream_t st) {
+  if (lanes == 4) return launch_indirect_defect4(p->ndim, p->pm, a, st);
+  if (lanes == 2) return launch_indirect_defect2(p->pm, a, st);
+  return launch_indirect_defect(p->ndim, p->pm, p->integ.method, a, st);
+}
+
+// Fill args -> decide (sweep_policy.hpp defect_lanes) -> stage in -> launch -> stage out.
 int lto_indirect_defect_dev(lto_indirect_plan* p, void* stream, const double* X, long ldx, const double* t,
                             int n_tgrids, double* defect, long ldd, double* errors) {
   if (!p) return LTO_ENULL;
@@ -759,70 +782,33 @@ int lto_indirect_defect_dev(lto_indirect_plan* p, void* stream, const double* X,
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   timing_begin(c, st);
-  // The reference's setting (12-dim, DOP853).  Two lanes per segment (tools/probe_defect2.py: 29 segments 99 -> 73 us, 4 096:
-  // 119 -> 88 us, 65 536 ordered: 0.43 -> 0.32 ms, 262 144: 0.44 -> 0.38 ms; 524 288: 0.60 -> 0.73 ms, so one lane beyond);
-  // round 3: four lanes per segment (a DPP quad, 16 segments per wavefront) up to eight wavefronts per SIMD -- 4 096 segments:
-  // 90 -> 77 us, 65 536 ordered: 0.31 -> 0.27 ms, 131 072: 0.32 -> 0.30 ms; 262 144: 0.39 -> 0.52 ms, so two lanes there.
-  // LTO_KERNEL_PER_LANE / LTO_KERNEL_COOP2 on the plan, or lto_indirect_plan_set_defect_lanes, force one form.
-  const bool ref_setting = p->ndim == 12 && p->integ.method == LTO_DOP853_ADAPTIVE;
-  // the same integrator setting on the 14-dim system (always-thrust-limited laws): the quad form while the chip has a SIMD per 16
-  // segments to spare, as for 12-dim (round 6)
-  const bool quad14 = p->ndim == 14 && p->integ.method == LTO_DOP853_ADAPTIVE && indirect_stm_coop2_14_available(p->pm);
-  int lanes = 1;
-  if (quad14) lanes = p->defect_lanes ? p->defect_lanes : ((p->kernel == LTO_KERNEL_AUTO || p->kernel == LTO_KERNEL_COOP2) && (long)(p->S + 15) / 16 <= 32L * c->cu_count) ? 4 : 1;
-  if (ref_setting) {
-    if (p->defect_lanes) lanes = p->defect_lanes;
-    else if (p->kernel == LTO_KERNEL_COOP2) lanes = 2;
-    else if (p->kernel == LTO_KERNEL_AUTO) {
-      lanes = ((long)(p->S + 15) / 16 <= 32L * c->cu_count) ? 4 : (p->S <= 262144 ? 2 : 1);
-      // Those thresholds come from the C5 study, where the slowest segment takes 8 x the mean number of trial steps and sets the
-      // sweep's time: more lanes per segment = a shorter stream for it.  A sweep whose segments all take about the same number
-      // of steps (the 20 trial trajectories of a line search) is throughput-bound once the chip is full, and fewer lanes per
-      // segment issue fewer instructions per segment (tools/probe_linesearch_lanes.py, 20 x 4 096 segments: 166 / 147 / 124 us
-      // with 4 / 2 / 1 lanes; 20 x 1 024: 73 / 61 / 94).  The previous sweep's statistics say which case this is.
-      // The verdict is the same in every run of the same call sequence (advisor finding, round 4: it used to be "whatever has
-      // arrived by then", read while the kernel might still be writing): statistics are consumed only behind the event recorded
-      // after k_step_stats -- the host waits for it here, i.e. for the EARLIER sweep that launched it, which a Newton loop has
-      // long read back -- then latched in the plan until the next statistics launch is consumed.  Inside a graph capture nothing
-      // may be waited for: the latched verdict stands.
-      if (p->h_stats && p->S >= 64L * c->cu_count) {
-        if (p->stats_pending) {
-          hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-          if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-          if (cap == hipStreamCaptureStatusNone && hipEventSynchronize(p->stats_ev) == hipSuccess) {
-            p->stats_pending = 0;
-            const long long sum = p->h_stats[0], mx = p->h_stats[1], cnt = p->h_stats[2];
-            p->stats_lanes = 0;
-            if (cnt == p->S && sum > 0 && mx * (long long)p->S <= 3 * sum)      // max <= 3 x mean: no tail worth shortening
-              p->stats_lanes = (p->S <= 160L * c->cu_count) ? 2 : 1;
-          }
-        }
-        if (p->stats_lanes) lanes = p->stats_lanes;
-      }
+  const bool stats = defect_stats_wanted(p->ndim, p->integ.method, p->kernel, p->defect_lanes, p->S, c->cu_count);
+  if (stats && p->h_stats && p->stats_pending) {
+    // The verdict is the same in every run of the same call sequence (advisor finding, round 4: it used to be "whatever has
+    // arrived by then", read while the kernel might still be writing): statistics are consumed only behind the event recorded
+    // after k_step_stats -- the host waits for it here, i.e. for the EARLIER sweep that launched it, which a Newton loop has
+    // long read back -- then latched in the plan until the next statistics launch is consumed.  Inside a graph capture nothing
+    // may be waited for: the latched verdict stands.
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+    if (cap == hipStreamCaptureStatusNone && hipEventSynchronize(p->stats_ev) == hipSuccess) {
+      p->stats_pending = 0;
+      p->stats_lanes = defect_stats_verdict(p->h_stats[0], p->h_stats[1], p->h_stats[2], p->S, c->cu_count);
     }
   }
-  if (p->out_blocks && lanes == 1) lanes = 2;          // the one-lane kernel writes struct-of-arrays only
+  const int lanes = defect_lanes(p->ndim, p->integ.method, p->pm, p->S, p->kernel, p->defect_lanes, (stats && p->h_stats) ? p->stats_lanes : 0,
+                                 p->out_blocks != 0, c->cu_count);
   rc = warm_args(p, 1, lanes > 1, &a);
   if (rc) return rc;
-  // balanced lane order: nodes in, defects out as records (IndirectArgs::Xa / Da), coalesced transposes either side of the sweep
-  // (LTO_LAYOUT_BLOCKS: the caller's defect array is the record array -- no transpose behind the sweep, whatever the order)
-  const bool blocks = p->out_blocks != 0;
-  const bool staged = a.order && p->order_kind == 1 && lanes > 1 && p->d_xa && (blocks || p->d_da);
-  if (staged) {
-    hipError_t q = launch_node_records(X, ldx, t, a.t_stride, p->n_nodes, (long)p->n_nodes * p->n_batch, p->d_xa, st);
-    if (q != hipSuccess) return set_err(c, LTO_EHIP, "launch_node_records", q);
-    a.Xa = p->d_xa; a.Da = p->d_da;
-  }
-  if (blocks) a.Da = defect;
-  hipError_t e = lanes == 4        ? (p->ndim == 12 ? launch_indirect_defect4(p->pm, a, st) : launch_indirect14_defect4(p->pm, a, st))
-                 : lanes == 2      ? launch_indirect_defect2(p->pm, a, st)
-                 : (p->ndim == 12) ? launch_indirect_defect(p->pm, p->integ.method, a, st)
-                                   : launch_indirect14_defect(p->pm, p->integ.method, a, st);
-  if (e == hipSuccess && staged && !blocks) e = launch_pack_soa(p->d_da, 12, p->S, defect, ldd, st);
+  bool staged = false;
+  rc = records_in(p, lanes > 1, &a, st, &staged);
+  if (rc) return rc;
+  hipError_t e = launch_defect(lanes, p, a, st);
+  if (e == hipSuccess) e = records_out(p, staged, a, st);
   timing_end(c, st);
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_indirect_defect", e);
   warm_filled(p, 1, a);
-  if (ref_setting && p->kernel == LTO_KERNEL_AUTO && !p->defect_lanes && p->S >= 64L * c->cu_count) {
+  if (stats) {
     // statistics for the next sweep's choice (a few us, stream-ordered, written by the kernel itself into page-locked memory)
     // not after every sweep (the extra launch and its host write cost ~10 us): after the first two, then every sixteenth
     const int age = p->stats_age++;
@@ -836,38 +822,6 @@ int lto_indirect_defect_dev(lto_indirect_plan* p, void* stream, const double* X,
   return LTO_OK;
 }
 
-/* What LTO_KERNEL_AUTO resolves to for an STM sweep: a pure function of the plan's shape and the cost table (no device, no context
- * state), so that the choice at sizes this build never ran on -- the per-rank batches of an 8-GPU run -- can be pinned by a CPU test
- * (tests/test_auto_kernel.py).  cost: us per round at 64 steps of the eight-wave / 48-segment / (unused) / 44-segment / 32-segment
- * pipelines for this dimension; per_lane3_us: the 12-dim per-lane kernel with three columns, rounds of 64 x CUs (only for RK4 with
- * 2 ... 5 steps); lane_us: the whole-segment lanes, rounds of 256 x CUs.
- * RK4 with >= 6 steps: the pipelines -- the eight-wave form while the batch is one round of it (16 segments per CU), above that the
- * family whose rounds are cheapest for THIS segment count, a partly filled round costing a whole one.  (Round 6: the per-lane kernel
- * left this table -- its rounds, 246 us per 64 x CUs, never beat the 32-segment pipeline's, 2 x 111 us.)  RK4 with fewer steps: the
- * per-lane kernel (fill and drain phases outweigh the pipelines' shorter phase), on a full chip its whole-segment forms.  13-stage
- * methods: the cooperative kernels; 12-dim DOP853 (the reference's setting) the two-lanes-per-state form. */
-static int auto_stm_kernel(int ndim, int method, int steps, int pm, long S, long cus, bool ordered, int cols_per_lane, const double* cost,
-                           double per_lane3_us, double lane_us) {
-  const auto rounds = [&](long per_round) { return (double)((S + per_round - 1) / per_round); };
-  if (method != LTO_RK4)      // DOP853: the two-lanes-per-state forms (12-dim; 14-dim for batches of the always-thrust-limited laws, round 6)
-    return (method == LTO_DOP853_ADAPTIVE && (ndim == 12 || indirect_stm_coop2_14_available(pm))) ? LTO_KERNEL_COOP2 : LTO_KERNEL_COOP;
-  if (steps < 6) {
-    if (steps >= 2 && indirect_stm_lane_available(ndim, method, S) && !ordered && cols_per_lane == 0 &&
-        rounds(256 * cus) * lane_us < rounds(64 * cus) * per_lane3_us)
-      return LTO_KERNEL_LANE;
-    return LTO_KERNEL_PER_LANE;
-  }
-  if (S <= 16 * cus) return LTO_KERNEL_PIPE8;
-  const double t8 = rounds(16 * cus) * cost[0];
-  const double t48 = std::min(rounds(48 * cus) * cost[1], ndim == 12 ? rounds(44 * cus) * cost[3] : 1e300);
-  const double t32 = indirect_stm_pipe32_available(ndim, pm) ? rounds(32 * cus) * cost[4] : 1e300;
-  int kern = (t32 < t8 && t32 < t48) ? LTO_KERNEL_PIPE32 : (t48 <= t8 ? LTO_KERNEL_PIPE48 : LTO_KERNEL_PIPE8);
-  // the whole-segment lanes (kernels_indirect_lane.hip, 12-dim): rounds of 256 x CUs segments -- four wavefronts of 64 per CU, one per
-  // SIMD.  A partly filled round costs a whole one, so the pipelines keep the sizes just above a multiple of their own, smaller rounds.
-  if (indirect_stm_lane_available(ndim, method, S) && !ordered && rounds(256 * cus) * lane_us < std::min(std::min(t8, t48), t32)) kern = LTO_KERNEL_LANE;
-  return kern;
-}
-
 int lto_indirect_auto_kernel(int ndim, int method, int steps, double p, long n_segments, int n_cus, int ordered) {
   if ((ndim != 12 && ndim != 14) || method < LTO_RK4 || method > LTO_DOP853_ADAPTIVE || n_segments < 1 || n_cus < 1) return LTO_EINVAL;
   if (!(p == 0.0 || p >= 1.0)) return LTO_EINVAL;           // the reference's error("Invalid value of p!") is a run-time code; here: not a plan
@@ -875,11 +829,20 @@ int lto_indirect_auto_kernel(int ndim, int method, int steps, double p, long n_s
   return auto_stm_kernel(ndim, method, steps, pm, n_segments, n_cus, ordered != 0, 0, kRoundCostDefault[ndim == 14 ? 1 : 0], kRoundCostDefault[0][2], kLaneRoundUs);
 }
 
-// One-step RK4 STM sweeps (SURVEY 8d's HBM-bound corner): from this many segments AUTO's per-lane family runs the form whose lane is
-// a whole segment (kernels_indirect_stream.hip): one wavefront of 64 segments per SIMD of an MI355X.  Below, the per-(segment,
-// column group) lanes fill the chip with four to twelve times the wavefronts and the sweep is latency-bound either way.
-static const long kStreamMinSegments = 65536;
+static hipError_t launch_stm(const StmChoice& ch, const lto_indirect_plan* p, const IndirectArgs& a, hipStream_t st) {
+  switch (ch.kernel) {
+    case LTO_KERNEL_COOP: return launch_indirect_stm_coop(p->ndim, p->pm, p->integ.method, a, st);
+    case LTO_KERNEL_COOP2: return launch_indirect_stm_coop2(p->ndim, p->pm, a, st);
+    case LTO_KERNEL_PIPE8: return launch_indirect_stm_pipe8(p->ndim, p->pm, a, st);
+    case LTO_KERNEL_PIPE48: return launch_indirect_stm_pipe48(p->ndim, p->pm, a, ch.seg44, st);
+    case LTO_KERNEL_PIPE32: return launch_indirect_stm_pipe32(p->ndim, p->pm, a, st);
+    case LTO_KERNEL_LANE: return launch_indirect_stm_lane(p->pm, a, st);
+  }
+  return ch.stream ? launch_indirect_stm_stream(p->ndim, p->pm, a, st)
+                   : launch_indirect_stm(p->ndim, p->pm, p->integ.method, p->cols_per_lane, a, st);
+}
 
+// Fill args -> decide (sweep_policy.hpp resolve_stm) -> stage in -> launch -> stage out.
 int lto_indirect_jacobian_dev(lto_indirect_plan* p, void* stream, const double* X, long ldx, const double* t,
                               int n_tgrids, double* Phi, long ldp, double* defect, long ldd) {
   if (!p) return LTO_ENULL;
@@ -894,73 +857,27 @@ int lto_indirect_jacobian_dev(lto_indirect_plan* p, void* stream, const double* 
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   timing_begin(c, st);
-  // Kernel choice (DESIGN.md "Kernels"; measured on MI355X with tools/probe_kernels.py, profiles/r03_probe_kernels.txt).
-  // RK4 with >= 6 steps per segment: the three-role pipeline kernels.  A workgroup of the eight-wave form owns 16 segments and a
-  // CU holds one (91 KB of LDS), so up to 16 x CUs segments (4 096 on MI355X) the sweep is one round -- 14-dim 76 us, 12-dim 66 us
-  // against 106 / 89 us (four-wave form, removed), 173 / 136 us per-lane, 238 / 116 us cooperative -- and above that every family
-  // runs in rounds of the segments the chip holds at once, a partly filled round costing a whole one: the family with the
-  // cheapest rounds for THIS segment count wins (lto_ctx::round_cost: us per round at 64 steps; the ratios do not depend on the step count): the
-  // eight-wave form in rounds of 16 x CUs, the 48-segment / 16-wave form in rounds of 48 x CUs (12-dim: 44 x CUs), for 12-dim also the per-lane
-  // kernel with 3 columns per lane in rounds of 64 x CUs.  13-stage methods: the wave-specialised kernel (DOP853 @1e-13,
-  // 4 096 segments: 0.32 ms vs 1.9 ms per-lane), for the reference's setting (12-dim, DOP853) its two-lanes-per-state form.
-  int kern = p->kernel;
-  if (kern == LTO_KERNEL_AUTO)
-    kern = auto_stm_kernel(p->ndim, p->integ.method, p->integ.steps, p->pm, p->S, c->cu_count > 0 ? c->cu_count : 256, p->use_order != 0, p->cols_per_lane,
-                           c->round_cost[p->ndim == 14 ? 1 : 0], c->round_cost[0][2], c->lane_round_us);
-  // Families that are gone since round 6 resolve to the one that took over (results agree to round-off, lto_indirect_plan_last_kernel
-  // says what ran): the 13-stage methods have no per-lane STM form any more, RK4 no cooperative form, and 12-dim DOP853 only the
-  // two-lanes-per-state cooperative form.
-  if (p->integ.method != LTO_RK4 && kern == LTO_KERNEL_PER_LANE) kern = LTO_KERNEL_COOP;
-  if (p->integ.method == LTO_RK4 && kern == LTO_KERNEL_COOP)
-    kern = auto_stm_kernel(p->ndim, LTO_RK4, p->integ.steps < 6 ? 6 : p->integ.steps, p->pm, p->S, c->cu_count > 0 ? c->cu_count : 256, p->use_order != 0, 0,
-                           c->round_cost[p->ndim == 14 ? 1 : 0], c->round_cost[0][2], c->lane_round_us);
-  if (p->integ.method == LTO_DOP853_ADAPTIVE && p->ndim == 12 && kern == LTO_KERNEL_COOP) kern = LTO_KERNEL_COOP2;
-  // the large-batch pipeline has two forms for 12-dim (48 or 44 segments per workgroup, kernels_indirect_pipe48.hip): the cheaper
-  // rounds for this segment count, whether AUTO or the caller chose the family
-  bool seg44 = false;
-  if (kern == LTO_KERNEL_PIPE48 && p->ndim == 12) {
-    const long cus = c->cu_count > 0 ? c->cu_count : 256;
-    const double* cost = c->round_cost[0];
-    const auto rounds = [&](long per_round) { return (double)((p->S + per_round - 1) / per_round); };
-    seg44 = p->p48_form ? p->p48_form == 44 : rounds(44 * cus) * cost[3] < rounds(48 * cus) * cost[1];
-  }
-  p->last_kernel = kern;
-  rc = warm_args(p, 0, kern == LTO_KERNEL_COOP2, &a);
+  const StmChoice ch = resolve_stm(p->ndim, p->integ.method, p->integ.steps, p->pm, p->S, p->kernel, p->cols_per_lane, p->use_order != 0, p->p48_form,
+                                   c->cu_count > 0 ? c->cu_count : 256, c->round_cost, c->lane_round_us);
+  const bool kernel_records = ch.kernel == LTO_KERNEL_COOP2;
+  p->last_kernel = ch.kernel;
+  rc = warm_args(p, 0, kernel_records, &a);
   if (rc) return rc;
   p->stm_swept = 1;
   const bool blocks = p->out_blocks != 0;
-  if (blocks && kern != LTO_KERNEL_COOP2) return set_err(c, LTO_EUNSUPPORTED, "LTO_LAYOUT_BLOCKS needs the two-lanes-per-state cooperative kernel (LTO_KERNEL_AUTO or _COOP2)");
-  if (!blocks && a.order && p->order_kind == 1 && kern == LTO_KERNEL_COOP2 && p->d_xa && p->d_da && !p->d_pa && !p->stage_failed) {
+  if (blocks && !kernel_records) return set_err(c, LTO_EUNSUPPORTED, "LTO_LAYOUT_BLOCKS needs the two-lanes-per-state cooperative kernel (LTO_KERNEL_AUTO or _COOP2)");
+  if (!blocks && a.order && p->order_kind == 1 && kernel_records && p->d_xa && p->d_da && !p->d_pa && !p->stage_failed) {
     // the lane order was made before this plan's first STM sweep: the Phi records come now -- unless the stream is being captured
     // (an allocation may not happen there; this sweep then runs unstaged and a later one outside a capture allocates)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) (void)stage_alloc(p, true);
     else (void)hipGetLastError();
   }
-  // LTO_LAYOUT_BLOCKS: the caller's Phi / defect arrays are the per-segment records the kernel writes (IndirectArgs::Pa / Da) -- no
-  // record arrays of the plan's own and no transposes behind the sweep, with or without a lane order
-  const bool staged = a.order && p->order_kind == 1 && kern == LTO_KERNEL_COOP2 && p->d_xa && (blocks || (p->d_da && p->d_pa));
-  if (staged) {
-    hipError_t q = launch_node_records(X, ldx, t, a.t_stride, p->n_nodes, (long)p->n_nodes * p->n_batch, p->d_xa, st);
-    if (q != hipSuccess) return set_err(c, LTO_EHIP, "launch_node_records", q);
-    a.Xa = p->d_xa; a.Pa = p->d_pa;
-    if (a.defect) a.Da = p->d_da;
-  }
-  if (blocks) { a.Pa = Phi; if (a.defect) a.Da = defect; }
-  hipError_t e;
-  if (kern == LTO_KERNEL_COOP) e = launch_indirect_stm_coop(p->ndim, p->pm, p->integ.method, a, st);
-  else if (kern == LTO_KERNEL_COOP2) e = (p->ndim == 12) ? launch_indirect_stm_coop2(p->pm, a, st) : launch_indirect_stm_coop2_14(p->pm, a, st);
-  else if (kern == LTO_KERNEL_PIPE8) e = launch_indirect_stm_pipe8(p->ndim, p->pm, a, st);
-  else if (kern == LTO_KERNEL_PIPE48) e = launch_indirect_stm_pipe48(p->ndim, p->pm, a, seg44, st);
-  else if (kern == LTO_KERNEL_PIPE32) e = launch_indirect_stm_pipe32(p->ndim, p->pm, a, st);
-  else if (kern == LTO_KERNEL_LANE) e = launch_indirect_stm_lane(p->pm, a, st);
-  else if (!a.order && (p->cols_per_lane == p->ndim || (p->cols_per_lane == 0 && p->S >= kStreamMinSegments &&
-                                                        indirect_stm_stream_available(p->ndim, p->integ.method, p->integ.steps, p->S))))
-    e = launch_indirect_stm_stream(p->ndim, p->pm, a, st);   // one RK4 step on a full chip: lane = segment, HBM-bound (kernels_indirect_stream.hip)
-  else e = (p->ndim == 12) ? launch_indirect_stm(p->pm, p->integ.method, p->cols_per_lane, a, st)
-                           : launch_indirect14_stm(p->pm, p->integ.method, p->cols_per_lane, a, st);
-  if (e == hipSuccess && staged && !blocks) e = launch_pack_soa(p->d_pa, 144, p->S, a.Phi, a.ldp, st);
-  if (e == hipSuccess && staged && !blocks && a.Da) e = launch_pack_soa(p->d_da, 12, p->S, a.defect, a.ldd, st);
+  bool staged = false;
+  rc = records_in(p, kernel_records, &a, st, &staged);
+  if (rc) return rc;
+  hipError_t e = launch_stm(ch, p, a, st);
+  if (e == hipSuccess) e = records_out(p, staged, a, st);
   timing_end(c, st);
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_indirect_stm", e);
   warm_filled(p, 0, a);
