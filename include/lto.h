@@ -308,6 +308,34 @@ int lto_indirect_add_time(lto_ctx* ctx, int ndim, int n_nodes, const double* XC,
                           const lto_integrator* integ, const lto_direct_orbits* orbits, double dt, int n_desired,
                           int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
                           double* defect, int* status_flag, int* iterations, double* history, double* cost);
+/* Mesh re-distribution of converged 12-dim solutions (the indirect method's counterpart of meshRefine_direct): the
+ * nodes of XC [12 x n_nodes x n_batch] on t [n_nodes x n_tgrids] (n_tgrids = 1 or n_batch) are moved, and their number changed to
+ * n_new, so that every new segment carries the same share of a per-segment monitor w_i > 0.  Per trajectory:
+ *   monitor   weights [(n_nodes-1) x n_batch] if not NULL (passes must be 1), otherwise the trial-step counts (accepted + rejected)
+ *             of one defect sweep of the input on its own grid (adaptive integrators only);
+ *   grid      C_0 = 0, C_{i+1} = C_i + w_i, W = C_{n-1}; for 0 < k < n_new - 1: g_k = k W / (n_new - 1), i the largest index with
+ *             C_i <= g_k, t_out_k = t_i + (g_k - C_i) / w_i (t_{i+1} - t_i); the first and last time are the input's, bit for bit.
+ *             (The C_i are summed in a fixed radix-64 order; integer counts are exact in any order.)
+ *   nodes     new node k = the input's own piecewise trajectory at t_out_k: old node i (the largest i with t_i <= t_out_k)
+ *             propagated over t_out_k - t_i with integ (RK4: integ.steps steps over that span).  A zero span, the first and the
+ *             last node are copies, bit for bit.  These are XC_guess [12 x n_new x n_batch].
+ *   passes    > 1 (counts only): monitor, grid and nodes again on the result, `passes` times in all.
+ *   re-solve  XC_out not NULL: the Newton loop of lto_indirect_solve_batch on t_out [n_new x n_batch] started from the guess
+ *             (XC_out, defect [12 x (n_new-1) x n_batch], status_flag, iterations, history as there); NULL: grid and guess only.
+ * steps_before [(n_nodes-1) x n_batch] / steps_after [(n_new-1) x n_batch] (may be NULL): the trial steps of a one-lane-per-segment
+ * defect sweep of the input / of the result (of the guess without a re-solve); a fixed-step integrator reports integ.steps.
+ * Every output but t_out may be NULL.  ndim != 12 or an integrator other than LTO_RK4 / LTO_DOP853_ADAPTIVE: LTO_EUNSUPPORTED;
+ * weights == NULL with a fixed-step integrator, passes < 1, passes > 1 with weights, n_new < 2, a weight that is not finite and
+ * positive, a grid (the input's, or a pass's result) that is not strictly increasing, more than 262 144 segments: LTO_EINVAL. */
+int lto_indirect_remesh_batch(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                              const lto_params* prm, int n_prm, const lto_integrator* integ, int n_new, const double* weights,
+                              int passes, int flag_adjointsOnly, int maxIter, double* t_out, double* XC_guess, double* XC_out,
+                              double* defect, int* status_flag, int* iterations, double* history, int* steps_before,
+                              int* steps_after);
+int lto_indirect_remesh(lto_ctx* ctx, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                        const lto_integrator* integ, int n_new, const double* weights, int passes, int flag_adjointsOnly,
+                        int maxIter, double* t_out, double* XC_guess, double* XC_out, double* defect, int* status_flag,
+                        int* iterations, double* history, int* steps_before, int* steps_after);
 
 /* One Jacobian sweep and one free-end QP step (arguments as lto_direct_qp_step); targets, model and beta [n_targets] (1 or
  * n_batch).  p_out [2 x n_batch] = (p1; p2); cost includes the beta term.  The 2 x 2 bound-constrained problem in p is solved

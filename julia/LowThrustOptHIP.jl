@@ -16,7 +16,7 @@ using SparseArrays, LinearAlgebra, Libdl
 export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pack_soa!, unpack_soa!, defect_norms!, indirect_defect_dev!,
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
-export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, addTimeFinal, tf_sweep,
+export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, addTimeFinal, tf_sweep, meshRefine_indirect, remesh_batch,
        direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_qp_step, direct_solve, direct_end_states, direct_qp_step_free, direct_solve_free,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
@@ -294,6 +294,46 @@ function tf_sweep(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64
     end
     check(ctx, rc)
     (XC, t, tau, Int.(status), Int.(iters), cost)
+end
+
+"""Mesh re-distribution of a converged 12-row indirect solution (`lto_indirect_remesh`, DESIGN 4.13), the counterpart of
+meshRefine_direct: `n_new` nodes (default: as many as before) placed so that every segment takes the same share of the integrator's
+trial steps (`passes` times over) or of `weights` [n_nodes - 1] (then `passes` must be 1), the new nodes taken from the solution's own
+piecewise trajectory, then the fixed-end Newton loop on the new grid.  Returns (XC_new, t_new, n_new) on status 0, otherwise the
+original (XC_all, t_TU, n_nodes) -- the convention of addTimeFinal."""
+function meshRefine_indirect(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}, MU, DU, TU, n_nodes, mass, thrustLimit,
+                             p, rho; n_new::Integer = n_nodes, passes::Integer = 2, weights::Union{Nothing,Vector{Float64}} = nothing,
+                             maxIter::Integer = 10, flag_adjointsOnly::Bool = false, integ::LtoIntegrator = LtoIntegrator())
+    ndim = size(XC_all, 1)
+    XC_new = zeros(ndim, n_new); t_new = zeros(n_new); defect1 = zeros(ndim, n_new - 1)
+    status = Ref{Cint}(0); iters = Ref{Cint}(0)
+    prm = Ref(LtoParams((MU, DU, TU, thrustLimit, mass, 1.0, p, rho)))
+    rc = ccall((:lto_indirect_remesh, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoParams}, Ref{LtoIntegrator}, Cint, Ptr{Cdouble}, Cint, Cint,
+                Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
+               ctx.handle, ndim, n_nodes, XC_all, t_TU, prm, Ref(integ), n_new, weights === nothing ? C_NULL : weights, passes,
+               flag_adjointsOnly ? 1 : 0, maxIter, t_new, C_NULL, XC_new, defect1, status, iters, C_NULL, C_NULL, C_NULL)
+    check(ctx, rc)
+    status[] == 0 ? (XC_new, t_new, Int(n_new)) : (XC_all, t_TU, Int(n_nodes))
+end
+
+"""Mesh re-distribution of n_batch solutions side by side (`lto_indirect_remesh_batch`): `XC_all` [12 x n_nodes x n_batch], `t_TU`
+[n_nodes x n_batch], `params` a vector of n_batch parameter tuples.  Returns (XC [12 x n_new x B], t [n_new x B], status [B],
+iterations [B], steps_before [(n_nodes-1) x B], steps_after [(n_new-1) x B])."""
+function remesh_batch(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::Matrix{Float64}, params::Vector; n_new::Integer = size(XC_all, 2),
+                      passes::Integer = 2, maxIter::Integer = 10, flag_adjointsOnly::Bool = false, integ::LtoIntegrator = LtoIntegrator())
+    ndim, n_nodes, B = size(XC_all)
+    prm = [LtoParams(q) for q in params]
+    XC = zeros(ndim, n_new, B); t = zeros(n_new, B); defect1 = zeros(ndim, n_new - 1, B)
+    status = zeros(Cint, B); iters = zeros(Cint, B); before = zeros(Cint, n_nodes - 1, B); after = zeros(Cint, n_new - 1, B)
+    rc = ccall((:lto_indirect_remesh_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Cint,
+                Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint},
+                Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
+               ctx.handle, ndim, n_nodes, B, XC_all, t_TU, B, prm, length(prm), Ref(integ), n_new, C_NULL, passes,
+               flag_adjointsOnly ? 1 : 0, maxIter, t, C_NULL, XC, defect1, status, iters, C_NULL, before, after)
+    check(ctx, rc)
+    (XC, t, Int.(status), Int.(iters), Int.(before), Int.(after))
 end
 
 # ---------------------------------------------------------------------------------------------- direct

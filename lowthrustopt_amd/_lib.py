@@ -88,6 +88,11 @@ SIGNATURES = {
     "lto_indirect_add_time": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator),
                                         C.POINTER(LtoDirectOrbits), C.c_double, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _vp, _vp, _vp]),
+    "lto_indirect_remesh_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.POINTER(LtoParams), C.c_int,
+                                            C.POINTER(LtoIntegrator), C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp]),
+    "lto_indirect_remesh": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator), C.c_int, _vp,
+                                      C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_direct_defect": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int,
                                     C.POINTER(LtoDirectParams), _vp, _vp]),
     "lto_direct_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int,

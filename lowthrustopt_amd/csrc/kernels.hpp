@@ -189,6 +189,34 @@ hipError_t launch_find_tau(const EndOrbitsDev& o, double* G, long ldg, int n, in
 // cost [K]: trapezoid over td of umag(|lambda_v|) along the dense outputs Y (layout as RemeshArgs), p / rho / aL of the control law
 hipError_t launch_dense_cost(const double* Y, long ldy, const double* td, int m, int K, double aL, double p, double rho, double* cost,
                              hipStream_t st);
+// Mesh equidistribution of the indirect method (kernels_remesh.hip).  Grid: per trajectory b the monitor of old segment
+// i is w[b (n-1) + i], or nacc + nrej there when w is null; old grids t[b t_stride + i].
+// Out: t_out [n_batch][n_new] and seg_of [n_batch][n_new], the old node each new one is propagated from.
+constexpr int kRemeshLdsSegs = 4096;         // segments whose partial sums one workgroup keeps in LDS
+constexpr int kRemeshMaxSegs = 64 * 64 * 64; // three radix-64 levels
+// doubles of scratch per trajectory above kRemeshLdsSegs segments (C, c_stride)
+inline size_t remesh_scratch_doubles(int n) {
+  const size_t m = (size_t)n - 1, m1 = (m + 63) / 64;
+  return ((m + 63) & ~(size_t)63) + ((m1 + 63) & ~(size_t)63);
+}
+struct RemeshGridArgs {
+  const double* t; int t_stride;
+  int n, n_new, n_batch;
+  const double* w;
+  const int* nacc; const int* nrej;
+  double* C; long c_stride;
+  double* t_out;
+  int* seg_of;
+};
+hipError_t launch_remesh_grid(const RemeshGridArgs& r, hipStream_t st);
+// Nodes: a = the sweep arguments of the OLD trajectories (X, t, tp, the integrator); new node j = b n_new + k -> G [12][ldg]
+struct RemeshNodeArgs {
+  const double* tn;
+  const int* seg_of;
+  double* G; long ldg;
+  int n_new, n_batch;
+};
+hipError_t launch_remesh_nodes(int pm, int method, const IndirectArgs& a, const RemeshNodeArgs& r, hipStream_t st);
 hipError_t launch_tau_update(double* tau, const double* p, const double* step, int n_batch, hipStream_t st);
 // free tf: tau and tf updates from p [n_batch][3]; the grids t [n_batch][n] from tau_grid, t0 [n_batch], tf [n_batch] and their na
 // copies per trajectory for the line search, tl [n_batch * na][n]

@@ -1,0 +1,152 @@
+// kernels_remesh.hip -- mesh equidistribution of a converged indirect solution: the new grid from a per-segment
+// monitor (k_remesh_grid) and the nodes of the input's own piecewise trajectory on it (k_remesh_nodes).
+#include "indirect_kernel.hpp"
+
+namespace lto {
+
+// ---- the grid.  One workgroup per trajectory.  Monitor w_i > 0 of old segment i (the caller's weights, or the trial-step counts
+// nacc + nrej of a defect sweep), C_0 = 0, C_{i+1} = C_i + w_i, W = C_{n-1}; new node k sits where the piecewise-linear C(t) reaches
+// g_k = k W / (n_new - 1).
+//
+// The scan has ONE summation order whatever the size and wherever the partial sums live (integer counts do not care, real weights
+// do): radix 64 in three levels.  A tile of 64 consecutive entries is scanned by a wavefront with six shift-and-add steps
+// (__shfl_up by 1, 2, .. 32: the DPP row / wave shifts; an LDS round trip per step would cost a barrier each); the tile totals are
+// scanned the same way, and theirs; then every entry adds the inclusive sum of the tiles before its own, top level first.
+// tests/remesh_reference.scan64 restates exactly this order.  64^3 = 262 144 segments is the limit (the host refuses more).
+// The partial sums of up to kRemeshLdsSegs segments stay in LDS; above that the same code runs on a global scratch block
+// (`C`, written and read by this workgroup only, between its own barriers).
+constexpr int kRemeshBlock = 256;
+
+__device__ __forceinline__ double tile_scan(double v, const int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const double u = __shfl_up(v, off, 64);
+    if (lane >= off) v += u;
+  }
+  return v;
+}
+
+// x[0 .. cnt) -> its tiles' inclusive scans in place, tot[T] = total of tile T.  Every wavefront takes whole tiles.
+__device__ __forceinline__ void scan_tiles(double* x, const int cnt, double* tot, const int tid) {
+  const int lane = tid & 63, tiles = (cnt + 63) >> 6;
+  for (int T = tid >> 6; T < tiles; T += kRemeshBlock / 64) {
+    const int i = T * 64 + lane;
+    const double v = tile_scan(i < cnt ? x[i] : 0.0, lane);
+    if (i < cnt) x[i] = v;
+    if (lane == 63) tot[T] = v;
+  }
+  __syncthreads();
+}
+
+// x[i] += inclusive sum of the tiles before i's (inc: the scanned tile totals)
+__device__ __forceinline__ void add_tile_offsets(double* x, const int cnt, const double* inc, const int tid) {
+  for (int i = tid; i < cnt; i += kRemeshBlock) {
+    const int T = i >> 6;
+    if (T) x[i] = inc[T - 1] + x[i];
+  }
+  __syncthreads();
+}
+
+template <bool IN_LDS>
+__global__ __launch_bounds__(kRemeshBlock) void k_remesh_grid(const RemeshGridArgs r) {
+#pragma clang fp contract(off)       // t'_k in the order the restatement writes it: no fused multiply-add
+  __shared__ double s1[IN_LDS ? kRemeshLdsSegs : 1], s2[IN_LDS ? kRemeshLdsSegs / 64 : 1], s3[64], s4[1];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = r.n, m = n - 1, n_new = r.n_new;
+  const int m1 = (m + 63) >> 6, m2 = (m1 + 63) >> 6;
+  double* c1 = IN_LDS ? s1 : r.C + (long)b * r.c_stride;
+  double* c2 = IN_LDS ? s2 : c1 + (((long)m + 63) & ~63L);
+  const double* t = r.t + (long)b * r.t_stride;
+  const double* w = r.w ? r.w + (long)b * m : nullptr;
+  const int* na = r.nacc ? r.nacc + (long)b * m : nullptr;
+  const int* nr = r.nrej ? r.nrej + (long)b * m : nullptr;
+  const auto monitor = [&](const int i) { return w ? w[i] : (double)(na[i] + nr[i]); };
+  for (int i = tid; i < m; i += kRemeshBlock) c1[i] = monitor(i);
+  __syncthreads();
+  scan_tiles(c1, m, c2, tid);
+  scan_tiles(c2, m1, s3, tid);
+  scan_tiles(s3, m2, s4, tid);
+  add_tile_offsets(c2, m1, s3, tid);
+  add_tile_offsets(c1, m, c2, tid);
+  // c1[i] = C_{i+1}
+  const double W = c1[m - 1];
+  double* tn = r.t_out + (long)b * n_new;
+  int* seg = r.seg_of + (long)b * n_new;
+  for (int k = tid; k < n_new; k += kRemeshBlock) {
+    if (k == 0) { tn[0] = t[0]; seg[0] = 0; continue; }
+    if (k == n_new - 1) { tn[k] = t[n - 1]; seg[k] = n - 1; continue; }
+    const double g = (double)k * W / (double)(n_new - 1);
+    int lo = 0, hi = m - 1;                     // the largest i in [0, m-1] with C_i <= g (a NaN g: i = 0)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (c1[mid - 1] <= g) lo = mid; else hi = mid - 1;
+    }
+    int i = lo;
+    const double Ci = i ? c1[i - 1] : 0.0;
+    const double ti = t[i];
+    const double tk = ti + (g - Ci) / monitor(i) * (t[i + 1] - ti);
+    // the node the new one is propagated from: the largest i with t_i <= t'_k (t'_k may round onto t_{i+1}: a copy of that node)
+    while (i < n - 1 && t[i + 1] <= tk) ++i;
+    tn[k] = tk;
+    seg[k] = i;
+  }
+}
+
+hipError_t launch_remesh_grid(const RemeshGridArgs& r, hipStream_t st) {
+  if (r.n_batch <= 0) return hipSuccess;
+  if (r.n < 2 || r.n_new < 2 || r.n - 1 > kRemeshMaxSegs) return hipErrorInvalidValue;
+  if (r.n - 1 <= kRemeshLdsSegs) hipLaunchKernelGGL(k_remesh_grid<true>, dim3(r.n_batch), dim3(kRemeshBlock), 0, st, r);
+  else {
+    if (!r.C || r.c_stride < (long)remesh_scratch_doubles(r.n)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_remesh_grid<false>, dim3(r.n_batch), dim3(kRemeshBlock), 0, st, r);
+  }
+  return hipGetLastError();
+}
+
+// ---- the nodes.  Lane = NEW node j = b n_new + k: it gathers old node seg_of[j] of its trajectory, integrates over its own span
+// t'_k - t_seg with the plan's integrator (advance<>, as the sweeps and k_indirect_dense) and stores struct-of-arrays in the solve
+// loop's node layout.  The new nodes inside one heavy old segment run side by side; no lane integrates further than one old
+// segment.  A zero span (the first and the last node always) stores the gathered node bit for bit.
+template <int PM, int METHOD>
+__global__ __launch_bounds__(64) void k_remesh_nodes(const IndirectArgs a, const RemeshNodeArgs r) {
+  const long j = (long)blockIdx.x * 64 + threadIdx.x;
+  if (j >= (long)r.n_new * r.n_batch) return;
+  const int traj = (int)(j / r.n_new);
+  using Sys = SysIndirect<12, PM, 0>;
+  Sys sys;
+  sys.tp = a.tp[(long)traj * a.tp_stride];
+  if (a.class_filter && p_class(sys.tp.p) != PM) return;
+  sys.w2 = 2.0 * sys.tp.omega;
+  const int i = r.seg_of[j];
+  const long node = (long)traj * a.n_nodes + i;
+  double y[12];
+#pragma unroll
+  for (int c = 0; c < 12; ++c) y[c] = a.X[c * a.ldx + node];
+  const double span = r.tn[j] - a.t[(long)traj * a.t_stride + i];
+  int nacc = 0, nrej = 0;
+  double maxErr = 0.0;
+  if (span > 0.0) advance<Sys, 12, METHOD>(sys, span, a, y, nacc, nrej, maxErr);
+#pragma unroll
+  for (int c = 0; c < 12; ++c) r.G[c * r.ldg + j] = y[c];
+}
+
+template <int METHOD>
+static hipError_t launch_remesh_nodes_pm(int pm, const IndirectArgs& a0, const RemeshNodeArgs& r, hipStream_t st) {
+  dim3 grid((unsigned)(((long)r.n_new * r.n_batch + 63) / 64));
+  (void)for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) {
+    hipLaunchKernelGGL((k_remesh_nodes<decltype(cls)::value, METHOD>), grid, dim3(64), 0, st, a, r);
+    return hipSuccess;
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_remesh_nodes(int pm, int method, const IndirectArgs& a, const RemeshNodeArgs& r, hipStream_t st) {
+  if ((long)r.n_new * r.n_batch <= 0) return hipSuccess;
+  switch (method) {
+    case M_RK4: return launch_remesh_nodes_pm<M_RK4>(pm, a, r, st);
+    case M_DOP853_ADAPTIVE: return launch_remesh_nodes_pm<M_DOP853_ADAPTIVE>(pm, a, r, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+}  // namespace lto

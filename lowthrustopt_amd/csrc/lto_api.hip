@@ -2357,6 +2357,164 @@ int lto_indirect_add_time(lto_ctx* c, int ndim, int n_nodes, const double* XC, c
                                      XC_guess, XC_out, t_out, tau_out, defect, status_flag, iterations, history, cost);
 }
 
+/* Mesh equidistribution of converged 12-dim solutions, every phase on the device: per pass the monitor (the caller's
+ * weights, or the trial-step counts of a one-lane defect sweep of the current trajectories), the new grids (k_remesh_grid) and the
+ * current trajectories' own states on them (k_remesh_nodes); then, if XC_out is set, the Newton loop of lto_indirect_solve_batch
+ * started from the last pass's nodes in HBM.  Between the upload of XC, t and weights and the download of the results only the new
+ * grids (once per pass: the host checks them, and the solve loop takes its grids from the host) and the step counts come down. */
+int lto_indirect_remesh_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                              const lto_params* prm, int n_prm, const lto_integrator* integ, int n_new, const double* weights,
+                              int passes, int flag_adjointsOnly, int maxIter, double* t_out, double* XC_guess, double* XC_out,
+                              double* defect, int* status_flag, int* iterations, double* history, int* steps_before,
+                              int* steps_after) {
+  if (!c) return LTO_ENULL;
+  if (!XC || !t || !prm || !integ || !t_out || (XC_out && !status_flag))
+    return set_err(c, LTO_ENULL, "lto_indirect_remesh_batch: a required argument is NULL");
+  if (ndim != 12) return set_err(c, LTO_EUNSUPPORTED, "lto_indirect_remesh_batch: ndim must be 12 (dense output)");
+  if (integ->method != LTO_RK4 && integ->method != LTO_DOP853_ADAPTIVE)
+    return set_err(c, LTO_EUNSUPPORTED, "lto_indirect_remesh_batch: dense output is built for LTO_RK4 and LTO_DOP853_ADAPTIVE");
+  const bool adaptive = integ->method == LTO_DOP853_ADAPTIVE;
+  if (n_batch < 1 || n_nodes < 2 || n_new < 2 || maxIter < 0 || passes < 1)
+    return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: need n_batch >= 1, n_nodes >= 2, n_new >= 2, maxIter >= 0, passes >= 1");
+  if ((n_tgrids != 1 && n_tgrids != n_batch) || (n_prm != 1 && n_prm != n_batch))
+    return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: n_tgrids / n_prm must be 1 or n_batch");
+  if (!weights && !adaptive) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: a fixed-step integrator has no step counts: pass weights");
+  if (weights && passes > 1) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: passes > 1 needs the step counts as the monitor (weights == NULL)");
+  const int B = n_batch, n0 = n_nodes, nn = n_new, nmax = n0 > nn ? n0 : nn;
+  if (nmax - 1 > kRemeshMaxSegs) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: more than 262144 segments per trajectory");
+  if ((long)B * nmax * 12 > 0x7fffffffL) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: batch too large");
+  const auto increasing = [](const double* g, int n, int count) {
+    for (int b = 0; b < count; ++b)
+      for (int i = 0; i + 1 < n; ++i)
+        if (!(g[(size_t)b * n + i] < g[(size_t)b * n + i + 1]) || !std::isfinite(g[(size_t)b * n + i + 1] - g[(size_t)b * n + i])) return false;
+    return true;
+  };
+  if (!increasing(t, n0, n_tgrids)) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: t must be finite and strictly increasing");
+  const long J0 = (long)B * n0, Jn = (long)B * nn, S0 = J0 - B, Sn = Jn - B, Smax = (long)B * (nmax - 1);
+  if (weights)
+    for (long i = 0; i < S0; ++i)
+      if (!(weights[i] > 0.0) || !std::isfinite(weights[i])) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: every weight must be finite and > 0");
+  int rc = bind_device(c);
+  if (rc) return rc;
+  CallTimer call_timer(c);
+  lto::HostBuf<int> h_cnt((size_t)2 * Smax);                // step counters on their way out (the stream copies into it)
+  if (!h_cnt.ok()) return set_err(c, LTO_ENOMEM, "lto_indirect_remesh_batch: out of host memory");
+  // device side: one block, carved 256-B aligned
+  const long Jmax = J0 > Jn ? J0 : Jn;
+  const size_t c_stride = nmax - 1 > kRemeshLdsSegs ? remesh_scratch_doubles(nmax) : 0;
+  const bool want_final = XC_out && steps_after && adaptive;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off += al256(bytes); return at; };
+  const size_t o_xa = take(sizeof(double) * 12 * Jmax), o_x0 = take(sizeof(double) * 12 * J0), o_g0 = take(sizeof(double) * 12 * Jn),
+               o_g1 = take(passes > 1 ? sizeof(double) * 12 * Jn : 0), o_xf = take(want_final ? sizeof(double) * 12 * Jn : 0),
+               o_t0 = take(sizeof(double) * n0 * n_tgrids), o_tn0 = take(sizeof(double) * Jn),
+               o_tn1 = take(passes > 1 ? sizeof(double) * Jn : 0), o_seg = take(sizeof(int) * Jn),
+               o_w = take(weights ? sizeof(double) * S0 : 0), o_def = take(adaptive ? sizeof(double) * 12 * Smax : 0),
+               o_c = take(sizeof(double) * c_stride * B);
+  HostCall call(c);
+  hipStream_t st = c->stream;
+  hipError_t e = hipMalloc(&call.block[0], off);
+  if (e != hipSuccess) { call.block[0] = nullptr; return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch", e); }
+  char* base = (char*)call.block[0];
+  double *d_xa = (double*)(base + o_xa), *d_x0 = (double*)(base + o_x0), *d_xf = (double*)(base + o_xf), *d_t0 = (double*)(base + o_t0),
+         *d_w = (double*)(base + o_w), *d_def = (double*)(base + o_def), *d_c = (double*)(base + o_c);
+  double* d_g[2] = {(double*)(base + o_g0), (double*)(base + o_g1)};
+  double* d_tn[2] = {(double*)(base + o_tn0), (double*)(base + o_tn1)};
+  int* d_seg = (int*)(base + o_seg);
+  e = hipMemcpyAsync(d_xa, XC, sizeof(double) * 12 * J0, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_t0, t, sizeof(double) * n0 * n_tgrids, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && weights) e = hipMemcpyAsync(d_w, weights, sizeof(double) * S0, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = launch_pack_soa(d_xa, 12, J0, d_x0, J0, st);
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: stage in", e);
+  // trial steps of a defect sweep of X on tg, one lane per segment whatever the batch size (a batch's counts are its singles'):
+  // left in the plan's counters; host_out (if set) = accepted + rejected once the stream has been waited for
+  int* pending_out = nullptr;
+  long pending_S = 0;
+  auto count_sweep = [&](lto_indirect_plan* p, const double* X, long J, const double* tg, int ntg, int* host_out) -> int {
+    p->defect_lanes = 1;
+    int r = lto_indirect_defect_dev(p, st, X, J, tg, ntg, d_def, p->S, nullptr);
+    if (r || !host_out) return r;
+    hipError_t q = hipMemcpyAsync(h_cnt.data(), p->d_nacc, sizeof(int) * (size_t)p->S, hipMemcpyDeviceToHost, st);
+    if (q == hipSuccess) q = hipMemcpyAsync(h_cnt.data() + p->S, p->d_nrej, sizeof(int) * (size_t)p->S, hipMemcpyDeviceToHost, st);
+    if (q != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: step counters", q);
+    pending_out = host_out; pending_S = p->S;
+    return LTO_OK;
+  };
+  auto counts_land = [&]() {
+    for (long i = 0; pending_out && i < pending_S; ++i) pending_out[i] = h_cnt[(size_t)i] + h_cnt[(size_t)(pending_S + i)];
+    pending_out = nullptr;
+  };
+  const double* d_xc = d_x0;
+  const double* d_tc = d_t0;
+  long Jc = J0;
+  int nc = n0, ntgc = n_tgrids;
+  for (int pass = 0; pass < passes; ++pass) {
+    call.idle = false;
+    rc = plan_build(c, 12, nc, B, prm, n_prm, integ, &call.plan[0]);
+    if (rc) return rc;
+    lto_indirect_plan* p = call.plan[0];
+    const bool swept = adaptive && (!weights || (pass == 0 && steps_before));
+    if (swept) rc = count_sweep(p, d_xc, Jc, d_tc, ntgc, pass == 0 ? steps_before : nullptr);
+    if (rc) return rc;
+    RemeshGridArgs ga;
+    ga.t = d_tc; ga.t_stride = ntgc == 1 ? 0 : nc; ga.n = nc; ga.n_new = nn; ga.n_batch = B;
+    ga.w = weights ? d_w : nullptr; ga.nacc = p->d_nacc; ga.nrej = p->d_nrej;
+    ga.C = c_stride ? d_c : nullptr; ga.c_stride = (long)c_stride;
+    ga.t_out = d_tn[pass & 1]; ga.seg_of = d_seg;
+    e = launch_remesh_grid(ga, st);
+    if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_remesh_grid", e);
+    IndirectArgs a;
+    rc = fill_indirect_args(p, d_xc, Jc, d_tc, ntgc, &a);
+    if (rc) return rc;
+    RemeshNodeArgs na;
+    na.tn = d_tn[pass & 1]; na.seg_of = d_seg; na.G = d_g[pass & 1]; na.ldg = Jn; na.n_new = nn; na.n_batch = B;
+    e = launch_remesh_nodes(p->pm, p->integ.method, a, na, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(t_out, d_tn[pass & 1], sizeof(double) * Jn, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = call.wait();
+    if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: re-mesh", e);
+    counts_land();
+    plan_free(p);                                            // (the stream is idle)
+    call.plan[0] = nullptr;
+    if (!increasing(t_out, nn, B))
+      return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: the new grid is not strictly increasing (n_new beyond the grid's resolution, or a NaN trajectory)");
+    d_xc = d_g[pass & 1]; d_tc = d_tn[pass & 1]; Jc = Jn; nc = nn; ntgc = B;
+  }
+  if (steps_before && !adaptive) for (long i = 0; i < S0; ++i) steps_before[i] = integ->steps;
+  if (XC_guess) {
+    call.idle = false;
+    e = launch_unpack_soa(d_xc, Jn, 12, Jn, d_xa, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(XC_guess, d_xa, sizeof(double) * 12 * Jn, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = call.wait();
+    if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: guess", e);
+  }
+  if (XC_out) {
+    rc = indirect_solve_impl(c, 12, nn, B, nullptr, d_xc, t_out, B, prm, n_prm, integ, flag_adjointsOnly, maxIter, XC_out,
+                             want_final ? d_xf : nullptr, defect, status_flag, iterations, history);
+    if (rc) return rc;
+  }
+  if (!steps_after) return LTO_OK;
+  if (!adaptive) {
+    for (long i = 0; i < Sn; ++i) steps_after[i] = integ->steps;
+    return LTO_OK;
+  }
+  call.idle = false;
+  rc = plan_build(c, 12, nn, B, prm, n_prm, integ, &call.plan[0]);
+  if (rc == LTO_OK) rc = count_sweep(call.plan[0], XC_out ? d_xf : d_xc, Jn, d_tc, B, steps_after);
+  if (rc) return rc;
+  e = call.wait();
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: step counters", e);
+  counts_land();
+  return LTO_OK;
+}
+
+int lto_indirect_remesh(lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                        const lto_integrator* integ, int n_new, const double* weights, int passes, int flag_adjointsOnly, int maxIter,
+                        double* t_out, double* XC_guess, double* XC_out, double* defect, int* status_flag, int* iterations,
+                        double* history, int* steps_before, int* steps_after) {
+  return lto_indirect_remesh_batch(c, ndim, n_nodes, 1, XC, t, 1, prm, 1, integ, n_new, weights, passes, flag_adjointsOnly, maxIter,
+                                   t_out, XC_guess, XC_out, defect, status_flag, iterations, history, steps_before, steps_after);
+}
+
 static bool direct_targets_expand(const lto_direct_targets* targets, int n_targets, int B, lto::HostBuf<lto_direct_targets>& out) {
   if (!out.alloc((size_t)B)) return false;
   for (int b = 0; b < B; ++b) out[(size_t)b] = targets[n_targets == 1 ? 0 : b];

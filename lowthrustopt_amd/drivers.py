@@ -880,6 +880,33 @@ def tf_sweep(XC_all, t_TU, Δts, MU, DU, TU, mass, thrustLimit, p, rho, Xf_times
             "iterations": r.iterations, "max_defect": np.abs(r.defect).max(axis=(0, 1)), "cost": r.cost}
 
 
+def meshRefine_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass, thrustLimit, p, rho, n_new=None, passes=2, weights=None, maxIter=10,
+                        flag_adjointsOnly=False, integ=None, ctx=None, verbose=True):
+    """Mesh re-distribution of a converged 12-row indirect solution, the counterpart of meshRefine_direct: the nodes
+    are moved -- and their number changed to n_new (default: n_nodes) -- so that every segment takes the same share of the
+    integrator's trial steps (or of the caller's per-segment weights), the new nodes are taken from the solution's own piecewise
+    trajectory, and the fixed-end indirect loop re-solves on the new grid.  One library call (lto_indirect_remesh_batch).
+    Returns (XC_new, t_new, n_new) on status 0, otherwise the original (XC_all, t_TU, n_nodes) unchanged -- the convention of
+    addTimeFinal."""
+    XC_all = np.array(XC_all, dtype=np.float64, order="F")
+    t_TU = np.array(t_TU, dtype=np.float64)
+    if XC_all.shape != (12, int(n_nodes)):
+        raise ValueError("meshRefine_indirect takes the 12-row solution [12 x n_nodes]; got shape %s" % (XC_all.shape,))
+    if t_TU.shape != (int(n_nodes),):
+        raise ValueError("meshRefine_indirect takes one time per node; got shape %s" % (t_TU.shape,))
+    n_new = int(n_nodes) if n_new is None else int(n_new)
+    params = hotpath.make_params(MU, DU, TU, thrustLimit, mass, 1.0, p, rho)
+    r = hotpath.indirect_remesh(XC_all, t_TU, params, n_new=n_new, weights=weights, passes=passes, integ=integ,
+                                flag_adjointsOnly=flag_adjointsOnly, maxIter=maxIter, ctx=ctx)
+    if verbose:
+        print("meshRefine_indirect: %d -> %d nodes, max trial steps %d -> %d (mean %.2f -> %.2f), status %d after %d iterations"
+              % (n_nodes, n_new, r.steps_before.max(), r.steps_after.max(), r.steps_before.mean(), r.steps_after.mean(), r.status,
+                 r.iterations))
+    if r.status == 0:
+        return r.XC_out.copy(), r.t_out.copy(), n_new
+    return XC_all, t_TU, int(n_nodes)
+
+
 def meshRefine_direct(X_all, u_all, t_TU, nstate, n_nodes, nsteps, Isp, MU, DU, TU, tol_min=1e-20, tol_max=1e-18,
                       max_nodes=1 << 20, batched=True, ops=None, verbose=True):
     """Errors-driven mesh refinement of the direct transcription (direct.jl:597-680): nodes are removed while the

@@ -869,6 +869,66 @@ def indirect_add_time(XC, t, params, Xf_times, Xf_states, dts, n_desired=200, in
     return AddTime(guess, XC_out, t_out, tau, defect, status, iters, history, cost)
 
 
+Remesh = collections.namedtuple("Remesh", "XC_guess XC_out t_out defect status iterations history steps_before steps_after")
+
+
+def indirect_remesh(XC, t, params, n_new=None, weights=None, passes=2, integ=None, flag_adjointsOnly=False, maxIter=10, ctx=None,
+                    solve=True):
+    """Mesh re-distribution of converged 12-dim solutions (lto_indirect_remesh_batch): XC [12 x n] or [12 x n x B] on
+    t [n] or [n x B] is put on n_new nodes (default n) placed so that every new segment carries the same share of a per-segment
+    monitor -- weights [(n-1)] / [(n-1) x B] (then passes must be 1), or, with weights = None, the trial-step counts of a defect
+    sweep with integ (adaptive integrators only), `passes` times over.  The new nodes lie on the input's own piecewise trajectory
+    (XC_guess); with solve = True the Newton loop of indirect_solve_batch then runs on the new grids.  Returns Remesh(XC_guess
+    [12 x n_new x B], XC_out, t_out [n_new x B], defect [12 x (n_new-1) x B], status [B], iterations [B], history, steps_before
+    [(n-1) x B], steps_after [(n_new-1) x B]); a single trajectory comes back without the batch axis, the solve's fields are None
+    when solve = False."""
+    X = _f64(XC)
+    ndim, n, B, batched = _batch_dims(X)
+    tt, ntg = _tgrids(t, n, B)
+    n_new = n if n_new is None else int(n_new)
+    passes = int(passes)
+    if n_new < 2:
+        raise LtoError(-1, "indirect_remesh: n_new must be >= 2")
+    if passes < 1:
+        raise LtoError(-1, "indirect_remesh: passes must be >= 1")
+    w = None
+    if weights is not None:
+        if passes != 1:
+            raise LtoError(-1, "indirect_remesh: caller weights are applied once: passes must be 1")
+        w = _f64(weights)
+        if w.shape != ((n - 1,) if not batched else (n - 1, B)):
+            raise ValueError("weights must be [n_nodes - 1] or [(n_nodes - 1) x n_batch], one per old segment")
+        if not np.all(np.isfinite(w)) or not np.all(w > 0.0):
+            raise LtoError(-1, "indirect_remesh: every weight must be finite and > 0")
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    prm, nprm = _params_array(params)
+    guess = np.zeros((ndim, n_new, B), order="F")
+    t_out = np.zeros((n_new, B), order="F")
+    before = np.zeros((n - 1, B), dtype=np.int32, order="F")
+    after = np.zeros((n_new - 1, B), dtype=np.int32, order="F")
+    XC_out = defect = status = iters = hist = None
+    if solve:
+        XC_out = np.zeros((ndim, n_new, B), order="F")
+        defect = np.zeros((ndim, n_new - 1, B), order="F")
+        status = np.zeros(B, dtype=np.int32)
+        iters = np.zeros(B, dtype=np.int32)
+        hist = np.full((2, max(int(maxIter), 1), B), np.nan, order="F")
+    ctx.check(ctx.fn("indirect_remesh_batch")(
+        ctx.handle, ndim, n, B, _ptr(X), _ptr(tt), ntg, prm, nprm, C.byref(integ), n_new, _ptr(w) if w is not None else None, passes,
+        1 if flag_adjointsOnly else 0, int(maxIter), _ptr(t_out), _ptr(guess), _ptr(XC_out) if solve else None,
+        _ptr(defect) if solve else None, _ptr(status) if solve else None, _ptr(iters) if solve else None,
+        _ptr(hist) if solve and maxIter > 0 else None, _ptr(before), _ptr(after)))
+    history = None
+    if solve:
+        history = [hist[:, ~np.isnan(hist[1, :, b]), b].T.copy() for b in range(B)]
+    if not batched:
+        one = lambda a: None if a is None else a[..., 0]   # noqa: E731
+        return Remesh(one(guess), one(XC_out), one(t_out), one(defect), None if status is None else int(status[0]),
+                      None if iters is None else int(iters[0]), None if history is None else history[0], one(before), one(after))
+    return Remesh(guess, XC_out, t_out, defect, status, iters, history, before, after)
+
+
 def direct_qp_step_free(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, models, beta, allowImpulsive=False, ctx=None):
     """One Jacobian sweep and one FREE-END QP step (flagEnd = true, lto_direct_qp_step_free): targets (lto_direct_targets, s0 and
     sf the end states at the current tau), models (lto_direct_end_model) and beta: one, or one per trajectory.  Returns
