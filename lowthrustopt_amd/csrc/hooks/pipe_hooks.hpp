@@ -16,8 +16,10 @@ constexpr bool kProbeBuild = false;
 struct BarrierWait {
   __device__ __forceinline__ void sync() { __syncthreads(); }
   __device__ __forceinline__ int sync_or(const int pred) { return __syncthreads_or(pred); }
+  __device__ __forceinline__ void stamp(int) {}       // probe build: ticks since the last barrier, at three points of the epilogue
+  __device__ __forceinline__ void drained() {}        // probe build: waits for the wave's global stores, then the third stamp
   __device__ __forceinline__ void report(double*, long, int, long) const {}          // (rows, ld, row, column)
-  __device__ __forceinline__ void report_edges(double*, long, int, long) const {}    // (rows, ld, first of four rows, column)
+  __device__ __forceinline__ void report_edges(double*, long, int, long) const {}    // (rows, ld, first of seven rows, column)
 };
 // ticks (s_memtime) and 100 MHz ticks of a region
 struct RegionClock {

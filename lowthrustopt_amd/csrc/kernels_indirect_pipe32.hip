@@ -21,6 +21,7 @@
 namespace lto {
 
 constexpr int P32_SEG = 32;
+constexpr int P32_WAVES = 12;   // all resident to the end: after the last step barrier they share the row stores of Phi (pipe_store_phi)
 
 template <int ND, int PM> struct Pipe32 {
   using Arg = PipeArg<ND, PM>;
@@ -55,7 +56,7 @@ __device__ __forceinline__ double q32_other_body(const double x) { return q32_fr
 
 template <int ND, int PM>
 __device__ __forceinline__ void pipe32_role_base(const IndirectArgs& a, const PipeLane& L, const int seg, const int q,
-                                                 double* s_int) {
+                                                 double* s_int, const double* s_coef, const int wave) {
   using P = Pipe32<ND, PM>;
   static_assert(ND == 12 || P::LM_OFF, "lambda_m on the chain: the stages do not pair");
   constexpr int NB = P::NB;
@@ -193,15 +194,20 @@ __device__ __forceinline__ void pipe32_role_base(const IndirectArgs& a, const Pi
     }
     __syncthreads();
   }
+  // (the node index passes through an empty asm, as in kernels_indirect_pipe48.hip: the compiler otherwise forms the address of
+  // x_{i+1} next to that of x_i before the loop and carries it through -- a spilled pair in a role that runs at 168 registers)
+  long node_e = L.node;
+  asm volatile("" : "+v"(node_e));
   if (L.in_range && q == 0) {
     if (a.defect) {
 #pragma unroll
-      for (int c = 0; c < NB; ++c) a.defect[c * a.ldd + L.s] = y[c] - a.X[c * a.ldx + L.node + 1];
+      for (int c = 0; c < NB; ++c) a.defect[c * a.ldd + L.s] = y[c] - a.X[c * a.ldx + node_e + 1];
     }
     if (a.errors) a.errors[L.s] = 0.0;
     if (a.nacc) a.nacc[L.s] = steps;
     if (a.nrej) a.nrej[L.s] = 0;
   }
+  pipe_store_phi<ND, P32_SEG, P32_WAVES>(a, s_coef, wave);
 }
 
 
@@ -210,7 +216,7 @@ __device__ __forceinline__ void pipe32_role_base(const IndirectArgs& a, const Pi
 // system it also accumulates lambda_m (see kernels_indirect_pipe8.hip) and writes that row of the defect.
 template <int ND, int PM>
 __device__ __forceinline__ void pipe32_role_coef(const IndirectArgs& a, const PipeLane& L, const int seg, const int stage,
-                                                 const double* s_int, double* s_coef, double* s_lm) {
+                                                 const double* s_int, double* s_coef, double* s_lm, const int wave) {
   using P = Pipe32<ND, PM>;
   using Coef = typename PipeCoef<ND>::type;
   constexpr int NI = P::NI, NC = P::NC, SD = P::SD;
@@ -251,12 +257,13 @@ __device__ __forceinline__ void pipe32_role_coef(const IndirectArgs& a, const Pi
       a.defect[(ND - 1) * a.ldd + L.s] = (a.X[r] + sum) - a.X[r + 1];
     }
   }
+  pipe_store_phi<ND, P32_SEG, P32_WAVES>(a, s_coef, wave);
 }
 
 // --------------------------------------------------------------------------------------------------- column role
 template <int ND, int PM>
 __device__ __forceinline__ void pipe32_role_columns(const IndirectArgs& a, const PipeLane& L, const int seg, const int col,
-                                                    const double* s_coef) {
+                                                    double* s_coef, const int wave) {
   using P = Pipe32<ND, PM>;
   constexpr int SD = P::SD, NA = P::NA;
   const int steps = a.steps;
@@ -269,12 +276,13 @@ __device__ __forceinline__ void pipe32_role_columns(const IndirectArgs& a, const
     if (p >= 2 && col < NA) col_dpp_step<ND, SD, P::Arg::LM, NA>(rec + ((p & 1) * 4) * SD, k, p - 2, y);   // spare lanes stay off: never DPP sources
     __syncthreads();
   }
-  if (L.in_range && col < ND) {
-    const double sc = (col < NA) ? a.stm_scale : 1.0;
-    const double poison = (col < NA) ? 0.0 : L.h - L.h;     // a unit column of a segment with a NaN (or infinite) span is NaN like the rest
+  // the coefficient ring is dead: it takes the Phi tile, and all twelve waves store whole rows (pipe_common.hpp)
+  const double sc = (col < NA) ? a.stm_scale : 1.0;
+  const double poison = (col < NA) ? 0.0 : L.h - L.h;     // a unit column of a segment with a NaN (or infinite) span is NaN like the rest
+  double v[ND];
 #pragma unroll
-    for (int r = 0; r < ND; ++r) a.Phi[(long)(col * ND + r) * a.ldp + L.s] = __builtin_fma(y[r], sc, poison);
-  }
+  for (int r = 0; r < ND; ++r) v[r] = __builtin_fma(y[r], sc, poison);
+  pipe_store_phi<ND, P32_SEG, P32_WAVES>(a, s_coef, wave, true, L, seg, col, v);
 }
 
 template <int ND, int PM>
@@ -289,9 +297,9 @@ __global__ __launch_bounds__(768) void k_indirect_pipe32(const IndirectArgs a) {
   const PipeLane L = pipe_lane<PM, P32_SEG>(a, seg);
   if (!__syncthreads_or(L.mine)) return;         // workgroup-uniform
   // the two roles with the long dependent streams issue first (three wavefronts share a SIMD and all meet at one barrier per step)
-  if (wave < 2) { __builtin_amdgcn_s_setprio(3); pipe32_role_base<ND, PM>(a, L, seg, lane & 3, s_int); }
-  else if (wave < 4) { __builtin_amdgcn_s_setprio(2); pipe32_role_coef<ND, PM>(a, L, seg, lane >> 4, s_int, s_coef, s_lm); }
-  else pipe32_role_columns<ND, PM>(a, L, seg, lane & 15, s_coef);
+  if (wave < 2) { __builtin_amdgcn_s_setprio(3); pipe32_role_base<ND, PM>(a, L, seg, lane & 3, s_int, s_coef, wave); }
+  else if (wave < 4) { __builtin_amdgcn_s_setprio(2); pipe32_role_coef<ND, PM>(a, L, seg, lane >> 4, s_int, s_coef, s_lm, wave); }
+  else pipe32_role_columns<ND, PM>(a, L, seg, lane & 15, s_coef, wave);
 }
 
 template <int ND, int PM>

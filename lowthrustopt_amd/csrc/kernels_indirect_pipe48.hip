@@ -37,10 +37,15 @@ template <int ND, int PM, int SEG_> struct Pipe48 {
   static constexpr int COEF_DOUBLES = 2 * 4 * SD;                  // [step parity][stage][segment record]
   static constexpr bool PARK = (ND == 14) || (PM == PM_PGEN);      // base role with the step's base point and RK4 sum in LDS
   static constexpr int PARK_DOUBLES = PARK ? 2 * ND * SEG : 1;
+  // waves resident to the end (SEG = 44: wave 12 leaves at once); after the last step barrier they share the row stores of Phi, in the
+  // order of their index (pipe_store_phi: the tile takes the place of the dead coefficient ring)
+  static constexpr int STORE_WAVES = (SEG == 44) ? 15 : 16;
+  static_assert(PhiTile<ND, SEG>::DOUBLES <= COEF_DOUBLES, "the Phi tile lives in the coefficient ring");
 };
 
 template <int ND, int PM, int SEG>
-__device__ __forceinline__ void pipe48_role_base(const IndirectArgs& a, const PipeLane& L, const int seg, const bool live, double* s_int) {
+__device__ __forceinline__ void pipe48_role_base(const IndirectArgs& a, const PipeLane& L, const int seg, const bool live, double* s_int,
+                                                 const double* s_coef) {
   using P = Pipe48<ND, PM, SEG>;
   constexpr int NI = P::NI, P48_SEG = P::SEG;
   const int steps = a.steps;
@@ -91,8 +96,10 @@ __device__ __forceinline__ void pipe48_role_base(const IndirectArgs& a, const Pi
     // store before the loop, a load behind it) but formed again from the segment index, which is pinned so that the division
     // cannot be hoisted in front of the loop.
     asm volatile("" : "+v"(s_e));
-    const int traj_e = s_e / a.seg_per_traj;
-    node_e = (long)traj_e * a.n_nodes + (s_e - traj_e * a.seg_per_traj);
+    int spt_e = a.seg_per_traj;      // ... and the divisor with it: its reciprocal was formed in front of the loop for pipe_lane and kept for here
+    asm volatile("" : "+s"(spt_e));
+    const int traj_e = s_e / spt_e;
+    node_e = (long)traj_e * a.n_nodes + (s_e - traj_e * spt_e);
   }
   if (L.in_range && live) {
     if (a.defect) {
@@ -103,6 +110,7 @@ __device__ __forceinline__ void pipe48_role_base(const IndirectArgs& a, const Pi
     if (a.nacc) a.nacc[s_e] = steps;
     if (a.nrej) a.nrej[s_e] = 0;
   }
+  pipe_store_phi<ND, SEG, P::STORE_WAVES>(a, s_coef, 0);
 }
 
 // Base role for the instantiations whose four RK4 arrays do not fit: y, k, the stage argument and the RK4 sum are 4 x ND doubles --
@@ -113,7 +121,7 @@ __device__ __forceinline__ void pipe48_role_base(const IndirectArgs& a, const Pi
 // operations per step on the base wave, no scratch.  Same operations in the same order as pipe48_role_base: same bits.
 template <int ND, int PM, int SEG>
 __device__ __forceinline__ void pipe48_role_base_parked(const IndirectArgs& a, const PipeLane& L, const int seg, const bool live,
-                                                        double* s_int, double* s_park) {
+                                                        double* s_int, double* s_park, const double* s_coef) {
   using P = Pipe48<ND, PM, SEG>;
   constexpr int NI = P::NI, P48_SEG = P::SEG;
   const int steps = a.steps;
@@ -162,22 +170,25 @@ __device__ __forceinline__ void pipe48_role_base_parked(const IndirectArgs& a, c
     }
     __syncthreads();
   }
+  long node_e = L.node;              // (pinned as in pipe48_role_base: the addresses of x_{i+1} are formed here, not in front of the loop)
+  asm volatile("" : "+v"(node_e));
   if (L.in_range && live) {
     if (a.defect) {
 #pragma unroll
-      for (int c = 0; c < ND; ++c) a.defect[c * a.ldd + L.s] = y[c] - a.X[c * a.ldx + L.node + 1];
+      for (int c = 0; c < ND; ++c) a.defect[c * a.ldd + L.s] = y[c] - a.X[c * a.ldx + node_e + 1];
     }
     if (a.errors) a.errors[L.s] = 0.0;
     if (a.nacc) a.nacc[L.s] = steps;
     if (a.nrej) a.nrej[L.s] = 0;
   }
+  pipe_store_phi<ND, SEG, P::STORE_WAVES>(a, s_coef, 0);
 }
 
 // lane = (segment, RK stage): the four stages of step p - 1 are built side by side in phase p; every coefficient except the
 // unit vector lhat (entries 14..16) is stored times the stage's RK4 argument weight (h/2, h/2, h, h/2: col_dpp_step).
 template <int ND, int PM, int SEG>
 __device__ __forceinline__ void pipe48_role_coef(const IndirectArgs& a, const PipeLane& L, const int seg, const int stage,
-                                                 const double* s_int, double* s_coef) {
+                                                 const double* s_int, double* s_coef, const int rank) {
   using P = Pipe48<ND, PM, SEG>;
   using Coef = typename PipeCoef<ND>::type;
   constexpr int NI = P::NI, NC = P::NC, P48_SEG = P::SEG;
@@ -202,12 +213,13 @@ __device__ __forceinline__ void pipe48_role_coef(const IndirectArgs& a, const Pi
     }
     __syncthreads();
   }
+  pipe_store_phi<ND, SEG, P::STORE_WAVES>(a, s_coef, rank);
 }
 
 // lane = (row = segment, column); one RK4 step = col_dpp_step
-template <int ND, int SEG>
+template <int ND, int SEG, int NW>
 __device__ __forceinline__ void pipe48_role_columns(const IndirectArgs& a, const PipeLane& L, const int seg, const int col,
-                                                    const double* s_coef) {
+                                                    double* s_coef, const int rank) {
   constexpr int SD = SEG * CoefBySegment::LD;
   const int steps = a.steps;
   const ColStepConst k(L.h, L.w2);
@@ -219,10 +231,10 @@ __device__ __forceinline__ void pipe48_role_columns(const IndirectArgs& a, const
       col_dpp_step<ND, SD>(s_coef + ((p & 1) * 4) * SD + CoefBySegment::lane_base(col, seg), k, p - 2, y);
     __syncthreads();
   }
-  if (L.in_range && col < ND) {
+  double v[ND];
 #pragma unroll
-    for (int r = 0; r < ND; ++r) a.Phi[(long)(col * ND + r) * a.ldp + L.s] = y[r] * a.stm_scale;
-  }
+  for (int r = 0; r < ND; ++r) v[r] = y[r] * a.stm_scale;
+  pipe_store_phi<ND, SEG, NW>(a, s_coef, rank, true, L, seg, col, v);
 }
 
 template <int ND, int PM, int SEG>
@@ -246,13 +258,14 @@ __global__ __launch_bounds__(1024) void k_indirect_pipe48(const IndirectArgs a) 
   // Every wave shares its SIMD with three others and all meet at one barrier per step: the two roles with the long dependent
   // streams and the fewest instructions (base 565, coefficients ~400 per step) issue first, or the step would last four times
   // the base wave's stream.
+  const int rank = (DROP12 && wave > 12) ? wave - 1 : wave;    // among the waves that stay to the end
   if (wave == 0) {
     __builtin_amdgcn_s_setprio(3);
-    if constexpr (P::PARK) pipe48_role_base_parked<ND, PM, SEG>(a, L, seg, lane < SEG, s_int, s_park);
-    else pipe48_role_base<ND, PM, SEG>(a, L, seg, lane < SEG, s_int);
+    if constexpr (P::PARK) pipe48_role_base_parked<ND, PM, SEG>(a, L, seg, lane < SEG, s_int, s_park, s_coef);
+    else pipe48_role_base<ND, PM, SEG>(a, L, seg, lane < SEG, s_int, s_coef);
   }
-  else if (wave < 4) { __builtin_amdgcn_s_setprio(2); pipe48_role_coef<ND, PM, SEG>(a, L, seg, lane >> 4, s_int, s_coef); }
-  else pipe48_role_columns<ND, SEG>(a, L, seg, lane & 15, s_coef);
+  else if (wave < 4) { __builtin_amdgcn_s_setprio(2); pipe48_role_coef<ND, PM, SEG>(a, L, seg, lane >> 4, s_int, s_coef, rank); }
+  else pipe48_role_columns<ND, SEG, P::STORE_WAVES>(a, L, seg, lane & 15, s_coef, rank);
 }
 
 template <int ND, int PM, int SEG>

@@ -42,7 +42,8 @@
 //
 // Edges (probe build, tools/probe_pipe8_edges.py; ticks at the contract size, 14-dim): the fill phase is ~5 000 (base steps 0, 1;
 // the column waves wait), the drain phase ~4 500 (the column waves' last two steps; base and coefficient waves wait), and after
-// the last barrier each wave stores its outputs.  The base wave loads the end node its defect needs (X at node + 1) during the drain
+// the last barrier the base and coefficient waves store the defect, the column waves put Phi into a tile in the dead coefficient ring,
+// and after one more barrier all seven waves store it as whole rows (pipe_common.hpp, pipe_store_phi).  The base wave loads the end node its defect needs (X at node + 1) during the drain
 // phase, before the last barrier: loaded after it, that load made the base wave's epilogue (~7 800 ticks) the workgroup's longest.
 //
 // For the always-thrust-limited control laws (p = 0, p = 1) of the 14-dim system nothing depends on lambda_m: the base
@@ -54,6 +55,12 @@
 namespace lto {
 
 constexpr int P8_SPIN_LIMIT = 1 << 22;   // polls before a waiting wave gives up (never hangs)
+
+// After the last phase barrier: the coefficient ring is dead and takes the Phi tile (pipe_common.hpp, pipe_store_phi).  Seven
+// waves are resident (w6 has left), the same seven the phase barriers count; they share the row stores in the order of their index.
+constexpr int P8_STORE_WAVES = 7;
+constexpr int P8_BASE_RANK = 2, P8_COEF_RANK = 3;
+__device__ __forceinline__ int p8_store_rank(const int wave) { return wave < 6 ? wave : 6; }
 
 // Probe hooks (pipe_hooks.hpp: no-ops in the product build): ticks each wave waits at the phase barriers -> row 16 of the probe
 // script's defect buffer, column 16 block + wave.
@@ -120,7 +127,7 @@ __device__ __forceinline__ void p8_signal(int* flag, const int value) {
 // LDS stores per step on the chain cost more (S = 29: 79 -> 84 us).
 template <int ND, int PM>
 __device__ __forceinline__ void pipe8_role_base(const IndirectArgs& a, const PipeLane& L, const int seg, const int slot,
-                                                double* s_int, Pipe8Flags* fl) {
+                                                double* s_int, const double* s_coef, Pipe8Flags* fl) {
   using P = Pipe8<ND, PM>;
   constexpr int NI = P::NI, NB = P::NB;
   const int steps = a.steps, npairs = (steps + 1) >> 1;
@@ -190,6 +197,7 @@ __device__ __forceinline__ void pipe8_role_base(const IndirectArgs& a, const Pip
     if (a.nrej) a.nrej[L.s] = 0;
     if (seg == 0) loop_clock.report(a.defect, a.ldd, 17, 18, L.s);     // probe build: ticks of the phase loop, per workgroup
   }
+  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8_BASE_RANK);
   P8_EDGES_REPORT(a);
 }
 
@@ -226,7 +234,7 @@ __device__ __forceinline__ double other_body(const double x) { return quad_from<
 
 template <int ND, int PM>
 __device__ __forceinline__ void pipe8_role_base_paired(const IndirectArgs& a, const PipeLane& L, const int seg, const int q,
-                                                       double* s_int, Pipe8Flags* fl) {
+                                                       double* s_int, const double* s_coef, Pipe8Flags* fl) {
   using P = Pipe8<ND, PM>;
   static_assert(ND == 12 || P::LM_OFF, "lambda_m on the chain: the stages do not pair");
   constexpr int NB = P::NB;
@@ -386,6 +394,7 @@ __device__ __forceinline__ void pipe8_role_base_paired(const IndirectArgs& a, co
     if (a.nrej) a.nrej[L.s] = 0;
     if (seg == 0) loop_clock.report(a.defect, a.ldd, 17, 18, L.s);     // probe build: ticks of the step loop, per workgroup
   }
+  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8_BASE_RANK);
   P8_EDGES_REPORT(a);
 }
 
@@ -450,26 +459,30 @@ __device__ __forceinline__ void pipe8_role_coef(const IndirectArgs& a, const Pip
       a.defect[(ND - 1) * a.ldd + L.s] = fl->fail ? __builtin_nan("") : (a.X[r] + sum) - a.X[r + 1];
     }
   }
+  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8_COEF_RANK);
   P8_EDGES_REPORT(a);
 }
 
-// STM column `col` of the lane's segment to global memory: y carries 3^k Phi (stm_scale undoes it); columns the row does
-// not integrate (col >= NA) are unit vectors.
-template <int ND, int NA>
-__device__ __forceinline__ void pipe8_store_column(const IndirectArgs& a, const PipeLane& L, const int col, const double (&y)[ND],
-                                                   const bool fail) {
-  if (L.in_range && col < ND) {
-    const double sc = (col < NA) ? a.stm_scale : 1.0;
-    const double poison = (col < NA) ? 0.0 : L.h - L.h;     // a unit column of a segment with a NaN (or infinite) span is NaN like the rest
+// STM column `col` of the lane's segment through the tile to global memory: y carries 3^k Phi (stm_scale undoes it); columns the
+// row does not integrate (col >= NA) are unit vectors.
+template <int ND, int NA, class Wait>
+__device__ __forceinline__ void pipe8_store_column(const IndirectArgs& a, const PipeLane& L, const int seg, const int col, const double (&y)[ND],
+                                                   const bool fail, double* s_coef, const int wave, Wait& w) {
+  const double sc = (col < NA) ? a.stm_scale : 1.0;
+  const double poison = (col < NA) ? 0.0 : L.h - L.h;     // a unit column of a segment with a NaN (or infinite) span is NaN like the rest
+  double v[ND];
 #pragma unroll
-    for (int r = 0; r < ND; ++r) a.Phi[(long)(col * ND + r) * a.ldp + L.s] = fail ? __builtin_nan("") : __builtin_fma(y[r], sc, poison);
-  }
+  for (int r = 0; r < ND; ++r) v[r] = fail ? __builtin_nan("") : __builtin_fma(y[r], sc, poison);
+  w.stamp(0);
+  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, p8_store_rank(wave), true, L, seg, col, v);
+  w.stamp(1);
+  w.drained();
 }
 
 // ------------------------------------------------------------------------------ column role, both steps of every phase
 template <int ND, int PM>
 __device__ __forceinline__ void pipe8_role_columns(const IndirectArgs& a, const PipeLane& L, const int seg, const int col,
-                                                   const double* s_coef, Pipe8Flags* fl, const int probe_bit) {
+                                                   double* s_coef, Pipe8Flags* fl, const int wave) {
   using P = Pipe8<ND, PM>;
   constexpr int SD = P::SD;
   const int steps = a.steps, npairs = (steps + 1) >> 1;
@@ -480,7 +493,7 @@ __device__ __forceinline__ void pipe8_role_columns(const IndirectArgs& a, const 
   for (int r = 0; r < ND; ++r) y[r] = (r == col) ? 1.0 : 0.0;
   P8_WAIT_DECL;
   for (int p = 0; p < npairs + 1; ++p) {
-    if (p >= 1 && PIPE_ROLE_ON(a, 4) && PIPE_ROLE_ON(a, probe_bit)) {
+    if (p >= 1 && PIPE_ROLE_ON(a, 4) && PIPE_ROLE_ON(a, wave == 7 ? 64 : 8)) {      // probe build: role switches per wave
       const int s0 = 2 * p - 2, s1 = 2 * p - 1;
       if (col < P::NA) col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rec + ((s0 & 3) * 4) * SD, k, s0, y);   // spare lanes stay off: never DPP sources
       if (s1 < steps) {
@@ -491,17 +504,18 @@ __device__ __forceinline__ void pipe8_role_columns(const IndirectArgs& a, const 
     P8_SYNC();
   }
   P8_WAIT_REPORT(a);
-  pipe8_store_column<ND, P::NA>(a, L, col, y, fl->fail != 0);
+  pipe8_store_column<ND, P::NA>(a, L, seg, col, y, fl->fail != 0, s_coef, wave, p8_wait);
   P8_EDGES_REPORT(a);
 }
 
 // --------------------------------------------------------------- column role of the alternating job (segments 12..15)
 // ODD = false (w4): step 2p - 2 in phase p, then state -> s_hand, hand = p.  ODD = true (w5): waits for the coefficients
 // of step 2p - 1 and for hand >= p, state <- s_hand, step 2p - 1, state -> s_hand.  The barrier at the end of the phase
-// orders w5's stores before w4's loads of the next phase.  After the last phase w4 stores the STM columns from s_hand.
+// orders w5's stores before w4's loads of the next phase.  After the last phase w4 takes the state from s_hand once more and puts
+// its columns into the Phi tile; w5 only joins the row stores.
 template <int ND, int PM, bool ODD>
 __device__ __forceinline__ void pipe8_role_columns_alt(const IndirectArgs& a, const PipeLane& L, const int seg, const int col,
-                                                       const double* s_coef, double* s_hand, Pipe8Flags* fl) {
+                                                       double* s_coef, double* s_hand, Pipe8Flags* fl) {
   using P = Pipe8<ND, PM>;
   constexpr int SD = P::SD;
   const int steps = a.steps, npairs = (steps + 1) >> 1;
@@ -552,7 +566,12 @@ __device__ __forceinline__ void pipe8_role_columns_alt(const IndirectArgs& a, co
   P8_WAIT_REPORT(a);
   if (!ODD) {
     load();
-    pipe8_store_column<ND, P::NA>(a, L, col, y, fl->fail != 0);
+    pipe8_store_column<ND, P::NA>(a, L, seg, col, y, fl->fail != 0, s_coef, 4, p8_wait);
+  } else {
+    p8_wait.stamp(0);
+    pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, p8_store_rank(5));
+    p8_wait.stamp(1);
+    p8_wait.drained();
   }
   P8_EDGES_REPORT(a);
 }
@@ -578,13 +597,13 @@ __global__ __launch_bounds__(512) void k_indirect_pipe8(const IndirectArgs a) {
   if (!__syncthreads_or(L.mine)) return;         // workgroup-uniform
   if (wave == 6) return;                         // shares the base wave's SIMD: leaves before the first phase barrier
   if (wave == 2) {
-    if constexpr (PAIRED) pipe8_role_base_paired<ND, PM>(a, L, seg, lane & 3, s_int, &s_fl);
-    else pipe8_role_base<ND, PM>(a, L, seg, lane >> 4, s_int, &s_fl);
+    if constexpr (PAIRED) pipe8_role_base_paired<ND, PM>(a, L, seg, lane & 3, s_int, s_coef, &s_fl);
+    else pipe8_role_base<ND, PM>(a, L, seg, lane >> 4, s_int, s_coef, &s_fl);
   }
   else if (wave == 3) pipe8_role_coef<ND, PM>(a, L, seg, lane >> 4, s_int, s_coef, s_lm, &s_fl);
   else if (wave == 4) pipe8_role_columns_alt<ND, PM, false>(a, L, seg, lane & 15, s_coef, s_hand, &s_fl);
   else if (wave == 5) pipe8_role_columns_alt<ND, PM, true>(a, L, seg, lane & 15, s_coef, s_hand, &s_fl);
-  else pipe8_role_columns<ND, PM>(a, L, seg, lane & 15, s_coef, &s_fl, wave == 7 ? 64 : 8);   // probe build: role switches per wave
+  else pipe8_role_columns<ND, PM>(a, L, seg, lane & 15, s_coef, &s_fl, wave);
 }
 
 template <int ND, int PM>

@@ -1,5 +1,6 @@
 // pipe_common.hpp -- pieces shared by the three-role pipeline kernels (kernels_indirect_pipe8.hip: 16 segments and eight waves per
-// workgroup, two RK4 steps per phase; kernels_indirect_pipe48.hip: 48 segments and sixteen waves, one step per phase).
+// workgroup, two RK4 steps per phase; kernels_indirect_pipe32.hip: 32 segments and twelve waves, kernels_indirect_pipe48.hip: 48
+// segments and sixteen waves, one step per phase).
 #pragma once
 #include "kernels.hpp"
 #include <pipe_hooks.hpp>   // product: hooks/ (no-ops); `make probe`: tools/probe_hooks/
@@ -68,6 +69,84 @@ __device__ __forceinline__ PipeLane pipe_lane(const IndirectArgs& a, const int s
   L.mine = !a.class_filter || p_class(L.tp.p) == PM;
   L.in_range = (s_raw < a.S) && L.mine;
   return L;
+}
+
+// ------------------------------------------------------------------ Phi to global memory through a transpose in LDS
+// A column lane is (segment, column) and holds the ND rows of its column, but Phi is [column * ND + row][segment]: stored from
+// the lanes, one instruction writes 13 or 14 pieces of 32 bytes (four neighbouring segments each) and no full line ever leaves the
+// CU, although the workgroup owns ND * ND complete rows of SEGS segments.  After the last step barrier the coefficient ring is
+// dead, so the column lanes put their values there as a tile [column][row][segment] (pipe_phi_put), one workgroup barrier
+// follows, and every resident wave stores whole rows (pipe_phi_rows): with SEGS = 16 an instruction is four rows of 128 bytes.
+// The tile also carries a table of the workgroup's segment targets -- the segment index after the optional balanced order, or -1
+// where nothing may be stored (shadow lanes; another control-law class of a mixed batch) -- so the row stores are the same
+// code whether a row is one line (no order: consecutive targets) or SEGS scattered doubles (balanced order).
+//
+// Banks.  ds_write_b64 is served in four groups of 16 contiguous lanes over 16 slots of 8 bytes: a group is one segment's 16
+// column lanes writing row r, i.e. doubles col * CS + r * SEGS + seg -- conflict-free when the column stride CS is odd (col * CS
+// mod 16 then takes 16 different values), so CS = ND * SEGS + 1.  ds_read_b64 is served in two groups of 32 lanes over 32 slots: a
+// group reads 32 / SEGS consecutive rows of the same column (ND and the rows per instruction are even, so a pair of rows never
+// straddles two columns), which are 32 consecutive doubles (rows are SEGS doubles apart): conflict-free wherever they start.
+template <int ND, int SEGS> struct PhiTile {
+  static constexpr int RPI = SEGS <= 16 ? 4 : SEGS <= 32 ? 2 : 1;    // rows per store instruction
+  static constexpr int LPR = 64 / RPI;                               // lanes per row (lanes >= SEGS of a row: idle)
+  static constexpr int GROUPS = ND * ND / RPI;                       // store instructions per workgroup
+  static constexpr int CS = ND * SEGS + 1;                           // doubles from one column to the next
+  static constexpr int TABLE = ND * CS;                              // the segment targets (SEGS ints) follow the tile
+  static constexpr int DOUBLES = TABLE + (SEGS + 1) / 2;
+  static_assert(SEGS <= LPR && (ND * ND) % RPI == 0 && ND % 2 == 0 && CS % 2 == 1, "row groups / bank arithmetic above");
+  __host__ __device__ static constexpr int at(int col, int row, int seg) { return col * CS + row * SEGS + seg; }
+};
+
+// A column lane (col < ND) puts the ND values of its column into the tile; the lane of column 0 also enters its segment's target.
+template <int ND, int SEGS>
+__device__ __forceinline__ void pipe_phi_put(double* ring, const PipeLane& L, const int seg, const int col, const double (&v)[ND]) {
+  using T = PhiTile<ND, SEGS>;
+  if (col < ND) {
+#pragma unroll
+    for (int r = 0; r < ND; ++r) ring[T::at(col, r, seg)] = v[r];
+  }
+  if (col == 0) reinterpret_cast<int*>(ring + T::TABLE)[seg] = L.in_range ? L.s : -1;
+}
+
+// After the barrier that follows pipe_phi_put: wave `rank` of the NW resident waves stores row groups rank, rank + NW, ...
+// Nontemporal: nobody reads Phi again before the kernel ends.  One 64-bit address product per wave; the rows that
+// follow are a constant stride further on.
+template <int ND, int SEGS, int NW>
+__device__ __forceinline__ void pipe_phi_rows(const IndirectArgs& a, const double* ring, const int rank) {
+  using T = PhiTile<ND, SEGS>;
+  // (the lane index passes through an empty asm: the compiler otherwise forms the row addresses in front of the caller's step loop
+  // and carries them through it -- spills in the roles that run at their register limit)
+  int lane = threadIdx.x & 63;
+  asm volatile("" : "+v"(lane));
+  const int sub = lane / T::LPR, seg = lane % T::LPR;
+  const int tgt = (seg < SEGS) ? reinterpret_cast<const int*>(ring + T::TABLE)[seg] : -1;
+  double* dst = a.Phi + ((long)(rank * T::RPI + sub) * a.ldp + tgt);
+  const long stride = (long)(NW * T::RPI) * a.ldp;
+#pragma unroll
+  for (int i = 0; i < (T::GROUPS + NW - 1) / NW; ++i) {
+    const int g = rank + i * NW;                       // wave-uniform
+    if (g < T::GROUPS && tgt >= 0) {
+      const int row = g * T::RPI + sub;
+      __builtin_nontemporal_store(ring[T::at(row / ND, row % ND, seg)], dst + i * stride);
+    }
+  }
+}
+
+// The whole store: the column lanes put `v` (put = true), the workgroup meets once, all NW resident waves store rows.  The
+// caller forms the values (every kernel form keeps its own expression: the bits of Phi do not change).
+template <int ND, int SEGS, int NW>
+__device__ __forceinline__ void pipe_store_phi(const IndirectArgs& a, double* ring, const int rank, const bool put, const PipeLane& L,
+                                               const int seg, const int col, const double (&v)[ND]) {
+  if (put) pipe_phi_put<ND, SEGS>(ring, L, seg, col, v);
+  __syncthreads();
+  pipe_phi_rows<ND, SEGS, NW>(a, ring, rank);
+}
+
+// ... and for the waves that hold no columns (base, coefficients): they meet the others and store their share of the rows
+template <int ND, int SEGS, int NW>
+__device__ __forceinline__ void pipe_store_phi(const IndirectArgs& a, const double* ring, const int rank) {
+  __syncthreads();
+  pipe_phi_rows<ND, SEGS, NW>(a, ring, rank);
 }
 
 // role switches: always on in the product build, a mask in IndirectArgs::max_steps in the probe build (pipe_hooks.hpp)

@@ -15,6 +15,11 @@ struct BarrierWait {
   // second-to-last barrier to arriving at the last (drain), and from leaving the last barrier to the report (epilogue)
   long long born = clock64(), first_leave = 0, prev_leave = 0, last_arrive = 0, last_leave = 0;
   int nsync = 0;
+  // stamps inside the epilogue (ticks since leaving the last barrier): 0 = before the first Phi store, 1 = after the last one is
+  // issued, 2 = after the wave's global stores have drained; drained() waits for them (probe build only) and takes stamp 2
+  long long mark[3] = {0, 0, 0};
+  __device__ __forceinline__ void stamp(int i) { mark[i] = clock64() - last_leave; }
+  __device__ __forceinline__ void drained() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(2); }
   __device__ __forceinline__ void sync() {
     const long long t = clock64(); __syncthreads(); const long long t2 = clock64();
     waited += t2 - t;
@@ -29,6 +34,7 @@ struct BarrierWait {
     rows[(row0 + 1) * ld + col] = (double)(nsync > 1 ? last_arrive - prev_leave : 0);
     rows[(row0 + 2) * ld + col] = (double)(clock64() - last_leave);
     rows[(row0 + 3) * ld + col] = (double)nsync;
+    for (int i = 0; i < 3; ++i) rows[(row0 + 4 + i) * ld + col] = (double)mark[i];
   }
 };
 struct RegionClock {

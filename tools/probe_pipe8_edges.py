@@ -2,7 +2,9 @@
 """Development aid: where a wavefront of the eight-wave contract sweep spends its ticks (probe build, LTO_HIP_LIB=build/liblto_probe.so).
 Per wave of the workgroup, medians over the workgroups: the fill (first hook to leaving the first phase barrier), the ticks waited at
 the phase barriers, the drain (leaving the second-to-last barrier to arriving at the last), the epilogue (leaving the last barrier to
-the end of the role, Phi / defect stores issued) and the number of barriers; the base wave's whole loop in ticks and microseconds."""
+the end of the role, Phi / defect stores issued) and the number of barriers; the base wave's whole loop in ticks and microseconds.
+The column waves' epilogue is split by three stamps, in ticks since the last barrier: `first` = before the first Phi store, `issued` =
+after the last one is issued, `drained` = after s_waitcnt vmcnt(0) (the probe build waits there; the product does not)."""
 import os
 import sys
 
@@ -41,10 +43,10 @@ def main():
         cyc, wall = dh[17, ::16], dh[18, ::16]
         ghz = np.median(cyc / wall) * 0.1
         print("ndim=%d  pipe8 %.1f us; base loop %.0f kticks = %.1f us at %.3f GHz" % (ndim, ms * 1e3, np.median(cyc) / 1e3, np.median(wall) / 100.0, ghz))
-        print("  %-2s %-16s %8s %8s %8s %8s %6s" % ("w", "role", "fill", "waited", "drain", "epilog", "syncs"))
+        print("  %-2s %-16s %8s %8s %8s %8s %6s %8s %8s %8s" % ("w", "role", "fill", "waited", "drain", "epilog", "syncs", "first", "issued", "drained"))
         for w in range(8):
             col = lambda r: np.median(dh[r].reshape(-1, 16)[:, w])
-            print("  w%d %-16s %8.0f %8.0f %8.0f %8.0f %6.0f" % (w, ROLES[w], col(20), col(16), col(21), col(22), col(23)))
+            print("  w%d %-16s %8.0f %8.0f %8.0f %8.0f %6.0f %8.0f %8.0f %8.0f" % (w, ROLES[w], col(20), col(16), col(21), col(22), col(23), col(24), col(25), col(26)))
         plan.close()
 
 
