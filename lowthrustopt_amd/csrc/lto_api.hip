@@ -172,8 +172,13 @@ int arena_reserve(lto_ctx* c, size_t bytes) {
 }
 inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// The scratch of one host-pointer call: every buffer is declared once with its element count (add), then reserve() grows the
-// arena to the exact sum of the 256-B-aligned sizes and fills in the pointers, in the order of declaration.
+// The scratch of one host-pointer call: every buffer is declared once with its element count (add); the layout is then
+// materialised in the order of declaration, every buffer on a 256-B boundary, and the pointers are filled in.  reserve() places it
+// in the context's arena, grown to the exact sum of the aligned sizes.  reserve_block() places it in one hipMalloc block of that
+// sum and hands the block to `slot` (a HostCall's block[k], which frees it): for the calls that run indirect_solve_impl in their
+// middle, which lays the arena out afresh.  A buffer of zero elements takes no bytes; its pointer is valid (the next buffer's
+// start, or the end) and nothing may be read through it.  (reserve_block of a layout with no bytes at all gets no block from
+// hipMalloc: every pointer is then null.)
 class ArenaLayout {
   static constexpr int kMax = 24;
   struct Slot { void* ptr; void (*set)(void*, char*); size_t bytes; };
@@ -183,16 +188,29 @@ class ArenaLayout {
     if (n_ < kMax) slot_[n_] = {&p, [](void* q, char* at) { *(T**)q = (T*)at; }, al256(sizeof(T) * count)};
     ++n_;
   }
+  size_t total() const {
+    size_t sum = 0;
+    for (int k = 0; k < n_; ++k) sum += slot_[k].bytes;
+    return sum;
+  }
+  void place(char* base) {
+    size_t off = 0;
+    for (int k = 0; k < n_; ++k) { slot_[k].set(slot_[k].ptr, base + off); off += slot_[k].bytes; }
+  }
  public:
   template <class... T> void add(size_t count, T*&... p) { (add1(p, count), ...); }   // buffers of `count` elements each
   int reserve(lto_ctx* c) {
     if (n_ > kMax) return set_err(c, LTO_EINVAL, "internal: too many scratch buffers");
-    size_t total = 0;
-    for (int k = 0; k < n_; ++k) total += slot_[k].bytes;
-    const int rc = arena_reserve(c, total);
+    const int rc = arena_reserve(c, total());
     if (rc) return rc;
-    size_t off = 0;
-    for (int k = 0; k < n_; ++k) { slot_[k].set(slot_[k].ptr, c->arena + off); off += slot_[k].bytes; }
+    place(c->arena);
+    return LTO_OK;
+  }
+  int reserve_block(lto_ctx* c, void*& slot, const char* who) {   // `who`: the error text of a failed allocation
+    if (n_ > kMax) return set_err(c, LTO_EINVAL, "internal: too many scratch buffers");
+    const hipError_t e = hipMalloc(&slot, total());
+    if (e != hipSuccess) { slot = nullptr; return set_err(c, LTO_EHIP, who, e); }
+    place((char*)slot);
     return LTO_OK;
   }
 };
@@ -1919,6 +1937,23 @@ int lto_indirect_jacobian(lto_ctx* c, int ndim, int n_nodes, int n_batch, const 
   return rc;
 }
 
+// LinRange(t0, te, m) into out[0..m)
+static void linrange(double t0, double te, int m, double* out) {
+  for (int k = 0; k < m; ++k) {
+    const double tau = (double)k / (double)(m - 1);
+    out[k] = (1.0 - tau) * t0 + tau * te;
+  }
+}
+// samples of segment i of a grid g[0..nn-1]: td[0..m) in [g_i, g_{i+1}), the first of them into first[i] (+ base); the last sample
+// is left to the caller's closing entry
+static void segment_samples(const double* g, int nn, const double* td, int m, int* first, int base) {
+  int j = 0;
+  for (int i = 0; i < nn - 1; ++i) {
+    first[i] = base + j;
+    while (j < m - 1 && td[j] < g[i + 1]) ++j;
+  }
+}
+
 /* densify of src/HelperFunctions.jl:51-101 for one trajectory: t_dense = LinRange(t[1], t[end], n_desired); every
  * segment is re-propagated and sampled at the t_dense points inside [t_i, t_{i+1}); the final propagated state is
  * appended (:94-97).  XC_dense [ndim x n_desired], t_dense [n_desired]. */
@@ -1934,17 +1969,9 @@ int lto_indirect_densify(lto_ctx* c, int ndim, int n_nodes, const double* XC, co
   lto_indirect_plan* p = call.plan[0];
   const int S = p->S;
   if (!h_first.alloc((size_t)S + 1)) return set_err(c, LTO_EHIP, "host allocation failed");
-  const double t0 = t[0], tn = t[n_nodes - 1];
-  for (int k = 0; k < n_desired; ++k) {
-    const double tau = (double)k / (double)(n_desired - 1);
-    t_dense[k] = (1.0 - tau) * t0 + tau * tn;
-  }
+  linrange(t[0], t[n_nodes - 1], n_desired, t_dense);
   // samples of segment i: t_dense in [t_i, t_{i+1}); the last grid point (== t_n) is served by the final state
-  int j = 0;
-  for (int i = 0; i < S; ++i) {
-    h_first[i] = j;
-    while (j < n_desired - 1 && t_dense[j] < t[i + 1]) ++j;
-  }
+  segment_samples(t, n_nodes, t_dense, n_desired, h_first.data(), 0);
   h_first[S] = n_desired - 1;
   const long J = n_nodes;
   double *d_aos, *d_X, *d_t, *d_td, *d_Y, *d_Yaos;
@@ -2206,13 +2233,14 @@ int lto_direct_end_states(lto_ctx* c, const lto_direct_orbits* orbits, int n_bat
   hipStream_t st = c->stream;
   rc = orbits_upload(c, orbits, dob, st);
   if (rc) return rc;
-  const size_t nd = (size_t)n_batch * (2 + 12 + 14);
-  hipError_t e = hipMalloc(&call.block[0], sizeof(double) * nd);
-  if (e != hipSuccess) { call.block[0] = nullptr; return set_err(c, LTO_EHIP, "lto_direct_end_states", e); }
-  double* d_tau = (double*)call.block[0];
-  double* d_s = d_tau + 2 * (size_t)n_batch;
-  double* d_m = d_s + 12 * (size_t)n_batch;
-  e = hipMemcpyAsync(d_tau, tau, sizeof(double) * 2 * n_batch, hipMemcpyHostToDevice, st);
+  double *d_tau, *d_s, *d_m;
+  ArenaLayout scratch;
+  scratch.add((size_t)2 * n_batch, d_tau);
+  scratch.add((size_t)12 * n_batch, d_s);
+  scratch.add((size_t)14 * n_batch, d_m);
+  rc = scratch.reserve_block(c, call.block[0], "lto_direct_end_states");
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(d_tau, tau, sizeof(double) * 2 * n_batch, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = launch_end_states(dob.o, d_tau, n_batch, d_s, 12, d_m, st);
   if (e == hipSuccess) e = hipMemcpyAsync(s_out, d_s, sizeof(double) * 12 * n_batch, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(model, d_m, sizeof(double) * 14 * n_batch, hipMemcpyDeviceToHost, st);
@@ -2252,26 +2280,19 @@ int lto_indirect_add_time_batch(lto_ctx* c, int ndim, int n_nodes, const double*
   if (!h_te.ok() || !h_td.ok() || !h_cp.ok() || !h_xe.ok() || !h_fe.ok() || !h_fc.ok())
     return set_err(c, LTO_ENOMEM, "lto_indirect_add_time_batch: out of host memory");
   const double t0 = t[0];
-  // samples of segment i of a grid g[0..nn-1]: td in [g_i, g_{i+1}); the last segment also takes the last sample (t_end itself: the
-  // lane steps onto it exactly as the final-state store of lto_indirect_densify does)
-  auto ranges = [&](const double* g, int nn, const double* tdb, int* f, int base) {
-    int j = 0;
-    for (int i = 0; i < nn - 1; ++i) {
-      f[i] = base + j;
-      while (j < m - 1 && tdb[j] < g[i + 1]) ++j;
-    }
-  };
+  // the sample ranges (segment_samples): the last segment also takes the last sample (t_end itself: the lane steps onto it exactly
+  // as the final-state store of lto_indirect_densify does)
   for (int b = 0; b < K; ++b) {
     const double te = t[n - 1] + dt[b];
     double* tb = &h_te[(size_t)b * ne];
     std::memcpy(tb, t, sizeof(double) * n);
     tb[n] = te;
     double* tdb = &h_td[(size_t)b * m];
-    for (int k = 0; k < m; ++k) { const double tau = (double)k / (double)(m - 1); tdb[k] = (1.0 - tau) * t0 + tau * te; }
+    linrange(t0, te, m, tdb);
     double* tnb = t_out + (size_t)b * n;
-    for (int k = 0; k < n; ++k) { const double tau = (double)k / (double)(n - 1); tnb[k] = (1.0 - tau) * t0 + tau * te; }
-    ranges(tb, ne, tdb, &h_fe[(size_t)b * n], b * m);
-    ranges(tnb, n, tdb, &h_fc[(size_t)b * (n - 1)], b * m);
+    linrange(t0, te, n, tnb);
+    segment_samples(tb, ne, tdb, m, &h_fe[(size_t)b * n], b * m);
+    segment_samples(tnb, n, tdb, m, &h_fc[(size_t)b * (n - 1)], b * m);
     double* xb = &h_xe[(size_t)12 * ne * b];
     std::memcpy(xb, XC, sizeof(double) * 12 * n);
     for (int q = 6; q < 12; ++q) xb[12 * (n - 1) + q] = 0.0;         // :199 (on a copy)
@@ -2280,15 +2301,21 @@ int lto_indirect_add_time_batch(lto_ctx* c, int ndim, int n_nodes, const double*
   h_fe[(size_t)K * n] = K * m;
   h_fc[(size_t)K * (n - 1)] = K * m;
   for (int i = 1; i < m - 1; ++i) h_cp[i] = 1.0 / (4.0 - h_cp[i - 1]);
-  // device side: one block, carved 256-B aligned
+  // device side: one block of the call's own (the solve loop below lays the arena out afresh)
   const long Je = (long)K * ne, Jn = (long)K * n, Jm = (long)K * m;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += al256(bytes); return at; };
-  const size_t o_xa = take(sizeof(double) * 12 * Je), o_xe = take(sizeof(double) * 12 * Je), o_te = take(sizeof(double) * Je),
-               o_tn = take(sizeof(double) * Jn), o_td = take(sizeof(double) * Jm), o_cp = take(sizeof(double) * m),
-               o_fe = take(sizeof(int) * (Jn + 1)), o_fc = take(sizeof(int) * (Jn - K + 1)), o_y = take(sizeof(double) * 12 * Jm),
-               o_mom = take(sizeof(double) * 12 * Jm), o_g = take(sizeof(double) * 12 * Jn), o_ga = take(sizeof(double) * 12 * Jn),
-               o_xc = take(sizeof(double) * 12 * Jn), o_tau = take(sizeof(double) * K), o_cost = take(sizeof(double) * K);
+  double *d_xa, *d_xe, *d_te, *d_tn, *d_td, *d_cp, *d_y, *d_mom, *d_g, *d_ga, *d_xc, *d_tau, *d_cost;
+  int *d_fe, *d_fc;
+  ArenaLayout scratch;
+  scratch.add((size_t)12 * Je, d_xa, d_xe);
+  scratch.add((size_t)Je, d_te);
+  scratch.add((size_t)Jn, d_tn);
+  scratch.add((size_t)Jm, d_td);
+  scratch.add((size_t)m, d_cp);
+  scratch.add((size_t)Jn + 1, d_fe);
+  scratch.add((size_t)(Jn - K) + 1, d_fc);
+  scratch.add((size_t)12 * Jm, d_y, d_mom);
+  scratch.add((size_t)12 * Jn, d_g, d_ga, d_xc);
+  scratch.add((size_t)K, d_tau, d_cost);
   lto_direct_orbits arr = *orbits;                 // the upload builds both tables: the departure side gets the arrival's
   arr.n0 = arr.nf; arr.t0 = arr.tf; arr.X0 = arr.Xf;
   DevOrbits dob;
@@ -2296,17 +2323,11 @@ int lto_indirect_add_time_batch(lto_ctx* c, int ndim, int n_nodes, const double*
   hipStream_t st = c->stream;
   rc = orbits_upload(c, &arr, dob, st);
   if (rc) return rc;
-  hipError_t e = hipMalloc(&call.block[0], off);
-  if (e != hipSuccess) { call.block[0] = nullptr; return set_err(c, LTO_EHIP, "lto_indirect_add_time_batch", e); }
-  char* base = (char*)call.block[0];
-  double *d_xa = (double*)(base + o_xa), *d_xe = (double*)(base + o_xe), *d_te = (double*)(base + o_te), *d_tn = (double*)(base + o_tn),
-         *d_td = (double*)(base + o_td), *d_cp = (double*)(base + o_cp), *d_y = (double*)(base + o_y), *d_mom = (double*)(base + o_mom),
-         *d_g = (double*)(base + o_g), *d_ga = (double*)(base + o_ga), *d_xc = (double*)(base + o_xc), *d_tau = (double*)(base + o_tau),
-         *d_cost = (double*)(base + o_cost);
-  int *d_fe = (int*)(base + o_fe), *d_fc = (int*)(base + o_fc);
+  rc = scratch.reserve_block(c, call.block[0], "lto_indirect_add_time_batch");
+  if (rc) return rc;
   rc = plan_build(c, 12, ne, K, prm, 1, integ, &call.plan[0]);
   if (rc) return rc;
-  e = hipMemcpyAsync(d_xa, h_xe.data(), sizeof(double) * 12 * Je, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(d_xa, h_xe.data(), sizeof(double) * 12 * Je, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_te, h_te.data(), sizeof(double) * Je, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_tn, t_out, sizeof(double) * Jn, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_td, h_td.data(), sizeof(double) * Jm, hipMemcpyHostToDevice, st);
@@ -2399,29 +2420,31 @@ int lto_indirect_remesh_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, co
   CallTimer call_timer(c);
   lto::HostBuf<int> h_cnt((size_t)2 * Smax);                // step counters on their way out (the stream copies into it)
   if (!h_cnt.ok()) return set_err(c, LTO_ENOMEM, "lto_indirect_remesh_batch: out of host memory");
-  // device side: one block, carved 256-B aligned
+  // device side: one block of the call's own (the solve loop below lays the arena out afresh); the second of a pair, the final
+  // trajectories, the weights, the defect and the monitor's scratch only where they are used
   const long Jmax = J0 > Jn ? J0 : Jn;
   const size_t c_stride = nmax - 1 > kRemeshLdsSegs ? remesh_scratch_doubles(nmax) : 0;
   const bool want_final = XC_out && steps_after && adaptive;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += al256(bytes); return at; };
-  const size_t o_xa = take(sizeof(double) * 12 * Jmax), o_x0 = take(sizeof(double) * 12 * J0), o_g0 = take(sizeof(double) * 12 * Jn),
-               o_g1 = take(passes > 1 ? sizeof(double) * 12 * Jn : 0), o_xf = take(want_final ? sizeof(double) * 12 * Jn : 0),
-               o_t0 = take(sizeof(double) * n0 * n_tgrids), o_tn0 = take(sizeof(double) * Jn),
-               o_tn1 = take(passes > 1 ? sizeof(double) * Jn : 0), o_seg = take(sizeof(int) * Jn),
-               o_w = take(weights ? sizeof(double) * S0 : 0), o_def = take(adaptive ? sizeof(double) * 12 * Smax : 0),
-               o_c = take(sizeof(double) * c_stride * B);
+  double *d_xa, *d_x0, *d_g[2], *d_xf, *d_t0, *d_tn[2], *d_w, *d_def, *d_c;
+  int* d_seg;
+  ArenaLayout scratch;
+  scratch.add((size_t)12 * Jmax, d_xa);
+  scratch.add((size_t)12 * J0, d_x0);
+  scratch.add((size_t)12 * Jn, d_g[0]);
+  scratch.add(passes > 1 ? (size_t)12 * Jn : 0, d_g[1]);
+  scratch.add(want_final ? (size_t)12 * Jn : 0, d_xf);
+  scratch.add((size_t)n0 * n_tgrids, d_t0);
+  scratch.add((size_t)Jn, d_tn[0]);
+  scratch.add(passes > 1 ? (size_t)Jn : 0, d_tn[1]);
+  scratch.add((size_t)Jn, d_seg);
+  scratch.add(weights ? (size_t)S0 : 0, d_w);
+  scratch.add(adaptive ? (size_t)12 * Smax : 0, d_def);
+  scratch.add(c_stride * B, d_c);
   HostCall call(c);
   hipStream_t st = c->stream;
-  hipError_t e = hipMalloc(&call.block[0], off);
-  if (e != hipSuccess) { call.block[0] = nullptr; return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch", e); }
-  char* base = (char*)call.block[0];
-  double *d_xa = (double*)(base + o_xa), *d_x0 = (double*)(base + o_x0), *d_xf = (double*)(base + o_xf), *d_t0 = (double*)(base + o_t0),
-         *d_w = (double*)(base + o_w), *d_def = (double*)(base + o_def), *d_c = (double*)(base + o_c);
-  double* d_g[2] = {(double*)(base + o_g0), (double*)(base + o_g1)};
-  double* d_tn[2] = {(double*)(base + o_tn0), (double*)(base + o_tn1)};
-  int* d_seg = (int*)(base + o_seg);
-  e = hipMemcpyAsync(d_xa, XC, sizeof(double) * 12 * J0, hipMemcpyHostToDevice, st);
+  rc = scratch.reserve_block(c, call.block[0], "lto_indirect_remesh_batch");
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(d_xa, XC, sizeof(double) * 12 * J0, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t0, t, sizeof(double) * n0 * n_tgrids, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && weights) e = hipMemcpyAsync(d_w, weights, sizeof(double) * S0, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = launch_pack_soa(d_xa, 12, J0, d_x0, J0, st);
@@ -2716,8 +2739,9 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
   p->qp_singular_out = d_sing;
   (void)report_reserve(c, (size_t)(fe ? 7 : 4) * B);
   hipStream_t st = c->stream;
-  // free ends: tau [2B] | tf [B] | p [3B] | end model [14B] | beta [B] | tf bounds [3B] | t0 [B] on the device, the orbit tables with
-  // their spline moments; free tf also: the grids [B][n] | tau_grid [B][n] | the tf column [nstate][S]
+  // free ends: tau [2B] | tf [B] (one buffer: the loop reads them back in one run), p [3B], end model [14B], beta [B], tf bounds [3B],
+  // t0 [B] on the device, the orbit tables with their spline moments; free tf also: the grids [B][n] | tau_grid [B][n] (one buffer:
+  // they arrive in one copy) and the tf column [nstate][S]
   double *d_tau = nullptr, *d_tf = nullptr, *d_p = nullptr, *d_em = nullptr, *d_beta = nullptr, *d_tfb = nullptr, *d_t0 = nullptr;
   double *d_tb = nullptr, *d_taug = nullptr, *d_dtf = nullptr;
   if (fe) {
@@ -2726,39 +2750,46 @@ static int direct_solve_impl(lto_ctx* c, int nstate, int n_nodes, int n_batch, c
     if (rc == LTO_OK && (!hb.ok() || !hg.ok())) rc = set_err(c, LTO_ENOMEM, "lto_direct_solve_free_batch: out of host memory");
     if (rc == LTO_OK) {
       for (int b = 0; b < B; ++b) hb[b] = fe->beta[n_targets == 1 ? 0 : b];
-      hipError_t e0 = hipMalloc(&call.block[0], sizeof(double) * 25 * B);
-      if (e0 != hipSuccess) { call.block[0] = nullptr; rc = set_err(c, LTO_EHIP, "free-end buffers", e0); }
-      else {
-        d_tau = (double*)call.block[0]; d_tf = d_tau + 2 * (size_t)B; d_p = d_tf + B; d_em = d_p + 3 * (size_t)B; d_beta = d_em + 14 * (size_t)B;
-        d_tfb = d_beta + B; d_t0 = d_tfb + 3 * (size_t)B;
-        e0 = hipMemcpyAsync(d_tau, fe->tau_in, sizeof(double) * 2 * B, hipMemcpyHostToDevice, st);
-        if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_beta, hb.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
-        if (e0 == hipSuccess) e0 = hipMemsetAsync(d_p, 0, sizeof(double) * 3 * B, st);
-        if (e0 == hipSuccess && tfm) {
-          // tf, t0, the bounds and tau_grid of every trajectory from its entry grid (:478-480); the grids start as t1
-          for (int b = 0; b < B; ++b) {
-            const lto_direct_tf_bounds& q = fe->tfb[n_targets == 1 ? 0 : b];
-            const double* g = t + (size_t)(n_tgrids == 1 ? 0 : b) * n;
-            hb[B + b] = g[n - 1]; hb[2 * (size_t)B + b] = g[0];
-            hb[3 * (size_t)B + 3 * b] = q.step; hb[3 * (size_t)B + 3 * b + 1] = q.tf_min; hb[3 * (size_t)B + 3 * b + 2] = q.tf_max;
-            for (long k = 0; k < n; ++k) {
-              hg[(size_t)b * n + k] = t1[(size_t)(n_tgrids == 1 ? 0 : b) * n + k];
-              hg[(size_t)(B + b) * n + k] = (g[k] - g[0]) / (g[n - 1] - g[0]) * 2.0 - 1.0;
-            }
-          }
-          e0 = hipMalloc(&call.block[1], sizeof(double) * (2 * (size_t)n * B + (size_t)nstate * S));
-          if (e0 != hipSuccess) call.block[1] = nullptr;
-          else {
-            d_tb = (double*)call.block[1]; d_taug = d_tb + (size_t)n * B; d_dtf = d_taug + (size_t)n * B;
-            e0 = hipMemcpyAsync(d_tf, &hb[B], sizeof(double) * B, hipMemcpyHostToDevice, st);
-            if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_t0, &hb[2 * (size_t)B], sizeof(double) * B, hipMemcpyHostToDevice, st);
-            if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_tfb, &hb[3 * (size_t)B], sizeof(double) * 3 * B, hipMemcpyHostToDevice, st);
-            if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_tb, hg.data(), sizeof(double) * 2 * n * B, hipMemcpyHostToDevice, st);
+      ArenaLayout ends;
+      ends.add((size_t)3 * B, d_tau);                      // tau [2B] | tf [B]
+      ends.add((size_t)3 * B, d_p);
+      ends.add((size_t)14 * B, d_em);
+      ends.add((size_t)B, d_beta);
+      ends.add((size_t)3 * B, d_tfb);
+      ends.add((size_t)B, d_t0);
+      rc = ends.reserve_block(c, call.block[0], "free-end buffers");
+    }
+    if (rc == LTO_OK) {
+      d_tf = d_tau + 2 * (size_t)B;
+      hipError_t e0 = hipMemcpyAsync(d_tau, fe->tau_in, sizeof(double) * 2 * B, hipMemcpyHostToDevice, st);
+      if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_beta, hb.data(), sizeof(double) * B, hipMemcpyHostToDevice, st);
+      if (e0 == hipSuccess) e0 = hipMemsetAsync(d_p, 0, sizeof(double) * 3 * B, st);
+      if (e0 == hipSuccess && tfm) {
+        // tf, t0, the bounds and tau_grid of every trajectory from its entry grid (:478-480); the grids start as t1
+        for (int b = 0; b < B; ++b) {
+          const lto_direct_tf_bounds& q = fe->tfb[n_targets == 1 ? 0 : b];
+          const double* g = t + (size_t)(n_tgrids == 1 ? 0 : b) * n;
+          hb[B + b] = g[n - 1]; hb[2 * (size_t)B + b] = g[0];
+          hb[3 * (size_t)B + 3 * b] = q.step; hb[3 * (size_t)B + 3 * b + 1] = q.tf_min; hb[3 * (size_t)B + 3 * b + 2] = q.tf_max;
+          for (long k = 0; k < n; ++k) {
+            hg[(size_t)b * n + k] = t1[(size_t)(n_tgrids == 1 ? 0 : b) * n + k];
+            hg[(size_t)(B + b) * n + k] = (g[k] - g[0]) / (g[n - 1] - g[0]) * 2.0 - 1.0;
           }
         }
-        if (e0 == hipSuccess) e0 = stream_wait(st);        // hb and hg are released at the end of this block
-        if (e0 != hipSuccess) rc = set_err(c, LTO_EHIP, "free-end buffers", e0);
+        ArenaLayout grids;
+        grids.add((size_t)2 * n * B, d_tb);                // grids [B][n] | tau_grid [B][n]
+        grids.add((size_t)nstate * S, d_dtf);
+        rc = grids.reserve_block(c, call.block[1], "free-end buffers");
+        if (rc == LTO_OK) {
+          d_taug = d_tb + (size_t)n * B;
+          e0 = hipMemcpyAsync(d_tf, &hb[B], sizeof(double) * B, hipMemcpyHostToDevice, st);
+          if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_t0, &hb[2 * (size_t)B], sizeof(double) * B, hipMemcpyHostToDevice, st);
+          if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_tfb, &hb[3 * (size_t)B], sizeof(double) * 3 * B, hipMemcpyHostToDevice, st);
+          if (e0 == hipSuccess) e0 = hipMemcpyAsync(d_tb, hg.data(), sizeof(double) * 2 * n * B, hipMemcpyHostToDevice, st);
+        }
       }
+      if (rc == LTO_OK && e0 == hipSuccess) e0 = stream_wait(st);        // hb and hg are released at the end of this block
+      if (rc == LTO_OK && e0 != hipSuccess) rc = set_err(c, LTO_EHIP, "free-end buffers", e0);
     }
     if (rc == LTO_OK && fe->flag_end) rc = direct_qp_workspace(p, tfm ? 4 : 3);
     if (rc) return rc;

@@ -13,10 +13,26 @@ def test_hostbuf_containers(tmp_path):
     assert out.returncode == 0 and "hostbuf ok" in out.stdout, out.stdout + out.stderr
 
 
-def test_no_throwing_containers_left_behind_the_abi():
-    """The three translation units that implement the C ABI hold no std::vector / std::map / std::string / std::thread any more."""
+def _host_units():
+    """Every host translation unit of the library -- the Makefile's SRCS but the kernels_*.hip -- and the internal headers they share."""
     import re
-    for unit in ("lto_api.hip", "lto_group.hip", "lto_comm.hip"):
+    csrc = os.path.join(ROOT, "lowthrustopt_amd", "csrc")
+    make = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")        # a wrapped list is one line
+    srcs = re.search(r"^SRCS\s*:=\s*(.*)$", make, flags=re.M).group(1).split()
+    on_disk = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert sorted(srcs) == on_disk, (srcs, on_disk)                              # the whole list was read, and it is the directory
+    units = [u for u in srcs if not u.startswith("kernels_")]
+    assert {"lto_group.hip", "lto_comm.hip"} < set(units), units        # and at least one unit for the rest of the ABI
+    assert all(u.startswith("lto_") for u in units), units              # the Makefile's SRCS holds kernels_*.hip and lto_*.hip only
+    headers = sorted(f for f in os.listdir(csrc) if f.startswith("lto_") and f.endswith(".hpp"))      # internal headers of the host units
+    return units + headers + ["hostbuf.hpp"]
+
+
+def test_no_throwing_containers_left_behind_the_abi():
+    """The translation units that implement the C ABI, and their internal headers, hold no std::vector / std::map / std::string /
+    std::thread any more."""
+    import re
+    for unit in _host_units():
         src = open(os.path.join(ROOT, "lowthrustopt_amd", "csrc", unit)).read()
         code = re.sub(r"//[^\n]*", "", src)                       # comments may name what was replaced
         for bad in ("std::vector", "std::unordered_map", "std::map<", "std::string", "std::thread", "#include <vector>"):
