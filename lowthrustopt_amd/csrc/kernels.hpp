@@ -34,7 +34,7 @@ struct IndirectArgs {
   // its own cache line (5 - 8 x the algorithmic traffic).  When these are set the kernel reads a node as ONE record
   //   Xa[node * NODE_REC + c], c < 12;  Xa[node * NODE_REC + 12] = the node's time
   // and writes a segment's results as records  Da[s * 12 + c],  Pa[s * 144 + col * 12 + row];  the plan converts between the
-  // caller's arrays and the records with coalesced transposes before / after the sweep (lto_api.hip).  Null: the arrays above.
+  // caller's arrays and the records with coalesced transposes before / after the sweep (lto_indirect_plan.hip).  Null: the arrays above.
   const double* Xa;
   double* Da;
   double* Pa;

@@ -32,7 +32,7 @@ template <> hipError_t launch_stm_nd<12>(int pm, int method, int cols, const Ind
     return hipErrorInvalidValue;
   }
   // 13-stage methods: no per-lane STM form (round 6: the memory-resident one-column-per-lane kernels, never AUTO's choice, are gone --
-  // lto_api.hip sends such sweeps to the cooperative kernels)
+  // lto_indirect_plan.hip sends such sweeps to the cooperative kernels)
   return hipErrorInvalidValue;
 }
 
@@ -46,7 +46,7 @@ hipError_t launch_indirect_stm(int ndim, int pm, int method, int cols, const Ind
 
 hipError_t launch_indirect_dense(int ndim, int pm, int method, const IndirectArgs& a, const DenseArgs& d, hipStream_t st) {
   if (a.S <= 0) return hipSuccess;
-  if (ndim != 12) return hipErrorInvalidValue;          // (lto_api.hip refuses these shapes with LTO_EUNSUPPORTED before it gets here)
+  if (ndim != 12) return hipErrorInvalidValue;          // (lto_indirect_plan.hip refuses these shapes with LTO_EUNSUPPORTED before it gets here)
   switch (method) {
     case M_RK4: return launch_dense_pm<12, M_RK4>(pm, a, d, st);
     case M_DOP853_ADAPTIVE: return launch_dense_pm<12, M_DOP853_ADAPTIVE>(pm, a, d, st);

@@ -9,7 +9,7 @@
 // and 13 x 6 slopes per lane, the tableau arithmetic per lane halves, nothing spills.  Both lanes hold r and lambda_v (three
 // doubles each cross over by v_mov_b32_dpp) and run one instruction stream (rhs12_base_half); error norms are pair sums
 // formed in the same order in both lanes, so both take the same decisions and the pair's control flow never diverges.
-// Twice the wavefronts of the one-lane kernel: AUTO runs it between 131 072 and 262 144 segments (lto_api.hip).
+// Twice the wavefronts of the one-lane kernel: AUTO runs it between 131 072 and 262 144 segments (lto_indirect_plan.hip).
 #include "kernels.hpp"
 #include "rk.hpp"
 #include "halves.hpp"
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64) void k_indirect_defect2(const IndirectArgs a) {
 // one stage ahead of their use (rk.hpp: dp8_load_row) instead of two s_mov_b32 per coefficient.  Same step control; the error
 // norms are quad sums formed in the same order in all four lanes, so a quad's control flow never diverges.  Measured
 // (tools/probe_defect2.py): 4 096 segments 90 -> 77 us per sweep, 29: 73 -> 63 us, 65 536 ordered: 0.31 -> 0.27 ms; AUTO up to
-// eight wavefronts per SIMD (lto_api.hip).
+// eight wavefronts per SIMD (lto_indirect_plan.hip).
 // ND = 14 (round 6): BASELINE configs[1]'s system for the always-thrust-limited laws -- lane 1 owns (v, m), lane 3 (lambda_r, lambda_m),
 // four components per lane with a zero in lanes 0 and 2 (halves.hpp rhs14_base_quad); norms over the 14 components.
 template <int PM, int ND = 12>

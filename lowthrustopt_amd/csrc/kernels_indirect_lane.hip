@@ -25,7 +25,7 @@
 // state parked there too during the column phase (24); four columns in LDS (24 KB per wavefront, four wavefronts per CU; 16-byte
 // pieces, one per lane and access).  490 registers, no scratch, no spill in any control-law class; nine columns would spill
 // (LANE_COLS_IN_REGISTERS).  It needs 64 segments per SIMD to fill the chip: AUTO compares its rounds of 256 x CUs segments with the
-// pipelines' (lto_api.hip).  The stage arguments pass through an empty asm before the matrices are built from them: otherwise the
+// pipelines' (lto_indirect_plan.hip).  The stage arguments pass through an empty asm before the matrices are built from them: otherwise the
 // compiler keeps ~20 more by-products per stage alive across the step.
 // 12-dim; every control-law class; RK4 with any number of steps.
 #include "kernels.hpp"

@@ -23,7 +23,7 @@ namespace lto {
 // 12-dim only): eleven column waves, the base wave's SIMD carries two of them (wave 12 leaves at once) -- with three, that SIMD
 // issues 565 + 3 x 310 instructions per step against 400 + 3 x 310 on the others and every step waits for it: one round of
 // 12 288 segments 163.9 us = 13.3 ns per segment, one of 11 264 139.3 us = 12.4 ns; C4 (262 144 segments) 3.56 -> 3.30 ms.  Which
-// form a 12-dim sweep takes is the caller's choice by round cost (lto_api.hip).  14-dim: 48 only -- there a step lasts as long as
+// form a 12-dim sweep takes is the caller's choice by round cost (lto_indirect_plan.hip).  14-dim: 48 only -- there a step lasts as long as
 // the base wave's own dependent chain whatever shares its SIMD (189 us for 11 264 segments and for 12 288).
 
 

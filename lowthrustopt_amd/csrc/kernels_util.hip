@@ -17,7 +17,7 @@ constexpr int LDS_BUDGET_DOUBLES = 8192;  // 64 KiB tile
 struct PackJob { const double* aos; double* soa; long count, ld; int ndim, tn, tiles; };
 
 // nodes per tile: as many as fit the LDS budget, at most 256, a multiple of 32 when possible -- and fewer when that leaves
-// the launch under 512 workgroups: the AoS side may be page-locked host memory behind the link (lto_api.hip, stage_in /
+// the launch under 512 workgroups: the AoS side may be page-locked host memory behind the link (lto_host_sweeps.hip, stage_in /
 // stage_out), where every trip of a thread's copy loop is a round trip of ~2 us, so a small batch wants one or two elements
 // per thread and its tiles spread over the chip (12 x 4 097 doubles read from the host: 20.5 us with 17 tiles of 256 nodes).
 static int tile_nodes(int ndim, long count) {

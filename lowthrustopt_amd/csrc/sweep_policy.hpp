@@ -1,8 +1,8 @@
 // sweep_policy.hpp -- which kernel form an indirect sweep runs: what every form is built for, and the rules that pick one.
 // Device-free (no HIP, no lto_ctx): tests/cabi/sweep_policy_check.cpp builds it with g++ and pins the choices on a CPU.  The
-// predicates are the ONLY statement of what a form is built for -- the plan setters of lto_api.hip validate through them, the rules
+// predicates are the ONLY statement of what a form is built for -- the plan setters of lto_indirect_plan.hip validate through them, the rules
 // below choose through them, the launchers of the kernel units refuse through them.  A new form: one predicate, one line in the
-// rule that should pick it, one case in launch_stm / launch_defect (lto_api.hip).
+// rule that should pick it, one case in launch_stm / launch_defect (lto_indirect_plan.hip).
 #pragma once
 #include <algorithm>
 #include "../../include/lto.h"

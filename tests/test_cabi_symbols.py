@@ -27,6 +27,16 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SIGNATURES) == syms     # the ctypes table binds exactly the header's entry points
 
 
+def test_library_exports_no_c_name_the_header_does_not_declare():
+    """The other direction: the unmangled lto_* names in the dynamic symbol table are exactly the header's.  The host units share
+    helpers through csrc/lto_host.hpp; one that lost its `static` and missed the hidden-visibility block there would otherwise widen
+    the ABI without anybody noticing."""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", lto.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = sorted(line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("lto_"))
+    assert exported == header_symbols()
+
+
 def test_version_and_error_codes():
     lib = lto.load_library()
     assert lib.lto_version() == 102

@@ -30,7 +30,7 @@ def P(a):
 
 
 def tp_vec(ndim, thr, mass_or_isp, td, p, rho):
-    """TrajParams exactly as lto_api.hip::make_traj_params fills it."""
+    """TrajParams exactly as lto_indirect_plan.hip::make_traj_params fills it."""
     aL = thr / mass_or_isp / 1e3 * (TU * TU) / DU if ndim == 12 else 0.0
     cT = thr / 1e3 * (TU * TU) / DU
     kt = td * 1e3 * DU / (TU * mass_or_isp * 9.81) if ndim == 14 else 0.0
