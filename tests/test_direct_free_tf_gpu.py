@@ -4,14 +4,13 @@ free-tf loop (lto_direct_solve_free_tf / _batch) on the halo demo."""
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
-from scipy.sparse.linalg import splu
 
 import lowthrustopt_amd as lto
 from lowthrustopt_amd import drivers, synth
 from oracle import oracle as O
 
 import direct_helpers as DH
+import qp_reference as QR
 
 ISP, NSTEPS = 2000.0, 10
 DAY = lto.day / lto.TU
@@ -76,55 +75,9 @@ def test_device_free_tf_step_matches_host(gpu_ctx, ns, imp, n):
 
 
 def _sparse_fixed_p(Jt, dtf, d, X, U, t, s0, sf, mass, dV1, dV2, imp, p3, DU, TU):
-    """The QP at fixed p (targets moved, defect + dtf p3): its KKT system assembled sparse and solved by splu after Ruiz scaling."""
-    ns, _, S = Jt.shape
-    n = S + 1
-    c2 = (DU / TU) ** 2
-    nz = ns * n + 3 * n + 6
-    iu, iv = ns * n, ns * n + 3 * n
-    dt = np.diff(t)
-    w = np.concatenate([dt / 2, [dt[-1] / 2]]) + np.concatenate([[0.0], dt[:-1] / 2, [0.0]])
-    Q = np.zeros(nz)
-    q = np.zeros(nz)
-    Q[iu:iv] = np.repeat(w, 3)
-    q[iu:iv] = (w[None, :] * U).T.reshape(-1)
-    Q[iv:] = c2
-    q[iv:] = c2 * np.r_[dV1, dV2]
-    ri, ci, vv, rhs = [], [], [], []
-    row = 0
-    for i in range(S):
-        for r in range(ns):
-            for c in range(2 * ns):
-                ri.append(row + r); ci.append(ns * i + c); vv.append(Jt[r, c, i])
-            for c in range(6):
-                ri.append(row + r); ci.append(iu + 3 * i + c); vv.append(Jt[r, 2 * ns + c, i])
-        rhs.extend(-d[:, i] - dtf[:, i] * p3)
-        row += ns
-    for k, s, dv, o in ((0, s0, dV1, 0), (n - 1, sf, dV2, 3)):
-        for j in range(6):
-            ri.append(row + j); ci.append(ns * k + j); vv.append(1.0)
-            if j >= 3:
-                ri.append(row + j); ci.append(iv + o + j - 3); vv.append(1.0)
-        rhs.extend(s - X[:6, k] - np.r_[0.0, 0.0, 0.0, dv])
-        row += 6
-    if ns == 7:
-        ri.append(row); ci.append(6); vv.append(1.0)
-        rhs.append(mass - X[6, 0])
-        row += 1
-    if not imp:
-        for j in range(6):
-            ri.append(row + j); ci.append(iv + j); vv.append(1.0)
-        rhs.extend(np.zeros(6))
-        row += 6
-    A = sp.csr_matrix((vv, (ri, ci)), shape=(row, nz))
-    K = sp.bmat([[sp.diags(2.0 * Q), A.T], [A, None]], format="csc")
-    r = np.concatenate([-2.0 * q, rhs])
-    D = np.ones(K.shape[0])
-    for _ in range(20):
-        Ks = sp.diags(D) @ K @ sp.diags(D)
-        D = D / np.sqrt(np.maximum(abs(Ks).max(axis=1).toarray().ravel(), 1e-300))
-    z = splu((sp.diags(D) @ K @ sp.diags(D)).tocsc()).solve(r * D) * D
-    return z[:ns * n].reshape(n, ns).T, z[iu:iv].reshape(n, 3).T
+    """The QP at fixed p (targets moved, defect + dtf p3): a frozen step of the sparse, refined host reference (qp_reference)."""
+    ref, _ = QR.QpSystem(Jt, t, imp, (DU / TU) ** 2).frozen(d + dtf * p3, X, U, s0, sf, mass, dV1, dV2)
+    return ref.dX, ref.dU
 
 
 @pytest.mark.gpu

@@ -8,6 +8,7 @@ import lowthrustopt_amd as lto
 from lowthrustopt_amd import drivers, synth
 
 import direct_helpers as DH
+import qp_reference as QR
 
 ISP, NSTEPS = 2000.0, 10
 
@@ -28,49 +29,9 @@ def _problems(n, ns, B, seed):
 
 
 def _host_qp_sparse(Jt, d, X, U, t, s0, sf, mass, dV1, dV2, imp):
-    """The same KKT system as drivers.direct_qp_dense, sparse, for the one large case."""
-    import scipy.sparse as sp
-    import scipy.sparse.linalg as spl
-    ns, _, S = Jt.shape
-    n = S + 1
-    nz = ns * n + 3 * n + 6
-    iu, iv = ns * n, ns * n + 3 * n
-    w = np.zeros(n)
-    w[:-1] += np.diff(t) / 2
-    w[1:] += np.diff(t) / 2
-    c2 = (lto.DU / lto.TU) ** 2
-    Q = np.r_[np.zeros(ns * n), np.repeat(w, 3), c2 * np.ones(6)]
-    q = np.r_[np.zeros(ns * n), (U * w[None, :]).T.reshape(-1), c2 * dV1, c2 * dV2]
-    rows, cols, vals, b = [], [], [], []
-    r0 = 0
-    for i in range(S):
-        for a in range(ns):
-            for c in range(2 * ns):
-                rows.append(r0 + a); cols.append(ns * i + c); vals.append(Jt[a, c, i])
-            for c in range(6):
-                rows.append(r0 + a); cols.append(iu + 3 * i + c); vals.append(Jt[a, 2 * ns + c, i])
-        b.extend(-d[:, i]); r0 += ns
-    for k, s, dv, o in ((0, s0, dV1, 0), (n - 1, sf, dV2, 3)):
-        for j in range(6):
-            rows.append(r0 + j); cols.append(ns * k + j); vals.append(1.0)
-            if j >= 3:
-                rows.append(r0 + j); cols.append(iv + o + j - 3); vals.append(1.0)
-        b.extend(s - X[:6, k] - np.r_[0, 0, 0, dv]); r0 += 6
-    if ns == 7:
-        rows.append(r0); cols.append(6); vals.append(1.0); b.append(mass - X[6, 0]); r0 += 1
-    if not imp:
-        for j in range(6):
-            rows.append(r0 + j); cols.append(iv + j); vals.append(1.0)
-        b.extend(np.zeros(6)); r0 += 6
-    A = sp.csr_matrix((vals, (rows, cols)), shape=(r0, nz))
-    K = sp.bmat([[sp.diags(2 * Q), A.T], [A, None]]).tocsc()
-    rhs = np.r_[-2 * q, b]
-    D = np.ones(K.shape[0])
-    for _ in range(20):
-        Ks = sp.diags(D) @ K @ sp.diags(D)
-        D = D / np.sqrt(np.maximum(abs(Ks).max(axis=1).toarray().ravel(), 1e-300))
-    z = spl.spsolve((sp.diags(D) @ K @ sp.diags(D)).tocsc(), rhs * D) * D
-    return z[:ns * n].reshape(n, ns).T, z[iu:iv].reshape(n, 3).T, (z[iv:iv + 6] if imp else np.zeros(6))
+    """The same KKT system as drivers.direct_qp_dense, sparse and refined (qp_reference), for the one large case."""
+    ref, _ = QR.QpSystem(Jt, t, imp, (lto.DU / lto.TU) ** 2).frozen(d, X, U, s0, sf, mass, dV1, dV2)
+    return ref.dX, ref.dU, ref.dV
 
 
 def _check_step(Jt, d, X, U, t, tgt, imp, dX, dU, dV, cost, dense=True):
