@@ -12,6 +12,9 @@ arrival phases tau1, tau2 (by at most 0.1 per step), so the transfer finds where
 starts from tau2 offset by --tau2-offset (default 0.02) from the stacked value and prints the final phases.
 --free-tf [days] also makes the time of flight a variable of the free iterations, at most `days` per step (default 1, the
 reference's bound; implies --free-ends 0 unless given): tf in [1 day, 40 days].
+--refine [tol_max] instead solves, refines the mesh on the device (lto_direct_refine, DESIGN 4.14: nodes removed while a segment's
+RKF7(8) estimate is below tol_max / 1000, segments bisected while one is above tol_max, default 1e-16) and solves again on the
+refined mesh; prints node counts and the largest estimate before and after, and the re-solve's status and iterations.
 """
 import importlib.util
 import os
@@ -78,6 +81,36 @@ def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100, free
     return res
 
 
+def refine_and_resolve(tol_max=1e-16, tol_min=None, max_nodes=120, maxIter=100, ctx=None, verbose=True):
+    """Solve on the demo's 30 nodes, refine the mesh of the solution in one device call, solve again on the refined mesh (one
+    lto_direct_solve call each).  Returns the figures it prints."""
+    ctx = ctx or lto.default_context(0)
+    tol_min = tol_max / 1000.0 if tol_min is None else tol_min
+    X, U, t, tau1, tau2, t0s, X0s, tfs, Xfs = demo_problem()
+    n, nsteps, Isp, mass = X.shape[1], 10, 2000.0, 1000.0
+
+    def solve(X, U, t, n):
+        out = drivers.multiShoot_CRTBP_direct(X, U, tau1, tau2, t, np.zeros(3), np.zeros(3), MU, DU, TU, n, nsteps, mass, Isp, t0s, X0s,
+                                              tfs, Xfs, False, False, 0.0, False, maxIter, verbose=False)
+        last = drivers.multiShoot_CRTBP_direct.last
+        return out[0], out[1], out[4], last["status"], last["iterations"], float(np.abs(out[7]).max())
+
+    X, U, t, st0, it0, d0 = solve(X, U, t, n)
+    _, e0 = lto.direct_defectCalc(X, U, t, nsteps, MU, DU, TU, Isp, ctx=ctx)
+    r = lto.direct_refine(X, U, t, nsteps, MU, DU, TU, Isp, tol_min, tol_max, max_nodes, ctx=ctx)
+    X2, U2, t2, st, it, d = solve(r.X, r.U, r.t, r.n)
+    _, e2 = lto.direct_defectCalc(X2, U2, t2, nsteps, MU, DU, TU, Isp, ctx=ctx)
+    res = {"n_before": n, "n_after": r.n, "n_removed": r.n_removed, "passes": r.passes, "refine_status": r.status, "tol_max": tol_max,
+           "max_error_before": float(e0.max()), "max_error_refined": float(r.errors.max()), "max_error_after": float(e2.max()),
+           "first_status": st0, "first_iterations": it0, "first_max_defect": d0, "status": st, "iterations": it, "max_defect": d}
+    if verbose:
+        print("direct: status %d after %d iterations on %d nodes, max defect %.2e, max estimate %.2e" % (st0, it0, n, d0, e0.max()))
+        print("refine (tol_min %.1e, tol_max %.1e): %d -> %d nodes (%d removed, %d insertion passes, status %d), max estimate %.2e"
+              % (tol_min, tol_max, n, r.n, r.n_removed, r.passes, r.status, r.errors.max()))
+        print("re-solve on %d nodes: status %d after %d iterations, max defect %.2e, max estimate %.2e" % (r.n, st, it, d, e2.max()))
+    return res
+
+
 def _arg(flag, default):
     """Value after `flag` (a number), the default if absent or not followed by a number, None if the flag is absent."""
     if flag not in sys.argv:
@@ -90,6 +123,9 @@ def _arg(flag, default):
 
 
 if __name__ == "__main__":
+    if "--refine" in sys.argv:
+        refine_and_resolve(tol_max=_arg("--refine", 1e-16))
+        sys.exit(0)
     free = _arg("--free-ends", 0.0)
     off = _arg("--tau2-offset", 0.02)
     if off is None:

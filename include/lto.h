@@ -220,6 +220,33 @@ int lto_direct_midpoints(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, con
                          const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm, double* x_mid,
                          double* defect, double* errors);
 
+/* Replaces meshRefine_direct (src/multiShoot_CRTBP_direct.jl:597-680) for n_batch trajectories in one call, on the device
+ * (DESIGN 4.14).  Inputs as lto_direct_defect.  Per trajectory, with the estimates of lto_direct_defect at `nsteps`:
+ *   removal    while n > 2 and min(errors) < tol_min: k = the first arg-min (0 becomes 1), node k is deleted;
+ *   insertion  while max(errors) > tol_max and n < max_nodes: in index order every segment with errors > tol_max is split, at
+ *              most max_nodes - n per pass: time t_i + (t_{i+1} - t_i)/2, state = lto_direct_midpoints' at nsteps = 2 (one
+ *              RKF7(8) step, the reference's ode7), control (u_i + u_{i+1})/2.
+ * Kept nodes, controls and times are bit copies; the first and the last node stay.  A segment whose propagated states are not
+ * numbers has a NaN estimate, which ends both phases for its trajectory.
+ *   max_nodes  the insertion's node limit AND the capacity of the outputs per trajectory (>= n_nodes)
+ *   X_out [nstate x max_nodes x n_batch], U_out [3 x max_nodes x n_batch] or NULL, t_out [max_nodes x n_batch]: the first
+ *              n_out[b] columns of trajectory b, NaN from there on
+ *   errors_out [(max_nodes-1) x n_batch] or NULL: the estimates of the final mesh (n_out[b] - 1 of them, then NaN)
+ *   n_removed, passes (insertion passes), status [n_batch], each or NULL.  status: 0 refined (min >= tol_min or two nodes
+ *              left, and max <= tol_max), 1 stopped at max_nodes with max > tol_max, 2 a NaN estimate.
+ * Limits (LTO_EINVAL beyond them): n_batch <= 65535 and max_nodes * n_batch * nstate <= 2^31 - 1.  The call's device scratch is
+ * about 37 doubles per node of capacity (max_nodes * n_batch); the whole capacity is filled and copied back, so give
+ * max_nodes as a limit near the size expected, not as "unbounded". */
+int lto_direct_refine_batch(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, const double* X, const double* U,
+                            const double* t, int n_tgrids, int nsteps, const lto_direct_params* prm, double tol_min,
+                            double tol_max, int max_nodes, double* X_out, double* U_out, double* t_out, int* n_out,
+                            int* n_removed, int* passes, int* status, double* errors_out);
+/* One trajectory (n_batch = 1). */
+int lto_direct_refine(lto_ctx* ctx, int nstate, int n_nodes, const double* X, const double* U, const double* t, int nsteps,
+                      const lto_direct_params* prm, double tol_min, double tol_max, int max_nodes, double* X_out,
+                      double* U_out, double* t_out, int* n_out, int* n_removed, int* passes, int* status,
+                      double* errors_out);
+
 /* Replaces jacobianCalc of multiShoot_CRTBP_direct (:111-143) and the tf partial (:503-516).
  *   Jac_temp    [nstate x nvar x (n_nodes-1) x n_batch], nvar = 2(nstate+3); block i is
  *               d defect_i / d [x_i; x_{i+1}; u_i; u_{i+1}] (variable order of :125), computed from

@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, addTimeFinal, tf_sweep, meshRefine_indirect, remesh_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_qp_step, direct_solve, direct_end_states, direct_qp_step_free, direct_solve_free,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_qp_step, direct_solve, direct_end_states, direct_qp_step_free, direct_solve_free,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -365,6 +365,31 @@ function direct_midpoints(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix
                ctx.handle, nstate, n_nodes, 1, X_all, u_all, t_TU, 1, nsteps, prm, x_mid, defect1, errors)
     check(ctx, rc)
     (x_mid, defect1, errors)
+end
+
+"""meshRefine_direct (direct.jl:597-680) in one library call with the trajectory resident on the GPU (`lto_direct_refine`,
+DESIGN 4.14): nodes are removed while the smallest RKF7(8) estimate is below `tol_min`, then segments are bisected while the
+largest is above `tol_max` and the mesh has fewer than `max_nodes` nodes.  Returns (X_all, u_all, t_TU, n_nodes) as the
+reference does, then (n_removed, passes, status, errors): status 0 refined, 1 stopped at `max_nodes`, 2 a NaN estimate."""
+function direct_refine(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Float64}, t_TU::Vector{Float64},
+                       nstate, n_nodes, nsteps, Isp, MU, DU, TU; tol_min = 1e-20, tol_max = 1e-18, max_nodes = 4 * n_nodes)
+    X_out = zeros(nstate, max_nodes)
+    U_out = zeros(3, max_nodes)
+    t_out = zeros(max_nodes)
+    errors = zeros(max_nodes - 1)
+    n_out = Ref{Cint}(0)
+    n_removed = Ref{Cint}(0)
+    passes = Ref{Cint}(0)
+    status = Ref{Cint}(0)
+    prm = Ref(LtoDirectParams(MU, DU, TU, Isp))
+    rc = ccall((:lto_direct_refine, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ref{LtoDirectParams}, Cdouble, Cdouble, Cint,
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cint}, Ref{Cint}, Ref{Cint}, Ref{Cint}, Ptr{Cdouble}),
+               ctx.handle, nstate, n_nodes, X_all, u_all, t_TU, nsteps, prm, tol_min, tol_max, max_nodes, X_out, U_out, t_out,
+               n_out, n_removed, passes, status, errors)
+    check(ctx, rc)
+    n = Int(n_out[])
+    (X_out[:, 1:n], U_out[:, 1:n], t_out[1:n], n, Int(n_removed[]), Int(passes[]), Int(status[]), errors[1:n-1])
 end
 
 """jacobianCalc + tf partial of multiShoot_CRTBP_direct: Jac_full [nstate(n_nodes-1) x n_nodes(nstate+3)+1]

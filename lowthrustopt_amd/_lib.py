@@ -99,6 +99,11 @@ SIGNATURES = {
                                       C.POINTER(LtoDirectParams), _vp, _vp, _vp, _vp]),
     "lto_direct_midpoints": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int,
                                        C.POINTER(LtoDirectParams), _vp, _vp, _vp]),
+    "lto_direct_refine_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int,
+                                          C.POINTER(LtoDirectParams), C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp]),
+    "lto_direct_refine": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams), C.c_double,
+                                    C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_group_create": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(_vp)]),
     "lto_group_destroy": (None, [_vp]),
     "lto_group_last_error": (C.c_char_p, [_vp]),

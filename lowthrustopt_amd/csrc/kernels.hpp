@@ -133,6 +133,31 @@ hipError_t launch_direct_jacobian(int nstate, const DirectArgs& a, hipStream_t s
 // base wave + one wave per sensitivity column for 32 segments, skewed by one RKF7(8) step (one barrier per step)
 hipError_t launch_direct_jacobian_pipe(int nstate, const DirectArgs& a, hipStream_t st);
 
+// Errors-driven mesh refinement of the direct transcription (kernels_direct_refine.hip).  All arrays node-major:
+// the input as the caller passes it, the working copies with max_nodes (M) nodes of room per trajectory.
+constexpr int kRefineLdsNodes = 1024;        // nodes whose estimates and links the removal's workgroup keeps in LDS (16 KB)
+enum RefineCtl { RC_N, RC_CUR, RC_ACTIVE, RC_STATUS, RC_NSPLIT, RC_REMOVED, RC_PASSES, RC_ROWS };   // rows of ctl [RC_ROWS][B]
+struct DirectRefineArgs {
+  const double* X_in;              // [B][n_in][nstate]
+  const double* U_in;              // [B][n_in][3]
+  const double* t_in; int t_in_stride;   // [n_in] per trajectory (stride 0: one grid for all)
+  int n_in, M, B;
+  double MU, kk, isp_g0, TU;       // as DirectArgs
+  int half_steps;
+  double tol_min, tol_max;
+  double *X[2], *U[2], *t[2], *E[2];   // working copies [B][M][nstate], [B][M][3], [B][M], [B][M] (E_i: estimate of segment i)
+  double* E0;                      // [B][n_in] estimates of the input mesh
+  int* ctl;                        // [RC_ROWS][B]: node count, current copy, in the insertion loop, status, splits of this pass, removed, passes
+  int* list;                       // [B][M] segments split in this pass, in order
+  double* rm_est; int* rm_link;    // removal above kRefineLdsNodes nodes: [B][n_in], [B][2][n_in]; else null
+  double *X_out, *U_out, *t_out, *E_out;   // [B][M][nstate], [B][M][3], [B][M], [B][M-1]: NaN beyond the node count
+};
+// estimates of the input + the whole removal phase + compaction into copy 0
+hipError_t launch_direct_refine_begin(int nstate, const DirectRefineArgs& a, hipStream_t st);
+// one insertion pass; max_split: upper bound of the splits of one trajectory in this pass (sizes the evaluation's grid)
+hipError_t launch_direct_refine_pass(int nstate, const DirectRefineArgs& a, int max_split, hipStream_t st);
+hipError_t launch_direct_refine_finish(int nstate, const DirectRefineArgs& a, hipStream_t st);
+
 // QP step of the direct method on the device (kernels_direct_qp.hip): the KKT system as a block-bidiagonal BVP, structured
 // orthogonal cyclic reduction.  Operands in the SoA layouts of the direct sweeps; targets [n_batch][19] (lto_direct_targets).
 struct DirectQpArgs {

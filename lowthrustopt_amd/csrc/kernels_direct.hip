@@ -12,18 +12,9 @@
 // derivative of the discrete map.  Column index = blockIdx.y (wave-uniform).
 #include "kernels.hpp"
 #include "rk.hpp"
+#include "direct_segment.hpp"
 
 namespace lto {
-
-template <int NS>
-struct SysDirect {
-  static constexpr int DIM = NS;
-  DirectLane L;
-  __device__ __forceinline__ void rhs(const double (&x)[NS], double (&k)[NS]) const {
-    VarCoef6 vc;
-    rhs_direct<NS, false>(x, L, k, vc);
-  }
-};
 
 // base (NS) + one sensitivity column (NS)
 template <int NS>
@@ -61,17 +52,8 @@ __device__ __forceinline__ void direct_setup(const DirectArgs& a, int& s, int& d
 #pragma unroll
   for (int c = 0; c < NS; ++c) x[c] = a.X[c * a.ldx + node];
   if (dir) { x[3] = -x[3]; x[4] = -x[4]; x[5] = -x[5]; }     // reverse velocity        (direct.jl:92)
-  const double td = dir ? -1.0 : 1.0;
-  L.MU = a.MU;
-  L.w2 = 2.0 * td;
-  L.cx = a.U[0 * a.ldu + node]; L.cy = a.U[1 * a.ldu + node]; L.cz = a.U[2 * a.ldu + node];
-  L.kk = a.kk;
-  { const double k6 = L.kk * 1e-3; L.tx = L.cx * k6; L.ty = L.cy * k6; L.tz = L.cz * k6; }   // NS = 6: control * kk / 1000.0
-  nc = sqrt(__builtin_fma(L.cx, L.cx, __builtin_fma(L.cy, L.cy, L.cz * L.cz)));
-  L.mdot = -td * nc / a.isp_g0 * a.TU;                       // prop_EP_deriv.jl:42
+  direct_lane(DirectConsts{a.MU, a.kk, a.isp_g0, a.TU}, dir, a.U[0 * a.ldu + node], a.U[1 * a.ldu + node], a.U[2 * a.ldu + node], L, nc);
 }
-
-__device__ __forceinline__ double xchg1(double v) { return __shfl_xor(v, 1); }
 
 // K3: defect + RKF7(8) error estimate.
 template <int NS>
@@ -80,21 +62,9 @@ __global__ __launch_bounds__(64) void k_direct_defect(const DirectArgs a) {
   double x[NS];
   SysDirect<NS> sys;
   direct_setup<NS>(a, s, dir, hhalf, span_total, x, sys.L, nc);
-  const double h = hhalf / (double)a.half_steps;
-  double maxErr = 0.0;
-  for (int k = 0; k < a.half_steps; ++k) {
-    double xn[NS];
-    const double delta = rkf78_step<SysDirect<NS>, NS>(sys, h, x, xn);
-    maxErr = fmax(maxErr, delta);
-#pragma unroll
-    for (int c = 0; c < NS; ++c) x[c] = xn[c];
-  }
-  if (dir) { x[3] = -x[3]; x[4] = -x[4]; x[5] = -x[5]; }     // direct.jl:98
+  double d[NS], e;
+  direct_segment<NS>(sys, dir, hhalf, a.half_steps, x, d, e);
   const bool active = s < a.S;   // recomputed here: no per-lane boolean is kept live across the integrator
-  double d[NS];
-#pragma unroll
-  for (int c = 0; c < NS; ++c) d[c] = x[c] - xchg1(x[c]);    // fwd lane: state_for - stateF_back  (:101)
-  const double e = fmax(maxErr, xchg1(maxErr));              // :104
   if (active && dir == 0) {
     if (a.mid) {                                             // node meshRefine_direct inserts (direct.jl:651-660)
 #pragma unroll

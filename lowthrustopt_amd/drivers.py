@@ -908,7 +908,7 @@ def meshRefine_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass, thrustLimit, p,
 
 
 def meshRefine_direct(X_all, u_all, t_TU, nstate, n_nodes, nsteps, Isp, MU, DU, TU, tol_min=1e-20, tol_max=1e-18,
-                      max_nodes=1 << 20, batched=True, ops=None, verbose=True):
+                      max_nodes=1 << 20, batched=True, ops=None, verbose=True, device=False):
     """Errors-driven mesh refinement of the direct transcription (direct.jl:597-680): nodes are removed while the
     smallest RKF7(8) error estimate of a segment is below tol_min, then segments are bisected while the largest is above
     tol_max (new state = forward propagation to the segment's middle, new control = mean of its two controls).
@@ -921,7 +921,27 @@ def meshRefine_direct(X_all, u_all, t_TU, nstate, n_nodes, nsteps, Isp, MU, DU, 
     batched=True bisects EVERY segment above tol_max in one pass: one error sweep + one mid-point sweep on the GPU per
     pass instead of one full sweep per inserted node.  The result is identical to the reference's one-node-per-pass
     loop, because a segment's error estimate depends only on its own two nodes, controls and times (direct.jl:77-105),
-    so splitting one segment never changes the decision for another; batched=False runs the literal loop."""
+    so splitting one segment never changes the decision for another; batched=False runs the literal loop.
+
+    device=True (with ops=None) runs both phases in ONE library call with the trajectory resident on the GPU
+    (lto_direct_refine) instead of one or two round trips per removed node / insertion pass; same result and the
+    same 4-tuple.  The call allocates, fills and returns its whole capacity, so the driver does not hand it max_nodes as it
+    stands: it starts with room for max(8 n_nodes, 1 024) nodes and, only if the refinement stops at that room while
+    max_nodes allows more, repeats the call from the input with eight times the room.  A call that does not reach its
+    capacity gives the mesh of any larger capacity, so the result is that of max_nodes itself."""
+    if device and ops is None:
+        limit = max(int(max_nodes), int(n_nodes))
+        room = min(limit, max(8 * int(n_nodes), 1024))
+        while True:
+            r = hotpath.direct_refine(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, tol_min, tol_max, room)
+            if r.status != 1 or room >= limit:
+                break
+            room = min(limit, 8 * room)
+        if verbose:
+            print("Starting with %d nodes." % n_nodes)
+            print("Removed %d nodes, added %d in %d passes (status %d). Now have %d nodes."
+                  % (r.n_removed, r.n - (int(n_nodes) - r.n_removed), r.passes, r.status, r.n))
+        return r.X, r.U, r.t, r.n
     ops = ops or HipDirectOps(MU, DU, TU, Isp)
     X = np.array(X_all, dtype=np.float64, order="F")
     U = np.array(u_all, dtype=np.float64, order="F")

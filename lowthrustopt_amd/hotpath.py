@@ -598,6 +598,52 @@ def direct_midpoints(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None):
     return x_mid, defect, errors
 
 
+DirectRefine = collections.namedtuple("DirectRefine", "X U t n n_removed passes status errors")
+
+
+def direct_refine(X, U, t, nsteps, MU, DU, TU, Isp, tol_min, tol_max, max_nodes, ctx=None):
+    """Errors-driven mesh refinement of the direct transcription on the device (lto_direct_refine_batch):
+    meshRefine_direct for X [nstate x n] or [nstate x n x B], U [3 x n (x B)], t [n] or [n x B] in ONE library call -- nodes are
+    removed while the smallest RKF7(8) estimate is below tol_min, then segments are bisected while the largest is above tol_max
+    and the mesh has fewer than max_nodes nodes.  Returns DirectRefine(X [nstate x n'], U [3 x n'], t [n'], n = n', n_removed,
+    passes, status (0 refined, 1 stopped at max_nodes, 2 a NaN estimate), errors [n' - 1] of the final mesh), or a list of
+    them, one per trajectory, for a batched input (the node counts differ)."""
+    X = _f64(X)
+    U = _f64(U)
+    ns, n, B, batched = _batch_dims(X)
+    if ns not in (6, 7):
+        raise ValueError("direct_refine: X must have 6 or 7 rows; got shape %s" % (X.shape,))
+    if n < 2:
+        raise ValueError("direct_refine: need at least two nodes")
+    if U.shape != ((3, n, B) if batched else (3, n)):
+        raise ValueError("direct_refine: U must be [3 x n_nodes] or [3 x n_nodes x n_batch], as X; got shape %s" % (U.shape,))
+    tt, ntg = _tgrids(t, n, B)
+    nsteps, M = int(nsteps), int(max_nodes)
+    if nsteps < 2:
+        raise LtoError(-1, "direct_refine: nsteps must be >= 2")
+    if M < n:
+        raise LtoError(-1, "direct_refine: max_nodes is the capacity of the result: it must be >= n_nodes")
+    tol_min, tol_max = float(tol_min), float(tol_max)
+    if np.isnan(tol_min) or np.isnan(tol_max):
+        raise LtoError(-1, "direct_refine: a tolerance is NaN")
+    ctx = ctx or default_context()
+    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    Xo = np.empty((ns, M, B), order="F")
+    Uo = np.empty((3, M, B), order="F")
+    to = np.empty((M, B), order="F")
+    eo = np.empty((M - 1, B), order="F")
+    n_out, n_rem, passes, status = (np.zeros(B, dtype=np.int32) for _ in range(4))
+    ctx.check(ctx.fn("direct_refine_batch")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(tt), ntg, nsteps, C.byref(prm), tol_min,
+                                            tol_max, M, _ptr(Xo), _ptr(Uo), _ptr(to), _ptr(n_out), _ptr(n_rem), _ptr(passes),
+                                            _ptr(status), _ptr(eo)))
+    out = []
+    for b in range(B):
+        k = int(n_out[b])
+        out.append(DirectRefine(np.asfortranarray(Xo[:, :k, b]), np.asfortranarray(Uo[:, :k, b]), to[:k, b].copy(), k, int(n_rem[b]),
+                                int(passes[b]), int(status[b]), eo[:k - 1, b].copy()))
+    return out if batched else out[0]
+
+
 def direct_jacobian_blocks(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None, out=None):
     """Compact direct Jacobian: (Jac_temp[nstate x nvar x (n-1)], ddefect_dtf[nstate x (n-1)], defect, errors);
     nvar = 2(nstate+3), variable order [x_i; x_{i+1}; u_i; u_{i+1}] (:125).  out = (Jac_temp, ddefect_dtf, defect, errors):
