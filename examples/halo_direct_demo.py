@@ -15,6 +15,10 @@ reference's bound; implies --free-ends 0 unless given): tf in [1 day, 40 days].
 --refine [tol_max] instead solves, refines the mesh on the device (lto_direct_refine, DESIGN 4.14: nodes removed while a segment's
 RKF7(8) estimate is below tol_max / 1000, segments bisected while one is above tol_max, default 1e-16) and solves again on the
 refined mesh; prints node counts and the largest estimate before and after, and the re-solve's status and iterations.
+--ballistic-guess takes the guess from drivers.stacked_guess instead: the reference's own construction (demo :116-157), 10 days
+ballistically on each orbit, made in one device call (lto_stack_guess_batch).
+--multi-start N runs N departure phases tau1 evenly spread over [0, 1) side by side (drivers.multiStart_direct: the guesses, the
+end targets and the solves are one device call each) and prints the ranking of the converged starts by cost.
 """
 import importlib.util
 import os
@@ -37,12 +41,17 @@ def _stacking():
     return mod
 
 
-def demo_problem(n_nodes=30, tof_days=20.0, tau1=0.75):
+def demo_problem(n_nodes=30, tof_days=20.0, tau1=0.75, ballistic=False):
     """(X_all [6 x n], u_all [3 x n], t_TU, tau1, tau2, X0_times, X0_states, Xf_times, Xf_states): the stacked guess and the two
-    orbit tables on normalised times LinRange(0, 1, 100) (demo :68-71).  tau2 = the phase of orbit 2 the stacking joins."""
-    X, t = _stacking().stacked_guess(n_nodes, tof_days, tau1)
+    orbit tables on normalised times LinRange(0, 1, 100) (demo :68-71).  tau2 = the phase of orbit 2 the stacking joins.
+    ballistic: the guess and tau2 of drivers.stacked_guess (half of tof_days on each orbit) instead of the table interpolation."""
     tabs = synth.halo_orbits()
     times = [np.linspace(0.0, 1.0, tb.shape[1]) for tb in tabs]
+    if ballistic:
+        tof = 0.5 * tof_days * lto.day / TU
+        X, t, tau1, tau2 = drivers.stacked_guess(n_nodes, tof, tof, tau1, times[0], tabs[0], times[1], tabs[1], MU)
+        return X, np.zeros((3, n_nodes)), t, tau1, tau2, times[0], tabs[0], times[1], tabs[1]
+    X, t = _stacking().stacked_guess(n_nodes, tof_days, tau1)
     # phase of the guess's last node on orbit 2 (find_tau, demo :151): nearest table sample, refined on a fine grid
     taus = np.linspace(0.0, 1.0, 20001)
     d = np.linalg.norm(synth.halo_state(1, taus * 99 * synth.HALO_DT[1]) - X[:, -1:], axis=0)
@@ -51,9 +60,10 @@ def demo_problem(n_nodes=30, tof_days=20.0, tau1=0.75):
     return X, U, t, tau1, tau2, times[0], tabs[0], times[1], tabs[1]
 
 
-def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100, free_ends=None, tau2_offset=0.0, free_tf=None):
+def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100, free_ends=None, tau2_offset=0.0, free_tf=None,
+         ballistic=False):
     ctx = lto.default_context(0)
-    X, U, t, tau1, tau2, t0s, X0s, tfs, Xfs = demo_problem()
+    X, U, t, tau1, tau2, t0s, X0s, tfs, Xfs = demo_problem(ballistic=ballistic)
     tau2 += tau2_offset
     n, nsteps, Isp, mass = X.shape[1], 10, 2000.0, 1000.0
     ops = drivers.HipDirectOps(MU, DU, TU, Isp, ctx) if python_loop else None
@@ -111,6 +121,23 @@ def refine_and_resolve(tol_max=1e-16, tol_min=None, max_nodes=120, maxIter=100, 
     return res
 
 
+def multi_start(n_starts, n_nodes=30, tof_days=20.0, maxIter=100, verbose=True):
+    """n_starts departure phases over [0, 1), the demo's setting otherwise (flagEnd = false); returns drivers.multiStart_direct's dict."""
+    tabs = synth.halo_orbits()
+    times = [np.linspace(0.0, 1.0, tb.shape[1]) for tb in tabs]
+    tof = 0.5 * tof_days * lto.day / TU
+    tau1s = np.arange(int(n_starts)) / float(n_starts)
+    t0 = time.perf_counter()
+    m = drivers.multiStart_direct(tau1s, tof, tof, n_nodes, 10, 1000.0, 2000.0, times[0], tabs[0], times[1], tabs[1], MU, DU, TU,
+                                  flagEnd=False, maxIter=maxIter)
+    if verbose:
+        print("multi-start: %d starts, %d converged (%.2f s)" % (tau1s.size, m["order"].size, time.perf_counter() - t0))
+        for rank, b in enumerate(m["order"]):
+            print("  %2d. tau1 = %.4f, tau2 = %.3f, cost %.6f, %d iterations, max defect %.2e, junction gap %.3e" % (
+                rank + 1, m["tau"][0, b], m["tau"][1, b], m["cost"][b], m["iterations"][b], m["max_defect"][b], m["gap"][0, b]))
+    return m
+
+
 def _arg(flag, default):
     """Value after `flag` (a number), the default if absent or not followed by a number, None if the flag is absent."""
     if flag not in sys.argv:
@@ -126,6 +153,9 @@ if __name__ == "__main__":
     if "--refine" in sys.argv:
         refine_and_resolve(tol_max=_arg("--refine", 1e-16))
         sys.exit(0)
+    if "--multi-start" in sys.argv:
+        multi_start(int(_arg("--multi-start", 8)))
+        sys.exit(0)
     free = _arg("--free-ends", 0.0)
     off = _arg("--tau2-offset", 0.02)
     if off is None:
@@ -134,4 +164,4 @@ if __name__ == "__main__":
     if free_tf is not None and free is None:
         free = 0.0                                        # a free tf moves on the free-end iterations
     main(verbose="-q" not in sys.argv, then_indirect="--then-indirect" in sys.argv, python_loop="--python-loop" in sys.argv,
-         free_ends=free, tau2_offset=off, free_tf=free_tf)
+         free_ends=free, tau2_offset=off, free_tf=free_tf, ballistic="--ballistic-guess" in sys.argv)

@@ -335,6 +335,21 @@ int lto_indirect_add_time(lto_ctx* ctx, int ndim, int n_nodes, const double* XC,
                           const lto_integrator* integ, const lto_direct_orbits* orbits, double dt, int n_desired,
                           int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
                           double* defect, int* status_flag, int* iterations, double* history, double* cost);
+/* Trajectory-stacking initial guesses (CRTBP_Multishoot_direct_demo.jl:116-157) for n_batch starts side by side,
+ * start b given by tau1[b] (phase on the departure table), tof1[b] and tof2[b] (TU, > 0).  Per start: t_out = LinRange(0, tof1 +
+ * tof2, n_nodes); the nodes with t_k < tof1 are the ballistic CRTBP flow (mass ratio MU) of the departure spline at tau1, node 0
+ * that state itself; the flow is carried on to tof1, tau2_0 = find_tau of that point on the arrival table (the first minimiser
+ * of |s(j / 1000) - x|_2 over j = 0..1000) and the nodes with t_k >= tof1 are the flow of the arrival spline at tau2_0 over
+ * t_k - tof1; tau2 = find_tau of node n-1, which is then replaced by the arrival spline at tau2.  The flow goes from node to node,
+ * every advance a fresh start of the integrator: LTO_DOP853_ADAPTIVE at integ's rtol / atol / max_steps, or LTO_RK4 with
+ * integ->steps steps per advance (any other method: LTO_EUNSUPPORTED).  Outputs: X_out [6 x n_nodes x n_batch], t_out [n_nodes x
+ * n_batch], tau_out [3 x n_batch] = (tau1 wrapped into [0, 1]; tau2_0; tau2), gap_out [2 x n_batch] = the two distances find_tau
+ * minimised (may be NULL), status [n_batch]: 0, or 2 if a node is not finite (max_steps used up: its nodes are NaN).
+ * LTO_EINVAL: n_nodes < 2, n_batch < 1, a tof not finite or <= 0, a tau1 not finite or |tau1| >= 1e6, MU outside (0, 1), a table
+ * with fewer than 2 samples, 6 n_nodes n_batch > 2^31 - 1. */
+int lto_stack_guess_batch(lto_ctx* ctx, int n_nodes, int n_batch, double MU, const lto_direct_orbits* orbits,
+                          const lto_integrator* integ, const double* tau1, const double* tof1, const double* tof2, double* X_out,
+                          double* t_out, double* tau_out, double* gap_out, int* status);
 /* Mesh re-distribution of converged 12-dim solutions (the indirect method's counterpart of meshRefine_direct): the
  * nodes of XC [12 x n_nodes x n_batch] on t [n_nodes x n_tgrids] (n_tgrids = 1 or n_batch) are moved, and their number changed to
  * n_new, so that every new segment carries the same share of a per-segment monitor w_i > 0.  Per trajectory:

@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, addTimeFinal, tf_sweep, meshRefine_indirect, remesh_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_qp_step, direct_solve, direct_end_states, direct_qp_step_free, direct_solve_free,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_qp_step, direct_solve, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -469,6 +469,28 @@ function direct_end_states(ctx::LtoContext, τ1, τ2, X0_times::Vector{Float64},
     end
     check(ctx, rc)
     (s[1:6], s[7:12], model[])
+end
+
+# The trajectory-stacking initial guess of the reference demos (CRTBP_Multishoot_direct_demo.jl:116-157) for B starts side by side
+# (`lto_stack_guess_batch`, DESIGN 4.15): per start tof1 TU ballistically on the departure orbit from phase tau1, the closest point
+# of the arrival orbit (find_tau), tof2 TU ballistically from there, n_nodes samples over LinRange(0, tof1 + tof2, n_nodes), the last
+# one snapped onto the arrival orbit.  Returns (X [6 x n_nodes x B], t [n_nodes x B], tau [3 x B] = (tau1 wrapped; tau2 at the
+# junction; tau2 at the end), gap [2 x B], status [B]).
+function stack_guess(ctx::LtoContext, tau1::Vector{Float64}, tof1::Vector{Float64}, tof2::Vector{Float64}, n_nodes::Integer,
+                     X0_times::Vector{Float64}, X0_states::Matrix{Float64}, Xf_times::Vector{Float64}, Xf_states::Matrix{Float64},
+                     MU; integ::LtoIntegrator = LtoIntegrator())
+    B = length(tau1)
+    (length(tof1) == B && length(tof2) == B) || error("stack_guess: tau1, tof1 and tof2 need one entry per start")
+    X = zeros(6, n_nodes, B); t = zeros(n_nodes, B); tau = zeros(3, B); gap = zeros(2, B); status = zeros(Cint, B)
+    rc = GC.@preserve X0_times X0_states Xf_times Xf_states begin
+        ob = Ref(_orbits(X0_times, X0_states, Xf_times, Xf_states))
+        ccall((:lto_stack_guess_batch, liblto), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cdouble, Ref{LtoDirectOrbits}, Ref{LtoIntegrator}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+               Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+              ctx.handle, n_nodes, B, Float64(MU), ob, Ref(integ), tau1, tof1, tof2, X, t, tau, gap, status)
+    end
+    check(ctx, rc)
+    (X, t, tau, gap, Int.(status))
 end
 
 # optimizeTraj with flagEnd = true: one Jacobian sweep and the exact free-end QP step.  Returns (x_update, u_update, p1_update,

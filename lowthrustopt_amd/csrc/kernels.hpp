@@ -214,6 +214,41 @@ hipError_t launch_find_tau(const EndOrbitsDev& o, double* G, long ldg, int n, in
 // cost [K]: trapezoid over td of umag(|lambda_v|) along the dense outputs Y (layout as RemeshArgs), p / rho / aL of the control law
 hipError_t launch_dense_cost(const double* Y, long ldy, const double* td, int m, int K, double aL, double p, double rho, double* cost,
                              hipStream_t st);
+// Stacked initial guesses (kernels_stack.hip), B starts side by side.  The device keeps everything per start as
+// struct-of-arrays over the starts -- element (row, b) of an [R][B] array at row * B + b -- so a wavefront's 64 starts move lines.
+constexpr int kStackCand = 1001;             // find_tau's candidates j / 1000
+constexpr int kStackCandLd = 1024;           // leading dimension of the candidate table [6][kStackCandLd]
+// Candidate table of the arrival orbit, cand [6][kStackCandLd] = s(j / 1000), and the start states y0 [6][B] = the departure
+// spline at tau1 [B]
+hipError_t launch_stack_prepare(const EndOrbitsDev& o, const double* tau1, int B, double* cand, double* y0, hipStream_t st);
+// One ballistic coast per start: from y0 [6][B] at time t_start[b] through the nodes k0[b] <= k < k1[b] of its grid t [n][B], every
+// node-to-node advance a fresh start of the integrator, the nodes into X [6 n][B] (row q n + k); then on to t_end[b], the state
+// there into xe [6][B].  t_start / t_end null: 0 / the time of the last node.
+struct StackArcArgs {
+  const double* y0;
+  const double* t;
+  const int* k0; const int* k1;              // null k0: 0; null k1: n
+  const double* t_start; const double* t_end;
+  int n, B;
+  double MU;
+  int steps;                                 // RK4
+  double rtol, atol; int max_steps;          // DOP853
+  double* X;
+  double* xe;
+};
+hipError_t launch_stack_arc(int method, const StackArcArgs& a, hipStream_t st);
+// find_tau of the points x [6][B] over the candidate table: tau [B] = j* / 1000, gap [B] = the smallest distance, snap [6][B] =
+// the arrival spline at tau (snap may be null).  With X_out set (the end search) the workgroup of start b also writes the start's
+// nodes, X [6 n][B] with node n - 1 replaced by the snap, to X_out [B][n][6] and status[b] = 2 if any of them is not finite, else 0.
+struct StackFindArgs {
+  EndOrbitsDev o;
+  const double* cand;
+  const double* x;
+  int n, B;
+  double* tau; double* gap; double* snap;
+  const double* X; double* X_out; int* status;
+};
+hipError_t launch_stack_find(const StackFindArgs& f, hipStream_t st);
 // Mesh equidistribution of the indirect method (kernels_remesh.hip).  Grid: per trajectory b the monitor of old segment
 // i is w[b (n-1) + i], or nacc + nrej there when w is null; old grids t[b t_stride + i].
 // Out: t_out [n_batch][n_new] and seg_of [n_batch][n_new], the old node each new one is propagated from.

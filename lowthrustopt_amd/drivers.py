@@ -758,6 +758,46 @@ def multiShoot_CRTBP_direct(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, 
     return out
 
 
+def stacked_guess(n_nodes, tof1, tof2, τ1, X0_times, X0_states, Xf_times, Xf_states, MU, ctx=None):
+    """The trajectory-stacking initial guess of the reference demos (CRTBP_Multishoot_direct_demo.jl:116-157) as one function and
+    one library call (lto_stack_guess_batch): tof1 TU ballistically on the departure orbit from phase τ1, the closest
+    point of the arrival orbit, tof2 TU ballistically from there, n_nodes samples over LinRange(0, tof1 + tof2, n_nodes), the last
+    one snapped onto the arrival orbit.  Returns (X_all [6 x n_nodes], t_TU, τ1 (wrapped into [0, 1]), τ2 (the phase of the last
+    node)).  The full record of the call is kept in `stacked_guess.last` (hotpath.StackGuess)."""
+    g = hotpath.stack_guess(float(τ1), float(tof1), float(tof2), n_nodes, (X0_times, X0_states, Xf_times, Xf_states), MU=MU, ctx=ctx)
+    stacked_guess.last = g
+    return g.X, g.t, g.tau1, g.tau2
+
+
+def multiStart_direct(τ1s, tof1s, tof2s, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times, Xf_states, MU, DU, TU,
+                      flagEnd=False, β=0.0, allowImpulsive=False, maxIter=100, ctx=None):
+    """A multi-start search of the direct method in three library calls: the stacked guesses of all starts (τ1s, tof1s, tof2s:
+    scalars or arrays, broadcast to B starts; hotpath.stack_guess), their end targets at (τ1, τ2) (hotpath.direct_end_states) and
+    the loop of multiShoot_CRTBP_direct for all of them side by side on their own grids, zero thrust as the guess
+    (hotpath.direct_solve_free).  Returns a dict of per-start arrays: status [B], iterations [B], max_defect [B], cost [B] (of the
+    last iteration; NaN where none ran), tau [2 x B] (final τ1; τ2), tau_guess [3 x B] (τ1; τ2 at the junction; τ2 at the end),
+    gap [2 x B], guess_status [B], X [6 x n x B], U [3 x n x B], t [n x B], dV [6 x B], defect, history [5 x maxIter x B], and
+    order: the indices of the status-0 starts by increasing cost."""
+    orbits = hotpath.DirectOrbits(X0_times, X0_states, Xf_times, Xf_states)
+    τ1s, tof1s, tof2s = (np.ascontiguousarray(v) for v in np.broadcast_arrays(
+        *(np.asarray(v, dtype=np.float64).reshape(-1) for v in (τ1s, tof1s, tof2s))))
+    g = hotpath.stack_guess(τ1s, tof1s, tof2s, n_nodes, orbits, MU=MU, ctx=ctx)
+    B = g.status.size
+    tau = np.asfortranarray(np.vstack([g.tau1, g.tau2]))
+    s0, sf, _, _, _, _ = hotpath.direct_end_states(tau, orbits, ctx=ctx)
+    targets = [hotpath.direct_targets(s0[:, b], sf[:, b], mass, np.zeros(3), np.zeros(3)) for b in range(B)]
+    U0 = np.zeros((3, int(n_nodes), B), order="F")
+    X, U, dV, t, defect, tau_out, status, iters, hist = hotpath.direct_solve_free(
+        g.X, U0, g.t, nsteps, MU, DU, TU, Isp, orbits, targets, tau, β, flagEnd, allowImpulsive, maxIter, ctx=ctx)
+    last = np.minimum(iters, hist.shape[1])               # a start that reached maxIter reports a count past it
+    cost = np.array([hist[1, last[b] - 1, b] if last[b] > 0 else np.nan for b in range(B)])
+    ok = np.flatnonzero(status == 0)
+    order = ok[np.argsort(cost[ok], kind="stable")]
+    return {"status": status, "iterations": iters, "max_defect": np.abs(defect).max(axis=(0, 1)), "cost": cost, "tau": tau_out,
+            "tau_guess": np.vstack([g.tau1, g.tau2_0, g.tau2]), "gap": g.gap, "guess_status": g.status, "X": X, "U": U, "t": t,
+            "dV": dV, "defect": defect, "history": hist, "order": order}
+
+
 def direct_loop_host(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times,
                      Xf_states, flagEnd, β, allowImpulsive, maxIter, ops, verbose=True, *, tf_bounds=None):
     """The Python mirror of the multiShoot_CRTBP_direct loop (direct.jl:477-594) on an injected `ops` back end, the QP solved on

@@ -19,7 +19,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from .constants import RK4, RKF78_FIXED, RKF78_ADAPTIVE, DOP853_ADAPTIVE  # noqa: F401
+from .constants import MU, RK4, RKF78_FIXED, RKF78_ADAPTIVE, DOP853_ADAPTIVE  # noqa: F401
 from ._lib import LtoError, LtoIntegrator, LtoParams, LtoDirectParams, LtoDirectTargets, LtoDirectOrbits, LtoDirectEndModel, LtoDirectTfBounds, LTO_EINVAL
 
 
@@ -864,6 +864,36 @@ def direct_end_states(tau, orbits, ctx=None):
     if not batched:
         return s[:6, 0], s[6:, 0], g0[:, 0], gf[:, 0], float(c0[0]), float(cf[0])
     return s[:6], s[6:], g0, gf, c0, cf
+
+
+StackGuess = collections.namedtuple("StackGuess", "X t tau1 tau2_0 tau2 gap status")
+
+
+def stack_guess(tau1, tof1, tof2, n_nodes, orbits, MU=MU, integ=None, ctx=None):
+    """Trajectory-stacking initial guesses on the device (lto_stack_guess_batch; the reference demo's block,
+    CRTBP_Multishoot_direct_demo.jl:116-157): per start a ballistic coast of tof1 TU on the departure orbit from phase tau1, the
+    closest point of the arrival orbit (find_tau), a coast of tof2 TU from there, both sampled at LinRange(0, tof1 + tof2, n_nodes),
+    the last node snapped onto the arrival orbit.  tau1, tof1, tof2: scalars, or arrays broadcast to one batch of B starts;
+    orbits = DirectOrbits or (X0_times, X0_states, Xf_times, Xf_states).  Returns StackGuess(X [6 x n x B], t [n x B], tau1 [B]
+    (wrapped into [0, 1]), tau2_0 [B] (junction), tau2 [B] (end), gap [2 x B] (the distances find_tau minimised), status [B]: 0, or
+    2 where a node is not finite) -- without the batch axis when all three are scalars."""
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    ob = _orbits(orbits)
+    args = [np.asarray(v, dtype=np.float64) for v in (tau1, tof1, tof2)]
+    batched = any(v.ndim > 0 for v in args)
+    t1, f1, f2 = (np.ascontiguousarray(v) for v in np.broadcast_arrays(*(v.reshape(-1) for v in args)))
+    B, n = t1.size, int(n_nodes)
+    X = np.zeros((6, max(n, 0), B), order="F")
+    t = np.zeros((max(n, 0), B), order="F")
+    tau = np.zeros((3, B), order="F")
+    gap = np.zeros((2, B), order="F")
+    status = np.zeros(B, dtype=np.int32)
+    ctx.check(ctx.fn("stack_guess_batch")(ctx.handle, n, B, float(MU), C.byref(ob.struct), C.byref(integ), _ptr(t1), _ptr(f1), _ptr(f2),
+                                          _ptr(X), _ptr(t), _ptr(tau), _ptr(gap), _ptr(status)))
+    if not batched:
+        return StackGuess(X[:, :, 0], t[:, 0], float(tau[0, 0]), float(tau[1, 0]), float(tau[2, 0]), gap[:, 0], int(status[0]))
+    return StackGuess(X, t, tau[0].copy(), tau[1].copy(), tau[2].copy(), gap, status)
 
 
 AddTime = collections.namedtuple("AddTime", "XC_guess XC_out t_out tau defect status iterations history cost")
