@@ -7,6 +7,10 @@ flagEnd = false, beta = 0, no impulses, at most 100 iterations.  The whole loop 
 solved exactly on the device, the batched line search -- is one lto_direct_solve call.  With --then-indirect the smoothed
 states are handed to the indirect method (p = 2, adjoints only first), the reference's sequence.
 
+With --costate-guess the indirect method starts from the costates the direct solve already holds -- the multipliers of its QP
+step (drivers.direct_to_indirect, one device call for the seed) -- with full Newton from the first iteration; given
+with --then-indirect too, the iteration counts of both routes are printed side by side.
+
 --free-ends [beta] runs the reference's other mode, flagEnd = true (default beta = 0): odd iterations also move the departure and
 arrival phases tau1, tau2 (by at most 0.1 per step), so the transfer finds where on the two orbits it starts and ends.  The run
 starts from tau2 offset by --tau2-offset (default 0.02) from the stacked value and prints the final phases.
@@ -61,7 +65,7 @@ def demo_problem(n_nodes=30, tof_days=20.0, tau1=0.75, ballistic=False):
 
 
 def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100, free_ends=None, tau2_offset=0.0, free_tf=None,
-         ballistic=False):
+         ballistic=False, costate_guess=False):
     ctx = lto.default_context(0)
     X, U, t, tau1, tau2, t0s, X0s, tfs, Xfs = demo_problem(ballistic=ballistic)
     tau2 += tau2_offset
@@ -84,10 +88,23 @@ def main(verbose=True, then_indirect=False, python_loop=False, maxIter=100, free
     if then_indirect and last["status"] == 0:
         rng = np.random.default_rng(0)
         XC = np.vstack([X, 0.1 * rng.standard_normal((6, n))])
-        XC, d, flag = drivers.multiShoot_CRTBP_indirect(XC, t, MU, DU, TU, n, mass, 10.0, False, True, 10, 2.0, 1.0, verbose=verbose)
-        XC, d, flag = drivers.multiShoot_CRTBP_indirect(XC, t, MU, DU, TU, n, mass, 10.0, False, False, 50, 2.0, 1.0, verbose=verbose)
-        print("indirect p = 2 from the direct solution: status %d, max defect %.2e" % (flag, np.abs(d).max()))
+        prm = lto.make_params(MU, DU, TU, 10.0, mass, 1.0, 2.0, 1.0)
+        XC, d, flag, it1, h1 = lto.indirect_solve(XC, t, prm, None, True, 10, ctx=ctx)
+        XC, d, flag, it2, h2 = lto.indirect_solve(XC, t, prm, None, False, 50, ctx=ctx)
+        for k, (er, alpha) in enumerate(list(h1) + list(h2) if verbose else []):
+            print("Iter %d. Max defect = %.2e. alpha = %.3f." % (k + 1 if k < len(h1) else k + 1 - len(h1), er, alpha))
+        print("indirect p = 2 from the direct solution, random costates: status %d, max defect %.2e, %d adjoints-only + %d full "
+              "iterations" % (flag, np.abs(d).max(), min(it1, 10), it2))
         res["indirect"] = (flag, float(np.abs(d).max()))
+        res["indirect_iterations"] = (min(it1, 10), it2)
+    if costate_guess and last["status"] == 0:
+        s0, sf = drivers.interpEndStates(tau1, tau2, t0s, X0s, tfs, Xfs)
+        r = drivers.direct_to_indirect(X, U, t, nsteps, mass, Isp, MU, DU, TU, 10.0, 50, state_0=s0, state_f=sf, ctx=ctx)
+        print("indirect p = 2 from the direct solution, costates from the QP multipliers: status %d, max defect %.2e, %d full "
+              "iterations (KKT residual of the seed %.1e)" % (r["status"][0], r["max_defect"][0], r["iterations"][0], r["kkt_res"][0]))
+        res["costate_guess"] = (int(r["status"][0]), float(r["max_defect"][0]), int(r["iterations"][0]))
+        if "indirect_iterations" in res:
+            print("iterations: %d + %d with random costates, %d with the multipliers" % (*res["indirect_iterations"], r["iterations"][0]))
     return res
 
 
@@ -164,4 +181,5 @@ if __name__ == "__main__":
     if free_tf is not None and free is None:
         free = 0.0                                        # a free tf moves on the free-end iterations
     main(verbose="-q" not in sys.argv, then_indirect="--then-indirect" in sys.argv, python_loop="--python-loop" in sys.argv,
-         free_ends=free, tau2_offset=off, free_tf=free_tf, ballistic="--ballistic-guess" in sys.argv)
+         free_ends=free, tau2_offset=off, free_tf=free_tf, ballistic="--ballistic-guess" in sys.argv,
+         costate_guess="--costate-guess" in sys.argv)

@@ -335,6 +335,22 @@ int lto_indirect_add_time(lto_ctx* ctx, int ndim, int n_nodes, const double* XC,
                           const lto_integrator* integ, const lto_direct_orbits* orbits, double dt, int n_desired,
                           int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
                           double* defect, int* status_flag, int* iterations, double* history, double* cost);
+/* Costates of n_batch direct solutions (host arrays, the layouts of lto_direct_qp_step): one Jacobian sweep, one frozen QP step
+ * (flagEnd = false, tf fixed) and the costates kernel at the given point (see lto_direct_costates_dev).  At a converged
+ * minimum-energy solution the step is zero and the multipliers are the discrete adjoints of the transcription.  Outputs: Lambda
+ * [nstate x n_nodes x n_batch]; mult [nstate x (n_nodes-1) x n_batch] (may be NULL); XC [12 x n_nodes x n_batch] = (X; c^2 Lambda)
+ * with c = TU^2 / DU / 1e3 / 1000 (may be NULL), the node vector lto_indirect_solve_batch takes for p = 2: the direct cost is sum
+ * w |u|^2 in N^2, the indirect one int |a|^2 dt with a = c u (1000 kg: the mass of the 6-state right-hand side), so lambda = c^2
+ * Lambda and lambda_v ~ -2 a; kkt_res [n_batch]; status [n_batch]: 0, or 1 for a singular KKT system (that trajectory's outputs are
+ * NaN; the call still returns LTO_OK).  nstate = 7 with XC: LTO_EUNSUPPORTED (the multipliers, the mass row included, are returned
+ * without XC; the 14-dim hand-over is not built).  lto_direct_costates: one trajectory. */
+int lto_direct_costates_batch(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
+                              int n_tgrids, int nsteps, const lto_direct_params* prm, const lto_direct_targets* targets,
+                              int n_targets, int allow_impulsive, double* Lambda, double* mult, double* XC, double* kkt_res,
+                              int* status);
+int lto_direct_costates(lto_ctx* ctx, int nstate, int n_nodes, const double* X, const double* U, const double* t, int nsteps,
+                        const lto_direct_params* prm, const lto_direct_targets* targets, int allow_impulsive, double* Lambda,
+                        double* mult, double* XC, double* kkt_res, int* status);
 /* Trajectory-stacking initial guesses (CRTBP_Multishoot_direct_demo.jl:116-157) for n_batch starts side by side,
  * start b given by tau1[b] (phase on the departure table), tof1[b] and tof2[b] (TU, > 0).  Per start: t_out = LinRange(0, tof1 +
  * tof2, n_nodes); the nodes with t_k < tof1 are the ballistic CRTBP flow (mass ratio MU) of the departure spline at tau1, node 0
@@ -606,6 +622,19 @@ int lto_direct_qp_step_dev(lto_direct_plan* plan, void* stream, const double* Ja
                            const lto_direct_targets* targets, int allow_impulsive, double* dX, double* dU, double* dV,
                            double* cost);
 const int* lto_direct_plan_qp_status(const lto_direct_plan* plan);
+/* Costates of the direct transcription from the multipliers of the plan's last frozen step (covector mapping).  Valid
+ * after lto_direct_qp_step_dev on this plan, on the same stream, with the Jac that step read (LTO_EINVAL before any step, or when
+ * the plan's last step was another variant).  With l_i the multiplier of defect i and E_i = d defect_i / d x_i, F_i = d defect_i /
+ * d x_{i+1}:  Lambda_k = E_k^T l_k for k < n_nodes - 1 and Lambda_{n-1} = -F_{n-2}^T l_{n-2}; at an interior node the two agree up
+ * to the solve's rounding (the QP's stationarity in dx_k).  Device outputs: Lambda [nstate][ldl], entry b * n_nodes + k; mult
+ * [nstate][ldm], entry b * (n_nodes - 1) + i, the raw multipliers l_i (may be NULL); kkt_res [n_batch], per trajectory the largest
+ * |E_k^T l_k + F_{k-1}^T l_{k-1}| over the interior nodes and components divided by its largest |Lambda| (0 with n_nodes = 2).  A
+ * trajectory whose step was singular (lto_direct_plan_qp_status) gets NaN in all three.  Units: the cost is sum w |u|^2 with u in N
+ * and w in TU; lto_direct_costates_batch gives the scaling to the indirect method's costates.
+ * LTO_ENULL: plan, Jac, Lambda or kkt_res NULL.  LTO_EINVAL: ldj < (n_nodes-1) n_batch, ldl < n_nodes n_batch, mult with ldm <
+ * (n_nodes-1) n_batch. */
+int lto_direct_costates_dev(lto_direct_plan* plan, void* stream, const double* Jac, long ldj, double* Lambda, long ldl, double* mult,
+                            long ldm, double* kkt_res);
 
 /* Newton step of the indirect method solved on the device: delta = -Jac_full \ defect for the block-bidiagonal
  * [Phi_i | -I] system with both end states fixed (src/multiShoot_CRTBP_indirect.jl:123-142, :181-182), by structured

@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, addTimeFinal, tf_sweep, meshRefine_indirect, remesh_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_qp_step, direct_solve, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -434,6 +434,25 @@ function direct_qp_step(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{F
                ctx.handle, nstate, n_nodes, 1, X_all, u_all, t_TU, 1, nsteps, prm, tg, 1, allowImpulsive, dX, dU, dV, cost)
     check(ctx, rc)
     (dX, dU, dV[1:3], dV[4:6], cost[1])
+end
+
+# Costates of a direct solution from the multipliers of a frozen QP step at the given point (lto_direct_costates; covector mapping):
+# returns (Lambda [nstate x n], mult [nstate x (n-1)], XC [12 x n] = (X; c^2 Lambda) with c = TU^2 / DU / 1e3 / 1000 -- the node
+# vector of the indirect method for p = 2, `nothing` for nstate = 7 --, kkt_res, status).
+function direct_costates(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Float64}, t_TU::Vector{Float64}, nsteps, Isp,
+                         MU, DU, TU, state_0, state_f, mass, dV1, dV2; allowImpulsive::Bool = false)
+    nstate, n_nodes = size(X_all)
+    Lambda = zeros(nstate, n_nodes); mult = zeros(nstate, n_nodes - 1); res = zeros(1); status = zeros(Cint, 1)
+    XC = nstate == 6 ? zeros(12, n_nodes) : nothing
+    prm = Ref(LtoDirectParams(MU, DU, TU, Isp))
+    tg = Ref(LtoDirectTargets(state_0, state_f, mass, dV1, dV2))
+    rc = ccall(entry(ctx, :direct_costates), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ref{LtoDirectParams}, Ref{LtoDirectTargets},
+                Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, nstate, n_nodes, X_all, u_all, t_TU, nsteps, prm, tg, allowImpulsive, Lambda, mult,
+               XC === nothing ? Ptr{Cdouble}(C_NULL) : pointer(XC), res, status)
+    check(ctx, rc)
+    (Lambda, mult, XC, res[1], Int(status[1]))
 end
 
 # The loop of multiShoot_CRTBP_direct (direct.jl:477-594) on the device: returns (X_all, u_all, t_TU, dV1, dV2, defect,

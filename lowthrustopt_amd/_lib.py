@@ -157,6 +157,11 @@ SIGNATURES = {
     "lto_direct_qp_step_dev": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long, _vp, C.c_int, _vp,
                                          C.c_int, _vp, _vp, _vp, _vp]),
     "lto_direct_plan_qp_status": (_vp, [_vp]),
+    "lto_direct_costates_dev": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long, _vp]),
+    "lto_direct_costates_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(LtoDirectParams),
+                                            _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lto_direct_costates": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams), _vp, C.c_int, _vp, _vp,
+                                      _vp, _vp, _vp]),
     "lto_direct_solve_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(LtoDirectParams),
                                          _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_direct_end_states": (C.c_int, [_vp, C.POINTER(LtoDirectOrbits), C.c_int, _vp, _vp, _vp]),

@@ -191,6 +191,22 @@ int* direct_qp_status(void* workspace, int n_batch);   // [n_batch] inside the w
 // and free tf: z0 | dz/dp1 | dz/dp2 | dz/dp3, then the 3 x 3 box QP in p.  Any other nr: hipErrorInvalidValue.
 hipError_t launch_direct_qp(int nstate, int nr, const DirectQpArgs& q, void* workspace, hipStream_t st);
 hipError_t launch_direct_qp_update_dv(double* targets, const double* dV, const double* step, int n_batch, hipStream_t st);
+// costates from the multipliers of the frozen step last solved in `workspace` (nr = 1): Lambda [nstate][ldl] entry
+// b * n_nodes + k, mult [nstate][ldm] entry b * (n_nodes - 1) + i (null: not wanted), kkt_res [n_batch]; XC [12][ldxc] =
+// (X; cc Lambda) for nstate 6 (null: not wanted; nstate 7 with XC: hipErrorInvalidValue).  acc: direct_costates_acc_bytes of device
+// scratch.
+struct DirectCostatesArgs {
+  int n_nodes, n_batch;
+  const double* Jac; long ldj;
+  double* Lambda; long ldl;
+  double* mult; long ldm;
+  double* kkt_res;
+  const double* X; long ldx;
+  double* XC; long ldxc;
+  double cc;
+};
+size_t direct_costates_acc_bytes(int n_batch);
+hipError_t launch_direct_costates(int nstate, const DirectCostatesArgs& o, void* workspace, void* acc, hipStream_t st);
 // the two orbit tables of the free-end model on the device: times [n], states and natural-spline second derivatives [n][6]
 struct EndOrbitsDev { int n[2]; const double* t[2]; const double* Y[2]; const double* M[2]; };
 // per trajectory b: s[b * s_stride + 0..11] = (s0; sf) at tau[2b], tau[2b+1], model[b][14] = (g0; gf; |c0|; |cf|)

@@ -860,6 +860,101 @@ hipError_t launch_direct_qp_update_dv(double* targets, const double* dV, const d
   return hipGetLastError();
 }
 
+// ---- costates from the multipliers of a frozen step: one lane per (trajectory, node), node index fastest, so that
+// a wavefront's loads of one Jacobian entry are one contiguous run.  With l_i = s_l l~_i the multiplier of defect i (the lambda part
+// of Y, unscaled; s_l is a power of two) and E_i, F_i the blocks d defect_i / d x_i, d defect_i / d x_{i+1}:
+//   Lambda_k = E_k^T l_k (k < n-1),  Lambda_{n-1} = -F_{n-2}^T l_{n-2};  interior residual E_k^T l_k + F_{k-1}^T l_{k-1}.
+// acc [n_batch][2]: bits of the largest |residual| and of the largest |Lambda| of every trajectory (k_qp_gmax's reduction).  With
+// XC (NS = 6 only): XC [12][ldxc] = (X; cc Lambda), the node vector of the indirect method.  A singular trajectory gets NaN.
+template <int NS>
+__global__ __launch_bounds__(QP_FIN) void k_qp_costates(QpArgs a, DirectCostatesArgs o, unsigned long long* acc) {
+  const int b = blockIdx.y, k = blockIdx.x * QP_FIN + threadIdx.x;
+  const bool bad = a.status[b] != 0;
+  double rmax = 0.0, lmax = 0.0;
+  if (k < a.n_nodes) {
+    const QpScale sc = qp_scale(a, b);
+    const long node = (long)b * a.n_nodes + k, s = (long)b * a.S_traj + k;
+    const bool hasE = k < a.n_nodes - 1, hasF = k > 0;
+    const double nan = __builtin_nan("");
+    double e[NS], f[NS];
+#pragma unroll
+    for (int c = 0; c < NS; ++c) e[c] = f[c] = 0.0;
+    if (hasE) {                                   // E_k^T l_k; segment k does not exist at the last node
+      double l[NS];
+#pragma unroll
+      for (int r = 0; r < NS; ++r) l[r] = sc.sl * a.Y[(long)(NS + 3 + r) * a.ldy + node];
+#pragma unroll
+      for (int c = 0; c < NS; ++c)
+#pragma unroll
+        for (int r = 0; r < NS; ++r) e[c] = __builtin_fma(a.Jac[(long)(c * NS + r) * a.ldj + s], l[r], e[c]);
+      if (o.mult)
+#pragma unroll
+        for (int r = 0; r < NS; ++r) o.mult[(long)r * o.ldm + s] = bad ? nan : l[r];
+    }
+    if (hasF) {                                   // F_{k-1}^T l_{k-1}
+      double l[NS];
+#pragma unroll
+      for (int r = 0; r < NS; ++r) l[r] = sc.sl * a.Y[(long)(NS + 3 + r) * a.ldy + node - 1];
+#pragma unroll
+      for (int c = 0; c < NS; ++c)
+#pragma unroll
+        for (int r = 0; r < NS; ++r) f[c] = __builtin_fma(a.Jac[(long)((NS + c) * NS + r) * a.ldj + s - 1], l[r], f[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < NS; ++c) {
+      const double lam = hasE ? e[c] : -f[c];
+      o.Lambda[(long)c * o.ldl + node] = bad ? nan : lam;
+      if (!bad) {
+        lmax = fmax(lmax, fabs(lam));
+        if (hasE && hasF) rmax = fmax(rmax, fabs(e[c] + f[c]));
+      }
+      if constexpr (NS == 6) {
+        if (o.XC) {
+          o.XC[(long)c * o.ldxc + node] = o.X[(long)c * o.ldx + node];
+          o.XC[(long)(6 + c) * o.ldxc + node] = bad ? nan : o.cc * lam;
+        }
+      }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) { rmax = fmax(rmax, __shfl_xor(rmax, off)); lmax = fmax(lmax, __shfl_xor(lmax, off)); }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(&acc[2 * b], (unsigned long long)__double_as_longlong(rmax));
+    atomicMax(&acc[2 * b + 1], (unsigned long long)__double_as_longlong(lmax));
+  }
+}
+// kkt_res = largest |residual| / largest |Lambda| per trajectory: 0 without an interior node, NaN for a singular trajectory
+__global__ void k_qp_costates_res(const int* status, const unsigned long long* acc, double* kkt_res, int n_batch) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n_batch) return;
+  const double r = __longlong_as_double((long long)acc[2 * b]), l = __longlong_as_double((long long)acc[2 * b + 1]);
+  kkt_res[b] = status[b] != 0 ? __builtin_nan("") : (r == 0.0 ? 0.0 : r / l);
+}
+
+size_t direct_costates_acc_bytes(int n_batch) { return sizeof(unsigned long long) * 2 * n_batch; }
+
+template <int NS>
+static hipError_t direct_costates_impl(const DirectCostatesArgs& o, void* workspace, void* acc, hipStream_t st) {
+  using D = QpDims<NS, 1>;                         // the layout of the frozen step's workspace (direct_qp_impl)
+  QpArgs a = {};
+  a.n_nodes = o.n_nodes; a.n_batch = o.n_batch; a.S_traj = o.n_nodes - 1;
+  a.Jac = o.Jac; a.ldj = o.ldj;
+  const size_t S = (size_t)a.S_traj * a.n_batch, J = (size_t)a.n_nodes * a.n_batch;
+  a.gw = (unsigned long long*)workspace;
+  a.status = direct_qp_status(workspace, a.n_batch);
+  a.Y = (double*)((char*)workspace + qp_header_bytes(a.n_batch)) + 2 * S * D::ROW + J * D::REC; a.ldy = (long)J;
+  const hipError_t e = hipMemsetAsync(acc, 0, direct_costates_acc_bytes(a.n_batch), st);
+  if (e != hipSuccess) return e;
+  const int nblk = (a.n_nodes + QP_FIN - 1) / QP_FIN;
+  hipLaunchKernelGGL((k_qp_costates<NS>), dim3(nblk, a.n_batch), dim3(QP_FIN), 0, st, a, o, (unsigned long long*)acc);
+  hipLaunchKernelGGL(k_qp_costates_res, dim3((a.n_batch + 63) / 64), dim3(64), 0, st, (const int*)a.status,
+                     (const unsigned long long*)acc, o.kkt_res, a.n_batch);
+  return hipGetLastError();
+}
+hipError_t launch_direct_costates(int nstate, const DirectCostatesArgs& o, void* workspace, void* acc, hipStream_t st) {
+  if (nstate == 7) return o.XC ? hipErrorInvalidValue : direct_costates_impl<7>(o, workspace, acc, st);
+  return direct_costates_impl<6>(o, workspace, acc, st);
+}
+
 hipError_t launch_direct_qp(int nstate, int nr, const DirectQpArgs& q, void* workspace, hipStream_t st) {
   switch (nr) {
     case 1: return (nstate == 7) ? direct_qp_impl<7, 1>(q, workspace, st) : direct_qp_impl<6, 1>(q, workspace, st);

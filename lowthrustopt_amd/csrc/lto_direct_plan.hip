@@ -24,6 +24,7 @@ int direct_plan_build(lto_ctx* c, int nstate, int n_nodes, int n_batch, int nste
 
 void direct_plan_free(lto_direct_plan* p) {
   if (p->qp_ws) (void)hipFree(p->qp_ws);        // hipFree waits for the device
+  if (p->cs_acc) (void)hipFree(p->cs_acc);
   delete p;
 }
 
@@ -104,6 +105,7 @@ int direct_qp_launch(lto_direct_plan* p, hipStream_t st, int nr, const double* J
   timing_begin(c, st);
   const hipError_t e = launch_direct_qp(p->nstate, nr, q, p->qp_ws, st);
   timing_end(c, st);
+  p->qp_last_nr = (e == hipSuccess) ? nr : 0;
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_direct_qp", e);
   return LTO_OK;
 }

@@ -129,6 +129,8 @@ struct lto_direct_plan {
   void* qp_ws;      // workspace of the QP step (kernels_direct_qp.hip), allocated at the plan's first step
   int qp_ws_nr;     // right-hand sides the workspace is sized for: 1 (frozen ends) or 3 (free ends, grown at the first free step)
   double* qp_singular_out;   // lto_direct_solve_batch: where the QP step also reports singular systems (device, [n_batch])
+  int qp_last_nr;   // right-hand sides of the last QP step on this plan (0: none yet): the workspace holds that variant's layout
+  void* cs_acc;     // reduction scratch of the costates kernel (lto_direct_costates.hip), allocated at its first call
 };
 
 #define LTO_HIP(c, call)                                              \
@@ -183,6 +185,10 @@ int direct_qp_launch(lto_direct_plan* p, hipStream_t st, int nr, const double* J
                      const lto_direct_targets* targets, int allow_impulsive, double* dX, double* dU, double* dV, double* cost,
                      const lto_direct_end_model* model = nullptr, const double* beta = nullptr, double* pout = nullptr,
                      const double* dtf = nullptr, const double* tfb = nullptr, const double* tf = nullptr);
+
+// lto_direct_costates.hip
+int direct_costates_launch(lto_direct_plan* p, hipStream_t st, const double* Jac, long ldj, double* Lambda, long ldl, double* mult,
+                           long ldm, double* kkt_res, const double* X = nullptr, long ldx = 0, double* XC = nullptr, long ldxc = 0);
 
 // lto_util.hip
 bool report_reserve(lto_ctx* c, size_t doubles);

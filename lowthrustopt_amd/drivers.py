@@ -381,10 +381,9 @@ def interpEndStates(τ1, τ2, X0_times, X0_states, Xf_times, Xf_states, MU=None)
     return s0, sf
 
 
-def direct_qp_dense(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, mass, dV1, dV2, DU, TU, allowImpulsive=False):
-    """optimizeTraj (direct.jl:248-403) for flagEnd = false, beta = 0, tf fixed -- the host restatement of the device QP step: the
-    equality-constrained QP's KKT system, assembled densely and solved by LU after symmetric (Ruiz) equilibration.
-    Returns (x_update, u_update, dV1_update, dV2_update, cost)."""
+def _direct_qp_kkt(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, mass, dV1, dV2, DU, TU, allowImpulsive):
+    """The dense KKT solve of direct_qp_dense.  Returns (z, w, c2, (ns, n, nz, iu, iv)): z = (dx node-major, du, the two impulse
+    updates, then the multipliers in the order of the constraints: the S linearised defects first)."""
     Jt = np.asarray(Jac_temp, dtype=np.float64)
     d = np.asarray(defect, dtype=np.float64)
     X = np.asarray(X_all, dtype=np.float64)
@@ -441,11 +440,118 @@ def direct_qp_dense(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, mass
         Ks = K * D[:, None] * D[None, :]
         D = D / np.sqrt(np.maximum(np.abs(Ks).max(axis=1), 1e-300))
     z = np.linalg.solve(K * D[:, None] * D[None, :], r * D) * D
+    return z, w, c2, (ns, n, nz, iu, iv)
+
+
+def direct_qp_dense(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, mass, dV1, dV2, DU, TU, allowImpulsive=False):
+    """optimizeTraj (direct.jl:248-403) for flagEnd = false, beta = 0, tf fixed -- the host restatement of the device QP step: the
+    equality-constrained QP's KKT system, assembled densely and solved by LU after symmetric (Ruiz) equilibration.
+    Returns (x_update, u_update, dV1_update, dV2_update, cost)."""
+    z, w, c2, (ns, n, nz, iu, iv) = _direct_qp_kkt(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, mass, dV1, dV2, DU, TU,
+                                                    allowImpulsive)
+    U = np.asarray(u_all, dtype=np.float64)
     x_update = z[:ns * n].reshape(n, ns).T
     u_update = z[iu:iv].reshape(n, 3).T
     dV1_u, dV2_u = (z[iv:iv + 3], z[iv + 3:iv + 6]) if allowImpulsive else (np.zeros(3), np.zeros(3))   # exact zeros when pinned
     cost = float(np.sum(w[None, :] * (U + u_update) ** 2) + c2 * (np.sum((dV1 + dV1_u) ** 2) + np.sum((dV2 + dV2_u) ** 2)))
     return x_update, u_update, dV1_u, dV2_u, cost
+
+
+def costates_from_multipliers(Jac_temp, mult):
+    """The node costates of the transcription from the multipliers l_i of its defects, with E_i = d defect_i / d x_i
+    and F_i = d defect_i / d x_{i+1}: Lambda_k = E_k' l_k for k < n - 1, Lambda_{n-1} = -F_{n-2}' l_{n-2}.  Returns (Lambda [ns x n],
+    kkt_res): the largest |E_k' l_k + F_{k-1}' l_{k-1}| over the interior nodes (the QP's stationarity in dx_k) divided by the
+    largest |Lambda|, 0 without an interior node."""
+    Jt = np.asarray(Jac_temp, dtype=np.float64)
+    l = np.asarray(mult, dtype=np.float64)
+    ns, _, S = Jt.shape
+    El = np.einsum("rci,ri->ci", Jt[:, :ns, :], l)
+    Fl = np.einsum("rci,ri->ci", Jt[:, ns:2 * ns, :], l)
+    Lam = np.concatenate([El, -Fl[:, -1:]], axis=1)
+    res = float(np.abs(El[:, 1:] + Fl[:, :-1]).max()) if S > 1 else 0.0
+    return Lam, (res / float(np.abs(Lam).max()) if res > 0.0 else 0.0)
+
+
+def direct_costates_dense(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, mass, dV1, dV2, DU, TU, allowImpulsive=False):
+    """The host mirror of lto_direct_costates: the multipliers of the defect constraints read out of direct_qp_dense's KKT solve
+    (grad cost + A' l = 0, the sign of kernels_direct_qp.hip) and the costates from them.  Returns (Lambda [ns x n], mult [ns x
+    (n-1)], kkt_res)."""
+    z, _, _, (ns, n, nz, _, _) = _direct_qp_kkt(Jac_temp, defect, X_all, u_all, t_TU, state_0, state_f, mass, dV1, dV2, DU, TU,
+                                                allowImpulsive)
+    mult = z[nz:nz + ns * (n - 1)].reshape(n - 1, ns).T
+    Lam, res = costates_from_multipliers(Jac_temp, mult)
+    return Lam, mult, res
+
+
+def costates_from_direct(X_all, u_all, t_TU, nsteps, mass, Isp, MU, DU, TU, state_0=None, state_f=None, dV1=None, dV2=None,
+                         allowImpulsive=False, ops=None, ctx=None):
+    """XC_all [12 x n (x B)] = (X; c^2 Lambda), the indirect method's node vector for p = 2 from direct solutions X_all [6 x n (x
+    B)], u_all (N), t_TU [n] or [n x B]: the costates are the multipliers of a frozen QP step at the given point, c =
+    hotpath.costate_scale(DU, TU).  The end targets default to the solutions' own end states (a converged frozen-end
+    solution sits on them; plus the impulses, which default to zero).  ops=None: lto_direct_costates_batch on the device; an injected `ops`
+    (`jacobian`, e.g. HipDirectOps or a CPU back end) runs the host mirror direct_costates_dense trajectory by trajectory.  The
+    record of the call is kept in `costates_from_direct.last` = {"Lambda", "mult", "kkt_res", "status"}."""
+    X = np.asarray(X_all, dtype=np.float64)
+    U = np.asarray(u_all, dtype=np.float64)
+    if X.shape[0] != 6:
+        raise NotImplementedError("costates_from_direct hands over to the 12-row system; the 14-row hand-over is not built")
+    batched = X.ndim == 3
+    X3, U3 = (X, U) if batched else (X[..., None], U[..., None])
+    B = X3.shape[2]
+    T = np.asarray(t_TU, dtype=np.float64)
+    per = lambda v, k: np.zeros((k, B)) if v is None else np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(k, -1), (k, B))  # noqa: E731
+    d1, d2 = per(dV1, 3).T, per(dV2, 3).T
+    s0 = [X3[:6, 0, b] + np.r_[0.0, 0.0, 0.0, d1[b]] for b in range(B)] if state_0 is None else per(state_0, 6).T
+    sf = [X3[:6, -1, b] + np.r_[0.0, 0.0, 0.0, d2[b]] for b in range(B)] if state_f is None else per(state_f, 6).T
+    if ops is None:
+        tg = [hotpath.direct_targets(s0[b], sf[b], mass, d1[b], d2[b]) for b in range(B)]
+        Lam, mult, XC, res, status = hotpath.direct_costates(X3, U3, T, nsteps, MU, DU, TU, Isp, tg, allowImpulsive, True, ctx=ctx)
+    else:
+        c = hotpath.costate_scale(DU, TU)
+        Lam, mult = np.zeros_like(X3), np.zeros((6, X3.shape[1] - 1, B))
+        res, status = np.zeros(B), np.zeros(B, dtype=np.int32)
+        for b in range(B):
+            t = T if T.ndim == 1 else T[:, b]
+            Jt, d = ops.jacobian(X3[..., b], U3[..., b], t, nsteps)
+            try:
+                Lam[..., b], mult[..., b], res[b] = direct_costates_dense(Jt, d, X3[..., b], U3[..., b], t, s0[b], sf[b], mass, d1[b],
+                                                                          d2[b], DU, TU, allowImpulsive)
+            except np.linalg.LinAlgError:
+                Lam[..., b], mult[..., b], res[b], status[b] = np.nan, np.nan, np.nan, 1
+        XC = np.concatenate([X3, (c * c) * Lam], axis=0)
+    costates_from_direct.last = {"Lambda": Lam if batched else Lam[..., 0], "mult": mult if batched else mult[..., 0],
+                                 "kkt_res": res if batched else float(res[0]), "status": status if batched else int(status[0])}
+    return np.asfortranarray(XC if batched else XC[..., 0])
+
+
+def direct_to_indirect(X_all, u_all, t_TU, nsteps, mass, Isp, MU, DU, TU, thrustLimit=10.0, maxIter=50, state_0=None, state_f=None,
+                       dV1=None, dV2=None, allowImpulsive=False, integ=None, ctx=None):
+    """The hand-over of the reference's workflow ("converge the direct method, then the indirect one") for a batch of converged
+    minimum-energy direct solutions X_all [6 x n x B] (or one, [6 x n]): the costate seed from the QP multipliers
+    (costates_from_direct), then lto_indirect_solve_batch with p = 2, full Newton from the first iteration -- no random costates
+    and no adjoints-only phase.  Returns a dict of per-trajectory results: XC [12 x n x B], defect, max_defect [B], status [B]
+    (0 converged to 1e-10, 1 maxIter, 2 NaN; 3 = no seed: the costates' KKT system was singular), iterations [B], seed [12 x n x B],
+    kkt_res [B]."""
+    X = np.asarray(X_all, dtype=np.float64)
+    batched = X.ndim == 3
+    X3 = X if batched else X[..., None]
+    U3 = np.asarray(u_all, dtype=np.float64).reshape(3, X3.shape[1], -1)
+    seed = costates_from_direct(X3, U3, t_TU, nsteps, mass, Isp, MU, DU, TU, state_0, state_f, dV1, dV2, allowImpulsive, ctx=ctx)
+    rec = costates_from_direct.last
+    B = X3.shape[2]
+    ok = np.flatnonzero(np.asarray(rec["status"]) == 0)
+    out = {"XC": np.full(seed.shape, np.nan, order="F"), "defect": np.full((12, X3.shape[1] - 1, B), np.nan, order="F"),
+           "max_defect": np.full(B, np.nan), "status": np.full(B, 3, dtype=np.int32), "iterations": np.zeros(B, dtype=np.int32),
+           "seed": seed, "kkt_res": np.asarray(rec["kkt_res"])}
+    if ok.size:
+        T = np.asarray(t_TU, dtype=np.float64)
+        prm = hotpath.make_params(MU, DU, TU, thrustLimit, mass, 1.0, 2.0, 1.0)
+        XC, d, status, iters, _ = hotpath.indirect_solve_batch(seed[..., ok], T if T.ndim == 1 else T[:, ok], prm, integ, False, maxIter,
+                                                               ctx=ctx)
+        out["XC"][..., ok], out["defect"][..., ok] = XC, d
+        out["max_defect"][ok] = np.abs(d).max(axis=(0, 1))
+        out["status"][ok], out["iterations"][ok] = status, iters
+    return out
 
 
 END_PERT = 0.05          # pert of the end model's finite differences (direct.jl:340)
@@ -770,14 +876,18 @@ def stacked_guess(n_nodes, tof1, tof2, τ1, X0_times, X0_states, Xf_times, Xf_st
 
 
 def multiStart_direct(τ1s, tof1s, tof2s, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times, Xf_states, MU, DU, TU,
-                      flagEnd=False, β=0.0, allowImpulsive=False, maxIter=100, ctx=None):
+                      flagEnd=False, β=0.0, allowImpulsive=False, maxIter=100, ctx=None, then_indirect=False, thrustLimit=10.0,
+                      maxIter_indirect=50):
     """A multi-start search of the direct method in three library calls: the stacked guesses of all starts (τ1s, tof1s, tof2s:
     scalars or arrays, broadcast to B starts; hotpath.stack_guess), their end targets at (τ1, τ2) (hotpath.direct_end_states) and
     the loop of multiShoot_CRTBP_direct for all of them side by side on their own grids, zero thrust as the guess
     (hotpath.direct_solve_free).  Returns a dict of per-start arrays: status [B], iterations [B], max_defect [B], cost [B] (of the
     last iteration; NaN where none ran), tau [2 x B] (final τ1; τ2), tau_guess [3 x B] (τ1; τ2 at the junction; τ2 at the end),
     gap [2 x B], guess_status [B], X [6 x n x B], U [3 x n x B], t [n x B], dV [6 x B], defect, history [5 x maxIter x B], and
-    order: the indices of the status-0 starts by increasing cost."""
+    order: the indices of the status-0 starts by increasing cost.
+    then_indirect: the converged starts are handed to the indirect method (direct_to_indirect: costates from the QP multipliers,
+    p = 2 at thrustLimit N, at most maxIter_indirect iterations); the dict gains "indirect" = direct_to_indirect's dict for those
+    starts, in the order of "indirect_starts" (their indices, increasing)."""
     orbits = hotpath.DirectOrbits(X0_times, X0_states, Xf_times, Xf_states)
     τ1s, tof1s, tof2s = (np.ascontiguousarray(v) for v in np.broadcast_arrays(
         *(np.asarray(v, dtype=np.float64).reshape(-1) for v in (τ1s, tof1s, tof2s))))
@@ -793,9 +903,18 @@ def multiStart_direct(τ1s, tof1s, tof2s, n_nodes, nsteps, mass, Isp, X0_times, 
     cost = np.array([hist[1, last[b] - 1, b] if last[b] > 0 else np.nan for b in range(B)])
     ok = np.flatnonzero(status == 0)
     order = ok[np.argsort(cost[ok], kind="stable")]
-    return {"status": status, "iterations": iters, "max_defect": np.abs(defect).max(axis=(0, 1)), "cost": cost, "tau": tau_out,
-            "tau_guess": np.vstack([g.tau1, g.tau2_0, g.tau2]), "gap": g.gap, "guess_status": g.status, "X": X, "U": U, "t": t,
-            "dV": dV, "defect": defect, "history": hist, "order": order}
+    out = {"status": status, "iterations": iters, "max_defect": np.abs(defect).max(axis=(0, 1)), "cost": cost, "tau": tau_out,
+           "tau_guess": np.vstack([g.tau1, g.tau2_0, g.tau2]), "gap": g.gap, "guess_status": g.status, "X": X, "U": U, "t": t,
+           "dV": dV, "defect": defect, "history": hist, "order": order}
+    if then_indirect:
+        out["indirect_starts"] = ok
+        out["indirect"] = None
+        if ok.size:
+            # the end targets of the frozen step are the states the direct loop ended on (with flagEnd: at the final phases)
+            out["indirect"] = direct_to_indirect(X[..., ok], U[..., ok], t[:, ok], nsteps, mass, Isp, MU, DU, TU, thrustLimit,
+                                                 maxIter_indirect, dV1=dV[:3, ok], dV2=dV[3:, ok], allowImpulsive=allowImpulsive,
+                                                 ctx=ctx)
+    return out
 
 
 def direct_loop_host(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times,

@@ -809,6 +809,40 @@ def direct_qp_step(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowIm
     return _direct_qp_call("direct_qp_step", 0, X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive, ctx)
 
 
+def costate_scale(DU, TU):
+    """c of a = c u: the controls of the direct method are in N, the acceleration of the 6-state right-hand side in DU/TU^2 for its
+    literal mass of 1000 kg (c = TU^2 / DU / 1e3 / 1000, formed as the library forms it).  The indirect method's costates are
+    c^2 times the direct transcription's."""
+    return (float(TU) * float(TU)) / float(DU) / 1e3 / 1000.0
+
+
+def direct_costates(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive=False, with_XC=None, ctx=None):
+    """Costates of direct solutions from the multipliers of a frozen QP step at the given point (lto_direct_costates_batch: one
+    Jacobian sweep, one QP step, one kernel).  Returns (Lambda [nstate x n], mult [nstate x (n-1)], XC [12 x n] =
+    (X; c^2 Lambda) with c = costate_scale(DU, TU) -- or None, kkt_res, status); a trailing batch axis on X_all / u_all does several
+    at once.  with_XC: default nstate == 6 (the 14-dim hand-over is not built: nstate 7 with XC raises LTO_EUNSUPPORTED).  status
+    1: that trajectory's KKT system is singular and its outputs are NaN."""
+    ctx = ctx or default_context()
+    X = _f64(X_all)
+    U = _f64(u_all)
+    ns, n, B, batched = _batch_dims(X)
+    t, ntg = _tgrids(t_TU, n, B)
+    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    tg, ntgt = _targets_array(targets)
+    want_xc = (ns == 6) if with_XC is None else bool(with_XC)
+    Lam = np.zeros((ns, n, B), order="F")
+    mult = np.zeros((ns, n - 1, B), order="F")
+    XC = np.zeros((12, n, B), order="F") if want_xc else None
+    res = np.zeros(B)
+    status = np.zeros(B, dtype=np.int32)
+    ctx.check(ctx.fn("direct_costates_batch")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(t), ntg, int(nsteps), C.byref(prm),
+                                              C.cast(tg, C.c_void_p), ntgt, 1 if allowImpulsive else 0, _ptr(Lam), _ptr(mult),
+                                              _ptr(XC) if want_xc else None, _ptr(res), _ptr(status)))
+    if not batched:
+        return Lam[..., 0], mult[..., 0], (XC[..., 0] if want_xc else None), float(res[0]), int(status[0])
+    return Lam, mult, XC, res, status
+
+
 def direct_solve(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, allowImpulsive=False, maxIter=100, ctx=None):
     """The loop of multiShoot_CRTBP_direct (direct.jl:477-594) on the device, trajectories resident in HBM (lto_direct_solve_batch).
     Returns (X_all, u_all, dV[6] = (dV1; dV2), t_TU, defect, status, iterations, history[3 x maxIter] = (max|defect|, cost, alpha));
@@ -1213,6 +1247,12 @@ class DirectPlan:
                                                            _dptr(X), int(ldx), _dptr(U), int(ldu), _dptr(t), int(n_tgrids),
                                                            _dptr(targets), 1 if allowImpulsive else 0, _dptr(dX), _dptr(dU),
                                                            _dptr(dV), _dptr(cost)))
+
+    def costates(self, Jac, ldj, Lambda, ldl, kkt_res, mult=None, ldm=0, stream=None):
+        """Costates from the multipliers of the plan's last frozen qp_step (lto_direct_costates_dev), device arrays: Lambda
+        [nstate][ldl] entry b n_nodes + k, kkt_res [n_batch], mult [nstate][ldm] entry b (n_nodes - 1) + i (optional)."""
+        self.ctx.check(self.ctx.lib.lto_direct_costates_dev(self.handle, stream, _dptr(Jac), int(ldj), _dptr(Lambda), int(ldl),
+                                                            _dptr(mult), int(ldm), _dptr(kkt_res)))
 
     def qp_status_ptr(self):
         """Device int [n_batch] of the last QP step: 1 = singular KKT system (lto_direct_plan_qp_status)."""
