@@ -1172,6 +1172,12 @@ class IndirectPlan:
         self.ctx.check(self.ctx.lib.lto_indirect_jacobian_dev(self.handle, stream, _dptr(X), int(ldx), _dptr(t),
                                                               int(n_tgrids), _dptr(Phi), int(ldp), _dptr(defect), int(ldd)))
 
+    def dense(self, X, ldx, t, n_tgrids, first, t_samples, Y, ldy, final_state=None, stream=None):
+        """Dense output (lto_indirect_dense_dev): segment s stores its state at t_samples[first[s] : first[s+1]] into the same
+        columns of Y [ndim][ldy]; first is int32 [S + 1]; final_state [ndim][n_batch], if given, takes every trajectory's x(t_n)."""
+        self.ctx.check(self.ctx.lib.lto_indirect_dense_dev(self.handle, stream, _dptr(X), int(ldx), _dptr(t), int(n_tgrids),
+                                                           _dptr(first), _dptr(t_samples), _dptr(Y), int(ldy), _dptr(final_state)))
+
     def newton_solve(self, Phi, ldp, defect, ldd, delta, ldx, stream=None, adjoints_only=False):
         """delta = -J \\ defect on the device; Phi=None re-uses the stored factorisation (SOC re-solve)."""
         self.ctx.check(self.ctx.lib.lto_indirect_newton_solve_dev(self.handle, stream, _dptr(Phi), int(ldp), _dptr(defect),
