@@ -19,6 +19,9 @@ reference's bound; implies --free-ends 0 unless given): tf in [1 day, 40 days].
 --refine [tol_max] instead solves, refines the mesh on the device (lto_direct_refine, DESIGN 4.14: nodes removed while a segment's
 RKF7(8) estimate is below tol_max / 1000, segments bisected while one is above tol_max, default 1e-16) and solves again on the
 refined mesh; prints node counts and the largest estimate before and after, and the re-solve's status and iterations.
+--equidistribute N solves, refines as --refine does, moves the refined mesh onto N nodes whose estimates are equidistributed
+(drivers.meshEquidistribute_direct, lto_direct_resample, DESIGN 4.17: two passes) and solves again on them; prints node counts,
+the largest and smallest estimate before and after, and the re-solve's status.
 --ballistic-guess takes the guess from drivers.stacked_guess instead: the reference's own construction (demo :116-157), 10 days
 ballistically on each orbit, made in one device call (lto_stack_guess_batch).
 --multi-start N runs N departure phases tau1 evenly spread over [0, 1) side by side (drivers.multiStart_direct: the guesses, the
@@ -138,6 +141,41 @@ def refine_and_resolve(tol_max=1e-16, tol_min=None, max_nodes=120, maxIter=100, 
     return res
 
 
+def equidistribute_and_resolve(n_new=30, tol_max=1e-16, max_nodes=120, passes=2, w_floor=None, maxIter=100, ctx=None, verbose=True):
+    """Solve on the demo's 30 nodes, refine the solution's mesh, resample it onto n_new nodes of equidistributed estimates and solve
+    again on them (one device call each).  Returns the figures it prints."""
+    ctx = ctx or lto.default_context(0)
+    X, U, t, tau1, tau2, t0s, X0s, tfs, Xfs = demo_problem()
+    n, nsteps, Isp, mass = X.shape[1], 10, 2000.0, 1000.0
+
+    def solve(X, U, t, n):
+        out = drivers.multiShoot_CRTBP_direct(X, U, tau1, tau2, t, np.zeros(3), np.zeros(3), MU, DU, TU, n, nsteps, mass, Isp, t0s, X0s,
+                                              tfs, Xfs, False, False, 0.0, False, maxIter, verbose=False)
+        last = drivers.multiShoot_CRTBP_direct.last
+        return out[0], out[1], out[4], last["status"], last["iterations"], float(np.abs(out[7]).max())
+
+    X, U, t, st0, it0, d0 = solve(X, U, t, n)
+    _, e0 = lto.direct_defectCalc(X, U, t, nsteps, MU, DU, TU, Isp, ctx=ctx)
+    r = lto.direct_refine(X, U, t, nsteps, MU, DU, TU, Isp, tol_max / 1000.0, tol_max, max_nodes, ctx=ctx)
+    kw = {} if w_floor is None else {"w_floor": w_floor}
+    Xe, Ue, te, rs = drivers.meshEquidistribute_direct(r, None, None, 6, None, nsteps, Isp, MU, DU, TU, int(n_new), passes=passes, ctx=ctx, **kw)
+    eq = drivers.meshEquidistribute_direct.last
+    X2, U2, t2, st, it, d = solve(Xe, Ue, te, int(n_new))
+    _, e2 = lto.direct_defectCalc(X2, U2, t2, nsteps, MU, DU, TU, Isp, ctx=ctx)
+    res = {"n_before": n, "n_refined": r.n, "n_after": int(n_new), "resample_status": int(rs), "first_status": st0,
+           "max_error_before": float(e0.max()), "min_error_before": float(e0.min()), "max_error_refined": float(r.errors.max()),
+           "min_error_refined": float(r.errors.min()), "max_error_resampled": float(eq.errors_after.max()),
+           "min_error_resampled": float(eq.errors_after.min()), "max_error_after": float(e2.max()), "min_error_after": float(e2.min()),
+           "status": st, "iterations": it, "max_defect": d}
+    if verbose:
+        print("direct: status %d after %d iterations on %d nodes, max defect %.2e, estimates %.2e .. %.2e" % (st0, it0, n, d0, e0.min(), e0.max()))
+        print("refine (tol_max %.1e): %d -> %d nodes, estimates %.2e .. %.2e" % (tol_max, n, r.n, r.errors.min(), r.errors.max()))
+        print("equidistribute (%d passes): %d -> %d nodes (status %d), estimates of the guess %.2e .. %.2e" % (
+            passes, r.n, n_new, rs, eq.errors_after.min(), eq.errors_after.max()))
+        print("re-solve on %d nodes: status %d after %d iterations, max defect %.2e, estimates %.2e .. %.2e" % (n_new, st, it, d, e2.min(), e2.max()))
+    return res
+
+
 def multi_start(n_starts, n_nodes=30, tof_days=20.0, maxIter=100, verbose=True):
     """n_starts departure phases over [0, 1), the demo's setting otherwise (flagEnd = false); returns drivers.multiStart_direct's dict."""
     tabs = synth.halo_orbits()
@@ -169,6 +207,9 @@ def _arg(flag, default):
 if __name__ == "__main__":
     if "--refine" in sys.argv:
         refine_and_resolve(tol_max=_arg("--refine", 1e-16))
+        sys.exit(0)
+    if "--equidistribute" in sys.argv:
+        equidistribute_and_resolve(int(_arg("--equidistribute", 30)))
         sys.exit(0)
     if "--multi-start" in sys.argv:
         multi_start(int(_arg("--multi-start", 8)))

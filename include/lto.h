@@ -247,6 +247,44 @@ int lto_direct_refine(lto_ctx* ctx, int nstate, int n_nodes, const double* X, co
                       double* U_out, double* t_out, int* n_out, int* n_removed, int* passes, int* status,
                       double* errors_out);
 
+/* Direct solutions resampled onto ONE node count n_new, on the device (the reference has no counterpart: its
+ * meshRefine_direct bisects and deletes, it never moves a node).  The input may be ragged, as lto_direct_refine_batch writes it:
+ *   X [nstate x n_cap x n_batch], U [3 x n_cap x n_batch], t [n_cap x n_batch]; trajectory b is its first n_in[b] columns
+ *   (n_in NULL: n_cap everywhere).  Columns from n_in[b] on are never read into a result; they may hold NaN.
+ * Per trajectory and pass, with n = its node count (n_in[b], then n_new):
+ *   estimates  e_i = the errors of lto_direct_defect at `nsteps` on the valid part, bit for bit; a segment whose propagated
+ *              states are not numbers has a NaN estimate;
+ *   monitor    r_i = e_i^(1/8) (the estimate is the local error of the 7th-order solution, e ~ C h^8), w_i = max(r_i,
+ *              w_floor * max_j r_j); all weights 1 if every r_j is 0.  `weights` [(n_cap-1) x n_batch] (finite, > 0 on every
+ *              valid segment; passes must be 1) replace estimates and monitor;
+ *   grid       C_0 = 0, C_{i+1} = C_i + w_i; t'_k = t_i + (g_k - C_i)/w_i (t_{i+1} - t_i) at g_k = k C_{n-1}/(n_new - 1), i the
+ *              largest index with C_i <= g_k; the end points are the old ones bit for bit;
+ *   nodes      i = the largest index with t_i <= t'_k, t_mid = t_i + (t_{i+1} - t_i)/2.  t'_k == t_i, or the last node: a bit
+ *              copy of that node's state and control.  t'_k <= t_mid: forward from x_i with u_i over t'_k - t_i.  Otherwise
+ *              backward from x_{i+1} (velocity reversed, u_{i+1}) over t_{i+1} - t'_k.  nsteps - 1 equal RKF7(8) steps; at
+ *              t'_k == t_mid the span is the sweep's 0.5 (t_{i+1} - t_i), so the state is lto_direct_midpoints' at `nsteps`
+ *              bit for bit.  Control u_i + s (u_{i+1} - u_i), s = (t'_k - t_i)/(t_{i+1} - t_i).
+ * Each further pass repeats this on the previous pass's output.  The call does not re-solve: the output is a guess in the
+ * layout lto_direct_solve_batch takes.
+ *   X_out [nstate x n_new x n_batch], U_out [3 x n_new x n_batch], t_out [n_new x n_batch]
+ *   errors_before [(n_cap-1) x n_batch] or NULL: the estimates of the input, NaN from n_in[b] - 1 on
+ *   errors_after  [(n_new-1) x n_batch] or NULL: the estimates of the output meshes
+ *   status [n_batch] or NULL: 0 resampled; 1 the new times of a pass were not strictly increasing (n_new beyond what the grid
+ *              resolves); 2 a NaN estimate inside the valid part.  With status != 0 the trajectory's outputs are NaN; the
+ *              others are untouched and the call still returns LTO_OK.
+ * LTO_ENULL: a NULL X, U, t, prm, X_out, U_out or t_out.  LTO_EINVAL: nstate not 6 or 7; n_cap < 2; n_batch < 1; n_new < 2;
+ * passes < 1; nsteps < 2; w_floor outside [0, 1) or not finite; an n_in[b] outside [2, n_cap]; times not finite or not strictly
+ * increasing inside a valid part; a weight of a valid segment not finite or <= 0; weights with passes > 1; more than 262 144
+ * segments per trajectory (max(n_cap, n_new) - 1); n_batch > 65535; max(n_cap, n_new) * n_batch * nstate > 2^31 - 1. */
+int lto_direct_resample_batch(lto_ctx* ctx, int nstate, int n_cap, int n_batch, const double* X, const double* U,
+                              const double* t, const int* n_in, int nsteps, const lto_direct_params* prm, int n_new,
+                              const double* weights, double w_floor, int passes, double* X_out, double* U_out, double* t_out,
+                              double* errors_before, double* errors_after, int* status);
+/* One trajectory of n_nodes nodes (n_batch = 1, n_in = NULL). */
+int lto_direct_resample(lto_ctx* ctx, int nstate, int n_nodes, const double* X, const double* U, const double* t, int nsteps,
+                        const lto_direct_params* prm, int n_new, const double* weights, double w_floor, int passes,
+                        double* X_out, double* U_out, double* t_out, double* errors_before, double* errors_after, int* status);
+
 /* Replaces jacobianCalc of multiShoot_CRTBP_direct (:111-143) and the tf partial (:503-516).
  *   Jac_temp    [nstate x nvar x (n_nodes-1) x n_batch], nvar = 2(nstate+3); block i is
  *               d defect_i / d [x_i; x_{i+1}; u_i; u_{i+1}] (variable order of :125), computed from

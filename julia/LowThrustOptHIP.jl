@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, addTimeFinal, tf_sweep, meshRefine_indirect, remesh_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -390,6 +390,32 @@ function direct_refine(ctx::LtoContext, X_all::Matrix{Float64}, u_all::Matrix{Fl
     check(ctx, rc)
     n = Int(n_out[])
     (X_out[:, 1:n], U_out[:, 1:n], t_out[1:n], n, Int(n_removed[]), Int(passes[]), Int(status[]), errors[1:n-1])
+end
+
+"""Direct solutions resampled onto one node count `n_new` in one library call (`lto_direct_resample_batch`, DESIGN 4.17): the new
+grid equidistributes the RKF7(8) estimates (weight e^(1/8), floored at `w_floor` times the largest; `weights` replace them, with
+`passes = 1`), the new nodes lie on the transcription's own half-arcs.  X [nstate x n_cap x n_batch], U [3 x n_cap x n_batch],
+t [n_cap x n_batch]; `n_in` = the valid columns of every trajectory, as `lto_direct_refine_batch` leaves them (nothing: all).
+Returns (X, U, t, errors_before, errors_after, status): status 0, 1 the new times were not strictly increasing, 2 a NaN estimate
+(the outputs of such a trajectory are NaN)."""
+function direct_resample(ctx::LtoContext, X::Array{Float64,3}, U::Array{Float64,3}, t::Matrix{Float64}, nsteps, Isp, MU, DU, TU,
+                         n_new; n_in::Union{Nothing,Vector{Cint}} = nothing, weights::Union{Nothing,Matrix{Float64}} = nothing,
+                         w_floor = 0.1, passes = 1)
+    nstate, n_cap, n_batch = size(X)
+    X_out = zeros(nstate, n_new, n_batch)
+    U_out = zeros(3, n_new, n_batch)
+    t_out = zeros(n_new, n_batch)
+    errors_before = zeros(n_cap - 1, n_batch)
+    errors_after = zeros(n_new - 1, n_batch)
+    status = zeros(Cint, n_batch)
+    prm = Ref(LtoDirectParams(MU, DU, TU, Isp))
+    rc = ccall((:lto_direct_resample_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Cint, Ref{LtoDirectParams}, Cint,
+                Ptr{Cdouble}, Cdouble, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, nstate, n_cap, n_batch, X, U, t, n_in === nothing ? C_NULL : n_in, nsteps, prm, n_new,
+               weights === nothing ? C_NULL : weights, w_floor, passes, X_out, U_out, t_out, errors_before, errors_after, status)
+    check(ctx, rc)
+    (X_out, U_out, t_out, errors_before, errors_after, Int.(status))
 end
 
 """jacobianCalc + tf partial of multiShoot_CRTBP_direct: Jac_full [nstate(n_nodes-1) x n_nodes(nstate+3)+1]

@@ -106,6 +106,11 @@ SIGNATURES = {
                                           _vp, _vp]),
     "lto_direct_refine": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams), C.c_double,
                                     C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_direct_resample_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int,
+                                            C.POINTER(LtoDirectParams), C.c_int, _vp, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                            _vp]),
+    "lto_direct_resample": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(LtoDirectParams), C.c_int, _vp,
+                                      C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_group_create": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(_vp)]),
     "lto_group_destroy": (None, [_vp]),
     "lto_group_last_error": (C.c_char_p, [_vp]),

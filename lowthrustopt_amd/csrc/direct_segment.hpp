@@ -1,7 +1,7 @@
 // direct_segment.hpp -- one segment of the direct transcription on a lane pair: the forward half-arc from node i and the backward
-// half-arc from node i+1 (lane parity = direction) meet through the xchg1 exchange.  The defect sweep (kernels_direct.hip) and the
-// mesh refinement (kernels_direct_refine.hip) evaluate segments through these functions alone, so an estimate or a mid-point of the
-// refinement is the sweep's, bit for bit.
+// half-arc from node i+1 (lane parity = direction) meet through the xchg1 exchange.  The defect sweep (kernels_direct.hip), the
+// mesh refinement (kernels_direct_refine.hip) and the resampling (kernels_direct_resample.hip) evaluate segments through these
+// functions alone, so an estimate or a mid-point of theirs is the sweep's, bit for bit.
 #pragma once
 #include "kernels.hpp"
 #include "rk.hpp"
@@ -58,6 +58,32 @@ __device__ __forceinline__ void direct_segment(const SysDirect<NS>& sys, const i
 #pragma unroll
   for (int c = 0; c < NS; ++c) d[c] = x[c] - xchg1(x[c]);    // fwd lane: state_for - stateF_back  (:101)
   e = fmax(maxErr, xchg1(maxErr));                           // :104
+}
+
+// The estimate the mesh tools decide on (the refinement, kernels_direct_refine.hip; the resampling, kernels_direct_resample.hip).
+// The sweep's fmax drops a NaN (rk.hpp), so a NaN node would read as a perfect segment and be "removed" together with its
+// neighbours, or weigh nothing in a monitor; here a segment whose end states are not numbers has a NaN estimate, which ends the
+// work on its trajectory (numpy's min / max propagate it and both comparisons are false).  Finite data: exactly e.
+template <int NS>
+__device__ __forceinline__ double refine_estimate(const double (&d)[NS], const double e) {
+  double bad = e;
+#pragma unroll
+  for (int c = 0; c < NS; ++c) bad += d[c];
+  return (bad != bad) ? bad : e;
+}
+
+// One segment on this lane pair from explicit operands: xs = this lane's node state (as stored), (ux, uy, uz) its control, hhalf
+// the half span.  Returns the estimate; xs becomes the half-arc's end state (forward lane: the mid-point state).
+template <int NS>
+__device__ __forceinline__ double refine_segment(const DirectConsts& k, const int dir, double (&xs)[NS], const double ux,
+                                                 const double uy, const double uz, const double hhalf, const int half_steps) {
+  SysDirect<NS> sys;
+  double nc;
+  direct_lane(k, dir, ux, uy, uz, sys.L, nc);
+  if (dir) { xs[3] = -xs[3]; xs[4] = -xs[4]; xs[5] = -xs[5]; }   // reverse velocity (direct.jl:92)
+  double d[NS], e;
+  direct_segment<NS>(sys, dir, hhalf, half_steps, xs, d, e);
+  return refine_estimate<NS>(d, e);
 }
 
 }  // namespace lto

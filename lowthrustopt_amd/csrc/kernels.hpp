@@ -293,6 +293,28 @@ struct RemeshNodeArgs {
   int n_new, n_batch;
 };
 hipError_t launch_remesh_nodes(int pm, int method, const IndirectArgs& a, const RemeshNodeArgs& r, hipStream_t st);
+// Resampling of direct solutions onto one node count (kernels_direct_resample.hip).  The current meshes, node-major
+// with `cap` columns per trajectory of which the first n[b] are valid (n null: all of them), and what one pass makes of them.
+struct DirectResampleArgs {
+  const double* X;                 // [B][cap][nstate]
+  const double* U;                 // [B][cap][3]
+  const double* t;                 // [B][cap]
+  const int* n;                    // [B] or null
+  int cap, B, n_new;
+  double MU, kk, isp_g0, TU;       // as DirectArgs
+  int half_steps;
+  double* E;                       // [B][cap-1] estimates of the current meshes, NaN behind the valid part
+  int from_E;                      // 1: the weights are made from E; 0: W holds the caller's
+  double w_floor;
+  double* W;                       // [B][cap-1] weights
+  double* C; long c_stride;        // running sums above kRemeshLdsSegs segments (remesh_scratch_doubles(cap) per trajectory), else null
+  int* status;                     // [B], sticky: 0, 1 new times not strictly increasing, 2 a NaN estimate
+  double* t_new;                   // [B][n_new]
+  double *X_new, *U_new;           // [B][n_new][nstate], [B][n_new][3]
+};
+hipError_t launch_direct_resample_errors(int nstate, const DirectResampleArgs& a, hipStream_t st);   // -> E
+hipError_t launch_direct_resample_grid(const DirectResampleArgs& a, hipStream_t st);                 // E or W -> W, t_new, status
+hipError_t launch_direct_resample_nodes(int nstate, const DirectResampleArgs& a, hipStream_t st);    // t_new -> X_new, U_new
 hipError_t launch_tau_update(double* tau, const double* p, const double* step, int n_batch, hipStream_t st);
 // free tf: tau and tf updates from p [n_batch][3]; the grids t [n_batch][n] from tau_grid, t0 [n_batch], tf [n_batch] and their na
 // copies per trajectory for the line search, tl [n_batch * na][n]

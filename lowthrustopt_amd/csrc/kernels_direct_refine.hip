@@ -18,31 +18,6 @@ namespace lto {
 
 constexpr int kRefineBlock = 256;
 
-// The estimate the refinement decides on.  The sweep's fmax drops a NaN (rk.hpp), so a NaN node would read as a perfect segment
-// and be "removed" together with its neighbours; here a segment whose end states are not numbers has a NaN estimate, which ends
-// both phases for its trajectory (numpy's min / max propagate it and both comparisons are false).  Finite data: exactly e.
-template <int NS>
-__device__ __forceinline__ double refine_estimate(const double (&d)[NS], const double e) {
-  double bad = e;
-#pragma unroll
-  for (int c = 0; c < NS; ++c) bad += d[c];
-  return (bad != bad) ? bad : e;
-}
-
-// One segment on this lane pair from explicit operands: xs = this lane's node state (as stored), (ux, uy, uz) its control, hhalf
-// the half span.  Returns the estimate; xs becomes the half-arc's end state (forward lane: the mid-point state).
-template <int NS>
-__device__ __forceinline__ double refine_segment(const DirectConsts& k, const int dir, double (&xs)[NS], const double ux,
-                                                 const double uy, const double uz, const double hhalf, const int half_steps) {
-  SysDirect<NS> sys;
-  double nc;
-  direct_lane(k, dir, ux, uy, uz, sys.L, nc);
-  if (dir) { xs[3] = -xs[3]; xs[4] = -xs[4]; xs[5] = -xs[5]; }   // reverse velocity (direct.jl:92)
-  double d[NS], e;
-  direct_segment<NS>(sys, dir, hhalf, half_steps, xs, d, e);
-  return refine_estimate<NS>(d, e);
-}
-
 __device__ __forceinline__ DirectConsts refine_consts(const DirectRefineArgs& a) { return DirectConsts{a.MU, a.kk, a.isp_g0, a.TU}; }
 
 // ---- the estimates of the input mesh: lane pair = segment, as k_direct_defect, on the caller's node-major arrays

@@ -1,6 +1,7 @@
 // kernels_remesh.hip -- mesh equidistribution of a converged indirect solution: the new grid from a per-segment
 // monitor (k_remesh_grid) and the nodes of the input's own piecewise trajectory on it (k_remesh_nodes).
 #include "indirect_kernel.hpp"
+#include "scan64.hpp"
 
 namespace lto {
 
@@ -8,45 +9,9 @@ namespace lto {
 // nacc + nrej of a defect sweep), C_0 = 0, C_{i+1} = C_i + w_i, W = C_{n-1}; new node k sits where the piecewise-linear C(t) reaches
 // g_k = k W / (n_new - 1).
 //
-// The scan has ONE summation order whatever the size and wherever the partial sums live (integer counts do not care, real weights
-// do): radix 64 in three levels.  A tile of 64 consecutive entries is scanned by a wavefront with six shift-and-add steps
-// (__shfl_up by 1, 2, .. 32: the DPP row / wave shifts; an LDS round trip per step would cost a barrier each); the tile totals are
-// scanned the same way, and theirs; then every entry adds the inclusive sum of the tiles before its own, top level first.
-// tests/remesh_reference.scan64 restates exactly this order.  64^3 = 262 144 segments is the limit (the host refuses more).
+// The running sum is scan64.hpp's: one summation order whatever the size (tests/remesh_reference.scan64 restates it).
 // The partial sums of up to kRemeshLdsSegs segments stay in LDS; above that the same code runs on a global scratch block
 // (`C`, written and read by this workgroup only, between its own barriers).
-constexpr int kRemeshBlock = 256;
-
-__device__ __forceinline__ double tile_scan(double v, const int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const double u = __shfl_up(v, off, 64);
-    if (lane >= off) v += u;
-  }
-  return v;
-}
-
-// x[0 .. cnt) -> its tiles' inclusive scans in place, tot[T] = total of tile T.  Every wavefront takes whole tiles.
-__device__ __forceinline__ void scan_tiles(double* x, const int cnt, double* tot, const int tid) {
-  const int lane = tid & 63, tiles = (cnt + 63) >> 6;
-  for (int T = tid >> 6; T < tiles; T += kRemeshBlock / 64) {
-    const int i = T * 64 + lane;
-    const double v = tile_scan(i < cnt ? x[i] : 0.0, lane);
-    if (i < cnt) x[i] = v;
-    if (lane == 63) tot[T] = v;
-  }
-  __syncthreads();
-}
-
-// x[i] += inclusive sum of the tiles before i's (inc: the scanned tile totals)
-__device__ __forceinline__ void add_tile_offsets(double* x, const int cnt, const double* inc, const int tid) {
-  for (int i = tid; i < cnt; i += kRemeshBlock) {
-    const int T = i >> 6;
-    if (T) x[i] = inc[T - 1] + x[i];
-  }
-  __syncthreads();
-}
-
 template <bool IN_LDS>
 __global__ __launch_bounds__(kRemeshBlock) void k_remesh_grid(const RemeshGridArgs r) {
 #pragma clang fp contract(off)       // t'_k in the order the restatement writes it: no fused multiply-add

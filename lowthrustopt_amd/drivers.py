@@ -877,7 +877,7 @@ def stacked_guess(n_nodes, tof1, tof2, τ1, X0_times, X0_states, Xf_times, Xf_st
 
 def multiStart_direct(τ1s, tof1s, tof2s, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times, Xf_states, MU, DU, TU,
                       flagEnd=False, β=0.0, allowImpulsive=False, maxIter=100, ctx=None, then_indirect=False, thrustLimit=10.0,
-                      maxIter_indirect=50):
+                      maxIter_indirect=50, remesh_nodes=None, remesh_tol_max=1e-16, remesh_w_floor=None):
     """A multi-start search of the direct method in three library calls: the stacked guesses of all starts (τ1s, tof1s, tof2s:
     scalars or arrays, broadcast to B starts; hotpath.stack_guess), their end targets at (τ1, τ2) (hotpath.direct_end_states) and
     the loop of multiShoot_CRTBP_direct for all of them side by side on their own grids, zero thrust as the guess
@@ -887,7 +887,13 @@ def multiStart_direct(τ1s, tof1s, tof2s, n_nodes, nsteps, mass, Isp, X0_times, 
     order: the indices of the status-0 starts by increasing cost.
     then_indirect: the converged starts are handed to the indirect method (direct_to_indirect: costates from the QP multipliers,
     p = 2 at thrustLimit N, at most maxIter_indirect iterations); the dict gains "indirect" = direct_to_indirect's dict for those
-    starts, in the order of "indirect_starts" (their indices, increasing)."""
+    starts, in the order of "indirect_starts" (their indices, increasing).
+    remesh_nodes (None: nothing of this runs): the converged starts are refined side by side (hotpath.direct_refine: nodes removed
+    below remesh_tol_max / 1000, segments bisected above remesh_tol_max, at most 4 n_nodes nodes), resampled onto remesh_nodes nodes
+    each (meshEquidistribute_direct, two passes, remesh_w_floor or its default) and solved again with fixed ends at their final
+    phases by one hotpath.direct_solve batch.  The dict gains "remesh_starts" (their indices) and "remesh" = a dict of X, U, t,
+    dV, status, iterations, max_defect, nodes_refined, resample_status and errors [(remesh_nodes-1) x starts] (the estimates of the
+    re-solved meshes), or None without a converged start; then_indirect then starts from the re-solved starts of status 0."""
     orbits = hotpath.DirectOrbits(X0_times, X0_states, Xf_times, Xf_states)
     τ1s, tof1s, tof2s = (np.ascontiguousarray(v) for v in np.broadcast_arrays(
         *(np.asarray(v, dtype=np.float64).reshape(-1) for v in (τ1s, tof1s, tof2s))))
@@ -906,15 +912,53 @@ def multiStart_direct(τ1s, tof1s, tof2s, n_nodes, nsteps, mass, Isp, X0_times, 
     out = {"status": status, "iterations": iters, "max_defect": np.abs(defect).max(axis=(0, 1)), "cost": cost, "tau": tau_out,
            "tau_guess": np.vstack([g.tau1, g.tau2_0, g.tau2]), "gap": g.gap, "guess_status": g.status, "X": X, "U": U, "t": t,
            "dV": dV, "defect": defect, "history": hist, "order": order}
+    if remesh_nodes is not None:
+        out["remesh_starts"] = ok
+        out["remesh"] = None
+        if ok.size:
+            parts = hotpath.direct_refine(X[..., ok], U[..., ok], t[:, ok], nsteps, MU, DU, TU, Isp, remesh_tol_max / 1000.0,
+                                          remesh_tol_max, 4 * int(n_nodes), ctx=ctx)
+            kw = {} if remesh_w_floor is None else {"w_floor": remesh_w_floor}
+            Xr, Ur, tr, rs = meshEquidistribute_direct(parts, None, None, 6, None, nsteps, Isp, MU, DU, TU, int(remesh_nodes), ctx=ctx, **kw)
+            s0, sf, _, _, _, _ = hotpath.direct_end_states(np.asfortranarray(tau_out[:, ok]), orbits, ctx=ctx)
+            targets = [hotpath.direct_targets(s0[:, j], sf[:, j], mass, dV[:3, b], dV[3:, b]) for j, b in enumerate(ok)]
+            X2, U2, dV2, t2, d2, st2, it2, _ = hotpath.direct_solve(Xr, Ur, tr, nsteps, MU, DU, TU, Isp, targets, allowImpulsive,
+                                                                    maxIter, ctx=ctx)
+            _, e2 = hotpath.direct_defectCalc(X2, U2, t2, nsteps, MU, DU, TU, Isp, ctx=ctx)
+            out["remesh"] = {"X": X2, "U": U2, "t": t2, "dV": dV2, "status": st2, "iterations": it2,
+                             "max_defect": np.abs(d2).max(axis=(0, 1)), "nodes_refined": np.array([p.n for p in parts]),
+                             "resample_status": rs, "errors": e2}
+            keep = np.flatnonzero(st2 == 0)
+            ok, X, U, t, dV = ok[keep], X2[..., keep], U2[..., keep], t2[:, keep], dV2[:, keep]
     if then_indirect:
         out["indirect_starts"] = ok
         out["indirect"] = None
         if ok.size:
             # the end targets of the frozen step are the states the direct loop ended on (with flagEnd: at the final phases)
-            out["indirect"] = direct_to_indirect(X[..., ok], U[..., ok], t[:, ok], nsteps, mass, Isp, MU, DU, TU, thrustLimit,
-                                                 maxIter_indirect, dV1=dV[:3, ok], dV2=dV[3:, ok], allowImpulsive=allowImpulsive,
+            sel = ok if remesh_nodes is None else slice(None)     # (after a re-mesh X, U, t, dV hold the re-solved starts alone)
+            out["indirect"] = direct_to_indirect(X[..., sel], U[..., sel], t[:, sel], nsteps, mass, Isp, MU, DU, TU, thrustLimit,
+                                                 maxIter_indirect, dV1=dV[:3, sel], dV2=dV[3:, sel], allowImpulsive=allowImpulsive,
                                                  ctx=ctx)
     return out
+
+
+W_FLOOR_DIRECT = 0.1      # meshEquidistribute_direct's default floor of the monitor
+
+
+def meshEquidistribute_direct(X, U, t, nstate, n_in, nsteps, Isp, MU, DU, TU, n_new, passes=2, w_floor=W_FLOOR_DIRECT, ctx=None):
+    """Direct solutions moved onto n_new nodes each whose RKF7(8) estimates are equidistributed (hotpath.direct_resample, one
+    library call; the reference's meshRefine_direct only bisects and deletes).  One trajectory X [nstate x n], U
+    [3 x n], t [n] or a batch with a trailing axis; n_in = the valid columns per trajectory as lto_direct_refine_batch leaves them
+    (None: all).  X may be what hotpath.direct_refine returned (then U, t and n_in are None).  No new segment is longer than
+    1 / w_floor times the finest in monitor measure.  The result is a guess for the solve calls, not a solution.  Returns (X, U, t,
+    status); the full record of the call is kept in `meshEquidistribute_direct.last` (hotpath.DirectResample)."""
+    first = X[0] if isinstance(X, (list, tuple)) and len(X) and isinstance(X[0], hotpath.DirectRefine) else X
+    rows = np.shape(first.X if isinstance(first, hotpath.DirectRefine) else first)[0]
+    if rows != nstate:
+        raise ValueError("meshEquidistribute_direct: X has %d rows, nstate is %d" % (rows, nstate))
+    r = hotpath.direct_resample(X, U, t, nsteps, MU, DU, TU, Isp, n_new, n_in=n_in, w_floor=w_floor, passes=passes, ctx=ctx)
+    meshEquidistribute_direct.last = r
+    return r.X, r.U, r.t, r.status
 
 
 def direct_loop_host(X_all, u_all, τ1, τ2, t_TU, dV1, dV2, MU, DU, TU, n_nodes, nsteps, mass, Isp, X0_times, X0_states, Xf_times,

@@ -644,6 +644,78 @@ def direct_refine(X, U, t, nsteps, MU, DU, TU, Isp, tol_min, tol_max, max_nodes,
     return out if batched else out[0]
 
 
+DirectResample = collections.namedtuple("DirectResample", "X U t errors_before errors_after status")
+
+
+def _ragged_slab(parts):
+    """The results of direct_refine's batch form side by side: (X [ns x cap x B], U, t [cap x B], n_in [B]), NaN behind every
+    trajectory's own nodes -- the layout lto_direct_refine_batch writes."""
+    cap, B, ns = max(p.n for p in parts), len(parts), parts[0].X.shape[0]
+    X = np.full((ns, cap, B), np.nan, order="F")
+    U = np.full((3, cap, B), np.nan, order="F")
+    t = np.full((cap, B), np.nan, order="F")
+    for b, p in enumerate(parts):
+        X[:, :p.n, b], U[:, :p.n, b], t[:p.n, b] = p.X, p.U, p.t
+    return X, U, t, np.array([p.n for p in parts], dtype=np.int32)
+
+
+def direct_resample(X, U=None, t=None, nsteps=10, MU=None, DU=None, TU=None, Isp=None, n_new=None, n_in=None, weights=None,
+                    w_floor=0.1, passes=1, ctx=None):
+    """Direct solutions resampled onto one node count n_new on the device (lto_direct_resample_batch): the new grid
+    equidistributes the RKF7(8) estimates of lto_direct_defect at `nsteps` (weight e^(1/8), floored at w_floor times the largest),
+    the new nodes lie on the transcription's own half-arcs.  X [nstate x n_cap (x B)], U [3 x n_cap (x B)], t [n_cap] or
+    [n_cap x B]; n_in [B] = the valid columns of every trajectory (None: all), the rest is never read.  X may instead be what
+    direct_refine returns -- one DirectRefine or the batch form's list -- with U and t left out.  weights [(n_cap-1) (x B)]
+    replace the monitor (passes must be 1).  Returns DirectResample(X [nstate x n_new (x B)], U, t [n_new (x B)], errors_before
+    [(n_cap-1) (x B)] (NaN behind the valid part), errors_after [(n_new-1) (x B)], status: 0, 1 the new times were not strictly
+    increasing, 2 a NaN estimate; the outputs of such a trajectory are NaN)."""
+    if isinstance(X, DirectRefine) or (isinstance(X, (list, tuple)) and len(X) and isinstance(X[0], DirectRefine)):
+        if U is not None or t is not None or n_in is not None:
+            raise ValueError("direct_resample: a direct_refine result brings its own U, t and node counts")
+        batched = not isinstance(X, DirectRefine)
+        X, U, t, n_in = _ragged_slab(list(X) if batched else [X])
+    else:
+        X = _f64(X)
+        batched = X.ndim == 3
+    if None in (MU, DU, TU, Isp) or n_new is None:
+        raise ValueError("direct_resample: MU, DU, TU, Isp and n_new are required")
+    X = _f64(X)
+    U = _f64(U)
+    ns, n, B, _ = _batch_dims(X)
+    if ns not in (6, 7):
+        raise ValueError("direct_resample: X must have 6 or 7 rows; got shape %s" % (X.shape,))
+    if U.shape != (3,) + X.shape[1:]:
+        raise ValueError("direct_resample: U must be [3 x n_cap] or [3 x n_cap x n_batch], as X; got shape %s" % (U.shape,))
+    tt, ntg = _tgrids(t, n, B)
+    if ntg != B:
+        tt = np.asfortranarray(np.repeat(tt[:, None], B, axis=1))
+    if n_in is not None:
+        n_in = np.ascontiguousarray(np.atleast_1d(n_in), dtype=np.int32)
+        if n_in.shape != (B,):
+            raise ValueError("direct_resample: n_in must have one entry per trajectory")
+    if weights is not None:
+        weights = _f64(weights)
+        if weights.shape != (n - 1,) + X.shape[2:]:
+            raise ValueError("direct_resample: weights must be [(n_cap-1)] or [(n_cap-1) x n_batch]")
+    ctx = ctx or default_context()
+    prm = LtoDirectParams(float(MU), float(DU), float(TU), float(Isp))
+    n_new = int(n_new)
+    m = max(n_new, 2)
+    Xo = np.empty((ns, m, B), order="F")
+    Uo = np.empty((3, m, B), order="F")
+    to = np.empty((m, B), order="F")
+    eb = np.empty((n - 1, B), order="F")
+    ea = np.empty((m - 1, B), order="F")
+    status = np.zeros(B, dtype=np.int32)
+    ctx.check(ctx.fn("direct_resample_batch")(ctx.handle, ns, n, B, _ptr(X), _ptr(U), _ptr(tt), _ptr(n_in) if n_in is not None else None,
+                                              int(nsteps), C.byref(prm), n_new, _ptr(weights) if weights is not None else None,
+                                              float(w_floor), int(passes), _ptr(Xo), _ptr(Uo), _ptr(to), _ptr(eb), _ptr(ea),
+                                              _ptr(status)))
+    if not batched:
+        return DirectResample(Xo[:, :, 0], Uo[:, :, 0], to[:, 0], eb[:, 0], ea[:, 0], int(status[0]))
+    return DirectResample(Xo, Uo, to, eb, ea, status)
+
+
 def direct_jacobian_blocks(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None, out=None):
     """Compact direct Jacobian: (Jac_temp[nstate x nvar x (n-1)], ddefect_dtf[nstate x (n-1)], defect, errors);
     nvar = 2(nstate+3), variable order [x_i; x_{i+1}; u_i; u_{i+1}] (:125).  out = (Jac_temp, ddefect_dtf, defect, errors):
