@@ -92,7 +92,29 @@ def mass_run(XC, t, Isp, rho_target, ctx, verbose=True, n=30, mass0=1e3):
     return out
 
 
-def main(seed=0, verbose=True, rho_target=1e-2, python_loop=False, mass_isp=None):
+def print_arcs(XC1, t, mass, rho_target, ctx):
+    """--arcs: the burn list and dv of every rho level of the ladder (one batched call behind homotopy_solve), beside the
+    trapezoid of umag over 200 samples of the dense output."""
+    rhos = [1.0]
+    while rhos[-1] / 2 > rho_target:
+        rhos.append(rhos[-1] / 2)
+    rhos.append(rho_target)
+    X, _, status, _, arcs = drivers.homotopy_solve(XC1, t, MU, DU, TU, mass, 0.05, rhos, ctx=ctx, verbose=False, arcs=True)
+    aL = 0.05 / mass / 1e3 * TU ** 2 / DU
+    for k, r in enumerate(rhos):
+        if arcs[k] is None:
+            print("arcs, rho = %-9g not converged (status %d)" % (r, status[k]))
+            continue
+        XD, td = lto.densify(X[:, :, k], t, lto.make_params(MU, DU, TU, 0.05, mass, 1.0, 1.0, r), 200, ctx=ctx)
+        u = 0.5 * (1 + np.tanh((np.linalg.norm(XD[9:12], axis=0) - 1) / (2 * r))) * aL
+        trap = float(np.sum(np.diff(td) * (u[1:] + u[:-1]) / 2))
+        a = arcs[k]
+        burns = ", ".join("%.3f-%.3f d" % (b0 * TU / 86400.0, b1 * TU / 86400.0) for b0, b1 in a["arcs"])
+        print("arcs, rho = %-9g dv %.6e DU/TU = %.3f m/s (trapezoid %.6e), burning %.3f d in %d arcs: %s"
+              % (r, a["dv"], a["dv_ms"], trap, a["burn_days"], len(a["arcs"]), burns))
+
+
+def main(seed=0, verbose=True, rho_target=1e-2, python_loop=False, mass_isp=None, arcs=False):
     ctx = lto.default_context(0)
     # default: every multiShoot_CRTBP_indirect call is ONE library call (lto_indirect_solve: Newton loop, line search
     # and end-state pinning on the device); --python-loop drives the same device operators from the Python mirror of
@@ -118,6 +140,8 @@ def main(seed=0, verbose=True, rho_target=1e-2, python_loop=False, mass_isp=None
                 lam = np.linalg.norm(XD[9:12], axis=0)
                 thr = 0.5 * (1 + np.tanh((lam - 1) / (2 * rho_target))) * 0.05
                 print("thrust profile: on %.0f %% of the flight, max %.3f N" % (100 * np.mean(thr > 0.025), thr.max()))
+                if arcs:
+                    print_arcs(XC1, t, mass, rho_target, ctx)
     if mass_isp is not None and flag == 0:
         res["mass"] = mass_run(XC, t, mass_isp, rho_target, ctx, verbose, n, mass)
     print("wall time %.2f s" % (time.perf_counter() - t0))
@@ -125,7 +149,7 @@ def main(seed=0, verbose=True, rho_target=1e-2, python_loop=False, mass_isp=None
 
 
 if __name__ == "__main__":
-    # usage: halo_transfer_demo.py [rho_target] [-q] [--python-loop] [--mass [Isp]]
+    # usage: halo_transfer_demo.py [rho_target] [-q] [--python-loop] [--mass [Isp]] [--arcs]
     argv = sys.argv[1:]
     mass_isp = None
     if "--mass" in argv:
@@ -136,4 +160,5 @@ if __name__ == "__main__":
             del argv[i + 1]
         del argv[i]
     args = [a for a in argv if not a.startswith("-")]
-    main(rho_target=float(args[0]) if args else 1e-2, verbose="-q" not in argv, python_loop="--python-loop" in argv, mass_isp=mass_isp)
+    main(rho_target=float(args[0]) if args else 1e-2, verbose="-q" not in argv, python_loop="--python-loop" in argv, mass_isp=mass_isp,
+         arcs="--arcs" in argv)

@@ -718,6 +718,36 @@ int lto_indirect_dense_dev(lto_indirect_plan* plan, void* stream, const double* 
                            int n_tgrids, const int* first, const double* t_samples, double* Y, long ldy,
                            double* final_state);
 
+/* Switch times, burn arcs and dv of indirect solutions.  For a trajectory with parameters (thrustLimit, mass, p, rho):
+ * n = |lambda_v|, aL = thrustLimit / mass / 1e3 * TU^2 / DU, umag(n) the control law of stateCostate_deriv.jl:36-53.  The engine is
+ * ON iff g > 0 with   p = 0: always on (no event);   p = 1: g = n - 1 (more than half thrust);   p > 1: g = n - p aL^(p-1) (clamped
+ * at the limit).  The trajectory is the piecewise multiple-shooting one: segment i is the flow from node i over [t_i, t_{i+1}], as
+ * the defect sweep integrates it.  Every segment integrates (y, q), q' = umag(n), q(t_i) = 0, with the integrator of the call --
+ * LTO_RK4 (`steps` steps) or LTO_DOP853_ADAPTIVE (all 13 components in the error norm, so the controller resolves the switch);
+ * any other method, or ndim != 12: LTO_EUNSUPPORTED.  After every accepted step the on-state at the step's two ends is compared;
+ * where it differs the crossing is bracketed by trial steps of the same formula from the step's start state, until the bracket's
+ * ends are adjacent doubles in absolute time (at most 60 halvings), and t_event is the bracket's upper end: the first time on the
+ * new side.  Integration continues from the accepted step unchanged.  TWO CROSSINGS INSIDE ONE ACCEPTED STEP ARE NOT SEEN.  A
+ * segment keeps at most 4 events.  Where the on-state at the end of segment i differs from the one at the start of segment i+1
+ * (the node's discontinuity straddles g = 0) an event at t_{i+1} is emitted, so that every list strictly alternates and its first
+ * kind is +1 iff the trajectory starts off.
+ * Outputs (column-major, trajectory b):  n_events[b];  t_event[max_events x B] ascending, NaN beyond n_events;  kind[max_events x B]
+ * +1 off->on, -1 on->off, 0 unused;  on0[b] the on-state at t[0];  dv[b] (DU/TU) the sum of the segments' q;  burn_time[b] (TU);
+ * dv_seg[(n_nodes-1) x B] the segments' q (may be NULL);  status[b]: 0 ok;  1 more than max_events events, or more than 4 in one
+ * segment: the lists are truncated in time order, n_events is the count of all events located, dv and burn_time are complete;
+ * 2 non-finite trajectory: every output of it is NaN or 0.
+ * n_tgrids and n_prm are 1 or n_batch.  LTO_ENULL; LTO_EINVAL (max_events < 1, n_nodes < 2, t not strictly increasing).
+ * _dev: X [12][ldx], t and the outputs are device arrays in the layouts above; asynchronous on `stream`. */
+int lto_indirect_events_batch(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                              const lto_params* prm, int n_prm, const lto_integrator* integ, int max_events, int* n_events,
+                              double* t_event, int* kind, int* on0, double* dv, double* burn_time, double* dv_seg, int* status);
+int lto_indirect_events(lto_ctx* ctx, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                        const lto_integrator* integ, int max_events, int* n_events, double* t_event, int* kind, int* on0,
+                        double* dv, double* burn_time, double* dv_seg, int* status);
+int lto_indirect_events_dev(lto_indirect_plan* plan, void* stream, const double* X, long ldx, const double* t, int n_tgrids,
+                            int max_events, int* n_events, double* t_event, int* kind, int* on0, double* dv, double* burn_time,
+                            double* dv_seg, int* status);
+
 int lto_direct_plan_create(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, int nsteps,
                            const lto_direct_params* prm, lto_direct_plan** out);
 void lto_direct_plan_destroy(lto_direct_plan* plan);

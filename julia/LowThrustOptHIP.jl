@@ -336,6 +336,34 @@ function remesh_batch(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::Matrix{Fl
     (XC, t, Int.(status), Int.(iters), Int.(before), Int.(after))
 end
 
+"""Switch times, burn arcs and dv of n_batch indirect solutions (`lto_indirect_events_batch`, DESIGN 4.18): `XC_all`
+[12 x n_nodes x n_batch], `t_TU` [n_nodes x n_batch], `params` a vector of n_batch parameter tuples.  Per trajectory a named tuple
+(arcs = [(t_on, t_off)] in TU, dv in DU/TU, burn_time in TU, n_events, status)."""
+function thrust_arcs(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::Matrix{Float64}, params::Vector; max_events::Integer = 64,
+                     integ::LtoIntegrator = LtoIntegrator())
+    ndim, n_nodes, B = size(XC_all)
+    prm = [LtoParams(q) for q in params]
+    n_events = zeros(Cint, B); t_event = fill(NaN, max_events, B); kind = zeros(Cint, max_events, B); on0 = zeros(Cint, B)
+    dv = zeros(B); burn = zeros(B); status = zeros(Cint, B)
+    rc = ccall((:lto_indirect_events_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Cint,
+                Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, ndim, n_nodes, B, XC_all, t_TU, B, prm, length(prm), Ref(integ), max_events, n_events, t_event, kind, on0,
+               dv, burn, C_NULL, status)
+    check(ctx, rc)
+    map(1:B) do b
+        arcs = Tuple{Float64,Float64}[]
+        on = on0[b] != 0; mark = t_TU[1, b]
+        for k in 1:min(n_events[b], max_events)
+            isnan(t_event[k, b]) && break
+            on ? push!(arcs, (mark, t_event[k, b])) : (mark = t_event[k, b])
+            on = !on
+        end
+        (on && status[b] == 0) && push!(arcs, (mark, t_TU[end, b]))
+        (arcs = arcs, dv = dv[b], burn_time = burn[b], n_events = Int(n_events[b]), status = Int(status[b]))
+    end
+end
+
 # ---------------------------------------------------------------------------------------------- direct
 "defectCalc of multiShoot_CRTBP_direct: returns (defect1[nstate x (n_nodes-1)], errors[n_nodes-1])."
 function direct_defectCalc(ctx::LtoHandle, X_all::Matrix{Float64}, u_all::Matrix{Float64}, t_TU::Vector{Float64},

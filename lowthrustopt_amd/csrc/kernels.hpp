@@ -107,6 +107,29 @@ struct DenseArgs {
   double* final_state;     // [ND][n_batch] or null: x(t_n) of every trajectory
 };
 hipError_t launch_indirect_dense(int ndim, int pm, int method, const IndirectArgs& a, const DenseArgs& d, hipStream_t st);
+// Switch times, burn arcs and dv (kernels_events.hip).  The per-segment records of k_indirect_events, struct-of-arrays
+// over the S segments, and what k_events_compact makes of them per trajectory.
+constexpr int kEventsPerSeg = 4;   // crossings a segment keeps
+struct EventsArgs {
+  double* tev;                     // [kEventsPerSeg][S] crossing times of the segment, in order
+  double* q;                       // [S] integral of umag over the segment (NaN: something of the segment is not finite)
+  double* ont;                     // [S] time the engine is on inside the segment
+  int* nev;                        // [S] crossings located (may exceed kEventsPerSeg: the true count)
+  int* on_s; int* on_e;            // [S] on-state at the segment's start / end
+  int max_events;
+  int* n_events;                   // [B]
+  double* t_event; int* kind;      // [B][max_events]
+  int* on0;                        // [B]
+  double* dv; double* burn;        // [B]
+  double* dv_seg;                  // [S] or null
+  int* status;                     // [B]
+};
+inline size_t events_record_bytes(long S) {
+  return ((sizeof(double) * (kEventsPerSeg + 2) + sizeof(int) * 3) * (size_t)S + 255) & ~(size_t)255;
+}
+// 12-dim, M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
+hipError_t launch_indirect_events(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st);
+hipError_t launch_events_compact(const IndirectArgs& a, const EventsArgs& e, int n_batch, hipStream_t st);
 // wave-specialised STM kernel (kernels_indirect_coop.hip): base wave + column waves per 16 segments
 hipError_t launch_indirect_stm_coop(int ndim, int pm, int method, const IndirectArgs& a, hipStream_t st);
 // the same with every 12-component state split over two lanes (kernels_indirect_coop2.hip), DOP853 adaptive only; the 14-dim form

@@ -1,0 +1,271 @@
+// kernels_events.hip -- switch times, burn arcs and dv of indirect solutions, gfx950.
+//
+// k_indirect_events: lane = segment.  The lane integrates the augmented state (y[12], q), q' = umag(|lambda_v|), q(t_i) = 0, over
+// [t_i, t_{i+1}] with the plan's integrator (RK4 x steps, or DOP853 with all 13 components in the error norm), compares the engine's
+// on-state at the two ends of every accepted step and, where it differs, brackets the crossing by trial steps of the same formula
+// from the step's start state with length theta h: bisection in theta until the bracket's ends are adjacent doubles in absolute
+// time, at most 60 halvings; t_event is the bracket's upper end (the first time on the new side).  Integration goes on from the
+// accepted step unchanged -- the law is continuous, nothing restarts.  TWO crossings inside one accepted step leave the on-state
+// at its ends equal and are not seen.  One launch per control-law class (kernels.hpp for_classes), per-segment records
+// struct-of-arrays.
+//
+// k_events_compact: one wavefront per trajectory over its segments, 64 at a time: an exclusive scan of the per-segment counts (the
+// joins included: where the on-state at the end of segment i differs from the one at the start of segment i+1, an event at
+// t_{i+1}), an ordered gather into the trajectory's list, dv and burn_time as lane-strided partial sums closed by a butterfly.  No
+// atomics: a trajectory's result does not depend on its batch.
+#include <hip/hip_runtime.h>
+
+#include "indirect_kernel.hpp"
+
+namespace lto {
+
+namespace {
+
+// The augmented system: the lean base RHS of the defect-only sweeps and of k_indirect_dense, and q' = umag as that RHS forms it.
+template <int PM>
+struct SysEvents {
+  static constexpr int DIM = 13;
+  TrajParams tp;
+  __device__ __forceinline__ void rhs(const double (&y)[13], double (&k)[13]) const {
+    double yb[12], kb[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) yb[i] = y[i];
+    rhs12_base<PM>(yb, tp, kb);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) k[i] = kb[i];
+    const double n2 = __builtin_fma(y[9], y[9], __builtin_fma(y[10], y[10], y[11] * y[11]));
+    const double inv_n = inv_norm_guarded(n2);
+    double m, ua;
+    control_base12<PM>(tp, n2 * inv_n, inv_n, m, ua);
+    k[12] = m;
+  }
+};
+
+// Threshold of the event function g = |lambda_v| - thr: p = 1: 1 (more than half thrust); p > 1: p aL^(p-1) (clamped at the limit)
+template <int PM>
+__device__ __forceinline__ double event_threshold(const TrajParams& tp) {
+  if (PM == PM_P1) return 1.0;
+  if (PM == PM_P2) return 2.0 * tp.accel_limit;
+  if (PM == PM_PGEN) return tp.p * pow(tp.accel_limit, tp.p - 1.0);
+  return 0.0;
+}
+// the engine is on iff g > 0 (g == 0, and a NaN, are off); p = 0: always on.  A double, not a bool (run_dop853's comment).
+template <int PM>
+__device__ __forceinline__ double on_state(const double (&y)[13], const double thr) {
+  if (PM == PM_P0) return 1.0;
+  const double n2 = __builtin_fma(y[9], y[9], __builtin_fma(y[10], y[10], y[11] * y[11]));
+  const double n = n2 * inv_norm_guarded(n2);
+  return (n - thr > 0.0) ? 1.0 : 0.0;
+}
+
+// What a lane keeps of its segment while it steps.
+struct SegEvents {
+  double on;          // current on-state
+  double tmark;       // since when it is on
+  double ont;         // on-time so far
+  double e0, e1, e2, e3;
+  int nev;
+  __device__ __forceinline__ void crossing(const double tev, const double on_new) {
+    e0 = (nev == 0) ? tev : e0;
+    e1 = (nev == 1) ? tev : e1;
+    e2 = (nev == 2) ? tev : e2;
+    e3 = (nev == 3) ? tev : e3;
+    ++nev;
+    if (on != 0.0) ont += tev - tmark;
+    else tmark = tev;
+    on = on_new;
+  }
+};
+
+// The step from absolute time t0 over h changed the on-state from on_prev: bracket the crossing in theta.  trial(theta h, yt): the
+// state one step of length theta h from the step's start state.
+template <int PM, class Trial>
+__device__ __forceinline__ double locate_crossing(const double t0, const double h, const double on_prev, const double thr, Trial&& trial) {
+  double lo = 0.0, hi = 1.0;
+  double t_hi = t0 + h;
+  for (int k = 0; k < 60; ++k) {
+    const double mid = 0.5 * (lo + hi);
+    double yt[13];
+    trial(mid * h, yt);
+    if (on_state<PM>(yt, thr) == on_prev) lo = mid;
+    else hi = mid;
+    const double t_lo = __builtin_fma(lo, h, t0);
+    t_hi = __builtin_fma(hi, h, t0);
+    if (!(t_hi > nextafter(t_lo, __builtin_huge_val()))) break;     // adjacent doubles (or the same one)
+  }
+  return t_hi;
+}
+
+template <int PM, int METHOD>
+__global__ __launch_bounds__(64) void k_indirect_events(const IndirectArgs a, const EventsArgs ev) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= a.S) return;
+  const int traj = s / a.seg_per_traj;
+  const int i = s - traj * a.seg_per_traj;
+  const long node = (long)traj * a.n_nodes + i;
+  const long tg = (long)traj * a.t_stride + i;
+  using Sys = SysEvents<PM>;
+  Sys sys;
+  sys.tp = a.tp[(long)traj * a.tp_stride];
+  if (a.class_filter && p_class(sys.tp.p) != PM) return;
+  const double thr = event_threshold<PM>(sys.tp);
+  double y[13];
+  double next_sum = 0.0;                          // node i + 1 only has to be finite
+#pragma unroll
+  for (int c = 0; c < 12; ++c) { y[c] = a.X[c * a.ldx + node]; next_sum += a.X[c * a.ldx + node + 1]; }
+  y[12] = 0.0;
+  const double ta = a.t[tg], tb = a.t[tg + 1];
+  const double span = tb - ta;
+  SegEvents se;
+  se.on = on_state<PM>(y, thr);
+  se.tmark = ta; se.ont = 0.0; se.nev = 0;
+  se.e0 = se.e1 = se.e2 = se.e3 = __builtin_nan("");
+  const double on_start = se.on;
+
+  if (METHOD == M_RK4) {
+    const double h = span / (double)a.steps;
+    for (int k = 0; k < a.steps; ++k) {
+      double y0[13];
+#pragma unroll
+      for (int c = 0; c < 13; ++c) y0[c] = y[c];
+      rk4_step(sys, h, y);
+      if (PM != PM_P0) {
+        const double on1 = on_state<PM>(y, thr);
+        if (on1 != se.on) {
+          const double tev = locate_crossing<PM>(__builtin_fma((double)k, h, ta), h, se.on, thr, [&](const double th, double (&yt)[13]) {
+#pragma unroll
+            for (int c = 0; c < 13; ++c) yt[c] = y0[c];
+            rk4_step(sys, th, yt);
+          });
+          se.crossing(tev, on1);
+        }
+      }
+    }
+  } else {
+    int nacc = 0, nrej = 0;
+    run_dop853_stepping<Sys, 13>(sys, span, a.rtol, a.atol, a.max_steps, y, nacc, nrej,
+                                 [&](const double t, const double h, const double (&y0)[13], double (&K)[13][13], const double (&yn)[13]) {
+      if (PM == PM_P0) return;
+      const double on1 = on_state<PM>(yn, thr);
+      if (on1 != se.on) {
+        const double tev = locate_crossing<PM>(ta + t, h, se.on, thr, [&](const double th, double (&yt)[13]) {
+          double E5, E3;
+          (void)dop853_try<Sys, 13>(sys, th, a.rtol, a.atol, y0, K, yt, E5, E3);
+        });
+        se.crossing(tev, on1);
+      }
+    });
+  }
+  if (se.on != 0.0) se.ont += tb - se.tmark;
+  double fin = next_sum;
+#pragma unroll
+  for (int c = 0; c < 13; ++c) fin += y[c];
+  fin += se.ont;
+  const bool finite = (fin - fin) == 0.0;
+  const long S = a.S;
+  ev.tev[0 * S + s] = se.e0; ev.tev[1 * S + s] = se.e1; ev.tev[2 * S + s] = se.e2; ev.tev[3 * S + s] = se.e3;
+  ev.q[s] = finite ? y[12] : __builtin_nan("");
+  ev.ont[s] = finite ? se.ont : __builtin_nan("");
+  ev.nev[s] = se.nev;
+  ev.on_s[s] = (on_start != 0.0) ? 1 : 0;
+  ev.on_e[s] = (se.on != 0.0) ? 1 : 0;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) { const int u = __shfl_xor(v, off, 64); v = u < v ? u : v; }
+  return v;
+}
+__device__ __forceinline__ int wave_scan_incl(int v, const int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int u = __shfl_up(v, off, 64);
+    if (lane >= off) v += u;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(64) void k_events_compact(const IndirectArgs a, const EventsArgs ev, const int n_batch) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= n_batch) return;
+  const int nseg = a.seg_per_traj, M = ev.max_events;
+  const long s0 = (long)b * nseg, S = a.S;
+  const double* tg = a.t + (long)b * a.t_stride;
+  double* t_out = ev.t_event + (long)b * M;
+  int* k_out = ev.kind + (long)b * M;
+  // dv and burn_time: lane l sums the segments l, l + 64, .. in order, then the butterfly
+  double pq = 0.0, pt = 0.0;
+  for (int i = lane; i < nseg; i += 64) { pq += ev.q[s0 + i]; pt += ev.ont[s0 + i]; }
+  const double dv = wave_sum(pq), bt = wave_sum(pt);
+  const bool bad = !((dv - dv) == 0.0 && (bt - bt) == 0.0);
+  int base = 0, limit = M, over = 0;
+  if (!bad) {
+    for (int c0 = 0; c0 < nseg; c0 += 64) {
+      const int i = c0 + lane;
+      const bool valid = i < nseg;
+      const long s = s0 + (valid ? i : 0);
+      const int nv = valid ? ev.nev[s] : 0;
+      const int os = valid ? ev.on_s[s] : 0;
+      const int join = (valid && i + 1 < nseg && ev.on_e[s] != ev.on_s[s + 1]) ? 1 : 0;
+      const int cnt = nv + join;
+      const int incl = wave_scan_incl(cnt, lane);
+      const int first = base + incl - cnt;
+      // a segment with more crossings than it keeps: the list ends ahead of the first one that is missing
+      const int hole = wave_min(nv > kEventsPerSeg ? first + kEventsPerSeg : 0x7fffffff);
+      if (hole < limit) limit = hole;
+      if (hole != 0x7fffffff) over = 1;
+      const int kept = nv < kEventsPerSeg ? nv : kEventsPerSeg;
+      for (int k = 0; k < kept; ++k) {
+        const int pos = first + k;
+        if (pos < limit) { t_out[pos] = ev.tev[(long)k * S + s]; k_out[pos] = ((os + k) & 1) ? -1 : 1; }
+      }
+      if (join) {
+        const int pos = first + nv;
+        if (pos < limit) { t_out[pos] = tg[i + 1]; k_out[pos] = ev.on_s[s + 1] ? 1 : -1; }
+      }
+      base += __shfl(incl, 63, 64);
+    }
+  }
+  const int listed = bad ? 0 : (base < limit ? base : limit);
+  for (int p = listed + lane; p < M; p += 64) { t_out[p] = __builtin_nan(""); k_out[p] = 0; }
+  if (ev.dv_seg)
+    for (int i = lane; i < nseg; i += 64) ev.dv_seg[s0 + i] = bad ? __builtin_nan("") : ev.q[s0 + i];
+  if (lane == 0) {
+    ev.n_events[b] = bad ? 0 : base;
+    ev.on0[b] = bad ? 0 : ev.on_s[s0];
+    ev.dv[b] = bad ? __builtin_nan("") : dv;
+    ev.burn[b] = bad ? __builtin_nan("") : bt;
+    ev.status[b] = bad ? 2 : ((base > M || over) ? 1 : 0);
+  }
+}
+
+template <int METHOD>
+hipError_t launch_events_pm(int pm, const IndirectArgs& a0, const EventsArgs& e, hipStream_t st) {
+  dim3 grid((a0.S + 63) / 64);
+  // every class is launched and the error state read once, behind the last launch (as launch_dense_pm)
+  (void)for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) {
+    hipLaunchKernelGGL((k_indirect_events<decltype(cls)::value, METHOD>), grid, dim3(64), 0, st, a, e);
+    return hipSuccess;
+  });
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_indirect_events(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st) {
+  if (method == M_RK4) return launch_events_pm<M_RK4>(pm, a, e, st);
+  if (method == M_DOP853_ADAPTIVE) return launch_events_pm<M_DOP853_ADAPTIVE>(pm, a, e, st);
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_events_compact(const IndirectArgs& a, const EventsArgs& e, int n_batch, hipStream_t st) {
+  hipLaunchKernelGGL(k_events_compact, dim3(n_batch), dim3(64), 0, st, a, e, n_batch);
+  return hipGetLastError();
+}
+
+}  // namespace lto

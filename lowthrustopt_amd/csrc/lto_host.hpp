@@ -119,6 +119,7 @@ struct lto_indirect_plan {
   int stm_swept;            // an STM sweep has run on this plan
   int stage_failed;         // an allocation of record staging failed: the sweeps gather from the caller's arrays (lto_indirect_plan_staging)
   int out_blocks;           // LTO_LAYOUT_BLOCKS: Phi [S][144] and defect [S][12] per-segment blocks instead of struct-of-arrays (lto_indirect_plan_set_output_layout)
+  void* d_events;           // per-segment records of lto_indirect_events_dev (kernels.hpp events_record_bytes), allocated at its first call
 };
 
 struct lto_direct_plan {

@@ -1214,7 +1214,51 @@ def controlLaw_cart(lambda_v, thrustLimit, p, rho, mass, DU=None, TU=None):
         return -umag * lam / n * mass * DU * 1e3 / TU ** 2          # DU/TU^2 -> N (:439)
 
 
-def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, maxIter=10, max_waves=12, ctx=None, verbose=True):
+def thrust_arcs(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, p, rho, Isp=None, max_events=64, integ=None, ctx=None):
+    """Burn arcs and dv of indirect solutions, read off the integration itself (hotpath.indirect_events) instead of
+    a plot of controlLaw_cart along densify (indirect.jl:348-440).  XC_all [12 x n] or [12 x n x B], t_TU [n] or [n x B]; mass,
+    thrustLimit, p and rho scalars or one per trajectory.  Per trajectory a dict: arcs = [(t_on, t_off)] in TU clipped to
+    [t0, tf], dv (DU/TU), dv_ms (m/s), burn_time (TU), burn_days, n_events, status, and with Isp the rocket-equation propellant
+    mass (1 - exp(-dv_ms / (Isp 9.81))) in kg.  A list of dicts for a batch, one dict otherwise."""
+    XC = np.asarray(XC_all, dtype=np.float64)
+    if XC.ndim not in (2, 3) or XC.shape[0] != 12:
+        raise ValueError("XC_all must be [12 x n] or [12 x n x B]")
+    batched = XC.ndim == 3
+    B = XC.shape[2] if batched else 1
+    t = np.asarray(t_TU, dtype=np.float64)
+    if t.shape not in ((XC.shape[1],), (XC.shape[1], B)):
+        raise ValueError("t_TU must be [n] or [n x B]")
+    per = [np.broadcast_to(np.asarray(v, dtype=np.float64), (B,)) for v in (mass, thrustLimit, p, rho)]
+    prms = [hotpath.make_params(MU, DU, TU, per[1][b], per[0][b], 1.0, per[2][b], per[3][b]) for b in range(B)]
+    ev = hotpath.indirect_events(XC if batched else XC[:, :, None], t if t.ndim == 1 else t, prms, max_events, integ, ctx)
+    out = []
+    for b in range(B):
+        tb = t if t.ndim == 1 else t[:, b]
+        t0, tf = float(tb[0]), float(tb[-1])
+        k = min(int(ev.n_events[b]), int(max_events))
+        times = ev.t_event[:k, b]
+        times = times[np.isfinite(times)]
+        on, mark, arcs = bool(ev.on0[b]), t0, []
+        for te in times:
+            if on:
+                arcs.append((mark, float(te)))
+            else:
+                mark = float(te)
+            on = not on
+        if on and ev.status[b] == 0:
+            arcs.append((mark, tf))
+        dv = float(ev.dv[b])
+        dv_ms = dv * DU / TU * 1e3
+        r = dict(arcs=arcs, dv=dv, dv_ms=dv_ms, burn_time=float(ev.burn_time[b]), burn_days=float(ev.burn_time[b]) * TU / 86400.0,
+                 n_events=int(ev.n_events[b]), status=int(ev.status[b]))
+        if Isp is not None:
+            r["propellant"] = float(per[0][b] * (1.0 - np.exp(-dv_ms / (Isp * 9.81))))
+        out.append(r)
+    return out if batched else out[0]
+
+
+def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, maxIter=10, max_waves=12, ctx=None, verbose=True,
+                   arcs=False):
     """Solve the whole smoothing ladder rho_0 > rho_1 > ... concurrently.  reduceFuel_indirect walks the
     ladder one level at a time, halving rho after each success (HelperFunctions.jl:158-188); here every unsolved level is
     one trajectory of a batched device Newton loop.  Wave 1 starts all levels from XC_all (a solution at or above
@@ -1222,7 +1266,8 @@ def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, max
     larger rho.  Stops when every level has converged, a wave makes no progress, or after max_waves.
 
     Returns (XC_levels [12 x n x L], defect [12 x (n-1) x L], status [L] (0 converged, else the last status_flag of the
-    level, 3 = never converged: HelperFunctions.jl:161), waves)."""
+    level, 3 = never converged: HelperFunctions.jl:161), waves).  arcs=True: one more batched call (thrust_arcs) over the
+    converged levels, returned as a fifth element -- a list with one dict per level, None where the level did not converge."""
     rhos = np.asarray(rhos, dtype=np.float64)
     order = np.argsort(-rhos)                                 # descending: neighbours in the list are neighbours in rho
     L = len(rhos)
@@ -1253,4 +1298,12 @@ def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, max
             print("wave %d: %d of %d levels converged (%d remaining)" % (waves, progress, len(todo), int((~solved).sum())))
         if progress == 0:
             break
+    if arcs:
+        ok = [k for k in range(L) if solved[k]]
+        level_arcs = [None] * L
+        if ok:
+            found = thrust_arcs(np.asfortranarray(X[:, :, ok]), t_TU, MU, DU, TU, mass, thrustLimit, p, rhos[ok], ctx=ctx)
+            for k, a in zip(ok, found):
+                level_arcs[k] = a
+        return np.asfortranarray(X), np.asfortranarray(D), status, waves, level_arcs
     return np.asfortranarray(X), np.asfortranarray(D), status, waves

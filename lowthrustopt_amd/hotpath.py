@@ -561,6 +561,45 @@ def densify(XC_all, t_TU, params, n_desired, integ=None, ctx=None):
     return XC_dense, t_dense
 
 
+class ThrustEvents:
+    """Result of indirect_events; B trajectories (batched) or one (the batch axis dropped): n_events [B], t_event and kind
+    [max_events x B], on0 [B], dv [B] (DU/TU), burn_time [B] (TU), dv_seg [(n-1) x B], status [B]."""
+
+    def __init__(self, n_events, t_event, kind, on0, dv, burn_time, dv_seg, status):
+        self.n_events, self.t_event, self.kind, self.on0 = n_events, t_event, kind, on0
+        self.dv, self.burn_time, self.dv_seg, self.status = dv, burn_time, dv_seg, status
+
+
+def indirect_events(XC_all, t_TU, params, max_events=64, integ=None, ctx=None, with_dv_seg=True):
+    """Switch times, burn arcs and dv of indirect solutions (lto_indirect_events_batch): XC_all [12 x n] or
+    [12 x n x B], t_TU [n] or [n x B], params one tuple or one per trajectory.  Events are located while the segments are
+    integrated (LTO_RK4 or LTO_DOP853_ADAPTIVE); dv is carried as a quadrature state.  Returns a ThrustEvents."""
+    XC = _f64(XC_all)
+    ndim, n, B, batched = _batch_dims(XC)
+    t, ntg = _tgrids(t_TU, n, B)
+    prm, nprm = _params_array(params)
+    if nprm != 1 and nprm != B:
+        raise ValueError("params must be one tuple or one per trajectory")
+    M = int(max_events)
+    Mr = max(M, 1)
+    n_events = np.zeros(B, dtype=np.int32)
+    t_event = np.full((Mr, B), np.nan, order="F")
+    kind = np.zeros((Mr, B), dtype=np.int32, order="F")
+    on0 = np.zeros(B, dtype=np.int32)
+    dv, burn = np.zeros(B), np.zeros(B)
+    dv_seg = np.zeros((n - 1, B), order="F") if with_dv_seg else None
+    status = np.zeros(B, dtype=np.int32)
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    ctx.check(ctx.fn("indirect_events_batch")(ctx.handle, ndim, n, B, _ptr(XC), _ptr(t), ntg, prm, nprm, C.byref(integ), M,
+                                              _ptr(n_events), _ptr(t_event), _ptr(kind), _ptr(on0), _ptr(dv), _ptr(burn),
+                                              _ptr(dv_seg), _ptr(status)))
+    if not batched:
+        return ThrustEvents(int(n_events[0]), t_event[:, 0], kind[:, 0], int(on0[0]), float(dv[0]), float(burn[0]),
+                            None if dv_seg is None else dv_seg[:, 0], int(status[0]))
+    return ThrustEvents(n_events, t_event, kind, on0, dv, burn, dv_seg, status)
+
+
 def direct_defectCalc(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None):
     """defectCalc of multiShoot_CRTBP_direct (:66-109): returns (defect[nstate x (n-1)], errors[n-1])."""
     ctx = ctx or default_context()
@@ -1249,6 +1288,13 @@ class IndirectPlan:
         columns of Y [ndim][ldy]; first is int32 [S + 1]; final_state [ndim][n_batch], if given, takes every trajectory's x(t_n)."""
         self.ctx.check(self.ctx.lib.lto_indirect_dense_dev(self.handle, stream, _dptr(X), int(ldx), _dptr(t), int(n_tgrids),
                                                            _dptr(first), _dptr(t_samples), _dptr(Y), int(ldy), _dptr(final_state)))
+
+    def events(self, X, ldx, t, n_tgrids, max_events, n_events, t_event, kind, on0, dv, burn_time, status, dv_seg=None, stream=None):
+        """Thrust events on device arrays (lto_indirect_events_dev): n_events, kind, on0, status int32; t_event, kind
+        [n_batch][max_events]; dv_seg [S] or None."""
+        self.ctx.check(self.ctx.lib.lto_indirect_events_dev(self.handle, stream, _dptr(X), int(ldx), _dptr(t), int(n_tgrids),
+                                                            int(max_events), _dptr(n_events), _dptr(t_event), _dptr(kind), _dptr(on0),
+                                                            _dptr(dv), _dptr(burn_time), _dptr(dv_seg), _dptr(status)))
 
     def newton_solve(self, Phi, ldp, defect, ldd, delta, ldx, stream=None, adjoints_only=False):
         """delta = -J \\ defect on the device; Phi=None re-uses the stored factorisation (SOC re-solve)."""
