@@ -731,7 +731,7 @@ int lto_indirect_dense_dev(lto_indirect_plan* plan, void* stream, const double* 
  * segment keeps at most 4 events.  Where the on-state at the end of segment i differs from the one at the start of segment i+1
  * (the node's discontinuity straddles g = 0) an event at t_{i+1} is emitted, so that every list strictly alternates and its first
  * kind is +1 iff the trajectory starts off.
- * Outputs (column-major, trajectory b):  n_events[b];  t_event[max_events x B] ascending, NaN beyond n_events;  kind[max_events x B]
+ * Outputs (column-major, trajectory b):  n_events[b];  t_event[max_events x B] ascending, NaN beyond the listed events;  kind[max_events x B]
  * +1 off->on, -1 on->off, 0 unused;  on0[b] the on-state at t[0];  dv[b] (DU/TU) the sum of the segments' q;  burn_time[b] (TU);
  * dv_seg[(n_nodes-1) x B] the segments' q (may be NULL);  status[b]: 0 ok;  1 more than max_events events, or more than 4 in one
  * segment: the lists are truncated in time order, n_events is the count of all events located, dv and burn_time are complete;

@@ -9,7 +9,7 @@ step's start state.
 
 Fixtures: the nodes of synth.indirect_problem with every node's costates rescaled -- lambda_v to a level around the threshold of
 g, lambda_r to a norm that sets how fast |lambda_v| moves.  Only the seeds and scalars below are stored; the searches that found
-them ran on the CPU."""
+them ran on the CPU.  Below the fixtures: segment templates, from which the shape sweep strings trajectories of any shape."""
 import functools
 from collections import namedtuple
 
@@ -23,7 +23,8 @@ KEEP = 4                    # events a segment keeps
 MIN_SLOPE = 0.1             # |dn/dt| at every fixture root, per TU
 MASS = 1000.0
 
-Traj = namedtuple("Traj", "n seed dt lev lam_r p rho thrust")     # lev = (lo, hi): |lambda_v| / threshold per node; dt: a length or (lo, hi)
+# lev = (lo, hi): |lambda_v| / threshold per node; dt: a length or (lo, hi); td: time_direction
+Traj = namedtuple("Traj", "n seed dt lev lam_r p rho thrust td", defaults=(1.0,))
 # name -> trajectories of the case (B = len)
 CASES = {
     "one_crossing": [Traj(2, 2, 0.15, (0.7, 1.3), 2.0, 1.0, 1e-2, 0.05)],
@@ -38,12 +39,25 @@ CASES = {
 EXTRA = {"many_crossings": [Traj(2, 20, 6.0, (0.9, 1.1), 0.3, 1.0, 1e-2, 0.05)]}
 
 
+# Sources of segment templates only (below): never run as trajectories of their own.  uniform34: equal lengths, for patterns
+# that share one time grid; the others one control-law class each (thrust 0.5 N for p = 3 keeps its threshold 3 aL^2 at 0.1).
+POOL_CASES = {
+    "uniform34": [Traj(34, 14, 0.05, (0.7, 1.3), 2.0, 1.0, 1e-2, 0.05)],
+    "pool_p15": [Traj(66, 31, (0.03, 0.06), (0.7, 1.3), 1.0, 1.5, 1.0, 0.05)],
+    "pool_p3": [Traj(66, 32, (0.03, 0.06), (0.7, 1.3), 1.0, 3.0, 1.0, 0.5)],
+    "pool_back": [Traj(66, 33, (0.03, 0.06), (0.7, 1.3), 2.0, 1.0, 1e-2, 0.05, -1.0)],
+}
+
+
 def _spec(name):
-    return CASES[name] if name in CASES else EXTRA[name]
+    for d in (CASES, EXTRA, POOL_CASES):
+        if name in d:
+            return d[name]
+    raise KeyError(name)
 
 
 def prm_tuple(tr):
-    return (MU, DU, TU, tr.thrust, MASS, 1.0, tr.p, tr.rho)
+    return (MU, DU, TU, tr.thrust, MASS, tr.td, tr.p, tr.rho)
 
 
 def accel_limit(prm):
@@ -105,7 +119,8 @@ def slope(O, y, prm):
     return float(np.dot(y[9:12], dy[9:12]) / np.linalg.norm(y[9:12]))
 
 
-Seg = namedtuple("Seg", "roots q on_s on_e ont slopes")
+# gmin: the smallest |g| at the reference's accepted steps (None: p = 0, or not recorded)
+Seg = namedtuple("Seg", "roots q on_s on_e ont slopes gmin", defaults=(None,))
 
 
 def _on_time(roots, on_s, ta, tb):
@@ -129,7 +144,8 @@ def seg_reference(O, y0, ta, tb, prm, tol=1e-13):
     roots = [] if ev is None else [float(r) for r in sol.t_events[0]]
     slopes = [] if ev is None else [slope(O, z, prm) for z in sol.y_events[0]]
     on_s, on_e = is_on(z0, prm), is_on(sol.y[:, -1], prm)
-    return Seg(roots, float(sol.y[12, -1]), on_s, on_e, _on_time(roots, on_s, ta, tb), slopes)
+    gmin = None if ev is None else min(abs(g_of(sol.y[:, k], prm)) for k in range(sol.y.shape[1]))
+    return Seg(roots, float(sol.y[12, -1]), on_s, on_e, _on_time(roots, on_s, ta, tb), slopes, gmin)
 
 
 def roots_brentq(O, y0, ta, prm, roots, tb, half=1e-4):
@@ -264,3 +280,354 @@ def bars(names=None):
     """(bar on |t_event - ref| in TU, relative bar on dv)."""
     e_t, e_dv = tolerances(names)
     return max(1e-12, 10.0 * e_t), max(1e-12, 10.0 * e_dv)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Segment templates.  Segment i is the flow from node i alone, and the CRTBP with this control law is autonomous: a segment
+# (node state, length) placed at any index with any start time t_i has its crossings at t_i + tau, the same q, on-time and
+# on-states at its ends.  So a template's reference is computed once (at t_i = 0, cached per process) and trajectories of any
+# shape are strung from template ids.  A template id is (case, trajectory, segment) of a fixture above, or
+# ("prox", "start" | "end", fraction): a node derived from PROX_BASE with the oracle's flow (below).
+# ---------------------------------------------------------------------------------------------------------------------------
+QUIET_MARGIN = 0.01         # a template without roots keeps |g| >= QUIET_MARGIN * threshold at every accepted step of the reference
+EPS = 2.0 ** -52
+FIVE = ("many_crossings", 0, 0)
+PROX_BASE = ("one_crossing", 0, 0)
+PROX = tuple(("prox", kind, frac) for kind in ("start", "end") for frac in (1e-3, 1e-6))
+# class -> (case, trajectory) whose segments are the class's candidate templates
+POOL_SRC = {
+    "p1": (("mixed66", 0), ("one_crossing", 0), ("two_crossings", 0), ("many_crossings", 0)),
+    "p1u": (("uniform34", 0),),
+    "p2": (("mixed66", 1),),
+    "p1.5": (("pool_p15", 0),),
+    "p3": (("pool_p3", 0),),
+    "p1back": (("pool_back", 0),),
+    "p0": (("mixed66", 2),),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _case_cached(name):
+    return case_problem(name)               # shared: nobody writes into it
+
+
+@functools.lru_cache(maxsize=None)
+def tmpl_node(tid):
+    """(node state [12], length, params tuple) of a template."""
+    if tid[0] == "prox":
+        return _prox_node(tid)
+    name, b, i = tid
+    XC, T, prms = _case_cached(name)
+    tr = _spec(name)[b]
+    L = float(T[i + 1, b] - T[i, b]) if isinstance(tr.dt, tuple) else float(tr.dt)
+    y0 = np.array(XC[:, i, b])
+    y0.setflags(write=False)
+    return y0, L, prms[b]
+
+
+def _prox_node(tid):
+    """From PROX_BASE (root tau*, length L): "start": the base's state at tau* - delta, to the base's end; "end": the base's
+    node, over tau* + delta; delta = fraction * L.  The crossing then lies delta behind the start or ahead of the end."""
+    from oracle import oracle as O
+    _, kind, frac = tid
+    y0, L, prm = tmpl_node(PROX_BASE)
+    root, = tmpl_seg(PROX_BASE).roots
+    delta = frac * L
+    if kind == "end":
+        return y0, root + delta, prm
+    y, rc, _, _ = O.flow_state_costate(y0, np.array(prm), root - delta, O.DOP853_ADAPTIVE, 0, 1e-13, 1e-13)
+    assert rc == 0
+    y = np.array(y, dtype=np.float64)
+    y.setflags(write=False)
+    return y, L - (root - delta), prm
+
+
+@functools.lru_cache(maxsize=None)
+def tmpl_seg(tid, tol=1e-13):
+    """The template's Seg with its roots as offsets tau from the segment's start."""
+    from oracle import oracle as O
+    y0, L, prm = tmpl_node(tid)
+    return seg_reference(O, y0, 0.0, L, prm, tol)
+
+
+@functools.lru_cache(maxsize=None)
+def tmpl_brentq(tid):
+    """The second determination of the template's roots; None where its bracket cannot be formed."""
+    from oracle import oracle as O
+    y0, L, prm = tmpl_node(tid)
+    s = tmpl_seg(tid)
+    if not s.roots:
+        return ()
+    try:
+        return tuple(roots_brentq(O, y0, 0.0, prm, s.roots, L))
+    except (ValueError, AssertionError):
+        return None
+
+
+def admitted(tid):
+    """Every root with |dn/dt| >= MIN_SLOPE and found by both CPU determinations; a quiet template clear of g = 0."""
+    y0, L, prm = tmpl_node(tid)
+    s = tmpl_seg(tid)
+    if s.on_e != s.on_s ^ (len(s.roots) & 1):
+        return False
+    if not s.roots:
+        return s.gmin is None or s.gmin >= QUIET_MARGIN * threshold(prm)
+    return all(abs(x) >= MIN_SLOPE for x in s.slopes) and tmpl_brentq(tid) is not None
+
+
+def klass(tid):
+    s = tmpl_seg(tid)
+    return (s.on_s, len(s.roots), s.on_e)
+
+
+@functools.lru_cache(maxsize=None)
+def pool(cls):
+    """The admitted templates of a class, in the order of their sources."""
+    out = []
+    for name, b in POOL_SRC[cls]:
+        out += [(name, b, i) for i in range(_spec(name)[b].n - 1) if admitted((name, b, i))]
+    return tuple(out)
+
+
+def pick(cls, on_s=None, nroots=None, on_e=None, k=0):
+    """The k-th (cyclically) admitted template of the class with these properties (None: any; nroots may be a tuple)."""
+    nr = None if nroots is None else (nroots if isinstance(nroots, tuple) else (nroots,))
+    hit = [tid for tid in pool(cls) if (on_s is None or klass(tid)[0] == on_s) and (nr is None or klass(tid)[1] in nr)
+           and (on_e is None or klass(tid)[2] == on_e)]
+    if not hit:
+        raise LookupError("no template (%s, %s, %s) in pool %s" % (on_s, nroots, on_e, cls))
+    return hit[k % len(hit)]
+
+
+def place(pattern, t0=0.0, rk4_steps=None, tol=1e-13):
+    """(XC [12 x n], t [n], segs) of the trajectory strung from the templates of `pattern`, n = len(pattern) + 1.  The nodes are
+    the templates' start states (the last node: the first one again, any finite state does), t accumulates their lengths, segs
+    are the cached Segs with the roots shifted to t_i + tau.  With rk4_steps the segments are seg_reference_rk4 at the placed
+    t_i instead: that bisection stops on adjacent doubles in absolute time."""
+    from oracle import oracle as O
+    n = len(pattern) + 1
+    XC, t, segs = np.empty((12, n), order="F"), np.empty(n), []
+    t[0] = t0
+    for i, tid in enumerate(pattern):
+        y0, L, prm = tmpl_node(tid)
+        XC[:, i] = y0
+        t[i + 1] = t[i] + L
+        if rk4_steps:
+            segs.append(seg_reference_rk4(O, y0, t[i], t[i + 1], prm, rk4_steps))
+        else:
+            s = tmpl_seg(tid, tol)
+            segs.append(s._replace(roots=[float(t[i] + r) for r in s.roots]))
+    XC[:, n - 1] = tmpl_node(pattern[0])[0]
+    return XC, t, segs
+
+
+def pattern_prm(pattern):
+    prm = tmpl_node(pattern[0])[2]
+    assert all(tmpl_node(tid)[2] == prm for tid in pattern)
+    return prm
+
+
+def event_owner(segs):
+    """Per event of the complete list, the segment that emits it (a join belongs to the segment ahead of the node)."""
+    own = []
+    for i, s in enumerate(segs):
+        own += [i] * len(s.roots)
+        if i + 1 < len(segs) and s.on_e != segs[i + 1].on_s:
+            own.append(i)
+    return own
+
+
+def compact_direct(segs, t, max_events):
+    """compact a second way, for the host test: all events of all segments and the joins sorted by time, then truncated."""
+    evs = [(r, -1 if (s.on_s + k) % 2 else 1) for s in segs for k, r in enumerate(s.roots)]
+    evs += [(float(t[i + 1]), 1 if b.on_s else -1) for i, (a, b) in enumerate(zip(segs[:-1], segs[1:])) if a.on_e != b.on_s]
+    evs.sort(key=lambda e: e[0])
+    holes = [sum(1 for e in evs if e[0] < s.roots[KEEP]) for s in segs if len(s.roots) > KEEP]
+    return len(evs), evs[:min([max_events] + holes)], int(len(evs) > max_events or bool(holes))
+
+
+# ---- patterns: lists of template ids, each built to realise one feature (tests/test_thrust_arcs_host.py holds them to it) ----
+NSEGS = (1, 2, 63, 64, 65, 128, 129)
+
+
+def pat_quiet(nseg, on, cls="p1"):
+    return [pick(cls, on, 0, on, k) for k in range(nseg)]
+
+
+def pat_sparse(nseg, where, cls="p1", special=None):
+    """Crossings (one each) in the segments of `where` only, every other segment quiet and no join; special: {index: template}
+    placed as they are (a join ahead of one where its start state differs)."""
+    special = special or {}
+    cur, out = klass(pick(cls, None, 1))[0], []
+    for i in range(nseg):
+        if i in special:
+            tid = special[i]
+        elif i in where:
+            tid = pick(cls, cur, 1, None, len(out))
+        else:
+            tid = pick(cls, cur, 0, cur, len(out))
+        out.append(tid)
+        cur = klass(tid)[2]
+    return out
+
+
+def pat_edges(nseg):
+    return pat_sparse(nseg, {0, 63, 64, nseg - 1})
+
+
+def pat_boundary_joins(nseg):
+    """All on up to node 64, off from there, on again from node 128: the only events are the joins at t[64] (and t[128])."""
+    return [pick("p1", s, 0, s, i) for i in range(nseg) for s in [1 if (i < 64 or i >= 128) else 0]]
+
+
+def pat_dense(nseg, cls="p1"):
+    """Every segment a one- or two-crossing template, joins where they fall -- but a join forced at the nodes 64 and 128, where
+    the compaction changes chunks, and none at their neighbours 63, 65 and 127."""
+    out, cur = [], None
+    for i in range(nseg):
+        want = None if cur is None else (1 - cur if i in (64, 128) else cur if i in (63, 65, 127) else None)
+        out.append(pick(cls, want, (1, 2), None, i))
+        cur = klass(out[-1])[2]
+    return out
+
+
+def pat_holes(at, nseg=129):
+    """The five-crossing template at the indices `at`, a crossing in every fifth segment otherwise."""
+    return pat_sparse(nseg, set(range(2, nseg, 5)) - set(at), special={i: FIVE for i in at})
+
+
+def pat_cycle(cls, nseg=65):
+    """The class's admitted templates in turn (the five-crossing one apart)."""
+    p = [tid for tid in pool(cls) if tid != FIVE]
+    return [p[k % len(p)] for k in range(nseg)]
+
+
+def pat_prox(tid, nseg):
+    """An end-proximity template alone, or as the last of nseg segments behind quiet ones of its start state."""
+    on = klass(tid)[0]
+    return [pick("p1", on, 0, on, k) for k in range(nseg - 1)] + [tid]
+
+
+def pat_plumbing():
+    """Six 65-segment trajectories of different event counts for one call; 4 holds the five-crossing template."""
+    return [pat_dense(65), pat_edges(65), pat_quiet(65, 1), pat_cycle("p1"), pat_holes((30,), 65), pat_boundary_joins(65)]
+
+
+def pat_shared_grid():
+    """Six patterns of equal-length templates: one time grid serves them all."""
+    p = pool("p1u")
+    return [[p[(k * (b + 1) + b) % len(p)] for k in range(65)] for b in range(6)]
+
+
+def sweep_patterns():
+    """name -> (family, class, pattern) of every DOP853 pattern of the sweep (the RK4 ones re-use "dense65" and the two-crossing
+    template).  The family names the pattern's kind; "quiet_off" has a dv bar of its own (pool_tolerances)."""
+    out = {}
+    for n in NSEGS:
+        out["quiet_on%d" % n] = ("quiet_on", "p1", pat_quiet(n, 1))
+        out["quiet_off%d" % n] = ("quiet_off", "p1", pat_quiet(n, 0))
+        out["edges%d" % n] = ("edges", "p1", pat_edges(n))
+    for n in (65, 128, 129):
+        out["joins%d" % n] = ("joins", "p1", pat_boundary_joins(n))
+    for n in (65, 129):
+        out["dense%d" % n] = ("dense", "p1", pat_dense(n))
+    for at in HOLES:
+        out["holes" + "_".join(map(str, at))] = ("holes", "p1", pat_holes(at))
+    for cls in CLASSES:
+        out["cycle_" + cls] = ("cycle_" + cls, cls, pat_cycle(cls))
+    for tid in PROX:
+        for n in (1, 65):
+            out["prox_%s_%g_%d" % (tid[1], tid[2], n)] = ("prox", "p1", pat_prox(tid, n))
+    for b, pat in enumerate(pat_plumbing()):
+        out["plumbing%d" % b] = ("plumbing", "p1", pat)
+    for b, pat in enumerate(pat_shared_grid()):
+        out["shared%d" % b] = ("shared", "p1u", pat)
+    return out
+
+
+HOLES = ((0,), (63,), (64,), (100,), (10, 70))
+CLASSES = ("p2", "p1.5", "p3", "p1back", "p0")
+
+
+@functools.lru_cache(maxsize=None)
+def prox_admitted():
+    """The end-proximity templates whose two CPU determinations both succeed."""
+    return tuple(tid for tid in PROX if admitted(tid) and klass(tid)[1] == 1)
+
+
+@functools.lru_cache(maxsize=None)
+def pool_tolerances():
+    """(e_t, e_dv, e_t of the five-crossing template), measured as tolerances() does: e_t the largest difference between the two
+    CPU determinations of any admitted template's root (the five-crossing template apart), e_dv the largest relative difference
+    of a sweep pattern's reference dv between rtol = atol = 1e-13 and 1e-12.  e_dv = {"rest": .., "quiet_off": ..}: the all-off
+    patterns apart, whose dv is nearly zero (1e-7 .. 4e-5 DU/TU), so that the integrators' absolute tolerance makes their
+    relative error a hundred times every other pattern's; one figure for all would widen every other pattern's bar by that.
+    "by_family" holds each family's own figure, for the record only: a family's few patterns give a noisy estimate (the
+    segments' errors cancel in the sum by luck), so no bar is taken from it."""
+    e_t, e_five = 0.0, 0.0
+    for tid in [t for cls in POOL_SRC for t in pool(cls)] + list(prox_admitted()):
+        s = tmpl_seg(tid)
+        if s.roots:
+            d = float(np.max(np.abs(np.array(tmpl_brentq(tid)) - np.array(s.roots))))
+            if tid == FIVE:
+                e_five = d
+            else:
+                e_t = max(e_t, d)
+    by_family = {}
+    for name, (fam, cls, pat) in sweep_patterns().items():
+        if any(tid in PROX and tid not in prox_admitted() for tid in pat):
+            continue
+        fine = wave_sum([tmpl_seg(tid).q for tid in pat])
+        coarse = wave_sum([tmpl_seg(tid, 1e-12).q for tid in pat])
+        by_family[fam] = max(by_family.get(fam, 0.0), abs(fine - coarse) / abs(fine))
+    e_dv = {"quiet_off": by_family["quiet_off"], "rest": max(v for k, v in by_family.items() if k != "quiet_off"),
+            "by_family": by_family}
+    return e_t, e_dv, e_five
+
+
+def sweep_bars(family):
+    """(bar on |t_event - ref| in TU before the rounding of t, relative bar on dv) of a family's patterns."""
+    e_t, e_dv, _ = pool_tolerances()
+    return max(1e-12, 10.0 * e_t), max(1e-12, 10.0 * e_dv["quiet_off" if family == "quiet_off" else "rest"])
+
+
+def five_bar():
+    return max(1e-12, 10.0 * pool_tolerances()[2])
+
+
+def event_bars(pattern, segs, bt):
+    """Per event of the complete list: the five-crossing template's own bar for its crossings, bt for every other event (bt
+    alone for a pattern without that template)."""
+    if FIVE not in pattern:
+        return bt
+    return np.array([five_bar() if (pattern[i] == FIVE) else bt for i in event_owner(segs)])
+
+
+def check_arcs(ev, b, ref, t, bars, label, abs_time=False, t_ulp=0):
+    """Trajectory b of a batched device result against its reference Arcs.  Exact: status, n_events, on0, kind, the NaN / 0 tail
+    beyond the listed events, dv == wave_sum(dv_seg).  Within bars = (bt, bdv): the listed times (bt a number, or one per
+    listed event), dv relative, dv_seg to dv's absolute bar, burn_time to a bar per event.  abs_time adds 4 eps max|t| to bt (the
+    rounding of absolute times on a trajectory that does not start at 0), t_ulp that many ulps of max|t|.  Returns the largest
+    time and dv errors."""
+    bt, bdv = bars
+    k, m = int(ev.n_events[b]), int(np.sum(np.isfinite(ref.t_event)))
+    tmax = float(np.max(np.abs(t)))
+    bt = np.asarray(bt, dtype=np.float64)
+    bt = (bt if bt.ndim == 0 else bt[:m]) + ((4.0 * EPS * tmax) if abs_time else 0.0) + t_ulp * np.spacing(tmax)
+    d_t = np.abs(ev.t_event[:m, b] - ref.t_event[:m])
+    e_time = float(np.max(d_t)) if m else 0.0
+    e_dv = abs(ev.dv[b] - ref.dv) / abs(ref.dv)
+    e_bt = abs(ev.burn_time[b] - ref.burn_time)
+    btm = float(np.max(bt))
+    print("MEASURED %s[%d]: n_events %d (ref %d), listed %d, |t - ref| %.3e (bar %.1e), dv rel %.3e (bar %.1e), burn_time %.3e"
+          % (label, b, k, ref.n_events, m, e_time, btm, e_dv, bdv, e_bt))
+    assert ev.status[b] == ref.status and k == ref.n_events and ev.on0[b] == ref.on0
+    assert np.array_equal(ev.kind[:, b], ref.kind)
+    assert np.all(np.isnan(ev.t_event[m:, b]))
+    assert m == 0 or bool(np.all(d_t <= bt))
+    assert e_dv <= bdv
+    assert e_bt <= max(k, 1) * btm + 1e-13 * (t[-1] - t[0])
+    if ev.dv_seg is not None:
+        assert np.all(np.abs(ev.dv_seg[:, b] - ref.dv_seg) <= bdv * abs(ref.dv))        # a segment's share of the total's bar
+        assert ev.dv[b] == wave_sum(ev.dv_seg[:, b])                     # the documented order of the sum, bit for bit
+    return e_time, e_dv
