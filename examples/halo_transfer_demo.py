@@ -89,6 +89,13 @@ def mass_run(XC, t, Isp, rho_target, ctx, verbose=True, n=30, mass0=1e3):
         if st != 0:
             break
         X, rho_prev = Xn, r
+    # arcs and mass budget of the last level reached, read off the integration (drivers.thrust_arcs_mass)
+    a = drivers.thrust_arcs_mass(X, t, MU, DU, TU, Isp, 0.05, 1.0, rho_prev, ctx=ctx)
+    out["arcs"] = a
+    burns = ", ".join("%.3f-%.3f d" % (b0 * TU / 86400.0, b1 * TU / 86400.0) for b0, b1 in a["arcs"])
+    print("mass, arcs, rho = %-9g dv %.3f m/s (rocket equation of the mass ratio %.3f m/s), burning %.3f d in %d arcs: %s"
+          % (rho_prev, a["dv_ms"], a["dv_rocket_ms"], a["burn_days"], len(a["arcs"]), burns))
+    print("mass, budget: propellant %.4f kg over the segments, m_f %.4f kg (last node %.4f kg)" % (a["propellant_kg"], a["mass_final_kg"], X[6, -1]))
     return out
 
 

@@ -748,6 +748,34 @@ int lto_indirect_events_dev(lto_indirect_plan* plan, void* stream, const double*
                             int max_events, int* n_events, double* t_event, int* kind, int* on0, double* dv, double* burn_time,
                             double* dv_seg, int* status);
 
+/* The same for the variable-mass system, y = (r, v, m, lambda_r, lambda_v, lambda_m), 14 rows.  Parameters
+ * (thrustLimit, Isp, p, rho), lto_params.mass carrying Isp as everywhere for 14 rows.  n = |lambda_v| (rows 10..12), m = y[6],
+ * cT = thrustLimit / 1e3 * TU^2 / DU, aL = cT / m, kappa = time_direction * 1e3 * DU / (TU * Isp * 9.81), umag(n, m) the law of the
+ * 14-row system (the 12-row law with aL = cT / m).  The engine is ON iff g > 0 (g == 0 and NaN are off) with   p = 0: always on (no
+ * event);   p = 1: g = n - 1;   p > 1: g = n - p (cT / m)^(p-1) with the CURRENT mass: the threshold moves as the engine burns.
+ * Every segment integrates (y[14], q), q' = umag, q(t_i) = 0, with LTO_RK4 (`steps` steps) or LTO_DOP853_ADAPTIVE (all 15
+ * components in the error norm); any other method, or a plan that is not 14-row: LTO_EUNSUPPORTED.  The crossing search (on-state
+ * compared at the two ends of every accepted step, bisection in theta by trial steps of the same formula from the step's start
+ * state to adjacent doubles, at most 60 halvings, t_event the bracket's upper end), the limit of 4 events per segment, the join
+ * events, the truncation rules and the status codes are exactly those of lto_indirect_events_batch above; TWO CROSSINGS INSIDE ONE
+ * ACCEPTED STEP ARE NOT SEEN here either.
+ * Mass budget:  dm_seg[(n_nodes-1) x B] (kg, may be NULL) = m_i - m(t_{i+1}), the node's mass minus the propagated one.  The lane
+ * carries the mass as m_i plus its change, so dm_seg keeps the digits that m_i + change would round away; where m_i + change == m_i
+ * as doubles the propagated mass is the node's mass and dm_seg is exactly 0 (Isp -> infinity: the constant-mass system).
+ * propellant[b] (kg, required) the sum of the trajectory's dm_seg in the order dv sums the q.
+ * A node mass that is not finite and positive makes its trajectory status 2 (outputs NaN or 0 as for a non-finite trajectory); no
+ * other trajectory is affected.  Errors as above.  _dev: X [14][ldx] on a 14-row plan. */
+int lto_indirect_events_mass_batch(lto_ctx* ctx, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                                   const lto_params* prm, int n_prm, const lto_integrator* integ, int max_events, int* n_events,
+                                   double* t_event, int* kind, int* on0, double* dv, double* burn_time, double* dv_seg,
+                                   double* propellant, double* dm_seg, int* status);
+int lto_indirect_events_mass(lto_ctx* ctx, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                             const lto_integrator* integ, int max_events, int* n_events, double* t_event, int* kind, int* on0,
+                             double* dv, double* burn_time, double* dv_seg, double* propellant, double* dm_seg, int* status);
+int lto_indirect_events_mass_dev(lto_indirect_plan* plan, void* stream, const double* X, long ldx, const double* t, int n_tgrids,
+                                 int max_events, int* n_events, double* t_event, int* kind, int* on0, double* dv, double* burn_time,
+                                 double* dv_seg, double* propellant, double* dm_seg, int* status);
+
 int lto_direct_plan_create(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, int nsteps,
                            const lto_direct_params* prm, lto_direct_plan** out);
 void lto_direct_plan_destroy(lto_direct_plan* plan);

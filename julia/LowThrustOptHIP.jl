@@ -364,6 +364,39 @@ function thrust_arcs(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::Matrix{Flo
     end
 end
 
+"""`thrust_arcs` for solutions of the 14-row variable-mass system (`lto_indirect_events_mass_batch`, DESIGN 4.19): `XC_all`
+[14 x n_nodes x n_batch], `params` with Isp in the mass slot.  Per trajectory the named tuple of `thrust_arcs` plus propellant_kg
+(read off the integrated mass), mass_final_kg = XC_all[7, 1, b] - propellant_kg and dv_rocket_ms = Isp 9.81 ln(m0 / mass_final)."""
+function thrust_arcs_mass(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::Matrix{Float64}, params::Vector; max_events::Integer = 64,
+                          integ::LtoIntegrator = LtoIntegrator())
+    ndim, n_nodes, B = size(XC_all)
+    ndim == 14 || throw(ArgumentError("XC_all must be [14 x n_nodes x n_batch]"))
+    prm = [LtoParams(q) for q in params]
+    n_events = zeros(Cint, B); t_event = fill(NaN, max_events, B); kind = zeros(Cint, max_events, B); on0 = zeros(Cint, B)
+    dv = zeros(B); burn = zeros(B); prop = zeros(B); status = zeros(Cint, B)
+    rc = ccall((:lto_indirect_events_mass_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Cint,
+                Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cint}),
+               ctx.handle, n_nodes, B, XC_all, t_TU, B, prm, length(prm), Ref(integ), max_events, n_events, t_event, kind, on0,
+               dv, burn, C_NULL, prop, C_NULL, status)
+    check(ctx, rc)
+    map(1:B) do b
+        arcs = Tuple{Float64,Float64}[]
+        on = on0[b] != 0; mark = t_TU[1, b]
+        for k in 1:min(n_events[b], max_events)
+            isnan(t_event[k, b]) && break
+            on ? push!(arcs, (mark, t_event[k, b])) : (mark = t_event[k, b])
+            on = !on
+        end
+        (on && status[b] == 0) && push!(arcs, (mark, t_TU[end, b]))
+        m0 = XC_all[7, 1, b]; mf = m0 - prop[b]
+        isp = prm[length(prm) == 1 ? 1 : b].mass
+        (arcs = arcs, dv = dv[b], burn_time = burn[b], n_events = Int(n_events[b]), status = Int(status[b]),
+         propellant_kg = prop[b], mass_final_kg = mf, dv_rocket_ms = isp * 9.81 * log(m0 / mf))
+    end
+end
+
 # ---------------------------------------------------------------------------------------------- direct
 "defectCalc of multiShoot_CRTBP_direct: returns (defect1[nstate x (n_nodes-1)], errors[n_nodes-1])."
 function direct_defectCalc(ctx::LtoHandle, X_all::Matrix{Float64}, u_all::Matrix{Float64}, t_TU::Vector{Float64},

@@ -947,8 +947,9 @@ __device__ __forceinline__ void coef12_from_parts(const double x, const double y
 
 // LM = false: lambda_m_dot is not evaluated (dy[13] = 0).  For the always-thrust-limited laws (p = 0, p = 1) nothing else
 // depends on lambda_m, and the eight-wave pipeline kernel integrates it in the coefficient wave, off the critical stream.
+// umag: the thrust magnitude the slopes were formed with (the quadrature of kernels_events.hip integrates it alongside).
 template <int PM, bool LM = true>
-__device__ __forceinline__ void rhs14_base(const double (&y)[14], const TrajParams& tp, double (&dy)[14]) {
+__device__ __forceinline__ void rhs14_base(const double (&y)[14], const TrajParams& tp, double (&dy)[14], double& umag) {
   static_assert(LM || PM == PM_P0 || PM == PM_P1, "lambda_m feeds back into the unclamped p > 1 law");
   const double MU = tp.MU;
   const double x = y[0], yy = y[1], z = y[2], mass = y[6];
@@ -1006,6 +1007,12 @@ __device__ __forceinline__ void rhs14_base(const double (&y)[14], const TrajPara
     const double tl = tlim ? 1.0 : 0.0, ntl = 1.0 - tl;
     dy[13] = __builtin_fma(-tl, (m * n) * inv_m, ntl * (kt * lm * m));
   }
+  umag = m;
+}
+template <int PM, bool LM = true>
+__device__ __forceinline__ void rhs14_base(const double (&y)[14], const TrajParams& tp, double (&dy)[14]) {
+  double umag;
+  rhs14_base<PM, LM>(y, tp, dy, umag);
 }
 
 // ----------------------------------------------------- the base RHS split for the paired-stage base role (pipe8)

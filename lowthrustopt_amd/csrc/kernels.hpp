@@ -123,12 +123,18 @@ struct EventsArgs {
   double* dv; double* burn;        // [B]
   double* dv_seg;                  // [S] or null
   int* status;                     // [B]
+  // the variable-mass form only (null for 12 rows).  Behind everything else: the 12-row kernels read the same offsets.
+  double* dm;                      // [S] node mass minus propagated mass (NaN with q)
+  double* dm_seg;                  // [S] or null
+  double* propellant;              // [B]
 };
-inline size_t events_record_bytes(long S) {
-  return ((sizeof(double) * (kEventsPerSeg + 2) + sizeof(int) * 3) * (size_t)S + 255) & ~(size_t)255;
+// 14 rows: one more double per segment (dm)
+inline size_t events_record_bytes(long S, int ndim = 12) {
+  return ((sizeof(double) * (kEventsPerSeg + 2 + (ndim == 14 ? 1 : 0)) + sizeof(int) * 3) * (size_t)S + 255) & ~(size_t)255;
 }
-// 12-dim, M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
+// M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue.  12-dim; _mass: 14-dim (X [14][ldx], e.dm and e.propellant set)
 hipError_t launch_indirect_events(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st);
+hipError_t launch_indirect_events_mass(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st);
 hipError_t launch_events_compact(const IndirectArgs& a, const EventsArgs& e, int n_batch, hipStream_t st);
 // wave-specialised STM kernel (kernels_indirect_coop.hip): base wave + column waves per 16 segments
 hipError_t launch_indirect_stm_coop(int ndim, int pm, int method, const IndirectArgs& a, hipStream_t st);

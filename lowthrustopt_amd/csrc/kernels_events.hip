@@ -13,6 +13,10 @@
 // joins included: where the on-state at the end of segment i differs from the one at the start of segment i+1, an event at
 // t_{i+1}), an ordered gather into the trajectory's list, dv and burn_time as lane-strided partial sums closed by a butterfly.  No
 // atomics: a trajectory's result does not depend on its batch.
+//
+// k_indirect_events_mass: the same lane for the 14-row variable-mass system, (y[14], q) with q' = umag as rhs14_base
+// forms it, DOP853 with all 15 components in the error norm.  The threshold of p > 1 is formed from the state's CURRENT mass, and the
+// lane leaves dm = m_i - m(t_{i+1}) with its records; k_events_compact sums it into `propellant` in the order of dv.
 #include <hip/hip_runtime.h>
 
 #include "indirect_kernel.hpp"
@@ -78,16 +82,16 @@ struct SegEvents {
 };
 
 // The step from absolute time t0 over h changed the on-state from on_prev: bracket the crossing in theta.  trial(theta h, yt): the
-// state one step of length theta h from the step's start state.
-template <int PM, class Trial>
-__device__ __forceinline__ double locate_crossing(const double t0, const double h, const double on_prev, const double thr, Trial&& trial) {
+// state one step of length theta h from the step's start state; on(yt): its on-state.
+template <int D, class On, class Trial>
+__device__ __forceinline__ double locate_crossing(const double t0, const double h, const double on_prev, On&& on, Trial&& trial) {
   double lo = 0.0, hi = 1.0;
   double t_hi = t0 + h;
   for (int k = 0; k < 60; ++k) {
     const double mid = 0.5 * (lo + hi);
-    double yt[13];
+    double yt[D];
     trial(mid * h, yt);
-    if (on_state<PM>(yt, thr) == on_prev) lo = mid;
+    if (on(yt) == on_prev) lo = mid;
     else hi = mid;
     const double t_lo = __builtin_fma(lo, h, t0);
     t_hi = __builtin_fma(hi, h, t0);
@@ -109,6 +113,7 @@ __global__ __launch_bounds__(64) void k_indirect_events(const IndirectArgs a, co
   sys.tp = a.tp[(long)traj * a.tp_stride];
   if (a.class_filter && p_class(sys.tp.p) != PM) return;
   const double thr = event_threshold<PM>(sys.tp);
+  const auto on_of = [&](const double (&yt)[13]) { return on_state<PM>(yt, thr); };
   double y[13];
   double next_sum = 0.0;                          // node i + 1 only has to be finite
 #pragma unroll
@@ -132,7 +137,7 @@ __global__ __launch_bounds__(64) void k_indirect_events(const IndirectArgs a, co
       if (PM != PM_P0) {
         const double on1 = on_state<PM>(y, thr);
         if (on1 != se.on) {
-          const double tev = locate_crossing<PM>(__builtin_fma((double)k, h, ta), h, se.on, thr, [&](const double th, double (&yt)[13]) {
+          const double tev = locate_crossing<13>(__builtin_fma((double)k, h, ta), h, se.on, on_of, [&](const double th, double (&yt)[13]) {
 #pragma unroll
             for (int c = 0; c < 13; ++c) yt[c] = y0[c];
             rk4_step(sys, th, yt);
@@ -148,7 +153,7 @@ __global__ __launch_bounds__(64) void k_indirect_events(const IndirectArgs a, co
       if (PM == PM_P0) return;
       const double on1 = on_state<PM>(yn, thr);
       if (on1 != se.on) {
-        const double tev = locate_crossing<PM>(ta + t, h, se.on, thr, [&](const double th, double (&yt)[13]) {
+        const double tev = locate_crossing<13>(ta + t, h, se.on, on_of, [&](const double th, double (&yt)[13]) {
           double E5, E3;
           (void)dop853_try<Sys, 13>(sys, th, a.rtol, a.atol, y0, K, yt, E5, E3);
         });
@@ -166,6 +171,125 @@ __global__ __launch_bounds__(64) void k_indirect_events(const IndirectArgs a, co
   ev.tev[0 * S + s] = se.e0; ev.tev[1 * S + s] = se.e1; ev.tev[2 * S + s] = se.e2; ev.tev[3 * S + s] = se.e3;
   ev.q[s] = finite ? y[12] : __builtin_nan("");
   ev.ont[s] = finite ? se.ont : __builtin_nan("");
+  ev.nev[s] = se.nev;
+  ev.on_s[s] = (on_start != 0.0) ? 1 : 0;
+  ev.on_e[s] = (se.on != 0.0) ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------- the variable-mass system
+// The lane carries the mass as m_i + y[6], y[6](t_i) = 0: a segment burns 1e-5 .. 1e-2 of the mass, and a propagated m near
+// 1000 kg is rounded to eps m = 1.1e-13 kg in every step, so m_i - m(t_{i+1}) formed from it is good to eps m / dm only (measured:
+// 2.6e-12 relative on 0.04 kg).  The RHS and the event function see m_i + y[6]; the propagated mass is m(t_{i+1}) = m_i + y[6],
+// and dm = m_i - m(t_{i+1}) is -y[6] with the digits that sum would round away -- unless the sum IS m_i: a segment that does not
+// move the mass by half a unit of its last place has burned nothing, dm = 0 (Isp -> infinity: the constant-mass system).
+template <int PM>
+struct SysEventsMass {
+  static constexpr int DIM = 15;
+  TrajParams tp;
+  double m_i;
+  __device__ __forceinline__ void rhs(const double (&y)[15], double (&k)[15]) const {
+    double yb[14], kb[14];
+#pragma unroll
+    for (int i = 0; i < 14; ++i) yb[i] = y[i];
+    yb[6] = m_i + y[6];
+    double umag;
+    rhs14_base<PM, true>(yb, tp, kb, umag);
+#pragma unroll
+    for (int i = 0; i < 14; ++i) k[i] = kb[i];
+    k[14] = umag;
+  }
+};
+
+// g = |lambda_v| - thr(m) > 0 with the state's own mass: p = 1: thr = 1; p > 1: thr = p (cT / m)^(p-1).  A NaN (a mass of 0 makes
+// one) is off.
+template <int PM>
+__device__ __forceinline__ double on_state_mass(const double (&y)[15], const TrajParams& tp, const double m_i) {
+  if (PM == PM_P0) return 1.0;
+  const double mass = m_i + y[6];
+  const double n2 = __builtin_fma(y[10], y[10], __builtin_fma(y[11], y[11], y[12] * y[12]));
+  const double n = n2 * inv_norm_guarded(n2);
+  double thr = 1.0;
+  if (PM == PM_P2) thr = 2.0 * (tp.cT * rcp_nr(mass));
+  if (PM == PM_PGEN) thr = tp.p * pow(tp.cT * rcp_nr(mass), tp.p - 1.0);
+  return (n - thr > 0.0) ? 1.0 : 0.0;
+}
+
+template <int PM, int METHOD>
+__global__ __launch_bounds__(64) void k_indirect_events_mass(const IndirectArgs a, const EventsArgs ev) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= a.S) return;
+  const int traj = s / a.seg_per_traj;
+  const int i = s - traj * a.seg_per_traj;
+  const long node = (long)traj * a.n_nodes + i;
+  const long tg = (long)traj * a.t_stride + i;
+  using Sys = SysEventsMass<PM>;
+  Sys sys;
+  sys.tp = a.tp[(long)traj * a.tp_stride];
+  if (a.class_filter && p_class(sys.tp.p) != PM) return;
+  const auto on_of = [&](const double (&yt)[15]) { return on_state_mass<PM>(yt, sys.tp, sys.m_i); };
+  double y[15];
+  double next_sum = 0.0;                          // node i + 1 only has to be finite (and its mass positive, below)
+#pragma unroll
+  for (int c = 0; c < 14; ++c) { y[c] = a.X[c * a.ldx + node]; next_sum += a.X[c * a.ldx + node + 1]; }
+  y[14] = 0.0;
+  sys.m_i = y[6];
+  y[6] = 0.0;
+  const double ta = a.t[tg], tb = a.t[tg + 1];
+  const double span = tb - ta;
+  SegEvents se;
+  se.on = on_of(y);
+  se.tmark = ta; se.ont = 0.0; se.nev = 0;
+  se.e0 = se.e1 = se.e2 = se.e3 = __builtin_nan("");
+  const double on_start = se.on;
+
+  if (METHOD == M_RK4) {
+    const double h = span / (double)a.steps;
+    for (int k = 0; k < a.steps; ++k) {
+      double y0[15];
+#pragma unroll
+      for (int c = 0; c < 15; ++c) y0[c] = y[c];
+      rk4_step(sys, h, y);
+      if (PM != PM_P0) {
+        const double on1 = on_of(y);
+        if (on1 != se.on) {
+          const double tev = locate_crossing<15>(__builtin_fma((double)k, h, ta), h, se.on, on_of, [&](const double th, double (&yt)[15]) {
+#pragma unroll
+            for (int c = 0; c < 15; ++c) yt[c] = y0[c];
+            rk4_step(sys, th, yt);
+          });
+          se.crossing(tev, on1);
+        }
+      }
+    }
+  } else {
+    int nacc = 0, nrej = 0;
+    run_dop853_stepping<Sys, 15>(sys, span, a.rtol, a.atol, a.max_steps, y, nacc, nrej,
+                                 [&](const double t, const double h, const double (&y0)[15], double (&K)[13][15], const double (&yn)[15]) {
+      if (PM == PM_P0) return;
+      const double on1 = on_of(yn);
+      if (on1 != se.on) {
+        const double tev = locate_crossing<15>(ta + t, h, se.on, on_of, [&](const double th, double (&yt)[15]) {
+          double E5, E3;
+          (void)dop853_try<Sys, 15>(sys, th, a.rtol, a.atol, y0, K, yt, E5, E3);
+        });
+        se.crossing(tev, on1);
+      }
+    });
+  }
+  if (se.on != 0.0) se.ont += tb - se.tmark;
+  double fin = next_sum;
+#pragma unroll
+  for (int c = 0; c < 15; ++c) fin += y[c];
+  fin += se.ont;
+  // the masses of the segment's two nodes, read again here instead of a flag kept across the integration: finite and positive
+  // (a NaN fails the comparison, an infinity the finite sum)
+  const double m_i = a.X[6 * a.ldx + node], m_n = a.X[6 * a.ldx + node + 1];
+  const bool finite = ((fin + m_i) - (fin + m_i)) == 0.0 && m_i > 0.0 && m_n > 0.0;
+  const long S = a.S;
+  ev.tev[0 * S + s] = se.e0; ev.tev[1 * S + s] = se.e1; ev.tev[2 * S + s] = se.e2; ev.tev[3 * S + s] = se.e3;
+  ev.q[s] = finite ? y[14] : __builtin_nan("");
+  ev.ont[s] = finite ? se.ont : __builtin_nan("");
+  ev.dm[s] = finite ? ((m_i + y[6] == m_i) ? 0.0 : -y[6]) : __builtin_nan("");
   ev.nev[s] = se.nev;
   ev.on_s[s] = (on_start != 0.0) ? 1 : 0;
   ev.on_e[s] = (se.on != 0.0) ? 1 : 0;
@@ -202,7 +326,11 @@ __global__ __launch_bounds__(64) void k_events_compact(const IndirectArgs a, con
   double pq = 0.0, pt = 0.0;
   for (int i = lane; i < nseg; i += 64) { pq += ev.q[s0 + i]; pt += ev.ont[s0 + i]; }
   const double dv = wave_sum(pq), bt = wave_sum(pt);
-  const bool bad = !((dv - dv) == 0.0 && (bt - bt) == 0.0);
+  double pm = 0.0;                               // the variable-mass form: the segments' dm, summed as q is
+  if (ev.dm)
+    for (int i = lane; i < nseg; i += 64) pm += ev.dm[s0 + i];
+  const double prop = wave_sum(pm);
+  const bool bad = !((dv - dv) == 0.0 && (bt - bt) == 0.0 && (prop - prop) == 0.0);
   int base = 0, limit = M, over = 0;
   if (!bad) {
     for (int c0 = 0; c0 < nseg; c0 += 64) {
@@ -235,7 +363,10 @@ __global__ __launch_bounds__(64) void k_events_compact(const IndirectArgs a, con
   for (int p = listed + lane; p < M; p += 64) { t_out[p] = __builtin_nan(""); k_out[p] = 0; }
   if (ev.dv_seg)
     for (int i = lane; i < nseg; i += 64) ev.dv_seg[s0 + i] = bad ? __builtin_nan("") : ev.q[s0 + i];
+  if (ev.dm_seg)
+    for (int i = lane; i < nseg; i += 64) ev.dm_seg[s0 + i] = bad ? __builtin_nan("") : ev.dm[s0 + i];
   if (lane == 0) {
+    if (ev.propellant) ev.propellant[b] = bad ? __builtin_nan("") : prop;
     ev.n_events[b] = bad ? 0 : base;
     ev.on0[b] = bad ? 0 : ev.on_s[s0];
     ev.dv[b] = bad ? __builtin_nan("") : dv;
@@ -255,11 +386,28 @@ hipError_t launch_events_pm(int pm, const IndirectArgs& a0, const EventsArgs& e,
   return hipGetLastError();
 }
 
+template <int METHOD>
+hipError_t launch_events_mass_pm(int pm, const IndirectArgs& a0, const EventsArgs& e, hipStream_t st) {
+  dim3 grid((a0.S + 63) / 64);
+  (void)for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) {
+    hipLaunchKernelGGL((k_indirect_events_mass<decltype(cls)::value, METHOD>), grid, dim3(64), 0, st, a, e);
+    return hipSuccess;
+  });
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_indirect_events(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st) {
   if (method == M_RK4) return launch_events_pm<M_RK4>(pm, a, e, st);
   if (method == M_DOP853_ADAPTIVE) return launch_events_pm<M_DOP853_ADAPTIVE>(pm, a, e, st);
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_indirect_events_mass(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st) {
+  if (!e.dm || !e.propellant) return hipErrorInvalidValue;
+  if (method == M_RK4) return launch_events_mass_pm<M_RK4>(pm, a, e, st);
+  if (method == M_DOP853_ADAPTIVE) return launch_events_mass_pm<M_DOP853_ADAPTIVE>(pm, a, e, st);
   return hipErrorInvalidValue;
 }
 

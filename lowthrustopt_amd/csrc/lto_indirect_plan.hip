@@ -75,7 +75,7 @@ void plan_free(lto_indirect_plan* p) {
   pool_free(p->ctx, p->d_xa, sizeof(double) * NODE_REC * (size_t)p->n_nodes * p->n_batch);
   pool_free(p->ctx, p->d_da, sizeof(double) * 12 * (size_t)p->S);
   pool_free(p->ctx, p->d_pa, sizeof(double) * 144 * (size_t)p->S);
-  pool_free(p->ctx, p->d_events, events_record_bytes(p->S));
+  pool_free(p->ctx, p->d_events, events_record_bytes(p->S, p->ndim));
   delete p;
 }
 

@@ -1257,6 +1257,66 @@ def thrust_arcs(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, p, rho, Isp=None, m
     return out if batched else out[0]
 
 
+def _arcs_of(ev, b, t0, tf, max_events):
+    """[(t_on, t_off)] of trajectory b of a batched ThrustEvents, clipped to [t0, tf]."""
+    k = min(int(ev.n_events[b]), int(max_events))
+    times = ev.t_event[:k, b]
+    times = times[np.isfinite(times)]
+    on, mark, arcs = bool(ev.on0[b]), t0, []
+    for te in times:
+        if on:
+            arcs.append((mark, float(te)))
+        else:
+            mark = float(te)
+        on = not on
+    if on and ev.status[b] == 0:
+        arcs.append((mark, tf))
+    return arcs
+
+
+def _mass_budget(ev, m0, Isp, DU, TU, t, max_events):
+    """The per-trajectory dicts of thrust_arcs_mass from a batched ThrustEvents of the 14-row system: m0 [B] the masses of the
+    first nodes, Isp [B], t [n] or [n x B]."""
+    out = []
+    for b in range(len(m0)):
+        tb = t if t.ndim == 1 else t[:, b]
+        dv = float(ev.dv[b])
+        dv_ms = dv * DU / TU * 1e3
+        prop = float(ev.propellant[b])
+        m_f = float(m0[b]) - prop
+        with np.errstate(invalid="ignore", divide="ignore"):
+            dv_rocket = float(Isp[b] * 9.81 * np.log(m0[b] / m_f))
+        out.append(dict(arcs=_arcs_of(ev, b, float(tb[0]), float(tb[-1]), max_events), dv=dv, dv_ms=dv_ms,
+                        burn_time=float(ev.burn_time[b]), burn_days=float(ev.burn_time[b]) * TU / 86400.0,
+                        n_events=int(ev.n_events[b]), status=int(ev.status[b]), propellant_kg=prop, mass_final_kg=m_f,
+                        dv_rocket_ms=dv_rocket))
+    return out
+
+
+def thrust_arcs_mass(XC_all, t_TU, MU, DU, TU, Isp, thrustLimit, p, rho, max_events=64, integ=None, ctx=None):
+    """thrust_arcs for solutions of the 14-row variable-mass system (hotpath.indirect_events_mass): XC_all [14 x n] or
+    [14 x n x B]; Isp, thrustLimit, p and rho scalars or one per trajectory.  The propellant is a state of the integration and is
+    read off it, not estimated from the rocket equation.  Per trajectory the dict of thrust_arcs plus propellant_kg (the sum of
+    the segments' mass drops), mass_final_kg = XC_all[6, 0] - propellant_kg and dv_rocket_ms = Isp 9.81 ln(m0 / mass_final): the
+    ideal velocity increment of that mass ratio, which dv_ms equals on a continuous trajectory."""
+    XC = np.asarray(XC_all, dtype=np.float64)
+    if XC.ndim not in (2, 3) or XC.shape[0] != 14:
+        raise ValueError("XC_all must be [14 x n] or [14 x n x B]")
+    batched = XC.ndim == 3
+    B = XC.shape[2] if batched else 1
+    t = np.asarray(t_TU, dtype=np.float64)
+    if t.shape not in ((XC.shape[1],), (XC.shape[1], B)):
+        raise ValueError("t_TU must be [n] or [n x B]")
+    per = [np.broadcast_to(np.asarray(v, dtype=np.float64), (B,)) for v in (Isp, thrustLimit, p, rho)]
+    if not np.all(per[0] > 0.0):
+        raise ValueError("Isp must be positive")
+    prms = [hotpath.make_params(MU, DU, TU, per[1][b], per[0][b], 1.0, per[2][b], per[3][b]) for b in range(B)]
+    X3 = XC if batched else XC[:, :, None]
+    ev = hotpath.indirect_events_mass(X3, t, prms, max_events, integ, ctx)
+    out = _mass_budget(ev, X3[6, 0, :], per[0], DU, TU, t, max_events)
+    return out if batched else out[0]
+
+
 def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, maxIter=10, max_waves=12, ctx=None, verbose=True,
                    arcs=False):
     """Solve the whole smoothing ladder rho_0 > rho_1 > ... concurrently.  reduceFuel_indirect walks the

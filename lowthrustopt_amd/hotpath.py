@@ -563,11 +563,13 @@ def densify(XC_all, t_TU, params, n_desired, integ=None, ctx=None):
 
 class ThrustEvents:
     """Result of indirect_events; B trajectories (batched) or one (the batch axis dropped): n_events [B], t_event and kind
-    [max_events x B], on0 [B], dv [B] (DU/TU), burn_time [B] (TU), dv_seg [(n-1) x B], status [B]."""
+    [max_events x B], on0 [B], dv [B] (DU/TU), burn_time [B] (TU), dv_seg [(n-1) x B], status [B].  From indirect_events_mass
+    also propellant [B] and dm_seg [(n-1) x B] in kg (None otherwise)."""
 
-    def __init__(self, n_events, t_event, kind, on0, dv, burn_time, dv_seg, status):
+    def __init__(self, n_events, t_event, kind, on0, dv, burn_time, dv_seg, status, propellant=None, dm_seg=None):
         self.n_events, self.t_event, self.kind, self.on0 = n_events, t_event, kind, on0
         self.dv, self.burn_time, self.dv_seg, self.status = dv, burn_time, dv_seg, status
+        self.propellant, self.dm_seg = propellant, dm_seg
 
 
 def indirect_events(XC_all, t_TU, params, max_events=64, integ=None, ctx=None, with_dv_seg=True):
@@ -598,6 +600,42 @@ def indirect_events(XC_all, t_TU, params, max_events=64, integ=None, ctx=None, w
         return ThrustEvents(int(n_events[0]), t_event[:, 0], kind[:, 0], int(on0[0]), float(dv[0]), float(burn[0]),
                             None if dv_seg is None else dv_seg[:, 0], int(status[0]))
     return ThrustEvents(n_events, t_event, kind, on0, dv, burn, dv_seg, status)
+
+
+def indirect_events_mass(XC_all, t_TU, params, max_events=64, integ=None, ctx=None, with_dv_seg=True, with_dm_seg=True):
+    """indirect_events for the 14-row variable-mass system (lto_indirect_events_mass_batch): XC_all [14 x n] or
+    [14 x n x B], params with Isp in the mass slot.  The threshold of p > 1 follows the state's mass.  Returns a ThrustEvents
+    with propellant [B] and dm_seg [(n-1) x B] (kg) added."""
+    XC = _f64(XC_all)
+    if XC.ndim not in (2, 3) or XC.shape[0] != 14:
+        raise ValueError("XC_all must be [14 x n] or [14 x n x B]")
+    ndim, n, B, batched = _batch_dims(XC)
+    t, ntg = _tgrids(t_TU, n, B)
+    prm, nprm = _params_array(params)
+    if nprm != 1 and nprm != B:
+        raise ValueError("params must be one tuple or one per trajectory")
+    if not all(prm[k].mass > 0.0 for k in range(nprm)):
+        raise ValueError("Isp (the mass slot of 14-row params) must be positive")
+    M = int(max_events)
+    Mr = max(M, 1)
+    n_events = np.zeros(B, dtype=np.int32)
+    t_event = np.full((Mr, B), np.nan, order="F")
+    kind = np.zeros((Mr, B), dtype=np.int32, order="F")
+    on0 = np.zeros(B, dtype=np.int32)
+    dv, burn, prop = np.zeros(B), np.zeros(B), np.zeros(B)
+    dv_seg = np.zeros((n - 1, B), order="F") if with_dv_seg else None
+    dm_seg = np.zeros((n - 1, B), order="F") if with_dm_seg else None
+    status = np.zeros(B, dtype=np.int32)
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    ctx.check(ctx.fn("indirect_events_mass_batch")(ctx.handle, n, B, _ptr(XC), _ptr(t), ntg, prm, nprm, C.byref(integ), M,
+                                                   _ptr(n_events), _ptr(t_event), _ptr(kind), _ptr(on0), _ptr(dv), _ptr(burn),
+                                                   _ptr(dv_seg), _ptr(prop), _ptr(dm_seg), _ptr(status)))
+    if not batched:
+        return ThrustEvents(int(n_events[0]), t_event[:, 0], kind[:, 0], int(on0[0]), float(dv[0]), float(burn[0]),
+                            None if dv_seg is None else dv_seg[:, 0], int(status[0]), float(prop[0]),
+                            None if dm_seg is None else dm_seg[:, 0])
+    return ThrustEvents(n_events, t_event, kind, on0, dv, burn, dv_seg, status, prop, dm_seg)
 
 
 def direct_defectCalc(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None):
@@ -1295,6 +1333,14 @@ class IndirectPlan:
         self.ctx.check(self.ctx.lib.lto_indirect_events_dev(self.handle, stream, _dptr(X), int(ldx), _dptr(t), int(n_tgrids),
                                                             int(max_events), _dptr(n_events), _dptr(t_event), _dptr(kind), _dptr(on0),
                                                             _dptr(dv), _dptr(burn_time), _dptr(dv_seg), _dptr(status)))
+
+    def events_mass(self, X, ldx, t, n_tgrids, max_events, n_events, t_event, kind, on0, dv, burn_time, propellant, status,
+                    dv_seg=None, dm_seg=None, stream=None):
+        """The same on a 14-row plan (lto_indirect_events_mass_dev): X [14][ldx]; propellant [n_batch]; dm_seg [S] or None."""
+        self.ctx.check(self.ctx.lib.lto_indirect_events_mass_dev(self.handle, stream, _dptr(X), int(ldx), _dptr(t), int(n_tgrids),
+                                                                 int(max_events), _dptr(n_events), _dptr(t_event), _dptr(kind),
+                                                                 _dptr(on0), _dptr(dv), _dptr(burn_time), _dptr(dv_seg),
+                                                                 _dptr(propellant), _dptr(dm_seg), _dptr(status)))
 
     def newton_solve(self, Phi, ldp, defect, ldd, delta, ldx, stream=None, adjoints_only=False):
         """delta = -J \\ defect on the device; Phi=None re-uses the stored factorisation (SOC re-solve)."""

@@ -1,0 +1,260 @@
+"""Host reference for the variable-mass thrust-arc kernels (k_indirect_events_mass, k_events_compact) -- CPU only, no
+library code under test.
+
+Per segment scipy.integrate.solve_ivp(method="DOP853", rtol = atol = 1e-13, events = g) on the 15-dimensional augmented system
+(y[14], q), q' = umag(|lambda_v|, m), with oracle.rhs_state_costate_mass and addtime_reference.umag at the state's own mass;
+g = n - 1 (p = 1) or n - p (cT / m)^(p-1) with the CURRENT mass (p > 1).  dm = m_i - m(t_{i+1}).  A second determination of every
+root: scipy.optimize.brentq on g of the oracle's own flow, oracle.indirect14(two nodes, [0, tau], want_stm=False), defect plus
+the next node.  For LTO_RK4 the device's algorithm restated in numpy (as thrust_reference.seg_reference_rk4).  The joins, the
+compaction and the order of the sums are thrust_reference's.
+
+Fixtures: the node sets of thrust_reference.CASES lifted to 14 rows: node masses m0 - 0.05 k, lambda_m = 0.3, lambda_v rescaled to
+the 14-row threshold AT EACH NODE'S OWN MASS (the 12-row scaling loses the p = 2 crossings at 700 kg), for
+(Isp, m0) in COMBOS.  Admission: both determinations succeed and |dg/dt| >= 0.1 per TU at every root, dg/dt including the
+threshold's own rate for p > 1.
+
+Bars, from the reference's own error as DESIGN 4.18 takes them: e_t the largest difference between the two determinations, e_dv
+and e_dm the largest relative differences of a trajectory's reference dv and propellant between tolerances 1e-13 and 1e-12;
+bars max(1e-12, 10 e_t) + 4 eps max|t| TU, 10 e_dv and 10 e_dm relative.  Measured over FIXTURES (5 s on one core):
+e_t = 8.9e-14 TU (66 nodes at Isp 20 s; 8.5e-15 on the 2- and 3-node cases), e_dv = 2.5e-9, e_dm = 2.5e-9 (both on the 0.6 TU
+segment at 700 kg; dm = m (1 - exp(-kappa q)) carries q's error), so the bars are 1e-12 TU, 2.5e-8 and 2.5e-8.  Rocket equation in
+the reference, |kappa q - ln(m_i / m_end)| <= 5.5e-16 over all segments.  The 14-row roots differ from the 12-row ones of the same
+nodes by 1.7e-8 TU (0.6 TU segment, second root, 1000 kg), 1.3e-4 TU (the same at 700 kg) and 3.7e-7 TU (p = 2, 1000 kg)."""
+import functools
+from collections import namedtuple
+
+import numpy as np
+
+import addtime_reference as A
+import thrust_reference as R
+from lowthrustopt_amd.constants import MU, DU, TU
+
+IDX12 = [0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12]      # rows of the 12-row system inside the 14-row one
+COMBOS = ((2000.0, 1000.0), (2000.0, 700.0), (20.0, 1000.0))
+SMALL = ("one_crossing", "join_only", "two_crossings")
+# (case, Isp, m0) the tests run, and the bars are measured on
+FIXTURES = tuple((c, isp, m0) for c in SMALL for isp, m0 in COMBOS) + (("mixed66", 2000.0, 1000.0), ("mixed66", 20.0, 1000.0))
+LAMBDA_M = 0.3
+DM_NODE = 0.05
+EPS = R.EPS
+
+
+def prm_tuple(tr, isp):
+    return (MU, DU, TU, tr.thrust, isp, tr.td, tr.p, tr.rho)
+
+
+def c_thrust(prm):
+    return prm[3] / 1e3 * prm[2] ** 2 / prm[1]
+
+
+def kappa(prm):
+    return prm[5] * 1e3 * prm[1] / (prm[2] * prm[4] * 9.81)
+
+
+def threshold(prm, m):
+    """g = |lambda_v| - threshold at mass m; None: p = 0, always on."""
+    p = prm[6]
+    if p == 0:
+        return None
+    return 1.0 if p == 1 else p * (c_thrust(prm) / m) ** (p - 1.0)
+
+
+def lift(XC12, tr, isp, m0):
+    """[14 x n] from a 12-row fixture trajectory."""
+    n = XC12.shape[1]
+    XC = np.zeros((14, n), order="F")
+    XC[IDX12] = XC12
+    XC[6] = m0 - DM_NODE * np.arange(n)
+    XC[13] = LAMBDA_M
+    thr12 = R.threshold(R.prm_tuple(tr))
+    if thr12 is not None:
+        for k in range(n):
+            XC[10:13, k] *= threshold(prm_tuple(tr, isp), XC[6, k]) / thr12
+    return XC
+
+
+@functools.lru_cache(maxsize=None)
+def case_problem(name, isp, m0):
+    """(XC [14 x n x B], T [n x B], [params tuples]) of a lifted case; shared, nobody writes into it."""
+    spec = R._spec(name)
+    parts = [R.make_traj(tr) for tr in spec]
+    XC = np.asfortranarray(np.stack([lift(p[0], tr, isp, m0) for p, tr in zip(parts, spec)], axis=2))
+    T = np.asfortranarray(np.stack([p[1] for p in parts], axis=1))
+    XC.setflags(write=False); T.setflags(write=False)
+    return XC, T, [prm_tuple(tr, isp) for tr in spec]
+
+
+def g_of(y, prm):
+    return float(np.linalg.norm(y[10:13]) - threshold(prm, y[6]))
+
+
+def is_on(y, prm):
+    return 1 if prm[6] == 0 else int(g_of(y, prm) > 0.0)
+
+
+def umag(y, prm):
+    return float(A.umag(np.asarray(y[10:13]).reshape(3, 1), prm[3], prm[6], prm[7], y[6], prm[1], prm[2])[0])
+
+
+def rhs15(O, z, prm):
+    out = np.empty(15)
+    out[:14] = O.rhs_state_costate_mass(z[:14], np.array(prm))
+    out[14] = umag(z, prm)
+    return out
+
+
+def slope(O, y, prm):
+    """dg/dt at a state: d|lambda_v|/dt minus the threshold's own rate (p > 1: the mass moves it)."""
+    dy = O.rhs_state_costate_mass(y[:14], np.array(prm))
+    s = float(np.dot(y[10:13], dy[10:13]) / np.linalg.norm(y[10:13]))
+    p = prm[6]
+    if p > 1:
+        s += p * (p - 1.0) * c_thrust(prm) ** (p - 1.0) * y[6] ** (-p) * dy[6]
+    return s
+
+
+SegM = namedtuple("SegM", "roots q on_s on_e ont slopes gmin dm m_end", defaults=(None, None, None))
+
+
+def seg_reference(O, y0, ta, tb, prm, tol=1e-13):
+    from scipy.integrate import solve_ivp
+    z0 = np.append(np.asarray(y0, dtype=np.float64), 0.0)
+    ev = None if prm[6] == 0 else (lambda t, z: g_of(z, prm))
+    sol = solve_ivp(lambda t, z: rhs15(O, z, prm), (ta, tb), z0, method="DOP853", rtol=tol, atol=tol, events=ev)
+    assert sol.success
+    roots = [] if ev is None else [float(r) for r in sol.t_events[0]]
+    slopes = [] if ev is None else [slope(O, z, prm) for z in sol.y_events[0]]
+    on_s, on_e = is_on(z0, prm), is_on(sol.y[:, -1], prm)
+    gmin = None if ev is None else min(abs(g_of(sol.y[:, k], prm)) for k in range(sol.y.shape[1]))
+    m_end = float(sol.y[6, -1])
+    return SegM(roots, float(sol.y[14, -1]), on_s, on_e, R._on_time(roots, on_s, ta, tb), slopes, gmin, float(z0[6] - m_end), m_end)
+
+
+def flow14(O, y0, prm, tau):
+    """The oracle's own flow of a node over tau: defect plus the next node."""
+    y0 = np.asarray(y0, dtype=np.float64)
+    XC = np.asfortranarray(np.stack([y0, y0], axis=1))
+    _, defect, rc = O.indirect14(XC, np.array([0.0, tau]), np.array(prm), O.DOP853_ADAPTIVE, 0, 1e-13, 1e-13, want_stm=False)
+    assert rc == 0
+    return defect[:, 0] + y0
+
+
+def roots_brentq(O, y0, ta, prm, roots, tb, half=1e-4):
+    from scipy.optimize import brentq
+
+    def f(tau):
+        return g_of(flow14(O, y0, prm, tau - ta), prm)
+    out = []
+    for r in roots:
+        lo, hi = max(ta + 1e-9, r - half), min(tb, r + half)
+        out.append(float(brentq(f, lo, hi, xtol=1e-16, rtol=8.9e-16)))
+    return out
+
+
+def _rk4(O, z, h, prm):
+    k1 = rhs15(O, z, prm)
+    k2 = rhs15(O, z + 0.5 * h * k1, prm)
+    k3 = rhs15(O, z + 0.5 * h * k2, prm)
+    k4 = rhs15(O, z + h * k3, prm)
+    return z + h / 6.0 * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
+
+
+def seg_reference_rk4(O, y0, ta, tb, prm, steps):
+    """One segment the way the device steps it with LTO_RK4."""
+    z = np.append(np.asarray(y0, dtype=np.float64), 0.0)
+    m_i = float(z[6])
+    h = (tb - ta) / steps
+    on_s = on = is_on(z, prm)
+    roots = []
+    for k in range(steps):
+        z0, t0 = z, ta + k * h
+        z = _rk4(O, z0, h, prm)
+        on1 = is_on(z, prm)
+        if on1 != on:
+            lo, hi, t_hi = 0.0, 1.0, t0 + h
+            for _ in range(60):
+                mid = 0.5 * (lo + hi)
+                if is_on(_rk4(O, z0, mid * h, prm), prm) == on:
+                    lo = mid
+                else:
+                    hi = mid
+                t_lo, t_hi = t0 + lo * h, t0 + hi * h
+                if not t_hi > np.nextafter(t_lo, np.inf):
+                    break
+            roots.append(float(t_hi))
+            on = on1
+    return SegM(roots, float(z[14]), on_s, on, R._on_time(roots, on_s, ta, tb), [], None, m_i - float(z[6]), float(z[6]))
+
+
+ArcsM = namedtuple("ArcsM", "arcs dm_seg propellant")
+
+
+def compact(segs, t, max_events=64):
+    """thrust_reference.compact of the segments, and the mass budget in the order of its sums."""
+    dm_seg = np.array([s.dm for s in segs])
+    return ArcsM(R.compact(segs, t, max_events), dm_seg, R.wave_sum(dm_seg))
+
+
+@functools.lru_cache(maxsize=None)
+def case_reference(name, isp, m0, tol=1e-13, rk4_steps=None, max_events=64):
+    """[(segments, ArcsM)] per trajectory of a lifted case; computed once per process."""
+    from oracle import oracle as O
+    XC, T, prms = case_problem(name, isp, m0)
+    out = []
+    for b, prm in enumerate(prms):
+        n = XC.shape[1]
+        if rk4_steps:
+            segs = [seg_reference_rk4(O, XC[:, i, b], T[i, b], T[i + 1, b], prm, rk4_steps) for i in range(n - 1)]
+        else:
+            segs = [seg_reference(O, XC[:, i, b], T[i, b], T[i + 1, b], prm, tol) for i in range(n - 1)]
+        out.append((segs, compact(segs, T[:, b], max_events)))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def case_brentq(name, isp, m0):
+    """Per trajectory, per segment: the second determination of its roots."""
+    from oracle import oracle as O
+    XC, T, prms = case_problem(name, isp, m0)
+    return [[roots_brentq(O, XC[:, i, b], T[i, b], prm, s.roots, T[i + 1, b]) if s.roots else [] for i, s in enumerate(segs)]
+            for b, (prm, (segs, _)) in enumerate(zip(prms, case_reference(name, isp, m0)))]
+
+
+def admitted(name, isp, m0):
+    """Both determinations succeed (case_brentq raises where a bracket cannot be formed) and every root is steep enough."""
+    case_brentq(name, isp, m0)
+    return all(abs(x) >= R.MIN_SLOPE for segs, _ in case_reference(name, isp, m0) for s in segs for x in s.slopes)
+
+
+@functools.lru_cache(maxsize=None)
+def tolerances(fixtures=FIXTURES):
+    """(e_t, e_dv, e_dm) measured on the fixtures."""
+    e_t = e_dv = e_dm = 0.0
+    for name, isp, m0 in fixtures:
+        fine, coarse = case_reference(name, isp, m0), case_reference(name, isp, m0, 1e-12)
+        second = case_brentq(name, isp, m0)
+        for b, (segs, ref) in enumerate(fine):
+            for i, s in enumerate(segs):
+                if s.roots:
+                    e_t = max(e_t, float(np.max(np.abs(np.array(second[b][i]) - np.array(s.roots)))))
+            e_dv = max(e_dv, abs(ref.arcs.dv - coarse[b][1].arcs.dv) / abs(ref.arcs.dv))
+            e_dm = max(e_dm, abs(ref.propellant - coarse[b][1].propellant) / abs(ref.propellant))
+    return e_t, e_dv, e_dm
+
+
+def bars(fixtures=FIXTURES):
+    """(bar on |t_event - ref| in TU before the rounding of t, relative bar on dv, relative bar on propellant)."""
+    e_t, e_dv, e_dm = tolerances(fixtures)
+    return max(1e-12, 10.0 * e_t), 10.0 * e_dv, 10.0 * e_dm
+
+
+def check_mass(ev, b, ref, bdm, label):
+    """Trajectory b of a batched device result against its reference mass budget: propellant relative, dm_seg to the
+    propellant's absolute bar, propellant == wave_sum(dm_seg) bit for bit.  Returns the relative propellant error."""
+    e = abs(ev.propellant[b] - ref.propellant) / abs(ref.propellant)
+    print("MEASURED %s[%d]: propellant %.6e kg, rel %.3e (bar %.1e)" % (label, b, ref.propellant, e, bdm))
+    assert e <= bdm
+    if ev.dm_seg is not None:
+        assert np.all(np.abs(ev.dm_seg[:, b] - ref.dm_seg) <= bdm * abs(ref.propellant))
+        assert ev.propellant[b] == R.wave_sum(ev.dm_seg[:, b])
+    return e
