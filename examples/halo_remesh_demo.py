@@ -5,7 +5,12 @@ The demo transfer (halo_transfer_demo.py) is taken down the rho ladder 1, 1/2, 1
 is then re-meshed so that every segment takes the same share of the integrator's trial steps, and re-solved on the new grid.
 Printed: max / mean / total trial steps per defect sweep before and after, and the defect- and STM-sweep kernel times on both grids.
 
+With --mass the ladder's last level is lifted to the 14-row variable-mass system (drivers.lift_to_mass), solved there with a free
+final mass, re-meshed (lto_indirect_remesh_mass_batch) and the trial steps and the propellant before and after are
+printed.
+
 usage: halo_remesh_demo.py [rho_target] [n_new] [passes]
+       halo_remesh_demo.py --mass [Isp]
 """
 import importlib.util
 import os
@@ -91,6 +96,34 @@ def main(rho_target=RHO_TARGET, n_new=None, passes=2):
     return r
 
 
+def main_mass(Isp=2000.0, rho_target=RHO_TARGET, n_new=None, passes=2):
+    ctx = lto.default_context(0)
+    t, levels = rho_ladder(rho_target)
+    rho, XC12 = levels[-1]
+    n = t.size
+    n_new = n_new or n
+    XC, _, flag = drivers.multiShoot_CRTBP_indirect_mass(drivers.lift_to_mass(XC12, MASS), t, MU, DU, TU, n, Isp, THRUST, False, False,
+                                                         30, 1.0, rho, verbose=False)
+    if flag != 0:
+        raise RuntimeError("the variable-mass solve did not converge (status %d)" % flag)
+    prm = lto.make_params(MU, DU, TU, THRUST, Isp, 1.0, 1.0, rho)
+    r = lto.indirect_remesh_mass(XC, t, prm, n_new=n_new, passes=passes, ctx=ctx)
+    print("variable mass, Isp = %g s, rho = %g, %d -> %d nodes, %d passes: status %d after %d iterations, max |defect| %.2e"
+          % (Isp, rho, n, n_new, passes, r.status, r.iterations, np.abs(r.defect).max()))
+    print("trial steps per defect sweep, old grid: " + stats(r.steps_before))
+    print("trial steps per defect sweep, new grid: " + stats(r.steps_after))
+    a0 = drivers.thrust_arcs_mass(XC, t, MU, DU, TU, Isp, THRUST, 1.0, rho, ctx=ctx)
+    print("propellant, old grid: %.6f kg (final mass %.6f kg)" % (a0["propellant_kg"], a0["mass_final_kg"]))
+    if r.status == 0:
+        a1 = drivers.thrust_arcs_mass(r.XC_out, r.t_out, MU, DU, TU, Isp, THRUST, 1.0, rho, ctx=ctx)
+        print("propellant, new grid: %.6f kg (final mass %.6f kg), relative difference %.2e"
+              % (a1["propellant_kg"], a1["mass_final_kg"], abs(a1["propellant_kg"] - a0["propellant_kg"]) / a0["propellant_kg"]))
+    return r
+
+
 if __name__ == "__main__":
     a = sys.argv[1:]
+    if a and a[0] == "--mass":
+        main_mass(float(a[1]) if len(a) > 1 else 2000.0)
+        sys.exit(0)
     main(float(a[0]) if a else RHO_TARGET, int(a[1]) if len(a) > 1 else None, int(a[2]) if len(a) > 2 else 2)

@@ -203,6 +203,11 @@ int lto_indirect_solve_batch(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, c
  * state appended.  XC_dense [ndim x n_desired], t_dense [n_desired]. */
 int lto_indirect_densify(lto_ctx* ctx, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
                          const lto_integrator* integ, int n_desired, double* XC_dense, double* t_dense);
+/* The same for one trajectory of the 14-row variable-mass system: XC [14 x n_nodes], XC_dense [14 x n_desired], Isp in
+ * prm->mass as everywhere for 14 rows.  lto_indirect_densify itself keeps answering LTO_EUNSUPPORTED to ndim = 14.  LTO_RK4 or
+ * LTO_DOP853_ADAPTIVE; any other method: LTO_EUNSUPPORTED.  LTO_ENULL; LTO_EINVAL (n_nodes < 2, n_desired < 2). */
+int lto_indirect_densify_mass(lto_ctx* ctx, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                              const lto_integrator* integ, int n_desired, double* XC_dense, double* t_dense);
 
 /* Replaces defectCalc of multiShoot_CRTBP_direct (src/multiShoot_CRTBP_direct.jl:66-109).
  *   X [nstate x n_nodes x n_batch] (nstate = 6 or 7), U [3 x n_nodes x n_batch] thrust in N,
@@ -432,6 +437,23 @@ int lto_indirect_remesh(lto_ctx* ctx, int ndim, int n_nodes, const double* XC, c
                         const lto_integrator* integ, int n_new, const double* weights, int passes, int flag_adjointsOnly,
                         int maxIter, double* t_out, double* XC_guess, double* XC_out, double* defect, int* status_flag,
                         int* iterations, double* history, int* steps_before, int* steps_after);
+/* The same for converged solutions of the 14-row variable-mass system, y = (r, v, m, lambda_r, lambda_v, lambda_m):
+ * XC [14 x n_nodes x n_batch], XC_guess / XC_out [14 x n_new x n_batch], defect [14 x (n_new-1) x n_batch], lto_params.mass carrying
+ * Isp as everywhere for 14 rows.  The monitor, the grid rule and its summation order, `passes`, the bit-copy rules (a zero span, the
+ * first and the last node), the limits and the error codes are those of lto_indirect_remesh_batch above; the nodes are propagated
+ * with the 14-row system, so the mass row of a new node is the propagated mass.  The re-solve is the 14-row loop of
+ * lto_indirect_solve_batch: it pins XC[0:7, 0] (position, velocity and m0) and XC[0:6, n_new-1], sets XC[13, n_new-1] = 0 and leaves
+ * the final mass free.  The guess's first and last nodes being copies, m0 and a converged input's lambda_m(tf) = 0 arrive there
+ * unchanged.  An integrator other than LTO_RK4 / LTO_DOP853_ADAPTIVE: LTO_EUNSUPPORTED. */
+int lto_indirect_remesh_mass_batch(lto_ctx* ctx, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                                   const lto_params* prm, int n_prm, const lto_integrator* integ, int n_new, const double* weights,
+                                   int passes, int flag_adjointsOnly, int maxIter, double* t_out, double* XC_guess, double* XC_out,
+                                   double* defect, int* status_flag, int* iterations, double* history, int* steps_before,
+                                   int* steps_after);
+int lto_indirect_remesh_mass(lto_ctx* ctx, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                             const lto_integrator* integ, int n_new, const double* weights, int passes, int flag_adjointsOnly,
+                             int maxIter, double* t_out, double* XC_guess, double* XC_out, double* defect, int* status_flag,
+                             int* iterations, double* history, int* steps_before, int* steps_after);
 
 /* One Jacobian sweep and one free-end QP step (arguments as lto_direct_qp_step); targets, model and beta [n_targets] (1 or
  * n_batch).  p_out [2 x n_batch] = (p1; p2); cost includes the beta term.  The 2 x 2 bound-constrained problem in p is solved
@@ -717,6 +739,13 @@ int lto_line_search_pick_dev(lto_ctx* ctx, void* stream, const double* sumsq, co
 int lto_indirect_dense_dev(lto_indirect_plan* plan, void* stream, const double* X, long ldx, const double* t,
                            int n_tgrids, const int* first, const double* t_samples, double* Y, long ldy,
                            double* final_state);
+/* Dense output of the 14-row variable-mass system: the contract of lto_indirect_dense_dev on a 14-row plan, X [14][ldx],
+ * Y [14][ldy], final_state [14 x n_batch]; every sample is reached by stepping the 14-row system onto it, so row 6 of Y is the
+ * propagated mass.  LTO_RK4 and LTO_DOP853_ADAPTIVE; a plan that is not 14-row, or any other method: LTO_EUNSUPPORTED, before
+ * anything is launched. */
+int lto_indirect_dense_mass_dev(lto_indirect_plan* plan, void* stream, const double* X, long ldx, const double* t,
+                                int n_tgrids, const int* first, const double* t_samples, double* Y, long ldy,
+                                double* final_state);
 
 /* Switch times, burn arcs and dv of indirect solutions.  For a trajectory with parameters (thrustLimit, mass, p, rho):
  * n = |lambda_v|, aL = thrustLimit / mass / 1e3 * TU^2 / DU, umag(n) the control law of stateCostate_deriv.jl:36-53.  The engine is

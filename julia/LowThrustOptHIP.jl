@@ -16,7 +16,7 @@ using SparseArrays, LinearAlgebra, Libdl
 export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pack_soa!, unpack_soa!, defect_norms!, indirect_defect_dev!,
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
-export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, addTimeFinal, tf_sweep, meshRefine_indirect, remesh_batch,
+export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
        direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
@@ -201,6 +201,21 @@ function densify(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}
     (XC_dense, t_dense)
 end
 
+"""densify for one solution of the 14-row variable-mass system (`lto_indirect_densify_mass`, DESIGN 4.20): `XC_all` [14 x n_nodes],
+`params` with Isp in the mass slot.  Returns (XC_dense [14 x n_desired], t_dense); row 7 is the propagated mass."""
+function densify_mass(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}, params, n_desired::Integer;
+                      integ::LtoIntegrator = LtoIntegrator())
+    size(XC_all, 1) == 14 || throw(ArgumentError("densify_mass takes the 14-row solution [14 x n_nodes]"))
+    n_nodes = size(XC_all, 2)
+    XC_dense = zeros(14, n_desired)
+    t_dense = zeros(n_desired)
+    rc = ccall((:lto_indirect_densify_mass, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoParams}, Ref{LtoIntegrator}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+               ctx.handle, n_nodes, XC_all, t_TU, Ref(LtoParams(params)), Ref(integ), n_desired, XC_dense, t_dense)
+    check(ctx, rc)
+    (XC_dense, t_dense)
+end
+
 """The whole Newton loop of multiShoot_CRTBP_indirect (indirect.jl:254-345) in one library call, trajectory resident on
 the GPU: returns (XC_all, defect, status_flag) exactly as the reference driver does, so
 `multiShoot_CRTBP_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass0, thrustLimit, plot_yn, flag_adjointsOnly, maxIter, p, rho)`
@@ -331,6 +346,47 @@ function remesh_batch(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::Matrix{Fl
                 Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint},
                 Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
                ctx.handle, ndim, n_nodes, B, XC_all, t_TU, B, prm, length(prm), Ref(integ), n_new, C_NULL, passes,
+               flag_adjointsOnly ? 1 : 0, maxIter, t, C_NULL, XC, defect1, status, iters, C_NULL, before, after)
+    check(ctx, rc)
+    (XC, t, Int.(status), Int.(iters), Int.(before), Int.(after))
+end
+
+"""`meshRefine_indirect` for a converged solution of the 14-row variable-mass system (`lto_indirect_remesh_mass`, DESIGN 4.20):
+`XC_all` [14 x n_nodes], Isp in place of the mass.  The re-solve keeps r0, v0, m0 and rf, vf and leaves the final mass free.  Returns
+(XC_new, t_new, n_new) on status 0, otherwise the original (XC_all, t_TU, n_nodes)."""
+function meshRefine_indirect_mass(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}, MU, DU, TU, n_nodes, Isp,
+                                  thrustLimit, p, rho; n_new::Integer = n_nodes, passes::Integer = 2,
+                                  weights::Union{Nothing,Vector{Float64}} = nothing, maxIter::Integer = 10,
+                                  flag_adjointsOnly::Bool = false, integ::LtoIntegrator = LtoIntegrator())
+    size(XC_all) == (14, n_nodes) || throw(ArgumentError("meshRefine_indirect_mass takes the 14-row solution [14 x n_nodes]"))
+    length(t_TU) == n_nodes || throw(ArgumentError("meshRefine_indirect_mass takes one time per node"))
+    XC_new = zeros(14, n_new); t_new = zeros(n_new); defect1 = zeros(14, n_new - 1)
+    status = Ref{Cint}(0); iters = Ref{Cint}(0)
+    prm = Ref(LtoParams((MU, DU, TU, thrustLimit, Isp, 1.0, p, rho)))
+    rc = ccall((:lto_indirect_remesh_mass, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoParams}, Ref{LtoIntegrator}, Cint, Ptr{Cdouble}, Cint, Cint,
+                Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
+               ctx.handle, n_nodes, XC_all, t_TU, prm, Ref(integ), n_new, weights === nothing ? C_NULL : weights, passes,
+               flag_adjointsOnly ? 1 : 0, maxIter, t_new, C_NULL, XC_new, defect1, status, iters, C_NULL, C_NULL, C_NULL)
+    check(ctx, rc)
+    status[] == 0 ? (XC_new, t_new, Int(n_new)) : (XC_all, t_TU, Int(n_nodes))
+end
+
+"""`remesh_batch` for the 14-row variable-mass system (`lto_indirect_remesh_mass_batch`): `XC_all` [14 x n_nodes x n_batch], `params`
+with Isp in the mass slot.  Returns (XC [14 x n_new x B], t [n_new x B], status [B], iterations [B], steps_before, steps_after)."""
+function remesh_mass_batch(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::Matrix{Float64}, params::Vector;
+                           n_new::Integer = size(XC_all, 2), passes::Integer = 2, maxIter::Integer = 10,
+                           flag_adjointsOnly::Bool = false, integ::LtoIntegrator = LtoIntegrator())
+    ndim, n_nodes, B = size(XC_all)
+    ndim == 14 || throw(ArgumentError("remesh_mass_batch takes 14-row solutions [14 x n_nodes x n_batch]"))
+    prm = [LtoParams(q) for q in params]
+    XC = zeros(14, n_new, B); t = zeros(n_new, B); defect1 = zeros(14, n_new - 1, B)
+    status = zeros(Cint, B); iters = zeros(Cint, B); before = zeros(Cint, n_nodes - 1, B); after = zeros(Cint, n_new - 1, B)
+    rc = ccall((:lto_indirect_remesh_mass_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Cint,
+                Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint},
+                Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
+               ctx.handle, n_nodes, B, XC_all, t_TU, B, prm, length(prm), Ref(integ), n_new, C_NULL, passes,
                flag_adjointsOnly ? 1 : 0, maxIter, t, C_NULL, XC, defect1, status, iters, C_NULL, before, after)
     check(ctx, rc)
     (XC, t, Int.(status), Int.(iters), Int.(before), Int.(after))

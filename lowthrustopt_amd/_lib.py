@@ -82,6 +82,7 @@ SIGNATURES = {
                                            C.POINTER(LtoIntegrator), C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lto_indirect_densify": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator), C.c_int,
                                        _vp, _vp]),
+    "lto_indirect_densify_mass": (C.c_int, [_vp, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator), C.c_int, _vp, _vp]),
     "lto_indirect_add_time_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator),
                                               C.POINTER(LtoDirectOrbits), C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                               _vp, _vp, _vp, _vp, _vp]),
@@ -95,6 +96,11 @@ SIGNATURES = {
                                             _vp, _vp, _vp, _vp]),
     "lto_indirect_remesh": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator), C.c_int, _vp,
                                       C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_indirect_remesh_mass_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.POINTER(LtoParams), C.c_int,
+                                                 C.POINTER(LtoIntegrator), C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, _vp]),
+    "lto_indirect_remesh_mass": (C.c_int, [_vp, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator), C.c_int, _vp,
+                                           C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_direct_defect": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int,
                                     C.POINTER(LtoDirectParams), _vp, _vp]),
     "lto_direct_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int,
@@ -137,6 +143,7 @@ SIGNATURES = {
     "lto_read_scalars_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
     "lto_line_search_pick_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_long, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_long]),
     "lto_indirect_dense_dev": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp]),
+    "lto_indirect_dense_mass_dev": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp]),
     "lto_indirect_events_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.POINTER(LtoParams), C.c_int,
                                             C.POINTER(LtoIntegrator), C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_indirect_events": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator), C.c_int, _vp,

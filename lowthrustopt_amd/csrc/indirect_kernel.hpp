@@ -423,5 +423,7 @@ template <> hipError_t launch_defect_nd<12>(int pm, int method, const IndirectAr
 template <> hipError_t launch_defect_nd<14>(int pm, int method, const IndirectArgs& a, hipStream_t st);
 template <> hipError_t launch_stm_nd<12>(int pm, int method, int cols, const IndirectArgs& a, hipStream_t st);
 template <> hipError_t launch_stm_nd<14>(int pm, int method, int cols, const IndirectArgs& a, hipStream_t st);
+// dense output of the 14-row system (kernels_indirect14.hip)
+hipError_t launch_dense14(int pm, int method, const IndirectArgs& a, const DenseArgs& d, hipStream_t st);
 
 }  // namespace lto

@@ -314,14 +314,15 @@ struct RemeshGridArgs {
   int* seg_of;
 };
 hipError_t launch_remesh_grid(const RemeshGridArgs& r, hipStream_t st);
-// Nodes: a = the sweep arguments of the OLD trajectories (X, t, tp, the integrator); new node j = b n_new + k -> G [12][ldg]
+// Nodes: a = the sweep arguments of the OLD trajectories (X, t, tp, the integrator); new node j = b n_new + k -> G [ndim][ldg]
+// (ndim = 12, or 14 for the variable-mass system)
 struct RemeshNodeArgs {
   const double* tn;
   const int* seg_of;
   double* G; long ldg;
   int n_new, n_batch;
 };
-hipError_t launch_remesh_nodes(int pm, int method, const IndirectArgs& a, const RemeshNodeArgs& r, hipStream_t st);
+hipError_t launch_remesh_nodes(int ndim, int pm, int method, const IndirectArgs& a, const RemeshNodeArgs& r, hipStream_t st);
 // Resampling of direct solutions onto one node count (kernels_direct_resample.hip).  The current meshes, node-major
 // with `cap` columns per trajectory of which the first n[b] are valid (n null: all of them), and what one pass makes of them.
 struct DirectResampleArgs {

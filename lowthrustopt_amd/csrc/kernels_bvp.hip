@@ -507,6 +507,11 @@ __device__ __forceinline__ void bvp_final_one(const BvpArgs& a, const double* ro
 // lambda_r, lambda_v (square: 14 x 14) or lambda_r, lambda_v only (adjoints-only: 14 x 13, least squares).  Householder QR with
 // lane = column (the pair reduction's reflection, 14 rows), then back-substitution on broadcast values.  The re-solve forms it
 // again from the kept matrix and the new right-hand side (one small problem per trajectory).
+// Rank: the reference's `\` is SuiteSparseQR, which treats a column whose diagonal of R is no larger than
+// 20 (m + n) eps max_j |A_:j|_2 as dependent and returns the basic solution with that unknown at zero.  The same rule here, on the
+// 14 x NC system that is left: for p = 0 every positive multiple of the costates solves the boundary-value problem, the system is
+// singular along that direction, and dividing by the rounding-sized last diagonal multiplied the costates of a converged guess by 19
+// (DESIGN 4.20).  A diagonal above the threshold is divided by exactly as before.
 template <int NU>
 __device__ __forceinline__ void bvp_final_qr14(const BvpArgs& a, const double* row, const double* rhs, const int b, const int lane) {
   constexpr int NX = 14;
@@ -522,6 +527,11 @@ __device__ __forceinline__ void bvp_final_qr14(const BvpArgs& a, const double* r
     else if (lane == NC) v = rhs ? rhs[r] : row[2 * NX * NU + r];
     col[r] = v;
   }
+  double cn2 = 0.0, an2 = 0.0;                          // the largest column norm of the matrix (squared)
+#pragma unroll
+  for (int r = 0; r < NX; ++r) cn2 = __builtin_fma(col[r], col[r], cn2);
+  bvp_static_for<0, NC>([&](auto kc) { an2 = fmax(an2, lane_bcast<decltype(kc)::value>(cn2)); });
+  const double rank_tol = 20.0 * (NX + NC) * 2.220446049250313e-16 * sqrt(an2);
   bvp_static_for<0, NC>([&](auto kc) {
     double vk, g;
     bvp_reflect<NX, decltype(kc)::value, NC + 1>(col, lane, vk, g);
@@ -531,7 +541,8 @@ __device__ __forceinline__ void bvp_final_qr14(const BvpArgs& a, const double* r
   for (int r = 0; r < NC; ++r) y[r] = lane_bcast<NC>(col[r]);      // Q^T r, the rows that meet R
   bvp_static_for<0, NC>([&](auto kc) {
     constexpr int k = NC - 1 - decltype(kc)::value;
-    x[k] = y[k] / lane_bcast<k>(col[k]);
+    const double dk = lane_bcast<k>(col[k]);
+    x[k] = !(fabs(dk) <= rank_tol) ? y[k] / dk : 0.0;     // (a NaN diagonal divides, and shows)
 #pragma unroll
     for (int r = 0; r < k; ++r) y[r] = __builtin_fma(-lane_bcast<k>(col[r]), x[k], y[r]);
   });

@@ -46,7 +46,10 @@ hipError_t launch_indirect_stm(int ndim, int pm, int method, int cols, const Ind
 
 hipError_t launch_indirect_dense(int ndim, int pm, int method, const IndirectArgs& a, const DenseArgs& d, hipStream_t st) {
   if (a.S <= 0) return hipSuccess;
-  if (ndim != 12) return hipErrorInvalidValue;          // (lto_indirect_plan.hip refuses these shapes with LTO_EUNSUPPORTED before it gets here)
+  // 14 rows: the instantiations live in kernels_indirect14.hip and are reached from lto_indirect_dense_mass_dev only
+  // (lto_indirect_dense_dev refuses such plans with LTO_EUNSUPPORTED before it gets here)
+  if (ndim == 14) return launch_dense14(pm, method, a, d, st);
+  if (ndim != 12) return hipErrorInvalidValue;
   switch (method) {
     case M_RK4: return launch_dense_pm<12, M_RK4>(pm, a, d, st);
     case M_DOP853_ADAPTIVE: return launch_dense_pm<12, M_DOP853_ADAPTIVE>(pm, a, d, st);

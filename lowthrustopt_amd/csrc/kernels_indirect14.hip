@@ -1,6 +1,6 @@
 // kernels_indirect14.hip -- ND = 14 instantiations of indirect_kernel.hpp: CRTBP state + mass + costates +
 // mass costate (BASELINE configs[1]; an extension with no reference counterpart, see dynamics.hpp / DESIGN.md).
-#include "indirect_kernel.hpp"
+#include "remesh_nodes.hpp"
 
 namespace lto {
 
@@ -26,6 +26,21 @@ template <> hipError_t launch_stm_nd<14>(int pm, int method, int cols, const Ind
     return hipErrorInvalidValue;
   }
   return hipErrorInvalidValue;      // 13-stage methods: cooperative kernels only (see kernels_indirect.hip)
+}
+
+// Dense output and re-mesh nodes of the variable-mass system: the lane-per-segment / lane-per-new-node kernels of the
+// 12-row system with SysIndirect<14, PM, 0>; RK4 and adaptive DOP853 as there.
+hipError_t launch_dense14(int pm, int method, const IndirectArgs& a, const DenseArgs& d, hipStream_t st) {
+  if (a.S <= 0) return hipSuccess;
+  switch (method) {
+    case M_RK4: return launch_dense_pm<14, M_RK4>(pm, a, d, st);
+    case M_DOP853_ADAPTIVE: return launch_dense_pm<14, M_DOP853_ADAPTIVE>(pm, a, d, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_remesh_nodes14(int pm, int method, const IndirectArgs& a, const RemeshNodeArgs& r, hipStream_t st) {
+  return launch_remesh_nodes_method<14>(pm, method, a, r, st);
 }
 
 }  // namespace lto

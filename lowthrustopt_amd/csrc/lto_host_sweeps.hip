@@ -92,6 +92,56 @@ void segment_samples(const double* g, int nn, const double* td, int m, int* firs
   }
 }
 
+// densify for one trajectory, for lto_indirect_densify (any ndim a plan can be built for; the 12-row dense entry then decides) and
+// lto_indirect_densify_mass (mass = true: 14 rows through lto_indirect_dense_mass_dev)
+static int densify_host(lto_ctx* c, bool mass, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                        const lto_integrator* integ, int n_desired, double* XC_dense, double* t_dense) {
+  lto::HostBuf<int> h_first;
+  HostCall call(c);
+  int rc = plan_build(c, ndim, n_nodes, 1, prm, 1, integ, &call.plan[0]);
+  if (rc) return rc;
+  lto_indirect_plan* p = call.plan[0];
+  const int S = p->S;
+  if (!h_first.alloc((size_t)S + 1)) return set_err(c, LTO_EHIP, "host allocation failed");
+  linrange(t[0], t[n_nodes - 1], n_desired, t_dense);
+  // samples of segment i: t_dense in [t_i, t_{i+1}); the last grid point (== t_n) is served by the final state
+  segment_samples(t, n_nodes, t_dense, n_desired, h_first.data(), 0);
+  h_first[S] = n_desired - 1;
+  const long J = n_nodes;
+  double *d_aos, *d_X, *d_t, *d_td, *d_Y, *d_Yaos;
+  int* d_first;
+  ArenaLayout scratch;
+  scratch.add((size_t)ndim * J, d_aos, d_X);
+  scratch.add((size_t)n_nodes, d_t);
+  scratch.add((size_t)S + 1, d_first);
+  scratch.add((size_t)n_desired, d_td);
+  scratch.add((size_t)ndim * n_desired, d_Y, d_Yaos);
+  rc = scratch.reserve(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  hipError_t e = hipMemcpyAsync(d_aos, XC, sizeof(double) * ndim * J, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n_nodes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_first, h_first.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_td, t_dense, sizeof(double) * n_desired, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = launch_pack_soa(d_aos, ndim, J, d_X, J, st);
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "stage in", e);
+  // the final state lands in the last column of Y: final_state[c * n_batch + traj] with ld = n_desired, offset n_desired-1
+  // is not expressible through the [ND][n_batch] layout, so take it into the tail of d_Yaos and splice on the host side
+  double* d_final = d_Yaos;   // [ndim] (n_batch = 1); overwritten by the unpack afterwards, so copy it out first
+  rc = mass ? lto_indirect_dense_mass_dev(p, st, d_X, J, d_t, 1, d_first, d_td, d_Y, n_desired, d_final)
+            : lto_indirect_dense_dev(p, st, d_X, J, d_t, 1, d_first, d_td, d_Y, n_desired, d_final);
+  if (rc == LTO_OK) {
+    // splice: Y[c][n_desired-1] = final[c]
+    for (int cc = 0; cc < ndim && e == hipSuccess; ++cc)
+      e = hipMemcpyAsync(d_Y + (size_t)cc * n_desired + (n_desired - 1), d_final + cc, sizeof(double), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = launch_unpack_soa(d_Y, n_desired, ndim, n_desired, d_Yaos, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(XC_dense, d_Yaos, sizeof(double) * ndim * n_desired, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = call.wait();
+    if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
+  }
+  return rc;
+}
+
 static int direct_host(lto_ctx* c, int nstate, int n_nodes, int n_batch, const double* X, const double* U, const double* t,
                        int n_tgrids, int nsteps, const lto_direct_params* prm, double* Jac_temp, double* ddefect_dtf,
                        double* defect, double* errors, bool want_jac, double* x_mid = nullptr) {
@@ -232,49 +282,19 @@ int lto_indirect_densify(lto_ctx* c, int ndim, int n_nodes, const double* XC, co
   if (!c) return LTO_ENULL;
   if (!XC || !t || !XC_dense || !t_dense) return set_err(c, LTO_ENULL, "XC, t, XC_dense or t_dense is NULL");
   if (n_desired < 2) return set_err(c, LTO_EINVAL, "n_desired must be >= 2");
-  lto::HostBuf<int> h_first;
-  HostCall call(c);
-  int rc = plan_build(c, ndim, n_nodes, 1, prm, 1, integ, &call.plan[0]);
-  if (rc) return rc;
-  lto_indirect_plan* p = call.plan[0];
-  const int S = p->S;
-  if (!h_first.alloc((size_t)S + 1)) return set_err(c, LTO_EHIP, "host allocation failed");
-  linrange(t[0], t[n_nodes - 1], n_desired, t_dense);
-  // samples of segment i: t_dense in [t_i, t_{i+1}); the last grid point (== t_n) is served by the final state
-  segment_samples(t, n_nodes, t_dense, n_desired, h_first.data(), 0);
-  h_first[S] = n_desired - 1;
-  const long J = n_nodes;
-  double *d_aos, *d_X, *d_t, *d_td, *d_Y, *d_Yaos;
-  int* d_first;
-  ArenaLayout scratch;
-  scratch.add((size_t)ndim * J, d_aos, d_X);
-  scratch.add((size_t)n_nodes, d_t);
-  scratch.add((size_t)S + 1, d_first);
-  scratch.add((size_t)n_desired, d_td);
-  scratch.add((size_t)ndim * n_desired, d_Y, d_Yaos);
-  rc = scratch.reserve(c);
-  if (rc) return rc;
-  hipStream_t st = c->stream;
-  hipError_t e = hipMemcpyAsync(d_aos, XC, sizeof(double) * ndim * J, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(double) * n_nodes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_first, h_first.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_td, t_dense, sizeof(double) * n_desired, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_pack_soa(d_aos, ndim, J, d_X, J, st);
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "stage in", e);
-  // the final state lands in the last column of Y: final_state[c * n_batch + traj] with ld = n_desired, offset n_desired-1
-  // is not expressible through the [ND][n_batch] layout, so take it into the tail of d_Yaos and splice on the host side
-  double* d_final = d_Yaos;   // [ndim] (n_batch = 1); overwritten by the unpack afterwards, so copy it out first
-  rc = lto_indirect_dense_dev(p, st, d_X, J, d_t, 1, d_first, d_td, d_Y, n_desired, d_final);
-  if (rc == LTO_OK) {
-    // splice: Y[c][n_desired-1] = final[c]
-    for (int cc = 0; cc < ndim && e == hipSuccess; ++cc)
-      e = hipMemcpyAsync(d_Y + (size_t)cc * n_desired + (n_desired - 1), d_final + cc, sizeof(double), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = launch_unpack_soa(d_Y, n_desired, ndim, n_desired, d_Yaos, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(XC_dense, d_Yaos, sizeof(double) * ndim * n_desired, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = call.wait();
-    if (e != hipSuccess) rc = set_err(c, LTO_EHIP, "stage out", e);
-  }
-  return rc;
+  return densify_host(c, false, ndim, n_nodes, XC, t, prm, integ, n_desired, XC_dense, t_dense);
+}
+
+/* densify for one trajectory of the variable-mass system: XC [14 x n_nodes], Isp in prm->mass; XC_dense
+ * [14 x n_desired].  The contract of lto_indirect_densify otherwise. */
+int lto_indirect_densify_mass(lto_ctx* c, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                              const lto_integrator* integ, int n_desired, double* XC_dense, double* t_dense) {
+  if (!c) return LTO_ENULL;
+  if (!XC || !t || !prm || !integ || !XC_dense || !t_dense) return set_err(c, LTO_ENULL, "lto_indirect_densify_mass: a required argument is NULL");
+  if (integ->method != LTO_RK4 && integ->method != LTO_DOP853_ADAPTIVE)
+    return set_err(c, LTO_EUNSUPPORTED, "lto_indirect_densify_mass: dense output is built for LTO_RK4 and LTO_DOP853_ADAPTIVE");
+  if (n_desired < 2 || n_nodes < 2) return set_err(c, LTO_EINVAL, "lto_indirect_densify_mass: need n_nodes >= 2 and n_desired >= 2");
+  return densify_host(c, true, 14, n_nodes, XC, t, prm, integ, n_desired, XC_dense, t_dense);
 }
 
 /* One Newton iteration of multiShoot_CRTBP_indirect on the device (indirect.jl:290-296; both settings of flag_adjointsOnly):

@@ -580,8 +580,10 @@ int lto_indirect_newton_solve_dev(lto_indirect_plan* p, void* stream, const doub
 }
 
 /* ------------------------------------------------------------------------------ dense output */
-int lto_indirect_dense_dev(lto_indirect_plan* p, void* stream, const double* X, long ldx, const double* t, int n_tgrids,
-                           const int* first, const double* t_samples, double* Y, long ldy, double* final_state) {
+// One body for both entries; `rows` is the row count the entry is declared for (12: lto_indirect_dense_dev, 14:
+// lto_indirect_dense_mass_dev).  A plan of another row count is refused before anything is launched.
+static int dense_dev_rows(int rows, lto_indirect_plan* p, void* stream, const double* X, long ldx, const double* t, int n_tgrids,
+                          const int* first, const double* t_samples, double* Y, long ldy, double* final_state) {
   if (!p) return LTO_ENULL;
   lto_ctx* c = p->ctx;
   IndirectArgs a;
@@ -590,8 +592,10 @@ int lto_indirect_dense_dev(lto_indirect_plan* p, void* stream, const double* X, 
   if (!first || !t_samples || !Y) return set_err(c, LTO_ENULL, "first, t_samples or Y is NULL");
   // dense output is built for what densify needs (HelperFunctions.jl:51-101 re-propagates with the solver of the sweep: the 12-dim
   // system, DOP853 for Vern8) and for the contract's RK4; round 6 removed the 24 other instantiations, which nothing ran
-  if (p->ndim != 12 || (p->integ.method != LTO_RK4 && p->integ.method != LTO_DOP853_ADAPTIVE))
-    return set_err(c, LTO_EUNSUPPORTED, "dense output is built for ndim = 12 with LTO_RK4 or LTO_DOP853_ADAPTIVE");
+  // (DESIGN 4.20 brought the 14-row RK4 / DOP853 forms back, behind an entry of their own)
+  if (p->ndim != rows || (p->integ.method != LTO_RK4 && p->integ.method != LTO_DOP853_ADAPTIVE))
+    return set_err(c, LTO_EUNSUPPORTED, rows == 12 ? "dense output is built for ndim = 12 with LTO_RK4 or LTO_DOP853_ADAPTIVE"
+                                                   : "lto_indirect_dense_mass_dev takes a 14-row plan with LTO_RK4 or LTO_DOP853_ADAPTIVE");
   rc = bind_device(c);
   if (rc) return rc;
   DenseArgs d;
@@ -603,6 +607,16 @@ int lto_indirect_dense_dev(lto_indirect_plan* p, void* stream, const double* X, 
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_indirect_dense", e);
   p->swept = 1;
   return LTO_OK;
+}
+
+int lto_indirect_dense_dev(lto_indirect_plan* p, void* stream, const double* X, long ldx, const double* t, int n_tgrids,
+                           const int* first, const double* t_samples, double* Y, long ldy, double* final_state) {
+  return dense_dev_rows(12, p, stream, X, ldx, t, n_tgrids, first, t_samples, Y, ldy, final_state);
+}
+
+int lto_indirect_dense_mass_dev(lto_indirect_plan* p, void* stream, const double* X, long ldx, const double* t, int n_tgrids,
+                                const int* first, const double* t_samples, double* Y, long ldy, double* final_state) {
+  return dense_dev_rows(14, p, stream, X, ldx, t, n_tgrids, first, t_samples, Y, ldy, final_state);
 }
 
 /* AUTO's cost table measured on this device: one full round of every RK4 STM family and dimension (16 / 48 / 64 x CUs segments,

@@ -1,6 +1,7 @@
 // lto_indirect_solve.hip -- the batched indirect Newton loop and what starts it from a new grid: addTimeFinal and mesh
 // equidistribution.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 #include "lto_host.hpp"
@@ -347,48 +348,55 @@ int lto_indirect_add_time(lto_ctx* c, int ndim, int n_nodes, const double* XC, c
                                      XC_guess, XC_out, t_out, tau_out, defect, status_flag, iterations, history, cost);
 }
 
-/* Mesh equidistribution of converged 12-dim solutions, every phase on the device: per pass the monitor (the caller's
+}  // extern "C"
+
+/* Mesh equidistribution of converged solutions of nd = 12 or 14 rows (`who` names the entry in the error texts),
+ * every phase on the device: per pass the monitor (the caller's
  * weights, or the trial-step counts of a one-lane defect sweep of the current trajectories), the new grids (k_remesh_grid) and the
  * current trajectories' own states on them (k_remesh_nodes); then, if XC_out is set, the Newton loop of lto_indirect_solve_batch
  * started from the last pass's nodes in HBM.  Between the upload of XC, t and weights and the download of the results only the new
  * grids (once per pass: the host checks them, and the solve loop takes its grids from the host) and the step counts come down. */
-int lto_indirect_remesh_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
-                              const lto_params* prm, int n_prm, const lto_integrator* integ, int n_new, const double* weights,
-                              int passes, int flag_adjointsOnly, int maxIter, double* t_out, double* XC_guess, double* XC_out,
-                              double* defect, int* status_flag, int* iterations, double* history, int* steps_before,
-                              int* steps_after) {
+static int remesh_rows(const int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC, const double* t,
+                       int n_tgrids, const lto_params* prm, int n_prm, const lto_integrator* integ, int n_new, const double* weights,
+                       int passes, int flag_adjointsOnly, int maxIter, double* t_out, double* XC_guess, double* XC_out,
+                       double* defect, int* status_flag, int* iterations, double* history, int* steps_before, int* steps_after) {
   if (!c) return LTO_ENULL;
+  const auto fail = [&](int code, const char* what, hipError_t q = hipSuccess) {
+    char text[384];
+    std::snprintf(text, sizeof text, "%s: %s", who, what);
+    return set_err(c, code, text, q);
+  };
   if (!XC || !t || !prm || !integ || !t_out || (XC_out && !status_flag))
-    return set_err(c, LTO_ENULL, "lto_indirect_remesh_batch: a required argument is NULL");
-  if (ndim != 12) return set_err(c, LTO_EUNSUPPORTED, "lto_indirect_remesh_batch: ndim must be 12 (dense output)");
+    return fail(LTO_ENULL, "a required argument is NULL");
+  if (ndim != nd) return fail(LTO_EUNSUPPORTED, "ndim must be 12 (dense output)");
   if (integ->method != LTO_RK4 && integ->method != LTO_DOP853_ADAPTIVE)
-    return set_err(c, LTO_EUNSUPPORTED, "lto_indirect_remesh_batch: dense output is built for LTO_RK4 and LTO_DOP853_ADAPTIVE");
+    return fail(LTO_EUNSUPPORTED, "dense output is built for LTO_RK4 and LTO_DOP853_ADAPTIVE");
   const bool adaptive = integ->method == LTO_DOP853_ADAPTIVE;
   if (n_batch < 1 || n_nodes < 2 || n_new < 2 || maxIter < 0 || passes < 1)
-    return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: need n_batch >= 1, n_nodes >= 2, n_new >= 2, maxIter >= 0, passes >= 1");
+    return fail(LTO_EINVAL, "need n_batch >= 1, n_nodes >= 2, n_new >= 2, maxIter >= 0, passes >= 1");
   if ((n_tgrids != 1 && n_tgrids != n_batch) || (n_prm != 1 && n_prm != n_batch))
-    return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: n_tgrids / n_prm must be 1 or n_batch");
-  if (!weights && !adaptive) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: a fixed-step integrator has no step counts: pass weights");
-  if (weights && passes > 1) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: passes > 1 needs the step counts as the monitor (weights == NULL)");
+    return fail(LTO_EINVAL, "n_tgrids / n_prm must be 1 or n_batch");
+  if (!weights && !adaptive) return fail(LTO_EINVAL, "a fixed-step integrator has no step counts: pass weights");
+  if (weights && passes > 1) return fail(LTO_EINVAL, "passes > 1 needs the step counts as the monitor (weights == NULL)");
   const int B = n_batch, n0 = n_nodes, nn = n_new, nmax = n0 > nn ? n0 : nn;
-  if (nmax - 1 > kRemeshMaxSegs) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: more than 262144 segments per trajectory");
-  if ((long)B * nmax * 12 > 0x7fffffffL) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: batch too large");
+  if (nmax - 1 > kRemeshMaxSegs) return fail(LTO_EINVAL, "more than 262144 segments per trajectory");
+  if ((long)B * nmax * nd > 0x7fffffffL) return fail(LTO_EINVAL, "batch too large");
   const auto increasing = [](const double* g, int n, int count) {
     for (int b = 0; b < count; ++b)
       for (int i = 0; i + 1 < n; ++i)
         if (!(g[(size_t)b * n + i] < g[(size_t)b * n + i + 1]) || !std::isfinite(g[(size_t)b * n + i + 1] - g[(size_t)b * n + i])) return false;
     return true;
   };
-  if (!increasing(t, n0, n_tgrids)) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: t must be finite and strictly increasing");
+  if (!increasing(t, n0, n_tgrids)) return fail(LTO_EINVAL, "t must be finite and strictly increasing");
   const long J0 = (long)B * n0, Jn = (long)B * nn, S0 = J0 - B, Sn = Jn - B, Smax = (long)B * (nmax - 1);
   if (weights)
     for (long i = 0; i < S0; ++i)
-      if (!(weights[i] > 0.0) || !std::isfinite(weights[i])) return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: every weight must be finite and > 0");
+      if (!(weights[i] > 0.0) || !std::isfinite(weights[i])) return fail(LTO_EINVAL, "every weight must be finite and > 0");
   int rc = bind_device(c);
   if (rc) return rc;
   CallTimer call_timer(c);
   lto::HostBuf<int> h_cnt((size_t)2 * Smax);                // step counters on their way out (the stream copies into it)
-  if (!h_cnt.ok()) return set_err(c, LTO_ENOMEM, "lto_indirect_remesh_batch: out of host memory");
+  if (!h_cnt.ok()) return fail(LTO_ENOMEM, "out of host memory");
   // device side: one block of the call's own (the solve loop below lays the arena out afresh); the second of a pair, the final
   // trajectories, the weights, the defect and the monitor's scratch only where they are used
   const long Jmax = J0 > Jn ? J0 : Jn;
@@ -397,27 +405,27 @@ int lto_indirect_remesh_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, co
   double *d_xa, *d_x0, *d_g[2], *d_xf, *d_t0, *d_tn[2], *d_w, *d_def, *d_c;
   int* d_seg;
   ArenaLayout scratch;
-  scratch.add((size_t)12 * Jmax, d_xa);
-  scratch.add((size_t)12 * J0, d_x0);
-  scratch.add((size_t)12 * Jn, d_g[0]);
-  scratch.add(passes > 1 ? (size_t)12 * Jn : 0, d_g[1]);
-  scratch.add(want_final ? (size_t)12 * Jn : 0, d_xf);
+  scratch.add((size_t)nd * Jmax, d_xa);
+  scratch.add((size_t)nd * J0, d_x0);
+  scratch.add((size_t)nd * Jn, d_g[0]);
+  scratch.add(passes > 1 ? (size_t)nd * Jn : 0, d_g[1]);
+  scratch.add(want_final ? (size_t)nd * Jn : 0, d_xf);
   scratch.add((size_t)n0 * n_tgrids, d_t0);
   scratch.add((size_t)Jn, d_tn[0]);
   scratch.add(passes > 1 ? (size_t)Jn : 0, d_tn[1]);
   scratch.add((size_t)Jn, d_seg);
   scratch.add(weights ? (size_t)S0 : 0, d_w);
-  scratch.add(adaptive ? (size_t)12 * Smax : 0, d_def);
+  scratch.add(adaptive ? (size_t)nd * Smax : 0, d_def);
   scratch.add(c_stride * B, d_c);
   HostCall call(c);
   hipStream_t st = c->stream;
-  rc = scratch.reserve_block(c, call.block[0], "lto_indirect_remesh_batch");
+  rc = scratch.reserve_block(c, call.block[0], who);
   if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(d_xa, XC, sizeof(double) * 12 * J0, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(d_xa, XC, sizeof(double) * nd * J0, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_t0, t, sizeof(double) * n0 * n_tgrids, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && weights) e = hipMemcpyAsync(d_w, weights, sizeof(double) * S0, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_pack_soa(d_xa, 12, J0, d_x0, J0, st);
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: stage in", e);
+  if (e == hipSuccess) e = launch_pack_soa(d_xa, nd, J0, d_x0, J0, st);
+  if (e != hipSuccess) return fail(LTO_EHIP, "stage in", e);
   // trial steps of a defect sweep of X on tg, one lane per segment whatever the batch size (a batch's counts are its singles'):
   // left in the plan's counters; host_out (if set) = accepted + rejected once the stream has been waited for
   int* pending_out = nullptr;
@@ -428,7 +436,7 @@ int lto_indirect_remesh_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, co
     if (r || !host_out) return r;
     hipError_t q = hipMemcpyAsync(h_cnt.data(), p->d_nacc, sizeof(int) * (size_t)p->S, hipMemcpyDeviceToHost, st);
     if (q == hipSuccess) q = hipMemcpyAsync(h_cnt.data() + p->S, p->d_nrej, sizeof(int) * (size_t)p->S, hipMemcpyDeviceToHost, st);
-    if (q != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: step counters", q);
+    if (q != hipSuccess) return fail(LTO_EHIP, "step counters", q);
     pending_out = host_out; pending_S = p->S;
     return LTO_OK;
   };
@@ -442,7 +450,7 @@ int lto_indirect_remesh_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, co
   int nc = n0, ntgc = n_tgrids;
   for (int pass = 0; pass < passes; ++pass) {
     call.idle = false;
-    rc = plan_build(c, 12, nc, B, prm, n_prm, integ, &call.plan[0]);
+    rc = plan_build(c, nd, nc, B, prm, n_prm, integ, &call.plan[0]);
     if (rc) return rc;
     lto_indirect_plan* p = call.plan[0];
     const bool swept = adaptive && (!weights || (pass == 0 && steps_before));
@@ -460,27 +468,27 @@ int lto_indirect_remesh_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, co
     if (rc) return rc;
     RemeshNodeArgs na;
     na.tn = d_tn[pass & 1]; na.seg_of = d_seg; na.G = d_g[pass & 1]; na.ldg = Jn; na.n_new = nn; na.n_batch = B;
-    e = launch_remesh_nodes(p->pm, p->integ.method, a, na, st);
+    e = launch_remesh_nodes(nd, p->pm, p->integ.method, a, na, st);
     if (e == hipSuccess) e = hipMemcpyAsync(t_out, d_tn[pass & 1], sizeof(double) * Jn, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = call.wait();
-    if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: re-mesh", e);
+    if (e != hipSuccess) return fail(LTO_EHIP, "re-mesh", e);
     counts_land();
     plan_free(p);                                            // (the stream is idle)
     call.plan[0] = nullptr;
     if (!increasing(t_out, nn, B))
-      return set_err(c, LTO_EINVAL, "lto_indirect_remesh_batch: the new grid is not strictly increasing (n_new beyond the grid's resolution, or a NaN trajectory)");
+      return fail(LTO_EINVAL, "the new grid is not strictly increasing (n_new beyond the grid's resolution, or a NaN trajectory)");
     d_xc = d_g[pass & 1]; d_tc = d_tn[pass & 1]; Jc = Jn; nc = nn; ntgc = B;
   }
   if (steps_before && !adaptive) for (long i = 0; i < S0; ++i) steps_before[i] = integ->steps;
   if (XC_guess) {
     call.idle = false;
-    e = launch_unpack_soa(d_xc, Jn, 12, Jn, d_xa, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(XC_guess, d_xa, sizeof(double) * 12 * Jn, hipMemcpyDeviceToHost, st);
+    e = launch_unpack_soa(d_xc, Jn, nd, Jn, d_xa, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(XC_guess, d_xa, sizeof(double) * nd * Jn, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = call.wait();
-    if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: guess", e);
+    if (e != hipSuccess) return fail(LTO_EHIP, "guess", e);
   }
   if (XC_out) {
-    rc = indirect_solve_impl(c, 12, nn, B, nullptr, d_xc, t_out, B, prm, n_prm, integ, flag_adjointsOnly, maxIter, XC_out,
+    rc = indirect_solve_impl(c, nd, nn, B, nullptr, d_xc, t_out, B, prm, n_prm, integ, flag_adjointsOnly, maxIter, XC_out,
                              want_final ? d_xf : nullptr, defect, status_flag, iterations, history);
     if (rc) return rc;
   }
@@ -490,13 +498,45 @@ int lto_indirect_remesh_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, co
     return LTO_OK;
   }
   call.idle = false;
-  rc = plan_build(c, 12, nn, B, prm, n_prm, integ, &call.plan[0]);
+  rc = plan_build(c, nd, nn, B, prm, n_prm, integ, &call.plan[0]);
   if (rc == LTO_OK) rc = count_sweep(call.plan[0], XC_out ? d_xf : d_xc, Jn, d_tc, B, steps_after);
   if (rc) return rc;
   e = call.wait();
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_remesh_batch: step counters", e);
+  if (e != hipSuccess) return fail(LTO_EHIP, "step counters", e);
   counts_land();
   return LTO_OK;
+}
+
+extern "C" {
+
+int lto_indirect_remesh_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                              const lto_params* prm, int n_prm, const lto_integrator* integ, int n_new, const double* weights,
+                              int passes, int flag_adjointsOnly, int maxIter, double* t_out, double* XC_guess, double* XC_out,
+                              double* defect, int* status_flag, int* iterations, double* history, int* steps_before,
+                              int* steps_after) {
+  return remesh_rows(12, "lto_indirect_remesh_batch", c, ndim, n_nodes, n_batch, XC, t, n_tgrids, prm, n_prm, integ, n_new, weights, passes,
+                     flag_adjointsOnly, maxIter, t_out, XC_guess, XC_out, defect, status_flag, iterations, history, steps_before,
+                     steps_after);
+}
+
+/* The same for the 14-row variable-mass system: the re-solve is the 14-row loop (m0 pinned, final mass free, mass
+ * costate of the last node 0). */
+int lto_indirect_remesh_mass_batch(lto_ctx* c, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                                   const lto_params* prm, int n_prm, const lto_integrator* integ, int n_new, const double* weights,
+                                   int passes, int flag_adjointsOnly, int maxIter, double* t_out, double* XC_guess, double* XC_out,
+                                   double* defect, int* status_flag, int* iterations, double* history, int* steps_before,
+                                   int* steps_after) {
+  return remesh_rows(14, "lto_indirect_remesh_mass_batch", c, 14, n_nodes, n_batch, XC, t, n_tgrids, prm, n_prm, integ, n_new, weights,
+                     passes, flag_adjointsOnly, maxIter, t_out, XC_guess, XC_out, defect, status_flag, iterations, history,
+                     steps_before, steps_after);
+}
+
+int lto_indirect_remesh_mass(lto_ctx* c, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                             const lto_integrator* integ, int n_new, const double* weights, int passes, int flag_adjointsOnly,
+                             int maxIter, double* t_out, double* XC_guess, double* XC_out, double* defect, int* status_flag,
+                             int* iterations, double* history, int* steps_before, int* steps_after) {
+  return lto_indirect_remesh_mass_batch(c, n_nodes, 1, XC, t, 1, prm, 1, integ, n_new, weights, passes, flag_adjointsOnly, maxIter, t_out,
+                                        XC_guess, XC_out, defect, status_flag, iterations, history, steps_before, steps_after);
 }
 
 int lto_indirect_remesh(lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,

@@ -1110,6 +1110,34 @@ def meshRefine_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass, thrustLimit, p,
     return XC_all, t_TU, int(n_nodes)
 
 
+def meshRefine_indirect_mass(XC_all, t_TU, MU, DU, TU, n_nodes, Isp, thrustLimit, p, rho, n_new=None, passes=2, weights=None,
+                             maxIter=10, flag_adjointsOnly=False, integ=None, ctx=None, verbose=True):
+    """meshRefine_indirect for a converged solution of the 14-row variable-mass system: the nodes are moved onto the
+    equidistributed grid along the solution's own piecewise trajectory, mass included, and the 14-row loop of
+    multiShoot_CRTBP_indirect_mass re-solves there (r0, v0, m0 and rf, vf fixed, final mass free).  One library call
+    (lto_indirect_remesh_mass_batch).  Returns (XC_new, t_new, n_new) on status 0, otherwise the original (XC_all, t_TU, n_nodes)
+    unchanged."""
+    XC_all = np.array(XC_all, dtype=np.float64, order="F")
+    t_TU = np.array(t_TU, dtype=np.float64)
+    if XC_all.shape != (14, int(n_nodes)):
+        raise ValueError("meshRefine_indirect_mass takes the 14-row solution [14 x n_nodes]; got shape %s" % (XC_all.shape,))
+    if t_TU.shape != (int(n_nodes),):
+        raise ValueError("meshRefine_indirect_mass takes one time per node; got shape %s" % (t_TU.shape,))
+    if not (Isp > 0):
+        raise ValueError("Isp must be positive; got %r" % (Isp,))
+    n_new = int(n_nodes) if n_new is None else int(n_new)
+    params = hotpath.make_params(MU, DU, TU, thrustLimit, Isp, 1.0, p, rho)
+    r = hotpath.indirect_remesh_mass(XC_all, t_TU, params, n_new=n_new, weights=weights, passes=passes, integ=integ,
+                                     flag_adjointsOnly=flag_adjointsOnly, maxIter=maxIter, ctx=ctx)
+    if verbose:
+        print("meshRefine_indirect_mass: %d -> %d nodes, max trial steps %d -> %d (mean %.2f -> %.2f), status %d after %d iterations"
+              % (n_nodes, n_new, r.steps_before.max(), r.steps_after.max(), r.steps_before.mean(), r.steps_after.mean(), r.status,
+                 r.iterations))
+    if r.status == 0:
+        return r.XC_out.copy(), r.t_out.copy(), n_new
+    return XC_all, t_TU, int(n_nodes)
+
+
 def meshRefine_direct(X_all, u_all, t_TU, nstate, n_nodes, nsteps, Isp, MU, DU, TU, tol_min=1e-20, tol_max=1e-18,
                       max_nodes=1 << 20, batched=True, ops=None, verbose=True, device=False):
     """Errors-driven mesh refinement of the direct transcription (direct.jl:597-680): nodes are removed while the

@@ -547,7 +547,8 @@ def indirect_solve_batch(XC_all, t_TU, params, integ=None, flag_adjointsOnly=Fal
 
 def densify(XC_all, t_TU, params, n_desired, integ=None, ctx=None):
     """densify (src/HelperFunctions.jl:51-101): (XC_dense[ndim x n_desired], t_dense[n_desired]); every segment is
-    re-propagated on the GPU and sampled at the uniformly spaced t_dense points that fall inside it."""
+    re-propagated on the GPU and sampled at the uniformly spaced t_dense points that fall inside it.  This is the 12-row entry:
+    14-row input (the variable-mass system) is refused here with LtoError -3 and goes to densify_mass."""
     ctx = ctx or default_context()
     integ = integ or integrator()
     XC = _f64(XC_all)
@@ -558,6 +559,27 @@ def densify(XC_all, t_TU, params, n_desired, integ=None, ctx=None):
     t_dense = np.zeros(int(n_desired))
     ctx.check(ctx.fn("indirect_densify")(ctx.handle, ndim, n, _ptr(XC), _ptr(t), prm, C.byref(integ), int(n_desired),
                                            _ptr(XC_dense), _ptr(t_dense)))
+    return XC_dense, t_dense
+
+
+def densify_mass(XC_all, t_TU, params, n_desired, integ=None, ctx=None):
+    """densify for one solution of the 14-row variable-mass system (lto_indirect_densify_mass): XC_all [14 x n],
+    params with Isp in the mass slot; (XC_dense [14 x n_desired], t_dense [n_desired]), row 6 the propagated mass.  LTO_RK4 or
+    LTO_DOP853_ADAPTIVE."""
+    XC = _f64(XC_all)
+    if XC.ndim != 2 or XC.shape[0] != 14:
+        raise ValueError("XC_all must be [14 x n]")
+    t = _f64(t_TU)
+    n = XC.shape[1]
+    if t.shape != (n,):
+        raise ValueError("t_TU must hold one time per node")
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    prm, _ = _params_array(params)
+    XC_dense = np.zeros((14, int(n_desired)), order="F")
+    t_dense = np.zeros(int(n_desired))
+    ctx.check(ctx.fn("indirect_densify_mass")(ctx.handle, n, _ptr(XC), _ptr(t), prm, C.byref(integ), int(n_desired),
+                                                _ptr(XC_dense), _ptr(t_dense)))
     return XC_dense, t_dense
 
 
@@ -1131,34 +1153,29 @@ def indirect_add_time(XC, t, params, Xf_times, Xf_states, dts, n_desired=200, in
 Remesh = collections.namedtuple("Remesh", "XC_guess XC_out t_out defect status iterations history steps_before steps_after")
 
 
-def indirect_remesh(XC, t, params, n_new=None, weights=None, passes=2, integ=None, flag_adjointsOnly=False, maxIter=10, ctx=None,
-                    solve=True):
-    """Mesh re-distribution of converged 12-dim solutions (lto_indirect_remesh_batch, DESIGN 4.13): XC [12 x n] or [12 x n x B] on
-    t [n] or [n x B] is put on n_new nodes (default n) placed so that every new segment carries the same share of a per-segment
-    monitor -- weights [(n-1)] / [(n-1) x B] (then passes must be 1), or, with weights = None, the trial-step counts of a defect
-    sweep with integ (adaptive integrators only), `passes` times over.  The new nodes lie on the input's own piecewise trajectory
-    (XC_guess); with solve = True the Newton loop of indirect_solve_batch then runs on the new grids.  Returns Remesh(XC_guess
-    [12 x n_new x B], XC_out, t_out [n_new x B], defect [12 x (n_new-1) x B], status [B], iterations [B], history, steps_before
-    [(n-1) x B], steps_after [(n_new-1) x B]); a single trajectory comes back without the batch axis, the solve's fields are None
-    when solve = False."""
+def _indirect_remesh(entry, rows, XC, t, params, n_new, weights, passes, integ, flag_adjointsOnly, maxIter, ctx, solve):
+    """indirect_remesh / indirect_remesh_mass: one body, `entry` the library call and `rows` its row count (None: the 12-row entry,
+    which takes ndim as an argument and decides itself)."""
     X = _f64(XC)
+    if rows is not None and (X.ndim not in (2, 3) or X.shape[0] != rows):
+        raise ValueError("XC must be [%d x n] or [%d x n x B]" % (rows, rows))
     ndim, n, B, batched = _batch_dims(X)
     tt, ntg = _tgrids(t, n, B)
     n_new = n if n_new is None else int(n_new)
     passes = int(passes)
     if n_new < 2:
-        raise LtoError(-1, "indirect_remesh: n_new must be >= 2")
+        raise LtoError(-1, "%s: n_new must be >= 2" % entry)
     if passes < 1:
-        raise LtoError(-1, "indirect_remesh: passes must be >= 1")
+        raise LtoError(-1, "%s: passes must be >= 1" % entry)
     w = None
     if weights is not None:
         if passes != 1:
-            raise LtoError(-1, "indirect_remesh: caller weights are applied once: passes must be 1")
+            raise LtoError(-1, "%s: caller weights are applied once: passes must be 1" % entry)
         w = _f64(weights)
         if w.shape != ((n - 1,) if not batched else (n - 1, B)):
             raise ValueError("weights must be [n_nodes - 1] or [(n_nodes - 1) x n_batch], one per old segment")
         if not np.all(np.isfinite(w)) or not np.all(w > 0.0):
-            raise LtoError(-1, "indirect_remesh: every weight must be finite and > 0")
+            raise LtoError(-1, "%s: every weight must be finite and > 0" % entry)
     ctx = ctx or default_context()
     integ = integ or integrator()
     prm, nprm = _params_array(params)
@@ -1173,8 +1190,9 @@ def indirect_remesh(XC, t, params, n_new=None, weights=None, passes=2, integ=Non
         status = np.zeros(B, dtype=np.int32)
         iters = np.zeros(B, dtype=np.int32)
         hist = np.full((2, max(int(maxIter), 1), B), np.nan, order="F")
-    ctx.check(ctx.fn("indirect_remesh_batch")(
-        ctx.handle, ndim, n, B, _ptr(X), _ptr(tt), ntg, prm, nprm, C.byref(integ), n_new, _ptr(w) if w is not None else None, passes,
+    ctx.check(ctx.fn(entry + "_batch")(
+        ctx.handle, *((ndim,) if rows is None else ()), n, B, _ptr(X), _ptr(tt), ntg, prm, nprm, C.byref(integ), n_new,
+        _ptr(w) if w is not None else None, passes,
         1 if flag_adjointsOnly else 0, int(maxIter), _ptr(t_out), _ptr(guess), _ptr(XC_out) if solve else None,
         _ptr(defect) if solve else None, _ptr(status) if solve else None, _ptr(iters) if solve else None,
         _ptr(hist) if solve and maxIter > 0 else None, _ptr(before), _ptr(after)))
@@ -1186,6 +1204,29 @@ def indirect_remesh(XC, t, params, n_new=None, weights=None, passes=2, integ=Non
         return Remesh(one(guess), one(XC_out), one(t_out), one(defect), None if status is None else int(status[0]),
                       None if iters is None else int(iters[0]), None if history is None else history[0], one(before), one(after))
     return Remesh(guess, XC_out, t_out, defect, status, iters, history, before, after)
+
+
+def indirect_remesh(XC, t, params, n_new=None, weights=None, passes=2, integ=None, flag_adjointsOnly=False, maxIter=10, ctx=None,
+                    solve=True):
+    """Mesh re-distribution of converged 12-dim solutions (lto_indirect_remesh_batch, DESIGN 4.13): XC [12 x n] or [12 x n x B] on
+    t [n] or [n x B] is put on n_new nodes (default n) placed so that every new segment carries the same share of a per-segment
+    monitor -- weights [(n-1)] / [(n-1) x B] (then passes must be 1), or, with weights = None, the trial-step counts of a defect
+    sweep with integ (adaptive integrators only), `passes` times over.  The new nodes lie on the input's own piecewise trajectory
+    (XC_guess); with solve = True the Newton loop of indirect_solve_batch then runs on the new grids.  Returns Remesh(XC_guess
+    [12 x n_new x B], XC_out, t_out [n_new x B], defect [12 x (n_new-1) x B], status [B], iterations [B], history, steps_before
+    [(n-1) x B], steps_after [(n_new-1) x B]); a single trajectory comes back without the batch axis, the solve's fields are None
+    when solve = False."""
+    return _indirect_remesh("indirect_remesh", None, XC, t, params, n_new, weights, passes, integ, flag_adjointsOnly, maxIter, ctx, solve)
+
+
+def indirect_remesh_mass(XC, t, params, n_new=None, weights=None, passes=2, integ=None, flag_adjointsOnly=False, maxIter=10, ctx=None,
+                         solve=True):
+    """indirect_remesh for converged solutions of the 14-row variable-mass system (lto_indirect_remesh_mass_batch):
+    XC [14 x n] or [14 x n x B], params with Isp in the mass slot.  Monitor, grid, passes and the result object are those of
+    indirect_remesh (14 rows wherever it has 12); with solve = True the 14-row Newton loop runs on the new grids: r, v and m0 of the
+    first node and r, v of the last stay fixed, the final mass is free and the last node's mass costate is 0."""
+    return _indirect_remesh("indirect_remesh_mass", 14, XC, t, params, n_new, weights, passes, integ, flag_adjointsOnly, maxIter, ctx,
+                            solve)
 
 
 def direct_qp_step_free(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, targets, models, beta, allowImpulsive=False, ctx=None):
@@ -1326,6 +1367,11 @@ class IndirectPlan:
         columns of Y [ndim][ldy]; first is int32 [S + 1]; final_state [ndim][n_batch], if given, takes every trajectory's x(t_n)."""
         self.ctx.check(self.ctx.lib.lto_indirect_dense_dev(self.handle, stream, _dptr(X), int(ldx), _dptr(t), int(n_tgrids),
                                                            _dptr(first), _dptr(t_samples), _dptr(Y), int(ldy), _dptr(final_state)))
+
+    def dense_mass(self, X, ldx, t, n_tgrids, first, t_samples, Y, ldy, final_state=None, stream=None):
+        """The same on a 14-row plan (lto_indirect_dense_mass_dev): X [14][ldx], Y [14][ldy], final_state [14 x n_batch] or None."""
+        self.ctx.check(self.ctx.lib.lto_indirect_dense_mass_dev(self.handle, stream, _dptr(X), int(ldx), _dptr(t), int(n_tgrids),
+                                                                _dptr(first), _dptr(t_samples), _dptr(Y), int(ldy), _dptr(final_state)))
 
     def events(self, X, ldx, t, n_tgrids, max_events, n_events, t_event, kind, on0, dv, burn_time, status, dv_seg=None, stream=None):
         """Thrust events on device arrays (lto_indirect_events_dev): n_events, kind, on0, status int32; t_event, kind
