@@ -378,6 +378,29 @@ int lto_indirect_add_time(lto_ctx* ctx, int ndim, int n_nodes, const double* XC,
                           const lto_integrator* integ, const lto_direct_orbits* orbits, double dt, int n_desired,
                           int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
                           double* defect, int* status_flag, int* iterations, double* history, double* cost);
+/* The same for a converged solution of the 14-row variable-mass system y = (r, v, m, lambda_r, lambda_v, lambda_m): XC
+ * [14 x n_nodes], prm with Isp in the mass slot; the arguments of lto_indirect_add_time_batch without ndim, its layouts with 14 rows,
+ * plus propellant at the end.  Per k: rows 7..13 of the last node are zeroed (on a copy) and the tail node appended at t[n-1] + dt[k].
+ * The tail is the 14-row system's own flow from that node, not a second system: with |lambda_v| = 0 the thrust acceleration is
+ * exactly zero, so position and velocity coast and rows 7..13 stay exactly 0, while the mass follows mdot = -kappa umag(0, m) m of the
+ * same right-hand side -- zero for p > 1 (the mass is constant bit for bit), the full-throttle flow for p = 0, the law's idle flow
+ * aL / (1 + e^(1 / rho)) for p = 1.  The mass row of the guess is a starting value only: the re-solve (the 14-row loop of
+ * lto_indirect_solve_batch: r, v, m of the first node and r, v of the last fixed, lambda_m of the last node 0) owns the final mass.
+ * Dense output, re-mesh (all 14 rows, the mass of the last node being the spline's end sample) and snap (rows 0..5) as above.
+ * cost [n_dt] (may be NULL): the trapezoid over the n_desired-point dense output of XC_out of the 14-row law's magnitude with the
+ * sample's own mass, aL_j = thrustLimit / 1e3 TU^2 / DU / m_j, in DU/TU; a sample whose magnitude is NaN or whose mass is not
+ * positive counts 0 (only a re-solve that did not converge leaves such a sample: read cost where status_flag is 0).  propellant [n_dt] (may be NULL; written when XC_out is set):
+ * XC[6, 0] - XC_out[6, n-1, k] in kg.  Codes as lto_indirect_add_time_batch; in addition a node mass that is not finite and
+ * positive: LTO_EINVAL. */
+int lto_indirect_add_time_mass_batch(lto_ctx* ctx, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                                     const lto_integrator* integ, const lto_direct_orbits* orbits, int n_dt, const double* dt,
+                                     int n_desired, int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out,
+                                     double* t_out, double* tau_out, double* defect, int* status_flag, int* iterations,
+                                     double* history, double* cost, double* propellant);
+int lto_indirect_add_time_mass(lto_ctx* ctx, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                               const lto_integrator* integ, const lto_direct_orbits* orbits, double dt, int n_desired,
+                               int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
+                               double* defect, int* status_flag, int* iterations, double* history, double* cost, double* propellant);
 /* Costates of n_batch direct solutions (host arrays, the layouts of lto_direct_qp_step): one Jacobian sweep, one frozen QP step
  * (flagEnd = false, tf fixed) and the costates kernel at the given point (see lto_direct_costates_dev).  At a converged
  * minimum-energy solution the step is zero and the multipliers are the discrete adjoints of the transcription.  Outputs: Lambda

@@ -16,7 +16,7 @@ using SparseArrays, LinearAlgebra, Libdl
 export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pack_soa!, unpack_soa!, defect_norms!, indirect_defect_dev!,
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
-export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
+export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
        direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
@@ -309,6 +309,56 @@ function tf_sweep(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64
     end
     check(ctx, rc)
     (XC, t, tau, Int.(status), Int.(iters), cost)
+end
+
+"""addTimeFinal for a converged solution of the 14-row variable-mass system (`lto_indirect_add_time_mass`, DESIGN 4.21): `XC_all`
+[14 x n_nodes], Isp in the mass slot of the parameters.  Rows 8:14 of the last node are zeroed on a copy; the tail of Δt TU is the
+14-row system's own flow with zero costates (the orbit coasts; the mass follows the law's flow at |λ_v| = 0: constant for p > 1,
+full throttle for p = 0, the idle flow aL / (1 + e^(1/ρ)) for p = 1); the 14-row loop re-solves with r0, v0, m0 and rf, vf fixed and
+the final mass free.  Returns (XC_new, t_new) on status 0, otherwise the original (XC_all, t_TU)."""
+function addTimeFinal_mass(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}, Δt, MU, DU, TU, n_nodes, Isp, thrustLimit,
+                           p, rho, Xf_times::Vector{Float64}, Xf_states::Matrix{Float64}; maxIter::Integer = 10,
+                           n_desired::Integer = 200, flag_adjointsOnly::Bool = false, integ::LtoIntegrator = LtoIntegrator())
+    size(XC_all) == (14, n_nodes) || throw(ArgumentError("addTimeFinal_mass takes the 14-row solution [14 x n_nodes]"))
+    XC_new = zeros(14, n_nodes); t_new = zeros(n_nodes); tau = zeros(1); defect1 = zeros(14, n_nodes - 1)
+    status = Ref{Cint}(0); iters = Ref{Cint}(0)
+    prm = Ref(LtoParams((MU, DU, TU, thrustLimit, Isp, 1.0, p, rho)))
+    rc = GC.@preserve Xf_times Xf_states begin
+        ob = Ref(LtoDirectOrbits(0, length(Xf_times), C_NULL, C_NULL, pointer(Xf_times), pointer(Xf_states)))
+        ccall((:lto_indirect_add_time_mass, liblto), Cint,
+              (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoParams}, Ref{LtoIntegrator}, Ref{LtoDirectOrbits}, Cdouble,
+               Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint},
+               Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx.handle, n_nodes, XC_all, t_TU, prm, Ref(integ), ob, Float64(Δt), n_desired, flag_adjointsOnly ? 1 : 0,
+              maxIter, C_NULL, XC_new, t_new, tau, defect1, status, iters, C_NULL, C_NULL, C_NULL)
+    end
+    check(ctx, rc)
+    status[] == 0 ? (XC_new, t_new) : (XC_all, t_TU)
+end
+
+"""addTimeFinal_mass for many Δt side by side (`lto_indirect_add_time_mass_batch`): the propellant-versus-time-of-flight curve of a
+converged variable-mass transfer.  Returns (XC [14 x n x K], t [n x K], tau [K], status [K], iterations [K], cost [K] in DU/TU,
+propellant [K] in kg = XC_all[7, 1] - XC[7, end, k])."""
+function tf_sweep_mass(ctx::LtoContext, XC_all::Matrix{Float64}, t_TU::Vector{Float64}, Δts::Vector{Float64}, MU, DU, TU, Isp,
+                       thrustLimit, p, rho, Xf_times::Vector{Float64}, Xf_states::Matrix{Float64}; maxIter::Integer = 10,
+                       n_desired::Integer = 200, flag_adjointsOnly::Bool = false, integ::LtoIntegrator = LtoIntegrator())
+    size(XC_all, 1) == 14 || throw(ArgumentError("tf_sweep_mass takes the 14-row solution [14 x n_nodes]"))
+    n_nodes = size(XC_all, 2)
+    K = length(Δts)
+    XC = zeros(14, n_nodes, K); t = zeros(n_nodes, K); tau = zeros(K); defect1 = zeros(14, n_nodes - 1, K)
+    status = zeros(Cint, K); iters = zeros(Cint, K); cost = zeros(K); propellant = zeros(K)
+    prm = Ref(LtoParams((MU, DU, TU, thrustLimit, Isp, 1.0, p, rho)))
+    rc = GC.@preserve Xf_times Xf_states begin
+        ob = Ref(LtoDirectOrbits(0, length(Xf_times), C_NULL, C_NULL, pointer(Xf_times), pointer(Xf_states)))
+        ccall((:lto_indirect_add_time_mass_batch, liblto), Cint,
+              (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoParams}, Ref{LtoIntegrator}, Ref{LtoDirectOrbits}, Cint,
+               Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint},
+               Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              ctx.handle, n_nodes, XC_all, t_TU, prm, Ref(integ), ob, K, Δts, n_desired, flag_adjointsOnly ? 1 : 0, maxIter,
+              C_NULL, XC, t, tau, defect1, status, iters, C_NULL, cost, propellant)
+    end
+    check(ctx, rc)
+    (XC, t, tau, Int.(status), Int.(iters), cost, propellant)
 end
 
 """Mesh re-distribution of a converged 12-row indirect solution (`lto_indirect_remesh`, DESIGN 4.13), the counterpart of

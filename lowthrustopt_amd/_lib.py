@@ -89,6 +89,12 @@ SIGNATURES = {
     "lto_indirect_add_time": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator),
                                         C.POINTER(LtoDirectOrbits), C.c_double, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _vp, _vp, _vp]),
+    "lto_indirect_add_time_mass_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator),
+                                                   C.POINTER(LtoDirectOrbits), C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_indirect_add_time_mass": (C.c_int, [_vp, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator),
+                                             C.POINTER(LtoDirectOrbits), C.c_double, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_stack_guess_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.POINTER(LtoDirectOrbits), C.POINTER(LtoIntegrator), _vp,
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_indirect_remesh_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.POINTER(LtoParams), C.c_int,

@@ -241,9 +241,10 @@ struct EndOrbitsDev { int n[2]; const double* t[2]; const double* Y[2]; const do
 // per trajectory b: s[b * s_stride + 0..11] = (s0; sf) at tau[2b], tau[2b+1], model[b][14] = (g0; gf; |c0|; |cf|)
 hipError_t launch_end_states(const EndOrbitsDev& o, const double* tau, int n_batch, double* s, int s_stride, double* model,
                              hipStream_t st);
-// addTimeFinal on the device (kernels_addtime.hip).  Re-mesh: K trajectories of m dense samples each, Y [12][ldy]
+// addTimeFinal on the device (kernels_addtime.hip).  Re-mesh: K trajectories of m dense samples each, Y [rows][ldy]
 // with trajectory b's samples in columns b*m .. b*m+m-1 at times td[b*m + j]; the natural spline of every row evaluated at the new
-// nodes tn[b*n + k] into G [12][ldg] (node b*n + k).  cp [m]: the Thomas factors of the (1, 4, 1) moment system; mom [m][12 K]: scratch.
+// nodes tn[b*n + k] into G [rows][ldg] (node b*n + k).  cp [m]: the Thomas factors of the (1, 4, 1) moment system; mom [m][rows K]:
+// scratch.  rows = 12, or 14 for the variable-mass system.
 struct RemeshArgs {
   const double* Y; long ldy;
   const double* td;
@@ -253,12 +254,15 @@ struct RemeshArgs {
   double* G; long ldg;
   int m, n, K;
 };
-hipError_t launch_remesh_spline(const RemeshArgs& r, hipStream_t st);
+hipError_t launch_remesh_spline(int rows, const RemeshArgs& r, hipStream_t st);
 // find_tau: node n-1 of each of the K trajectories in G snapped onto the arrival table (o, e = 1); tau [K] = tau*
 hipError_t launch_find_tau(const EndOrbitsDev& o, double* G, long ldg, int n, int K, double* tau, hipStream_t st);
 // cost [K]: trapezoid over td of umag(|lambda_v|) along the dense outputs Y (layout as RemeshArgs), p / rho / aL of the control law
 hipError_t launch_dense_cost(const double* Y, long ldy, const double* td, int m, int K, double aL, double p, double rho, double* cost,
                              hipStream_t st);
+// the same along 14-row dense outputs Y [14][ldy]: lambda_v in rows 10..12, aL = cT / (row 6) per sample, cT = thrustLimit / 1e3 TU^2 / DU
+hipError_t launch_dense_cost_mass(const double* Y, long ldy, const double* td, int m, int K, double cT, double p, double rho,
+                                  double* cost, hipStream_t st);
 // Stacked initial guesses (kernels_stack.hip), B starts side by side.  The device keeps everything per start as
 // struct-of-arrays over the starts -- element (row, b) of an [R][B] array at row * B + b -- so a wavefront's 64 starts move lines.
 constexpr int kStackCand = 1001;             // find_tau's candidates j / 1000

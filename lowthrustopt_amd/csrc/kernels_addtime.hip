@@ -7,15 +7,17 @@
 
 namespace lto {
 
-// ---- re-mesh: natural cubic spline through each of the 12 x K sample rows, evaluated at the n new nodes.
+// ---- re-mesh: natural cubic spline through each of the ROWS x K sample rows (12: state and costate; 14: the variable-mass system,
+// DESIGN 4.21 -- the mass and its costate are rows like any other), evaluated at the n new nodes.
 // Lane = (component, trajectory) pair, pair = c * K + b.  The knots of a trajectory are LinRange(t0, t_end, m): uniform, so the
 // moment system M_{i-1} + 4 M_i + M_{i+1} = 6 / h^2 (y_{i+1} - 2 y_i + y_{i-1}), M_0 = M_{m-1} = 0, has constant coefficients and
 // its Thomas factors cp[] are the same for every lane (computed on the host).  The forward sweep keeps d' in mom[j * P + pair]
 // (coalesced over the lanes), the backward sweep turns it into the moments in place, then the lane evaluates its row at the new
 // nodes with the knots' own spacing -- the form of drivers._natural_spline.  Nodes 0 and n-1 coincide with knots 0 and m-1: the
 // sample itself is returned there, bit for bit.
+template <int ROWS>
 __global__ __launch_bounds__(64) void k_remesh_spline(const RemeshArgs r) {
-  const int P = 12 * r.K;
+  const int P = ROWS * r.K;
   const int pair = blockIdx.x * 64 + threadIdx.x;
   if (pair >= P) return;
   const int c = pair / r.K, b = pair - c * r.K;
@@ -57,8 +59,10 @@ __global__ __launch_bounds__(64) void k_remesh_spline(const RemeshArgs r) {
   }
 }
 
-hipError_t launch_remesh_spline(const RemeshArgs& r, hipStream_t st) {
-  hipLaunchKernelGGL(k_remesh_spline, dim3((12 * r.K + 63) / 64), dim3(64), 0, st, r);
+hipError_t launch_remesh_spline(int rows, const RemeshArgs& r, hipStream_t st) {
+  if (rows == 12) hipLaunchKernelGGL(k_remesh_spline<12>, dim3((12 * r.K + 63) / 64), dim3(64), 0, st, r);
+  else if (rows == 14) hipLaunchKernelGGL(k_remesh_spline<14>, dim3((14 * r.K + 63) / 64), dim3(64), 0, st, r);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
@@ -144,6 +148,38 @@ __global__ __launch_bounds__(64) void k_dense_cost(const double* Y, long ldy, co
 hipError_t launch_dense_cost(const double* Y, long ldy, const double* td, int m, int K, double aL, double p, double rho, double* cost,
                              hipStream_t st) {
   hipLaunchKernelGGL(k_dense_cost, dim3((K + 63) / 64), dim3(64), 0, st, Y, ldy, td, m, K, aL, p, rho, cost);
+  return hipGetLastError();
+}
+
+// ---- the same for the 14-row variable-mass system: lambda_v is rows 10..12, and the acceleration limit is the
+// sample's own, aL_j = cT / m_j with m_j row 6 and cT = thrustLimit / 1e3 TU^2 / DU.  The expression forms are k_dense_cost's.
+// A sample whose mass is not positive (a re-solve that did not converge can leave one) counts 0, as a NaN does.
+__global__ __launch_bounds__(64) void k_dense_cost_mass(const double* Y, long ldy, const double* td, int m, int K, double cT, double p,
+                                                        double rho, double* cost) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= K) return;
+  const long o = (long)b * m;
+  double acc = 0.0, uprev = 0.0, tprev = 0.0;
+  for (int j = 0; j < m; ++j) {
+    const double lx = Y[10 * ldy + o + j], ly = Y[11 * ldy + o + j], lz = Y[12 * ldy + o + j];
+    const double nv = sqrt(lx * lx + ly * ly + lz * lz);
+    const double ms = Y[6 * ldy + o + j];
+    const double aL = cT / ms;
+    double u;
+    if (p == 0.0) u = aL;
+    else if (p == 1.0) u = 0.5 * (1.0 + tanh((nv - 1.0) / (2.0 * rho))) * aL;
+    else { u = pow(nv / p, 1.0 / (p - 1.0)); if (u > aL) u = aL; }   // np.minimum: a NaN stays NaN
+    if (u != u || !(ms > 0.0)) u = 0.0;
+    const double tj = td[o + j];
+    if (j > 0) acc += 0.5 * (tj - tprev) * (uprev + u);
+    uprev = u; tprev = tj;
+  }
+  cost[b] = acc;
+}
+
+hipError_t launch_dense_cost_mass(const double* Y, long ldy, const double* td, int m, int K, double cT, double p, double rho,
+                                  double* cost, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_cost_mass, dim3((K + 63) / 64), dim3(64), 0, st, Y, ldy, td, m, K, cT, p, rho, cost);
   return hipGetLastError();
 }
 

@@ -219,36 +219,49 @@ int lto_indirect_solve(lto_ctx* c, int ndim, int n_nodes, const double* XC_in, c
                                   status_flag, iterations, history);
 }
 
-/* addTimeFinal (src/HelperFunctions.jl:196-250, re-specified in DESIGN 4.12) for K time-of-flight changes dt[K] of one converged
- * 12-dim solution, every phase on the device: the K extended trajectories (end costates zeroed, a ballistic tail node at
- * t[n-1] + dt) through the dense-output sweep at LinRange(t[0], t_end, n_desired); the natural-spline re-mesh onto LinRange(t[0],
- * t_end, n) (k_remesh_spline); the snap of the last node onto the arrival orbit (k_find_tau); then, if XC_out is set, the fixed-end
- * Newton loop of lto_indirect_solve_batch started from the guesses in HBM, and the cost of its results (k_dense_cost). */
-int lto_indirect_add_time_batch(lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
-                                const lto_integrator* integ, const lto_direct_orbits* orbits, int n_dt, const double* dt, int n_desired,
-                                int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
-                                double* defect, int* status_flag, int* iterations, double* history, double* cost) {
+}  // extern "C"
+
+/* addTimeFinal (src/HelperFunctions.jl:196-250, re-specified in DESIGN 4.12, 4.21) for K time-of-flight changes dt[K] of one converged
+ * solution of nd = 12 or 14 rows (`who` names the entry in the error texts), every phase on the device: the K extended trajectories
+ * (end costates zeroed, a tail node at t[n-1] + dt) through the dense-output sweep at LinRange(t[0], t_end, n_desired); the
+ * natural-spline re-mesh onto LinRange(t[0], t_end, n) (k_remesh_spline); the snap of the last node onto the arrival orbit
+ * (k_find_tau); then, if XC_out is set, the Newton loop of lto_indirect_solve_batch started from the guesses in HBM, and the cost of
+ * its results (k_dense_cost / k_dense_cost_mass).  14 rows: the tail is the 14-row system's own flow with zero costates (the thrust
+ * acceleration exactly zero, the mass by mdot = -kappa umag(0, m) m of the same right-hand side), the re-solve leaves the final mass
+ * free, and propellant [K] = XC[6, 0] - XC_out[6, n-1, k]. */
+static int add_time_rows(const int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t,
+                         const lto_params* prm, const lto_integrator* integ, const lto_direct_orbits* orbits, int n_dt, const double* dt,
+                         int n_desired, int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out,
+                         double* tau_out, double* defect, int* status_flag, int* iterations, double* history, double* cost,
+                         double* propellant) {
   if (!c) return LTO_ENULL;
+  const auto fail = [&](int code, const char* what, hipError_t q = hipSuccess) {
+    char text[384];
+    std::snprintf(text, sizeof text, "%s: %s", who, what);
+    return set_err(c, code, text, q);
+  };
   if (!XC || !t || !prm || !integ || !orbits || !dt || !t_out || !tau_out || (XC_out && !status_flag))
-    return set_err(c, LTO_ENULL, "lto_indirect_add_time_batch: a required argument is NULL");
-  if (ndim != 12) return set_err(c, LTO_EUNSUPPORTED, "lto_indirect_add_time_batch: ndim must be 12 (dense output)");
+    return fail(LTO_ENULL, "a required argument is NULL");
+  if (ndim != nd) return fail(LTO_EUNSUPPORTED, nd == 12 ? "ndim must be 12 (dense output)" : "ndim must be 14");
   if (integ->method != LTO_RK4 && integ->method != LTO_DOP853_ADAPTIVE)
-    return set_err(c, LTO_EUNSUPPORTED, "lto_indirect_add_time_batch: dense output is built for LTO_RK4 and LTO_DOP853_ADAPTIVE");
+    return fail(LTO_EUNSUPPORTED, "dense output is built for LTO_RK4 and LTO_DOP853_ADAPTIVE");
   if (n_dt < 1 || n_nodes < 2 || n_desired < 4 || maxIter < 0)
-    return set_err(c, LTO_EINVAL, "lto_indirect_add_time_batch: need n_dt >= 1, n_nodes >= 2, n_desired >= 4, maxIter >= 0");
+    return fail(LTO_EINVAL, "need n_dt >= 1, n_nodes >= 2, n_desired >= 4, maxIter >= 0");
   for (int b = 0; b < n_dt; ++b)
-    if (!(dt[b] > 0.0) || !std::isfinite(dt[b])) return set_err(c, LTO_EINVAL, "lto_indirect_add_time_batch: every dt must be finite and > 0");
-  if (orbits->nf < 2 || !orbits->tf || !orbits->Xf) return set_err(c, LTO_EINVAL, "lto_indirect_add_time_batch: the arrival table needs >= 2 samples");
+    if (!(dt[b] > 0.0) || !std::isfinite(dt[b])) return fail(LTO_EINVAL, "every dt must be finite and > 0");
+  if (orbits->nf < 2 || !orbits->tf || !orbits->Xf) return fail(LTO_EINVAL, "the arrival table needs >= 2 samples");
   const int K = n_dt, n = n_nodes, m = n_desired, ne = n + 1;
-  if ((long)K * m * 12 > 0x7fffffffL || (long)K * ne * 12 > 0x7fffffffL) return set_err(c, LTO_EINVAL, "lto_indirect_add_time_batch: batch too large");
+  if (nd == 14)
+    for (int j = 0; j < n; ++j)
+      if (!(XC[(size_t)14 * j + 6] > 0.0) || !std::isfinite(XC[(size_t)14 * j + 6])) return fail(LTO_EINVAL, "every node mass must be finite and > 0");
+  if ((long)K * m * nd > 0x7fffffffL || (long)K * ne * nd > 0x7fffffffL) return fail(LTO_EINVAL, "batch too large");
   int rc = bind_device(c);
   if (rc) return rc;
   CallTimer call_timer(c);
   // host side: the grids, the sample ranges of every segment, the extended trajectories and the Thomas factors
-  lto::HostBuf<double> h_te((size_t)K * ne), h_td((size_t)K * m), h_cp((size_t)m, 0.0), h_xe((size_t)12 * K * ne);
+  lto::HostBuf<double> h_te((size_t)K * ne), h_td((size_t)K * m), h_cp((size_t)m, 0.0), h_xe((size_t)nd * K * ne);
   lto::HostBuf<int> h_fe((size_t)K * n + 1), h_fc((size_t)K * (n - 1) + 1);
-  if (!h_te.ok() || !h_td.ok() || !h_cp.ok() || !h_xe.ok() || !h_fe.ok() || !h_fc.ok())
-    return set_err(c, LTO_ENOMEM, "lto_indirect_add_time_batch: out of host memory");
+  if (!h_te.ok() || !h_td.ok() || !h_cp.ok() || !h_xe.ok() || !h_fe.ok() || !h_fc.ok()) return fail(LTO_ENOMEM, "out of host memory");
   const double t0 = t[0];
   // the sample ranges (segment_samples): the last segment also takes the last sample (t_end itself: the lane steps onto it exactly
   // as the final-state store of lto_indirect_densify does)
@@ -263,10 +276,10 @@ int lto_indirect_add_time_batch(lto_ctx* c, int ndim, int n_nodes, const double*
     linrange(t0, te, n, tnb);
     segment_samples(tb, ne, tdb, m, &h_fe[(size_t)b * n], b * m);
     segment_samples(tnb, n, tdb, m, &h_fc[(size_t)b * (n - 1)], b * m);
-    double* xb = &h_xe[(size_t)12 * ne * b];
-    std::memcpy(xb, XC, sizeof(double) * 12 * n);
-    for (int q = 6; q < 12; ++q) xb[12 * (n - 1) + q] = 0.0;         // :199 (on a copy)
-    std::memcpy(xb + 12 * n, xb + 12 * (n - 1), sizeof(double) * 12);  // the tail's end node: never read by the sweep
+    double* xb = &h_xe[(size_t)nd * ne * b];
+    std::memcpy(xb, XC, sizeof(double) * nd * n);
+    for (int q = nd / 2; q < nd; ++q) xb[nd * (n - 1) + q] = 0.0;        // :199 (on a copy); 14 rows: lambda_r, lambda_v, lambda_m
+    std::memcpy(xb + nd * n, xb + nd * (n - 1), sizeof(double) * nd);    // the tail's end node: never read by the sweep
   }
   h_fe[(size_t)K * n] = K * m;
   h_fc[(size_t)K * (n - 1)] = K * m;
@@ -276,15 +289,15 @@ int lto_indirect_add_time_batch(lto_ctx* c, int ndim, int n_nodes, const double*
   double *d_xa, *d_xe, *d_te, *d_tn, *d_td, *d_cp, *d_y, *d_mom, *d_g, *d_ga, *d_xc, *d_tau, *d_cost;
   int *d_fe, *d_fc;
   ArenaLayout scratch;
-  scratch.add((size_t)12 * Je, d_xa, d_xe);
+  scratch.add((size_t)nd * Je, d_xa, d_xe);
   scratch.add((size_t)Je, d_te);
   scratch.add((size_t)Jn, d_tn);
   scratch.add((size_t)Jm, d_td);
   scratch.add((size_t)m, d_cp);
   scratch.add((size_t)Jn + 1, d_fe);
   scratch.add((size_t)(Jn - K) + 1, d_fc);
-  scratch.add((size_t)12 * Jm, d_y, d_mom);
-  scratch.add((size_t)12 * Jn, d_g, d_ga, d_xc);
+  scratch.add((size_t)nd * Jm, d_y, d_mom);
+  scratch.add((size_t)nd * Jn, d_g, d_ga, d_xc);
   scratch.add((size_t)K, d_tau, d_cost);
   lto_direct_orbits arr = *orbits;                 // the upload builds both tables: the departure side gets the arrival's
   arr.n0 = arr.nf; arr.t0 = arr.tf; arr.X0 = arr.Xf;
@@ -293,51 +306,71 @@ int lto_indirect_add_time_batch(lto_ctx* c, int ndim, int n_nodes, const double*
   hipStream_t st = c->stream;
   rc = orbits_upload(c, &arr, dob, st);
   if (rc) return rc;
-  rc = scratch.reserve_block(c, call.block[0], "lto_indirect_add_time_batch");
+  rc = scratch.reserve_block(c, call.block[0], who);
   if (rc) return rc;
-  rc = plan_build(c, 12, ne, K, prm, 1, integ, &call.plan[0]);
+  rc = plan_build(c, nd, ne, K, prm, 1, integ, &call.plan[0]);
   if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(d_xa, h_xe.data(), sizeof(double) * 12 * Je, hipMemcpyHostToDevice, st);
+  const auto dense = nd == 14 ? lto_indirect_dense_mass_dev : lto_indirect_dense_dev;
+  hipError_t e = hipMemcpyAsync(d_xa, h_xe.data(), sizeof(double) * nd * Je, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_te, h_te.data(), sizeof(double) * Je, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_tn, t_out, sizeof(double) * Jn, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_td, h_td.data(), sizeof(double) * Jm, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_cp, h_cp.data(), sizeof(double) * m, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_fe, h_fe.data(), sizeof(int) * (Jn + 1), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_fc, h_fc.data(), sizeof(int) * (Jn - K + 1), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_pack_soa(d_xa, 12, Je, d_xe, Je, st);
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_add_time_batch: stage in", e);
-  // 1-2: the extended trajectories' dense output, Y [12][K m]
-  rc = lto_indirect_dense_dev(call.plan[0], st, d_xe, Je, d_te, K, d_fe, d_td, d_y, Jm, nullptr);
+  if (e == hipSuccess) e = launch_pack_soa(d_xa, nd, Je, d_xe, Je, st);
+  if (e != hipSuccess) return fail(LTO_EHIP, "stage in", e);
+  // 1-2: the extended trajectories' dense output, Y [nd][K m]
+  rc = dense(call.plan[0], st, d_xe, Je, d_te, K, d_fe, d_td, d_y, Jm, nullptr);
   if (rc) return rc;
-  // 3-4: re-mesh, then the end snapped onto the arrival orbit; the guesses G [12][K n] in the solve's layout
+  // 3-4: re-mesh, then the end snapped onto the arrival orbit; the guesses G [nd][K n] in the solve's layout
   RemeshArgs ra;
   ra.Y = d_y; ra.ldy = Jm; ra.td = d_td; ra.tn = d_tn; ra.cp = d_cp; ra.mom = d_mom; ra.G = d_g; ra.ldg = Jn;
   ra.m = m; ra.n = n; ra.K = K;
-  e = launch_remesh_spline(ra, st);
+  e = launch_remesh_spline(nd, ra, st);
   if (e == hipSuccess) e = launch_find_tau(dob.o, d_g, Jn, n, K, d_tau, st);
   if (e == hipSuccess) e = hipMemcpyAsync(tau_out, d_tau, sizeof(double) * K, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && XC_guess) {
-    e = launch_unpack_soa(d_g, Jn, 12, Jn, d_ga, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(XC_guess, d_ga, sizeof(double) * 12 * Jn, hipMemcpyDeviceToHost, st);
+    e = launch_unpack_soa(d_g, Jn, nd, Jn, d_ga, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(XC_guess, d_ga, sizeof(double) * nd * Jn, hipMemcpyDeviceToHost, st);
   }
   if (e == hipSuccess) e = call.wait();
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_add_time_batch: re-mesh", e);
+  if (e != hipSuccess) return fail(LTO_EHIP, "re-mesh", e);
   if (!XC_out) return LTO_OK;
-  // 5: the fixed-end Newton loop on the new grids (:236-237), started from G
-  rc = indirect_solve_impl(c, 12, n, K, nullptr, d_g, t_out, K, prm, 1, integ, flag_adjointsOnly, maxIter, XC_out, cost ? d_xc : nullptr,
+  // 5: the Newton loop on the new grids (:236-237), started from G (12 rows: fixed ends; 14: m0 fixed, the final mass free)
+  rc = indirect_solve_impl(c, nd, n, K, nullptr, d_g, t_out, K, prm, 1, integ, flag_adjointsOnly, maxIter, XC_out, cost ? d_xc : nullptr,
                            defect, status_flag, iterations, history);
-  if (rc || !cost) return rc;
+  if (rc) return rc;
+  if (nd == 14 && propellant)
+    for (int b = 0; b < K; ++b) propellant[b] = XC[6] - XC_out[(size_t)14 * n * b + (size_t)14 * (n - 1) + 6];
+  if (!cost) return rc;
   // the cost of every result: its dense output at the same LinRange(t[0], t_end, n_desired), trapezoid of umag
   call.idle = false;
-  rc = plan_build(c, 12, n, K, prm, 1, integ, &call.plan[1]);
-  if (rc == LTO_OK) rc = lto_indirect_dense_dev(call.plan[1], st, d_xc, Jn, d_tn, K, d_fc, d_td, d_y, Jm, nullptr);
+  rc = plan_build(c, nd, n, K, prm, 1, integ, &call.plan[1]);
+  if (rc == LTO_OK) rc = dense(call.plan[1], st, d_xc, Jn, d_tn, K, d_fc, d_td, d_y, Jm, nullptr);
   if (rc) return rc;
-  const double aL = prm->thrustLimit / prm->mass / 1e3 * (prm->TU * prm->TU) / prm->DU;   // stateCostate_deriv.jl:33
-  e = launch_dense_cost(d_y, Jm, d_td, m, K, aL, prm->p, prm->rho, d_cost, st);
+  if (nd == 14) {
+    const double cT = prm->thrustLimit / 1e3 * (prm->TU * prm->TU) / prm->DU;                // aL = cT / m, the sample's own mass
+    e = launch_dense_cost_mass(d_y, Jm, d_td, m, K, cT, prm->p, prm->rho, d_cost, st);
+  } else {
+    const double aL = prm->thrustLimit / prm->mass / 1e3 * (prm->TU * prm->TU) / prm->DU;   // stateCostate_deriv.jl:33
+    e = launch_dense_cost(d_y, Jm, d_td, m, K, aL, prm->p, prm->rho, d_cost, st);
+  }
   if (e == hipSuccess) e = hipMemcpyAsync(cost, d_cost, sizeof(double) * K, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = call.wait();
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_indirect_add_time_batch: cost", e);
+  if (e != hipSuccess) return fail(LTO_EHIP, "cost", e);
   return LTO_OK;
+}
+
+extern "C" {
+
+int lto_indirect_add_time_batch(lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                                const lto_integrator* integ, const lto_direct_orbits* orbits, int n_dt, const double* dt, int n_desired,
+                                int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
+                                double* defect, int* status_flag, int* iterations, double* history, double* cost) {
+  return add_time_rows(12, "lto_indirect_add_time_batch", c, ndim, n_nodes, XC, t, prm, integ, orbits, n_dt, dt, n_desired,
+                       flag_adjointsOnly, maxIter, XC_guess, XC_out, t_out, tau_out, defect, status_flag, iterations, history, cost,
+                       nullptr);
 }
 
 int lto_indirect_add_time(lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
@@ -346,6 +379,25 @@ int lto_indirect_add_time(lto_ctx* c, int ndim, int n_nodes, const double* XC, c
                           int* iterations, double* history, double* cost) {
   return lto_indirect_add_time_batch(c, ndim, n_nodes, XC, t, prm, integ, orbits, 1, &dt, n_desired, flag_adjointsOnly, maxIter,
                                      XC_guess, XC_out, t_out, tau_out, defect, status_flag, iterations, history, cost);
+}
+
+/* The same for the 14-row variable-mass system. */
+int lto_indirect_add_time_mass_batch(lto_ctx* c, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                                     const lto_integrator* integ, const lto_direct_orbits* orbits, int n_dt, const double* dt,
+                                     int n_desired, int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out,
+                                     double* tau_out, double* defect, int* status_flag, int* iterations, double* history, double* cost,
+                                     double* propellant) {
+  return add_time_rows(14, "lto_indirect_add_time_mass_batch", c, 14, n_nodes, XC, t, prm, integ, orbits, n_dt, dt, n_desired,
+                       flag_adjointsOnly, maxIter, XC_guess, XC_out, t_out, tau_out, defect, status_flag, iterations, history, cost,
+                       propellant);
+}
+
+int lto_indirect_add_time_mass(lto_ctx* c, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                               const lto_integrator* integ, const lto_direct_orbits* orbits, double dt, int n_desired,
+                               int flag_adjointsOnly, int maxIter, double* XC_guess, double* XC_out, double* t_out, double* tau_out,
+                               double* defect, int* status_flag, int* iterations, double* history, double* cost, double* propellant) {
+  return lto_indirect_add_time_mass_batch(c, n_nodes, XC, t, prm, integ, orbits, 1, &dt, n_desired, flag_adjointsOnly, maxIter,
+                                          XC_guess, XC_out, t_out, tau_out, defect, status_flag, iterations, history, cost, propellant);
 }
 
 }  // extern "C"

@@ -1083,6 +1083,50 @@ def tf_sweep(XC_all, t_TU, Δts, MU, DU, TU, mass, thrustLimit, p, rho, Xf_times
             "iterations": r.iterations, "max_defect": np.abs(r.defect).max(axis=(0, 1)), "cost": r.cost}
 
 
+def addTimeFinal_mass(XC_all, t_TU, Δt, MU, DU, TU, n_nodes, Isp, thrustLimit, p, rho, Xf_times, Xf_states, maxIter=10,
+                      n_desired=200, flag_adjointsOnly=False, integ=None, ctx=None, verbose=True):
+    """addTimeFinal for a converged solution of the 14-row variable-mass system (one library call,
+    lto_indirect_add_time_mass_batch): rows 7..13 of the last node are zeroed on a copy (the caller's array is not changed), the
+    tail of Δt TU is the 14-row system's own flow with zero costates -- the orbit coasts, the mass follows the law's flow at
+    |λ_v| = 0: constant for p > 1, full throttle for p = 0, the idle flow aL / (1 + e^(1/ρ)) for p = 1 -- and the 14-row loop
+    re-solves on LinRange(t[0], t[end] + Δt, n_nodes) with r0, v0, m0 and rf, vf fixed and the final mass free: the guess's mass
+    row is a starting value only.  Returns (XC_new, t_new) on status 0, otherwise the original (XC_all, t_TU) unchanged."""
+    XC_all = np.array(XC_all, dtype=np.float64, order="F")
+    t_TU = np.array(t_TU, dtype=np.float64)
+    if XC_all.shape != (14, int(n_nodes)):
+        raise ValueError("addTimeFinal_mass takes the 14-row solution [14 x n_nodes]; got shape %s" % (XC_all.shape,))
+    if not (Isp > 0):
+        raise ValueError("Isp must be positive; got %r" % (Isp,))
+    params = hotpath.make_params(MU, DU, TU, thrustLimit, Isp, 1.0, p, rho)
+    r = hotpath.indirect_add_time_mass(XC_all, t_TU, params, Xf_times, Xf_states, [float(Δt)], n_desired=n_desired, integ=integ,
+                                       flag_adjointsOnly=flag_adjointsOnly, maxIter=maxIter, ctx=ctx)
+    if verbose:
+        print("addTimeFinal_mass: Δt = %.6g TU, τ* = %.3f, status %d after %d iterations, propellant %.6f kg"
+              % (Δt, r.tau[0], r.status[0], r.iterations[0], r.propellant[0]))
+    if r.status[0] == 0:
+        return r.XC_out[:, :, 0].copy(), r.t_out[:, 0].copy()
+    return XC_all, t_TU
+
+
+def tf_sweep_mass(XC_all, t_TU, Δts, MU, DU, TU, Isp, thrustLimit, p, rho, Xf_times, Xf_states, maxIter=10, n_desired=200,
+                  flag_adjointsOnly=False, integ=None, ctx=None):
+    """addTimeFinal_mass for many Δt at once: the propellant-versus-time-of-flight curve of a converged variable-mass transfer in
+    one library call.  Returns the dict of tf_sweep (XC [14 x n x K]; cost with every sample's own mass) plus propellant_kg [K] =
+    XC_all[6, 0] - XC[6, -1, k] and mass_final_kg [K] = XC[6, -1, k]."""
+    XC_all = np.asarray(XC_all, dtype=np.float64)
+    if XC_all.ndim != 2 or XC_all.shape[0] != 14:
+        raise ValueError("tf_sweep_mass takes the 14-row solution [14 x n_nodes]; got shape %s" % (XC_all.shape,))
+    if not (Isp > 0):
+        raise ValueError("Isp must be positive; got %r" % (Isp,))
+    params = hotpath.make_params(MU, DU, TU, thrustLimit, Isp, 1.0, p, rho)
+    dts = np.asarray(Δts, dtype=np.float64).reshape(-1)
+    r = hotpath.indirect_add_time_mass(XC_all, t_TU, params, Xf_times, Xf_states, dts, n_desired=n_desired, integ=integ,
+                                       flag_adjointsOnly=flag_adjointsOnly, maxIter=maxIter, ctx=ctx)
+    return {"dt": dts, "tof": r.t_out[-1] - r.t_out[0], "XC": r.XC_out, "t": r.t_out, "tau": r.tau, "status": r.status,
+            "iterations": r.iterations, "max_defect": np.abs(r.defect).max(axis=(0, 1)), "cost": r.cost,
+            "propellant_kg": r.propellant, "mass_final_kg": r.XC_out[6, -1, :].copy()}
+
+
 def meshRefine_indirect(XC_all, t_TU, MU, DU, TU, n_nodes, mass, thrustLimit, p, rho, n_new=None, passes=2, weights=None, maxIter=10,
                         flag_adjointsOnly=False, integ=None, ctx=None, verbose=True):
     """Mesh re-distribution of a converged 12-row indirect solution, the counterpart of meshRefine_direct: the nodes

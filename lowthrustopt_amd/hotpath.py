@@ -1102,22 +1102,19 @@ def stack_guess(tau1, tof1, tof2, n_nodes, orbits, MU=MU, integ=None, ctx=None):
 
 
 AddTime = collections.namedtuple("AddTime", "XC_guess XC_out t_out tau defect status iterations history cost")
+AddTimeMass = collections.namedtuple("AddTimeMass", AddTime._fields + ("propellant",))
 
 
-def indirect_add_time(XC, t, params, Xf_times, Xf_states, dts, n_desired=200, integ=None, flag_adjointsOnly=False, maxIter=10,
-                      solve=True, ctx=None):
-    """addTimeFinal (src/HelperFunctions.jl:196-250, re-specified: DESIGN 4.12) for K time-of-flight changes at once
-    (lto_indirect_add_time_batch): the converged 12-dim solution XC [12 x n] on t [n] with a ballistic tail of dts[k] TU,
-    densified at n_desired points, re-meshed onto LinRange(t[0], t[n-1] + dts[k], n) and its end snapped onto the arrival orbit
-    table (Xf_times [nf] in [0, 1], Xf_states [6 x nf]); then, with solve = True, the fixed-end Newton loop on the new grids.
-    Returns AddTime(XC_guess [12 x n x K], XC_out [12 x n x K], t_out [n x K], tau [K], defect [12 x (n-1) x K], status [K],
-    iterations [K], history (one array of (max|defect|, alpha) per trajectory), cost [K] in DU/TU); the solve's fields are None
-    when solve = False."""
+def _indirect_add_time(entry, rows, XC, t, params, Xf_times, Xf_states, dts, n_desired, integ, flag_adjointsOnly, maxIter, solve, ctx):
+    """indirect_add_time / indirect_add_time_mass: one body, `entry` the library call and `rows` its row count (None: the 12-row
+    entry, which takes ndim as an argument and decides itself)."""
+    if rows is not None and (np.ndim(XC) != 2 or np.shape(XC)[0] != rows):       # before any library call
+        raise ValueError("%s takes one trajectory [%d x n_nodes]" % (entry, rows))
     ctx = ctx or default_context()
     integ = integ or integrator()
     X = _f64(XC)
     if X.ndim != 2:
-        raise ValueError("indirect_add_time takes one trajectory [ndim x n_nodes]")
+        raise ValueError("%s takes one trajectory [ndim x n_nodes]" % entry)
     ndim, n = X.shape
     tt = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
     if tt.size != n:
@@ -1131,7 +1128,7 @@ def indirect_add_time(XC, t, params, Xf_times, Xf_states, dts, n_desired=200, in
     guess = np.zeros((ndim, n, K), order="F")
     t_out = np.zeros((n, K), order="F")
     tau = np.zeros(K)
-    XC_out = defect = status = iters = hist = cost = None
+    XC_out = defect = status = iters = hist = cost = prop = None
     if solve:
         XC_out = np.zeros((ndim, n, K), order="F")
         defect = np.zeros((ndim, n - 1, K), order="F")
@@ -1139,15 +1136,49 @@ def indirect_add_time(XC, t, params, Xf_times, Xf_states, dts, n_desired=200, in
         iters = np.zeros(K, dtype=np.int32)
         hist = np.full((2, max(int(maxIter), 1), K), np.nan, order="F")
         cost = np.zeros(K)
-    ctx.check(ctx.fn("indirect_add_time_batch")(
-        ctx.handle, ndim, n, _ptr(X), _ptr(tt), prm, C.byref(integ), C.byref(ob.struct), K, _ptr(dts), int(n_desired),
-        1 if flag_adjointsOnly else 0, int(maxIter), _ptr(guess), _ptr(XC_out) if solve else None, _ptr(t_out), _ptr(tau),
-        _ptr(defect) if solve else None, _ptr(status) if solve else None, _ptr(iters) if solve else None,
-        _ptr(hist) if solve and maxIter > 0 else None, _ptr(cost) if solve else None))
+        prop = np.zeros(K)
+    out = lambda a: _ptr(a) if solve else None   # noqa: E731
+    args = [ctx.handle]
+    if rows is None:
+        args.append(ndim)
+    args += [n, _ptr(X), _ptr(tt), prm, C.byref(integ), C.byref(ob.struct), K, _ptr(dts), int(n_desired),
+             1 if flag_adjointsOnly else 0, int(maxIter), _ptr(guess), out(XC_out), _ptr(t_out), _ptr(tau), out(defect), out(status),
+             out(iters), _ptr(hist) if solve and maxIter > 0 else None, out(cost)]
+    if rows is not None:
+        args.append(out(prop))                                  # the mass entry's last argument
+    ctx.check(ctx.fn(entry + "_batch")(*args))
     history = None
     if solve:
         history = [hist[:, ~np.isnan(hist[1, :, b]), b].T.copy() for b in range(K)]
-    return AddTime(guess, XC_out, t_out, tau, defect, status, iters, history, cost)
+    result = AddTime(guess, XC_out, t_out, tau, defect, status, iters, history, cost)
+    return result if rows is None else AddTimeMass(*result, prop)
+
+
+def indirect_add_time(XC, t, params, Xf_times, Xf_states, dts, n_desired=200, integ=None, flag_adjointsOnly=False, maxIter=10,
+                      solve=True, ctx=None):
+    """addTimeFinal (src/HelperFunctions.jl:196-250, re-specified: DESIGN 4.12) for K time-of-flight changes at once
+    (lto_indirect_add_time_batch): the converged 12-dim solution XC [12 x n] on t [n] with a ballistic tail of dts[k] TU,
+    densified at n_desired points, re-meshed onto LinRange(t[0], t[n-1] + dts[k], n) and its end snapped onto the arrival orbit
+    table (Xf_times [nf] in [0, 1], Xf_states [6 x nf]); then, with solve = True, the fixed-end Newton loop on the new grids.
+    Returns AddTime(XC_guess [12 x n x K], XC_out [12 x n x K], t_out [n x K], tau [K], defect [12 x (n-1) x K], status [K],
+    iterations [K], history (one array of (max|defect|, alpha) per trajectory), cost [K] in DU/TU); the solve's fields are None
+    when solve = False."""
+    return _indirect_add_time("indirect_add_time", None, XC, t, params, Xf_times, Xf_states, dts, n_desired, integ, flag_adjointsOnly,
+                              maxIter, solve, ctx)
+
+
+def indirect_add_time_mass(XC, t, params, Xf_times, Xf_states, dts, n_desired=200, integ=None, flag_adjointsOnly=False, maxIter=10,
+                           solve=True, ctx=None):
+    """indirect_add_time for a converged solution of the 14-row variable-mass system (lto_indirect_add_time_mass_batch):
+    XC [14 x n], params with Isp in the mass slot.  Rows 7..13 of the last node are zeroed on a copy; the tail of dts[k] TU is the
+    14-row system's own flow with zero costates -- position and velocity coast, the costates stay exactly 0, and the mass follows
+    mdot = -kappa umag(0, m) m of the same right-hand side: constant for p > 1, the full-throttle flow for p = 0, the law's idle
+    flow aL / (1 + e^(1 / rho)) for p = 1.  The mass row of the guess is a starting value: with solve = True the 14-row Newton loop
+    (r, v, m of the first node and r, v of the last fixed, the last node's mass costate 0) owns the final mass.  Returns
+    AddTimeMass: the fields of AddTime with 14 rows -- cost [K] in DU/TU with every sample's own mass in the acceleration limit --
+    plus propellant [K] = XC[6, 0] - XC_out[6, -1, k] in kg; the solve's fields are None when solve = False."""
+    return _indirect_add_time("indirect_add_time_mass", 14, XC, t, params, Xf_times, Xf_states, dts, n_desired, integ, flag_adjointsOnly,
+                              maxIter, solve, ctx)
 
 
 Remesh = collections.namedtuple("Remesh", "XC_guess XC_out t_out defect status iterations history steps_before steps_after")
