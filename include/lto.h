@@ -8,6 +8,8 @@
  * The reference has no FFI of its own (pure Julia); these entry points are what a `ccall` from the
  * two Julia drivers binds instead of running the closures' serial `for i = 1:n_nodes-1` loops
  * (INTEGRATION.md shows the Julia side).  Plain C: pointers, ints and doubles only.
+ * Beyond the closures the library carries the drivers' loops and what they feed (Newton solves, QP steps, re-meshes, dense
+ * output, thrust events) and the replay of a solution's thrust history from dispersed starts (lto_control_replay_batch).
  *
  * Conventions
  *   - All floating point data is binary64.  Host arrays use the reference's Julia layouts
@@ -827,6 +829,34 @@ int lto_indirect_events_mass(lto_ctx* ctx, int n_nodes, const double* XC, const 
 int lto_indirect_events_mass_dev(lto_indirect_plan* plan, void* stream, const double* X, long ldx, const double* t, int n_tgrids,
                                  int max_events, int* n_events, double* t_event, int* kind, int* on0, double* dv, double* burn_time,
                                  double* dv_seg, double* propellant, double* dm_seg, int* status);
+
+/* Control replay: fly a given history of lambda_v from n_batch starts.  x = (r, v) for nstate = 6, (r, v, m) for
+ * nstate = 7; the right-hand side is rows 0..5 of the 12-row system, or rows 0..6 of the 14-row system, with lambda_v replaced by
+ * the spline value L(t) and every other costate unused:  n = |L|;  aL = thrustLimit / mass / 1e3 * TU^2 / DU (nstate 6, the
+ * constant lto_params.mass) or cT / m with the current mass (nstate 7, lto_params.mass carrying Isp as everywhere for 14 rows);
+ * umag(n) the control law for p = 0, p = 1, p > 1;  thrust acceleration -umag L / n (0 where n is 0);  mdot = -kappa umag m,
+ * kappa = time_direction * 1e3 * DU / (TU * Isp * 9.81);  q' = umag.  This is the reference's CRTBP_prop_EP_NNControl_deriv!
+ * (src/CRTBP_prop_EP_deriv.jl:128-215) with its two defects resolved: the `mass` undefined at :142 is the one above, and the flow
+ * rate of :195, which feeds an acceleration into a formula in newtons, is the 14-row system's.
+ * Control history: knots LinRange(t0, t1, n_knots), values lamv [3 x n_knots x n_hist] column-major, n_hist = 1 (one history for
+ * every start) or n_batch (each start its own); L is the natural cubic spline (second derivative 0 at both ends) per component.
+ * The integration runs knot interval by knot interval -- no step spans a knot -- each interval a span of its own with
+ * LTO_DOP853_ADAPTIVE (x and q in the error norm; max_steps counts per interval) or LTO_RK4 (`steps` steps per interval); any
+ * other method, or nstate not 6 or 7: LTO_EUNSUPPORTED.
+ * x0 [nstate x B];  n_prm is 1 or B.  Out: x_final [nstate x B];  dv [B] (DU/TU) = q(t1);  accepted / rejected [B] summed over the
+ * intervals (either may be NULL);  X_samples [nstate x n_samples x B]: the state at the knots k with k % sample_every == 0, and at
+ * the last knot if that rule does not list it (sample_every = 0: none, X_samples may be NULL); the sample at knot 0 is x0 and the
+ * last sample x_final, bit for bit.  status[b]: 0 ok;  2 a non-finite input or state, a start mass that is not finite and positive
+ * (nstate 7), or an interval out of max_steps: x_final, dv and the samples from that interval on are NaN, no other trajectory is
+ * affected.  LTO_ENULL; LTO_EINVAL (n_knots < 4, t1 <= t0 or not finite, n_hist or n_prm not 1 or B, sample_every < 0,
+ * n_batch < 1). */
+int lto_control_replay_batch(lto_ctx* ctx, int nstate, int n_knots, int n_batch, double t0, double t1, const double* lamv,
+                             int n_hist, const double* x0, const lto_params* prm, int n_prm, const lto_integrator* integ,
+                             int sample_every, double* x_final, double* X_samples, double* dv, int* accepted, int* rejected,
+                             int* status);
+int lto_control_replay(lto_ctx* ctx, int nstate, int n_knots, double t0, double t1, const double* lamv, const double* x0,
+                       const lto_params* prm, const lto_integrator* integ, int sample_every, double* x_final, double* X_samples,
+                       double* dv, int* accepted, int* rejected, int* status);
 
 int lto_direct_plan_create(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, int nsteps,
                            const lto_direct_params* prm, lto_direct_plan** out);

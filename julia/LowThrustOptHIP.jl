@@ -503,6 +503,32 @@ function thrust_arcs_mass(ctx::LtoContext, XC_all::Array{Float64,3}, t_TU::Matri
     end
 end
 
+"""Control replay (`lto_control_replay_batch`, DESIGN 4.22): fly the history `lamv` [3 x n_knots x n_hist] of lambda_v, given at
+the knots LinRange(t0, t1, n_knots) with n_hist = 1 or n_batch, from the starts `x0` [nstate x n_batch] (nstate 6: r, v with the
+constant `mass` of the parameters; nstate 7: r, v, m with Isp in the mass slot).  The control is the natural cubic spline of `lamv`,
+integrated knot interval by knot interval.  Returns the named tuple (x_final [nstate x B], dv [B] in DU/TU, accepted, rejected,
+status [B], samples [nstate x n_samples x B] at the knots k with k % sample_every == 0 and the last one; `nothing` for
+sample_every = 0)."""
+function control_replay(ctx::LtoContext, x0::Matrix{Float64}, lamv::Array{Float64,3}, t0::Real, t1::Real, params::Vector;
+                        sample_every::Integer = 0, integ::LtoIntegrator = LtoIntegrator())
+    nstate, B = size(x0)
+    size(lamv, 1) == 3 || throw(ArgumentError("lamv must be [3 x n_knots x n_hist]"))
+    n_knots, n_hist = size(lamv, 2), size(lamv, 3)
+    prm = [LtoParams(q) for q in params]
+    last = n_knots - 1
+    ns = sample_every > 0 ? div(last, sample_every) + 1 + (last % sample_every != 0 ? 1 : 0) : 0
+    x_final = zeros(nstate, B); samples = zeros(nstate, max(ns, 1), B); dv = zeros(B)
+    accepted = zeros(Cint, B); rejected = zeros(Cint, B); status = zeros(Cint, B)
+    rc = ccall((:lto_control_replay_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{LtoParams}, Cint,
+                Ref{LtoIntegrator}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}),
+               ctx.handle, nstate, n_knots, B, Float64(t0), Float64(t1), lamv, n_hist, x0, prm, length(prm), Ref(integ), sample_every,
+               x_final, samples, dv, accepted, rejected, status)
+    check(ctx, rc)
+    (x_final = x_final, dv = dv, accepted = Int.(accepted), rejected = Int.(rejected), status = Int.(status),
+     samples = ns > 0 ? samples : nothing)
+end
+
 # ---------------------------------------------------------------------------------------------- direct
 "defectCalc of multiShoot_CRTBP_direct: returns (defect1[nstate x (n_nodes-1)], errors[n_nodes-1])."
 function direct_defectCalc(ctx::LtoHandle, X_all::Matrix{Float64}, u_all::Matrix{Float64}, t_TU::Vector{Float64},

@@ -10,7 +10,8 @@ from .hotpath import (Context, Group, Comm, GroupComm, auto_kernel, default_cont
                       direct_qp_step, direct_solve, direct_costates, costate_scale, DirectOrbits, direct_end_model, direct_end_states,
                       direct_qp_step_free, direct_solve_free, direct_tf_bounds, direct_qp_step_free_tf, direct_solve_free_tf,
                       indirect_add_time, indirect_remesh, direct_refine, direct_resample, stack_guess, StackGuess, indirect_events, ThrustEvents,
-                      indirect_events_mass, densify_mass, indirect_remesh_mass, indirect_add_time_mass)
+                      indirect_events_mass, densify_mass, indirect_remesh_mass, indirect_add_time_mass, control_replay, ControlReplay,
+                      replay_sample_knots)
 from . import synth  # noqa: F401
 
 __version__ = "0.1.0"

@@ -136,6 +136,26 @@ inline size_t events_record_bytes(long S, int ndim = 12) {
 hipError_t launch_indirect_events(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st);
 hipError_t launch_indirect_events_mass(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st);
 hipError_t launch_events_compact(const IndirectArgs& a, const EventsArgs& e, int n_batch, hipStream_t st);
+// Control replay (kernels_replay.hip).  The moment kernel: lamv [n_hist][n_knots][3] as the caller passes it, cp [n_knots]
+// the Thomas factors of the (1, 4, 1) system, mom [n_knots][3 n_hist] scratch; vm [n_knots][6][n_hist] = per knot and component the
+// value and the moment of the natural spline.
+hipError_t launch_replay_moments(const double* lamv, const double* cp, double* mom, double* vm, int n_knots, int n_hist, double h,
+                                 hipStream_t st);
+// The replay itself: of `a` it reads tp / tp_stride, steps, rtol, atol and max_steps (max_steps per knot interval).
+struct ReplayArgs {
+  const double* vm; int n_hist;    // as above; n_hist = 1 or n_batch
+  int n_knots, n_batch;
+  double h;                        // (t1 - t0) / (n_knots - 1)
+  const double* x0;                // [nstate][n_batch]
+  double* x_final;                 // [nstate][n_batch]
+  double* dv;                      // [n_batch]
+  int* nacc; int* nrej;            // [n_batch], summed over the intervals
+  int* status;                     // [n_batch]: 0 ok, 2 not finite / mass not positive / an interval out of max_steps
+  double* samples; long ld_s;      // [nstate][ld_s], trajectory b's sample j in column b n_samples + j; null: none
+  int n_samples, sample_every;     // knots k with k % sample_every == 0, and the last one
+};
+// nstate 6 or 7, method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
+hipError_t launch_control_replay(int nstate, int pm, int method, const IndirectArgs& a, const ReplayArgs& r, hipStream_t st);
 // wave-specialised STM kernel (kernels_indirect_coop.hip): base wave + column waves per 16 segments
 hipError_t launch_indirect_stm_coop(int ndim, int pm, int method, const IndirectArgs& a, hipStream_t st);
 // the same with every 12-component state split over two lanes (kernels_indirect_coop2.hip), DOP853 adaptive only; the 14-dim form

@@ -13,6 +13,8 @@
                               what the reference's `nstate == 7` branches (:158-161, :195-199) were meant to solve.
                               Both systems run one loop (_solve_indirect) and one least-squares step (_ols_step); they
                               differ only in which entries of XC_all[:, node] are pinned (_PINS, keyed by the row count)
+  fly_control / dispersion    src/CRTBP_prop_EP_deriv.jl:128-215 re-specified (CRTBP_prop_EP_NNControl_deriv!): a
+                              solution's lambda_v(t) as a spline, flown open loop from dispersed starts in ONE device call
   controlLaw_cart             src/multiShoot_CRTBP_indirect.jl:389-440 (costates -> thrust vectors in N: the u_all format
                                                                         of the direct transcription; host post-processing)
 
@@ -1387,6 +1389,79 @@ def thrust_arcs_mass(XC_all, t_TU, MU, DU, TU, Isp, thrustLimit, p, rho, max_eve
     ev = hotpath.indirect_events_mass(X3, t, prms, max_events, integ, ctx)
     out = _mass_budget(ev, X3[6, 0, :], per[0], DU, TU, t, max_events)
     return out if batched else out[0]
+
+
+def replay_misses(x_final, x_target, DU, TU):
+    """Misses of replayed end states x_final [nstate x B] against x_target [nstate]: dict of miss_r_km and miss_v_ms [B] (the
+    2-norms of the position and velocity differences) and, for 7 states, miss_m_kg (final mass minus the target's)."""
+    xf = np.asarray(x_final, dtype=np.float64)
+    d = xf - np.asarray(x_target, dtype=np.float64)[:, None]
+    out = dict(miss_r_km=np.linalg.norm(d[0:3], axis=0) * DU, miss_v_ms=np.linalg.norm(d[3:6], axis=0) * DU / TU * 1e3)
+    if xf.shape[0] == 7:
+        out["miss_m_kg"] = d[6].copy()
+    return out
+
+
+def dispersion_starts(x_nominal, n_samples, sigma_r_km, sigma_v_ms, seed, DU, TU):
+    """x0 [nstate x n_samples]: the nominal start with Gaussian position errors of sigma_r_km per axis and velocity errors of
+    sigma_v_ms per axis from numpy.random.default_rng(seed); sample 0 is the nominal start itself, a mass row is left alone."""
+    x = np.asarray(x_nominal, dtype=np.float64)
+    n = int(n_samples)
+    if n < 1:
+        raise ValueError("n_samples must be >= 1")
+    rng = np.random.default_rng(seed)
+    err = rng.standard_normal((6, n))
+    err[0:3] *= float(sigma_r_km) / DU
+    err[3:6] *= float(sigma_v_ms) / 1e3 * TU / DU
+    err[:, 0] = 0.0
+    x0 = np.array(np.repeat(x[:, None], n, axis=1), order="F")
+    x0[0:6] += err
+    x0[:, 0] = x
+    return x0
+
+
+def fly_control(ctx, XC_all, t_TU, prm, x0=None, lamv=None, n_knots=257, integ=None, sample_every=0):
+    """Fly the thrust history of an indirect solution from given starts (hotpath.control_replay).  XC_all [12 x n] or
+    [14 x n] with its grid t_TU and its parameters prm (LtoParams or the 8-tuple; 14 rows: Isp in the mass slot).  The solution
+    is sampled at n_knots even times with hotpath.densify / densify_mass, lambda_v (rows 9..11, or 10..12) at those knots is the
+    control history -- or lamv [3 x n_knots] / [3 x n_knots x B], a corrector's -- and the 6- or 7-state is replayed from x0
+    [nstate x B] (default: the solution's own first node).  Returns a dict: x_final, miss_r_km, miss_v_ms (and miss_m_kg for 14
+    rows) against the solution's last node, dv (DU/TU), dv_ms, status, accepted, rejected, samples, sample_knots, lamv, t_knots."""
+    XC = np.asarray(XC_all, dtype=np.float64)
+    if XC.ndim != 2 or XC.shape[0] not in (12, 14):
+        raise ValueError("XC_all must be [12 x n] or [14 x n]")
+    nd = XC.shape[0]
+    ns = 6 if nd == 12 else 7
+    t = np.asarray(t_TU, dtype=np.float64)
+    p = prm if isinstance(prm, hotpath.LtoParams) else hotpath.make_params(*prm)
+    if lamv is None:
+        dense, t_knots = (hotpath.densify if nd == 12 else hotpath.densify_mass)(XC, t, p, int(n_knots), integ, ctx)
+        lamv = np.array(dense[9:12] if nd == 12 else dense[10:13], order="F")
+    else:
+        lamv = np.asarray(lamv, dtype=np.float64)
+        t_knots = np.linspace(t[0], t[-1], lamv.shape[1])
+    x0 = XC[:ns, :1].copy() if x0 is None else np.asarray(x0, dtype=np.float64).reshape(ns, -1)
+    r = hotpath.control_replay(x0, lamv, float(t[0]), float(t[-1]), p, integ, sample_every, ctx)
+    out = dict(x_final=r.x_final, dv=r.dv, dv_ms=r.dv * p.DU / p.TU * 1e3, status=r.status, accepted=r.accepted,
+               rejected=r.rejected, samples=r.samples, sample_knots=r.sample_knots, lamv=lamv, t_knots=t_knots)
+    out.update(replay_misses(r.x_final, XC[:ns, -1], p.DU, p.TU))
+    return out
+
+
+def dispersion(ctx, XC_all, t_TU, prm, n_samples, sigma_r_km, sigma_v_ms, seed, n_knots=257, integ=None, lamv=None):
+    """Monte-Carlo dispersion of an indirect solution's open-loop thrust history: n_samples starts drawn by dispersion_starts
+    around the solution's first node (sample 0 undisturbed), all flown by fly_control in one call.  Returns fly_control's dict
+    plus x0 and, over the samples of status 0, percentiles = {"miss_r_km": {50: .., 95: .., 99: ..}, "miss_v_ms": {..}}."""
+    XC = np.asarray(XC_all, dtype=np.float64)
+    ns = 6 if XC.shape[0] == 12 else 7
+    p = prm if isinstance(prm, hotpath.LtoParams) else hotpath.make_params(*prm)
+    x0 = dispersion_starts(XC[:ns, 0], n_samples, sigma_r_km, sigma_v_ms, seed, p.DU, p.TU)
+    out = fly_control(ctx, XC, t_TU, p, x0, lamv, n_knots, integ)
+    ok = np.asarray(out["status"]) == 0
+    out["x0"] = x0
+    out["percentiles"] = {k: {q: (float(np.percentile(out[k][ok], q)) if ok.any() else float("nan")) for q in (50, 95, 99)}
+                          for k in ("miss_r_km", "miss_v_ms")}
+    return out
 
 
 def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, maxIter=10, max_waves=12, ctx=None, verbose=True,

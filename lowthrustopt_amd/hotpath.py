@@ -660,6 +660,67 @@ def indirect_events_mass(XC_all, t_TU, params, max_events=64, integ=None, ctx=No
     return ThrustEvents(n_events, t_event, kind, on0, dv, burn, dv_seg, status, prop, dm_seg)
 
 
+class ControlReplay:
+    """Result of control_replay; B starts (batched) or one (the batch axis dropped): x_final [nstate x B], dv [B] (DU/TU),
+    accepted / rejected [B] (steps summed over the knot intervals), status [B] (0 ok, 2 no result: NaN), samples
+    [nstate x n_samples x B] at the knots sample_knots (None without sampling)."""
+
+    def __init__(self, x_final, dv, accepted, rejected, status, samples, sample_knots):
+        self.x_final, self.dv, self.accepted, self.rejected, self.status = x_final, dv, accepted, rejected, status
+        self.samples, self.sample_knots = samples, sample_knots
+
+
+def replay_sample_knots(n_knots, sample_every):
+    """The knots control_replay samples: k % sample_every == 0, and the last one; none for sample_every = 0."""
+    if sample_every <= 0:
+        return np.zeros(0, dtype=np.int64)
+    ks = list(range(0, int(n_knots), int(sample_every)))
+    if ks[-1] != n_knots - 1:
+        ks.append(n_knots - 1)
+    return np.array(ks, dtype=np.int64)
+
+
+def control_replay(x0, lamv, t0, t1, params, integ=None, sample_every=0, ctx=None):
+    """Fly a history of lambda_v from many starts (lto_control_replay_batch): x0 [nstate] or [nstate x B] with nstate 6
+    (r, v; params.mass the constant mass) or 7 (r, v, m; the mass slot carries Isp); lamv [3 x n_knots] (one history for every
+    start) or [3 x n_knots x B] (one per start) at the knots LinRange(t0, t1, n_knots); params one tuple or one per start.  The
+    control is the natural cubic spline of lamv, integrated knot interval by knot interval with LTO_RK4 (`steps` per interval) or
+    LTO_DOP853_ADAPTIVE.  Returns a ControlReplay."""
+    X = _f64(x0)
+    if X.ndim not in (1, 2):
+        raise ValueError("x0 must be [nstate] or [nstate x B]")
+    batched = X.ndim == 2
+    X2 = np.asfortranarray(X.reshape(X.shape[0], -1, order="F"))
+    nstate, B = X2.shape
+    L = _f64(lamv)
+    if L.ndim not in (2, 3) or L.shape[0] != 3:
+        raise ValueError("lamv must be [3 x n_knots] or [3 x n_knots x n_hist]")
+    L3 = np.asfortranarray(L.reshape(3, L.shape[1], -1, order="F"))
+    n_knots, n_hist = L3.shape[1], L3.shape[2]
+    if n_hist != 1 and n_hist != B:
+        raise ValueError("lamv must hold one history or one per start")
+    if isinstance(params, tuple) and len(params) == 8 and np.isscalar(params[0]):
+        params = make_params(*params)
+    prm, nprm = _params_array(params)
+    if nprm != 1 and nprm != B:
+        raise ValueError("params must be one tuple or one per start")
+    every = int(sample_every)
+    knots = replay_sample_knots(n_knots, every)
+    x_final = np.zeros((nstate, B), order="F")
+    samples = np.zeros((nstate, len(knots), B), order="F") if every > 0 else None
+    dv = np.zeros(B)
+    acc, rej, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    ctx.check(ctx.fn("control_replay_batch")(ctx.handle, nstate, n_knots, B, float(t0), float(t1), _ptr(L3), n_hist, _ptr(X2), prm,
+                                             nprm, C.byref(integ), every, _ptr(x_final), _ptr(samples), _ptr(dv), _ptr(acc),
+                                             _ptr(rej), _ptr(status)))
+    if not batched:
+        return ControlReplay(x_final[:, 0], float(dv[0]), int(acc[0]), int(rej[0]), int(status[0]),
+                             None if samples is None else samples[:, :, 0], knots)
+    return ControlReplay(x_final, dv, acc, rej, status, samples, knots)
+
+
 def direct_defectCalc(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None):
     """defectCalc of multiShoot_CRTBP_direct (:66-109): returns (defect[nstate x (n-1)], errors[n-1])."""
     ctx = ctx or default_context()
