@@ -7,6 +7,13 @@ per axis, lambda_v(t) of the solution as a natural cubic spline over 257 even kn
 interval in one library call.  Prints the nominal replay's miss at the arrival node and the 50th, 95th and 99th percentiles of
 the dispersed misses.  The transfer is 20 days along an unstable orbit family and nothing corrects the flight: the misses show
 how fast an injection error grows, which is what a corrector would have to take out.
+
+  python examples/halo_dispersion_demo.py [n_samples] [--guided [update_every]]
+
+With --guided the same starts are also flown with neighbouring-extremal feedback (drivers.dispersion_guided ->
+lto_guidance_gains_batch, lto_guided_flight_batch): the costate is reset from the feedback gains at every
+update_every-th node of the solution (default 1), and the open-loop and guided percentiles are printed side by side with the
+dv the feedback costs over the nominal's.
 """
 import importlib.util
 import os
@@ -20,7 +27,7 @@ from lowthrustopt_amd import drivers  # noqa: E402
 from lowthrustopt_amd.constants import MU, DU, TU, day  # noqa: E402
 
 
-def main(n_samples=4096, sigma_r_km=1.0, sigma_v_ms=0.01, seed=0, n_knots=257, verbose=True):
+def main(n_samples=4096, sigma_r_km=1.0, sigma_v_ms=0.01, seed=0, n_knots=257, verbose=True, guided=None):
     spec = importlib.util.spec_from_file_location("halo_demo", os.path.join(ROOT, "examples", "halo_transfer_demo.py"))
     demo = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(demo)
@@ -42,8 +49,27 @@ def main(n_samples=4096, sigma_r_km=1.0, sigma_v_ms=0.01, seed=0, n_knots=257, v
         print("  percentile   miss [km]    miss [m/s]")
         for q in (50, 95, 99):
             print("  %9d  %11.4g  %12.4g" % (q, pc["miss_r_km"][q], pc["miss_v_ms"][q]))
-    return nominal, out
+    if guided is None:
+        return nominal, out
+    t0 = time.perf_counter()
+    g = drivers.dispersion_guided(ctx, XC, t, prm, n_samples, sigma_r_km, sigma_v_ms, seed, update_every=guided)
+    wall = time.perf_counter() - t0
+    if verbose:
+        pg = g["percentiles"]
+        print("guided, an update every %d node(s) of %d: gains and %d flights in %.1f ms; %d of them with status 0; nominal dv %.4f m/s" % (
+            guided, XC.shape[1], n_samples, wall * 1e3, int((g["status"] == 0).sum()), g["dv_nominal_ms"]))
+        print("  percentile   open loop [km]  [m/s]      guided [km]     [m/s]   dv excess [m/s]")
+        for q in (50, 95, 99):
+            print("  %9d  %14.4g  %9.4g  %12.4g  %9.4g  %12.4g" % (q, pc["miss_r_km"][q], pc["miss_v_ms"][q], pg["miss_r_km"][q],
+                                                                    pg["miss_v_ms"][q], pg["dv_excess_ms"][q]))
+    return nominal, out, g
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 4096)
+    args = sys.argv[1:]
+    guided = None
+    if "--guided" in args:
+        i = args.index("--guided")
+        guided = int(args[i + 1]) if i + 1 < len(args) and args[i + 1].isdigit() else 1
+        del args[i:i + (2 if i + 1 < len(args) and args[i + 1].isdigit() else 1)]
+    main(int(args[0]) if args else 4096, guided=guided)

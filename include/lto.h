@@ -9,7 +9,8 @@
  * two Julia drivers binds instead of running the closures' serial `for i = 1:n_nodes-1` loops
  * (INTEGRATION.md shows the Julia side).  Plain C: pointers, ints and doubles only.
  * Beyond the closures the library carries the drivers' loops and what they feed (Newton solves, QP steps, re-meshes, dense
- * output, thrust events) and the replay of a solution's thrust history from dispersed starts (lto_control_replay_batch).
+ * output, thrust events) and the replay of a solution's thrust history from dispersed starts (lto_control_replay_batch), and
+ * neighbouring-extremal guidance about a solution (lto_guidance_gains_batch, lto_guided_flight_batch).
  *
  * Conventions
  *   - All floating point data is binary64.  Host arrays use the reference's Julia layouts
@@ -857,6 +858,49 @@ int lto_control_replay_batch(lto_ctx* ctx, int nstate, int n_knots, int n_batch,
 int lto_control_replay(lto_ctx* ctx, int nstate, int n_knots, double t0, double t1, const double* lamv, const double* x0,
                        const lto_params* prm, const lto_integrator* integ, int sample_every, double* x_final, double* X_samples,
                        double* dv, int* accepted, int* rejected, int* status);
+
+/* Neighbouring-extremal guidance: the first-order optimal feedback about a converged 12-row solution with a fixed
+ * arrival state.  ndim must be 12: 14-row input (the variable-mass system) is refused with LTO_EUNSUPPORTED -- the mass row is not
+ * built -- and so is every method but LTO_RK4 and LTO_DOP853_ADAPTIVE.
+ * Gains.  XC [12 x n_nodes x n_batch], t [n_nodes x n_tgrids], prm and integ as in lto_indirect_events_batch.  The call runs the STM
+ * sweep of lto_indirect_jacobian on a plan of its own (the kernel LTO_KERNEL_AUTO picks) and, with Phi_k = d y(t_{k+1}) / d y(t_k)
+ * cut into 6 x 6 blocks A = Phi[0:6,0:6], B = Phi[0:6,6:12], C = Phi[6:12,0:6], D = Phi[6:12,6:12], the backward sweep
+ *   K_{n-2} = -B^-1 A,   K_k = (D - K_{k+1} B)^-1 (K_{k+1} A - C),  k = n-3 .. 0,
+ * every solve an LU with partial (row) pivoting and six right-hand sides: d lambda_k = K_k d x_k keeps the linearised arrival state
+ * where it is.  Outputs: K [6 x 6 x (n_nodes-1) x n_batch] column-major blocks;  pivot [(n_nodes-1) x n_batch] (may be NULL) = the
+ * smallest |u_ii| over the largest |entry| of the matrix solved at that node;  status[b]: 0 ok;  2 a non-finite Phi or gain;  3 a
+ * node's pivot ratio is below sing_tol -- a state of the problem, not an error: for p = 0 the costate's scale is a null direction of
+ * B, and so it is for p = 1 with a sharp switch while the law is saturated over the last segment (fully on or off: the thrust
+ * magnitude no longer answers to the costate, so the arrival state is not controllable to first order).  On status 2 and 3
+ * the gains of the failing node and of every earlier node are NaN, the later ones are valid (pivot: the failing node's ratio -- NaN
+ * where the block itself is not finite -- and NaN before it); no other trajectory is affected, and a trajectory's gains are bit for
+ * bit those of its single call.  LTO_ENULL; LTO_EINVAL (n_nodes < 2, n_batch < 1, t not strictly increasing, n_tgrids or n_prm not 1
+ * or n_batch, sing_tol not in (0, 1)). */
+int lto_guidance_gains_batch(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                             const lto_params* prm, int n_prm, const lto_integrator* integ, double sing_tol, double* K,
+                             double* pivot, int* status);
+int lto_guidance_gains(lto_ctx* ctx, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                       const lto_integrator* integ, double sing_tol, double* K, double* pivot, int* status);
+/* Guided flight.  The nominal XC_nom [12 x n_nodes x n_nom] with its node times t [n_nodes x n_nom] and gains K [6 x 6 x
+ * (n_nodes-1) x n_nom], n_nom = 1 (one nominal for every start) or n_batch;  x0 [6 x n_batch] the starts;  nav [6 x n_upd x
+ * n_batch] or NULL, n_upd = (n_nodes-2) / update_every + 1: the navigation error added to the measured state at update j.  A start
+ * carries y = (x, lambda, q), q' = umag (the 13 components of the thrust-event sweep), lambda(t_0) = lambda_nom,0.  For
+ * k = 0 .. n_nodes-2:  if update_every > 0 and k % update_every == 0, lambda <- lambda_nom,k + K_k (x - x_nom,k + e_j),
+ * j = k / update_every, otherwise lambda runs on by its own equation;  then y is integrated over [t_k, t_{k+1}] as a span of its own
+ * with LTO_DOP853_ADAPTIVE (all 13 components in the error norm; max_steps counts per span) or LTO_RK4 (`steps` steps per span).
+ * update_every = 0 never updates: the plain 12-row flow from (x0, lambda_nom,0).
+ * Out: x_final [6 x B];  lam_final [6 x B] (may be NULL);  dv [B] (DU/TU) the sum of the spans' q;  X_nodes [6 x n_nodes x B] (may
+ * be NULL): node 0 is x0 and the last node x_final, bit for bit;  accepted / rejected [B] summed over the spans (either may be
+ * NULL);  status[b]: 0 ok;  2 a non-finite input, state or applied gain, or a span out of max_steps: x_final, lam_final, dv and the
+ * nodes behind the failing span's start are NaN, no other start is affected.  n_prm is 1 or n_batch.  LTO_ENULL; LTO_EINVAL
+ * (n_nodes < 2, n_batch < 1, n_nom or n_prm not 1 or n_batch, update_every < 0, t not strictly increasing). */
+int lto_guided_flight_batch(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, const double* XC_nom, const double* t, const double* K,
+                            int n_nom, const double* x0, int update_every, const double* nav, const lto_params* prm, int n_prm,
+                            const lto_integrator* integ, double* x_final, double* lam_final, double* dv, double* X_nodes,
+                            int* accepted, int* rejected, int* status);
+int lto_guided_flight(lto_ctx* ctx, int ndim, int n_nodes, const double* XC_nom, const double* t, const double* K, const double* x0,
+                      int update_every, const double* nav, const lto_params* prm, const lto_integrator* integ, double* x_final,
+                      double* lam_final, double* dv, double* X_nodes, int* accepted, int* rejected, int* status);
 
 int lto_direct_plan_create(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, int nsteps,
                            const lto_direct_params* prm, lto_direct_plan** out);

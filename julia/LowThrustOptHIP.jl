@@ -18,7 +18,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
        direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
-       LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf,
+       LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
 const liblto = get(ENV, "LTO_HIP_LIB", joinpath(@__DIR__, "..", "lowthrustopt_amd", "liblto_hip.so"))
@@ -527,6 +527,48 @@ function control_replay(ctx::LtoContext, x0::Matrix{Float64}, lamv::Array{Float6
     check(ctx, rc)
     (x_final = x_final, dv = dv, accepted = Int.(accepted), rejected = Int.(rejected), status = Int.(status),
      samples = ns > 0 ? samples : nothing)
+end
+
+"""Neighbouring-extremal feedback gains (`lto_guidance_gains_batch`, DESIGN 4.23) of the 12-row solutions `XC` [12 x n x B] on the
+grids `t` [n x n_tgrids] (n_tgrids = 1 or B): the segment STMs are swept on the device and turned into gains by the backward
+recurrence that keeps the linearised arrival state fixed.  Returns the named tuple (K [6 x 6 x (n-1) x B] with
+d lambda_k = K[:, :, k, b] d x_k, pivot [(n-1) x B], status [B]: 0 ok, 2 not finite, 3 a pivot ratio below sing_tol -- K is NaN from
+that node down to node 0)."""
+function guidance_gains(ctx::LtoContext, XC::Array{Float64,3}, t::Matrix{Float64}, params::Vector;
+                        sing_tol::Real = 1e-10, integ::LtoIntegrator = LtoIntegrator())
+    ndim, n, B = size(XC)
+    prm = [LtoParams(q) for q in params]
+    K = zeros(6, 6, n - 1, B); pivot = zeros(n - 1, B); status = zeros(Cint, B)
+    rc = ccall((:lto_guidance_gains_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Cdouble,
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, ndim, n, B, XC, t, size(t, 2), prm, length(prm), Ref(integ), Float64(sing_tol), K, pivot, status)
+    check(ctx, rc)
+    (K = K, pivot = pivot, status = Int.(status))
+end
+
+"""Guided flight (`lto_guided_flight_batch`, DESIGN 4.23): the starts `x0` [6 x B] flown about the nominal `XC_nom` [12 x n x n_nom]
+with node times `t` [n x n_nom] and gains `K` [6 x 6 x (n-1) x n_nom] (n_nom = 1 or B).  At node k with k % update_every == 0 the
+costate is reset to lambda_nom,k + K_k (x - x_nom,k + e_j), e_j = nav[:, j, b] (`nav` [6 x n_upd x B] or `nothing`);
+update_every = 0 never updates.  Returns the named tuple (x_final, lam_final [6 x B], dv [B] in DU/TU, nodes [6 x n x B],
+accepted, rejected, status [B])."""
+function guided_flight(ctx::LtoContext, XC_nom::Array{Float64,3}, t::Matrix{Float64}, K::Array{Float64,4}, x0::Matrix{Float64},
+                       params::Vector; update_every::Integer = 1, nav::Union{Nothing,Array{Float64,3}} = nothing,
+                       integ::LtoIntegrator = LtoIntegrator())
+    ndim, n, n_nom = size(XC_nom)
+    B = size(x0, 2)
+    prm = [LtoParams(q) for q in params]
+    x_final = zeros(6, B); lam_final = zeros(6, B); dv = zeros(B); nodes = zeros(6, n, B)
+    accepted = zeros(Cint, B); rejected = zeros(Cint, B); status = zeros(Cint, B)
+    rc = ccall((:lto_guided_flight_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+                Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint},
+                Ptr{Cint}, Ptr{Cint}),
+               ctx.handle, ndim, n, B, XC_nom, t, K, n_nom, x0, update_every, nav === nothing ? C_NULL : nav, prm, length(prm),
+               Ref(integ), x_final, lam_final, dv, nodes, accepted, rejected, status)
+    check(ctx, rc)
+    (x_final = x_final, lam_final = lam_final, dv = dv, nodes = nodes, accepted = Int.(accepted), rejected = Int.(rejected),
+     status = Int.(status))
 end
 
 # ---------------------------------------------------------------------------------------------- direct

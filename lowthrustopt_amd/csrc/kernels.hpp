@@ -156,6 +156,38 @@ struct ReplayArgs {
 };
 // nstate 6 or 7, method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
 hipError_t launch_control_replay(int nstate, int pm, int method, const IndirectArgs& a, const ReplayArgs& r, hipStream_t st);
+// Neighbouring-extremal guidance (kernels_guidance.hip).  The backward sweep over the segment STMs of a 12-row sweep:
+// Phi [144][ldp] (col * 12 + row, segment b (n_nodes - 1) + k); K [36][(n_nodes - 1) n_batch] = the caller's [6 x 6 x (n-1) x B].
+struct GainsArgs {
+  const double* Phi; long ldp;
+  int n_nodes, n_batch;
+  double sing_tol;
+  double* K;
+  double* pivot;                   // [(n_nodes - 1) n_batch] or null
+  int* status;                     // [n_batch]: 0 ok, 2 not finite, 3 a pivot ratio below sing_tol
+};
+hipError_t launch_guidance_gains(const GainsArgs& g, hipStream_t st);
+// The guided flight: of `a` it reads tp / tp_stride, steps, rtol, atol and max_steps (max_steps per node interval).  Everything is
+// laid out [row][lanes]: nom row k 12 + c, K row k 36 + r + 6 c and t row k over n_nom = 1 or n_batch columns; x0 row c, nav row
+// j 6 + c, x_final / lam_final row c and nodes row k 6 + c over n_batch columns.
+struct GuidedArgs {
+  const double* nom; const double* K; const double* t; int n_nom;
+  int n_nodes, n_batch;
+  int every;                       // update cadence in nodes, 0: never
+  const double* x0;
+  const double* nav;               // or null
+  double* x_final;
+  double* lam_final;               // or null
+  double* dv;                      // [n_batch]
+  double* nodes;                   // or null
+  int* nacc; int* nrej;            // [n_batch], summed over the intervals
+  int* status;                     // [n_batch]: 0 ok, 2 not finite / an interval out of max_steps
+};
+// method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
+hipError_t launch_guided_flight(int pm, int method, const IndirectArgs& a, const GuidedArgs& g, hipStream_t st);
+// the caller's column-major [rows x count] <-> [row][count], any number of rows
+hipError_t launch_rows_to_lanes(const double* aos, long rows, long count, double* soa, hipStream_t st);
+hipError_t launch_lanes_to_rows(const double* soa, long rows, long count, double* aos, hipStream_t st);
 // wave-specialised STM kernel (kernels_indirect_coop.hip): base wave + column waves per 16 segments
 hipError_t launch_indirect_stm_coop(int ndim, int pm, int method, const IndirectArgs& a, hipStream_t st);
 // the same with every 12-component state split over two lanes (kernels_indirect_coop2.hip), DOP853 adaptive only; the 14-dim form

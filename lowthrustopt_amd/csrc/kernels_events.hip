@@ -25,25 +25,7 @@ namespace lto {
 
 namespace {
 
-// The augmented system: the lean base RHS of the defect-only sweeps and of k_indirect_dense, and q' = umag as that RHS forms it.
-template <int PM>
-struct SysEvents {
-  static constexpr int DIM = 13;
-  TrajParams tp;
-  __device__ __forceinline__ void rhs(const double (&y)[13], double (&k)[13]) const {
-    double yb[12], kb[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) yb[i] = y[i];
-    rhs12_base<PM>(yb, tp, kb);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) k[i] = kb[i];
-    const double n2 = __builtin_fma(y[9], y[9], __builtin_fma(y[10], y[10], y[11] * y[11]));
-    const double inv_n = inv_norm_guarded(n2);
-    double m, ua;
-    control_base12<PM>(tp, n2 * inv_n, inv_n, m, ua);
-    k[12] = m;
-  }
-};
+// SysEvents, the augmented system (y[12], q), is in indirect_kernel.hpp: the guided flight (kernels_guidance.hip) integrates it too.
 
 // Threshold of the event function g = |lambda_v| - thr: p = 1: 1 (more than half thrust); p > 1: p aL^(p-1) (clamped at the limit)
 template <int PM>

@@ -1464,6 +1464,97 @@ def dispersion(ctx, XC_all, t_TU, prm, n_samples, sigma_r_km, sigma_v_ms, seed, 
     return out
 
 
+def neighbouring_gains(ctx, XC_all, t_TU, prm, integ=None, sing_tol=1e-10):
+    """Neighbouring-extremal feedback gains of 12-row solutions (hotpath.guidance_gains): XC_all [12 x n] or
+    [12 x n x B] with its grid and parameters.  Returns a dict: K [6 x 6 x (n-1) (x B)], pivot, status, and ok = status == 0."""
+    g = hotpath.guidance_gains(XC_all, t_TU, prm, integ, sing_tol, ctx)
+    return dict(K=g.K, pivot=g.pivot, status=g.status, ok=np.asarray(g.status) == 0)
+
+
+def guided_nav(n_updates, n_samples, nav_sigma_r_km, nav_sigma_v_ms, seed, DU, TU):
+    """nav [6 x n_updates x n_samples]: Gaussian navigation errors of nav_sigma_r_km per position axis and nav_sigma_v_ms per
+    velocity axis from numpy.random.default_rng(seed); sample 0 navigates without error."""
+    rng = np.random.default_rng(seed)
+    e = rng.standard_normal((6, int(n_updates), int(n_samples)))
+    e[0:3] *= float(nav_sigma_r_km) / DU
+    e[3:6] *= float(nav_sigma_v_ms) / 1e3 * TU / DU
+    e[:, :, 0] = 0.0
+    return np.asfortranarray(e)
+
+
+def fly_guided(ctx, XC_all, t_TU, prm, x0=None, n_guid=None, update_every=1, nav=None, integ=None):
+    """Fly a 12-row indirect solution with neighbouring-extremal feedback from given starts (hotpath.guidance_gains and
+    hotpath.guided_flight).  XC_all [12 x n] with its grid t_TU and its parameters prm (LtoParams or the 8-tuple).
+    n_guid resamples the solution onto that many even nodes with hotpath.densify first -- an extremal sampled more finely is still
+    an extremal, and that is how more frequent updates are had.  The costate is updated at every update_every-th node (0: never,
+    the open-loop flow of the start's state under the nominal's first costate); nav [6 x n_upd (x B)] is added to the measured state
+    at the updates.  x0 [6 x B] (default: the solution's own first node).  Returns a dict: x_final, lam_final, miss_r_km and
+    miss_v_ms against the solution's last node, dv (DU/TU), dv_ms, dv_nominal_ms (the guided flight of the nominal start without
+    navigation error), dv_excess_ms = dv_ms - dv_nominal_ms, status, accepted, rejected, K, pivot, gain_status, XC_guid, t_guid."""
+    XC = np.asarray(XC_all, dtype=np.float64)
+    if XC.ndim != 2 or XC.shape[0] != 12:
+        raise ValueError("XC_all must be [12 x n]: guidance is built for 12-row solutions")
+    t = np.asarray(t_TU, dtype=np.float64)
+    if t.shape != (XC.shape[1],):
+        raise ValueError("t_TU must hold one time per node")
+    p = prm if isinstance(prm, hotpath.LtoParams) else hotpath.make_params(*prm)
+    if n_guid is not None:
+        if int(n_guid) < 2:
+            raise ValueError("n_guid must be >= 2")
+        XC, t = hotpath.densify(XC, t, p, int(n_guid), integ, ctx)
+    n = XC.shape[1]
+    n_upd = hotpath.guided_updates(n, update_every)
+    x0 = XC[:6, :1].copy() if x0 is None else np.asarray(x0, dtype=np.float64).reshape(6, -1)
+    B = x0.shape[1]
+    if nav is not None:
+        nav = np.asarray(nav, dtype=np.float64)
+        if nav.shape not in ((6, n_upd), (6, n_upd, B)):
+            raise ValueError("nav must be [6 x %d] or [6 x %d x %d]" % (n_upd, n_upd, B))
+        if nav.ndim == 2:
+            nav = np.repeat(nav[:, :, None], B, axis=2)
+    g = hotpath.guidance_gains(XC, t, p, integ, ctx=ctx)
+    if int(update_every) > 0 and g.status != 0:
+        raise ValueError("the solution has no finite gains (status %d, smallest pivot ratio %.3g): fly it with update_every = 0"
+                         % (g.status, np.nanmin(g.pivot)))
+    K = g.K if g.status == 0 else np.zeros_like(g.K)
+    x_all = np.concatenate([XC[:6, :1], x0], axis=1)         # column 0: the nominal start, the reference of the dv excess
+    nav_all = None if nav is None else np.concatenate([np.zeros((6, n_upd, 1)), nav], axis=2)
+    r = hotpath.guided_flight(XC, t, K, x_all, p, update_every, nav_all, integ, ctx=ctx)
+    dv_ms = r.dv * p.DU / p.TU * 1e3
+    out = dict(x_final=r.x_final[:, 1:], lam_final=r.lam_final[:, 1:], dv=r.dv[1:], dv_ms=dv_ms[1:], dv_nominal_ms=float(dv_ms[0]),
+               dv_excess_ms=dv_ms[1:] - dv_ms[0], status=r.status[1:], accepted=r.accepted[1:], rejected=r.rejected[1:], K=g.K,
+               pivot=g.pivot, gain_status=g.status, XC_guid=XC, t_guid=t)
+    out.update(replay_misses(out["x_final"], XC[:6, -1], p.DU, p.TU))
+    return out
+
+
+def dispersion_guided(ctx, XC_all, t_TU, prm, n_samples, sigma_r_km, sigma_v_ms, seed, n_guid=None, update_every=1, integ=None,
+                      nav_sigma_r_km=None, nav_sigma_v_ms=None, nav_seed=None):
+    """Monte-Carlo dispersion of a 12-row indirect solution flown with neighbouring-extremal feedback: the starts of `dispersion`
+    (the same dispersion_starts draws, sample 0 undisturbed), all flown by fly_guided in one call, so the two runs compare sample
+    by sample.  nav_sigma_r_km / nav_sigma_v_ms (both or neither) add Gaussian navigation errors from
+    numpy.random.default_rng(nav_seed) at every update (guided_nav).  Returns fly_guided's dict plus x0, nav and, over the samples
+    of status 0, percentiles = {"miss_r_km": {50: .., 95: .., 99: ..}, "miss_v_ms": {..}, "dv_excess_ms": {..}}."""
+    XC = np.asarray(XC_all, dtype=np.float64)
+    if XC.ndim != 2 or XC.shape[0] != 12:
+        raise ValueError("XC_all must be [12 x n]: guidance is built for 12-row solutions")
+    if (nav_sigma_r_km is None) != (nav_sigma_v_ms is None):
+        raise ValueError("nav_sigma_r_km and nav_sigma_v_ms are given together")
+    p = prm if isinstance(prm, hotpath.LtoParams) else hotpath.make_params(*prm)
+    x0 = dispersion_starts(XC[:6, 0], n_samples, sigma_r_km, sigma_v_ms, seed, p.DU, p.TU)
+    nav = None
+    if nav_sigma_r_km is not None:
+        n_upd = hotpath.guided_updates(XC.shape[1] if n_guid is None else int(n_guid), update_every)
+        nav = guided_nav(n_upd, n_samples, nav_sigma_r_km, nav_sigma_v_ms, nav_seed, p.DU, p.TU)
+    out = fly_guided(ctx, XC, t_TU, p, x0, n_guid, update_every, nav, integ)
+    ok = np.asarray(out["status"]) == 0
+    out["x0"] = x0
+    out["nav"] = nav
+    out["percentiles"] = {k: {q: (float(np.percentile(out[k][ok], q)) if ok.any() else float("nan")) for q in (50, 95, 99)}
+                          for k in ("miss_r_km", "miss_v_ms", "dv_excess_ms")}
+    return out
+
+
 def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, maxIter=10, max_waves=12, ctx=None, verbose=True,
                    arcs=False):
     """Solve the whole smoothing ladder rho_0 > rho_1 > ... concurrently.  reduceFuel_indirect walks the

@@ -38,6 +38,8 @@ def make_params(MU, DU, TU, thrustLimit, mass, time_direction, p, rho):
 def _params_array(params):
     if isinstance(params, LtoParams):
         params = [params]
+    elif isinstance(params, tuple) and len(params) == 8 and np.isscalar(params[0]):   # the bare 8-tuple
+        params = [make_params(*params)]
     params = [p if isinstance(p, LtoParams) else make_params(*p) for p in params]
     arr = (LtoParams * len(params))(*params)
     return arr, len(params)
@@ -719,6 +721,102 @@ def control_replay(x0, lamv, t0, t1, params, integ=None, sample_every=0, ctx=Non
         return ControlReplay(x_final[:, 0], float(dv[0]), int(acc[0]), int(rej[0]), int(status[0]),
                              None if samples is None else samples[:, :, 0], knots)
     return ControlReplay(x_final, dv, acc, rej, status, samples, knots)
+
+
+class GuidanceGains:
+    """Result of guidance_gains; B trajectories (batched) or one (the batch axis dropped): K [6 x 6 x (n-1) x B] with
+    d lambda_k = K[:, :, k] d x_k, pivot [(n-1) x B] (smallest |u_ii| over the largest |entry| of the matrix solved at that node),
+    status [B] (0 ok, 2 not finite, 3 a pivot ratio below sing_tol: K is NaN from that node down to node 0)."""
+
+    def __init__(self, K, pivot, status):
+        self.K, self.pivot, self.status = K, pivot, status
+
+
+def guidance_gains(XC_all, t_TU, params, integ=None, sing_tol=1e-10, ctx=None):
+    """Neighbouring-extremal feedback gains of 12-row solutions (lto_guidance_gains_batch): XC_all [12 x n] or
+    [12 x n x B], t_TU [n] or [n x B], params one tuple or one per trajectory.  The segment STMs are swept on the device (LTO_RK4 or
+    LTO_DOP853_ADAPTIVE) and turned into gains by the backward recurrence that keeps the linearised arrival state fixed.  14-row
+    input is refused (LtoError -3).  Returns a GuidanceGains."""
+    ctx, (ndim, n, B, batched), args = _indirect_args(XC_all, t_TU, params, integ, ctx)
+    S = max(n - 1, 0)
+    K = np.zeros((6, 6, S, B), order="F")
+    pivot = np.zeros((S, B), order="F")
+    status = np.zeros(B, dtype=np.int32)
+    ctx.check(ctx.fn("guidance_gains_batch")(*args, float(sing_tol), _ptr(K), _ptr(pivot), _ptr(status)))
+    if not batched:
+        return GuidanceGains(K[:, :, :, 0], pivot[:, 0], int(status[0]))
+    return GuidanceGains(K, pivot, status)
+
+
+class GuidedFlight:
+    """Result of guided_flight; B starts (batched) or one (the batch axis dropped): x_final and lam_final [6 x B], dv [B] (DU/TU),
+    nodes [6 x n x B] (the state at every node; None unless asked for), accepted / rejected [B] (steps summed over the node
+    intervals), status [B] (0 ok, 2 no result: NaN)."""
+
+    def __init__(self, x_final, lam_final, dv, nodes, accepted, rejected, status):
+        self.x_final, self.lam_final, self.dv, self.nodes = x_final, lam_final, dv, nodes
+        self.accepted, self.rejected, self.status = accepted, rejected, status
+
+
+def guided_updates(n_nodes, update_every):
+    """Number of updates of a guided flight: the nodes k <= n_nodes - 2 with k % update_every == 0; none for update_every = 0."""
+    n, every = int(n_nodes), int(update_every)
+    if every < 0:
+        raise ValueError("update_every must be >= 0")
+    return (n - 2) // every + 1 if every > 0 and n >= 2 else 0
+
+
+def guided_flight(XC_nom, t_TU, K, x0, params, update_every=1, nav=None, integ=None, with_nodes=False, ctx=None):
+    """Fly starts under neighbouring-extremal feedback about a nominal (lto_guided_flight_batch): XC_nom [12 x n] with
+    t_TU [n] and K [6 x 6 x (n-1)] (one nominal for every start) or [12 x n x B], [n x B], [6 x 6 x (n-1) x B] (one per start); x0 [6]
+    or [6 x B]; nav [6 x n_upd] / [6 x n_upd x B] or None, n_upd = guided_updates(n, update_every): the navigation error added to
+    the measured state at update j; params one tuple or one per start.  At node k with k % update_every == 0 the costate is reset
+    to lambda_nom,k + K_k (x - x_nom,k + e_j); update_every = 0 never updates.  Returns a GuidedFlight."""
+    X = _f64(x0)
+    if X.ndim not in (1, 2) or X.shape[0] != 6:
+        raise ValueError("x0 must be [6] or [6 x B]")
+    batched = X.ndim == 2
+    X2 = np.asfortranarray(X.reshape(6, -1, order="F"))
+    B = X2.shape[1]
+    XC = _f64(XC_nom)
+    if XC.ndim not in (2, 3):
+        raise ValueError("XC_nom must be [ndim x n] or [ndim x n x n_nom]")
+    XC3 = np.asfortranarray(XC.reshape(XC.shape[0], XC.shape[1], -1, order="F"))
+    ndim, n, n_nom = XC3.shape
+    if n_nom != 1 and n_nom != B:
+        raise ValueError("XC_nom must hold one nominal or one per start")
+    t = _f64(t_TU)
+    if t.size != n * n_nom or t.shape[0] != n:
+        raise ValueError("t_TU must be [n] or [n x n_nom]")
+    t = np.asfortranarray(t.reshape(n, n_nom, order="F"))
+    Kg = _f64(K)
+    if Kg.size != 36 * max(n - 1, 0) * n_nom or Kg.shape[:2] != (6, 6):
+        raise ValueError("K must be [6 x 6 x (n-1)] or [6 x 6 x (n-1) x n_nom]")
+    Kg = np.asfortranarray(Kg.reshape(6, 6, n - 1, n_nom, order="F"))
+    every = int(update_every)
+    n_upd = guided_updates(n, every)
+    E = None
+    if nav is not None and n_upd > 0:
+        E = _f64(nav)
+        if E.shape[0] != 6 or E.size != 6 * n_upd * B:
+            raise ValueError("nav must be [6 x n_upd x B] with n_upd = %d" % n_upd)
+        E = np.asfortranarray(E.reshape(6, n_upd, B, order="F"))
+    prm, nprm = _params_array(params)
+    if nprm != 1 and nprm != B:
+        raise ValueError("params must be one tuple or one per start")
+    x_final, lam_final = np.zeros((6, B), order="F"), np.zeros((6, B), order="F")
+    dv = np.zeros(B)
+    nodes = np.zeros((6, n, B), order="F") if with_nodes else None
+    acc, rej, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    ctx.check(ctx.fn("guided_flight_batch")(ctx.handle, ndim, n, B, _ptr(XC3), _ptr(t), _ptr(Kg), n_nom, _ptr(X2), every, _ptr(E), prm,
+                                            nprm, C.byref(integ), _ptr(x_final), _ptr(lam_final), _ptr(dv), _ptr(nodes), _ptr(acc),
+                                            _ptr(rej), _ptr(status)))
+    if not batched:
+        return GuidedFlight(x_final[:, 0], lam_final[:, 0], float(dv[0]), None if nodes is None else nodes[:, :, 0], int(acc[0]),
+                            int(rej[0]), int(status[0]))
+    return GuidedFlight(x_final, lam_final, dv, nodes, acc, rej, status)
 
 
 def direct_defectCalc(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None):
