@@ -485,22 +485,40 @@ __device__ __forceinline__ void pipe8_role_columns(const IndirectArgs& a, const 
                                                    double* s_coef, Pipe8Flags* fl, const int wave) {
   using P = Pipe8<ND, PM>;
   constexpr int SD = P::SD;
-  const int steps = a.steps, npairs = (steps + 1) >> 1;
+  const int steps = a.steps;                                 // (steps + 1) / 2 + 1 phases, one barrier each
   const ColStepConst k(L.h, L.w2);
   const double* rec = s_coef + CoefBySegment::lane_base(col, seg);
   double y[ND];
 #pragma unroll
   for (int r = 0; r < ND; ++r) y[r] = (r == col) ? 1.0 : 0.0;
+  const bool role_on = PIPE_ROLE_ON(a, 4) && PIPE_ROLE_ON(a, wave == 7 ? 64 : 8);      // probe build: role switches per wave
   P8_WAIT_DECL;
-  for (int p = 0; p < npairs + 1; ++p) {
-    if (p >= 1 && PIPE_ROLE_ON(a, 4) && PIPE_ROLE_ON(a, wave == 7 ? 64 : 8)) {      // probe build: role switches per wave
+  P8_SYNC();                                                 // the fill phase
+  // Full phases: ONE divergent region around both steps, y -> z -> y, straight line.  A join between the steps, or a step in
+  // place, would have the new column take the registers of the old one while that is still being read -- ND copies per step
+  // (pipe_common.hpp, col_dpp_step).
+  for (int p = 1; p <= steps / 2; ++p) {
+    if (role_on) {
       const int s0 = 2 * p - 2, s1 = 2 * p - 1;
-      if (col < P::NA) col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rec + ((s0 & 3) * 4) * SD, k, s0, y);   // spare lanes stay off: never DPP sources
-      if (s1 < steps) {
+      if (col < P::NA) {                                     // spare lanes stay off: never DPP sources
+        double z[ND];
+        col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rec + ((s0 & 3) * 4) * SD, k, y, z);
+        // The poll now shares a basic block with the even step, and the scheduler (max-ilp) would issue its first load at the top
+        // of that block -- a phase too early for the flag, so every phase would go through the sleeping loop.  The empty asm is a
+        // memory barrier that needs a finished row of z: the load stays behind the whole even step, where it was.
+#pragma unroll
+        for (int r = 0; r < ND; ++r) asm volatile("" : "+v"(z[r]) : : "memory");
         if (PIPE_ROLE_ON(a, 2)) p8_wait_for(&fl->coef_steps, s1 + 1, &fl->fail);
-        if (col < P::NA) col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rec + ((s1 & 3) * 4) * SD, k, s1, y);
+        col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rec + ((s1 & 3) * 4) * SD, k, z, y);
+        if (col_rescale_due(s1)) col_rescale(y);             // (never due after the even step)
       }
     }
+    P8_SYNC();
+  }
+  // An odd number of steps: the last phase has one, in place.  Kept out of the loop: as a branch inside it, z would be alive on a
+  // path round the odd step, which then could not use z's registers up in its third stage.
+  if (steps & 1) {
+    if (role_on && col < P::NA) col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rec + (((steps - 1) & 3) * 4) * SD, k, steps - 1, y);
     P8_SYNC();
   }
   P8_WAIT_REPORT(a);
@@ -531,41 +549,51 @@ __device__ __forceinline__ void pipe8_role_columns_alt(const IndirectArgs& a, co
   // against 2 x 17.5) -- the hand-over is 10 % of a step on the two SIMDs that share this job
   static_assert(ND % 2 == 0, "pairs of rows");
   p8_d2* hand2 = reinterpret_cast<p8_d2*>(s_hand);
-  auto load = [&]() {
-    if (on) {
+  auto load = [&](double (&v)[ND]) {
 #pragma unroll
-      for (int q = 0; q < ND / 2; ++q) { const p8_d2 v = hand2[q * 64 + lane]; y[2 * q] = v.x; y[2 * q + 1] = v.y; }
-    }
+    for (int q = 0; q < ND / 2; ++q) { const p8_d2 t = hand2[q * 64 + lane]; v[2 * q] = t.x; v[2 * q + 1] = t.y; }
   };
-  auto store = [&]() {
-    if (on) {
+  auto store = [&](const double (&v)[ND]) {
 #pragma unroll
-      for (int q = 0; q < ND / 2; ++q) hand2[q * 64 + lane] = p8_d2{y[2 * q], y[2 * q + 1]};
-    }
+    for (int q = 0; q < ND / 2; ++q) hand2[q * 64 + lane] = p8_d2{v[2 * q], v[2 * q + 1]};
   };
-  if (!ODD) __builtin_amdgcn_s_setprio(2);
+  // The column lives in s_hand between the steps -- w4 puts the unit vectors there before its first -- and in registers only
+  // inside a step: loaded into one set, advanced into another, stored from there.  Nothing is carried round the phase loop, so
+  // no register has to be handed back to where the next phase expects it.
+  if (!ODD) {
+    __builtin_amdgcn_s_setprio(2);
+    if (on) store(y);
+  }
   P8_WAIT_DECL;
   for (int p = 0; p < npairs + 1; ++p) {
     if (p >= 1 && PIPE_ROLE_ON(a, 4) && PIPE_ROLE_ON(a, 32)) {
       const int step = 2 * p - 2 + (ODD ? 1 : 0);
+      const double* rs = rec + ((step & 3) * 4) * SD;
       if (!ODD) {
-        if (p > 1) load();
-        if (on) col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rec + ((step & 3) * 4) * SD, k, step, y);
-        store();
+        if (on) {
+          double v[ND], o[ND];
+          load(v);
+          col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rs, k, v, o);      // even step: the rescale is never due
+          store(o);
+        }
         p8_signal(&fl->hand, p);
       } else if (step < steps) {
         if (PIPE_ROLE_ON(a, 2)) p8_wait_for(&fl->coef_steps, step + 1, &fl->fail);
         p8_wait_for(&fl->hand, p, &fl->fail);
-        load();
-        if (on) col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rec + ((step & 3) * 4) * SD, k, step, y);
-        store();
+        if (on) {
+          double v[ND], o[ND];
+          load(v);
+          col_dpp_step<ND, SD, P::Arg::LM, P::NA>(rs, k, v, o);
+          if (col_rescale_due(step)) col_rescale(o);
+          store(o);
+        }
       }
     }
     P8_SYNC();
   }
   P8_WAIT_REPORT(a);
   if (!ODD) {
-    load();
+    if (on) load(y);
     pipe8_store_column<ND, P::NA>(a, L, seg, col, y, fl->fail != 0, s_coef, 4, p8_wait);
   } else {
     p8_wait.stamp(0);

@@ -183,6 +183,7 @@ __device__ __forceinline__ void fmac_c(double& acc, const double cA, const doubl
 // The rows with coefficient products accumulate straight onto init (no separate slope, no separate RK update); the
 // Coriolis rows start with a plain FMA, the others with a copy of init.  Same formulas as var_col12 / var_col14.
 // LM = false (always-thrust-limited laws of the 14-dim system): d lambda_m_dot / d lambda_m = 0, that term is skipped.
+// `out` may be the same array as `init` (row c of out is formed from row c of init alone), not the same as `arg`.
 template <int ND, bool LM = true, int NA = ND>
 __device__ __forceinline__ void col_dpp_stage(const double cA, const double cB, const double aw2, const double a,
                                               const double (&arg)[ND], const double (&init)[ND], double (&out)[ND]) {
@@ -238,20 +239,46 @@ struct ColStepConst {
   double h2, h, h2w, hw;
   __device__ __forceinline__ ColStepConst(double hh, double w2) : h2(0.5 * hh), h(hh), h2w(0.5 * hh * w2), hw(hh * w2) {}
 };
+// Registers.  The step below is out of place: `y` is read up to the third stage (init) while the new column grows in B from the
+// first stage on, so the two cannot share registers, and wherever control flow makes the new column take the place of the old one
+// (a loop edge, the join behind a divergent `if`) the compiler has to copy ND doubles.  A caller that advances two steps between
+// such places ping-pongs -- y -> z -> y, straight line -- and pays no copy at all (kernels_indirect_pipe8.hip); the in-place form
+// further down is for one step per loop iteration.
 template <int ND, int SD, bool LM = true, int NA = ND>
-__device__ __forceinline__ void col_dpp_step(const double* rec, const ColStepConst& k, const int step, double (&y)[ND]) {
-  double B[ND], V1[ND], V2[ND], V3[ND];
+__device__ __forceinline__ void col_dpp_step(const double* rec, const ColStepConst& k, const double (&y)[ND], double (&out)[ND]) {
+  double V1[ND], V2[ND], V3[ND];
   col_dpp_stage<ND, LM, NA>(rec[0], rec[16], k.h2w, k.h2, y, y, V1);
 #pragma unroll
-  for (int c = 0; c < ND; ++c) B[c] = V1[c] - y[c];
+  for (int c = 0; c < ND; ++c) out[c] = V1[c] - y[c];
   col_dpp_stage<ND, LM, NA>(rec[SD], rec[SD + 16], k.h2w, k.h2, V1, y, V2);
 #pragma unroll
-  for (int c = 0; c < ND; ++c) B[c] = __builtin_fma(2.0, V2[c], B[c]);
+  for (int c = 0; c < ND; ++c) out[c] = __builtin_fma(2.0, V2[c], out[c]);
   col_dpp_stage<ND, LM, NA>(rec[2 * SD], rec[2 * SD + 16], k.hw, k.h, V2, y, V3);
 #pragma unroll
-  for (int c = 0; c < ND; ++c) B[c] += V3[c];
-  col_dpp_stage<ND, LM, NA>(rec[3 * SD], rec[3 * SD + 16], k.h2w, k.h2, V3, B, y);
-  if (((step + 1) & (COL_RESCALE_EVERY - 1)) == 0) {
+  for (int c = 0; c < ND; ++c) out[c] += V3[c];
+  col_dpp_stage<ND, LM, NA>(rec[3 * SD], rec[3 * SD + 16], k.h2w, k.h2, V3, out, out);
+}
+
+// Is the rescale due after step `step`?  Only ever after an odd step.
+static_assert(COL_RESCALE_EVERY % 2 == 0, "callers skip the test after even steps");
+__device__ __forceinline__ bool col_rescale_due(const int step) { return ((step + 1) & (COL_RESCALE_EVERY - 1)) == 0; }
+// y *= 3^-COL_RESCALE_EVERY where the registers are (the same v_mul_f64 the compiler emits, with a tied operand): written in C++ the
+// product lands in fresh registers, and the path that does NOT rescale -- 255 steps of 256 -- copies the column to meet it
+template <int ND>
+__device__ __forceinline__ void col_rescale(double (&y)[ND]) {
+  const double f = COL_RESCALE;
+#pragma unroll
+  for (int c = 0; c < ND; ++c) asm("v_mul_f64 %0, %0, %1" : "+v"(y[c]) : "s"(f));
+}
+
+// one step in place, rescale included (the new column is copied to where the old one was either way)
+template <int ND, int SD, bool LM = true, int NA = ND>
+__device__ __forceinline__ void col_dpp_step(const double* rec, const ColStepConst& k, const int step, double (&y)[ND]) {
+  double B[ND];
+  col_dpp_step<ND, SD, LM, NA>(rec, k, y, B);
+#pragma unroll
+  for (int c = 0; c < ND; ++c) y[c] = B[c];
+  if (col_rescale_due(step)) {
 #pragma unroll
     for (int c = 0; c < ND; ++c) y[c] *= COL_RESCALE;
   }
