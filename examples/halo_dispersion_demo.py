@@ -8,12 +8,17 @@ interval in one library call.  Prints the nominal replay's miss at the arrival n
 the dispersed misses.  The transfer is 20 days along an unstable orbit family and nothing corrects the flight: the misses show
 how fast an injection error grows, which is what a corrector would have to take out.
 
-  python examples/halo_dispersion_demo.py [n_samples] [--guided [update_every]]
+  python examples/halo_dispersion_demo.py [n_samples] [--guided [update_every]] [--mass]
 
 With --guided the same starts are also flown with neighbouring-extremal feedback (drivers.dispersion_guided ->
 lto_guidance_gains_batch, lto_guided_flight_batch): the costate is reset from the feedback gains at every
 update_every-th node of the solution (default 1), and the open-loop and guided percentiles are printed side by side with the
 dv the feedback costs over the nominal's.
+
+With --mass the transfer is the variable-mass one (14 rows, m0 = 1000 kg, Isp = 2000 s, free final mass:
+drivers.multiShoot_CRTBP_indirect_mass from the lifted p = 2 solution), the replay carries the mass, and --guided flies it through
+drivers.dispersion_guided_mass (lto_guidance_gains_mass_batch, lto_guided_flight_mass_batch): the table gains the
+propellant the feedback costs over the nominal's, in kg, read off the integrated mass.
 """
 import importlib.util
 import os
@@ -27,7 +32,7 @@ from lowthrustopt_amd import drivers  # noqa: E402
 from lowthrustopt_amd.constants import MU, DU, TU, day  # noqa: E402
 
 
-def main(n_samples=4096, sigma_r_km=1.0, sigma_v_ms=0.01, seed=0, n_knots=257, verbose=True, guided=None):
+def main(n_samples=4096, sigma_r_km=1.0, sigma_v_ms=0.01, seed=0, n_knots=257, verbose=True, guided=None, mass=False, Isp=2000.0):
     spec = importlib.util.spec_from_file_location("halo_demo", os.path.join(ROOT, "examples", "halo_transfer_demo.py"))
     demo = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(demo)
@@ -36,13 +41,20 @@ def main(n_samples=4096, sigma_r_km=1.0, sigma_v_ms=0.01, seed=0, n_knots=257, v
         raise RuntimeError("the p = 2 solve did not converge (status %d)" % flag)
     ctx = lto.default_context(0)
     prm = (MU, DU, TU, 10.0, 1e3, 1.0, 2.0, 1.0)
+    if mass:
+        XC, _, flag = drivers.multiShoot_CRTBP_indirect_mass(drivers.lift_to_mass(XC, 1e3), t, MU, DU, TU, XC.shape[1], Isp, 10.0, False,
+                                                             False, 50, 2.0, 1.0, verbose=False)
+        if flag != 0:
+            raise RuntimeError("the variable-mass p = 2 solve did not converge (status %d)" % flag)
+        prm = (MU, DU, TU, 10.0, Isp, 1.0, 2.0, 1.0)
     nominal = drivers.fly_control(ctx, XC, t, prm, n_knots=n_knots)
     t0 = time.perf_counter()
     out = drivers.dispersion(ctx, XC, t, prm, n_samples, sigma_r_km, sigma_v_ms, seed, n_knots=n_knots)
     wall = time.perf_counter() - t0
     if verbose:
         pc = out["percentiles"]
-        print("p = 2 transfer, tof %.3f days, %d knots; nominal replay: miss %.4g km, %.4g m/s, dv %.4f m/s" % (
+        print("p = 2 transfer%s, tof %.3f days, %d knots; nominal replay: miss %.4g km, %.4g m/s, dv %.4f m/s" % (
+            " with variable mass (Isp %g s, propellant %.4f kg)" % (Isp, XC[6, 0] - XC[6, -1]) if mass else "",
             (t[-1] - t[0]) * TU / day, n_knots, nominal["miss_r_km"][0], nominal["miss_v_ms"][0], nominal["dv_ms"][0]))
         print("%d starts, sigma %.3g km and %.3g m/s per axis, in %.1f ms; %d of them with status 0" % (
             n_samples, sigma_r_km, sigma_v_ms, wall * 1e3, int((out["status"] == 0).sum())))
@@ -52,16 +64,20 @@ def main(n_samples=4096, sigma_r_km=1.0, sigma_v_ms=0.01, seed=0, n_knots=257, v
     if guided is None:
         return nominal, out
     t0 = time.perf_counter()
-    g = drivers.dispersion_guided(ctx, XC, t, prm, n_samples, sigma_r_km, sigma_v_ms, seed, update_every=guided)
+    g = (drivers.dispersion_guided_mass if mass else drivers.dispersion_guided)(ctx, XC, t, prm, n_samples, sigma_r_km, sigma_v_ms, seed,
+                                                                                update_every=guided)
     wall = time.perf_counter() - t0
     if verbose:
         pg = g["percentiles"]
         print("guided, an update every %d node(s) of %d: gains and %d flights in %.1f ms; %d of them with status 0; nominal dv %.4f m/s" % (
             guided, XC.shape[1], n_samples, wall * 1e3, int((g["status"] == 0).sum()), g["dv_nominal_ms"]))
-        print("  percentile   open loop [km]  [m/s]      guided [km]     [m/s]   dv excess [m/s]")
+        if mass:
+            print("  nominal propellant %.6f kg (the guided flight of the nominal start)" % g["propellant_nominal_kg"])
+        print("  percentile   open loop [km]  [m/s]      guided [km]     [m/s]   dv excess [m/s]%s" % ("  propellant excess [kg]" if mass else ""))
         for q in (50, 95, 99):
-            print("  %9d  %14.4g  %9.4g  %12.4g  %9.4g  %12.4g" % (q, pc["miss_r_km"][q], pc["miss_v_ms"][q], pg["miss_r_km"][q],
-                                                                    pg["miss_v_ms"][q], pg["dv_excess_ms"][q]))
+            print("  %9d  %14.4g  %9.4g  %12.4g  %9.4g  %12.4g%s" % (q, pc["miss_r_km"][q], pc["miss_v_ms"][q], pg["miss_r_km"][q],
+                                                                      pg["miss_v_ms"][q], pg["dv_excess_ms"][q],
+                                                                      "  %18.4g" % pg["propellant_excess_kg"][q] if mass else ""))
     return nominal, out, g
 
 
@@ -72,4 +88,7 @@ if __name__ == "__main__":
         i = args.index("--guided")
         guided = int(args[i + 1]) if i + 1 < len(args) and args[i + 1].isdigit() else 1
         del args[i:i + (2 if i + 1 < len(args) and args[i + 1].isdigit() else 1)]
-    main(int(args[0]) if args else 4096, guided=guided)
+    mass = "--mass" in args
+    if mass:
+        args.remove("--mass")
+    main(int(args[0]) if args else 4096, guided=guided, mass=mass)

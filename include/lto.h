@@ -10,7 +10,7 @@
  * (INTEGRATION.md shows the Julia side).  Plain C: pointers, ints and doubles only.
  * Beyond the closures the library carries the drivers' loops and what they feed (Newton solves, QP steps, re-meshes, dense
  * output, thrust events) and the replay of a solution's thrust history from dispersed starts (lto_control_replay_batch), and
- * neighbouring-extremal guidance about a solution (lto_guidance_gains_batch, lto_guided_flight_batch).
+ * neighbouring-extremal guidance about a solution (lto_guidance_gains_batch, lto_guided_flight_batch, and their _mass forms).
  *
  * Conventions
  *   - All floating point data is binary64.  Host arrays use the reference's Julia layouts
@@ -860,8 +860,8 @@ int lto_control_replay(lto_ctx* ctx, int nstate, int n_knots, double t0, double 
                        double* dv, int* accepted, int* rejected, int* status);
 
 /* Neighbouring-extremal guidance: the first-order optimal feedback about a converged 12-row solution with a fixed
- * arrival state.  ndim must be 12: 14-row input (the variable-mass system) is refused with LTO_EUNSUPPORTED -- the mass row is not
- * built -- and so is every method but LTO_RK4 and LTO_DOP853_ADAPTIVE.
+ * arrival state.  ndim must be 12: 14-row input (the variable-mass system) is refused with LTO_EUNSUPPORTED -- it goes to
+ * lto_guidance_gains_mass_batch and lto_guided_flight_mass_batch below -- and so is every method but LTO_RK4 and LTO_DOP853_ADAPTIVE.
  * Gains.  XC [12 x n_nodes x n_batch], t [n_nodes x n_tgrids], prm and integ as in lto_indirect_events_batch.  The call runs the STM
  * sweep of lto_indirect_jacobian on a plan of its own (the kernel LTO_KERNEL_AUTO picks) and, with Phi_k = d y(t_{k+1}) / d y(t_k)
  * cut into 6 x 6 blocks A = Phi[0:6,0:6], B = Phi[0:6,6:12], C = Phi[6:12,0:6], D = Phi[6:12,6:12], the backward sweep
@@ -901,6 +901,37 @@ int lto_guided_flight_batch(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, co
 int lto_guided_flight(lto_ctx* ctx, int ndim, int n_nodes, const double* XC_nom, const double* t, const double* K, const double* x0,
                       int update_every, const double* nav, const lto_params* prm, const lto_integrator* integ, double* x_final,
                       double* lam_final, double* dv, double* X_nodes, int* accepted, int* rejected, int* status);
+/* The same for solutions of the 14-row variable-mass system: y = (x, lambda), x = (r, v, m), lambda = (lambda_r,
+ * lambda_v, lambda_m), prm.mass carries Isp [s] as everywhere for 14 rows.  The solve pins r_f, v_f and lambda_m(t_f) = 0 and leaves
+ * m_f free, so the gains keep d r_f = d v_f = 0 and d lambda_m(t_f) = 0: with Phi_k cut into 7 x 7 blocks A = Phi[0:7,0:7],
+ * B = Phi[0:7,7:14], C = Phi[7:14,0:7], D = Phi[7:14,7:14],
+ *   K_{n-2} = -M^-1 N,  M = rows 0..5 of B over row 6 of D,  N = rows 0..5 of A over row 6 of C,
+ *   K_k = (D - K_{k+1} B)^-1 (K_{k+1} A - C),  k = n-3 .. 0,
+ * every node one 7 x 7 system with seven right-hand sides, the matrix as it stands (no scaling).  XC [14 x n_nodes x n_batch];
+ * K [7 x 7 x (n_nodes-1) x n_batch];  pivot, status, sing_tol and the LTO_ENULL / LTO_EINVAL rules as lto_guidance_gains_batch.
+ * p = 0 and a law saturated over the whole last segment are singular (status 3) as in 12 rows.  Every method but LTO_RK4 and
+ * LTO_DOP853_ADAPTIVE: LTO_EUNSUPPORTED. */
+int lto_guidance_gains_mass_batch(lto_ctx* ctx, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                                  const lto_params* prm, int n_prm, const lto_integrator* integ, double sing_tol, double* K,
+                                  double* pivot, int* status);
+int lto_guidance_gains_mass(lto_ctx* ctx, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                            const lto_integrator* integ, double sing_tol, double* K, double* pivot, int* status);
+/* Guided flight of the 14-row system.  XC_nom [14 x n_nodes x n_nom], t [n_nodes x n_nom], K [7 x 7 x (n_nodes-1) x n_nom];
+ * x0 [7 x n_batch] (r, v, m);  nav [7 x n_upd x n_batch] or NULL.  A start carries (x[7], lambda[7], q), q' = umag, the 15 components
+ * of lto_indirect_events_mass_batch, all in LTO_DOP853_ADAPTIVE's error norm; the update resets all seven costates,
+ * lambda <- lambda_nom,k + K_k (x - x_nom,k + e_j), the measured mass included.  Spans, update_every, accepted / rejected and the
+ * LTO_ENULL / LTO_EINVAL rules as lto_guided_flight_batch; update_every = 0 is the plain 14-row flow from (x0, lambda_nom,0).
+ * Out: x_final [7 x B] (row 6 the final mass: the propellant is x0[6] - x_final[6]);  lam_final [7 x B] (may be NULL);  dv [B];
+ * X_nodes [7 x n_nodes x B] (may be NULL): node 0 is x0 and the last node x_final, bit for bit;  status[b]: 0 ok;  2 a non-finite
+ * input, state or applied gain, a span out of max_steps, or a mass that is not finite and positive at a span's start (the start
+ * mass first of all): NaN from the failing span on, no other start is affected. */
+int lto_guided_flight_mass_batch(lto_ctx* ctx, int n_nodes, int n_batch, const double* XC_nom, const double* t, const double* K,
+                                 int n_nom, const double* x0, int update_every, const double* nav, const lto_params* prm, int n_prm,
+                                 const lto_integrator* integ, double* x_final, double* lam_final, double* dv, double* X_nodes,
+                                 int* accepted, int* rejected, int* status);
+int lto_guided_flight_mass(lto_ctx* ctx, int n_nodes, const double* XC_nom, const double* t, const double* K, const double* x0,
+                           int update_every, const double* nav, const lto_params* prm, const lto_integrator* integ, double* x_final,
+                           double* lam_final, double* dv, double* X_nodes, int* accepted, int* rejected, int* status);
 
 int lto_direct_plan_create(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, int nsteps,
                            const lto_direct_params* prm, lto_direct_plan** out);

@@ -18,7 +18,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
        direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
-       LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight,
+       LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
 const liblto = get(ENV, "LTO_HIP_LIB", joinpath(@__DIR__, "..", "lowthrustopt_amd", "liblto_hip.so"))
@@ -565,6 +565,47 @@ function guided_flight(ctx::LtoContext, XC_nom::Array{Float64,3}, t::Matrix{Floa
                 Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint},
                 Ptr{Cint}, Ptr{Cint}),
                ctx.handle, ndim, n, B, XC_nom, t, K, n_nom, x0, update_every, nav === nothing ? C_NULL : nav, prm, length(prm),
+               Ref(integ), x_final, lam_final, dv, nodes, accepted, rejected, status)
+    check(ctx, rc)
+    (x_final = x_final, lam_final = lam_final, dv = dv, nodes = nodes, accepted = Int.(accepted), rejected = Int.(rejected),
+     status = Int.(status))
+end
+
+"""`guidance_gains` for solutions of the 14-row variable-mass system (`lto_guidance_gains_mass_batch`, DESIGN 4.24): `XC`
+[14 x n x B], Isp in the mass slot of the parameters.  The gains keep d r_f = d v_f = 0 and d lambda_m(t_f) = 0; the final mass is
+free.  Returns the named tuple (K [7 x 7 x (n-1) x B], pivot [(n-1) x B], status [B])."""
+function guidance_gains_mass(ctx::LtoContext, XC::Array{Float64,3}, t::Matrix{Float64}, params::Vector;
+                             sing_tol::Real = 1e-10, integ::LtoIntegrator = LtoIntegrator())
+    ndim, n, B = size(XC)
+    ndim == 14 || throw(ArgumentError("XC must be [14 x n x B]"))
+    prm = [LtoParams(q) for q in params]
+    K = zeros(7, 7, n - 1, B); pivot = zeros(n - 1, B); status = zeros(Cint, B)
+    rc = ccall((:lto_guidance_gains_mass_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Cdouble,
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, n, B, XC, t, size(t, 2), prm, length(prm), Ref(integ), Float64(sing_tol), K, pivot, status)
+    check(ctx, rc)
+    (K = K, pivot = pivot, status = Int.(status))
+end
+
+"""`guided_flight` for the 14-row variable-mass system (`lto_guided_flight_mass_batch`, DESIGN 4.24): the starts `x0` [7 x B]
+(r, v, m) flown about the nominal `XC_nom` [14 x n x n_nom] with gains `K` [7 x 7 x (n-1) x n_nom]; `nav` [7 x n_upd x B] or
+`nothing`.  The update resets all seven costates from the seven measured states.  Returns the named tuple (x_final, lam_final
+[7 x B] -- x_final[7, b] the final mass --, dv [B], nodes [7 x n x B], accepted, rejected, status [B])."""
+function guided_flight_mass(ctx::LtoContext, XC_nom::Array{Float64,3}, t::Matrix{Float64}, K::Array{Float64,4},
+                            x0::Matrix{Float64}, params::Vector; update_every::Integer = 1,
+                            nav::Union{Nothing,Array{Float64,3}} = nothing, integ::LtoIntegrator = LtoIntegrator())
+    ndim, n, n_nom = size(XC_nom)
+    ndim == 14 || throw(ArgumentError("XC_nom must be [14 x n x n_nom]"))
+    B = size(x0, 2)
+    prm = [LtoParams(q) for q in params]
+    x_final = zeros(7, B); lam_final = zeros(7, B); dv = zeros(B); nodes = zeros(7, n, B)
+    accepted = zeros(Cint, B); rejected = zeros(Cint, B); status = zeros(Cint, B)
+    rc = ccall((:lto_guided_flight_mass_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+                Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint},
+                Ptr{Cint}, Ptr{Cint}),
+               ctx.handle, n, B, XC_nom, t, K, n_nom, x0, update_every, nav === nothing ? C_NULL : nav, prm, length(prm),
                Ref(integ), x_final, lam_final, dv, nodes, accepted, rejected, status)
     check(ctx, rc)
     (x_final = x_final, lam_final = lam_final, dv = dv, nodes = nodes, accepted = Int.(accepted), rejected = Int.(rejected),

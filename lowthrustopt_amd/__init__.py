@@ -11,7 +11,8 @@ from .hotpath import (Context, Group, Comm, GroupComm, auto_kernel, default_cont
                       direct_qp_step_free, direct_solve_free, direct_tf_bounds, direct_qp_step_free_tf, direct_solve_free_tf,
                       indirect_add_time, indirect_remesh, direct_refine, direct_resample, stack_guess, StackGuess, indirect_events, ThrustEvents,
                       indirect_events_mass, densify_mass, indirect_remesh_mass, indirect_add_time_mass, control_replay, ControlReplay,
-                      replay_sample_knots, guidance_gains, GuidanceGains, guided_flight, GuidedFlight, guided_updates)
+                      replay_sample_knots, guidance_gains, GuidanceGains, guided_flight, GuidedFlight, guided_updates,
+                      guidance_gains_mass, guided_flight_mass)
 from . import synth  # noqa: F401
 
 __version__ = "0.1.0"

@@ -174,6 +174,15 @@ SIGNATURES = {
                                           C.POINTER(LtoParams), C.c_int, C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_guided_flight": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(LtoParams),
                                     C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_guidance_gains_mass_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.POINTER(LtoParams), C.c_int,
+                                                C.POINTER(LtoIntegrator), C.c_double, _vp, _vp, _vp]),
+    "lto_guidance_gains_mass": (C.c_int, [_vp, C.c_int, _vp, _vp, C.POINTER(LtoParams), C.POINTER(LtoIntegrator), C.c_double, _vp,
+                                          _vp, _vp]),
+    "lto_guided_flight_mass_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp,
+                                               C.POINTER(LtoParams), C.c_int, C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp]),
+    "lto_guided_flight_mass": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(LtoParams),
+                                         C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_indirect_plan_steps_accepted": (_vp, [_vp]),
     "lto_indirect_plan_steps_rejected": (_vp, [_vp]),
     "lto_indirect_plan_copy_steps": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -79,6 +79,26 @@ struct SysEvents {
   }
 };
 
+// The same for the 14-row variable-mass system, (y[14], q) (kernels_events.hip says why the mass is carried as
+// m_i + y[6], y[6] = 0 at the span's start).
+template <int PM>
+struct SysEventsMass {
+  static constexpr int DIM = 15;
+  TrajParams tp;
+  double m_i;
+  __device__ __forceinline__ void rhs(const double (&y)[15], double (&k)[15]) const {
+    double yb[14], kb[14];
+#pragma unroll
+    for (int i = 0; i < 14; ++i) yb[i] = y[i];
+    yb[6] = m_i + y[6];
+    double umag;
+    rhs14_base<PM, true>(yb, tp, kb, umag);
+#pragma unroll
+    for (int i = 0; i < 14; ++i) k[i] = kb[i];
+    k[14] = umag;
+  }
+};
+
 // x^(-1/8) and x^(1/9) without pow()
 __device__ __forceinline__ double pow_m8th(double x) { return 1.0 / sqrt(sqrt(sqrt(x))); }
 __device__ __forceinline__ double pow_9th(double x) { return cbrt(cbrt(x)); }

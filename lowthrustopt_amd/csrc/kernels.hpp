@@ -156,8 +156,9 @@ struct ReplayArgs {
 };
 // nstate 6 or 7, method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
 hipError_t launch_control_replay(int nstate, int pm, int method, const IndirectArgs& a, const ReplayArgs& r, hipStream_t st);
-// Neighbouring-extremal guidance (kernels_guidance.hip).  The backward sweep over the segment STMs of a 12-row sweep:
-// Phi [144][ldp] (col * 12 + row, segment b (n_nodes - 1) + k); K [36][(n_nodes - 1) n_batch] = the caller's [6 x 6 x (n-1) x B].
+// Neighbouring-extremal guidance (kernels_guidance.hip), nx = 6 (12-row solutions) or 7 (14-row, variable mass).
+// The backward sweep over the segment STMs of a 2 nx-row sweep: Phi [(2 nx)^2][ldp] (col * 2 nx + row, segment b (n_nodes - 1) + k);
+// K [nx^2][(n_nodes - 1) n_batch] = the caller's [nx x nx x (n-1) x B].
 struct GainsArgs {
   const double* Phi; long ldp;
   int n_nodes, n_batch;
@@ -165,11 +166,12 @@ struct GainsArgs {
   double* K;
   double* pivot;                   // [(n_nodes - 1) n_batch] or null
   int* status;                     // [n_batch]: 0 ok, 2 not finite, 3 a pivot ratio below sing_tol
+  int nx;                          // 6 or 7; anything else: hipErrorInvalidValue
 };
 hipError_t launch_guidance_gains(const GainsArgs& g, hipStream_t st);
 // The guided flight: of `a` it reads tp / tp_stride, steps, rtol, atol and max_steps (max_steps per node interval).  Everything is
-// laid out [row][lanes]: nom row k 12 + c, K row k 36 + r + 6 c and t row k over n_nom = 1 or n_batch columns; x0 row c, nav row
-// j 6 + c, x_final / lam_final row c and nodes row k 6 + c over n_batch columns.
+// laid out [row][lanes]: nom row k 2 nx + c, K row k nx^2 + r + nx c and t row k over n_nom = 1 or n_batch columns; x0 row c, nav row
+// j nx + c, x_final / lam_final row c and nodes row k nx + c over n_batch columns.
 struct GuidedArgs {
   const double* nom; const double* K; const double* t; int n_nom;
   int n_nodes, n_batch;
@@ -181,7 +183,8 @@ struct GuidedArgs {
   double* dv;                      // [n_batch]
   double* nodes;                   // or null
   int* nacc; int* nrej;            // [n_batch], summed over the intervals
-  int* status;                     // [n_batch]: 0 ok, 2 not finite / an interval out of max_steps
+  int* status;                     // [n_batch]: 0 ok, 2 not finite / an interval out of max_steps / nx = 7: a mass not positive
+  int nx;                          // 6 or 7; anything else: hipErrorInvalidValue
 };
 // method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
 hipError_t launch_guided_flight(int pm, int method, const IndirectArgs& a, const GuidedArgs& g, hipStream_t st);

@@ -164,23 +164,7 @@ __global__ __launch_bounds__(64) void k_indirect_events(const IndirectArgs a, co
 // 2.6e-12 relative on 0.04 kg).  The RHS and the event function see m_i + y[6]; the propagated mass is m(t_{i+1}) = m_i + y[6],
 // and dm = m_i - m(t_{i+1}) is -y[6] with the digits that sum would round away -- unless the sum IS m_i: a segment that does not
 // move the mass by half a unit of its last place has burned nothing, dm = 0 (Isp -> infinity: the constant-mass system).
-template <int PM>
-struct SysEventsMass {
-  static constexpr int DIM = 15;
-  TrajParams tp;
-  double m_i;
-  __device__ __forceinline__ void rhs(const double (&y)[15], double (&k)[15]) const {
-    double yb[14], kb[14];
-#pragma unroll
-    for (int i = 0; i < 14; ++i) yb[i] = y[i];
-    yb[6] = m_i + y[6];
-    double umag;
-    rhs14_base<PM, true>(yb, tp, kb, umag);
-#pragma unroll
-    for (int i = 0; i < 14; ++i) k[i] = kb[i];
-    k[14] = umag;
-  }
-};
+// SysEventsMass itself lives in indirect_kernel.hpp beside SysEvents: the guided flight of 14-row solutions carries it too.
 
 // g = |lambda_v| - thr(m) > 0 with the state's own mass: p = 1: thr = 1; p > 1: thr = p (cT / m)^(p-1).  A NaN (a mass of 0 makes
 // one) is off.

@@ -1,23 +1,27 @@
-// kernels_guidance.hip -- neighbouring-extremal guidance, gfx950.
+// kernels_guidance.hip -- neighbouring-extremal guidance (DESIGN 4.23, and 4.24 for the variable-mass system), gfx950.
 //
-// k_guidance_gains: one wavefront per trajectory, lanes 0..35 one element (row r = e % 6, column c = e / 6) of a 6 x 6 block each.
-// With Phi_k = d y(t_{k+1}) / d y(t_k) = [A B; C D] and d lambda_k = K_k d x_k keeping the linearised arrival state fixed:
-//   K_{n-2} = -B^-1 A,    K_k = (D - K_{k+1} B)^-1 (K_{k+1} A - C),  k = n-3 .. 0.
-// Every node is one 6 x 6 system M X = R with six right-hand sides, solved by LU with partial (row) pivoting: lane (r, c) holds
-// M[r][c] and R[r][c], rows and columns move between lanes by __shfl, every lane runs the same pivot search on the same six
+// k_guidance_gains<NX>: one wavefront per trajectory, lanes 0 .. NX^2 - 1 one element (row r = e % NX, column c = e / NX) of an
+// NX x NX block each; NX = 6 for 12-row solutions, 7 for the 14-row variable-mass ones (x = (r, v, m), lambda = (l_r, l_v, l_m)).
+// With Phi_k = d y(t_{k+1}) / d y(t_k) = [A B; C D] and d lambda_k = K_k d x_k keeping the linearised arrival conditions:
+//   K_{n-2} = -M^-1 N,    K_k = (D - K_{k+1} B)^-1 (K_{k+1} A - C),  k = n-3 .. 0.
+// NX = 6: the arrival state is fixed, M = B, N = A.  NX = 7: r_f, v_f and lambda_m(t_f) = 0 are fixed and m_f is free: M is rows
+// 0..5 of B over row 6 of D, N rows 0..5 of A over row 6 of C.
+// Every node is one NX x NX system M X = R with NX right-hand sides, solved by LU with partial (row) pivoting: lane (r, c) holds
+// M[r][c] and R[r][c], rows and columns move between lanes by __shfl, every lane runs the same pivot search on the same NX
 // values, so there is no LDS and no barrier, and nothing is shared between wavefronts: a trajectory's gains do not depend on its
-// batch.  pivot[k] = min |u_ii| / max |M|; below sing_tol the node and every earlier one get NaN gains (status 3), a non-finite
-// block or gain does the same with status 2.
+// batch.  pivot[k] = min |u_ii| / max |M|, M as it stands (no scaling); below sing_tol the node and every earlier one get NaN gains
+// (status 3), a non-finite block or gain does the same with status 2.
 //
-// k_guided_flight: lane = start.  The lane carries (x, lambda, q), q' = umag -- SysEvents, 13 components, all in DOP853's error
-// norm -- node interval by node interval, each a span of its own (run_dop853, or `steps` RK4 steps).  At node k with
-// k % update_every == 0 the costate is reset to lambda_nom,k + K_k (x - x_nom,k + e_j); otherwise it runs on.  The nominal, the
-// gains and the grid are laid out [row][n_nom]: one address for all lanes when n_nom = 1, coalesced over the lanes when every start
-// has its own.  Starts, navigation errors and every output are [row][B].  One launch per control-law class, per-lane flags as
-// doubles, no atomics.
+// k_guided_flight<NX>: lane = start.  The lane carries (x, lambda, q), q' = umag -- SysEvents, 13 components, or SysEventsMass, 15,
+// all in DOP853's error norm -- node interval by node interval, each a span of its own (run_dop853, or `steps` RK4 steps).  At node
+// k with k % update_every == 0 the costate is reset to lambda_nom,k + K_k (x - x_nom,k + e_j), for NX = 7 with the measured mass
+// among the seven rows; otherwise it runs on.  NX = 7 carries the mass over a span as m_k + y[6] (kernels_events.hip) and fails a
+// lane whose mass at a span's start is not positive.  The nominal, the gains and the grid are laid out [row][n_nom]: one address
+// for all lanes when n_nom = 1, coalesced over the lanes when every start has its own.  Starts, navigation errors and every output
+// are [row][B].  One launch per control-law class, per-lane flags as doubles, no atomics.
 //
 // k_rows_to_lanes / k_lanes_to_rows: the caller's column-major [rows x count] arrays <-> [row][count]; the row counts here
-// (36 (n - 1) for the gains) are beyond what the tiled pack kernels of kernels_util.hip take.
+// (36 (n - 1) or 49 (n - 1) for the gains) are beyond what the tiled pack kernels of kernels_util.hip take.
 #include <hip/hip_runtime.h>
 
 #include "indirect_kernel.hpp"
@@ -51,41 +55,48 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+template <int NX>
 __global__ __launch_bounds__(64) void k_guidance_gains(const GainsArgs g) {
+  constexpr int ND = 2 * NX, NE = NX * NX;
+  static_assert(NE <= 64, "one element per lane of one wavefront");
   const int b = blockIdx.x;
   const int e = threadIdx.x;
-  const bool el = e < 36;                        // lanes 36..63 carry zeros through every shuffle
-  const int r = el ? e % 6 : 0, c = el ? e / 6 : 0;
+  const bool el = e < NE;                        // the lanes behind the block carry zeros through every shuffle
+  const int r = el ? e % NX : 0, c = el ? e / NX : 0;
   const int segs = g.n_nodes - 1;
   const double nan = __builtin_nan("");
   double kn = 0.0;                               // K_{k+1}[r][c]
   double dead = 0.0;                             // 2 or 3 once a node has failed: wave-uniform
   for (int k = segs - 1; k >= 0; --k) {
     const long s = (long)b * segs + k;
-    double* Kout = g.K + 36 * s;
+    double* Kout = g.K + NE * s;
     if (dead != 0.0) {
       if (el) Kout[e] = nan;
       if (g.pivot && e == 0) g.pivot[s] = nan;
       continue;
     }
-    // Phi [144][ldp], entry col * 12 + row
+    // Phi [ND ND][ldp], entry col * ND + row
     double A = 0.0, Bm = 0.0, Cm = 0.0, D = 0.0;
     if (el) {
-      A = g.Phi[(long)(c * 12 + r) * g.ldp + s];
-      Bm = g.Phi[(long)((c + 6) * 12 + r) * g.ldp + s];
-      Cm = g.Phi[(long)(c * 12 + r + 6) * g.ldp + s];
-      D = g.Phi[(long)((c + 6) * 12 + r + 6) * g.ldp + s];
+      A = g.Phi[(long)(c * ND + r) * g.ldp + s];
+      Bm = g.Phi[(long)((c + NX) * ND + r) * g.ldp + s];
+      Cm = g.Phi[(long)(c * ND + r + NX) * g.ldp + s];
+      D = g.Phi[(long)((c + NX) * ND + r + NX) * g.ldp + s];
     }
     double m, x;
     if (k == segs - 1) {
-      m = Bm; x = -A;
+      if (NX == 7 && r == 6) {                   // the arrival condition d lambda_m = 0 in place of d m = 0
+        m = D; x = -Cm;
+      } else {
+        m = Bm; x = -A;
+      }
     } else {
       double kb = 0.0, ka = 0.0;
 #pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const double krj = __shfl(kn, r + 6 * j, 64);
-        kb = __builtin_fma(krj, __shfl(Bm, j + 6 * c, 64), kb);
-        ka = __builtin_fma(krj, __shfl(A, j + 6 * c, 64), ka);
+      for (int j = 0; j < NX; ++j) {
+        const double krj = __shfl(kn, r + NX * j, 64);
+        kb = __builtin_fma(krj, __shfl(Bm, j + NX * c, 64), kb);
+        ka = __builtin_fma(krj, __shfl(A, j + NX * c, 64), ka);
       }
       m = D - kb; x = ka - Cm;
     }
@@ -95,21 +106,21 @@ __global__ __launch_bounds__(64) void k_guidance_gains(const GainsArgs g) {
     // LU with row pivoting, the right-hand sides carried along
     double umin = __builtin_huge_val();
 #pragma unroll
-    for (int p = 0; p < 6; ++p) {
+    for (int p = 0; p < NX; ++p) {
       int piv = p;
-      double best = fabs(__shfl(m, p + 6 * p, 64));
+      double best = fabs(__shfl(m, p + NX * p, 64));
 #pragma unroll
-      for (int i = p + 1; i < 6; ++i) {
-        const double v = fabs(__shfl(m, i + 6 * p, 64));
+      for (int i = p + 1; i < NX; ++i) {
+        const double v = fabs(__shfl(m, i + NX * p, 64));
         if (v > best) { best = v; piv = i; }
       }
       umin = fmin(umin, best);
       const int src = (r == p) ? piv : ((r == piv) ? p : r);
-      m = __shfl(m, src + 6 * c, 64);
-      x = __shfl(x, src + 6 * c, 64);
-      const double upp = __shfl(m, p + 6 * p, 64);
-      const double l = __shfl(m, r + 6 * p, 64) / upp;
-      const double mp = __shfl(m, p + 6 * c, 64), xp = __shfl(x, p + 6 * c, 64);
+      m = __shfl(m, src + NX * c, 64);
+      x = __shfl(x, src + NX * c, 64);
+      const double upp = __shfl(m, p + NX * p, 64);
+      const double l = __shfl(m, r + NX * p, 64) / upp;
+      const double mp = __shfl(m, p + NX * c, 64), xp = __shfl(x, p + NX * c, 64);
       if (el && r > p) {
         m = (c > p) ? __builtin_fma(-l, mp, m) : 0.0;
         x = __builtin_fma(-l, xp, x);
@@ -117,11 +128,11 @@ __global__ __launch_bounds__(64) void k_guidance_gains(const GainsArgs g) {
     }
     // back substitution, row by row from the last
 #pragma unroll
-    for (int i = 5; i >= 0; --i) {
-      double acc = __shfl(x, i + 6 * c, 64);
+    for (int i = NX - 1; i >= 0; --i) {
+      double acc = __shfl(x, i + NX * c, 64);
 #pragma unroll
-      for (int j = 5; j > i; --j) acc = __builtin_fma(-__shfl(m, i + 6 * j, 64), __shfl(x, j + 6 * c, 64), acc);
-      const double uii = __shfl(m, i + 6 * i, 64);
+      for (int j = NX - 1; j > i; --j) acc = __builtin_fma(-__shfl(m, i + NX * j, 64), __shfl(x, j + NX * c, 64), acc);
+      const double uii = __shfl(m, i + NX * i, 64);
       if (el && r == i) x = acc / uii;
     }
     const double ratio = umin / mmax;
@@ -136,52 +147,59 @@ __global__ __launch_bounds__(64) void k_guidance_gains(const GainsArgs g) {
   if (e == 0) g.status[b] = (int)dead;
 }
 
-template <int PM, int METHOD>
+template <int NX, int PM>
+struct GuidedSys { using type = SysEvents<PM>; };
+template <int PM>
+struct GuidedSys<7, PM> { using type = SysEventsMass<PM>; };
+
+template <int NX, int PM, int METHOD>
 __global__ __launch_bounds__(64) void k_guided_flight(const IndirectArgs a, const GuidedArgs g) {
+  constexpr int ND = 2 * NX, NE = NX * NX, DIM = ND + 1;
   const int b = blockIdx.x * 64 + threadIdx.x;
   const int B = g.n_batch;
   if (b >= B) return;
-  using Sys = SysEvents<PM>;
+  using Sys = typename GuidedSys<NX, PM>::type;
+  static_assert(Sys::DIM == DIM, "state, costate and the quadrature of umag");
   Sys sys;
   sys.tp = a.tp[(long)b * a.tp_stride];
   if (a.class_filter && p_class(sys.tp.p) != PM) return;
   const long nn = g.n_nom;
   const long h = (nn == 1) ? 0 : b;
-  const double* nom = g.nom + h;                 // [(k 12 + c)][n_nom]
-  const double* Kd = g.K + h;                    // [(k 36 + r + 6 c)][n_nom]
+  const double* nom = g.nom + h;                 // [(k ND + c)][n_nom]
+  const double* Kd = g.K + h;                    // [(k NE + r + NX c)][n_nom]
   const double* tg = g.t + h;                    // [k][n_nom]
   const int n = g.n_nodes, every = g.every;
-  double y[13];
+  double y[DIM];
 #pragma unroll
-  for (int c = 0; c < 6; ++c) y[c] = g.x0[(long)c * B + b];
+  for (int c = 0; c < NX; ++c) y[c] = g.x0[(long)c * B + b];
 #pragma unroll
-  for (int c = 0; c < 6; ++c) y[6 + c] = nom[(long)(6 + c) * nn];
-  y[12] = 0.0;
+  for (int c = 0; c < NX; ++c) y[NX + c] = nom[(long)(NX + c) * nn];
+  y[ND] = 0.0;
   // per-lane flags are doubles (run_dop853's comment, DESIGN.md "Compiler hazards")
   double failed = 0.0;
   int nacc = 0, nrej = 0;
   double dv = 0.0;
   if (g.nodes) {                                  // node 0: the start itself, bit for bit
 #pragma unroll
-    for (int c = 0; c < 6; ++c) g.nodes[(long)c * B + b] = y[c];
+    for (int c = 0; c < NX; ++c) g.nodes[(long)c * B + b] = y[c];
   }
   int k = 0, j = 0, next_upd = (every > 0) ? 0 : -1;
   for (; k < n - 1; ++k) {
     if (k == next_upd) {
-      const double* nk = nom + (long)k * 12 * nn;
-      const double* Kk = Kd + (long)k * 36 * nn;
-      double dx[6];
+      const double* nk = nom + (long)k * ND * nn;
+      const double* Kk = Kd + (long)k * NE * nn;
+      double dx[NX];
 #pragma unroll
-      for (int c = 0; c < 6; ++c) {
+      for (int c = 0; c < NX; ++c) {
         dx[c] = y[c] - nk[(long)c * nn];
-        if (g.nav) dx[c] += g.nav[((long)j * 6 + c) * B + b];
+        if (g.nav) dx[c] += g.nav[((long)j * NX + c) * B + b];
       }
 #pragma unroll
-      for (int r = 0; r < 6; ++r) {
+      for (int r = 0; r < NX; ++r) {
         double acc = 0.0;
 #pragma unroll
-        for (int c = 0; c < 6; ++c) acc = __builtin_fma(Kk[(long)(r + 6 * c) * nn], dx[c], acc);
-        y[6 + r] = nk[(long)(6 + r) * nn] + acc;
+        for (int c = 0; c < NX; ++c) acc = __builtin_fma(Kk[(long)(r + NX * c) * nn], dx[c], acc);
+        y[NX + r] = nk[(long)(NX + r) * nn] + acc;
       }
       ++j;
       next_upd += every;
@@ -189,40 +207,46 @@ __global__ __launch_bounds__(64) void k_guided_flight(const IndirectArgs a, cons
     const double span = tg[(long)(k + 1) * nn] - tg[(long)k * nn];
     double insum = span;                          // the start, the nominal's costate and the applied gain have to be finite
 #pragma unroll
-    for (int c = 0; c < 12; ++c) insum += y[c];
+    for (int c = 0; c < ND; ++c) insum += y[c];
     if (!((insum - insum) == 0.0)) { failed = 1.0; break; }
-    y[12] = 0.0;
+    if constexpr (NX == 7) {                      // the span starts from the mass it has: m_k + y[6], y[6] = 0
+      if (!(y[6] > 0.0)) { failed = 1.0; break; }
+      sys.m_i = y[6];
+      y[6] = 0.0;
+    }
+    y[ND] = 0.0;
     if (METHOD == M_RK4) {
       const double hs = span / (double)a.steps;
       for (int s = 0; s < a.steps; ++s) rk4_step(sys, hs, y);
       nacc += a.steps;
     } else {
       int na = 0, nr = 0;
-      run_dop853<Sys, 13>(sys, span, a.rtol, a.atol, a.max_steps, y, na, nr);
+      run_dop853<Sys, DIM>(sys, span, a.rtol, a.atol, a.max_steps, y, na, nr);
       nacc += na; nrej += nr;
     }
+    if constexpr (NX == 7) y[6] = sys.m_i + y[6];
     double fin = 0.0;
 #pragma unroll
-    for (int c = 0; c < 13; ++c) fin += y[c];
+    for (int c = 0; c < DIM; ++c) fin += y[c];
     if (!((fin - fin) == 0.0)) { failed = 1.0; break; }
-    dv += y[12];
+    dv += y[ND];
     if (g.nodes) {
 #pragma unroll
-      for (int c = 0; c < 6; ++c) g.nodes[((long)(k + 1) * 6 + c) * B + b] = y[c];
+      for (int c = 0; c < NX; ++c) g.nodes[((long)(k + 1) * NX + c) * B + b] = y[c];
     }
   }
   const double nan = __builtin_nan("");
   if (failed != 0.0 && g.nodes) {                 // the nodes from the failed span on
     for (int kk = k + 1; kk < n; ++kk) {
 #pragma unroll
-      for (int c = 0; c < 6; ++c) g.nodes[((long)kk * 6 + c) * B + b] = nan;
+      for (int c = 0; c < NX; ++c) g.nodes[((long)kk * NX + c) * B + b] = nan;
     }
   }
 #pragma unroll
-  for (int c = 0; c < 6; ++c) g.x_final[(long)c * B + b] = (failed != 0.0) ? nan : y[c];
+  for (int c = 0; c < NX; ++c) g.x_final[(long)c * B + b] = (failed != 0.0) ? nan : y[c];
   if (g.lam_final) {
 #pragma unroll
-    for (int c = 0; c < 6; ++c) g.lam_final[(long)c * B + b] = (failed != 0.0) ? nan : y[6 + c];
+    for (int c = 0; c < NX; ++c) g.lam_final[(long)c * B + b] = (failed != 0.0) ? nan : y[NX + c];
   }
   g.dv[b] = (failed != 0.0) ? nan : dv;
   g.status[b] = (failed != 0.0) ? 2 : 0;
@@ -230,15 +254,22 @@ __global__ __launch_bounds__(64) void k_guided_flight(const IndirectArgs a, cons
   g.nrej[b] = nrej;
 }
 
-template <int METHOD>
+template <int NX, int METHOD>
 hipError_t launch_guided_pm(int pm, const IndirectArgs& a0, const GuidedArgs& g, hipStream_t st) {
   dim3 grid((g.n_batch + 63) / 64);
   // every class is launched and the error state read once, behind the last launch (as launch_dense_pm)
   (void)for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) {
-    hipLaunchKernelGGL((k_guided_flight<decltype(cls)::value, METHOD>), grid, dim3(64), 0, st, a, g);
+    hipLaunchKernelGGL((k_guided_flight<NX, decltype(cls)::value, METHOD>), grid, dim3(64), 0, st, a, g);
     return hipSuccess;
   });
   return hipGetLastError();
+}
+
+template <int NX>
+hipError_t launch_guided_nx(int pm, int method, const IndirectArgs& a, const GuidedArgs& g, hipStream_t st) {
+  if (method == M_RK4) return launch_guided_pm<NX, M_RK4>(pm, a, g, st);
+  if (method == M_DOP853_ADAPTIVE) return launch_guided_pm<NX, M_DOP853_ADAPTIVE>(pm, a, g, st);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -258,13 +289,15 @@ hipError_t launch_lanes_to_rows(const double* soa, long rows, long count, double
 }
 
 hipError_t launch_guidance_gains(const GainsArgs& g, hipStream_t st) {
-  hipLaunchKernelGGL(k_guidance_gains, dim3((unsigned)g.n_batch), dim3(64), 0, st, g);
+  if (g.nx == 6) hipLaunchKernelGGL(k_guidance_gains<6>, dim3((unsigned)g.n_batch), dim3(64), 0, st, g);
+  else if (g.nx == 7) hipLaunchKernelGGL(k_guidance_gains<7>, dim3((unsigned)g.n_batch), dim3(64), 0, st, g);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
 hipError_t launch_guided_flight(int pm, int method, const IndirectArgs& a, const GuidedArgs& g, hipStream_t st) {
-  if (method == M_RK4) return launch_guided_pm<M_RK4>(pm, a, g, st);
-  if (method == M_DOP853_ADAPTIVE) return launch_guided_pm<M_DOP853_ADAPTIVE>(pm, a, g, st);
+  if (g.nx == 6) return launch_guided_nx<6>(pm, method, a, g, st);
+  if (g.nx == 7) return launch_guided_nx<7>(pm, method, a, g, st);
   return hipErrorInvalidValue;
 }
 

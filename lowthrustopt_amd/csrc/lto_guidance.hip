@@ -2,17 +2,29 @@
 // in, runs the STM sweep of a short-lived plan of its own (the kernel AUTO picks), leaves Phi in HBM and runs the backward sweep over
 // it.  The guided flight stages the nominal, the gains, the grid, the starts and the navigation errors into the [row][lanes]
 // layouts of k_guided_flight and brings the end states, the nodes, dv, the step counts and the status back.  The scratch is laid
-// out by ArenaLayout.  12-row solutions only: the mass row is not built.
+// out by ArenaLayout.  One host path for both row counts: the 12-row entries (ndim must be 12) and the _mass entries of the 14-row
+// variable-mass system, half-dimension nx = 6 or 7.
 #include <cmath>
+#include <cstdio>
+#include <cstring>
 
 #include "lto_host.hpp"
 
 namespace {
 
-int guidance_supported(lto_ctx* c, int ndim, const lto_integrator* integ, const char* who) {
-  if (ndim != 12) return set_err(c, LTO_EUNSUPPORTED, "guidance gains and guided flights are built for 12-row solutions (ndim = 12)");
+// nd: the row count the entry is built for (12, or 14 for the _mass entries); ndim: what the caller passed
+int guidance_supported(lto_ctx* c, int nd, int ndim, const lto_integrator* integ, const char* who) {
+  if (ndim != nd)
+    return set_err(c, LTO_EUNSUPPORTED, "guidance gains and guided flights take ndim = 12; 14-row solutions go to lto_guidance_gains_mass_batch and lto_guided_flight_mass_batch");
   if (integ->method != LTO_RK4 && integ->method != LTO_DOP853_ADAPTIVE) return set_err(c, LTO_EUNSUPPORTED, who);
   return LTO_OK;
+}
+
+// "<entry>: <what>" with the entry's own name
+int fail(lto_ctx* c, int code, const char* who, const char* what, hipError_t e = hipSuccess) {
+  char msg[256];
+  std::snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return set_err(c, code, msg, e);
 }
 
 bool grids_increase(const double* t, int n_nodes, int n_grids) {
@@ -36,92 +48,121 @@ hipError_t lanes_out(const double* d_in, long rows, long count, double* d_tmp, d
   return e == hipSuccess ? hipMemcpyAsync(host, d_tmp, sizeof(double) * (size_t)rows * count, hipMemcpyDeviceToHost, st) : e;
 }
 
-}  // namespace
-
-extern "C" {
-
-int lto_guidance_gains_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
-                             const lto_params* prm, int n_prm, const lto_integrator* integ, double sing_tol, double* K,
-                             double* pivot, int* status) {
+int gains_batch(int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC, const double* t,
+                int n_tgrids, const lto_params* prm, int n_prm, const lto_integrator* integ, double sing_tol, double* K, double* pivot,
+                int* status) {
   if (!c) return LTO_ENULL;
   CallTimer call_timer(c);
   if (!XC || !t || !prm || !integ || !K || !status)
-    return set_err(c, LTO_ENULL, "lto_guidance_gains_batch: XC, t, prm, integ, K or status is NULL");
-  int rc = guidance_supported(c, ndim, integ, "guidance gains are built for LTO_RK4 or LTO_DOP853_ADAPTIVE");
+    return fail(c, LTO_ENULL, who, "XC, t, prm, integ, K or status is NULL");
+  int rc = guidance_supported(c, nd, ndim, integ, "guidance gains are built for LTO_RK4 or LTO_DOP853_ADAPTIVE");
   if (rc) return rc;
-  if (n_nodes < 2 || n_batch < 1) return set_err(c, LTO_EINVAL, "lto_guidance_gains_batch: need n_nodes >= 2 and n_batch >= 1");
-  if (n_tgrids != 1 && n_tgrids != n_batch) return set_err(c, LTO_EINVAL, "lto_guidance_gains_batch: n_tgrids must be 1 or n_batch");
-  if (n_prm != 1 && n_prm != n_batch) return set_err(c, LTO_EINVAL, "lto_guidance_gains_batch: n_prm must be 1 or n_batch");
-  if (!(sing_tol > 0.0 && sing_tol < 1.0)) return set_err(c, LTO_EINVAL, "lto_guidance_gains_batch: sing_tol must lie in (0, 1)");
+  if (n_nodes < 2 || n_batch < 1) return fail(c, LTO_EINVAL, who, "need n_nodes >= 2 and n_batch >= 1");
+  if (n_tgrids != 1 && n_tgrids != n_batch) return fail(c, LTO_EINVAL, who, "n_tgrids must be 1 or n_batch");
+  if (n_prm != 1 && n_prm != n_batch) return fail(c, LTO_EINVAL, who, "n_prm must be 1 or n_batch");
+  if (!(sing_tol > 0.0 && sing_tol < 1.0)) return fail(c, LTO_EINVAL, who, "sing_tol must lie in (0, 1)");
   if (!grids_increase(t, n_nodes, n_tgrids))
-    return set_err(c, LTO_EINVAL, "lto_guidance_gains_batch: t must be finite and strictly increasing");
-  const int B = n_batch;
+    return fail(c, LTO_EINVAL, who, "t must be finite and strictly increasing");
+  const int B = n_batch, nx = nd / 2;
+  // 14 rows, DOP853: AUTO takes the two-lanes-per-state STM kernel for batches whose laws are all p = 0 or p = 1 and the one-piece
+  // cooperative kernel otherwise, and the two differ in the last bits -- swept as one batch, a p <= 1 trajectory's gains would
+  // depend on the classes of its neighbours.  A batch that mixes the two kinds is therefore run as two calls, one per kind, each
+  // with the kernel AUTO picks for it and for each of its trajectories alone.
+  if (nd == 14 && integ->method == LTO_DOP853_ADAPTIVE && n_prm == B) {
+    HostBuf<int> idx((size_t)B);                  // the p <= 1 trajectories from the front, the others from the back
+    if (!idx.ok()) return fail(c, LTO_ENOMEM, who, "host memory");
+    int n_lim = 0, n_oth = 0;
+    for (int b = 0; b < B; ++b) {
+      if ((1 << lto::p_class(prm[b].p)) & kThrustLimitedClasses) idx[n_lim++] = b;
+      else idx[B - 1 - n_oth++] = b;
+    }
+    if (n_lim > 0 && n_oth > 0) {
+      const size_t xc = (size_t)nd * n_nodes, kk = (size_t)nx * nx * (n_nodes - 1), segs = (size_t)n_nodes - 1;
+      for (int kind = 0; kind < 2; ++kind) {
+        const int* ix = idx.data() + (kind == 0 ? 0 : n_lim);
+        const size_t m = kind == 0 ? n_lim : n_oth;
+        HostBuf<double> Xs(xc * m), ts(n_tgrids == 1 ? 0 : (size_t)n_nodes * m), Ks(kk * m), ps(segs * m);
+        HostBuf<lto_params> prms(m);
+        HostBuf<int> sts(m);
+        if (!Xs.ok() || !ts.ok() || !Ks.ok() || !ps.ok() || !prms.ok() || !sts.ok()) return fail(c, LTO_ENOMEM, who, "host memory");
+        for (size_t j = 0; j < m; ++j) {
+          std::memcpy(Xs.data() + xc * j, XC + xc * ix[j], sizeof(double) * xc);
+          if (n_tgrids != 1) std::memcpy(ts.data() + (size_t)n_nodes * j, t + (size_t)n_nodes * ix[j], sizeof(double) * n_nodes);
+          prms[j] = prm[ix[j]];
+        }
+        rc = gains_batch(nd, who, c, ndim, n_nodes, (int)m, Xs.data(), n_tgrids == 1 ? t : ts.data(), n_tgrids == 1 ? 1 : (int)m,
+                         prms.data(), (int)m, integ, sing_tol, Ks.data(), ps.data(), sts.data());
+        if (rc) return rc;
+        for (size_t j = 0; j < m; ++j) {
+          std::memcpy(K + kk * ix[j], Ks.data() + kk * j, sizeof(double) * kk);
+          if (pivot) std::memcpy(pivot + segs * ix[j], ps.data() + segs * j, sizeof(double) * segs);
+          status[ix[j]] = sts[j];
+        }
+      }
+      return LTO_OK;
+    }
+  }
   const size_t J = (size_t)n_nodes * B, S = (size_t)(n_nodes - 1) * B, nt = (size_t)n_nodes * n_tgrids;
   HostCall call(c);
-  rc = plan_build(c, 12, n_nodes, n_batch, prm, n_prm, integ, &call.plan[0]);
+  rc = plan_build(c, nd, n_nodes, n_batch, prm, n_prm, integ, &call.plan[0]);
   if (rc) return rc;
   double *d_aos, *d_X, *d_t, *d_def, *d_phi, *d_K, *d_piv;
   int* d_status;
   ArenaLayout scratch;
-  scratch.add(12 * J, d_aos, d_X);
+  scratch.add((size_t)nd * J, d_aos, d_X);
   scratch.add(nt, d_t);
-  scratch.add(12 * S, d_def);
-  scratch.add(144 * S, d_phi);
-  scratch.add(36 * S, d_K);
+  scratch.add((size_t)nd * S, d_def);
+  scratch.add((size_t)nd * nd * S, d_phi);
+  scratch.add((size_t)nx * nx * S, d_K);
   scratch.add(S, d_piv);
   scratch.add((size_t)B, d_status);
   rc = scratch.reserve(c);
   if (rc) return rc;
   hipStream_t st = c->stream;
-  hipError_t e = stage_in(c, XC, 12, (long)J, d_aos, d_X, (long)J, st);
+  hipError_t e = stage_in(c, XC, nd, (long)J, d_aos, d_X, (long)J, st);
   if (e == hipSuccess) e = vec_in(c, t, (long)nt, d_t, st);
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_guidance_gains_batch: stage in", e);
+  if (e != hipSuccess) return fail(c, LTO_EHIP, who, "stage in", e);
   rc = lto_indirect_jacobian_dev(call.plan[0], st, d_X, (long)J, d_t, n_tgrids, d_phi, (long)S, d_def, (long)S);
   if (rc) return rc;
   GainsArgs g{};
   g.Phi = d_phi; g.ldp = (long)S; g.n_nodes = n_nodes; g.n_batch = B; g.sing_tol = sing_tol;
-  g.K = d_K; g.pivot = d_piv; g.status = d_status;
+  g.K = d_K; g.pivot = d_piv; g.status = d_status; g.nx = nx;
   e = launch_guidance_gains(g, st);
   timing_end(c, st);                             // the sweep's start to the gains' end
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_guidance_gains", e);
-  e = hipMemcpyAsync(K, d_K, sizeof(double) * 36 * S, hipMemcpyDeviceToHost, st);
+  e = hipMemcpyAsync(K, d_K, sizeof(double) * nx * nx * S, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && pivot) e = hipMemcpyAsync(pivot, d_piv, sizeof(double) * S, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(status, d_status, sizeof(int) * B, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = call.wait();
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_guidance_gains_batch: stage out", e);
+  if (e != hipSuccess) return fail(c, LTO_EHIP, who, "stage out", e);
   return LTO_OK;
 }
 
-int lto_guidance_gains(lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
-                       const lto_integrator* integ, double sing_tol, double* K, double* pivot, int* status) {
-  return lto_guidance_gains_batch(c, ndim, n_nodes, 1, XC, t, 1, prm, 1, integ, sing_tol, K, pivot, status);
-}
-
-int lto_guided_flight_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC_nom, const double* t, const double* K,
-                            int n_nom, const double* x0, int update_every, const double* nav, const lto_params* prm, int n_prm,
-                            const lto_integrator* integ, double* x_final, double* lam_final, double* dv, double* X_nodes,
-                            int* accepted, int* rejected, int* status) {
+int flight_batch(int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC_nom, const double* t,
+                 const double* K, int n_nom, const double* x0, int update_every, const double* nav, const lto_params* prm, int n_prm,
+                 const lto_integrator* integ, double* x_final, double* lam_final, double* dv, double* X_nodes, int* accepted,
+                 int* rejected, int* status) {
   if (!c) return LTO_ENULL;
   CallTimer call_timer(c);
   if (!XC_nom || !t || !K || !x0 || !prm || !integ || !x_final || !dv || !status)
-    return set_err(c, LTO_ENULL, "lto_guided_flight_batch: XC_nom, t, K, x0, prm, integ, x_final, dv or status is NULL");
-  int rc = guidance_supported(c, ndim, integ, "guided flights are built for LTO_RK4 or LTO_DOP853_ADAPTIVE");
+    return fail(c, LTO_ENULL, who, "XC_nom, t, K, x0, prm, integ, x_final, dv or status is NULL");
+  int rc = guidance_supported(c, nd, ndim, integ, "guided flights are built for LTO_RK4 or LTO_DOP853_ADAPTIVE");
   if (rc) return rc;
-  if (n_nodes < 2 || n_batch < 1) return set_err(c, LTO_EINVAL, "lto_guided_flight_batch: need n_nodes >= 2 and n_batch >= 1");
-  if (n_nom != 1 && n_nom != n_batch) return set_err(c, LTO_EINVAL, "lto_guided_flight_batch: n_nom must be 1 or n_batch");
-  if (n_prm != 1 && n_prm != n_batch) return set_err(c, LTO_EINVAL, "lto_guided_flight_batch: n_prm must be 1 or n_batch");
-  if (update_every < 0) return set_err(c, LTO_EINVAL, "lto_guided_flight_batch: update_every must be >= 0");
+  if (n_nodes < 2 || n_batch < 1) return fail(c, LTO_EINVAL, who, "need n_nodes >= 2 and n_batch >= 1");
+  if (n_nom != 1 && n_nom != n_batch) return fail(c, LTO_EINVAL, who, "n_nom must be 1 or n_batch");
+  if (n_prm != 1 && n_prm != n_batch) return fail(c, LTO_EINVAL, who, "n_prm must be 1 or n_batch");
+  if (update_every < 0) return fail(c, LTO_EINVAL, who, "update_every must be >= 0");
   if (!grids_increase(t, n_nodes, n_nom))
-    return set_err(c, LTO_EINVAL, "lto_guided_flight_batch: t must be finite and strictly increasing");
-  const int B = n_batch, n = n_nodes;
+    return fail(c, LTO_EINVAL, who, "t must be finite and strictly increasing");
+  const int B = n_batch, n = n_nodes, nx = nd / 2;
   const int n_upd = update_every > 0 ? (n - 2) / update_every + 1 : 0;
   const bool with_nav = nav && n_upd > 0;
   HostCall call(c);
   // two nodes per trajectory: the plan is asked for the parameters, the classes and the integrator's defaults only
-  rc = plan_build(c, 12, 2, B, prm, n_prm, integ, &call.plan[0]);
+  rc = plan_build(c, nd, 2, B, prm, n_prm, integ, &call.plan[0]);
   if (rc) return rc;
   lto_indirect_plan* p = call.plan[0];
-  const long r_nom = 12L * n, r_K = 36L * (n - 1), r_nav = 6L * n_upd, r_nodes = 6L * n;
+  const long r_nom = (long)nd * n, r_K = (long)nx * nx * (n - 1), r_nav = (long)nx * n_upd, r_nodes = (long)nx * n;
   const bool tr_nom = n_nom > 1, tr_B = B > 1;   // a single column needs no transpose and no second buffer
   double *d_nom, *d_noma, *d_K, *d_Ka, *d_t, *d_ta, *d_x0, *d_x0a, *d_nav, *d_nava;
   double *d_xf, *d_xfa, *d_lf, *d_lfa, *d_nd, *d_nda, *d_dv;
@@ -133,12 +174,12 @@ int lto_guided_flight_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, cons
   scratch.add(tr_nom ? (size_t)r_K * n_nom : 0, d_Ka);
   scratch.add((size_t)n * n_nom, d_t);
   scratch.add(tr_nom ? (size_t)n * n_nom : 0, d_ta);
-  scratch.add((size_t)6 * B, d_x0, d_xf);
-  scratch.add(tr_B ? (size_t)6 * B : 0, d_x0a, d_xfa);
+  scratch.add((size_t)nx * B, d_x0, d_xf);
+  scratch.add(tr_B ? (size_t)nx * B : 0, d_x0a, d_xfa);
   scratch.add(with_nav ? (size_t)r_nav * B : 0, d_nav);
   scratch.add(with_nav && tr_B ? (size_t)r_nav * B : 0, d_nava);
-  scratch.add(lam_final ? (size_t)6 * B : 0, d_lf);
-  scratch.add(lam_final && tr_B ? (size_t)6 * B : 0, d_lfa);
+  scratch.add(lam_final ? (size_t)nx * B : 0, d_lf);
+  scratch.add(lam_final && tr_B ? (size_t)nx * B : 0, d_lfa);
   scratch.add(X_nodes ? (size_t)r_nodes * B : 0, d_nd);
   scratch.add(X_nodes && tr_B ? (size_t)r_nodes * B : 0, d_nda);
   scratch.add((size_t)B, d_dv);
@@ -149,9 +190,9 @@ int lto_guided_flight_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, cons
   hipError_t e = lanes_in(XC_nom, r_nom, n_nom, d_noma, d_nom, st);
   if (e == hipSuccess) e = lanes_in(K, r_K, n_nom, d_Ka, d_K, st);
   if (e == hipSuccess) e = lanes_in(t, n, n_nom, d_ta, d_t, st);
-  if (e == hipSuccess) e = lanes_in(x0, 6, B, d_x0a, d_x0, st);
+  if (e == hipSuccess) e = lanes_in(x0, nx, B, d_x0a, d_x0, st);
   if (e == hipSuccess && with_nav) e = lanes_in(nav, r_nav, B, d_nava, d_nav, st);
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_guided_flight_batch: stage in", e);
+  if (e != hipSuccess) return fail(c, LTO_EHIP, who, "stage in", e);
   IndirectArgs a{};
   a.tp = p->d_tp; a.tp_stride = (n_prm == 1) ? 0 : 1;
   a.steps = p->integ.steps; a.rtol = p->integ.rtol; a.atol = p->integ.atol; a.max_steps = p->integ.max_steps;
@@ -159,21 +200,57 @@ int lto_guided_flight_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, cons
   g.nom = d_nom; g.K = d_K; g.t = d_t; g.n_nom = n_nom; g.n_nodes = n; g.n_batch = B; g.every = update_every;
   g.x0 = d_x0; g.nav = with_nav ? d_nav : nullptr;
   g.x_final = d_xf; g.lam_final = lam_final ? d_lf : nullptr; g.dv = d_dv; g.nodes = X_nodes ? d_nd : nullptr;
-  g.nacc = d_acc; g.nrej = d_rej; g.status = d_status;
+  g.nacc = d_acc; g.nrej = d_rej; g.status = d_status; g.nx = nx;
   timing_begin(c, st);
   e = launch_guided_flight(p->pm, p->integ.method, a, g, st);
   timing_end(c, st);
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_guided_flight", e);
-  e = lanes_out(d_xf, 6, B, d_xfa, x_final, st);
-  if (e == hipSuccess && lam_final) e = lanes_out(d_lf, 6, B, d_lfa, lam_final, st);
+  e = lanes_out(d_xf, nx, B, d_xfa, x_final, st);
+  if (e == hipSuccess && lam_final) e = lanes_out(d_lf, nx, B, d_lfa, lam_final, st);
   if (e == hipSuccess && X_nodes) e = lanes_out(d_nd, r_nodes, B, d_nda, X_nodes, st);
   if (e == hipSuccess) e = hipMemcpyAsync(dv, d_dv, sizeof(double) * B, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && accepted) e = hipMemcpyAsync(accepted, d_acc, sizeof(int) * B, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && rejected) e = hipMemcpyAsync(rejected, d_rej, sizeof(int) * B, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(status, d_status, sizeof(int) * B, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = call.wait();
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "lto_guided_flight_batch: stage out", e);
+  if (e != hipSuccess) return fail(c, LTO_EHIP, who, "stage out", e);
   return LTO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lto_guidance_gains_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                             const lto_params* prm, int n_prm, const lto_integrator* integ, double sing_tol, double* K,
+                             double* pivot, int* status) {
+  return gains_batch(12, "lto_guidance_gains_batch", c, ndim, n_nodes, n_batch, XC, t, n_tgrids, prm, n_prm, integ, sing_tol, K, pivot,
+                     status);
+}
+
+int lto_guidance_gains(lto_ctx* c, int ndim, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                       const lto_integrator* integ, double sing_tol, double* K, double* pivot, int* status) {
+  return lto_guidance_gains_batch(c, ndim, n_nodes, 1, XC, t, 1, prm, 1, integ, sing_tol, K, pivot, status);
+}
+
+int lto_guidance_gains_mass_batch(lto_ctx* c, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                                  const lto_params* prm, int n_prm, const lto_integrator* integ, double sing_tol, double* K,
+                                  double* pivot, int* status) {
+  return gains_batch(14, "lto_guidance_gains_mass_batch", c, 14, n_nodes, n_batch, XC, t, n_tgrids, prm, n_prm, integ, sing_tol, K,
+                     pivot, status);
+}
+
+int lto_guidance_gains_mass(lto_ctx* c, int n_nodes, const double* XC, const double* t, const lto_params* prm,
+                            const lto_integrator* integ, double sing_tol, double* K, double* pivot, int* status) {
+  return lto_guidance_gains_mass_batch(c, n_nodes, 1, XC, t, 1, prm, 1, integ, sing_tol, K, pivot, status);
+}
+
+int lto_guided_flight_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC_nom, const double* t, const double* K,
+                            int n_nom, const double* x0, int update_every, const double* nav, const lto_params* prm, int n_prm,
+                            const lto_integrator* integ, double* x_final, double* lam_final, double* dv, double* X_nodes,
+                            int* accepted, int* rejected, int* status) {
+  return flight_batch(12, "lto_guided_flight_batch", c, ndim, n_nodes, n_batch, XC_nom, t, K, n_nom, x0, update_every, nav, prm, n_prm,
+                      integ, x_final, lam_final, dv, X_nodes, accepted, rejected, status);
 }
 
 int lto_guided_flight(lto_ctx* c, int ndim, int n_nodes, const double* XC_nom, const double* t, const double* K, const double* x0,
@@ -181,6 +258,21 @@ int lto_guided_flight(lto_ctx* c, int ndim, int n_nodes, const double* XC_nom, c
                       double* lam_final, double* dv, double* X_nodes, int* accepted, int* rejected, int* status) {
   return lto_guided_flight_batch(c, ndim, n_nodes, 1, XC_nom, t, K, 1, x0, update_every, nav, prm, 1, integ, x_final, lam_final, dv,
                                  X_nodes, accepted, rejected, status);
+}
+
+int lto_guided_flight_mass_batch(lto_ctx* c, int n_nodes, int n_batch, const double* XC_nom, const double* t, const double* K,
+                                 int n_nom, const double* x0, int update_every, const double* nav, const lto_params* prm, int n_prm,
+                                 const lto_integrator* integ, double* x_final, double* lam_final, double* dv, double* X_nodes,
+                                 int* accepted, int* rejected, int* status) {
+  return flight_batch(14, "lto_guided_flight_mass_batch", c, 14, n_nodes, n_batch, XC_nom, t, K, n_nom, x0, update_every, nav, prm,
+                      n_prm, integ, x_final, lam_final, dv, X_nodes, accepted, rejected, status);
+}
+
+int lto_guided_flight_mass(lto_ctx* c, int n_nodes, const double* XC_nom, const double* t, const double* K, const double* x0,
+                           int update_every, const double* nav, const lto_params* prm, const lto_integrator* integ, double* x_final,
+                           double* lam_final, double* dv, double* X_nodes, int* accepted, int* rejected, int* status) {
+  return lto_guided_flight_mass_batch(c, n_nodes, 1, XC_nom, t, K, 1, x0, update_every, nav, prm, 1, integ, x_final, lam_final, dv,
+                                      X_nodes, accepted, rejected, status);
 }
 
 }  // extern "C"

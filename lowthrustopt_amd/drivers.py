@@ -1555,6 +1555,106 @@ def dispersion_guided(ctx, XC_all, t_TU, prm, n_samples, sigma_r_km, sigma_v_ms,
     return out
 
 
+def neighbouring_gains_mass(ctx, XC_all, t_TU, prm, integ=None, sing_tol=1e-10):
+    """neighbouring_gains for solutions of the 14-row variable-mass system (hotpath.guidance_gains_mass): XC_all
+    [14 x n] or [14 x n x B], Isp in the mass slot of prm.  Returns a dict: K [7 x 7 x (n-1) (x B)], pivot, status, ok."""
+    g = hotpath.guidance_gains_mass(XC_all, t_TU, prm, integ, sing_tol, ctx)
+    return dict(K=g.K, pivot=g.pivot, status=g.status, ok=np.asarray(g.status) == 0)
+
+
+def fly_guided_mass(ctx, XC_all, t_TU, prm, x0=None, n_guid=None, update_every=1, nav=None, integ=None):
+    """fly_guided for a solution of the 14-row variable-mass system (hotpath.guidance_gains_mass and hotpath.guided_flight_mass,
+    DESIGN 4.24).  XC_all [14 x n] with its grid t_TU and its parameters prm (Isp in the mass slot); n_guid resamples through
+    hotpath.densify_mass; x0 [7 x B] (r, v, m; default: the solution's own first node); nav [7 x n_upd (x B)] is added to the
+    measured state, the mass included, at the updates.  Returns fly_guided's dict with x_final and lam_final [7 x B], K
+    [7 x 7 x (n-1)], and besides miss_m_kg (final mass minus the solution's last node's), propellant_kg = x0[6] - x_final[6] per
+    start, propellant_nominal_kg (the guided flight of the nominal start, which rides in the same call) and propellant_excess_kg
+    = propellant_kg - propellant_nominal_kg."""
+    XC = np.asarray(XC_all, dtype=np.float64)
+    if XC.ndim != 2 or XC.shape[0] != 14:
+        raise ValueError("XC_all must be [14 x n]")
+    t = np.asarray(t_TU, dtype=np.float64)
+    if t.shape != (XC.shape[1],):
+        raise ValueError("t_TU must hold one time per node")
+    p = prm if isinstance(prm, hotpath.LtoParams) else hotpath.make_params(*prm)
+    if n_guid is not None:
+        if int(n_guid) < 2:
+            raise ValueError("n_guid must be >= 2")
+        XC, t = hotpath.densify_mass(XC, t, p, int(n_guid), integ, ctx)
+    n = XC.shape[1]
+    n_upd = hotpath.guided_updates(n, update_every)
+    x0 = XC[:7, :1].copy() if x0 is None else np.asarray(x0, dtype=np.float64).reshape(7, -1)
+    B = x0.shape[1]
+    if nav is not None:
+        nav = np.asarray(nav, dtype=np.float64)
+        if nav.shape not in ((7, n_upd), (7, n_upd, B)):
+            raise ValueError("nav must be [7 x %d] or [7 x %d x %d]" % (n_upd, n_upd, B))
+        if nav.ndim == 2:
+            nav = np.repeat(nav[:, :, None], B, axis=2)
+    g = hotpath.guidance_gains_mass(XC, t, p, integ, ctx=ctx)
+    if int(update_every) > 0 and g.status != 0:
+        raise ValueError("the solution has no finite gains (status %d, smallest pivot ratio %.3g): fly it with update_every = 0"
+                         % (g.status, np.nanmin(g.pivot)))
+    K = g.K if g.status == 0 else np.zeros_like(g.K)
+    x_all = np.concatenate([XC[:7, :1], x0], axis=1)         # column 0: the nominal start, the reference of the excesses
+    nav_all = None if nav is None else np.concatenate([np.zeros((7, n_upd, 1)), nav], axis=2)
+    r = hotpath.guided_flight_mass(XC, t, K, x_all, p, update_every, nav_all, integ, ctx=ctx)
+    dv_ms = r.dv * p.DU / p.TU * 1e3
+    prop = x_all[6] - r.x_final[6]
+    out = dict(x_final=r.x_final[:, 1:], lam_final=r.lam_final[:, 1:], dv=r.dv[1:], dv_ms=dv_ms[1:], dv_nominal_ms=float(dv_ms[0]),
+               dv_excess_ms=dv_ms[1:] - dv_ms[0], propellant_kg=prop[1:], propellant_nominal_kg=float(prop[0]),
+               propellant_excess_kg=prop[1:] - prop[0], status=r.status[1:], accepted=r.accepted[1:], rejected=r.rejected[1:],
+               K=g.K, pivot=g.pivot, gain_status=g.status, XC_guid=XC, t_guid=t)
+    out.update(replay_misses(out["x_final"], XC[:7, -1], p.DU, p.TU))
+    return out
+
+
+def guided_nav_mass(n_updates, n_samples, nav_sigma_m_kg, seed):
+    """nav_m [n_updates x n_samples]: Gaussian errors of nav_sigma_m_kg on the measured mass from numpy.random.default_rng(seed);
+    sample 0 navigates without error."""
+    e = np.random.default_rng(seed).standard_normal((int(n_updates), int(n_samples))) * float(nav_sigma_m_kg)
+    e[:, 0] = 0.0
+    return e
+
+
+def dispersion_guided_mass(ctx, XC_all, t_TU, prm, n_samples, sigma_r_km, sigma_v_ms, seed, n_guid=None, update_every=1, integ=None,
+                           nav_sigma_r_km=None, nav_sigma_v_ms=None, nav_seed=None, sigma_m_kg=None, m_seed=None,
+                           nav_sigma_m_kg=None, nav_m_seed=None):
+    """dispersion_guided for a solution of the 14-row variable-mass system: the starts `dispersion` makes for that solution (the
+    same dispersion_starts draws, sample 0 undisturbed, the mass row left alone), all flown by fly_guided_mass in one call.
+    sigma_m_kg adds a Gaussian error to the start mass of every sample but 0 from numpy.random.default_rng(m_seed);
+    nav_sigma_r_km / nav_sigma_v_ms (both or neither; guided_nav, nav_seed) and nav_sigma_m_kg (guided_nav_mass, nav_m_seed) add
+    navigation errors at every update.  Returns fly_guided_mass's dict plus x0, nav and, over the samples of status 0, percentiles
+    = {"miss_r_km": {50: .., 95: .., 99: ..}, "miss_v_ms": {..}, "dv_excess_ms": {..}, "propellant_excess_kg": {..}}."""
+    XC = np.asarray(XC_all, dtype=np.float64)
+    if XC.ndim != 2 or XC.shape[0] != 14:
+        raise ValueError("XC_all must be [14 x n]")
+    if (nav_sigma_r_km is None) != (nav_sigma_v_ms is None):
+        raise ValueError("nav_sigma_r_km and nav_sigma_v_ms are given together")
+    p = prm if isinstance(prm, hotpath.LtoParams) else hotpath.make_params(*prm)
+    n_samples = int(n_samples)
+    x0 = dispersion_starts(XC[:7, 0], n_samples, sigma_r_km, sigma_v_ms, seed, p.DU, p.TU)
+    if sigma_m_kg is not None:
+        em = np.random.default_rng(m_seed).standard_normal(n_samples) * float(sigma_m_kg)
+        em[0] = 0.0
+        x0[6] += em
+    nav = None
+    if nav_sigma_r_km is not None or nav_sigma_m_kg is not None:
+        n_upd = hotpath.guided_updates(XC.shape[1] if n_guid is None else int(n_guid), update_every)
+        nav = np.zeros((7, n_upd, n_samples), order="F")
+        if nav_sigma_r_km is not None:
+            nav[0:6] = guided_nav(n_upd, n_samples, nav_sigma_r_km, nav_sigma_v_ms, nav_seed, p.DU, p.TU)
+        if nav_sigma_m_kg is not None:
+            nav[6] = guided_nav_mass(n_upd, n_samples, nav_sigma_m_kg, nav_m_seed)
+    out = fly_guided_mass(ctx, XC, t_TU, p, x0, n_guid, update_every, nav, integ)
+    ok = np.asarray(out["status"]) == 0
+    out["x0"] = x0
+    out["nav"] = nav
+    out["percentiles"] = {k: {q: (float(np.percentile(out[k][ok], q)) if ok.any() else float("nan")) for q in (50, 95, 99)}
+                          for k in ("miss_r_km", "miss_v_ms", "dv_excess_ms", "propellant_excess_kg")}
+    return out
+
+
 def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, maxIter=10, max_waves=12, ctx=None, verbose=True,
                    arcs=False):
     """Solve the whole smoothing ladder rho_0 > rho_1 > ... concurrently.  reduceFuel_indirect walks the

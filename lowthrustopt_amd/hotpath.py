@@ -772,15 +772,20 @@ def guided_flight(XC_nom, t_TU, K, x0, params, update_every=1, nav=None, integ=N
     or [6 x B]; nav [6 x n_upd] / [6 x n_upd x B] or None, n_upd = guided_updates(n, update_every): the navigation error added to
     the measured state at update j; params one tuple or one per start.  At node k with k % update_every == 0 the costate is reset
     to lambda_nom,k + K_k (x - x_nom,k + e_j); update_every = 0 never updates.  Returns a GuidedFlight."""
+    return _guided_flight(6, XC_nom, t_TU, K, x0, params, update_every, nav, integ, with_nodes, ctx)
+
+
+def _guided_flight(nx, XC_nom, t_TU, K, x0, params, update_every, nav, integ, with_nodes, ctx):
+    """guided_flight (nx = 6: ndim as XC_nom has it, the library answers) and guided_flight_mass (nx = 7: XC_nom has 14 rows)."""
     X = _f64(x0)
-    if X.ndim not in (1, 2) or X.shape[0] != 6:
-        raise ValueError("x0 must be [6] or [6 x B]")
+    if X.ndim not in (1, 2) or X.shape[0] != nx:
+        raise ValueError("x0 must be [%d] or [%d x B]" % (nx, nx))
     batched = X.ndim == 2
-    X2 = np.asfortranarray(X.reshape(6, -1, order="F"))
+    X2 = np.asfortranarray(X.reshape(nx, -1, order="F"))
     B = X2.shape[1]
     XC = _f64(XC_nom)
-    if XC.ndim not in (2, 3):
-        raise ValueError("XC_nom must be [ndim x n] or [ndim x n x n_nom]")
+    if XC.ndim not in (2, 3) or (nx == 7 and XC.shape[0] != 14):
+        raise ValueError("XC_nom must be [ndim x n] or [ndim x n x n_nom]" if nx == 6 else "XC_nom must be [14 x n] or [14 x n x n_nom]")
     XC3 = np.asfortranarray(XC.reshape(XC.shape[0], XC.shape[1], -1, order="F"))
     ndim, n, n_nom = XC3.shape
     if n_nom != 1 and n_nom != B:
@@ -790,33 +795,67 @@ def guided_flight(XC_nom, t_TU, K, x0, params, update_every=1, nav=None, integ=N
         raise ValueError("t_TU must be [n] or [n x n_nom]")
     t = np.asfortranarray(t.reshape(n, n_nom, order="F"))
     Kg = _f64(K)
-    if Kg.size != 36 * max(n - 1, 0) * n_nom or Kg.shape[:2] != (6, 6):
-        raise ValueError("K must be [6 x 6 x (n-1)] or [6 x 6 x (n-1) x n_nom]")
-    Kg = np.asfortranarray(Kg.reshape(6, 6, n - 1, n_nom, order="F"))
+    if Kg.size != nx * nx * max(n - 1, 0) * n_nom or Kg.shape[:2] != (nx, nx):
+        raise ValueError("K must be [%d x %d x (n-1)] or [%d x %d x (n-1) x n_nom]" % (nx, nx, nx, nx))
+    Kg = np.asfortranarray(Kg.reshape(nx, nx, n - 1, n_nom, order="F"))
     every = int(update_every)
     n_upd = guided_updates(n, every)
     E = None
     if nav is not None and n_upd > 0:
         E = _f64(nav)
-        if E.shape[0] != 6 or E.size != 6 * n_upd * B:
-            raise ValueError("nav must be [6 x n_upd x B] with n_upd = %d" % n_upd)
-        E = np.asfortranarray(E.reshape(6, n_upd, B, order="F"))
+        if E.shape[0] != nx or E.size != nx * n_upd * B:
+            raise ValueError("nav must be [%d x n_upd x B] with n_upd = %d" % (nx, n_upd))
+        E = np.asfortranarray(E.reshape(nx, n_upd, B, order="F"))
     prm, nprm = _params_array(params)
     if nprm != 1 and nprm != B:
         raise ValueError("params must be one tuple or one per start")
-    x_final, lam_final = np.zeros((6, B), order="F"), np.zeros((6, B), order="F")
+    if nx == 7 and not all(prm[k].mass > 0.0 for k in range(nprm)):
+        raise ValueError("Isp (the mass slot of 14-row params) must be positive")
+    x_final, lam_final = np.zeros((nx, B), order="F"), np.zeros((nx, B), order="F")
     dv = np.zeros(B)
-    nodes = np.zeros((6, n, B), order="F") if with_nodes else None
+    nodes = np.zeros((nx, n, B), order="F") if with_nodes else None
     acc, rej, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
     ctx = ctx or default_context()
     integ = integ or integrator()
-    ctx.check(ctx.fn("guided_flight_batch")(ctx.handle, ndim, n, B, _ptr(XC3), _ptr(t), _ptr(Kg), n_nom, _ptr(X2), every, _ptr(E), prm,
-                                            nprm, C.byref(integ), _ptr(x_final), _ptr(lam_final), _ptr(dv), _ptr(nodes), _ptr(acc),
-                                            _ptr(rej), _ptr(status)))
+    tail = (n, B, _ptr(XC3), _ptr(t), _ptr(Kg), n_nom, _ptr(X2), every, _ptr(E), prm, nprm, C.byref(integ), _ptr(x_final),
+            _ptr(lam_final), _ptr(dv), _ptr(nodes), _ptr(acc), _ptr(rej), _ptr(status))
+    if nx == 6:
+        ctx.check(ctx.fn("guided_flight_batch")(ctx.handle, ndim, *tail))
+    else:
+        ctx.check(ctx.fn("guided_flight_mass_batch")(ctx.handle, *tail))
     if not batched:
         return GuidedFlight(x_final[:, 0], lam_final[:, 0], float(dv[0]), None if nodes is None else nodes[:, :, 0], int(acc[0]),
                             int(rej[0]), int(status[0]))
     return GuidedFlight(x_final, lam_final, dv, nodes, acc, rej, status)
+
+
+def guidance_gains_mass(XC_all, t_TU, params, integ=None, sing_tol=1e-10, ctx=None):
+    """guidance_gains for solutions of the 14-row variable-mass system (lto_guidance_gains_mass_batch): XC_all [14 x n]
+    or [14 x n x B], params with Isp in the mass slot.  The gains keep d r_f = d v_f = 0 and d lambda_m(t_f) = 0, the final mass is
+    free.  Returns a GuidanceGains with K [7 x 7 x (n-1) x B]: d lambda_k = K[:, :, k] d x_k, x = (r, v, m)."""
+    XC = _f64(XC_all)
+    if XC.ndim not in (2, 3) or XC.shape[0] != 14:
+        raise ValueError("XC_all must be [14 x n] or [14 x n x B]")
+    prm, nprm = _params_array(params)
+    if not all(prm[k].mass > 0.0 for k in range(nprm)):
+        raise ValueError("Isp (the mass slot of 14-row params) must be positive")
+    ctx, (ndim, n, B, batched), args = _indirect_args(XC, t_TU, params, integ, ctx)
+    S = max(n - 1, 0)
+    K = np.zeros((7, 7, S, B), order="F")
+    pivot = np.zeros((S, B), order="F")
+    status = np.zeros(B, dtype=np.int32)
+    ctx.check(ctx.fn("guidance_gains_mass_batch")(args[0], *args[2:], float(sing_tol), _ptr(K), _ptr(pivot), _ptr(status)))
+    if not batched:
+        return GuidanceGains(K[:, :, :, 0], pivot[:, 0], int(status[0]))
+    return GuidanceGains(K, pivot, status)
+
+
+def guided_flight_mass(XC_nom, t_TU, K, x0, params, update_every=1, nav=None, integ=None, with_nodes=False, ctx=None):
+    """guided_flight for the 14-row variable-mass system (lto_guided_flight_mass_batch): XC_nom [14 x n (x B)], K
+    [7 x 7 x (n-1) (x B)], x0 [7] or [7 x B] (r, v, m), nav [7 x n_upd (x B)] or None, params with Isp in the mass slot.  The update
+    resets all seven costates from the seven measured states, the mass included.  Returns a GuidedFlight with x_final and
+    lam_final [7 x B] (x_final[6] the final mass) and nodes [7 x n x B]."""
+    return _guided_flight(7, XC_nom, t_TU, K, x0, params, update_every, nav, integ, with_nodes, ctx)
 
 
 def direct_defectCalc(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None):
