@@ -435,6 +435,43 @@ int lto_direct_costates(lto_ctx* ctx, int nstate, int n_nodes, const double* X, 
 int lto_stack_guess_batch(lto_ctx* ctx, int n_nodes, int n_batch, double MU, const lto_direct_orbits* orbits,
                           const lto_integrator* integ, const double* tau1, const double* tof1, const double* tof2, double* X_out,
                           double* t_out, double* tau_out, double* gap_out, int* status);
+/* Periodic orbits of the CRTBP (mass ratio MU) with the xz-plane symmetry -- halo and planar Lyapunov orbits -- for n_batch orbits
+ * side by side.  A result does not depend on its batch: orbit b equals its single call bit for bit.
+ *
+ * lto_halo_correct_batch: the differential corrector.  seeds [6 x n_batch]: rows 0, 2 and 4 are read (x0, z0, vy0); the flight
+ * starts at (x0, 0, z0, 0, vy0, 0) and ends at the first return to y = 0, located to adjacent doubles in time.  The residual there
+ * is (vx, vz); one Newton step solves the 2 x 2 system of the state-transition matrix, corrected for the moving crossing time, for
+ *   LTO_HALO_HOLD_Z0   x0 and vy0          LTO_HALO_HOLD_X0   z0 and vy0
+ *   LTO_HALO_PLANAR    vy0 alone, residual vx (z0 must be 0)
+ * and the loop ends when max |residual| < tol or after max_iter steps, all inside one kernel.  The flight is LTO_DOP853_ADAPTIVE at
+ * integ's rtol / atol / max_steps (the error norm over the state and all 36 variational components) searched up to t_max, or LTO_RK4
+ * with integ->steps steps over t_max (the half period is what the call looks for); any other method: LTO_EUNSUPPORTED.
+ * Outputs: state_out [6 x n_batch] (the corrected start), period_out [n_batch] = 2 x the crossing time, resid_out [n_batch] (may be
+ * NULL), iterations [n_batch] = Newton steps taken (may be NULL), history [(max_iter + 1) x n_batch] = the residual of every flight,
+ * NaN past the last (may be NULL), status [n_batch]: 0 converged; 1 max_iter reached (max_iter = 0: the seed is evaluated);
+ * 2 unusable seed or flight (not finite, vy0 = 0, z0 != 0 with LTO_HALO_PLANAR, no crossing before t_max, max_steps used up);
+ * 3 singular step, |det| <= sing_tol x the product of the Jacobian's row norms.  Status 2 and 3: state, period and residual NaN.
+ * LTO_EINVAL: n_batch < 1, max_iter < 0, tol <= 0, t_max not finite or <= 0, sing_tol outside [0, 1), MU outside (0, 1), an unknown
+ * mode, LTO_RK4 with steps < 1.
+ *
+ * lto_halo_table_batch: one revolution from state0 [6 x n_batch] over period [n_batch], the state-transition matrix carried through,
+ * stopped at t_i = i P / (n_samples - 1): X_out [6 x n_samples x n_batch] (the last column is the integrated state, not a copy of
+ * the first), tau_out [n_samples] = i / (n_samples - 1) (the layout lto_direct_orbits reads), M_out [6 x 6 x n_batch] = Phi(P),
+ * closure [n_batch] = max |x(P) - x(0)|, jacobi [2 x n_batch] = (C at the start; the largest |C(t_i) - C(0)|), C = x^2 + y^2 +
+ * 2 (1 - MU) / r1 + 2 MU / r2 - v^2, nu [2 x n_batch] = the stability indices -(alpha +- sqrt(alpha^2 - 4 beta + 8)) / 4 with
+ * alpha = 2 - tr M, beta = (alpha^2 + 2 - tr M^2) / 2 (NaN where the discriminant is negative), status [n_batch]: 0, or 2 where the
+ * flight has no finite result (a period that is not finite and > 0, max_steps used up in a sample interval).  Every output but X_out
+ * and status may be NULL.  LTO_DOP853_ADAPTIVE, or LTO_RK4 with integ->steps steps per sample interval; any other method:
+ * LTO_EUNSUPPORTED.  LTO_EINVAL: n_samples < 2, n_batch < 1, MU outside (0, 1), 6 n_samples n_batch > 2^31 - 1. */
+#define LTO_HALO_HOLD_Z0 0
+#define LTO_HALO_HOLD_X0 1
+#define LTO_HALO_PLANAR 2
+int lto_halo_correct_batch(lto_ctx* ctx, int n_batch, double MU, int mode, const double* seeds, double tol, int max_iter,
+                           double t_max, double sing_tol, const lto_integrator* integ, double* state_out, double* period_out,
+                           double* resid_out, int* iterations, double* history, int* status);
+int lto_halo_table_batch(lto_ctx* ctx, int n_samples, int n_batch, double MU, const double* state0, const double* period,
+                         const lto_integrator* integ, double* X_out, double* tau_out, double* M_out, double* closure,
+                         double* jacobi, double* nu, int* status);
 /* Mesh re-distribution of converged 12-dim solutions (the indirect method's counterpart of meshRefine_direct): the
  * nodes of XC [12 x n_nodes x n_batch] on t [n_nodes x n_tgrids] (n_tgrids = 1 or n_batch) are moved, and their number changed to
  * n_new, so that every new segment carries the same share of a per-segment monitor w_i > 0.  Per trajectory:

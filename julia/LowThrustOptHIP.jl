@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_table,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -812,6 +812,42 @@ function stack_guess(ctx::LtoContext, tau1::Vector{Float64}, tof1::Vector{Float6
     end
     check(ctx, rc)
     (X, t, tau, gap, Int.(status))
+end
+
+# The differential corrector of periodic orbits with the xz-plane symmetry (`lto_halo_correct_batch`, DESIGN 4.25) for B seeds side by
+# side: seeds [6 x B] = (x0, ., z0, ., vy0, .), mode 0 hold z0 / 1 hold x0 / 2 planar.  Returns (state [6 x B], period [B], resid [B],
+# iterations [B], history [(max_iter + 1) x B], status [B]).
+function halo_correct(ctx::LtoContext, seeds::Matrix{Float64}, mode::Integer, MU; tol = 1e-12, max_iter::Integer = 15, t_max = 10.0,
+                      sing_tol = 1e-12, integ::LtoIntegrator = LtoIntegrator())
+    size(seeds, 1) == 6 || error("halo_correct: seeds must be 6 x B")
+    B = size(seeds, 2)
+    state = zeros(6, B); period = zeros(B); resid = zeros(B); hist = zeros(max_iter + 1, B)
+    its = zeros(Cint, B); status = zeros(Cint, B)
+    rc = ccall((:lto_halo_correct_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cdouble, Cint, Ptr{Cdouble}, Cdouble, Cint, Cdouble, Cdouble, Ref{LtoIntegrator}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, B, Float64(MU), mode, seeds, Float64(tol), max_iter, Float64(t_max), Float64(sing_tol), Ref(integ), state,
+               period, resid, its, hist, status)
+    check(ctx, rc)
+    (state, period, resid, Int.(its), hist, Int.(status))
+end
+
+# One revolution of B periodic orbits from (state0 [6 x B], period [B]) at n_samples equal times, the state-transition matrix carried
+# through (`lto_halo_table_batch`, DESIGN 4.25).  Returns (times [n], X [6 x n x B], M [6 x 6 x B], closure [B], jacobi [2 x B],
+# nu [2 x B], status [B]); (times, X[:, :, b]) is an orbit table as interpEndStates and direct_solve_free take it.
+function halo_table(ctx::LtoContext, state0::Matrix{Float64}, period::Vector{Float64}, n_samples::Integer, MU;
+                    integ::LtoIntegrator = LtoIntegrator())
+    size(state0, 1) == 6 || error("halo_table: state0 must be 6 x B")
+    B = size(state0, 2)
+    length(period) == B || error("halo_table: one period per orbit")
+    X = zeros(6, n_samples, B); times = zeros(n_samples); M = zeros(6, 6, B); closure = zeros(B); jac = zeros(2, B); nu = zeros(2, B)
+    status = zeros(Cint, B)
+    rc = ccall((:lto_halo_table_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoIntegrator}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, n_samples, B, Float64(MU), state0, period, Ref(integ), X, times, M, closure, jac, nu, status)
+    check(ctx, rc)
+    (times, X, M, closure, jac, nu, Int.(status))
 end
 
 # optimizeTraj with flagEnd = true: one Jacobian sweep and the exact free-end QP step.  Returns (x_update, u_update, p1_update,

@@ -97,6 +97,10 @@ SIGNATURES = {
                                              _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_stack_guess_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.POINTER(LtoDirectOrbits), C.POINTER(LtoIntegrator), _vp,
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_halo_correct_batch": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _vp, C.c_double, C.c_int, C.c_double, C.c_double,
+                                         C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_halo_table_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, _vp, C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
     "lto_indirect_remesh_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.POINTER(LtoParams), C.c_int,
                                             C.POINTER(LtoIntegrator), C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp, _vp]),

@@ -353,6 +353,36 @@ struct StackFindArgs {
   const double* X; double* X_out; int* status;
 };
 hipError_t launch_stack_find(const StackFindArgs& f, hipStream_t st);
+// Periodic orbits with the xz-plane symmetry (kernels_halo.hip): 8 lanes per orbit, 8 orbits per wavefront.  Every
+// array is in the caller's layout (orbit b's record contiguous).
+// The differential corrector: seed [6][B] (x0, z0 and vy0 are read: rows 0, 2, 4), mode 0 hold z0 / 1 hold x0 / 2 planar.
+struct HaloCorrectArgs {
+  const double* seed;
+  int B, mode, max_iter;
+  double MU, tol, t_max, sing_tol;
+  int steps;                                 // RK4: steps over t_max
+  double rtol, atol; int max_steps;          // DOP853
+  double* state;                             // [6][B]
+  double* period; double* resid;             // [B]
+  double* hist;                              // [max_iter + 1][B]
+  int* iters; int* status;                   // [B]
+};
+// method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
+hipError_t launch_halo_correct(int method, const HaloCorrectArgs& a, hipStream_t st);
+// One revolution from state0 [6][B] over period [B], sampled at t_i = i P / (n - 1)
+struct HaloTableArgs {
+  const double* state0; const double* period;
+  int n, B;
+  double MU;
+  int steps;                                 // RK4: steps per sample interval
+  double rtol, atol; int max_steps;          // DOP853: max_steps counts per sample interval
+  double* X;                                 // [6][n][B]
+  double* M;                                 // [6][6][B]
+  double* closure;                           // [B]
+  double* jacobi; double* nu;                // [2][B]
+  int* status;                               // [B]
+};
+hipError_t launch_halo_table(int method, const HaloTableArgs& a, hipStream_t st);
 // Mesh equidistribution of the indirect method (kernels_remesh.hip).  Grid: per trajectory b the monitor of old segment
 // i is w[b (n-1) + i], or nacc + nrej there when w is null; old grids t[b t_stride + i].
 // Out: t_out [n_batch][n_new] and seg_of [n_batch][n_new], the old node each new one is propagated from.

@@ -1,0 +1,312 @@
+// kernels_halo.hip -- periodic orbits of the CRTBP with the xz-plane symmetry (halo, planar Lyapunov), B orbits side by side
+// (DESIGN 4.25), gfx950.
+//
+// One GROUP of 8 adjacent lanes per orbit, 8 orbits per wavefront (dop853_group.hpp).  Lane c < 6 of a group integrates the ballistic
+// base state with column c of Phi = dx/dx0 -- 12 components, the gravity gradient formed once per stage -- and lanes 6 and 7 shadow
+// lane 0 and store nothing.  The lanes of a group take identical steps (the error norm runs over the base and all 36 variational
+// components), and everything a group decides it decides from the base, which every lane carries: no lane of a group ever leaves
+// the others.  A group beyond the batch shadows the last orbit.  No LDS, plain vector stores.
+//
+// k_halo_correct: the differential corrector, the whole Newton loop in the kernel.  Per iteration: fly from (x0, 0, z0, 0, vy0, 0)
+// to the first return to y = 0 -- the first accepted step at whose end y has left the side vy0 sent it to, the crossing bracketed
+// by trial steps of the same formula from the step's start (bisection of the step length until the bracket's ends are adjacent
+// doubles in time, at most 60 halvings; the rule of kernels_events.hip), the state and Phi there from one more trial step -- then
+// the residual (vx, vz) and the 2 x 2 Jacobian  Phi[(3,5),(i,4)] - f[(3,5)] Phi[1,(i,4)] / f[1]  (the second term: the crossing
+// time moves with the unknowns), solved in every lane of the group alike.
+//
+// k_halo_table: one revolution from (state0, P) with Phi carried through, stopped at t_i = i P / (n - 1), every sample interval a
+// span of its own; the samples, M = Phi(P), the closure, the Jacobi constant and its drift, the stability indices.
+#include "kernels.hpp"
+#include "dop853_group.hpp"
+
+namespace lto {
+
+namespace {
+
+// The CRTBP without thrust and one column c of its variational equations: y = (r, v, c_r, c_v), c' = [0 I; G 2W] c.
+struct SysHaloVar {
+  static constexpr int DIM = 12;
+  double MU;
+  __device__ __forceinline__ void rhs(const double (&y)[12], double (&k)[12]) const {
+    const double x = y[0], yy = y[1], z = y[2];
+    const double a = x + MU, b = a - 1.0;
+    const double yz2 = __builtin_fma(yy, yy, z * z);
+    const double d1 = __builtin_fma(a, a, yz2), d2 = __builtin_fma(b, b, yz2);
+    const double i1 = rsqrt_nr(d1), i2 = rsqrt_nr(d2);
+    const double c1 = (1.0 - MU) * (i1 * i1 * i1), c2 = MU * (i2 * i2 * i2);
+    const double cs = c1 + c2;
+    k[0] = y[3]; k[1] = y[4]; k[2] = y[5];
+    k[3] = __builtin_fma(-c1, a, __builtin_fma(-c2, b, __builtin_fma(2.0, y[4], x)));
+    k[4] = __builtin_fma(-cs, yy, __builtin_fma(-2.0, y[3], yy));
+    k[5] = -cs * z;
+    // gravity gradient G = d(acceleration) / d(position), symmetric
+    const double q1 = 3.0 * c1 * (i1 * i1), q2 = 3.0 * c2 * (i2 * i2), qs = q1 + q2;
+    const double qa = __builtin_fma(q1, a, q2 * b);
+    const double gxx = __builtin_fma(q1 * a, a, __builtin_fma(q2 * b, b, 1.0 - cs));
+    const double gyy = __builtin_fma(qs * yy, yy, 1.0 - cs);
+    const double gzz = __builtin_fma(qs * z, z, -cs);
+    const double gxy = qa * yy, gxz = qa * z, gyz = qs * yy * z;
+    k[6] = y[9]; k[7] = y[10]; k[8] = y[11];
+    k[9] = __builtin_fma(gxx, y[6], __builtin_fma(gxy, y[7], __builtin_fma(gxz, y[8], 2.0 * y[10])));
+    k[10] = __builtin_fma(gxy, y[6], __builtin_fma(gyy, y[7], __builtin_fma(gyz, y[8], -2.0 * y[9])));
+    k[11] = __builtin_fma(gxz, y[6], __builtin_fma(gyz, y[7], gzz * y[8]));
+  }
+};
+
+// Jacobi constant C = x^2 + y^2 + 2 (1 - MU) / r1 + 2 MU / r2 - v^2
+__device__ __forceinline__ double jacobi_constant(const double MU, const double (&y)[12]) {
+  const double a = y[0] + MU, b = a - 1.0;
+  const double yz2 = __builtin_fma(y[1], y[1], y[2] * y[2]);
+  const double r1 = sqrt(__builtin_fma(a, a, yz2)), r2 = sqrt(__builtin_fma(b, b, yz2));
+  const double v2 = __builtin_fma(y[3], y[3], __builtin_fma(y[4], y[4], y[5] * y[5]));
+  return __builtin_fma(y[0], y[0], y[1] * y[1]) + 2.0 * (1.0 - MU) / r1 + 2.0 * MU / r2 - v2;
+}
+
+__device__ __forceinline__ bool finite12(const double (&y)[12]) {
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) s += y[i];
+  return (s - s) == 0.0;
+}
+
+// the start of a flight in lane `col`'s view: the base state and column `col` of the identity
+__device__ __forceinline__ void halo_start(const double (&x)[6], const int col, double (&y)[12]) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { y[i] = x[i]; y[6 + i] = (i == col) ? 1.0 : 0.0; }
+}
+
+// The step from time t over h took y across the plane: bracket the crossing in theta (kernels_events.hip locate_crossing's
+// bisection) and return its time, the state one trial step of that length from the step's start in yc.
+// trial(th, yt): the state one step of length th from the step's start; side: the sign of y before the crossing.
+template <class Trial>
+__device__ __forceinline__ double halo_crossing(const double t, const double h, const double side, Trial&& trial, double (&yc)[12]) {
+  double lo = 0.0, hi = 1.0;
+  for (int k = 0; k < 60; ++k) {
+    const double mid = 0.5 * (lo + hi);
+    double yt[12];
+    trial(mid * h, yt);
+    if (side * yt[1] > 0.0) lo = mid;
+    else hi = mid;
+    const double t_lo = __builtin_fma(lo, h, t), t_hi = __builtin_fma(hi, h, t);
+    if (!(t_hi > nextafter(t_lo, __builtin_huge_val()))) break;     // adjacent doubles (or the same one)
+  }
+  trial(hi * h, yc);
+  return __builtin_fma(hi, h, t);
+}
+
+}  // namespace
+
+template <int METHOD>
+__global__ __launch_bounds__(64) void k_halo_correct(const HaloCorrectArgs a) {
+  const int gid = blockIdx.x * 64 + threadIdx.x;
+  const int g = gid >> 3, c = gid & 7;
+  const int gbase = threadIdx.x & ~7;
+  const int b = (g < a.B) ? g : a.B - 1;         // a group beyond the batch shadows the last orbit
+  const int col = (c < 6) ? c : 0;
+  const double colw = (c < 6) ? 1.0 : 0.0;
+  SysHaloVar sys;
+  sys.MU = a.MU;
+  double x0 = a.seed[6 * (long)b + 0], z0 = a.seed[6 * (long)b + 2], vy0 = a.seed[6 * (long)b + 4];
+  const int iu = (a.mode == LTO_HALO_HOLD_X0) ? 2 : 0;  // the position unknown: x0 (hold z0), z0 (hold x0); planar: none
+  const bool planar = a.mode == LTO_HALO_PLANAR;
+  const bool store = (g < a.B) && (c == 0);
+  double* hist = a.hist + (long)(a.max_iter + 1) * b;
+
+  // per-lane flags are doubles (run_dop853's comment, DESIGN.md "Compiler hazards")
+  double status = -1.0;
+  double tc = 0.0, res = __builtin_nan("");
+  int it = 0, nrec = 0;
+  {
+    const double s = x0 + z0 + vy0;
+    if (!((s - s) == 0.0) || vy0 == 0.0 || (planar && z0 != 0.0)) status = 2.0;
+  }
+  while (status < 0.0) {
+    const double xs[6] = {x0, 0.0, z0, 0.0, vy0, 0.0};
+    double y[12], yc[12];
+    halo_start(xs, col, y);
+    const double side = (vy0 > 0.0) ? 1.0 : -1.0;
+    double found = 0.0;
+    if (METHOD == M_RK4) {
+      const double h = a.t_max / (double)a.steps;
+      for (int k = 0; k < a.steps; ++k) {
+        double ys[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) ys[i] = y[i];
+        rk4_step(sys, h, y);
+        if (!(side * y[1] > 0.0)) {
+          if (y[1] == y[1]) {
+            tc = halo_crossing(__builtin_fma((double)k, h, 0.0), h, side, [&](const double th, double (&yt)[12]) {
+#pragma unroll
+              for (int i = 0; i < 12; ++i) yt[i] = ys[i];
+              rk4_step(sys, th, yt);
+            }, yc);
+            found = 1.0;
+          }
+          break;
+        }
+      }
+    } else {
+      int na = 0, nr = 0;
+      (void)run_dop853_group<SysHaloVar, 6, 6>(sys, a.t_max, a.rtol, a.atol, a.max_steps, colw, y, na, nr,
+          [&](const double t, const double h, const double (&ys)[12], double (&K)[13][12], const double (&yn)[12]) -> double {
+        if (side * yn[1] > 0.0) return 0.0;
+        if (yn[1] == yn[1]) {
+          tc = halo_crossing(t, h, side, [&](const double th, double (&yt)[12]) {
+            double E5, E3;
+            (void)dop853_try<SysHaloVar, 6>(sys, th, a.rtol, a.atol, ys, K, yt, E5, E3);
+          }, yc);
+          found = 1.0;
+        }
+        return 1.0;
+      });
+    }
+    if (found == 0.0 || !finite12(yc)) { status = 2.0; break; }
+    // the residual at the crossing
+    res = planar ? fabs(yc[3]) : fmax(fabs(yc[3]), fabs(yc[5]));
+    if (store) hist[it] = res;
+    nrec = it + 1;
+    if (res < a.tol) { status = 0.0; break; }
+    if (it >= a.max_iter) { status = 1.0; break; }
+    // f at the crossing and the entries of Phi the step reads: row r of column j is component 6 + r of lane gbase + j
+    double f[12];
+    sys.rhs(yc, f);
+    const double p1u = __shfl(yc[7], gbase + iu, 64), p3u = __shfl(yc[9], gbase + iu, 64), p5u = __shfl(yc[11], gbase + iu, 64);
+    const double p14 = __shfl(yc[7], gbase + 4, 64), p34 = __shfl(yc[9], gbase + 4, 64), p54 = __shfl(yc[11], gbase + 4, 64);
+    const double w3 = f[3] / f[1], w5 = f[5] / f[1];
+    const double j00 = __builtin_fma(-w3, p1u, p3u), j01 = __builtin_fma(-w3, p14, p34);
+    const double j10 = __builtin_fma(-w5, p1u, p5u), j11 = __builtin_fma(-w5, p14, p54);
+    if (planar) {
+      if (!(fabs(j01) > 0.0) || !((j01 - j01) == 0.0)) { status = 3.0; break; }
+      vy0 -= yc[3] / j01;
+    } else {
+      const double det = j00 * j11 - j01 * j10;
+      const double n0 = sqrt(__builtin_fma(j00, j00, j01 * j01)), n1 = sqrt(__builtin_fma(j10, j10, j11 * j11));
+      if (!(fabs(det) > a.sing_tol * (n0 * n1)) || !((det - det) == 0.0)) { status = 3.0; break; }
+      const double du = (j11 * yc[3] - j01 * yc[5]) / det, dv = (j00 * yc[5] - j10 * yc[3]) / det;
+      if (iu == 0) x0 -= du;
+      else z0 -= du;
+      vy0 -= dv;
+    }
+    ++it;
+  }
+  if (store) {
+    const bool fail = status >= 2.0;
+    const double nan = __builtin_nan("");
+    double* so = a.state + 6 * (long)b;
+    so[0] = fail ? nan : x0; so[1] = fail ? nan : 0.0; so[2] = fail ? nan : z0;
+    so[3] = fail ? nan : 0.0; so[4] = fail ? nan : vy0; so[5] = fail ? nan : 0.0;
+    a.period[b] = fail ? nan : 2.0 * tc;
+    a.resid[b] = fail ? nan : res;
+    a.iters[b] = it;
+    a.status[b] = (int)status;
+    for (int k = nrec; k <= a.max_iter; ++k) hist[k] = nan;
+  }
+}
+
+hipError_t launch_halo_correct(int method, const HaloCorrectArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)(((long)a.B * kGroupLanes + 63) / 64));
+  if (method == M_RK4) hipLaunchKernelGGL(k_halo_correct<M_RK4>, grid, dim3(64), 0, st, a);
+  else if (method == M_DOP853_ADAPTIVE) hipLaunchKernelGGL(k_halo_correct<M_DOP853_ADAPTIVE>, grid, dim3(64), 0, st, a);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+template <int METHOD>
+__global__ __launch_bounds__(64) void k_halo_table(const HaloTableArgs a) {
+  const int gid = blockIdx.x * 64 + threadIdx.x;
+  const int g = gid >> 3, c = gid & 7;
+  const int gbase = threadIdx.x & ~7;
+  const int b = (g < a.B) ? g : a.B - 1;
+  const int col = (c < 6) ? c : 0;
+  const double colw = (c < 6) ? 1.0 : 0.0;
+  const bool store = (g < a.B) && (c == 0);
+  SysHaloVar sys;
+  sys.MU = a.MU;
+  double xs[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) xs[q] = a.state0[6 * (long)b + q];
+  const double P = a.period[b];
+  const int n = a.n;
+  double y[12];
+  halo_start(xs, col, y);
+  const double C0 = jacobi_constant(a.MU, y);
+  double drift = 0.0;
+  double* Xb = a.X + 6 * (long)n * b;
+  if (store) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) Xb[q] = y[q];
+  }
+  const double dt = P / (double)(n - 1);
+  double tprev = 0.0;
+  for (int i = 1; i < n; ++i) {
+    const double ti = (i == n - 1) ? P : (double)i * dt;
+    const double span = ti - tprev;
+    tprev = ti;
+    if (METHOD == M_RK4) {
+      if (span > 0.0) {
+        const double h = span / (double)a.steps;
+        for (int k = 0; k < a.steps; ++k) rk4_step(sys, h, y);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 12; ++q) y[q] = __builtin_nan("");
+      }
+    } else {
+      int na = 0, nr = 0;
+      const double done = run_dop853_group<SysHaloVar, 6, 6>(sys, span, a.rtol, a.atol, a.max_steps, colw, y, na, nr,
+          [](const double, const double, const double (&)[12], double (&)[13][12], const double (&)[12]) -> double { return 0.0; });
+      if (done == 0.0 || span == 0.0) {           // a period that is not positive has no table
+#pragma unroll
+        for (int q = 0; q < 12; ++q) y[q] = __builtin_nan("");
+      }
+    }
+    const double dC = fabs(jacobi_constant(a.MU, y) - C0);
+    drift = (dC > drift || dC != dC) ? dC : drift;     // a NaN stays
+    if (store) {
+#pragma unroll
+      for (int q = 0; q < 6; ++q) Xb[6 * (long)i + q] = y[q];
+    }
+  }
+  // M = Phi(P): lane j holds column j in y[6..11].  tr M and tr M^2 in a fixed order, in every lane alike.
+  double tr = 0.0, tr2 = 0.0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    tr += __shfl(y[6 + r], gbase + r, 64);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const double mrj = __shfl(y[6 + r], gbase + j, 64), mjr = __shfl(y[6 + j], gbase + r, 64);
+      tr2 = __builtin_fma(mrj, mjr, tr2);
+    }
+  }
+  const bool ok = finite12(y) && ((tr2 - tr2) == 0.0);
+  if ((g < a.B) && (c < 6)) {
+    double* Mb = a.M + 36 * (long)b + 6 * c;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) Mb[r] = y[6 + r];
+  }
+  if (store) {
+    double cl = 0.0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) cl = fmax(cl, fabs(y[q] - xs[q]));
+    const double nan = __builtin_nan("");
+    a.closure[b] = ok ? cl : nan;
+    a.jacobi[2 * (long)b] = C0;
+    a.jacobi[2 * (long)b + 1] = drift;
+    // alpha = 2 - tr M, beta = (alpha^2 + 2 - tr M^2) / 2, nu = -(alpha +- sqrt(alpha^2 - 4 beta + 8)) / 4
+    const double alpha = 2.0 - tr, beta = 0.5 * (alpha * alpha + 2.0 - tr2);
+    const double disc = alpha * alpha - 4.0 * beta + 8.0;
+    const double root = sqrt(disc);                      // NaN for a negative discriminant
+    a.nu[2 * (long)b] = ok ? -0.25 * (alpha + root) : nan;
+    a.nu[2 * (long)b + 1] = ok ? -0.25 * (alpha - root) : nan;
+    a.status[b] = ok ? 0 : 2;
+  }
+}
+
+hipError_t launch_halo_table(int method, const HaloTableArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)(((long)a.B * kGroupLanes + 63) / 64));
+  if (method == M_RK4) hipLaunchKernelGGL(k_halo_table<M_RK4>, grid, dim3(64), 0, st, a);
+  else if (method == M_DOP853_ADAPTIVE) hipLaunchKernelGGL(k_halo_table<M_DOP853_ADAPTIVE>, grid, dim3(64), 0, st, a);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+}  // namespace lto

@@ -32,6 +32,8 @@ host, as in the reference (`-Jac_sparse \\ defect_vec`, :182).
 
 `ops` lets the CPU unit tests inject a different propagation back end; the product default is the HIP library.
 """
+import collections
+
 import numpy as np
 
 from . import hotpath
@@ -1705,3 +1707,106 @@ def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, max
                 level_arcs[k] = a
         return np.asfortranarray(X), np.asfortranarray(D), status, waves, level_arcs
     return np.asfortranarray(X), np.asfortranarray(D), status, waves
+
+
+# ------------------------------------------------------------------------------------ periodic orbits
+def libration_point(which, MU):
+    """x of the collinear libration point L1 (which = 1 or 'L1') or L2 (2 or 'L2') of the CRTBP with mass ratio MU: the root of
+    x - (1 - MU) (x + MU) / |x + MU|^3 - MU (x - 1 + MU) / |x - 1 + MU|^3 by Newton's method from the Hill-sphere estimate."""
+    which = {1: 1, 2: 2, "L1": 1, "L2": 2}.get(which)
+    if which is None:
+        raise ValueError("which must be 1, 2, 'L1' or 'L2'")
+    rh = (MU / 3.0) ** (1.0 / 3.0)
+    x = 1.0 - MU - rh if which == 1 else 1.0 - MU + rh
+    for _ in range(50):
+        a, b = x + MU, x - 1.0 + MU
+        f = x - (1.0 - MU) * a / abs(a) ** 3 - MU * b / abs(b) ** 3
+        df = 1.0 + 2.0 * (1.0 - MU) / abs(a) ** 3 + 2.0 * MU / abs(b) ** 3
+        dx = f / df
+        x -= dx
+        if abs(dx) < 1e-16:
+            break
+    return float(x)
+
+
+def lyapunov_seed(which, Ax, MU):
+    """The linear planar Lyapunov seed of x-amplitude Ax about L1 or L2: x0 = x_L - Ax, vy0 = k lam Ax with
+    lam^2 = (2 - c2 + sqrt(9 c2^2 - 8 c2)) / 2, k = (lam^2 + 1 + 2 c2) / (2 lam), c2 = (1 - MU) / |x_L + MU|^3 + MU / |x_L - 1 + MU|^3.
+    Returns (seed [6], the linear period 2 pi / lam)."""
+    xL = libration_point(which, MU)
+    c2 = (1.0 - MU) / abs(xL + MU) ** 3 + MU / abs(xL - 1.0 + MU) ** 3
+    lam = np.sqrt((2.0 - c2 + np.sqrt(9.0 * c2 * c2 - 8.0 * c2)) / 2.0)
+    k = (lam * lam + 1.0 + 2.0 * c2) / (2.0 * lam)
+    return np.array([xL - Ax, 0.0, 0.0, 0.0, k * lam * Ax, 0.0]), float(2.0 * np.pi / lam)
+
+
+HaloOrbit = collections.namedtuple("HaloOrbit", "times states state0 period jacobi nu M closure resid iterations status")
+HaloFamily = collections.namedtuple("HaloFamily", "states period resid iterations status")
+
+
+def halo_orbit(seed, mode, n_samples=100, tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None, ctx=None):
+    """A periodic orbit from a rough symmetric seed [6], both steps on the device: correct it (hotpath.halo_correct; mode 'z0',
+    'x0' or 'planar'), then sample one revolution (hotpath.halo_table).  Returns HaloOrbit: (times [n], states [6 x n]) ready for
+    DirectOrbits, the corrected start, the period, the Jacobi constant (C, its largest drift over the samples), the stability
+    indices, the monodromy matrix, the closure max |x(P) - x(0)|, the corrector's last residual and step count, and status: the
+    corrector's (0 converged, 1 max_iter, 2 unusable, 3 singular) or, if that is 0, the table's (0 or 2).  The table of an orbit
+    the corrector gave up on (status 2 or 3) is NaN."""
+    MU = hotpath.MU if MU is None else MU
+    c = hotpath.halo_correct(np.asarray(seed, dtype=np.float64).reshape(6), mode, tol=tol, max_iter=max_iter, t_max=t_max, MU=MU,
+                             integ=integ, ctx=ctx)
+    tb = hotpath.halo_table(c.state, c.period, n_samples, MU=MU, integ=integ, ctx=ctx)
+    return HaloOrbit(tb.times, tb.X, c.state, c.period, tb.jacobi, tb.nu, tb.M, tb.closure, c.resid, c.iterations,
+                     c.status if c.status else tb.status)
+
+
+def halo_family(seed, values, hold="x0", tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None, ctx=None):
+    """Natural-parameter continuation of a family of periodic orbits in the held coordinate (hold = 'x0' or 'z0'): member k has
+    that coordinate = values[k]; its seed is the secant through the last two points of the march (the caller's seed counts as the
+    first point, and the first member starts from the seed itself with the coordinate set), corrected on the device.  seed [6]
+    with values [K], or seed [6 x F] with values [K] or [K x F]: the F families advance side by side, one device call per member
+    index.  Returns HaloFamily(states [6 x K (x F)], period, resid, iterations, status [K (x F)]).  A member the corrector gives up
+    on (status 2 or 3) is NaN and so is the rest of its family."""
+    if hold not in ("x0", "z0"):
+        raise ValueError("hold must be 'x0' or 'z0'")
+    MU = hotpath.MU if MU is None else MU
+    ip = 0 if hold == "x0" else 2
+    S = np.asarray(seed, dtype=np.float64)
+    batched = S.ndim == 2
+    S = S.reshape(6, -1).copy()
+    F = S.shape[1]
+    V = np.asarray(values, dtype=np.float64)
+    V = np.broadcast_to(V.reshape(V.shape[0], -1), (V.shape[0], F))
+    K = V.shape[0]
+    states = np.zeros((6, K, F))
+    period, resid = np.zeros((K, F)), np.zeros((K, F))
+    its, status = np.zeros((K, F), dtype=np.int32), np.zeros((K, F), dtype=np.int32)
+    prev, cur = None, S
+    for k in range(K):
+        guess = cur.copy()
+        if prev is not None:
+            d = cur[ip] - prev[ip]
+            ok = d != 0.0
+            guess[:, ok] = cur[:, ok] + (cur[:, ok] - prev[:, ok]) * ((V[k, ok] - cur[ip, ok]) / d[ok])
+        guess[ip] = V[k]
+        c = hotpath.halo_correct(guess, hold, tol=tol, max_iter=max_iter, t_max=t_max, MU=MU, integ=integ, ctx=ctx)
+        states[:, k], period[k], resid[k], its[k], status[k] = c.state, c.period, c.resid, c.iterations, c.status
+        prev, cur = cur, np.array(c.state)
+    if not batched:
+        return HaloFamily(states[:, :, 0], period[:, 0], resid[:, 0], its[:, 0], status[:, 0])
+    return HaloFamily(states, period, resid, its, status)
+
+
+def halo_family_fill(members, k, hold="x0", tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None, ctx=None):
+    """k new members between each neighbouring pair of members [6 x K] of a family: the seeds are the pair's linear interpolants
+    at j / (k + 1), j = 1..k, and all (K - 1) k of them are corrected in ONE device call with the interpolated coordinate `hold`
+    kept.  Returns hotpath.HaloCorrect over the new members in the order of the family."""
+    if hold not in ("x0", "z0"):
+        raise ValueError("hold must be 'x0' or 'z0'")
+    Mb = np.asarray(members, dtype=np.float64)
+    if Mb.ndim != 2 or Mb.shape[0] != 6 or Mb.shape[1] < 2 or int(k) < 1:
+        raise ValueError("members must be [6 x K] with K >= 2, and k >= 1")
+    k = int(k)
+    w = np.arange(1, k + 1) / (k + 1.0)
+    seeds = np.concatenate([Mb[:, [i]] * (1.0 - w) + Mb[:, [i + 1]] * w for i in range(Mb.shape[1] - 1)], axis=1)
+    return hotpath.halo_correct(seeds, hold, tol=tol, max_iter=max_iter, t_max=t_max, MU=hotpath.MU if MU is None else MU, integ=integ,
+                                ctx=ctx)

@@ -1299,6 +1299,86 @@ def stack_guess(tau1, tof1, tof2, n_nodes, orbits, MU=MU, integ=None, ctx=None):
     return StackGuess(X, t, tau[0].copy(), tau[1].copy(), tau[2].copy(), gap, status)
 
 
+HALO_HOLD_Z0, HALO_HOLD_X0, HALO_PLANAR = 0, 1, 2
+_HALO_MODES = {"z0": HALO_HOLD_Z0, "hold_z0": HALO_HOLD_Z0, "x0": HALO_HOLD_X0, "hold_x0": HALO_HOLD_X0, "planar": HALO_PLANAR}
+HaloCorrect = collections.namedtuple("HaloCorrect", "state period resid iterations history status")
+HaloTable = collections.namedtuple("HaloTable", "times X M closure jacobi nu status")
+
+
+def _halo_mode(mode):
+    if isinstance(mode, str):
+        if mode not in _HALO_MODES:
+            raise ValueError("mode must be 'z0' (hold z0), 'x0' (hold x0) or 'planar'")
+        return _HALO_MODES[mode]
+    if mode not in (HALO_HOLD_Z0, HALO_HOLD_X0, HALO_PLANAR):
+        raise ValueError("mode must be HALO_HOLD_Z0, HALO_HOLD_X0 or HALO_PLANAR")
+    return int(mode)
+
+
+def halo_correct(seeds, mode, tol=1e-12, max_iter=15, t_max=10.0, MU=MU, sing_tol=1e-12, integ=None, ctx=None):
+    """The differential corrector of periodic orbits with the xz-plane symmetry on the device (lto_halo_correct_batch, DESIGN
+    4.25).  seeds [6] or [6 x B]: (x0, ., z0, ., vy0, .), the flight starts at (x0, 0, z0, 0, vy0, 0); mode 'z0' (hold z0: x0 and
+    vy0 move), 'x0' (hold x0: z0 and vy0 move) or 'planar' (z0 = 0, vy0 moves) -- or the HALO_* constants.  The first return to
+    y = 0 is searched up to t_max (TU); with RK4 integ.steps steps span t_max.  Returns HaloCorrect(state [6 x B], period [B],
+    resid [B], iterations [B], history [(max_iter + 1) x B] (NaN past the last flight), status [B]: 0 converged, 1 max_iter
+    reached, 2 unusable seed or flight, 3 singular step) -- without the batch axis for a single seed."""
+    mode = _halo_mode(mode)                       # the shapes and the mode are checked before any library call
+    S = np.asarray(seeds, dtype=np.float64)
+    if S.ndim not in (1, 2) or S.shape[0] != 6 or S.size == 0:
+        raise ValueError("seeds must be [6] or [6 x B]")
+    max_iter = int(max_iter)
+    if max_iter < 0:
+        raise ValueError("max_iter must be >= 0")
+    batched = S.ndim == 2
+    S = np.asfortranarray(S.reshape(6, -1))
+    B = S.shape[1]
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    state = np.zeros((6, B), order="F")
+    period = np.zeros(B)
+    resid = np.zeros(B)
+    hist = np.zeros((max_iter + 1, B), order="F")
+    its = np.zeros(B, dtype=np.int32)
+    status = np.zeros(B, dtype=np.int32)
+    ctx.check(ctx.fn("halo_correct_batch")(ctx.handle, B, float(MU), mode, _ptr(S), float(tol), max_iter, float(t_max), float(sing_tol),
+                                           C.byref(integ), _ptr(state), _ptr(period), _ptr(resid), _ptr(its), _ptr(hist), _ptr(status)))
+    if not batched:
+        return HaloCorrect(state[:, 0], float(period[0]), float(resid[0]), int(its[0]), hist[:, 0], int(status[0]))
+    return HaloCorrect(state, period, resid, its, hist, status)
+
+
+def halo_table(state0, period, n_samples, MU=MU, integ=None, ctx=None):
+    """One revolution of periodic orbits on the device, sampled at n_samples equal times with the state-transition matrix carried
+    through (lto_halo_table_batch).  state0 [6] or [6 x B], period scalar or [B].  Returns HaloTable(times [n] = i /
+    (n - 1), X [6 x n x B], M [6 x 6 x B] = Phi(P), closure [B], jacobi [2 x B] = (C, largest drift over the samples), nu [2 x B]
+    (stability indices), status [B]: 0, or 2 without a finite result) -- without the batch axis for a single orbit.  (times, X) is
+    what DirectOrbits takes."""
+    S = np.asarray(state0, dtype=np.float64)
+    if S.ndim not in (1, 2) or S.shape[0] != 6 or S.size == 0:
+        raise ValueError("state0 must be [6] or [6 x B]")
+    batched = S.ndim == 2
+    S = np.asfortranarray(S.reshape(6, -1))
+    B = S.shape[1]
+    P = np.ascontiguousarray(np.broadcast_to(np.asarray(period, dtype=np.float64).reshape(-1), (B,)))
+    n = int(n_samples)
+    if n < 2:
+        raise ValueError("n_samples must be >= 2")
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    X = np.zeros((6, n, B), order="F")
+    times = np.zeros(n)
+    M = np.zeros((6, 6, B), order="F")
+    closure = np.zeros(B)
+    jac = np.zeros((2, B), order="F")
+    nu = np.zeros((2, B), order="F")
+    status = np.zeros(B, dtype=np.int32)
+    ctx.check(ctx.fn("halo_table_batch")(ctx.handle, n, B, float(MU), _ptr(S), _ptr(P), C.byref(integ), _ptr(X), _ptr(times), _ptr(M),
+                                         _ptr(closure), _ptr(jac), _ptr(nu), _ptr(status)))
+    if not batched:
+        return HaloTable(times, X[:, :, 0], M[:, :, 0], float(closure[0]), jac[:, 0], nu[:, 0], int(status[0]))
+    return HaloTable(times, X, M, closure, jac, nu, status)
+
+
 AddTime = collections.namedtuple("AddTime", "XC_guess XC_out t_out tau defect status iterations history cost")
 AddTimeMass = collections.namedtuple("AddTimeMass", AddTime._fields + ("propellant",))
 
