@@ -472,6 +472,80 @@ int lto_halo_correct_batch(lto_ctx* ctx, int n_batch, double MU, int mode, const
 int lto_halo_table_batch(lto_ctx* ctx, int n_samples, int n_batch, double MU, const double* state0, const double* period,
                          const lto_integrator* integ, double* X_out, double* tau_out, double* M_out, double* closure,
                          double* jacobi, double* nu, int* status);
+/* Invariant manifolds of periodic orbits: the free ways off an orbit and onto one, from the monodromy matrix
+ * lto_halo_table_batch hands back.  A result does not depend on its batch: orbit b, arc b and row b equal their single call bit for
+ * bit.  The flights are LTO_DOP853_ADAPTIVE at integ's rtol / atol / max_steps, or LTO_RK4 with integ->steps steps per flight (per
+ * span); any other method: LTO_EUNSUPPORTED.
+ *
+ * lto_halo_manifold_seeds_batch: the eigen-directions at n_phase phases of each orbit and the perturbed starts.  state0 [6 x
+ * n_batch], period [n_batch], M [6 x 6 x n_batch] (the layout of lto_halo_table_batch's M_out), tau [n_phase] shared by the batch,
+ * each finite and wrapped into [0, 1), eps > 0 the offset in the 6-norm of (DU, DU / TU).
+ *   eigen step   lambda_u = the eigenvalue of largest modulus by power iteration on M (Rayleigh quotient of the unit iterate, whose
+ *                sign is aligned with the iterate before it, so a negative real lambda_u is accepted), converged when the unit
+ *                vector moves by < 1e-15 in max-abs between iterations, at most LTO_MANIFOLD_POWER_CAP iterations; v_s by inverse
+ *                iteration on M - I / lambda_u (det M = 1: reciprocal pairs; a 6 x 6 LU with partial pivoting, at most
+ *                LTO_MANIFOLD_INVERSE_CAP solves); lambda_s = the Rayleigh quotient of v_s, reported on its own so that lambda_u
+ *                lambda_s - 1 measures how symplectic M is.  Both vectors have unit 6-norm and v_x(0) > 0 (v_x(0) = 0 exactly:
+ *                the component of largest magnitude positive): "+" is then the exterior branch at L2, for both.  The sign is
+ *                fixed at phase 0 only and carried along the orbit by the flow, so a branch is continuous in tau.
+ *   transport    the base state and one variational vector, 12 components, the error norm over all of them: the unstable vector
+ *                FORWARD from phase 0 over tau P, the stable vector BACKWARD over (1 - tau) P (the time-reversed system over a
+ *                positive span; carried forward it would lose two more digits to the unstable direction).  tau = 0 flies nothing.
+ *                Both vectors are unit vectors again at the phase.
+ * Outputs: lambda_out [2 x n_batch] = (lambda_u, lambda_s); X_out and V_out [6 x 2 x n_phase x n_batch]: the orbit point as each
+ * of the two flights reached it (0 the unstable one's, 1 the stable one's) and the vector there; starts_out [6 x 4 x n_phase x
+ * n_batch] = X +- eps V in the order (u+, u-, s+, s-), eps V rounded before it is added, the stable starts from the backward
+ * flight's point; status [n_batch]: 0; 1 no usable hyperbolic pair (M not finite, the power iteration not converged at its cap --
+ * a complex dominant pair, say -- or |lambda_u| <= 1); 2 a flight without a finite result (max_steps used up, a period that is not
+ * finite and > 0).  Status 1 and 2 leave NaN in that orbit's outputs.  Every output but starts_out and status may be NULL.
+ * LTO_EINVAL: n_phase < 1, n_batch < 1, MU outside (0, 1), eps not finite or <= 0, a tau not finite, 24 n_phase n_batch > 2^31 - 1,
+ * LTO_RK4 with steps < 1.
+ *
+ * lto_section_flight_batch: n_arcs ballistic arcs, one lane each, from y0 [6 x n_arcs] over the SIGNED time t_max [n_arcs] (finite,
+ * non-zero; negative: backward in time, the time-reversed system over |t_max|) to the section g(y) = y[sec_axis] - sec_value = 0.
+ *   crossing     an accepted step at whose end g has the sign opposite to the arc's current side, the side being the sign of g at
+ *                the last point where g != 0 (an arc that starts exactly on the section has not crossed it).  sec_dir = +1 / -1
+ *                counts the changes of g from - to + / + to - only, 0 both, IN THE ORDER THE FLIGHT VISITS THE POINTS: for a
+ *                backward arc that is the opposite of the physical sense.  Two crossings inside one accepted step are missed, as
+ *                by any step-end test.  The n_cross-th counted crossing ends the arc and is located: the step length is bisected
+ *                by trial steps of the same formula from the step's start, through the same first slope, until the bracket's ends
+ *                are adjacent doubles in time (at most 60 halvings); state and time come from one more trial step to the far end
+ *                of the bracket, so a flight started from a returned state looks for the NEXT crossing.  Earlier crossings are
+ *                counted and the flight goes on from the accepted step's end.  n_cross = 0: no section, fly to t_max.
+ *   r_min [2]    distances from the two primaries (0 disables one): an accepted step that ends closer ends the arc there with
+ *                status 3; the event is not located.  A crossing in the same step comes first.
+ *   samples      n_samples >= 2: the flight goes sample interval by sample interval, each a fresh start of the integrator
+ *                (max_steps counts per interval), and stops exactly at t_k = k dt, dt = |t_max| / (n_samples - 1), t_k = |t_max|
+ *                for the last; the crossing count and the side carry across intervals.  X_out [6 x n_samples x n_arcs]
+ *                (lto_halo_table_batch's sample layout), sample 0 the start, samples past the arc's end NaN.  n_samples = 0: one
+ *                span, X_out unused (may be NULL).  The two forms take different steps, so their ends agree to the tolerance,
+ *                not to the bit.
+ * Outputs: x_end [6 x n_arcs], t_end [n_arcs] the signed flight time, count [n_arcs] the crossings counted, dC [n_arcs] = |C(end) -
+ * C(start)| of the Jacobi constant (may be NULL), status [n_arcs]: 0 ended as asked (the n_cross-th crossing, or t_max with n_cross
+ * = 0); 1 t_max reached first (state and time there; count says how far it got); 2 no finite result (the start not finite,
+ * max_steps used up): everything NaN; 3 an accepted step ended within r_min of a primary (state and time of that step end).
+ * LTO_EINVAL: n_arcs < 1, n_samples = 1 or < 0, n_cross < 0, sec_axis outside 0..5, sec_dir outside {-1, 0, 1}, sec_value not
+ * finite, a t_max zero or not finite, r_min negative or not finite, MU outside (0, 1), 6 n_samples n_arcs > 2^31 - 1, LTO_RK4 with
+ * steps < 1.
+ *
+ * lto_state_match_batch: for each state of A [6 x nA] the nearest of Bs [6 x nB] in d = sqrt(|dr|^2 + (w |dv|)^2), w >= 0.  Every
+ * product and every sum is rounded on its own (no fused multiply-add), in this order, so the host can reproduce d bit for bit:
+ *   q_i = (A_i - Bs_i)^2;  dr2 = (q_0 + q_1) + q_2;  dv2 = (q_3 + q_4) + q_5;  d = sqrt(dr2 + (w w) dv2)
+ * with a correctly rounded square root.  The winner is the (distance, index) lexicographic minimum, the same whatever the reduction
+ * order: the lowest index on ties, a NaN distance never wins, a row whose distances are all NaN gets index -1 and NaN.  Outputs:
+ * index [nA], dist [nA], dr [nA] = sqrt(dr2) and dv [nA] = sqrt(dv2) of the chosen pair (dr and dv may be NULL).  LTO_EINVAL: nA or nB
+ * < 1, w negative or not finite. */
+#define LTO_MANIFOLD_POWER_CAP 500
+#define LTO_MANIFOLD_INVERSE_CAP 8
+int lto_halo_manifold_seeds_batch(lto_ctx* ctx, int n_phase, int n_batch, double MU, const double* state0, const double* period,
+                                  const double* M, const double* tau, double eps, const lto_integrator* integ, double* lambda_out,
+                                  double* X_out, double* V_out, double* starts_out, int* status);
+int lto_section_flight_batch(lto_ctx* ctx, int n_arcs, double MU, const double* y0, const double* t_max, int sec_axis,
+                             double sec_value, int sec_dir, int n_cross, const double* r_min, int n_samples,
+                             const lto_integrator* integ, double* x_end, double* t_end, int* count, double* dC, double* X_out,
+                             int* status);
+int lto_state_match_batch(lto_ctx* ctx, int nA, int nB, const double* A, const double* Bs, double w, int* index, double* dist,
+                          double* dr, double* dv);
 /* Mesh re-distribution of converged 12-dim solutions (the indirect method's counterpart of meshRefine_direct): the
  * nodes of XC [12 x n_nodes x n_batch] on t [n_nodes x n_tgrids] (n_tgrids = 1 or n_batch) are moved, and their number changed to
  * n_new, so that every new segment carries the same share of a per-segment monitor w_i > 0.  Per trajectory:

@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_table,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_table, manifold_seeds, section_flight, state_match,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -848,6 +848,58 @@ function halo_table(ctx::LtoContext, state0::Matrix{Float64}, period::Vector{Flo
                ctx.handle, n_samples, B, Float64(MU), state0, period, Ref(integ), X, times, M, closure, jac, nu, status)
     check(ctx, rc)
     (times, X, M, closure, jac, nu, Int.(status))
+end
+
+# The eigen-directions of B periodic orbits at the phases tau and the perturbed starts (`lto_halo_manifold_seeds_batch`, DESIGN 4.26):
+# state0 [6 x B], period [B], M [6 x 6 x B] as halo_table returns it, tau [P] shared by the batch, eps the offset.  Returns (lambda
+# [2 x B] = (lambda_u, lambda_s), X [6 x 2 x P x B], V [6 x 2 x P x B], starts [6 x 4 x P x B] in the order (u+, u-, s+, s-), status [B]).
+function manifold_seeds(ctx::LtoContext, state0::Matrix{Float64}, period::Vector{Float64}, M::Array{Float64,3}, tau::Vector{Float64}, MU;
+                        eps = 1e-6, integ::LtoIntegrator = LtoIntegrator())
+    size(state0, 1) == 6 || error("manifold_seeds: state0 must be 6 x B")
+    B = size(state0, 2)
+    length(period) == B || error("manifold_seeds: one period per orbit")
+    size(M) == (6, 6, B) || error("manifold_seeds: M must be 6 x 6 x B")
+    P = length(tau)
+    P >= 1 || error("manifold_seeds: at least one phase")
+    lambda = zeros(2, B); X = zeros(6, 2, P, B); V = zeros(6, 2, P, B); starts = zeros(6, 4, P, B); status = zeros(Cint, B)
+    rc = ccall((:lto_halo_manifold_seeds_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Ref{LtoIntegrator},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, P, B, Float64(MU), state0, period, M, tau, Float64(eps), Ref(integ), lambda, X, V, starts, status)
+    check(ctx, rc)
+    (lambda, X, V, starts, Int.(status))
+end
+
+# Ballistic arcs from y0 [6 x N] over the signed times t_max [N] to the section y[sec_axis] = sec_value (`lto_section_flight_batch`,
+# DESIGN 4.26; sec_axis counts from 0 as in C).  Returns (x_end [6 x N], t_end [N], count [N], dC [N], X [6 x n_samples x N], status [N]).
+function section_flight(ctx::LtoContext, y0::Matrix{Float64}, t_max::Vector{Float64}, MU; sec_axis::Integer = 1, sec_value = 0.0,
+                        sec_dir::Integer = 0, n_cross::Integer = 1, r_min::Vector{Float64} = [0.0, 0.0], n_samples::Integer = 0,
+                        integ::LtoIntegrator = LtoIntegrator())
+    size(y0, 1) == 6 || error("section_flight: y0 must be 6 x N")
+    N = size(y0, 2)
+    length(t_max) == N || error("section_flight: one t_max per arc")
+    length(r_min) == 2 || error("section_flight: r_min has two entries")
+    x_end = zeros(6, N); t_end = zeros(N); dC = zeros(N); X = zeros(6, n_samples, N); count = zeros(Cint, N); status = zeros(Cint, N)
+    rc = ccall((:lto_section_flight_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Cint, Cint, Ptr{Cdouble}, Cint, Ref{LtoIntegrator},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, N, Float64(MU), y0, t_max, sec_axis, Float64(sec_value), sec_dir, n_cross, r_min, n_samples, Ref(integ),
+               x_end, t_end, count, dC, X, status)
+    check(ctx, rc)
+    (x_end, t_end, Int.(count), dC, X, Int.(status))
+end
+
+# For each column of A [6 x nA] the nearest column of Bs [6 x nB] in sqrt(|dr|^2 + (w |dv|)^2) (`lto_state_match_batch`, DESIGN 4.26).
+# Returns (index [nA], 1-based, 0 where every distance is NaN; dist [nA]; dr [nA]; dv [nA]).
+function state_match(ctx::LtoContext, A::Matrix{Float64}, Bs::Matrix{Float64}; w = 1.0)
+    size(A, 1) == 6 && size(Bs, 1) == 6 || error("state_match: A and Bs must have 6 rows")
+    nA = size(A, 2); nB = size(Bs, 2)
+    index = zeros(Cint, nA); dist = zeros(nA); dr = zeros(nA); dv = zeros(nA)
+    rc = ccall((:lto_state_match_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+               ctx.handle, nA, nB, A, Bs, Float64(w), index, dist, dr, dv)
+    check(ctx, rc)
+    (Int.(index) .+ 1, dist, dr, dv)
 end
 
 # optimizeTraj with flagEnd = true: one Jacobian sweep and the exact free-end QP step.  Returns (x_update, u_update, p1_update,

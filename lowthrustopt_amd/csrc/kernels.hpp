@@ -383,6 +383,50 @@ struct HaloTableArgs {
   int* status;                               // [B]
 };
 hipError_t launch_halo_table(int method, const HaloTableArgs& a, hipStream_t st);
+// Invariant manifolds of periodic orbits (kernels_manifold.hip).  Every array is in the caller's layout.
+// Seeds: the hyperbolic pair of M [6][6][B] (one lane per orbit), the two eigenvectors carried along the orbit to the phases tau [P]
+// (one lane per (orbit, phase, kind), kind 0 unstable forward over tau P, kind 1 stable backward over (1 - tau) P), then the starts
+// and the statuses (one lane per (orbit, phase)).  Three kernels behind one another on the stream.
+struct ManifoldSeedArgs {
+  const double* state0; const double* period;  // [6][B], [B]
+  const double* M;                             // [6][6][B]
+  const double* tau;                           // [P], wrapped into [0, 1) by the host
+  int P, B;
+  double MU, eps;
+  int steps;                                   // RK4: steps per flight
+  double rtol, atol; int max_steps;            // DOP853
+  double* lambda;                              // [2][B]
+  double* vec0;                                // [6][2][B] scratch: (v_u, v_s) at phase 0
+  double* eig_flag;                            // [B] scratch: 0 good, 1 no usable hyperbolic pair
+  double* fly_flag;                            // [2][P][B] scratch: 0 good, 2 no finite result
+  double* X; double* V;                        // [6][2][P][B]
+  double* starts;                              // [6][4][P][B]
+  int* status;                                 // [B]
+};
+// method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
+hipError_t launch_manifold_seeds(int method, const ManifoldSeedArgs& a, hipStream_t st);
+// Ballistic arcs to a Poincare section, one lane per arc
+struct SectionFlightArgs {
+  const double* y0; const double* t_max;       // [6][N], [N] signed
+  int N, axis, dir, n_cross, n_samples;
+  double MU, value, rmin1, rmin2;
+  int steps;                                   // RK4: steps per span
+  double rtol, atol; int max_steps;            // DOP853: max_steps counts per span
+  double* x_end;                               // [6][N]
+  double* t_end; double* dC;                   // [N]
+  double* X;                                   // [6][n_samples][N], unused with n_samples = 0
+  int* count; int* status;                     // [N]
+};
+hipError_t launch_section_flight(int method, const SectionFlightArgs& a, hipStream_t st);
+// The nearest of Bs [6][nB] for each of A [6][nA]; dr / dv may be null
+struct StateMatchArgs {
+  const double* A; const double* Bs;
+  int nA, nB;
+  double w;
+  int* index;
+  double* dist; double* dr; double* dv;
+};
+hipError_t launch_state_match(const StateMatchArgs& a, hipStream_t st);
 // Mesh equidistribution of the indirect method (kernels_remesh.hip).  Grid: per trajectory b the monitor of old segment
 // i is w[b (n-1) + i], or nacc + nrej there when w is null; old grids t[b t_stride + i].
 // Out: t_out [n_batch][n_new] and seg_of [n_batch][n_new], the old node each new one is propagated from.

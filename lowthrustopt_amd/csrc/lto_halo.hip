@@ -5,16 +5,12 @@
 
 #include "lto_host.hpp"
 
-namespace {
-
-// what both calls ask of the integrator: 0, or the error code with the context's message set
+// what the flying calls of this unit and of lto_manifold.hip ask of the integrator: 0, or the error code with the context's message set
 int halo_integrator_check(lto_ctx* c, const lto_integrator* integ, const char* unsupported, const char* steps) {
   if (integ->method != LTO_RK4 && integ->method != LTO_DOP853_ADAPTIVE) return set_err(c, LTO_EUNSUPPORTED, unsupported);
   if (integ->method == LTO_RK4 && integ->steps < 1) return set_err(c, LTO_EINVAL, steps);
   return LTO_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

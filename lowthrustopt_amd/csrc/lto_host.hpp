@@ -212,6 +212,9 @@ int indirect_solve_impl(lto_ctx* c, int ndim, int n_nodes, int n_batch, const do
 // lto_direct_solve.hip
 int orbits_upload(lto_ctx* c, const lto_direct_orbits* ob, DevOrbits& d, hipStream_t st);
 
+// lto_halo.hip
+int halo_integrator_check(lto_ctx* c, const lto_integrator* integ, const char* unsupported, const char* steps);
+
 inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // The scratch of one host-pointer call: every buffer is declared once with its element count (add); the layout is then

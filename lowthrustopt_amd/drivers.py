@@ -1810,3 +1810,109 @@ def halo_family_fill(members, k, hold="x0", tol=1e-12, max_iter=15, t_max=10.0, 
     seeds = np.concatenate([Mb[:, [i]] * (1.0 - w) + Mb[:, [i + 1]] * w for i in range(Mb.shape[1] - 1)], axis=1)
     return hotpath.halo_correct(seeds, hold, tol=tol, max_iter=max_iter, t_max=t_max, MU=hotpath.MU if MU is None else MU, integ=integ,
                                 ctx=ctx)
+
+
+ManifoldArcs = collections.namedtuple("ManifoldArcs", "branch tau start x_end t_end count dC status lam seeds")
+ManifoldConnection = collections.namedtuple(
+    "ManifoldConnection", "dist dr_km dv_ms tau1 tau2 branch1 branch2 t1 t2 x1 x2 start1 start2 MU")
+_MANIFOLD_BRANCHES = ("u+", "u-", "s+", "s-")
+
+
+def _orbit_parts(orbit):
+    """(state0 [6], period, M [6 x 6]) of what halo_orbit returns, or of such a tuple."""
+    if isinstance(orbit, HaloOrbit):
+        return np.asarray(orbit.state0, dtype=np.float64), float(orbit.period), np.asarray(orbit.M, dtype=np.float64)
+    try:
+        state0, period, M = orbit
+    except (TypeError, ValueError):
+        raise ValueError("orbit must be what halo_orbit returns, or (state0, period, M)")
+    state0, M = np.asarray(state0, dtype=np.float64), np.asarray(M, dtype=np.float64)
+    if state0.shape != (6,) or M.shape != (6, 6):
+        raise ValueError("orbit must be what halo_orbit returns, or (state0 [6], period, M [6 x 6])")
+    return state0, float(period), M
+
+
+def _branch_list(branches):
+    if not isinstance(branches, str) or len(branches) % 2 or not branches:
+        raise ValueError("branches must be a string made of 'u+', 'u-', 's+', 's-'")
+    out = [branches[i:i + 2] for i in range(0, len(branches), 2)]
+    if any(b not in _MANIFOLD_BRANCHES for b in out) or len(set(out)) != len(out):
+        raise ValueError("branches must be a string made of 'u+', 'u-', 's+', 's-', each at most once")
+    return out
+
+
+def halo_manifold(orbit, n_phase, eps=1e-6, branches="u+u-s+s-", section=None, n_cross=1, t_max=12.0, r_min=(0.0, 0.0), MU=None,
+                  integ=None, ctx=None):
+    """The invariant-manifold tubes of a periodic orbit flown to a Poincare section, in two library calls: the
+    eigen-directions and perturbed starts at the phases j / n_phase (hotpath.manifold_seeds), then one flight call for all selected
+    arcs (hotpath.section_flight) -- unstable arcs forward over t_max TU, stable arcs backward.  orbit: what halo_orbit returns, or
+    (state0, period, M); branches: which of 'u+', 'u-', 's+', 's-' fly ('+': the side with v_x(0) > 0, the exterior one at L2);
+    section = (axis, value), default x = 1 - MU.  Returns ManifoldArcs of N = n_phase x len(branches) arcs, phase by phase: branch
+    [N], tau [N], start [6 x N], x_end [6 x N], t_end [N] (signed), count [N], dC [N], status [N] (section_flight's), lam =
+    (lambda_u, lambda_s) and seeds, the hotpath.ManifoldSeeds record.  A seed status other than 0 raises ValueError."""
+    MU = hotpath.MU if MU is None else MU
+    state0, period, M = _orbit_parts(orbit)
+    names = _branch_list(branches)
+    n_phase = int(n_phase)
+    if n_phase < 1:
+        raise ValueError("n_phase must be >= 1")
+    section = ("x", 1.0 - MU) if section is None else section
+    tau = np.arange(n_phase) / float(n_phase)
+    seeds = hotpath.manifold_seeds(state0, period, M, tau, eps=eps, MU=MU, integ=integ, ctx=ctx)
+    if seeds.status != 0:
+        raise ValueError("the orbit has no usable hyperbolic pair (status %d of manifold_seeds)" % seeds.status)
+    which = [_MANIFOLD_BRANCHES.index(b) for b in names]
+    start = np.asfortranarray(seeds.starts[:, which, :].transpose(0, 2, 1).reshape(6, -1, order="C"))      # arc = phase * nb + branch
+    branch = np.array(names * n_phase)
+    T = np.where(np.char.startswith(branch, "u"), abs(float(t_max)), -abs(float(t_max)))
+    fl = hotpath.section_flight(start, T, section=section, sec_dir=0, n_cross=n_cross, r_min=r_min, MU=MU, integ=integ, ctx=ctx)
+    return ManifoldArcs(branch, np.repeat(tau, len(names)), start, fl.x_end, fl.t_end, fl.count, fl.dC, fl.status, seeds.lam, seeds)
+
+
+def manifold_connections(dep, arr, section=None, n_phase=64, eps=1e-6, n_cross=1, t_max=12.0, r_min=(0.0, 0.0), w=1.0, k=10, MU=None,
+                         DU=None, TU=None, integ=None, ctx=None):
+    """Where the unstable manifold of `dep` and the stable manifold of `arr` come close on a section: both tubes by halo_manifold
+    (n_phase phases each, both branches), every departure arc that reached the section matched to its nearest arrival arc by one
+    hotpath.state_match call in d = sqrt(|dr|^2 + (w |dv|)^2), and the k best pairs by increasing distance.  Returns a list of
+    ManifoldConnection(dist, dr_km, dv_ms, tau1, tau2 (the phases on the two orbits), branch1, branch2, t1 > 0, t2 < 0 (the flight
+    times to the section, TU), x1, x2 (the two states on the section), start1, start2 (the arcs' starts), MU)."""
+    from .constants import DU as DU0, TU as TU0
+    MU = hotpath.MU if MU is None else MU
+    DU, TU = DU0 if DU is None else DU, TU0 if TU is None else TU
+    a = halo_manifold(dep, n_phase, eps=eps, branches="u+u-", section=section, n_cross=n_cross, t_max=t_max, r_min=r_min, MU=MU,
+                      integ=integ, ctx=ctx)
+    b = halo_manifold(arr, n_phase, eps=eps, branches="s+s-", section=section, n_cross=n_cross, t_max=t_max, r_min=r_min, MU=MU,
+                      integ=integ, ctx=ctx)
+    A = np.where(a.status == 0, a.x_end, np.nan)
+    Bs = np.where(b.status == 0, b.x_end, np.nan)
+    m = hotpath.state_match(A, Bs, w=w, ctx=ctx)
+    order = [i for i in np.argsort(m.dist, kind="stable") if m.index[i] >= 0][:int(k)]
+    out = []
+    for i in order:
+        j = int(m.index[i])
+        out.append(ManifoldConnection(float(m.dist[i]), float(m.dr[i]) * DU, float(m.dv[i]) * DU / TU * 1e3, float(a.tau[i]),
+                                      float(b.tau[j]), str(a.branch[i]), str(b.branch[j]), float(a.t_end[i]), float(b.t_end[j]),
+                                      a.x_end[:, i].copy(), b.x_end[:, j].copy(), a.start[:, i].copy(), b.start[:, j].copy(), MU))
+    return out
+
+
+def manifold_guess(connection, n_nodes, integ=None, ctx=None):
+    """A connection of manifold_connections as an initial guess: both arcs flown again with samples (hotpath.section_flight with
+    n_cross = 0 and t_max = their crossing times) and stitched in flight order -- departure point, section, arrival point; the nodes
+    are shared out in proportion to the two flight times and the section is represented by the departure arc's end alone.  Returns
+    (X [6 x n_nodes], t_TU, tau1, tau2), the tuple stacked_guess returns."""
+    c = connection
+    n_nodes = int(n_nodes)
+    if n_nodes < 4:
+        raise ValueError("n_nodes must be >= 4")
+    t1, t2 = float(c.t1), abs(float(c.t2))
+    n1 = min(max(int(round(n_nodes * t1 / (t1 + t2))), 2), n_nodes - 2)
+    n2 = n_nodes - n1
+    f1 = hotpath.section_flight(c.start1, t1, n_cross=0, n_samples=n1, MU=c.MU, integ=integ, ctx=ctx)
+    f2 = hotpath.section_flight(c.start2, -t2, n_cross=0, n_samples=n2 + 1, MU=c.MU, integ=integ, ctx=ctx)
+    X = np.asfortranarray(np.concatenate([f1.X, f2.X[:, ::-1][:, 1:]], axis=1))
+    s2 = np.arange(n2 + 1) * (t2 / n2)
+    s2[-1] = t2
+    t = np.concatenate([np.arange(n1) * (t1 / (n1 - 1)), t1 + (t2 - s2[::-1][1:])])
+    t[n1 - 1] = t1
+    return X, t, c.tau1, c.tau2

@@ -1379,6 +1379,154 @@ def halo_table(state0, period, n_samples, MU=MU, integ=None, ctx=None):
     return HaloTable(times, X, M, closure, jac, nu, status)
 
 
+ManifoldSeeds = collections.namedtuple("ManifoldSeeds", "lam X V starts tau status")
+SectionFlight = collections.namedtuple("SectionFlight", "x_end t_end count dC X status")
+StateMatch = collections.namedtuple("StateMatch", "index dist dr dv")
+_SECTION_AXES = {"x": 0, "y": 1, "z": 2, "vx": 3, "vy": 4, "vz": 5}
+
+
+def _flight_integrator(integ):
+    integ = integ or integrator()
+    if integ.method not in (RK4, DOP853_ADAPTIVE):
+        raise ValueError("the flight is built for RK4 and DOP853_ADAPTIVE")
+    if integ.method == RK4 and integ.steps < 1:
+        raise ValueError("RK4 needs steps >= 1")
+    return integ
+
+
+def manifold_seeds(state0, period, M, tau, eps=1e-6, MU=MU, integ=None, ctx=None):
+    """The hyperbolic eigen-directions of periodic orbits at the phases tau and the perturbed manifold starts
+    (lto_halo_manifold_seeds_batch).  state0 [6] or [6 x B], period scalar or [B], M [6 x 6] or [6 x 6 x B] as
+    halo_table returns it, tau [P] (any finite values; they are wrapped into [0, 1)), eps the offset in the 6-norm of (DU, DU / TU).
+    Returns ManifoldSeeds(lam [2 x B] = (lambda_u, lambda_s), X [6 x 2 x P x B] the orbit point as the (unstable, stable) flight
+    reached it, V [6 x 2 x P x B] the unit vectors there, starts [6 x 4 x P x B] = X +- eps V in the order (u+, u-, s+, s-), tau [P]
+    as wrapped, status [B]: 0, 1 no usable hyperbolic pair, 2 a flight without a finite result) -- without the batch axis for a
+    single orbit."""
+    S = np.asarray(state0, dtype=np.float64)
+    if S.ndim not in (1, 2) or S.shape[0] != 6 or S.size == 0:
+        raise ValueError("state0 must be [6] or [6 x B]")
+    batched = S.ndim == 2
+    S = np.asfortranarray(S.reshape(6, -1))
+    B = S.shape[1]
+    Mm = np.asarray(M, dtype=np.float64)
+    if Mm.shape != ((6, 6, B) if batched else (6, 6)):
+        raise ValueError("M must be [6 x 6] for one orbit, [6 x 6 x B] for a batch")
+    Mm = np.asfortranarray(Mm.reshape(6, 6, B))
+    P = np.asarray(period, dtype=np.float64).reshape(-1)
+    if P.size not in (1, B):
+        raise ValueError("period must be a scalar or [B]")
+    P = np.ascontiguousarray(np.broadcast_to(P, (B,)))
+    tau = np.ascontiguousarray(np.asarray(tau, dtype=np.float64).reshape(-1))
+    if tau.size < 1 or not np.all(np.isfinite(tau)):
+        raise ValueError("tau must hold at least one phase, all finite")
+    eps = float(eps)
+    if not (np.isfinite(eps) and eps > 0.0):
+        raise ValueError("eps must be finite and > 0")
+    integ = _flight_integrator(integ)
+    ctx = ctx or default_context()
+    n = tau.size
+    lam = np.zeros((2, B), order="F")
+    X = np.zeros((6, 2, n, B), order="F")
+    V = np.zeros((6, 2, n, B), order="F")
+    starts = np.zeros((6, 4, n, B), order="F")
+    status = np.zeros(B, dtype=np.int32)
+    ctx.check(ctx.fn("halo_manifold_seeds_batch")(ctx.handle, n, B, float(MU), _ptr(S), _ptr(P), _ptr(Mm), _ptr(tau), eps, C.byref(integ),
+                                                  _ptr(lam), _ptr(X), _ptr(V), _ptr(starts), _ptr(status)))
+    wrapped = tau - np.floor(tau)
+    wrapped[wrapped >= 1.0] = 0.0
+    if not batched:
+        return ManifoldSeeds(lam[:, 0], X[..., 0], V[..., 0], starts[..., 0], wrapped, int(status[0]))
+    return ManifoldSeeds(lam, X, V, starts, wrapped, status)
+
+
+def section_flight(y0, t_max, section=("y", 0.0), sec_dir=0, n_cross=1, r_min=(0.0, 0.0), n_samples=0, MU=MU, integ=None, ctx=None):
+    """Ballistic CRTBP arcs flown to a Poincare section (lto_section_flight_batch, DESIGN 4.26), one lane per arc.  y0 [6] or [6 x N];
+    t_max scalar or [N], SIGNED (negative: backward in time), finite and non-zero; section = (axis, value) with axis 0..5 or one of
+    'x', 'y', 'z', 'vx', 'vy', 'vz'; sec_dir +1 / -1 counts sign changes of g = y[axis] - value from - to + / + to - in the order
+    the flight visits the points (for a backward arc the opposite of the physical sense), 0 both; the n_cross-th counted crossing ends
+    the arc (n_cross = 0: no section, fly to t_max); r_min = distances from the two primaries that end an arc with status 3 (0: off);
+    n_samples = 0, or >= 2 for samples at k t_max / (n_samples - 1).  Returns SectionFlight(x_end [6 x N], t_end [N] signed, count
+    [N], dC [N] the Jacobi constant's drift, X [6 x n_samples x N] or None, status [N]: 0 ended as asked, 1 t_max reached first,
+    2 no finite result, 3 inside r_min) -- without the batch axis for a single arc."""
+    Y = np.asarray(y0, dtype=np.float64)
+    if Y.ndim not in (1, 2) or Y.shape[0] != 6 or Y.size == 0:
+        raise ValueError("y0 must be [6] or [6 x N]")
+    batched = Y.ndim == 2
+    Y = np.asfortranarray(Y.reshape(6, -1))
+    N = Y.shape[1]
+    T = np.asarray(t_max, dtype=np.float64).reshape(-1)
+    if T.size not in (1, N):
+        raise ValueError("t_max must be a scalar or [N]")
+    T = np.ascontiguousarray(np.broadcast_to(T, (N,)))
+    if not np.all(np.isfinite(T)) or np.any(T == 0.0):
+        raise ValueError("every t_max must be finite and non-zero")
+    try:
+        axis, value = section
+    except (TypeError, ValueError):
+        raise ValueError("section must be (axis, value)")
+    if isinstance(axis, str):
+        if axis not in _SECTION_AXES:
+            raise ValueError("section axis must be 0..5 or one of 'x', 'y', 'z', 'vx', 'vy', 'vz'")
+        axis = _SECTION_AXES[axis]
+    if axis not in (0, 1, 2, 3, 4, 5):
+        raise ValueError("section axis must be 0..5 or one of 'x', 'y', 'z', 'vx', 'vy', 'vz'")
+    value = float(value)
+    if not np.isfinite(value):
+        raise ValueError("the section's value must be finite")
+    if sec_dir not in (-1, 0, 1):
+        raise ValueError("sec_dir must be -1, 0 or +1")
+    n_cross, n_samples = int(n_cross), int(n_samples)
+    if n_cross < 0:
+        raise ValueError("n_cross must be >= 0")
+    if n_samples < 0 or n_samples == 1:
+        raise ValueError("n_samples must be 0 or >= 2")
+    R = np.ascontiguousarray(np.asarray(r_min, dtype=np.float64).reshape(-1))
+    if R.size != 2 or not np.all(np.isfinite(R)) or np.any(R < 0.0):
+        raise ValueError("r_min must hold two finite distances >= 0")
+    integ = _flight_integrator(integ)
+    ctx = ctx or default_context()
+    x_end = np.zeros((6, N), order="F")
+    t_end = np.zeros(N)
+    dC = np.zeros(N)
+    count = np.zeros(N, dtype=np.int32)
+    status = np.zeros(N, dtype=np.int32)
+    X = np.zeros((6, n_samples, N), order="F") if n_samples else None
+    ctx.check(ctx.fn("section_flight_batch")(ctx.handle, N, float(MU), _ptr(Y), _ptr(T), int(axis), value, int(sec_dir), n_cross, _ptr(R),
+                                             n_samples, C.byref(integ), _ptr(x_end), _ptr(t_end), _ptr(count), _ptr(dC), _ptr(X),
+                                             _ptr(status)))
+    if not batched:
+        return SectionFlight(x_end[:, 0], float(t_end[0]), int(count[0]), float(dC[0]), None if X is None else X[:, :, 0], int(status[0]))
+    return SectionFlight(x_end, t_end, count, dC, X, status)
+
+
+def state_match(A, Bs, w=1.0, ctx=None):
+    """For each state of A [6] or [6 x nA] the nearest of Bs [6 x nB] in d = sqrt(|dr|^2 + (w |dv|)^2) (lto_state_match_batch, DESIGN
+    4.26): the lowest index on ties, a NaN distance never wins, index -1 and NaN where every distance is NaN.  Returns
+    StateMatch(index [nA], dist [nA], dr [nA], dv [nA]) -- scalars for a single state of A."""
+    Aa = np.asarray(A, dtype=np.float64)
+    if Aa.ndim not in (1, 2) or Aa.shape[0] != 6 or Aa.size == 0:
+        raise ValueError("A must be [6] or [6 x nA]")
+    Bb = np.asarray(Bs, dtype=np.float64)
+    if Bb.ndim != 2 or Bb.shape[0] != 6 or Bb.size == 0:
+        raise ValueError("Bs must be [6 x nB]")
+    w = float(w)
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError("w must be finite and >= 0")
+    batched = Aa.ndim == 2
+    Aa = np.asfortranarray(Aa.reshape(6, -1))
+    Bb = np.asfortranarray(Bb)
+    nA, nB = Aa.shape[1], Bb.shape[1]
+    ctx = ctx or default_context()
+    index = np.zeros(nA, dtype=np.int32)
+    dist = np.zeros(nA)
+    dr = np.zeros(nA)
+    dv = np.zeros(nA)
+    ctx.check(ctx.fn("state_match_batch")(ctx.handle, nA, nB, _ptr(Aa), _ptr(Bb), w, _ptr(index), _ptr(dist), _ptr(dr), _ptr(dv)))
+    if not batched:
+        return StateMatch(int(index[0]), float(dist[0]), float(dr[0]), float(dv[0]))
+    return StateMatch(index, dist, dr, dv)
+
+
 AddTime = collections.namedtuple("AddTime", "XC_guess XC_out t_out tau defect status iterations history cost")
 AddTimeMass = collections.namedtuple("AddTimeMass", AddTime._fields + ("propellant",))
 
