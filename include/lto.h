@@ -472,6 +472,35 @@ int lto_halo_correct_batch(lto_ctx* ctx, int n_batch, double MU, int mode, const
 int lto_halo_table_batch(lto_ctx* ctx, int n_samples, int n_batch, double MU, const double* state0, const double* period,
                          const lto_integrator* integ, double* X_out, double* tau_out, double* M_out, double* closure,
                          double* jacobi, double* nu, int* status);
+/* Periodic orbits at a given Jacobi constant or a given period: the corrector of lto_halo_correct_batch with one more
+ * unknown and one more equation.  The unknowns are (x0, z0, vy0) -- with planar != 0 (x0, vy0), and z0 must be 0 --, the flight is
+ * lto_halo_correct_batch's (from (x0, 0, z0, 0, vy0, 0) to the first return to y = 0, LTO_DOP853_ADAPTIVE with the error norm over
+ * the state and the three columns of the state-transition matrix the step reads, or LTO_RK4 with integ->steps steps over t_max), the
+ * residual is (vx, vz, q - q*) -- planar: (vx, q - q*) -- with
+ *   LTO_HALO_TARGET_JACOBI   q = the Jacobi constant C of the start state (its row of the Jacobian is analytic)
+ *   LTO_HALO_TARGET_PERIOD   q = 2 x the crossing time (its row is -2 Phi[1, j] / f[1])
+ * and one Newton step solves the 3 x 3 system by LU with partial pivoting; the loop ends when max |residual| < tol or after max_iter
+ * steps.  seeds [6 x n_batch] (rows 0, 2 and 4 are read), targets [n_targets x n_batch]: orbit b's members k = 0 .. n_targets - 1 are
+ * corrected one after another inside the one launch, member 0 from the seed, member 1 from member 0's state, member k >= 2 from
+ *   s_(k-1) + (s_(k-1) - s_(k-2)) w,   w = (q*_k - q*_(k-1)) / (q*_(k-1) - q*_(k-2))
+ * (difference, product and sum each rounded once; no predictor where q*_(k-1) = q*_(k-2)).  A result does not depend on its batch:
+ * orbit b equals its single call bit for bit, and member k equals a single call seeded with the predictor's point.
+ * Outputs, member (k, b) at record n_targets b + k: state_out [6 x n_targets x n_batch], period_out = 2 x the crossing time,
+ * jacobi_out = C of state_out (may be NULL), resid_out (may be NULL), iterations = Newton steps taken (may be NULL), history
+ * [(max_iter + 1) x n_targets x n_batch] = the residual of every flight, NaN past the last (may be NULL), status: 0 converged;
+ * 1 max_iter reached (max_iter = 0: the start is evaluated) -- such a member still serves as a point of the march; 2 unusable (start
+ * or target not finite, vy0 = 0, z0 != 0 with planar, a period target <= 0, no crossing before t_max, max_steps used up); 3 singular
+ * step, |det| <= sing_tol x the product of the Jacobian's row 2-norms, or det not finite.  Status 2 and 3: state, period, jacobi and
+ * resid NaN, and the members after it in the same orbit are NaN with status 2.
+ * LTO_EINVAL: n_targets < 1, n_batch < 1, max_iter < 0, tol <= 0, t_max not finite or <= 0, sing_tol outside [0, 1), MU outside
+ * (0, 1), an unknown `what`, LTO_RK4 with steps < 1, 6 n_targets n_batch, (max_iter + 1) n_targets n_batch or 8 n_batch > 2^31 - 1.  Any other
+ * method than the two: LTO_EUNSUPPORTED. */
+#define LTO_HALO_TARGET_JACOBI 0
+#define LTO_HALO_TARGET_PERIOD 1
+int lto_halo_target_batch(lto_ctx* ctx, int n_targets, int n_batch, double MU, int planar, int what, const double* seeds,
+                          const double* targets, double tol, int max_iter, double t_max, double sing_tol,
+                          const lto_integrator* integ, double* state_out, double* period_out, double* jacobi_out, double* resid_out,
+                          int* iterations, double* history, int* status);
 /* Invariant manifolds of periodic orbits: the free ways off an orbit and onto one, from the monodromy matrix
  * lto_halo_table_batch hands back.  A result does not depend on its batch: orbit b, arc b and row b equal their single call bit for
  * bit.  The flights are LTO_DOP853_ADAPTIVE at integ's rtol / atol / max_steps, or LTO_RK4 with integ->steps steps per flight (per

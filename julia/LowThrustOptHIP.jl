@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_table, manifold_seeds, section_flight, state_match,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_target, halo_table, manifold_seeds, section_flight, state_match,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -830,6 +830,27 @@ function halo_correct(ctx::LtoContext, seeds::Matrix{Float64}, mode::Integer, MU
                period, resid, its, hist, status)
     check(ctx, rc)
     (state, period, resid, Int.(its), hist, Int.(status))
+end
+
+# Periodic orbits at a given Jacobi constant (what = 0) or period (what = 1) (`lto_halo_target_batch`, DESIGN 4.27): seeds [6 x B],
+# targets [K x B] -- orbit b's K members are corrected one after another in one launch, each from the secant through the last two.
+# Returns (state [6 x K x B], period, jacobi, resid, iterations [K x B], history [(max_iter + 1) x K x B], status [K x B]).
+function halo_target(ctx::LtoContext, seeds::Matrix{Float64}, targets::Matrix{Float64}, what::Integer, MU; planar::Bool = false,
+                     tol = 1e-12, max_iter::Integer = 15, t_max = 10.0, sing_tol = 1e-12, integ::LtoIntegrator = LtoIntegrator())
+    size(seeds, 1) == 6 || error("halo_target: seeds must be 6 x B")
+    B = size(seeds, 2)
+    size(targets, 2) == B || error("halo_target: targets must be K x B")
+    (what == 0 || what == 1) || error("halo_target: what must be 0 (Jacobi constant) or 1 (period)")
+    K = size(targets, 1)
+    state = zeros(6, K, B); period = zeros(K, B); jac = zeros(K, B); resid = zeros(K, B); hist = zeros(max_iter + 1, K, B)
+    its = zeros(Cint, K, B); status = zeros(Cint, K, B)
+    rc = ccall((:lto_halo_target_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cdouble, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cint, Cdouble, Cdouble,
+                Ref{LtoIntegrator}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, K, B, Float64(MU), planar ? 1 : 0, what, seeds, targets, Float64(tol), max_iter, Float64(t_max),
+               Float64(sing_tol), Ref(integ), state, period, jac, resid, its, hist, status)
+    check(ctx, rc)
+    (state, period, jac, resid, Int.(its), hist, Int.(status))
 end
 
 # One revolution of B periodic orbits from (state0 [6 x B], period [B]) at n_samples equal times, the state-transition matrix carried

@@ -383,6 +383,22 @@ struct HaloTableArgs {
   int* status;                               // [B]
 };
 hipError_t launch_halo_table(int method, const HaloTableArgs& a, hipStream_t st);
+// The corrector with a target (kernels_halo_target.hip): the Jacobi constant (what = 0) or the period (what = 1) is
+// asked for, (x0, z0, vy0) move -- planar: (x0, vy0) -- and orbit b's T members are corrected one after another in the launch, each
+// from the secant through the last two.  Member (k, b) is record T b + k of every output.
+struct HaloTargetArgs {
+  const double* seed;                        // [6][B]
+  const double* target;                      // [T][B]
+  int T, B, planar, what, max_iter;
+  double MU, tol, t_max, sing_tol;
+  int steps;                                 // RK4: steps over t_max
+  double rtol, atol; int max_steps;          // DOP853
+  double* state;                             // [6][T][B]
+  double* period; double* jacobi; double* resid;  // [T][B]
+  double* hist;                              // [max_iter + 1][T][B]
+  int* iters; int* status;                   // [T][B]
+};
+hipError_t launch_halo_target(int method, const HaloTargetArgs& a, hipStream_t st);
 // Invariant manifolds of periodic orbits (kernels_manifold.hip).  Every array is in the caller's layout.
 // Seeds: the hyperbolic pair of M [6][6][B] (one lane per orbit), the two eigenvectors carried along the orbit to the phases tau [P]
 // (one lane per (orbit, phase, kind), kind 0 unstable forward over tau P, kind 1 stable backward over (1 - tau) P), then the starts

@@ -1916,3 +1916,139 @@ def manifold_guess(connection, n_nodes, integ=None, ctx=None):
     t = np.concatenate([np.arange(n1) * (t1 / (n1 - 1)), t1 + (t2 - s2[::-1][1:])])
     t[n1 - 1] = t1
     return X, t, c.tau1, c.tau2
+
+
+# ------------------------------------------------------------------------------------ orbits at a given C or period
+def _one_target(jacobi, period):
+    """('jacobi' | 'period', value): exactly one of the two must be given."""
+    if (jacobi is None) == (period is None):
+        raise ValueError("give exactly one of jacobi and period")
+    return ("jacobi", float(jacobi)) if period is None else ("period", float(period))
+
+
+def _jacobi_of(state, MU):
+    """The Jacobi constant of states [6 (x F)] in numpy."""
+    x, y, z, vx, vy, vz = np.asarray(state, dtype=np.float64)
+    r1 = np.sqrt((x + MU) ** 2 + y * y + z * z)
+    r2 = np.sqrt((x + MU - 1.0) ** 2 + y * y + z * z)
+    return x * x + y * y + 2.0 * (1.0 - MU) / r1 + 2.0 * MU / r2 - (vx * vx + vy * vy + vz * vz)
+
+
+def _step_table(start, end, n_steps):
+    """[n_steps x F]: row k = start + (end - start) (k + 1) / n_steps, the last row `end` itself."""
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise ValueError("n_steps must be >= 1")
+    start = np.asarray(start, dtype=np.float64).reshape(-1)
+    end = np.broadcast_to(np.asarray(end, dtype=np.float64).reshape(-1), start.shape)
+    tab = start[None, :] + (end - start)[None, :] * (np.arange(1, n_steps + 1) / float(n_steps))[:, None]
+    tab[-1] = end
+    return tab
+
+
+def halo_orbit_at(seed, jacobi=None, period=None, planar=False, n_samples=100, tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None,
+                  ctx=None):
+    """A periodic orbit of a prescribed Jacobi constant or a prescribed period from a symmetric seed [6], both steps on the device:
+    the targeted corrector (hotpath.halo_target), then one revolution sampled (hotpath.halo_table).  Exactly one of jacobi and period
+    must be given.  Returns HaloOrbit as halo_orbit does."""
+    what, q = _one_target(jacobi, period)
+    MU = hotpath.MU if MU is None else MU
+    c = hotpath.halo_target(np.asarray(seed, dtype=np.float64).reshape(6), q, what=what, planar=planar, tol=tol, max_iter=max_iter,
+                            t_max=t_max, MU=MU, integ=integ, ctx=ctx)
+    tb = hotpath.halo_table(c.state, c.period, n_samples, MU=MU, integ=integ, ctx=ctx)
+    return HaloOrbit(tb.times, tb.X, c.state, c.period, tb.jacobi, tb.nu, tb.M, tb.closure, c.resid, c.iterations,
+                     c.status if c.status else tb.status)
+
+
+def halo_family_by(seed, values, what, planar=False, tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None, ctx=None):
+    """A family of periodic orbits parametrised by the Jacobi constant (what = 'jacobi') or the period ('period'): member k has that
+    quantity = values[k], its start the secant through the last two members in the value -- the whole march in ONE device call
+    (hotpath.halo_target).  seed [6] with values [K], or seed [6 x F] with values [K] or [K x F]: the F families advance side by
+    side.  Returns HaloFamily(states [6 x K (x F)], period, resid, iterations, status [K (x F)]).  A member the corrector gives up on
+    (status 2 or 3) is NaN and so is the rest of its family."""
+    V = np.asarray(values, dtype=np.float64)
+    if V.ndim < 1:
+        raise ValueError("values must be [K] or [K x F]")
+    c = hotpath.halo_target(seed, V, what=what, planar=planar, tol=tol, max_iter=max_iter, t_max=t_max,
+                            MU=hotpath.MU if MU is None else MU, integ=integ, ctx=ctx)
+    return HaloFamily(c.state, c.period, c.resid, c.iterations, c.status)
+
+
+def matched_orbits(seeds, jacobi, n_steps=8, planar=False, n_samples=100, tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None,
+                   ctx=None):
+    """Several periodic orbits brought to ONE Jacobi constant in one device call: orbit f of seeds [6 x F] (corrected orbits, as
+    halo_correct returns them) marches from its own C to `jacobi` in n_steps equal steps (hotpath.halo_target), then all F are
+    sampled in one hotpath.halo_table call.  Returns a list of F HaloOrbit; `iterations` counts the last member's Newton steps and
+    `status` is that member's, or the table's."""
+    MU = hotpath.MU if MU is None else MU
+    S = np.asarray(seeds, dtype=np.float64)
+    if S.ndim != 2 or S.shape[0] != 6 or S.shape[1] < 1:
+        raise ValueError("seeds must be [6 x F]")
+    if not np.isfinite(float(jacobi)):
+        raise ValueError("jacobi must be finite")
+    steps = _step_table(_jacobi_of(S, MU), float(jacobi), n_steps)
+    c = hotpath.halo_target(S, steps, what="jacobi", planar=planar, tol=tol, max_iter=max_iter, t_max=t_max, MU=MU, integ=integ, ctx=ctx)
+    state, period = np.asfortranarray(c.state[:, -1, :]), np.ascontiguousarray(c.period[-1])
+    tb = hotpath.halo_table(state, period, n_samples, MU=MU, integ=integ, ctx=ctx)
+    return [HaloOrbit(tb.times, tb.X[:, :, f], state[:, f], float(period[f]), tb.jacobi[:, f], tb.nu[:, f], tb.M[:, :, f],
+                      float(tb.closure[f]), float(c.resid[-1, f]), int(c.iterations[-1, f]),
+                      int(c.status[-1, f]) if c.status[-1, f] else int(tb.status[f])) for f in range(S.shape[1])]
+
+
+def _refine_phases(centre, half_width, n_phase):
+    """The n_phase phases of one refinement level: equally spaced over centre -+ half_width, both ends included."""
+    return centre + half_width * np.linspace(-1.0, 1.0, int(n_phase))
+
+
+def _refine_shrink(half_width, n_phase):
+    """The next level's half width: the window shrinks by n_phase / 2."""
+    return half_width / (0.5 * int(n_phase))
+
+
+def manifold_connection_refine(dep, arr, connection, levels=4, n_phase=16, spacing=1.0 / 64.0, eps=1e-6, section=None, n_cross=1,
+                               t_max=12.0, r_min=(0.0, 0.0), w=1.0, MU=None, DU=None, TU=None, integ=None, ctx=None):
+    """Zoom in on a pair manifold_connections found.  `spacing` is the phase spacing of the search that found it (1 / its n_phase).
+    Each level takes n_phase phases within -+ one previous spacing of (tau1, tau2) on the pair's two branches only -- one
+    hotpath.manifold_seeds call for both orbits with the explicit phases, one section_flight call for the 2 n_phase arcs, one
+    state_match call -- the best pair becomes the next centre and the window shrinks by n_phase / 2.  A level that finds nothing
+    closer keeps its centre, so the distance never grows.  Returns the list of ManifoldConnection, one per level."""
+    from .constants import DU as DU0, TU as TU0
+    c = connection
+    MU = c.MU if MU is None else MU
+    DU, TU = DU0 if DU is None else DU, TU0 if TU is None else TU
+    levels, n_phase = int(levels), int(n_phase)
+    if levels < 1 or n_phase < 3:
+        raise ValueError("need levels >= 1 and n_phase >= 3")
+    if c.branch1 not in ("u+", "u-") or c.branch2 not in ("s+", "s-"):
+        raise ValueError("connection must pair an unstable branch of dep with a stable branch of arr")
+    parts = [_orbit_parts(dep), _orbit_parts(arr)]
+    state0 = np.asfortranarray(np.array([p[0] for p in parts]).T)
+    period = np.array([p[1] for p in parts])
+    M = np.asfortranarray(np.stack([p[2] for p in parts], axis=2))
+    section = ("x", 1.0 - MU) if section is None else section
+    i1, i2 = _MANIFOLD_BRANCHES.index(c.branch1), _MANIFOLD_BRANCHES.index(c.branch2)
+    T = np.concatenate([np.full(n_phase, abs(float(t_max))), np.full(n_phase, -abs(float(t_max)))])
+    best, tau1, tau2, h = c, float(c.tau1), float(c.tau2), float(spacing)
+    out = []
+    for _ in range(levels):
+        p1, p2 = _refine_phases(tau1, h, n_phase), _refine_phases(tau2, h, n_phase)
+        seeds = hotpath.manifold_seeds(state0, period, M, np.concatenate([p1, p2]), eps=eps, MU=MU, integ=integ, ctx=ctx)
+        if np.any(seeds.status != 0):
+            raise ValueError("an orbit has no usable hyperbolic pair (status %s of manifold_seeds)" % list(seeds.status))
+        start = np.asfortranarray(np.concatenate([seeds.starts[:, i1, :n_phase, 0], seeds.starts[:, i2, n_phase:, 1]], axis=1))
+        fl = hotpath.section_flight(start, T, section=section, sec_dir=0, n_cross=n_cross, r_min=r_min, MU=MU, integ=integ, ctx=ctx)
+        ends = np.where(fl.status == 0, fl.x_end, np.nan)
+        m = hotpath.state_match(ends[:, :n_phase], ends[:, n_phase:], w=w, ctx=ctx)
+        ok = [i for i in range(n_phase) if m.index[i] >= 0]
+        if ok:
+            i = min(ok, key=lambda q: m.dist[q])
+            j = int(m.index[i])
+            if m.dist[i] < best.dist:
+                best = ManifoldConnection(float(m.dist[i]), float(m.dr[i]) * DU, float(m.dv[i]) * DU / TU * 1e3, float(seeds.tau[i]),
+                                          float(seeds.tau[n_phase + j]), c.branch1, c.branch2, float(fl.t_end[i]),
+                                          float(fl.t_end[n_phase + j]), fl.x_end[:, i].copy(), fl.x_end[:, n_phase + j].copy(),
+                                          start[:, i].copy(), start[:, n_phase + j].copy(), MU)
+                tau1, tau2 = float(p1[i]), float(p2[j])
+        out.append(best)
+        h = _refine_shrink(h, n_phase)
+    return out

@@ -1347,6 +1347,64 @@ def halo_correct(seeds, mode, tol=1e-12, max_iter=15, t_max=10.0, MU=MU, sing_to
     return HaloCorrect(state, period, resid, its, hist, status)
 
 
+HALO_TARGET_JACOBI, HALO_TARGET_PERIOD = 0, 1
+_HALO_TARGETS = {"jacobi": HALO_TARGET_JACOBI, "period": HALO_TARGET_PERIOD}
+HaloTarget = collections.namedtuple("HaloTarget", "state period jacobi resid iterations history status")
+
+
+def halo_target(seeds, targets, what="jacobi", planar=False, tol=1e-12, max_iter=15, t_max=10.0, MU=MU, sing_tol=1e-12, integ=None,
+                ctx=None):
+    """Periodic orbits at a given Jacobi constant (what = 'jacobi') or period ('period') on the device (lto_halo_target_batch,
+    DESIGN 4.27): the corrector of halo_correct with (x0, z0, vy0) -- planar: (x0, vy0), z0 = 0 -- as unknowns and q - q* as a third
+    residual.  seeds [6] or [6 x B]; targets a scalar (every orbit's one target), [K] (the K members of a march, the same for every
+    orbit) or [K x B]: orbit b's members are corrected one after another in the one launch, each from the secant through the last
+    two.  Returns HaloTarget(state [6 x K x B], period, jacobi, resid, iterations [K x B], history [(max_iter + 1) x K x B] (NaN past
+    the last flight), status [K x B]: 0 converged, 1 max_iter reached, 2 unusable, 3 singular step) -- without the batch axis for
+    a single seed and without the target axis for a scalar target."""
+    if isinstance(what, str):                     # shapes, enumerations and finiteness are checked before any library call
+        if what not in _HALO_TARGETS:
+            raise ValueError("what must be 'jacobi' or 'period'")
+        what = _HALO_TARGETS[what]
+    elif what not in (HALO_TARGET_JACOBI, HALO_TARGET_PERIOD):
+        raise ValueError("what must be HALO_TARGET_JACOBI or HALO_TARGET_PERIOD")
+    S = np.asarray(seeds, dtype=np.float64)
+    if S.ndim not in (1, 2) or S.shape[0] != 6 or S.size == 0:
+        raise ValueError("seeds must be [6] or [6 x B]")
+    batched = S.ndim == 2
+    S = np.asfortranarray(S.reshape(6, -1))
+    B = S.shape[1]
+    Q = np.asarray(targets, dtype=np.float64)
+    marched = Q.ndim >= 1
+    if Q.ndim > 2 or Q.size == 0 or (Q.ndim == 2 and (not batched or Q.shape[1] != B)):
+        raise ValueError("targets must be a scalar, [K] or, with seeds [6 x B], [K x B]")
+    K = Q.shape[0] if marched else 1
+    Q = np.asfortranarray(np.broadcast_to(Q.reshape(K, -1), (K, B)))
+    max_iter = int(max_iter)
+    if max_iter < 0:
+        raise ValueError("max_iter must be >= 0")
+    tol, t_max, sing_tol = float(tol), float(t_max), float(sing_tol)
+    if not (tol > 0.0) or not (np.isfinite(t_max) and t_max > 0.0) or not (0.0 <= sing_tol < 1.0):
+        raise ValueError("need tol > 0, t_max finite and > 0, sing_tol in [0, 1)")
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    state = np.zeros((6, K, B), order="F")
+    period, jac, resid = np.zeros((K, B), order="F"), np.zeros((K, B), order="F"), np.zeros((K, B), order="F")
+    hist = np.zeros((max_iter + 1, K, B), order="F")
+    its = np.zeros((K, B), dtype=np.int32, order="F")
+    status = np.zeros((K, B), dtype=np.int32, order="F")
+    ctx.check(ctx.fn("halo_target_batch")(ctx.handle, K, B, float(MU), int(bool(planar)), int(what), _ptr(S), _ptr(Q), tol, max_iter, t_max,
+                                          sing_tol, C.byref(integ), _ptr(state), _ptr(period), _ptr(jac), _ptr(resid), _ptr(its),
+                                          _ptr(hist), _ptr(status)))
+    out = [state, period, jac, resid, its, hist, status]
+    if not batched:
+        out = [o[..., 0] for o in out]
+    if not marched:
+        out = [out[0][:, 0]] + [o[0] for o in out[1:5]] + [out[5][:, 0], out[6][0]]
+    if not batched and not marched:
+        out = [out[0], float(out[1]), float(out[2]), float(out[3]), int(out[4]), out[5], int(out[6])]
+    return HaloTarget(*out)
+
+
 def halo_table(state0, period, n_samples, MU=MU, integ=None, ctx=None):
     """One revolution of periodic orbits on the device, sampled at n_samples equal times with the state-transition matrix carried
     through (lto_halo_table_batch).  state0 [6] or [6 x B], period scalar or [B].  Returns HaloTable(times [n] = i /
