@@ -427,6 +427,104 @@ __device__ __forceinline__ void rhs14(const double (&y)[14], const TrajParams& t
   }
 }
 
+// ------------------------------------------------------------------ column coefficients times a weight (pipeline sweeps)
+// The coefficient waves of the pipeline sweeps store every value of VarCoef14 except lhat times the stage's RK4 weight w.
+// Every such value is a sum of terms that are linear in a few roots -- kappa_b / d_b^(3/2) for G and H, the acceleration limit for the
+// always-thrust-limited laws (p = 0, p = 1: m, ua, ub, un are all proportional to it), m / ua / ub / un themselves for the p > 1
+// laws (their clamp compares unweighted values) -- so w goes into the roots, three of them constants of the lane (CoefWeight), and
+// the values come out weighted: no product per stored value.  The slopes are not formed (a coefficient wave needs none but
+// lambda_m_dot).  Same formulas, term by term, as the VAR block of rhs14, which every other kernel keeps (and the 12-dim sweeps:
+// pipe_common.hpp, pipe_coef_build).
+struct CoefWeight {
+  double w, k1w, k2w, cw;     // w, w (1 - MU), w MU, w cT
+  __device__ __forceinline__ CoefWeight(const double w_, const TrajParams& tp) : w(w_), k1w(w_ * (1.0 - tp.MU)), k2w(w_ * tp.MU), cw(w_ * tp.cT) {}
+};
+
+// w G, w H at position (x, yy, z) and lambda_v = (lx0, ly0, lz0)
+__device__ __forceinline__ void gravity_coef_weighted(const double x, const double yy, const double z, const double lx0, const double ly0,
+                                                      const double lz0, const double MU, const CoefWeight& W, VarCoef12& g) {
+  const double a = x + MU, b = a - 1.0;
+  const double yz2 = __builtin_fma(yy, yy, z * z);
+  const double d1 = __builtin_fma(a, a, yz2), d2 = __builtin_fma(b, b, yz2);
+  const double i1 = rsqrt_nr(d1), i2 = rsqrt_nr(d2);
+  const double i1s = i1 * i1, i2s = i2 * i2;
+  const double c1 = W.k1w * (i1s * i1), c2 = W.k2w * (i2s * i2);
+  const double cs = c1 + c2, omc = W.w - cs;                   // w cs, w (1 - cs)
+  const double e1 = 3.0 * c1 * i1s, e2 = 3.0 * c2 * i2s;
+  const double ee = e1 + e2;
+  const double sa = e1 * a, tb = e2 * b;
+  const double st = sa + tb;
+  g.Gxx = __builtin_fma(sa, a, __builtin_fma(tb, b, omc));
+  g.Gyy = __builtin_fma(ee * yy, yy, omc);
+  g.Gzz = __builtin_fma(ee * z, z, -cs);
+  g.Gxy = st * yy; g.Gxz = st * z; g.Gyz = ee * yy * z;
+  const double s1 = __builtin_fma(a, lx0, __builtin_fma(yy, ly0, z * lz0));
+  const double s2 = __builtin_fma(b, lx0, __builtin_fma(yy, ly0, z * lz0));
+  const double q1 = 5.0 * e1 * i1s * s1, q2 = 5.0 * e2 * i2s * s2;
+  const double es = __builtin_fma(e1, s1, e2 * s2);
+  const double qq = q1 + q2;
+  const double qa = __builtin_fma(q1, a, q2 * b);
+  g.Hxx = es + 2.0 * st * lx0 - __builtin_fma(q1 * a, a, q2 * b * b);
+  g.Hyy = es + 2.0 * ee * yy * ly0 - qq * yy * yy;
+  g.Hzz = es + 2.0 * ee * z * lz0 - qq * z * z;
+  g.Hxy = __builtin_fma(st, ly0, ee * yy * lx0) - qa * yy;
+  g.Hxz = __builtin_fma(st, lz0, ee * z * lx0) - qa * z;
+  g.Hyz = ee * __builtin_fma(yy, lz0, z * ly0) - qq * yy * z;
+}
+
+// the control law's w m, w ua, w ub, w un (aL: the acceleration limit, aLw: w times it)
+template <int PM>
+__device__ __forceinline__ void control_weighted(const TrajParams& tp, const double aL, const double aLw, const double w, const double n,
+                                                 const double inv_n, double& m, double& ua, double& ub, double& un, bool& tlim) {
+  static_assert(PM >= PM_P0 && PM < PM_ANY, "compiled per control-law class");
+  if constexpr (PM == PM_P0 || PM == PM_P1) {
+    control_law<PM, true>(tp, aLw, n, inv_n, m, ua, ub, un, tlim);
+  } else {
+    control_law<PM, true>(tp, aL, n, inv_n, m, ua, ub, un, tlim);
+    m *= w; ua *= w; ub *= w; un *= w;
+  }
+}
+
+// vc = w x (the coefficients of rhs14<PM, true> at y), lhat unweighted; returns w lambda_m_dot of the thrust-limited laws (what
+// the coefficient waves accumulate for p = 0, p = 1).  For those two laws tl = 1, ntl = 0 are known here: mm and Ll are exact
+// zeros and the blend of rhs14 is gone.
+template <int PM>
+__device__ __forceinline__ double coef14_weighted(const double (&y)[14], const TrajParams& tp, const CoefWeight& W, VarCoef14& vc) {
+  VarCoef12& g = vc.c;
+  const double mass = y[6];
+  const double lx0 = y[10], ly0 = y[11], lz0 = y[12], lm = y[13];
+  gravity_coef_weighted(y[0], y[1], y[2], lx0, ly0, lz0, tp.MU, W, g);
+  const double n2 = __builtin_fma(lx0, lx0, __builtin_fma(ly0, ly0, lz0 * lz0));
+  const double inv_n = (n2 > 0.0) ? rsqrt_nr(n2) : 0.0;
+  const double n = n2 * inv_n;
+  const double inv_m = rcp_nr(mass);
+  double m, un;
+  bool tlim;
+  control_weighted<PM>(tp, tp.cT * inv_m, W.cw * inv_m, W.w, n, inv_n, m, g.ua, g.ub, un, tlim);
+  const double lhx = lx0 * inv_n, lhy = ly0 * inv_n, lhz = lz0 * inv_n;
+  g.lx = lhx; g.ly = lhy; g.lz = lhz;
+  const double kt = tp.kappa_td;
+  const double mn_over_m = (m * n) * inv_m;
+  vc.mn = -kt * mass * un;
+  if constexpr (PM == PM_P0 || PM == PM_P1) {
+    const double um_neg = m * inv_m;
+    vc.umx = um_neg * lhx; vc.umy = um_neg * lhy; vc.umz = um_neg * lhz;
+    vc.mm = 0.0;
+    vc.Lm = 2.0 * mn_over_m * inv_m;
+    vc.Ln = -(__builtin_fma(un, n, m) * inv_m);
+    vc.Ll = 0.0;
+  } else {
+    const double tl = tlim ? 1.0 : 0.0, ntl = 1.0 - tl;
+    const double um_neg = tl * (m * inv_m);
+    vc.umx = um_neg * lhx; vc.umy = um_neg * lhy; vc.umz = um_neg * lhz;
+    vc.mm = -kt * (ntl * m);
+    vc.Lm = tl * (2.0 * mn_over_m * inv_m);
+    vc.Ln = __builtin_fma(-tl, __builtin_fma(un, n, m) * inv_m, ntl * (kt * lm * un));
+    vc.Ll = ntl * (kt * m);
+  }
+  return -mn_over_m;
+}
+
 // One STM column c = (a, b, mu, g, d, nu) of the 14-dim system.
 __device__ __forceinline__ void var_col14(const VarCoef14& v, const double w2, const double (&c)[14], double (&dc)[14]) {
   const VarCoef12& vc = v.c;

@@ -404,17 +404,18 @@ template <int ND, int PM>
 __device__ __forceinline__ void pipe8_role_coef(const IndirectArgs& a, const PipeLane& L, const int seg, const int stage,
                                                 const double* s_int, double* s_coef, double* s_lm, Pipe8Flags* fl) {
   using P = Pipe8<ND, PM>;
-  using Coef = typename PipeCoef<ND>::type;
-  constexpr int NI = P::NI, NC = P::NC, SD = P::SD;
+  constexpr int NI = P::NI, SD = P::SD;
   const int steps = a.steps, npairs = (steps + 1) >> 1;
   // every coefficient except the unit vector lhat (entries 14..16) is stored times the stage's RK4 argument weight
-  // (the last stage carries h/2 = 3 h/6: the column lanes advance 3 y per step, col_dpp_step)
+  // (the last stage carries h/2 = 3 h/6: the column lanes advance 3 y per step, col_dpp_step); the weight enters the few roots
+  // the coefficients are sums of (dynamics.hpp, coef12_weighted / coef14_weighted), not every stored value
   const double as = (stage == 2) ? L.h : 0.5 * L.h;
-  const double bw = (stage == 0 || stage == 3) ? L.h * (1.0 / 6.0) : L.h * (1.0 / 3.0);   // RK4 weight of the stage's slope
+  const CoefWeight W(as, L.tp);                             // (14-dim)
+  const double rb = (stage == 1) ? 2.0 / 3.0 : 1.0 / 3.0;   // RK4 weight of the stage's slope (h/6, h/3, h/3, h/6) over `as`
   double lm_acc = 0.0;
   auto build = [&](const int step) {
     const int slab = (step & 3) * 4 + stage;
-    double arg[ND], dead[ND];
+    double arg[ND];
 #pragma unroll
     for (int c = 0; c < ND; ++c) arg[c] = 0.0;
     const p8_d2* src = reinterpret_cast<const p8_d2*>(s_int + slab * P::SLABD) + seg;
@@ -423,15 +424,20 @@ __device__ __forceinline__ void pipe8_role_coef(const IndirectArgs& a, const Pip
     for (int q = 0; q < P::NPAIR; ++q) { const p8_d2 v = src[q * PIPE_SEG]; lv[2 * q] = v.x; lv[2 * q + 1] = v.y; }
 #pragma unroll
     for (int e = 0; e < NI; ++e) arg[P::Arg::idx[e]] = lv[P::lin(e)];
-    Coef vc;
-    if constexpr (ND == 12) rhs12<PM, true>(arg, L.tp, dead, vc);
-    else rhs14<PM, true>(arg, L.tp, dead, vc);
-    if constexpr (P::LM_OFF) lm_acc = __builtin_fma(bw, dead[ND - 1], lm_acc);   // lambda_m_dot = -umag n / m at this stage
-    const double* o = reinterpret_cast<const double*>(&vc);
-    double* dst = s_coef + slab * SD;
-    constexpr int NST = P::LM_OFF ? NC - 1 : NC;     // d lambda_m_dot / d lambda_m = 0 for these laws: never read
+    // (LM_OFF: lm_acc takes lambda_m_dot = -umag n / m at this stage)
+    if constexpr (ND == 12) {
+      // (12-dim: rhs12 and a product per stored value.  With the weight in the roots the build was 14 products shorter and the
+      // sweep measured 0.07 us slower: profiles/r10_pipe_level.txt)
+      double dead[ND];
+      VarCoef12 vc;
+      rhs12<PM, true>(arg, L.tp, dead, vc);
+      const double* o = reinterpret_cast<const double*>(&vc);
+      double* dst = s_coef + slab * SD;
 #pragma unroll
-    for (int e = 0; e < NST; ++e) dst[CoefBySegment::at<P::NA>(e, seg)] = (e < 14 || e > 16) ? o[e] * as : o[e];
+      for (int e = 0; e < P::NC; ++e) dst[CoefBySegment::at<P::NA>(e, seg)] = (e < 14 || e > 16) ? o[e] * as : o[e];
+    } else {
+      pipe_coef_build<ND, PM, P::Arg::LM, P::NA>(arg, L.tp, W, rb, s_coef + slab * SD, seg, lm_acc);
+    }
   };
   P8_WAIT_DECL;
   for (int p = 0; p < npairs + 1; ++p) {

@@ -41,6 +41,39 @@ struct CoefBySegment {   // [segment][value], records padded to 33 doubles: the 
   __device__ static int lane_base(int lane, int seg) { return seg * LD + lane; }
 };
 
+// The record of one (stage, segment): the values of VarCoef12 / 14 in their order.  LM = false (always-thrust-limited laws of the
+// 14-dim system, a decision on the control-law class at compile time): d mdot / d m (mm) and d lambda_m_dot / d lambda_m (Ll, the
+// last value) are exact zeros there; they are not stored and no column stage multiplies by them.
+template <int ND, bool LM> struct CoefRecord {
+  static constexpr int NC = sizeof(typename PipeCoef<ND>::type) / sizeof(double);
+  static constexpr bool ZEROS_OUT = (ND == 14) && !LM;
+  static constexpr int MM = 20, LL = 24;                         // vc.mm, vc.Ll
+  static constexpr int N = ZEROS_OUT ? NC - 2 : NC;
+  static constexpr bool stored(int e) { return !(ZEROS_OUT && (e == MM || e == LL)); }
+  static constexpr int pos(int e) { return (ZEROS_OUT && e > MM) ? e - 1 : e; }
+};
+static_assert(offsetof(VarCoef14, mm) == CoefRecord<14, false>::MM * sizeof(double) && offsetof(VarCoef14, Ll) == CoefRecord<14, false>::LL * sizeof(double), "CoefRecord::MM, LL");
+
+// The coefficient lane of (stage, segment): the coefficients at the stage argument `arg`, times the stage's weight (W; lhat
+// unweighted), into the record at dst (the stage's slab).  Where the coefficient wave integrates lambda_m (14-dim, LM = false)
+// lm_acc takes the stage's share, (RK4 weight of the slope) x lambda_m_dot = rb x (w lambda_m_dot): rb = 2/3 for the second stage,
+// 1/3 for the others (h/6, h/3, h/3, h/6 over h/2, h/2, h, h/2).
+template <int ND, int PM, bool LM, int NA>
+__device__ __forceinline__ void pipe_coef_build(const double (&arg)[ND], const TrajParams& tp, const CoefWeight& W, const double rb,
+                                                double* dst, const int seg, double& lm_acc) {
+  using R = CoefRecord<ND, LM>;
+  static_assert(ND == 14, "the 12-dim coefficient lanes keep rhs12 and a product per stored value");
+  static_assert(R::N <= 2 * NA, "two values per active column lane");
+  typename PipeCoef<ND>::type vc;
+  const double lmw = coef14_weighted<PM>(arg, tp, W, vc);
+  if constexpr (!LM) lm_acc = __builtin_fma(rb, lmw, lm_acc);
+  const double* o = reinterpret_cast<const double*>(&vc);
+#pragma unroll
+  for (int e = 0; e < R::NC; ++e) {
+    if (R::stored(e)) dst[CoefBySegment::at<NA>(R::pos(e), seg)] = o[e];
+  }
+}
+
 // What a lane knows about its segment.
 struct PipeLane {
   int s;            // segment (after the optional balanced order)
@@ -182,7 +215,8 @@ __device__ __forceinline__ void fmac_c(double& acc, const double cA, const doubl
 //   out = init + a F(arg) arg
 // The rows with coefficient products accumulate straight onto init (no separate slope, no separate RK update); the
 // Coriolis rows start with a plain FMA, the others with a copy of init.  Same formulas as var_col12 / var_col14.
-// LM = false (always-thrust-limited laws of the 14-dim system): d lambda_m_dot / d lambda_m = 0, that term is skipped.
+// LM = false (always-thrust-limited laws of the 14-dim system): d mdot / d m = d lambda_m_dot / d lambda_m = 0, those two terms are
+// skipped and the record does not hold them (CoefRecord).
 // `out` may be the same array as `init` (row c of out is formed from row c of init alone), not the same as `arg`.
 template <int ND, bool LM = true, int NA = ND>
 __device__ __forceinline__ void col_dpp_stage(const double cA, const double cB, const double aw2, const double a,
@@ -192,8 +226,9 @@ __device__ __forceinline__ void col_dpp_stage(const double cA, const double cB, 
   enum { Gxx, Gyy, Gzz, Gxy, Gxz, Gyz, Hxx, Hyy, Hzz, Hxy, Hxz, Hyz, Ua, Ub, Lx, Ly, Lz, Umx, Umy, Umz, Mm, Mn, LLm, LLn, LLl };
   const double ax = arg[0], ay = arg[1], az = arg[2];
   const double dx = arg[D], dyv = arg[D + 1], dz = arg[D + 2];
-#define FM(E, acc, x) fmac_c<NA, E, false>(acc, cA, cB, x)
-#define FN(E, acc, x) fmac_c<NA, E, true>(acc, cA, cB, x)
+  using R = CoefRecord<ND, LM>;
+#define FM(E, acc, x) fmac_c<NA, R::pos(E), false>(acc, cA, cB, x)
+#define FN(E, acc, x) fmac_c<NA, R::pos(E), true>(acc, cA, cB, x)
   double ld = 0.0;
   FM(Lx, ld, dx); FM(Ly, ld, dyv); FM(Lz, ld, dz);
   double tl = 0.0;
@@ -215,7 +250,8 @@ __device__ __forceinline__ void col_dpp_stage(const double cA, const double cB, 
     const double mu = arg[6];
     FM(Umx, o3, mu); FM(Umy, o4, mu); FM(Umz, o5, mu);
     double o6 = init[6], o13 = init[13];
-    FM(Mm, o6, mu); FM(Mn, o6, ld);
+    if constexpr (LM) FM(Mm, o6, mu);
+    FM(Mn, o6, ld);
     FM(LLm, o13, mu); FM(LLn, o13, ld);
     if constexpr (LM) FM(LLl, o13, arg[13]);
     out[6] = o6; out[13] = o13;
