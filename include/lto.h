@@ -501,6 +501,43 @@ int lto_halo_target_batch(lto_ctx* ctx, int n_targets, int n_batch, double MU, i
                           const double* targets, double tol, int max_iter, double t_max, double sing_tol,
                           const lto_integrator* integ, double* state_out, double* period_out, double* jacobi_out, double* resid_out,
                           int* iterations, double* history, int* status);
+/* Families of periodic orbits by pseudo-arclength continuation.  The unknowns u = (x0, z0, vy0) move along the
+ * family's own tangent, so that no coordinate, Jacobi constant or period has to stay monotone along the family.  The flight is
+ * lto_halo_target_batch's; F = (vx, vz) at the first return to y = 0 and DF [2 x 3] = Phi[(3,5), j] - f[(3,5)] Phi[1, j] / f[1],
+ * j = 0, 2, 4 -- with planar != 0 the z0 row and column of the system are the identity's, and z0 must be 0.
+ *   tangent    c = DF_0 x DF_1, n = |c|_2, sigma = the sign of c . t_row, t = sigma c / n, det = sigma n (the signed determinant of
+ *              [DF; t]: it changes sign between two members where another family branches off)
+ *   a member   from the point u_prev with the row vector t_row and the step ds: u_pred = u_prev + ds t_row (product and sum each
+ *              rounded once), then u <- u - [DF; t_row]^-1 (F; t_row . (u - u_pred)) by the 3 x 3 LU of lto_halo_target_batch until
+ *              res = max(|vx|, |vz|, |t_row . (u - u_pred)|) < tol (planar: without |vz|), or max_iter steps (status 1)
+ *   the step   an attempt fails if its status is not 0 or if t . t_row < cos_min (status 4; cos_min = 0: no such test); then
+ *              ds <- ds / 2 and the member is tried again from u_prev; once ds < ds_min the member keeps the last attempt's status
+ *              and the rest of the orbit's members are NaN with status 2.  After an accepted member of <= fast_iter Newton steps
+ *              ds <- min(ds grow, ds_max).  The next member starts from the accepted u with t_row = its tangent.
+ *   the start  dir_is_tangent = 0: member 0 is the seed corrected onto the family perpendicularly to the family -- u_pred = the
+ *              seed, t_row = the tangent of the seed's own DF (first flight) with the sign that makes t_row . dir0 > 0, kept for the
+ *              member; its ds_out is 0, it is tried once, and ds0 is the step of member 1.  dir_is_tangent = 1: the seed is a point
+ *              of the family and dir0 its tangent, used as given (not normalised); member 0 is the step from it by ds0.  With the
+ *              seed at a branch point and dir0 = (0, +-1, 0) this leaves a planar family for the one that is born there.
+ * seeds [6 x n_batch] (rows 0, 2, 4 are read), dir0 [3 x n_batch], ds0 [n_batch].  A result does not depend on its batch, and member
+ * k equals bit for bit (but for `halvings`) the one-member call with dir_is_tangent = 1, grow = 1, seed = member k - 1's state_out,
+ * dir0 = its tangent_out and ds0 = member k's ds_out.
+ * Outputs, member (k, b) at record n_members b + k: state_out [6 x ..], tangent_out [3 x ..], det_out, ds_out (the step of the last
+ * attempt), halvings, period_out = 2 x the crossing time, jacobi_out, resid_out, iterations and history [(max_iter + 1) x ..] of the
+ * last attempt (NaN past its last flight), status: 0 converged; 1 max_iter reached (the numbers of the last attempt are kept);
+ * 2 unusable (seed or dir0 not finite, dir0 = 0, vy0 = 0, z0 != 0 with planar, with dir_is_tangent = 0 a dir0 perpendicular to the
+ * seed's tangent, no crossing before t_max, max_steps used up); 3 singular step (lto_halo_target_batch's test) or no tangent (n or
+ * c . t_row zero or not finite); 4 the tangent turned beyond cos_min.  Status 2, 3, 4: the member's numbers are NaN.  Any status but 0
+ * ends the orbit's march.  Every output but state_out and status may be NULL.
+ * LTO_EINVAL: lto_halo_target_batch's cases (n_members for n_targets), a ds0 not finite or <= 0, ds_min <= 0 or > ds_max, ds_max not
+ * finite, grow < 1 or not finite, fast_iter < 0, cos_min outside [0, 1).  Any other method than LTO_RK4 and LTO_DOP853_ADAPTIVE:
+ * LTO_EUNSUPPORTED. */
+int lto_halo_arclength_batch(lto_ctx* ctx, int n_members, int n_batch, double MU, int planar, int dir_is_tangent, const double* seeds,
+                             const double* dir0, const double* ds0, double ds_min, double ds_max, double grow, int fast_iter,
+                             double cos_min, double tol, int max_iter, double t_max, double sing_tol, const lto_integrator* integ,
+                             double* state_out, double* tangent_out, double* det_out, double* ds_out, int* halvings,
+                             double* period_out, double* jacobi_out, double* resid_out, int* iterations, double* history,
+                             int* status);
 /* Invariant manifolds of periodic orbits: the free ways off an orbit and onto one, from the monodromy matrix
  * lto_halo_table_batch hands back.  A result does not depend on its batch: orbit b, arc b and row b equal their single call bit for
  * bit.  The flights are LTO_DOP853_ADAPTIVE at integ's rtol / atol / max_steps, or LTO_RK4 with integ->steps steps per flight (per

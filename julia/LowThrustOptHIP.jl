@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_target, halo_table, manifold_seeds, section_flight, state_match,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_target, halo_arclength, halo_table, manifold_seeds, section_flight, state_match,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -851,6 +851,34 @@ function halo_target(ctx::LtoContext, seeds::Matrix{Float64}, targets::Matrix{Fl
                Float64(sing_tol), Ref(integ), state, period, jac, resid, its, hist, status)
     check(ctx, rc)
     (state, period, jac, resid, Int.(its), hist, Int.(status))
+end
+
+# Families of periodic orbits by pseudo-arclength continuation (`lto_halo_arclength_batch`, DESIGN 4.28): seeds [6 x B], dir0 [3 x B]
+# and ds0 [B]; orbit b's K members, their step halvings and the growth of ds run in one launch.  dir_is_tangent = false: member 0 is
+# the seed corrected onto the family, the march leaves towards dir0; true: the seed is a point of the family and dir0 its tangent.
+# Returns (state [6 x K x B], tangent [3 x K x B], det, ds [K x B], halvings, period, jacobi, resid, iterations [K x B],
+# history [(max_iter + 1) x K x B], status [K x B]).
+function halo_arclength(ctx::LtoContext, seeds::Matrix{Float64}, dir0::Matrix{Float64}, ds0::Vector{Float64}, n_members::Integer, MU;
+                        planar::Bool = false, dir_is_tangent::Bool = false, ds_min = minimum(ds0) / 1024, ds_max = maximum(ds0),
+                        grow = 1.0, fast_iter::Integer = 3, cos_min = 0.0, tol = 1e-12, max_iter::Integer = 15, t_max = 10.0,
+                        sing_tol = 1e-12, integ::LtoIntegrator = LtoIntegrator())
+    size(seeds, 1) == 6 || error("halo_arclength: seeds must be 6 x B")
+    B = size(seeds, 2)
+    size(dir0) == (3, B) || error("halo_arclength: dir0 must be 3 x B")
+    length(ds0) == B || error("halo_arclength: one ds0 per orbit")
+    K = Int(n_members)
+    state = zeros(6, K, B); tangent = zeros(3, K, B); det = zeros(K, B); ds = zeros(K, B); period = zeros(K, B); jac = zeros(K, B)
+    resid = zeros(K, B); hist = zeros(max_iter + 1, K, B)
+    halv = zeros(Cint, K, B); its = zeros(Cint, K, B); status = zeros(Cint, K, B)
+    rc = ccall((:lto_halo_arclength_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cdouble, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Cdouble, Cint,
+                Cdouble, Cdouble, Cint, Cdouble, Cdouble, Ref{LtoIntegrator}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, K, B, Float64(MU), planar ? 1 : 0, dir_is_tangent ? 1 : 0, seeds, dir0, ds0, Float64(ds_min), Float64(ds_max),
+               Float64(grow), fast_iter, Float64(cos_min), Float64(tol), max_iter, Float64(t_max), Float64(sing_tol), Ref(integ),
+               state, tangent, det, ds, halv, period, jac, resid, its, hist, status)
+    check(ctx, rc)
+    (state, tangent, det, ds, Int.(halv), period, jac, resid, Int.(its), hist, Int.(status))
 end
 
 # One revolution of B periodic orbits from (state0 [6 x B], period [B]) at n_samples equal times, the state-transition matrix carried

@@ -14,7 +14,8 @@ from .hotpath import (Context, Group, Comm, GroupComm, auto_kernel, default_cont
                       replay_sample_knots, guidance_gains, GuidanceGains, guided_flight, GuidedFlight, guided_updates,
                       guidance_gains_mass, guided_flight_mass, halo_correct, HaloCorrect, halo_table, HaloTable,
                       HALO_HOLD_Z0, HALO_HOLD_X0, HALO_PLANAR, manifold_seeds, ManifoldSeeds, section_flight, SectionFlight,
-                      state_match, StateMatch, halo_target, HaloTarget, HALO_TARGET_JACOBI, HALO_TARGET_PERIOD)
+                      state_match, StateMatch, halo_target, HaloTarget, HALO_TARGET_JACOBI, HALO_TARGET_PERIOD,
+                      halo_arclength, HaloArclength)
 from . import synth  # noqa: F401
 
 __version__ = "0.1.0"

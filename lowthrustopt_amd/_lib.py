@@ -103,6 +103,9 @@ SIGNATURES = {
                                        _vp, _vp]),
     "lto_halo_target_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_int, C.c_double,
                                         C.c_double, C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_halo_arclength_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double,
+                                           C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                           C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lto_halo_manifold_seeds_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_double,
                                                 C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp]),
     "lto_section_flight_batch": (C.c_int, [_vp, C.c_int, C.c_double, _vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, _vp, C.c_int,

@@ -399,6 +399,25 @@ struct HaloTargetArgs {
   int* iters; int* status;                   // [T][B]
 };
 hipError_t launch_halo_target(int method, const HaloTargetArgs& a, hipStream_t st);
+// Pseudo-arclength continuation of a family of periodic orbits (kernels_halo_arclength.hip): the unknowns (x0, z0, vy0)
+// move along the family's tangent, the third equation keeps the iterate on the plane perpendicular to the tangent through the
+// predicted point, and orbit b's T members, their step halvings and the growth of ds all run inside the launch.  Member (k, b) is
+// record T b + k of every output.
+struct HaloArclengthArgs {
+  const double* seed;                        // [6][B]
+  const double* dir0;                        // [3][B]
+  const double* ds0;                         // [B]
+  int T, B, planar, dir_is_tangent, max_iter, fast_iter;
+  double MU, ds_min, ds_max, grow, cos_min, tol, t_max, sing_tol;
+  int steps;                                 // RK4: steps over t_max
+  double rtol, atol; int max_steps;          // DOP853
+  double* state;                             // [6][T][B]
+  double* tangent;                           // [3][T][B]
+  double* det; double* ds; double* period; double* jacobi; double* resid;  // [T][B]
+  double* hist;                              // [max_iter + 1][T][B]
+  int* halvings; int* iters; int* status;    // [T][B]
+};
+hipError_t launch_halo_arclength(int method, const HaloArclengthArgs& a, hipStream_t st);
 // Invariant manifolds of periodic orbits (kernels_manifold.hip).  Every array is in the caller's layout.
 // Seeds: the hyperbolic pair of M [6][6][B] (one lane per orbit), the two eigenvectors carried along the orbit to the phases tau [P]
 // (one lane per (orbit, phase, kind), kind 0 unstable forward over tau P, kind 1 stable backward over (1 - tau) P), then the starts

@@ -1741,7 +1741,8 @@ def lyapunov_seed(which, Ax, MU):
 
 
 HaloOrbit = collections.namedtuple("HaloOrbit", "times states state0 period jacobi nu M closure resid iterations status")
-HaloFamily = collections.namedtuple("HaloFamily", "states period resid iterations status")
+# tangent, det and ds are filled by the pseudo-arclength march (halo_family_arclength) and None otherwise
+HaloFamily = collections.namedtuple("HaloFamily", "states period resid iterations status tangent det ds", defaults=(None, None, None))
 
 
 def halo_orbit(seed, mode, n_samples=100, tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None, ctx=None):
@@ -2052,3 +2053,127 @@ def manifold_connection_refine(dep, arr, connection, levels=4, n_phase=16, spaci
         out.append(best)
         h = _refine_shrink(h, n_phase)
     return out
+
+
+# ------------------------------------------------------------------------------------ families by pseudo-arclength
+HaloBranchPoint = collections.namedtuple("HaloBranchPoint", "state tangent det period jacobi s trials status")
+HaloBranch = collections.namedtuple("HaloBranch", "family branch_point lyapunov table")
+
+
+def halo_family_arclength(seed, n_members, ds, direction, planar=False, tangent=None, ds_min=None, ds_max=None, grow=1.0, fast_iter=3,
+                          cos_min=0.0, tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None, ctx=None):
+    """A family of periodic orbits followed along its own tangent in (x0, z0, vy0), the whole march with its step control in ONE
+    device call (hotpath.halo_arclength): it passes the folds of x0, z0, vy0, C and P that stop halo_family and halo_family_by.
+    seed [6] or [6 x F] (the F families advance side by side).  Without `tangent` member 0 is the seed corrected onto the family and
+    the march leaves it towards `direction` [3] or [3 x F]; with `tangent` [3] or [3 x F] the seed is a point of the family, member
+    0 the step of ds from it along that tangent, and `direction` is not read (pass None).  Returns HaloFamily(states
+    [6 x K (x F)], period, resid, iterations, status, tangent [3 x K (x F)], det, ds [K (x F)])."""
+    mode1 = tangent is not None
+    if not mode1 and direction is None:
+        raise ValueError("give a direction [3] to leave the seed along, or the seed's tangent")
+    c = hotpath.halo_arclength(seed, n_members, ds, tangent if mode1 else direction, planar=planar, dir_is_tangent=mode1, ds_min=ds_min,
+                               ds_max=ds_max, grow=grow, fast_iter=fast_iter, cos_min=cos_min, tol=tol, max_iter=max_iter, t_max=t_max,
+                               MU=hotpath.MU if MU is None else MU, integ=integ, ctx=ctx)
+    return HaloFamily(c.state, c.period, c.resid, c.iterations, c.status, c.tangent, c.det, c.ds)
+
+
+def _sign_changes(v):
+    """The indices k >= 1 with v[k] v[k - 1] < 0 (a NaN on either side is no change)."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        return [int(k) for k in np.nonzero(v[1:] * v[:-1] < 0.0)[0] + 1]
+
+
+def family_bifurcations(fam):
+    """The members k of one family (HaloFamily of halo_family_arclength, no family axis) with det_k det_(k-1) < 0: between members
+    k - 1 and k another family branches off."""
+    if fam.det is None or np.ndim(fam.det) != 1:
+        raise ValueError("fam must be one family marched by halo_family_arclength")
+    return _sign_changes(fam.det)
+
+
+def family_folds(fam):
+    """Per unknown, the members k of one family where that component of the tangent changes sign: {'x0': [...], 'z0': [...],
+    'vy0': [...]} -- the coordinate has an extremum between members k - 1 and k."""
+    if fam.tangent is None or np.ndim(fam.tangent) != 2:
+        raise ValueError("fam must be one family marched by halo_family_arclength")
+    return {name: _sign_changes(fam.tangent[j]) for j, name in enumerate(("x0", "z0", "vy0"))}
+
+
+def _secant_next(s0, d0, s1, d1):
+    """The zero of the line through (s0, d0) and (s1, d1)."""
+    return s1 - d1 * (s1 - s0) / (d1 - d0)
+
+
+def halo_branch_point(fam, k, planar=False, max_trials=8, rel=1e-9, tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None, ctx=None):
+    """The point between members k - 1 and k of one family (k from family_bifurcations) where det = 0: a secant in the arclength s
+    from member k - 1 on det(s), every trial a one-member call from member k - 1 along its tangent; it stops at |det| < rel
+    |det_(k-1)| or after max_trials.  Returns HaloBranchPoint(state, tangent, det, period, jacobi, s, trials [(s, det)], status of
+    the last trial)."""
+    k = int(k)
+    if fam.det is None or np.ndim(fam.det) != 1 or not 1 <= k < fam.det.shape[0]:
+        raise ValueError("fam must be one family marched by halo_family_arclength and 1 <= k < its length")
+    if not fam.det[k] * fam.det[k - 1] < 0.0:
+        raise ValueError("det does not change sign between members k - 1 and k")
+    MU = hotpath.MU if MU is None else MU
+    s0, d0, s1, d1 = 0.0, float(fam.det[k - 1]), float(fam.ds[k]), float(fam.det[k])
+    trials, m, s = [], None, s1
+    for _ in range(int(max_trials)):
+        s = _secant_next(s0, d0, s1, d1)
+        if not (np.isfinite(s) and s > 0.0):
+            break
+        m = hotpath.halo_arclength(fam.states[:, k - 1], 1, s, fam.tangent[:, k - 1], planar=planar, dir_is_tangent=True, ds_min=s, ds_max=s,
+                                   tol=tol, max_iter=max_iter, t_max=t_max, MU=MU, integ=integ, ctx=ctx)
+        if m.status[0] != 0:
+            break
+        trials.append((s, float(m.det[0])))
+        if abs(m.det[0]) < rel * abs(fam.det[k - 1]):
+            break
+        s0, d0, s1, d1 = s1, d1, s, float(m.det[0])
+    if m is None:
+        raise ValueError("the secant left the interval at its first trial")
+    return HaloBranchPoint(m.state[:, 0], m.tangent[:, 0], float(m.det[0]), float(m.period[0]), float(m.jacobi[0]), float(s), trials,
+                           int(m.status[0]))
+
+
+def halo_from_lyapunov(which, n_members, ds, north=True, Ax=1e-2, ds_switch=1e-2, ds_lyapunov=1e-2, block=16, max_blocks=16, n_samples=0,
+                       grow=1.0, tol=1e-12, max_iter=15, t_max=10.0, MU=None, integ=None, ctx=None):
+    """A halo family from the mass ratio alone: the linear Lyapunov seed of x-amplitude Ax about L1 or L2 (lyapunov_seed), the planar
+    corrector, the planar family in the 3-unknown form (z0 = 0) towards larger orbits in blocks of `block` members of step
+    ds_lyapunov until det changes sign, the branch point (halo_branch_point), one step of ds_switch off the plane along (0, +1, 0)
+    (north) or (0, -1, 0), and n_members members of step ds up the halo family (a step the kernel had to halve grows back by `grow`
+    up to ds).  n_samples > 0: one hotpath.halo_table call for all members.  Returns HaloBranch(family: HaloFamily whose member 0 is
+    the step off the plane, branch_point: HaloBranchPoint, lyapunov: the planar family's last block as HaloFamily, table: HaloTable
+    or None)."""
+    MU = hotpath.MU if MU is None else MU
+    kw = dict(tol=tol, max_iter=max_iter, t_max=t_max, MU=MU, integ=integ, ctx=ctx)
+    seed, _ = lyapunov_seed(which, Ax, MU)
+    c = hotpath.halo_correct(seed, "planar", **kw)
+    if c.status != 0:
+        raise ValueError("the planar corrector gave up on the Lyapunov seed (status %d)" % c.status)
+    fam = halo_family_arclength(c.state, block, ds_lyapunov, [0.0, 0.0, 1.0 if c.state[4] > 0.0 else -1.0], **kw)
+    for _ in range(int(max_blocks)):
+        if np.any(fam.status != 0):
+            raise ValueError("the planar family ended before a bifurcation (statuses %s)" % list(fam.status))
+        flips = family_bifurcations(fam)
+        if flips:
+            break
+        nxt = halo_family_arclength(fam.states[:, -1], block, float(fam.ds[-1]) if fam.ds[-1] > 0.0 else ds_lyapunov, None,
+                                    tangent=fam.tangent[:, -1], **kw)
+        # the last member of the block before leads the new one, so that a sign change across the seam is seen
+        fam = HaloFamily(*[np.concatenate([np.asarray(a)[..., -1:], np.asarray(b)], axis=-1) for a, b in zip(fam, nxt)])
+    else:
+        raise ValueError("no bifurcation within %d blocks of %d members" % (int(max_blocks), int(block)))
+    bp = halo_branch_point(fam, flips[0], **kw)
+    if bp.status != 0:
+        raise ValueError("the branch point's last trial has status %d" % bp.status)
+    sw = halo_family_arclength(bp.state, 1, ds_switch, None, tangent=[0.0, 1.0 if north else -1.0, 0.0], **kw)
+    if sw.status[0] != 0:
+        raise ValueError("the step off the plane has status %d" % sw.status[0])
+    up = halo_family_arclength(sw.states[:, 0], n_members, ds, None, tangent=sw.tangent[:, 0], grow=grow, ds_max=ds, **kw)
+    family = HaloFamily(*[np.concatenate([np.asarray(a), np.asarray(b)], axis=-1) for a, b in zip(sw, up)])
+    table = None
+    if int(n_samples) > 0:
+        table = hotpath.halo_table(np.asfortranarray(family.states), np.ascontiguousarray(family.period), int(n_samples), MU=MU,
+                                   integ=integ, ctx=ctx)
+    return HaloBranch(family, bp, fam, table)

@@ -1405,6 +1405,71 @@ def halo_target(seeds, targets, what="jacobi", planar=False, tol=1e-12, max_iter
     return HaloTarget(*out)
 
 
+HaloArclength = collections.namedtuple("HaloArclength",
+                                       "state tangent det ds halvings period jacobi resid iterations history status")
+
+
+def halo_arclength(seeds, n_members, ds, direction, planar=False, dir_is_tangent=False, ds_min=None, ds_max=None, grow=1.0, fast_iter=3,
+                   cos_min=0.0, tol=1e-12, max_iter=15, t_max=10.0, MU=MU, sing_tol=1e-12, integ=None, ctx=None):
+    """A family of periodic orbits by pseudo-arclength continuation on the device (lto_halo_arclength_batch): the
+    unknowns (x0, z0, vy0) -- planar: (x0, vy0), z0 = 0 -- move along the family's tangent, so that the march passes the folds of
+    every coordinate, of the Jacobi constant and of the period.  seeds [6] or [6 x B]; ds a scalar or [B], the first step;
+    direction [3] or [3 x B] in (x0, z0, vy0).  dir_is_tangent = False: member 0 is the seed corrected onto the family, and the
+    march leaves it towards the side of `direction`; True: the seed is a point of the family, `direction` its tangent (used as
+    given) and member 0 the step from it by ds -- from a branch point with direction (0, +-1, 0) onto the family born there.  A
+    failed attempt (not converged in max_iter steps, or the tangent turned beyond cos_min) is tried again with ds / 2 down to
+    ds_min (default: the smallest ds / 1024); after a member of <= fast_iter steps ds grows by `grow` up to ds_max (default: the
+    largest ds).  Returns HaloArclength(state [6 x K x B], tangent [3 x K x B], det (its sign changes where another family branches
+    off), ds (the accepted steps), halvings, period, jacobi, resid, iterations [K x B], history [(max_iter + 1) x K x B], status
+    [K x B]: 0 converged, 1 max_iter reached, 2 unusable, 3 singular step or no tangent, 4 the tangent turned beyond cos_min; any
+    status but 0 ends the orbit's march, the rest is NaN with status 2) -- without the batch axis for a single seed."""
+    S = np.asarray(seeds, dtype=np.float64)       # shapes and values are checked before any library call
+    if S.ndim not in (1, 2) or S.shape[0] != 6 or S.size == 0:
+        raise ValueError("seeds must be [6] or [6 x B]")
+    batched = S.ndim == 2
+    S = np.asfortranarray(S.reshape(6, -1))
+    B = S.shape[1]
+    K = int(n_members)
+    if K < 1:
+        raise ValueError("n_members must be >= 1")
+    D = np.asarray(direction, dtype=np.float64)
+    if D.ndim not in (1, 2) or D.shape[0] != 3 or (D.ndim == 2 and (not batched or D.shape[1] != B)):
+        raise ValueError("direction must be [3] or, with seeds [6 x B], [3 x B]")
+    D = np.asfortranarray(np.broadcast_to(D.reshape(3, -1), (3, B)))
+    s0 = np.asarray(ds, dtype=np.float64)
+    if s0.ndim > 1 or (s0.ndim == 1 and (not batched or s0.size != B)):
+        raise ValueError("ds must be a scalar or, with seeds [6 x B], [B]")
+    s0 = np.ascontiguousarray(np.broadcast_to(s0.reshape(-1), (B,)))
+    if not np.all(np.isfinite(s0)) or not np.all(s0 > 0.0):
+        raise ValueError("ds must be finite and > 0")
+    ds_min = float(s0.min() / 1024.0 if ds_min is None else ds_min)
+    ds_max = float(s0.max() if ds_max is None else ds_max)
+    grow, cos_min, fast_iter, max_iter = float(grow), float(cos_min), int(fast_iter), int(max_iter)
+    if not (ds_min > 0.0) or not (ds_min <= ds_max) or not np.isfinite(ds_max):
+        raise ValueError("need 0 < ds_min <= ds_max, both finite")
+    if not (grow >= 1.0) or not np.isfinite(grow) or fast_iter < 0 or not (0.0 <= cos_min < 1.0):
+        raise ValueError("need grow finite and >= 1, fast_iter >= 0, cos_min in [0, 1)")
+    if max_iter < 0:
+        raise ValueError("max_iter must be >= 0")
+    tol, t_max, sing_tol = float(tol), float(t_max), float(sing_tol)
+    if not (tol > 0.0) or not (np.isfinite(t_max) and t_max > 0.0) or not (0.0 <= sing_tol < 1.0):
+        raise ValueError("need tol > 0, t_max finite and > 0, sing_tol in [0, 1)")
+    ctx = ctx or default_context()
+    integ = integ or integrator()
+    state, tangent = np.zeros((6, K, B), order="F"), np.zeros((3, K, B), order="F")
+    det, dso, period, jac, resid = (np.zeros((K, B), order="F") for _ in range(5))
+    hist = np.zeros((max_iter + 1, K, B), order="F")
+    halv, its, status = (np.zeros((K, B), dtype=np.int32, order="F") for _ in range(3))
+    ctx.check(ctx.fn("halo_arclength_batch")(ctx.handle, K, B, float(MU), int(bool(planar)), int(bool(dir_is_tangent)), _ptr(S), _ptr(D),
+                                             _ptr(s0), ds_min, ds_max, grow, fast_iter, cos_min, tol, max_iter, t_max, sing_tol,
+                                             C.byref(integ), _ptr(state), _ptr(tangent), _ptr(det), _ptr(dso), _ptr(halv), _ptr(period),
+                                             _ptr(jac), _ptr(resid), _ptr(its), _ptr(hist), _ptr(status)))
+    out = [state, tangent, det, dso, halv, period, jac, resid, its, hist, status]
+    if not batched:
+        out = [o[..., 0] for o in out]
+    return HaloArclength(*out)
+
+
 def halo_table(state0, period, n_samples, MU=MU, integ=None, ctx=None):
     """One revolution of periodic orbits on the device, sampled at n_samples equal times with the state-transition matrix carried
     through (lto_halo_table_batch).  state0 [6] or [6 x B], period scalar or [B].  Returns HaloTable(times [n] = i /
