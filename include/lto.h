@@ -612,6 +612,52 @@ int lto_section_flight_batch(lto_ctx* ctx, int n_arcs, double MU, const double* 
                              int* status);
 int lto_state_match_batch(lto_ctx* ctx, int nA, int nB, const double* A, const double* Bs, double w, int* index, double* dist,
                           double* dr, double* dv);
+/* Station-keeping on periodic orbits: the Floquet-mode feedback gains from the directions
+ * lto_halo_manifold_seeds_batch hands back, and batched flights under any impulsive linear feedback.  A result does not depend on
+ * its batch: record b and run b equal their single call bit for bit.
+ *
+ * lto_stationkeep_gains_batch: V [6 x 2 x n_phase x n_batch] in the layout of the seeds call's V_out (0 the unstable unit vector
+ * v_u, 1 the stable one v_s), one record per (phase, orbit).  With S = [2 Omega, -I; I, 0], Omega = [0 1 0; -1 0 0; 0 0 0], S v_s is a
+ * left eigenvector of the monodromy matrix for lambda_u at every phase.  Every product, sum and quotient is rounded on its own (no
+ * fused multiply-add), sums run left to right over the index from the first term, the square roots are correctly rounded, so the
+ * host can reproduce the outputs bit for bit:
+ *   w = (2 v_s[1] - v_s[3], -2 v_s[0] - v_s[4], -v_s[5], v_s[0], v_s[1], v_s[2])
+ *   p = sum_i w_i v_u_i;  ns = sqrt(sum_i w_i w_i);  nu = sqrt(sum_i v_u_i v_u_i)
+ *   W_i = w_i / p;  wv2 = (W_3 W_3 + W_4 W_4) + W_5 W_5;  alpha = sqrt(wv2) / sqrt(sum_i W_i W_i)
+ *   G[r + 3 c] = (-(W_{3+r} W_c)) / wv2,  r = 0..2, c = 0..5
+ * Outputs: W [6 x n_phase x n_batch] (W . v_u = 1), G [3 x 6 x n_phase x n_batch] (column-major 3 x 6 blocks: dv = G dx is the
+ * minimum-norm velocity change that zeroes the unstable component W . dx), alpha [n_phase x n_batch] = |w_v| / |W|, how well a
+ * velocity change reaches the unstable mode; W and alpha may be NULL.  status [n_phase x n_batch]: 0; 2 a non-finite input; 3 alpha
+ * <= sing_tol (or not a number) or |p| <= (sing_tol ns) nu.  Status 2 and 3 leave NaN in that record's outputs and touch no other.
+ * LTO_EINVAL: n_phase or n_batch < 1, sing_tol outside [0, 1), 18 n_phase n_batch > 2^31 - 1.
+ *
+ * lto_stationkeep_flight_batch: n_batch runs, one lane each, about n_orb = 1 (one orbit for every run) or n_batch (run b about orbit
+ * b) orbits given by X_ref [6 x n_man x n_orb] the reference points at the burn epochs, dt [n_man x n_orb] the ballistic span after
+ * burn j (finite, > 0) and G [3 x 6 x n_man x n_orb] the gains (any finite matrices: the flight knows nothing of their origin).  x0
+ * [6 x n_batch] is the state at the first burn epoch; nav [6 x n_upd x n_batch] and exe [4 x n_upd x n_batch], n_upd = n_rev n_man
+ * (either may be NULL: no error), are drawn by the caller.  Per run, for u = r n_man + j, r = 0..n_rev-1, j = 0..n_man-1:
+ *   1. d = x - X_ref_j;  dev[0, u, b] = |d_r|, dev[1, u, b] = |d_v|
+ *   2. r_lost > 0 and |d_r| > r_lost: status 1, lost_at = u, the run ends with the state and the totals it has
+ *   3. c = G_j (d + nav[:, u, b]), m = |c|.  m < dv_min: no burn, dv_hist[u, b] = 0.  Otherwise, dv_max > 0 and m > dv_max: c <- c
+ *      (dv_max / m); the applied burn a = (1 + exe[0, u, b]) c + exe[1:4, u, b]; v <- v + a, dv_total += |a|, n_burn += 1,
+ *      dv_hist[u, b] = |a|
+ *   4. x over dt_j as a span of its own: LTO_DOP853_ADAPTIVE at integ's rtol / atol / max_steps (the error norm over the six
+ *      components, max_steps counted per span), or LTO_RK4 with integ->steps steps per span; any other method: LTO_EUNSUPPORTED.
+ * Outputs: x_final [6 x n_batch] the state after the last span, dv_total [n_batch], n_burn [n_batch], dev [2 x n_upd x n_batch],
+ * dv_hist [n_upd x n_batch], dev_final [2 x n_batch] the deviation from X_ref_0 after the last span, accepted / rejected [n_batch]
+ * summed over the spans, status [n_batch]: 0; 1 lost; 2 a non-finite start, reference, gain, error draw, burn or state, or a span
+ * that used up max_steps: x_final, dv_total and dev_final are NaN; lost_at [n_batch] (-1: not lost).  A lost run keeps dev[:, lost_at]
+ * and reports it as dev_final; its dv_hist from lost_at on and its dev past lost_at are NaN.  A failed run's dev and dv_hist are
+ * NaN from the update that failed on.  dev, dv_hist, dev_final, n_burn, accepted, rejected and lost_at may be NULL.
+ * LTO_EINVAL: n_man, n_rev or n_batch < 1, n_orb neither 1 nor n_batch, a dt not finite or <= 0, dv_min, dv_max or r_lost negative
+ * or not finite, MU outside (0, 1), LTO_RK4 with steps < 1, 6 n_upd n_batch > 2^31 - 1. */
+int lto_stationkeep_gains_batch(lto_ctx* ctx, int n_phase, int n_batch, const double* V, double sing_tol, double* W, double* G,
+                                double* alpha, int* status);
+int lto_stationkeep_flight_batch(lto_ctx* ctx, int n_man, int n_rev, int n_batch, double MU, const double* X_ref, const double* dt,
+                                 const double* G, int n_orb, const double* x0, const double* nav, const double* exe, double dv_min,
+                                 double dv_max, double r_lost, const lto_integrator* integ, double* x_final, double* dv_total,
+                                 int* n_burn, double* dev, double* dv_hist, double* dev_final, int* accepted, int* rejected,
+                                 int* status, int* lost_at);
 /* Mesh re-distribution of converged 12-dim solutions (the indirect method's counterpart of meshRefine_direct): the
  * nodes of XC [12 x n_nodes x n_batch] on t [n_nodes x n_tgrids] (n_tgrids = 1 or n_batch) are moved, and their number changed to
  * n_new, so that every new segment carries the same share of a per-segment monitor w_i > 0.  Per trajectory:

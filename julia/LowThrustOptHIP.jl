@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_target, halo_arclength, halo_table, manifold_seeds, section_flight, state_match,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_target, halo_arclength, halo_table, manifold_seeds, section_flight, state_match, stationkeep_gains, stationkeep_flight,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -949,6 +949,49 @@ function state_match(ctx::LtoContext, A::Matrix{Float64}, Bs::Matrix{Float64}; w
                ctx.handle, nA, nB, A, Bs, Float64(w), index, dist, dr, dv)
     check(ctx, rc)
     (Int.(index) .+ 1, dist, dr, dv)
+end
+
+# The Floquet-mode station-keeping gains from the directions V [6 x 2 x P x B] of manifold_seeds (`lto_stationkeep_gains_batch`,
+# DESIGN 4.29).  Returns (W [6 x P x B], G [3 x 6 x P x B], alpha [P x B], status [P x B]).
+function stationkeep_gains(ctx::LtoContext, V::Array{Float64,4}; sing_tol = 1e-8)
+    size(V, 1) == 6 && size(V, 2) == 2 || error("stationkeep_gains: V must be 6 x 2 x P x B")
+    P = size(V, 3); B = size(V, 4)
+    W = zeros(6, P, B); G = zeros(3, 6, P, B); alpha = zeros(P, B); status = zeros(Cint, P, B)
+    rc = ccall((:lto_stationkeep_gains_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, P, B, V, Float64(sing_tol), W, G, alpha, status)
+    check(ctx, rc)
+    (W, G, alpha, Int.(status))
+end
+
+# B runs from x0 [6 x B] under the impulsive feedback G [3 x 6 x n_man x n_orb] about X_ref [6 x n_man x n_orb] with the spans dt
+# [n_man x n_orb], n_orb = 1 or B, for n_rev revolutions (`lto_stationkeep_flight_batch`, DESIGN 4.29).  nav [6 x n_upd x B] and exe
+# [4 x n_upd x B] or nothing.  Returns (x_final [6 x B], dv_total [B], n_burn [B], dev [2 x n_upd x B], dv_hist [n_upd x B], dev_final
+# [2 x B], accepted [B], rejected [B], status [B], lost_at [B], counted from 0 as in C, -1: not lost).
+function stationkeep_flight(ctx::LtoContext, X_ref::Array{Float64,3}, dt::Matrix{Float64}, G::Array{Float64,4}, x0::Matrix{Float64},
+                            n_rev::Integer, MU; nav = nothing, exe = nothing, dv_min = 0.0, dv_max = 0.0, r_lost = 0.0,
+                            integ::LtoIntegrator = LtoIntegrator())
+    size(x0, 1) == 6 || error("stationkeep_flight: x0 must be 6 x B")
+    B = size(x0, 2)
+    size(X_ref, 1) == 6 || error("stationkeep_flight: X_ref must be 6 x n_man x n_orb")
+    n_man = size(X_ref, 2); n_orb = size(X_ref, 3)
+    n_orb == 1 || n_orb == B || error("stationkeep_flight: one orbit or one per run")
+    size(dt) == (n_man, n_orb) || error("stationkeep_flight: dt must be n_man x n_orb")
+    size(G) == (3, 6, n_man, n_orb) || error("stationkeep_flight: G must be 3 x 6 x n_man x n_orb")
+    n_upd = n_rev * n_man
+    nav === nothing || size(nav) == (6, n_upd, B) || error("stationkeep_flight: nav must be 6 x n_upd x B")
+    exe === nothing || size(exe) == (4, n_upd, B) || error("stationkeep_flight: exe must be 4 x n_upd x B")
+    x_final = zeros(6, B); dv_total = zeros(B); dev = zeros(2, n_upd, B); dv_hist = zeros(n_upd, B); dev_final = zeros(2, B)
+    n_burn = zeros(Cint, B); acc = zeros(Cint, B); rej = zeros(Cint, B); status = zeros(Cint, B); lost_at = zeros(Cint, B)
+    rc = ccall((:lto_stationkeep_flight_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Cdouble, Cdouble, Cdouble, Ref{LtoIntegrator}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}),
+               ctx.handle, n_man, n_rev, B, Float64(MU), X_ref, dt, G, n_orb, x0, nav === nothing ? C_NULL : nav,
+               exe === nothing ? C_NULL : exe, Float64(dv_min), Float64(dv_max), Float64(r_lost), Ref(integ), x_final, dv_total, n_burn,
+               dev, dv_hist, dev_final, acc, rej, status, lost_at)
+    check(ctx, rc)
+    (x_final, dv_total, Int.(n_burn), dev, dv_hist, dev_final, Int.(acc), Int.(rej), Int.(status), Int.(lost_at))
 end
 
 # optimizeTraj with flagEnd = true: one Jacobian sweep and the exact free-end QP step.  Returns (x_update, u_update, p1_update,

@@ -462,6 +462,38 @@ struct StateMatchArgs {
   double* dist; double* dr; double* dv;
 };
 hipError_t launch_state_match(const StateMatchArgs& a, hipStream_t st);
+// Station-keeping on periodic orbits (kernels_stationkeep.hip).  Every array is in the caller's layout.
+// Gains: one lane per (phase, orbit) record g = n_phase b + j of V [6][2][n] (0 unstable, 1 stable).  W and alpha may be null.
+struct StationGainsArgs {
+  const double* V;                             // [6][2][n]
+  long n;                                      // n_phase n_batch
+  double sing_tol;
+  double* W;                                   // [6][n]
+  double* G;                                   // [3][6][n], column-major 3 x 6 blocks
+  double* alpha;                               // [n]
+  int* status;                                 // [n]
+};
+hipError_t launch_stationkeep_gains(const StationGainsArgs& a, hipStream_t st);
+// Flights with impulsive linear feedback, one lane per run; update u = r n_man + j, n_upd = n_rev n_man.  n_orb = 1: every run reads
+// the one orbit's reference, gains and spans; n_orb = B: run b reads orbit b's.  nav, exe, dev, dv_hist, dev_final, n_burn, accepted,
+// rejected and lost_at may be null.
+struct StationFlightArgs {
+  const double* X_ref; const double* dt; const double* G;   // [6][n_man][n_orb], [n_man][n_orb], [3][6][n_man][n_orb]
+  const double* x0;                            // [6][B]
+  const double* nav; const double* exe;        // [6][n_upd][B], [4][n_upd][B]
+  int n_man, n_rev, B, n_orb;
+  double MU, dv_min, dv_max, r_lost;
+  int steps;                                   // RK4: steps per span
+  double rtol, atol; int max_steps;            // DOP853: max_steps counts per span
+  double* x_final;                             // [6][B]
+  double* dv_total;                            // [B]
+  double* dev;                                 // [2][n_upd][B]
+  double* dv_hist;                             // [n_upd][B]
+  double* dev_final;                           // [2][B]
+  int* n_burn; int* accepted; int* rejected; int* status; int* lost_at;   // [B]
+};
+// method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
+hipError_t launch_stationkeep_flight(int method, const StationFlightArgs& a, hipStream_t st);
 // Mesh equidistribution of the indirect method (kernels_remesh.hip).  Grid: per trajectory b the monitor of old segment
 // i is w[b (n-1) + i], or nacc + nrej there when w is null; old grids t[b t_stride + i].
 // Out: t_out [n_batch][n_new] and seg_of [n_batch][n_new], the old node each new one is propagated from.

@@ -19,6 +19,7 @@
 // No LDS but the match's two reduction arrays, no atomics, plain vector stores; per-lane flags are doubles (DESIGN "Compiler hazards").
 #include "kernels.hpp"
 #include "dop853_stop.hpp"
+#include "crtbp_ballistic.hpp"
 
 namespace lto {
 
@@ -56,24 +57,7 @@ struct SysCrtbpVarDir {
   }
 };
 
-// The ballistic CRTBP, y = (r, v) (the expressions of kernels_stack.hip's SysBallistic), times sgn = +-1.
-struct SysCrtbpDir {
-  static constexpr int DIM = 6;
-  double MU, sgn;
-  __device__ __forceinline__ void rhs(const double (&y)[6], double (&k)[6]) const {
-    const double x = y[0], yy = y[1], z = y[2];
-    const double a = x + MU, b = a - 1.0;
-    const double yz2 = __builtin_fma(yy, yy, z * z);
-    const double d1 = __builtin_fma(a, a, yz2), d2 = __builtin_fma(b, b, yz2);
-    const double i1 = rsqrt_nr(d1), i2 = rsqrt_nr(d2);
-    const double c1 = (1.0 - MU) * (i1 * i1 * i1), c2 = MU * (i2 * i2 * i2);
-    const double cs = c1 + c2;
-    k[0] = sgn * y[3]; k[1] = sgn * y[4]; k[2] = sgn * y[5];
-    k[3] = sgn * __builtin_fma(-c1, a, __builtin_fma(-c2, b, __builtin_fma(2.0, y[4], x)));
-    k[4] = sgn * __builtin_fma(-cs, yy, __builtin_fma(-2.0, y[3], yy));
-    k[5] = sgn * (-cs * z);
-  }
-};
+// The ballistic CRTBP, y = (r, v), times sgn = +-1: SysCrtbpDir of crtbp_ballistic.hpp, with finite_all.
 
 // Jacobi constant C = x^2 + y^2 + 2 (1 - MU) / r1 + 2 MU / r2 - v^2
 __device__ __forceinline__ double jacobi6(const double MU, const double (&y)[6]) {
@@ -82,14 +66,6 @@ __device__ __forceinline__ double jacobi6(const double MU, const double (&y)[6])
   const double r1 = sqrt(__builtin_fma(a, a, yz2)), r2 = sqrt(__builtin_fma(b, b, yz2));
   const double v2 = __builtin_fma(y[3], y[3], __builtin_fma(y[4], y[4], y[5] * y[5]));
   return __builtin_fma(y[0], y[0], y[1] * y[1]) + 2.0 * (1.0 - MU) / r1 + 2.0 * MU / r2 - v2;
-}
-
-template <int N>
-__device__ __forceinline__ bool finite_all(const double (&y)[N]) {
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < N; ++i) s += y[i];
-  return (s - s) == 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- 6 x 6 algebra

@@ -2177,3 +2177,125 @@ def halo_from_lyapunov(which, n_members, ds, north=True, Ax=1e-2, ds_switch=1e-2
         table = hotpath.halo_table(np.asfortranarray(family.states), np.ascontiguousarray(family.period), int(n_samples), MU=MU,
                                    integ=integ, ctx=ctx)
     return HaloBranch(family, bp, fam, table)
+
+
+# ------------------------------------------------------------------------------------------- station-keeping
+StationGains = collections.namedtuple("StationGains", "tau X_ref dt G W alpha lam")
+YEAR_DAYS = 365.25
+
+
+def stationkeep_spans(tau, period):
+    """dt [n_man]: the ballistic span after the burn at phase tau_j, ((tau_{j+1} - tau_j) mod 1) P, the wrap-round span from the
+    last phase to the first one of the next revolution last.  tau [n_man] in [0, 1), strictly increasing; one phase: dt = P."""
+    tau = np.asarray(tau, dtype=np.float64).reshape(-1)
+    if tau.size < 1 or not np.all(np.isfinite(tau)) or np.any(tau < 0.0) or np.any(tau >= 1.0) or np.any(np.diff(tau) <= 0.0):
+        raise ValueError("the burn phases must lie in [0, 1) and increase strictly")
+    d = np.mod(np.roll(tau, -1) - tau, 1.0)
+    if tau.size == 1:
+        d[0] = 1.0
+    return d * float(period)
+
+
+def stationkeeping_gains(orbit, taus=None, n_man=4, sing_tol=1e-8, MU=None, integ=None, ctx=None):
+    """The Floquet-mode station-keeping law of a periodic orbit in two library calls: the hyperbolic directions at
+    the burn phases (hotpath.manifold_seeds), then the gains (hotpath.stationkeep_gains).  orbit: what halo_orbit returns, or
+    (state0, period, M); taus [n_man] the burn phases (any finite values, wrapped into [0, 1), increasing after the wrap), default j
+    / n_man.  Returns StationGains(tau [n_man] as wrapped, X_ref [6 x n_man] the orbit point at each phase as the stable vector's
+    flight reached it, dt [n_man] the span after each burn (stationkeep_spans), G [3 x 6 x n_man], W [6 x n_man], alpha [n_man],
+    lam = (lambda_u, lambda_s)).  A seeds or gains status other than 0 raises ValueError."""
+    MU = hotpath.MU if MU is None else MU
+    state0, period, M = _orbit_parts(orbit)
+    if taus is None:
+        n_man = int(n_man)
+        if n_man < 1:
+            raise ValueError("n_man must be >= 1")
+        taus = np.arange(n_man) / float(n_man)
+    seeds = hotpath.manifold_seeds(state0, period, M, taus, MU=MU, integ=integ, ctx=ctx)
+    if seeds.status != 0:
+        raise ValueError("the orbit has no usable hyperbolic pair (status %d of manifold_seeds)" % seeds.status)
+    dt = stationkeep_spans(seeds.tau, period)
+    g = hotpath.stationkeep_gains(seeds.V, sing_tol, ctx=ctx)
+    if np.any(g.status != 0):
+        raise ValueError("no usable gain at phase(s) %s (statuses %s of stationkeep_gains)"
+                         % (list(seeds.tau[g.status != 0]), list(g.status[g.status != 0])))
+    return StationGains(seeds.tau, np.asfortranarray(seeds.X[:, 1, :]), dt, g.G, g.W, g.alpha, seeds.lam)
+
+
+def stationkeep_draws(n_runs, n_upd, inj_sigma_r_km, inj_sigma_v_ms, nav_sigma_r_km, nav_sigma_v_ms, exe_sigma_frac, exe_sigma_ms,
+                      seed, DU, TU):
+    """The error draws of a station-keeping Monte Carlo from numpy.random.default_rng(seed), always in the order injection,
+    navigation, execution, so that a stream does not move when another sigma changes: inj [6 x n_runs] (Gaussian, sigma per
+    position axis in km and per velocity axis in m/s), nav [6 x n_upd x n_runs] (the same units, added to the measured deviation
+    at every update), exe [4 x n_upd x n_runs] (row 0 the relative magnitude error of sigma exe_sigma_frac, rows 1:4 a bias of
+    exe_sigma_ms m/s per axis).  Every run is disturbed: there is no nominal run 0 as in dispersion_starts, a run on the orbit
+    itself says nothing about keeping it.  nav is None when both its sigmas are None, exe likewise; a single None counts as 0."""
+    n, m = int(n_runs), int(n_upd)
+    if n < 1 or m < 1:
+        raise ValueError("n_runs and n_upd must be >= 1")
+    pos, vel = 1.0 / DU, 1e-3 * TU / DU
+    rng = np.random.default_rng(seed)
+    inj = rng.standard_normal((6, n))
+    nav = rng.standard_normal((6, m, n))
+    exe = rng.standard_normal((4, m, n))
+    inj[0:3] *= float(inj_sigma_r_km) * pos
+    inj[3:6] *= float(inj_sigma_v_ms) * vel
+    if nav_sigma_r_km is None and nav_sigma_v_ms is None:
+        nav = None
+    else:
+        nav[0:3] *= float(nav_sigma_r_km or 0.0) * pos
+        nav[3:6] *= float(nav_sigma_v_ms or 0.0) * vel
+        nav = np.asfortranarray(nav)
+    if exe_sigma_frac is None and exe_sigma_ms is None:
+        exe = None
+    else:
+        exe[0] *= float(exe_sigma_frac or 0.0)
+        exe[1:4] *= float(exe_sigma_ms or 0.0) * vel
+        exe = np.asfortranarray(exe)
+    return np.asfortranarray(inj), nav, exe
+
+
+def stationkeep(orbit, n_rev, n_runs, inj_sigma_r_km=1.0, inj_sigma_v_ms=0.01, nav_sigma_r_km=None, nav_sigma_v_ms=None,
+                exe_sigma_frac=None, exe_sigma_ms=None, n_man=4, taus=None, dv_min_ms=0.0, dv_max_ms=0.0, r_lost_km=0.0, seed=0,
+                DU=None, TU=None, MU=None, integ=None, gains=None, ctx=None):
+    """Monte-Carlo station-keeping cost of a periodic orbit: n_runs runs injected at the first burn phase with
+    Gaussian errors (stationkeep_draws), flown for n_rev revolutions of n_man burns each under the Floquet-mode
+    law of stationkeeping_gains -- or under `gains`, any StationGains (one with G = 0 flies uncontrolled) -- in ONE flight call
+    (hotpath.stationkeep_flight).  dv_min_ms the dead band, dv_max_ms the largest burn (0: none), r_lost_km the position deviation
+    that ends a run as lost (0: never).  Returns a dict: dv_ms [n_runs] the summed |dv|, t_days [n_runs] the time flown (to the
+    loss for a lost run), dv_per_year_ms = dv_ms per 365.25 days of t_days, n_burn, dev_r_km and dev_v_ms [n_upd x n_runs] the
+    deviation at every update, dv_hist_ms [n_upd x n_runs], dev_final_r_km, dev_final_v_ms, x_final, status, lost_at, lost_share,
+    gains, x0, nav, exe and, over the runs of status 0, percentiles = {"dv_ms": {50: .., 95: .., 99: ..}, "dv_per_year_ms": {..},
+    "dev_r_km": {..}, "dev_v_ms": {..}} (the last two of each run's largest deviation)."""
+    from .constants import DU as DU0, TU as TU0
+    DU, TU = DU0 if DU is None else float(DU), TU0 if TU is None else float(TU)
+    MU = hotpath.MU if MU is None else MU
+    n_rev, n_runs = int(n_rev), int(n_runs)
+    if n_rev < 1 or n_runs < 1:
+        raise ValueError("n_rev and n_runs must be >= 1")
+    g = stationkeeping_gains(orbit, taus, n_man, MU=MU, integ=integ, ctx=ctx) if gains is None else gains
+    X_ref = np.asarray(g.X_ref, dtype=np.float64)
+    dt = np.asarray(g.dt, dtype=np.float64).reshape(-1)
+    if X_ref.ndim != 2 or X_ref.shape != (6, dt.size):
+        raise ValueError("gains must be a StationGains of one orbit: X_ref [6 x n_man], dt [n_man], G [3 x 6 x n_man]")
+    n_upd = n_rev * dt.size
+    inj, nav, exe = stationkeep_draws(n_runs, n_upd, inj_sigma_r_km, inj_sigma_v_ms, nav_sigma_r_km, nav_sigma_v_ms, exe_sigma_frac,
+                                      exe_sigma_ms, seed, DU, TU)
+    x0 = np.asfortranarray(X_ref[:, :1] + inj)
+    km, ms = DU, DU / TU * 1e3
+    r = hotpath.stationkeep_flight(X_ref, dt, g.G, x0, n_rev, nav, exe, float(dv_min_ms) / ms, float(dv_max_ms) / ms,
+                                   float(r_lost_km) / km, MU=MU, integ=integ, ctx=ctx)
+    status, lost_at = np.asarray(r.status), np.asarray(r.lost_at)
+    t_upd = np.concatenate([[0.0], np.cumsum(np.tile(dt, n_rev))])            # the time of update u; [n_upd]: the end
+    t_days = t_upd[np.where(status == 1, lost_at, n_upd)] * TU / day
+    dv_ms = np.asarray(r.dv_total) * ms
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_year = np.where(t_days > 0.0, dv_ms / (t_days / YEAR_DAYS), np.nan)
+    out = dict(dv_ms=dv_ms, t_days=t_days, dv_per_year_ms=per_year, n_burn=r.n_burn, dev_r_km=r.dev[0] * km, dev_v_ms=r.dev[1] * ms,
+               dv_hist_ms=r.dv_hist * ms, dev_final_r_km=r.dev_final[0] * km, dev_final_v_ms=r.dev_final[1] * ms, x_final=r.x_final,
+               status=status, lost_at=lost_at, lost_share=float(np.mean(status == 1)), gains=g, x0=x0, nav=nav, exe=exe)
+    ok = status == 0
+    per_run = dict(dv_ms=dv_ms, dv_per_year_ms=per_year, dev_r_km=np.max(out["dev_r_km"], axis=0, initial=0.0),
+                   dev_v_ms=np.max(out["dev_v_ms"], axis=0, initial=0.0))
+    out["percentiles"] = {k: {q: (float(np.percentile(v[ok], q)) if ok.any() else float("nan")) for q in (50, 95, 99)}
+                          for k, v in per_run.items()}
+    return out

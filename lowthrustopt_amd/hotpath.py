@@ -1650,6 +1650,113 @@ def state_match(A, Bs, w=1.0, ctx=None):
     return StateMatch(index, dist, dr, dv)
 
 
+StationkeepGains = collections.namedtuple("StationkeepGains", "W G alpha status")
+StationkeepFlight = collections.namedtuple(
+    "StationkeepFlight", "x_final dv_total n_burn dev dv_hist dev_final accepted rejected status lost_at")
+
+
+def stationkeep_gains(V, sing_tol=1e-8, ctx=None):
+    """The Floquet-mode station-keeping gains from the hyperbolic directions of manifold_seeds (lto_stationkeep_gains_batch, DESIGN
+    4.29).  V [6 x 2 x P] or [6 x 2 x P x B], ManifoldSeeds.V as it is (index 0 the unstable unit vector, 1 the stable one).
+    Returns StationkeepGains(W [6 x P x B] = S v_s scaled so that W . v_u = 1, the left eigenvector of the monodromy matrix for
+    lambda_u; G [3 x 6 x P x B] = -w_v W^T / |w_v|^2, w_v = W[3:6]: dv = G dx is the smallest velocity change that zeroes the
+    unstable component of dx; alpha [P x B] = |w_v| / |W|; status [P x B]: 0, 2 a non-finite input, 3 alpha <= sing_tol or
+    |S v_s . v_u| <= sing_tol |S v_s| |v_u|; NaN outputs where status != 0) -- without the batch axis for [6 x 2 x P]."""
+    Vv = np.asarray(V, dtype=np.float64)
+    if Vv.ndim not in (3, 4) or Vv.shape[:2] != (6, 2) or Vv.size == 0:
+        raise ValueError("V must be [6 x 2 x P] or [6 x 2 x P x B]")
+    sing_tol = float(sing_tol)
+    if not (0.0 <= sing_tol < 1.0):
+        raise ValueError("sing_tol must lie in [0, 1)")
+    batched = Vv.ndim == 4
+    P = Vv.shape[2]
+    Vv = np.asfortranarray(Vv.reshape(6, 2, P, -1, order="F"))
+    B = Vv.shape[3]
+    ctx = ctx or default_context()
+    W = np.zeros((6, P, B), order="F")
+    G = np.zeros((3, 6, P, B), order="F")
+    alpha = np.zeros((P, B), order="F")
+    status = np.zeros((P, B), dtype=np.int32, order="F")
+    ctx.check(ctx.fn("stationkeep_gains_batch")(ctx.handle, P, B, _ptr(Vv), sing_tol, _ptr(W), _ptr(G), _ptr(alpha), _ptr(status)))
+    if not batched:
+        return StationkeepGains(W[..., 0], G[..., 0], alpha[:, 0], status[:, 0])
+    return StationkeepGains(W, G, alpha, status)
+
+
+def stationkeep_flight(X_ref, dt, G, x0, n_rev, nav=None, exe=None, dv_min=0.0, dv_max=0.0, r_lost=0.0, MU=MU, integ=None, ctx=None,
+                       history=True):
+    """Runs flown under an impulsive linear feedback about periodic orbits (lto_stationkeep_flight_batch), one lane per
+    run.  X_ref [6 x n_man], dt [n_man], G [3 x 6 x n_man] (one orbit for every run) or [6 x n_man x B], [n_man x B], [3 x 6 x n_man x
+    B] (one per run): the reference point, the gain and the ballistic span after burn j, every dt finite and > 0.  x0 [6] or [6 x
+    B]: the state at the first burn epoch.  nav [6 x n_upd (x B)] and exe [4 x n_upd (x B)] or None, n_upd = n_rev n_man: the
+    navigation error added to the measured deviation, and (scale error, bias [3]) of the executed burn.  At update u = r n_man + j:
+    d = x - X_ref_j; lost if r_lost > 0 and |d_r| > r_lost; c = G_j (d + nav_u); no burn if |c| < dv_min; |c| clipped to dv_max
+    (0: no limit); v += (1 + exe_0) c + exe_1:4; then the span dt_j.  Returns StationkeepFlight(x_final [6 x B], dv_total [B],
+    n_burn [B], dev [2 x n_upd x B] = (|d_r|, |d_v|) at every update, dv_hist [n_upd x B] the applied |dv| (0: skipped), dev_final
+    [2 x B] against X_ref_0 (a lost run: the deviation that lost it), accepted, rejected, status [B]: 0, 1 lost, 2 no finite
+    result; lost_at [B] the update of the loss or -1) -- without the batch axis for a single start.  history=False leaves dev and
+    dv_hist out (None): 24 n_upd bytes per run that a large Monte Carlo need not bring back."""
+    X = np.asarray(x0, dtype=np.float64)
+    if X.ndim not in (1, 2) or X.shape[0] != 6 or X.size == 0:
+        raise ValueError("x0 must be [6] or [6 x B]")
+    batched = X.ndim == 2
+    X = np.asfortranarray(X.reshape(6, -1))
+    B = X.shape[1]
+    Xr = np.asarray(X_ref, dtype=np.float64)
+    if Xr.ndim not in (2, 3) or Xr.shape[0] != 6 or Xr.size == 0:
+        raise ValueError("X_ref must be [6 x n_man] or [6 x n_man x n_orb]")
+    n_man = Xr.shape[1]
+    Xr = np.asfortranarray(Xr.reshape(6, n_man, -1, order="F"))
+    n_orb = Xr.shape[2]
+    if n_orb != 1 and n_orb != B:
+        raise ValueError("X_ref must hold one orbit or one per run")
+    T = np.asarray(dt, dtype=np.float64)
+    if T.size != n_man * n_orb or T.shape[0] != n_man:
+        raise ValueError("dt must be [n_man] or [n_man x n_orb]")
+    T = np.asfortranarray(T.reshape(n_man, n_orb, order="F"))
+    if not np.all(np.isfinite(T)) or np.any(T <= 0.0):
+        raise ValueError("every dt must be finite and > 0")
+    Gg = np.asarray(G, dtype=np.float64)
+    if Gg.size != 18 * n_man * n_orb or Gg.shape[:3] != (3, 6, n_man):
+        raise ValueError("G must be [3 x 6 x n_man] or [3 x 6 x n_man x n_orb]")
+    Gg = np.asfortranarray(Gg.reshape(3, 6, n_man, n_orb, order="F"))
+    n_rev = int(n_rev)
+    if n_rev < 1:
+        raise ValueError("n_rev must be >= 1")
+    n_upd = n_rev * n_man
+    errs = []
+    for name, arr, rows in (("nav", nav, 6), ("exe", exe, 4)):
+        if arr is None:
+            errs.append(None)
+            continue
+        E = np.asarray(arr, dtype=np.float64)
+        if E.ndim not in (2, 3) or E.shape[0] != rows or E.shape[1] != n_upd or E.size not in (rows * n_upd, rows * n_upd * B):
+            raise ValueError("%s must be [%d x n_upd] or [%d x n_upd x B] with n_upd = %d" % (name, rows, rows, n_upd))
+        E = E.reshape(rows, n_upd, -1, order="F")
+        errs.append(np.asfortranarray(np.broadcast_to(E, (rows, n_upd, B))))
+    dv_min, dv_max, r_lost = float(dv_min), float(dv_max), float(r_lost)
+    for name, v in (("dv_min", dv_min), ("dv_max", dv_max), ("r_lost", r_lost)):
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError("%s must be finite and >= 0" % name)
+    integ = _flight_integrator(integ)
+    ctx = ctx or default_context()
+    x_final = np.zeros((6, B), order="F")
+    dv_total = np.zeros(B)
+    dev = np.zeros((2, n_upd, B), order="F") if history else None
+    dv_hist = np.zeros((n_upd, B), order="F") if history else None
+    dev_final = np.zeros((2, B), order="F")
+    n_burn, acc, rej, status, lost_at = (np.zeros(B, dtype=np.int32) for _ in range(5))
+    ctx.check(ctx.fn("stationkeep_flight_batch")(ctx.handle, n_man, n_rev, B, float(MU), _ptr(Xr), _ptr(T), _ptr(Gg), n_orb, _ptr(X),
+                                                 _ptr(errs[0]), _ptr(errs[1]), dv_min, dv_max, r_lost, C.byref(integ), _ptr(x_final),
+                                                 _ptr(dv_total), _ptr(n_burn), _ptr(dev), _ptr(dv_hist), _ptr(dev_final), _ptr(acc),
+                                                 _ptr(rej), _ptr(status), _ptr(lost_at)))
+    if not batched:
+        return StationkeepFlight(x_final[:, 0], float(dv_total[0]), int(n_burn[0]), dev[:, :, 0] if history else None,
+                                 dv_hist[:, 0] if history else None, dev_final[:, 0],
+                                 int(acc[0]), int(rej[0]), int(status[0]), int(lost_at[0]))
+    return StationkeepFlight(x_final, dv_total, n_burn, dev, dv_hist, dev_final, acc, rej, status, lost_at)
+
+
 AddTime = collections.namedtuple("AddTime", "XC_guess XC_out t_out tau defect status iterations history cost")
 AddTimeMass = collections.namedtuple("AddTimeMass", AddTime._fields + ("propellant",))
 
