@@ -15,18 +15,19 @@
 // Four column waves do not fit three SIMDs evenly (a wavefront cannot be split and cannot move), so a phase is TWO RK4 steps (one
 // workgroup barrier per phase) and the columns of segments 12..15 are advanced by two wavefronts in turn:
 //
-//   wave  SIMD  role                                         instructions per phase (two steps), ND = 14
-//   w0    A     columns of segments 0..3,  both steps        680
-//   w4    A     columns of segments 12..15, EVEN step        340   -> hands the 14 doubles per lane to w5 through LDS
-//   w1    B     columns of segments 4..7,  both steps        680
-//   w5    B     columns of segments 12..15, ODD step         340   <- waits for w4's flag
-//   w2    C     base trajectory, both steps                  ~860 (paired stages; round 2: ~1100)
-//   w6    C     exits at once
-//   w3    D     coefficients of both steps                   ~360
-//   w7    D     columns of segments 8..11, both steps        680
+//   role                                             instructions per phase (two steps), ND = 14      wave, 14-dim   12-dim
+//   columns of segments 0..3,  both steps            608                                              w4 (A)         w4 (A)
+//   columns of segments 4..7,  both steps            608                                              w1 (B)         w1 (B)
+//   columns of segments 8..11, both steps            608                                              w7 (D)         w7 (D)
+//   columns of segments 12..15, EVEN step ("wE")     308   -> hands the 14 doubles per lane to wO     w5 (B)         w5 (B)
+//   columns of segments 12..15, ODD step  ("wO")     308   <- waits for wE's flag                     w3 (D)         w0 (A)
+//   base trajectory, both steps                      796 (paired stages)                              w2 (C)         w2 (C)
+//   coefficients of both steps                       356                                              w0 (A)         w3 (D)
+//   exits at once                                                                                     w6 (C)         w6 (C)
 //
-// (hardware places wave i and wave i + 4 of a workgroup on the same SIMD: tools/micro/sync_probe.hip).  w4 runs with
-// raised priority so that its step finishes early in the phase and w5 can follow.  A SIMD works through its wavefronts' streams
+// (hardware places wave i and wave i + 4 of a workgroup on the same SIMD: tools/micro/sync_probe.hip; which wave runs which role
+// is the table P8Place below, one map per ND).  wE runs with
+// raised priority so that its step finishes early in the phase and wO can follow.  A SIMD works through its wavefronts' streams
 // essentially one after the other at the issue rate of a lone wavefront (tools/micro/prio_probe.hip), so what bounds the sweep is
 // (sum of the workgroup's streams) / 4: DESIGN.md section 6.
 //
@@ -36,8 +37,8 @@
 // 2p - 2 (coefficients complete since the last barrier) and 2p - 1 (built during this phase: they wait for the coefficient
 // wave's counter, which by then is long set).  Both hand-overs are rings of four steps in LDS (91 KB in all: one
 // workgroup per CU); steps / 2 + 1 phases per sweep.  Waiting: a wave only ever waits (bounded poll of one LDS word) for a
-// wave that, in this phase, waits for nothing that depends on the waiter -- base: never; coefficients: base; w4: nothing;
-// columns: coefficients' first pass; w5: w4 -- so every wave reaches every barrier.  A poll that runs out (it cannot
+// wave that, in this phase, waits for nothing that depends on the waiter -- base: never; coefficients: base; wE: nothing;
+// columns: coefficients' first pass; wO: wE -- so every wave reaches every barrier.  A poll that runs out (it cannot
 // while the producer runs) raises a workgroup flag that turns the workgroup's outputs into NaN instead of hanging.
 //
 // Edges (probe build, tools/probe_pipe8_edges.py; ticks at the contract size, 14-dim): the fill phase is ~5 000 (base steps 0, 1;
@@ -56,11 +57,54 @@ namespace lto {
 
 constexpr int P8_SPIN_LIMIT = 1 << 22;   // polls before a waiting wave gives up (never hangs)
 
-// After the last phase barrier: the coefficient ring is dead and takes the Phi tile (pipe_common.hpp, pipe_store_phi).  Seven
-// waves are resident (w6 has left), the same seven the phase barriers count; they share the row stores in the order of their index.
+// ------------------------------------------------------------------------------------------------------------ placement
+// Which wave runs which role.  Hardware places wave i and wave i + 4 of a workgroup on the same SIMD, so the map decides which roles
+// share one; everything below that needs a wave number -- the dispatch, a column wave's segments, the exiting wave, the order of
+// the Phi row stores, the probe build's per-wave switches -- takes it from here.  One map per ND.
+enum P8Role : int { P8_BASE, P8_COEF, P8_COL0, P8_COL1, P8_COL2, P8_ALT_EVEN, P8_ALT_ODD, P8_EXIT, P8_NROLES };
+
+// A SIMD gives its OLDER wave (index < 4) the issue slots it asks for and the younger one what is left, and
+// LDS stores leave a CU over two half-paths, one for the even waves' SIMDs and one for the odd ones'.  So three things are decided
+// here besides which roles share a SIMD: which of the two is the older wave, which waves store on the base wave's half, and the
+// order of the Phi row stores.  Measured, not derived (Placement; profiles/r11_pipe8_placement.txt): the
+// coefficient wave must be an older wave (as a younger one the sweep is 9-12 us longer); the wave of the alternating job's even
+// step, which runs with raised priority, sits beside column job 1, and the odd step's wave is the older wave of its SIMD.
+//   role of wave 0..7, and the same read by SIMD: {older wave, younger wave} of A (w0, w4), B (w1, w5), C (w2, w6), D (w3, w7)
+template <int ND> struct P8Map;
+template <> struct P8Map<14> {    // coefficients beside column job 0, the odd step beside column job 2
+  static constexpr P8Role map[8] = {P8_COEF, P8_COL1, P8_BASE, P8_ALT_ODD, P8_COL0, P8_ALT_EVEN, P8_EXIT, P8_COL2};
+  static constexpr P8Role simd[4][2] = {{P8_COEF, P8_COL0}, {P8_COL1, P8_ALT_EVEN}, {P8_BASE, P8_EXIT}, {P8_ALT_ODD, P8_COL2}};
+};
+template <> struct P8Map<12> {    // the odd step beside column job 0, coefficients beside column job 2
+  static constexpr P8Role map[8] = {P8_ALT_ODD, P8_COL1, P8_BASE, P8_COEF, P8_COL0, P8_ALT_EVEN, P8_EXIT, P8_COL2};
+  static constexpr P8Role simd[4][2] = {{P8_ALT_ODD, P8_COL0}, {P8_COL1, P8_ALT_EVEN}, {P8_BASE, P8_EXIT}, {P8_COEF, P8_COL2}};
+};
+
+template <int ND> struct P8Place : P8Map<ND> {
+  using P8Map<ND>::map;
+  using P8Map<ND>::simd;
+  static constexpr int wave_of(const P8Role r) { for (int w = 0; w < 8; ++w) if (map[w] == r) return w; return -1; }
+  static constexpr int count(const P8Role r) { int n = 0; for (int w = 0; w < 8; ++w) n += (map[w] == r); return n; }
+  // Seven waves are resident after the exiting one has left, the same seven the phase barriers count; they share the row stores of
+  // Phi in the order of their index (pipe_common.hpp, pipe_store_phi)
+  static constexpr int rank_of(const int wave) { int n = 0; for (int w = 0; w < wave; ++w) n += (map[w] != P8_EXIT); return n; }
+  static constexpr int rank_of(const P8Role r) { return rank_of(wave_of(r)); }
+  static constexpr bool every_role_once() { for (int r = 0; r < P8_NROLES; ++r) if (count((P8Role)r) != 1) return false; return true; }
+  static constexpr bool simd_pairs_hold() { for (int i = 0; i < 4; ++i) if (map[i] != simd[i][0] || map[i + 4] != simd[i][1]) return false; return true; }
+  static constexpr unsigned ranks_seen() { unsigned m = 0; for (int w = 0; w < 8; ++w) if (map[w] != P8_EXIT) m |= 1u << rank_of(w); return m; }
+  static_assert(every_role_once(), "every role on exactly one wave: one base, one coefficient wave, exactly one wave exits");
+  static_assert(simd_pairs_hold(), "waves i and i + 4 share a SIMD: the map and its reading by SIMD disagree");
+  static_assert(ranks_seen() == 0x7Fu, "the store ranks of the resident waves are a permutation of 0..6");
+  static_assert((wave_of(P8_BASE) ^ wave_of(P8_EXIT)) == 4, "the base wave has its SIMD to itself: its partner is the wave that exits");
+};
+
+// After the last phase barrier: the coefficient ring is dead and takes the Phi tile (pipe_common.hpp, pipe_store_phi).
 constexpr int P8_STORE_WAVES = 7;
-constexpr int P8_BASE_RANK = 2, P8_COEF_RANK = 3;
-__device__ __forceinline__ int p8_store_rank(const int wave) { return wave < 6 ? wave : 6; }
+// rank of a plain column wave (its index is a run-time value: three waves share that role's code)
+template <int ND> __device__ __forceinline__ int p8_store_rank(const int wave) {
+  constexpr int X = P8Place<ND>::wave_of(P8_EXIT);
+  return wave < X ? wave : (X == 6) ? 6 : wave - 1;      // (above an exiting wave 6 there is only wave 7)
+}
 
 // Probe hooks (pipe_hooks.hpp: no-ops in the product build): ticks each wave waits at the phase barriers -> row 16 of the probe
 // script's defect buffer, column 16 block + wave.
@@ -98,7 +142,7 @@ typedef double p8_d2 __attribute__((ext_vector_type(2)));
 struct Pipe8Flags {
   int base_steps;    // steps whose stage arguments the base wave has published
   int coef_steps;    // steps whose coefficients are complete
-  int hand;          // phases in which w4 has handed its state to w5
+  int hand;          // phases in which wE has handed its state to wO
   int fail;          // a poll ran out
 };
 
@@ -197,7 +241,7 @@ __device__ __forceinline__ void pipe8_role_base(const IndirectArgs& a, const Pip
     if (a.nrej) a.nrej[L.s] = 0;
     if (seg == 0) loop_clock.report(a.defect, a.ldd, 17, 18, L.s);     // probe build: ticks of the phase loop, per workgroup
   }
-  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8_BASE_RANK);
+  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8Place<ND>::rank_of(P8_BASE));
   P8_EDGES_REPORT(a);
 }
 
@@ -394,7 +438,7 @@ __device__ __forceinline__ void pipe8_role_base_paired(const IndirectArgs& a, co
     if (a.nrej) a.nrej[L.s] = 0;
     if (seg == 0) loop_clock.report(a.defect, a.ldd, 17, 18, L.s);     // probe build: ticks of the step loop, per workgroup
   }
-  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8_BASE_RANK);
+  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8Place<ND>::rank_of(P8_BASE));
   P8_EDGES_REPORT(a);
 }
 
@@ -465,7 +509,7 @@ __device__ __forceinline__ void pipe8_role_coef(const IndirectArgs& a, const Pip
       a.defect[(ND - 1) * a.ldd + L.s] = fl->fail ? __builtin_nan("") : (a.X[r] + sum) - a.X[r + 1];
     }
   }
-  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8_COEF_RANK);
+  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8Place<ND>::rank_of(P8_COEF));
   P8_EDGES_REPORT(a);
 }
 
@@ -473,14 +517,14 @@ __device__ __forceinline__ void pipe8_role_coef(const IndirectArgs& a, const Pip
 // row does not integrate (col >= NA) are unit vectors.
 template <int ND, int NA, class Wait>
 __device__ __forceinline__ void pipe8_store_column(const IndirectArgs& a, const PipeLane& L, const int seg, const int col, const double (&y)[ND],
-                                                   const bool fail, double* s_coef, const int wave, Wait& w) {
+                                                   const bool fail, double* s_coef, const int rank, Wait& w) {
   const double sc = (col < NA) ? a.stm_scale : 1.0;
   const double poison = (col < NA) ? 0.0 : L.h - L.h;     // a unit column of a segment with a NaN (or infinite) span is NaN like the rest
   double v[ND];
 #pragma unroll
   for (int r = 0; r < ND; ++r) v[r] = fail ? __builtin_nan("") : __builtin_fma(y[r], sc, poison);
   w.stamp(0);
-  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, p8_store_rank(wave), true, L, seg, col, v);
+  pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, rank, true, L, seg, col, v);
   w.stamp(1);
   w.drained();
 }
@@ -497,7 +541,7 @@ __device__ __forceinline__ void pipe8_role_columns(const IndirectArgs& a, const 
   double y[ND];
 #pragma unroll
   for (int r = 0; r < ND; ++r) y[r] = (r == col) ? 1.0 : 0.0;
-  const bool role_on = PIPE_ROLE_ON(a, 4) && PIPE_ROLE_ON(a, wave == 7 ? 64 : 8);      // probe build: role switches per wave
+  const bool role_on = PIPE_ROLE_ON(a, 4) && PIPE_ROLE_ON(a, wave == P8Place<ND>::wave_of(P8_COL2) ? 64 : 8);      // probe build: role switches per wave
   P8_WAIT_DECL;
   P8_SYNC();                                                 // the fill phase
   // Full phases: ONE divergent region around both steps, y -> z -> y, straight line.  A join between the steps, or a step in
@@ -528,15 +572,15 @@ __device__ __forceinline__ void pipe8_role_columns(const IndirectArgs& a, const 
     P8_SYNC();
   }
   P8_WAIT_REPORT(a);
-  pipe8_store_column<ND, P::NA>(a, L, seg, col, y, fl->fail != 0, s_coef, wave, p8_wait);
+  pipe8_store_column<ND, P::NA>(a, L, seg, col, y, fl->fail != 0, s_coef, p8_store_rank<ND>(wave), p8_wait);
   P8_EDGES_REPORT(a);
 }
 
 // --------------------------------------------------------------- column role of the alternating job (segments 12..15)
-// ODD = false (w4): step 2p - 2 in phase p, then state -> s_hand, hand = p.  ODD = true (w5): waits for the coefficients
+// ODD = false (wE): step 2p - 2 in phase p, then state -> s_hand, hand = p.  ODD = true (wO): waits for the coefficients
 // of step 2p - 1 and for hand >= p, state <- s_hand, step 2p - 1, state -> s_hand.  The barrier at the end of the phase
-// orders w5's stores before w4's loads of the next phase.  After the last phase w4 takes the state from s_hand once more and puts
-// its columns into the Phi tile; w5 only joins the row stores.
+// orders wO's stores before wE's loads of the next phase.  After the last phase wE takes the state from s_hand once more and puts
+// its columns into the Phi tile; wO only joins the row stores.
 template <int ND, int PM, bool ODD>
 __device__ __forceinline__ void pipe8_role_columns_alt(const IndirectArgs& a, const PipeLane& L, const int seg, const int col,
                                                        double* s_coef, double* s_hand, Pipe8Flags* fl) {
@@ -563,7 +607,7 @@ __device__ __forceinline__ void pipe8_role_columns_alt(const IndirectArgs& a, co
 #pragma unroll
     for (int q = 0; q < ND / 2; ++q) hand2[q * 64 + lane] = p8_d2{v[2 * q], v[2 * q + 1]};
   };
-  // The column lives in s_hand between the steps -- w4 puts the unit vectors there before its first -- and in registers only
+  // The column lives in s_hand between the steps -- wE puts the unit vectors there before its first -- and in registers only
   // inside a step: loaded into one set, advanced into another, stored from there.  Nothing is carried round the phase loop, so
   // no register has to be handed back to where the next phase expects it.
   if (!ODD) {
@@ -600,10 +644,10 @@ __device__ __forceinline__ void pipe8_role_columns_alt(const IndirectArgs& a, co
   P8_WAIT_REPORT(a);
   if (!ODD) {
     if (on) load(y);
-    pipe8_store_column<ND, P::NA>(a, L, seg, col, y, fl->fail != 0, s_coef, 4, p8_wait);
+    pipe8_store_column<ND, P::NA>(a, L, seg, col, y, fl->fail != 0, s_coef, P8Place<ND>::rank_of(P8_ALT_EVEN), p8_wait);
   } else {
     p8_wait.stamp(0);
-    pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, p8_store_rank(5));
+    pipe_store_phi<ND, PIPE_SEG, P8_STORE_WAVES>(a, s_coef, P8Place<ND>::rank_of(P8_ALT_ODD));
     p8_wait.stamp(1);
     p8_wait.drained();
   }
@@ -621,22 +665,26 @@ __global__ __launch_bounds__(512) void k_indirect_pipe8(const IndirectArgs a) {
   __shared__ Pipe8Flags s_fl;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  // waves 0, 1, 7: column waves 0, 1, 2; waves 4, 5: the alternating column job 3; wave 2 base, wave 3 coefficients
-  const bool col_wave = (wave != 2 && wave != 3);
-  const int cw = (wave == 7) ? 2 : (wave >= 4) ? 3 : wave;
+  using Pl = P8Place<ND>;
+  constexpr int W_BASE = Pl::wave_of(P8_BASE), W_COEF = Pl::wave_of(P8_COEF), W_EXIT = Pl::wave_of(P8_EXIT);
+  constexpr int W_COL0 = Pl::wave_of(P8_COL0), W_COL1 = Pl::wave_of(P8_COL1), W_COL2 = Pl::wave_of(P8_COL2);
+  constexpr int W_EVEN = Pl::wave_of(P8_ALT_EVEN), W_ODD = Pl::wave_of(P8_ALT_ODD);
+  // column jobs 0, 1, 2: segments 0..3, 4..7, 8..11; job 3, segments 12..15, alternates between two waves
+  const bool col_wave = (wave != W_BASE && wave != W_COEF);
+  const int cw = (wave == W_COL2) ? 2 : (wave == W_COL0) ? 0 : (wave == W_COL1) ? 1 : 3;
   constexpr bool PAIRED = (ND == 12) || P::LM_OFF;   // base role with paired stages: a segment is a DPP quad of the base wave
-  const int seg = col_wave ? cw * 4 + (lane >> 4) : (PAIRED && wave == 2) ? (lane >> 2) : (lane & (PIPE_SEG - 1));
+  const int seg = col_wave ? cw * 4 + (lane >> 4) : (PAIRED && wave == W_BASE) ? (lane >> 2) : (lane & (PIPE_SEG - 1));
   const PipeLane L = pipe_lane<PM>(a, seg);
   if (threadIdx.x == 0) { s_fl.base_steps = 0; s_fl.coef_steps = 0; s_fl.hand = 0; s_fl.fail = 0; }
   if (!__syncthreads_or(L.mine)) return;         // workgroup-uniform
-  if (wave == 6) return;                         // shares the base wave's SIMD: leaves before the first phase barrier
-  if (wave == 2) {
+  if (wave == W_EXIT) return;                    // shares the base wave's SIMD: leaves before the first phase barrier
+  if (wave == W_BASE) {
     if constexpr (PAIRED) pipe8_role_base_paired<ND, PM>(a, L, seg, lane & 3, s_int, s_coef, &s_fl);
     else pipe8_role_base<ND, PM>(a, L, seg, lane >> 4, s_int, s_coef, &s_fl);
   }
-  else if (wave == 3) pipe8_role_coef<ND, PM>(a, L, seg, lane >> 4, s_int, s_coef, s_lm, &s_fl);
-  else if (wave == 4) pipe8_role_columns_alt<ND, PM, false>(a, L, seg, lane & 15, s_coef, s_hand, &s_fl);
-  else if (wave == 5) pipe8_role_columns_alt<ND, PM, true>(a, L, seg, lane & 15, s_coef, s_hand, &s_fl);
+  else if (wave == W_COEF) pipe8_role_coef<ND, PM>(a, L, seg, lane >> 4, s_int, s_coef, s_lm, &s_fl);
+  else if (wave == W_EVEN) pipe8_role_columns_alt<ND, PM, false>(a, L, seg, lane & 15, s_coef, s_hand, &s_fl);
+  else if (wave == W_ODD) pipe8_role_columns_alt<ND, PM, true>(a, L, seg, lane & 15, s_coef, s_hand, &s_fl);
   else pipe8_role_columns<ND, PM>(a, L, seg, lane & 15, s_coef, &s_fl, wave);
 }
 

@@ -15,7 +15,10 @@ import lowthrustopt_amd as lto
 from lowthrustopt_amd import synth
 from probe_kernels import timeit
 
-ROLES = ["cols 0-3", "cols 4-7", "base", "coef", "cols 12-15 even", "cols 12-15 odd", "(w6)", "cols 8-11"]
+# role of wave 0..7 per dimension: the placement table of kernels_indirect_pipe8.hip (P8Map<ND>::map), kept in step by hand
+COL0, COL1, COL2, BASE, COEF, EVEN, ODD, EXIT = "cols 0-3", "cols 4-7", "cols 8-11", "base", "coef", "cols 12-15 even", "cols 12-15 odd", "(exits)"
+PLACEMENT = {14: [COEF, COL1, BASE, ODD, COL0, EVEN, EXIT, COL2],
+             12: [ODD, COL1, BASE, COEF, COL0, EVEN, EXIT, COL2]}
 
 
 def main():
@@ -46,7 +49,7 @@ def main():
         print("  %-2s %-16s %8s %8s %8s %8s %6s %8s %8s %8s" % ("w", "role", "fill", "waited", "drain", "epilog", "syncs", "first", "issued", "drained"))
         for w in range(8):
             col = lambda r: np.median(dh[r].reshape(-1, 16)[:, w])
-            print("  w%d %-16s %8.0f %8.0f %8.0f %8.0f %6.0f %8.0f %8.0f %8.0f" % (w, ROLES[w], col(20), col(16), col(21), col(22), col(23), col(24), col(25), col(26)))
+            print("  w%d %-16s %8.0f %8.0f %8.0f %8.0f %6.0f %8.0f %8.0f %8.0f" % (w, PLACEMENT[ndim][w], col(20), col(16), col(21), col(22), col(23), col(24), col(25), col(26)))
         plan.close()
 
 
