@@ -2,7 +2,7 @@
 // what the section flights (kernels_manifold.hip) and the station-keeping flights (kernels_stationkeep.hip, DESIGN
 // 4.29) both fly.
 #pragma once
-#include "indirect_kernel.hpp"
+#include "dop853_lane.hpp"
 
 namespace lto {
 

@@ -3,7 +3,7 @@
 // bisection that locates the return to y = 0.  gfx950 device code.
 #pragma once
 #include "kernels.hpp"
-#include "dop853_group.hpp"
+#include "dop853_lane.hpp"
 
 namespace lto {
 

@@ -13,7 +13,7 @@
 #pragma once
 #include <type_traits>
 #include "kernels.hpp"
-#include "rk.hpp"
+#include "dop853_lane.hpp"
 
 namespace lto {
 
@@ -99,9 +99,11 @@ struct SysEventsMass {
   }
 };
 
-// x^(-1/8) and x^(1/9) without pow()
-__device__ __forceinline__ double pow_m8th(double x) { return 1.0 / sqrt(sqrt(sqrt(x))); }
-__device__ __forceinline__ double pow_9th(double x) { return cbrt(cbrt(x)); }
+// The augmented system of an ND-row solution: what the thrust events and the guided flight integrate.
+template <int ND, int PM>
+struct AugmentedSys { using type = SysEvents<PM>; };
+template <int PM>
+struct AugmentedSys<14, PM> { using type = SysEventsMass<PM>; };
 
 // ode78 (GeneralCode/ode.jl:479-534): h0 = span/50, hmax = span/2.5, hmin = span/1e7; accept when
 // delta <= tau = tol max(|x|_inf, 1); h <- min(hmax, 0.8 h (tau/delta)^(1/8)).  Error and |x|_inf run
@@ -142,170 +144,6 @@ __device__ __forceinline__ void run_rkf78_adaptive(const Sys& sys, const double 
   // not at t1 (max_steps used up, ode78's step-size floor ode.jl:479,524, or a decreasing grid: forward integration
   // only): no result -- NaN, never a state at some t < t1 that looks propagated
   if (t < span || !(span >= 0.0)) {           // a NaN span counts as a negative one
-#pragma unroll
-    for (int i = 0; i < D; ++i) y[i] = __builtin_nan("");
-  }
-}
-
-// Adaptive DOP853 (DESIGN.md 'Integrators'): initial step by Hairer's d0/d1/d2 rule, accept if err < 1, factor = min(10, 0.9 err^(-1/8)) (<= 1 after a rejection),
-// rejection factor max(0.2, 0.9 err^(-1/8)).
-template <class Sys, int NERR>
-__device__ __forceinline__ void run_dop853(const Sys& sys, const double span, const double rtol, const double atol,
-                                           const int max_steps, double (&y)[Sys::DIM], int& nacc, int& nrej) {
-  constexpr int D = Sys::DIM;
-  double K[13][D];
-  nacc = 0; nrej = 0;
-  if (!(span > 0.0)) {
-    if (span != 0.0) {     // decreasing grid (forward integration only) or NaN span: no result
-#pragma unroll
-      for (int i = 0; i < D; ++i) y[i] = __builtin_nan("");
-    }
-    return;
-  }
-  sys.rhs(y, K[0]);
-  double h_abs;
-  {
-    double d0 = 0.0, d1 = 0.0;
-#pragma unroll
-    for (int i = 0; i < NERR; ++i) {
-      const double isc = rcp_nr(__builtin_fma(rtol, fabs(y[i]), atol));
-      d0 = __builtin_fma(y[i] * isc, y[i] * isc, d0);
-      d1 = __builtin_fma(K[0][i] * isc, K[0][i] * isc, d1);
-    }
-    d0 = sqrt(d0 / NERR); d1 = sqrt(d1 / NERR);
-    const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    double yt[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) yt[i] = __builtin_fma(h0, K[0][i], y[i]);
-    sys.rhs(yt, K[1]);
-    double d2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < NERR; ++i) {
-      const double isc = rcp_nr(__builtin_fma(rtol, fabs(y[i]), atol));
-      const double df = (K[1][i] - K[0][i]) * isc;
-      d2 = __builtin_fma(df, df, d2);
-    }
-    d2 = sqrt(d2 / NERR) / h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow_9th(0.01 / fmax(d1, d2));
-    h_abs = fmin(fmin(100.0 * h0, h1), span);
-  }
-  double t = 0.0;
-  // Flags are kept as per-lane doubles, not bools: hipcc 7.2 turns per-lane booleans that stay live across these
-  // spill-heavy bodies into SGPR lane masks that are spilled/reloaded, and a 14-dim kernel returned garbage that
-  // way (DESIGN.md "Compiler hazards").
-  double rejected = 0.0;
-  while (t < span && nacc + nrej < max_steps) {
-    double h = h_abs;
-    double last = 0.0;
-    if (t + h >= span) { h = span - t; last = 1.0; }
-    double yn[D];
-    double E5, E3;
-    (void)dop853_try<Sys, NERR>(sys, h, rtol, atol, y, K, yn, E5, E3);
-    // the step decision every DOP853 kernel of this library takes (rk.hpp dp8_decide): the one- / two- / four-lane defect sweeps
-    // AUTO switches between share one controller (advisor finding, round 4)
-    double h_next, accept, bad;
-    dp8_decide(E5, E3, h, rejected, (double)NERR, h_next, accept, bad);
-    h_abs = h_next;
-    if (accept != 0.0) {
-      t = (last != 0.0) ? span : t + h;
-#pragma unroll
-      for (int i = 0; i < D; ++i) { y[i] = yn[i]; K[0][i] = K[12][i]; }
-      ++nacc;
-      rejected = 0.0;
-    } else {
-      rejected = 1.0;
-      ++nrej;
-      if (bad != 0.0) {                       // a NaN never recovers: poison and stop instead of max_steps retries
-#pragma unroll
-        for (int i = 0; i < D; ++i) y[i] = bad;
-        t = span;
-      }
-    }
-  }
-  if (t < span) {                             // max_steps trial steps used up before t1: no result
-#pragma unroll
-    for (int i = 0; i < D; ++i) y[i] = __builtin_nan("");
-  }
-}
-
-// The stepping form of run_dop853 (kernels_events.hip): the same start (Hairer's d0/d1/d2 rule), the same trial step and the same
-// decision (dop853_try, dp8_decide), and after every ACCEPTED step
-//   hook(t, h, y, K, yn)     y = the state at t (relative to the segment's start), K[0] = f(y), yn = the state at t + h
-// before the step is taken over.  The hook may run further trial steps from y through K (dop853_try leaves y and K[0] alone and
-// overwrites K[1..12]); the new state's slope is kept aside for it.  run_dop853 itself is untouched: its kernels keep their code.
-template <class Sys, int NERR, class Hook>
-__device__ __forceinline__ void run_dop853_stepping(const Sys& sys, const double span, const double rtol, const double atol,
-                                                    const int max_steps, double (&y)[Sys::DIM], int& nacc, int& nrej, Hook&& hook) {
-  constexpr int D = Sys::DIM;
-  double K[13][D];
-  nacc = 0; nrej = 0;
-  if (!(span > 0.0)) {
-    if (span != 0.0) {
-#pragma unroll
-      for (int i = 0; i < D; ++i) y[i] = __builtin_nan("");
-    }
-    return;
-  }
-  sys.rhs(y, K[0]);
-  double h_abs;
-  {
-    double d0 = 0.0, d1 = 0.0;
-#pragma unroll
-    for (int i = 0; i < NERR; ++i) {
-      const double isc = rcp_nr(__builtin_fma(rtol, fabs(y[i]), atol));
-      d0 = __builtin_fma(y[i] * isc, y[i] * isc, d0);
-      d1 = __builtin_fma(K[0][i] * isc, K[0][i] * isc, d1);
-    }
-    d0 = sqrt(d0 / NERR); d1 = sqrt(d1 / NERR);
-    const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    double yt[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) yt[i] = __builtin_fma(h0, K[0][i], y[i]);
-    sys.rhs(yt, K[1]);
-    double d2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < NERR; ++i) {
-      const double isc = rcp_nr(__builtin_fma(rtol, fabs(y[i]), atol));
-      const double df = (K[1][i] - K[0][i]) * isc;
-      d2 = __builtin_fma(df, df, d2);
-    }
-    d2 = sqrt(d2 / NERR) / h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow_9th(0.01 / fmax(d1, d2));
-    h_abs = fmin(fmin(100.0 * h0, h1), span);
-  }
-  double t = 0.0;
-  double rejected = 0.0;                        // per-lane flags as doubles (run_dop853, DESIGN.md "Compiler hazards")
-  while (t < span && nacc + nrej < max_steps) {
-    double h = h_abs;
-    double last = 0.0;
-    if (t + h >= span) { h = span - t; last = 1.0; }
-    double yn[D];
-    double E5, E3;
-    (void)dop853_try<Sys, NERR>(sys, h, rtol, atol, y, K, yn, E5, E3);
-    double h_next, accept, bad;
-    dp8_decide(E5, E3, h, rejected, (double)NERR, h_next, accept, bad);
-    h_abs = h_next;
-    if (accept != 0.0) {
-      double fn[D];
-#pragma unroll
-      for (int i = 0; i < D; ++i) fn[i] = K[12][i];
-      hook(t, h, y, K, yn);
-      t = (last != 0.0) ? span : t + h;
-#pragma unroll
-      for (int i = 0; i < D; ++i) { y[i] = yn[i]; K[0][i] = fn[i]; }
-      ++nacc;
-      rejected = 0.0;
-    } else {
-      rejected = 1.0;
-      ++nrej;
-      if (bad != 0.0) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) y[i] = bad;
-        t = span;
-      }
-    }
-  }
-  if (t < span) {
 #pragma unroll
     for (int i = 0; i < D; ++i) y[i] = __builtin_nan("");
   }

@@ -132,9 +132,8 @@ struct EventsArgs {
 inline size_t events_record_bytes(long S, int ndim = 12) {
   return ((sizeof(double) * (kEventsPerSeg + 2 + (ndim == 14 ? 1 : 0)) + sizeof(int) * 3) * (size_t)S + 255) & ~(size_t)255;
 }
-// M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue.  12-dim; _mass: 14-dim (X [14][ldx], e.dm and e.propellant set)
-hipError_t launch_indirect_events(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st);
-hipError_t launch_indirect_events_mass(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st);
+// M_RK4 or M_DOP853_ADAPTIVE, nd = 12 or 14 (X [14][ldx], e.dm and e.propellant set); anything else: hipErrorInvalidValue
+hipError_t launch_indirect_events(int nd, int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st);
 hipError_t launch_events_compact(const IndirectArgs& a, const EventsArgs& e, int n_batch, hipStream_t st);
 // Control replay (kernels_replay.hip).  The moment kernel: lamv [n_hist][n_knots][3] as the caller passes it, cp [n_knots]
 // the Thomas factors of the (1, 4, 1) system, mom [n_knots][3 n_hist] scratch; vm [n_knots][6][n_hist] = per knot and component the

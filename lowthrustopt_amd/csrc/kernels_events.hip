@@ -14,12 +14,13 @@
 // t_{i+1}), an ordered gather into the trajectory's list, dv and burn_time as lane-strided partial sums closed by a butterfly.  No
 // atomics: a trajectory's result does not depend on its batch.
 //
-// k_indirect_events_mass: the same lane for the 14-row variable-mass system, (y[14], q) with q' = umag as rhs14_base
+// k_indirect_events<14>: the same lane for the 14-row variable-mass system, (y[14], q) with q' = umag as rhs14_base
 // forms it, DOP853 with all 15 components in the error norm.  The threshold of p > 1 is formed from the state's CURRENT mass, and the
 // lane leaves dm = m_i - m(t_{i+1}) with its records; k_events_compact sums it into `propellant` in the order of dv.
 #include <hip/hip_runtime.h>
 
 #include "indirect_kernel.hpp"
+#include "wave_reduce.hpp"
 
 namespace lto {
 
@@ -35,7 +36,7 @@ __device__ __forceinline__ double event_threshold(const TrajParams& tp) {
   if (PM == PM_PGEN) return tp.p * pow(tp.accel_limit, tp.p - 1.0);
   return 0.0;
 }
-// the engine is on iff g > 0 (g == 0, and a NaN, are off); p = 0: always on.  A double, not a bool (run_dop853's comment).
+// the engine is on iff g > 0 (g == 0, and a NaN, are off); p = 0: always on.  A double, not a bool (dop853_lane.hpp).
 template <int PM>
 __device__ __forceinline__ double on_state(const double (&y)[13], const double thr) {
   if (PM == PM_P0) return 1.0;
@@ -82,82 +83,6 @@ __device__ __forceinline__ double locate_crossing(const double t0, const double 
   return t_hi;
 }
 
-template <int PM, int METHOD>
-__global__ __launch_bounds__(64) void k_indirect_events(const IndirectArgs a, const EventsArgs ev) {
-  const int s = blockIdx.x * 64 + threadIdx.x;
-  if (s >= a.S) return;
-  const int traj = s / a.seg_per_traj;
-  const int i = s - traj * a.seg_per_traj;
-  const long node = (long)traj * a.n_nodes + i;
-  const long tg = (long)traj * a.t_stride + i;
-  using Sys = SysEvents<PM>;
-  Sys sys;
-  sys.tp = a.tp[(long)traj * a.tp_stride];
-  if (a.class_filter && p_class(sys.tp.p) != PM) return;
-  const double thr = event_threshold<PM>(sys.tp);
-  const auto on_of = [&](const double (&yt)[13]) { return on_state<PM>(yt, thr); };
-  double y[13];
-  double next_sum = 0.0;                          // node i + 1 only has to be finite
-#pragma unroll
-  for (int c = 0; c < 12; ++c) { y[c] = a.X[c * a.ldx + node]; next_sum += a.X[c * a.ldx + node + 1]; }
-  y[12] = 0.0;
-  const double ta = a.t[tg], tb = a.t[tg + 1];
-  const double span = tb - ta;
-  SegEvents se;
-  se.on = on_state<PM>(y, thr);
-  se.tmark = ta; se.ont = 0.0; se.nev = 0;
-  se.e0 = se.e1 = se.e2 = se.e3 = __builtin_nan("");
-  const double on_start = se.on;
-
-  if (METHOD == M_RK4) {
-    const double h = span / (double)a.steps;
-    for (int k = 0; k < a.steps; ++k) {
-      double y0[13];
-#pragma unroll
-      for (int c = 0; c < 13; ++c) y0[c] = y[c];
-      rk4_step(sys, h, y);
-      if (PM != PM_P0) {
-        const double on1 = on_state<PM>(y, thr);
-        if (on1 != se.on) {
-          const double tev = locate_crossing<13>(__builtin_fma((double)k, h, ta), h, se.on, on_of, [&](const double th, double (&yt)[13]) {
-#pragma unroll
-            for (int c = 0; c < 13; ++c) yt[c] = y0[c];
-            rk4_step(sys, th, yt);
-          });
-          se.crossing(tev, on1);
-        }
-      }
-    }
-  } else {
-    int nacc = 0, nrej = 0;
-    run_dop853_stepping<Sys, 13>(sys, span, a.rtol, a.atol, a.max_steps, y, nacc, nrej,
-                                 [&](const double t, const double h, const double (&y0)[13], double (&K)[13][13], const double (&yn)[13]) {
-      if (PM == PM_P0) return;
-      const double on1 = on_state<PM>(yn, thr);
-      if (on1 != se.on) {
-        const double tev = locate_crossing<13>(ta + t, h, se.on, on_of, [&](const double th, double (&yt)[13]) {
-          double E5, E3;
-          (void)dop853_try<Sys, 13>(sys, th, a.rtol, a.atol, y0, K, yt, E5, E3);
-        });
-        se.crossing(tev, on1);
-      }
-    });
-  }
-  if (se.on != 0.0) se.ont += tb - se.tmark;
-  double fin = next_sum;
-#pragma unroll
-  for (int c = 0; c < 13; ++c) fin += y[c];
-  fin += se.ont;
-  const bool finite = (fin - fin) == 0.0;
-  const long S = a.S;
-  ev.tev[0 * S + s] = se.e0; ev.tev[1 * S + s] = se.e1; ev.tev[2 * S + s] = se.e2; ev.tev[3 * S + s] = se.e3;
-  ev.q[s] = finite ? y[12] : __builtin_nan("");
-  ev.ont[s] = finite ? se.ont : __builtin_nan("");
-  ev.nev[s] = se.nev;
-  ev.on_s[s] = (on_start != 0.0) ? 1 : 0;
-  ev.on_e[s] = (se.on != 0.0) ? 1 : 0;
-}
-
 // ---------------------------------------------------------------------------------------- the variable-mass system
 // The lane carries the mass as m_i + y[6], y[6](t_i) = 0: a segment burns 1e-5 .. 1e-2 of the mass, and a propagated m near
 // 1000 kg is rounded to eps m = 1.1e-13 kg in every step, so m_i - m(t_{i+1}) formed from it is good to eps m / dm only (measured:
@@ -180,26 +105,33 @@ __device__ __forceinline__ double on_state_mass(const double (&y)[15], const Tra
   return (n - thr > 0.0) ? 1.0 : 0.0;
 }
 
-template <int PM, int METHOD>
-__global__ __launch_bounds__(64) void k_indirect_events_mass(const IndirectArgs a, const EventsArgs ev) {
+// ND = 12: (y[12], q) under SysEvents.  ND = 14: (y[14], q) under SysEventsMass, the on-state from the current mass, and dm.
+template <int ND, int PM, int METHOD>
+__global__ __launch_bounds__(64) void k_indirect_events(const IndirectArgs a, const EventsArgs ev) {
+  constexpr int D = ND + 1;
   const int s = blockIdx.x * 64 + threadIdx.x;
   if (s >= a.S) return;
   const int traj = s / a.seg_per_traj;
   const int i = s - traj * a.seg_per_traj;
   const long node = (long)traj * a.n_nodes + i;
   const long tg = (long)traj * a.t_stride + i;
-  using Sys = SysEventsMass<PM>;
+  using Sys = typename AugmentedSys<ND, PM>::type;
+  static_assert(Sys::DIM == D, "state, costate and the quadrature of umag");
   Sys sys;
   sys.tp = a.tp[(long)traj * a.tp_stride];
   if (a.class_filter && p_class(sys.tp.p) != PM) return;
-  const auto on_of = [&](const double (&yt)[15]) { return on_state_mass<PM>(yt, sys.tp, sys.m_i); };
-  double y[15];
+  double thr = 0.0;
+  if constexpr (ND == 12) thr = event_threshold<PM>(sys.tp);
+  const auto on_of = [&](const double (&yt)[D]) {
+    if constexpr (ND == 12) return on_state<PM>(yt, thr);
+    else return on_state_mass<PM>(yt, sys.tp, sys.m_i);
+  };
+  double y[D];
   double next_sum = 0.0;                          // node i + 1 only has to be finite (and its mass positive, below)
 #pragma unroll
-  for (int c = 0; c < 14; ++c) { y[c] = a.X[c * a.ldx + node]; next_sum += a.X[c * a.ldx + node + 1]; }
-  y[14] = 0.0;
-  sys.m_i = y[6];
-  y[6] = 0.0;
+  for (int c = 0; c < ND; ++c) { y[c] = a.X[c * a.ldx + node]; next_sum += a.X[c * a.ldx + node + 1]; }
+  y[ND] = 0.0;
+  if constexpr (ND == 14) { sys.m_i = y[6]; y[6] = 0.0; }
   const double ta = a.t[tg], tb = a.t[tg + 1];
   const double span = tb - ta;
   SegEvents se;
@@ -211,16 +143,16 @@ __global__ __launch_bounds__(64) void k_indirect_events_mass(const IndirectArgs 
   if (METHOD == M_RK4) {
     const double h = span / (double)a.steps;
     for (int k = 0; k < a.steps; ++k) {
-      double y0[15];
+      double y0[D];
 #pragma unroll
-      for (int c = 0; c < 15; ++c) y0[c] = y[c];
+      for (int c = 0; c < D; ++c) y0[c] = y[c];
       rk4_step(sys, h, y);
       if (PM != PM_P0) {
         const double on1 = on_of(y);
         if (on1 != se.on) {
-          const double tev = locate_crossing<15>(__builtin_fma((double)k, h, ta), h, se.on, on_of, [&](const double th, double (&yt)[15]) {
+          const double tev = locate_crossing<D>(__builtin_fma((double)k, h, ta), h, se.on, on_of, [&](const double th, double (&yt)[D]) {
 #pragma unroll
-            for (int c = 0; c < 15; ++c) yt[c] = y0[c];
+            for (int c = 0; c < D; ++c) yt[c] = y0[c];
             rk4_step(sys, th, yt);
           });
           se.crossing(tev, on1);
@@ -229,55 +161,44 @@ __global__ __launch_bounds__(64) void k_indirect_events_mass(const IndirectArgs 
     }
   } else {
     int nacc = 0, nrej = 0;
-    run_dop853_stepping<Sys, 15>(sys, span, a.rtol, a.atol, a.max_steps, y, nacc, nrej,
-                                 [&](const double t, const double h, const double (&y0)[15], double (&K)[13][15], const double (&yn)[15]) {
-      if (PM == PM_P0) return;
+    run_dop853_stop<Sys, D>(sys, span, a.rtol, a.atol, a.max_steps, y, nacc, nrej,
+                            [&](const double t, const double h, const double (&y0)[D], double (&K)[13][D], const double (&yn)[D]) {
+      if (PM == PM_P0) return 0.0;
       const double on1 = on_of(yn);
       if (on1 != se.on) {
-        const double tev = locate_crossing<15>(ta + t, h, se.on, on_of, [&](const double th, double (&yt)[15]) {
+        const double tev = locate_crossing<D>(ta + t, h, se.on, on_of, [&](const double th, double (&yt)[D]) {
           double E5, E3;
-          (void)dop853_try<Sys, 15>(sys, th, a.rtol, a.atol, y0, K, yt, E5, E3);
+          (void)dop853_try<Sys, D>(sys, th, a.rtol, a.atol, y0, K, yt, E5, E3);
         });
         se.crossing(tev, on1);
       }
+      return 0.0;
     });
   }
   if (se.on != 0.0) se.ont += tb - se.tmark;
   double fin = next_sum;
 #pragma unroll
-  for (int c = 0; c < 15; ++c) fin += y[c];
+  for (int c = 0; c < D; ++c) fin += y[c];
   fin += se.ont;
-  // the masses of the segment's two nodes, read again here instead of a flag kept across the integration: finite and positive
-  // (a NaN fails the comparison, an infinity the finite sum)
-  const double m_i = a.X[6 * a.ldx + node], m_n = a.X[6 * a.ldx + node + 1];
-  const bool finite = ((fin + m_i) - (fin + m_i)) == 0.0 && m_i > 0.0 && m_n > 0.0;
+  bool finite;
+  double dm = 0.0;
+  if constexpr (ND == 14) {
+    // the masses of the segment's two nodes, read again here instead of a flag kept across the integration: finite and positive
+    // (a NaN fails the comparison, an infinity the finite sum)
+    const double m_i = a.X[6 * a.ldx + node], m_n = a.X[6 * a.ldx + node + 1];
+    finite = ((fin + m_i) - (fin + m_i)) == 0.0 && m_i > 0.0 && m_n > 0.0;
+    dm = (m_i + y[6] == m_i) ? 0.0 : -y[6];
+  } else {
+    finite = (fin - fin) == 0.0;
+  }
   const long S = a.S;
   ev.tev[0 * S + s] = se.e0; ev.tev[1 * S + s] = se.e1; ev.tev[2 * S + s] = se.e2; ev.tev[3 * S + s] = se.e3;
-  ev.q[s] = finite ? y[14] : __builtin_nan("");
+  ev.q[s] = finite ? y[ND] : __builtin_nan("");
   ev.ont[s] = finite ? se.ont : __builtin_nan("");
-  ev.dm[s] = finite ? ((m_i + y[6] == m_i) ? 0.0 : -y[6]) : __builtin_nan("");
+  if constexpr (ND == 14) ev.dm[s] = finite ? dm : __builtin_nan("");
   ev.nev[s] = se.nev;
   ev.on_s[s] = (on_start != 0.0) ? 1 : 0;
   ev.on_e[s] = (se.on != 0.0) ? 1 : 0;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) { const int u = __shfl_xor(v, off, 64); v = u < v ? u : v; }
-  return v;
-}
-__device__ __forceinline__ int wave_scan_incl(int v, const int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int u = __shfl_up(v, off, 64);
-    if (lane >= off) v += u;
-  }
-  return v;
 }
 
 __global__ __launch_bounds__(64) void k_events_compact(const IndirectArgs a, const EventsArgs ev, const int n_batch) {
@@ -341,39 +262,29 @@ __global__ __launch_bounds__(64) void k_events_compact(const IndirectArgs a, con
   }
 }
 
-template <int METHOD>
+template <int ND, int METHOD>
 hipError_t launch_events_pm(int pm, const IndirectArgs& a0, const EventsArgs& e, hipStream_t st) {
   dim3 grid((a0.S + 63) / 64);
   // every class is launched and the error state read once, behind the last launch (as launch_dense_pm)
   (void)for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) {
-    hipLaunchKernelGGL((k_indirect_events<decltype(cls)::value, METHOD>), grid, dim3(64), 0, st, a, e);
+    hipLaunchKernelGGL((k_indirect_events<ND, decltype(cls)::value, METHOD>), grid, dim3(64), 0, st, a, e);
     return hipSuccess;
   });
   return hipGetLastError();
 }
 
-template <int METHOD>
-hipError_t launch_events_mass_pm(int pm, const IndirectArgs& a0, const EventsArgs& e, hipStream_t st) {
-  dim3 grid((a0.S + 63) / 64);
-  (void)for_classes<PM_P0, PM_P1, PM_P2, PM_PGEN>(pm, a0, [&](auto cls, const IndirectArgs& a) {
-    hipLaunchKernelGGL((k_indirect_events_mass<decltype(cls)::value, METHOD>), grid, dim3(64), 0, st, a, e);
-    return hipSuccess;
-  });
-  return hipGetLastError();
+template <int ND>
+hipError_t launch_events_nd(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st) {
+  if (method == M_RK4) return launch_events_pm<ND, M_RK4>(pm, a, e, st);
+  if (method == M_DOP853_ADAPTIVE) return launch_events_pm<ND, M_DOP853_ADAPTIVE>(pm, a, e, st);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-hipError_t launch_indirect_events(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st) {
-  if (method == M_RK4) return launch_events_pm<M_RK4>(pm, a, e, st);
-  if (method == M_DOP853_ADAPTIVE) return launch_events_pm<M_DOP853_ADAPTIVE>(pm, a, e, st);
-  return hipErrorInvalidValue;
-}
-
-hipError_t launch_indirect_events_mass(int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st) {
-  if (!e.dm || !e.propellant) return hipErrorInvalidValue;
-  if (method == M_RK4) return launch_events_mass_pm<M_RK4>(pm, a, e, st);
-  if (method == M_DOP853_ADAPTIVE) return launch_events_mass_pm<M_DOP853_ADAPTIVE>(pm, a, e, st);
+hipError_t launch_indirect_events(int nd, int pm, int method, const IndirectArgs& a, const EventsArgs& e, hipStream_t st) {
+  if (nd == 12) return launch_events_nd<12>(pm, method, a, e, st);
+  if (nd == 14 && e.dm && e.propellant) return launch_events_nd<14>(pm, method, a, e, st);
   return hipErrorInvalidValue;
 }
 

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "indirect_kernel.hpp"
+#include "wave_reduce.hpp"
 
 namespace lto {
 
@@ -42,17 +43,6 @@ __global__ __launch_bounds__(256) void k_lanes_to_rows(const double* soa, const 
   if (i >= rows * count) return;
   const long row = i / count, j = i - row * count;
   aos[row + rows * j] = soa[i];
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 template <int NX>
@@ -147,18 +137,13 @@ __global__ __launch_bounds__(64) void k_guidance_gains(const GainsArgs g) {
   if (e == 0) g.status[b] = (int)dead;
 }
 
-template <int NX, int PM>
-struct GuidedSys { using type = SysEvents<PM>; };
-template <int PM>
-struct GuidedSys<7, PM> { using type = SysEventsMass<PM>; };
-
 template <int NX, int PM, int METHOD>
 __global__ __launch_bounds__(64) void k_guided_flight(const IndirectArgs a, const GuidedArgs g) {
   constexpr int ND = 2 * NX, NE = NX * NX, DIM = ND + 1;
   const int b = blockIdx.x * 64 + threadIdx.x;
   const int B = g.n_batch;
   if (b >= B) return;
-  using Sys = typename GuidedSys<NX, PM>::type;
+  using Sys = typename AugmentedSys<ND, PM>::type;
   static_assert(Sys::DIM == DIM, "state, costate and the quadrature of umag");
   Sys sys;
   sys.tp = a.tp[(long)b * a.tp_stride];
@@ -175,7 +160,7 @@ __global__ __launch_bounds__(64) void k_guided_flight(const IndirectArgs a, cons
 #pragma unroll
   for (int c = 0; c < NX; ++c) y[NX + c] = nom[(long)(NX + c) * nn];
   y[ND] = 0.0;
-  // per-lane flags are doubles (run_dop853's comment, DESIGN.md "Compiler hazards")
+  // per-lane flags are doubles (dop853_lane.hpp, DESIGN.md "Compiler hazards")
   double failed = 0.0;
   int nacc = 0, nrej = 0;
   double dv = 0.0;

@@ -1,7 +1,7 @@
 // kernels_halo.hip -- periodic orbits of the CRTBP with the xz-plane symmetry (halo, planar Lyapunov), B orbits side by side
 // (DESIGN 4.25), gfx950.
 //
-// One GROUP of 8 adjacent lanes per orbit, 8 orbits per wavefront (dop853_group.hpp).  Lane c < 6 of a group integrates the ballistic
+// One GROUP of 8 adjacent lanes per orbit, 8 orbits per wavefront (dop853_lane.hpp).  Lane c < 6 of a group integrates the ballistic
 // base state with column c of Phi = dx/dx0 -- 12 components, the gravity gradient formed once per stage -- and lanes 6 and 7 shadow
 // lane 0 and store nothing.  The lanes of a group take identical steps (the error norm runs over the base and all 36 variational
 // components), and everything a group decides it decides from the base, which every lane carries: no lane of a group ever leaves
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(64) void k_halo_correct(const HaloCorrectArgs a) {
   const bool store = (g < a.B) && (c == 0);
   double* hist = a.hist + (long)(a.max_iter + 1) * b;
 
-  // per-lane flags are doubles (run_dop853's comment, DESIGN.md "Compiler hazards")
+  // per-lane flags are doubles (dop853_lane.hpp, DESIGN.md "Compiler hazards")
   double status = -1.0;
   double tc = 0.0, res = __builtin_nan("");
   int it = 0, nrec = 0;

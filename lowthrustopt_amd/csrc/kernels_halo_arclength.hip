@@ -99,7 +99,7 @@ __global__ __launch_bounds__(64) void k_halo_arclength(const HaloArclengthArgs a
   double up[3] = {a.seed[6 * (long)b + 0], a.seed[6 * (long)b + 2], a.seed[6 * (long)b + 4]};
   double tw[3] = {a.dir0[3 * (long)b + 0], a.dir0[3 * (long)b + 1], a.dir0[3 * (long)b + 2]};
   double ds = a.ds0[b];
-  double dead = 0.0;                             // per-lane flags are doubles (run_dop853's comment, DESIGN.md "Compiler hazards")
+  double dead = 0.0;                             // per-lane flags are doubles (dop853_lane.hpp, DESIGN.md "Compiler hazards")
   {
     const double s = up[0] + up[1] + up[2] + tw[0] + tw[1] + tw[2];
     if (!finite1(s) || up[2] == 0.0 || (planar && up[1] != 0.0) || (tw[0] == 0.0 && tw[1] == 0.0 && tw[2] == 0.0)) dead = 1.0;

@@ -1,7 +1,7 @@
 // kernels_halo_target.hip -- periodic orbits of the CRTBP at a given Jacobi constant or a given period, B orbits side by side, each
 // marched through T target values inside one launch, gfx950.
 //
-// One GROUP of 8 adjacent lanes per orbit (dop853_group.hpp), as in kernels_halo.hip, but the group carries only the three columns of
+// One GROUP of 8 adjacent lanes per orbit (dop853_lane.hpp), as in kernels_halo.hip, but the group carries only the three columns of
 // Phi = dx/dx0 the Newton step reads: lane 0 column 0 (x0), lane 1 column 2 (z0), lane 2 column 4 (vy0); lanes 3..7 shadow lane 0
 // and add nothing to the error norm, which therefore runs over 6 + 3 x 6 = 24 components.  Everything a group decides it decides
 // from values every lane of it holds alike: no lane ever leaves the others.  A group beyond the batch shadows the last orbit.
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(64) void k_halo_target(const HaloTargetArgs a) {
   double s1[3] = {a.seed[6 * (long)b + 0], a.seed[6 * (long)b + 2], a.seed[6 * (long)b + 4]};
   double s2[3] = {s1[0], s1[1], s1[2]};
   double q1 = 0.0, q2 = 0.0;
-  double dead = 0.0;                             // per-lane flags are doubles (run_dop853's comment, DESIGN.md "Compiler hazards")
+  double dead = 0.0;                             // per-lane flags are doubles (dop853_lane.hpp, DESIGN.md "Compiler hazards")
 
   for (int k = 0; k < a.T; ++k) {
     const long m = (long)a.T * b + k;

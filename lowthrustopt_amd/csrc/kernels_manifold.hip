@@ -7,18 +7,17 @@
 //                       6 x 6 LU with partial pivoting, rows exchanged by selects: every index is a compile-time constant and the
 //                       matrix stays in registers), lambda_s the Rayleigh quotient of v_s.
 // k_manifold_transport  one lane per (orbit, phase, kind): the base state with ONE variational vector, 12 components, the error
-//                       norm over all of them (run_dop853, untouched).  The unstable vector flies forward over tau P, the stable one
+//                       norm over all of them (run_dop853).  The unstable vector flies forward over tau P, the stable one
 //                       backward over (1 - tau) P as the time-reversed system over a positive span.
 // k_manifold_starts     one lane per (orbit, phase): the orbit's status from the flags of all its flights, the starts X +- eps V
 //                       (the product rounded, then the sum: what the host forms from the outputs), NaN for an orbit without result.
-// k_section_flight      one lane per arc, 6 components, run_dop853_stop (dop853_stop.hpp) with a hook that counts the section's
+// k_section_flight      one lane per arc, 6 components, run_dop853_stop (dop853_lane.hpp) with a hook that counts the section's
 //                       crossings, locates the last one asked for (the bisection of kernels_halo.hip's halo_crossing) and ends the
 //                       flight there or at a step end inside r_min.
 // k_state_match         one workgroup per state of A: a (distance, index) lexicographic minimum over Bs (the rule of k_stack_find).
 //
 // No LDS but the match's two reduction arrays, no atomics, plain vector stores; per-lane flags are doubles (DESIGN "Compiler hazards").
 #include "kernels.hpp"
-#include "dop853_stop.hpp"
 #include "crtbp_ballistic.hpp"
 
 namespace lto {

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(64) void k_control_replay(const IndirectArgs a, con
 #pragma unroll
   for (int c = 0; c < NS; ++c) { y[c] = r.x0[(long)c * B + b]; insum += y[c]; }
   y[NS] = 0.0;
-  // per-lane flags are doubles (run_dop853's comment, DESIGN.md "Compiler hazards")
+  // per-lane flags are doubles (dop853_lane.hpp, DESIGN.md "Compiler hazards")
   double failed = ((insum - insum) == 0.0) ? 0.0 : 1.0;
   if (NS == 7 && !(y[NS - 1] > 0.0)) failed = 1.0;
   int nacc = 0, nrej = 0;

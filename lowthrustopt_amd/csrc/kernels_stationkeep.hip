@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64) void k_stationkeep_flight(const StationFlightAr
   double y[6];
 #pragma unroll
   for (int q = 0; q < 6; ++q) y[q] = a.x0[6L * b + q];
-  // per-lane flags are doubles (run_dop853's comment)
+  // per-lane flags are doubles (dop853_lane.hpp)
   double st = finite_all(y) ? 0.0 : 2.0;       // 0 in flight, 1 lost, 2 failed
   double total = 0.0, dev_r = 0.0, dev_v = 0.0;
   int nb = 0, nacc = 0, nrej = 0;

@@ -52,8 +52,7 @@ int events_dev(int nd, lto_indirect_plan* p, void* stream, const double* X, long
   ev.dv_seg = dv_seg; ev.status = status;
   hipStream_t st = (hipStream_t)stream;
   timing_begin(c, st);
-  hipError_t e = nd == 12 ? launch_indirect_events(p->pm, p->integ.method, a, ev, st)
-                          : launch_indirect_events_mass(p->pm, p->integ.method, a, ev, st);
+  hipError_t e = launch_indirect_events(nd, p->pm, p->integ.method, a, ev, st);
   if (e == hipSuccess) e = launch_events_compact(a, ev, p->n_batch, st);
   timing_end(c, st);
   if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_indirect_events", e);

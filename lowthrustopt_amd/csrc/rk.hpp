@@ -20,7 +20,9 @@ namespace lto {
 // 64-bit literals of an unrolled 13-stage loop out of it, runs out of scalar registers and spills them to VGPR lanes
 // (v_readlane / v_writelane inside the loop); an asm statement cannot be hoisted.
 __device__ __forceinline__ double coef_here(double c) {
+#ifdef __AMDGCN__
   asm volatile("" : "+s"(c));
+#endif
   return c;
 }
 

@@ -1,16 +1,20 @@
-// Host stub of <hip/hip_runtime.h>: lets g++ compile lowthrustopt_amd/csrc/dynamics.hpp so the CPU test-suite can
-// check the PRODUCT's device formulas (RHS, variational coefficients, fused column path) against the oracle
-// without a GPU.  The reduced-precision seeds mimic v_rsq_f64 / v_rcp_f64 (~2^-23) so the refinement steps are
-// exercised too.
+// Host stub of <hip/hip_runtime.h>: lets g++ compile lowthrustopt_amd/csrc/dynamics.hpp, rk.hpp and dop853_lane.hpp so the CPU
+// test-suite can check the PRODUCT's device formulas (RHS, variational coefficients, fused column path, the adaptive DOP853 lane
+// driver) against the oracle without a GPU.  The reduced-precision seeds mimic v_rsq_f64 / v_rcp_f64 (~2^-23) so the refinement
+// steps are exercised too.
 #pragma once
 #include <cmath>
 #define __device__
 #define __host__
 #define __forceinline__ inline
-#define __constant__ static const
+#define __constant__ const
 using std::fabs; using std::fmax; using std::fmin; using std::sqrt; using std::exp; using std::pow; using std::cbrt;
 static inline double __builtin_amdgcn_rsq(double x) { return (double)(float)(1.0 / std::sqrt(x)); }
 static inline double __builtin_amdgcn_rcp(double x) { return (double)(float)(1.0 / x); }
+static inline double __dmul_rn(double a, double b) { return a * b; }
+static inline double __ddiv_rn(double a, double b) { return a / b; }
+static inline double __dadd_rn(double a, double b) { return a + b; }
+static inline double __shfl_xor(double v, int, int) { return v; }      // one lane: only there so that the group form parses
 #include <cstring>
 static inline long long __double_as_longlong(double x) { long long r; std::memcpy(&r, &x, 8); return r; }
 static inline double __longlong_as_double(long long x) { double r; std::memcpy(&r, &x, 8); return r; }

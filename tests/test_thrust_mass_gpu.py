@@ -1,4 +1,4 @@
-"""Variable-mass thrust arcs on the device (k_indirect_events_mass, k_events_compact) against
+"""Variable-mass thrust arcs on the device (k_indirect_events<14>, k_events_compact) against
 tests/thrust_mass_reference.py.
 
 Bars, from the reference's own error (thrust_mass_reference.bars): |t_event - ref| <= max(1e-12 TU, 10 e_t) + 4 eps max|t|,

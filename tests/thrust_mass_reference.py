@@ -1,4 +1,4 @@
-"""Host reference for the variable-mass thrust-arc kernels (k_indirect_events_mass, k_events_compact) -- CPU only, no
+"""Host reference for the variable-mass thrust-arc kernels (k_indirect_events<14>, k_events_compact) -- CPU only, no
 library code under test.
 
 Per segment scipy.integrate.solve_ivp(method="DOP853", rtol = atol = 1e-13, events = g) on the 15-dimensional augmented system
