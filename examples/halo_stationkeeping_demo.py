@@ -19,8 +19,15 @@ Last, a short family of halo orbits between the packaged orbits 1 and 2 (drivers
 members' runs in one call with one orbit per run (n_orb = n_batch), 6 revolutions: the yearly cost against the unstable multiplier
 lambda_u.
 
-  python examples/halo_stationkeeping_demo.py [runs]
+With --law target-point the table is printed for both laws from the same draws: the target-point law of Howell &
+Pernicka (drivers.target_point_gains) asks the position deviation to vanish at --horizons periods after every burn, weighted by
+--weights against --q times |dv|^2.  It feeds the whole deviation back, the along-track part included, and keeps the runs the
+Floquet-mode law loses at 20 revolutions.
+
+  python examples/halo_stationkeeping_demo.py [runs] [--law target-point [--horizons 0.5 1.0] [--q 1e-2] [--weights 1 1]]
 """
+import argparse
+import itertools
 import os
 import sys
 
@@ -37,7 +44,7 @@ NAV_LEVELS = ((0.1, 0.001), (1.0, 0.01), (10.0, 0.1))       # km, m/s, 1 sigma p
 MS = DU / TU * 1e3
 
 
-def main(runs=4096):
+def main(runs=4096, law="floquet", horizons=(0.5, 1.0), q=1e-2, weights=None):
     ctx = lto.default_context(0)
     tabs = [np.asarray(tb[:6], dtype=float) for tb in synth.halo_orbits()]
     seed = tabs[0][:, 0].copy()
@@ -48,18 +55,26 @@ def main(runs=4096):
           % (orbit.period, orbit.period * TU / day, g.lam[0], g.lam[1], np.array2string(g.alpha, precision=3)))
     print("%d runs, %d burns per revolution, injection 1 km / 1 cm/s, execution 1 %% + 0.1 mm/s, lost beyond %.0f km, seed %d"
           % (runs, N_MAN, R_LOST_KM, SEED))
-    print("  revolutions  navigation error    dv per year, m/s (50 / 95 / 99 %)   lost    largest deviation, km (50 / 99 %)  at the end, km (50 %)"
-          "  call ms   uncontrolled: days kept (50 %), lost")
     common = dict(inj_sigma_r_km=1.0, inj_sigma_v_ms=0.01, exe_sigma_frac=0.01, exe_sigma_ms=1e-4, r_lost_km=R_LOST_KM, seed=SEED, MU=MU,
                   gains=g, ctx=ctx)
-    for n_rev in N_REVS:
-        for nr, nv in NAV_LEVELS:
-            out = drivers.stationkeep(orbit, n_rev, runs, nav_sigma_r_km=nr, nav_sigma_v_ms=nv, **common)
+    laws = [("", g)]
+    if law == "target-point":
+        gt = drivers.target_point_gains(orbit, n_man=N_MAN, horizons=horizons, q=q, weights=weights, MU=MU, ctx=ctx)
+        print("target-point law: horizons %s periods, q %g, weights %s (DU, DU/TU); both laws fly the same draws"
+              % (list(horizons), q, "ones" if weights is None else list(weights)))
+        laws = [("Floquet       ", g), ("target-point  ", gt)]
+    print(("law           " if len(laws) > 1 else "") +
+          "  revolutions  navigation error    dv per year, m/s (50 / 95 / 99 %)   lost    largest deviation, km (50 / 99 %)  at the end, km (50 %)"
+          "  call ms   uncontrolled: days kept (50 %), lost")
+    for n_rev, (nr, nv) in itertools.product(N_REVS, NAV_LEVELS):
+        # the uncontrolled runs do not depend on the law: once per row of draws
+        free = drivers.stationkeep(orbit, n_rev, runs, nav_sigma_r_km=nr, nav_sigma_v_ms=nv,
+                                   **dict(common, gains=g._replace(G=np.zeros_like(g.G)), exe_sigma_frac=None, exe_sigma_ms=None))
+        for name, gl in laws:
+            out = drivers.stationkeep(orbit, n_rev, runs, nav_sigma_r_km=nr, nav_sigma_v_ms=nv, **dict(common, gains=gl))
             ms = ctx.last_call_ms()
-            free = drivers.stationkeep(orbit, n_rev, runs, nav_sigma_r_km=nr, nav_sigma_v_ms=nv,
-                                       **dict(common, gains=g._replace(G=np.zeros_like(g.G)), exe_sigma_frac=None, exe_sigma_ms=None))
             p = out["percentiles"]
-            print("  %3d (%3.0f d)  %5.1f km %5.1f cm/s   %8.3f / %8.3f / %8.3f      %5.1f %%     %9.1f / %9.1f             %9.1f         %7.2f    %6.1f, %.1f %%"
+            print(name + "  %3d (%3.0f d)  %5.1f km %5.1f cm/s   %8.3f / %8.3f / %8.3f      %5.1f %%     %9.1f / %9.1f             %9.1f         %7.2f    %6.1f, %.1f %%"
                   % (n_rev, n_rev * orbit.period * TU / day, nr, nv * 100.0, p["dv_per_year_ms"][50], p["dv_per_year_ms"][95],
                      p["dv_per_year_ms"][99], 100.0 * out["lost_share"], p["dev_r_km"][50], p["dev_r_km"][99],
                      float(np.median(out["dev_final_r_km"][out["status"] == 0])), ms, float(np.median(free["t_days"])),
@@ -94,4 +109,11 @@ def main(runs=4096):
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 4096)
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("runs", nargs="?", type=int, default=4096)
+    ap.add_argument("--law", choices=("floquet", "target-point"), default="floquet")
+    ap.add_argument("--horizons", nargs="+", type=float, default=[0.5, 1.0], help="targets, in periods after every burn")
+    ap.add_argument("--q", type=float, default=1e-2, help="weight of |dv|^2")
+    ap.add_argument("--weights", nargs="+", type=float, default=None, help="weight of the position deviation at each target")
+    a = ap.parse_args()
+    main(a.runs, a.law, tuple(a.horizons), a.q, None if a.weights is None else tuple(a.weights))

@@ -658,6 +658,53 @@ int lto_stationkeep_flight_batch(lto_ctx* ctx, int n_man, int n_rev, int n_batch
                                  double dv_max, double r_lost, const lto_integrator* integ, double* x_final, double* dv_total,
                                  int* n_burn, double* dev, double* dv_hist, double* dev_final, int* accepted, int* rejected,
                                  int* status, int* lost_at);
+/* Target-point station-keeping: the state-transition matrices between phases of a periodic orbit, and the law of
+ * Howell & Pernicka built from them.  A record does not depend on its batch: it equals its single call bit for bit.
+ *
+ * lto_halo_stm_batch: one record per (phase, orbit), record g = n_phase b + j.  state0 [6 x n_batch] and period [n_batch] as
+ * lto_halo_table_batch takes them, tau [n_phase] the phases, shared by the batch, each finite and wrapped into [0, 1), horizon
+ * [n_tgt] the targets in periods, finite, > 0 and strictly increasing.  Per record, with t_j = tau_j P:
+ *   coast     the six-component ballistic state from state0 over tau_j P (tau = 0 flies nothing): X_out [6 x n_phase x n_batch]
+ *   spans     from X_out and Phi = I, the base state with all six columns of the variational equations (42 components in the
+ *             error norm, the lanes of lto_halo_table_batch) over (h_k - h_{k-1}) P, h_0 = 0, k = 1..n_tgt, each a span of its
+ *             own: Phi_out [6 x 6 x n_tgt x n_phase x n_batch] (column-major 6 x 6 blocks) = Phi(t_j + h_k P, t_j), X_tgt [6 x
+ *             n_tgt x n_phase x n_batch] the orbit point there (may be NULL)
+ * LTO_DOP853_ADAPTIVE at integ's rtol / atol / max_steps, max_steps counted per span (the coast is one), or LTO_RK4 with
+ * integ->steps steps per span, the coast counting as one span; any other method: LTO_EUNSUPPORTED.  accepted / rejected [n_phase x
+ * n_batch] (may be NULL) are summed over the coast and the spans.  status [n_phase x n_batch]: 0; 2 no finite result (a state or
+ * period that is not finite, period <= 0, a span that used up max_steps, a result that is not finite): NaN in every output of that
+ * record and in no other.
+ * LTO_EINVAL: n_phase, n_tgt or n_batch < 1, MU outside (0, 1), a horizon not finite, <= 0 or not above the one before it, a tau not
+ * finite, LTO_RK4 with steps < 1, 36 n_tgt n_phase n_batch > 2^31 - 1.
+ *
+ * lto_stationkeep_target_gains_batch: Phi [6 x 6 x n_tgt x n_rec] in the layout of Phi_out, one record per 6 x 6 x n_tgt block.
+ * With Phi_k = [A_k B_k; C_k D_k] (3 x 3 blocks) a burn dv at the record's epoch leaves the position deviation m_k = A_k p + B_k (e
+ * + dv) at target k for the measured deviation dx = (p, e).  dv = G dx minimises q |dv|^2 + sum_k r_k |m_k|^2:
+ *   H = q I + sum_k r_k B_k^T B_k,  N = sum_k r_k B_k^T [A_k | B_k],  G = -H^-1 N.
+ * q >= 0, r [n_tgt] each >= 0 and not all zero.  Every product, sum, difference and quotient is rounded on its own (no fused
+ * multiply-add), the square roots are correctly rounded, in this order, so the host can reproduce G bit for bit.  T_k [3 x 6] =
+ * rows 0..2 of Phi_k (T_k[m, c] = Phi[m + 6 c + 36 k]), B_k = its columns 3..5:
+ *   s_k[i, c] = (T_k[0, 3+i] T_k[0, c] + T_k[1, 3+i] T_k[1, c]) + T_k[2, 3+i] T_k[2, c]       i = 0..2, c = 0..5
+ *   n[i, c]   = r_0 s_0[i, c], then n[i, c] + r_k s_k[i, c] for k = 1, 2, ...
+ *   h[i, j]   = the same sum with c = 3 + j, for j <= i;  H[i, i] = q + h[i, i],  H[i, j] = h[i, j] (j < i)
+ *   hmax = max(max(H00, H11), H22)
+ *   d0 = H00, L00 = sqrt(d0), L10 = H10 / L00, L20 = H20 / L00
+ *   d1 = H11 - L10 L10, L11 = sqrt(d1), L21 = (H21 - L20 L10) / L11
+ *   d2 = (H22 - L20 L20) - L21 L21, L22 = sqrt(d2)
+ *   per column c:  z0 = n[0, c] / L00,  z1 = (n[1, c] - L10 z0) / L11,  z2 = ((n[2, c] - L20 z0) - L21 z1) / L22
+ *                  x2 = z2 / L22,  x1 = (z1 - L21 x2) / L11,  x0 = ((z0 - L10 x1) - L20 x2) / L00
+ *                  G[r + 3 c] = -x_r
+ * Outputs: G [3 x 6 x n_rec], the layout lto_stationkeep_flight_batch reads; pivot [n_rec] (may be NULL) = min(min(d0, d1), d2) /
+ * hmax, the smallest squared Cholesky pivot over the largest diagonal entry of H; status [n_rec]: 0; 2 an entry of the record's
+ * Phi that is not finite; 3 a d_i that is not > sing_tol hmax.  Status 2 and 3 leave NaN in that record's G and pivot and touch no
+ * other.
+ * LTO_EINVAL: n_tgt or n_rec < 1, q negative or not finite, an r negative or not finite, every r zero, sing_tol outside [0, 1), 36
+ * n_tgt n_rec > 2^31 - 1. */
+int lto_halo_stm_batch(lto_ctx* ctx, int n_phase, int n_tgt, int n_batch, double MU, const double* state0, const double* period,
+                       const double* tau, const double* horizon, const lto_integrator* integ, double* X_out, double* Phi_out,
+                       double* X_tgt, int* accepted, int* rejected, int* status);
+int lto_stationkeep_target_gains_batch(lto_ctx* ctx, int n_tgt, int n_rec, const double* Phi, double q, const double* r,
+                                       double sing_tol, double* G, double* pivot, int* status);
 /* Mesh re-distribution of converged 12-dim solutions (the indirect method's counterpart of meshRefine_direct): the
  * nodes of XC [12 x n_nodes x n_batch] on t [n_nodes x n_tgrids] (n_tgrids = 1 or n_batch) are moved, and their number changed to
  * n_new, so that every new segment carries the same share of a per-segment monitor w_i > 0.  Per trajectory:

@@ -17,7 +17,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
-       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_target, halo_arclength, halo_table, manifold_seeds, section_flight, state_match, stationkeep_gains, stationkeep_flight,
+       direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_target, halo_arclength, halo_table, manifold_seeds, section_flight, state_match, stationkeep_gains, stationkeep_flight, halo_stm, stationkeep_target_gains,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
@@ -992,6 +992,42 @@ function stationkeep_flight(ctx::LtoContext, X_ref::Array{Float64,3}, dt::Matrix
                dev, dv_hist, dev_final, acc, rej, status, lost_at)
     check(ctx, rc)
     (x_final, dv_total, Int.(n_burn), dev, dv_hist, dev_final, Int.(acc), Int.(rej), Int.(status), Int.(lost_at))
+end
+
+# The state-transition matrices between phases of B periodic orbits (`lto_halo_stm_batch`, DESIGN 4.30): state0 [6 x B], period [B],
+# tau [P] the phases shared by the batch, horizons [K] in periods, > 0 and strictly increasing.  Returns (X [6 x P x B] the orbit
+# point at each phase, Phi [6 x 6 x K x P x B] = Phi(t_j + h_k P, t_j), X_tgt [6 x K x P x B], accepted [P x B], rejected [P x B],
+# status [P x B]).
+function halo_stm(ctx::LtoContext, state0::Matrix{Float64}, period::Vector{Float64}, tau::Vector{Float64}, horizons::Vector{Float64},
+                  MU; integ::LtoIntegrator = LtoIntegrator())
+    size(state0, 1) == 6 || error("halo_stm: state0 must be 6 x B")
+    B = size(state0, 2)
+    length(period) == B || error("halo_stm: one period per orbit")
+    P = length(tau); K = length(horizons)
+    P >= 1 && K >= 1 || error("halo_stm: at least one phase and one horizon")
+    X = zeros(6, P, B); Phi = zeros(6, 6, K, P, B); Xt = zeros(6, K, P, B)
+    acc = zeros(Cint, P, B); rej = zeros(Cint, P, B); status = zeros(Cint, P, B)
+    rc = ccall((:lto_halo_stm_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{LtoIntegrator},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}),
+               ctx.handle, P, K, B, Float64(MU), state0, period, tau, horizons, Ref(integ), X, Phi, Xt, acc, rej, status)
+    check(ctx, rc)
+    (X, Phi, Xt, Int.(acc), Int.(rej), Int.(status))
+end
+
+# The target-point station-keeping gains from Phi [6 x 6 x K x n] of halo_stm (`lto_stationkeep_target_gains_batch`, DESIGN 4.30):
+# dv = G dx minimises q |dv|^2 + sum_k r[k] |position deviation at target k|^2.  Returns (G [3 x 6 x n], pivot [n], status [n]).
+function stationkeep_target_gains(ctx::LtoContext, Phi::Array{Float64,4}; q = 1e-2, r::Vector{Float64} = ones(size(Phi, 3)),
+                                  sing_tol = 1e-12)
+    size(Phi, 1) == 6 && size(Phi, 2) == 6 || error("stationkeep_target_gains: Phi must be 6 x 6 x K x n")
+    K = size(Phi, 3); n = size(Phi, 4)
+    length(r) == K || error("stationkeep_target_gains: one weight per target")
+    G = zeros(3, 6, n); pivot = zeros(n); status = zeros(Cint, n)
+    rc = ccall((:lto_stationkeep_target_gains_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, K, n, Phi, Float64(q), r, Float64(sing_tol), G, pivot, status)
+    check(ctx, rc)
+    (G, pivot, Int.(status))
 end
 
 # optimizeTraj with flagEnd = true: one Jacobian sweep and the exact free-end QP step.  Returns (x_update, u_update, p1_update,

@@ -15,7 +15,8 @@ from .hotpath import (Context, Group, Comm, GroupComm, auto_kernel, default_cont
                       guidance_gains_mass, guided_flight_mass, halo_correct, HaloCorrect, halo_table, HaloTable,
                       HALO_HOLD_Z0, HALO_HOLD_X0, HALO_PLANAR, manifold_seeds, ManifoldSeeds, section_flight, SectionFlight,
                       state_match, StateMatch, halo_target, HaloTarget, HALO_TARGET_JACOBI, HALO_TARGET_PERIOD,
-                      halo_arclength, HaloArclength, stationkeep_gains, StationkeepGains, stationkeep_flight, StationkeepFlight)
+                      halo_arclength, HaloArclength, stationkeep_gains, StationkeepGains, stationkeep_flight, StationkeepFlight,
+                      halo_stm, HaloStm, stationkeep_target_gains, StationkeepTargetGains)
 from . import synth  # noqa: F401
 
 __version__ = "0.1.0"

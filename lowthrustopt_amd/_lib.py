@@ -115,6 +115,9 @@ SIGNATURES = {
     "lto_stationkeep_flight_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp,
                                                C.c_double, C.c_double, C.c_double, C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _vp, _vp]),
+    "lto_halo_stm_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.POINTER(LtoIntegrator), _vp,
+                                     _vp, _vp, _vp, _vp, _vp]),
+    "lto_stationkeep_target_gains_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_double, _vp, _vp, _vp]),
     "lto_indirect_remesh_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.POINTER(LtoParams), C.c_int,
                                             C.POINTER(LtoIntegrator), C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp, _vp]),

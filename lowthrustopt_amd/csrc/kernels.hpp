@@ -493,6 +493,35 @@ struct StationFlightArgs {
 };
 // method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
 hipError_t launch_stationkeep_flight(int method, const StationFlightArgs& a, hipStream_t st);
+// Target-point station-keeping.  Phase-to-phase STMs (kernels_halo_stm.hip): one group of 8 lanes per (phase, orbit)
+// record g = P b + j; a coast over tau_j period_b, then the K spans (h_k - h_{k-1}) period_b with Phi carried through from the
+// identity at the phase.  Xt, accepted and rejected may be null.
+struct HaloStmArgs {
+  const double* state0; const double* period;  // [6][B], [B]
+  const double* tau;                           // [P], wrapped into [0, 1) by the host
+  const double* horizon;                       // [K], in periods, strictly increasing from > 0
+  int P, K, B;
+  double MU;
+  int steps;                                   // RK4: steps per span, the coast counting as one
+  double rtol, atol; int max_steps;            // DOP853: max_steps counts per span
+  double* X;                                   // [6][P][B]
+  double* Phi;                                 // [6][6][K][P][B], column-major blocks
+  double* Xt;                                  // [6][K][P][B]
+  int* accepted; int* rejected; int* status;   // [P][B]
+};
+// method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
+hipError_t launch_halo_stm(int method, const HaloStmArgs& a, hipStream_t st);
+// Target-point gains (kernels_stationkeep.hip): one lane per record of Phi [6][6][K][n].  pivot may be null.
+struct StationTargetGainsArgs {
+  const double* Phi;                           // [6][6][K][n]
+  const double* r;                             // [K]
+  int K; long n;
+  double q, sing_tol;
+  double* G;                                   // [3][6][n], column-major 3 x 6 blocks
+  double* pivot;                               // [n]
+  int* status;                                 // [n]
+};
+hipError_t launch_stationkeep_target_gains(const StationTargetGainsArgs& a, hipStream_t st);
 // Mesh equidistribution of the indirect method (kernels_remesh.hip).  Grid: per trajectory b the monitor of old segment
 // i is w[b (n-1) + i], or nacc + nrej there when w is null; old grids t[b t_stride + i].
 // Out: t_out [n_batch][n_new] and seg_of [n_batch][n_new], the old node each new one is propagated from.

@@ -6,6 +6,9 @@
 //                       (w . v_u), G = -w_v W^T / |w_v|^2 the minimum-norm velocity change that zeroes the unstable component,
 //                       alpha = |w_v| / |W|.  No fused multiply-add: every product and every sum rounded on its own, in the order
 //                       include/lto.h states, so the host reproduces the outputs bit for bit.
+// k_stationkeep_target_gains  one lane per record: the target-point law of Howell & Pernicka from the phase-to-phase
+//                       STMs of k_halo_stm, G = -H^-1 N with H = q I + sum_k r_k B_k^T B_k, N = sum_k r_k B_k^T [A_k | B_k], by a 3 x 3
+//                       Cholesky factorisation.  The same rule: no fused multiply-add, the order of include/lto.h.
 // k_stationkeep_flight  one lane per run, 6 components, span by span under run_dop853 (or `steps` RK4 steps) over SysCrtbpDir
 //                       (crtbp_ballistic.hpp): at every burn epoch the deviation from the reference point, the lost test, the
 //                       commanded burn G (d + nav), dead band and clip, the execution error, the impulse, then the ballistic span.
@@ -72,6 +75,85 @@ __global__ __launch_bounds__(64) void k_stationkeep_gains(const StationGainsArgs
 
 hipError_t launch_stationkeep_gains(const StationGainsArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_stationkeep_gains, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(64) void k_stationkeep_target_gains(const StationTargetGainsArgs a) {
+#pragma clang fp contract(off)                 // the order of include/lto.h, every operation rounded on its own
+  const long g = (long)blockIdx.x * 64 + threadIdx.x;
+  if (g >= a.n) return;
+  const double* Pg = a.Phi + 36 * (long)a.K * g;
+  double H[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // the lower triangle: 00, 10, 11, 20, 21, 22
+  double N[3][6];
+  double bad = 0.0;
+  for (int k = 0; k < a.K; ++k) {
+    const double* Pk = Pg + 36 * (long)k;
+    const double rk = a.r[k];
+    double T[3][6];                            // T = [A_k | B_k], the position rows of Phi_k; B_k = its columns 3..5
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+#pragma unroll
+      for (int r = 0; r < 6; ++r) {
+        const double v = Pk[6 * c + r];
+        bad += ((v - v) == 0.0) ? 0.0 : 1.0;
+        if (r < 3) T[r][c] = v;
+      }
+    }
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j, ++e) {
+        double s = T[0][3 + i] * T[0][3 + j];
+        s = s + T[1][3 + i] * T[1][3 + j];
+        s = s + T[2][3 + i] * T[2][3 + j];
+        const double t = rk * s;
+        H[e] = (k == 0) ? t : H[e] + t;
+      }
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double s = T[0][3 + i] * T[0][c];
+        s = s + T[1][3 + i] * T[1][c];
+        s = s + T[2][3 + i] * T[2][c];
+        const double t = rk * s;
+        N[i][c] = (k == 0) ? t : N[i][c] + t;
+      }
+    }
+  }
+  const double h00 = a.q + H[0], h10 = H[1], h11 = a.q + H[2], h20 = H[3], h21 = H[4], h22 = a.q + H[5];
+  const double hmax = fmax(fmax(h00, h11), h22);
+  const double lim = a.sing_tol * hmax;
+  // Cholesky H = L L^T: d_i the squared pivots
+  const double d0 = h00;
+  const double l00 = __dsqrt_rn(d0);
+  const double l10 = h10 / l00, l20 = h20 / l00;
+  const double d1 = h11 - l10 * l10;
+  const double l11 = __dsqrt_rn(d1);
+  const double l21 = (h21 - l20 * l10) / l11;
+  const double d2 = (h22 - l20 * l20) - l21 * l21;
+  const double l22 = __dsqrt_rn(d2);
+  double st = 0.0;
+  if (bad != 0.0) st = 2.0;
+  else if (!(d0 > lim) || !(d1 > lim) || !(d2 > lim)) st = 3.0;
+  const double nan = __builtin_nan("");
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const double z0 = N[0][c] / l00;
+    const double z1 = (N[1][c] - l10 * z0) / l11;
+    const double z2 = ((N[2][c] - l20 * z0) - l21 * z1) / l22;
+    const double x2 = z2 / l22;
+    const double x1 = (z1 - l21 * x2) / l11;
+    const double x0 = ((z0 - l10 * x1) - l20 * x2) / l00;
+    a.G[18 * g + 3 * c + 0] = (st != 0.0) ? nan : -x0;
+    a.G[18 * g + 3 * c + 1] = (st != 0.0) ? nan : -x1;
+    a.G[18 * g + 3 * c + 2] = (st != 0.0) ? nan : -x2;
+  }
+  if (a.pivot) a.pivot[g] = (st != 0.0) ? nan : fmin(fmin(d0, d1), d2) / hmax;
+  a.status[g] = (int)st;
+}
+
+hipError_t launch_stationkeep_target_gains(const StationTargetGainsArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(k_stationkeep_target_gains, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

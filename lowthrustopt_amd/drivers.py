@@ -2221,6 +2221,34 @@ def stationkeeping_gains(orbit, taus=None, n_man=4, sing_tol=1e-8, MU=None, inte
     return StationGains(seeds.tau, np.asfortranarray(seeds.X[:, 1, :]), dt, g.G, g.W, g.alpha, seeds.lam)
 
 
+def target_point_gains(orbit, taus=None, n_man=4, horizons=(0.5, 1.0), q=1e-2, weights=None, sing_tol=1e-12, MU=None, integ=None,
+                       ctx=None):
+    """The target-point station-keeping law of a periodic orbit in two library calls: the state-transition matrices
+    from every burn phase to its targets (hotpath.halo_stm), then the gains (hotpath.stationkeep_target_gains).  The law needs no
+    hyperbolic pair, so it also serves orbits manifold_seeds refuses.  orbit: what halo_orbit returns, or (state0, period, M) (M is not read);
+    taus [n_man] the burn phases (any finite values, wrapped into [0, 1), increasing after the wrap), default j / n_man; horizons
+    [K] the targets in periods after each burn; q the weight of |dv|^2 and weights [K] those of the position deviation at each
+    target (default ones), in DU and DU/TU.  Returns StationGains(tau [n_man] as wrapped, X_ref [6 x n_man] the orbit point at each
+    phase, dt [n_man] the span after each burn (stationkeep_spans), G [3 x 6 x n_man], W = alpha = lam = None), which
+    stationkeep(..., gains=...) flies as it is.  An STM or gains status other than 0 raises ValueError."""
+    MU = hotpath.MU if MU is None else MU
+    state0, period = _orbit_parts(orbit)[:2]
+    if taus is None:
+        n_man = int(n_man)
+        if n_man < 1:
+            raise ValueError("n_man must be >= 1")
+        taus = np.arange(n_man) / float(n_man)
+    stm = hotpath.halo_stm(state0, period, taus, horizons, MU=MU, integ=integ, ctx=ctx)
+    if np.any(stm.status != 0):
+        raise ValueError("no state-transition matrix at phase(s) %s (status 2 of halo_stm)" % list(stm.tau[stm.status != 0]))
+    dt = stationkeep_spans(stm.tau, period)
+    g = hotpath.stationkeep_target_gains(stm.Phi, q, weights, sing_tol, ctx=ctx)
+    if np.any(g.status != 0):
+        raise ValueError("no usable gain at phase(s) %s (statuses %s of stationkeep_target_gains)"
+                         % (list(stm.tau[g.status != 0]), list(g.status[g.status != 0])))
+    return StationGains(stm.tau, np.asfortranarray(stm.X), dt, g.G, None, None, None)
+
+
 def stationkeep_draws(n_runs, n_upd, inj_sigma_r_km, inj_sigma_v_ms, nav_sigma_r_km, nav_sigma_v_ms, exe_sigma_frac, exe_sigma_ms,
                       seed, DU, TU):
     """The error draws of a station-keeping Monte Carlo from numpy.random.default_rng(seed), always in the order injection,

@@ -1757,6 +1757,94 @@ def stationkeep_flight(X_ref, dt, G, x0, n_rev, nav=None, exe=None, dv_min=0.0, 
     return StationkeepFlight(x_final, dv_total, n_burn, dev, dv_hist, dev_final, acc, rej, status, lost_at)
 
 
+HaloStm = collections.namedtuple("HaloStm", "X Phi X_tgt tau horizons accepted rejected status")
+StationkeepTargetGains = collections.namedtuple("StationkeepTargetGains", "G pivot status")
+
+
+def _horizons(horizons):
+    h = np.ascontiguousarray(np.asarray(horizons, dtype=np.float64).reshape(-1))
+    if h.size < 1 or not np.all(np.isfinite(h)) or h[0] <= 0.0 or np.any(np.diff(h) <= 0.0):
+        raise ValueError("horizons must hold at least one target, all finite, > 0 and strictly increasing")
+    return h
+
+
+def halo_stm(state0, period, tau, horizons, MU=MU, integ=None, ctx=None):
+    """The state-transition matrices between phases of periodic orbits (lto_halo_stm_batch).  state0 [6] or [6 x B],
+    period scalar or [B], tau [P] the phases (any finite values; they are wrapped into [0, 1)), horizons [K] in periods, finite, > 0
+    and strictly increasing.  Returns HaloStm(X [6 x P x B] the orbit point at each phase, Phi [6 x 6 x K x P x B] = Phi(t_j + h_k
+    period, t_j) with t_j = tau_j period, X_tgt [6 x K x P x B] the orbit point at each target, tau [P] as wrapped, horizons [K],
+    accepted and rejected [P x B] the steps of the coast and the spans, status [P x B]: 0, or 2 without a finite result, NaN in that
+    record) -- without the batch axis for a single orbit."""
+    S = np.asarray(state0, dtype=np.float64)
+    if S.ndim not in (1, 2) or S.shape[0] != 6 or S.size == 0:
+        raise ValueError("state0 must be [6] or [6 x B]")
+    batched = S.ndim == 2
+    S = np.asfortranarray(S.reshape(6, -1))
+    B = S.shape[1]
+    P = np.asarray(period, dtype=np.float64).reshape(-1)
+    if P.size not in (1, B):
+        raise ValueError("period must be a scalar or [B]")
+    P = np.ascontiguousarray(np.broadcast_to(P, (B,)))
+    tau = np.ascontiguousarray(np.asarray(tau, dtype=np.float64).reshape(-1))
+    if tau.size < 1 or not np.all(np.isfinite(tau)):
+        raise ValueError("tau must hold at least one phase, all finite")
+    h = _horizons(horizons)
+    if not (0.0 < float(MU) < 1.0):
+        raise ValueError("MU must lie in (0, 1)")
+    n, K = tau.size, h.size
+    if 36 * K * n * B > 0x7fffffff:
+        raise ValueError("36 n_tgt n_phase n_batch must not exceed 2^31 - 1")
+    integ = _flight_integrator(integ)
+    ctx = ctx or default_context()
+    X = np.zeros((6, n, B), order="F")
+    Phi = np.zeros((6, 6, K, n, B), order="F")
+    Xt = np.zeros((6, K, n, B), order="F")
+    acc, rej, status = (np.zeros((n, B), dtype=np.int32, order="F") for _ in range(3))
+    ctx.check(ctx.fn("halo_stm_batch")(ctx.handle, n, K, B, float(MU), _ptr(S), _ptr(P), _ptr(tau), _ptr(h), C.byref(integ), _ptr(X),
+                                       _ptr(Phi), _ptr(Xt), _ptr(acc), _ptr(rej), _ptr(status)))
+    wrapped = tau - np.floor(tau)
+    wrapped[wrapped >= 1.0] = 0.0
+    if not batched:
+        return HaloStm(X[..., 0], Phi[..., 0], Xt[..., 0], wrapped, h, acc[:, 0], rej[:, 0], status[:, 0])
+    return HaloStm(X, Phi, Xt, wrapped, h, acc, rej, status)
+
+
+def stationkeep_target_gains(Phi, q=1e-2, r=None, sing_tol=1e-12, ctx=None):
+    """The target-point station-keeping gains of Howell & Pernicka from phase-to-phase STMs (lto_stationkeep_target_gains_batch,
+    DESIGN 4.30).  Phi [6 x 6 x K] (one record), [6 x 6 x K x P] or [6 x 6 x K x P x B], HaloStm.Phi as it is; q >= 0 the weight of
+    |dv|^2, r [K] the weights of the position deviation at each target (>= 0, not all zero; default ones).  Returns
+    StationkeepTargetGains(G [3 x 6 (x P (x B))] with dv = G dx = -H^-1 N dx, H = q I + sum_k r_k B_k^T B_k, N = sum_k r_k B_k^T
+    [A_k | B_k]; pivot: the smallest squared Cholesky pivot of H over its largest diagonal entry; status: 0, 2 a non-finite input,
+    3 a pivot not > sing_tol times the largest diagonal entry; NaN outputs where status != 0)."""
+    Pp = np.asarray(Phi, dtype=np.float64)
+    if Pp.ndim not in (3, 4, 5) or Pp.shape[:2] != (6, 6) or Pp.size == 0:
+        raise ValueError("Phi must be [6 x 6 x K], [6 x 6 x K x P] or [6 x 6 x K x P x B]")
+    K = Pp.shape[2]
+    tail = Pp.shape[3:]
+    q = float(q)
+    if not (np.isfinite(q) and q >= 0.0):
+        raise ValueError("q must be finite and >= 0")
+    rr = np.ones(K) if r is None else np.ascontiguousarray(np.asarray(r, dtype=np.float64).reshape(-1))
+    if rr.size != K or not np.all(np.isfinite(rr)) or np.any(rr < 0.0) or not np.any(rr > 0.0):
+        raise ValueError("r must hold one finite weight >= 0 per target, not all zero")
+    sing_tol = float(sing_tol)
+    if not (0.0 <= sing_tol < 1.0):
+        raise ValueError("sing_tol must lie in [0, 1)")
+    Pp = np.asfortranarray(Pp.reshape(6, 6, K, -1, order="F"))
+    n = Pp.shape[3]
+    if 36 * K * n > 0x7fffffff:
+        raise ValueError("36 n_tgt n_rec must not exceed 2^31 - 1")
+    ctx = ctx or default_context()
+    G = np.zeros((3, 6, n), order="F")
+    pivot = np.zeros(n)
+    status = np.zeros(n, dtype=np.int32)
+    ctx.check(ctx.fn("stationkeep_target_gains_batch")(ctx.handle, K, n, _ptr(Pp), q, _ptr(rr), sing_tol, _ptr(G), _ptr(pivot),
+                                                       _ptr(status)))
+    if not tail:
+        return StationkeepTargetGains(G[..., 0], float(pivot[0]), int(status[0]))
+    return StationkeepTargetGains(G.reshape((3, 6) + tail, order="F"), pivot.reshape(tail, order="F"), status.reshape(tail, order="F"))
+
+
 AddTime = collections.namedtuple("AddTime", "XC_guess XC_out t_out tau defect status iterations history cost")
 AddTimeMass = collections.namedtuple("AddTimeMass", AddTime._fields + ("propellant",))
 
