@@ -10,6 +10,18 @@ namespace lto {
 // integrator ids (== LTO_* in include/lto.h)
 enum Method : int { M_RK4 = 0, M_RKF78_FIXED = 1, M_RKF78_ADAPTIVE = 2, M_DOP853_ADAPTIVE = 3 };
 
+// The launch of a kernel that is built once per integrator, for the flights that know RK4 and DOP853: `lanes` lanes in workgroups
+// of 64, k_rk4 for M_RK4, k_dop853 for M_DOP853_ADAPTIVE; any other method: hipErrorInvalidValue.
+template <class Args>
+static inline hipError_t launch_by_method(int method, void (*k_rk4)(Args), void (*k_dop853)(Args), long lanes, const Args& a,
+                                          hipStream_t st) {
+  const dim3 grid((unsigned)((lanes + 63) / 64));
+  if (method == M_RK4) hipLaunchKernelGGL(k_rk4, grid, dim3(64), 0, st, a);
+  else if (method == M_DOP853_ADAPTIVE) hipLaunchKernelGGL(k_dop853, grid, dim3(64), 0, st, a);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
 // Device layout (include/lto.h, "device-resident API"): node j = b*n_nodes + k, segment
 // s = b*seg_per_traj + i, component-major with leading dimensions ld*.
 struct IndirectArgs {

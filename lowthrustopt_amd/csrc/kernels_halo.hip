@@ -1,39 +1,31 @@
 // kernels_halo.hip -- periodic orbits of the CRTBP with the xz-plane symmetry (halo, planar Lyapunov), B orbits side by side
 // (DESIGN 4.25), gfx950.
 //
-// One GROUP of 8 adjacent lanes per orbit, 8 orbits per wavefront (dop853_lane.hpp).  Lane c < 6 of a group integrates the ballistic
-// base state with column c of Phi = dx/dx0 -- 12 components, the gravity gradient formed once per stage -- and lanes 6 and 7 shadow
-// lane 0 and store nothing.  The lanes of a group take identical steps (the error norm runs over the base and all 36 variational
-// components), and everything a group decides it decides from the base, which every lane carries: no lane of a group ever leaves
-// the others.  A group beyond the batch shadows the last orbit.  No LDS, plain vector stores.
+// One GROUP of 8 adjacent lanes per orbit, 8 orbits per wavefront (halo_common.hpp group_lane, dop853_lane.hpp).  Lane c < 6 of a
+// group integrates the ballistic base state with column c of Phi = dx/dx0 -- 12 components, the gravity gradient formed once per
+// stage -- and lanes 6 and 7 shadow lane 0 and store nothing.  The lanes of a group take identical steps (the error norm runs over
+// the base and all 36 variational components), and everything a group decides it decides from the base, which every lane carries:
+// no lane of a group ever leaves the others.  No LDS, plain vector stores.
 //
-// k_halo_correct: the differential corrector, the whole Newton loop in the kernel.  Per iteration: fly from (x0, 0, z0, 0, vy0, 0)
-// to the first return to y = 0 -- the first accepted step at whose end y has left the side vy0 sent it to, the crossing bracketed
-// by trial steps of the same formula from the step's start (bisection of the step length until the bracket's ends are adjacent
-// doubles in time, at most 60 halvings; the rule of kernels_events.hip), the state and Phi there from one more trial step -- then
-// the residual (vx, vz) and the 2 x 2 Jacobian  Phi[(3,5),(i,4)] - f[(3,5)] Phi[1,(i,4)] / f[1]  (the second term: the crossing
-// time moves with the unknowns), solved in every lane of the group alike.
+// k_halo_correct: the differential corrector, the whole Newton loop in the kernel.  Per iteration: the return flight
+// (halo_return_rk4, or the same rule under the group driver), then the residual (vx, vz) and the 2 x 2 Jacobian from the columns
+// (the position unknown, vy0) of DF (halo_df_column), solved in every lane of the group alike.
 //
 // k_halo_table: one revolution from (state0, P) with Phi carried through, stopped at t_i = i P / (n - 1), every sample interval a
 // span of its own; the samples, M = Phi(P), the closure, the Jacobi constant and its drift, the stability indices.
-#include "halo_common.hpp"      // SysHaloVar, jacobi_constant, finite12, halo_start, halo_crossing
+#include "halo_common.hpp"
 
 namespace lto {
 
 template <int METHOD>
 __global__ __launch_bounds__(64) void k_halo_correct(const HaloCorrectArgs a) {
-  const int gid = blockIdx.x * 64 + threadIdx.x;
-  const int g = gid >> 3, c = gid & 7;
-  const int gbase = threadIdx.x & ~7;
-  const int b = (g < a.B) ? g : a.B - 1;         // a group beyond the batch shadows the last orbit
-  const int col = (c < 6) ? c : 0;
-  const double colw = (c < 6) ? 1.0 : 0.0;
+  const GroupLane<int> L = group_lane<6, 1>(a.B);
+  const int b = L.rec;
   SysHaloVar sys;
   sys.MU = a.MU;
   double x0 = a.seed[6 * (long)b + 0], z0 = a.seed[6 * (long)b + 2], vy0 = a.seed[6 * (long)b + 4];
   const int iu = (a.mode == LTO_HALO_HOLD_X0) ? 2 : 0;  // the position unknown: x0 (hold z0), z0 (hold x0); planar: none
   const bool planar = a.mode == LTO_HALO_PLANAR;
-  const bool store = (g < a.B) && (c == 0);
   double* hist = a.hist + (long)(a.max_iter + 1) * b;
 
   // per-lane flags are doubles (dop853_lane.hpp, DESIGN.md "Compiler hazards")
@@ -45,33 +37,17 @@ __global__ __launch_bounds__(64) void k_halo_correct(const HaloCorrectArgs a) {
     if (!((s - s) == 0.0) || vy0 == 0.0 || (planar && z0 != 0.0)) status = 2.0;
   }
   while (status < 0.0) {
-    const double xs[6] = {x0, 0.0, z0, 0.0, vy0, 0.0};
-    double y[12], yc[12];
-    halo_start(xs, col, y);
-    const double side = (vy0 > 0.0) ? 1.0 : -1.0;
+    double yc[12];
     double found = 0.0;
     if (METHOD == M_RK4) {
-      const double h = a.t_max / (double)a.steps;
-      for (int k = 0; k < a.steps; ++k) {
-        double ys[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) ys[i] = y[i];
-        rk4_step(sys, h, y);
-        if (!(side * y[1] > 0.0)) {
-          if (y[1] == y[1]) {
-            tc = halo_crossing(__builtin_fma((double)k, h, 0.0), h, side, [&](const double th, double (&yt)[12]) {
-#pragma unroll
-              for (int i = 0; i < 12; ++i) yt[i] = ys[i];
-              rk4_step(sys, th, yt);
-            }, yc);
-            found = 1.0;
-          }
-          break;
-        }
-      }
-    } else {
+      found = halo_return_rk4(sys, x0, z0, vy0, L.col, a, tc, yc);
+    } else {                                     // halo_return_rk4's rule under the group driver (halo_common.hpp: why in place)
+      const double xs[6] = {x0, 0.0, z0, 0.0, vy0, 0.0};
+      double y[12];
+      halo_start(xs, L.col, y);
+      const double side = (vy0 > 0.0) ? 1.0 : -1.0;
       int na = 0, nr = 0;
-      (void)run_dop853_group<SysHaloVar, 6, 6>(sys, a.t_max, a.rtol, a.atol, a.max_steps, colw, y, na, nr,
+      (void)run_dop853_group<SysHaloVar, 6, 6>(sys, a.t_max, a.rtol, a.atol, a.max_steps, L.colw, y, na, nr,
           [&](const double t, const double h, const double (&ys)[12], double (&K)[13][12], const double (&yn)[12]) -> double {
         if (side * yn[1] > 0.0) return 0.0;
         if (yn[1] == yn[1]) {
@@ -87,18 +63,17 @@ __global__ __launch_bounds__(64) void k_halo_correct(const HaloCorrectArgs a) {
     if (found == 0.0 || !finite12(yc)) { status = 2.0; break; }
     // the residual at the crossing
     res = planar ? fabs(yc[3]) : fmax(fabs(yc[3]), fabs(yc[5]));
-    if (store) hist[it] = res;
+    if (L.lead) hist[it] = res;
     nrec = it + 1;
     if (res < a.tol) { status = 0.0; break; }
     if (it >= a.max_iter) { status = 1.0; break; }
-    // f at the crossing and the entries of Phi the step reads: row r of column j is component 6 + r of lane gbase + j
+    // f at the crossing and the 2 x 2 Jacobian: the columns of DF in the position unknown and in vy0
     double f[12];
     sys.rhs(yc, f);
-    const double p1u = __shfl(yc[7], gbase + iu, 64), p3u = __shfl(yc[9], gbase + iu, 64), p5u = __shfl(yc[11], gbase + iu, 64);
-    const double p14 = __shfl(yc[7], gbase + 4, 64), p34 = __shfl(yc[9], gbase + 4, 64), p54 = __shfl(yc[11], gbase + 4, 64);
     const double w3 = f[3] / f[1], w5 = f[5] / f[1];
-    const double j00 = __builtin_fma(-w3, p1u, p3u), j01 = __builtin_fma(-w3, p14, p34);
-    const double j10 = __builtin_fma(-w5, p1u, p5u), j11 = __builtin_fma(-w5, p14, p54);
+    double j00, j10, j01, j11, p1;
+    halo_df_column(yc, w3, w5, L.gbase, iu, j00, j10, p1);
+    halo_df_column(yc, w3, w5, L.gbase, 4, j01, j11, p1);
     if (planar) {
       if (!(fabs(j01) > 0.0) || !((j01 - j01) == 0.0)) { status = 3.0; break; }
       vy0 -= yc[3] / j01;
@@ -113,37 +88,17 @@ __global__ __launch_bounds__(64) void k_halo_correct(const HaloCorrectArgs a) {
     }
     ++it;
   }
-  if (store) {
-    const bool fail = status >= 2.0;
-    const double nan = __builtin_nan("");
-    double* so = a.state + 6 * (long)b;
-    so[0] = fail ? nan : x0; so[1] = fail ? nan : 0.0; so[2] = fail ? nan : z0;
-    so[3] = fail ? nan : 0.0; so[4] = fail ? nan : vy0; so[5] = fail ? nan : 0.0;
-    a.period[b] = fail ? nan : 2.0 * tc;
-    a.resid[b] = fail ? nan : res;
-    a.iters[b] = it;
-    a.status[b] = (int)status;
-    for (int k = nrec; k <= a.max_iter; ++k) hist[k] = nan;
-  }
+  if (L.lead) halo_member_store(a, b, hist, x0, z0, vy0, tc, res, it, nrec, status);
 }
 
 hipError_t launch_halo_correct(int method, const HaloCorrectArgs& a, hipStream_t st) {
-  const dim3 grid((unsigned)(((long)a.B * kGroupLanes + 63) / 64));
-  if (method == M_RK4) hipLaunchKernelGGL(k_halo_correct<M_RK4>, grid, dim3(64), 0, st, a);
-  else if (method == M_DOP853_ADAPTIVE) hipLaunchKernelGGL(k_halo_correct<M_DOP853_ADAPTIVE>, grid, dim3(64), 0, st, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return launch_by_method(method, k_halo_correct<M_RK4>, k_halo_correct<M_DOP853_ADAPTIVE>, (long)a.B * kGroupLanes, a, st);
 }
 
 template <int METHOD>
 __global__ __launch_bounds__(64) void k_halo_table(const HaloTableArgs a) {
-  const int gid = blockIdx.x * 64 + threadIdx.x;
-  const int g = gid >> 3, c = gid & 7;
-  const int gbase = threadIdx.x & ~7;
-  const int b = (g < a.B) ? g : a.B - 1;
-  const int col = (c < 6) ? c : 0;
-  const double colw = (c < 6) ? 1.0 : 0.0;
-  const bool store = (g < a.B) && (c == 0);
+  const GroupLane<int> L = group_lane<6, 1>(a.B);
+  const int b = L.rec, gbase = L.gbase;
   SysHaloVar sys;
   sys.MU = a.MU;
   double xs[6];
@@ -152,11 +107,11 @@ __global__ __launch_bounds__(64) void k_halo_table(const HaloTableArgs a) {
   const double P = a.period[b];
   const int n = a.n;
   double y[12];
-  halo_start(xs, col, y);
+  halo_start(xs, L.col, y);
   const double C0 = jacobi_constant(a.MU, y);
   double drift = 0.0;
   double* Xb = a.X + 6 * (long)n * b;
-  if (store) {
+  if (L.lead) {
 #pragma unroll
     for (int q = 0; q < 6; ++q) Xb[q] = y[q];
   }
@@ -176,7 +131,7 @@ __global__ __launch_bounds__(64) void k_halo_table(const HaloTableArgs a) {
       }
     } else {
       int na = 0, nr = 0;
-      const double done = run_dop853_group<SysHaloVar, 6, 6>(sys, span, a.rtol, a.atol, a.max_steps, colw, y, na, nr,
+      const double done = run_dop853_group<SysHaloVar, 6, 6>(sys, span, a.rtol, a.atol, a.max_steps, L.colw, y, na, nr,
           [](const double, const double, const double (&)[12], double (&)[13][12], const double (&)[12]) -> double { return 0.0; });
       if (done == 0.0 || span == 0.0) {           // a period that is not positive has no table
 #pragma unroll
@@ -185,7 +140,7 @@ __global__ __launch_bounds__(64) void k_halo_table(const HaloTableArgs a) {
     }
     const double dC = fabs(jacobi_constant(a.MU, y) - C0);
     drift = (dC > drift || dC != dC) ? dC : drift;     // a NaN stays
-    if (store) {
+    if (L.lead) {
 #pragma unroll
       for (int q = 0; q < 6; ++q) Xb[6 * (long)i + q] = y[q];
     }
@@ -202,12 +157,12 @@ __global__ __launch_bounds__(64) void k_halo_table(const HaloTableArgs a) {
     }
   }
   const bool ok = finite12(y) && ((tr2 - tr2) == 0.0);
-  if ((g < a.B) && (c < 6)) {
-    double* Mb = a.M + 36 * (long)b + 6 * c;
+  if (L.column) {
+    double* Mb = a.M + 36 * (long)b + 6 * L.c;
 #pragma unroll
     for (int r = 0; r < 6; ++r) Mb[r] = y[6 + r];
   }
-  if (store) {
+  if (L.lead) {
     double cl = 0.0;
 #pragma unroll
     for (int q = 0; q < 6; ++q) cl = fmax(cl, fabs(y[q] - xs[q]));
@@ -226,11 +181,7 @@ __global__ __launch_bounds__(64) void k_halo_table(const HaloTableArgs a) {
 }
 
 hipError_t launch_halo_table(int method, const HaloTableArgs& a, hipStream_t st) {
-  const dim3 grid((unsigned)(((long)a.B * kGroupLanes + 63) / 64));
-  if (method == M_RK4) hipLaunchKernelGGL(k_halo_table<M_RK4>, grid, dim3(64), 0, st, a);
-  else if (method == M_DOP853_ADAPTIVE) hipLaunchKernelGGL(k_halo_table<M_DOP853_ADAPTIVE>, grid, dim3(64), 0, st, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return launch_by_method(method, k_halo_table<M_RK4>, k_halo_table<M_DOP853_ADAPTIVE>, (long)a.B * kGroupLanes, a, st);
 }
 
 }  // namespace lto

@@ -1,67 +1,22 @@
 // kernels_halo_arclength.hip -- families of periodic orbits of the CRTBP by pseudo-arclength continuation, B families side by side,
 // each marched through T members inside one launch with its own step control, gfx950.
 //
-// The mapping and the flight are k_halo_target's (kernels_halo_target.hip): one GROUP of 8 adjacent lanes per orbit, lanes 0, 1, 2
-// carry columns 0, 2, 4 of Phi = dx/dx0, lanes 3..7 shadow lane 0 and add nothing to the error norm.  Everything a group decides it
-// decides from values every lane of it holds in the same bits.  A group beyond the batch shadows the last orbit.  No LDS, plain
-// vector stores, flags are per-lane doubles.
+// The mapping is k_halo_target's (halo_common.hpp group_lane): lanes 0, 1, 2 of a group carry columns 0, 2, 4 of Phi = dx/dx0.
+// Everything a group decides it decides from values every lane of it holds in the same bits.  No LDS, plain vector stores, flags
+// are per-lane doubles.
 //
-// With u = (x0, z0, vy0), per flight: F = (vx, vz) at the first return to y = 0 and
-//   DF = Phi[(3,5), j] - f[(3,5)] Phi[1, j] / f[1],   j = 0, 2, 4            (planar: the z0 row and column are the identity's)
+// With u = (x0, z0, vy0), per flight (halo_return_rk4, or the same rule under the group driver): F = (vx, vz) at the first return
+// to y = 0, DF from halo_df_column (planar: halo_planar_patch) and
 //   c = DF_0 x DF_1,   n = |c|_2,   sigma = sign(c . t_row),   t = sigma c / n,   det = sigma n
 // A member is the step from u_prev along the row vector t_row: u_pred = u_prev + ds t_row (product and sum rounded one by one), then
 //   u <- u - [DF; t_row]^-1 (F; t_row . (u - u_pred))
-// by the LU with partial pivoting by selects of k_halo_target.  An attempt that does not converge, or whose tangent turns beyond
-// cos_min, is tried again from the same u_prev with half the step; after a fast member the step grows.
+// by newton_solve3.  An attempt that does not converge, or whose tangent turns beyond cos_min, is tried again from the same u_prev
+// with half the step; after a fast member the step grows.
 #include "halo_common.hpp"
 
 namespace lto {
 
 namespace {
-
-__device__ __forceinline__ void swap_if(const bool p, double& u, double& v) {
-  const double t = p ? v : u;
-  v = p ? u : v;
-  u = t;
-}
-
-// d = J^-1 r (kernels_halo_target.hip's, kept in step with it).  Returns 1.0 for a singular step -- |det| <= sing_tol x the product
-// of the row 2-norms, or det not finite -- else 0.0.
-__device__ __forceinline__ double newton_solve3(const double (&J)[3][3], const double (&r)[3], const double sing_tol, double (&d)[3]) {
-  const double m0 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-  const double m1 = J[1][0] * J[2][2] - J[1][2] * J[2][0];
-  const double m2 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-  const double det = J[0][0] * m0 - J[0][1] * m1 + J[0][2] * m2;
-  double prod = 1.0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) prod *= sqrt(__builtin_fma(J[i][0], J[i][0], __builtin_fma(J[i][1], J[i][1], J[i][2] * J[i][2])));
-  d[0] = d[1] = d[2] = __builtin_nan("");
-  if (!(fabs(det) > sing_tol * prod) || !((det - det) == 0.0)) return 1.0;
-  double A[3][4];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { A[i][0] = J[i][0]; A[i][1] = J[i][1]; A[i][2] = J[i][2]; A[i][3] = r[i]; }
-  // column 0: the largest of |A[.][0]| to row 0
-  bool p = fabs(A[1][0]) > fabs(A[0][0]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) swap_if(p, A[0][j], A[1][j]);
-  p = fabs(A[2][0]) > fabs(A[0][0]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) swap_if(p, A[0][j], A[2][j]);
-  const double l1 = A[1][0] / A[0][0], l2 = A[2][0] / A[0][0];
-#pragma unroll
-  for (int j = 1; j < 4; ++j) { A[1][j] = __builtin_fma(-l1, A[0][j], A[1][j]); A[2][j] = __builtin_fma(-l2, A[0][j], A[2][j]); }
-  // column 1
-  p = fabs(A[2][1]) > fabs(A[1][1]);
-#pragma unroll
-  for (int j = 1; j < 4; ++j) swap_if(p, A[1][j], A[2][j]);
-  const double l3 = A[2][1] / A[1][1];
-#pragma unroll
-  for (int j = 2; j < 4; ++j) A[2][j] = __builtin_fma(-l3, A[1][j], A[2][j]);
-  d[2] = A[2][3] / A[2][2];
-  d[1] = __builtin_fma(-A[1][2], d[2], A[1][3]) / A[1][1];
-  d[0] = __builtin_fma(-A[0][1], d[1], __builtin_fma(-A[0][2], d[2], A[0][3])) / A[0][0];
-  return 0.0;
-}
 
 // u + ds t, product and sum rounded on their own
 __device__ __forceinline__ double predictor_point(const double u, const double ds, const double t) {
@@ -81,14 +36,9 @@ __device__ __forceinline__ bool finite1(const double v) { return (v - v) == 0.0;
 
 template <int METHOD>
 __global__ __launch_bounds__(64) void k_halo_arclength(const HaloArclengthArgs a) {
-  const int gid = blockIdx.x * 64 + threadIdx.x;
-  const int g = gid >> 3, c = gid & 7;
-  const int gbase = threadIdx.x & ~7;
-  const int b = (g < a.B) ? g : a.B - 1;         // a group beyond the batch shadows the last orbit
-  const int col = (c < 3) ? 2 * c : 0;           // lanes 0, 1, 2: columns 0, 2, 4
-  const double colw = (c < 3) ? 1.0 : 0.0;
+  const GroupLane<int> L = group_lane<3, 2>(a.B);      // lanes 0, 1, 2: columns 0, 2, 4
+  const int b = L.rec;
   const bool planar = a.planar != 0;
-  const bool store = (g < a.B) && (c == 0);
   const double nan = __builtin_nan("");
   SysHaloVar sys;
   sys.MU = a.MU;
@@ -124,33 +74,17 @@ __global__ __launch_bounds__(64) void k_halo_arclength(const HaloArclengthArgs a
         if (!finite1(s) || u[2] == 0.0 || (planar && u[1] != 0.0)) status = 2.0;
       }
       while (status < 0.0) {                     // flights of the attempt
-        const double xs[6] = {u[0], 0.0, u[1], 0.0, u[2], 0.0};
-        double y[12], yc[12];
-        halo_start(xs, col, y);
-        const double side = (u[2] > 0.0) ? 1.0 : -1.0;
+        double yc[12];
         double found = 0.0;
         if (METHOD == M_RK4) {
-          const double h = a.t_max / (double)a.steps;
-          for (int n = 0; n < a.steps; ++n) {
-            double ys[12];
-#pragma unroll
-            for (int i = 0; i < 12; ++i) ys[i] = y[i];
-            rk4_step(sys, h, y);
-            if (!(side * y[1] > 0.0)) {
-              if (y[1] == y[1]) {
-                tc = halo_crossing(__builtin_fma((double)n, h, 0.0), h, side, [&](const double th, double (&yt)[12]) {
-#pragma unroll
-                  for (int i = 0; i < 12; ++i) yt[i] = ys[i];
-                  rk4_step(sys, th, yt);
-                }, yc);
-                found = 1.0;
-              }
-              break;
-            }
-          }
-        } else {
+          found = halo_return_rk4(sys, u[0], u[1], u[2], L.col, a, tc, yc);
+        } else {                                     // halo_return_rk4's rule under the group driver (halo_common.hpp: why in place)
+          const double xs[6] = {u[0], 0.0, u[1], 0.0, u[2], 0.0};
+          double y[12];
+          halo_start(xs, L.col, y);
+          const double side = (u[2] > 0.0) ? 1.0 : -1.0;
           int na = 0, nr = 0;
-          (void)run_dop853_group<SysHaloVar, 6, 3>(sys, a.t_max, a.rtol, a.atol, a.max_steps, colw, y, na, nr,
+          (void)run_dop853_group<SysHaloVar, 6, 3>(sys, a.t_max, a.rtol, a.atol, a.max_steps, L.colw, y, na, nr,
               [&](const double t, const double h, const double (&ys)[12], double (&K)[13][12], const double (&yn)[12]) -> double {
             if (side * yn[1] > 0.0) return 0.0;
             if (yn[1] == yn[1]) {
@@ -164,22 +98,17 @@ __global__ __launch_bounds__(64) void k_halo_arclength(const HaloArclengthArgs a
           });
         }
         if (found == 0.0 || !finite12(yc)) { status = 2.0; break; }
-        // DF at the crossing: row r of column 2 j of Phi is component 6 + r of lane gbase + j
+        // DF at the crossing from the group's three columns; the third row is set below, before the solve
         double f[12];
         sys.rhs(yc, f);
         const double w3 = f[3] / f[1], w5 = f[5] / f[1];
         double J[3][3], r[3] = {yc[3], yc[5], 0.0}, d[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-          const double p1 = __shfl(yc[7], gbase + j, 64), p3 = __shfl(yc[9], gbase + j, 64), p5 = __shfl(yc[11], gbase + j, 64);
-          J[0][j] = __builtin_fma(-w3, p1, p3);
-          J[1][j] = __builtin_fma(-w5, p1, p5);
+          double p1;
+          halo_df_column(yc, w3, w5, L.gbase, j, J[0][j], J[1][j], p1);
         }
-        if (planar) {
-          J[0][1] = 0.0;
-          J[1][0] = 0.0; J[1][1] = 1.0; J[1][2] = 0.0;
-          r[1] = 0.0;
-        }
+        if (planar) halo_planar_patch(J, r);
         // the tangent of this flight's DF, not yet oriented
         const double cr[3] = {__builtin_fma(J[0][1], J[1][2], -(J[0][2] * J[1][1])), __builtin_fma(J[0][2], J[1][0], -(J[0][0] * J[1][2])),
                               __builtin_fma(J[0][0], J[1][1], -(J[0][1] * J[1][0]))};
@@ -200,7 +129,7 @@ __global__ __launch_bounds__(64) void k_halo_arclength(const HaloArclengthArgs a
         r[2] = dot3(tw, du);
         res = fmax(fabs(r[0]), fabs(r[2]));
         if (!planar) res = fmax(res, fabs(r[1]));
-        if (store) hist[it] = res;
+        if (L.lead) hist[it] = res;
         nrec = it + 1;
         const bool conv = res < a.tol;
         if (conv || it >= a.max_iter) {
@@ -228,22 +157,15 @@ __global__ __launch_bounds__(64) void k_halo_arclength(const HaloArclengthArgs a
     }
 
     const bool fail = status >= 2.0;
-    if (store) {
-      double* so = a.state + 6 * m;
-      so[0] = fail ? nan : u[0]; so[1] = fail ? nan : 0.0; so[2] = fail ? nan : u[1];
-      so[3] = fail ? nan : 0.0; so[4] = fail ? nan : u[2]; so[5] = fail ? nan : 0.0;
+    if (L.lead) {
+      halo_member_store(a, m, hist, u[0], u[1], u[2], tc, res, it, nrec, status);
       double* to = a.tangent + 3 * m;
       to[0] = fail ? nan : tn[0]; to[1] = fail ? nan : tn[1]; to[2] = fail ? nan : tn[2];
       const double xs[12] = {u[0], 0.0, u[1], 0.0, u[2], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       a.det[m] = fail ? nan : det;
       a.ds[m] = dsa;
-      a.period[m] = fail ? nan : 2.0 * tc;
       a.jacobi[m] = fail ? nan : jacobi_constant(MU, xs);
-      a.resid[m] = fail ? nan : res;
       a.halvings[m] = halv;
-      a.iters[m] = it;
-      a.status[m] = (int)status;
-      for (int n = nrec; n <= a.max_iter; ++n) hist[n] = nan;
     }
     if (status != 0.0) {
       dead = 1.0;                                // the rest of this orbit's members: NaN, status 2
@@ -259,11 +181,7 @@ __global__ __launch_bounds__(64) void k_halo_arclength(const HaloArclengthArgs a
 }
 
 hipError_t launch_halo_arclength(int method, const HaloArclengthArgs& a, hipStream_t st) {
-  const dim3 grid((unsigned)(((long)a.B * kGroupLanes + 63) / 64));
-  if (method == M_RK4) hipLaunchKernelGGL(k_halo_arclength<M_RK4>, grid, dim3(64), 0, st, a);
-  else if (method == M_DOP853_ADAPTIVE) hipLaunchKernelGGL(k_halo_arclength<M_DOP853_ADAPTIVE>, grid, dim3(64), 0, st, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return launch_by_method(method, k_halo_arclength<M_RK4>, k_halo_arclength<M_DOP853_ADAPTIVE>, (long)a.B * kGroupLanes, a, st);
 }
 
 }  // namespace lto

@@ -23,18 +23,12 @@ namespace lto {
 
 template <int METHOD>
 __global__ __launch_bounds__(64) void k_halo_stm(const HaloStmArgs a) {
-  const long gid = (long)blockIdx.x * 64 + threadIdx.x;
-  const long g = gid >> 3;
-  const int c = (int)(gid & 7);
-  const long n_rec = (long)a.P * a.B;
-  const long rec = (g < n_rec) ? g : n_rec - 1;  // a group beyond the last record shadows it
+  const GroupLane<long> L = group_lane<6, 1>((long)a.P * a.B);
+  const long rec = L.rec;
   const int b = (int)(rec / a.P), j = (int)(rec - (long)b * a.P);
-  const int col = (c < 6) ? c : 0;
-  const double colw = (c < 6) ? 1.0 : 0.0;
-  const bool lead = (g < n_rec) && (c == 0), column = (g < n_rec) && (c < 6);
   const int K = a.K;
   double* Xo = a.X + 6 * rec;
-  double* Pc = a.Phi + 36 * (long)K * rec + 6 * col;   // this lane's column of block 0
+  double* Pc = a.Phi + 36 * (long)K * rec + 6 * L.col;   // this lane's column of block 0
   double* Xt = a.Xt ? a.Xt + 6 * (long)K * rec : nullptr;
   double xs[6];
 #pragma unroll
@@ -68,14 +62,14 @@ __global__ __launch_bounds__(64) void k_halo_stm(const HaloStmArgs a) {
     if (!finite_all(xs)) fail = 1.0;
   }
   if (fail == 0.0) {
-    if (lead) {
+    if (L.lead) {
 #pragma unroll
       for (int q = 0; q < 6; ++q) Xo[q] = xs[q];
     }
     SysHaloVar sys;
     sys.MU = a.MU;
     double y[12];
-    halo_start(xs, col, y);
+    halo_start(xs, L.col, y);
     double hprev = 0.0;
     for (int k = 0; k < K; ++k) {
       const double hk = a.horizon[k];
@@ -88,18 +82,18 @@ __global__ __launch_bounds__(64) void k_halo_stm(const HaloStmArgs a) {
         nacc += a.steps;
       } else {
         int na = 0, nr = 0;
-        done = run_dop853_group<SysHaloVar, 6, 6>(sys, span, a.rtol, a.atol, a.max_steps, colw, y, na, nr,
+        done = run_dop853_group<SysHaloVar, 6, 6>(sys, span, a.rtol, a.atol, a.max_steps, L.colw, y, na, nr,
             [](const double, const double, const double (&)[12], double (&)[13][12], const double (&)[12]) -> double { return 0.0; });
         nacc += na; nrej += nr;
       }
       // one decision for the group: a column that is not finite in any lane fails the record in all of them
       const double bad = group8_sum(finite12(y) ? 0.0 : 1.0);
       if (done == 0.0 || bad != 0.0) { fail = 1.0; break; }
-      if (column) {
+      if (L.column) {
 #pragma unroll
         for (int r = 0; r < 6; ++r) Pc[36 * (long)k + r] = y[6 + r];
       }
-      if (lead && Xt) {
+      if (L.lead && Xt) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) Xt[6 * (long)k + q] = y[q];
       }
@@ -108,21 +102,21 @@ __global__ __launch_bounds__(64) void k_halo_stm(const HaloStmArgs a) {
   if (fail != 0.0) {
     const double nan = __builtin_nan("");
     for (int k = 0; k < K; ++k) {
-      if (column) {
+      if (L.column) {
 #pragma unroll
         for (int r = 0; r < 6; ++r) Pc[36 * (long)k + r] = nan;
       }
-      if (lead && Xt) {
+      if (L.lead && Xt) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) Xt[6 * (long)k + q] = nan;
       }
     }
-    if (lead) {
+    if (L.lead) {
 #pragma unroll
       for (int q = 0; q < 6; ++q) Xo[q] = nan;
     }
   }
-  if (lead) {
+  if (L.lead) {
     if (a.accepted) a.accepted[rec] = nacc;
     if (a.rejected) a.rejected[rec] = nrej;
     a.status[rec] = (fail != 0.0) ? 2 : 0;
@@ -130,11 +124,7 @@ __global__ __launch_bounds__(64) void k_halo_stm(const HaloStmArgs a) {
 }
 
 hipError_t launch_halo_stm(int method, const HaloStmArgs& a, hipStream_t st) {
-  const dim3 grid((unsigned)(((long)a.P * a.B * kGroupLanes + 63) / 64));
-  if (method == M_RK4) hipLaunchKernelGGL(k_halo_stm<M_RK4>, grid, dim3(64), 0, st, a);
-  else if (method == M_DOP853_ADAPTIVE) hipLaunchKernelGGL(k_halo_stm<M_DOP853_ADAPTIVE>, grid, dim3(64), 0, st, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return launch_by_method(method, k_halo_stm<M_RK4>, k_halo_stm<M_DOP853_ADAPTIVE>, (long)a.P * a.B * kGroupLanes, a, st);
 }
 
 }  // namespace lto

@@ -312,10 +312,7 @@ hipError_t launch_manifold_seeds(int method, const ManifoldSeedArgs& a, hipStrea
   hipLaunchKernelGGL(k_manifold_eigen, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const dim3 grid((unsigned)((2L * a.P * a.B + 63) / 64));
-  if (method == M_RK4) hipLaunchKernelGGL(k_manifold_transport<M_RK4>, grid, dim3(64), 0, st, a);
-  else hipLaunchKernelGGL(k_manifold_transport<M_DOP853_ADAPTIVE>, grid, dim3(64), 0, st, a);
-  e = hipGetLastError();
+  e = launch_by_method(method, k_manifold_transport<M_RK4>, k_manifold_transport<M_DOP853_ADAPTIVE>, 2L * a.P * a.B, a, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_manifold_starts, dim3((unsigned)(((long)a.P * a.B + 63) / 64)), dim3(64), 0, st, a);
   return hipGetLastError();
@@ -489,11 +486,7 @@ __global__ __launch_bounds__(64) void k_section_flight(const SectionFlightArgs a
 }
 
 hipError_t launch_section_flight(int method, const SectionFlightArgs& a, hipStream_t st) {
-  const dim3 grid((unsigned)((a.N + 63) / 64));
-  if (method == M_RK4) hipLaunchKernelGGL(k_section_flight<M_RK4>, grid, dim3(64), 0, st, a);
-  else if (method == M_DOP853_ADAPTIVE) hipLaunchKernelGGL(k_section_flight<M_DOP853_ADAPTIVE>, grid, dim3(64), 0, st, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return launch_by_method(method, k_section_flight<M_RK4>, k_section_flight<M_DOP853_ADAPTIVE>, a.N, a, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- nearest partner

@@ -86,11 +86,7 @@ __global__ __launch_bounds__(64) void k_stack_arc(const StackArcArgs a) {
 }
 
 hipError_t launch_stack_arc(int method, const StackArcArgs& a, hipStream_t st) {
-  const dim3 grid((a.B + 63) / 64);
-  if (method == M_RK4) hipLaunchKernelGGL(k_stack_arc<M_RK4>, grid, dim3(64), 0, st, a);
-  else if (method == M_DOP853_ADAPTIVE) hipLaunchKernelGGL(k_stack_arc<M_DOP853_ADAPTIVE>, grid, dim3(64), 0, st, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return launch_by_method(method, k_stack_arc<M_RK4>, k_stack_arc<M_DOP853_ADAPTIVE>, a.B, a, st);
 }
 
 // ---- find_tau as a scan of the candidate table: one workgroup per start, the rule of k_find_tau (kernels_addtime.hip) -- the first

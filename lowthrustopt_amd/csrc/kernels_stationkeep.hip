@@ -279,18 +279,9 @@ __global__ __launch_bounds__(64) void k_stationkeep_flight(const StationFlightAr
   a.status[b] = (int)st;
 }
 
-template <int METHOD>
-static hipError_t launch_stationkeep_method(const StationFlightArgs& a, hipStream_t st) {
-  const dim3 grid((unsigned)((a.B + 63) / 64));
-  if (a.n_orb == 1) hipLaunchKernelGGL((k_stationkeep_flight<METHOD, true>), grid, dim3(64), 0, st, a);
-  else hipLaunchKernelGGL((k_stationkeep_flight<METHOD, false>), grid, dim3(64), 0, st, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_stationkeep_flight(int method, const StationFlightArgs& a, hipStream_t st) {
-  if (method == M_RK4) return launch_stationkeep_method<M_RK4>(a, st);
-  if (method == M_DOP853_ADAPTIVE) return launch_stationkeep_method<M_DOP853_ADAPTIVE>(a, st);
-  return hipErrorInvalidValue;
+  if (a.n_orb == 1) return launch_by_method(method, k_stationkeep_flight<M_RK4, true>, k_stationkeep_flight<M_DOP853_ADAPTIVE, true>, a.B, a, st);
+  return launch_by_method(method, k_stationkeep_flight<M_RK4, false>, k_stationkeep_flight<M_DOP853_ADAPTIVE, false>, a.B, a, st);
 }
 
 }  // namespace lto
