@@ -389,8 +389,10 @@ def pool(cls):
     return tuple(out)
 
 
-def pick(cls, on_s=None, nroots=None, on_e=None, k=0):
-    """The k-th (cyclically) admitted template of the class with these properties (None: any; nroots may be a tuple)."""
+def pick(cls, on_s=None, nroots=None, on_e=None, k=0, src=None):
+    """The k-th (cyclically) admitted template of the class with these properties (None: any; nroots may be a tuple).  src: the
+    provider of pool and klass (None: the 12-row templates of this module; thrust_mass_reference.Pools: the lifted ones)."""
+    pool, klass = (src or SRC12).pool, (src or SRC12).klass
     nr = None if nroots is None else (nroots if isinstance(nroots, tuple) else (nroots,))
     hit = [tid for tid in pool(cls) if (on_s is None or klass(tid)[0] == on_s) and (nr is None or klass(tid)[1] in nr)
            and (on_e is None or klass(tid)[2] == on_e)]
@@ -447,75 +449,97 @@ def compact_direct(segs, t, max_events):
 
 
 # ---- patterns: lists of template ids, each built to realise one feature (tests/test_thrust_arcs_host.py holds them to it) ----
+# Every builder takes src, the provider of pick / klass / pool / FIVE: None is this module's 12-row templates (SRC12).
 NSEGS = (1, 2, 63, 64, 65, 128, 129)
 
 
-def pat_quiet(nseg, on, cls="p1"):
-    return [pick(cls, on, 0, on, k) for k in range(nseg)]
+class _Src12:
+    """The 12-row templates as a pool provider."""
+    FIVE = FIVE
+    pool = staticmethod(pool)
+    klass = staticmethod(klass)
+
+    def pick(self, *a, **kw):
+        return pick(*a, **kw)
 
 
-def pat_sparse(nseg, where, cls="p1", special=None):
+SRC12 = _Src12()
+
+
+def pat_quiet(nseg, on, cls="p1", src=None):
+    src = src or SRC12
+    return [src.pick(cls, on, 0, on, k) for k in range(nseg)]
+
+
+def pat_sparse(nseg, where, cls="p1", special=None, src=None):
     """Crossings (one each) in the segments of `where` only, every other segment quiet and no join; special: {index: template}
     placed as they are (a join ahead of one where its start state differs)."""
+    src = src or SRC12
     special = special or {}
-    cur, out = klass(pick(cls, None, 1))[0], []
+    cur, out = src.klass(src.pick(cls, None, 1))[0], []
     for i in range(nseg):
         if i in special:
             tid = special[i]
         elif i in where:
-            tid = pick(cls, cur, 1, None, len(out))
+            tid = src.pick(cls, cur, 1, None, len(out))
         else:
-            tid = pick(cls, cur, 0, cur, len(out))
+            tid = src.pick(cls, cur, 0, cur, len(out))
         out.append(tid)
-        cur = klass(tid)[2]
+        cur = src.klass(tid)[2]
     return out
 
 
-def pat_edges(nseg):
-    return pat_sparse(nseg, {0, 63, 64, nseg - 1})
+def pat_edges(nseg, src=None):
+    return pat_sparse(nseg, {0, 63, 64, nseg - 1}, src=src)
 
 
-def pat_boundary_joins(nseg):
+def pat_boundary_joins(nseg, src=None):
     """All on up to node 64, off from there, on again from node 128: the only events are the joins at t[64] (and t[128])."""
-    return [pick("p1", s, 0, s, i) for i in range(nseg) for s in [1 if (i < 64 or i >= 128) else 0]]
+    src = src or SRC12
+    return [src.pick("p1", s, 0, s, i) for i in range(nseg) for s in [1 if (i < 64 or i >= 128) else 0]]
 
 
-def pat_dense(nseg, cls="p1"):
+def pat_dense(nseg, cls="p1", src=None):
     """Every segment a one- or two-crossing template, joins where they fall -- but a join forced at the nodes 64 and 128, where
     the compaction changes chunks, and none at their neighbours 63, 65 and 127."""
+    src = src or SRC12
     out, cur = [], None
     for i in range(nseg):
         want = None if cur is None else (1 - cur if i in (64, 128) else cur if i in (63, 65, 127) else None)
-        out.append(pick(cls, want, (1, 2), None, i))
-        cur = klass(out[-1])[2]
+        out.append(src.pick(cls, want, (1, 2), None, i))
+        cur = src.klass(out[-1])[2]
     return out
 
 
-def pat_holes(at, nseg=129):
+def pat_holes(at, nseg=129, src=None):
     """The five-crossing template at the indices `at`, a crossing in every fifth segment otherwise."""
-    return pat_sparse(nseg, set(range(2, nseg, 5)) - set(at), special={i: FIVE for i in at})
+    src = src or SRC12
+    return pat_sparse(nseg, set(range(2, nseg, 5)) - set(at), special={i: src.FIVE for i in at}, src=src)
 
 
-def pat_cycle(cls, nseg=65):
+def pat_cycle(cls, nseg=65, src=None):
     """The class's admitted templates in turn (the five-crossing one apart)."""
-    p = [tid for tid in pool(cls) if tid != FIVE]
+    src = src or SRC12
+    p = [tid for tid in src.pool(cls) if tid != src.FIVE]
     return [p[k % len(p)] for k in range(nseg)]
 
 
-def pat_prox(tid, nseg):
+def pat_prox(tid, nseg, src=None):
     """An end-proximity template alone, or as the last of nseg segments behind quiet ones of its start state."""
-    on = klass(tid)[0]
-    return [pick("p1", on, 0, on, k) for k in range(nseg - 1)] + [tid]
+    src = src or SRC12
+    on = src.klass(tid)[0]
+    return [src.pick("p1", on, 0, on, k) for k in range(nseg - 1)] + [tid]
 
 
-def pat_plumbing():
+def pat_plumbing(src=None):
     """Six 65-segment trajectories of different event counts for one call; 4 holds the five-crossing template."""
-    return [pat_dense(65), pat_edges(65), pat_quiet(65, 1), pat_cycle("p1"), pat_holes((30,), 65), pat_boundary_joins(65)]
+    return [pat_dense(65, src=src), pat_edges(65, src=src), pat_quiet(65, 1, src=src), pat_cycle("p1", src=src),
+            pat_holes((30,), 65, src=src), pat_boundary_joins(65, src=src)]
 
 
-def pat_shared_grid():
+def pat_shared_grid(src=None):
     """Six patterns of equal-length templates: one time grid serves them all."""
-    p = pool("p1u")
+    p = (src or SRC12).pool("p1u")
     return [[p[(k * (b + 1) + b) % len(p)] for k in range(65)] for b in range(6)]
 
 
