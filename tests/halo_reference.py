@@ -88,6 +88,19 @@ def correct(seed, mode, MU, tol=1e-12, max_iter=15, t_max=10.0, rtol=RTOL, atol=
         it += 1
 
 
+def count_is_safe(history, tol):
+    """No residual of a reference run lies within [tol / 10, 10 tol]: the device, whose residuals are this reference's to 1e-11 and
+    in practice to 1e-13, then stops at the same iteration, and its count is held to this one exactly, not to within one."""
+    return not any(0.1 * tol <= h <= 10.0 * tol for h in history)
+
+
+def same_count(iterations, ref_iterations, ref_history, tol):
+    """The device's iteration count against a reference run's: equal where the count is safe, within one elsewhere."""
+    if count_is_safe(ref_history, tol):
+        return int(iterations) == int(ref_iterations)
+    return abs(int(iterations) - int(ref_iterations)) <= 1
+
+
 def jacobi(state, MU):
     x, y, z, vx, vy, vz = state
     r1 = np.sqrt((x + MU) ** 2 + y * y + z * z)

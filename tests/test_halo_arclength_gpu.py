@@ -5,7 +5,8 @@ Bounds.  Device against reference, per case class on (states, tangents, periods,
 between (1e-13, 1e-14) and (1e-11, 1e-12) over the class's cases, rounded up to a power of ten (halo_arclength_reference.BOUNDS, with
 the spreads; tests/test_halo_arclength_host.py holds the spread to a tenth and vets every input as far from a decision's edge).  Only
 states, tangents, det, periods, iteration counts, ds_out and halvings are compared with the reference.  The step sizes and halving
-counts must be the reference's exactly; an iteration count may differ by one (a last residual near tol).
+counts must be the reference's exactly, and so must an iteration count unless a residual of the reference's run lies within
+[tol / 10, 10 tol] (halo_reference.same_count): there it may differ by one.
 
   class        spread state / tangent / period / det        bound                          device (MI355X, worst of B = 1, 9, 17)
   planar       1.4e-14 / 6.6e-13 / 3.3e-12 / 5.1e-11        1e-12 / 1e-11 / 1e-10 / 1e-9   6.7e-16 / 8.7e-15 / 4.6e-13 / 1.6e-12
@@ -55,7 +56,7 @@ def _against(r, b, ref, bound, label):
                       abs(r.det[k, b] - m.det) / abs(m.det)])
         worst = np.maximum(worst, e)
         assert np.all(e <= np.array(bound)), (label, k, b, e, bound)
-        assert abs(int(r.iterations[k, b]) - m.iterations) <= 1, (label, k, b, r.iterations[k, b], m.iterations)
+        assert HR.same_count(r.iterations[k, b], m.iterations, m.history, TOL), (label, k, b, r.iterations[k, b], m.iterations, m.history)
         assert r.ds[k, b] == m.ds and r.halvings[k, b] == m.halvings, (label, k, b, r.ds[k, b], m.ds, r.halvings[k, b], m.halvings)
         assert r.resid[k, b] < TOL and abs(r.jacobi[k, b] - HR.jacobi(r.state[:, k, b], MU)) <= 1e-14
         assert r.state[1, k, b] == 0.0 and r.state[3, k, b] == 0.0 and r.state[5, k, b] == 0.0
@@ -145,7 +146,8 @@ def test_ds_min_ends_one_family_beside_an_unchanged_neighbour(gpu_ctx):
     assert np.all(np.isnan(r.history[:, 1:, 0])) and np.all(r.iterations[1:, 0] == 0)
     # the attempt that was refused did converge: its history is kept
     n = int(r.iterations[0, 0]) + 1
-    assert abs(n - 1 - refs[0][0].iterations) <= 1 and np.all(np.isfinite(r.history[:n, 0, 0])) and r.history[n - 1, 0, 0] < TOL
+    assert HR.same_count(n - 1, refs[0][0].iterations, refs[0][0].history, TOL)
+    assert np.all(np.isfinite(r.history[:n, 0, 0])) and r.history[n - 1, 0, 0] < TOL
     _against(r, 1, refs[1], AR.BOUNDS[case.cls], "dsmin neighbour")
     single = _batched(_step_call(gpu_ctx, case, b=1))
     assert all(_same(r, k, 1, single, k, 0) for k in range(3))

@@ -98,7 +98,7 @@ def test_target_against_the_reference(gpu_ctx, planar, what, B):
         assert e_state <= b_state and e_P <= b_P
         assert e_q < TOL and resid[b] < TOL
         assert abs(jac[b] - HR.jacobi(state[:, b], MU)) <= 1e-14
-        assert abs(int(its[b]) - ref.iterations) <= 1
+        assert HR.same_count(its[b], ref.iterations, ref.history, TOL), (b, its[b], ref.history)
         assert state[1, b] == 0.0 and state[3, b] == 0.0 and state[5, b] == 0.0 and (not planar or state[2, b] == 0.0)
         n = int(its[b]) + 1                                # the history: one residual per flight, NaN past the last
         assert np.all(np.isfinite(hist[:n, b])) and np.all(np.isnan(hist[n:, b])) and hist[n - 1, b] == resid[b]
@@ -135,7 +135,7 @@ def test_march_to_a_common_jacobi_constant(gpu_ctx, K):
             assert rb.status[k, b] == 0 and ref[k].status == 0
             assert e_state <= b_state and e_P <= b_P
             assert abs(HR.jacobi(rb.state[:, k, b], MU) - targets[k, b]) < TOL and rb.resid[k, b] < TOL
-            assert abs(int(rb.iterations[k, b]) - ref[k].iterations) <= 1
+            assert HR.same_count(rb.iterations[k, b], ref[k].iterations, ref[k].history, TOL), (k, b, ref[k].history)
             # the member is the single call from the predictor's point, formed here from the call's own outputs
             if k == 0:
                 start = seeds[:, b]
@@ -156,7 +156,7 @@ def test_march_of_halo_orbit_1_to_the_jacobi_constant_of_orbit_2(gpu_ctx):
     for k in range(4):
         e_state, e_P = np.abs(r.state[:, k] - ref[k].state).max(), abs(r.period[k] - ref[k].period)
         print("member %d: state %.2e, P %.2e, iterations %d (reference %d)" % (k, e_state, e_P, r.iterations[k], ref[k].iterations))
-        assert r.status[k] == 0 and e_state <= b_state and e_P <= b_P and abs(int(r.iterations[k]) - ref[k].iterations) <= 1
+        assert r.status[k] == 0 and e_state <= b_state and e_P <= b_P and HR.same_count(r.iterations[k], ref[k].iterations, ref[k].history, TOL)
     # the family is a curve: the member of orbit 2's C is orbit 2
     assert np.abs(r.state[:, -1] - s2).max() <= b_state and abs(r.period[-1] - P2) <= b_P
     drv = drivers.halo_family_by(s1, targets, "jacobi", tol=TOL, ctx=gpu_ctx)
