@@ -112,8 +112,11 @@ __device__ __forceinline__ void sign_rule6(double (&v)[6]) {
 }
 
 // LU of C with partial pivoting, in place (L below the diagonal, unit diagonal implied); piv[k] = the row exchanged with row k.
-// The exchange runs over the rows below k with a predicate, so no index depends on data.  A pivot that is exactly 0 (the shift
-// is an eigenvalue to the last bit) is replaced by `tiny`: inverse iteration wants the direction, not the size.
+// The exchange runs over the rows below k with a predicate, so no index depends on data.  Only the columns from k on are
+// exchanged: the multipliers already stored left of them stay with the step that made them, which is what lu6_solve needs, since
+// it exchanges and eliminates step by step (exchanging them too would ask for all exchanges of x before the first elimination).
+// A pivot that is exactly 0 (the shift is an eigenvalue to the last bit) is replaced by `tiny`: inverse iteration wants the
+// direction, not the size.
 __device__ __forceinline__ void lu6(double (&C)[6][6], int (&piv)[6], const double tiny) {
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
@@ -129,7 +132,7 @@ __device__ __forceinline__ void lu6(double (&C)[6][6], int (&piv)[6], const doub
     for (int r = k + 1; r < 6; ++r) {
       const bool ex = (r == p);
 #pragma unroll
-      for (int c = 0; c < 6; ++c) {
+      for (int c = k; c < 6; ++c) {
         const double u = C[k][c], l = C[r][c];
         C[k][c] = ex ? l : u;
         C[r][c] = ex ? u : l;

@@ -28,9 +28,11 @@ def sign_rule(v):
 EigPair = collections.namedtuple("EigPair", "lam_u lam_s v_u v_s")
 
 
-def eig_pair(M, digits=50):
+def eig_pair(M, digits=50, reciprocal=False):
     """(lambda_u, lambda_s, v_u, v_s) of M at `digits` digits: the eigenvalue of largest and of smallest modulus, unit vectors with
-    the sign rule (v_x > 0); None if the dominant eigenvalue is not real (a complex pair) or M is not finite."""
+    the sign rule (v_x > 0); None if the dominant eigenvalue is not real (a complex pair) or M is not finite.  reciprocal: lambda_s
+    is the eigenvalue nearest 1 / lambda_u instead, what inverse iteration with that shift looks for -- the same one for a
+    monodromy matrix, another for a matrix without reciprocal pairs."""
     M = np.asarray(M, dtype=float)
     if not np.all(np.isfinite(M)):
         return None
@@ -38,7 +40,7 @@ def eig_pair(M, digits=50):
         E, ER = mpmath.eig(mpmath.matrix(M.tolist()))
         mods = [abs(e) for e in E]
         iu = max(range(6), key=lambda i: mods[i])
-        i_s = min(range(6), key=lambda i: mods[i])
+        i_s = min(range(6), key=(lambda i: abs(E[i] - 1 / E[iu])) if reciprocal else (lambda i: mods[i]))
         tol = mpmath.mpf(10) ** (-(digits - 10))
         if abs(mpmath.im(E[iu])) > tol * mods[iu] or not mods[iu] > 1:
             return None
@@ -50,6 +52,106 @@ def eig_pair(M, digits=50):
             n = mpmath.sqrt(sum(x * x for x in col))
             out.append(sign_rule([float(x / n) for x in col]))
         return EigPair(float(mpmath.re(E[iu])), float(mpmath.re(E[i_s])), out[0], out[1])
+
+
+def synthetic_monodromy(seed, lam_u, second, negative=False, mix=0.3, detune=0.0):
+    """Q D Q^-1 with the reciprocal pairs (lam_u, 1 / lam_u), (second, 1 / second) and the rotation pair e^{+-i}; lam_u < 0 with
+    `negative`.  Q = I + mix U(-1, 1) is a generic matrix, so v_s is NOT the mirrored v_u (the pattern of test_manifold_host's
+    synthetic_M, with the spectrum and the seed free).  detune: lambda_s = (1 + detune) / lam_u, so the inverse iteration's shift
+    1 / lambda_u misses it by that much and more than one solve is needed (with an exact shift a single solve of the nearly
+    singular system returns v_s from ANY right-hand side, and nothing the solve does to it can be seen)."""
+    rng = np.random.RandomState(seed)
+    Q = np.eye(6) + mix * rng.uniform(-1.0, 1.0, (6, 6))
+    c, s = np.cos(1.0), np.sin(1.0)
+    lam = -float(lam_u) if negative else float(lam_u)
+    D = np.zeros((6, 6))
+    D[0, 0], D[1, 1] = lam, (1.0 + detune) / lam
+    D[2, 2], D[3, 3] = float(second), 1.0 / float(second)
+    D[4:, 4:] = np.array([[c, -s], [s, c]])
+    return Q @ D @ np.linalg.inv(Q)
+
+
+def permuted(M, perm):
+    """P M P^T for the permutation matrix P = I[perm]: row i of the result is row perm[i] of M, and the columns alike."""
+    p = np.asarray(perm)
+    return np.asarray(M, dtype=float)[np.ix_(p, p)]
+
+
+def permuted_pair(e, perm):
+    """The 50-digit reference of P M P^T from that of M: the eigenvalues are M's, the vectors P v followed by the sign rule."""
+    p = np.asarray(perm)
+    return EigPair(e.lam_u, e.lam_s, sign_rule(e.v_u[p]), sign_rule(e.v_s[p]))
+
+
+POWER_CAP, INVERSE_CAP = 500, 8                      # LTO_MANIFOLD_POWER_CAP, LTO_MANIFOLD_INVERSE_CAP of include/lto.h
+Restated = collections.namedtuple("Restated", "status power_its last_move pivots margin inverse_its lam_u lam_s v_u v_s")
+
+
+def _unit_step(w, v):
+    """sign w / |w| with the sign that makes w . v >= 0, and how far that is from v in max-abs."""
+    s = -1.0 if float(w @ v) < 0.0 else 1.0
+    u = s * (w / np.sqrt(float(w @ w)))
+    return u, float(np.abs(u - v).max())
+
+
+def eigen_restatement(M, power_cap=POWER_CAP, inverse_cap=INVERSE_CAP):
+    """The eigen step as include/lto.h words it, in numpy: power iteration from the fixed start (1, .9, .8, .7, .6, .5) / |.|, the
+    iterate's sign aligned with the one before it, converged when it moves by < 1e-15 in max-abs, at most power_cap iterations;
+    lambda_u its Rayleigh quotient; inverse iteration on M - I / lambda_u from v_u mirrored in the xz-plane, a 6 x 6 LU with partial
+    pivoting (the first of equal maxima), at most inverse_cap solves; lambda_s the Rayleigh quotient of v_s; the sign rule last.
+
+    Written from the header, not from the kernel; numpy rounds every product on its own where the device may fuse, so the two need
+    not agree to the bit.  It vets inputs -- which rows the LU exchanges (pivots [6], pivots[k] = the row exchanged with row k;
+    margin = the smallest ratio of a chosen pivot to the runner-up, so a near-tie is seen), how many iterations are taken and how
+    far the iterate still moves at the end (last_move) -- and measures what the documented algorithm delivers.  It is never the
+    expected value of a comparison with the device."""
+    A = np.asarray(M, dtype=float)
+    nan6 = np.full(6, np.nan)
+    if not np.all(np.isfinite(A)):
+        return Restated(1, 0, np.nan, None, np.nan, 0, np.nan, np.nan, nan6, nan6)
+    vu = np.array([1.0, 0.9, 0.8, 0.7, 0.6, 0.5])
+    vu = vu / np.sqrt(float(vu @ vu))
+    conv, its, move = False, 0, np.inf
+    while its < power_cap and not conv:
+        vu, move = _unit_step(A @ vu, vu)
+        its += 1
+        conv = move < 1e-15
+    lam_u = float(vu @ (A @ vu))
+    if not conv or not abs(lam_u) > 1.0:
+        return Restated(1, its, move, None, np.nan, 0, lam_u, np.nan, nan6, nan6)
+    C = A - np.eye(6) / lam_u
+    piv, margin = [], np.inf
+    for k in range(6):
+        col = np.abs(C[k:, k])
+        p = k + int(np.argmax(col))                                  # argmax: the first of equal maxima
+        if col.size > 1:
+            rest = np.delete(col, p - k).max()
+            margin = min(margin, col[p - k] / rest if rest > 0.0 else np.inf)
+        piv.append(p)
+        C[[k, p]] = C[[p, k]]
+        if C[k, k] == 0.0:
+            C[k, k] = 2.220446049250313e-16 * abs(lam_u)
+        for r in range(k + 1, 6):
+            ell = C[r, k] / C[k, k]
+            C[r, k] = ell
+            C[r, k + 1:] = C[r, k + 1:] - ell * C[k, k + 1:]
+    vs = np.where(np.arange(6) & 1, -vu, vu)
+    iits, conv = 0, False
+    while iits < inverse_cap and not conv:
+        x = vs.copy()
+        for k in range(6):                                           # P x: every exchange, in the order they were made (whole rows
+            x[[k, piv[k]]] = x[[piv[k], k]]                          # of C were exchanged, the multipliers left of k with them)
+        for k in range(6):                                           # L y = P x
+            x[k + 1:] = x[k + 1:] - C[k + 1:, k] * x[k]
+        for k in range(5, -1, -1):                                   # U z = y
+            x[k] = (x[k] - float(C[k, k + 1:] @ x[k + 1:])) / C[k, k]
+        vs, imove = _unit_step(x, vs)
+        iits += 1
+        conv = imove < 1e-15
+    lam_s = float(vs @ (A @ vs))
+    if not np.all(np.isfinite(vs)) or not np.isfinite(lam_s):
+        return Restated(1, its, move, tuple(piv), margin, iits, lam_u, np.nan, nan6, nan6)
+    return Restated(0, its, move, tuple(piv), float(margin), iits, lam_u, lam_s, sign_rule(vu), sign_rule(vs))
 
 
 # -------------------------------------------------------------------------------------------------------------------- transport
@@ -141,6 +243,23 @@ def flight(y0, t_max, axis, value, MU, sec_dir=0, n_cross=1, rtol=RTOL, atol=ATO
             return Flight(s.y_events[0][-1], sgn * s.t_events[0][-1], count, 0, closest)
         return Flight(s.y[:, -1], sgn * s.t[-1], count, 1, closest)
     return Flight(s.y[:, -1], sgn * s.t[-1], 0, 0, closest)
+
+
+def sign_changes(y0, t_max, axis, value, MU, until, dt=0.005, rtol=RTOL, atol=ATOL):
+    """(times [n], slopes [n]) of the sign changes of g = y[axis] - value along the arc over the first `until` time units (at most
+    |t_max|), from the dense output of one solve without an event, sampled every dt: times count from the start and are positive,
+    located by linear interpolation between two samples; slopes are dg/ds along the flight at those times.  Two sign changes
+    closer than dt are missed; the callers ask for a distance forty times that."""
+    sgn = -1.0 if t_max < 0.0 else 1.0
+    T = min(abs(t_max), until)
+    f = rhs6(MU, sgn)
+    s = solve_ivp(f, (0.0, T), np.asarray(y0, dtype=float), method="DOP853", rtol=rtol, atol=atol, dense_output=True)
+    tt = np.linspace(0.0, T, int(np.ceil(T / dt)) + 1)
+    g = s.sol(tt)[axis] - value
+    k = np.nonzero(g[:-1] * g[1:] < 0.0)[0]
+    tc = tt[k] + (tt[k + 1] - tt[k]) * g[k] / (g[k] - g[k + 1])
+    slopes = np.array([f(0.0, s.sol(t))[axis] for t in tc])
+    return tc, slopes
 
 
 def flight_samples(y0, t_max, n, MU, rtol=RTOL, atol=ATOL):
