@@ -857,6 +857,12 @@ int lto_indirect_plan_copy_steps(lto_indirect_plan* plan, void* stream, int* acc
  * against 0.30 ms and 54 MB). */
 int lto_indirect_plan_rebalance(lto_indirect_plan* plan, void* stream);
 int lto_indirect_plan_reset_order(lto_indirect_plan* plan);
+/* Read-only: the lane order the plan's NEXT adaptive sweep would use.  *kind_out = 0: the natural order (fixed-step plans, plans
+ * that were never rebalanced, after lto_indirect_plan_reset_order) -- order_host is not touched and may be NULL; 1: the global
+ * order; 2: the windowed order -- order_host[0 .. S) receives the lane -> segment map (S = (n_nodes - 1) * n_batch ints), copied
+ * behind everything queued on `stream`, which is synchronised before the call returns.  plan or kind_out NULL, or order_host NULL
+ * with an order in use: LTO_ENULL, nothing written. */
+int lto_indirect_plan_copy_order(lto_indirect_plan* plan, void* stream, int* order_host, int* kind_out);
 /* Warm start of the adaptive step-size controller (ndim = 12, DOP853_ADAPTIVE -- the reference's integrator setting, whose
  * sweeps last as long as their slowest segment; other plans: LTO_EINVAL).  When on, every STM sweep / defect-only sweep of
  * this plan that runs the two-lane kernels starts each segment from the step size that segment's first accepted step had in
@@ -1027,6 +1033,21 @@ int lto_read_scalars_dev(lto_ctx* ctx, void* stream, const double* a, int na, co
 int lto_line_search_pick_dev(lto_ctx* ctx, void* stream, const double* sumsq, const double* maxabs, const double* alphas, int n_alpha,
                              const double* trial_defect, long ldt, int ndim, int seg_per_traj, int n_batch, double* step,
                              double* maxabs_out, double* defect, long ldd);
+/* Read-only entries to the load balancing of the adaptive sweeps, for step counts of the caller's choosing: the same
+ * launches lto_indirect_plan_rebalance and the defect sweeps run, without a plan.  The environment switches LTO_ORDER_MODE and
+ * LTO_ORDER_WEAVE play no part.  Both synchronise `stream` before they return; not thread-safe per context.
+ * lto_segment_order_dev: order_dev[0 .. n_segments) (device ints) <- the lane order for the step counts accepted_dev[s] +
+ * rejected_dev[s] (device ints), kind 1 = global (heaviest first over the whole batch), kind 2 = windowed with `weave` windows of
+ * an XCD's list interleaved (1 .. 255; 0 = the kernel's choice; ignored by kind 1 but checked).  Workspace comes from the context.
+ * kind not 1 or 2, weave outside 0 .. 255, n_segments < 1: LTO_EINVAL; a NULL pointer: LTO_ENULL; order_dev is then untouched. */
+int lto_segment_order_dev(lto_ctx* ctx, int kind, int weave, int n_segments, const int* accepted_dev, const int* rejected_dev,
+                          int* order_dev, void* stream);
+/* lto_step_stats_dev: out_host[0 .. 3) <- [sum, max, n_segments] of accepted_dev[s] + rejected_dev[s] over s < n_segments: the
+ * trial-step statistics a defect sweep leaves for the next one's choice of lanes per segment.  The maximum is taken from 0 up (step
+ * counts are not negative).  The call also checks that the kernel left its device scratch zeroed for the next launch (LTO_EHIP if
+ * not).  n_segments < 1: LTO_EINVAL; a NULL pointer: LTO_ENULL; out_host is then untouched. */
+int lto_step_stats_dev(lto_ctx* ctx, int n_segments, const int* accepted_dev, const int* rejected_dev, long long* out_host,
+                       void* stream);
 
 /* Dense output (device): segment s is sampled at t_samples[first[s] .. first[s+1]) (sorted, inside the segment);
  * Y[c*ldy + j] = x_c(t_samples[j]); final_state[c*n_batch + b] (or NULL) = x(t_n) of trajectory b.  Built for what densify

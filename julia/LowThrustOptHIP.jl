@@ -15,7 +15,7 @@ using SparseArrays, LinearAlgebra, Libdl
 
 export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pack_soa!, unpack_soa!, defect_norms!, indirect_defect_dev!,
        indirect_jacobian_dev!, newton_solve_dev!, axpy_dev!, direct_defect_dev!, direct_jacobian_dev!, rebalance!, set_kernel!, set_warm_start!, set_defect_lanes!,
-       comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms
+       comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms, copy_order!, segment_order_dev!, step_stats_dev!
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
        direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_target, halo_arclength, halo_table, manifold_seeds, section_flight, state_match, stationkeep_gains, stationkeep_flight, halo_stm, stationkeep_target_gains,
        LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass,
@@ -1236,6 +1236,23 @@ line_search_pick_dev!(ctx::LtoContext, stream, sumsq, maxabs, alphas, n_alpha::I
 
 "Order the lanes of the following adaptive sweeps by the last sweep's step counts (results unchanged)."
 rebalance!(pl::LtoIndirectPlan, stream) = check(pl.ctx, ccall((:lto_indirect_plan_rebalance, liblto), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), pl.handle, devptr(stream)))
+"`(kind, order)`: the lane order the plan's next adaptive sweep would use; kind 0 natural (`order` untouched), 1 global, 2 windowed. `order` needs (n_nodes - 1) * n_batch elements; entries are 0-based segment indices."
+function copy_order!(pl::LtoIndirectPlan, stream, order::Vector{Cint})
+    kind = Ref{Cint}(-1)
+    check(pl.ctx, ccall((:lto_indirect_plan_copy_order, liblto), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}), pl.handle, devptr(stream), order, kind))
+    (Int(kind[]), order)
+end
+"The lane order of the adaptive sweeps for step counts of the caller's choosing (device Cint arrays): kind 1 global, 2 windowed with `weave` windows interleaved (0: the kernel's choice). Read-only; returns when done."
+segment_order_dev!(ctx::LtoContext, kind::Integer, weave::Integer, n_segments::Integer, accepted, rejected, order, stream) =
+    check(ctx, ccall((:lto_segment_order_dev, liblto), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                     ctx.handle, kind, weave, n_segments, devptr(accepted), devptr(rejected), devptr(order), devptr(stream)))
+"`out[1:3] <- [sum, max, n_segments]` of accepted + rejected (device Cint arrays), as the defect sweeps' step statistics report them."
+function step_stats_dev!(ctx::LtoContext, n_segments::Integer, accepted, rejected, out::Vector{Int64}, stream)
+    length(out) >= 3 || throw(ArgumentError("step_stats_dev!: out needs at least 3 elements"))
+    check(ctx, ccall((:lto_step_stats_dev, liblto), Cint, (Ptr{Cvoid}, Cint, DevPtr, DevPtr, Ptr{Int64}, Ptr{Cvoid}),
+                     ctx.handle, n_segments, devptr(accepted), devptr(rejected), out, devptr(stream)))
+    out
+end
 "LTO_KERNEL_*: 0 auto, 1 per-lane, 2 cooperative, 5 eight-wave pipeline (RK4 plans), 6 cooperative with two lanes per state (12-dim DOP853 plans), 7 pipeline for large batches, 8 32-segment pipeline, 9 whole-segment lanes (RK4 plans); 3 = the direct plans' pipelined Jacobian kernel."
 set_kernel!(pl::LtoIndirectPlan, kernel::Integer) = check(pl.ctx, ccall((:lto_indirect_plan_set_kernel, liblto), Cint, (Ptr{Cvoid}, Cint), pl.handle, kernel))
 "Family LTO_KERNEL_AUTO resolves to for an STM sweep of this shape on a device with `n_cus` compute units (MI355X cost table): LTO_KERNEL_* (no GPU needed)."

@@ -6,7 +6,7 @@ from ._lib import LtoError, LtoParams, LtoIntegrator, LtoDirectParams, LtoDirect
 from .hotpath import (Context, Group, Comm, GroupComm, auto_kernel, default_context, integrator, make_params, indirect_defectCalc, indirect_stm,  # noqa: F401
                       indirect_scatter, indirect_scatter_mass, indirect_jacobianCalc, direct_defectCalc, direct_jacobian_blocks,
                       direct_scatter, direct_jacobianCalc, direct_endpoint_partials, direct_midpoints, densify, indirect_newton_step, indirect_solve, indirect_solve_batch, IndirectPlan, DirectPlan, pack_soa, unpack_soa,
-                      defect_norms, trial_points, line_search_pick, read_scalars, current_stream_ptr, direct_targets,
+                      defect_norms, trial_points, line_search_pick, read_scalars, segment_order, step_stats, current_stream_ptr, direct_targets,
                       direct_qp_step, direct_solve, direct_costates, costate_scale, DirectOrbits, direct_end_model, direct_end_states,
                       direct_qp_step_free, direct_solve_free, direct_tf_bounds, direct_qp_step_free_tf, direct_solve_free_tf,
                       indirect_add_time, indirect_remesh, direct_refine, direct_resample, stack_guess, StackGuess, indirect_events, ThrustEvents,

@@ -212,6 +212,9 @@ SIGNATURES = {
     "lto_indirect_plan_staging": (C.c_int, [_vp]),
     "lto_indirect_plan_rebalance": (C.c_int, [_vp, _vp]),
     "lto_indirect_plan_reset_order": (C.c_int, [_vp]),
+    "lto_indirect_plan_copy_order": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "lto_segment_order_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "lto_step_stats_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "lto_indirect_plan_set_warm_start": (C.c_int, [_vp, C.c_int]),
     "lto_indirect_plan_set_defect_lanes": (C.c_int, [_vp, C.c_int]),
     "lto_indirect_plan_set_kernel": (C.c_int, [_vp, C.c_int]),

@@ -615,8 +615,10 @@ constexpr int LTO_ORDER_BINS = 1024;   // int workspace launch_segment_order nee
 constexpr int LTO_ORDER_WINDOW = 1024;       // largest window (one thread per segment in k_order_window)
 constexpr int LTO_XCDS = 8;
 // Window size for a batch of S segments: as close to 1 024 as gives every XCD the same number of windows -- 8 k windows for
-// k = ceil(S / 8 192), a multiple of 16 segments (the interleave unit) -- so that the XCDs' lists line up with the contiguous
-// eighths of the order the kernels' workgroups are mapped to (xcd_unit below).  S = 65 536, 262 144, 20 x 4 096: 1 024.
+// k = ceil(S / 8 192), a multiple of 16 segments (the interleave unit).  When S is a multiple of 8 192 (or is 4 096) the eight
+// lists are equally long and ARE the contiguous eighths of the order the kernels' workgroups are mapped to (xcd_unit below).  At
+// any other S the window is rounded up to 16 segments, the lists differ in length, and a few per cent of the positions are worked
+// by a neighbouring XCD (DESIGN 4.9 has the figures; results do not depend on it).  S = 65 536, 262 144, 20 x 4 096: 1 024.
 inline int order_window_size(long S) {
   const long k = (S + 8191) / 8192 > 0 ? (S + 8191) / 8192 : 1;
   long w = (S + 8 * k - 1) / (8 * k);

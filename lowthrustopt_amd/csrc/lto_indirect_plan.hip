@@ -385,6 +385,24 @@ int lto_indirect_plan_reset_order(lto_indirect_plan* p) {
   return LTO_OK;
 }
 
+int lto_indirect_plan_copy_order(lto_indirect_plan* p, void* stream, int* order_host, int* kind_out) {
+  if (!p) return LTO_ENULL;
+  lto_ctx* c = p->ctx;
+  if (!kind_out) return set_err(c, LTO_ENULL, "kind_out is NULL");
+  const int kind = (p->use_order && p->d_order) ? p->order_kind : 0;       // what fill_indirect_args hands the next sweep
+  if (kind != 0) {
+    if (!order_host) return set_err(c, LTO_ENULL, "order_host is NULL and the plan has a lane order");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(order_host, p->d_order, sizeof(int) * (size_t)p->S, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return set_err(c, LTO_EHIP, "copy lane order", e);
+  }
+  *kind_out = kind;
+  return LTO_OK;
+}
+
 int lto_indirect_plan_set_kernel(lto_indirect_plan* p, int kernel) {
   if (!p) return LTO_ENULL;
   // (selectors 3 and 4 are not indirect families: 3 = LTO_KERNEL_DIRECT_PIPE, the direct plans' pipelined Jacobian kernel; 4 is unassigned)

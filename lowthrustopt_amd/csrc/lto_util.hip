@@ -1,5 +1,5 @@
-// lto_util.hip -- the small device-resident entry points: axpy, trial points, line-search pick, scalars to the host, AoS <-> SoA,
-// defect norms.
+// lto_util.hip -- the small device-resident entry points: axpy, trial points, line-search pick, scalars to the host, lane order and
+// step statistics read back, AoS <-> SoA, defect norms.
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -112,6 +112,68 @@ int lto_read_scalars_dev(lto_ctx* c, void* stream, const double* a, int na, cons
   if (rc) return rc;
   (void)report_reserve(c, (size_t)na + nb);
   return read_scalars(c, (hipStream_t)stream, a, na, b, nb, out);
+}
+
+/* ------------------------------------------------------------------------------ lane order and step statistics, read back */
+// The launchers lto_indirect_plan_rebalance runs, on step counts of the caller's choosing.  The workspace is the context's arena,
+// which the next host-pointer call lays out afresh: the stream is drained before the call returns.
+int lto_segment_order_dev(lto_ctx* c, int kind, int weave, int n_segments, const int* accepted_dev, const int* rejected_dev,
+                          int* order_dev, void* stream) {
+  if (!c) return LTO_ENULL;
+  if (!accepted_dev || !rejected_dev || !order_dev) return set_err(c, LTO_ENULL, "accepted_dev, rejected_dev or order_dev is NULL");
+  if (kind != 1 && kind != 2) return set_err(c, LTO_EINVAL, "kind must be 1 (global order) or 2 (windowed order)");
+  if (weave < 0 || weave > 255) return set_err(c, LTO_EINVAL, "weave must be 0 (choose) .. 255");
+  if (n_segments < 1) return set_err(c, LTO_EINVAL, "need n_segments >= 1");
+  int rc = bind_device(c);
+  if (rc) return rc;
+  int* work;
+  ArenaLayout scratch;
+  scratch.add(order_workspace_ints(n_segments), work);
+  rc = scratch.reserve(c);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = kind == 2 ? launch_segment_order_windowed(accepted_dev, rejected_dev, n_segments, weave, work, order_dev, st)
+                           : launch_segment_order(accepted_dev, rejected_dev, n_segments, work, order_dev, st);
+  const hipError_t q = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = q;
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_segment_order", e);
+  return LTO_OK;
+}
+
+// k_step_stats as a defect sweep launches it: a zeroed device scratch, a page-locked landing block (here the call's own).  The
+// kernel's last workgroup must leave the scratch zeroed for the next launch; the call reads it back and says so if it did not.
+int lto_step_stats_dev(lto_ctx* c, int n_segments, const int* accepted_dev, const int* rejected_dev, long long* out_host, void* stream) {
+  if (!c) return LTO_ENULL;
+  if (!accepted_dev || !rejected_dev || !out_host) return set_err(c, LTO_ENULL, "accepted_dev, rejected_dev or out_host is NULL");
+  if (n_segments < 1) return set_err(c, LTO_EINVAL, "need n_segments >= 1");
+  int rc = bind_device(c);
+  if (rc) return rc;
+  unsigned long long* acc;
+  ArenaLayout scratch;
+  scratch.add(4, acc);
+  rc = scratch.reserve(c);
+  if (rc) return rc;
+  void* hp = nullptr; void* dp = nullptr;
+  if (hipHostMalloc(&hp, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
+    const hipError_t e = hipGetLastError();
+    if (hp) (void)hipHostFree(hp);
+    return set_err(c, LTO_EHIP, "page-locked block of the step statistics", e);
+  }
+  long long* land = (long long*)hp;
+  for (int k = 0; k < 8; ++k) land[k] = -1;                 // a word the kernel does not write shows
+  unsigned long long left[3] = {1, 1, 1};
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(acc, 0, sizeof(unsigned long long) * 4, st);
+  if (e == hipSuccess) e = launch_step_stats(accepted_dev, rejected_dev, n_segments, acc, (long long*)dp, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(left, acc, sizeof left, hipMemcpyDeviceToHost, st);
+  const hipError_t q = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = q;
+  const long long got[3] = {land[0], land[1], land[2]};
+  (void)hipHostFree(hp);
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_step_stats", e);
+  if (left[0] || left[1] || left[2]) return set_err(c, LTO_EHIP, "k_step_stats left its device scratch non-zero: the next launch would add to it");
+  for (int k = 0; k < 3; ++k) out_host[k] = got[k];
+  return LTO_OK;
 }
 
 /* ------------------------------------------------------------------------------ utilities */

@@ -2175,6 +2175,20 @@ class IndirectPlan:
     def reset_order(self):
         self.ctx.check(self.ctx.lib.lto_indirect_plan_reset_order(self.handle))
 
+    def copy_order(self, stream=None, out=None):
+        """(kind, order): the lane order the plan's next adaptive sweep would use (lto_indirect_plan_copy_order).  kind 0: natural
+        order, `order` is `out` as it was given (None if none was); 1 global, 2 windowed: order[S] int32 (written into `out` if given)."""
+        if out is None:
+            buf = np.full(self.S, -1, dtype=np.int32)
+        else:
+            buf = out
+            if (not isinstance(buf, np.ndarray) or buf.dtype != np.int32 or not buf.flags["C_CONTIGUOUS"] or not buf.flags["WRITEABLE"]
+                    or buf.size < self.S):
+                raise LtoError(LTO_EINVAL, "copy_order: `out` must be a writeable C-contiguous int32 array of at least S = %d elements" % self.S)
+        kind = C.c_int(-1)
+        self.ctx.check(self.ctx.lib.lto_indirect_plan_copy_order(self.handle, stream, _ptr(buf), C.byref(kind)))
+        return kind.value, (buf if (kind.value != 0 or out is not None) else None)
+
     def step_counts(self, stream=None):
         """(accepted[S], rejected[S]) of the last adaptive sweep (numpy int32)."""
         acc = np.zeros(self.S, dtype=np.int32)
@@ -2287,6 +2301,23 @@ def line_search_pick(ctx, sumsq, maxabs, alphas, trial_defect, ldt, ndim, seg_pe
     na = int(alphas.numel() if hasattr(alphas, "numel") else len(alphas))
     ctx.check(ctx.lib.lto_line_search_pick_dev(ctx.handle, stream, _dptr(sumsq), _dptr(maxabs), _dptr(alphas), na, _dptr(trial_defect), int(ldt),
                                                int(ndim), int(seg_per_traj), int(n_batch), _dptr(step), _dptr(maxabs_out), _dptr(defect), int(ldd)))
+
+
+def segment_order(ctx, kind, accepted, rejected, order, n_segments, weave=0, stream=None):
+    """order[:n_segments] (device int32) <- the lane order of the adaptive sweeps for the step counts accepted + rejected (device
+    int32): kind 1 global, 2 windowed with `weave` windows interleaved (0: the kernel's choice).  lto_segment_order_dev; back when done."""
+    ctx.check(ctx.lib.lto_segment_order_dev(ctx.handle, int(kind), int(weave), int(n_segments), _dptr(accepted), _dptr(rejected),
+                                            _dptr(order), stream))
+
+
+def step_stats(ctx, accepted, rejected, n_segments, out=None, stream=None):
+    """[sum, max, n_segments] of accepted + rejected (device int32) as k_step_stats reports them (lto_step_stats_dev): int64 [3]."""
+    if out is None:
+        out = np.full(3, -1, dtype=np.int64)
+    if (not isinstance(out, np.ndarray) or out.dtype != np.int64 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"] or out.size < 3):
+        raise LtoError(LTO_EINVAL, "step_stats: `out` must be a writeable C-contiguous int64 array of at least 3 elements")
+    ctx.check(ctx.lib.lto_step_stats_dev(ctx.handle, int(n_segments), _dptr(accepted), _dptr(rejected), _ptr(out), stream))
+    return out
 
 
 def read_scalars(ctx, a, na, b, nb, out, stream=None):

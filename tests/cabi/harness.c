@@ -33,6 +33,13 @@ static int self_check(void) {
   if (lto_indirect_auto_kernel(13, LTO_RK4, 64, 1.0, 4096, 256, 0) != LTO_EINVAL) return fail("auto kernel accepted ndim 13", 0, NULL);
   if (lto_indirect_auto_kernel(12, LTO_RK4, 64, 0.5, 4096, 256, 0) != LTO_EINVAL) return fail("auto kernel accepted p = 0.5", 0, NULL);
   if (lto_comm_rccl_ranks(NULL) != LTO_ENULL || lto_last_call_order(NULL) != LTO_ENULL) return fail("NULL handles accepted", 0, NULL);
+  {
+    int kind = -9, order[1] = {-9};
+    long long stats[3] = {-9, -9, -9};
+    if (lto_segment_order_dev(NULL, 2, 0, 1, order, order, order, NULL) != LTO_ENULL || lto_step_stats_dev(NULL, 1, order, order, stats, NULL) != LTO_ENULL ||
+        lto_indirect_plan_copy_order(NULL, NULL, order, &kind) != LTO_ENULL || kind != -9 || order[0] != -9 || stats[0] != -9)
+      return fail("read-back entries accepted a NULL handle or wrote through it", 0, NULL);
+  }
   printf("host logic: LTO_KERNEL_AUTO resolves as documented\n");
   rc = lto_create(&c, 0);
   if (rc == LTO_ENODEVICE) { printf("no device: lto_create refused (LTO_ENODEVICE), no CPU fallback\n"); return 0; }
