@@ -1223,6 +1223,37 @@ int lto_guided_flight_mass_batch(lto_ctx* ctx, int n_nodes, int n_batch, const d
 int lto_guided_flight_mass(lto_ctx* ctx, int n_nodes, const double* XC_nom, const double* t, const double* K, const double* x0,
                            int update_every, const double* nav, const lto_params* prm, const lto_integrator* integ, double* x_final,
                            double* lam_final, double* dv, double* X_nodes, int* accepted, int* rejected, int* status);
+/* Linear covariance of the guided flight: what a start covariance P0 and a navigation covariance R leave of the state
+ * covariance at every node, to first order -- exactly the linearisation of the guided flight above, nothing more (no process noise,
+ * no execution error, no dv statistics).  ndim is 12 or 14 (NX = ndim / 2, ND = ndim; with 14 rows the gains are those of
+ * lto_guidance_gains_mass_batch and prm.mass carries Isp).  The call runs the gains call as it stands (the same STM sweep, backward
+ * sweep and split of mixed 14-row DOP853 batches: K, pivot and gain_status are bit for bit its outputs) and then, with Phi_k and
+ * K_k still on the device, one forward pass per (trajectory, case).  A case i is (P0[:, :, i], R[:, :, i], update_every[i]); the
+ * cases are shared by all trajectories.  Per pair the pass carries the ND x ND covariance Z of z = (dx, dlambda):
+ *   P0 and R are symmetrised on load, a[r][c] <- 0.5 * (a[r][c] + a[c][r]);  Z = 0 but Z_xx = P0;  for k = 0 .. n_nodes-2:
+ *   1. if update_every > 0 and k % update_every == 0, with P = Z_xx:  S = P + R (element by element, first);  U = K_k P;
+ *      V = K_k S;  Z_lx = U;  Z_xl = U^T (copied, not recomputed);  Z_ll = V K_k^T;  Z_xx is left alone;
+ *   2. T = Phi_k Z;  Z' = T Phi_k^T;  Z[r][c] = 0.5 * (Z'[r][c] + Z'[c][r]);
+ *   3. P_{k+1} = Z_xx.
+ * The arithmetic is fixed so that a host reproduces it bit for bit: binary64, every product and every sum rounded on its own (no
+ * fused multiply-add), every dot product accumulated from its first product over j = 0, 1, ..:
+ *   U[r][c] = sum_j K[r][j] P[j][c];  V[r][c] = sum_j K[r][j] S[j][c];  Z_ll[r][c] = sum_j V[r][j] K[c][j];
+ *   T[r][c] = sum_j Phi[r][j] Z[j][c];  Z'[r][c] = sum_j T[r][j] Phi[c][j].
+ * update_every = 0 never reads a gain; a gain at a node that is not an update node is never looked at.
+ * In: n_cases >= 1;  P0, R [NX x NX x n_cases];  update_every [n_cases], each >= 0.  Out: K [NX x NX x (n_nodes-1) x n_batch], pivot
+ * [(n_nodes-1) x n_batch], Phi [ND x ND x (n_nodes-1) x n_batch] (the STMs the call used, laid out as lto_indirect_jacobian's) and
+ * P_nodes [NX x NX x n_nodes x n_cases x n_batch] may each be NULL;  gain_status [n_batch];  P_final [NX x NX x n_cases x n_batch];
+ * cov_status [n_cases x n_batch].  Node 0 of P_nodes is the symmetrised P0 as it is, its last node equals P_final bit for bit.
+ * cov_status: 0 ok;  2 a non-finite P0 or R (found at node 0, whether R is used or not), a non-finite Phi_k, or a non-finite gain
+ * at an update node k -- the NaN gains of a gain_status 2 or 3 trajectory end up here: P is NaN from node k + 1 on and P_final is NaN;
+ * no other case and no other trajectory is affected.  A (trajectory, case) pair's outputs are bit for bit those of the call with
+ * that trajectory and that case alone.  LTO_ENULL and LTO_EINVAL as lto_guidance_gains_batch, and LTO_EINVAL for n_cases < 1
+ * (or above 262140) or an update_every[i] < 0;  LTO_EUNSUPPORTED for ndim not 12 or 14 and for every method but LTO_RK4 and
+ * LTO_DOP853_ADAPTIVE. */
+int lto_guidance_covariance_batch(lto_ctx* ctx, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                                  const lto_params* prm, int n_prm, const lto_integrator* integ, double sing_tol, int n_cases,
+                                  const double* P0, const double* R, const int* update_every, double* K, double* pivot,
+                                  int* gain_status, double* Phi, double* P_nodes, double* P_final, int* cov_status);
 
 int lto_direct_plan_create(lto_ctx* ctx, int nstate, int n_nodes, int n_batch, int nsteps,
                            const lto_direct_params* prm, lto_direct_plan** out);

@@ -18,7 +18,7 @@ export LtoIndirectPlan, LtoDirectPlan, LtoComm, LtoCommWindows, pinned_array, pa
        comm_unique_id, allgather_dev!, allreduce_dev!, ctx_stream, last_call_ms, copy_order!, segment_order_dev!, step_stats_dev!
 export LtoContext, LtoGroup, indirect_defectCalc, indirect_jacobianCalc, indirect_stm, indirect_newton_step, indirect_solve, indirect_solve_batch, densify, densify_mass, addTimeFinal, tf_sweep, addTimeFinal_mass, tf_sweep_mass, meshRefine_indirect, remesh_batch, meshRefine_indirect_mass, remesh_mass_batch,
        direct_defectCalc, direct_jacobianCalc, direct_midpoints, direct_refine, direct_resample, direct_qp_step, direct_solve, direct_costates, direct_end_states, direct_qp_step_free, direct_solve_free, stack_guess, halo_correct, halo_target, halo_arclength, halo_table, manifold_seeds, section_flight, state_match, stationkeep_gains, stationkeep_flight, halo_stm, stationkeep_target_gains,
-       LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass,
+       LtoDirectTfBounds, direct_qp_step_free_tf, direct_solve_free_tf, guidance_gains, guided_flight, guidance_gains_mass, guided_flight_mass, guidance_covariance,
        LtoDirectTargets, LtoDirectEndModel, LTO_RK4, LTO_RKF78_FIXED, LTO_RKF78_ADAPTIVE, LTO_DOP853_ADAPTIVE
 
 const liblto = get(ENV, "LTO_HIP_LIB", joinpath(@__DIR__, "..", "lowthrustopt_amd", "liblto_hip.so"))
@@ -610,6 +610,39 @@ function guided_flight_mass(ctx::LtoContext, XC_nom::Array{Float64,3}, t::Matrix
     check(ctx, rc)
     (x_final = x_final, lam_final = lam_final, dv = dv, nodes = nodes, accepted = Int.(accepted), rejected = Int.(rejected),
      status = Int.(status))
+end
+
+"""Linear covariance of the guided flight (`lto_guidance_covariance_batch`, DESIGN 4.31) about the solutions `XC` [ndim x n x B],
+ndim 12 or 14 (NX = ndim / 2; 14 rows: Isp in the mass slot of the parameters), on the grids `t` [n x n_tgrids].  The cases
+`P0`, `R` [NX x NX x n_cases] and `update_every` [n_cases] (each >= 0) are shared by all trajectories: one call sweeps the STMs,
+builds the gains and runs the forward pass of every (trajectory, case).  Returns the named tuple (P_final [NX x NX x n_cases x B],
+P_nodes [NX x NX x n x n_cases x B] or `nothing`, cov_status [n_cases x B]: 0 ok, 2 not finite; K, pivot, gain_status as
+`guidance_gains`; Phi [ndim x ndim x (n-1) x B] or `nothing`)."""
+function guidance_covariance(ctx::LtoContext, XC::Array{Float64,3}, t::Matrix{Float64}, params::Vector, P0::Array{Float64,3},
+                             R::Array{Float64,3}, update_every::Vector{<:Integer}; sing_tol::Real = 1e-10,
+                             integ::LtoIntegrator = LtoIntegrator(), with_nodes::Bool = false, with_phi::Bool = false)
+    ndim, n, B = size(XC)
+    (ndim == 12 || ndim == 14) || throw(ArgumentError("XC must be [12 x n x B] or [14 x n x B]"))
+    nx = ndim ÷ 2
+    nc = length(update_every)
+    (nc >= 1 && size(P0) == (nx, nx, nc) && size(R) == (nx, nx, nc)) ||
+        throw(ArgumentError("P0 and R must be [NX x NX x n_cases] with one update_every per case"))
+    all(>=(0), update_every) || throw(ArgumentError("update_every must be >= 0"))
+    prm = [LtoParams(q) for q in params]
+    every = Cint.(update_every)
+    K = zeros(nx, nx, n - 1, B); pivot = zeros(n - 1, B); gain_status = zeros(Cint, B)
+    Phi = with_phi ? zeros(ndim, ndim, n - 1, B) : nothing
+    P_nodes = with_nodes ? zeros(nx, nx, n, nc, B) : nothing
+    P_final = zeros(nx, nx, nc, B); cov_status = zeros(Cint, nc, B)
+    rc = ccall((:lto_guidance_covariance_batch, liblto), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{LtoParams}, Cint, Ref{LtoIntegrator}, Cdouble,
+                Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cint}),
+               ctx.handle, ndim, n, B, XC, t, size(t, 2), prm, length(prm), Ref(integ), Float64(sing_tol), nc, P0, R, every, K, pivot,
+               gain_status, Phi === nothing ? C_NULL : Phi, P_nodes === nothing ? C_NULL : P_nodes, P_final, cov_status)
+    check(ctx, rc)
+    (P_final = P_final, P_nodes = P_nodes, cov_status = Int.(cov_status), K = K, pivot = pivot, gain_status = Int.(gain_status),
+     Phi = Phi)
 end
 
 # ---------------------------------------------------------------------------------------------- direct

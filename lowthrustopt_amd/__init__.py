@@ -12,7 +12,7 @@ from .hotpath import (Context, Group, Comm, GroupComm, auto_kernel, default_cont
                       indirect_add_time, indirect_remesh, direct_refine, direct_resample, stack_guess, StackGuess, indirect_events, ThrustEvents,
                       indirect_events_mass, densify_mass, indirect_remesh_mass, indirect_add_time_mass, control_replay, ControlReplay,
                       replay_sample_knots, guidance_gains, GuidanceGains, guided_flight, GuidedFlight, guided_updates,
-                      guidance_gains_mass, guided_flight_mass, halo_correct, HaloCorrect, halo_table, HaloTable,
+                      guidance_gains_mass, guided_flight_mass, guidance_covariance, GuidanceCovariance, halo_correct, HaloCorrect, halo_table, HaloTable,
                       HALO_HOLD_Z0, HALO_HOLD_X0, HALO_PLANAR, manifold_seeds, ManifoldSeeds, section_flight, SectionFlight,
                       state_match, StateMatch, halo_target, HaloTarget, HALO_TARGET_JACOBI, HALO_TARGET_PERIOD,
                       halo_arclength, HaloArclength, stationkeep_gains, StationkeepGains, stationkeep_flight, StationkeepFlight,

@@ -204,6 +204,9 @@ SIGNATURES = {
                                                _vp]),
     "lto_guided_flight_mass": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(LtoParams),
                                          C.POINTER(LtoIntegrator), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lto_guidance_covariance_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.POINTER(LtoParams), C.c_int,
+                                                C.POINTER(LtoIntegrator), C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _vp]),
     "lto_indirect_plan_steps_accepted": (_vp, [_vp]),
     "lto_indirect_plan_steps_rejected": (_vp, [_vp]),
     "lto_indirect_plan_copy_steps": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -199,6 +199,21 @@ struct GuidedArgs {
 };
 // method M_RK4 or M_DOP853_ADAPTIVE; anything else: hipErrorInvalidValue
 hipError_t launch_guided_flight(int pm, int method, const IndirectArgs& a, const GuidedArgs& g, hipStream_t st);
+// Linear covariance of the guided flight (kernels_guidance_cov.hip): the forward pass over the Phi and K that the
+// gains sweep left in HBM (their layouts as in GainsArgs).  P0, R [nx^2][n_cases] and every output are the caller's column-major
+// arrays as they stand: P_nodes [nx^2][n_nodes][n_cases][n_batch], P_final [nx^2][n_cases][n_batch], status [n_cases][n_batch].
+struct CovArgs {
+  const double* Phi; long ldp;
+  const double* K;
+  int n_nodes, n_batch, n_cases;
+  const double* P0; const double* R;
+  const int* every;                // [n_cases], each >= 0
+  double* P_nodes;                 // or null
+  double* P_final;
+  int* status;                     // 0 ok, 2 not finite
+  int nx;                          // 6 or 7; anything else: hipErrorInvalidValue
+};
+hipError_t launch_guidance_covariance(const CovArgs& a, hipStream_t st);
 // the caller's column-major [rows x count] <-> [row][count], any number of rows
 hipError_t launch_rows_to_lanes(const double* aos, long rows, long count, double* soa, hipStream_t st);
 hipError_t launch_lanes_to_rows(const double* soa, long rows, long count, double* aos, hipStream_t st);

@@ -48,13 +48,23 @@ hipError_t lanes_out(const double* d_in, long rows, long count, double* d_tmp, d
   return e == hipSuccess ? hipMemcpyAsync(host, d_tmp, sizeof(double) * (size_t)rows * count, hipMemcpyDeviceToHost, st) : e;
 }
 
+// The covariance call's own arguments (lto_guidance_covariance_batch): the gains call with `cov` set runs the forward pass of
+// k_guidance_covariance over the Phi and K it has in HBM, and K becomes optional.
+struct CovCall {
+  int n_cases;
+  const double* P0; const double* R; const int* every;
+  double* Phi; double* P_nodes; double* P_final; int* status;
+};
+
 int gains_batch(int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC, const double* t,
                 int n_tgrids, const lto_params* prm, int n_prm, const lto_integrator* integ, double sing_tol, double* K, double* pivot,
-                int* status) {
+                int* status, const CovCall* cov = nullptr) {
   if (!c) return LTO_ENULL;
   CallTimer call_timer(c);
-  if (!XC || !t || !prm || !integ || !K || !status)
-    return fail(c, LTO_ENULL, who, "XC, t, prm, integ, K or status is NULL");
+  if (!XC || !t || !prm || !integ || !status || (!cov && !K))
+    return fail(c, LTO_ENULL, who, cov ? "XC, t, prm, integ or gain_status is NULL" : "XC, t, prm, integ, K or status is NULL");
+  if (cov && (!cov->P0 || !cov->R || !cov->every || !cov->P_final || !cov->status))
+    return fail(c, LTO_ENULL, who, "P0, R, update_every, P_final or cov_status is NULL");
   int rc = guidance_supported(c, nd, ndim, integ, "guidance gains are built for LTO_RK4 or LTO_DOP853_ADAPTIVE");
   if (rc) return rc;
   if (n_nodes < 2 || n_batch < 1) return fail(c, LTO_EINVAL, who, "need n_nodes >= 2 and n_batch >= 1");
@@ -63,7 +73,13 @@ int gains_batch(int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, int 
   if (!(sing_tol > 0.0 && sing_tol < 1.0)) return fail(c, LTO_EINVAL, who, "sing_tol must lie in (0, 1)");
   if (!grids_increase(t, n_nodes, n_tgrids))
     return fail(c, LTO_EINVAL, who, "t must be finite and strictly increasing");
+  if (cov) {
+    if (cov->n_cases < 1 || cov->n_cases > 4 * 65535) return fail(c, LTO_EINVAL, who, "need 1 <= n_cases <= 262140");
+    for (int i = 0; i < cov->n_cases; ++i)
+      if (cov->every[i] < 0) return fail(c, LTO_EINVAL, who, "update_every must be >= 0");
+  }
   const int B = n_batch, nx = nd / 2;
+  const size_t ne = (size_t)nx * nx, nc = cov ? (size_t)cov->n_cases : 0;
   // 14 rows, DOP853: AUTO takes the two-lanes-per-state STM kernel for batches whose laws are all p = 0 or p = 1 and the one-piece
   // cooperative kernel otherwise, and the two differ in the last bits -- swept as one batch, a p <= 1 trajectory's gains would
   // depend on the classes of its neighbours.  A batch that mixes the two kinds is therefore run as two calls, one per kind, each
@@ -85,18 +101,34 @@ int gains_batch(int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, int 
         HostBuf<lto_params> prms(m);
         HostBuf<int> sts(m);
         if (!Xs.ok() || !ts.ok() || !Ks.ok() || !ps.ok() || !prms.ok() || !sts.ok()) return fail(c, LTO_ENOMEM, who, "host memory");
+        // the covariance outputs of this kind's trajectories, scattered back like the gains
+        const size_t ph = (size_t)nd * nd * segs, pn = ne * n_nodes * nc, pf = ne * nc;
+        HostBuf<double> Phs(cov && cov->Phi ? ph * m : 0), Pns(cov && cov->P_nodes ? pn * m : 0), Pfs(cov ? pf * m : 0);
+        HostBuf<int> css(cov ? nc * m : 0);
+        if (!Phs.ok() || !Pns.ok() || !Pfs.ok() || !css.ok()) return fail(c, LTO_ENOMEM, who, "host memory");
+        CovCall sub{};
+        if (cov) {
+          sub = *cov;
+          sub.Phi = cov->Phi ? Phs.data() : nullptr; sub.P_nodes = cov->P_nodes ? Pns.data() : nullptr;
+          sub.P_final = Pfs.data(); sub.status = css.data();
+        }
         for (size_t j = 0; j < m; ++j) {
           std::memcpy(Xs.data() + xc * j, XC + xc * ix[j], sizeof(double) * xc);
           if (n_tgrids != 1) std::memcpy(ts.data() + (size_t)n_nodes * j, t + (size_t)n_nodes * ix[j], sizeof(double) * n_nodes);
           prms[j] = prm[ix[j]];
         }
         rc = gains_batch(nd, who, c, ndim, n_nodes, (int)m, Xs.data(), n_tgrids == 1 ? t : ts.data(), n_tgrids == 1 ? 1 : (int)m,
-                         prms.data(), (int)m, integ, sing_tol, Ks.data(), ps.data(), sts.data());
+                         prms.data(), (int)m, integ, sing_tol, Ks.data(), ps.data(), sts.data(), cov ? &sub : nullptr);
         if (rc) return rc;
         for (size_t j = 0; j < m; ++j) {
-          std::memcpy(K + kk * ix[j], Ks.data() + kk * j, sizeof(double) * kk);
+          if (K) std::memcpy(K + kk * ix[j], Ks.data() + kk * j, sizeof(double) * kk);
           if (pivot) std::memcpy(pivot + segs * ix[j], ps.data() + segs * j, sizeof(double) * segs);
           status[ix[j]] = sts[j];
+          if (!cov) continue;
+          if (cov->Phi) std::memcpy(cov->Phi + ph * ix[j], Phs.data() + ph * j, sizeof(double) * ph);
+          if (cov->P_nodes) std::memcpy(cov->P_nodes + pn * ix[j], Pns.data() + pn * j, sizeof(double) * pn);
+          std::memcpy(cov->P_final + pf * ix[j], Pfs.data() + pf * j, sizeof(double) * pf);
+          std::memcpy(cov->status + nc * ix[j], css.data() + nc * j, sizeof(int) * nc);
         }
       }
       return LTO_OK;
@@ -106,8 +138,8 @@ int gains_batch(int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, int 
   HostCall call(c);
   rc = plan_build(c, nd, n_nodes, n_batch, prm, n_prm, integ, &call.plan[0]);
   if (rc) return rc;
-  double *d_aos, *d_X, *d_t, *d_def, *d_phi, *d_K, *d_piv;
-  int* d_status;
+  double *d_aos, *d_X, *d_t, *d_def, *d_phi, *d_K, *d_piv, *d_phi_aos, *d_P0, *d_R, *d_Pn, *d_Pf;
+  int *d_status, *d_every, *d_cst;
   ArenaLayout scratch;
   scratch.add((size_t)nd * J, d_aos, d_X);
   scratch.add(nt, d_t);
@@ -116,11 +148,20 @@ int gains_batch(int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, int 
   scratch.add((size_t)nx * nx * S, d_K);
   scratch.add(S, d_piv);
   scratch.add((size_t)B, d_status);
+  scratch.add(cov && cov->Phi ? (size_t)nd * nd * S : 0, d_phi_aos);
+  scratch.add(ne * nc, d_P0, d_R);
+  scratch.add(cov && cov->P_nodes ? ne * nc * J : 0, d_Pn);
+  scratch.add(ne * nc * B, d_Pf);
+  scratch.add(nc, d_every);
+  scratch.add(nc * B, d_cst);
   rc = scratch.reserve(c);
   if (rc) return rc;
   hipStream_t st = c->stream;
   hipError_t e = stage_in(c, XC, nd, (long)J, d_aos, d_X, (long)J, st);
   if (e == hipSuccess) e = vec_in(c, t, (long)nt, d_t, st);
+  if (e == hipSuccess && cov) e = hipMemcpyAsync(d_P0, cov->P0, sizeof(double) * ne * nc, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && cov) e = hipMemcpyAsync(d_R, cov->R, sizeof(double) * ne * nc, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && cov) e = hipMemcpyAsync(d_every, cov->every, sizeof(int) * nc, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return fail(c, LTO_EHIP, who, "stage in", e);
   rc = lto_indirect_jacobian_dev(call.plan[0], st, d_X, (long)J, d_t, n_tgrids, d_phi, (long)S, d_def, (long)S);
   if (rc) return rc;
@@ -128,11 +169,25 @@ int gains_batch(int nd, const char* who, lto_ctx* c, int ndim, int n_nodes, int 
   g.Phi = d_phi; g.ldp = (long)S; g.n_nodes = n_nodes; g.n_batch = B; g.sing_tol = sing_tol;
   g.K = d_K; g.pivot = d_piv; g.status = d_status; g.nx = nx;
   e = launch_guidance_gains(g, st);
-  timing_end(c, st);                             // the sweep's start to the gains' end
-  if (e != hipSuccess) return set_err(c, LTO_EHIP, "launch_guidance_gains", e);
-  e = hipMemcpyAsync(K, d_K, sizeof(double) * nx * nx * S, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && cov) {                  // Phi and K stay where they are: the forward pass reads them from HBM
+    CovArgs v{};
+    v.Phi = d_phi; v.ldp = (long)S; v.K = d_K; v.n_nodes = n_nodes; v.n_batch = B; v.n_cases = cov->n_cases;
+    v.P0 = d_P0; v.R = d_R; v.every = d_every; v.P_nodes = cov->P_nodes ? d_Pn : nullptr; v.P_final = d_Pf; v.status = d_cst;
+    v.nx = nx;
+    e = launch_guidance_covariance(v, st);
+  }
+  timing_end(c, st);                             // the sweep's start to the gains' (and the covariance pass's) end
+  if (e != hipSuccess) return set_err(c, LTO_EHIP, cov ? "launch_guidance_gains / launch_guidance_covariance" : "launch_guidance_gains", e);
+  if (K) e = hipMemcpyAsync(K, d_K, sizeof(double) * nx * nx * S, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && pivot) e = hipMemcpyAsync(pivot, d_piv, sizeof(double) * S, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(status, d_status, sizeof(int) * B, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && cov) {
+    if (cov->Phi) e = stage_out(c, d_phi, (long)S, nd * nd, (long)S, d_phi_aos, cov->Phi, st);
+    if (e == hipSuccess && cov->P_nodes)
+      e = hipMemcpyAsync(cov->P_nodes, d_Pn, sizeof(double) * ne * nc * J, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(cov->P_final, d_Pf, sizeof(double) * ne * nc * B, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(cov->status, d_cst, sizeof(int) * nc * B, hipMemcpyDeviceToHost, st);
+  }
   if (e == hipSuccess) e = call.wait();
   if (e != hipSuccess) return fail(c, LTO_EHIP, who, "stage out", e);
   return LTO_OK;
@@ -243,6 +298,17 @@ int lto_guidance_gains_mass_batch(lto_ctx* c, int n_nodes, int n_batch, const do
 int lto_guidance_gains_mass(lto_ctx* c, int n_nodes, const double* XC, const double* t, const lto_params* prm,
                             const lto_integrator* integ, double sing_tol, double* K, double* pivot, int* status) {
   return lto_guidance_gains_mass_batch(c, n_nodes, 1, XC, t, 1, prm, 1, integ, sing_tol, K, pivot, status);
+}
+
+int lto_guidance_covariance_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC, const double* t, int n_tgrids,
+                                  const lto_params* prm, int n_prm, const lto_integrator* integ, double sing_tol, int n_cases,
+                                  const double* P0, const double* R, const int* update_every, double* K, double* pivot,
+                                  int* gain_status, double* Phi, double* P_nodes, double* P_final, int* cov_status) {
+  const char* who = "lto_guidance_covariance_batch";
+  if (!c) return LTO_ENULL;
+  if (ndim != 12 && ndim != 14) return fail(c, LTO_EUNSUPPORTED, who, "ndim must be 12 or 14");
+  const CovCall cov{n_cases, P0, R, update_every, Phi, P_nodes, P_final, cov_status};
+  return gains_batch(ndim, who, c, ndim, n_nodes, n_batch, XC, t, n_tgrids, prm, n_prm, integ, sing_tol, K, pivot, gain_status, &cov);
 }
 
 int lto_guided_flight_batch(lto_ctx* c, int ndim, int n_nodes, int n_batch, const double* XC_nom, const double* t, const double* K,

@@ -1657,6 +1657,105 @@ def dispersion_guided_mass(ctx, XC_all, t_TU, prm, n_samples, sigma_r_km, sigma_
     return out
 
 
+def covariance_diag(nx, sigma_r_km, sigma_v_ms, sigma_m_kg, DU, TU):
+    """The diagonal covariance [nx x nx] of per-axis position, velocity and (nx = 7) mass sigmas in the units of dispersion_starts
+    and guided_nav: km -> DU, m/s -> DU/TU, the mass row in kg as it is.  None counts as zero."""
+    d = np.zeros(nx)
+    d[0:3] = (0.0 if sigma_r_km is None else float(sigma_r_km)) / DU
+    d[3:6] = (0.0 if sigma_v_ms is None else float(sigma_v_ms)) / 1e3 * TU / DU
+    if nx == 7:
+        d[6] = 0.0 if sigma_m_kg is None else float(sigma_m_kg)
+    return np.diag(d * d)
+
+
+def covariance_sigmas(P, DU, TU):
+    """What covariance_guided reports of covariances P [nx x nx x ...] (nx = 6 or 7, DU and DU/TU units, the mass in kg): a dict of
+    sigma_r_km and sigma_v_ms (the trace RSS of the position and velocity blocks), sigma_r_max_km (the largest principal position
+    sigma) and, for nx = 7, sigma_m_kg, each of P's trailing shape; every root is sqrt(max(0, .)), NaN stays NaN."""
+    P = np.asarray(P, dtype=np.float64)
+    nx = P.shape[0]
+    if P.ndim < 2 or P.shape[1] != nx or nx not in (6, 7):
+        raise ValueError("P must be [6 x 6 x ...] or [7 x 7 x ...]")
+
+    def root(v):
+        return np.sqrt(np.where(np.isnan(v), np.nan, np.maximum(0.0, v)))
+    tr_r = P[0, 0] + P[1, 1] + P[2, 2]
+    tr_v = P[3, 3] + P[4, 4] + P[5, 5]
+    Prr = np.moveaxis(P[0:3, 0:3], (0, 1), (-2, -1))
+    Prr = 0.5 * (Prr + np.swapaxes(Prr, -1, -2))
+    ok = np.all(np.isfinite(Prr), axis=(-2, -1))
+    lam = np.full(Prr.shape[:-2], np.nan)
+    if np.any(ok):
+        lam[ok] = np.linalg.eigvalsh(Prr[ok])[..., -1]
+    out = dict(sigma_r_km=root(tr_r) * DU, sigma_v_ms=root(tr_v) * DU / TU * 1e3, sigma_r_max_km=root(lam) * DU)
+    if nx == 7:
+        out["sigma_m_kg"] = root(P[6, 6])
+    return out
+
+
+def _covariance_guided(nx, ctx, XC_all, t_TU, prm, sigma_r_km, sigma_v_ms, sigma_m_kg, n_guid, update_every, integ, nav_sigma_r_km,
+                       nav_sigma_v_ms, nav_sigma_m_kg, sing_tol):
+    XC = np.asarray(XC_all, dtype=np.float64)
+    if XC.ndim != 2 or XC.shape[0] != 2 * nx:
+        raise ValueError("XC_all must be [%d x n]" % (2 * nx))
+    t = np.asarray(t_TU, dtype=np.float64)
+    if t.shape != (XC.shape[1],):
+        raise ValueError("t_TU must hold one time per node")
+    p = prm if isinstance(prm, hotpath.LtoParams) else hotpath.make_params(*prm)
+    navs = [np.asarray(0.0 if v is None else v, dtype=np.float64) for v in (nav_sigma_r_km, nav_sigma_v_ms, nav_sigma_m_kg)]
+    ev = np.asarray(update_every)
+    if not np.issubdtype(ev.dtype, np.integer) or np.any(ev < 0):
+        raise ValueError("update_every must hold integers >= 0")
+    shape = np.broadcast_shapes(ev.shape, *[v.shape for v in navs])           # the case list: the settings broadcast together
+    ev_c = np.broadcast_to(ev, shape).reshape(-1)
+    nav_c = [np.broadcast_to(v, shape).reshape(-1) for v in navs]
+    nc = ev_c.shape[0]
+    P0 = np.repeat(covariance_diag(nx, sigma_r_km, sigma_v_ms, sigma_m_kg, p.DU, p.TU)[:, :, None], nc, axis=2)
+    R = np.stack([covariance_diag(nx, nav_c[0][i], nav_c[1][i], nav_c[2][i], p.DU, p.TU) for i in range(nc)], axis=2)
+    if n_guid is not None:
+        if int(n_guid) < 2:
+            raise ValueError("n_guid must be >= 2")
+        XC, t = (hotpath.densify if nx == 6 else hotpath.densify_mass)(XC, t, p, int(n_guid), integ, ctx)
+    c = hotpath.guidance_covariance(XC, t, p, P0, R, ev_c, integ, sing_tol, with_nodes=True, ctx=ctx)
+    n = XC.shape[1]
+    nodes = covariance_sigmas(c.P_nodes, p.DU, p.TU)                           # [n x n_cases]
+    out = dict(P_final=c.P_final.reshape((nx, nx) + shape), P_nodes=c.P_nodes.reshape((nx, nx, n) + shape),
+               cov_status=c.cov_status.reshape(shape), gain_status=c.gain_status, K=c.K, pivot=c.pivot, XC_guid=XC, t_guid=t,
+               update_every=np.broadcast_to(ev, shape).copy(), sigma_r_km=nodes["sigma_r_km"].reshape((n,) + shape),
+               sigma_v_ms=nodes["sigma_v_ms"].reshape((n,) + shape))
+    out["miss_r_km_rss"] = out["sigma_r_km"][-1]
+    out["miss_v_ms_rss"] = out["sigma_v_ms"][-1]
+    out["miss_r_km_max"] = nodes["sigma_r_max_km"].reshape((n,) + shape)[-1]
+    if nx == 7:
+        out["sigma_m_kg"] = nodes["sigma_m_kg"].reshape((n,) + shape)
+        out["sigma_mf_kg"] = out["sigma_m_kg"][-1]
+    return out
+
+
+def covariance_guided(ctx, XC_all, t_TU, prm, sigma_r_km, sigma_v_ms, n_guid=None, update_every=1, integ=None, nav_sigma_r_km=None,
+                      nav_sigma_v_ms=None, sing_tol=1e-10):
+    """Linear covariance of a 12-row solution flown with neighbouring-extremal feedback (hotpath.guidance_covariance):
+    the deterministic twin of dispersion_guided.  The start covariance is diagonal with sigma_r_km per position axis and sigma_v_ms
+    per velocity axis (the units of dispersion_starts), the navigation covariance likewise from nav_sigma_r_km / nav_sigma_v_ms
+    (guided_nav; None: no navigation error).  nav_sigma_* and update_every may be arrays that broadcast together into the case
+    list -- a whole table of settings costs one call.  n_guid resamples the solution as fly_guided does.  Returns a dict, every entry
+    with the broadcast shape of the cases behind its own axes: sigma_r_km and sigma_v_ms [n x ...] (the trace RSS at every node),
+    miss_r_km_rss and miss_v_ms_rss (the arrival node's), miss_r_km_max (the largest principal position sigma at arrival), P_final
+    [6 x 6 x ...], P_nodes [6 x 6 x n x ...], cov_status (0 ok, 2 not finite: the case has no finite gains or inputs), gain_status,
+    K, pivot, XC_guid, t_guid, update_every."""
+    return _covariance_guided(6, ctx, XC_all, t_TU, prm, sigma_r_km, sigma_v_ms, None, n_guid, update_every, integ, nav_sigma_r_km,
+                              nav_sigma_v_ms, None, sing_tol)
+
+
+def covariance_guided_mass(ctx, XC_all, t_TU, prm, sigma_r_km, sigma_v_ms, n_guid=None, update_every=1, integ=None,
+                           nav_sigma_r_km=None, nav_sigma_v_ms=None, sigma_m_kg=None, nav_sigma_m_kg=None, sing_tol=1e-10):
+    """covariance_guided for a solution of the 14-row variable-mass system, the twin of dispersion_guided_mass: sigma_m_kg is the
+    start mass's sigma and nav_sigma_m_kg the measured mass's (it broadcasts with the other case settings).  The dict gains
+    sigma_m_kg [n x ...] and sigma_mf_kg (the final mass's sigma); P_final is [7 x 7 x ...]."""
+    return _covariance_guided(7, ctx, XC_all, t_TU, prm, sigma_r_km, sigma_v_ms, sigma_m_kg, n_guid, update_every, integ,
+                              nav_sigma_r_km, nav_sigma_v_ms, nav_sigma_m_kg, sing_tol)
+
+
 def homotopy_solve(XC_all, t_TU, MU, DU, TU, mass, thrustLimit, rhos, p=1.0, maxIter=10, max_waves=12, ctx=None, verbose=True,
                    arcs=False):
     """Solve the whole smoothing ladder rho_0 > rho_1 > ... concurrently.  reduceFuel_indirect walks the

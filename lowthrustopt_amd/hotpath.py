@@ -858,6 +858,73 @@ def guided_flight_mass(XC_nom, t_TU, K, x0, params, update_every=1, nav=None, in
     return _guided_flight(7, XC_nom, t_TU, K, x0, params, update_every, nav, integ, with_nodes, ctx)
 
 
+GuidanceCovariance = collections.namedtuple("GuidanceCovariance", "P_final P_nodes cov_status K pivot gain_status Phi")
+
+
+def _covariance_cases(P0, R, update_every, nx):
+    """(P0 [nx x nx x n_cases], R likewise, update_every int32 [n_cases], single): the case list of guidance_covariance checked
+    before the library is touched; a single [nx x nx] P0 with a scalar update_every is one case."""
+    P, Rm = _f64(P0), _f64(R)
+    for name, A in (("P0", P), ("R", Rm)):
+        if A.ndim not in (2, 3) or A.shape[0] != nx or A.shape[1] != nx:
+            raise ValueError("%s must be [%d x %d] or [%d x %d x n_cases]" % (name, nx, nx, nx, nx))
+    if P.shape != Rm.shape:
+        raise ValueError("P0 and R must have the same shape")
+    ev = np.asarray(update_every)
+    if ev.ndim > 1 or not np.issubdtype(ev.dtype, np.integer):
+        raise ValueError("update_every must be an integer or a vector of integers")
+    single = P.ndim == 2 and ev.ndim == 0
+    P3 = np.asfortranarray(P.reshape(nx, nx, -1, order="F"))
+    R3 = np.asfortranarray(Rm.reshape(nx, nx, -1, order="F"))
+    ev = np.ascontiguousarray(ev.reshape(-1), dtype=np.int32)
+    n_cases = P3.shape[2]
+    if n_cases < 1 or ev.shape[0] != n_cases:
+        raise ValueError("update_every must hold one entry per case (%d)" % n_cases)
+    if np.any(ev < 0):
+        raise ValueError("update_every must be >= 0")
+    return P3, R3, ev, single
+
+
+def guidance_covariance(XC_all, t_TU, params, P0, R, update_every, integ=None, sing_tol=1e-10, with_nodes=False, with_phi=False,
+                        ctx=None):
+    """Linear covariance of the guided flight about 12-row or 14-row solutions (lto_guidance_covariance_batch):
+    XC_all [ndim x n] or [ndim x n x B], ndim 12 or 14 (nx = ndim / 2; 14 rows: params with Isp in the mass slot), t_TU [n] or
+    [n x B]; the cases P0, R [nx x nx x n_cases] and update_every [n_cases] (or one [nx x nx] pair with a scalar update_every) are
+    shared by all trajectories.  One call sweeps the STMs, builds the gains and runs the forward pass of every (trajectory, case).
+    Returns a GuidanceCovariance: P_final [nx x nx x n_cases x B], P_nodes [nx x nx x n x n_cases x B] (with_nodes, else None),
+    cov_status [n_cases x B] (0 ok, 2 not finite), K, pivot and gain_status as guidance_gains has them, Phi [ndim x ndim x (n-1) x B]
+    (with_phi, else None).  A single case drops the case axis, a single trajectory the batch axis."""
+    XC = _f64(XC_all)
+    if XC.ndim not in (2, 3) or XC.shape[0] not in (12, 14):
+        raise ValueError("XC_all must be [12 x n], [14 x n] or either with a trailing batch axis")
+    nx = XC.shape[0] // 2
+    P3, R3, ev, single = _covariance_cases(P0, R, update_every, nx)
+    prm, nprm = _params_array(params)
+    if nx == 7 and not all(prm[k].mass > 0.0 for k in range(nprm)):
+        raise ValueError("Isp (the mass slot of 14-row params) must be positive")
+    ctx, (ndim, n, B, batched), args = _indirect_args(XC, t_TU, params, integ, ctx)
+    if n < 2:
+        raise ValueError("XC_all must hold at least two nodes")
+    S, nc = n - 1, P3.shape[2]
+    K = np.zeros((nx, nx, S, B), order="F")
+    pivot = np.zeros((S, B), order="F")
+    gain_status = np.zeros(B, dtype=np.int32)
+    Phi = np.zeros((ndim, ndim, S, B), order="F") if with_phi else None
+    P_nodes = np.zeros((nx, nx, n, nc, B), order="F") if with_nodes else None
+    P_final = np.zeros((nx, nx, nc, B), order="F")
+    cov_status = np.zeros((nc, B), dtype=np.int32, order="F")
+    ctx.check(ctx.fn("guidance_covariance_batch")(*args, float(sing_tol), nc, _ptr(P3), _ptr(R3), _ptr(ev), _ptr(K), _ptr(pivot),
+                                                  _ptr(gain_status), _ptr(Phi), _ptr(P_nodes), _ptr(P_final), _ptr(cov_status)))
+    if single:
+        P_final, cov_status = P_final[:, :, 0], cov_status[0]
+        P_nodes = None if P_nodes is None else P_nodes[:, :, :, 0]
+    if not batched:
+        return GuidanceCovariance(P_final[..., 0], None if P_nodes is None else P_nodes[..., 0],
+                                  int(cov_status[0]) if single else cov_status[..., 0], K[:, :, :, 0], pivot[:, 0],
+                                  int(gain_status[0]), None if Phi is None else Phi[:, :, :, 0])
+    return GuidanceCovariance(P_final, P_nodes, cov_status, K, pivot, gain_status, Phi)
+
+
 def direct_defectCalc(X_all, u_all, t_TU, nsteps, MU, DU, TU, Isp, ctx=None):
     """defectCalc of multiShoot_CRTBP_direct (:66-109): returns (defect[nstate x (n-1)], errors[n-1])."""
     ctx = ctx or default_context()
