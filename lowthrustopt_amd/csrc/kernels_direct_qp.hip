@@ -642,15 +642,12 @@ __global__ void k_qp_free_box(QpArgs a, double* dV, double* pout, double* cost, 
 // face p1 = lo, p1 = hi, p2 = lo, p2 = hi, p3 = lo, p3 = hi (qp_box2 on the other two coordinates, in increasing order).  phi is
 // convex, so the smallest phi among them is the minimum, also when H is singular.  Ties: the smaller max(|p1|/0.1, |p2|/0.1,
 // |p3|/step) (the last term 0 when step = 0), then the earlier candidate.  p [n_batch][3].
+// phi(p1, p2, p3) = the free-end step's qp_phi(p1, p2) + the terms of p3, which are exactly 0 at p3 = 0: a trajectory whose tf is
+// pinned (step = 0) beside one whose tf moves reports the cost its free-end step reports, to the last bit.
 __device__ __forceinline__ double qp_phi3(const double (&G)[3], const double (&H)[3][3], const double phi0, const double (&p)[3]) {
-  double q = 0.0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    q += H[i][i] * p[i] * p[i];
-#pragma unroll
-    for (int j = i + 1; j < 3; ++j) q += 2.0 * H[i][j] * p[i] * p[j];
-  }
-  return phi0 + G[0] * p[0] + G[1] * p[1] + G[2] * p[2] + 0.5 * q;
+  const double H2[3] = {H[0][0], H[0][1], H[1][1]};
+  const double q3 = __builtin_fma(H[2][2] * p[2], p[2], __builtin_fma(2.0 * H[1][2] * p[1], p[2], 2.0 * H[0][2] * p[0] * p[2]));
+  return qp_phi(G, H2, phi0, p[0], p[1]) + __builtin_fma(G[2], p[2], 0.5 * q3);
 }
 template <int NS>
 __global__ __launch_bounds__(64) void k_qp_free_box3(QpArgsTf a, double* dV, double* pout, double* cost, double* singular, const double* part, int nblk) {
